@@ -33,17 +33,20 @@ class _Keys:
 
 
 def _keys():
-    os.makedirs(CACHE, exist_ok=True)
     pv, pp = os.path.join(CACHE, f"vm_k{K}_pub{N_PUB}.vk"), os.path.join(CACHE, f"vm_k{K}_pub{N_PUB}.params")
     if os.path.exists(pv) and os.path.exists(pp):
         return _Keys(open(pv, "rb").read(), open(pp, "rb").read())
     s = circuits.setup_vector_mul(K, N_PUB)
     vk, params = s.vk, s.params
     s.free()
-    for path, data in ((pv, vk), (pp, params)):
-        with open(path + ".tmp", "wb") as f:
-            f.write(data)
-        os.replace(path + ".tmp", path)
+    try:   # the cache only saves the keygen's time: a checkout that cannot be written to makes the keys every time
+        os.makedirs(CACHE, exist_ok=True)
+        for path, data in ((pv, vk), (pp, params)):
+            with open(path + ".tmp", "wb") as f:
+                f.write(data)
+            os.replace(path + ".tmp", path)
+    except OSError:
+        pass
     return _Keys(vk, params)
 
 

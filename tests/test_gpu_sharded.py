@@ -153,7 +153,8 @@ def test_config3_shard_size(big):
 def test_config2_exactly_1024_proofs_at_k14():
     """BASELINE.json config 2 as stated: a batch of 1024 distinct proofs at k = 14 on one GPU, bit-exact against the oracle —
     statuses, both accumulator points and the verdict (the oracle needs ~2 s for the 1024 proofs).  The proofs are the bench's own
-    (bench.load_or_make_proofs: cached under .bench_cache/, generated with the test prover if the cache is missing)."""
+    (bench.load_or_make_proofs: cached under .bench_cache/ or, in a read-only checkout, the user's temp directory; generated with
+    the test prover if no cache holds them)."""
     import sys, os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
