@@ -85,6 +85,23 @@ int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, u
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
 int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal);
+// the same over R arbitrary ranges of proofs (h2v_batch_recheck): d_ranges[2 r] = first, [2 r + 1] = count (first + count <= n);
+// d_out[(r * n_shared + j) * 8] = canonical( sum over the proofs p of range r of shared[j][p] )
+int fold_shared_ranges_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t n_shared, const uint32_t* d_ranges, uint32_t n_ranges, uint32_t* d_out);
+
+// The re-check of ranges of a finished launch (h2v_batch_recheck): resources of its own, grow-only, so that the launch's accumulators,
+// workspace and result block are never touched
+struct Recheck {
+    MsmWorkspace ws;
+    uint32_t cap_terms = 0, cap_problems = 0, cap_per_problem = 0;   // what ws was allocated for
+    uint32_t cap_ranges = 0, cap_fold = 0;                           // ranges per chunk the buffers below hold; folded scalars (words / 8)
+    uint32_t* ranges = nullptr;   // [cap_ranges][first, count]
+    uint32_t* fold = nullptr;     // [range][shared base][8]
+    G1J* acc = nullptr;           // [2 r] left, [2 r + 1] right
+    uint32_t* ok = nullptr;       // [cap_ranges]
+    uint8_t* out_bytes = nullptr; uint32_t* out_ident = nullptr;     // [cap_ranges][128]; [2 cap_ranges]
+    void release();
+};
 }  // namespace h2v
 
 struct h2v_batch {
@@ -103,6 +120,8 @@ struct h2v_batch {
     uint32_t groups = 1;              // independent accumulator batches inside this launch (h2v_batch_set_groups)
     const h2v::Fr* ext_mult = nullptr; const uint32_t* ext_idx = nullptr;   // multipliers gathered from a larger sequence (h2v_verify_batch_shapes)
     bool launched = false, with_pairing = false;
+    bool finished = false;            // the last launch has been finished (h2v_batch_finish*) and nothing was uploaded or launched since: h2v_batch_recheck may read it
+    std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
     // device buffers (sized for max_proofs with the plan of the first upload; re-allocated if a later plan needs more)
     uint8_t* proofs = nullptr; uint8_t* inst = nullptr; uint8_t* tail = nullptr;
     h2v::G1A* pts = nullptr; h2v::G1A* phi = nullptr;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)
@@ -118,6 +137,7 @@ struct h2v_batch {
     uint32_t* fold_failed = nullptr;  // [groups] failed proofs reported by the folded shards (h2v_batch_fold_check_enqueue)
     uint8_t* results = nullptr; uint8_t* results_host = nullptr; size_t results_bytes = 0;   // ok / fold_failed / out_ident / out_bytes / status live in `results`
     h2v::MsmWorkspace ws;
+    h2v::Recheck recheck;             // h2v_batch_recheck's own workspace and outputs
     h2v::MsmSplit split;              // how the last launch left its accumulators to the pairing (parts == 0: whole points in acc)
     bool acc_stale = false;           // a launch without a pairing left pieces only: acc / out_bytes are put together on demand (ensure_whole)
     bool tail_on_aux = false;         // the last launch's whole accumulators, their bytes and the result copy are still the auxiliary stream's business (close_enqueue): join_tail before the main stream touches them

@@ -9,6 +9,13 @@
 
 using namespace h2v;
 
+void h2v::Recheck::release() {
+    ws.release();
+    hipFree(ranges); hipFree(fold); hipFree(acc); hipFree(ok); hipFree(out_bytes); hipFree(out_ident);
+    ranges = nullptr; fold = nullptr; acc = nullptr; ok = nullptr; out_bytes = nullptr; out_ident = nullptr;
+    cap_terms = cap_problems = cap_per_problem = cap_ranges = cap_fold = 0;
+}
+
 namespace {
 
 template <class T> int dev_alloc(T*& p, size_t count) {
@@ -108,10 +115,21 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     if ((rc = ensure_buffers(b, pd))) return rc;
     if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
-    b->plan = pin.take(); b->n = (uint32_t)n; b->launched = false; b->decompressed = false;
+    b->plan = pin.take(); b->n = (uint32_t)n; b->launched = false; b->finished = false; b->decompressed = false;
     std::vector<uint8_t> os_rand;
     if (!rand_tail) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand_tail = os_rand.data(); n_tail = n; }
     for (size_t i = 0; i < n_tail; ++i) if (!scalar_is_canonical(rand_tail + 32 * i)) { set_last_error("h2v_batch_upload: rand32 scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
+    // a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs
+    b->zero_below.assign(b->groups, 0);
+    if (n) {
+        const size_t G = b->groups, gs = n / G, nt = n_tail / G;
+        for (size_t g = 0; g < G; ++g)
+            for (size_t j = nt; j-- > 1;) {
+                uint64_t w[4];
+                memcpy(w, rand_tail + 32 * (g * nt + j), 32);
+                if (!(w[0] | w[1] | w[2] | w[3])) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
+            }
+    }
     if (n_tail > b->cap_tail) { if ((rc = dev_alloc(b->tail, 32 * n_tail))) return rc; b->cap_tail = n_tail; }
     b->n_tail = (uint32_t)n_tail;
     hipStream_t s = b->stream;
@@ -203,6 +221,27 @@ int ensure_whole(h2v_batch* b);
 int export_batch_records(h2v_batch* b, void* device_dst);
 #define H2V_SPLIT_MAX_GROUPS 64u
 
+// The two MSM problems of the proofs [p0, p0 + count) of an uploaded batch: acc2[0] <- the left channel (SHPLONK: sum_p m_p * h2_p;
+// GWC: the witness points), acc2[1] <- the right channel = the proofs' pooled Guard terms + the VK-wide bases with the n_shared
+// folded scalars `shared_scal`.  Both index the batch's point array; unused slots have zero scalars and cost nothing.
+void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_t p0, uint32_t count, G1J* acc2, const uint32_t* shared_scal, uint32_t n_shared) {
+    const uint32_t np = pl.n_points;
+    const size_t first = p0 * np;
+    if (pl.left_term_order.size() == 1 && !pl.left_term_order[0].first) {
+        // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of `count` terms, not the
+        // count * np slots with `count` of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
+        const size_t at = first + pl.left_term_order[0].second;
+        pr.p.push_back(MsmProblem(b->left_scal + at * 8, b->pts + at, acc2, 8 * np, np, count));
+        pr.p.back().phi = b->phi + at;
+    } else {
+        pr.p.push_back(MsmProblem(b->left_scal + first * 8, b->pts + first, acc2, 8, 1, count * np));
+        pr.p.back().phi = b->phi + first;
+        pr.p.back().nnz = count * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
+    }
+    pr.p.push_back(MsmProblem(b->msm_scal + first * 8, b->pts + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts + (size_t)b->n * np, n_shared));
+    pr.p.back().phi = b->phi + first; pr.p.back().phi2 = b->phi + (size_t)b->n * np;
+}
+
 int launch_impl(h2v_batch* b, int with_pairing) {
     if (!b || !b->plan) { set_last_error("h2v_batch_launch: nothing uploaded"); return H2V_ERR_BAD_ARGUMENT; }
     h2v_ctx* ctx = b->ctx;
@@ -212,7 +251,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     hipStream_t s = b->stream;
     uint32_t n = b->n;
     const uint32_t G = b->groups, gs = n / G;
-    b->with_pairing = with_pairing != 0; b->launched = true;
+    b->with_pairing = with_pairing != 0; b->launched = true; b->finished = false;
     int rc;
     if ((rc = join_tail(b))) return rc;
     int ev = 0;
@@ -233,30 +272,11 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     b->decompressed = false;   // (a later h2v_batch_launch on the same upload runs the stage again: every launch does all of its work)
     mark();
     if ((rc = transcript_stage_enqueue(s, g))) return rc;
-    // both channels of every group in one set of launches: [2g] left (SHPLONK: sum_p m_p * h2_p; GWC: the witness points),
-    // [2g+1] right = the group's pooled Guard terms + its folded VK-wide bases.  Both index the same point array; unused
-    // slots have zero scalars and cost nothing.  The descriptors are addresses and sizes: they go to the device on the auxiliary stream, beside the decompression (msm_prepare_problems below).
+    // both channels of every group in one set of launches: [2g] left, [2g+1] right (channel_problems), the group's folded VK-wide
+    // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: they go to the device on the auxiliary stream, beside the decompression (msm_prepare_problems below).
     MsmProblems pr;
-    {
-        const uint32_t np = pl.n_points;
-        for (uint32_t g = 0; g < G; ++g) {
-            const size_t first = (size_t)g * gs * np;
-            if (pl.left_term_order.size() == 1 && !pl.left_term_order[0].first) {
-                // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of gs terms, not the
-                // group's gs * np slots with gs of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
-                const size_t at = first + pl.left_term_order[0].second;
-                pr.p.push_back(MsmProblem(b->left_scal + at * 8, b->pts + at, b->acc + 2 * g, 8 * np, np, gs));
-                pr.p.back().phi = b->phi + at;
-            } else {
-                pr.p.push_back(MsmProblem(b->left_scal + first * 8, b->pts + first, b->acc + 2 * g, 8, 1, gs * np));
-                pr.p.back().phi = b->phi + first;
-                pr.p.back().nnz = gs * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
-            }
-            pr.p.push_back(MsmProblem(b->msm_scal + first * 8, b->pts + first, b->acc + 2 * g + 1, 8, 1, gs * np,
-                                      b->msm_scal + ((size_t)n * np + (size_t)g * pl.n_shared) * 8, b->pts + (size_t)n * np, n ? pl.n_shared : 0));
-            pr.p.back().phi = b->phi + first; pr.p.back().phi2 = b->phi + (size_t)n * np;
-        }
-    }
+    for (uint32_t g = 0; g < G; ++g)
+        channel_problems(pr, b, pl, (size_t)g * gs, gs, b->acc + 2 * g, b->msm_scal + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
     b->ws.tune = ctx->tuning;
     // the batch multipliers depend only on the uploaded draws: they run on the auxiliary stream beside decompression and transcript
     if (n) {
@@ -421,6 +441,91 @@ int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out
         if (out_left) memcpy(out_left + 64 * (size_t)g, &outb[128 * (size_t)g], 64);
         if (out_right) memcpy(out_right + 64 * (size_t)g, &outb[128 * (size_t)g + 64], 64);
     }
+    b->finished = true;
+    return 0;
+}
+// the verdict of group g's own pairing check in the last finished launch (finish_impl folds the statuses into group_ok; this is the pairing alone)
+bool pairing_passed(const h2v_batch* b, uint32_t g) { return b->with_pairing && reinterpret_cast<const uint32_t*>(b->results_host)[g] != 0; }
+
+// Range re-checks (h2v_batch_recheck).  A range [first, first + count) of group g is checked as the launch checks the whole group:
+// e(sum_p m_p L_p, s_g2) e(sum_p m_p R_p, -g2) = 1 over its proofs' resident scalars (already multiplied by m_p, zeroed for failed
+// proofs) — the range's own fold of the VK-wide scalars, two MSMs, one pairing.  Nothing before the MSM runs again, and nothing the
+// launch left (ws, acc, split, the result block) is touched: the re-check has its own workspace and outputs (b->recheck).
+// At most MSM_MAX_PROBLEMS / 2 ranges, and about the launch's own term count, go into one set of launches.
+int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
+    if (!b || (n_ranges && (!first || !count || !range_ok))) { set_last_error("h2v_batch_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!b->finished || !b->plan) { set_last_error("h2v_batch_recheck: no finished launch to re-check"); return H2V_ERR_BAD_ARGUMENT; }
+    const Plan& pl = b->plan->host;
+    const uint32_t n = b->n, G = b->groups, gs = n / G, np = pl.n_points, ns = pl.n_shared;
+    for (size_t i = 0; i < n_ranges; ++i) {
+        const size_t f = first[i], c = count[i];
+        if (!c || f >= n || c > n - f) { set_last_error("h2v_batch_recheck: empty range, or a range past the launch's proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        const size_t g = f / gs;
+        // multipliers are products of the later draws of the proof's OWN group: the last proof of every group has multiplier 1, and a range
+        // over two groups could hold two proofs with equal multipliers whose errors cancel
+        if ((f + c - 1) / gs != g) { set_last_error("h2v_batch_recheck: a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
+        if (f - g * gs < b->zero_below[g]) { set_last_error("h2v_batch_recheck: a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    if (!n_ranges) return 0;
+    h2v_ctx* ctx = b->ctx;
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = join_tail(b))) return rc;
+    hipStream_t s = b->stream;
+    Recheck& rk = b->recheck;
+    const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;
+    if (!rk.cap_ranges) {
+        if ((rc = dev_alloc(rk.ranges, 2 * (size_t)max_ranges)) || (rc = dev_alloc(rk.acc, 2 * (size_t)max_ranges)) || (rc = dev_alloc(rk.ok, (size_t)max_ranges)) ||
+            (rc = dev_alloc(rk.out_bytes, 128 * (size_t)max_ranges)) || (rc = dev_alloc(rk.out_ident, 2 * (size_t)max_ranges))) return rc;
+        rk.cap_ranges = max_ranges;
+    }
+    if ((size_t)ns * max_ranges > rk.cap_fold) { if ((rc = dev_alloc(rk.fold, 8 * (size_t)ns * max_ranges))) return rc; rk.cap_fold = ns * max_ranges; }
+    const bool strided = pl.left_term_order.size() == 1 && !pl.left_term_order[0].first;
+    auto terms_of = [&](size_t c) { return (strided ? c : c * np) + c * np + ns; };
+    const size_t budget = 2 * ((size_t)n * np + (size_t)max_ranges * ns);   // > terms_of(n): every range fits in a chunk of its own
+    std::vector<uint32_t> desc;
+    std::vector<uint32_t> okv;
+    std::vector<uint8_t> outb;
+    for (size_t i0 = 0; i0 < n_ranges;) {
+        size_t i1 = i0, total = 0;
+        uint32_t per = 0;
+        while (i1 < n_ranges && i1 - i0 < max_ranges && (i1 == i0 || total + terms_of(count[i1]) <= budget)) {
+            total += terms_of(count[i1]);
+            per = std::max(per, (uint32_t)(count[i1] * np + ns));
+            ++i1;
+        }
+        const uint32_t R = (uint32_t)(i1 - i0);
+        if (total > rk.cap_terms || 2 * R > rk.cap_problems || per > rk.cap_per_problem) {
+            hipStreamSynchronize(s);   // (an earlier chunk may still use the workspace)
+            const uint32_t t = std::max<uint32_t>(rk.cap_terms, (uint32_t)total), q = std::max(rk.cap_problems, 2 * R), m = std::max(rk.cap_per_problem, per);
+            if ((rc = rk.ws.alloc(t, q, m))) { rk.cap_terms = rk.cap_problems = rk.cap_per_problem = 0; return rc; }
+            rk.cap_terms = t; rk.cap_problems = q; rk.cap_per_problem = m;
+        }
+        desc.resize(2 * (size_t)R);
+        for (uint32_t r = 0; r < R; ++r) { desc[2 * r] = (uint32_t)first[i0 + r]; desc[2 * r + 1] = (uint32_t)count[i0 + r]; }
+        H2V_HIP_CHECK(hipMemcpyAsync(rk.ranges, desc.data(), 8 * (size_t)R, hipMemcpyHostToDevice, s));
+        if ((rc = fold_shared_ranges_enqueue(s, b->shared, n, ns, rk.ranges, R, rk.fold))) return rc;
+        MsmProblems pr;
+        for (uint32_t r = 0; r < R; ++r) channel_problems(pr, b, pl, first[i0 + r], (uint32_t)count[i0 + r], rk.acc + 2 * r, rk.fold + (size_t)r * ns * 8, ns);
+        rk.ws.tune = ctx->tuning; rk.ws.profile = false;
+        if ((rc = msm_enqueue_multi(s, rk.ws, pr))) return rc;
+        if ((rc = pairing_check_enqueue(s, ctx->pairing, rk.acc, R, rk.ok))) return rc;
+        okv.resize(R);
+        H2V_HIP_CHECK(hipMemcpyAsync(okv.data(), rk.ok, 4 * (size_t)R, hipMemcpyDeviceToHost, s));
+        if (out_left || out_right) {
+            if ((rc = point_to_bytes_enqueue(s, rk.acc, rk.out_bytes, rk.out_ident, 2 * R))) return rc;
+            outb.resize(128 * (size_t)R);
+            H2V_HIP_CHECK(hipMemcpyAsync(outb.data(), rk.out_bytes, outb.size(), hipMemcpyDeviceToHost, s));
+        }
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_last_error(std::string("h2v_batch_recheck: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+        for (uint32_t r = 0; r < R; ++r) {
+            range_ok[i0 + r] = okv[r] ? 1 : 0;
+            if (out_left) memcpy(out_left + 64 * (i0 + r), &outb[128 * (size_t)r], 64);
+            if (out_right) memcpy(out_right + 64 * (i0 + r), &outb[128 * (size_t)r + 64], 64);
+        }
+        i0 = i1;
+    }
     return 0;
 }
 
@@ -522,6 +627,56 @@ int pack_and_run(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const siz
     return rc;
 }
 
+// The search of h2v_verify_batch_identify, measured at 1024 proofs (tools/identify_probe.py): every failing range is cut into
+// H2V_IDENTIFY_FANOUT pieces per round — or straight into single proofs once the failing ranges hold at most H2V_IDENTIFY_DIRECT
+// proofs together, one set of re-check launches (MSM_MAX_PROBLEMS / 2 checks).  A round is a latency chain up to ~128 checks (32 ranges
+// of 32 proofs: 1.9 ms, 128 single proofs: 2.0 ms, 512: 4.1 ms), so rounds are what to save: one bad proof in 1024 takes two (32 + 32 checks).
+#define H2V_IDENTIFY_FANOUT 32
+#define H2V_IDENTIFY_DIRECT 512
+
+// the pairing's verdict of a failed batch of one group, proof by proof: st[i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof whose own
+// check fails (st[i] == 0 on entry).  A range whose check fails holds at least one failing proof (the check of a range is the product of its
+// pieces' checks), so every round ends with at least one failing piece per failing range.
+int identify_search(h2v_batch* b, std::vector<int>& st, size_t* n_checks) {
+    const size_t n = st.size();
+    // proofs with a non-zero status contribute nothing: a range is trimmed to its first and last live proof, and one without a live proof passes
+    auto trim = [&](size_t a, size_t c, std::vector<std::pair<size_t, size_t>>& out) {
+        size_t e = a + c;
+        while (a < e && st[a]) ++a;
+        while (e > a && st[e - 1]) --e;
+        if (e > a) out.push_back({a, e - a});
+    };
+    std::vector<std::pair<size_t, size_t>> failing, pieces;
+    trim(0, n, failing);
+    int rc = 0;
+    while (!failing.empty()) {
+        pieces.clear();
+        size_t total = 0;
+        for (auto& r : failing) total += r.second;
+        for (auto& r : failing) {
+            if (r.second == 1) { st[r.first] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE; continue; }   // (its check already was that proof's own)
+            const size_t k = total <= H2V_IDENTIFY_DIRECT ? r.second : std::min<size_t>(H2V_IDENTIFY_FANOUT, r.second);
+            for (size_t i = 0; i < k; ++i) {
+                const size_t a = r.first + r.second * i / k, e = r.first + r.second * (i + 1) / k;
+                trim(a, e - a, pieces);
+            }
+        }
+        if (pieces.empty()) break;
+        std::vector<size_t> f(pieces.size()), c(pieces.size());
+        std::vector<int> ok(pieces.size(), 0);
+        for (size_t i = 0; i < pieces.size(); ++i) { f[i] = pieces[i].first; c[i] = pieces[i].second; }
+        if ((rc = recheck_impl(b, pieces.size(), f.data(), c.data(), ok.data(), nullptr, nullptr))) return rc;
+        *n_checks += pieces.size();
+        failing.clear();
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            if (ok[i]) continue;
+            if (c[i] == 1) st[f[i]] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;
+            else failing.push_back(pieces[i]);
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -579,6 +734,7 @@ void h2v_batch_destroy(h2v_batch* b) {
     hipFree(b->line_ws);
     if (b->results_host) hipHostFree(b->results_host);
     b->ws.release();
+    b->recheck.release();
     for (int i = 0; i < 8; ++i) if (b->ev[i]) hipEventDestroy(b->ev[i]);
     if (b->aux) { hipStreamSynchronize(b->aux); hipStreamDestroy(b->aux); }
     if (b->copy) { hipStreamSynchronize(b->copy); hipStreamDestroy(b->copy); }
@@ -611,7 +767,7 @@ int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    b->groups = (uint32_t)groups; b->launched = false;  // the next upload re-sizes the workspace
+    b->groups = (uint32_t)groups; b->launched = false; b->finished = false;  // the next upload re-sizes the workspace
     return 0;
 }
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups) {
@@ -840,6 +996,43 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     int ok = 0;
     if ((rc = fold_check_locked(ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
     if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
+    return 0;
+}
+
+int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+    return recheck_impl(b, n_ranges, first, count, range_ok, out_left_xy, out_right_xy);
+}
+
+int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
+                              const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64],
+                              size_t* n_range_checks) {
+    if (n_range_checks) *n_range_checks = 0;
+    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    // a single proof's check equals SingleStrategy's only when its multiplier is non-zero: no draw may be zero
+    std::vector<uint8_t> os_rand;
+    int rc;
+    if (!rand32 && n) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand32 = os_rand.data(); }
+    auto is_zero = [](const uint8_t* r) { for (int k = 0; k < 32; ++k) if (r[k]) return false; return true; };
+    for (size_t i = 0; i < n; ++i) {
+        if (!is_zero(rand32 + 32 * i)) continue;
+        if (os_rand.empty()) { set_last_error("h2v_verify_batch_identify: a draw in rand32 is zero"); return H2V_ERR_BAD_ARGUMENT; }
+        std::vector<uint8_t> one;
+        do { if ((rc = os_random_scalars(one, 1))) return rc; } while (is_zero(one.data()));   // (an OS draw of zero: probability 2^-254)
+        memcpy(&os_rand[32 * i], one.data(), 32);
+    }
+    std::vector<int> st(n ? n : 1, 0);
+    int ok = 0;
+    h2v_batch* b = nullptr;
+    if ((rc = pack_and_run(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, false, 1, st.data(), &ok, out_left_xy, out_right_xy, &b))) return rc;
+    st.resize(n);
+    std::lock_guard<std::mutex> lock(ctx->mu);   // the kept batch is the context's scratch batch until it is given back
+    size_t checks = 0;
+    if (n && !pairing_passed(b, 0)) rc = identify_search(b, st, &checks);
+    if (rc) { h2v_batch_destroy(b); return rc; }
+    scratch_batch_give(ctx, b);
+    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
+    if (batch_ok) *batch_ok = ok;
+    if (n_range_checks) *n_range_checks = checks;
     return 0;
 }
 

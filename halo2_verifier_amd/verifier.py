@@ -281,6 +281,29 @@ class Context:
             check(self._lib.h2v_verify_batch_shapes(self._h, n, pa, pl, ia, ncols, cl, rb, st, ctypes.byref(ok), left, right))
         return bool(ok.value), list(st)[:n], left.raw, right.raw
 
+    def verify_batch_identify(self, proofs, instances, rand=None):
+        """verify_batch plus the proofs that made it fail (h2v_verify_batch_identify).  Returns (batch_ok, statuses, left_xy, right_xy):
+        batch_ok / left_xy / right_xy are what verify_batch returns for the same arguments, statuses[i] is what verify_each returns for
+        proof i.  rand: n non-zero scalars or None.  One instance shape per call.  The number of range checks the search ran is kept in
+        self.last_range_checks."""
+        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(self, proofs, instances)
+        if not all(l == shapes[0] for l in shapes):
+            raise ValueError("verify_batch_identify takes one instance shape per call")
+        rb = None
+        if rand is not None:
+            if len(rand) != n:
+                raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
+            rb = b"".join(_scalar32(r) for r in rand)
+        lens = shapes[0] if shapes else [0] * ncols
+        cl = (ctypes.c_size_t * max(ncols, 1))(*lens)
+        st = (ctypes.c_int * max(n, 1))()
+        ok = ctypes.c_int(0)
+        left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+        checks = ctypes.c_size_t(0)
+        check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, cl, rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
+        self.last_range_checks = checks.value
+        return bool(ok.value), list(st)[:n], left.raw, right.raw
+
     def verify_each(self, proofs, instances):
         n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(self, proofs, instances)
         st = (ctypes.c_int * max(n, 1))()
@@ -540,6 +563,23 @@ class Batch:
         lr, rr = left.raw, right.raw
         statuses = bytes(memoryview(st).cast('B')[:4 * self.n]) if raw_statuses else memoryview(st).cast('B').cast('i').tolist()[:self.n]
         return ([bool(v) for v in ok], statuses, [lr[64 * i:64 * i + 64] for i in range(g)], [rr[64 * i:64 * i + 64] for i in range(g)])
+
+    def recheck(self, ranges):
+        """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
+        ranges: list of (first, count), each inside one group of the launch.  -> (oks, lefts, rights): one verdict and the two
+        evaluated channels (64-byte x | y) per range."""
+        ranges = [(int(f), int(c)) for f, c in ranges]
+        for f, c in ranges:   # (size_t on the C side: a negative value would wrap around; the library checks the rest)
+            if f < 0 or c < 0:
+                raise ValueError(f"range ({f}, {c}): first and count must be non-negative")
+        k = len(ranges)
+        first = (ctypes.c_size_t * max(k, 1))(*[f for f, _ in ranges])
+        count = (ctypes.c_size_t * max(k, 1))(*[c for _, c in ranges])
+        ok = (ctypes.c_int * max(k, 1))()
+        left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
+        check(self._lib.h2v_batch_recheck(self._h, k, first, count, ok, left, right))
+        lr, rr = left.raw, right.raw
+        return [bool(v) for v in ok][:k], [lr[64 * i:64 * i + 64] for i in range(k)], [rr[64 * i:64 * i + 64] for i in range(k)]
 
     PROFILE_KERNEL = 3   # H2V_PROFILE_KERNEL: the dominant kernel's own timestamps only
 

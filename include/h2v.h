@@ -217,6 +217,21 @@ int h2v_verify_each(h2v_ctx* ctx, size_t n,
                     const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
                     int* per_proof_status);
 
+/* Which proofs made a batch fail: h2v_verify_batch, plus the proofs that fail the pairing.  batch_ok / out_left_xy / out_right_xy
+ * are exactly what h2v_verify_batch returns for the same arguments; per_proof_status[i] is what h2v_verify_each returns for proof i
+ * (0, the instance / transcript / opening errors, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE).  When the batch's pairing passes this costs
+ * what h2v_verify_batch costs; otherwise the failing ranges of proofs are re-checked on the batch's resident scalars
+ * (h2v_batch_recheck) and cut until single proofs remain.  A proof flagged H2V_ERR_CONSTRAINT_SYSTEM_FAILURE always fails
+ * SingleStrategy; a failing proof escapes only with the probability AccumulatorStrategy itself allows (<= n / r).
+ * rand32 must hold no zero scalar (H2V_ERR_BAD_ARGUMENT); NULL = draw from the OS RNG.
+ * n_range_checks (may be NULL): how many range checks the search ran (0 when the batch passes). */
+int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n,
+                              const uint8_t* const* proofs, const size_t* proof_lens,
+                              const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
+                              const uint8_t* rand32,
+                              int* per_proof_status, int* batch_ok,
+                              uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks);
+
 /* Debug / parity: the Guard of one proof term by term in the order the reference appends them (shplonk.rs:256-264;
  * gwc.rs:86-132: witness_with_aux, commitment_multi query by query — a commitment opened at several points occurs once per
  * query, each time with that query's own scalar — then (eval_multi, -g)), and the
@@ -270,6 +285,15 @@ int h2v_batch_finish(h2v_batch* b, int* per_proof_status, int* batch_ok, uint8_t
 int h2v_batch_set_groups(h2v_batch* b, size_t groups);
 /* As h2v_batch_finish for a grouped batch: group_ok[n_groups], out_left_xy / out_right_xy = n_groups x 64 bytes. */
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups);
+/* Pairing checks of ranges of the last FINISHED launch of b (h2v_batch_finish / _finish_groups), on its resident per-proof Guard
+ * scalars: no stage before the MSM runs again.  Range i = proofs [first[i], first[i] + count[i]); count > 0; every range inside one
+ * group of the launch (else H2V_ERR_BAD_ARGUMENT: the last proof of every group has multiplier 1, so a range over two groups could
+ * pair up equal multipliers); ranges may overlap.  range_ok[i] = the check of sum over the range of (multiplier_p * Guard_p), proofs
+ * with a non-zero status contributing nothing; out_left_xy / out_right_xy (n_ranges x 64 bytes each, may be NULL) the two evaluated
+ * channels per range.  A range over a proof whose multiplier is zero (a zero draw behind it in its group) is H2V_ERR_BAD_ARGUMENT: its
+ * check would say nothing about that proof.  The launch's own results, and later uploads and launches, are unaffected.  Synchronous. */
+int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count,
+                      int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
 /* Device address of this batch's accumulator points after launch: per group [left, right], 2 x 108 bytes each, Jacobian
  * (X, Y, Z) in the library's Montgomery limb layout (debug / inspection; the record a sharded run exchanges is written by
  * h2v_batch_export_accumulators). */

@@ -155,6 +155,25 @@ public:
         statuses_.resize(items_.size());
         return ok != 0;
     }
+    // finalize() plus the proofs that made the batch fail (h2v_verify_batch_identify): returns what finalize() returns, and statuses()
+    // then holds, for every proof, the plonk::Error SingleStrategy reports for it — ConstraintSystemFailure for the proofs whose own
+    // pairing fails.  The draws must be non-zero.  One instance shape, no seed.
+    bool finalize_identify() {
+        if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes an accumulation without a seed");
+        Context ctx(params_, vk_, device_, mo_, tr_, ci_);
+        size_t ncols = 0;
+        check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
+        detail::Packed pk(items_, ncols);
+        if (!pk.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes one instance shape");
+        if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
+        statuses_.assign(items_.size() ? items_.size() : 1, 0);
+        int ok = 0;
+        check(h2v_verify_batch_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
+                                        rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_, &range_checks_));
+        statuses_.resize(items_.size());
+        return ok != 0;
+    }
+    size_t range_checks() const { return range_checks_; }   // re-checks the last finalize_identify() ran (0: the batch passed)
     const std::vector<int>& statuses() const { return statuses_; }
     const uint8_t* left() const { return left_; }     // evaluated channels of the final DualMSM, canonical x|y
     const uint8_t* right() const { return right_; }
@@ -166,8 +185,23 @@ private:
     bool seeded_ = false;
     Bytes seed_ls_, seed_lb_, seed_rs_, seed_rb_;
     std::vector<int> statuses_;
+    size_t range_checks_ = 0;
     uint8_t left_[64] = {0}, right_[64] = {0};
 };
+
+// The pairing checks of ranges (first, count) of a batch's last finished launch on its resident scalars (h2v_batch_recheck): one verdict
+// per range; lefts / rights (optional) receive the evaluated channels, 64 bytes per range.
+struct RangeChecks { std::vector<bool> ok; Bytes lefts, rights; };
+inline RangeChecks recheck(h2v_batch* b, const std::vector<std::pair<size_t, size_t>>& ranges) {
+    std::vector<size_t> first, count;
+    for (const auto& r : ranges) { first.push_back(r.first); count.push_back(r.second); }
+    std::vector<int> ok(ranges.size() ? ranges.size() : 1, 0);
+    RangeChecks out;
+    out.lefts.assign(64 * ranges.size(), 0); out.rights.assign(64 * ranges.size(), 0);
+    check(h2v_batch_recheck(b, ranges.size(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
+    for (size_t i = 0; i < ranges.size(); ++i) out.ok.push_back(ok[i] != 0);
+    return out;
+}
 
 // kzg/strategy.rs:143-181: one pairing per proof, checked inside verify_proof
 class SingleStrategy {
