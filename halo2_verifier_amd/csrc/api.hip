@@ -99,11 +99,9 @@ void h2v_ctx_destroy(h2v_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->scratch_batch) { h2v_batch_destroy(ctx->scratch_batch); ctx->scratch_batch = nullptr; }
-    ctx->pairing.release();
-    ctx->msm_ws.release();
     ctx_release_vk(ctx);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // (frees the pairing tables and the MSM workspace)
 }
 
 int h2v_msm_g1(h2v_ctx* ctx, const uint8_t* scalars32, const uint8_t* bases64, size_t n, uint8_t out_xy[64], int* out_is_identity) {
@@ -117,14 +115,10 @@ int h2v_msm_g1(h2v_ctx* ctx, const uint8_t* scalars32, const uint8_t* bases64, s
     // staging buffers and the Pippenger workspace are kept in the context and only grow (seven hipMalloc / hipFree pairs per
     // call before); they are owned by the context, so no return path below can leak them
     OneShotMsm& w = ctx->one_shot;
-    if (nn > w.cap || !w.res.p) {
-        const size_t cap = nn < 1024 ? 1024 : nn;
-        w.cap = 0;
-        if ((rc = w.sb.alloc(32 * cap)) || (rc = w.bb.alloc(64 * cap)) || (rc = w.s.alloc(8 * cap)) || (rc = w.b.alloc(cap)) || (rc = w.flags.alloc(2 * cap + 2)) ||
-            (rc = w.res.alloc(1)) || (rc = w.out.alloc(64))) return rc;
-        if ((rc = ctx->msm_ws.alloc((uint32_t)cap, 1))) return rc;
-        w.cap = (uint32_t)cap;
-    }
+    const size_t cap = nn < 1024 ? 1024 : nn;
+    if ((rc = w.sb.reserve(32 * cap)) || (rc = w.bb.reserve(64 * cap)) || (rc = w.s.reserve(8 * cap)) || (rc = w.b.reserve(cap)) || (rc = w.flags.reserve(2 * cap + 2)) ||
+        (rc = w.res.reserve(1)) || (rc = w.out.reserve(64))) return rc;
+    if ((rc = ctx->msm_ws.reserve((uint32_t)cap, 1))) return rc;
     std::vector<uint32_t> flags(2 * n + 1);
     if (n) {
         H2V_HIP_CHECK(hipMemcpyAsync(w.sb.p, scalars32, 32 * n, hipMemcpyHostToDevice, s));

@@ -93,14 +93,25 @@ int fold_shared_ranges_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, ui
 // workspace and result block are never touched
 struct Recheck {
     MsmWorkspace ws;
-    uint32_t cap_terms = 0, cap_problems = 0, cap_per_problem = 0;   // what ws was allocated for
-    uint32_t cap_ranges = 0, cap_fold = 0;                           // ranges per chunk the buffers below hold; folded scalars (words / 8)
-    uint32_t* ranges = nullptr;   // [cap_ranges][first, count]
-    uint32_t* fold = nullptr;     // [range][shared base][8]
-    G1J* acc = nullptr;           // [2 r] left, [2 r + 1] right
-    uint32_t* ok = nullptr;       // [cap_ranges]
-    uint8_t* out_bytes = nullptr; uint32_t* out_ident = nullptr;     // [cap_ranges][128]; [2 cap_ranges]
-    void release();
+    DevBuf<uint32_t> ranges;      // [range][first, count]
+    DevBuf<uint32_t> fold;        // [range][shared base][8]
+    DevBuf<G1J> acc;              // [2 r] left, [2 r + 1] right
+    DevBuf<uint32_t> ok;          // [range]
+    DevBuf<uint8_t> out_bytes; DevBuf<uint32_t> out_ident;     // [range][128]; [2 range]
+};
+
+// The block of everything h2v_batch_finish reads back, in bytes, for G groups and n proofs: [ok G][fold_failed G][out_ident 2 G]
+// [out_bytes 128 G][status n] (words, words, words, bytes, words).  One device block and one pinned host block share it: one copy
+// per launch (four separate copies into pageable memory were ~0.13 ms of a 20-step launch).  The device block keeps the place of `ok`,
+// unused: the verdicts are written into the host block, and the offsets of the two blocks agree.
+struct ResultsLayout {
+    size_t G, n;
+    size_t ok() const { return 0; }
+    size_t fold_failed() const { return 4 * G; }
+    size_t out_ident() const { return 8 * G; }
+    size_t out_bytes() const { return 16 * G; }
+    size_t status() const { return 144 * G; }
+    size_t total() const { return 144 * G + 4 * n; }
 };
 }  // namespace h2v
 
@@ -122,27 +133,28 @@ struct h2v_batch {
     bool launched = false, with_pairing = false;
     bool finished = false;            // the last launch has been finished (h2v_batch_finish*) and nothing was uploaded or launched since: h2v_batch_recheck may read it
     std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
-    // device buffers (sized for max_proofs with the plan of the first upload; re-allocated if a later plan needs more)
-    uint8_t* proofs = nullptr; uint8_t* inst = nullptr; uint8_t* tail = nullptr;
-    h2v::G1A* pts = nullptr; h2v::G1A* phi = nullptr;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)
-    uint8_t* ycanon = nullptr; int* status = nullptr;
-    unsigned long long* words = nullptr; h2v::Fr* chal = nullptr; h2v::Fr* mult = nullptr; h2v::Fr* slots = nullptr;
-    uint32_t* msm_scal = nullptr; h2v::Fr* shared = nullptr; uint32_t* left_scal = nullptr;
-    h2v::Fr* insteval = nullptr;  // [query][proof] (wide instance vectors)
-    uint32_t* guard_scal = nullptr;   // [proof][guard term][8] (h2v_guard_msm with GWC)
+    // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
+    h2v::DevBuf<uint8_t> proofs, inst, tail;
+    h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)
+    h2v::DevBuf<uint8_t> ycanon;
+    h2v::DevBuf<unsigned long long> words; h2v::DevBuf<h2v::Fr> chal, mult, slots;
+    h2v::DevBuf<uint32_t> msm_scal; h2v::DevBuf<h2v::Fr> shared; h2v::DevBuf<uint32_t> left_scal;
+    h2v::DevBuf<h2v::Fr> insteval;    // [query][proof] (wide instance vectors)
+    h2v::DevBuf<uint32_t> guard_scal; // [proof][guard term][8] (h2v_guard_msm with GWC)
     bool want_guard = false;          // the next upload takes the guard variant of the plan
-    h2v::G1J* acc = nullptr;      // per group: [2g] left, [2g+1] right
-    uint32_t* ok = nullptr;       // [groups] — in the pinned host block (results_host): the pairing kernels write their verdicts straight to the host
+    h2v::DevBuf<h2v::G1J> acc;        // per group: [2g] left, [2g+1] right
+    // the results block (h2v::ResultsLayout) on the device and in pinned host memory; the pointers below point into it for the upload's group count
+    h2v::DevBuf<uint8_t> results; h2v::MappedHostBuf results_host;
+    uint32_t* ok = nullptr;           // [groups] — in the host block: the pairing kernels write their verdicts straight to the host
     uint8_t* out_bytes = nullptr; uint32_t* out_ident = nullptr;
     uint32_t* fold_failed = nullptr;  // [groups] failed proofs reported by the folded shards (h2v_batch_fold_check_enqueue)
-    uint8_t* results = nullptr; uint8_t* results_host = nullptr; size_t results_bytes = 0;   // ok / fold_failed / out_ident / out_bytes / status live in `results`
+    int* status = nullptr;
     h2v::MsmWorkspace ws;
     h2v::Recheck recheck;             // h2v_batch_recheck's own workspace and outputs
     h2v::MsmSplit split;              // how the last launch left its accumulators to the pairing (parts == 0: whole points in acc)
     bool acc_stale = false;           // a launch without a pairing left pieces only: acc / out_bytes are put together on demand (ensure_whole)
     bool tail_on_aux = false;         // the last launch's whole accumulators, their bytes and the result copy are still the auxiliary stream's business (close_enqueue): join_tail before the main stream touches them
-    void* line_ws = nullptr; size_t line_ws_groups = 0;   // k_pair_lines' output, H2V_PAIRING_LINE_WS_BYTES per group
-    size_t cap_proof_bytes = 0, cap_inst_bytes = 0, cap_tail = 0, cap_plan_sig = 0;
+    h2v::DevBuf<uint8_t> line_ws;     // k_pair_lines' output, H2V_PAIRING_LINE_WS_BYTES per group
     uint32_t stream_words = 0;
     // profiling
     int profiling = 0;                // 0 off, 1: the dominant kernel's own events (msm_accumulate), 2: + an event between the stages

@@ -9,63 +9,62 @@
 
 using namespace h2v;
 
-void h2v::Recheck::release() {
-    ws.release();
-    hipFree(ranges); hipFree(fold); hipFree(acc); hipFree(ok); hipFree(out_bytes); hipFree(out_ident);
-    ranges = nullptr; fold = nullptr; acc = nullptr; ok = nullptr; out_bytes = nullptr; out_ident = nullptr;
-    cap_terms = cap_problems = cap_per_problem = cap_ranges = cap_fold = 0;
-}
-
 namespace {
 
-template <class T> int dev_alloc(T*& p, size_t count) {
-    if (p) { hipFree(p); p = nullptr; }
-    H2V_HIP_CHECK(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-    return 0;
+// Element counts of a batch's buffers for a plan, max_proofs N and G groups.  The batch keeps the largest it has met (ensure_buffers).
+struct BatchSizes {
+    uint32_t stream_words;   // the absorbed stream of one proof, in 64-bit words
+    size_t proofs, inst, pts, ycanon, words, chal, mult, slots, msm_scal, shared, left_scal, insteval, guard_scal, acc, results;
+    uint32_t ws_terms, ws_problems, ws_per_problem;   // MsmWorkspace::reserve
+};
+BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G) {
+    BatchSizes z;
+    const uint32_t words = (uint32_t)((pl.stream.size() + 7) / 8);
+    const uint32_t blockw = pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256 ? 17 : 16;   // 136-byte Keccak / 128-byte Blake2b blocks
+    z.stream_words = (words + blockw) / blockw * blockw;  // whole blocks, plus room for a final partial one
+    z.proofs = N * pl.proof_len;
+    z.inst = N * (size_t)pl.n_instance_values * 32;
+    z.pts = N * pl.n_points + pl.n_shared;
+    z.ycanon = N * pl.n_points * 32;
+    z.words = (size_t)z.stream_words * N;
+    z.chal = (size_t)pl.squeeze_at.size() * N;
+    z.mult = N;
+    z.slots = (size_t)std::max(std::max(pl.n_slots, pl.n_slots_k[0]), std::max(pl.n_slots_k[1], pl.n_slots_k[2])) * N;
+    z.msm_scal = (N * pl.n_points + G * pl.n_shared) * 8;
+    z.shared = (size_t)pl.n_shared * N;
+    z.left_scal = N * pl.n_points * 8;
+    z.insteval = N * pl.inst_queries.size();
+    z.guard_scal = N * pl.guard_term_order.size() * 8;
+    z.acc = 2 * G;
+    z.results = ResultsLayout{G, N}.total();
+    z.ws_terms = (uint32_t)(2 * (N * pl.n_points + G * pl.n_shared));
+    z.ws_problems = (uint32_t)(2 * G);
+    z.ws_per_problem = (uint32_t)((N + G - 1) / G * pl.n_points + pl.n_shared);
+    return z;
 }
 
-// (re)allocate the per-batch device workspace for a given plan
-int ensure_buffers(h2v_batch* b, PlanDevice* pd) {
-    const Plan& pl = pd->host;
-    size_t N = b->max_proofs, G = b->groups;
-    size_t sig = pl.guard_term_order.size() * 977u + G * 7919u + pl.inst_queries.size() * 31u + (size_t)pl.opts.transcript * 77u + (size_t)pl.opts.multiopen * 131u + (size_t)pl.n_points * 1000003u + (size_t)pl.n_slots * 10007u + ((size_t)pl.n_slots_k[0] + pl.n_slots_k[1] + pl.n_slots_k[2]) * 1009u + pl.n_shared * 101u + pl.stream.size() + pl.proof_len * 7u + pl.n_instance_values * 13u + pl.n_challenges;
-    if (b->cap_plan_sig == sig && b->pts) return 0;
+// grow the batch's buffers to what `pl` needs at the batch's capacity and group count, and point ok / fold_failed / out_ident /
+// out_bytes / status into the results block laid out for that group count
+int ensure_buffers(h2v_batch* b, const Plan& pl) {
+    const size_t N = b->max_proofs, G = b->groups;
+    const BatchSizes z = batch_sizes(pl, N, G);
     int rc;
-    uint32_t words = (uint32_t)((pl.stream.size() + 7) / 8);
-    const uint32_t blockw = pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256 ? 17 : 16;   // 136-byte Keccak / 128-byte Blake2b blocks
-    words = (words + blockw) / blockw * blockw;  // whole blocks, plus room for a final partial one
-    b->stream_words = words;
-    if ((rc = dev_alloc(b->proofs, N * pl.proof_len))) return rc;
-    if ((rc = dev_alloc(b->inst, N * (size_t)pl.n_instance_values * 32))) return rc;
-    if ((rc = dev_alloc(b->pts, N * pl.n_points + pl.n_shared))) return rc;
-    if ((rc = dev_alloc(b->phi, N * pl.n_points + pl.n_shared))) return rc;
-    if ((rc = dev_alloc(b->ycanon, N * pl.n_points * 32))) return rc;
-    if ((rc = dev_alloc(b->words, (size_t)words * N))) return rc;
-    if ((rc = dev_alloc(b->chal, (size_t)pl.squeeze_at.size() * N))) return rc;
-    if ((rc = dev_alloc(b->mult, N))) return rc;
-    if ((rc = dev_alloc(b->slots, (size_t)std::max(std::max(pl.n_slots, pl.n_slots_k[0]), std::max(pl.n_slots_k[1], pl.n_slots_k[2])) * N))) return rc;
-    if ((rc = dev_alloc(b->msm_scal, (N * pl.n_points + G * pl.n_shared) * 8))) return rc;
-    if ((rc = dev_alloc(b->shared, (size_t)pl.n_shared * N))) return rc;
-    if ((rc = dev_alloc(b->left_scal, N * pl.n_points * 8))) return rc;
-    if ((rc = dev_alloc(b->insteval, N * pl.inst_queries.size()))) return rc;
-    if ((rc = dev_alloc(b->guard_scal, N * pl.guard_term_order.size() * 8))) return rc;
-    if ((rc = dev_alloc(b->acc, 2 * G))) return rc;
-    // everything h2v_batch_finish reads back sits in ONE block, mirrored by one pinned host buffer: a single copy per launch (four
-    // separate copies into pageable memory were ~0.13 ms of a 20-step launch): [ok G][fold_failed G][out_ident 2 G][out_bytes 128 G][status N]
-    // (the device block keeps the place of `ok`, unused: the offsets of the two blocks agree)
-    b->results_bytes = 144 * G + 4 * N;
-    if ((rc = dev_alloc(b->results, b->results_bytes))) return rc;
-    if (b->results_host) { hipHostFree(b->results_host); b->results_host = nullptr; }
-    H2V_HIP_CHECK(hipHostMalloc((void**)&b->results_host, b->results_bytes ? b->results_bytes : 1, hipHostMallocMapped));
+    if ((rc = b->proofs.reserve(z.proofs)) || (rc = b->inst.reserve(z.inst)) || (rc = b->pts.reserve(z.pts)) || (rc = b->phi.reserve(z.pts)) ||
+        (rc = b->ycanon.reserve(z.ycanon)) || (rc = b->words.reserve(z.words)) || (rc = b->chal.reserve(z.chal)) || (rc = b->mult.reserve(z.mult)) ||
+        (rc = b->slots.reserve(z.slots)) || (rc = b->msm_scal.reserve(z.msm_scal)) || (rc = b->shared.reserve(z.shared)) ||
+        (rc = b->left_scal.reserve(z.left_scal)) || (rc = b->insteval.reserve(z.insteval)) || (rc = b->guard_scal.reserve(z.guard_scal)) ||
+        (rc = b->acc.reserve(z.acc)) || (rc = b->results.reserve(z.results)) || (rc = b->results_host.reserve(z.results)))
+        return rc;
     // the verdicts are the LAST thing a launch produces: the pairing kernel writes them into the host block itself (one word per group over
     // PCIe) and no copy follows it; everything else in the block is final before the pairing starts and is copied beside it (close_enqueue)
-    { void* dp = nullptr; H2V_HIP_CHECK(hipHostGetDevicePointer(&dp, b->results_host, 0)); b->ok = reinterpret_cast<uint32_t*>(dp); }
-    b->fold_failed = reinterpret_cast<uint32_t*>(b->results) + G;
-    b->out_ident = reinterpret_cast<uint32_t*>(b->results) + 2 * G;
-    b->out_bytes = b->results + 16 * G;
-    b->status = reinterpret_cast<int*>(b->results + 144 * G);
-    if ((rc = b->ws.alloc((uint32_t)(2 * (N * pl.n_points + G * pl.n_shared)), (uint32_t)(2 * G), (uint32_t)((N + G - 1) / G * pl.n_points + pl.n_shared)))) return rc;
-    b->cap_plan_sig = sig;
+    const ResultsLayout L{G, N};
+    b->ok = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b->results_host.dev) + L.ok());
+    b->fold_failed = reinterpret_cast<uint32_t*>(b->results.p + L.fold_failed());
+    b->out_ident = reinterpret_cast<uint32_t*>(b->results.p + L.out_ident());
+    b->out_bytes = b->results.p + L.out_bytes();
+    b->status = reinterpret_cast<int*>(b->results.p + L.status());
+    if ((rc = b->ws.reserve(z.ws_terms, z.ws_problems, z.ws_per_problem))) return rc;
+    b->stream_words = z.stream_words;
     return 0;
 }
 
@@ -113,7 +112,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     if (rand_tail && n_tail < n) { set_last_error("h2v_batch_upload: n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->groups > 1 && (n % b->groups || (rand_tail && n_tail % b->groups))) { set_last_error("h2v_batch_upload: n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = ensure_buffers(b, pd))) return rc;
+    if ((rc = ensure_buffers(b, pl))) return rc;
     if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
     b->plan = pin.take(); b->n = (uint32_t)n; b->launched = false; b->finished = false; b->decompressed = false;
     std::vector<uint8_t> os_rand;
@@ -130,21 +129,21 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
                 if (!(w[0] | w[1] | w[2] | w[3])) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
             }
     }
-    if (n_tail > b->cap_tail) { if ((rc = dev_alloc(b->tail, 32 * n_tail))) return rc; b->cap_tail = n_tail; }
+    if ((rc = b->tail.reserve(32 * n_tail))) return rc;
     b->n_tail = (uint32_t)n_tail;
     hipStream_t s = b->stream;
     if (!n) { H2V_HIP_CHECK(hipStreamSynchronize(s)); return 0; }
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
-        if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
-        else H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs + p0 * pl.proof_len, pl.proof_len, proofs_flat + p0 * proof_len, proof_len, pl.proof_len, p1 - p0, hipMemcpyHostToDevice, cs));
+        if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs.p + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
+        else H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + p0 * pl.proof_len, pl.proof_len, proofs_flat + p0 * proof_len, proof_len, pl.proof_len, p1 - p0, hipMemcpyHostToDevice, cs));
         return 0;
     };
     auto copy_rest = [&](hipStream_t cs) -> int {
-        if (pl.n_instance_values) H2V_HIP_CHECK(hipMemcpyAsync(b->inst, instances_flat, n * (size_t)pl.n_instance_values * 32, hipMemcpyHostToDevice, cs));
-        H2V_HIP_CHECK(hipMemcpyAsync(b->tail, rand_tail, 32 * n_tail, hipMemcpyHostToDevice, cs));
+        if (pl.n_instance_values) H2V_HIP_CHECK(hipMemcpyAsync(b->inst.p, instances_flat, n * (size_t)pl.n_instance_values * 32, hipMemcpyHostToDevice, cs));
+        H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, rand_tail, 32 * n_tail, hipMemcpyHostToDevice, cs));
         // VK-wide bases sit behind the batch's own points so that one MSM covers both
-        H2V_HIP_CHECK(hipMemcpyAsync(b->pts + n * (size_t)pl.n_points, pd->shared_bases, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
-        H2V_HIP_CHECK(hipMemcpyAsync(b->phi + n * (size_t)pl.n_points, pd->shared_phi, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
+        H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
+        H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
         return 0;
     };
     if (!overlap) {
@@ -190,7 +189,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         // the proofs in two halves: [first half] -> its decompression is enqueued -> [second half, instances, draws] travel while the GPU
         // decompresses the first -> the second half's decompression.  Two rounds of the decompression kernel at half occupancy take about
         // what one round at full occupancy takes, and the second copy hides behind the first round.
-        StageArgs g{(uint32_t)n, &pl, pd, b->proofs, b->inst, b->pts, b->phi, b->ycanon, b->status, b->words, b->stream_words, b->chal};
+        StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
         if ((rc = decompress_begin_enqueue(s, g))) return rc;
         const size_t half = (n / 2 + 15) / 16 * 16;
         if ((rc = copy_proofs(b->copy, 0, half))) return rc;
@@ -203,9 +202,9 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         b->decompressed = true;
         return 0;
     }
-    for (auto& r : runs) H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs + r.first, pl.proof_len, proofs_flat + r.first, proof_len, r.second, n, hipMemcpyHostToDevice, b->copy));
+    for (auto& r : runs) H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + r.first, pl.proof_len, proofs_flat + r.first, proof_len, r.second, n, hipMemcpyHostToDevice, b->copy));
     H2V_HIP_CHECK(hipStreamSynchronize(b->copy));
-    StageArgs g{(uint32_t)n, &pl, pd, b->proofs, b->inst, b->pts, b->phi, b->ycanon, b->status, b->words, b->stream_words, b->chal};
+    StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
     if ((rc = decompress_begin_enqueue(s, g))) return rc;
     if ((rc = decompress_range_enqueue(s, g, 0, (uint32_t)n))) return rc;
     // (the whole proofs again, point bytes included: identical bytes over the ones the kernel is reading)
@@ -231,15 +230,15 @@ void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_
         // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of `count` terms, not the
         // count * np slots with `count` of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
         const size_t at = first + pl.left_term_order[0].second;
-        pr.p.push_back(MsmProblem(b->left_scal + at * 8, b->pts + at, acc2, 8 * np, np, count));
-        pr.p.back().phi = b->phi + at;
+        pr.p.push_back(MsmProblem(b->left_scal.p + at * 8, b->pts.p + at, acc2, 8 * np, np, count));
+        pr.p.back().phi = b->phi.p + at;
     } else {
-        pr.p.push_back(MsmProblem(b->left_scal + first * 8, b->pts + first, acc2, 8, 1, count * np));
-        pr.p.back().phi = b->phi + first;
+        pr.p.push_back(MsmProblem(b->left_scal.p + first * 8, b->pts.p + first, acc2, 8, 1, count * np));
+        pr.p.back().phi = b->phi.p + first;
         pr.p.back().nnz = count * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
     }
-    pr.p.push_back(MsmProblem(b->msm_scal + first * 8, b->pts + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts + (size_t)b->n * np, n_shared));
-    pr.p.back().phi = b->phi + first; pr.p.back().phi2 = b->phi + (size_t)b->n * np;
+    pr.p.push_back(MsmProblem(b->msm_scal.p + first * 8, b->pts.p + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts.p + (size_t)b->n * np, n_shared));
+    pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
 }
 
 int launch_impl(h2v_batch* b, int with_pairing) {
@@ -257,7 +256,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     int ev = 0;
     auto mark = [&]() { if (b->profiling >= 2) hipEventRecord(b->ev[ev], s); ++ev; };   // (an event record is a barrier packet: ~6 us of idle stream each)
     mark();
-    StageArgs g{n, &pl, pd, b->proofs, b->inst, b->pts, b->phi, b->ycanon, b->status, b->words, b->stream_words, b->chal};
+    StageArgs g{n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
     // stage 1: point decompression + canonicity checks (already on the stream, behind its chunked upload, after h2v_batch_upload_launch);
     // stage 2: absorbed stream, Blake2b challenges, batch multipliers.  The status words are cleared first, then the auxiliary stream is
     // forked: the scalar canonicity check (proof bytes only) runs there beside the decompression, with the multipliers
@@ -265,8 +264,9 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     // cleared per launch: fold_failed (set by h2v_batch_fold_check_enqueue only) and — unless the upload already did (h2v_batch_upload_launch) —
     // the status words.  The results block is [ok][fold_failed][out_ident][out_bytes][status]: one fill from fold_failed to the last status word
     // (the output bytes in between are written later in the launch) instead of two
-    if (run_decompress && n) H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, (size_t)((uint8_t*)(b->status + n) - (uint8_t*)b->fold_failed), s));
-    else H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, 4 * (size_t)G, s));
+    const ResultsLayout L{G, n};
+    if (run_decompress && n) H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, L.total() - L.fold_failed(), s));
+    else H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, 4 * (size_t)G, s));   // (its G words)
     H2V_HIP_CHECK(hipEventRecord(b->ev_fork0, s));   // everything enqueued before this point (uploads, the cleared status words) is visible to the auxiliary stream
     if (run_decompress && (rc = decompress_range_enqueue(s, g, 0, n))) return rc;
     b->decompressed = false;   // (a later h2v_batch_launch on the same upload runs the stage again: every launch does all of its work)
@@ -276,7 +276,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: they go to the device on the auxiliary stream, beside the decompression (msm_prepare_problems below).
     MsmProblems pr;
     for (uint32_t g = 0; g < G; ++g)
-        channel_problems(pr, b, pl, (size_t)g * gs, gs, b->acc + 2 * g, b->msm_scal + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
+        channel_problems(pr, b, pl, (size_t)g * gs, gs, b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
     b->ws.tune = ctx->tuning;
     // the batch multipliers depend only on the uploaded draws: they run on the auxiliary stream beside decompression and transcript
     if (n) {
@@ -285,32 +285,32 @@ int launch_impl(h2v_batch* b, int with_pairing) {
         if (run_decompress && (rc = decompress_finish_enqueue(sm, g))) return rc;   // k_check_scalars
         // multipliers: suffix products of the uploaded draws — or, for a batch that is a non-contiguous subset of a larger
         // accumulation (h2v_verify_batch_shapes), gathered from the multipliers of the whole sequence
-        if (b->ext_mult) { if ((rc = gather_multipliers_enqueue(sm, b->ext_mult, b->ext_idx, n, b->mult))) return rc; }
-        else if ((rc = multipliers_enqueue(sm, b->tail, b->n_tail, n, G, b->mult))) return rc;
+        if (b->ext_mult) { if ((rc = gather_multipliers_enqueue(sm, b->ext_mult, b->ext_idx, n, b->mult.p))) return rc; }
+        else if ((rc = multipliers_enqueue(sm, b->tail.p, b->n_tail, n, G, b->mult.p))) return rc;
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
-        if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal, 0, (size_t)n * pl.n_points * 32, sm));
+        if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, sm));
         if ((rc = msm_prepare_problems(sm, b->ws, pr))) return rc;   // (5 us of launch + kernel boundary that the main stream's chain no longer carries)
         H2V_HIP_CHECK(hipEventRecord(b->ev_join0, sm));
         H2V_HIP_CHECK(hipStreamWaitEvent(s, b->ev_join0, 0));   // joined before the Fr program reads them
     }
     mark();
-    FrvmArgs a{pd->code, (uint32_t)pl.code.size(), pd->consts, b->slots, n, b->proofs, pl.proof_len, pd->scalar_offsets, b->inst, pl.n_instance_values,
-               b->chal, b->mult, b->status, b->msm_scal, pl.n_points, b->shared, b->left_scal, b->insteval, b->guard_scal, (uint32_t)pl.guard_term_order.size()};
+    FrvmArgs a{pd->code.p, (uint32_t)pl.code.size(), pd->consts.p, b->slots.p, n, b->proofs.p, pl.proof_len, pd->scalar_offsets.p, b->inst.p, pl.n_instance_values,
+               b->chal.p, b->mult.p, b->status, b->msm_scal.p, pl.n_points, b->shared.p, b->left_scal.p, b->insteval.p, b->guard_scal.p, (uint32_t)pl.guard_term_order.size()};
     if (n && pl.wide_instances) {
         Fr step = pl.omega;
         for (int i = 0; i < 8; ++i) step = step.sqr();   // omega^256: a thread's stride through the column
         const Fr step_inv = step.inv();
         for (size_t q = 0; q < pl.inst_queries.size(); ++q) {
-            InstEvalArgs ia{b->inst, pl.n_instance_values, b->chal, pl.x_chal, n, pl.domain_k, pl.inst_queries[q].base, pl.inst_queries[q].len,
-                            pl.inst_queries[q].w_start, pl.omega, step, step_inv, pl.n_inv, b->insteval + q * (size_t)n, b->status};
+            InstEvalArgs ia{b->inst.p, pl.n_instance_values, b->chal.p, pl.x_chal, n, pl.domain_k, pl.inst_queries[q].base, pl.inst_queries[q].len,
+                            pl.inst_queries[q].w_start, pl.omega, step, step_inv, pl.n_inv, b->insteval.p + q * (size_t)n, b->status};
             if ((rc = instance_eval_enqueue(s, ia))) return rc;
         }
     }
     a.force_streams = ctx->tuning.frvm_streams; a.force_lds_kb = ctx->tuning.frvm_lds_kb;
-    for (int k = 0; k < 3; ++k) { for (int q = 0; q < k + 2; ++q) { a.code_k[k][q] = pd->code_k[k][q]; a.n_code_k[k][q] = (uint32_t)pl.code_k[k][q].size(); } a.n_slots_k[k] = pl.n_slots_k[k]; }
+    for (int k = 0; k < 3; ++k) { for (int q = 0; q < k + 2; ++q) { a.code_k[k][q] = pd->code_k[k][q].p; a.n_code_k[k][q] = (uint32_t)pl.code_k[k][q].size(); } a.n_slots_k[k] = pl.n_slots_k[k]; }
     if ((rc = frvm_enqueue(s, a, pl.n_slots))) return rc;
     mark();
-    if (n) { if ((rc = fold_shared_enqueue(s, b->shared, n, pl.n_points, pl.n_shared, G, b->msm_scal))) return rc; }
+    if (n) { if ((rc = fold_shared_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->msm_scal.p))) return rc; }
     mark();
     {
         b->ws.profile = b->profiling >= 1; b->ws.profile_recorded = false;
@@ -321,11 +321,9 @@ int launch_impl(h2v_batch* b, int with_pairing) {
         const uint32_t parts_knob = ctx->tuning.msm_parts > 0 ? (uint32_t)ctx->tuning.msm_parts : MSM_MAX_PARTS;   // h2v_tuning.msm_parts
         b->ws.tune = ctx->tuning;
         if (n && G <= H2V_SPLIT_MAX_GROUPS && parts_knob > 1) {
-            if (b->line_ws_groups < G) {
-                if (b->line_ws) { hipStreamSynchronize(s); hipFree(b->line_ws); b->line_ws = nullptr; b->line_ws_groups = 0; }
-                H2V_HIP_CHECK(hipMalloc(&b->line_ws, (size_t)G * H2V_PAIRING_LINE_WS_BYTES));
-                b->line_ws_groups = G;
-            }
+            const size_t line_bytes = (size_t)G * H2V_PAIRING_LINE_WS_BYTES;
+            if (b->line_ws.p && line_bytes > b->line_ws.cap) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (an earlier launch's pairing may still read it)
+            if ((rc = b->line_ws.reserve(line_bytes))) return rc;
             b->split.want_parts = parts_knob;
         }
         if ((rc = msm_enqueue_multi(s, b->ws, pr, b->split.want_parts > 1 ? &b->split : nullptr))) return rc;
@@ -347,22 +345,24 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
     b->acc_stale = false;
     if (!with_pairing) {
         if (b->split.parts) { b->acc_stale = true; return 0; }   // pieces only for now
-        return point_to_bytes_enqueue(s, b->acc, b->out_bytes, b->out_ident, 2 * G);
+        return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
     }
     H2V_HIP_CHECK(hipEventRecord(b->ev_fork, s));
     H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork, 0));
     // (beside the pairing: kept off the pairing workgroups' CUs by an LDS request, internal.h)
     if (b->split.parts && (rc = msm_combine_enqueue(b->aux, b->ws, b->split, H2V_AUX_LDS_RESERVE))) return rc;   // acc <- the whole points
-    if ((rc = point_to_bytes_enqueue(b->aux, b->acc, b->out_bytes, b->out_ident, 2 * G, H2V_AUX_LDS_RESERVE))) return rc;
+    if ((rc = point_to_bytes_enqueue(b->aux, b->acc.p, b->out_bytes, b->out_ident, 2 * G, H2V_AUX_LDS_RESERVE))) return rc;
     // the result block (all but the verdicts, which the pairing kernel writes to the host itself) goes back on the auxiliary stream too, and the
     // main stream does NOT wait for it: its last operation is the pairing kernel — the join (a barrier packet) and the copy behind it were
     // 16 us at the end of every launch.  h2v_batch_finish waits for both streams; anything else that touches the batch first calls join_tail.
     // (by a kernel, not hipMemcpyAsync: a copy enqueued now, behind kernels that end a launch later, can hold up an SDMA queue — util.hip)
-    if ((rc = copy_words_enqueue(b->aux, b->results + 4 * (size_t)G, b->ok + G, 35 * (size_t)G + (size_t)b->n, H2V_AUX_LDS_RESERVE))) return rc;
+    const ResultsLayout L{G, b->n};
+    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), static_cast<uint8_t*>(b->results_host.dev) + L.fold_failed(), (L.total() - L.fold_failed()) / 4,
+                                 H2V_AUX_LDS_RESERVE))) return rc;
     H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
     b->tail_on_aux = true;
-    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
-    else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc, G, b->ok))) return rc;
+    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
+    else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc.p, G, b->ok))) return rc;
     return 0;
 }
 // the main stream waits for what the last launch left on the auxiliary stream (before anything new reads or overwrites it)
@@ -377,7 +377,7 @@ int ensure_whole(h2v_batch* b) {
     if (!b->acc_stale) return 0;
     int rc;
     if ((rc = msm_combine_enqueue(b->stream, b->ws, b->split))) return rc;
-    if ((rc = point_to_bytes_enqueue(b->stream, b->acc, b->out_bytes, b->out_ident, 2 * b->groups))) return rc;
+    if ((rc = point_to_bytes_enqueue(b->stream, b->acc.p, b->out_bytes, b->out_ident, 2 * b->groups))) return rc;
     b->acc_stale = false;
     return 0;
 }
@@ -385,7 +385,7 @@ int ensure_whole(h2v_batch* b) {
 int export_batch_records(h2v_batch* b, void* device_dst) {
     { int rcj = join_tail(b); if (rcj) return rcj; }
     if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
-    return export_records_enqueue(b->stream, b->acc, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
+    return export_records_enqueue(b->stream, b->acc.p, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
 }
 
 // group_ok / out_left / out_right hold one entry (64 bytes) per group
@@ -395,6 +395,7 @@ int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out
     hipStream_t s = b->stream;
     const uint32_t n = b->n, G = b->groups, gs = n / G;
     { int rcw = ensure_whole(b); if (rcw) return rcw; }
+    const ResultsLayout L{G, n};
     hipError_t e;
     if (b->tail_on_aux) {
         // a launch that ended in its own pairing checks: the block is on its way on the auxiliary stream, the verdicts come from the kernel
@@ -402,15 +403,15 @@ int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out
         e = hipStreamSynchronize(s);
         if (e == hipSuccess) e = hipStreamSynchronize(b->aux);   // (not hipEventSynchronize on its last event: that wait goes through the runtime's event thread, and a host that re-uploads per launch lost 40 % to it)
     } else {
-        const size_t nbytes = 144 * (size_t)G + 4 * (size_t)n;
-        H2V_HIP_CHECK(hipMemcpyAsync(b->results_host + 4 * (size_t)G, b->results + 4 * (size_t)G, nbytes - 4 * (size_t)G, hipMemcpyDeviceToHost, s));
+        H2V_HIP_CHECK(hipMemcpyAsync(b->results_host.p + L.fold_failed(), b->results.p + L.fold_failed(), L.total() - L.fold_failed(), hipMemcpyDeviceToHost, s));
         e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) { set_last_error(std::string("h2v_batch_finish: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
-    const uint32_t* okv = reinterpret_cast<const uint32_t*>(b->results_host);
-    const uint32_t* foldf = okv + G;
-    const uint8_t* outb = b->results_host + 16 * (size_t)G;
-    const int* st = reinterpret_cast<const int*>(b->results_host + 144 * (size_t)G);
+    const uint8_t* host = b->results_host.p;
+    const uint32_t* okv = reinterpret_cast<const uint32_t*>(host + L.ok());
+    const uint32_t* foldf = reinterpret_cast<const uint32_t*>(host + L.fold_failed());
+    const uint8_t* outb = host + L.out_bytes();
+    const int* st = reinterpret_cast<const int*>(host + L.status());
     for (int i = 0; i < 7; ++i) b->last_ms[i] = 0;
     if (b->profiling >= 2) {
         // events: 0 start, 1 after decompression, 2 after transcript + multipliers, 3 after Fr program, 4 after fold, 5 after MSMs, 6 after pairing
@@ -445,7 +446,9 @@ int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out
     return 0;
 }
 // the verdict of group g's own pairing check in the last finished launch (finish_impl folds the statuses into group_ok; this is the pairing alone)
-bool pairing_passed(const h2v_batch* b, uint32_t g) { return b->with_pairing && reinterpret_cast<const uint32_t*>(b->results_host)[g] != 0; }
+bool pairing_passed(const h2v_batch* b, uint32_t g) {
+    return b->with_pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
+}
 
 // Range re-checks (h2v_batch_recheck).  A range [first, first + count) of group g is checked as the launch checks the whole group:
 // e(sum_p m_p L_p, s_g2) e(sum_p m_p R_p, -g2) = 1 over its proofs' resident scalars (already multiplied by m_p, zeroed for failed
@@ -474,12 +477,8 @@ int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_
     hipStream_t s = b->stream;
     Recheck& rk = b->recheck;
     const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;
-    if (!rk.cap_ranges) {
-        if ((rc = dev_alloc(rk.ranges, 2 * (size_t)max_ranges)) || (rc = dev_alloc(rk.acc, 2 * (size_t)max_ranges)) || (rc = dev_alloc(rk.ok, (size_t)max_ranges)) ||
-            (rc = dev_alloc(rk.out_bytes, 128 * (size_t)max_ranges)) || (rc = dev_alloc(rk.out_ident, 2 * (size_t)max_ranges))) return rc;
-        rk.cap_ranges = max_ranges;
-    }
-    if ((size_t)ns * max_ranges > rk.cap_fold) { if ((rc = dev_alloc(rk.fold, 8 * (size_t)ns * max_ranges))) return rc; rk.cap_fold = ns * max_ranges; }
+    if ((rc = rk.ranges.reserve(2 * (size_t)max_ranges)) || (rc = rk.acc.reserve(2 * (size_t)max_ranges)) || (rc = rk.ok.reserve(max_ranges)) ||
+        (rc = rk.out_bytes.reserve(128 * (size_t)max_ranges)) || (rc = rk.out_ident.reserve(2 * (size_t)max_ranges)) || (rc = rk.fold.reserve(8 * (size_t)ns * max_ranges))) return rc;
     const bool strided = pl.left_term_order.size() == 1 && !pl.left_term_order[0].first;
     auto terms_of = [&](size_t c) { return (strided ? c : c * np) + c * np + ns; };
     const size_t budget = 2 * ((size_t)n * np + (size_t)max_ranges * ns);   // > terms_of(n): every range fits in a chunk of its own
@@ -495,27 +494,23 @@ int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_
             ++i1;
         }
         const uint32_t R = (uint32_t)(i1 - i0);
-        if (total > rk.cap_terms || 2 * R > rk.cap_problems || per > rk.cap_per_problem) {
-            hipStreamSynchronize(s);   // (an earlier chunk may still use the workspace)
-            const uint32_t t = std::max<uint32_t>(rk.cap_terms, (uint32_t)total), q = std::max(rk.cap_problems, 2 * R), m = std::max(rk.cap_per_problem, per);
-            if ((rc = rk.ws.alloc(t, q, m))) { rk.cap_terms = rk.cap_problems = rk.cap_per_problem = 0; return rc; }
-            rk.cap_terms = t; rk.cap_problems = q; rk.cap_per_problem = m;
-        }
+        if (!rk.ws.covers((uint32_t)total, 2 * R, per)) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (an earlier chunk may still use the workspace)
+        if ((rc = rk.ws.reserve((uint32_t)total, 2 * R, per))) return rc;
         desc.resize(2 * (size_t)R);
         for (uint32_t r = 0; r < R; ++r) { desc[2 * r] = (uint32_t)first[i0 + r]; desc[2 * r + 1] = (uint32_t)count[i0 + r]; }
-        H2V_HIP_CHECK(hipMemcpyAsync(rk.ranges, desc.data(), 8 * (size_t)R, hipMemcpyHostToDevice, s));
-        if ((rc = fold_shared_ranges_enqueue(s, b->shared, n, ns, rk.ranges, R, rk.fold))) return rc;
+        H2V_HIP_CHECK(hipMemcpyAsync(rk.ranges.p, desc.data(), 8 * (size_t)R, hipMemcpyHostToDevice, s));
+        if ((rc = fold_shared_ranges_enqueue(s, b->shared.p, n, ns, rk.ranges.p, R, rk.fold.p))) return rc;
         MsmProblems pr;
-        for (uint32_t r = 0; r < R; ++r) channel_problems(pr, b, pl, first[i0 + r], (uint32_t)count[i0 + r], rk.acc + 2 * r, rk.fold + (size_t)r * ns * 8, ns);
+        for (uint32_t r = 0; r < R; ++r) channel_problems(pr, b, pl, first[i0 + r], (uint32_t)count[i0 + r], rk.acc.p + 2 * r, rk.fold.p + (size_t)r * ns * 8, ns);
         rk.ws.tune = ctx->tuning; rk.ws.profile = false;
         if ((rc = msm_enqueue_multi(s, rk.ws, pr))) return rc;
-        if ((rc = pairing_check_enqueue(s, ctx->pairing, rk.acc, R, rk.ok))) return rc;
+        if ((rc = pairing_check_enqueue(s, ctx->pairing, rk.acc.p, R, rk.ok.p))) return rc;
         okv.resize(R);
-        H2V_HIP_CHECK(hipMemcpyAsync(okv.data(), rk.ok, 4 * (size_t)R, hipMemcpyDeviceToHost, s));
+        H2V_HIP_CHECK(hipMemcpyAsync(okv.data(), rk.ok.p, 4 * (size_t)R, hipMemcpyDeviceToHost, s));
         if (out_left || out_right) {
-            if ((rc = point_to_bytes_enqueue(s, rk.acc, rk.out_bytes, rk.out_ident, 2 * R))) return rc;
+            if ((rc = point_to_bytes_enqueue(s, rk.acc.p, rk.out_bytes.p, rk.out_ident.p, 2 * R))) return rc;
             outb.resize(128 * (size_t)R);
-            H2V_HIP_CHECK(hipMemcpyAsync(outb.data(), rk.out_bytes, outb.size(), hipMemcpyDeviceToHost, s));
+            H2V_HIP_CHECK(hipMemcpyAsync(outb.data(), rk.out_bytes.p, outb.size(), hipMemcpyDeviceToHost, s));
         }
         const hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) { set_last_error(std::string("h2v_batch_recheck: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
@@ -729,12 +724,6 @@ void h2v_batch_destroy(h2v_batch* b) {
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    hipFree(b->proofs); hipFree(b->inst); hipFree(b->tail); hipFree(b->pts); hipFree(b->phi); hipFree(b->ycanon); hipFree(b->results); hipFree(b->words); hipFree(b->chal);
-    hipFree(b->mult); hipFree(b->slots); hipFree(b->msm_scal); hipFree(b->shared); hipFree(b->left_scal); hipFree(b->insteval); hipFree(b->guard_scal); hipFree(b->acc);
-    hipFree(b->line_ws);
-    if (b->results_host) hipHostFree(b->results_host);
-    b->ws.release();
-    b->recheck.release();
     for (int i = 0; i < 8; ++i) if (b->ev[i]) hipEventDestroy(b->ev[i]);
     if (b->aux) { hipStreamSynchronize(b->aux); hipStreamDestroy(b->aux); }
     if (b->copy) { hipStreamSynchronize(b->copy); hipStreamDestroy(b->copy); }
@@ -744,7 +733,7 @@ void h2v_batch_destroy(h2v_batch* b) {
     if (b->ev_fork0) hipEventDestroy(b->ev_fork0);
     if (b->ev_join0) hipEventDestroy(b->ev_join0);
     if (b->stream && b->owns_stream) hipStreamDestroy(b->stream);
-    delete b;
+    delete b;   // (frees the buffers)
 }
 
 int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
@@ -767,7 +756,7 @@ int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    b->groups = (uint32_t)groups; b->launched = false; b->finished = false;  // the next upload re-sizes the workspace
+    b->groups = (uint32_t)groups; b->launched = false; b->finished = false;  // the next upload grows the buffers if the group count needs more
     return 0;
 }
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups) {
@@ -775,9 +764,9 @@ int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, 
     return finish_impl(b, per_proof_status, group_ok, out_left_xy, out_right_xy);
 }
 int h2v_batch_accumulators(h2v_batch* b, void** device_ptr, size_t* nbytes) {
-    if (!b || !b->acc || !device_ptr) { set_last_error("h2v_batch_accumulators: nothing uploaded"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!b || !b->acc.p || !device_ptr) { set_last_error("h2v_batch_accumulators: nothing uploaded"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->launched) { H2V_HIP_CHECK(hipSetDevice(b->ctx->device)); int rcw = join_tail(b); if (!rcw) rcw = ensure_whole(b); if (rcw) return rcw; }
-    *device_ptr = b->acc;
+    *device_ptr = b->acc.p;
     if (nbytes) *nbytes = 2 * sizeof(G1J) * b->groups;   // raw points, no failure word: see h2v_batch_export_accumulators
     return 0;
 }
@@ -804,9 +793,9 @@ int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, 
     // the fold keeps the cut of this rank's own launch: records cut the same way add up piece by piece, the pairing takes the pieces
     // (the folded pieces replace the rank's own in the workspace: they were exported before the collective that brought these records)
     if (b->split.parts) {
-        G1JSlot* pieces = b->ws.pieces; G1JSlot* ready = b->ws.pieces + (size_t)MSM_MAX_PARTS * b->ws.cap_problems;
-        if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, b->split.parts, b->split.shift, b->acc, pieces, ready, b->fold_failed))) return rc;
-    } else if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, 1, 0, b->acc, nullptr, nullptr, b->fold_failed))) return rc;
+        G1JSlot* pieces = b->ws.pieces.p; G1JSlot* ready = b->ws.pieces.p + (size_t)MSM_MAX_PARTS * b->ws.cap_problems;
+        if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, b->split.parts, b->split.shift, b->acc.p, pieces, ready, b->fold_failed))) return rc;
+    } else if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, 1, 0, b->acc.p, nullptr, nullptr, b->fold_failed))) return rc;
     if ((rc = close_enqueue(b, true))) return rc;
     b->with_pairing = true;
     return 0;
@@ -916,7 +905,7 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
 // (kzg/strategy.rs:129, msm.rs:173-176), whatever group they fall in: the suffix products are computed once over the whole
 // sequence and every group gathers its own.
 // The instance shapes of a call are chosen by whoever supplies the proofs, and every distinct shape costs a plan compilation
-// (O(program length^2) host work, ~10 device uploads) and a resize of the batch workspace: a call takes at most
+// (O(program length^2) host work, ~10 device uploads) and may grow the batch's buffers: a call takes at most
 // H2V_MAX_SHAPES_PER_CALL distinct shapes (H2V_ERR_UNSUPPORTED beyond), the groups share ONE batch object, and the plans go
 // through the context's bounded cache (H2V_MAX_CACHED_PLANS, least recently used out).
 #define H2V_MAX_SHAPES_PER_CALL 64
@@ -953,7 +942,7 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = multipliers_enqueue(ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p))) return rc;
     H2V_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    // one batch object serves every shape group (its workspace follows the group's plan: ensure_buffers)
+    // one batch object serves every shape group (its buffers grow to the largest group's plan: ensure_buffers)
     size_t max_group = 1, max_inst = 0;
     for (auto& g : groups) { max_group = std::max(max_group, g.second.size()); size_t t = 0; for (size_t l : g.first) t += l; max_inst = std::max(max_inst, t); }
     h2v_batch* b = nullptr;
@@ -1059,20 +1048,20 @@ int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const ui
         size_t TL = pl.left_term_order.size();
         if (T > *n_right || TL > *n_left) { set_last_error("h2v_guard_msm: output capacity too small"); rc = H2V_ERR_BAD_ARGUMENT; break; }
         std::vector<uint32_t> lscal((size_t)pl.n_points * 8);
-        if (hipMemcpy(lscal.data(), b->left_scal, lscal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
+        if (hipMemcpy(lscal.data(), b->left_scal.p, lscal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
         std::vector<uint32_t> scal((size_t)pl.n_points * 8);
         std::vector<Fr> shared(pl.n_shared);
         std::vector<G1A> pts(pl.n_points + pl.n_shared);
         std::vector<Fr> chal(pl.squeeze_at.size());
-        if (hipMemcpy(scal.data(), b->msm_scal, scal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shared.data(), b->shared, sizeof(Fr) * pl.n_shared, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(pts.data(), b->pts, sizeof(G1A) * pts.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(chal.data(), b->chal, sizeof(Fr) * chal.size(), hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
+        if (hipMemcpy(scal.data(), b->msm_scal.p, scal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shared.data(), b->shared.p, sizeof(Fr) * pl.n_shared, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(pts.data(), b->pts.p, sizeof(G1A) * pts.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(chal.data(), b->chal.p, sizeof(Fr) * chal.size(), hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
         auto put_pt = [](const G1A& p, uint8_t* o) { if (p.is_identity()) memset(o, 0, 64); else { p.x.to_bytes(o); p.y.to_bytes(o + 32); } };
         if (!pl.guard_term_order.empty()) {
             // GWC: term by term as the reference appends them (gwc.rs:86-132), each with its own scalar
             T = pl.guard_term_order.size();
             if (T > *n_right) { set_last_error("h2v_guard_msm: output capacity too small"); rc = H2V_ERR_BAD_ARGUMENT; break; }
             std::vector<uint32_t> gs(T * 8);
-            if (hipMemcpy(gs.data(), b->guard_scal, gs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
+            if (hipMemcpy(gs.data(), b->guard_scal.p, gs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
             for (size_t t = 0; t < T; ++t) {
                 auto w = pl.guard_term_order[t];
                 memcpy(right_scalars32 + 32 * t, &gs[t * 8], 32);

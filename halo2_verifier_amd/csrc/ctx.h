@@ -10,7 +10,6 @@ struct h2v_batch;
 namespace h2v {
 // staging buffers of h2v_msm_g1, kept between calls (grow-only)
 struct OneShotMsm {
-    uint32_t cap = 0;
     DevBuf<uint8_t> sb, bb, out; DevBuf<uint32_t> s, flags; DevBuf<G1A> b; DevBuf<G1J> res;
 };
 }  // namespace h2v

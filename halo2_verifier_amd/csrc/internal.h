@@ -18,18 +18,47 @@ void set_last_error(const std::string& s);
         }                                                                                       \
     } while (0)
 
-// Device allocation owned by a scope: error paths that `return` from the middle of an entry point free what they took.
+// Device allocation owned by its holder (a scope, a batch, a workspace): error paths that `return` from the middle of an entry point
+// free what they took, and long-lived objects free theirs when they are deleted.
 template <class T> struct DevBuf {
     T* p = nullptr;
+    size_t cap = 0;   // elements p holds
     DevBuf() {}
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) hipFree(p); }
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { reset(); }
     int alloc(size_t count) {
-        if (p) { hipFree(p); p = nullptr; }
+        reset();
         H2V_HIP_CHECK(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
+        cap = count ? count : 1;
         return 0;
     }
+    // grow-only: a new allocation (contents not kept) only when count exceeds what p holds
+    int reserve(size_t count) { return p && count <= cap ? 0 : alloc(count); }
+    void reset() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Pinned host memory mapped into the device's address space (hipHostMallocMapped): `p` for the host, `dev` for kernels that write
+// to it directly.  Grow-only like DevBuf::reserve.
+struct MappedHostBuf {
+    uint8_t* p = nullptr;
+    void* dev = nullptr;
+    size_t cap = 0;   // bytes
+    MappedHostBuf() {}
+    MappedHostBuf(const MappedHostBuf&) = delete;
+    MappedHostBuf& operator=(const MappedHostBuf&) = delete;
+    ~MappedHostBuf() { reset(); }
+    int reserve(size_t bytes) {
+        if (p && bytes <= cap) return 0;
+        reset();
+        H2V_HIP_CHECK(hipHostMalloc((void**)&p, bytes ? bytes : 1, hipHostMallocMapped));
+        H2V_HIP_CHECK(hipHostGetDevicePointer(&dev, p, 0));
+        cap = bytes ? bytes : 1;
+        return 0;
+    }
+    void reset() { if (p) hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
 };
 
 // Forced kernel variants (include/h2v.h: h2v_tuning; every field 0 = automatic).  Lives in the context; a launch copies it into
@@ -94,35 +123,42 @@ struct MsmSplit {
 };
 
 struct MsmWorkspace {
-    uint32_t cap_terms = 0, cap_problems = 0;
-    uint32_t* counts = nullptr;   // [problems * windows * buckets + 3]  (last three words: number of heavy buckets, list cursor, number of straddling buckets)
-    uint32_t* offsets = nullptr;  // [problems * windows * buckets]
-    uint32_t* cursor = nullptr;   // scatter cursors, then the heavy-bucket list
-    uint32_t* list = nullptr;     // term indices sorted by (problem, window, bucket)
-    G1JSlot* bucket_pts = nullptr;  // [problems * windows * buckets]
-    G1JSlot* window_sums = nullptr; // [problems * windows]
-    G1JSlot* pieces = nullptr;      // [2][problems * MSM_MAX_PARTS] partial Horner sums (MsmSplit): Jacobian, then line-ready
-    std::vector<MsmProblem> prepared; // the caller's problems msm_prepare_problems uploaded ahead of the next msm_enqueue_multi (empty: none)
-    MsmProblem* problems = nullptr;  // [cap_problems] descriptors of the launch in flight (sub-problems when large problems are cut)
-    MsmProblem* parents = nullptr;   // [cap_parents] the caller's problems when they were cut
-    G1JSlot* merged_sums = nullptr;  // [cap_parents * 128] window sums of the caller's problems, merged over their sub-problems
-    const MsmProblem* final_problems = nullptr;   // whichever of the two the last launch's Horner wrote through
-    uint32_t cap_parents = 0;
-    uint32_t* block_sums = nullptr;  // [cap_buckets / 1024 + 2] prefix-sum scratch
-    G1JSlot* partial = nullptr;      // [2 * cap_list / chunk] head and tail pieces of the accumulation chunks
-    uint32_t* redo = nullptr;        // [cap_list / chunk] chunks msm_accumulate left to msm_accumulate_redo (complete formulas)
-    uint32_t* glv = nullptr;         // [cap_list / 2] signed window digits of the launch's terms, window-major per problem (LDS sort path)
-    G1A* phi_pts = nullptr;          // [cap_terms] phi(P) = (beta x, y) of every base of the launch (LDS sort path): made once per term instead of once per list entry
-    uint32_t* seg_total = nullptr;   // [problems * windows] entries per list segment
-    uint32_t* seg_start = nullptr;   // [problems * windows + 1] logical start of every segment
+    // what the workspace was sized for (reserve): terms of a launch, the caller's problems, terms of the largest problem
+    uint32_t cap_terms = 0, cap_parents = 0, cap_per_problem = 0;
+    uint32_t cap_problems = 0;                 // problems of a launch once large ones are cut into sub-problems
     size_t cap_buckets = 0, cap_list = 0;
+    DevBuf<uint32_t> counts;       // [problems * windows * buckets + 3]  (last three words: number of heavy buckets, list cursor, number of straddling buckets)
+    DevBuf<uint32_t> offsets;      // [problems * windows * buckets]
+    DevBuf<uint32_t> cursor;       // scatter cursors, then the heavy-bucket list
+    DevBuf<uint32_t> list;         // term indices sorted by (problem, window, bucket)
+    DevBuf<G1JSlot> bucket_pts;    // [problems * windows * buckets]
+    DevBuf<G1JSlot> window_sums;   // [problems * windows]
+    DevBuf<G1JSlot> pieces;        // [2][problems * MSM_MAX_PARTS] partial Horner sums (MsmSplit): Jacobian, then line-ready
+    std::vector<MsmProblem> prepared; // the caller's problems msm_prepare_problems uploaded ahead of the next msm_enqueue_multi (empty: none)
+    DevBuf<MsmProblem> problems;   // [cap_problems] descriptors of the launch in flight (sub-problems when large problems are cut)
+    DevBuf<MsmProblem> parents;    // [cap_parents] the caller's problems when they were cut
+    DevBuf<G1JSlot> merged_sums;   // [cap_parents * 128] window sums of the caller's problems, merged over their sub-problems
+    const MsmProblem* final_problems = nullptr;   // whichever of the two the last launch's Horner wrote through
+    DevBuf<uint32_t> block_sums;   // [cap_buckets / 1024 + 2] prefix-sum scratch
+    DevBuf<G1JSlot> partial;       // [2 * cap_list / chunk] head and tail pieces of the accumulation chunks
+    DevBuf<uint32_t> redo;         // [cap_list / chunk] chunks msm_accumulate left to msm_accumulate_redo (complete formulas)
+    DevBuf<uint32_t> glv;          // [cap_list / 2] signed window digits of the launch's terms, window-major per problem (LDS sort path)
+    DevBuf<G1A> phi_pts;           // [cap_terms] phi(P) = (beta x, y) of every base of the launch (LDS sort path): made once per term instead of once per list entry
+    DevBuf<uint32_t> seg_total;    // [problems * windows] entries per list segment
+    DevBuf<uint32_t> seg_start;    // [problems * windows + 1] logical start of every segment
     // optional HIP events around msm_accumulate (the dominant kernel: bench.py's roofline.kernels), recorded when `profile` is set
     Tuning tune;                     // forced variants for the next launch (copied from the context by the caller)
     bool profile = false, profile_recorded = false;
     hipEvent_t ev_acc[2] = {nullptr, nullptr};
-    // max_terms_per_problem sizes the bucket arrays (the window plan follows the largest problem of a launch)
-    int alloc(uint32_t max_total_terms, uint32_t max_problems, uint32_t max_terms_per_problem = 0);
-    void release();
+    // Grow-only: every dimension becomes the larger of what the workspace holds and what is asked for, and the buffers are allocated
+    // again only if one of them grew (a workspace sized for more serves less).  max_terms_per_problem sizes the bucket arrays (the window
+    // plan follows the largest problem of a launch); 0 = max_total_terms.
+    int reserve(uint32_t max_total_terms, uint32_t max_problems, uint32_t max_terms_per_problem = 0);
+    bool covers(uint32_t max_total_terms, uint32_t max_problems, uint32_t max_terms_per_problem = 0) const;
+    MsmWorkspace() {}
+    MsmWorkspace(const MsmWorkspace&) = delete;
+    MsmWorkspace& operator=(const MsmWorkspace&) = delete;
+    ~MsmWorkspace() { for (hipEvent_t e : ev_acc) if (e) hipEventDestroy(e); }
 };
 // Enqueue all problems of `pr` (each: sum_i scalars[i] * bases[i] -> *out, Jacobian, device memory).  Asynchronous on `s`.
 // With `split` (want_parts > 1) the Horner over the windows stops early: problem q is left as `parts` points

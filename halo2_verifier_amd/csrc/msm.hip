@@ -126,11 +126,17 @@ static inline bool msm_latency_bound(size_t total_terms) { return total_terms <=
 // Large problems are cut into sub-problems of at most MSM_LDS_SORT_MAX_TERMS terms (msm_enqueue_multi): the workspace is sized for the
 // sub-problems, and for the uncut form too (h2v_tuning.msm_no_term_split).
 static inline uint32_t msm_subproblems(uint32_t n) { return n > MSM_LDS_SORT_MAX_TERMS ? (n + MSM_LDS_SORT_MAX_TERMS - 1) / MSM_LDS_SORT_MAX_TERMS : 1u; }
-int MsmWorkspace::alloc(uint32_t max_terms, uint32_t max_problems, uint32_t max_per_problem) {
-    release();
+bool MsmWorkspace::covers(uint32_t max_terms, uint32_t max_problems, uint32_t max_per_problem) const {
     if (!max_per_problem || max_per_problem > max_terms) max_per_problem = max_terms;
+    return counts.p && max_terms <= cap_terms && max_problems <= cap_parents && max_per_problem <= cap_per_problem;
+}
+int MsmWorkspace::reserve(uint32_t max_terms, uint32_t max_problems, uint32_t max_per_problem) {
+    if (!max_per_problem || max_per_problem > max_terms) max_per_problem = max_terms;
+    if (covers(max_terms, max_problems, max_per_problem)) return 0;
+    max_terms = std::max(max_terms, cap_terms); max_problems = std::max(max_problems, cap_parents); max_per_problem = std::max(max_per_problem, cap_per_problem);
+    cap_terms = cap_parents = cap_per_problem = 0;   // (covers nothing until every buffer below is in place)
+    prepared.clear(); final_problems = nullptr; profile_recorded = false;
     const uint32_t subs = msm_subproblems(max_per_problem);
-    cap_terms = max_terms; cap_parents = max_problems;
     cap_problems = (uint32_t)std::min<size_t>((size_t)max_problems * subs, MSM_MAX_PROBLEMS);
     if (cap_problems < max_problems) cap_problems = max_problems;
     const uint32_t per_sub = subs > 1 ? MSM_LDS_SORT_MAX_TERMS : max_per_problem;   // a cut problem's pieces can be exactly the limit
@@ -155,54 +161,23 @@ int MsmWorkspace::alloc(uint32_t max_terms, uint32_t max_problems, uint32_t max_
         }
     }
     cap_buckets = mb;
-    H2V_HIP_CHECK(hipMalloc(&counts, (mb + MSM_CONTROL_WORDS) * 4));
-    H2V_HIP_CHECK(hipMalloc(&offsets, mb * 4));
-    H2V_HIP_CHECK(hipMalloc(&cursor, 2 * mb * 4));   // scatter cursors; then the fix-up's work lists (second half: the team list)
-    H2V_HIP_CHECK(hipMalloc(&list, cap_list * 4));
-    H2V_HIP_CHECK(hipMalloc(&bucket_pts, mb * sizeof(G1JSlot)));
-    H2V_HIP_CHECK(hipMalloc(&window_sums, (size_t)128 * cap_problems * sizeof(G1JSlot)));
-    H2V_HIP_CHECK(hipMalloc(&merged_sums, (size_t)128 * cap_parents * sizeof(G1JSlot)));
-    H2V_HIP_CHECK(hipMalloc(&pieces, (size_t)2 * MSM_MAX_PARTS * cap_problems * sizeof(G1JSlot)));
-    H2V_HIP_CHECK(hipMalloc(&problems, (size_t)cap_problems * sizeof(MsmProblem)));
-    H2V_HIP_CHECK(hipMalloc(&parents, (size_t)cap_parents * sizeof(MsmProblem)));
-    H2V_HIP_CHECK(hipMalloc(&block_sums, (mb / 1024 + 2) * 4));
     // chunks of a launch at most: cap_list / 16, or (short lists, msm_chunk_len) a quarter of up to MSM_SHORT_LIST entries
     const size_t max_chunks = std::max<size_t>(cap_list / MSM_CHUNK_MIN + 1, std::min<size_t>(cap_list, MSM_SHORT_LIST) / MSM_CHUNK_SMALL + 1);
-    H2V_HIP_CHECK(hipMalloc(&partial, max_chunks * 2 * sizeof(G1JSlot)));
-    H2V_HIP_CHECK(hipMalloc(&redo, max_chunks * 4));
-    H2V_HIP_CHECK(hipMalloc(&glv, (cap_list / 2 + 1) * 4));   // digit table: one word per (term, window)
-    H2V_HIP_CHECK(hipMalloc(&phi_pts, ((size_t)cap_terms + 1) * sizeof(G1A)));
-    H2V_HIP_CHECK(hipMalloc(&seg_total, ((size_t)128 * cap_problems + 2) * 4));
-    H2V_HIP_CHECK(hipMalloc(&seg_start, ((size_t)128 * cap_problems + 2) * 4));
+    int rc;
+    if ((rc = counts.alloc(mb + MSM_CONTROL_WORDS)) || (rc = offsets.alloc(mb)) ||
+        (rc = cursor.alloc(2 * mb)) ||   // scatter cursors; then the fix-up's work lists (second half: the team list)
+        (rc = list.alloc(cap_list)) || (rc = bucket_pts.alloc(mb)) || (rc = window_sums.alloc((size_t)128 * cap_problems)) ||
+        (rc = merged_sums.alloc((size_t)128 * max_problems)) || (rc = pieces.alloc((size_t)2 * MSM_MAX_PARTS * cap_problems)) ||
+        (rc = problems.alloc(cap_problems)) || (rc = parents.alloc(max_problems)) || (rc = block_sums.alloc(mb / 1024 + 2)) ||
+        (rc = partial.alloc(max_chunks * 2)) || (rc = redo.alloc(max_chunks)) ||
+        (rc = glv.alloc(cap_list / 2 + 1)) ||   // digit table: one word per (term, window)
+        (rc = phi_pts.alloc((size_t)max_terms + 1)) || (rc = seg_total.alloc((size_t)128 * cap_problems + 2)) || (rc = seg_start.alloc((size_t)128 * cap_problems + 2))) {
+        cap_problems = 0; cap_buckets = cap_list = 0;   // (msm_enqueue_multi refuses every launch until a reserve succeeds)
+        return rc;
+    }
     for (int i = 0; i < 2; ++i) if (!ev_acc[i]) H2V_HIP_CHECK(hipEventCreate(&ev_acc[i]));
+    cap_terms = max_terms; cap_parents = max_problems; cap_per_problem = max_per_problem;
     return 0;
-}
-void MsmWorkspace::release() {
-    if (counts) hipFree(counts);
-    if (offsets) hipFree(offsets);
-    if (cursor) hipFree(cursor);
-    if (list) hipFree(list);
-    if (bucket_pts) hipFree(bucket_pts);
-    if (window_sums) hipFree(window_sums);
-    if (pieces) hipFree(pieces);
-    pieces = nullptr;
-    if (problems) hipFree(problems);
-    if (parents) hipFree(parents);
-    if (merged_sums) hipFree(merged_sums);
-    parents = nullptr; merged_sums = nullptr; final_problems = nullptr; cap_parents = 0;
-    if (block_sums) hipFree(block_sums);
-    if (partial) hipFree(partial);
-    if (redo) hipFree(redo);
-    redo = nullptr;
-    if (glv) hipFree(glv);
-    if (phi_pts) hipFree(phi_pts);
-    phi_pts = nullptr;
-    if (seg_total) hipFree(seg_total);
-    if (seg_start) hipFree(seg_start);
-    glv = seg_total = seg_start = nullptr;
-    counts = offsets = cursor = list = block_sums = nullptr; bucket_pts = window_sums = partial = nullptr; problems = nullptr;
-    for (int i = 0; i < 2; ++i) if (ev_acc[i]) { hipEventDestroy(ev_acc[i]); ev_acc[i] = nullptr; }
-    cap_terms = 0; cap_problems = 0; profile_recorded = false;
 }
 
 // ---- GLV decomposition for BN254 G1 (constants derived in DESIGN.md section 4; lattice basis (a1, b1), (a2, b2) with
@@ -1100,8 +1075,8 @@ int msm_prepare_problems(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr)
     MsmLaunchShape L;
     int rc = msm_shape(ws, pr, L);
     if (rc) return rc;
-    if (L.cut) msm_upload_problems(s, L.parents_p, false, ws.parents);
-    msm_upload_problems(s, L.launch_p, true, ws.problems);
+    if (L.cut) msm_upload_problems(s, L.parents_p, false, ws.parents.p);
+    msm_upload_problems(s, L.launch_p, true, ws.problems.p);
     H2V_HIP_CHECK(hipGetLastError());
     ws.prepared = pr.p;
     return 0;
@@ -1119,13 +1094,13 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     const bool uploaded = msm_same_problems(ws.prepared, pr.p);   // msm_prepare_problems, earlier in stream order
     ws.prepared.clear();
     if (!uploaded) {
-        if (cut) msm_upload_problems(s, L.parents_p, false, ws.parents);
-        msm_upload_problems(s, launch_p, true, ws.problems);
+        if (cut) msm_upload_problems(s, L.parents_p, false, ws.parents.p);
+        msm_upload_problems(s, launch_p, true, ws.problems.p);
     }
     const uint32_t count = (uint32_t)launch_p.size();
-    ws.final_problems = cut ? ws.parents : ws.problems;
+    ws.final_problems = cut ? ws.parents.p : ws.problems.p;
     if (nmax == 0) {
-        hipLaunchKernelGGL(msm_final, dim3((4 * count + 63) / 64), dim3(64), 0, s, ws.window_sums, ws.problems, count, MsmPlan{0, 2, 0, 3});
+        hipLaunchKernelGGL(msm_final, dim3((4 * count + 63) / 64), dim3(64), 0, s, ws.window_sums.p, ws.problems.p, count, MsmPlan{0, 2, 0, 3});
         H2V_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -1142,25 +1117,25 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     MsmSeg g;
     const uint32_t lanes_round = ws.tune.msm_acc_waves == 4 ? 262144u : MSM_ACC_LANES_PER_ROUND;
     if (lds_sort) {
-        hipLaunchKernelGGL(msm_glv_prep, dim3((nmax + 255) / 256, count), dim3(256), 0, s, ws.problems, count, p, ws.glv, ws.phi_pts);
+        hipLaunchKernelGGL(msm_glv_prep, dim3((nmax + 255) / 256, count), dim3(256), 0, s, ws.problems.p, count, p, ws.glv.p, ws.phi_pts.p);
         if (sort_lds > 64 * 1024) H2V_HIP_CHECK(hipFuncSetAttribute((const void*)msm_sort_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-        hipLaunchKernelGGL(msm_sort_lds, dim3(p.windows, count), dim3(MSM_SORT_THREADS), sort_lds, s, ws.problems, ws.glv, p, stride, ws.counts, ws.offsets, ws.list, ws.seg_total);
-        hipLaunchKernelGGL(msm_seg_scan, dim3(1), dim3(1024), 0, s, ws.seg_total, p.windows * count, ws.seg_start, ws.counts + nb);
-        g = MsmSeg{ws.seg_start, p.windows * count, p.buckets, stride, lanes_round};
+        hipLaunchKernelGGL(msm_sort_lds, dim3(p.windows, count), dim3(MSM_SORT_THREADS), sort_lds, s, ws.problems.p, ws.glv.p, p, stride, ws.counts.p, ws.offsets.p, ws.list.p, ws.seg_total.p);
+        hipLaunchKernelGGL(msm_seg_scan, dim3(1), dim3(1024), 0, s, ws.seg_total.p, p.windows * count, ws.seg_start.p, ws.counts.p + nb);
+        g = MsmSeg{ws.seg_start.p, p.windows * count, p.buckets, stride, lanes_round};
     } else {
-    H2V_HIP_CHECK(hipMemsetAsync(ws.counts, 0, ((size_t)nb + MSM_CONTROL_WORDS) * 4, s));
-    H2V_HIP_CHECK(hipMemsetAsync(ws.seg_start, 0, 4, s));   // one segment that starts at 0
+    H2V_HIP_CHECK(hipMemsetAsync(ws.counts.p, 0, ((size_t)nb + MSM_CONTROL_WORDS) * 4, s));
+    H2V_HIP_CHECK(hipMemsetAsync(ws.seg_start.p, 0, 4, s));   // one segment that starts at 0
     const uint32_t tiles = (nmax + MSM_TILE - 1) / MSM_TILE;
     dim3 gt(8 * ((count + 7) / 8) * tiles);
     const uint32_t wpp = std::max<uint32_t>(1u, std::min<uint32_t>(p.windows, MSM_LDS_WORDS / p.buckets));
     const size_t lds = (size_t)wpp * p.buckets * 4;
-    hipLaunchKernelGGL(msm_count_or_scatter<false>, gt, dim3(MSM_TILE_THREADS), lds, s, ws.problems, count, tiles, p, wpp, ws.counts, ws.offsets, ws.cursor, ws.list);
+    hipLaunchKernelGGL(msm_count_or_scatter<false>, gt, dim3(MSM_TILE_THREADS), lds, s, ws.problems.p, count, tiles, p, wpp, ws.counts.p, ws.offsets.p, ws.cursor.p, ws.list.p);
     const uint32_t nblk = (nb + 1023) / 1024;
-    hipLaunchKernelGGL(msm_block_sums, dim3(nblk), dim3(1024), 0, s, ws.counts, ws.block_sums, nb);
-    hipLaunchKernelGGL(msm_scan_sums, dim3(1), dim3(1024), 0, s, ws.block_sums, nblk, ws.counts + nb + 1);
-    hipLaunchKernelGGL(msm_offsets, dim3(nblk), dim3(1024), 0, s, ws.counts, ws.block_sums, ws.offsets, ws.cursor, nb);
-    hipLaunchKernelGGL(msm_count_or_scatter<true>, gt, dim3(MSM_TILE_THREADS), lds, s, ws.problems, count, tiles, p, wpp, ws.counts, ws.offsets, ws.cursor, ws.list);
-    g = MsmSeg{ws.seg_start, 1, nb, 0, lanes_round};
+    hipLaunchKernelGGL(msm_block_sums, dim3(nblk), dim3(1024), 0, s, ws.counts.p, ws.block_sums.p, nb);
+    hipLaunchKernelGGL(msm_scan_sums, dim3(1), dim3(1024), 0, s, ws.block_sums.p, nblk, ws.counts.p + nb + 1);
+    hipLaunchKernelGGL(msm_offsets, dim3(nblk), dim3(1024), 0, s, ws.counts.p, ws.block_sums.p, ws.offsets.p, ws.cursor.p, nb);
+    hipLaunchKernelGGL(msm_count_or_scatter<true>, gt, dim3(MSM_TILE_THREADS), lds, s, ws.problems.p, count, tiles, p, wpp, ws.counts.p, ws.offsets.p, ws.cursor.p, ws.list.p);
+    g = MsmSeg{ws.seg_start.p, 1, nb, 0, lanes_round};
     }
     // one lane per chunk of the sorted list; the entry count is only known on the device, the grid covers the host's bound on it.
     // Surplus workgroups are not free: the kernel holds exactly its occupancy in working workgroups (3 waves per SIMD), so the
@@ -1168,17 +1143,17 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     // workgroups, 0.07 ms, at the end of every 20-step launch.
     const uint32_t acc_blocks = msm_accumulate_blocks(total_nz * 2 * p.windows, lanes_round);
     {
-        const G1A* phi_tab = lds_sort ? (const G1A*)ws.phi_pts : (const G1A*)nullptr;
+        const G1A* phi_tab = lds_sort ? (const G1A*)ws.phi_pts.p : (const G1A*)nullptr;
         auto kern = ws.tune.msm_acc_waves == 4 ? msm_accumulate<4> : msm_accumulate<3>;
         // (the profiling events are attached to the dispatch itself — its own start and stop timestamps — instead of being recorded around it:
         // a recorded event is a barrier packet, ~6 us of idle stream on either side of the kernel)
         if (ws.profile) {
-            hipExtLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.ev_acc[0], ws.ev_acc[1], 0, ws.problems, nbq, ws.counts, ws.offsets, ws.list, ws.bucket_pts, ws.partial, nb, g, ws.counts + nb, ws.cursor, phi_tab, ws.redo);
+            hipExtLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.ev_acc[0], ws.ev_acc[1], 0, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
             ws.profile_recorded = true;
-        } else hipLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.problems, nbq, ws.counts, ws.offsets, ws.list, ws.bucket_pts, ws.partial, nb, g, ws.counts + nb, ws.cursor, phi_tab, ws.redo);
+        } else hipLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
     }
-    hipLaunchKernelGGL(msm_accumulate_redo, dim3(256), dim3(64), 0, s, ws.problems, nbq, ws.counts, ws.offsets, ws.list, ws.bucket_pts, ws.partial, nb, g, ws.counts + nb, ws.cursor, ws.redo);
-    hipLaunchKernelGGL(msm_fixup, dim3((nb + 63) / 64 + MSM_FIXUP_TEAM_BLOCKS + MSM_FIXUP_HEAVY_BLOCKS), dim3(64), 0, s, ws.counts, ws.offsets, ws.partial, ws.cursor, ws.bucket_pts, nb, g);
+    hipLaunchKernelGGL(msm_accumulate_redo, dim3(256), dim3(64), 0, s, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, ws.redo.p);
+    hipLaunchKernelGGL(msm_fixup, dim3((nb + 63) / 64 + MSM_FIXUP_TEAM_BLOCKS + MSM_FIXUP_HEAVY_BLOCKS), dim3(64), 0, s, ws.counts.p, ws.offsets.p, ws.partial.p, ws.cursor.p, ws.bucket_pts.p, nb, g);
     {
         // Two-wave workgroups land on overlapping SIMD pairs when a CU holds two of them (measured: 0.57 ms for what one wave per
         // window does in 0.48), so beyond 256 windows a workgroup is FOUR waves reducing two windows, two waves each: every wave
@@ -1192,18 +1167,18 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
         const uint32_t slots = ((T * wpw <= 64 && nw > 1024) || ws.tune.msm_window_slots == 3) ? 3u : (uint32_t)MSM_WIN_SLOTS;
         const size_t win_lds = (size_t)slots * T * wpw * sizeof(G1J);   // 34 KB for one wave, 135 KB for four
         if (win_lds > 64 * 1024) H2V_HIP_CHECK(hipFuncSetAttribute((const void*)msm_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds));
-        hipLaunchKernelGGL(msm_window, dim3((nw + wpw - 1) / wpw), dim3(T * wpw), win_lds, s, ws.bucket_pts, ws.counts, ws.window_sums, p, nw, wpw, slots);
+        hipLaunchKernelGGL(msm_window, dim3((nw + wpw - 1) / wpw), dim3(T * wpw), win_lds, s, ws.bucket_pts.p, ws.counts.p, ws.window_sums.p, p, nw, wpw, slots);
     }
-    const G1JSlot* sums = ws.window_sums;
+    const G1JSlot* sums = ws.window_sums.p;
     if (cut) {
-        hipLaunchKernelGGL(msm_merge_windows, dim3((8 * n_callers * p.windows + 63) / 64), dim3(64), 0, s, ws.window_sums, ws.parents, n_callers, p.windows, ws.merged_sums);
-        sums = ws.merged_sums;
+        hipLaunchKernelGGL(msm_merge_windows, dim3((8 * n_callers * p.windows + 63) / 64), dim3(64), 0, s, ws.window_sums.p, ws.parents.p, n_callers, p.windows, ws.merged_sums.p);
+        sums = ws.merged_sums.p;
     }
     if (split && split->want_parts > 1 && p.windows > 1) {
         const uint32_t want = std::min<uint32_t>(split->want_parts, MSM_MAX_PARTS);
         const uint32_t wpp = (p.windows + want - 1) / want, parts = (p.windows + wpp - 1) / wpp;
-        hipLaunchKernelGGL(msm_final_parts, dim3((4 * n_callers * parts + 63) / 64), dim3(64), 0, s, sums, ws.final_problems, n_callers, p, parts, wpp, ws.pieces, ws.pieces + (size_t)MSM_MAX_PARTS * ws.cap_problems);
-        split->parts = parts; split->shift = p.c * wpp; split->count = n_callers; split->pts = ws.pieces; split->ready = ws.pieces + (size_t)MSM_MAX_PARTS * ws.cap_problems;
+        hipLaunchKernelGGL(msm_final_parts, dim3((4 * n_callers * parts + 63) / 64), dim3(64), 0, s, sums, ws.final_problems, n_callers, p, parts, wpp, ws.pieces.p, ws.pieces.p + (size_t)MSM_MAX_PARTS * ws.cap_problems);
+        split->parts = parts; split->shift = p.c * wpp; split->count = n_callers; split->pts = ws.pieces.p; split->ready = ws.pieces.p + (size_t)MSM_MAX_PARTS * ws.cap_problems;
     } else {
         hipLaunchKernelGGL(msm_final, dim3((4 * n_callers + 63) / 64), dim3(64), 0, s, sums, ws.final_problems, n_callers, p);
     }

@@ -23,24 +23,23 @@ std::vector<uint32_t> pairing_program2();   // two operation streams per check: 
 #define H2V_PAIRING_LINE_WS_BYTES ((size_t)66 * 6 * sizeof(Fq2))   // per check: k_pair_lines' output, one Fq12 per Miller iteration (+ 2 corrections)
 
 struct PairingDevice {
-    LineCoeff* l_sg2 = nullptr;  // line coefficients for s_g2
-    LineCoeff* l_ng2 = nullptr;  // line coefficients for -g2
+    DevBuf<LineCoeff> l_sg2;     // line coefficients for s_g2
+    DevBuf<LineCoeff> l_ng2;     // line coefficients for -g2
     // line coefficients of the multiples 2^(shift j) s_g2, -2^(shift j) g2, j < parts (for checks over split accumulators): made on
     // the host on first use of a (shift, parts) pair, kept for the life of the context.  Row 2 j + side, H2V_PAIRING_LINES entries each.
-    struct SplitTable { uint32_t shift, parts; LineCoeff* lines; };
+    struct SplitTable { uint32_t shift, parts; DevBuf<LineCoeff> lines; };
     std::vector<SplitTable> split;
     std::mutex split_mu;
     G2A h_sg2, h_ng2;            // host copies for those tables
     int split_lines(uint32_t shift, uint32_t parts, const LineCoeff** out);
-    PairingConsts* consts = nullptr;
-    uint32_t* prog = nullptr;    // the pairing's operation table (pairing.hip: pairing_program)
+    DevBuf<PairingConsts> consts;
+    DevBuf<uint32_t> prog;       // the pairing's operation table (pairing.hip: pairing_program)
     uint32_t n_ops = 0;
-    uint32_t* prog_merged = nullptr;   // the same with one line product per Miller iteration (checks over split accumulators)
+    DevBuf<uint32_t> prog_merged;      // the same with one line product per Miller iteration (checks over split accumulators)
     uint32_t n_ops_merged = 0;
-    uint32_t* prog2 = nullptr;         // two streams per check (k_pairing2): uint2 per step
+    DevBuf<uint32_t> prog2;            // two streams per check (k_pairing2): uint2 per step
     uint32_t n_steps2 = 0;
     int upload(const ParamsHost& p);
-    void release();
 };
 
 int pairing_check_enqueue(hipStream_t s, const PairingDevice& pd, const G1J* d_pairs, uint32_t n, uint32_t* d_ok);

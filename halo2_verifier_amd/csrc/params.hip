@@ -123,23 +123,21 @@ int PairingDevice::upload(const ParamsHost& p) {
     int nb = g2_prepare(ng2, k, b.data());
     if (na != H2V_PAIRING_LINES || nb != H2V_PAIRING_LINES) { set_last_error("pairing: unexpected Miller loop length"); return H2V_ERR_DEVICE; }
     h_sg2 = p.s_g2; h_ng2 = ng2;
-    H2V_HIP_CHECK(hipMalloc(&l_sg2, sizeof(LineCoeff) * na));
-    H2V_HIP_CHECK(hipMalloc(&l_ng2, sizeof(LineCoeff) * na));
-    H2V_HIP_CHECK(hipMalloc(&consts, sizeof(PairingConsts)));
-    H2V_HIP_CHECK(hipMemcpy(l_sg2, a.data(), sizeof(LineCoeff) * na, hipMemcpyHostToDevice));
-    H2V_HIP_CHECK(hipMemcpy(l_ng2, b.data(), sizeof(LineCoeff) * na, hipMemcpyHostToDevice));
-    H2V_HIP_CHECK(hipMemcpy(consts, &k, sizeof(PairingConsts), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = l_sg2.alloc(na)) || (rc = l_ng2.alloc(na)) || (rc = consts.alloc(1))) return rc;
+    H2V_HIP_CHECK(hipMemcpy(l_sg2.p, a.data(), sizeof(LineCoeff) * na, hipMemcpyHostToDevice));
+    H2V_HIP_CHECK(hipMemcpy(l_ng2.p, b.data(), sizeof(LineCoeff) * na, hipMemcpyHostToDevice));
+    H2V_HIP_CHECK(hipMemcpy(consts.p, &k, sizeof(PairingConsts), hipMemcpyHostToDevice));
     const std::vector<uint32_t> ops = pairing_program(false), opsm = pairing_program(true);
     n_ops = (uint32_t)ops.size(); n_ops_merged = (uint32_t)opsm.size();
-    H2V_HIP_CHECK(hipMalloc(&prog, 4 * ops.size()));
-    H2V_HIP_CHECK(hipMemcpy(prog, ops.data(), 4 * ops.size(), hipMemcpyHostToDevice));
-    H2V_HIP_CHECK(hipMalloc(&prog_merged, 4 * opsm.size()));
-    H2V_HIP_CHECK(hipMemcpy(prog_merged, opsm.data(), 4 * opsm.size(), hipMemcpyHostToDevice));
+    if ((rc = prog.alloc(ops.size())) || (rc = prog_merged.alloc(opsm.size()))) return rc;
+    H2V_HIP_CHECK(hipMemcpy(prog.p, ops.data(), 4 * ops.size(), hipMemcpyHostToDevice));
+    H2V_HIP_CHECK(hipMemcpy(prog_merged.p, opsm.data(), 4 * opsm.size(), hipMemcpyHostToDevice));
     const std::vector<uint32_t> ops2 = pairing_program2();
     n_steps2 = (uint32_t)(ops2.size() / 2);
     if (n_steps2 > H2V_PAIR2_MAX_STEPS) { set_last_error("pairing: two-stream table too long"); return H2V_ERR_DEVICE; }
-    H2V_HIP_CHECK(hipMalloc(&prog2, 4 * ops2.size()));
-    H2V_HIP_CHECK(hipMemcpy(prog2, ops2.data(), 4 * ops2.size(), hipMemcpyHostToDevice));
+    if ((rc = prog2.alloc(ops2.size()))) return rc;
+    H2V_HIP_CHECK(hipMemcpy(prog2.p, ops2.data(), 4 * ops2.size(), hipMemcpyHostToDevice));
     return 0;
 }
 // 2^shift * q by the Miller loop's own doubling step (homogeneous projective), back to affine
@@ -152,7 +150,7 @@ static G2A g2_times_pow2(const G2A& q, uint32_t shift, const PairingConsts& k) {
 }
 int PairingDevice::split_lines(uint32_t shift, uint32_t parts, const LineCoeff** out) {
     std::lock_guard<std::mutex> lock(split_mu);
-    for (const SplitTable& t : split) if (t.shift == shift && t.parts == parts) { *out = t.lines; return 0; }
+    for (const SplitTable& t : split) if (t.shift == shift && t.parts == parts) { *out = t.lines.p; return 0; }
     const PairingConsts k = pairing_consts_host();
     std::vector<LineCoeff> rows((size_t)2 * parts * H2V_PAIRING_LINES), one(MAX_LINE_COEFFS);
     G2A a = h_sg2, b = h_ng2;
@@ -164,26 +162,13 @@ int PairingDevice::split_lines(uint32_t shift, uint32_t parts, const LineCoeff**
             std::copy(one.begin(), one.begin() + H2V_PAIRING_LINES, rows.begin() + (size_t)(2 * j + sd) * H2V_PAIRING_LINES);
         }
     }
-    LineCoeff* d = nullptr;
-    H2V_HIP_CHECK(hipMalloc(&d, sizeof(LineCoeff) * rows.size()));
-    hipError_t e = hipMemcpy(d, rows.data(), sizeof(LineCoeff) * rows.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(d); set_last_error(std::string("pairing: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
-    split.push_back(SplitTable{shift, parts, d});
-    *out = d;
+    DevBuf<LineCoeff> d;
+    int rc;
+    if ((rc = d.alloc(rows.size()))) return rc;
+    H2V_HIP_CHECK(hipMemcpy(d.p, rows.data(), sizeof(LineCoeff) * rows.size(), hipMemcpyHostToDevice));
+    *out = d.p;
+    split.push_back(SplitTable{shift, parts, std::move(d)});
     return 0;
-}
-void PairingDevice::release() {
-    for (SplitTable& t : split) if (t.lines) hipFree(t.lines);
-    split.clear();
-    if (l_sg2) hipFree(l_sg2);
-    if (l_ng2) hipFree(l_ng2);
-    if (consts) hipFree(consts);
-    if (prog) hipFree(prog);
-    if (prog_merged) hipFree(prog_merged);
-    if (prog2) hipFree(prog2);
-    prog2 = nullptr; n_steps2 = 0;
-    prog_merged = nullptr; n_ops_merged = 0;
-    l_sg2 = l_ng2 = nullptr; consts = nullptr; prog = nullptr; n_ops = 0;
 }
 
 }  // namespace h2v

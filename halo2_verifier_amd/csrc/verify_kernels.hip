@@ -660,9 +660,9 @@ int decompress_stage_enqueue(hipStream_t s, const StageArgs& g) {
     const Plan& pl = *g.plan;
     H2V_HIP_CHECK(hipMemsetAsync(g.status, 0, sizeof(int) * n, s));
     uint32_t tp = n * pl.n_points;
-    hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs, pl.proof_len, g.pd->point_offsets, pl.n_points, pl.n_main_points, n, g.pts, g.phi, g.ycanon, g.status);
+    hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, n, g.pts, g.phi, g.ycanon, g.status);
     uint32_t ts = n * (pl.n_scalars + pl.n_instance_values);
-    if (ts) hipLaunchKernelGGL(k_check_scalars, dim3((ts + 255) / 256), dim3(256), 0, s, g.proofs, pl.proof_len, g.pd->scalar_offsets, pl.n_scalars, g.inst, pl.n_instance_values, n, g.status);
+    if (ts) hipLaunchKernelGGL(k_check_scalars, dim3((ts + 255) / 256), dim3(256), 0, s, g.proofs, pl.proof_len, g.pd->scalar_offsets.p, pl.n_scalars, g.inst, pl.n_instance_values, n, g.status);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -676,7 +676,7 @@ int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uin
     const uint32_t m = p1 - p0, tp = m * pl.n_points;
     if (!tp) return 0;
     if (!src) { src = g.proofs; src_stride = pl.proof_len; }
-    hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, src + (size_t)p0 * src_stride, src_stride, g.pd->point_offsets, pl.n_points, pl.n_main_points, m,
+    hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, src + (size_t)p0 * src_stride, src_stride, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, m,
                        g.pts + (size_t)p0 * pl.n_points, g.phi + (size_t)p0 * pl.n_points, g.ycanon + (size_t)p0 * pl.n_points * 32, g.status + p0);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
@@ -684,7 +684,7 @@ int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uin
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g) {
     const Plan& pl = *g.plan;
     const uint32_t ts = g.n * (pl.n_scalars + pl.n_instance_values);
-    if (ts) hipLaunchKernelGGL(k_check_scalars, dim3((ts + 255) / 256), dim3(256), 0, s, g.proofs, pl.proof_len, g.pd->scalar_offsets, pl.n_scalars, g.inst, pl.n_instance_values, g.n, g.status);
+    if (ts) hipLaunchKernelGGL(k_check_scalars, dim3((ts + 255) / 256), dim3(256), 0, s, g.proofs, pl.proof_len, g.pd->scalar_offsets.p, pl.n_scalars, g.inst, pl.n_instance_values, g.n, g.status);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -694,16 +694,16 @@ int transcript_stage_enqueue(hipStream_t s, const StageArgs& g) {
     const Plan& pl = *g.plan;
     uint32_t stream_len = (uint32_t)pl.stream.size();
     uint32_t n_words = g.stream_words;
-    hipLaunchKernelGGL(k_stream_build, dim3((n + STREAM_PROOFS_PER_BLOCK - 1) / STREAM_PROOFS_PER_BLOCK), dim3(256), 0, s, g.pd->stream, stream_len, g.proofs, pl.proof_len, g.ycanon, pl.n_points, g.inst,
+    hipLaunchKernelGGL(k_stream_build, dim3((n + STREAM_PROOFS_PER_BLOCK - 1) / STREAM_PROOFS_PER_BLOCK), dim3(256), 0, s, g.pd->stream.p, stream_len, g.proofs, pl.proof_len, g.ycanon, pl.n_points, g.inst,
                        pl.n_instance_values, n, n_words, g.words);
     if (pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256)
-        hipLaunchKernelGGL(k_transcript_keccak, dim3((n + 63) / 64), dim3(64), 0, s, g.words, n_words, g.pd->squeeze_at, (uint32_t)pl.squeeze_at.size(), n, g.chal);
+        hipLaunchKernelGGL(k_transcript_keccak, dim3((n + 63) / 64), dim3(64), 0, s, g.words, n_words, g.pd->squeeze_at.p, (uint32_t)pl.squeeze_at.size(), n, g.chal);
     else
     {
         const uint32_t nsq = (uint32_t)pl.squeeze_at.size();
         const size_t lds = ((size_t)16 * TR4_MSG_STRIDE + (size_t)16 * nsq * 8) * 8;
         if (lds > 60 * 1024) { set_last_error("transcript: too many challenges for one workgroup's LDS"); return H2V_ERR_UNSUPPORTED; }
-        hipLaunchKernelGGL(k_transcript, dim3((n + 15) / 16), dim3(64), lds, s, g.words, n_words, g.pd->squeeze_at, nsq, n, g.chal);
+        hipLaunchKernelGGL(k_transcript, dim3((n + 15) / 16), dim3(64), lds, s, g.words, n_words, g.pd->squeeze_at.p, nsq, n, g.chal);
     }
     H2V_HIP_CHECK(hipGetLastError());
     return 0;

@@ -125,19 +125,18 @@ int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<s
 
 struct PlanDevice {
     Plan host;
-    VmInstr* code = nullptr;
-    VmInstr* code_k[3][FRVM_MAX_STREAMS] = {{nullptr}};
-    Fr* consts = nullptr;
-    TranscriptSrc* stream = nullptr;
-    uint32_t* squeeze_at = nullptr;
-    uint32_t* point_offsets = nullptr;
-    uint32_t* scalar_offsets = nullptr;
-    G1A* shared_bases = nullptr; G1A* shared_phi = nullptr;   // the VK-wide bases and their images under phi (MsmProblem::phi2)
+    DevBuf<VmInstr> code;
+    DevBuf<VmInstr> code_k[3][FRVM_MAX_STREAMS];   // (streams q < K only)
+    DevBuf<Fr> consts;
+    DevBuf<TranscriptSrc> stream;
+    DevBuf<uint32_t> squeeze_at;
+    DevBuf<uint32_t> point_offsets;
+    DevBuf<uint32_t> scalar_offsets;
+    DevBuf<G1A> shared_bases, shared_phi;   // the VK-wide bases and their images under phi (MsmProblem::phi2)
     int pins = 0;             // users that hold the plan (batches between upload and their next upload / destruction, entry points while
                               // they read it); guarded by VkDevice::mu.  Only unpinned plans are evicted.
     uint64_t last_use = 0;    // VkDevice::clock at the last ctx_get_plan
     int upload();
-    void release();
 };
 
 // Compiled plans of one VK, keyed by instance column lengths.  A plan costs a compilation (one single-stream emit + three list

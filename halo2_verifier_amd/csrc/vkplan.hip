@@ -1109,10 +1109,10 @@ int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<s
 }
 
 // =============================================================================== device upload
-template <class T> static int upload_vec(const std::vector<T>& v, T*& d) {
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    H2V_HIP_CHECK(hipMalloc(&d, bytes));
-    if (!v.empty()) H2V_HIP_CHECK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+template <class T> static int upload_vec(const std::vector<T>& v, DevBuf<T>& d) {
+    int rc;
+    if ((rc = d.alloc(v.size()))) return rc;
+    if (!v.empty()) H2V_HIP_CHECK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 int PlanDevice::upload() {
@@ -1130,10 +1130,6 @@ int PlanDevice::upload() {
     if ((rc = upload_vec(phi, shared_phi))) return rc;
     return 0;
 }
-void PlanDevice::release() {
-    hipFree(code); for (int k = 0; k < 3; ++k) for (int q = 0; q < FRVM_MAX_STREAMS; ++q) hipFree(code_k[k][q]); hipFree(consts); hipFree(stream); hipFree(squeeze_at); hipFree(point_offsets); hipFree(scalar_offsets); hipFree(shared_bases); hipFree(shared_phi);
-    code = nullptr; consts = nullptr; stream = nullptr; squeeze_at = nullptr; point_offsets = nullptr; scalar_offsets = nullptr; shared_bases = nullptr; shared_phi = nullptr;
-}
 
 int ctx_load_vk(h2v_ctx* ctx, const uint8_t* vk, size_t vk_len, int vk_format) {
     VkDevice* v = new VkDevice();
@@ -1146,7 +1142,7 @@ int ctx_load_vk(h2v_ctx* ctx, const uint8_t* vk, size_t vk_len, int vk_format) {
 size_t ctx_total_instance_columns(const h2v_ctx* ctx) { return ctx->vk ? (size_t)ctx->circuit_instances * ctx->vk->vk.num_instance_columns : 0; }
 void ctx_release_vk(h2v_ctx* ctx) {
     if (!ctx->vk) return;
-    for (auto& kv : ctx->vk->plans) { kv.second->release(); delete kv.second; }
+    for (auto& kv : ctx->vk->plans) delete kv.second;
     delete ctx->vk;
     ctx->vk = nullptr;
 }
@@ -1169,7 +1165,7 @@ int ctx_get_plan(h2v_ctx* ctx, const std::vector<size_t>& col_lens_in, PlanDevic
     if (rc) { set_last_error("plan: " + err); delete pd; return rc; }
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     rc = pd->upload();
-    if (rc) { pd->release(); delete pd; return rc; }
+    if (rc) { delete pd; return rc; }
     pd->last_use = ++vd.clock; pd->pins = 1;
     vd.plans[key] = pd;
     // bounded cache: release the least recently used plans nobody holds (never the one just made: it is pinned)
@@ -1178,7 +1174,7 @@ int ctx_get_plan(h2v_ctx* ctx, const std::vector<size_t>& col_lens_in, PlanDevic
         for (auto jt = vd.plans.begin(); jt != vd.plans.end(); ++jt)
             if (jt->second->pins == 0 && (victim == vd.plans.end() || jt->second->last_use < victim->second->last_use)) victim = jt;
         if (victim == vd.plans.end()) break;   // everything is in use: the cache may exceed its bound while that lasts
-        victim->second->release(); delete victim->second;
+        delete victim->second;
         vd.plans.erase(victim);
     }
     *out = pd;

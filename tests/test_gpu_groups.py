@@ -140,8 +140,10 @@ def test_group_argument_checks(pool):
     b.launch()
     with pytest.raises(h2v.H2VError):       # a grouped batch has no single verdict
         b.finish()
-    ok, st, _, _ = b.finish_groups()
+    got = b.finish_groups()
+    ok, st, _, _ = got
     assert ok == [True] * 4 and st == [0] * 12
+    assert got == _grouped(ctx, P[:12], I[:12], [1] * 12, 4)
     with pytest.raises(h2v.H2VError):
         b.set_groups(0)
     # back to one group: the plain finish works again on the same object
@@ -150,6 +152,13 @@ def test_group_argument_checks(pool):
     b.launch()
     ok1, st1, l1, r1 = b.finish()
     assert (ok1, st1, l1, r1) == ctx.verify_batch(P[:12], I[:12], [3] * 12)
+    assert ([ok1], st1, [l1], [r1]) == _grouped(ctx, P[:12], I[:12], [3] * 12, 1)
+    # and four groups again: the object's buffers, last sized for four groups, served one group and now four (4 -> 1 -> 4)
+    rand4 = [7 + i for i in range(12)]
+    b.set_groups(4)
+    b.upload(flat, 1024, inst, [8], _rand_bytes(rand4))
+    b.launch()
+    assert b.finish_groups() == _grouped(ctx, P[:12], I[:12], rand4, 4)
     b.close()
     ctx.close()
 

@@ -31,6 +31,7 @@ def _mixed(s, lens, seed):
 
 
 def test_batch_with_per_proof_instance_shapes():
+    import halo2_verifier_amd as h2v
     s = circuits.setup_vector_mul(8, 8)
     lens = [8, 5, 8, 3, 5, 8, 0, 3, 3, 8, 5]
     P, I = _mixed(s, lens, 7)
@@ -60,6 +61,21 @@ def test_batch_with_per_proof_instance_shapes():
     assert got == exp and got[0] is False and got[1][4] == -5
     # OS-drawn multipliers
     assert ctx.verify_batch(P, I, None)[0] is True
+    # one staged batch across plans: the 8-value shape's plan, the 3-value shape's (smaller: it runs in buffers sized for the larger), the
+    # 8-value shape's again — every launch bit for bit what a fresh batch gives
+    def staged(b, idx):
+        flat = b"".join(P[j] for j in idx)
+        inst = b"".join(v for j in idx for col in I[j] for v in col)
+        b.upload(flat, len(P[0]), inst, [lens[idx[0]]], b"".join(rand[j].to_bytes(32, "little") for j in idx))
+        b.launch(with_pairing=True)
+        return b.finish()
+    b = h2v.Batch(ctx, 4, 8)
+    for idx in ([0, 2, 5, 9], [3, 7, 8], [0, 2, 5, 9]):
+        fresh = h2v.Batch(ctx, 4, 8)
+        want = staged(fresh, idx)
+        fresh.close()
+        assert want[0] is True and staged(b, idx) == want
+    b.close()
     ctx.close()
     s.free()
 
