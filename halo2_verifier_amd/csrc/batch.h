@@ -113,6 +113,15 @@ struct ResultsLayout {
     size_t status() const { return 144 * G; }
     size_t total() const { return 144 * G + 4 * n; }
 };
+
+// Where a batch is in its life.  An operation sets the stage as its last step, once it has succeeded; a failed upload, launch, finish or
+// fold leaves the batch Empty, and the calls that need an upload or a launch refuse it until an upload succeeds.
+enum class BatchStage { Empty, Uploaded, Launched, Finished };
+struct LaunchRecord {           // what the last launch (or fold) left (close_enqueue)
+    bool pairing = false;       // its pairing checks were enqueued: the `ok` words are its verdicts
+    bool pieces = false;        // no pairing, accumulators in pieces only: acc / out_bytes are put together on demand (ensure_whole)
+    bool tail_on_aux = false;   // whatever the stage: its whole accumulators, their bytes and the result copy are still on the auxiliary stream (join_tail)
+};
 }  // namespace h2v
 
 struct h2v_batch {
@@ -124,14 +133,13 @@ struct h2v_batch {
     // h2v_batch_upload_launch: the host -> device copies run on `copy`, chunk by chunk, each followed (after the blocking copy has
     // returned) by the decompression of that chunk on `stream`
     hipStream_t copy = nullptr;
-    bool decompressed = false;        // the next launch finds its points already decompressed (set by h2v_batch_upload_launch)
+    h2v::BatchStage stage = h2v::BatchStage::Empty;
+    bool decompressed = false;        // Uploaded: the upload has decompressed the points already (h2v_batch_upload_launch)
+    h2v::LaunchRecord last;
     size_t max_proofs = 0, max_inst = 0;
     h2v::PlanDevice* plan = nullptr;  // set at upload (depends on the instance shape)
     uint32_t n = 0, n_tail = 0;
     uint32_t groups = 1;              // independent accumulator batches inside this launch (h2v_batch_set_groups)
-    const h2v::Fr* ext_mult = nullptr; const uint32_t* ext_idx = nullptr;   // multipliers gathered from a larger sequence (h2v_verify_batch_shapes)
-    bool launched = false, with_pairing = false;
-    bool finished = false;            // the last launch has been finished (h2v_batch_finish*) and nothing was uploaded or launched since: h2v_batch_recheck may read it
     std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
     // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
     h2v::DevBuf<uint8_t> proofs, inst, tail;
@@ -141,7 +149,6 @@ struct h2v_batch {
     h2v::DevBuf<uint32_t> msm_scal; h2v::DevBuf<h2v::Fr> shared; h2v::DevBuf<uint32_t> left_scal;
     h2v::DevBuf<h2v::Fr> insteval;    // [query][proof] (wide instance vectors)
     h2v::DevBuf<uint32_t> guard_scal; // [proof][guard term][8] (h2v_guard_msm with GWC)
-    bool want_guard = false;          // the next upload takes the guard variant of the plan
     h2v::DevBuf<h2v::G1J> acc;        // per group: [2g] left, [2g+1] right
     // the results block (h2v::ResultsLayout) on the device and in pinned host memory; the pointers below point into it for the upload's group count
     h2v::DevBuf<uint8_t> results; h2v::MappedHostBuf results_host;
@@ -152,8 +159,6 @@ struct h2v_batch {
     h2v::MsmWorkspace ws;
     h2v::Recheck recheck;             // h2v_batch_recheck's own workspace and outputs
     h2v::MsmSplit split;              // how the last launch left its accumulators to the pairing (parts == 0: whole points in acc)
-    bool acc_stale = false;           // a launch without a pairing left pieces only: acc / out_bytes are put together on demand (ensure_whole)
-    bool tail_on_aux = false;         // the last launch's whole accumulators, their bytes and the result copy are still the auxiliary stream's business (close_enqueue): join_tail before the main stream touches them
     h2v::DevBuf<uint8_t> line_ws;     // k_pair_lines' output, H2V_PAIRING_LINE_WS_BYTES per group
     uint32_t stream_words = 0;
     // profiling

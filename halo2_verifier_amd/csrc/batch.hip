@@ -5,6 +5,7 @@
 #include <string.h>
 #include <algorithm>
 #include <map>
+#include <utility>
 #include <stdio.h>
 
 using namespace h2v;
@@ -73,6 +74,7 @@ bool scalar_is_canonical(const uint8_t* s) {
     for (int j = 0; j < 8; ++j) raw[j] = (uint32_t)s[4 * j] | ((uint32_t)s[4 * j + 1] << 8) | ((uint32_t)s[4 * j + 2] << 16) | ((uint32_t)s[4 * j + 3] << 24);
     return !Fr::geq_p(raw);
 }
+bool scalar_is_zero(const uint8_t* s) { for (int k = 0; k < 32; ++k) if (s[k]) return false; return true; }
 
 // Fr::random(getrandom_or_panic()) of AccumulatorStrategy::process (kzg/strategy.rs:129): 64 OS-random bytes reduced mod r
 int os_random_scalars(std::vector<uint8_t>& out, size_t n) {
@@ -90,49 +92,80 @@ int os_random_scalars(std::vector<uint8_t>& out, size_t n) {
     return 0;
 }
 
+// The draws of a call: the caller's `rand32` (n scalars, refused unless canonical) or, when it is null, n OS draws kept in `storage`.
+// `nonzero`: a zero draw of the caller's is refused and an OS draw of zero is drawn again.
+int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false) {
+    int rc;
+    std::vector<uint8_t> one;
+    if (!rand32) {
+        if ((rc = os_random_scalars(storage, n))) return rc;
+        for (size_t i = 0; nonzero && i < n; ++i)   // (an OS draw of zero: probability 2^-254)
+            while (scalar_is_zero(&storage[32 * i])) { if ((rc = os_random_scalars(one, 1))) return rc; memcpy(&storage[32 * i], one.data(), 32); }
+        rand32 = storage.data();
+        return 0;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (nonzero && scalar_is_zero(rand32 + 32 * i)) { set_last_error(std::string(who) + ": a draw in rand32 is zero"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!scalar_is_canonical(rand32 + 32 * i)) { set_last_error(std::string(who) + ": rand32 scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    return 0;
+}
+
+// A call made from a stage it does not accept: every call accepts the stages from `least` on
+int require_stage(const h2v_batch* b, BatchStage least, const char* who) {
+    if (b && b->stage >= least) return 0;
+    static const char* const missing[] = {"", "nothing uploaded since the last failed call or set_groups", "nothing launched", "no finished launch"};
+    set_last_error(std::string(who) + ": " + (b ? missing[(int)least] : "null argument"));
+    return H2V_ERR_BAD_ARGUMENT;
+}
+
+// The stage an operation leaves: Empty on every way out but its last step, commit(its stage of success).  (b may be null.)
+struct StageCommit {
+    h2v_batch* b;
+    ~StageCommit() { if (b) b->stage = BatchStage::Empty; }
+    void commit(BatchStage st) { b->stage = st; b = nullptr; }
+};
+
 int join_tail(h2v_batch* b);
 // `overlap`: the copies run on the batch's copy stream in chunks and the decompression of every chunk is enqueued on the batch's own
 // stream behind that chunk's event (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
+// `guard`: the guard variant of the plan (h2v_guard_msm)
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
-                const uint8_t* rand_tail, size_t n_tail, bool overlap = false) {
+                const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false) {
+    StageCommit commit{b};
     if (!b || (n && !proofs_flat)) { set_last_error("h2v_batch_upload: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (n > b->max_proofs) { set_last_error("h2v_batch_upload: n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
     h2v_ctx* ctx = b->ctx;
-    { H2V_HIP_CHECK(hipSetDevice(ctx->device)); int rcj = join_tail(b); if (rcj) return rcj; }
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
     if (ncols != ctx_total_instance_columns(ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }  // lib.rs:51-55
-    std::vector<size_t> lens(col_lens, col_lens + ncols);
     PlanPin pin(ctx);
-    int rc = pin.get(lens, b->want_guard);
+    int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols), guard);
     if (rc) return rc;
-    PlanDevice* pd = pin.pd;
-    const Plan& pl = pd->host;
+    const Plan& pl = pin.pd->host;
     if (proof_len < pl.proof_len) { set_last_error("h2v_batch_upload: proof_len is shorter than this VK's proof"); return H2V_ERR_BAD_ARGUMENT; }
     if (pl.n_instance_values && n && !instances_flat) { set_last_error("h2v_batch_upload: instances missing"); return H2V_ERR_BAD_ARGUMENT; }
     if (rand_tail && n_tail < n) { set_last_error("h2v_batch_upload: n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->groups > 1 && (n % b->groups || (rand_tail && n_tail % b->groups))) { set_last_error("h2v_batch_upload: n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
-    H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = ensure_buffers(b, pl))) return rc;
-    if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
-    b->plan = pin.take(); b->n = (uint32_t)n; b->launched = false; b->finished = false; b->decompressed = false;
     std::vector<uint8_t> os_rand;
-    if (!rand_tail) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand_tail = os_rand.data(); n_tail = n; }
-    for (size_t i = 0; i < n_tail; ++i) if (!scalar_is_canonical(rand_tail + 32 * i)) { set_last_error("h2v_batch_upload: rand32 scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!rand_tail) n_tail = n;
+    if ((rc = resolve_draws(rand_tail, n_tail, os_rand, "h2v_batch_upload"))) return rc;
+    // every argument is valid: from here on the batch takes the upload
+    if ((rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
+    if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
+    b->plan = pin.take(); b->n = (uint32_t)n;
+    const PlanDevice* pd = b->plan;
     // a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs
     b->zero_below.assign(b->groups, 0);
     if (n) {
         const size_t G = b->groups, gs = n / G, nt = n_tail / G;
         for (size_t g = 0; g < G; ++g)
-            for (size_t j = nt; j-- > 1;) {
-                uint64_t w[4];
-                memcpy(w, rand_tail + 32 * (g * nt + j), 32);
-                if (!(w[0] | w[1] | w[2] | w[3])) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
-            }
+            for (size_t j = nt; j-- > 1;)
+                if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
     }
     if ((rc = b->tail.reserve(32 * n_tail))) return rc;
     b->n_tail = (uint32_t)n_tail;
     hipStream_t s = b->stream;
-    if (!n) { H2V_HIP_CHECK(hipStreamSynchronize(s)); return 0; }
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
         if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs.p + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
         else H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + p0 * pl.proof_len, pl.proof_len, proofs_flat + p0 * proof_len, proof_len, pl.proof_len, p1 - p0, hipMemcpyHostToDevice, cs));
@@ -146,11 +179,6 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
         return 0;
     };
-    if (!overlap) {
-        if ((rc = copy_proofs(s, 0, n)) || (rc = copy_rest(s))) return rc;
-        H2V_HIP_CHECK(hipStreamSynchronize(s));  // the host buffers are the caller's again
-        return 0;
-    }
     // Overlapped form (h2v_batch_upload_launch).  What was measured on the way (profiles/r03_h2d_microbench.txt, r03_upload_timeline.txt):
     //  * a 26 MB copy takes 0.47 ms from pageable and from pinned memory alike, and an "asynchronous" copy out of pageable memory
     //    returns only when the data is on the device — the calling thread is the one thing it blocks;
@@ -173,18 +201,18 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     }
     size_t point_bytes = 0;
     for (auto& r : runs) point_bytes += r.second;
-    int mode = ctx->tuning.upload_mode;
+    int mode = overlap ? ctx->tuning.upload_mode : 3;
     if (mode == 0) mode = 1;   // (one launch + finish, best of 15, tools/h2d_probe.py: resident 2.98 ms, points-first 3.29, two halves 3.33, plain 3.47;
                                //  in the benchmark's loop, PCIe-inclusive over resident: 0.905 / 0.885 / 0.835, tools/r03_ab.sh)
     if (mode == 1 && (runs.size() > 4 || 2 * point_bytes > pl.proof_len)) mode = 3;   // points all over the proof, or most of it: nothing to gain
     if (n < 2048) mode = 3;                                                           // a copy of a megabyte or two is not worth two launches
     if (mode == 3) {
-        if ((rc = copy_proofs(s, 0, n)) || (rc = copy_rest(s))) return rc;
-        H2V_HIP_CHECK(hipStreamSynchronize(s));
-        return 0;
+        if (n && ((rc = copy_proofs(s, 0, n)) || (rc = copy_rest(s)))) return rc;
+        H2V_HIP_CHECK(hipStreamSynchronize(s));  // the host buffers are the caller's again
+    } else {
+        if (!b->copy) H2V_HIP_CHECK(hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking));
+        H2V_HIP_CHECK(hipStreamSynchronize(s));   // an earlier launch of this batch may still read the buffers (normally long finished: h2v_batch_finish)
     }
-    if (!b->copy) H2V_HIP_CHECK(hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking));
-    H2V_HIP_CHECK(hipStreamSynchronize(s));   // an earlier launch of this batch may still read the buffers (normally long finished: h2v_batch_finish)
     if (mode == 2) {
         // the proofs in two halves: [first half] -> its decompression is enqueued -> [second half, instances, draws] travel while the GPU
         // decompresses the first -> the second half's decompression.  Two rounds of the decompression kernel at half occupancy take about
@@ -199,19 +227,19 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         H2V_HIP_CHECK(hipStreamSynchronize(b->copy));   // everything is on the device; the host buffers are the caller's again
         if ((rc = decompress_range_enqueue(s, g, (uint32_t)half, (uint32_t)n))) return rc;
         if ((rc = decompress_finish_enqueue(s, g))) return rc;
-        b->decompressed = true;
-        return 0;
+    } else if (mode != 3) {   // (1)
+        for (auto& r : runs) H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + r.first, pl.proof_len, proofs_flat + r.first, proof_len, r.second, n, hipMemcpyHostToDevice, b->copy));
+        H2V_HIP_CHECK(hipStreamSynchronize(b->copy));
+        StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
+        if ((rc = decompress_begin_enqueue(s, g))) return rc;
+        if ((rc = decompress_range_enqueue(s, g, 0, (uint32_t)n))) return rc;
+        // (the whole proofs again, point bytes included: identical bytes over the ones the kernel is reading)
+        if ((rc = copy_proofs(b->copy, 0, n)) || (rc = copy_rest(b->copy))) return rc;
+        H2V_HIP_CHECK(hipStreamSynchronize(b->copy));   // everything is on the device; the host buffers are the caller's again
+        if ((rc = decompress_finish_enqueue(s, g))) return rc;
     }
-    for (auto& r : runs) H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + r.first, pl.proof_len, proofs_flat + r.first, proof_len, r.second, n, hipMemcpyHostToDevice, b->copy));
-    H2V_HIP_CHECK(hipStreamSynchronize(b->copy));
-    StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
-    if ((rc = decompress_begin_enqueue(s, g))) return rc;
-    if ((rc = decompress_range_enqueue(s, g, 0, (uint32_t)n))) return rc;
-    // (the whole proofs again, point bytes included: identical bytes over the ones the kernel is reading)
-    if ((rc = copy_proofs(b->copy, 0, n)) || (rc = copy_rest(b->copy))) return rc;
-    H2V_HIP_CHECK(hipStreamSynchronize(b->copy));   // everything is on the device; the host buffers are the caller's again
-    if ((rc = decompress_finish_enqueue(s, g))) return rc;
-    b->decompressed = true;
+    b->decompressed = mode != 3;
+    commit.commit(BatchStage::Uploaded);
     return 0;
 }
 
@@ -241,8 +269,11 @@ void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_
     pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
 }
 
-int launch_impl(h2v_batch* b, int with_pairing) {
-    if (!b || !b->plan) { set_last_error("h2v_batch_launch: nothing uploaded"); return H2V_ERR_BAD_ARGUMENT; }
+// ext_mult / ext_idx: the multipliers of a non-contiguous subset of a larger accumulation (h2v_verify_batch_shapes), instead of the draws'
+int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr) {
+    int rc;
+    if ((rc = require_stage(b, BatchStage::Uploaded, "h2v_batch_launch"))) return rc;
+    StageCommit commit{b};
     h2v_ctx* ctx = b->ctx;
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     PlanDevice* pd = b->plan;
@@ -250,8 +281,6 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     hipStream_t s = b->stream;
     uint32_t n = b->n;
     const uint32_t G = b->groups, gs = n / G;
-    b->with_pairing = with_pairing != 0; b->launched = true; b->finished = false;
-    int rc;
     if ((rc = join_tail(b))) return rc;
     int ev = 0;
     auto mark = [&]() { if (b->profiling >= 2) hipEventRecord(b->ev[ev], s); ++ev; };   // (an event record is a barrier packet: ~6 us of idle stream each)
@@ -260,7 +289,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     // stage 1: point decompression + canonicity checks (already on the stream, behind its chunked upload, after h2v_batch_upload_launch);
     // stage 2: absorbed stream, Blake2b challenges, batch multipliers.  The status words are cleared first, then the auxiliary stream is
     // forked: the scalar canonicity check (proof bytes only) runs there beside the decompression, with the multipliers
-    const bool run_decompress = !b->decompressed;
+    const bool run_decompress = !(b->stage == BatchStage::Uploaded && b->decompressed);   // (a relaunch of the same upload runs it again)
     // cleared per launch: fold_failed (set by h2v_batch_fold_check_enqueue only) and — unless the upload already did (h2v_batch_upload_launch) —
     // the status words.  The results block is [ok][fold_failed][out_ident][out_bytes][status]: one fill from fold_failed to the last status word
     // (the output bytes in between are written later in the launch) instead of two
@@ -269,7 +298,6 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     else H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, 4 * (size_t)G, s));   // (its G words)
     H2V_HIP_CHECK(hipEventRecord(b->ev_fork0, s));   // everything enqueued before this point (uploads, the cleared status words) is visible to the auxiliary stream
     if (run_decompress && (rc = decompress_range_enqueue(s, g, 0, n))) return rc;
-    b->decompressed = false;   // (a later h2v_batch_launch on the same upload runs the stage again: every launch does all of its work)
     mark();
     if ((rc = transcript_stage_enqueue(s, g))) return rc;
     // both channels of every group in one set of launches: [2g] left, [2g+1] right (channel_problems), the group's folded VK-wide
@@ -283,9 +311,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
         H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork0, 0));
         hipStream_t sm = b->aux;
         if (run_decompress && (rc = decompress_finish_enqueue(sm, g))) return rc;   // k_check_scalars
-        // multipliers: suffix products of the uploaded draws — or, for a batch that is a non-contiguous subset of a larger
-        // accumulation (h2v_verify_batch_shapes), gathered from the multipliers of the whole sequence
-        if (b->ext_mult) { if ((rc = gather_multipliers_enqueue(sm, b->ext_mult, b->ext_idx, n, b->mult.p))) return rc; }
+        if (ext_mult) { if ((rc = gather_multipliers_enqueue(sm, ext_mult, ext_idx, n, b->mult.p))) return rc; }
         else if ((rc = multipliers_enqueue(sm, b->tail.p, b->n_tail, n, G, b->mult.p))) return rc;
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
         if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, sm));
@@ -331,6 +357,7 @@ int launch_impl(h2v_batch* b, int with_pairing) {
     mark();
     if ((rc = close_enqueue(b, with_pairing != 0))) return rc;
     mark();
+    commit.commit(BatchStage::Launched);
     return 0;
 }
 
@@ -342,9 +369,9 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
     hipStream_t s = b->stream;
     const uint32_t G = b->groups;
     int rc;
-    b->acc_stale = false;
+    b->last.pairing = with_pairing; b->last.pieces = false;
     if (!with_pairing) {
-        if (b->split.parts) { b->acc_stale = true; return 0; }   // pieces only for now
+        if (b->split.parts) { b->last.pieces = true; return 0; }   // pieces only for now
         return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
     }
     H2V_HIP_CHECK(hipEventRecord(b->ev_fork, s));
@@ -360,25 +387,25 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
     if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), static_cast<uint8_t*>(b->results_host.dev) + L.fold_failed(), (L.total() - L.fold_failed()) / 4,
                                  H2V_AUX_LDS_RESERVE))) return rc;
     H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
-    b->tail_on_aux = true;
+    b->last.tail_on_aux = true;
     if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
     else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc.p, G, b->ok))) return rc;
     return 0;
 }
 // the main stream waits for what the last launch left on the auxiliary stream (before anything new reads or overwrites it)
 int join_tail(h2v_batch* b) {
-    if (!b->tail_on_aux) return 0;
-    b->tail_on_aux = false;
+    if (!b->last.tail_on_aux) return 0;
+    b->last.tail_on_aux = false;
     H2V_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_join, 0));
     return 0;
 }
 // the whole accumulators (acc) and their affine bytes, if the last launch left pieces only
 int ensure_whole(h2v_batch* b) {
-    if (!b->acc_stale) return 0;
+    if (!b->last.pieces) return 0;
     int rc;
     if ((rc = msm_combine_enqueue(b->stream, b->ws, b->split))) return rc;
     if ((rc = point_to_bytes_enqueue(b->stream, b->acc.p, b->out_bytes, b->out_ident, 2 * b->groups))) return rc;
-    b->acc_stale = false;
+    b->last.pieces = false;
     return 0;
 }
 // the batch's accumulator records (pieces if the launch left pieces)
@@ -389,17 +416,18 @@ int export_batch_records(h2v_batch* b, void* device_dst) {
 }
 
 // group_ok / out_left / out_right hold one entry (64 bytes) per group
-int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left, uint8_t* out_right) {
-    if (!b || !b->launched) { set_last_error("h2v_batch_finish: nothing launched"); return H2V_ERR_BAD_ARGUMENT; }
+int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group_ok, uint8_t* out_left, uint8_t* out_right) {
+    if (int rc = require_stage(b, BatchStage::Launched, who)) return rc;
+    StageCommit commit{b};
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     hipStream_t s = b->stream;
     const uint32_t n = b->n, G = b->groups, gs = n / G;
     { int rcw = ensure_whole(b); if (rcw) return rcw; }
     const ResultsLayout L{G, n};
     hipError_t e;
-    if (b->tail_on_aux) {
+    if (b->last.tail_on_aux) {
         // a launch that ended in its own pairing checks: the block is on its way on the auxiliary stream, the verdicts come from the kernel
-        b->tail_on_aux = false;
+        b->last.tail_on_aux = false;
         e = hipStreamSynchronize(s);
         if (e == hipSuccess) e = hipStreamSynchronize(b->aux);   // (not hipEventSynchronize on its last event: that wait goes through the runtime's event thread, and a host that re-uploads per launch lost 40 % to it)
     } else {
@@ -438,16 +466,16 @@ int finish_impl(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out
     }
     for (uint32_t g = 0; g < G; ++g) {
         // a sharded group is accepted only if no shard reported a failed proof (their terms are zeroed out of the accumulators)
-        if (group_ok) group_ok[g] = (all_ok[g] && !foldf[g] && (!b->with_pairing || okv[g])) ? 1 : 0;
+        if (group_ok) group_ok[g] = (all_ok[g] && !foldf[g] && (!b->last.pairing || okv[g])) ? 1 : 0;
         if (out_left) memcpy(out_left + 64 * (size_t)g, &outb[128 * (size_t)g], 64);
         if (out_right) memcpy(out_right + 64 * (size_t)g, &outb[128 * (size_t)g + 64], 64);
     }
-    b->finished = true;
+    commit.commit(BatchStage::Finished);
     return 0;
 }
 // the verdict of group g's own pairing check in the last finished launch (finish_impl folds the statuses into group_ok; this is the pairing alone)
 bool pairing_passed(const h2v_batch* b, uint32_t g) {
-    return b->with_pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
+    return b->last.pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
 }
 
 // Range re-checks (h2v_batch_recheck).  A range [first, first + count) of group g is checked as the launch checks the whole group:
@@ -456,8 +484,9 @@ bool pairing_passed(const h2v_batch* b, uint32_t g) {
 // launch left (ws, acc, split, the result block) is touched: the re-check has its own workspace and outputs (b->recheck).
 // At most MSM_MAX_PROBLEMS / 2 ranges, and about the launch's own term count, go into one set of launches.
 int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
-    if (!b || (n_ranges && (!first || !count || !range_ok))) { set_last_error("h2v_batch_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (!b->finished || !b->plan) { set_last_error("h2v_batch_recheck: no finished launch to re-check"); return H2V_ERR_BAD_ARGUMENT; }
+    int rc;
+    if ((rc = require_stage(b, BatchStage::Finished, "h2v_batch_recheck"))) return rc;
+    if (n_ranges && (!first || !count || !range_ok)) { set_last_error("h2v_batch_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     const Plan& pl = b->plan->host;
     const uint32_t n = b->n, G = b->groups, gs = n / G, np = pl.n_points, ns = pl.n_shared;
     for (size_t i = 0; i < n_ranges; ++i) {
@@ -472,7 +501,6 @@ int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_
     if (!n_ranges) return 0;
     h2v_ctx* ctx = b->ctx;
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc;
     if ((rc = join_tail(b))) return rc;
     hipStream_t s = b->stream;
     Recheck& rk = b->recheck;
@@ -524,26 +552,32 @@ int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_
     return 0;
 }
 
-// one-shot calls reuse a batch object kept in the context (up to H2V_SCRATCH_BATCH_MAX proofs of capacity)
+// A one-shot call's hold on its context: ctx->mu (the context's stream and scratch batch serve one call at a time) and, once taken, the
+// scratch batch, given back at the end of the call — or destroyed if it holds more than H2V_SCRATCH_BATCH_MAX proofs.  (After an error it is Empty.)
 #define H2V_SCRATCH_BATCH_MAX 1024u
-int scratch_batch_take(h2v_ctx* ctx, size_t capacity, size_t max_inst, h2v_batch** out) {
-    h2v_batch* b = ctx->scratch_batch;
-    ctx->scratch_batch = nullptr;
-    if (b && (b->max_proofs < capacity || b->max_inst < max_inst)) { h2v_batch_destroy(b); b = nullptr; }
-    if (!b) { int rc = h2v_batch_create(ctx, capacity, max_inst, &b); if (rc) return rc; }
-    *out = b;
-    return 0;
-}
-void scratch_batch_give(h2v_ctx* ctx, h2v_batch* b) {
-    if (!b) return;
-    if (b->max_proofs > H2V_SCRATCH_BATCH_MAX || ctx->scratch_batch) { h2v_batch_destroy(b); return; }
-    ctx->scratch_batch = b;
-}
+struct ScratchBatch {
+    h2v_ctx* const ctx;
+    std::lock_guard<std::mutex> lock;
+    h2v_batch* b = nullptr;
+    explicit ScratchBatch(h2v_ctx* c) : ctx(c), lock(c->mu) {}
+    ~ScratchBatch() { if (b && b->max_proofs <= H2V_SCRATCH_BATCH_MAX && !ctx->scratch_batch) ctx->scratch_batch = b; else h2v_batch_destroy(b); }
+    int take(size_t capacity, size_t max_inst) {   // the context's batch, or a new one if it has none or a smaller one (once per holder)
+        b = std::exchange(ctx->scratch_batch, nullptr);
+        if (b && (b->max_proofs < capacity || b->max_inst < max_inst)) { h2v_batch_destroy(b); b = nullptr; }
+        return b ? 0 : h2v_batch_create(ctx, capacity, max_inst, &b);
+    }
+};
 
-// pack pointer-array proofs / instances into the flat layout; proofs shorter than the VK's proof are
-// the reader running dry: "failed to fill whole buffer" -> Error::Transcript, or Opening inside the multi-open part
-int pack_inputs(const Plan& pl, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
-                std::vector<uint8_t>& flat, std::vector<uint8_t>& iflat, std::vector<int>& forced) {
+// The argument checks of a one-shot call over one instance shape, its plan (in `pin`), and its pointer-array proofs / instances packed
+// into the flat layout; proofs shorter than the VK's proof are the reader running dry: "failed to fill whole buffer" -> Error::Transcript,
+// or Opening inside the multi-open part
+int pack_inputs(PlanPin& pin, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
+                const size_t* col_lens, std::vector<uint8_t>& flat, std::vector<uint8_t>& iflat, std::vector<int>& forced) {
+    if ((n && (!proofs || !proof_lens)) || (ncols && !col_lens)) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!pin.ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+    if (ncols != ctx_total_instance_columns(pin.ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
+    if (int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols))) return rc;
+    const Plan& pl = pin.pd->host;
     const size_t per_inst = (size_t)pl.n_instance_values * 32;
     flat.assign(n * pl.proof_len, 0); iflat.assign(n * per_inst, 0); forced.assign(n, 0);
     // byte offset where the multi-open part starts: h1 is the first point after all scalars
@@ -561,65 +595,25 @@ int pack_inputs(const Plan& pl, size_t n, const uint8_t* const* proofs, const si
     return 0;
 }
 
-int pack_and_run(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
-                 const size_t* col_lens, const uint8_t* rand32, bool single, int with_pairing, int* per_proof_status, int* batch_ok, uint8_t* out_left,
-                 uint8_t* out_right, h2v_batch** keep, bool guard = false) {
-    if (!ctx || (n && (!proofs || !proof_lens)) || (ncols && !col_lens)) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ncols != ctx_total_instance_columns(ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
-    std::lock_guard<std::mutex> lock(ctx->mu);   // one one-shot call per context at a time (it owns the context's scratch batch)
-    std::vector<size_t> lens(col_lens, col_lens + ncols);
-    PlanPin pin(ctx);
-    int rc = pin.get(lens);
-    if (rc) return rc;
+// One AccumulatorStrategy batch of a one-shot call, run on the context's scratch batch; the batch stays in `sb` for the caller
+int pack_and_run(ScratchBatch& sb, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
+                 const size_t* col_lens, const uint8_t* rand32, int with_pairing, bool guard, int* per_proof_status, int* batch_ok, uint8_t* out_left,
+                 uint8_t* out_right) {
+    PlanPin pin(sb.ctx);
+    std::vector<uint8_t> flat, iflat; std::vector<int> forced;
+    int rc;
+    if ((rc = pack_inputs(pin, n, proofs, proof_lens, instances32, ncols, col_lens, flat, iflat, forced))) return rc;
     const Plan& pl = pin.pd->host;
-    size_t per_inst = (size_t)pl.n_instance_values * 32;
-    std::vector<uint8_t> flat, iflat;
-    std::vector<int> forced;
-    if ((rc = pack_inputs(pl, n, proofs, proof_lens, instances32, flat, iflat, forced))) return rc;
-    h2v_batch* b = nullptr;
-    if (single) {
-        // SingleStrategy (kzg/strategy.rs:143-181) = an accumulator of ONE proof with multiplier 1 and its own pairing: run the
-        // proofs as one-proof groups of grouped launches, at most MSM_MAX_PROBLEMS / 2 per launch
-        const size_t per = MSM_MAX_PROBLEMS / 2;
-        if ((rc = scratch_batch_take(ctx, std::min(n ? n : 1, per), pl.n_instance_values, &b))) return rc;
-        b->want_guard = false;
-        bool all = true;
-        for (size_t off = 0; off < n && !rc; off += per) {
-            const size_t m = std::min(per, n - off);
-            std::vector<uint8_t> ones(32 * m, 0);
-            for (size_t i = 0; i < m; ++i) ones[32 * i] = 1;
-            std::vector<int> st(m, 0), gok(m, 0);
-            if ((rc = h2v_batch_set_groups(b, m))) break;
-            if ((rc = upload_impl(b, m, flat.data() + off * pl.proof_len, pl.proof_len, iflat.data() + off * per_inst, ncols, col_lens, ones.data(), m))) break;
-            if ((rc = launch_impl(b, 1))) break;
-            if ((rc = finish_impl(b, st.data(), gok.data(), nullptr, nullptr))) break;
-            for (size_t i = 0; i < m; ++i) {
-                int v = forced[off + i] ? forced[off + i] : st[i];
-                if (v == 0 && !gok[i]) v = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;  // kzg/strategy.rs:171-175
-                if (per_proof_status) per_proof_status[off + i] = v;
-                if (v != 0) all = false;
-            }
-        }
-        if (batch_ok && !rc) *batch_ok = all ? 1 : 0;
-        scratch_batch_give(ctx, b);
-        return rc;
-    }
-    if ((rc = scratch_batch_take(ctx, n ? n : 1, pl.n_instance_values, &b))) return rc;
-    if ((rc = h2v_batch_set_groups(b, 1))) { h2v_batch_destroy(b); return rc; }
-    b->want_guard = guard;
-    do {
-        if ((rc = upload_impl(b, n, flat.data(), pl.proof_len, iflat.data(), ncols, col_lens, rand32, rand32 ? n : 0))) break;
-        if ((rc = launch_impl(b, with_pairing))) break;
-        std::vector<int> st(n ? n : 1, 0);
-        int ok = 0;
-        if ((rc = finish_impl(b, st.data(), &ok, out_left, out_right))) break;
-        for (size_t i = 0; i < n; ++i) if (forced[i]) { st[i] = forced[i]; ok = 0; }
-        if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
-        if (batch_ok) *batch_ok = ok;
-    } while (0);
-    if (keep && !rc) *keep = b; else scratch_batch_give(ctx, b);
-    return rc;
+    if ((rc = sb.take(n ? n : 1, pl.n_instance_values)) || (rc = h2v_batch_set_groups(sb.b, 1))) return rc;
+    if ((rc = upload_impl(sb.b, n, flat.data(), pl.proof_len, iflat.data(), ncols, col_lens, rand32, rand32 ? n : 0, false, guard)) ||
+        (rc = launch_impl(sb.b, with_pairing))) return rc;
+    std::vector<int> st(n ? n : 1, 0);
+    int ok = 0;
+    if ((rc = finish_impl(sb.b, "h2v_batch_finish", st.data(), &ok, out_left, out_right))) return rc;
+    for (size_t i = 0; i < n; ++i) if (forced[i]) { st[i] = forced[i]; ok = 0; }
+    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
+    if (batch_ok) *batch_ok = ok;
+    return 0;
 }
 
 // The search of h2v_verify_batch_identify, measured at 1024 proofs (tools/identify_probe.py): every failing range is cut into
@@ -743,29 +737,28 @@ int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t 
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
                             const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail, int with_pairing) {
-    int rc = upload_impl(b, n, proofs_flat, proof_len, instances_flat, n_instance_columns, col_lens, rand32_tail, n_tail, true);
-    if (rc) return rc;
+    if (int rc = upload_impl(b, n, proofs_flat, proof_len, instances_flat, n_instance_columns, col_lens, rand32_tail, n_tail, true)) return rc;
     return launch_impl(b, with_pairing);
 }
 int h2v_batch_finish(h2v_batch* b, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
     if (b && b->groups > 1) { set_last_error("h2v_batch_finish: the batch is grouped, use h2v_batch_finish_groups"); return H2V_ERR_BAD_ARGUMENT; }
-    return finish_impl(b, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    return finish_impl(b, "h2v_batch_finish", per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
 int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (!b || !groups || groups > MSM_MAX_PROBLEMS / 2 || groups > b->max_proofs) { set_last_error("h2v_batch_set_groups: bad group count"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    b->groups = (uint32_t)groups; b->launched = false; b->finished = false;  // the next upload grows the buffers if the group count needs more
+    b->groups = (uint32_t)groups; b->stage = BatchStage::Empty;  // the next upload grows the buffers if the group count needs more
     return 0;
 }
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups) {
     if (!b || n_groups != b->groups) { set_last_error("h2v_batch_finish_groups: n_groups does not match h2v_batch_set_groups"); return H2V_ERR_BAD_ARGUMENT; }
-    return finish_impl(b, per_proof_status, group_ok, out_left_xy, out_right_xy);
+    return finish_impl(b, "h2v_batch_finish_groups", per_proof_status, group_ok, out_left_xy, out_right_xy);
 }
 int h2v_batch_accumulators(h2v_batch* b, void** device_ptr, size_t* nbytes) {
     if (!b || !b->acc.p || !device_ptr) { set_last_error("h2v_batch_accumulators: nothing uploaded"); return H2V_ERR_BAD_ARGUMENT; }
-    if (b->launched) { H2V_HIP_CHECK(hipSetDevice(b->ctx->device)); int rcw = join_tail(b); if (!rcw) rcw = ensure_whole(b); if (rcw) return rcw; }
+    if (b->stage >= BatchStage::Launched) { H2V_HIP_CHECK(hipSetDevice(b->ctx->device)); int rcw = join_tail(b); if (!rcw) rcw = ensure_whole(b); if (rcw) return rcw; }
     *device_ptr = b->acc.p;
     if (nbytes) *nbytes = 2 * sizeof(G1J) * b->groups;   // raw points, no failure word: see h2v_batch_export_accumulators
     return 0;
@@ -780,14 +773,17 @@ int h2v_batch_set_stream(h2v_batch* b, void* hip_stream) {
     return join_tail(b);   // (the new stream waits for what the last launch left on the auxiliary stream)
 }
 int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
-    if (!b || !b->launched || !device_dst) { set_last_error("h2v_batch_export_accumulators: nothing launched"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rc = require_stage(b, BatchStage::Launched, "h2v_batch_export_accumulators")) return rc;
+    if (!device_dst) { set_last_error("h2v_batch_export_accumulators: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     return export_batch_records(b, device_dst);
 }
 int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, size_t n_parts) {
-    if (!b || !b->launched || !device_accumulators || !n_parts) { set_last_error("h2v_batch_fold_check_enqueue: bad argument"); return H2V_ERR_BAD_ARGUMENT; }
-    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     int rc;
+    if ((rc = require_stage(b, BatchStage::Launched, "h2v_batch_fold_check_enqueue"))) return rc;
+    StageCommit commit{b};
+    if (!device_accumulators || !n_parts) { set_last_error("h2v_batch_fold_check_enqueue: bad argument"); return H2V_ERR_BAD_ARGUMENT; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     if ((rc = join_tail(b))) return rc;
     const uint32_t G = b->groups;
     // the fold keeps the cut of this rank's own launch: records cut the same way add up piece by piece, the pairing takes the pieces
@@ -797,7 +793,7 @@ int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, 
         if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, b->split.parts, b->split.shift, b->acc.p, pieces, ready, b->fold_failed))) return rc;
     } else if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, 1, 0, b->acc.p, nullptr, nullptr, b->fold_failed))) return rc;
     if ((rc = close_enqueue(b, true))) return rc;
-    b->with_pairing = true;
+    commit.commit(b->stage);   // (a launch folded after its finish stays Finished)
     return 0;
 }
 int h2v_batch_set_profiling(h2v_batch* b, int level) { if (!b) return H2V_ERR_BAD_ARGUMENT; b->profiling = level == 0 ? 0 : (level == H2V_PROFILE_KERNEL ? 1 : 2); return 0; }
@@ -836,7 +832,9 @@ int h2v_fold_check(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts
 
 int h2v_verify_batch(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
                      const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    return pack_and_run(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, false, 1, per_proof_status, batch_ok, out_left_xy, out_right_xy, nullptr);
+    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    ScratchBatch sb(ctx);
+    return pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
 
 // AccumulatorStrategy::with(msm_accumulator) (kzg/strategy.rs:75-78): the strategy starts from an existing DualMSM — the
@@ -855,10 +853,10 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     if (n_seed_left > (1u << 24) || n_seed_right > (1u << 24)) { set_last_error("h2v_verify_batch_seeded: seed too large"); return H2V_ERR_BAD_ARGUMENT; }
     int rc;
     std::vector<uint8_t> os_rand;
-    if (!rand32 && n) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand32 = os_rand.data(); }
+    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_seeded"))) return rc;
     // the product of this call's draws, and the seed's scalars times it (host: a few hundred Fr products)
     Fr M = Fr::one();
-    for (size_t i = 0; i < n; ++i) { Fr r; if (!Fr::from_bytes(rand32 + 32 * i, r)) { set_last_error("h2v_verify_batch_seeded: rand32 scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; } M = M * r; }
+    for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
     std::vector<uint8_t> sc[2];
     const uint8_t* in_s[2] = {seed_left_scalars32, seed_right_scalars32};
     const size_t ns[2] = {n_seed_left, n_seed_right};
@@ -875,28 +873,24 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     if ((rc = h2v_msm_g1(ctx, sc[0].data(), seed_left_bases64, n_seed_left, seed_xy, &ident))) return rc;         // (rejects bases that are not on the curve)
     if ((rc = h2v_msm_g1(ctx, sc[1].data(), seed_right_bases64, n_seed_right, seed_xy + 64, &ident))) return rc;
     // the proofs: one batch without its pairing, kept for the fold
-    h2v_batch* b = nullptr;
-    int ok_unused = 0;
-    if ((rc = pack_and_run(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, false, 0, per_proof_status, &ok_unused, nullptr, nullptr, &b))) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    do {
-        if (hipSetDevice(ctx->device) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
-        DevBuf<uint8_t> d_xy, d_records; DevBuf<G1A> d_aff; DevBuf<G1J> d_jac; DevBuf<uint32_t> d_flags;
-        if ((rc = d_xy.alloc(128)) || (rc = d_records.alloc(2 * H2V_ACC_RECORD_BYTES)) || (rc = d_aff.alloc(2)) || (rc = d_jac.alloc(2)) || (rc = d_flags.alloc(2))) break;
-        hipStream_t s = b->stream;
-        if (hipMemcpyAsync(d_xy.p, seed_xy, 128, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error("h2v_verify_batch_seeded: copy failed"); rc = H2V_ERR_DEVICE; break; }
-        if ((rc = bases_from_bytes_enqueue(s, d_xy.p, d_aff.p, d_flags.p, 2))) break;
-        if ((rc = affine_to_jacobian_enqueue(s, d_aff.p, d_jac.p, 2))) break;
-        if ((rc = export_batch_records(b, d_records.p))) break;                                                                  // record 0: the proofs of this call
-        if ((rc = export_records_enqueue(s, d_jac.p, nullptr, 1, 0, nullptr, 0, 1, d_records.p + H2V_ACC_RECORD_BYTES))) break;   // record 1: the scaled seed
-        if ((rc = h2v_batch_fold_check_enqueue(b, d_records.p, 2))) break;
-        int ok = 0;
-        if ((rc = finish_impl(b, nullptr, &ok, out_left_xy, out_right_xy))) break;   // (synchronises: the scoped buffers outlive their use)
-        if (per_proof_status) for (size_t i = 0; i < n; ++i) if (per_proof_status[i] != 0) ok = 0;   // (short proofs: statuses forced on the host)
-        if (batch_ok) *batch_ok = ok;
-    } while (0);
-    if (rc) h2v_batch_destroy(b); else scratch_batch_give(ctx, b);
-    return rc;
+    ScratchBatch sb(ctx);
+    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 0, false, per_proof_status, nullptr, nullptr, nullptr))) return rc;
+    h2v_batch* b = sb.b;
+    if (hipSetDevice(ctx->device) != hipSuccess) return H2V_ERR_DEVICE;
+    DevBuf<uint8_t> d_xy, d_records; DevBuf<G1A> d_aff; DevBuf<G1J> d_jac; DevBuf<uint32_t> d_flags;
+    if ((rc = d_xy.alloc(128)) || (rc = d_records.alloc(2 * H2V_ACC_RECORD_BYTES)) || (rc = d_aff.alloc(2)) || (rc = d_jac.alloc(2)) || (rc = d_flags.alloc(2))) return rc;
+    hipStream_t s = b->stream;
+    if (hipMemcpyAsync(d_xy.p, seed_xy, 128, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error("h2v_verify_batch_seeded: copy failed"); return H2V_ERR_DEVICE; }
+    if ((rc = bases_from_bytes_enqueue(s, d_xy.p, d_aff.p, d_flags.p, 2))) return rc;
+    if ((rc = affine_to_jacobian_enqueue(s, d_aff.p, d_jac.p, 2))) return rc;
+    if ((rc = export_batch_records(b, d_records.p))) return rc;                                                                  // record 0: the proofs of this call
+    if ((rc = export_records_enqueue(s, d_jac.p, nullptr, 1, 0, nullptr, 0, 1, d_records.p + H2V_ACC_RECORD_BYTES))) return rc;   // record 1: the scaled seed
+    if ((rc = h2v_batch_fold_check_enqueue(b, d_records.p, 2))) return rc;
+    int ok = 0;
+    if ((rc = finish_impl(b, "h2v_batch_finish", nullptr, &ok, out_left_xy, out_right_xy))) return rc;   // (synchronises: the scoped buffers outlive their use)
+    if (per_proof_status) for (size_t i = 0; i < n; ++i) if (per_proof_status[i] != 0) ok = 0;   // (short proofs: statuses forced on the host)
+    if (batch_ok) *batch_ok = ok;
+    return 0;
 }
 
 // N x verify_proof with per-proof instance shapes (lib.rs:33-49 takes `instances` per call): proofs are grouped by shape
@@ -932,9 +926,8 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
         return h2v_verify_batch(ctx, n, proofs, proof_lens, instances32, nc, n ? col_lens_per_proof : nullptr, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
     std::vector<uint8_t> os_rand;
     int rc;
-    if (!rand32) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand32 = os_rand.data(); }
-    for (size_t i = 0; i < n; ++i) if (!scalar_is_canonical(rand32 + 32 * i)) { set_last_error("h2v_verify_batch_shapes: rand32 scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
-    std::lock_guard<std::mutex> lock(ctx->mu);   // a one-shot entry point: it owns the context's stream and scratch batch for its duration
+    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_shapes"))) return rc;
+    ScratchBatch sb(ctx);   // (the context's stream too)
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     // whole-sequence multipliers on the context's stream
     DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
@@ -945,34 +938,27 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     // one batch object serves every shape group (its buffers grow to the largest group's plan: ensure_buffers)
     size_t max_group = 1, max_inst = 0;
     for (auto& g : groups) { max_group = std::max(max_group, g.second.size()); size_t t = 0; for (size_t l : g.first) t += l; max_inst = std::max(max_inst, t); }
-    h2v_batch* b = nullptr;
-    if ((rc = scratch_batch_take(ctx, max_group, max_inst, &b))) return rc;
-    b->want_guard = false;
+    if ((rc = sb.take(max_group, max_inst))) return rc;
+    h2v_batch* b = sb.b;
     bool all_ok = true;
     size_t idx_off = 0;
-    for (size_t gi = 0; gi < groups.size() && !rc; ++gi) {
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
         const std::vector<size_t>& idx = groups[gi].second;
         const size_t m = idx.size();
-        PlanPin pin(ctx);
-        if ((rc = pin.get(groups[gi].first))) break;
-        const Plan& pl = pin.pd->host;
         std::vector<const uint8_t*> pp(m), ip(m); std::vector<size_t> plen(m);
         for (size_t j = 0; j < m; ++j) { pp[j] = proofs[idx[j]]; plen[j] = proof_lens[idx[j]]; ip[j] = instances32 ? instances32[idx[j]] : nullptr; }
+        PlanPin pin(ctx);
         std::vector<uint8_t> flat, iflat; std::vector<int> forced;
-        if ((rc = pack_inputs(pl, m, pp.data(), plen.data(), ip.data(), flat, iflat, forced))) break;
+        if ((rc = pack_inputs(pin, m, pp.data(), plen.data(), ip.data(), nc, groups[gi].first.data(), flat, iflat, forced))) return rc;
+        const Plan& pl = pin.pd->host;
         std::vector<uint32_t> idx32(idx.begin(), idx.end());
-        if (hipMemcpy(d_idx.p + idx_off, idx32.data(), 4 * m, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("h2v_verify_batch_shapes: hipMemcpy failed"); rc = H2V_ERR_DEVICE; break; }
+        if (hipMemcpy(d_idx.p + idx_off, idx32.data(), 4 * m, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("h2v_verify_batch_shapes: hipMemcpy failed"); return H2V_ERR_DEVICE; }
         std::vector<uint8_t> ones(32 * m, 0);
         for (size_t j = 0; j < m; ++j) ones[32 * j] = 1;      // placeholder draws: the multipliers come from d_mult
         std::vector<int> st(m, 0); int gok = 0;
-        if ((rc = h2v_batch_set_groups(b, 1))) break;
-        if ((rc = upload_impl(b, m, flat.data(), pl.proof_len, iflat.data(), nc, groups[gi].first.data(), ones.data(), m))) break;
-        b->ext_mult = d_mult.p; b->ext_idx = d_idx.p + idx_off;
-        rc = launch_impl(b, 0);
-        if (!rc) rc = export_batch_records(b, d_records.p + gi * H2V_ACC_RECORD_BYTES);
-        if (!rc) rc = finish_impl(b, st.data(), &gok, nullptr, nullptr);
-        b->ext_mult = nullptr; b->ext_idx = nullptr;
-        if (rc) break;
+        if ((rc = h2v_batch_set_groups(b, 1)) || (rc = upload_impl(b, m, flat.data(), pl.proof_len, iflat.data(), nc, groups[gi].first.data(), ones.data(), m)) ||
+            (rc = launch_impl(b, 0, d_mult.p, d_idx.p + idx_off)) || (rc = export_batch_records(b, d_records.p + gi * H2V_ACC_RECORD_BYTES)) ||
+            (rc = finish_impl(b, "h2v_batch_finish", st.data(), &gok, nullptr, nullptr))) return rc;
         for (size_t j = 0; j < m; ++j) {
             int v = forced[j] ? forced[j] : st[j];
             if (per_proof_status) per_proof_status[idx[j]] = v;
@@ -980,8 +966,6 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
         }
         idx_off += m;
     }
-    if (rc) { h2v_batch_destroy(b); return rc; }
-    scratch_batch_give(ctx, b);
     int ok = 0;
     if ((rc = fold_check_locked(ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
     if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
@@ -1000,25 +984,14 @@ int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proo
     // a single proof's check equals SingleStrategy's only when its multiplier is non-zero: no draw may be zero
     std::vector<uint8_t> os_rand;
     int rc;
-    if (!rand32 && n) { if ((rc = os_random_scalars(os_rand, n))) return rc; rand32 = os_rand.data(); }
-    auto is_zero = [](const uint8_t* r) { for (int k = 0; k < 32; ++k) if (r[k]) return false; return true; };
-    for (size_t i = 0; i < n; ++i) {
-        if (!is_zero(rand32 + 32 * i)) continue;
-        if (os_rand.empty()) { set_last_error("h2v_verify_batch_identify: a draw in rand32 is zero"); return H2V_ERR_BAD_ARGUMENT; }
-        std::vector<uint8_t> one;
-        do { if ((rc = os_random_scalars(one, 1))) return rc; } while (is_zero(one.data()));   // (an OS draw of zero: probability 2^-254)
-        memcpy(&os_rand[32 * i], one.data(), 32);
-    }
+    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_identify", true))) return rc;
     std::vector<int> st(n ? n : 1, 0);
     int ok = 0;
-    h2v_batch* b = nullptr;
-    if ((rc = pack_and_run(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, false, 1, st.data(), &ok, out_left_xy, out_right_xy, &b))) return rc;
+    ScratchBatch sb(ctx);
+    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, st.data(), &ok, out_left_xy, out_right_xy))) return rc;
     st.resize(n);
-    std::lock_guard<std::mutex> lock(ctx->mu);   // the kept batch is the context's scratch batch until it is given back
     size_t checks = 0;
-    if (n && !pairing_passed(b, 0)) rc = identify_search(b, st, &checks);
-    if (rc) { h2v_batch_destroy(b); return rc; }
-    scratch_batch_give(ctx, b);
+    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search(sb.b, st, &checks))) return rc;
     if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
     if (batch_ok) *batch_ok = ok;
     if (n_range_checks) *n_range_checks = checks;
@@ -1027,8 +1000,32 @@ int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proo
 
 int h2v_verify_each(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
                     const size_t* col_lens, int* per_proof_status) {
-    int ok = 0;
-    return pack_and_run(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, nullptr, true, 1, per_proof_status, &ok, nullptr, nullptr, nullptr);
+    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    ScratchBatch sb(ctx);
+    PlanPin pin(ctx);
+    std::vector<uint8_t> flat, iflat; std::vector<int> forced;
+    int rc;
+    if ((rc = pack_inputs(pin, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, flat, iflat, forced))) return rc;
+    const Plan& pl = pin.pd->host;
+    // SingleStrategy (kzg/strategy.rs:143-181) = an accumulator of ONE proof with multiplier 1 and its own pairing: run the
+    // proofs as one-proof groups of grouped launches, at most MSM_MAX_PROBLEMS / 2 per launch
+    const size_t per = MSM_MAX_PROBLEMS / 2, per_inst = (size_t)pl.n_instance_values * 32;
+    if ((rc = sb.take(std::min(n ? n : 1, per), pl.n_instance_values))) return rc;
+    for (size_t off = 0; off < n; off += per) {
+        const size_t m = std::min(per, n - off);
+        std::vector<uint8_t> ones(32 * m, 0);
+        for (size_t i = 0; i < m; ++i) ones[32 * i] = 1;
+        std::vector<int> st(m, 0), gok(m, 0);
+        if ((rc = h2v_batch_set_groups(sb.b, m)) ||
+            (rc = upload_impl(sb.b, m, flat.data() + off * pl.proof_len, pl.proof_len, iflat.data() + off * per_inst, n_instance_columns, col_lens, ones.data(), m)) ||
+            (rc = launch_impl(sb.b, 1)) || (rc = finish_impl(sb.b, "h2v_batch_finish_groups", st.data(), gok.data(), nullptr, nullptr))) return rc;
+        for (size_t i = 0; i < m; ++i) {
+            int v = forced[off + i] ? forced[off + i] : st[i];
+            if (v == 0 && !gok[i]) v = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;  // kzg/strategy.rs:171-175
+            if (per_proof_status) per_proof_status[off + i] = v;
+        }
+    }
+    return 0;
 }
 
 int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const uint8_t* instances32, size_t n_instance_columns, const size_t* col_lens,
@@ -1037,65 +1034,63 @@ int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const ui
     if (!ctx || !proof || !n_right || !n_left) { set_last_error("h2v_guard_msm: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     uint8_t one[32] = {1};
     const uint8_t* pp[1] = {proof}; size_t pl1[1] = {proof_len}; const uint8_t* ip[1] = {instances32};
-    int st = 0, ok = 0;
-    h2v_batch* b = nullptr;
-    int rc = pack_and_run(ctx, 1, pp, pl1, ip, n_instance_columns, col_lens, one, false, 0, &st, &ok, nullptr, nullptr, &b, true);
+    int st = 0;
+    ScratchBatch sb(ctx);
+    int rc = pack_and_run(sb, 1, pp, pl1, ip, n_instance_columns, col_lens, one, 0, true, &st, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (st != 0) { h2v_batch_destroy(b); return st; }
+    if (st != 0) return st;
+    const h2v_batch* b = sb.b;
     const Plan& pl = b->plan->host;
     size_t T = pl.right_term_order.size();
-    do {
-        size_t TL = pl.left_term_order.size();
-        if (T > *n_right || TL > *n_left) { set_last_error("h2v_guard_msm: output capacity too small"); rc = H2V_ERR_BAD_ARGUMENT; break; }
-        std::vector<uint32_t> lscal((size_t)pl.n_points * 8);
-        if (hipMemcpy(lscal.data(), b->left_scal.p, lscal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
-        std::vector<uint32_t> scal((size_t)pl.n_points * 8);
-        std::vector<Fr> shared(pl.n_shared);
-        std::vector<G1A> pts(pl.n_points + pl.n_shared);
-        std::vector<Fr> chal(pl.squeeze_at.size());
-        if (hipMemcpy(scal.data(), b->msm_scal.p, scal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shared.data(), b->shared.p, sizeof(Fr) * pl.n_shared, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(pts.data(), b->pts.p, sizeof(G1A) * pts.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(chal.data(), b->chal.p, sizeof(Fr) * chal.size(), hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
-        auto put_pt = [](const G1A& p, uint8_t* o) { if (p.is_identity()) memset(o, 0, 64); else { p.x.to_bytes(o); p.y.to_bytes(o + 32); } };
-        if (!pl.guard_term_order.empty()) {
-            // GWC: term by term as the reference appends them (gwc.rs:86-132), each with its own scalar
-            T = pl.guard_term_order.size();
-            if (T > *n_right) { set_last_error("h2v_guard_msm: output capacity too small"); rc = H2V_ERR_BAD_ARGUMENT; break; }
-            std::vector<uint32_t> gs(T * 8);
-            if (hipMemcpy(gs.data(), b->guard_scal.p, gs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = H2V_ERR_DEVICE; break; }
-            for (size_t t = 0; t < T; ++t) {
-                auto w = pl.guard_term_order[t];
-                memcpy(right_scalars32 + 32 * t, &gs[t * 8], 32);
-                put_pt(pts[w.first ? pl.n_points + w.second : w.second], right_bases64 + 64 * t);
-            }
-        } else
+    size_t TL = pl.left_term_order.size();
+    if (T > *n_right || TL > *n_left) { set_last_error("h2v_guard_msm: output capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
+    std::vector<uint32_t> lscal((size_t)pl.n_points * 8);
+    if (hipMemcpy(lscal.data(), b->left_scal.p, lscal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
+    std::vector<uint32_t> scal((size_t)pl.n_points * 8);
+    std::vector<Fr> shared(pl.n_shared);
+    std::vector<G1A> pts(pl.n_points + pl.n_shared);
+    std::vector<Fr> chal(pl.squeeze_at.size());
+    if (hipMemcpy(scal.data(), b->msm_scal.p, scal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shared.data(), b->shared.p, sizeof(Fr) * pl.n_shared, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(pts.data(), b->pts.p, sizeof(G1A) * pts.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(chal.data(), b->chal.p, sizeof(Fr) * chal.size(), hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
+    auto put_pt = [](const G1A& p, uint8_t* o) { if (p.is_identity()) memset(o, 0, 64); else { p.x.to_bytes(o); p.y.to_bytes(o + 32); } };
+    if (!pl.guard_term_order.empty()) {
+        // GWC: term by term as the reference appends them (gwc.rs:86-132), each with its own scalar
+        T = pl.guard_term_order.size();
+        if (T > *n_right) { set_last_error("h2v_guard_msm: output capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
+        std::vector<uint32_t> gs(T * 8);
+        if (hipMemcpy(gs.data(), b->guard_scal.p, gs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
         for (size_t t = 0; t < T; ++t) {
-            auto w = pl.right_term_order[t];
-            if (w.first) { shared[w.second].to_bytes(right_scalars32 + 32 * t); put_pt(pts[pl.n_points + w.second], right_bases64 + 64 * t); }
-            else { memcpy(right_scalars32 + 32 * t, &scal[(size_t)w.second * 8], 32); put_pt(pts[w.second], right_bases64 + 64 * t); }
+            auto w = pl.guard_term_order[t];
+            memcpy(right_scalars32 + 32 * t, &gs[t * 8], 32);
+            put_pt(pts[w.first ? pl.n_points + w.second : w.second], right_bases64 + 64 * t);
         }
-        *n_right = T;
-        for (size_t t = 0; t < TL; ++t) {
-            uint32_t slot = pl.left_term_order[t].second;
-            memcpy(left_scalars32 + 32 * t, &lscal[(size_t)slot * 8], 32);
-            put_pt(pts[slot], left_bases64 + 64 * t);
-        }
-        *n_left = TL;
-        if (challenges32 && n_challenges) {
-            // reorder squeeze order -> [user challenges.., theta, beta, gamma, y, x, y', v, u]
-            size_t nc = pl.n_challenges;
-            if (nc > *n_challenges) { set_last_error("h2v_guard_msm: challenge capacity too small"); rc = H2V_ERR_BAD_ARGUMENT; break; }
-            // squeeze order is the transcript order; user challenges are interleaved by phase. Rebuild the map as compile_plan did.
-            const VkHost& vk = ctx->vk->vk;
-            std::vector<uint32_t> order;
-            uint8_t max_phase = 0; for (uint8_t p2 : vk.advice_column_phase) max_phase = std::max(max_phase, p2);
-            for (unsigned ph = 0; ph <= max_phase; ++ph) for (uint32_t i = 0; i < vk.num_challenges; ++i) if (vk.challenge_phase[i] == ph) order.push_back(i);
-            for (uint32_t i = 0; i + vk.num_challenges < nc; ++i) order.push_back(vk.num_challenges + i);
-            for (size_t q = 0; q < order.size() && q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * order[q]);
-            *n_challenges = nc;
-        }
-    } while (0);
-    h2v_batch_destroy(b);
-    return rc;
+    } else
+    for (size_t t = 0; t < T; ++t) {
+        auto w = pl.right_term_order[t];
+        if (w.first) { shared[w.second].to_bytes(right_scalars32 + 32 * t); put_pt(pts[pl.n_points + w.second], right_bases64 + 64 * t); }
+        else { memcpy(right_scalars32 + 32 * t, &scal[(size_t)w.second * 8], 32); put_pt(pts[w.second], right_bases64 + 64 * t); }
+    }
+    *n_right = T;
+    for (size_t t = 0; t < TL; ++t) {
+        uint32_t slot = pl.left_term_order[t].second;
+        memcpy(left_scalars32 + 32 * t, &lscal[(size_t)slot * 8], 32);
+        put_pt(pts[slot], left_bases64 + 64 * t);
+    }
+    *n_left = TL;
+    if (challenges32 && n_challenges) {
+        // reorder squeeze order -> [user challenges.., theta, beta, gamma, y, x, y', v, u]
+        size_t nc = pl.n_challenges;
+        if (nc > *n_challenges) { set_last_error("h2v_guard_msm: challenge capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
+        // squeeze order is the transcript order; user challenges are interleaved by phase. Rebuild the map as compile_plan did.
+        const VkHost& vk = ctx->vk->vk;
+        std::vector<uint32_t> order;
+        uint8_t max_phase = 0; for (uint8_t p2 : vk.advice_column_phase) max_phase = std::max(max_phase, p2);
+        for (unsigned ph = 0; ph <= max_phase; ++ph) for (uint32_t i = 0; i < vk.num_challenges; ++i) if (vk.challenge_phase[i] == ph) order.push_back(i);
+        for (uint32_t i = 0; i + vk.num_challenges < nc; ++i) order.push_back(vk.num_challenges + i);
+        for (size_t q = 0; q < order.size() && q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * order[q]);
+        *n_challenges = nc;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -21,7 +21,10 @@ Entry points
       the staged form both are built on (and bench.py pipelines): upload the shard once, launch() = shard pipeline -> export ->
       all-gather -> fold -> one pairing, asynchronous on the batch's stream; finish() fetches the verdict.
 """
+import ctypes
 import os
+
+from . import _lib
 
 _FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 
@@ -62,13 +65,12 @@ def draw_scalars(n: int) -> bytes:
     """n x Fr::random(OsRng) as AccumulatorStrategy::process draws them (kzg/strategy.rs:129): 64 OS-random bytes reduced mod r,
     32 little-endian canonical bytes each."""
     try:   # the library's own generator (h2v_random_scalars: what rand32 = NULL draws inside the one-shot entry points)
-        import ctypes
-        from . import _lib
-        buf = ctypes.create_string_buffer(max(32 * n, 1))
-        _lib.check(_lib.load_library().h2v_random_scalars(buf, n))
-        return buf.raw[: 32 * n]
-    except _lib.H2VError:   # library not built (orchestration tests without the product): the same distribution from os.urandom
+        lib = _lib.load_library()
+    except (_lib.H2VError, OSError, AttributeError):   # library missing or stale (orchestration tests without the product): the same distribution from os.urandom
         return b"".join((int.from_bytes(os.urandom(64), "little") % _FR_MODULUS).to_bytes(32, "little") for _ in range(n))
+    buf = ctypes.create_string_buffer(max(32 * n, 1))
+    _lib.check(lib.h2v_random_scalars(buf, n))   # (a failing generator is an error, never replaced by other draws)
+    return buf.raw[: 32 * n]
 
 
 def _scalar_bytes(rand) -> bytes:

@@ -251,7 +251,11 @@ int h2v_random_scalars(uint8_t* out32, size_t n);
 /* ---- staged interface: inputs resident in HBM, asynchronous execution on the batch's stream.
  * h2v_verify_batch == upload + launch + finish.  A sharded (multi-GPU) run uses
  * h2v_batch_launch(b, 0) on every rank, exchanges the accumulator records (h2v_batch_export_accumulators),
- * and closes with h2v_batch_fold_check_enqueue (or h2v_fold_check). */
+ * and closes with h2v_batch_fold_check_enqueue (or h2v_fold_check).
+ * After an error from h2v_batch_upload, h2v_batch_launch, h2v_batch_upload_launch, h2v_batch_finish(_groups) or
+ * h2v_batch_fold_check_enqueue the batch holds nothing: every call that works on an upload or a launch (launch, finish,
+ * finish_groups, recheck, export_accumulators, fold_check_enqueue) returns H2V_ERR_BAD_ARGUMENT until an upload succeeds.
+ * h2v_batch_set_groups leaves the batch empty in the same way. */
 int h2v_batch_create(h2v_ctx* ctx, size_t max_proofs, size_t max_instance_values_per_proof, h2v_batch** out);
 void h2v_batch_destroy(h2v_batch* b);
 /* Host -> device copy of one shard.  proofs_flat = n * proof_len bytes, instances_flat = n * (sum col_lens) * 32 bytes.

@@ -176,3 +176,26 @@ def test_verify_batch_sharded_draws_are_common_when_rank0_draws():
     assert all(p.exitcode == 0 for p in procs)
     ok, st, same = q.get(timeout=5)
     assert ok is True and st == [0] * 5 and same is True
+
+
+def test_draw_scalars_falls_back_only_when_the_library_cannot_load(monkeypatch):
+    """draw_scalars takes os.urandom only when load_library itself fails; a generator that fails is an error, never other draws."""
+    from halo2_verifier_amd import _lib, distributed as h2d
+
+    def missing():
+        raise OSError("cannot open shared object file")
+    monkeypatch.setattr(_lib, "load_library", missing)
+    out = h2d.draw_scalars(5)
+    assert len(out) == 32 * 5
+    assert all(int.from_bytes(out[32 * i:32 * i + 32], "little") < R_MOD for i in range(5))
+
+    class FailingGenerator:
+        def h2v_random_scalars(self, buf, n):
+            return -9
+
+        def h2v_last_error(self):
+            return b"h2v_random_scalars: short read from /dev/urandom"
+    monkeypatch.setattr(_lib, "load_library", lambda: FailingGenerator())
+    with pytest.raises(_lib.H2VError) as e:
+        h2d.draw_scalars(5)
+    assert e.value.code == -9
