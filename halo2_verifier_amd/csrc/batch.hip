@@ -4,7 +4,9 @@
 #include "batch.h"
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <map>
+#include <memory>
 #include <utility>
 #include <stdio.h>
 
@@ -412,6 +414,15 @@ int ensure_whole(h2v_batch* b) {
 int export_batch_records(h2v_batch* b, void* device_dst) {
     { int rcj = join_tail(b); if (rcj) return rcj; }
     if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
+    return export_records_enqueue(b->stream, b->acc.p, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
+}
+
+// the batch's accumulator records as whole points.  For a record in pieces, the one-pairing fold (fold_check_locked) puts the pieces
+// together with ~254 dependent doublings per record, one record after another: 1.15 ms for two records at 1024 proofs each, where
+// the batch's own msm_combine_parts takes 0.34 ms on its stream, beside the other batches of the call (h2v_verify_batch_keys).
+int export_whole_records(h2v_batch* b, void* device_dst) {
+    int rc;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
     return export_records_enqueue(b->stream, b->acc.p, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
 }
 
@@ -893,83 +904,192 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     return 0;
 }
 
-// N x verify_proof with per-proof instance shapes (lib.rs:33-49 takes `instances` per call): proofs are grouped by shape
-// (one compiled plan each), every group runs as its own batch without a pairing, and the groups' accumulator records are
-// folded into the single pairing.  The multiplier of proof i is the product of the draws of ALL later proofs in call order
+// N x verify_proof with per-proof instance shapes (lib.rs:33-49 takes `instances` per call) and, in h2v_verify_batch_keys, per-proof
+// VerifyingKeys (lib.rs:33-49 takes `vk` per call too; kzg/strategy.rs:125-140 only ever sees MSMs): proofs are grouped by (key, shape)
+// (one compiled plan each), every group runs as its own batch without a pairing on its key's scratch batch, and the groups' accumulator
+// records are folded into the single pairing.  The multiplier of proof i is the product of the draws of ALL later proofs in call order
 // (kzg/strategy.rs:129, msm.rs:173-176), whatever group they fall in: the suffix products are computed once over the whole
 // sequence and every group gathers its own.
 // The instance shapes of a call are chosen by whoever supplies the proofs, and every distinct shape costs a plan compilation
 // (O(program length^2) host work, ~10 device uploads) and may grow the batch's buffers: a call takes at most
-// H2V_MAX_SHAPES_PER_CALL distinct shapes (H2V_ERR_UNSUPPORTED beyond), the groups share ONE batch object, and the plans go
-// through the context's bounded cache (H2V_MAX_CACHED_PLANS, least recently used out).
+// H2V_MAX_SHAPES_PER_CALL distinct (key, shape) groups (H2V_ERR_UNSUPPORTED beyond), the groups of a key share ONE batch object, and
+// the plans go through the context's bounded cache (H2V_MAX_CACHED_PLANS, least recently used out).
 #define H2V_MAX_SHAPES_PER_CALL 64
+
+// the proofs of one key with one instance shape, in call order
+struct CallGroup { size_t key; std::vector<size_t> shape, idx; };
+
+// the (key, shape) groups of a call in first-appearance order; every pointer the groups will read is checked here
+static int group_proofs(const char* who, size_t n, const uint32_t* key_of_proof, const size_t* n_instance_columns, const size_t* col_lens,
+                        const uint8_t* const* proofs, const uint8_t* const* instances32, std::vector<CallGroup>& groups) {
+    std::map<std::pair<size_t, std::vector<size_t>>, size_t> group_of;
+    const size_t* cl = col_lens;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t k = key_of_proof ? key_of_proof[i] : 0, nc = n_instance_columns[k];
+        std::vector<size_t> shape(cl, cl + nc);
+        cl += nc;
+        if (!proofs[i]) { set_last_error(std::string(who) + ": null proof pointer"); return H2V_ERR_BAD_ARGUMENT; }
+        size_t values = 0;
+        for (size_t l : shape) values += l;
+        if (values && (!instances32 || !instances32[i])) { set_last_error(std::string(who) + ": null instances pointer"); return H2V_ERR_BAD_ARGUMENT; }
+        auto it = group_of.find({k, shape});
+        if (it == group_of.end()) {
+            if (groups.size() == H2V_MAX_SHAPES_PER_CALL) { set_last_error(std::string(who) + ": more than 64 distinct (key, instance shape) groups in one call"); return H2V_ERR_UNSUPPORTED; }
+            it = group_of.emplace(std::make_pair(k, shape), groups.size()).first;
+            groups.push_back({k, shape, {}});
+        }
+        groups[it->second].idx.push_back(i);
+    }
+    return 0;
+}
+
+// The groups of a call on their keys' scratch batches (hold[k]: context k's, taken by the caller; keys without a group are not touched),
+// their records (whole points: export_whole_records) folded into ONE pairing on the first group's context.  rand32: the n draws in
+// call order (resolved).
+// Keys do not wait for each other on the host: each round enqueues one group of every key (upload, launch without a pairing, record
+// export on that key's batch stream), then finishes them; groups of one key run one after another on its batch.
+static int run_groups(ScratchBatch* const* hold, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+                      const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+    h2v_ctx* fold_ctx = hold[groups[0].key]->ctx;
+    H2V_HIP_CHECK(hipSetDevice(fold_ctx->device));
+    int rc;
+    // the groups of every key, and each group's proof indices at its offset of one index array
+    std::map<size_t, std::vector<size_t>> of_key;
+    std::vector<uint32_t> idx32;
+    std::vector<size_t> idx_off(groups.size());
+    size_t rounds = 0;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        std::vector<size_t>& kg = of_key[groups[gi].key];
+        kg.push_back(gi);
+        rounds = std::max(rounds, kg.size());
+        idx_off[gi] = idx32.size();
+        idx32.insert(idx32.end(), groups[gi].idx.begin(), groups[gi].idx.end());
+    }
+    // whole-sequence multipliers on the folding context's stream
+    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
+    if ((rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
+    H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
+    if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p))) return rc;
+    H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
+    // one batch object per key serves every shape group of that key (its buffers grow to the largest group's plan: ensure_buffers)
+    for (auto& kv : of_key) {
+        size_t max_group = 1, max_inst = 0;
+        for (size_t gi : kv.second) { max_group = std::max(max_group, groups[gi].idx.size()); size_t t = 0; for (size_t l : groups[gi].shape) t += l; max_inst = std::max(max_inst, t); }
+        if ((rc = hold[kv.first]->take(max_group, max_inst))) return rc;
+    }
+    // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
+    struct Drain {
+        std::vector<h2v_batch*> bs;
+        ~Drain() { for (h2v_batch* b : bs) { hipStreamSynchronize(b->stream); hipStreamSynchronize(b->aux); } }
+    } drain;
+    for (auto& kv : of_key) drain.bs.push_back(hold[kv.first]->b);
+    std::vector<std::vector<int>> forced(groups.size());
+    bool all_ok = true;
+    for (size_t r = 0; r < rounds; ++r) {
+        for (auto& kv : of_key) {
+            if (r >= kv.second.size()) continue;
+            const size_t gi = kv.second[r];
+            const CallGroup& grp = groups[gi];
+            h2v_batch* b = hold[kv.first]->b;
+            const size_t m = grp.idx.size();
+            std::vector<const uint8_t*> pp(m), ip(m); std::vector<size_t> plen(m);
+            for (size_t j = 0; j < m; ++j) { pp[j] = proofs[grp.idx[j]]; plen[j] = proof_lens[grp.idx[j]]; ip[j] = instances32 ? instances32[grp.idx[j]] : nullptr; }
+            PlanPin pin(b->ctx);
+            std::vector<uint8_t> flat, iflat;
+            if ((rc = pack_inputs(pin, m, pp.data(), plen.data(), ip.data(), grp.shape.size(), grp.shape.data(), flat, iflat, forced[gi]))) return rc;
+            const Plan& pl = pin.pd->host;
+            std::vector<uint8_t> ones(32 * m, 0);
+            for (size_t j = 0; j < m; ++j) ones[32 * j] = 1;      // placeholder draws: the multipliers come from d_mult
+            if ((rc = h2v_batch_set_groups(b, 1)) || (rc = upload_impl(b, m, flat.data(), pl.proof_len, iflat.data(), grp.shape.size(), grp.shape.data(), ones.data(), m)) ||
+                (rc = launch_impl(b, 0, d_mult.p, d_idx.p + idx_off[gi])) || (rc = export_whole_records(b, d_records.p + gi * H2V_ACC_RECORD_BYTES))) return rc;
+        }
+        for (auto& kv : of_key) {
+            if (r >= kv.second.size()) continue;
+            const size_t gi = kv.second[r];
+            const std::vector<size_t>& idx = groups[gi].idx;
+            std::vector<int> st(idx.size(), 0); int gok = 0;
+            if ((rc = finish_impl(hold[kv.first]->b, "h2v_batch_finish", st.data(), &gok, nullptr, nullptr))) return rc;
+            for (size_t j = 0; j < idx.size(); ++j) {
+                int v = forced[gi][j] ? forced[gi][j] : st[j];
+                if (per_proof_status) per_proof_status[idx[j]] = v;
+                if (v != 0) all_ok = false;
+            }
+        }
+    }
+    drain.bs.clear();   // (every group is finished)
+    int ok = 0;
+    if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
+    if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
+    return 0;
+}
+
 int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
                             size_t n_instance_columns, const size_t* col_lens_per_proof, const uint8_t* rand32, int* per_proof_status, int* batch_ok,
                             uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
     if (!ctx || (n && (!proofs || !proof_lens)) || (n && n_instance_columns && !col_lens_per_proof)) { set_last_error("h2v_verify_batch_shapes: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
     if (n_instance_columns != ctx_total_instance_columns(ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
-    const size_t nc = n_instance_columns;
-    std::vector<std::pair<std::vector<size_t>, std::vector<size_t>>> groups;   // (shape, proof indices) in first-appearance order
-    std::map<std::vector<size_t>, size_t> group_of;
-    for (size_t i = 0; i < n; ++i) {
-        std::vector<size_t> shape(col_lens_per_proof + i * nc, col_lens_per_proof + (i + 1) * nc);
-        auto it = group_of.find(shape);
-        if (it == group_of.end()) {
-            if (groups.size() == H2V_MAX_SHAPES_PER_CALL) { set_last_error("h2v_verify_batch_shapes: more than 64 distinct instance shapes in one call"); return H2V_ERR_UNSUPPORTED; }
-            it = group_of.emplace(shape, groups.size()).first;
-            groups.push_back({shape, {}});
-        }
-        groups[it->second].second.push_back(i);
-    }
-    if (groups.size() <= 1)
-        return h2v_verify_batch(ctx, n, proofs, proof_lens, instances32, nc, n ? col_lens_per_proof : nullptr, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-    std::vector<uint8_t> os_rand;
+    std::vector<CallGroup> groups;
     int rc;
+    if ((rc = group_proofs("h2v_verify_batch_shapes", n, nullptr, &n_instance_columns, col_lens_per_proof, proofs, instances32, groups))) return rc;
+    if (groups.size() <= 1)
+        return h2v_verify_batch(ctx, n, proofs, proof_lens, instances32, n_instance_columns, n ? col_lens_per_proof : nullptr, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    std::vector<uint8_t> os_rand;
     if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_shapes"))) return rc;
     ScratchBatch sb(ctx);   // (the context's stream too)
-    H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    // whole-sequence multipliers on the context's stream
-    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
-    if ((rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
-    H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = multipliers_enqueue(ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p))) return rc;
-    H2V_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    // one batch object serves every shape group (its buffers grow to the largest group's plan: ensure_buffers)
-    size_t max_group = 1, max_inst = 0;
-    for (auto& g : groups) { max_group = std::max(max_group, g.second.size()); size_t t = 0; for (size_t l : g.first) t += l; max_inst = std::max(max_inst, t); }
-    if ((rc = sb.take(max_group, max_inst))) return rc;
-    h2v_batch* b = sb.b;
-    bool all_ok = true;
-    size_t idx_off = 0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const std::vector<size_t>& idx = groups[gi].second;
-        const size_t m = idx.size();
-        std::vector<const uint8_t*> pp(m), ip(m); std::vector<size_t> plen(m);
-        for (size_t j = 0; j < m; ++j) { pp[j] = proofs[idx[j]]; plen[j] = proof_lens[idx[j]]; ip[j] = instances32 ? instances32[idx[j]] : nullptr; }
-        PlanPin pin(ctx);
-        std::vector<uint8_t> flat, iflat; std::vector<int> forced;
-        if ((rc = pack_inputs(pin, m, pp.data(), plen.data(), ip.data(), nc, groups[gi].first.data(), flat, iflat, forced))) return rc;
-        const Plan& pl = pin.pd->host;
-        std::vector<uint32_t> idx32(idx.begin(), idx.end());
-        if (hipMemcpy(d_idx.p + idx_off, idx32.data(), 4 * m, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("h2v_verify_batch_shapes: hipMemcpy failed"); return H2V_ERR_DEVICE; }
-        std::vector<uint8_t> ones(32 * m, 0);
-        for (size_t j = 0; j < m; ++j) ones[32 * j] = 1;      // placeholder draws: the multipliers come from d_mult
-        std::vector<int> st(m, 0); int gok = 0;
-        if ((rc = h2v_batch_set_groups(b, 1)) || (rc = upload_impl(b, m, flat.data(), pl.proof_len, iflat.data(), nc, groups[gi].first.data(), ones.data(), m)) ||
-            (rc = launch_impl(b, 0, d_mult.p, d_idx.p + idx_off)) || (rc = export_batch_records(b, d_records.p + gi * H2V_ACC_RECORD_BYTES)) ||
-            (rc = finish_impl(b, "h2v_batch_finish", st.data(), &gok, nullptr, nullptr))) return rc;
-        for (size_t j = 0; j < m; ++j) {
-            int v = forced[j] ? forced[j] : st[j];
-            if (per_proof_status) per_proof_status[idx[j]] = v;
-            if (v != 0) all_ok = false;
-        }
-        idx_off += m;
+    ScratchBatch* hold[1] = {&sb};
+    return run_groups(hold, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+}
+
+// what the accumulation and its pairing read from the params (shplonk.rs's -g term, msm.rs:185-203); k may differ
+static bool same_srs(const ParamsHost& a, const ParamsHost& b) {
+    auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
+    return !memcmp(&a.g, &b.g, sizeof(G1A)) && same_g2(a.g2, b.g2) && same_g2(a.s_g2, b.s_g2);
+}
+
+int h2v_verify_batch_keys(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+                          const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
+                          int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
+    // every argument check comes before the first HIP call
+    if (!ctxs || !n_keys || !n_instance_columns || (n && (!key_of_proof || !proofs || !proof_lens))) { set_last_error("h2v_verify_batch_keys: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t k = 0; k < n_keys; ++k) {
+        if (!ctxs[k]) { set_last_error("h2v_verify_batch_keys: null context"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!ctxs[k]->vk) { set_last_error("h2v_verify_batch_keys: a context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+        for (size_t j = 0; j < k; ++j)
+            if (ctxs[j] == ctxs[k]) { set_last_error("h2v_verify_batch_keys: the same context twice"); return H2V_ERR_BAD_ARGUMENT; }
+        if (ctxs[k]->device != ctxs[0]->device) { set_last_error("h2v_verify_batch_keys: contexts on different devices"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!same_srs(ctxs[k]->params, ctxs[0]->params)) { set_last_error("h2v_verify_batch_keys: contexts over different params (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
     }
-    int ok = 0;
-    if ((rc = fold_check_locked(ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
-    if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
-    return 0;
+    for (size_t k = 0; k < n_keys; ++k)
+        if (n_instance_columns[k] != ctx_total_instance_columns(ctxs[k])) { set_last_error("h2v_verify_batch_keys: instances do not match a VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
+    size_t total_cols = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (key_of_proof[i] >= n_keys) { set_last_error("h2v_verify_batch_keys: key index out of range"); return H2V_ERR_BAD_ARGUMENT; }
+        total_cols += n_instance_columns[key_of_proof[i]];
+    }
+    if (total_cols && !col_lens) { set_last_error("h2v_verify_batch_keys: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    std::vector<CallGroup> groups;
+    int rc;
+    if ((rc = group_proofs("h2v_verify_batch_keys", n, key_of_proof, n_instance_columns, col_lens, proofs, instances32, groups))) return rc;
+    if (groups.empty()) {
+        std::vector<size_t> zeros(n_instance_columns[0] ? n_instance_columns[0] : 1, 0);
+        return h2v_verify_batch(ctxs[0], 0, proofs, proof_lens, instances32, n_instance_columns[0], zeros.data(), rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    }
+    if (groups.size() == 1)   // (one key, one shape: the proofs are that group, in call order)
+        return h2v_verify_batch(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32, per_proof_status,
+                                batch_ok, out_left_xy, out_right_xy);
+    std::vector<uint8_t> os_rand;
+    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_keys"))) return rc;
+    // every context's lock and scratch batch for the whole call, taken in one global order (by address): calls over overlapping sets of
+    // contexts cannot deadlock
+    std::vector<size_t> order(n_keys);
+    for (size_t k = 0; k < n_keys; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::less<const h2v_ctx*>()(ctxs[a], ctxs[b]); });
+    std::vector<std::unique_ptr<ScratchBatch>> holders(n_keys);
+    std::vector<ScratchBatch*> hold(n_keys);
+    for (size_t k : order) { holders[k].reset(new ScratchBatch(ctxs[k])); hold[k] = holders[k].get(); }
+    return run_groups(hold.data(), groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
 
 int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {

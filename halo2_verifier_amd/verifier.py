@@ -8,13 +8,9 @@ library; this file only marshals bytes.
 """
 import ctypes
 import enum
-import os
 
 from . import _lib
-from . import distributed
 from ._lib import H2VError, check
-
-_FR_MODULUS = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 
 
 class SerdeFormat(enum.IntEnum):  # helpers.rs:7-19
@@ -351,7 +347,7 @@ class AccumulatorStrategy(_Strategy):
         super().__init__(params)
         self.rand, self.device, self.circuit_instances = rand, device, circuit_instances
         self.seed = None
-        self.left_xy = self.right_xy = None   # the evaluated channels after finalize() (single-VK accumulations)
+        self.left_xy = self.right_xy = None   # the evaluated channels after finalize()
 
     @classmethod
     def with_accumulator(cls, params, left, right, rand=None, device=0, circuit_instances=1):
@@ -365,19 +361,19 @@ class AccumulatorStrategy(_Strategy):
     def finalize(self) -> bool:
         """One pairing for everything that was accumulated.  verify_proof takes a VK per call and one strategy may accumulate
         proofs of DIFFERENT VKs over the same params (kzg/strategy.rs:125-140 only ever sees MSMs): proofs are grouped by VK,
-        every VK gets its own context and accumulator pair (no pairing), the draws are indexed by call order over ALL queued
-        proofs (proof i is scaled by the product of the draws of all later proofs, whatever their VK), and the accumulator
-        records are folded by h2v_fold_check into the single pairing."""
+        every VK gets its own context, and h2v_verify_batch_keys runs them all with the draws indexed by call order over ALL
+        queued proofs (proof i is scaled by the product of the draws of all later proofs, whatever their VK) into one pairing.
+        left_xy / right_xy hold the evaluated channels afterwards."""
         if not self._items:
             return True  # empty DualMSM: both channels are the identity, e(0,..)e(0,..) == 1
         n = len(self._items)
         rand = self.rand
         if rand is not None and len(rand) != n:
             raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
-        groups = {}
-        for i, (vk, _, _) in enumerate(self._items):
-            groups.setdefault((vk.data, int(vk.format)), []).append(i)
-        if len(groups) == 1:
+        keys = {}
+        for vk, _, _ in self._items:
+            keys.setdefault((vk.data, int(vk.format)), vk)
+        if len(keys) == 1:
             ctx = Context(self.params, self._items[0][0], self.device, circuit_instances=self.circuit_instances)
             try:
                 ok, _, self.left_xy, self.right_xy = ctx.verify_batch([p for _, _, p in self._items], [i for _, i, _ in self._items], rand, seed=self.seed)
@@ -386,41 +382,16 @@ class AccumulatorStrategy(_Strategy):
                 ctx.close()
         if self.seed is not None:
             raise ValueError("a seeded accumulation takes proofs of one VerifyingKey")
-        return self._finalize_mixed(groups, rand)
-
-    def _finalize_mixed(self, groups, rand):
-        import torch  # device memory for the gathered records (plumbing only)
-        lib = _lib.load_library()
-        n = len(self._items)
-        if rand is None:
-            rand = [int.from_bytes(os.urandom(64), "little") % _FR_MODULUS for _ in range(n)]
-        rb = [_scalar32(r) for r in rand]
-        # A VK's proofs are not contiguous in call order, so the library's "tail" convention (multiplier = product of the later
-        # draws of the SAME upload) is fed per proof: proof i is uploaded as a one-proof shard whose tail is the draws of
-        # proofs (i, n) of the whole accumulated sequence.  Mixed-VK accumulation is a rare path; clarity over speed.
-        records = torch.zeros(n * distributed.ACC_BYTES, dtype=torch.uint8, device=f"cuda:{self.device}")
-        ctxs, ok_all = {}, True
+        index = {key: k for k, key in enumerate(keys)}
+        ctxs = []
         try:
-            for key, idx in groups.items():
-                ctx = ctxs[key] = Context(self.params, self._items[idx[0]][0], self.device, circuit_instances=self.circuit_instances)
-                for i in idx:
-                    _, inst, proof = self._items[i]
-                    flat, lens = _flatten_instances(inst)
-                    b = Batch(ctx, 1, max(sum(lens), 1))
-                    try:
-                        b.upload(proof, len(proof), flat, lens, b"".join(rb[i:]))
-                        b.launch(with_pairing=False)
-                        b.export_accumulators(records.data_ptr() + i * distributed.ACC_BYTES)
-                        _, st, _, _ = b.finish()
-                        ok_all = ok_all and st == [0]
-                    finally:
-                        b.close()
-            ok = ctypes.c_int(0)
-            any_ctx = next(iter(ctxs.values()))
-            check(lib.h2v_fold_check(any_ctx._h, ctypes.c_void_p(records.data_ptr()), n, ctypes.byref(ok), None, None))
-            return bool(ok.value) and ok_all
+            for vk in keys.values():
+                ctxs.append(Context(self.params, vk, self.device, circuit_instances=self.circuit_instances))
+            ok, _, self.left_xy, self.right_xy = verify_batch_keys(ctxs, [index[(vk.data, int(vk.format))] for vk, _, _ in self._items],
+                                                                   [p for _, _, p in self._items], [i for _, i, _ in self._items], rand)
+            return ok
         finally:
-            for c in ctxs.values():
+            for c in ctxs:
                 c.close()
 
 
@@ -456,6 +427,56 @@ def verify_batch(params, vk, proofs, instances, rand=None, device=0):
         return ctx.verify_batch(proofs, instances, rand)
     finally:
         ctx.close()
+
+
+def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None):
+    """N x verify_proof on ONE AccumulatorStrategy whose proofs belong to several VerifyingKeys over the same params, then
+    finalize() (h2v_verify_batch_keys): contexts[k] holds key k, proof i belongs to contexts[key_of_proof[i]].  instances: per
+    proof, list of columns (shapes may differ from proof to proof; every proof of a key has that key's column count).  rand: n
+    draws in call order, or None.  Returns (batch_ok, statuses, left_xy, right_xy)."""
+    contexts = list(contexts)
+    n = len(proofs)
+    if len(key_of_proof) != n or len(instances) != n:
+        raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {len(key_of_proof)} and {len(instances)}")
+    if not contexts:
+        raise ValueError("at least one context")
+    lib = _lib.load_library()
+    for p in proofs:
+        if not isinstance(p, (bytes, bytearray)):
+            raise TypeError("proofs must be bytes")
+    for k in key_of_proof:
+        if not 0 <= int(k) < len(contexts):
+            raise ValueError(f"key index {k} out of range for {len(contexts)} contexts")
+    flats, shapes = [], []
+    for inst in instances:
+        f, l = _flatten_instances(inst)
+        flats.append(f)
+        shapes.append(l)
+    ncols = [None] * len(contexts)
+    for k, l in zip(key_of_proof, shapes):
+        if ncols[k] is None:
+            ncols[k] = len(l)
+        elif ncols[k] != len(l):
+            raise ValueError("all proofs of one key must have the same number of instance columns")
+    ncols = [c.proof_shape()["n_instance_columns"] if v is None else v for c, v in zip(contexts, ncols)]
+    rb = None
+    if rand is not None:
+        if len(rand) != n:
+            raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
+        rb = b"".join(_scalar32(r) for r in rand)
+    PA = ctypes.c_char_p * max(n, 1)
+    pa = PA(*[bytes(p) for p in proofs]) if n else PA()
+    pl = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    ia = PA(*flats) if n else PA()
+    ka = (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])
+    ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
+    nca = (ctypes.c_size_t * len(contexts))(*ncols)
+    cl = (ctypes.c_size_t * max(sum(len(l) for l in shapes), 1))(*[v for l in shapes for v in l])
+    st = (ctypes.c_int * max(n, 1))()
+    ok = ctypes.c_int(0)
+    left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+    check(lib.h2v_verify_batch_keys(ca, len(contexts), ka, n, pa, pl, ia, nca, cl, rb, st, ctypes.byref(ok), left, right))
+    return bool(ok.value), list(st)[:n], left.raw, right.raw
 
 
 class Batch:

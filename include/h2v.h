@@ -190,6 +190,25 @@ int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n,
                             int* per_proof_status, int* batch_ok,
                             uint8_t out_left_xy[64], uint8_t out_right_xy[64]);
 
+/* N x verify_proof on ONE AccumulatorStrategy whose proofs belong to several VerifyingKeys, then finalize(): one pairing.
+ *   replaces: the same loop as h2v_verify_batch with a different `vk` per call (lib.rs:33-49 takes params, vk and instances on
+ *             every call; kzg/strategy.rs:125-140 only ever sees MSMs), followed by s.finalize().
+ * ctxs[k]: a context per key (its own VK and multi-open / transcript / circuit_instances options), every one on the same device and
+ * over the same params (g[0], g2 and s_g2 equal; k may differ), no context twice; key_of_proof[i] < n_keys.  Keys no proof uses are
+ * allowed.  Any of these violated: H2V_ERR_BAD_ARGUMENT, before any device work.
+ * n_instance_columns[k]: must equal context k's instance-column count (else H2V_ERR_INVALID_INSTANCES, as h2v_verify_batch).
+ * col_lens: proof by proof in call order, n_instance_columns[key_of_proof[i]] entries each (per-proof shapes allowed).
+ * rand32 / per_proof_status / batch_ok / out_*: as h2v_verify_batch, with draws and multipliers in CALL order over all keys: proof i
+ * is scaled by the product of the draws of all later proofs, whatever their key.  n == 0 behaves as h2v_verify_batch on ctxs[0].
+ * At most 64 distinct (key, instance shape) groups per call (H2V_ERR_UNSUPPORTED beyond).  The call holds every context (and its
+ * one-shot scratch batch) for its whole duration, taking them in one global order, so concurrent calls over overlapping sets of
+ * contexts do not deadlock. */
+int h2v_verify_batch_keys(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n,
+                          const uint8_t* const* proofs, const size_t* proof_lens,
+                          const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                          const uint8_t* rand32, int* per_proof_status, int* batch_ok,
+                          uint8_t out_left_xy[64], uint8_t out_right_xy[64]);
+
 /* As h2v_verify_batch, starting from an existing accumulator instead of an empty one:
  *   replaces: AccumulatorStrategy::with(msm_accumulator) (poly/kzg/strategy.rs:75-78) — the reference's only pause / resume hook —
  *             followed by the same loop of verify_proof calls and finalize().

@@ -127,14 +127,18 @@ public:
     }
     // rand32: the Fr::random draws of process() (kzg/strategy.rs:129), one 32-byte canonical scalar per proof; empty = OS RNG
     void set_randomness(Bytes rand32) { rand_ = std::move(rand32); }
+    // verify_proof takes a VK per call (lib.rs:33-49): proofs of several VerifyingKeys over the same params may share one strategy
     void push(const VerifyingKey& vk, Instances inst, Bytes proof) {
-        if (!items_.empty() && vk.bytes != vk_.bytes) throw Failure(H2V_ERR_BAD_ARGUMENT, "one AccumulatorStrategy batch verifies proofs of one VerifyingKey");
-        vk_ = vk;
+        size_t k = 0;
+        while (k < vks_.size() && !(vks_[k].bytes == vk.bytes && vks_[k].format == vk.format)) ++k;
+        if (k == vks_.size()) vks_.push_back(vk);
+        key_of_.push_back((uint32_t)k);
         items_.emplace_back(std::move(inst), std::move(proof));
     }
     // -> true iff every verify_proof succeeded and the pairing check passed; statuses() then holds the per-proof plonk::Error
     bool finalize() {
-        Context ctx(params_, vk_, device_, mo_, tr_, ci_);
+        if (vks_.size() > 1) return finalize_keys();
+        Context ctx(params_, vk(), device_, mo_, tr_, ci_);
         size_t ncols = 0;
         check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
         detail::Packed pk(items_, ncols);
@@ -160,7 +164,8 @@ public:
     // pairing fails.  The draws must be non-zero.  One instance shape, no seed.
     bool finalize_identify() {
         if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes an accumulation without a seed");
-        Context ctx(params_, vk_, device_, mo_, tr_, ci_);
+        if (vks_.size() > 1) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes proofs of one VerifyingKey");
+        Context ctx(params_, vk(), device_, mo_, tr_, ci_);
         size_t ncols = 0;
         check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
         detail::Packed pk(items_, ncols);
@@ -179,7 +184,37 @@ public:
     const uint8_t* right() const { return right_; }
 
 private:
-    ParamsKZG params_; VerifyingKey vk_; int device_; MultiOpen mo_; TranscriptKind tr_; int ci_;
+    VerifyingKey vk() const { return vks_.empty() ? VerifyingKey{} : vks_[0]; }
+    // proofs of several VerifyingKeys: a context per key, every proof in call order (h2v_verify_batch_keys)
+    bool finalize_keys() {
+        if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes proofs of one VerifyingKey");
+        if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
+        std::vector<std::unique_ptr<Context>> ctxs;
+        std::vector<h2v_ctx*> handles;
+        std::vector<size_t> ncols(vks_.size(), 0);
+        for (size_t k = 0; k < vks_.size(); ++k) {
+            ctxs.emplace_back(new Context(params_, vks_[k], device_, mo_, tr_, ci_));
+            handles.push_back(ctxs.back()->handle());
+            check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
+        }
+        std::vector<const uint8_t*> proofs, insts;
+        std::vector<size_t> lens, col_lens;
+        std::vector<Bytes> flat(items_.size());
+        for (size_t i = 0; i < items_.size(); ++i) {
+            const Instances& inst = items_[i].first;
+            if (inst.size() != ncols[key_of_[i]]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
+            for (const Column& c : inst) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
+            proofs.push_back(items_[i].second.data()); lens.push_back(items_[i].second.size()); insts.push_back(flat[i].data());
+        }
+        statuses_.assign(items_.size(), 0);
+        int ok = 0;
+        check(h2v_verify_batch_keys(handles.data(), handles.size(), key_of_.data(), items_.size(), proofs.data(), lens.data(), insts.data(), ncols.data(),
+                                    col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
+        return ok != 0;
+    }
+
+    ParamsKZG params_; std::vector<VerifyingKey> vks_; int device_; MultiOpen mo_; TranscriptKind tr_; int ci_;
+    std::vector<uint32_t> key_of_;   // the key (index into vks_) of every queued proof
     std::vector<std::pair<Instances, Bytes>> items_;
     Bytes rand_;
     bool seeded_ = false;

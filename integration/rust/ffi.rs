@@ -68,6 +68,9 @@ extern "C" {
     pub fn h2v_verify_batch_shapes(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                                    instances32: *const *const u8, n_instance_columns: usize, col_lens_per_proof: *const usize, rand32: *const u8,
                                    per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
+    pub fn h2v_verify_batch_keys(ctxs: *const *mut h2v_ctx, n_keys: usize, key_of_proof: *const u32, n: usize, proofs: *const *const u8,
+                                 proof_lens: *const usize, instances32: *const *const u8, n_instance_columns: *const usize, col_lens: *const usize,
+                                 rand32: *const u8, per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_verify_batch_seeded(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                                    instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, rand32: *const u8,
                                    seed_left_scalars32: *const u8, seed_left_bases64: *const u8, n_seed_left: usize,

@@ -2,6 +2,8 @@
 //!
 //! * `GpuBatchVerifier`        — whole-batch seam: N x `verify_proof` + `AccumulatorStrategy::finalize`
 //!                               (halo2_verifier/src/lib.rs:33-49, poly/kzg/strategy.rs:125-140) in one call.
+//! * `GpuMultiKeyVerifier`     — the same seam over several VerifyingKeys sharing the params: one context per key,
+//!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
 //! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) whose `finalize`
 //!                               evaluates the two `MSMKZG` channels and the pairing on the GPU
 //!                               (poly/kzg/msm.rs:81-86, 185-203) while `verify_proof` itself stays on the CPU.
@@ -83,6 +85,66 @@ impl<'p> GpuBatchVerifier<'p> {
     }
 }
 impl<'p> Drop for GpuBatchVerifier<'p> { fn drop(&mut self) { unsafe { h2v_ctx_destroy(self.ctx) } } }
+
+/// Whole-batch seam over several circuits: N x `verify_proof` with a different `vk` per call on ONE `AccumulatorStrategy`, then
+/// `finalize` — one pairing for all of them (h2v_verify_batch_keys).  Every key shares the params.
+pub struct GpuMultiKeyVerifier<'p> {
+    ctxs: Vec<*mut h2v_ctx>,
+    n_cols: Vec<usize>,
+    keys: Vec<u32>,
+    proofs: Vec<&'p [u8]>,
+    instances: Vec<Vec<u8>>,
+    col_lens: Vec<usize>,
+}
+
+impl<'p> GpuMultiKeyVerifier<'p> {
+    /// One context per key (key index = position in `vks`), all over `params`.
+    pub fn new(params: &ParamsKZG<Bn256>, vks: &[&VerifyingKey<G1Affine>], device: i32) -> Result<Self, Error> {
+        let mut pb = Vec::new();
+        params.write_custom(&mut pb, SerdeFormat::RawBytes).map_err(|_| Error::Opening)?;
+        let mut me = Self { ctxs: Vec::new(), n_cols: Vec::new(), keys: Vec::new(), proofs: Vec::new(), instances: Vec::new(), col_lens: Vec::new() };
+        for vk in vks {
+            let mut vb = Vec::new();
+            vk.write(&mut vb, SerdeFormat::RawBytes).map_err(|_| Error::Opening)?;
+            let mut ctx = core::ptr::null_mut();
+            let rc = unsafe { h2v_ctx_create(pb.as_ptr(), pb.len(), H2V_SERDE_RAW_BYTES, vb.as_ptr(), vb.len(), H2V_SERDE_RAW_BYTES, device, &mut ctx) };
+            if rc != 0 { return Err(map_err(rc)); }   // (the contexts made so far go with `me`)
+            me.ctxs.push(ctx);
+            let mut ncols = 0usize;
+            let rc = unsafe { h2v_ctx_proof_shape(ctx, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), &mut ncols) };
+            if rc != 0 { return Err(map_err(rc)); }
+            me.n_cols.push(ncols);
+        }
+        Ok(me)
+    }
+
+    /// One `verify_proof(&params, vks[key], strategy, &[instances], &mut Blake2bRead::init(proof))` call.
+    pub fn push(&mut self, key: usize, proof: &'p [u8], instances: &[&[Fr]]) -> Result<(), Error> {
+        if key >= self.ctxs.len() || instances.len() != self.n_cols[key] { return Err(Error::InvalidInstances); }
+        let mut flat = Vec::with_capacity(32 * instances.iter().map(|c| c.len()).sum::<usize>());
+        for col in instances { for v in col.iter() { flat.extend_from_slice(v.to_repr().as_ref()); } }
+        self.col_lens.extend(instances.iter().map(|c| c.len()));
+        self.keys.push(key as u32);
+        self.proofs.push(proof);
+        self.instances.push(flat);
+        Ok(())
+    }
+
+    /// `strategy.finalize()`: true iff every proof is well formed and the single pairing check passes.
+    pub fn finalize(self) -> Result<bool, Error> {
+        let n = self.proofs.len();
+        let ptrs: Vec<*const u8> = self.proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = self.proofs.iter().map(|p| p.len()).collect();
+        let iptrs: Vec<*const u8> = self.instances.iter().map(|i| i.as_ptr()).collect();
+        let (mut status, mut ok) = (vec![0i32; n.max(1)], 0i32);
+        let rc = unsafe { h2v_verify_batch_keys(self.ctxs.as_ptr(), self.ctxs.len(), self.keys.as_ptr(), n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(),
+                                                self.n_cols.as_ptr(), self.col_lens.as_ptr(), core::ptr::null(), status.as_mut_ptr(), &mut ok,
+                                                core::ptr::null_mut(), core::ptr::null_mut()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(ok == 1)
+    }
+}
+impl<'p> Drop for GpuMultiKeyVerifier<'p> { fn drop(&mut self) { for &c in &self.ctxs { unsafe { h2v_ctx_destroy(c) } } } }
 
 /// Trait seam: same `process` as AccumulatorStrategy (kzg/strategy.rs:125-136); `finalize` on the GPU.
 pub struct GpuAccumulatorStrategy<'params> { acc: DualMSM<'params, Bn256>, ctx: *mut h2v_ctx }
