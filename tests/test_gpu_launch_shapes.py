@@ -9,12 +9,13 @@ csrc/batch.hip): the throughput launches of bench.py run variants that the small
   * more than 64 groups per launch: whole accumulators (full Horner) and the whole-point pairing instead of pieces;
   * h2v_verify_each beyond 512 proofs: several grouped launches of one-proof groups.
 Every group of a grouped launch must equal — verdict, per-proof statuses, both accumulator points — a separate h2v_verify_batch
-over the same proofs and draws, which tests/test_gpu_sharded.py ties to the CPU oracle at 1024 proofs (and two groups are checked
-against the oracle here directly)."""
+over the same proofs and draws, and the exact linear reference (tests/batch_reference.py); two groups are also checked against the
+oracle's quadratic restatement directly."""
 import random
 
 import pytest
 
+import batch_reference
 import circuits
 from circuits import R_MOD
 
@@ -79,6 +80,7 @@ def test_throughput_launch_groups_equal_separate_batches(pool, G, gs):
     for g, (Pg, Ig, rg) in enumerate(groups):
         ref = ctx.verify_batch(Pg, Ig, rg)      # a 1024-proof launch of its own: K = 4, all slots in LDS, four waves per window, pieces
         assert (ok[g], st[g * gs:(g + 1) * gs], left[g], right[g]) == ref, g
+        assert batch_reference.expected([(s, p, i) for p, i in zip(Pg, Ig)], rg) == ref, g      # every group against the exact reference
         if g in (0, g_bad_point):
             assert circuits.oracle_verify_batch(s, Pg, Ig, rg) == ref
     assert len(set(left)) == G

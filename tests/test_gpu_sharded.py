@@ -9,6 +9,7 @@ import random
 
 import pytest
 
+import batch_reference
 import circuits
 from circuits import R_MOD
 
@@ -234,6 +235,7 @@ def test_config3_and_5_full_size_through_the_entry_point(big):
     rand = [rnd.randrange(1, R_MOD) for _ in range(n)]
     ref = ctx.verify_batch(Pn, In, rand)
     assert ref[0] is True and ref[1] == [0] * n
+    assert batch_reference.expected([(s, p, i) for p, i in zip(Pn, In)], rand) == ref          # the exact reference, not another GPU run
     got = h2d.verify_batch_sharded_local(ctx, Pn, In, rand, 8)
     assert got == ref
     # the same unsharded result from two very different launch shapes: one batch, and the fold of 64 shards of 1024
@@ -244,6 +246,22 @@ def test_config3_and_5_full_size_through_the_entry_point(big):
     got = h2d.verify_batch_sharded_local(ctx, bad, In, rand, 8)
     assert got[0] is False and [i for i, v in enumerate(got[1]) if v] == [k] and got[1][k] == -5
     assert got == ctx.verify_batch(bad, In, rand)
+    ctx.close()
+
+
+def test_full_size_one_repeated_proof(big):
+    """65 536 copies of one proof with every multiplier 1: every bucket of the right channel holds every copy of its term (the heavy
+    fix-up across the whole launch) and the left channel is one bucket of window 0 — equal to the exact reference, unsharded and over
+    8 shards."""
+    from halo2_verifier_amd import distributed as h2d
+    s, P, I = big
+    ctx = _ctx(s)
+    n = 65536
+    Pn, In, rand = [P[7]] * n, [I[7]] * n, [1] * n
+    exp = batch_reference.expected([(s, P[7], I[7])] * n, rand)
+    assert exp[0] is True and exp[2] != bytes(64)
+    assert ctx.verify_batch(Pn, In, rand) == exp
+    assert h2d.verify_batch_sharded_local(ctx, Pn, In, rand, 8) == exp
     ctx.close()
 
 
