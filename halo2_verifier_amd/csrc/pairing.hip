@@ -545,6 +545,17 @@ __global__ void __launch_bounds__(PAIR_THREADS) k_pairing(const G1J* __restrict_
 #define PL_MAX_PARTS MSM_MAX_PARTS
 #define PL_MAX_EL (2 * PL_MAX_PARTS)   // sparse pairs per iteration: parts x (doubling, addition)
 struct PairIters { uint8_t first[PAIR_ITERS], cnt[PAIR_ITERS]; };   // iteration -> its lines in the context's tables
+static PairIters pair_iterations() {
+    PairIters its;
+    uint32_t line = 0;
+    for (int i = 63; i >= 0; --i) {
+        const uint32_t cnt = 1u + (uint32_t)((ATE_LOW >> i) & 1);
+        its.first[63 - i] = (uint8_t)line; its.cnt[63 - i] = (uint8_t)cnt;
+        line += cnt;
+    }
+    for (int i = 64; i < PAIR_ITERS; ++i) { its.first[i] = (uint8_t)line++; its.cnt[i] = 1; }
+    return its;
+}
 struct PairLinesShared {
     Coef el0[PL_MAX_EL][6];                         // the tree's elements, ping-pong with u.t.el1
     union {
@@ -662,15 +673,7 @@ int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot*
     int rc = pd.split_lines(shift, parts, &tab);
     if (rc) return rc;
     Fq2* lines = reinterpret_cast<Fq2*>(d_line_ws);
-    PairIters its;
-    uint32_t line = 0;
-    for (int i = 63; i >= 0; --i) {
-        const uint32_t cnt = 1u + (uint32_t)((ATE_LOW >> i) & 1);
-        its.first[63 - i] = (uint8_t)line; its.cnt[63 - i] = (uint8_t)cnt;
-        line += cnt;
-    }
-    for (int i = 64; i < PAIR_ITERS; ++i) { its.first[i] = (uint8_t)line++; its.cnt[i] = 1; }
-    hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, s, d_ready, parts, tab, its, lines);
+    hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, s, d_ready, parts, tab, pair_iterations(), lines);
     // (one_stream: h2v_tuning.pairing_one_stream — the single-stream table over the same lines)
     if (pd.prog2.p && !one_stream) hipLaunchKernelGGL(k_pairing2, dim3(n), dim3(2 * PAIR_THREADS), 0, s, n, pd.consts.p, reinterpret_cast<const uint2*>(pd.prog2.p), pd.n_steps2, (const Fq2*)lines, d_ok);
     else {

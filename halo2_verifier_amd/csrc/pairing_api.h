@@ -42,6 +42,10 @@ struct PairingDevice {
     int upload(const ParamsHost& p);
 };
 
+// the rows of PairingDevice::split_lines on the host: row 2 j + side holds the H2V_PAIRING_LINES line coefficients of 2^(shift j) s_g2
+// (side 0) or 2^(shift j) (-g2) (side 1)
+int split_line_rows(const G2A& sg2, const G2A& ng2, uint32_t shift, uint32_t parts, std::vector<LineCoeff>& rows);
+
 int pairing_check_enqueue(hipStream_t s, const PairingDevice& pd, const G1J* d_pairs, uint32_t n, uint32_t* d_ok);
 // check g over split accumulators: left = sum_j 2^(shift j) piece[(2 g) parts + j], right likewise at 2 g + 1 (MsmSplit), the
 // pieces given line-ready as (X Z, Y, Z^3); d_line_ws: n * H2V_PAIRING_LINE_WS_BYTES of device scratch owned by the caller

@@ -148,12 +148,11 @@ static G2A g2_times_pow2(const G2A& q, uint32_t shift, const PairingConsts& k) {
     const Fq2 zi = r.z.inv();
     return G2A{r.x * zi, r.y * zi, false};
 }
-int PairingDevice::split_lines(uint32_t shift, uint32_t parts, const LineCoeff** out) {
-    std::lock_guard<std::mutex> lock(split_mu);
-    for (const SplitTable& t : split) if (t.shift == shift && t.parts == parts) { *out = t.lines.p; return 0; }
+int split_line_rows(const G2A& sg2, const G2A& ng2, uint32_t shift, uint32_t parts, std::vector<LineCoeff>& rows) {
     const PairingConsts k = pairing_consts_host();
-    std::vector<LineCoeff> rows((size_t)2 * parts * H2V_PAIRING_LINES), one(MAX_LINE_COEFFS);
-    G2A a = h_sg2, b = h_ng2;
+    std::vector<LineCoeff> one(MAX_LINE_COEFFS);
+    rows.assign((size_t)2 * parts * H2V_PAIRING_LINES, LineCoeff{});
+    G2A a = sg2, b = ng2;
     for (uint32_t j = 0; j < parts; ++j) {
         if (j) { a = g2_times_pow2(a, shift, k); b = g2_times_pow2(b, shift, k); }
         const G2A* side[2] = {&a, &b};
@@ -162,8 +161,15 @@ int PairingDevice::split_lines(uint32_t shift, uint32_t parts, const LineCoeff**
             std::copy(one.begin(), one.begin() + H2V_PAIRING_LINES, rows.begin() + (size_t)(2 * j + sd) * H2V_PAIRING_LINES);
         }
     }
+    return 0;
+}
+int PairingDevice::split_lines(uint32_t shift, uint32_t parts, const LineCoeff** out) {
+    std::lock_guard<std::mutex> lock(split_mu);
+    for (const SplitTable& t : split) if (t.shift == shift && t.parts == parts) { *out = t.lines.p; return 0; }
+    std::vector<LineCoeff> rows;
+    int rc = split_line_rows(h_sg2, h_ng2, shift, parts, rows);
+    if (rc) return rc;
     DevBuf<LineCoeff> d;
-    int rc;
     if ((rc = d.alloc(rows.size()))) return rc;
     H2V_HIP_CHECK(hipMemcpy(d.p, rows.data(), sizeof(LineCoeff) * rows.size(), hipMemcpyHostToDevice));
     *out = d.p;

@@ -1,0 +1,263 @@
+// The pairing kernels' device arithmetic on inputs chosen by tests/test_gpu_pairing_units.py: the real pair_step6,
+// pair_coefficients6 (coef_form inside both), pair_in_fq_star6, k_pair_lines and the two check entry points of pairing.hip, fed raw
+// 29-bit limbs so that the Python side picks every representative (Montgomery v 2^261 mod p, or that plus p).  Built with the
+// library's flags by halo2_verifier_amd/csrc/Makefile (build/pairing_units).
+//
+//   pairing_units step    IN OUT          one operation step per workgroup, in k_pairing's layout (128 threads) or as column B of
+//                                         k_pairing2's (256 threads); OUT: the six stored forms of the destination register
+//   pairing_units check   IN OUT          pair_in_fq_star6 of crafted registers
+//   pairing_units lines   PARAMS IN OUT   k_pair_lines over crafted pieces with the split tables of a PairingDevice
+//   pairing_units verdict PARAMS IN OUT   pairing_check_split_enqueue (k_pairing2 or one stream) and pairing_check_enqueue
+// Files are little-endian uint32 words; the layouts are in the readers below.  Every HIP call is checked: the first error ends the
+// program with a non-zero status.  Every index that reaches a kernel is checked on the host first.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+#include "../../halo2_verifier_amd/csrc/pairing.hip"
+#include "../../halo2_verifier_amd/csrc/params.hip"
+
+namespace h2v {
+static std::string g_err;
+void set_last_error(const std::string& s) { g_err = s; }
+}
+using namespace h2v;
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
+#define REQUIRE(c, msg) do { if (!(c)) { fprintf(stderr, "bad input: %s\n", msg); exit(2); } } while (0)
+#define RC(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s: %d %s\n", #x, rc_, g_err.c_str()); exit(4); } } while (0)
+
+static std::vector<uint32_t> slurp_words(const char* path) {
+    std::ifstream f(path, std::ios::binary);
+    REQUIRE(f.good(), "cannot open input");
+    std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    REQUIRE(b.size() % 4 == 0, "input is not whole words");
+    std::vector<uint32_t> w(b.size() / 4);
+    memcpy(w.data(), b.data(), b.size());
+    return w;
+}
+static void spill(const char* path, const void* p, size_t bytes) {
+    FILE* f = fopen(path, "wb");
+    REQUIRE(f && fwrite(p, 1, bytes, f) == bytes && fclose(f) == 0, "cannot write output");
+}
+template <class T> static T* to_device(const T* h, size_t n) {
+    T* d = nullptr;
+    CK(hipMalloc(&d, (n ? n : 1) * sizeof(T)));
+    if (n) CK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+}
+// a cursor over the input words
+struct Words {
+    const std::vector<uint32_t>& w;
+    size_t at = 0;
+    uint32_t next() { REQUIRE(at < w.size(), "input too short"); return w[at++]; }
+    template <class T> void take(T* out, size_t n) {
+        static_assert(sizeof(T) % 4 == 0, "word records");
+        const size_t words = n * sizeof(T) / 4;
+        REQUIRE(at + words <= w.size(), "input too short");
+        memcpy((void*)out, w.data() + at, words * 4);
+        at += words;
+    }
+};
+
+// ---- step: registers 0, 1 come from the pool, register 2 starts as limbs no kernel stores (0xffffffff), the line from the line pool
+#define UNIT_REGS 3
+struct StepCase { uint32_t word, ra, rb, line; };   // operation word (pair_op), pool index of register 0, of register 1, line pool index
+__global__ void __launch_bounds__(2 * PAIR_THREADS) k_units_step(const StepCase* __restrict__ cases, const Coef6 (*__restrict__ pool)[6],
+                                                                  const Fq2 (*__restrict__ lines)[6], const PairingConsts* __restrict__ consts,
+                                                                  uint32_t col, Coef6 (*__restrict__ out)[6]) {
+    __shared__ Coef6 reg[UNIT_REGS][6];
+    __shared__ Fq2 line[1][6];
+    const StepCase c = cases[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    constexpr uint32_t RW = sizeof(Coef6) * 6 / 4, LW = sizeof(Fq2) * 6 / 4;
+    for (uint32_t k = t; k < RW; k += blockDim.x) {
+        reinterpret_cast<uint32_t*>(reg[0])[k] = reinterpret_cast<const uint32_t*>(pool[c.ra])[k];
+        reinterpret_cast<uint32_t*>(reg[1])[k] = reinterpret_cast<const uint32_t*>(pool[c.rb])[k];
+        reinterpret_cast<uint32_t*>(reg[2])[k] = 0xffffffffu;
+    }
+    for (uint32_t k = t; k < LW; k += blockDim.x) reinterpret_cast<uint32_t*>(line[0])[k] = reinterpret_cast<const uint32_t*>(lines[c.line])[k];
+    __syncthreads();
+    const uint32_t op = c.word & 255u, rd = (c.word >> 8) & 255u, ra = (c.word >> 16) & 255u, rb = c.word >> 24;
+    if (t / PAIR_THREADS == col) {   // the group that runs the step: all of k_pairing's block, or the second half of k_pairing2's
+        const uint32_t tl = t % PAIR_THREADS;
+        if (op <= P_MULL) pair_step6(op, rd, ra, rb, line, reg, tl);
+        else pair_coefficients6(op, rd, ra, reg, consts, tl);
+    }
+    __syncthreads();
+    for (uint32_t k = t; k < RW; k += blockDim.x) reinterpret_cast<uint32_t*>(out[blockIdx.x])[k] = reinterpret_cast<const uint32_t*>(reg[rd])[k];
+}
+
+// IN: n_pool, n_lines, n_a (k_pairing layout), n_b (column B), pool[n_pool] (Coef6[6]), lines[n_lines] (Fq2[6]), cases[n_a + n_b]
+// OUT: the destination register (Coef6[6]) of every case, in input order
+static int mode_step(const char* in, const char* outp) {
+    const std::vector<uint32_t> w = slurp_words(in);
+    Words r{w};
+    const uint32_t n_pool = r.next(), n_lines = r.next(), n_a = r.next(), n_b = r.next();
+    REQUIRE(n_pool && n_lines && n_pool < (1u << 24) && n_lines < (1u << 24) && (size_t)n_a + n_b < (1u << 24), "sizes");
+    std::vector<Coef6> pool((size_t)n_pool * 6);
+    std::vector<Fq2> lines((size_t)n_lines * 6);
+    std::vector<StepCase> cases((size_t)n_a + n_b);
+    r.take(pool.data(), pool.size()); r.take(lines.data(), lines.size()); r.take(cases.data(), cases.size());
+    REQUIRE(r.at == w.size(), "trailing input");
+    for (const StepCase& c : cases) {
+        const uint32_t op = c.word & 255u, rd = (c.word >> 8) & 255u, ra = (c.word >> 16) & 255u, rb = c.word >> 24;
+        const bool known = op == P_SQR || op == P_MUL || op == P_MULL || op == P_CONJ || op == P_CONJ0 || op == P_COPY || op == P_FROB ||
+                           op == P_FROB2 || op == P_FROB3 || op == P_FROB4;
+        REQUIRE(known && rd < UNIT_REGS && ra < UNIT_REGS, "operation word");
+        REQUIRE(op == P_MULL ? rb == 0 : (op == P_MUL ? rb < UNIT_REGS : rb == 0), "operand b");
+        REQUIRE(c.ra < n_pool && c.rb < n_pool && c.line < n_lines, "pool index");
+    }
+    const PairingConsts k = pairing_consts_host();
+    PairingConsts* d_k = to_device(&k, 1);
+    auto* d_pool = reinterpret_cast<const Coef6(*)[6]>(to_device(pool.data(), pool.size()));
+    auto* d_lines = reinterpret_cast<const Fq2(*)[6]>(to_device(lines.data(), lines.size()));
+    StepCase* d_cases = to_device(cases.data(), cases.size());
+    Coef6* d_out = nullptr;
+    CK(hipMalloc(&d_out, (cases.size() ? cases.size() : 1) * 6 * sizeof(Coef6)));
+    auto* out6 = reinterpret_cast<Coef6(*)[6]>(d_out);
+    if (n_a) hipLaunchKernelGGL(k_units_step, dim3(n_a), dim3(PAIR_THREADS), 0, 0, d_cases, d_pool, d_lines, d_k, 0u, out6);
+    CK(hipGetLastError());
+    if (n_b) hipLaunchKernelGGL(k_units_step, dim3(n_b), dim3(2 * PAIR_THREADS), 0, 0, d_cases + n_a, d_pool, d_lines, d_k, 1u, out6 + n_a);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<Coef6> out(cases.size() * 6);
+    if (!out.empty()) CK(hipMemcpy(out.data(), d_out, out.size() * sizeof(Coef6), hipMemcpyDeviceToHost));
+    spill(outp, out.data(), out.size() * sizeof(Coef6));
+    printf("step: %u + %u cases\n", n_a, n_b);
+    return 0;
+}
+
+// ---- check: IN: n, registers[n] (Coef6[6]); OUT: n words, pair_in_fq_star6
+__global__ void k_units_check(const Coef6 (*__restrict__ x)[6], uint32_t n, uint32_t* __restrict__ ok) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ok[i] = pair_in_fq_star6(x[i]) ? 1u : 0u;
+}
+static int mode_check(const char* in, const char* outp) {
+    const std::vector<uint32_t> w = slurp_words(in);
+    Words r{w};
+    const uint32_t n = r.next();
+    REQUIRE(n && n < (1u << 20), "sizes");
+    std::vector<Coef6> regs((size_t)n * 6);
+    r.take(regs.data(), regs.size());
+    REQUIRE(r.at == w.size(), "trailing input");
+    auto* d_regs = reinterpret_cast<const Coef6(*)[6]>(to_device(regs.data(), regs.size()));
+    uint32_t* d_ok = nullptr;
+    CK(hipMalloc(&d_ok, n * 4));
+    hipLaunchKernelGGL(k_units_check, dim3((n + 63) / 64), dim3(64), 0, 0, d_regs, n, d_ok);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<uint32_t> ok(n);
+    CK(hipMemcpy(ok.data(), d_ok, n * 4, hipMemcpyDeviceToHost));
+    spill(outp, ok.data(), n * 4);
+    printf("check: %u registers\n", n);
+    return 0;
+}
+
+static void upload_params(const char* path, PairingDevice& pd) {
+    const std::vector<uint32_t> w = slurp_words(path);
+    ParamsHost params;
+    std::string err;
+    if (!params_from_bytes(reinterpret_cast<const uint8_t*>(w.data()), w.size() * 4, H2V_SERDE_RAW_BYTES, params, err)) { fprintf(stderr, "params: %s\n", err.c_str()); exit(2); }
+    RC(pd.upload(params));
+}
+// pieces of n checks over `parts` split accumulators, G1J each (X Z, Y, Z^3 for the split entry points), into G1JSlot
+static G1JSlot* read_slots(Words& r, size_t count) {
+    std::vector<G1J> pts(count);
+    r.take(pts.data(), count);
+    std::vector<G1JSlot> slots(count);
+    for (size_t i = 0; i < count; ++i) slots[i] = pts[i];
+    return to_device(slots.data(), count);
+}
+
+// ---- lines: IN: n_jobs, then per job: shift, parts, n, pieces[n * 2 * parts] (check c: L_j at (2c) parts + j, R_j at (2c + 1) parts + j)
+// OUT: per job, k_pair_lines' output: n x PAIR_ITERS x 6 Fq2;  OUT.tables: per job, the host rows of its table (split_line_rows)
+static int mode_lines(const char* params, const char* in, const char* outp) {
+    PairingDevice pd;
+    upload_params(params, pd);
+    const std::vector<uint32_t> w = slurp_words(in);
+    Words r{w};
+    const uint32_t jobs = r.next();
+    std::vector<Fq2> all;
+    std::vector<LineCoeff> all_rows;
+    for (uint32_t jb = 0; jb < jobs; ++jb) {
+        const uint32_t shift = r.next(), parts = r.next(), n = r.next();
+        REQUIRE(parts >= 1 && parts <= PL_MAX_PARTS && n >= 1 && n <= 64 && shift < 256, "lines job");
+        G1JSlot* d_ready = read_slots(r, (size_t)2 * parts * n);
+        const LineCoeff* tab = nullptr;
+        RC(pd.split_lines(shift, parts, &tab));
+        std::vector<LineCoeff> rows;
+        RC(split_line_rows(pd.h_sg2, pd.h_ng2, shift, parts, rows));
+        all_rows.insert(all_rows.end(), rows.begin(), rows.end());
+        Fq2* d_out = nullptr;
+        CK(hipMalloc(&d_out, (size_t)n * PAIR_ITERS * 6 * sizeof(Fq2)));
+        hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, 0, d_ready, parts, tab, pair_iterations(), d_out);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        const size_t at = all.size();
+        all.resize(at + (size_t)n * PAIR_ITERS * 6);
+        CK(hipMemcpy(all.data() + at, d_out, (size_t)n * PAIR_ITERS * 6 * sizeof(Fq2), hipMemcpyDeviceToHost));
+        CK(hipFree(d_out));
+        CK(hipFree(d_ready));
+    }
+    REQUIRE(r.at == w.size(), "trailing input");
+    spill(outp, all.data(), all.size() * sizeof(Fq2));
+    spill((std::string(outp) + ".tables").c_str(), all_rows.data(), all_rows.size() * sizeof(LineCoeff));
+    printf("lines: %u jobs\n", jobs);
+    return 0;
+}
+
+// ---- verdict: IN: n_jobs, then per job: kind (0: split, k_pairing2; 1: split, one stream; 2: whole points), shift, parts, n,
+// pieces (split: n * 2 * parts line-ready pieces as in `lines`; whole: n pairs of Jacobian points); OUT: the n verdicts of every job
+static int mode_verdict(const char* params, const char* in, const char* outp) {
+    PairingDevice pd;
+    upload_params(params, pd);
+    const std::vector<uint32_t> w = slurp_words(in);
+    Words r{w};
+    const uint32_t jobs = r.next();
+    std::vector<uint32_t> all;
+    for (uint32_t jb = 0; jb < jobs; ++jb) {
+        const uint32_t kind = r.next(), shift = r.next(), parts = r.next(), n = r.next();
+        REQUIRE(kind <= 2 && n >= 1 && n <= 64 && shift < 256, "verdict job");
+        uint32_t* d_ok = nullptr;
+        CK(hipMalloc(&d_ok, n * 4));
+        CK(hipMemset(d_ok, 0xff, n * 4));
+        if (kind == 2) {
+            std::vector<G1J> pairs((size_t)2 * n);
+            r.take(pairs.data(), pairs.size());
+            G1J* d_pairs = to_device(pairs.data(), pairs.size());
+            RC(pairing_check_enqueue(0, pd, d_pairs, n, d_ok));
+            CK(hipDeviceSynchronize());
+            CK(hipFree(d_pairs));
+        } else {
+            REQUIRE(parts >= 1 && parts <= PL_MAX_PARTS, "verdict parts");
+            G1JSlot* d_ready = read_slots(r, (size_t)2 * parts * n);
+            void* d_ws = nullptr;
+            CK(hipMalloc(&d_ws, (size_t)n * H2V_PAIRING_LINE_WS_BYTES));
+            RC(pairing_check_split_enqueue(0, pd, d_ready, n, parts, shift, d_ws, d_ok, kind == 1));
+            CK(hipDeviceSynchronize());
+            CK(hipFree(d_ws));
+            CK(hipFree(d_ready));
+        }
+        const size_t at = all.size();
+        all.resize(at + n);
+        CK(hipMemcpy(all.data() + at, d_ok, n * 4, hipMemcpyDeviceToHost));
+        CK(hipFree(d_ok));
+    }
+    REQUIRE(r.at == w.size(), "trailing input");
+    spill(outp, all.data(), all.size() * 4);
+    printf("verdict: %u jobs\n", jobs);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "step" && argc == 4) return mode_step(argv[2], argv[3]);
+    if (mode == "check" && argc == 4) return mode_check(argv[2], argv[3]);
+    if (mode == "lines" && argc == 5) return mode_lines(argv[2], argv[3], argv[4]);
+    if (mode == "verdict" && argc == 5) return mode_verdict(argv[2], argv[3], argv[4]);
+    fprintf(stderr, "usage: pairing_units step|check IN OUT | lines|verdict PARAMS IN OUT\n");
+    return 2;
+}
