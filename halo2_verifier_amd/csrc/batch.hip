@@ -1201,13 +1201,7 @@ int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const ui
         // reorder squeeze order -> [user challenges.., theta, beta, gamma, y, x, y', v, u]
         size_t nc = pl.n_challenges;
         if (nc > *n_challenges) { set_last_error("h2v_guard_msm: challenge capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
-        // squeeze order is the transcript order; user challenges are interleaved by phase. Rebuild the map as compile_plan did.
-        const VkHost& vk = ctx->vk->vk;
-        std::vector<uint32_t> order;
-        uint8_t max_phase = 0; for (uint8_t p2 : vk.advice_column_phase) max_phase = std::max(max_phase, p2);
-        for (unsigned ph = 0; ph <= max_phase; ++ph) for (uint32_t i = 0; i < vk.num_challenges; ++i) if (vk.challenge_phase[i] == ph) order.push_back(i);
-        for (uint32_t i = 0; i + vk.num_challenges < nc; ++i) order.push_back(vk.num_challenges + i);
-        for (size_t q = 0; q < order.size() && q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * order[q]);
+        for (size_t q = 0; q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * pl.squeeze_order[q]);
         *n_challenges = nc;
     }
     return 0;

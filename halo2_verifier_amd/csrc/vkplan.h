@@ -90,7 +90,8 @@ struct Plan {
     std::vector<std::pair<uint8_t, uint32_t>> left_term_order;  // reference order of the left channel's terms
     // transcript
     std::vector<TranscriptSrc> stream;     // absorbed byte stream incl. the 0x00 challenge markers
-    std::vector<uint32_t> squeeze_at;      // stream length at which challenge i is squeezed
+    std::vector<uint32_t> squeeze_at;      // stream length at which the i-th squeeze happens
+    std::vector<uint32_t> squeeze_order;   // challenge id of the i-th squeeze (a user challenge of a phase no advice column has is never squeezed)
     uint32_t n_challenges = 0;             // user challenges + theta, beta, gamma, y, x, y', v, u
     uint32_t n_user_challenges = 0;
     // program

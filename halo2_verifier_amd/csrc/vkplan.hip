@@ -231,21 +231,21 @@ struct Builder {
     // Fewer live values = fewer slots = all of them in LDS (k_frvm).
     static bool is_load(uint32_t op) { return op == OP_LOAD_SCALAR || op == OP_LOAD_INST || op == OP_LOAD_CHAL || op == OP_LOAD_MULT || op == OP_LOAD_INSTEVAL; }
     static bool takes_const_operands(uint32_t op) { return op == OP_MUL || op == OP_ADD || op == OP_SUB; }
+    static int n_operands(uint32_t op) {
+        switch (op) {
+            case OP_MUL: case OP_ADD: case OP_SUB: return 2;
+            case OP_NEG: case OP_INV: case OP_POW: case OP_SQRN: case OP_STORE_MSM: case OP_STORE_SHARED: case OP_STORE_LEFT: case OP_STORE_GUARD: return 1;
+            default: return 0;
+        }
+    }
     void emit(std::vector<VmInstr>& code, uint32_t& n_slots) const {
         const size_t n = nodes.size();
-        auto n_operands = [&](const Node& nd) -> int {
-            switch (nd.op) {
-                case OP_MUL: case OP_ADD: case OP_SUB: return 2;
-                case OP_NEG: case OP_INV: case OP_POW: case OP_SQRN: case OP_STORE_MSM: case OP_STORE_SHARED: case OP_STORE_LEFT: case OP_STORE_GUARD: return 1;
-                default: return 0;
-            }
-        };
         std::vector<Val> order;
         std::vector<char> emitted(n, 0);
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes[i];
             if (nd.op == OP_CONST || is_load(nd.op)) continue;   // on demand
-            const int k = n_operands(nd);
+            const int k = n_operands(nd.op);
             for (int j = 0; j < k; ++j) {
                 const Val v = j == 0 ? nd.a : nd.b;
                 if (emitted[v]) continue;
@@ -259,7 +259,7 @@ struct Builder {
         for (size_t q = 0; q < m; ++q) pos[order[q]] = q;
         for (size_t q = 0; q < m; ++q) {
             const Node& nd = nodes[order[q]];
-            const int k = n_operands(nd);
+            const int k = n_operands(nd.op);
             for (int j = 0; j < k; ++j) { const Val v = j == 0 ? nd.a : nd.b; if (emitted[v]) last_use[v] = std::max(last_use[v], q); }
         }
         std::vector<uint32_t> slot(n, 0), free_list;
@@ -319,13 +319,6 @@ struct Builder {
     void emit_streams(const int K, std::vector<VmInstr>* code, uint32_t& n_slots) const {
         const size_t n = nodes.size();
         const double BAR = 0.3;   // what the scheduler charges for a barrier, in products (swept in round 2: 0.1 .. 2.0, flat around 0.3)
-        auto n_operands = [&](const Node& nd) -> int {
-            switch (nd.op) {
-                case OP_MUL: case OP_ADD: case OP_SUB: return 2;
-                case OP_NEG: case OP_INV: case OP_POW: case OP_SQRN: case OP_STORE_MSM: case OP_STORE_SHARED: case OP_STORE_LEFT: case OP_STORE_GUARD: return 1;
-                default: return 0;
-            }
-        };
         auto is_compute = [&](Val v) { return nodes[v].op != OP_CONST && !is_load(nodes[v].op); };
         auto inline_const = [&](const Node& consumer, Val v) { return nodes[v].op == OP_CONST && takes_const_operands(consumer.op); };
         auto operand = [&](Val v, int j) -> Val { return j ? nodes[v].b : nodes[v].a; };
@@ -341,7 +334,7 @@ struct Builder {
         // the compute nodes v has to wait for: its operands, and for a status-reading store the inversions
         auto deps = [&](Val v) -> std::vector<Val> {
             std::vector<Val> d;
-            for (int j = 0; j < n_operands(nodes[v]); ++j) { const Val u = operand(v, j); if (is_compute(u) && distinct(v, j)) d.push_back(u); }
+            for (int j = 0; j < n_operands(nodes[v].op); ++j) { const Val u = operand(v, j); if (is_compute(u) && distinct(v, j)) d.push_back(u); }
             if (reads_status(v)) for (Val u : inv_nodes) if (std::find(d.begin(), d.end(), u) == d.end()) d.push_back(u);
             return d;
         };
@@ -395,7 +388,7 @@ struct Builder {
             return pl;
         };
         auto append = [&](int q, Val v) {
-            for (int j = 0; j < n_operands(nodes[v]); ++j) {
+            for (int j = 0; j < n_operands(nodes[v].op); ++j) {
                 const Val u = operand(v, j);
                 if (is_compute(u) || inline_const(nodes[v], u) || loaded[q][u]) continue;
                 clk[q] += op_weight(nodes[u]); items[q].push_back({1, u, clk[q]}); loaded[q][u] = 1;
@@ -417,7 +410,7 @@ struct Builder {
                     if (bl[ready[r]] < top - SLACK) continue;
                     const Node& nd = nodes[ready[r]];
                     bool uses = false;
-                    for (int j = 0; j < n_operands(nd); ++j) if ((j ? nd.b : nd.a) == last_node) uses = true;
+                    for (int j = 0; j < n_operands(nd.op); ++j) if ((j ? nd.b : nd.a) == last_node) uses = true;
                     if (uses && (loc == (size_t)-1 || bl[ready[r]] > bl[ready[loc]])) loc = r;
                 }
                 if (loc != (size_t)-1) best = loc;
@@ -481,7 +474,7 @@ struct Builder {
                     last_epoch[id] = std::max(last_epoch[id], ep);
                     if (owner[id] == q) last_pos[id] = k;
                 };
-                if (it.kind == 0) for (int j = 0; j < n_operands(nd); ++j) { const Val u = j ? nd.b : nd.a; if (!inline_const(nd, u)) touch(value_of(u, q)); }
+                if (it.kind == 0) for (int j = 0; j < n_operands(nd.op); ++j) { const Val u = j ? nd.b : nd.a; if (!inline_const(nd, u)) touch(value_of(u, q)); }
                 if (nd.has_result) { const size_t id = it.kind == 1 ? value_of(it.v, q) : (size_t)it.v; has_def[id] = 1; touch(id); }
             }
         }
@@ -516,7 +509,7 @@ struct Builder {
                         default: in.a = opnd(nd.a); in.b = nd.imm; break;   // POW / SQRN / STORE_*
                     }
                     // private operands that die here free their slots first: the interpreter reads before it writes
-                    if (it.kind == 0) for (int j = 0; j < n_operands(nd); ++j) {
+                    if (it.kind == 0) for (int j = 0; j < n_operands(nd.op); ++j) {
                         const Val u = j ? nd.b : nd.a;
                         if (inline_const(nd, u) || (j == 1 && nd.b == nd.a)) continue;
                         const size_t id = value_of(u, q);
@@ -540,341 +533,354 @@ struct Builder {
         }
         n_slots = next ? next : 1;
     }
-};
 
-enum CommitKind { K_ADVICE, K_PERM_PRODUCT, K_LOOKUP, K_SHUFFLE, K_FIXED, K_PERM_COMMON, K_H_MSM, K_RANDOM };
-struct CommitRef {
-    int kind, idx, inst;   // inst: the circuit instance the commitment belongs to (0 for the VK-wide ones)
-    bool operator==(const CommitRef& o) const { return kind == o.kind && idx == o.idx && inst == o.inst; }
+    // diagnostics kept with the plan (tests/cpp/plan_host.hip prints them): the DAG's work and critical path in units of one Fr product
+    void dag_costs(double& work, double& critical_path) const {
+        std::vector<double> depth(nodes.size(), 0.0);
+        work = 0; critical_path = 0;
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            const Node& nd = nodes[i];
+            const int k = n_operands(nd.op);
+            const double w = nd.op == OP_CONST ? 0.0 : op_weight(nd);
+            depth[i] = (k == 0 ? 0.0 : k == 1 ? depth[nd.a] : std::max(depth[nd.a], depth[nd.b])) + w;
+            work += w; critical_path = std::max(critical_path, depth[i]);
+        }
+    }
 };
-struct SymQuery { CommitRef c; int64_t rot; Val eval; };  // point = x * omega^rot (rot normalised mod n)
-}  // namespace
 
 // =============================================================================== plan compiler
-int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<size_t>& col_lens, PlanOptions opts, Plan& plan, std::string& err) {
-    plan.opts = opts;
-    const bool gwc = opts.multiopen == H2V_MULTIOPEN_GWC;
+// compile_plan follows the phases of verify_proof (lib.rs:33-425).  Builder nodes are numbered in creation order and the emitted
+// programs follow that numbering, so the order of the Builder calls below is part of the plan.
+struct Shape {   // the counts of the VK, the options and the instance shape
+    bool gwc;
+    size_t M, NIC, A, L, Sh, P, chunk, nsets, H, Qa, Qf, Qi, Ch, bf, total_inst;
+    uint8_t max_phase;
+    // challenge ids: the user's, then theta, beta, gamma, y, x; SHPLONK squeezes y', v, u (shplonk.rs:195-199), GWC v, u (gwc.rs:73-83)
+    uint32_t C_THETA, C_BETA, C_GAMMA, C_Y, C_X, C_SY, C_SV, C_SU;
+};
+
+int check_shape(const VkHost& vk, const ParamsHost& params, const std::vector<size_t>& col_lens, const PlanOptions& opts, Plan& plan, Shape& s, std::string& err) {
+    s.gwc = opts.multiopen == H2V_MULTIOPEN_GWC;
     if (opts.multiopen < 0 || opts.multiopen > 1 || opts.transcript < 0 || opts.transcript > 1) { err = "unknown multiopen / transcript option"; return H2V_ERR_BAD_ARGUMENT; }
     // M circuit instances share the transcript (`instances: &[&[&[Fr]]]`, lib.rs:33-55): col_lens is instance-major, M x columns
-    const size_t M = opts.circuit_instances > 0 ? (size_t)opts.circuit_instances : 1;
-    if (col_lens.size() != M * vk.num_instance_columns) { err = "instances do not match the VK's instance column count"; return H2V_ERR_INVALID_INSTANCES; }
-    const size_t NIC = vk.num_instance_columns;
+    s.M = opts.circuit_instances > 0 ? (size_t)opts.circuit_instances : 1;
+    s.NIC = vk.num_instance_columns;
+    if (col_lens.size() != s.M * s.NIC) { err = "instances do not match the VK's instance column count"; return H2V_ERR_INVALID_INSTANCES; }
     if (params.k != vk.k) { err = "params.k differs from vk.k"; return H2V_ERR_BAD_ARGUMENT; }
-    const uint64_t n = 1ULL << vk.k;
-    size_t total_inst = 0;
-    for (size_t l : col_lens) total_inst += l;
-    if (total_inst > (1u << 20)) { err = "more than 2^20 instance values per proof are not supported by this build"; return H2V_ERR_INSTANCE_TOO_LARGE; }
-    for (size_t l : col_lens) if (l > n) { err = "instance column longer than the domain"; return H2V_ERR_INSTANCE_TOO_LARGE; }
-    plan.col_lens = col_lens; plan.n_instance_values = (uint32_t)total_inst;
+    s.total_inst = 0;
+    for (size_t l : col_lens) s.total_inst += l;
+    if (s.total_inst > (1u << 20)) { err = "more than 2^20 instance values per proof are not supported by this build"; return H2V_ERR_INSTANCE_TOO_LARGE; }
+    for (size_t l : col_lens) if (l > (1ULL << vk.k)) { err = "instance column longer than the domain"; return H2V_ERR_INSTANCE_TOO_LARGE; }
+    plan.col_lens = col_lens; plan.n_instance_values = (uint32_t)s.total_inst;
     {   // h2v_options.instance_kernel_threshold overrides the bound (tests force the kernel path on small circuits with 1)
         const size_t threshold = opts.instance_kernel_threshold > 0 ? (size_t)opts.instance_kernel_threshold - 1 : 1024;
-        plan.wide_instances = total_inst > threshold;
+        plan.wide_instances = s.total_inst > threshold;
     }
+    s.A = vk.num_advice_columns; s.L = vk.lookups.size(); s.Sh = vk.shuffles.size(); s.P = vk.permutation_columns.size();
+    s.chunk = vk.cs_degree - 2; s.nsets = s.P == 0 ? 0 : (s.P + s.chunk - 1) / s.chunk; s.H = vk.cs_degree - 1;
+    s.Qa = vk.advice_queries.size(); s.Qf = vk.fixed_queries.size(); s.Qi = vk.instance_queries.size(); s.Ch = vk.num_challenges;
+    s.bf = vk.blinding_factors();
+    s.max_phase = 0;
+    for (uint8_t p : vk.advice_column_phase) s.max_phase = std::max(s.max_phase, p);
+    if (vk.advice_column_phase.size() != s.A || vk.challenge_phase.size() != s.Ch || vk.fixed_commitments.size() < vk.num_fixed_columns) { err = "inconsistent VK"; return H2V_ERR_FORMAT; }
+    // a proof of this VK: Np points, Ns scalars.  The layout tables are linear in them; a key that asks for more
+    // than 2^16 of either is refused rather than laid out (real keys: tens to hundreds)
+    const uint64_t np_total = (uint64_t)s.M * (s.A + 3 * s.L + s.Sh + s.nsets) + 1 + s.H + 2 + 64;
+    const uint64_t ns_total = (uint64_t)s.M * (s.Qa + 3 * s.nsets + 5 * s.L + 2 * s.Sh) + s.Qf + 1 + s.P;
+    if (np_total > 65536 || ns_total > 65536) { err = "a proof of this VerifyingKey has more than 65536 points or scalars: not supported by this build"; return H2V_ERR_UNSUPPORTED; }
+    for (const QueryH& q : vk.instance_queries) if (q.column.index >= s.NIC) { err = "instance query names a missing column"; return H2V_ERR_FORMAT; }
+    for (const QueryH& q : vk.advice_queries) if (q.column.index >= s.A) { err = "advice query names a missing column"; return H2V_ERR_FORMAT; }
+    for (const QueryH& q : vk.fixed_queries) if (q.column.index >= vk.fixed_commitments.size()) { err = "fixed query names a missing column"; return H2V_ERR_FORMAT; }
+    s.C_THETA = (uint32_t)s.Ch; s.C_BETA = s.C_THETA + 1; s.C_GAMMA = s.C_THETA + 2; s.C_Y = s.C_THETA + 3; s.C_X = s.C_THETA + 4;
+    s.C_SY = s.C_THETA + 5; s.C_SV = s.gwc ? s.C_THETA + 5 : s.C_THETA + 6; s.C_SU = s.C_SV + 1;
+    return 0;
+}
 
-    const size_t A = vk.num_advice_columns, L = vk.lookups.size(), Sh = vk.shuffles.size(), P = vk.permutation_columns.size();
-    const size_t chunk = vk.cs_degree - 2, nsets = P == 0 ? 0 : (P + chunk - 1) / chunk, H = vk.cs_degree - 1;
-    const size_t Qa = vk.advice_queries.size(), Qf = vk.fixed_queries.size(), Ch = vk.num_challenges;
-    const size_t bf = vk.blinding_factors();
-    uint8_t max_phase = 0;
-    for (uint8_t p : vk.advice_column_phase) max_phase = std::max(max_phase, p);
-    if (vk.advice_column_phase.size() != A || vk.challenge_phase.size() != Ch || vk.fixed_commitments.size() < vk.num_fixed_columns) { err = "inconsistent VK"; return H2V_ERR_FORMAT; }
-
-    // ---------------- domain constants (poly/domain.rs:34-140)
-    Fr omega;
-    {
+struct Domain {   // poly/domain.rs:34-140
+    uint64_t n;
+    Fr omega, omega_inv, n_inv, delta;
+    explicit Domain(uint32_t k) : n(1ULL << k) {
         // ROOT_OF_UNITY = 7^((r-1)/2^28); omega = ROOT_OF_UNITY^(2^(28-k))
         uint32_t e[8]; for (int i = 0; i < 8; ++i) e[i] = FrParams::P(i);
         e[0] -= 1;
         for (int i = 0; i < 8; ++i) e[i] = (e[i] >> 28) | (i < 7 ? (e[i + 1] << 4) : 0);
         omega = Fr::from_u32(7).pow_limbs(e);
-        for (uint32_t i = vk.k; i < 28; ++i) omega = omega.sqr();
+        for (uint32_t i = k; i < 28; ++i) omega = omega.sqr();
+        omega_inv = omega.inv();
+        n_inv = Fr::from_u32((uint32_t)n).inv();  // k <= 28
+        delta = Fr::from_u32(7);
+        for (int i = 0; i < 28; ++i) delta = delta.sqr();  // DELTA = 7^(2^28)
     }
-    const Fr omega_inv = omega.inv();
-    const Fr n_inv = Fr::from_u32((uint32_t)n).inv();  // k <= 28
-    Fr delta = Fr::from_u32(7);
-    for (int i = 0; i < 28; ++i) delta = delta.sqr();  // DELTA = 7^(2^28)
-    auto omega_pow = [&](int64_t r) {
-        Fr base = r >= 0 ? omega : omega_inv;
+    Fr pow(int64_t r) const {   // omega^r
+        Fr base = r >= 0 ? omega : omega_inv, acc = Fr::one();
         uint64_t e = (uint64_t)(r >= 0 ? r : -r);
-        Fr acc = Fr::one();
         for (int i = 63; i >= 0; --i) { acc = acc.sqr(); if ((e >> i) & 1) acc = acc * base; }
         return acc;
-    };
-    auto norm_rot = [&](int64_t r) { int64_t m = (int64_t)n; return ((r % m) + m) % m; };
-
-    // a proof of this VK: Np points, Ns scalars.  The layout tables below are linear in them; a key that asks for more
-    // than 2^16 of either is refused rather than laid out (real keys: tens to hundreds)
-    {
-        const uint64_t np_total = (uint64_t)M * (A + 3 * L + Sh + nsets) + 1 + H + 2 + 64;
-        const uint64_t ns_total = (uint64_t)M * (Qa + 3 * nsets + 5 * L + 2 * Sh) + Qf + 1 + P;
-        if (np_total > 65536 || ns_total > 65536) { err = "a proof of this VerifyingKey has more than 65536 points or scalars: not supported by this build"; return H2V_ERR_UNSUPPORTED; }
     }
-    // ---------------- proof layout + transcript stream
-    // point slots; the per-instance ones are indexed [m * count + i]
-    std::vector<uint32_t> advice_slot(M * A, 0), lk_input_slot(M * L), lk_table_slot(M * L), lk_product_slot(M * L), sh_slot(M * Sh), perm_slot(M * nsets), h_slot(H);
-    uint32_t random_slot = 0;
-    uint32_t np = 0, nsc = 0, off = 0;
-    std::vector<uint32_t> squeeze_order;  // challenge id of each squeeze
-    auto emit_const = [&](uint8_t b) { plan.stream.push_back({TranscriptSrc::CONST, b, 0}); };
-    auto absorb_point = [&]() -> uint32_t {
-        uint32_t slot = np++;
+    int64_t norm(int64_t r) const { int64_t m = (int64_t)n; return ((r % m) + m) % m; }
+};
+
+// ---------------- proof layout: point slots and scalar indices, per circuit instance and VK-wide
+struct PermSetLayout { uint32_t slot, eval, next, last; };   // `last`: every set but the final one
+struct LookupLayout { uint32_t input_slot, table_slot, product_slot, product, product_next, input, input_inv, table; };
+struct ShuffleLayout { uint32_t slot, product, product_next; };
+struct InstanceLayout {
+    std::vector<uint32_t> advice_slot, advice_eval;   // by advice column / by advice query
+    std::vector<PermSetLayout> perm;
+    std::vector<LookupLayout> lookups;
+    std::vector<ShuffleLayout> shuffles;
+};
+struct VkLayout {
+    std::vector<uint32_t> h_slot, fixed_eval, sigma_eval;
+    uint32_t random_slot = 0, random_eval = 0;
+    std::vector<int64_t> gwc_points;   // GWC: the distinct opening points, and the witness point read for each (gwc.rs:138-163)
+    std::vector<uint32_t> gwc_w_slot;  // (SHPLONK: Plan::slot_h1, slot_h2)
+};
+
+// appends to the plan's proof layout and absorbed stream
+struct Transcript {
+    Plan& plan;
+    void constant(uint8_t b) { plan.stream.push_back({TranscriptSrc::CONST, b, 0}); }
+    uint32_t point() {
+        const uint32_t slot = (uint32_t)plan.point_offsets.size(), off = plan.proof_len;
         plan.point_offsets.push_back(off);
-        emit_const(1);
+        constant(1);
         for (uint32_t i = 0; i < 32; ++i) plan.stream.push_back({(uint8_t)(i == 31 ? TranscriptSrc::PROOF_MASKED : TranscriptSrc::PROOF), 0, off + i});
         for (uint32_t i = 0; i < 32; ++i) plan.stream.push_back({TranscriptSrc::YCOORD, 0, slot * 32 + i});
-        off += 32;
+        plan.proof_len += 32;
         return slot;
-    };
-    auto absorb_scalar = [&]() -> uint32_t {
-        uint32_t idx = nsc++;
+    }
+    uint32_t scalar() {
+        const uint32_t idx = (uint32_t)plan.scalar_offsets.size(), off = plan.proof_len;
         plan.scalar_offsets.push_back(off);
-        emit_const(2);
+        constant(2);
         for (uint32_t i = 0; i < 32; ++i) plan.stream.push_back({TranscriptSrc::PROOF, 0, off + i});
-        off += 32;
+        plan.proof_len += 32;
         return idx;
-    };
-    auto squeeze = [&](uint32_t chal_id) {
-        emit_const(0);
+    }
+    void squeeze(uint32_t chal_id) {
+        constant(0);
         plan.squeeze_at.push_back((uint32_t)plan.stream.size());
-        squeeze_order.push_back(chal_id);
-    };
-    // SHPLONK squeezes y', v, u (shplonk.rs:195-199); GWC squeezes v, u (gwc.rs:73-83)
-    const uint32_t C_THETA = (uint32_t)Ch, C_BETA = C_THETA + 1, C_GAMMA = C_THETA + 2, C_Y = C_THETA + 3, C_X = C_THETA + 4;
-    const uint32_t C_SY = C_THETA + 5, C_SV = gwc ? C_THETA + 5 : C_THETA + 6, C_SU = C_SV + 1;
-    plan.n_user_challenges = (uint32_t)Ch; plan.n_challenges = C_SU + 1;
-    if (opts.transcript == H2V_TRANSCRIPT_KECCAK256)   // Keccak256Read::init absorbs the label (transcript/mod.rs:143-145)
-        for (const char* c = "Halo2-Transcript"; *c; ++c) emit_const((uint8_t)*c);
+        plan.squeeze_order.push_back(chal_id);
+    }
+};
+
+// everything up to the multi-open part (lib.rs:76-253)
+void lay_out_proof(const VkHost& vk, const Shape& s, int transcript, Transcript& tr, std::vector<InstanceLayout>& inst, VkLayout& vkl) {
+    Plan& plan = tr.plan;
+    plan.n_user_challenges = (uint32_t)s.Ch; plan.n_challenges = s.C_SU + 1;
+    if (transcript == H2V_TRANSCRIPT_KECCAK256)   // Keccak256Read::init absorbs the label (transcript/mod.rs:143-145)
+        for (const char* c = "Halo2-Transcript"; *c; ++c) tr.constant((uint8_t)*c);
     {   // vk.hash_into + instances (plonk/vk.rs:145-152, lib.rs:76-82)
         uint8_t repr[32]; vk.transcript_repr.to_bytes(repr);
-        emit_const(2);
-        for (int i = 0; i < 32; ++i) emit_const(repr[i]);
-        for (uint32_t v = 0; v < total_inst; ++v) { emit_const(2); for (uint32_t i = 0; i < 32; ++i) plan.stream.push_back({TranscriptSrc::INSTANCE, 0, v * 32 + i}); }
+        tr.constant(2);
+        for (int i = 0; i < 32; ++i) tr.constant(repr[i]);
+        for (uint32_t v = 0; v < s.total_inst; ++v) { tr.constant(2); for (uint32_t i = 0; i < 32; ++i) plan.stream.push_back({TranscriptSrc::INSTANCE, 0, v * 32 + i}); }
     }
-    for (unsigned phase = 0; phase <= max_phase; ++phase) {  // lib.rs:91-109: every instance's advice of the phase, then its challenges
-        for (size_t m = 0; m < M; ++m)
-            for (size_t i = 0; i < A; ++i) if (vk.advice_column_phase[i] == phase) advice_slot[m * A + i] = absorb_point();
-        for (size_t i = 0; i < Ch; ++i) if (vk.challenge_phase[i] == phase) squeeze((uint32_t)i);
+    for (InstanceLayout& il : inst) {
+        il.advice_slot.assign(s.A, 0); il.advice_eval.resize(s.Qa);
+        il.perm.resize(s.nsets); il.lookups.resize(s.L); il.shuffles.resize(s.Sh);
     }
-    squeeze(C_THETA);
-    for (size_t m = 0; m < M; ++m) for (size_t i = 0; i < L; ++i) { lk_input_slot[m * L + i] = absorb_point(); lk_table_slot[m * L + i] = absorb_point(); }   // lib.rs:117-126
-    squeeze(C_BETA); squeeze(C_GAMMA);
-    for (size_t m = 0; m < M; ++m) for (size_t i = 0; i < nsets; ++i) perm_slot[m * nsets + i] = absorb_point();     // lib.rs:134-139
-    for (size_t m = 0; m < M; ++m) for (size_t i = 0; i < L; ++i) lk_product_slot[m * L + i] = absorb_point();         // lib.rs:141-150
-    for (size_t m = 0; m < M; ++m) for (size_t i = 0; i < Sh; ++i) sh_slot[m * Sh + i] = absorb_point();               // lib.rs:152-161
-    random_slot = absorb_point();
-    squeeze(C_Y);
-    for (size_t i = 0; i < H; ++i) h_slot[i] = absorb_point();
-    squeeze(C_X);
-    // evaluations (lib.rs:220-253)
-    std::vector<uint32_t> s_adv(M * Qa), s_fix(Qf), s_sigma(P);   // advice evaluations: instance by instance (lib.rs:220-222)
-    for (auto& s : s_adv) s = absorb_scalar();
-    for (auto& s : s_fix) s = absorb_scalar();
-    uint32_t s_random = absorb_scalar();
-    for (auto& s : s_sigma) s = absorb_scalar();
-    struct PS { uint32_t eval, next, last; bool has_last; };
-    std::vector<PS> s_perm(M * nsets);
-    for (size_t m = 0; m < M; ++m)
-        for (size_t i = 0; i < nsets; ++i) {
-            PS& ps = s_perm[m * nsets + i];
-            ps.eval = absorb_scalar(); ps.next = absorb_scalar();
-            ps.has_last = i + 1 < nsets;
-            ps.last = ps.has_last ? absorb_scalar() : 0;
+    for (unsigned phase = 0; phase <= s.max_phase; ++phase) {  // lib.rs:91-109: every instance's advice of the phase, then its challenges
+        for (InstanceLayout& il : inst) for (size_t i = 0; i < s.A; ++i) if (vk.advice_column_phase[i] == phase) il.advice_slot[i] = tr.point();
+        for (size_t i = 0; i < s.Ch; ++i) if (vk.challenge_phase[i] == phase) tr.squeeze((uint32_t)i);
+    }
+    tr.squeeze(s.C_THETA);
+    for (InstanceLayout& il : inst) for (LookupLayout& l : il.lookups) { l.input_slot = tr.point(); l.table_slot = tr.point(); }   // lib.rs:117-126
+    tr.squeeze(s.C_BETA); tr.squeeze(s.C_GAMMA);
+    for (InstanceLayout& il : inst) for (PermSetLayout& p : il.perm) p.slot = tr.point();              // lib.rs:134-139
+    for (InstanceLayout& il : inst) for (LookupLayout& l : il.lookups) l.product_slot = tr.point();     // lib.rs:141-150
+    for (InstanceLayout& il : inst) for (ShuffleLayout& sh : il.shuffles) sh.slot = tr.point();         // lib.rs:152-161
+    vkl.random_slot = tr.point();
+    tr.squeeze(s.C_Y);
+    vkl.h_slot.resize(s.H);
+    for (uint32_t& h : vkl.h_slot) h = tr.point();
+    plan.x_chal = (uint32_t)plan.squeeze_order.size();
+    tr.squeeze(s.C_X);
+    // evaluations (lib.rs:220-253); the advice evaluations instance by instance (lib.rs:220-222)
+    for (InstanceLayout& il : inst) for (uint32_t& e : il.advice_eval) e = tr.scalar();
+    vkl.fixed_eval.resize(s.Qf); vkl.sigma_eval.resize(s.P);
+    for (uint32_t& e : vkl.fixed_eval) e = tr.scalar();
+    vkl.random_eval = tr.scalar();
+    for (uint32_t& e : vkl.sigma_eval) e = tr.scalar();
+    for (InstanceLayout& il : inst)
+        for (size_t i = 0; i < s.nsets; ++i) { PermSetLayout& p = il.perm[i]; p.eval = tr.scalar(); p.next = tr.scalar(); p.last = i + 1 < s.nsets ? tr.scalar() : 0; }
+    for (InstanceLayout& il : inst) for (LookupLayout& l : il.lookups) { l.product = tr.scalar(); l.product_next = tr.scalar(); l.input = tr.scalar(); l.input_inv = tr.scalar(); l.table = tr.scalar(); }
+    for (InstanceLayout& il : inst) for (ShuffleLayout& sh : il.shuffles) { sh.product = tr.scalar(); sh.product_next = tr.scalar(); }
+    plan.n_main_points = (uint32_t)plan.point_offsets.size();
+    plan.opening_offset = plan.proof_len;
+}
+
+// ---------------- the query list (lib.rs:349-414) and the rotation sets (shplonk.rs:58-149), symbolic in the rotation
+typedef std::pair<uint8_t, uint32_t> Term;   // a commitment by its MSM base: (is_shared, point slot or VK-wide base)
+const Term QUOTIENT = {2, 0};   // the commitment of h: a nested MSM over the h slots, not one base
+struct Query { Term c; int64_t rot; uint32_t eval; };   // commitment, point x * omega^rot (rot normalised mod n), proof scalar #eval (QUOTIENT: none)
+struct RotSet { std::vector<int64_t> rots; std::vector<Term> commits; };
+struct Opening { std::vector<Query> queries; std::vector<RotSet> sets; std::set<int64_t> super; };
+
+Opening opening(const VkHost& vk, const Shape& s, const Domain& dom, const std::vector<InstanceLayout>& inst, const VkLayout& vkl) {
+    Opening op;
+    auto add = [&](Term c, int64_t rot, uint32_t eval) { op.queries.push_back({c, dom.norm(rot), eval}); };
+    const size_t F = vk.fixed_commitments.size();
+    for (const InstanceLayout& il : inst) {   // per instance: advice, permutation, lookups, shuffles
+        for (size_t qi = 0; qi < s.Qa; ++qi) add({0, il.advice_slot[vk.advice_queries[qi].column.index]}, vk.advice_queries[qi].rotation, il.advice_eval[qi]);
+        for (const PermSetLayout& p : il.perm) { add({0, p.slot}, 0, p.eval); add({0, p.slot}, 1, p.next); }
+        for (size_t i = s.nsets; i-- > 1;) add({0, il.perm[i - 1].slot}, -(int64_t)(s.bf + 1), il.perm[i - 1].last);
+        for (const LookupLayout& l : il.lookups) {
+            add({0, l.product_slot}, 0, l.product); add({0, l.input_slot}, 0, l.input); add({0, l.table_slot}, 0, l.table);
+            add({0, l.input_slot}, -1, l.input_inv); add({0, l.product_slot}, 1, l.product_next);
         }
-    struct LS { uint32_t product, product_next, input, input_inv, table; };
-    std::vector<LS> s_lk(M * L);
-    for (auto& s : s_lk) { s.product = absorb_scalar(); s.product_next = absorb_scalar(); s.input = absorb_scalar(); s.input_inv = absorb_scalar(); s.table = absorb_scalar(); }
-    struct SS { uint32_t product, product_next; };
-    std::vector<SS> s_sh(M * Sh);
-    for (auto& s : s_sh) { s.product = absorb_scalar(); s.product_next = absorb_scalar(); }
-    plan.n_main_points = np;
-    plan.opening_offset = off;
-    // distinct opening points in first-appearance order of the query list (lib.rs:349-414) — GWC reads one witness
-    // point per distinct point (gwc.rs:138-163); computed here because the number of points it reads depends on it
-    std::vector<int64_t> gwc_points;
-    std::vector<uint32_t> gwc_w_slot;
-    if (gwc) {
-        auto seen = [&](int64_t r) { int64_t k2 = norm_rot(r); for (int64_t e : gwc_points) if (e == k2) return; gwc_points.push_back(k2); };
-        // (every instance contributes the same rotations in the same order, so the first-appearance order is instance 0's)
-        for (const QueryH& q : vk.advice_queries) seen(q.rotation);
-        if (nsets) { seen(0); seen(1); if (nsets > 1) seen(-(int64_t)(bf + 1)); }
-        if (L) { seen(0); seen(-1); seen(1); }
-        if (Sh) { seen(0); seen(1); }
-        for (const QueryH& q : vk.fixed_queries) seen(q.rotation);
-        seen(0);
-        squeeze(C_SV);
-        for (size_t i = 0; i < gwc_points.size(); ++i) gwc_w_slot.push_back(absorb_point());
-        squeeze(C_SU);
+        for (const ShuffleLayout& sh : il.shuffles) { add({0, sh.slot}, 0, sh.product); add({0, sh.slot}, 1, sh.product_next); }
+    }
+    for (size_t qi = 0; qi < s.Qf; ++qi) add({1, vk.fixed_queries[qi].column.index}, vk.fixed_queries[qi].rotation, vkl.fixed_eval[qi]);
+    for (size_t i = 0; i < s.P; ++i) add({1, (uint32_t)(F + i)}, 0, vkl.sigma_eval[i]);
+    add(QUOTIENT, 0, 0);
+    add({0, vkl.random_slot}, 0, vkl.random_eval);
+    std::vector<std::pair<Term, std::set<int64_t>>> cmap;
+    for (const Query& q : op.queries) {
+        op.super.insert(q.rot);
+        bool found = false;
+        for (auto& e : cmap) if (e.first == q.c) { e.second.insert(q.rot); found = true; break; }
+        if (!found) cmap.push_back({q.c, {q.rot}});
+    }
+    for (auto& e : cmap) {
+        bool found = false;
+        for (auto& r : op.sets) if (std::set<int64_t>(r.rots.begin(), r.rots.end()) == e.second) { r.commits.push_back(e.first); found = true; break; }
+        if (!found) op.sets.push_back({std::vector<int64_t>(e.second.begin(), e.second.end()), {e.first}});
+    }
+    return op;
+}
+
+// the multi-open part: GWC reads a witness per distinct opening point, in first-appearance order of the query list (gwc.rs:73-83,
+// 138-163); SHPLONK reads h1, h2 (shplonk.rs:195-200)
+void lay_out_multiopen(const Shape& s, const Opening& op, Transcript& tr, VkLayout& vkl) {
+    if (s.gwc) {
+        for (const Query& q : op.queries) if (std::find(vkl.gwc_points.begin(), vkl.gwc_points.end(), q.rot) == vkl.gwc_points.end()) vkl.gwc_points.push_back(q.rot);
+        tr.squeeze(s.C_SV);
+        for (size_t i = 0; i < vkl.gwc_points.size(); ++i) vkl.gwc_w_slot.push_back(tr.point());
+        tr.squeeze(s.C_SU);
     } else {
-        squeeze(C_SY); squeeze(C_SV);
-        plan.slot_h1 = absorb_point();
-        squeeze(C_SU);
-        plan.slot_h2 = absorb_point();
+        tr.squeeze(s.C_SY); tr.squeeze(s.C_SV);
+        tr.plan.slot_h1 = tr.point();
+        tr.squeeze(s.C_SU);
+        tr.plan.slot_h2 = tr.point();
     }
-    plan.n_points = np; plan.n_scalars = nsc; plan.proof_len = off;
-    // challenge id -> position in squeeze order
-    std::vector<uint32_t> sq_of(plan.n_challenges, 0);
-    for (size_t q = 0; q < squeeze_order.size(); ++q) sq_of[squeeze_order[q]] = (uint32_t)q;
+    tr.plan.n_points = (uint32_t)tr.plan.point_offsets.size(); tr.plan.n_scalars = (uint32_t)tr.plan.scalar_offsets.size();
+}
 
-    // ---------------- the Fr program
-    Builder b;
+// ---------------- the Fr program
+struct Challenges { std::vector<Val> user; Val theta, beta, gamma, y, x, sy, sv, su, xn, xn_m1; };
+Challenges load_challenges(Builder& b, const Shape& s, const Plan& plan, uint32_t k) {
+    std::vector<uint32_t> sq_of(plan.n_challenges, 0);   // challenge id -> position in squeeze order
+    for (size_t q = 0; q < plan.squeeze_order.size(); ++q) sq_of[plan.squeeze_order[q]] = (uint32_t)q;
     auto chal = [&](uint32_t id) { return b.load_chal(sq_of[id]); };
-    std::vector<Val> user_ch(Ch);
-    for (size_t i = 0; i < Ch; ++i) user_ch[i] = chal((uint32_t)i);
-    Val theta = chal(C_THETA), beta = chal(C_BETA), gamma = chal(C_GAMMA), y = chal(C_Y), x = chal(C_X), sv = chal(C_SV), su = chal(C_SU);
-    plan.x_chal = sq_of[C_X]; plan.domain_k = vk.k; plan.omega = omega; plan.n_inv = n_inv;
-    Val sy = gwc ? sv : chal(C_SY);
-    Val xn = b.sqrn(x, vk.k);  // x^n, n = 2^k   (lib.rs:180,259)
-    Val xn_m1 = b.sub(xn, b.one());
+    Challenges c;
+    for (size_t i = 0; i < s.Ch; ++i) c.user.push_back(chal((uint32_t)i));
+    c.theta = chal(s.C_THETA); c.beta = chal(s.C_BETA); c.gamma = chal(s.C_GAMMA); c.y = chal(s.C_Y); c.x = chal(s.C_X); c.sv = chal(s.C_SV); c.su = chal(s.C_SU);
+    c.sy = s.gwc ? c.sv : chal(s.C_SY);
+    c.xn = b.sqrn(c.x, k);  // x^n, n = 2^k   (lib.rs:180,259)
+    c.xn_m1 = b.sub(c.xn, b.one());
+    return c;
+}
 
-    // every inversion of the proof goes through one batch inversion
-    //   [0] xn - 1 (vanishing.rs:100)  [1] x (interpolation denominators)  [2] z_diff_0 (shplonk.rs:215)  [3..] x - omega^i
-    std::map<int64_t, size_t> l_index;  // normalised rotation -> position in `dens`
-    std::vector<int64_t> l_rots;
-    auto need_l = [&](int64_t r) { int64_t k2 = norm_rot(r); if (!l_index.count(k2)) { l_index[k2] = l_rots.size(); l_rots.push_back(r); } };
-    for (int64_t r = -(int64_t)(bf + 1); r <= 0; ++r) need_l(r);
-    {
-        size_t flat = 0; (void)flat;
-        for (const QueryH& q : vk.instance_queries) {
-            if (q.column.index >= NIC) { err = "instance query names a missing column"; return H2V_ERR_FORMAT; }
-            if (!plan.wide_instances) for (size_t m = 0; m < M; ++m) for (size_t j = 0; j < col_lens[m * NIC + q.column.index]; ++j) need_l((int64_t)j - q.rotation);
-        }
+// Every evaluation of the proof, loaded here in this order; the phases below load what they use where they use it, which finds
+// these nodes (load_scalar is hash-consed), so the node ids stay those of this first load.
+void load_evaluations(Builder& b, const std::vector<InstanceLayout>& inst, const VkLayout& vkl) {
+    for (const InstanceLayout& il : inst) for (uint32_t e : il.advice_eval) b.load_scalar(e);
+    for (uint32_t e : vkl.fixed_eval) b.load_scalar(e);
+    for (uint32_t e : vkl.sigma_eval) b.load_scalar(e);
+    b.load_scalar(vkl.random_eval);
+    for (const InstanceLayout& il : inst) {
+        for (size_t i = 0; i < il.perm.size(); ++i) { b.load_scalar(il.perm[i].eval); b.load_scalar(il.perm[i].next); if (i + 1 < il.perm.size()) b.load_scalar(il.perm[i].last); }
+        for (const LookupLayout& l : il.lookups) for (uint32_t e : {l.product, l.product_next, l.input, l.input_inv, l.table}) b.load_scalar(e);
+        for (const ShuffleLayout& sh : il.shuffles) { b.load_scalar(sh.product); b.load_scalar(sh.product_next); }
     }
+}
 
-    // ---------------- symbolic SHPLONK bookkeeping needs the query list; build evals first
-    std::vector<Val> advice_evals_all(M * Qa), fixed_evals(Qf), sigma_evals(P);
-    for (size_t i = 0; i < M * Qa; ++i) advice_evals_all[i] = b.load_scalar(s_adv[i]);
-    for (size_t i = 0; i < Qf; ++i) fixed_evals[i] = b.load_scalar(s_fix[i]);
-    for (size_t i = 0; i < P; ++i) sigma_evals[i] = b.load_scalar(s_sigma[i]);
-    Val random_eval = b.load_scalar(s_random);
+// prod (u - x omega^r) over the opening points outside the set (shplonk.rs:215-240)
+Val z_outside(Builder& b, const Opening& op, const RotSet& rs, Val u, const std::map<int64_t, Val>& point_of) {
+    Val z = b.one();
+    for (int64_t r : op.super) if (std::find(rs.rots.begin(), rs.rots.end(), r) == rs.rots.end()) z = b.mul(b.sub(u, point_of.at(r)), z);
+    return z;
+}
 
-    // rotation sets (shplonk.rs:58-149), symbolic in the rotation; the evaluations are filled in below
-    std::vector<SymQuery> queries;
-    auto add_query = [&](CommitRef c, int64_t rot, Val e) { queries.push_back({c, norm_rot(rot), e}); };
-    // (the eval Vals of h / instance-dependent values are patched after they exist; collect structure first)
-    std::vector<Val> pz_all(M * nsets), pz_next_all(M * nsets), pz_last_all(M * nsets);
-    struct LV { Val product, product_next, input, input_inv, table; };
-    std::vector<LV> lk_all(M * L);
-    struct SV2 { Val product, product_next; };
-    std::vector<SV2> shv_all(M * Sh);
-    for (size_t m = 0; m < M; ++m) {   // lib.rs:349-391: per instance advice, permutation, lookups, shuffles
-        const int im = (int)m;
-        for (size_t qi = 0; qi < Qa; ++qi) {
-            if (vk.advice_queries[qi].column.index >= A) { err = "advice query names a missing column"; return H2V_ERR_FORMAT; }
-            add_query({K_ADVICE, (int)vk.advice_queries[qi].column.index, im}, vk.advice_queries[qi].rotation, advice_evals_all[m * Qa + qi]);
-        }
-        Val* pz = &pz_all[m * nsets]; Val* pz_next = &pz_next_all[m * nsets]; Val* pz_last = &pz_last_all[m * nsets];
-        for (size_t i = 0; i < nsets; ++i) {
-            const PS& ps = s_perm[m * nsets + i];
-            pz[i] = b.load_scalar(ps.eval); pz_next[i] = b.load_scalar(ps.next); if (ps.has_last) pz_last[i] = b.load_scalar(ps.last);
-        }
-        for (size_t i = 0; i < nsets; ++i) { add_query({K_PERM_PRODUCT, (int)i, im}, 0, pz[i]); add_query({K_PERM_PRODUCT, (int)i, im}, 1, pz_next[i]); }
-        for (size_t i = nsets; i-- > 0;) { if (i + 1 == nsets) continue; add_query({K_PERM_PRODUCT, (int)i, im}, -(int64_t)(bf + 1), pz_last[i]); }
-        for (size_t i = 0; i < L; ++i) {
-            const LS& ls = s_lk[m * L + i];
-            LV& e = lk_all[m * L + i];
-            e = {b.load_scalar(ls.product), b.load_scalar(ls.product_next), b.load_scalar(ls.input), b.load_scalar(ls.input_inv), b.load_scalar(ls.table)};
-            add_query({K_LOOKUP, (int)(3 * i + 0), im}, 0, e.product);
-            add_query({K_LOOKUP, (int)(3 * i + 1), im}, 0, e.input);
-            add_query({K_LOOKUP, (int)(3 * i + 2), im}, 0, e.table);
-            add_query({K_LOOKUP, (int)(3 * i + 1), im}, -1, e.input_inv);
-            add_query({K_LOOKUP, (int)(3 * i + 0), im}, 1, e.product_next);
-        }
-        for (size_t i = 0; i < Sh; ++i) {
-            SV2& e = shv_all[m * Sh + i];
-            e = {b.load_scalar(s_sh[m * Sh + i].product), b.load_scalar(s_sh[m * Sh + i].product_next)};
-            add_query({K_SHUFFLE, (int)i, im}, 0, e.product);
-            add_query({K_SHUFFLE, (int)i, im}, 1, e.product_next);
-        }
-    }
-    for (size_t qi = 0; qi < Qf; ++qi) {
-        if (vk.fixed_queries[qi].column.index >= vk.fixed_commitments.size()) { err = "fixed query names a missing column"; return H2V_ERR_FORMAT; }
-        add_query({K_FIXED, (int)vk.fixed_queries[qi].column.index, 0}, vk.fixed_queries[qi].rotation, fixed_evals[qi]);
-    }
-    for (size_t i = 0; i < P; ++i) add_query({K_PERM_COMMON, (int)i, 0}, 0, sigma_evals[i]);
-    const size_t q_hmsm = queries.size();
-    add_query({K_H_MSM, 0, 0}, 0, 0 /* patched: expected_h_eval */);
-    add_query({K_RANDOM, 0, 0}, 0, random_eval);
-
-    struct RotSet { std::vector<int64_t> rots; std::vector<CommitRef> commits; };
-    std::vector<RotSet> rsets; std::set<int64_t> super;
-    {
-        std::vector<std::pair<CommitRef, std::set<int64_t>>> cmap;
-        for (const SymQuery& q : queries) {
-            super.insert(q.rot);
-            bool found = false;
-            for (auto& e : cmap) if (e.first == q.c) { e.second.insert(q.rot); found = true; break; }
-            if (!found) cmap.push_back({q.c, {q.rot}});
-        }
-        for (auto& e : cmap) {
-            bool found = false;
-            for (auto& r : rsets) if (std::set<int64_t>(r.rots.begin(), r.rots.end()) == e.second) { r.commits.push_back(e.first); found = true; break; }
-            if (!found) rsets.push_back({std::vector<int64_t>(e.second.begin(), e.second.end()), {e.first}});
-        }
-    }
-
-    // ---------------- batch inversion
-    std::map<int64_t, Val> point_of;  // x * omega^rot for the opening points
-    for (int64_t r : super) point_of[r] = b.mul(x, b.cst(omega_pow(r)));
-    Val z_diff_0 = b.one();
-    if (!gwc) for (int64_t r : super) if (std::find(rsets[0].rots.begin(), rsets[0].rots.end(), r) == rsets[0].rots.end()) z_diff_0 = b.mul(b.sub(su, point_of[r]), z_diff_0);
+// Every inversion of the proof goes through one batch inversion: xn - 1 (vanishing.rs:100), x (interpolation denominators), z_diff_0
+// (shplonk.rs:215) and x - omega^r for each rotation r of a Lagrange value l_r(x) the program uses.
+struct Inverses {
+    Val xn_m1_inv, x_inv, z_0_diff_inverse, common;
+    std::vector<Val> x_minus;          // 1 / (x - omega^r) for r in rots
+    std::vector<int64_t> rots;
+    std::map<int64_t, size_t> index;   // normalised rotation -> position in rots
+    Val lagrange(Builder& b, const Domain& dom, int64_t r) const { size_t i = index.at(dom.norm(r)); return b.mul(b.mul(x_minus[i], common), b.cst(dom.pow(rots[i]))); }
+};
+Inverses invert(Builder& b, const VkHost& vk, const Shape& s, const Domain& dom, const std::vector<size_t>& col_lens, bool wide, const Challenges& c, Val z_diff_0) {
+    Inverses iv;
+    // l_last, l_blind, l_0 (lib.rs:259-270) and, unless k_instance_eval evaluates them, l_{j - rot} for every instance value
+    auto need = [&](int64_t r) { int64_t k2 = dom.norm(r); if (!iv.index.count(k2)) { iv.index[k2] = iv.rots.size(); iv.rots.push_back(r); } };
+    for (int64_t r = -(int64_t)(s.bf + 1); r <= 0; ++r) need(r);
+    if (!wide) for (const QueryH& q : vk.instance_queries) for (size_t m = 0; m < s.M; ++m) for (size_t j = 0; j < col_lens[m * s.NIC + q.column.index]; ++j) need((int64_t)j - q.rotation);
     // GWC needs neither 1/x nor 1/z_diff_0; keeping two harmless entries keeps the indices below fixed
-    std::vector<Val> inv_list = {xn_m1, gwc ? b.one() : x, gwc ? b.one() : z_diff_0};
-    for (int64_t r : l_rots) inv_list.push_back(b.sub(x, b.cst(omega_pow(r))));
+    std::vector<Val> inv_list = {c.xn_m1, s.gwc ? b.one() : c.x, s.gwc ? b.one() : z_diff_0};
+    for (int64_t r : iv.rots) inv_list.push_back(b.sub(c.x, b.cst(dom.pow(r))));
     b.batch_invert(inv_list);
-    Val xn_m1_inv = inv_list[0], x_inv = inv_list[1], z_0_diff_inverse = inv_list[2];
-    Val common = b.mul(xn_m1, b.cst(n_inv));  // (xn - 1) * barycentric_weight   (poly/domain.rs:206)
-    auto l_at = [&](int64_t r) { size_t i = l_index[norm_rot(r)]; return b.mul(b.mul(inv_list[3 + i], common), b.cst(omega_pow(l_rots[i]))); };
+    iv.xn_m1_inv = inv_list[0]; iv.x_inv = inv_list[1]; iv.z_0_diff_inverse = inv_list[2];
+    iv.x_minus.assign(inv_list.begin() + 3, inv_list.end());
+    iv.common = b.mul(c.xn_m1, b.cst(dom.n_inv));  // (xn - 1) * barycentric_weight   (poly/domain.rs:206)
+    return iv;
+}
 
-    // ---------------- instance evaluations (lib.rs:173-218): sum_j inst[col][j] * l_{j - rot}(x)
-    std::vector<std::vector<Val>> instance_evals_all(M);
-    {
-        std::vector<uint32_t> col_base(col_lens.size(), 0);
-        for (size_t c = 1; c < col_lens.size(); ++c) col_base[c] = col_base[c - 1] + (uint32_t)col_lens[c - 1];
-        std::map<int64_t, Val> l_cache;
-        for (size_t m = 0; m < M; ++m)
-            for (const QueryH& q : vk.instance_queries) {
-                const size_t col = m * NIC + q.column.index;
-                if (plan.wide_instances) {   // evaluated by k_instance_eval before the program runs
-                    plan.inst_queries.push_back({col_base[col], (uint32_t)col_lens[col], omega_pow(-(int64_t)q.rotation)});
-                    instance_evals_all[m].push_back(b.load_insteval((uint32_t)plan.inst_queries.size() - 1));
-                    continue;
-                }
-                Val acc = b.zero();
-                for (size_t j = 0; j < col_lens[col]; ++j) {
-                    int64_t r = norm_rot((int64_t)j - q.rotation);
-                    if (!l_cache.count(r)) l_cache[r] = l_at(r);
-                    acc = b.add(acc, b.mul(b.load_inst(col_base[col] + (uint32_t)j), l_cache[r]));
-                }
-                instance_evals_all[m].push_back(acc);
+// instance evaluations (lib.rs:173-218): sum_j inst[col][j] * l_{j - rot}(x), per circuit instance and instance query
+std::vector<std::vector<Val>> instance_evaluations(Builder& b, const VkHost& vk, const Shape& s, const Domain& dom, const Inverses& iv, Plan& plan) {
+    std::vector<std::vector<Val>> evals(s.M);
+    const std::vector<size_t>& col_lens = plan.col_lens;
+    std::vector<uint32_t> col_base(col_lens.size(), 0);
+    for (size_t c = 1; c < col_lens.size(); ++c) col_base[c] = col_base[c - 1] + (uint32_t)col_lens[c - 1];
+    std::map<int64_t, Val> l_cache;
+    for (size_t m = 0; m < s.M; ++m)
+        for (const QueryH& q : vk.instance_queries) {
+            const size_t col = m * s.NIC + q.column.index;
+            if (plan.wide_instances) {   // evaluated by k_instance_eval before the program runs
+                plan.inst_queries.push_back({col_base[col], (uint32_t)col_lens[col], dom.pow(-(int64_t)q.rotation)});
+                evals[m].push_back(b.load_insteval((uint32_t)plan.inst_queries.size() - 1));
+                continue;
             }
-    }
-    // l_last, l_blind, l_0 (lib.rs:259-270)
-    Val l_last = l_at(-(int64_t)(bf + 1));
-    Val l_blind = b.zero();
-    for (int64_t r = -(int64_t)bf; r <= -1; ++r) l_blind = b.add(l_blind, l_at(r));
-    Val l_0 = l_at(0);
+            Val acc = b.zero();
+            for (size_t j = 0; j < col_lens[col]; ++j) {
+                int64_t r = dom.norm((int64_t)j - q.rotation);
+                if (!l_cache.count(r)) l_cache[r] = iv.lagrange(b, dom, r);
+                acc = b.add(acc, b.mul(b.load_inst(col_base[col] + (uint32_t)j), l_cache[r]));
+            }
+            evals[m].push_back(acc);
+        }
+    return evals;
+}
 
-    // ---------------- expressions (lib.rs:273-346)
-    const size_t Qi = vk.instance_queries.size();
-    int expr_err = 0;
+// the constraint expressions of every instance (lib.rs:273-346) folded by y into expected_h_eval (vanishing.rs:92-121); `panic`: the
+// VK makes the reference panic (an empty expression, an out-of-range index)
+Val expected_h_eval(Builder& b, const VkHost& vk, const Shape& s, const Domain& dom, const Challenges& c, const Inverses& iv, const std::vector<InstanceLayout>& inst,
+                    const VkLayout& vkl, const std::vector<std::vector<Val>>& instance_evals, bool& panic) {
+    const Val l_last = iv.lagrange(b, dom, -(int64_t)(s.bf + 1));
+    Val l_blind = b.zero();
+    for (int64_t r = -(int64_t)s.bf; r <= -1; ++r) l_blind = b.add(l_blind, iv.lagrange(b, dom, r));
+    const Val l_0 = iv.lagrange(b, dom, 0);
     std::vector<Val> exprs;
-    Val active_rows = b.sub(b.one(), b.add(l_last, l_blind));
-    for (size_t m = 0; m < M; ++m) {   // lib.rs:273-346: flat_map over the instances — gates, permutation, lookups, shuffles of each
-        const Val* advice_evals = &advice_evals_all[m * Qa];
-        const std::vector<Val>& instance_evals = instance_evals_all[m];
+    const Val active_rows = b.sub(b.one(), b.add(l_last, l_blind));
+    for (size_t m = 0; m < s.M; ++m) {   // flat_map over the instances: gates, permutation, lookups, shuffles of each
+        const InstanceLayout& il = inst[m];
+        auto ev = [&](uint32_t scalar) { return b.load_scalar(scalar); };
         std::map<std::pair<uint32_t, uint32_t>, Val> pow_cache;
         auto var_at = [&](uint32_t idx) -> Val {
-            if (idx < Qa) return advice_evals[idx];
-            if (idx < Qa + Qf) return fixed_evals[idx - Qa];
-            if (idx < Qa + Qf + Qi) return instance_evals[idx - Qa - Qf];
-            if (idx < Qa + Qf + Qi + Ch) return user_ch[idx - Qa - Qf - Qi];
-            expr_err = 1; return b.zero();  // "index out of range" panic (vk.rs:501)
+            if (idx < s.Qa) return ev(il.advice_eval[idx]);
+            if (idx < s.Qa + s.Qf) return ev(vkl.fixed_eval[idx - s.Qa]);
+            if (idx < s.Qa + s.Qf + s.Qi) return instance_evals[m][idx - s.Qa - s.Qf];
+            if (idx < s.Qa + s.Qf + s.Qi + s.Ch) return c.user[idx - s.Qa - s.Qf - s.Qi];
+            panic = true; return b.zero();  // "index out of range" panic (vk.rs:501)
         };
         auto eval_expr = [&](const ExprH& e) -> Val {
-            if (e.terms.empty()) { expr_err = 1; return b.zero(); }  // unwrap on empty terms (multilinear.rs:65)
+            if (e.terms.empty()) { panic = true; return b.zero(); }  // unwrap on empty terms (multilinear.rs:65)
             Val sum = 0; bool first = true;
             for (const TermH& t : e.terms) {
-                if (t.coeff_idx >= vk.coeff_vals.size()) { expr_err = 1; return b.zero(); }
+                if (t.coeff_idx >= vk.coeff_vals.size()) { panic = true; return b.zero(); }
                 Val prod = b.one();
                 for (const auto& f : t.factors) {
                     auto key = std::make_pair(f.first, f.second);
@@ -889,164 +895,141 @@ int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<s
             return sum;
         };
         for (const ExprH& g : vk.gates) exprs.push_back(eval_expr(g));
-        auto column_eval = [&](const ColumnH& c) -> Val {  // get_any_query_index(column, Rotation::cur()) (vk.rs:413-455)
-            const std::vector<QueryH>& qs = c.type <= 2 ? vk.advice_queries : (c.type == COL_FIXED ? vk.fixed_queries : vk.instance_queries);
+        auto column_eval = [&](const ColumnH& col) -> Val {  // get_any_query_index(column, Rotation::cur()) (vk.rs:413-455)
+            const std::vector<QueryH>& qs = col.type <= 2 ? vk.advice_queries : (col.type == COL_FIXED ? vk.fixed_queries : vk.instance_queries);
             for (size_t i = 0; i < qs.size(); ++i)
-                if (qs[i].column.index == c.index && qs[i].column.type == c.type && qs[i].rotation == 0)
-                    return c.type <= 2 ? advice_evals[i] : (c.type == COL_FIXED ? fixed_evals[i] : instance_evals[i]);
-            expr_err = 1; return b.zero();
+                if (qs[i].column.index == col.index && qs[i].column.type == col.type && qs[i].rotation == 0)
+                    return col.type <= 2 ? ev(il.advice_eval[i]) : (col.type == COL_FIXED ? ev(vkl.fixed_eval[i]) : instance_evals[m][i]);
+            panic = true; return b.zero();
         };
-        const Val* pz = &pz_all[m * nsets]; const Val* pz_next = &pz_next_all[m * nsets]; const Val* pz_last = &pz_last_all[m * nsets];
-        if (nsets > 0) {  // permutation.rs:189-288
-            exprs.push_back(b.mul(l_0, b.sub(b.one(), pz[0])));
-            exprs.push_back(b.mul(b.sub(b.sqr(pz[nsets - 1]), pz[nsets - 1]), l_last));
-            for (size_t i = 1; i < nsets; ++i) exprs.push_back(b.mul(b.sub(pz[i], pz_last[i - 1]), l_0));
-            Val beta_x = b.mul(beta, x);
-            for (size_t ci = 0; ci < nsets; ++ci) {
-                size_t lo = ci * chunk, hi = std::min(P, lo + chunk);
-                Val left = pz_next[ci], right = pz[ci];
-                Fr dpow = delta.pow_u32((uint32_t)(ci * chunk));
+        if (s.nsets > 0) {  // permutation.rs:189-288
+            const Val z_first = ev(il.perm[0].eval), z_final = ev(il.perm[s.nsets - 1].eval);
+            exprs.push_back(b.mul(l_0, b.sub(b.one(), z_first)));
+            exprs.push_back(b.mul(b.sub(b.sqr(z_final), z_final), l_last));
+            for (size_t i = 1; i < s.nsets; ++i) exprs.push_back(b.mul(b.sub(ev(il.perm[i].eval), ev(il.perm[i - 1].last)), l_0));
+            Val beta_x = b.mul(c.beta, c.x);
+            for (size_t ci = 0; ci < s.nsets; ++ci) {
+                size_t lo = ci * s.chunk, hi = std::min(s.P, lo + s.chunk);
+                Val left = ev(il.perm[ci].next), right = ev(il.perm[ci].eval);
+                Fr dpow = dom.delta.pow_u32((uint32_t)(ci * s.chunk));
                 for (size_t j = lo; j < hi; ++j) {
                     Val v = column_eval(vk.permutation_columns[j]);
-                    left = b.mul(left, b.add(b.add(v, b.mul(beta, sigma_evals[j])), gamma));
-                    right = b.mul(right, b.add(b.add(v, b.mul(beta_x, b.cst(dpow))), gamma));
-                    dpow = dpow * delta;
+                    left = b.mul(left, b.add(b.add(v, b.mul(c.beta, ev(vkl.sigma_eval[j]))), c.gamma));
+                    right = b.mul(right, b.add(b.add(v, b.mul(beta_x, b.cst(dpow))), c.gamma));
+                    dpow = dpow * dom.delta;
                 }
                 exprs.push_back(b.mul(b.sub(left, right), active_rows));
             }
         }
-        auto compress = [&](const std::vector<ExprH>& es) { Val acc = b.zero(); for (const ExprH& e : es) acc = b.add(b.mul(acc, theta), eval_expr(e)); return acc; };
-        for (size_t i = 0; i < L; ++i) {  // lookup.rs:159-230
-            const LV& e = lk_all[m * L + i];
-            exprs.push_back(b.mul(l_0, b.sub(b.one(), e.product)));
-            exprs.push_back(b.mul(l_last, b.sub(b.sqr(e.product), e.product)));
-            Val left = b.mul(b.mul(e.product_next, b.add(e.input, beta)), b.add(e.table, gamma));
-            Val right = b.mul(b.mul(e.product, b.add(compress(vk.lookups[i].input), beta)), b.add(compress(vk.lookups[i].table), gamma));
+        auto compress = [&](const std::vector<ExprH>& es) { Val acc = b.zero(); for (const ExprH& e : es) acc = b.add(b.mul(acc, c.theta), eval_expr(e)); return acc; };
+        for (size_t i = 0; i < s.L; ++i) {  // lookup.rs:159-230
+            const Val product = ev(il.lookups[i].product), product_next = ev(il.lookups[i].product_next);
+            const Val input = ev(il.lookups[i].input), input_inv = ev(il.lookups[i].input_inv), table = ev(il.lookups[i].table);
+            exprs.push_back(b.mul(l_0, b.sub(b.one(), product)));
+            exprs.push_back(b.mul(l_last, b.sub(b.sqr(product), product)));
+            Val left = b.mul(b.mul(product_next, b.add(input, c.beta)), b.add(table, c.gamma));
+            Val right = b.mul(b.mul(product, b.add(compress(vk.lookups[i].input), c.beta)), b.add(compress(vk.lookups[i].table), c.gamma));
             exprs.push_back(b.mul(b.sub(left, right), active_rows));
-            exprs.push_back(b.mul(l_0, b.sub(e.input, e.table)));
-            exprs.push_back(b.mul(b.mul(b.sub(e.input, e.table), b.sub(e.input, e.input_inv)), active_rows));
+            exprs.push_back(b.mul(l_0, b.sub(input, table)));
+            exprs.push_back(b.mul(b.mul(b.sub(input, table), b.sub(input, input_inv)), active_rows));
         }
-        for (size_t i = 0; i < Sh; ++i) {  // shuffle.rs:148-203
-            const SV2& e = shv_all[m * Sh + i];
-            exprs.push_back(b.mul(l_0, b.sub(b.one(), e.product)));
-            exprs.push_back(b.mul(l_last, b.sub(b.sqr(e.product), e.product)));
-            Val left = b.mul(e.product_next, b.add(compress(vk.shuffles[i].shuffle), gamma));
-            Val right = b.mul(e.product, b.add(compress(vk.shuffles[i].input), gamma));
+        for (size_t i = 0; i < s.Sh; ++i) {  // shuffle.rs:148-203
+            const Val product = ev(il.shuffles[i].product), product_next = ev(il.shuffles[i].product_next);
+            exprs.push_back(b.mul(l_0, b.sub(b.one(), product)));
+            exprs.push_back(b.mul(l_last, b.sub(b.sqr(product), product)));
+            Val left = b.mul(product_next, b.add(compress(vk.shuffles[i].shuffle), c.gamma));
+            Val right = b.mul(product, b.add(compress(vk.shuffles[i].input), c.gamma));
             exprs.push_back(b.mul(b.sub(left, right), active_rows));
         }
     }
-    if (expr_err) { err = "the VK makes the reference panic (empty expression polynomial or out-of-range index)"; return H2V_ERR_REFERENCE_PANIC; }
-    // vanishing.rs:92-121
     Val h_eval = b.zero();
-    for (Val v : exprs) h_eval = b.add(b.mul(h_eval, y), v);
-    Val expected_h_eval = b.mul(h_eval, xn_m1_inv);
-    queries[q_hmsm].eval = expected_h_eval;
+    for (Val v : exprs) h_eval = b.add(b.mul(h_eval, c.y), v);
+    return b.mul(h_eval, iv.xn_m1_inv);
+}
 
-    // ---------------- SHPLONK scalar preparation (shplonk.rs:202-264)
-    auto eval_of = [&](const CommitRef& c, int64_t rot) -> Val {
-        for (const SymQuery& q : queries) if (q.c == c && q.rot == rot) return q.eval;
-        return b.zero();
-    };
-    Val mult = b.load_mult();
-    std::vector<Val> msm_scalar(np, (Val)-1);                    // per point slot
-    const size_t F = vk.fixed_commitments.size();
-    plan.n_shared = (uint32_t)(F + P + 1);
-    std::vector<Val> shared_scalar(plan.n_shared, (Val)-1);
-    plan.shared_bases.clear();
-    for (const G1A& c : vk.fixed_commitments) plan.shared_bases.push_back(c);
-    for (const G1A& c : vk.permutation_commitments) plan.shared_bases.push_back(c);
-    plan.shared_bases.push_back(params.g);
-    auto slot_of = [&](const CommitRef& c) -> std::pair<uint8_t, uint32_t> {  // (is_shared, index)
-        switch (c.kind) {
-            case K_ADVICE: return {0, advice_slot[c.inst * A + c.idx]};
-            case K_PERM_PRODUCT: return {0, perm_slot[c.inst * nsets + c.idx]};
-            case K_LOOKUP: return {0, c.idx % 3 == 0 ? lk_product_slot[c.inst * L + c.idx / 3] : (c.idx % 3 == 1 ? lk_input_slot[c.inst * L + c.idx / 3] : lk_table_slot[c.inst * L + c.idx / 3])};
-            case K_SHUFFLE: return {0, sh_slot[c.inst * Sh + c.idx]};
-            case K_FIXED: return {1, (uint32_t)c.idx};
-            case K_PERM_COMMON: return {1, (uint32_t)(F + c.idx)};
-            case K_RANDOM: return {0, random_slot};
-            default: return {0, 0};
-        }
-    };
-    auto assign = [&](std::pair<uint8_t, uint32_t> where, Val v) {
-        Val& dst = where.first ? shared_scalar[where.second] : msm_scalar[where.second];
+// ---------------- the output scalars of one proof: per point slot (MSM and left channel) and per VK-wide base, with the reference's
+// term orders
+const Val NONE = (Val)-1;
+struct Scalars {
+    std::vector<Val> msm, shared, left;
+    std::vector<Term> right_order, left_order, guard_order;
+    bool guard;   // GWC guard variant: each term's own scalar is stored as well (OP_STORE_GUARD)
+    Scalars(size_t np, size_t n_shared, bool g) : msm(np, NONE), shared(n_shared, NONE), left(np, NONE), guard(g) {}
+    void term(Builder& b, Term where, Val v) {
+        Val& dst = where.first ? shared[where.second] : msm[where.second];
         // SHPLONK: a commitment belongs to exactly one rotation set; GWC: a commitment opened at several points occurs once
         // per point — its scalars are summed and it is reported once (first appearance) in the Guard
-        if (dst == (Val)-1) { plan.right_term_order.push_back(where); dst = v; }
+        if (dst == NONE) { right_order.push_back(where); dst = v; }
         else dst = b.add(dst, v);
+        if (guard) { b.store_guard(v, (uint32_t)guard_order.size()); guard_order.push_back(where); }
+    }
+    // the quotient commitment is a nested MSM: bases h_{H-1} .. h_0 with scalars w xn^{H-1} .. w (vanishing.rs:102-112)
+    void quotient(Builder& b, Val w, Val xn, const std::vector<uint32_t>& h_slot) {
+        const size_t H = h_slot.size();
+        std::vector<Val> xnp(H); if (H) xnp[0] = b.one();
+        for (size_t t = 1; t < H; ++t) xnp[t] = b.mul(xnp[t - 1], xn);
+        for (size_t t = H; t-- > 0;) term(b, {0, h_slot[t]}, b.mul(w, xnp[t]));
+    }
+    void left_term(uint32_t slot, Val v) { left[slot] = v; left_order.push_back({0, slot}); }
+};
+Val eval_of(Builder& b, const Query& q, Val h_eval) { return q.c == QUOTIENT ? h_eval : b.load_scalar(q.eval); }
+
+// gwc.rs:86-132: point group i has weight u^i, query j inside it weight v^j; the right channel in the reference's term order:
+// witness_with_aux, commitment_multi query by query, (eval_multi, -g)
+void gwc_scalars(Builder& b, const Challenges& c, const Opening& op, const std::map<int64_t, Val>& point_of, Val h_eval, const VkLayout& vkl, Scalars& out) {
+    const size_t G = vkl.gwc_points.size();
+    std::vector<std::vector<const Query*>> groups(G);
+    for (const Query& q : op.queries) groups[std::find(vkl.gwc_points.begin(), vkl.gwc_points.end(), q.rot) - vkl.gwc_points.begin()].push_back(&q);
+    Val power_of_u = b.one();
+    std::vector<Val> pu(G);
+    for (size_t i = 0; i < G; ++i) { pu[i] = power_of_u; power_of_u = b.mul(c.su, power_of_u); }
+    for (size_t i = 0; i < G; ++i) {
+        out.term(b, {0, vkl.gwc_w_slot[i]}, b.mul(pu[i], point_of.at(vkl.gwc_points[i])));   // witness_with_aux (gwc.rs:118-119, added first :127)
+        out.left_term(vkl.gwc_w_slot[i], pu[i]);
+    }
+    Val eval_multi = b.zero();
+    for (size_t i = 0; i < G; ++i) {
+        Val power_of_v = b.one(), eval_batch = b.zero();
+        for (const Query* q : groups[i]) {
+            Val w = b.mul(power_of_v, pu[i]);
+            if (q->c == QUOTIENT) out.quotient(b, w, c.xn, vkl.h_slot);
+            else out.term(b, q->c, w);   // commitment_multi, query by query (gwc.rs:96-116)
+            eval_batch = b.add(eval_batch, b.mul(power_of_v, eval_of(b, *q, h_eval)));
+            power_of_v = b.mul(c.sv, power_of_v);
+        }
+        eval_multi = b.add(eval_multi, b.mul(pu[i], eval_batch));
+    }
+    out.term(b, {1, (uint32_t)out.shared.size() - 1}, eval_multi);   // (eval_multi, -g) (gwc.rs:130-131)
+}
+
+// shplonk.rs:202-264
+void shplonk_scalars(Builder& b, const Domain& dom, const Challenges& c, const Opening& op, const std::map<int64_t, Val>& point_of, const Inverses& iv, Val h_eval,
+                     const VkLayout& vkl, const Plan& plan, Scalars& out) {
+    auto eval_at = [&](const Term& t, int64_t rot) -> Val {
+        for (const Query& q : op.queries) if (q.c == t && q.rot == rot) return eval_of(b, q, h_eval);
+        return b.zero();
     };
-    std::vector<Val> left_scalar(np, (Val)-1);
-    if (gwc) {
-        // gwc.rs:86-132: point group i has weight u^i, query j inside it weight v^j
-        std::vector<std::vector<const SymQuery*>> groups(gwc_points.size());
-        for (const SymQuery& q : queries) {
-            size_t gi = std::find(gwc_points.begin(), gwc_points.end(), q.rot) - gwc_points.begin();
-            if (gi >= groups.size()) { err = "internal: opening point missing from the GWC point list"; return H2V_ERR_BAD_ARGUMENT; }
-            groups[gi].push_back(&q);
-        }
-        // reference term order of the right channel: witness_with_aux, commitment_multi, (eval_multi, -g)
-        Val power_of_u = b.one();
-        std::vector<Val> pu(groups.size());
-        for (size_t i = 0; i < groups.size(); ++i) { pu[i] = power_of_u; power_of_u = b.mul(su, power_of_u); }
-        auto guard_term = [&](std::pair<uint8_t, uint32_t> where, Val v) {
-            if (!opts.guard_terms) return;
-            b.store_guard(v, (uint32_t)plan.guard_term_order.size());
-            plan.guard_term_order.push_back(where);
-        };
-        for (size_t i = 0; i < groups.size(); ++i) {
-            const Val wz = b.mul(pu[i], point_of[gwc_points[i]]);
-            assign({0, gwc_w_slot[i]}, wz);
-            guard_term({0, gwc_w_slot[i]}, wz);            // witness_with_aux (gwc.rs:118-119, added to the right channel first :127)
-            left_scalar[gwc_w_slot[i]] = pu[i];
-            plan.left_term_order.push_back({0, gwc_w_slot[i]});
-        }
-        Val eval_multi = b.zero();
-        for (size_t i = 0; i < groups.size(); ++i) {
-            Val power_of_v = b.one(), eval_batch = b.zero();
-            for (const SymQuery* q : groups[i]) {
-                Val w = b.mul(power_of_v, pu[i]);
-                if (q->c.kind == K_H_MSM) {
-                    std::vector<Val> xnp(H); if (H) xnp[0] = b.one();
-                    for (size_t t = 1; t < H; ++t) xnp[t] = b.mul(xnp[t - 1], xn);
-                    for (size_t t = H; t-- > 0;) { const Val hw = b.mul(w, xnp[t]); assign({0, h_slot[t]}, hw); guard_term({0, h_slot[t]}, hw); }
-                } else { assign(slot_of(q->c), w); guard_term(slot_of(q->c), w); }   // commitment_multi, query by query (gwc.rs:96-116)
-                eval_batch = b.add(eval_batch, b.mul(power_of_v, q->eval));
-                power_of_v = b.mul(sv, power_of_v);
-            }
-            eval_multi = b.add(eval_multi, b.mul(pu[i], eval_batch));
-        }
-        plan.shared_bases.back().y = plan.shared_bases.back().y.neg();  // the last VK-wide base is -g for GWC (gwc.rs:130-131)
-        assign({1, (uint32_t)(F + P)}, eval_multi);
-        guard_term({1, (uint32_t)(F + P)}, eval_multi);    // (eval_multi, -g) (gwc.rs:130-131)
-    } else {
     Val z_0 = b.one();
-    for (int64_t r : rsets[0].rots) z_0 = b.mul(b.sub(su, point_of[r]), z_0);
+    for (int64_t r : op.sets[0].rots) z_0 = b.mul(b.sub(c.su, point_of.at(r)), z_0);
     Val r_outer = b.zero();
     Val power_of_v = b.one();
-    // powers of x^-1 for the interpolation denominators
-    std::vector<Val> xinv_pow = {b.one(), x_inv};
-    for (size_t i = 0; i < rsets.size(); ++i) {
-        const RotSet& rs = rsets[i];
-        Val z_diff_i;
-        if (i == 0) z_diff_i = b.one();
-        else {
-            Val zd = b.one();
-            for (int64_t r : super) if (std::find(rs.rots.begin(), rs.rots.end(), r) == rs.rots.end()) zd = b.mul(b.sub(su, point_of[r]), zd);
-            z_diff_i = b.mul(zd, z_0_diff_inverse);
-        }
+    std::vector<Val> xinv_pow = {b.one(), iv.x_inv};   // powers of x^-1 for the interpolation denominators
+    for (size_t i = 0; i < op.sets.size(); ++i) {
+        const RotSet& rs = op.sets[i];
+        const Val z_diff_i = i == 0 ? b.one() : b.mul(z_outside(b, op, rs, c.su, point_of), iv.z_0_diff_inverse);
         // Lagrange weights at u over this set's points: W_k = prod_{m != k}(u - p_m) / prod_{m != k}(p_k - p_m),
         // p_k - p_m = x (omega^rk - omega^rm): the omega part is a per-VK constant, the x part one shared inverse.
         size_t s = rs.rots.size();
         std::vector<Val> W(s);
         if (s > 1) {
-            while (xinv_pow.size() < s) xinv_pow.push_back(b.mul(xinv_pow.back(), x_inv));
+            while (xinv_pow.size() < s) xinv_pow.push_back(b.mul(xinv_pow.back(), iv.x_inv));
             for (size_t k2 = 0; k2 < s; ++k2) {
                 Fr cden = Fr::one();
                 Val num = b.one();
                 for (size_t m = 0; m < s; ++m) {
                     if (m == k2) continue;
-                    cden = cden * (omega_pow(rs.rots[k2]) - omega_pow(rs.rots[m]));
-                    num = b.mul(num, b.sub(su, point_of[rs.rots[m]]));
+                    cden = cden * (dom.pow(rs.rots[k2]) - dom.pow(rs.rots[m]));
+                    num = b.mul(num, b.sub(c.su, point_of.at(rs.rots[m])));
                 }
                 W[k2] = b.mul(b.mul(num, xinv_pow[s - 1]), b.cst(cden.inv()));
             }
@@ -1054,57 +1037,71 @@ int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<s
         Val set_weight = b.mul(power_of_v, z_diff_i);
         Val r_inner = b.zero();
         Val power_of_y = b.one();
-        for (size_t j = 0; j < rs.commits.size(); ++j) {
-            const CommitRef& c = rs.commits[j];
+        for (const Term& t : rs.commits) {
             Val r_u;  // r_ij(u)
-            if (s == 1) r_u = eval_of(c, rs.rots[0]);
-            else { r_u = b.zero(); for (size_t k2 = 0; k2 < s; ++k2) r_u = b.add(r_u, b.mul(eval_of(c, rs.rots[k2]), W[k2])); }
+            if (s == 1) r_u = eval_at(t, rs.rots[0]);
+            else { r_u = b.zero(); for (size_t k2 = 0; k2 < s; ++k2) r_u = b.add(r_u, b.mul(eval_at(t, rs.rots[k2]), W[k2])); }
             r_inner = b.add(r_inner, b.mul(power_of_y, r_u));
             Val term_scalar = b.mul(power_of_y, set_weight);
-            if (c.kind == K_H_MSM) {
-                // nested MSM: bases h_{H-1} .. h_0 with scalars xn^{H-1} .. 1 (vanishing.rs:102-112)
-                std::vector<Val> xnp(H); if (H) xnp[0] = b.one();
-                for (size_t t = 1; t < H; ++t) xnp[t] = b.mul(xnp[t - 1], xn);
-                for (size_t t = H; t-- > 0;) assign({0, h_slot[t]}, b.mul(term_scalar, xnp[t]));
-            } else {
-                assign(slot_of(c), term_scalar);
-            }
-            power_of_y = b.mul(sy, power_of_y);
+            if (t == QUOTIENT) out.quotient(b, term_scalar, c.xn, vkl.h_slot);
+            else out.term(b, t, term_scalar);
+            power_of_y = b.mul(c.sy, power_of_y);
         }
         r_outer = b.add(r_outer, b.mul(b.mul(power_of_v, r_inner), z_diff_i));
-        power_of_v = b.mul(sv, power_of_v);
+        power_of_v = b.mul(c.sv, power_of_v);
     }
-    assign({1, (uint32_t)(F + P)}, b.neg(r_outer));
-    assign({0, plan.slot_h1}, b.neg(z_0));
-    assign({0, plan.slot_h2}, su);
-    left_scalar[plan.slot_h2] = b.one();   // left channel: (1, h2) per proof (shplonk.rs:262)
-    plan.left_term_order.push_back({0, plan.slot_h2});
-    }
-    // stores, scaled by the proof's batch multiplier (kzg/strategy.rs:129, msm.rs:173-176)
-    for (uint32_t s2 = 0; s2 < np; ++s2) b.store_msm(msm_scalar[s2] == (Val)-1 ? b.zero() : b.mul(msm_scalar[s2], mult), s2);
-    for (uint32_t j = 0; j < plan.n_shared; ++j) b.store_shared(shared_scalar[j] == (Val)-1 ? b.zero() : b.mul(shared_scalar[j], mult), j);
-    for (uint32_t s2 = 0; s2 < np; ++s2) if (left_scalar[s2] != (Val)-1) b.store_left(b.mul(left_scalar[s2], mult), s2);
+    out.term(b, {1, (uint32_t)out.shared.size() - 1}, b.neg(r_outer));
+    out.term(b, {0, plan.slot_h1}, b.neg(z_0));
+    out.term(b, {0, plan.slot_h2}, c.su);
+    out.left_term(plan.slot_h2, b.one());   // left channel: (1, h2) per proof (shplonk.rs:262)
+}
+}  // namespace
 
+int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<size_t>& col_lens, PlanOptions opts, Plan& plan, std::string& err) {
+    plan.opts = opts;
+    Shape s;
+    if (const int rc = check_shape(vk, params, col_lens, opts, plan, s, err)) return rc;
+    const Domain dom(vk.k);
+    plan.domain_k = vk.k; plan.omega = dom.omega; plan.n_inv = dom.n_inv;
+    // proof layout, transcript stream, query list
+    Transcript tr{plan};
+    std::vector<InstanceLayout> inst(s.M);
+    VkLayout vkl;
+    lay_out_proof(vk, s, opts.transcript, tr, inst, vkl);
+    const Opening op = opening(vk, s, dom, inst, vkl);
+    lay_out_multiopen(s, op, tr, vkl);
+    // the Fr program
+    Builder b;
+    const Challenges c = load_challenges(b, s, plan, vk.k);
+    load_evaluations(b, inst, vkl);
+    std::map<int64_t, Val> point_of;  // x * omega^rot for the opening points
+    for (int64_t r : op.super) point_of[r] = b.mul(c.x, b.cst(dom.pow(r)));
+    const Val z_diff_0 = s.gwc ? b.one() : z_outside(b, op, op.sets[0], c.su, point_of);
+    const Inverses iv = invert(b, vk, s, dom, col_lens, plan.wide_instances, c, z_diff_0);
+    const std::vector<std::vector<Val>> instance_evals = instance_evaluations(b, vk, s, dom, iv, plan);
+    bool panic = false;
+    const Val h_eval = expected_h_eval(b, vk, s, dom, c, iv, inst, vkl, instance_evals, panic);
+    if (panic) { err = "the VK makes the reference panic (empty expression polynomial or out-of-range index)"; return H2V_ERR_REFERENCE_PANIC; }
+    // the multi-open scalars
+    const Val mult = b.load_mult();
+    plan.shared_bases.clear();
+    for (const G1A& g : vk.fixed_commitments) plan.shared_bases.push_back(g);
+    for (const G1A& g : vk.permutation_commitments) plan.shared_bases.push_back(g);
+    plan.shared_bases.push_back(params.g);
+    if (s.gwc) plan.shared_bases.back().y = plan.shared_bases.back().y.neg();  // the last VK-wide base is -g for GWC (gwc.rs:130-131)
+    plan.n_shared = (uint32_t)plan.shared_bases.size();
+    Scalars out(plan.n_points, plan.n_shared, opts.guard_terms && s.gwc);
+    if (s.gwc) gwc_scalars(b, c, op, point_of, h_eval, vkl, out);
+    else shplonk_scalars(b, dom, c, op, point_of, iv, h_eval, vkl, plan, out);
+    plan.right_term_order = out.right_order; plan.left_term_order = out.left_order; plan.guard_term_order = out.guard_order;
+    // stores, scaled by the proof's batch multiplier (kzg/strategy.rs:129, msm.rs:173-176)
+    for (uint32_t i = 0; i < plan.n_points; ++i) b.store_msm(out.msm[i] == NONE ? b.zero() : b.mul(out.msm[i], mult), i);
+    for (uint32_t j = 0; j < plan.n_shared; ++j) b.store_shared(out.shared[j] == NONE ? b.zero() : b.mul(out.shared[j], mult), j);
+    for (uint32_t i = 0; i < plan.n_points; ++i) if (out.left[i] != NONE) b.store_left(b.mul(out.left[i], mult), i);
     b.emit(plan.code, plan.n_slots);
     for (int K = 2; K <= FRVM_MAX_STREAMS; ++K) { b.emit_streams(K, plan.code_k[K - 2], plan.n_slots_k[K - 2]); plan.makespan_k[K - 2] = b.makespan_k; }
-    {   // diagnostics kept with the plan (tests/cpp/plan_host.hip prints them): the DAG's work and critical path in units of one Fr product
-        std::vector<double> depth(b.nodes.size(), 0.0);
-        double work = 0, cp = 0;
-        for (size_t i = 0; i < b.nodes.size(); ++i) {
-            const Node& nd = b.nodes[i];
-            double d0 = 0;
-            const bool two = nd.op == OP_MUL || nd.op == OP_ADD || nd.op == OP_SUB;
-            const bool one = two || nd.op == OP_NEG || nd.op == OP_INV || nd.op == OP_POW || nd.op == OP_SQRN || nd.op == OP_STORE_MSM || nd.op == OP_STORE_SHARED || nd.op == OP_STORE_LEFT || nd.op == OP_STORE_GUARD;
-            if (one) d0 = depth[nd.a];
-            if (two) d0 = std::max(d0, depth[nd.b]);
-            const double w = nd.op == OP_CONST ? 0.0 : Builder::op_weight(nd);
-            depth[i] = d0 + w;
-            work += w; cp = std::max(cp, depth[i]);
-        }
-        plan.dag_work = work; plan.dag_critical_path = cp;
-    }
+    b.dag_costs(plan.dag_work, plan.dag_critical_path);
     plan.consts = b.consts;
-    // LOAD_CHAL immediates already refer to squeeze order
     return 0;
 }
 
