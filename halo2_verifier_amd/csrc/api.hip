@@ -1,5 +1,5 @@
 // C-ABI entry points (include/h2v.h): context, standalone MSM and pairing check.
-// The batch-verification entry points live in batch.hip.
+// The batch-verification entry points live in batch.hip (staged) and oneshot.hip (one-shot).
 #include "../../include/h2v.h"
 #include "ctx.h"
 #include <mutex>

@@ -122,6 +122,13 @@ struct LaunchRecord {           // what the last launch (or fold) left (close_en
     bool pieces = false;        // no pairing, accumulators in pieces only: acc / out_bytes are put together on demand (ensure_whole)
     bool tail_on_aux = false;   // whatever the stage: its whole accumulators, their bytes and the result copy are still on the auxiliary stream (join_tail)
 };
+// The staged batch's steps (batch.hip) that the one-shot entry points (oneshot.hip) run on their scratch batches
+int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false);
+int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
+                const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false);
+int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
+bool pairing_passed(const h2v_batch* b, uint32_t g);
+int export_whole_records(h2v_batch* b, void* device_dst);
 }  // namespace h2v
 
 struct h2v_batch {

@@ -1,18 +1,15 @@
-// C-ABI batch verification entry points (include/h2v.h): staged upload / launch / finish, the
-// one-shot h2v_verify_batch / h2v_verify_each / h2v_guard_msm built on them, and h2v_fold_check.
+// C-ABI staged batch (include/h2v.h, h2v_batch_*): upload / launch / finish, range re-checks, export and fold.  The one-shot entry
+// points (oneshot.hip) run on it through the steps batch.h declares.
 #include "../../include/h2v.h"
 #include "batch.h"
 #include <string.h>
 #include <algorithm>
-#include <functional>
-#include <map>
-#include <memory>
 #include <utility>
 #include <stdio.h>
 
 using namespace h2v;
 
-namespace {
+namespace h2v {
 
 // Element counts of a batch's buffers for a plan, max_proofs N and G groups.  The batch keeps the largest it has met (ensure_buffers).
 struct BatchSizes {
@@ -94,9 +91,95 @@ int os_random_scalars(std::vector<uint8_t>& out, size_t n) {
     return 0;
 }
 
+// A call made from a stage it does not accept: every call accepts the stages from `least` on
+int require_stage(const h2v_batch* b, BatchStage least, const char* who) {
+    if (b && b->stage >= least) return 0;
+    static const char* const missing[] = {"", "nothing uploaded since the last failed call or set_groups", "nothing launched", "no finished launch"};
+    set_last_error(std::string(who) + ": " + (b ? missing[(int)least] : "null argument"));
+    return H2V_ERR_BAD_ARGUMENT;
+}
+
+// The stage an operation leaves: Empty on every way out but its last step, commit(its stage of success).  (b may be null.)
+struct StageCommit {
+    h2v_batch* b;
+    ~StageCommit() { if (b) b->stage = BatchStage::Empty; }
+    void commit(BatchStage st) { b->stage = st; b = nullptr; }
+};
+
+#define H2V_SPLIT_MAX_GROUPS 64u
+
+// The two MSM problems of the proofs [p0, p0 + count) of an uploaded batch: acc2[0] <- the left channel (SHPLONK: sum_p m_p * h2_p;
+// GWC: the witness points), acc2[1] <- the right channel = the proofs' pooled Guard terms + the VK-wide bases with the n_shared
+// folded scalars `shared_scal`.  Both index the batch's point array; unused slots have zero scalars and cost nothing.
+void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_t p0, uint32_t count, G1J* acc2, const uint32_t* shared_scal, uint32_t n_shared) {
+    const uint32_t np = pl.n_points;
+    const size_t first = p0 * np;
+    if (pl.left_term_order.size() == 1 && !pl.left_term_order[0].first) {
+        // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of `count` terms, not the
+        // count * np slots with `count` of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
+        const size_t at = first + pl.left_term_order[0].second;
+        pr.p.push_back(MsmProblem(b->left_scal.p + at * 8, b->pts.p + at, acc2, 8 * np, np, count));
+        pr.p.back().phi = b->phi.p + at;
+    } else {
+        pr.p.push_back(MsmProblem(b->left_scal.p + first * 8, b->pts.p + first, acc2, 8, 1, count * np));
+        pr.p.back().phi = b->phi.p + first;
+        pr.p.back().nnz = count * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
+    }
+    pr.p.push_back(MsmProblem(b->msm_scal.p + first * 8, b->pts.p + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts.p + (size_t)b->n * np, n_shared));
+    pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
+}
+
+// The end of a launch: the pairing checks and the conversion of the accumulators to affine bytes only READ the accumulators, and
+// both are latency chains on a few waves (0.5 ms and 0.35 ms) — they run side by side, the conversion and the copy of the result block
+// on the batch's auxiliary stream.  That stream is NOT joined back into the main one (its last event, ev_join, is what join_tail makes
+// the main stream wait for if anything but h2v_batch_finish comes next).
+int close_enqueue(h2v_batch* b, bool with_pairing) {
+    hipStream_t s = b->stream;
+    const uint32_t G = b->groups;
+    int rc;
+    b->last.pairing = with_pairing; b->last.pieces = false;
+    if (!with_pairing) {
+        if (b->split.parts) { b->last.pieces = true; return 0; }   // pieces only for now
+        return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
+    }
+    H2V_HIP_CHECK(hipEventRecord(b->ev_fork, s));
+    H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork, 0));
+    // (beside the pairing: kept off the pairing workgroups' CUs by an LDS request, internal.h)
+    if (b->split.parts && (rc = msm_combine_enqueue(b->aux, b->ws, b->split, H2V_AUX_LDS_RESERVE))) return rc;   // acc <- the whole points
+    if ((rc = point_to_bytes_enqueue(b->aux, b->acc.p, b->out_bytes, b->out_ident, 2 * G, H2V_AUX_LDS_RESERVE))) return rc;
+    // the result block (all but the verdicts, which the pairing kernel writes to the host itself) goes back on the auxiliary stream too, and the
+    // main stream does NOT wait for it: its last operation is the pairing kernel — the join (a barrier packet) and the copy behind it were
+    // 16 us at the end of every launch.  h2v_batch_finish waits for both streams; anything else that touches the batch first calls join_tail.
+    // (by a kernel, not hipMemcpyAsync: a copy enqueued now, behind kernels that end a launch later, can hold up an SDMA queue — util.hip)
+    const ResultsLayout L{G, b->n};
+    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), static_cast<uint8_t*>(b->results_host.dev) + L.fold_failed(), (L.total() - L.fold_failed()) / 4,
+                                 H2V_AUX_LDS_RESERVE))) return rc;
+    H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
+    b->last.tail_on_aux = true;
+    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
+    else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc.p, G, b->ok))) return rc;
+    return 0;
+}
+// the main stream waits for what the last launch left on the auxiliary stream (before anything new reads or overwrites it)
+int join_tail(h2v_batch* b) {
+    if (!b->last.tail_on_aux) return 0;
+    b->last.tail_on_aux = false;
+    H2V_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_join, 0));
+    return 0;
+}
+// the whole accumulators (acc) and their affine bytes, if the last launch left pieces only
+int ensure_whole(h2v_batch* b) {
+    if (!b->last.pieces) return 0;
+    int rc;
+    if ((rc = msm_combine_enqueue(b->stream, b->ws, b->split))) return rc;
+    if ((rc = point_to_bytes_enqueue(b->stream, b->acc.p, b->out_bytes, b->out_ident, 2 * b->groups))) return rc;
+    b->last.pieces = false;
+    return 0;
+}
+
 // The draws of a call: the caller's `rand32` (n scalars, refused unless canonical) or, when it is null, n OS draws kept in `storage`.
 // `nonzero`: a zero draw of the caller's is refused and an OS draw of zero is drawn again.
-int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false) {
+int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero) {
     int rc;
     std::vector<uint8_t> one;
     if (!rand32) {
@@ -113,27 +196,11 @@ int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storag
     return 0;
 }
 
-// A call made from a stage it does not accept: every call accepts the stages from `least` on
-int require_stage(const h2v_batch* b, BatchStage least, const char* who) {
-    if (b && b->stage >= least) return 0;
-    static const char* const missing[] = {"", "nothing uploaded since the last failed call or set_groups", "nothing launched", "no finished launch"};
-    set_last_error(std::string(who) + ": " + (b ? missing[(int)least] : "null argument"));
-    return H2V_ERR_BAD_ARGUMENT;
-}
-
-// The stage an operation leaves: Empty on every way out but its last step, commit(its stage of success).  (b may be null.)
-struct StageCommit {
-    h2v_batch* b;
-    ~StageCommit() { if (b) b->stage = BatchStage::Empty; }
-    void commit(BatchStage st) { b->stage = st; b = nullptr; }
-};
-
-int join_tail(h2v_batch* b);
 // `overlap`: the copies run on the batch's copy stream in chunks and the decompression of every chunk is enqueued on the batch's own
 // stream behind that chunk's event (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
 // `guard`: the guard variant of the plan (h2v_guard_msm)
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
-                const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false) {
+                const uint8_t* rand_tail, size_t n_tail, bool overlap, bool guard) {
     StageCommit commit{b};
     if (!b || (n && !proofs_flat)) { set_last_error("h2v_batch_upload: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (n > b->max_proofs) { set_last_error("h2v_batch_upload: n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
@@ -245,34 +312,8 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     return 0;
 }
 
-int close_enqueue(h2v_batch* b, bool with_pairing);
-int ensure_whole(h2v_batch* b);
-int export_batch_records(h2v_batch* b, void* device_dst);
-#define H2V_SPLIT_MAX_GROUPS 64u
-
-// The two MSM problems of the proofs [p0, p0 + count) of an uploaded batch: acc2[0] <- the left channel (SHPLONK: sum_p m_p * h2_p;
-// GWC: the witness points), acc2[1] <- the right channel = the proofs' pooled Guard terms + the VK-wide bases with the n_shared
-// folded scalars `shared_scal`.  Both index the batch's point array; unused slots have zero scalars and cost nothing.
-void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_t p0, uint32_t count, G1J* acc2, const uint32_t* shared_scal, uint32_t n_shared) {
-    const uint32_t np = pl.n_points;
-    const size_t first = p0 * np;
-    if (pl.left_term_order.size() == 1 && !pl.left_term_order[0].first) {
-        // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of `count` terms, not the
-        // count * np slots with `count` of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
-        const size_t at = first + pl.left_term_order[0].second;
-        pr.p.push_back(MsmProblem(b->left_scal.p + at * 8, b->pts.p + at, acc2, 8 * np, np, count));
-        pr.p.back().phi = b->phi.p + at;
-    } else {
-        pr.p.push_back(MsmProblem(b->left_scal.p + first * 8, b->pts.p + first, acc2, 8, 1, count * np));
-        pr.p.back().phi = b->phi.p + first;
-        pr.p.back().nnz = count * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
-    }
-    pr.p.push_back(MsmProblem(b->msm_scal.p + first * 8, b->pts.p + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts.p + (size_t)b->n * np, n_shared));
-    pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
-}
-
 // ext_mult / ext_idx: the multipliers of a non-contiguous subset of a larger accumulation (h2v_verify_batch_shapes), instead of the draws'
-int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr) {
+int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32_t* ext_idx) {
     int rc;
     if ((rc = require_stage(b, BatchStage::Uploaded, "h2v_batch_launch"))) return rc;
     StageCommit commit{b};
@@ -363,60 +404,6 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, co
     return 0;
 }
 
-// The end of a launch: the pairing checks and the conversion of the accumulators to affine bytes only READ the accumulators, and
-// both are latency chains on a few waves (0.5 ms and 0.35 ms) — they run side by side, the conversion and the copy of the result block
-// on the batch's auxiliary stream.  That stream is NOT joined back into the main one (its last event, ev_join, is what join_tail makes
-// the main stream wait for if anything but h2v_batch_finish comes next).
-int close_enqueue(h2v_batch* b, bool with_pairing) {
-    hipStream_t s = b->stream;
-    const uint32_t G = b->groups;
-    int rc;
-    b->last.pairing = with_pairing; b->last.pieces = false;
-    if (!with_pairing) {
-        if (b->split.parts) { b->last.pieces = true; return 0; }   // pieces only for now
-        return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
-    }
-    H2V_HIP_CHECK(hipEventRecord(b->ev_fork, s));
-    H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork, 0));
-    // (beside the pairing: kept off the pairing workgroups' CUs by an LDS request, internal.h)
-    if (b->split.parts && (rc = msm_combine_enqueue(b->aux, b->ws, b->split, H2V_AUX_LDS_RESERVE))) return rc;   // acc <- the whole points
-    if ((rc = point_to_bytes_enqueue(b->aux, b->acc.p, b->out_bytes, b->out_ident, 2 * G, H2V_AUX_LDS_RESERVE))) return rc;
-    // the result block (all but the verdicts, which the pairing kernel writes to the host itself) goes back on the auxiliary stream too, and the
-    // main stream does NOT wait for it: its last operation is the pairing kernel — the join (a barrier packet) and the copy behind it were
-    // 16 us at the end of every launch.  h2v_batch_finish waits for both streams; anything else that touches the batch first calls join_tail.
-    // (by a kernel, not hipMemcpyAsync: a copy enqueued now, behind kernels that end a launch later, can hold up an SDMA queue — util.hip)
-    const ResultsLayout L{G, b->n};
-    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), static_cast<uint8_t*>(b->results_host.dev) + L.fold_failed(), (L.total() - L.fold_failed()) / 4,
-                                 H2V_AUX_LDS_RESERVE))) return rc;
-    H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
-    b->last.tail_on_aux = true;
-    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
-    else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc.p, G, b->ok))) return rc;
-    return 0;
-}
-// the main stream waits for what the last launch left on the auxiliary stream (before anything new reads or overwrites it)
-int join_tail(h2v_batch* b) {
-    if (!b->last.tail_on_aux) return 0;
-    b->last.tail_on_aux = false;
-    H2V_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_join, 0));
-    return 0;
-}
-// the whole accumulators (acc) and their affine bytes, if the last launch left pieces only
-int ensure_whole(h2v_batch* b) {
-    if (!b->last.pieces) return 0;
-    int rc;
-    if ((rc = msm_combine_enqueue(b->stream, b->ws, b->split))) return rc;
-    if ((rc = point_to_bytes_enqueue(b->stream, b->acc.p, b->out_bytes, b->out_ident, 2 * b->groups))) return rc;
-    b->last.pieces = false;
-    return 0;
-}
-// the batch's accumulator records (pieces if the launch left pieces)
-int export_batch_records(h2v_batch* b, void* device_dst) {
-    { int rcj = join_tail(b); if (rcj) return rcj; }
-    if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
-    return export_records_enqueue(b->stream, b->acc.p, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
-}
-
 // the batch's accumulator records as whole points.  For a record in pieces, the one-pairing fold (fold_check_locked) puts the pieces
 // together with ~254 dependent doublings per record, one record after another: 1.15 ms for two records at 1024 proofs each, where
 // the batch's own msm_combine_parts takes 0.34 ms on its stream, beside the other batches of the call (h2v_verify_batch_keys).
@@ -489,12 +476,16 @@ bool pairing_passed(const h2v_batch* b, uint32_t g) {
     return b->last.pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
 }
 
+}  // namespace h2v
+
+extern "C" {
+
 // Range re-checks (h2v_batch_recheck).  A range [first, first + count) of group g is checked as the launch checks the whole group:
 // e(sum_p m_p L_p, s_g2) e(sum_p m_p R_p, -g2) = 1 over its proofs' resident scalars (already multiplied by m_p, zeroed for failed
 // proofs) — the range's own fold of the VK-wide scalars, two MSMs, one pairing.  Nothing before the MSM runs again, and nothing the
 // launch left (ws, acc, split, the result block) is touched: the re-check has its own workspace and outputs (b->recheck).
 // At most MSM_MAX_PROBLEMS / 2 ranges, and about the launch's own term count, go into one set of launches.
-int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
+int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
     int rc;
     if ((rc = require_stage(b, BatchStage::Finished, "h2v_batch_recheck"))) return rc;
     if (n_ranges && (!first || !count || !range_ok)) { set_last_error("h2v_batch_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
@@ -562,124 +553,6 @@ int recheck_impl(h2v_batch* b, size_t n_ranges, const size_t* first, const size_
     }
     return 0;
 }
-
-// A one-shot call's hold on its context: ctx->mu (the context's stream and scratch batch serve one call at a time) and, once taken, the
-// scratch batch, given back at the end of the call — or destroyed if it holds more than H2V_SCRATCH_BATCH_MAX proofs.  (After an error it is Empty.)
-#define H2V_SCRATCH_BATCH_MAX 1024u
-struct ScratchBatch {
-    h2v_ctx* const ctx;
-    std::lock_guard<std::mutex> lock;
-    h2v_batch* b = nullptr;
-    explicit ScratchBatch(h2v_ctx* c) : ctx(c), lock(c->mu) {}
-    ~ScratchBatch() { if (b && b->max_proofs <= H2V_SCRATCH_BATCH_MAX && !ctx->scratch_batch) ctx->scratch_batch = b; else h2v_batch_destroy(b); }
-    int take(size_t capacity, size_t max_inst) {   // the context's batch, or a new one if it has none or a smaller one (once per holder)
-        b = std::exchange(ctx->scratch_batch, nullptr);
-        if (b && (b->max_proofs < capacity || b->max_inst < max_inst)) { h2v_batch_destroy(b); b = nullptr; }
-        return b ? 0 : h2v_batch_create(ctx, capacity, max_inst, &b);
-    }
-};
-
-// The argument checks of a one-shot call over one instance shape, its plan (in `pin`), and its pointer-array proofs / instances packed
-// into the flat layout; proofs shorter than the VK's proof are the reader running dry: "failed to fill whole buffer" -> Error::Transcript,
-// or Opening inside the multi-open part
-int pack_inputs(PlanPin& pin, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
-                const size_t* col_lens, std::vector<uint8_t>& flat, std::vector<uint8_t>& iflat, std::vector<int>& forced) {
-    if ((n && (!proofs || !proof_lens)) || (ncols && !col_lens)) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (!pin.ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ncols != ctx_total_instance_columns(pin.ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
-    if (int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols))) return rc;
-    const Plan& pl = pin.pd->host;
-    const size_t per_inst = (size_t)pl.n_instance_values * 32;
-    flat.assign(n * pl.proof_len, 0); iflat.assign(n * per_inst, 0); forced.assign(n, 0);
-    // byte offset where the multi-open part starts: h1 is the first point after all scalars
-    size_t opening_at = pl.opening_offset;
-    for (size_t i = 0; i < n; ++i) {
-        if (!proofs[i]) { set_last_error("null proof pointer"); return H2V_ERR_BAD_ARGUMENT; }
-        if (proof_lens[i] < pl.proof_len) {
-            // the reader runs dry; every point of the packed copy is made undecodable (x = 2^254-1 >= p) so that the proof
-            // contributes nothing, and the status is set to what the reference reports for the place where it ran dry
-            forced[i] = proof_lens[i] < opening_at ? H2V_ERR_TRANSCRIPT : H2V_ERR_OPENING;
-            memset(&flat[i * pl.proof_len], 0xff, pl.proof_len);
-        } else memcpy(&flat[i * pl.proof_len], proofs[i], pl.proof_len);
-        if (per_inst) { if (!instances32 || !instances32[i]) { set_last_error("null instances pointer"); return H2V_ERR_BAD_ARGUMENT; } memcpy(&iflat[i * per_inst], instances32[i], per_inst); }
-    }
-    return 0;
-}
-
-// One AccumulatorStrategy batch of a one-shot call, run on the context's scratch batch; the batch stays in `sb` for the caller
-int pack_and_run(ScratchBatch& sb, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
-                 const size_t* col_lens, const uint8_t* rand32, int with_pairing, bool guard, int* per_proof_status, int* batch_ok, uint8_t* out_left,
-                 uint8_t* out_right) {
-    PlanPin pin(sb.ctx);
-    std::vector<uint8_t> flat, iflat; std::vector<int> forced;
-    int rc;
-    if ((rc = pack_inputs(pin, n, proofs, proof_lens, instances32, ncols, col_lens, flat, iflat, forced))) return rc;
-    const Plan& pl = pin.pd->host;
-    if ((rc = sb.take(n ? n : 1, pl.n_instance_values)) || (rc = h2v_batch_set_groups(sb.b, 1))) return rc;
-    if ((rc = upload_impl(sb.b, n, flat.data(), pl.proof_len, iflat.data(), ncols, col_lens, rand32, rand32 ? n : 0, false, guard)) ||
-        (rc = launch_impl(sb.b, with_pairing))) return rc;
-    std::vector<int> st(n ? n : 1, 0);
-    int ok = 0;
-    if ((rc = finish_impl(sb.b, "h2v_batch_finish", st.data(), &ok, out_left, out_right))) return rc;
-    for (size_t i = 0; i < n; ++i) if (forced[i]) { st[i] = forced[i]; ok = 0; }
-    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
-    if (batch_ok) *batch_ok = ok;
-    return 0;
-}
-
-// The search of h2v_verify_batch_identify, measured at 1024 proofs (tools/identify_probe.py): every failing range is cut into
-// H2V_IDENTIFY_FANOUT pieces per round — or straight into single proofs once the failing ranges hold at most H2V_IDENTIFY_DIRECT
-// proofs together, one set of re-check launches (MSM_MAX_PROBLEMS / 2 checks).  A round is a latency chain up to ~128 checks (32 ranges
-// of 32 proofs: 1.9 ms, 128 single proofs: 2.0 ms, 512: 4.1 ms), so rounds are what to save: one bad proof in 1024 takes two (32 + 32 checks).
-#define H2V_IDENTIFY_FANOUT 32
-#define H2V_IDENTIFY_DIRECT 512
-
-// the pairing's verdict of a failed batch of one group, proof by proof: st[i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof whose own
-// check fails (st[i] == 0 on entry).  A range whose check fails holds at least one failing proof (the check of a range is the product of its
-// pieces' checks), so every round ends with at least one failing piece per failing range.
-int identify_search(h2v_batch* b, std::vector<int>& st, size_t* n_checks) {
-    const size_t n = st.size();
-    // proofs with a non-zero status contribute nothing: a range is trimmed to its first and last live proof, and one without a live proof passes
-    auto trim = [&](size_t a, size_t c, std::vector<std::pair<size_t, size_t>>& out) {
-        size_t e = a + c;
-        while (a < e && st[a]) ++a;
-        while (e > a && st[e - 1]) --e;
-        if (e > a) out.push_back({a, e - a});
-    };
-    std::vector<std::pair<size_t, size_t>> failing, pieces;
-    trim(0, n, failing);
-    int rc = 0;
-    while (!failing.empty()) {
-        pieces.clear();
-        size_t total = 0;
-        for (auto& r : failing) total += r.second;
-        for (auto& r : failing) {
-            if (r.second == 1) { st[r.first] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE; continue; }   // (its check already was that proof's own)
-            const size_t k = total <= H2V_IDENTIFY_DIRECT ? r.second : std::min<size_t>(H2V_IDENTIFY_FANOUT, r.second);
-            for (size_t i = 0; i < k; ++i) {
-                const size_t a = r.first + r.second * i / k, e = r.first + r.second * (i + 1) / k;
-                trim(a, e - a, pieces);
-            }
-        }
-        if (pieces.empty()) break;
-        std::vector<size_t> f(pieces.size()), c(pieces.size());
-        std::vector<int> ok(pieces.size(), 0);
-        for (size_t i = 0; i < pieces.size(); ++i) { f[i] = pieces[i].first; c[i] = pieces[i].second; }
-        if ((rc = recheck_impl(b, pieces.size(), f.data(), c.data(), ok.data(), nullptr, nullptr))) return rc;
-        *n_checks += pieces.size();
-        failing.clear();
-        for (size_t i = 0; i < pieces.size(); ++i) {
-            if (ok[i]) continue;
-            if (c[i] == 1) st[f[i]] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;
-            else failing.push_back(pieces[i]);
-        }
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
 
 int h2v_random_scalars(uint8_t* out32, size_t n) {
     if (n && !out32) { set_last_error("h2v_random_scalars: null argument"); return H2V_ERR_BAD_ARGUMENT; }
@@ -787,7 +660,9 @@ int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
     if (int rc = require_stage(b, BatchStage::Launched, "h2v_batch_export_accumulators")) return rc;
     if (!device_dst) { set_last_error("h2v_batch_export_accumulators: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
-    return export_batch_records(b, device_dst);
+    if (int rc = join_tail(b)) return rc;   // (the records: pieces if the launch left pieces)
+    if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
+    return export_records_enqueue(b->stream, b->acc.p, nullptr, 1, 0, b->status, b->n, b->groups, device_dst);
 }
 int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, size_t n_parts) {
     int rc;
@@ -813,398 +688,6 @@ int h2v_batch_timings(h2v_batch* b, float* ms, int cap) {
     int k = cap < 7 ? cap : 7;
     for (int i = 0; i < k; ++i) ms[i] = b->last_ms[i];
     return k;
-}
-
-// (the caller holds ctx->mu)
-static int fold_check_locked(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts, int* ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
-    H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    DevBuf<G1J> acc; DevBuf<uint32_t> d_ok, d_ident, d_failed; DevBuf<uint8_t> d_out;   // freed on every return path
-    int rc;
-    if ((rc = acc.alloc(2)) || (rc = d_ok.alloc(1)) || (rc = d_out.alloc(128)) || (rc = d_ident.alloc(2)) || (rc = d_failed.alloc(1))) return rc;
-    uint32_t okv = 0, failed = 0; uint8_t outb[128];
-    if ((rc = fold_records_enqueue(s, device_accumulators, (uint32_t)n_parts, 1, 1, 0, acc.p, nullptr, nullptr, d_failed.p))) return rc;   // whole points: records in pieces are put together
-    if ((rc = pairing_check_enqueue(s, ctx->pairing, acc.p, 1, d_ok.p))) return rc;
-    if ((rc = point_to_bytes_enqueue(s, acc.p, d_out.p, d_ident.p, 2))) return rc;
-    H2V_HIP_CHECK(hipMemcpyAsync(&okv, d_ok.p, 4, hipMemcpyDeviceToHost, s));
-    H2V_HIP_CHECK(hipMemcpyAsync(&failed, d_failed.p, 4, hipMemcpyDeviceToHost, s));
-    H2V_HIP_CHECK(hipMemcpyAsync(outb, d_out.p, 128, hipMemcpyDeviceToHost, s));
-    H2V_HIP_CHECK(hipStreamSynchronize(s));
-    *ok = (okv && !failed) ? 1 : 0;
-    if (out_left_xy) memcpy(out_left_xy, outb, 64);
-    if (out_right_xy) memcpy(out_right_xy, outb + 64, 64);
-    return 0;
-}
-int h2v_fold_check(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts, int* ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    if (!ctx || !device_accumulators || !n_parts || !ok) { set_last_error("h2v_fold_check: bad argument"); return H2V_ERR_BAD_ARGUMENT; }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    return fold_check_locked(ctx, device_accumulators, n_parts, ok, out_left_xy, out_right_xy);
-}
-
-int h2v_verify_batch(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
-                     const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    ScratchBatch sb(ctx);
-    return pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-}
-
-// AccumulatorStrategy::with(msm_accumulator) (kzg/strategy.rs:75-78): the strategy starts from an existing DualMSM — the
-// reference's only pause / resume hook — instead of an empty one.  Every later process() scales the WHOLE accumulator by its fresh
-// draw before the proof's Guard joins (strategy.rs:129), so the seed ends up scaled by the product of ALL n draws of this call:
-// the seed's two channels are evaluated (two pooled MSMs with the scalars already multiplied by that product), written as a
-// record, and folded with the batch's own record into the one pairing.
-int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
-                            const size_t* col_lens, const uint8_t* rand32,
-                            const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
-                            const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
-                            int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    if (!ctx || (n_seed_left && (!seed_left_scalars32 || !seed_left_bases64)) || (n_seed_right && (!seed_right_scalars32 || !seed_right_bases64))) {
-        set_last_error("h2v_verify_batch_seeded: null argument"); return H2V_ERR_BAD_ARGUMENT;
-    }
-    if (n_seed_left > (1u << 24) || n_seed_right > (1u << 24)) { set_last_error("h2v_verify_batch_seeded: seed too large"); return H2V_ERR_BAD_ARGUMENT; }
-    int rc;
-    std::vector<uint8_t> os_rand;
-    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_seeded"))) return rc;
-    // the product of this call's draws, and the seed's scalars times it (host: a few hundred Fr products)
-    Fr M = Fr::one();
-    for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
-    std::vector<uint8_t> sc[2];
-    const uint8_t* in_s[2] = {seed_left_scalars32, seed_right_scalars32};
-    const size_t ns[2] = {n_seed_left, n_seed_right};
-    for (int side = 0; side < 2; ++side) {
-        sc[side].resize(32 * ns[side]);
-        for (size_t j = 0; j < ns[side]; ++j) {
-            Fr v;
-            if (!Fr::from_bytes(in_s[side] + 32 * j, v)) { set_last_error("h2v_verify_batch_seeded: seed scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
-            (v * M).to_bytes(&sc[side][32 * j]);
-        }
-    }
-    uint8_t seed_xy[128];
-    int ident = 0;
-    if ((rc = h2v_msm_g1(ctx, sc[0].data(), seed_left_bases64, n_seed_left, seed_xy, &ident))) return rc;         // (rejects bases that are not on the curve)
-    if ((rc = h2v_msm_g1(ctx, sc[1].data(), seed_right_bases64, n_seed_right, seed_xy + 64, &ident))) return rc;
-    // the proofs: one batch without its pairing, kept for the fold
-    ScratchBatch sb(ctx);
-    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 0, false, per_proof_status, nullptr, nullptr, nullptr))) return rc;
-    h2v_batch* b = sb.b;
-    if (hipSetDevice(ctx->device) != hipSuccess) return H2V_ERR_DEVICE;
-    DevBuf<uint8_t> d_xy, d_records; DevBuf<G1A> d_aff; DevBuf<G1J> d_jac; DevBuf<uint32_t> d_flags;
-    if ((rc = d_xy.alloc(128)) || (rc = d_records.alloc(2 * H2V_ACC_RECORD_BYTES)) || (rc = d_aff.alloc(2)) || (rc = d_jac.alloc(2)) || (rc = d_flags.alloc(2))) return rc;
-    hipStream_t s = b->stream;
-    if (hipMemcpyAsync(d_xy.p, seed_xy, 128, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error("h2v_verify_batch_seeded: copy failed"); return H2V_ERR_DEVICE; }
-    if ((rc = bases_from_bytes_enqueue(s, d_xy.p, d_aff.p, d_flags.p, 2))) return rc;
-    if ((rc = affine_to_jacobian_enqueue(s, d_aff.p, d_jac.p, 2))) return rc;
-    if ((rc = export_batch_records(b, d_records.p))) return rc;                                                                  // record 0: the proofs of this call
-    if ((rc = export_records_enqueue(s, d_jac.p, nullptr, 1, 0, nullptr, 0, 1, d_records.p + H2V_ACC_RECORD_BYTES))) return rc;   // record 1: the scaled seed
-    if ((rc = h2v_batch_fold_check_enqueue(b, d_records.p, 2))) return rc;
-    int ok = 0;
-    if ((rc = finish_impl(b, "h2v_batch_finish", nullptr, &ok, out_left_xy, out_right_xy))) return rc;   // (synchronises: the scoped buffers outlive their use)
-    if (per_proof_status) for (size_t i = 0; i < n; ++i) if (per_proof_status[i] != 0) ok = 0;   // (short proofs: statuses forced on the host)
-    if (batch_ok) *batch_ok = ok;
-    return 0;
-}
-
-// N x verify_proof with per-proof instance shapes (lib.rs:33-49 takes `instances` per call) and, in h2v_verify_batch_keys, per-proof
-// VerifyingKeys (lib.rs:33-49 takes `vk` per call too; kzg/strategy.rs:125-140 only ever sees MSMs): proofs are grouped by (key, shape)
-// (one compiled plan each), every group runs as its own batch without a pairing on its key's scratch batch, and the groups' accumulator
-// records are folded into the single pairing.  The multiplier of proof i is the product of the draws of ALL later proofs in call order
-// (kzg/strategy.rs:129, msm.rs:173-176), whatever group they fall in: the suffix products are computed once over the whole
-// sequence and every group gathers its own.
-// The instance shapes of a call are chosen by whoever supplies the proofs, and every distinct shape costs a plan compilation
-// (O(program length^2) host work, ~10 device uploads) and may grow the batch's buffers: a call takes at most
-// H2V_MAX_SHAPES_PER_CALL distinct (key, shape) groups (H2V_ERR_UNSUPPORTED beyond), the groups of a key share ONE batch object, and
-// the plans go through the context's bounded cache (H2V_MAX_CACHED_PLANS, least recently used out).
-#define H2V_MAX_SHAPES_PER_CALL 64
-
-// the proofs of one key with one instance shape, in call order
-struct CallGroup { size_t key; std::vector<size_t> shape, idx; };
-
-// the (key, shape) groups of a call in first-appearance order; every pointer the groups will read is checked here
-static int group_proofs(const char* who, size_t n, const uint32_t* key_of_proof, const size_t* n_instance_columns, const size_t* col_lens,
-                        const uint8_t* const* proofs, const uint8_t* const* instances32, std::vector<CallGroup>& groups) {
-    std::map<std::pair<size_t, std::vector<size_t>>, size_t> group_of;
-    const size_t* cl = col_lens;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t k = key_of_proof ? key_of_proof[i] : 0, nc = n_instance_columns[k];
-        std::vector<size_t> shape(cl, cl + nc);
-        cl += nc;
-        if (!proofs[i]) { set_last_error(std::string(who) + ": null proof pointer"); return H2V_ERR_BAD_ARGUMENT; }
-        size_t values = 0;
-        for (size_t l : shape) values += l;
-        if (values && (!instances32 || !instances32[i])) { set_last_error(std::string(who) + ": null instances pointer"); return H2V_ERR_BAD_ARGUMENT; }
-        auto it = group_of.find({k, shape});
-        if (it == group_of.end()) {
-            if (groups.size() == H2V_MAX_SHAPES_PER_CALL) { set_last_error(std::string(who) + ": more than 64 distinct (key, instance shape) groups in one call"); return H2V_ERR_UNSUPPORTED; }
-            it = group_of.emplace(std::make_pair(k, shape), groups.size()).first;
-            groups.push_back({k, shape, {}});
-        }
-        groups[it->second].idx.push_back(i);
-    }
-    return 0;
-}
-
-// The groups of a call on their keys' scratch batches (hold[k]: context k's, taken by the caller; keys without a group are not touched),
-// their records (whole points: export_whole_records) folded into ONE pairing on the first group's context.  rand32: the n draws in
-// call order (resolved).
-// Keys do not wait for each other on the host: each round enqueues one group of every key (upload, launch without a pairing, record
-// export on that key's batch stream), then finishes them; groups of one key run one after another on its batch.
-static int run_groups(ScratchBatch* const* hold, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
-                      const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
-    h2v_ctx* fold_ctx = hold[groups[0].key]->ctx;
-    H2V_HIP_CHECK(hipSetDevice(fold_ctx->device));
-    int rc;
-    // the groups of every key, and each group's proof indices at its offset of one index array
-    std::map<size_t, std::vector<size_t>> of_key;
-    std::vector<uint32_t> idx32;
-    std::vector<size_t> idx_off(groups.size());
-    size_t rounds = 0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        std::vector<size_t>& kg = of_key[groups[gi].key];
-        kg.push_back(gi);
-        rounds = std::max(rounds, kg.size());
-        idx_off[gi] = idx32.size();
-        idx32.insert(idx32.end(), groups[gi].idx.begin(), groups[gi].idx.end());
-    }
-    // whole-sequence multipliers on the folding context's stream
-    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
-    if ((rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
-    H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-    H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-    if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p))) return rc;
-    H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
-    // one batch object per key serves every shape group of that key (its buffers grow to the largest group's plan: ensure_buffers)
-    for (auto& kv : of_key) {
-        size_t max_group = 1, max_inst = 0;
-        for (size_t gi : kv.second) { max_group = std::max(max_group, groups[gi].idx.size()); size_t t = 0; for (size_t l : groups[gi].shape) t += l; max_inst = std::max(max_inst, t); }
-        if ((rc = hold[kv.first]->take(max_group, max_inst))) return rc;
-    }
-    // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
-    struct Drain {
-        std::vector<h2v_batch*> bs;
-        ~Drain() { for (h2v_batch* b : bs) { hipStreamSynchronize(b->stream); hipStreamSynchronize(b->aux); } }
-    } drain;
-    for (auto& kv : of_key) drain.bs.push_back(hold[kv.first]->b);
-    std::vector<std::vector<int>> forced(groups.size());
-    bool all_ok = true;
-    for (size_t r = 0; r < rounds; ++r) {
-        for (auto& kv : of_key) {
-            if (r >= kv.second.size()) continue;
-            const size_t gi = kv.second[r];
-            const CallGroup& grp = groups[gi];
-            h2v_batch* b = hold[kv.first]->b;
-            const size_t m = grp.idx.size();
-            std::vector<const uint8_t*> pp(m), ip(m); std::vector<size_t> plen(m);
-            for (size_t j = 0; j < m; ++j) { pp[j] = proofs[grp.idx[j]]; plen[j] = proof_lens[grp.idx[j]]; ip[j] = instances32 ? instances32[grp.idx[j]] : nullptr; }
-            PlanPin pin(b->ctx);
-            std::vector<uint8_t> flat, iflat;
-            if ((rc = pack_inputs(pin, m, pp.data(), plen.data(), ip.data(), grp.shape.size(), grp.shape.data(), flat, iflat, forced[gi]))) return rc;
-            const Plan& pl = pin.pd->host;
-            std::vector<uint8_t> ones(32 * m, 0);
-            for (size_t j = 0; j < m; ++j) ones[32 * j] = 1;      // placeholder draws: the multipliers come from d_mult
-            if ((rc = h2v_batch_set_groups(b, 1)) || (rc = upload_impl(b, m, flat.data(), pl.proof_len, iflat.data(), grp.shape.size(), grp.shape.data(), ones.data(), m)) ||
-                (rc = launch_impl(b, 0, d_mult.p, d_idx.p + idx_off[gi])) || (rc = export_whole_records(b, d_records.p + gi * H2V_ACC_RECORD_BYTES))) return rc;
-        }
-        for (auto& kv : of_key) {
-            if (r >= kv.second.size()) continue;
-            const size_t gi = kv.second[r];
-            const std::vector<size_t>& idx = groups[gi].idx;
-            std::vector<int> st(idx.size(), 0); int gok = 0;
-            if ((rc = finish_impl(hold[kv.first]->b, "h2v_batch_finish", st.data(), &gok, nullptr, nullptr))) return rc;
-            for (size_t j = 0; j < idx.size(); ++j) {
-                int v = forced[gi][j] ? forced[gi][j] : st[j];
-                if (per_proof_status) per_proof_status[idx[j]] = v;
-                if (v != 0) all_ok = false;
-            }
-        }
-    }
-    drain.bs.clear();   // (every group is finished)
-    int ok = 0;
-    if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
-    if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
-    return 0;
-}
-
-int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
-                            size_t n_instance_columns, const size_t* col_lens_per_proof, const uint8_t* rand32, int* per_proof_status, int* batch_ok,
-                            uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    if (!ctx || (n && (!proofs || !proof_lens)) || (n && n_instance_columns && !col_lens_per_proof)) { set_last_error("h2v_verify_batch_shapes: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-    if (n_instance_columns != ctx_total_instance_columns(ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
-    std::vector<CallGroup> groups;
-    int rc;
-    if ((rc = group_proofs("h2v_verify_batch_shapes", n, nullptr, &n_instance_columns, col_lens_per_proof, proofs, instances32, groups))) return rc;
-    if (groups.size() <= 1)
-        return h2v_verify_batch(ctx, n, proofs, proof_lens, instances32, n_instance_columns, n ? col_lens_per_proof : nullptr, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-    std::vector<uint8_t> os_rand;
-    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_shapes"))) return rc;
-    ScratchBatch sb(ctx);   // (the context's stream too)
-    ScratchBatch* hold[1] = {&sb};
-    return run_groups(hold, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-}
-
-// what the accumulation and its pairing read from the params (shplonk.rs's -g term, msm.rs:185-203); k may differ
-static bool same_srs(const ParamsHost& a, const ParamsHost& b) {
-    auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
-    return !memcmp(&a.g, &b.g, sizeof(G1A)) && same_g2(a.g2, b.g2) && same_g2(a.s_g2, b.s_g2);
-}
-
-int h2v_verify_batch_keys(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
-                          const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
-                          int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
-    // every argument check comes before the first HIP call
-    if (!ctxs || !n_keys || !n_instance_columns || (n && (!key_of_proof || !proofs || !proof_lens))) { set_last_error("h2v_verify_batch_keys: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    for (size_t k = 0; k < n_keys; ++k) {
-        if (!ctxs[k]) { set_last_error("h2v_verify_batch_keys: null context"); return H2V_ERR_BAD_ARGUMENT; }
-        if (!ctxs[k]->vk) { set_last_error("h2v_verify_batch_keys: a context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-        for (size_t j = 0; j < k; ++j)
-            if (ctxs[j] == ctxs[k]) { set_last_error("h2v_verify_batch_keys: the same context twice"); return H2V_ERR_BAD_ARGUMENT; }
-        if (ctxs[k]->device != ctxs[0]->device) { set_last_error("h2v_verify_batch_keys: contexts on different devices"); return H2V_ERR_BAD_ARGUMENT; }
-        if (!same_srs(ctxs[k]->params, ctxs[0]->params)) { set_last_error("h2v_verify_batch_keys: contexts over different params (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
-    }
-    for (size_t k = 0; k < n_keys; ++k)
-        if (n_instance_columns[k] != ctx_total_instance_columns(ctxs[k])) { set_last_error("h2v_verify_batch_keys: instances do not match a VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
-    size_t total_cols = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (key_of_proof[i] >= n_keys) { set_last_error("h2v_verify_batch_keys: key index out of range"); return H2V_ERR_BAD_ARGUMENT; }
-        total_cols += n_instance_columns[key_of_proof[i]];
-    }
-    if (total_cols && !col_lens) { set_last_error("h2v_verify_batch_keys: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    std::vector<CallGroup> groups;
-    int rc;
-    if ((rc = group_proofs("h2v_verify_batch_keys", n, key_of_proof, n_instance_columns, col_lens, proofs, instances32, groups))) return rc;
-    if (groups.empty()) {
-        std::vector<size_t> zeros(n_instance_columns[0] ? n_instance_columns[0] : 1, 0);
-        return h2v_verify_batch(ctxs[0], 0, proofs, proof_lens, instances32, n_instance_columns[0], zeros.data(), rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-    }
-    if (groups.size() == 1)   // (one key, one shape: the proofs are that group, in call order)
-        return h2v_verify_batch(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32, per_proof_status,
-                                batch_ok, out_left_xy, out_right_xy);
-    std::vector<uint8_t> os_rand;
-    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_keys"))) return rc;
-    // every context's lock and scratch batch for the whole call, taken in one global order (by address): calls over overlapping sets of
-    // contexts cannot deadlock
-    std::vector<size_t> order(n_keys);
-    for (size_t k = 0; k < n_keys; ++k) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::less<const h2v_ctx*>()(ctxs[a], ctxs[b]); });
-    std::vector<std::unique_ptr<ScratchBatch>> holders(n_keys);
-    std::vector<ScratchBatch*> hold(n_keys);
-    for (size_t k : order) { holders[k].reset(new ScratchBatch(ctxs[k])); hold[k] = holders[k].get(); }
-    return run_groups(hold.data(), groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
-}
-
-int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
-    return recheck_impl(b, n_ranges, first, count, range_ok, out_left_xy, out_right_xy);
-}
-
-int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
-                              const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64],
-                              size_t* n_range_checks) {
-    if (n_range_checks) *n_range_checks = 0;
-    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    // a single proof's check equals SingleStrategy's only when its multiplier is non-zero: no draw may be zero
-    std::vector<uint8_t> os_rand;
-    int rc;
-    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_identify", true))) return rc;
-    std::vector<int> st(n ? n : 1, 0);
-    int ok = 0;
-    ScratchBatch sb(ctx);
-    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, st.data(), &ok, out_left_xy, out_right_xy))) return rc;
-    st.resize(n);
-    size_t checks = 0;
-    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search(sb.b, st, &checks))) return rc;
-    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
-    if (batch_ok) *batch_ok = ok;
-    if (n_range_checks) *n_range_checks = checks;
-    return 0;
-}
-
-int h2v_verify_each(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
-                    const size_t* col_lens, int* per_proof_status) {
-    if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    ScratchBatch sb(ctx);
-    PlanPin pin(ctx);
-    std::vector<uint8_t> flat, iflat; std::vector<int> forced;
-    int rc;
-    if ((rc = pack_inputs(pin, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, flat, iflat, forced))) return rc;
-    const Plan& pl = pin.pd->host;
-    // SingleStrategy (kzg/strategy.rs:143-181) = an accumulator of ONE proof with multiplier 1 and its own pairing: run the
-    // proofs as one-proof groups of grouped launches, at most MSM_MAX_PROBLEMS / 2 per launch
-    const size_t per = MSM_MAX_PROBLEMS / 2, per_inst = (size_t)pl.n_instance_values * 32;
-    if ((rc = sb.take(std::min(n ? n : 1, per), pl.n_instance_values))) return rc;
-    for (size_t off = 0; off < n; off += per) {
-        const size_t m = std::min(per, n - off);
-        std::vector<uint8_t> ones(32 * m, 0);
-        for (size_t i = 0; i < m; ++i) ones[32 * i] = 1;
-        std::vector<int> st(m, 0), gok(m, 0);
-        if ((rc = h2v_batch_set_groups(sb.b, m)) ||
-            (rc = upload_impl(sb.b, m, flat.data() + off * pl.proof_len, pl.proof_len, iflat.data() + off * per_inst, n_instance_columns, col_lens, ones.data(), m)) ||
-            (rc = launch_impl(sb.b, 1)) || (rc = finish_impl(sb.b, "h2v_batch_finish_groups", st.data(), gok.data(), nullptr, nullptr))) return rc;
-        for (size_t i = 0; i < m; ++i) {
-            int v = forced[off + i] ? forced[off + i] : st[i];
-            if (v == 0 && !gok[i]) v = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;  // kzg/strategy.rs:171-175
-            if (per_proof_status) per_proof_status[off + i] = v;
-        }
-    }
-    return 0;
-}
-
-int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const uint8_t* instances32, size_t n_instance_columns, const size_t* col_lens,
-                  uint8_t* right_scalars32, uint8_t* right_bases64, size_t* n_right, uint8_t* left_scalars32, uint8_t* left_bases64, size_t* n_left,
-                  uint8_t* challenges32, size_t* n_challenges) {
-    if (!ctx || !proof || !n_right || !n_left) { set_last_error("h2v_guard_msm: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    uint8_t one[32] = {1};
-    const uint8_t* pp[1] = {proof}; size_t pl1[1] = {proof_len}; const uint8_t* ip[1] = {instances32};
-    int st = 0;
-    ScratchBatch sb(ctx);
-    int rc = pack_and_run(sb, 1, pp, pl1, ip, n_instance_columns, col_lens, one, 0, true, &st, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    if (st != 0) return st;
-    const h2v_batch* b = sb.b;
-    const Plan& pl = b->plan->host;
-    size_t T = pl.right_term_order.size();
-    size_t TL = pl.left_term_order.size();
-    if (T > *n_right || TL > *n_left) { set_last_error("h2v_guard_msm: output capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
-    std::vector<uint32_t> lscal((size_t)pl.n_points * 8);
-    if (hipMemcpy(lscal.data(), b->left_scal.p, lscal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
-    std::vector<uint32_t> scal((size_t)pl.n_points * 8);
-    std::vector<Fr> shared(pl.n_shared);
-    std::vector<G1A> pts(pl.n_points + pl.n_shared);
-    std::vector<Fr> chal(pl.squeeze_at.size());
-    if (hipMemcpy(scal.data(), b->msm_scal.p, scal.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shared.data(), b->shared.p, sizeof(Fr) * pl.n_shared, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(pts.data(), b->pts.p, sizeof(G1A) * pts.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(chal.data(), b->chal.p, sizeof(Fr) * chal.size(), hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
-    auto put_pt = [](const G1A& p, uint8_t* o) { if (p.is_identity()) memset(o, 0, 64); else { p.x.to_bytes(o); p.y.to_bytes(o + 32); } };
-    if (!pl.guard_term_order.empty()) {
-        // GWC: term by term as the reference appends them (gwc.rs:86-132), each with its own scalar
-        T = pl.guard_term_order.size();
-        if (T > *n_right) { set_last_error("h2v_guard_msm: output capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
-        std::vector<uint32_t> gs(T * 8);
-        if (hipMemcpy(gs.data(), b->guard_scal.p, gs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return H2V_ERR_DEVICE;
-        for (size_t t = 0; t < T; ++t) {
-            auto w = pl.guard_term_order[t];
-            memcpy(right_scalars32 + 32 * t, &gs[t * 8], 32);
-            put_pt(pts[w.first ? pl.n_points + w.second : w.second], right_bases64 + 64 * t);
-        }
-    } else
-    for (size_t t = 0; t < T; ++t) {
-        auto w = pl.right_term_order[t];
-        if (w.first) { shared[w.second].to_bytes(right_scalars32 + 32 * t); put_pt(pts[pl.n_points + w.second], right_bases64 + 64 * t); }
-        else { memcpy(right_scalars32 + 32 * t, &scal[(size_t)w.second * 8], 32); put_pt(pts[w.second], right_bases64 + 64 * t); }
-    }
-    *n_right = T;
-    for (size_t t = 0; t < TL; ++t) {
-        uint32_t slot = pl.left_term_order[t].second;
-        memcpy(left_scalars32 + 32 * t, &lscal[(size_t)slot * 8], 32);
-        put_pt(pts[slot], left_bases64 + 64 * t);
-    }
-    *n_left = TL;
-    if (challenges32 && n_challenges) {
-        // reorder squeeze order -> [user challenges.., theta, beta, gamma, y, x, y', v, u]
-        size_t nc = pl.n_challenges;
-        if (nc > *n_challenges) { set_last_error("h2v_guard_msm: challenge capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
-        for (size_t q = 0; q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * pl.squeeze_order[q]);
-        *n_challenges = nc;
-    }
-    return 0;
 }
 
 }  // extern "C"

@@ -136,30 +136,58 @@ def _flatten_instances(instances):
     return bytes(flat), lens
 
 
-def _marshal_batch(ctx, proofs, instances):
-    """Pointer arrays for h2v_verify_batch / h2v_verify_each.  Everything the C side will index is checked here: one
-    instance list per proof, proofs are bytes, every scalar is 32 bytes.  Returns (n, proof ptrs, proof lens, instance
-    ptrs, per-proof column lengths [n][ncols], keep-alive list)."""
+def _sizes(values):
+    """values as a size_t array (of at least one element)"""
+    values = list(values)
+    return (ctypes.c_size_t * max(len(values), 1))(*values)
+
+
+def _col_lens(shapes, ncols):
+    """The column lengths of a call whose proofs share one instance shape: shapes[0], or ncols empty columns for no proofs."""
+    return _sizes(shapes[0] if shapes else [0] * ncols)
+
+
+def _rand_bytes(rand, n):
+    """The draws of a one-shot call as n 32-byte scalars, or None (the library draws them)."""
+    if rand is None:
+        return None
+    if len(rand) != n:
+        raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")   # the C side reads n * 32 bytes
+    return b"".join(_scalar32(r) for r in rand)
+
+
+def _marshal_batch(contexts, proofs, instances, key_of_proof=None):
+    """Pointer arrays for the one-shot calls.  Everything the C side will index is checked here: one instance list per proof,
+    proofs are bytes, key indices are in range, every scalar is 32 bytes, the proofs of a key have one column count.  Proof i
+    belongs to contexts[key_of_proof[i]] (None: to contexts[0]).  Returns (n, proof ptrs, proof lens, instance ptrs, per-proof
+    column lengths [n][ncols], the column count of every key, keep-alive list)."""
     n = len(proofs)
     if len(instances) != n:
         raise ValueError(f"{n} proofs but {len(instances)} instance lists: verify_proof takes one per proof (lib.rs:33-49)")
     for p in proofs:
         if not isinstance(p, (bytes, bytearray)):
             raise TypeError("proofs must be bytes")
-    PA = ctypes.c_char_p * max(n, 1)
-    pa = PA(*[bytes(p) for p in proofs]) if n else PA()
-    pl = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    if key_of_proof is None:
+        keys = [0] * n
+    else:
+        keys = [int(k) for k in key_of_proof]
+        for k in keys:
+            if not 0 <= k < len(contexts):
+                raise ValueError(f"key index {k} out of range for {len(contexts)} contexts")
     flats, shapes = [], []
     for inst in instances:
         f, l = _flatten_instances(inst)
         flats.append(f)
         shapes.append(l)
-    ncols = len(shapes[0]) if shapes else ctx.proof_shape()["n_instance_columns"]
-    for l in shapes:
-        if len(l) != ncols:
-            raise ValueError("all proofs of a batch must have the same number of instance columns")
+    pairs = set(zip(keys, map(len, shapes)))   # (key, column count)
+    ncols = dict(pairs)
+    if len(ncols) != len(pairs):
+        raise ValueError("all proofs of one VerifyingKey must have the same number of instance columns")
+    ncols = [ncols[k] if k in ncols else c.proof_shape()["n_instance_columns"] for k, c in enumerate(contexts)]
+    PA = ctypes.c_char_p * max(n, 1)
+    pa = PA(*[bytes(p) for p in proofs]) if n else PA()
     ia = PA(*flats) if n else PA()
-    return n, pa, pl, ia, shapes, ncols, flats
+    return n, pa, _sizes(len(p) for p in proofs), ia, shapes, ncols, flats
 
 
 class Context:
@@ -243,12 +271,8 @@ class Context:
         seed: an existing accumulator to start from — AccumulatorStrategy::with (kzg/strategy.rs:75-78) — as
         ((left_scalars, left_bases), (right_scalars, right_bases)): scalars ints / 32-byte strings, bases 64-byte x | y.
         Returns (batch_ok, statuses, left_xy, right_xy)."""
-        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(self, proofs, instances)
-        rb = None
-        if rand is not None:
-            if len(rand) != n:
-                raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")   # the C side reads n * 32 bytes
-            rb = b"".join(_scalar32(r) for r in rand)
+        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
+        rb = _rand_bytes(rand, n)
         st = (ctypes.c_int * max(n, 1))()
         ok = ctypes.c_int(0)
         left = ctypes.create_string_buffer(64)
@@ -264,17 +288,12 @@ class Context:
                 if any(len(b) != 64 for b in bases):
                     raise ValueError("every seed base must be 64 bytes (x | y)")
                 sides.append((b"".join(_scalar32(x) for x in scalars), b"".join(bases), len(scalars)))
-            lens = shapes[0] if shapes else [0] * ncols
-            cl = (ctypes.c_size_t * max(ncols, 1))(*lens)
-            check(self._lib.h2v_verify_batch_seeded(self._h, n, pa, pl, ia, ncols, cl, rb, sides[0][0], sides[0][1], sides[0][2], sides[1][0], sides[1][1], sides[1][2],
-                                                    st, ctypes.byref(ok), left, right))
+            check(self._lib.h2v_verify_batch_seeded(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, *sides[0], *sides[1], st, ctypes.byref(ok),
+                                                    left, right))
         elif all(l == shapes[0] for l in shapes):
-            lens = shapes[0] if shapes else [0] * ncols
-            cl = (ctypes.c_size_t * max(ncols, 1))(*lens)
-            check(self._lib.h2v_verify_batch(self._h, n, pa, pl, ia, ncols, cl, rb, st, ctypes.byref(ok), left, right))
+            check(self._lib.h2v_verify_batch(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right))
         else:
-            cl = (ctypes.c_size_t * max(n * ncols, 1))(*[v for l in shapes for v in l])
-            check(self._lib.h2v_verify_batch_shapes(self._h, n, pa, pl, ia, ncols, cl, rb, st, ctypes.byref(ok), left, right))
+            check(self._lib.h2v_verify_batch_shapes(self._h, n, pa, pl, ia, ncols, _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok), left, right))
         return bool(ok.value), list(st)[:n], left.raw, right.raw
 
     def verify_batch_identify(self, proofs, instances, rand=None):
@@ -282,31 +301,23 @@ class Context:
         batch_ok / left_xy / right_xy are what verify_batch returns for the same arguments, statuses[i] is what verify_each returns for
         proof i.  rand: n non-zero scalars or None.  One instance shape per call.  The number of range checks the search ran is kept in
         self.last_range_checks."""
-        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(self, proofs, instances)
+        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
         if not all(l == shapes[0] for l in shapes):
             raise ValueError("verify_batch_identify takes one instance shape per call")
-        rb = None
-        if rand is not None:
-            if len(rand) != n:
-                raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
-            rb = b"".join(_scalar32(r) for r in rand)
-        lens = shapes[0] if shapes else [0] * ncols
-        cl = (ctypes.c_size_t * max(ncols, 1))(*lens)
+        rb = _rand_bytes(rand, n)
         st = (ctypes.c_int * max(n, 1))()
         ok = ctypes.c_int(0)
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
         checks = ctypes.c_size_t(0)
-        check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, cl, rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
+        check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
         self.last_range_checks = checks.value
         return bool(ok.value), list(st)[:n], left.raw, right.raw
 
     def verify_each(self, proofs, instances):
-        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(self, proofs, instances)
+        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
         st = (ctypes.c_int * max(n, 1))()
         if all(l == shapes[0] for l in shapes):
-            lens = shapes[0] if shapes else [0] * ncols
-            cl = (ctypes.c_size_t * max(ncols, 1))(*lens)
-            check(self._lib.h2v_verify_each(self._h, n, pa, pl, ia, ncols, cl, st))
+            check(self._lib.h2v_verify_each(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), st))
             return list(st)[:n]
         # SingleStrategy proofs are independent: run every instance shape as its own call and put the statuses back in order
         out = [0] * n
@@ -321,7 +332,7 @@ class Context:
 
     def guard_msm(self, proof, instances, cap=4096):
         f, lens = _flatten_instances(instances)
-        cl = (ctypes.c_size_t * max(len(lens), 1))(*lens)
+        cl = _sizes(lens)
         rs, rb = ctypes.create_string_buffer(32 * cap), ctypes.create_string_buffer(64 * cap)
         ls, lb = ctypes.create_string_buffer(32 * 64), ctypes.create_string_buffer(64 * 64)
         ch = ctypes.create_string_buffer(32 * 64)
@@ -441,41 +452,15 @@ def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None):
     if not contexts:
         raise ValueError("at least one context")
     lib = _lib.load_library()
-    for p in proofs:
-        if not isinstance(p, (bytes, bytearray)):
-            raise TypeError("proofs must be bytes")
-    for k in key_of_proof:
-        if not 0 <= int(k) < len(contexts):
-            raise ValueError(f"key index {k} out of range for {len(contexts)} contexts")
-    flats, shapes = [], []
-    for inst in instances:
-        f, l = _flatten_instances(inst)
-        flats.append(f)
-        shapes.append(l)
-    ncols = [None] * len(contexts)
-    for k, l in zip(key_of_proof, shapes):
-        if ncols[k] is None:
-            ncols[k] = len(l)
-        elif ncols[k] != len(l):
-            raise ValueError("all proofs of one key must have the same number of instance columns")
-    ncols = [c.proof_shape()["n_instance_columns"] if v is None else v for c, v in zip(contexts, ncols)]
-    rb = None
-    if rand is not None:
-        if len(rand) != n:
-            raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
-        rb = b"".join(_scalar32(r) for r in rand)
-    PA = ctypes.c_char_p * max(n, 1)
-    pa = PA(*[bytes(p) for p in proofs]) if n else PA()
-    pl = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in proofs])
-    ia = PA(*flats) if n else PA()
+    n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
+    rb = _rand_bytes(rand, n)
     ka = (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])
     ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
-    nca = (ctypes.c_size_t * len(contexts))(*ncols)
-    cl = (ctypes.c_size_t * max(sum(len(l) for l in shapes), 1))(*[v for l in shapes for v in l])
     st = (ctypes.c_int * max(n, 1))()
     ok = ctypes.c_int(0)
     left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
-    check(lib.h2v_verify_batch_keys(ca, len(contexts), ka, n, pa, pl, ia, nca, cl, rb, st, ctypes.byref(ok), left, right))
+    check(lib.h2v_verify_batch_keys(ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok),
+                                    left, right))
     return bool(ok.value), list(st)[:n], left.raw, right.raw
 
 

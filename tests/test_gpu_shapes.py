@@ -138,3 +138,21 @@ def test_many_instance_shapes_go_through_a_bounded_plan_cache():
     assert e.value.code == -19
     ctx.close()
     s.free()
+
+
+def test_no_proofs_have_no_column_lengths():
+    """h2v_verify_batch_shapes without proofs has no column lengths to plan for: refused as h2v_verify_batch refuses absent col_lens,
+    after the column-count check.  (h2v_verify_batch_keys without proofs runs the empty batch over empty columns: test_gpu_multi_key.)"""
+    import ctypes
+    from halo2_verifier_amd import _lib
+    s = circuits.setup_vector_mul(8, 8)
+    ctx = _ctx(s)
+    lib = _lib.load_library()
+    ncols = ctx.proof_shape()["n_instance_columns"]
+    assert ncols > 0
+    st, ok = (ctypes.c_int * 1)(), ctypes.c_int(7)
+    assert lib.h2v_verify_batch_shapes(ctx._h, 0, None, None, None, ncols, None, None, st, ctypes.byref(ok), None, None) == -16       # BAD_ARGUMENT
+    assert lib.h2v_verify_batch_shapes(ctx._h, 0, None, None, None, ncols + 1, None, None, st, ctypes.byref(ok), None, None) == -1    # INVALID_INSTANCES
+    assert ok.value == 7   # nothing was written
+    ctx.close()
+    s.free()
