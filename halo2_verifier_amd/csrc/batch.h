@@ -85,16 +85,25 @@ int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, u
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
 int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal);
-// the same over R arbitrary ranges of proofs (h2v_batch_recheck): d_ranges[2 r] = first, [2 r + 1] = count (first + count <= n);
-// d_out[(r * n_shared + j) * 8] = canonical( sum over the proofs p of range r of shared[j][p] )
-int fold_shared_ranges_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t n_shared, const uint32_t* d_ranges, uint32_t n_ranges, uint32_t* d_out);
+// One range of a re-check (k_fold_ranges): proofs [first, first + count) of a batch whose VK-wide scalars are shared[j][p] (j <
+// n_shared, p < n); its n_shared folded scalars go to rows [out, out + n_shared) of the output.  Ranges of one launch may belong to
+// different batches (h2v_batches_recheck), so each carries its own batch's pointer and sizes.
+struct FoldRange {
+    const Fr* shared;
+    uint32_t n, n_shared;
+    uint32_t first, count;
+    uint32_t out, pad;
+};
+// the same fold as fold_shared_enqueue over R ranges: d_out[(d_ranges[r].out + j) * 8] = canonical( sum over the proofs p of range r of
+// its shared[j][p] ); max_shared >= every range's n_shared
+int fold_shared_ranges_enqueue(hipStream_t s, const FoldRange* d_ranges, uint32_t n_ranges, uint32_t max_shared, uint32_t* d_out);
 
-// The re-check of ranges of a finished launch (h2v_batch_recheck): resources of its own, grow-only, so that the launch's accumulators,
-// workspace and result block are never touched
+// The re-check of ranges of finished launches (h2v_batch_recheck, h2v_batches_recheck, on the first batch's): resources of its own,
+// grow-only, so that the launches' accumulators, workspaces and result blocks are never touched
 struct Recheck {
     MsmWorkspace ws;
-    DevBuf<uint32_t> ranges;      // [range][first, count]
-    DevBuf<uint32_t> fold;        // [range][shared base][8]
+    DevBuf<FoldRange> ranges;     // [range]
+    DevBuf<uint32_t> fold;        // [range's rows][8]: the ranges' folded VK-wide scalars, one after another
     DevBuf<G1J> acc;              // [2 r] left, [2 r + 1] right
     DevBuf<uint32_t> ok;          // [range]
     DevBuf<uint8_t> out_bytes; DevBuf<uint32_t> out_ident;     // [range][128]; [2 range]
@@ -128,6 +137,11 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
                 const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false);
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
 bool pairing_passed(const h2v_batch* b, uint32_t g);
+// what the accumulation and its pairing read from the params (shplonk.rs's -g term, msm.rs:185-203); k may differ
+bool same_srs(const ParamsHost& a, const ParamsHost& b);
+// h2v_batches_recheck (h2v_batch_recheck: one batch, batch_of_range NULL); `who` names the entry point in the error messages
+int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range, const size_t* first,
+                 const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right);
 int export_whole_records(h2v_batch* b, void* device_dst);
 }  // namespace h2v
 

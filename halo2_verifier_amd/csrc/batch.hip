@@ -476,62 +476,92 @@ bool pairing_passed(const h2v_batch* b, uint32_t g) {
     return b->last.pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
 }
 
-}  // namespace h2v
+bool same_srs(const ParamsHost& a, const ParamsHost& b) {
+    auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
+    return !memcmp(&a.g, &b.g, sizeof(G1A)) && same_g2(a.g2, b.g2) && same_g2(a.s_g2, b.s_g2);
+}
 
-extern "C" {
-
-// Range re-checks (h2v_batch_recheck).  A range [first, first + count) of group g is checked as the launch checks the whole group:
-// e(sum_p m_p L_p, s_g2) e(sum_p m_p R_p, -g2) = 1 over its proofs' resident scalars (already multiplied by m_p, zeroed for failed
-// proofs) — the range's own fold of the VK-wide scalars, two MSMs, one pairing.  Nothing before the MSM runs again, and nothing the
-// launch left (ws, acc, split, the result block) is touched: the re-check has its own workspace and outputs (b->recheck).
-// At most MSM_MAX_PROBLEMS / 2 ranges, and about the launch's own term count, go into one set of launches.
-int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
+// Range re-checks (h2v_batch_recheck, h2v_batches_recheck).  A range [first, first + count) of group g of a batch is checked as the
+// launch checks the whole group: e(sum_p m_p L_p, s_g2) e(sum_p m_p R_p, -g2) = 1 over its proofs' resident scalars (already multiplied
+// by m_p, zeroed for failed proofs) — the range's own fold of the VK-wide scalars, two MSMs, one pairing.  Nothing before the MSM runs
+// again, and nothing the launches left (ws, acc, split, the result block) is touched: the re-check has its own workspace and outputs, the
+// first batch's (batches[0]->recheck), and runs on that batch's stream.  The ranges of one set of launches may belong to different batches
+// over the same SRS: the fold, the MSM problems and the pairing take addresses and sizes range by range, and one batch's pairing tables
+// serve them all.  At most MSM_MAX_PROBLEMS / 2 ranges, and about the largest launch's own term count, go into one set of launches.
+int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range, const size_t* first,
+                 const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
+    const std::string w(who);
     int rc;
-    if ((rc = require_stage(b, BatchStage::Finished, "h2v_batch_recheck"))) return rc;
-    if (n_ranges && (!first || !count || !range_ok)) { set_last_error("h2v_batch_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    const Plan& pl = b->plan->host;
-    const uint32_t n = b->n, G = b->groups, gs = n / G, np = pl.n_points, ns = pl.n_shared;
+    // every argument check comes before the first HIP call and the first output
+    if (!batches || !n_batches) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t k = 0; k < n_batches; ++k) {
+        if ((rc = require_stage(batches[k], BatchStage::Finished, who))) return rc;
+        if (batches[k]->ctx->device != batches[0]->ctx->device) { set_last_error(w + ": batches on different devices"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!same_srs(batches[k]->ctx->params, batches[0]->ctx->params)) { set_last_error(w + ": batches over different params (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    if (n_ranges && (!first || !count || !range_ok)) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    auto batch_of = [&](size_t i) -> h2v_batch* { return batches[batch_of_range ? batch_of_range[i] : 0]; };
     for (size_t i = 0; i < n_ranges; ++i) {
+        if (batch_of_range && batch_of_range[i] >= n_batches) { set_last_error(w + ": batch index out of range"); return H2V_ERR_BAD_ARGUMENT; }
+        const h2v_batch* b = batch_of(i);
+        const size_t n = b->n, gs = n / b->groups;
         const size_t f = first[i], c = count[i];
-        if (!c || f >= n || c > n - f) { set_last_error("h2v_batch_recheck: empty range, or a range past the launch's proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!c || f >= n || c > n - f) { set_last_error(w + ": empty range, or a range past the launch's proofs"); return H2V_ERR_BAD_ARGUMENT; }
         const size_t g = f / gs;
         // multipliers are products of the later draws of the proof's OWN group: the last proof of every group has multiplier 1, and a range
         // over two groups could hold two proofs with equal multipliers whose errors cancel
-        if ((f + c - 1) / gs != g) { set_last_error("h2v_batch_recheck: a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
-        if (f - g * gs < b->zero_below[g]) { set_last_error("h2v_batch_recheck: a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
+        if ((f + c - 1) / gs != g) { set_last_error(w + ": a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
+        if (f - g * gs < b->zero_below[g]) { set_last_error(w + ": a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
     }
     if (!n_ranges) return 0;
-    h2v_ctx* ctx = b->ctx;
+    h2v_batch* host = batches[0];
+    h2v_ctx* ctx = host->ctx;
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    if ((rc = join_tail(b))) return rc;
-    hipStream_t s = b->stream;
-    Recheck& rk = b->recheck;
+    // the re-check runs on the first batch's stream behind what its last launch left; every other batch's streams are idle before it reads
+    // their buffers (a finished batch's normally are: only a fold after the finish leaves work behind)
+    if ((rc = join_tail(host))) return rc;
+    for (size_t k = 1; k < n_batches; ++k)
+        if (batches[k] != host) { H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->stream)); H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->aux)); }
+    hipStream_t s = host->stream;
+    Recheck& rk = host->recheck;
     const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;
-    if ((rc = rk.ranges.reserve(2 * (size_t)max_ranges)) || (rc = rk.acc.reserve(2 * (size_t)max_ranges)) || (rc = rk.ok.reserve(max_ranges)) ||
-        (rc = rk.out_bytes.reserve(128 * (size_t)max_ranges)) || (rc = rk.out_ident.reserve(2 * (size_t)max_ranges)) || (rc = rk.fold.reserve(8 * (size_t)ns * max_ranges))) return rc;
-    const bool strided = pl.left_term_order.size() == 1 && !pl.left_term_order[0].first;
-    auto terms_of = [&](size_t c) { return (strided ? c : c * np) + c * np + ns; };
-    const size_t budget = 2 * ((size_t)n * np + (size_t)max_ranges * ns);   // > terms_of(n): every range fits in a chunk of its own
-    std::vector<uint32_t> desc;
+    // the plan facts of every range's batch, and the term budget of a set: about the largest launch's own
+    auto plan_of = [&](size_t i) -> const Plan& { return batch_of(i)->plan->host; };
+    auto strided = [](const Plan& pl) { return pl.left_term_order.size() == 1 && !pl.left_term_order[0].first; };
+    auto terms_of = [&](size_t i) { const Plan& pl = plan_of(i); const size_t c = count[i], np = pl.n_points; return (strided(pl) ? c : c * np) + c * np + pl.n_shared; };
+    size_t budget = 0;   // > terms_of(every range): every range fits in a set of its own
+    for (size_t k = 0; k < n_batches; ++k) { const Plan& pl = batches[k]->plan->host; budget = std::max(budget, 2 * ((size_t)batches[k]->n * pl.n_points + (size_t)max_ranges * pl.n_shared)); }
+    if ((rc = rk.ranges.reserve(max_ranges)) || (rc = rk.acc.reserve(2 * (size_t)max_ranges)) || (rc = rk.ok.reserve(max_ranges)) ||
+        (rc = rk.out_bytes.reserve(128 * (size_t)max_ranges)) || (rc = rk.out_ident.reserve(2 * (size_t)max_ranges))) return rc;
+    std::vector<FoldRange> desc;
     std::vector<uint32_t> okv;
     std::vector<uint8_t> outb;
     for (size_t i0 = 0; i0 < n_ranges;) {
         size_t i1 = i0, total = 0;
-        uint32_t per = 0;
-        while (i1 < n_ranges && i1 - i0 < max_ranges && (i1 == i0 || total + terms_of(count[i1]) <= budget)) {
-            total += terms_of(count[i1]);
-            per = std::max(per, (uint32_t)(count[i1] * np + ns));
+        uint32_t per = 0, rows = 0, max_shared = 0;
+        while (i1 < n_ranges && i1 - i0 < max_ranges && (i1 == i0 || total + terms_of(i1) <= budget)) {
+            const Plan& pl = plan_of(i1);
+            total += terms_of(i1);
+            per = std::max(per, (uint32_t)(count[i1] * pl.n_points + pl.n_shared));
+            rows += pl.n_shared; max_shared = std::max(max_shared, pl.n_shared);
             ++i1;
         }
         const uint32_t R = (uint32_t)(i1 - i0);
-        if (!rk.ws.covers((uint32_t)total, 2 * R, per)) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (an earlier chunk may still use the workspace)
-        if ((rc = rk.ws.reserve((uint32_t)total, 2 * R, per))) return rc;
-        desc.resize(2 * (size_t)R);
-        for (uint32_t r = 0; r < R; ++r) { desc[2 * r] = (uint32_t)first[i0 + r]; desc[2 * r + 1] = (uint32_t)count[i0 + r]; }
-        H2V_HIP_CHECK(hipMemcpyAsync(rk.ranges.p, desc.data(), 8 * (size_t)R, hipMemcpyHostToDevice, s));
-        if ((rc = fold_shared_ranges_enqueue(s, b->shared.p, n, ns, rk.ranges.p, R, rk.fold.p))) return rc;
+        const bool grow = !rk.ws.covers((uint32_t)total, 2 * R, per) || rk.fold.cap < 8 * (size_t)rows;
+        if (grow) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (an earlier set may still use the workspace)
+        if ((rc = rk.ws.reserve((uint32_t)total, 2 * R, per)) || (rc = rk.fold.reserve(8 * (size_t)std::max(rows, 1u)))) return rc;
+        desc.resize(R);
+        for (uint32_t r = 0, row = 0; r < R; ++r) {
+            const h2v_batch* b = batch_of(i0 + r);
+            const uint32_t ns = b->plan->host.n_shared;
+            desc[r] = FoldRange{b->shared.p, b->n, ns, (uint32_t)first[i0 + r], (uint32_t)count[i0 + r], row, 0};
+            row += ns;
+        }
+        H2V_HIP_CHECK(hipMemcpyAsync(rk.ranges.p, desc.data(), sizeof(FoldRange) * R, hipMemcpyHostToDevice, s));
+        if ((rc = fold_shared_ranges_enqueue(s, rk.ranges.p, R, max_shared, rk.fold.p))) return rc;
         MsmProblems pr;
-        for (uint32_t r = 0; r < R; ++r) channel_problems(pr, b, pl, first[i0 + r], (uint32_t)count[i0 + r], rk.acc.p + 2 * r, rk.fold.p + (size_t)r * ns * 8, ns);
+        for (uint32_t r = 0; r < R; ++r)
+            channel_problems(pr, batch_of(i0 + r), plan_of(i0 + r), first[i0 + r], (uint32_t)count[i0 + r], rk.acc.p + 2 * r, rk.fold.p + (size_t)desc[r].out * 8, desc[r].n_shared);
         rk.ws.tune = ctx->tuning; rk.ws.profile = false;
         if ((rc = msm_enqueue_multi(s, rk.ws, pr))) return rc;
         if ((rc = pairing_check_enqueue(s, ctx->pairing, rk.acc.p, R, rk.ok.p))) return rc;
@@ -543,7 +573,7 @@ int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const 
             H2V_HIP_CHECK(hipMemcpyAsync(outb.data(), rk.out_bytes.p, outb.size(), hipMemcpyDeviceToHost, s));
         }
         const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_last_error(std::string("h2v_batch_recheck: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+        if (e != hipSuccess) { set_last_error(w + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
         for (uint32_t r = 0; r < R; ++r) {
             range_ok[i0 + r] = okv[r] ? 1 : 0;
             if (out_left) memcpy(out_left + 64 * (i0 + r), &outb[128 * (size_t)r], 64);
@@ -552,6 +582,21 @@ int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const 
         i0 = i1;
     }
     return 0;
+}
+
+}  // namespace h2v
+
+extern "C" {
+
+int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right) {
+    if (!b) return require_stage(b, BatchStage::Finished, "h2v_batch_recheck");
+    return recheck_impl("h2v_batch_recheck", &b, 1, n_ranges, nullptr, first, count, range_ok, out_left, out_right);
+}
+
+int h2v_batches_recheck(h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range, const size_t* first, const size_t* count,
+                        int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+    if (!batches || (n_ranges && !batch_of_range)) { set_last_error("h2v_batches_recheck: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    return recheck_impl("h2v_batches_recheck", batches, n_batches, n_ranges, batch_of_range, first, count, range_ok, out_left_xy, out_right_xy);
 }
 
 int h2v_random_scalars(uint8_t* out32, size_t n) {

@@ -1,4 +1,4 @@
-// C-ABI one-shot verification entry points (include/h2v.h): h2v_verify_batch and its _seeded / _shapes / _keys / _identify forms,
+// C-ABI one-shot verification entry points (include/h2v.h): h2v_verify_batch and its _seeded / _shapes / _keys / _identify / _keys_identify forms,
 // h2v_verify_each, h2v_guard_msm and h2v_fold_check.  Each call runs on its context's scratch batch through the staged batch of batch.hip.
 #include "../../include/h2v.h"
 #include "batch.h"
@@ -68,24 +68,25 @@ std::vector<uint8_t> unit_draws(size_t n) {
     return d;
 }
 
-// Packed proofs on the scratch batch, first half: proofs [off, off + m) of `sb` as `groups` groups, uploaded with the draws rand32 (null: OS
-// draws) and launched with or without the pairing checks, the multipliers gathered from mult[idx[..]] if mult is given.  Nothing waits.
-int enqueue_group(const ScratchBatch& sb, size_t off, size_t m, size_t groups, const uint8_t* rand32, int with_pairing, bool guard = false,
+// Packed proofs on a batch (the scratch batch, or one the call made for itself), first half: proofs [off, off + m) of `sb` as `groups`
+// groups on b, uploaded with the draws rand32 (null: OS draws) and launched with or without the pairing checks, the multipliers gathered
+// from mult[idx[..]] if mult is given.  Nothing waits.
+int enqueue_group(const ScratchBatch& sb, h2v_batch* b, size_t off, size_t m, size_t groups, const uint8_t* rand32, int with_pairing, bool guard = false,
                   const Fr* mult = nullptr, const uint32_t* idx = nullptr) {
     const Plan& pl = sb.pin.pd->host;
     int rc;
-    if ((rc = h2v_batch_set_groups(sb.b, groups)) ||
-        (rc = upload_impl(sb.b, m, sb.flat.data() + off * pl.proof_len, pl.proof_len, sb.iflat.data() + off * (size_t)pl.n_instance_values * 32, sb.cols.size(), sb.cols.data(),
+    if ((rc = h2v_batch_set_groups(b, groups)) ||
+        (rc = upload_impl(b, m, sb.flat.data() + off * pl.proof_len, pl.proof_len, sb.iflat.data() + off * (size_t)pl.n_instance_values * 32, sb.cols.size(), sb.cols.data(),
                           rand32, m, false, guard))) return rc;
-    return launch_impl(sb.b, with_pairing, mult, idx);
+    return launch_impl(b, with_pairing, mult, idx);
 }
 
-// Second half: the statuses of the launch of proofs [off, ..) into st and its group verdicts into group_ok (either may be null), with the
-// statuses pack_inputs forced in place of the device's and the groups that hold such a proof failed
-int collect_group(const ScratchBatch& sb, size_t off, int* st, int* group_ok, uint8_t* out_left = nullptr, uint8_t* out_right = nullptr) {
-    if (int rc = h2v_batch_finish_groups(sb.b, st, group_ok, out_left, out_right, sb.b->groups)) return rc;
-    for (uint32_t i = 0; i < sb.b->n; ++i)
-        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[i / (sb.b->n / sb.b->groups)] = 0; }
+// Second half: the statuses of b's launch of proofs [off, ..) of `sb` into st and its group verdicts into group_ok (either may be null),
+// with the statuses pack_inputs forced in place of the device's and the groups that hold such a proof failed
+int collect_group(const ScratchBatch& sb, h2v_batch* b, size_t off, int* st, int* group_ok, uint8_t* out_left = nullptr, uint8_t* out_right = nullptr) {
+    if (int rc = h2v_batch_finish_groups(b, st, group_ok, out_left, out_right, b->groups)) return rc;
+    for (uint32_t i = 0; i < b->n; ++i)
+        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[i / (b->n / b->groups)] = 0; }
     return 0;
 }
 
@@ -95,62 +96,76 @@ int pack_and_run(ScratchBatch& sb, size_t n, const uint8_t* const* proofs, const
                  uint8_t* out_right) {
     int rc;
     if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, ncols, col_lens)) || (rc = sb.take(n ? n : 1, sb.pin.pd->host.n_instance_values)) ||
-        (rc = enqueue_group(sb, 0, n, 1, rand32, with_pairing, guard))) return rc;
-    return collect_group(sb, 0, per_proof_status, batch_ok, out_left, out_right);
+        (rc = enqueue_group(sb, sb.b, 0, n, 1, rand32, with_pairing, guard))) return rc;
+    return collect_group(sb, sb.b, 0, per_proof_status, batch_ok, out_left, out_right);
 }
 
 // The search of h2v_verify_batch_identify, measured at 1024 proofs (tools/identify_probe.py): every failing range is cut into
 // H2V_IDENTIFY_FANOUT pieces per round — or straight into single proofs once the failing ranges hold at most H2V_IDENTIFY_DIRECT
 // proofs together, one set of re-check launches (MSM_MAX_PROBLEMS / 2 checks).  A round is a latency chain up to ~128 checks (32 ranges
 // of 32 proofs: 1.9 ms, 128 single proofs: 2.0 ms, 512: 4.1 ms), so rounds are what to save: one bad proof in 1024 takes two (32 + 32 checks).
+// Over several batches (h2v_verify_batch_keys_identify) a round starts from one failing range per group, up to 64 of them: the fanout
+// shrinks as the failing ranges grow in number, so that a round stays within H2V_IDENTIFY_ROUND checks — one set of launches, whose cost
+// grows far less than its width (see above) — while a round of one or a few failing ranges keeps the full fanout.
 #define H2V_IDENTIFY_FANOUT 32
 #define H2V_IDENTIFY_DIRECT 512
+#define H2V_IDENTIFY_ROUND (MSM_MAX_PROBLEMS / 2)
 
-// the pairing's verdict of a failed batch of one group, proof by proof: st[i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof whose own
-// check fails (st[i] == 0 on entry).  A range whose check fails holds at least one failing proof (the check of a range is the product of its
-// pieces' checks), so every round ends with at least one failing piece per failing range.
-int identify_search(h2v_batch* b, std::vector<int>& st, size_t* n_checks) {
-    const size_t n = st.size();
+// the pairing's verdict of failed batches of one group each, proof by proof: st[k][i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof
+// i of batch bs[k] whose own check fails (st[k][i] == 0 on entry).  A range whose check fails holds at least one failing proof (the check
+// of a range is the product of its pieces' checks), so every round ends with at least one failing piece per failing range.  Every round is
+// ONE re-check over the pieces of all batches (recheck_impl).  With one batch the policy is the one measured above, and its whole range is
+// known to fail (its own pairing did).  Over several batches only the fold of all of them is known to fail: the first round checks every
+// batch's range, a one-proof range included, before anything is flagged.
+int identify_search(const std::vector<h2v_batch*>& bs, std::vector<std::vector<int>>& st, size_t* n_checks) {
+    struct Item { uint32_t b; size_t first, count; };
     // proofs with a non-zero status contribute nothing: a range is trimmed to its first and last live proof, and one without a live proof passes
-    auto trim = [&](size_t a, size_t c, std::vector<std::pair<size_t, size_t>>& out) {
+    auto trim = [&](uint32_t k, size_t a, size_t c, std::vector<Item>& out) {
+        const std::vector<int>& sk = st[k];
         size_t e = a + c;
-        while (a < e && st[a]) ++a;
-        while (e > a && st[e - 1]) --e;
-        if (e > a) out.push_back({a, e - a});
+        while (a < e && sk[a]) ++a;
+        while (e > a && sk[e - 1]) --e;
+        if (e > a) out.push_back({k, a, e - a});
     };
-    std::vector<std::pair<size_t, size_t>> failing, pieces;
-    trim(0, n, failing);
+    std::vector<Item> failing, pieces;
+    for (uint32_t k = 0; k < bs.size(); ++k) trim(k, 0, st[k].size(), failing);
+    const bool pooled = bs.size() > 1;
+    bool known = !pooled;   // every range in `failing` has failed a check of its own
     int rc = 0;
     while (!failing.empty()) {
         pieces.clear();
         size_t total = 0;
-        for (auto& r : failing) total += r.second;
+        for (auto& r : failing) total += r.count;
+        const size_t fanout = pooled ? std::min<size_t>(H2V_IDENTIFY_FANOUT, std::max<size_t>(2, H2V_IDENTIFY_ROUND / failing.size())) : H2V_IDENTIFY_FANOUT;
         for (auto& r : failing) {
-            if (r.second == 1) { st[r.first] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE; continue; }   // (its check already was that proof's own)
-            const size_t k = total <= H2V_IDENTIFY_DIRECT ? r.second : std::min<size_t>(H2V_IDENTIFY_FANOUT, r.second);
+            if (r.count == 1 && known) { st[r.b][r.first] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE; continue; }   // (its check already was that proof's own)
+            const size_t k = total <= H2V_IDENTIFY_DIRECT ? r.count : std::min<size_t>(fanout, r.count);
             for (size_t i = 0; i < k; ++i) {
-                const size_t a = r.first + r.second * i / k, e = r.first + r.second * (i + 1) / k;
-                trim(a, e - a, pieces);
+                const size_t a = r.first + r.count * i / k, e = r.first + r.count * (i + 1) / k;
+                trim(r.b, a, e - a, pieces);
             }
         }
         if (pieces.empty()) break;
+        std::vector<uint32_t> bor(pieces.size());
         std::vector<size_t> f(pieces.size()), c(pieces.size());
         std::vector<int> ok(pieces.size(), 0);
-        for (size_t i = 0; i < pieces.size(); ++i) { f[i] = pieces[i].first; c[i] = pieces[i].second; }
-        if ((rc = h2v_batch_recheck(b, pieces.size(), f.data(), c.data(), ok.data(), nullptr, nullptr))) return rc;
+        for (size_t i = 0; i < pieces.size(); ++i) { bor[i] = pieces[i].b; f[i] = pieces[i].first; c[i] = pieces[i].count; }
+        if ((rc = recheck_impl("identification", bs.data(), bs.size(), pieces.size(), bor.data(), f.data(), c.data(), ok.data(), nullptr, nullptr))) return rc;
         *n_checks += pieces.size();
+        known = true;
         failing.clear();
         for (size_t i = 0; i < pieces.size(); ++i) {
             if (ok[i]) continue;
-            if (c[i] == 1) st[f[i]] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;
+            if (c[i] == 1) st[bor[i]][f[i]] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;
             else failing.push_back(pieces[i]);
         }
     }
     return 0;
 }
 
-// (the caller holds ctx->mu)
-int fold_check_locked(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts, int* ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+// (the caller holds ctx->mu)  pairing_ok (may be null): the pairing's own verdict, before the records' failure counts are folded into `ok`
+int fold_check_locked(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts, int* ok, uint8_t* out_left_xy, uint8_t* out_right_xy,
+                      int* pairing_ok = nullptr) {
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     DevBuf<G1J> acc; DevBuf<uint32_t> d_ok, d_ident, d_failed; DevBuf<uint8_t> d_out;   // freed on every return path
@@ -165,6 +180,7 @@ int fold_check_locked(h2v_ctx* ctx, const void* device_accumulators, size_t n_pa
     H2V_HIP_CHECK(hipMemcpyAsync(outb, d_out.p, 128, hipMemcpyDeviceToHost, s));
     H2V_HIP_CHECK(hipStreamSynchronize(s));
     *ok = (okv && !failed) ? 1 : 0;
+    if (pairing_ok) *pairing_ok = okv ? 1 : 0;
     if (out_left_xy) memcpy(out_left_xy, outb, 64);
     if (out_right_xy) memcpy(out_right_xy, outb + 64, 64);
     return 0;
@@ -216,8 +232,12 @@ int group_proofs(const char* who, size_t n, size_t n_keys, const uint32_t* key_o
 // export_whole_records) folded into ONE pairing on the first group's context.  rand32: the n draws in call order (resolved).
 // Keys do not wait for each other on the host: each round enqueues one group of every key (upload, launch without a pairing, record
 // export on that key's batch stream), then finishes them; groups of one key run one after another on its batch.
+// n_checks (identification, h2v_verify_batch_keys_identify): every group stays resident — a key's first group on its scratch batch, its
+// later groups on batches made for the call (destroyed at its end) — and when the folded pairing itself fails, the failing proofs are
+// searched for over all groups at once (identify_search); the number of range checks it ran is ADDED to *n_checks.
 int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
-               const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+               const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy,
+               size_t* n_checks = nullptr) {
     // every context's lock and scratch batch for the whole call, taken in one global order (by address): calls over overlapping sets of
     // contexts cannot deadlock
     std::vector<size_t> order(n_keys);
@@ -253,13 +273,30 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         for (size_t gi : kv.second) { max_group = std::max(max_group, groups[gi].idx.size()); size_t t = 0; for (size_t l : groups[gi].shape) t += l; max_inst = std::max(max_inst, t); }
         if ((rc = hold[kv.first]->take(max_group, max_inst))) return rc;
     }
+    // the batch of every group: its key's scratch batch, or (identification, a key's later groups) a batch of its own for the call
+    struct Destroy { void operator()(h2v_batch* b) const { h2v_batch_destroy(b); } };
+    std::vector<std::unique_ptr<h2v_batch, Destroy>> own;
+    std::vector<h2v_batch*> on(groups.size());
+    for (auto& kv : of_key)
+        for (size_t r = 0; r < kv.second.size(); ++r) {
+            const size_t gi = kv.second[r];
+            on[gi] = hold[kv.first]->b;
+            if (!n_checks || r == 0) continue;
+            size_t inst = 0;
+            for (size_t l : groups[gi].shape) inst += l;
+            h2v_batch* b = nullptr;
+            if ((rc = h2v_batch_create(ctxs[kv.first], groups[gi].idx.size(), inst, &b))) return rc;
+            own.emplace_back(b);
+            on[gi] = b;
+        }
     // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
     struct Drain {
         std::vector<h2v_batch*> bs;
         ~Drain() { for (h2v_batch* b : bs) { hipStreamSynchronize(b->stream); hipStreamSynchronize(b->aux); } }
     } drain;
-    for (auto& kv : of_key) drain.bs.push_back(hold[kv.first]->b);
+    drain.bs = on;
     bool all_ok = true;
+    std::vector<std::vector<int>> st(groups.size());
     for (size_t r = 0; r < rounds; ++r) {
         for (auto& kv : of_key) {
             if (r >= kv.second.size()) continue;
@@ -268,37 +305,35 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
             ScratchBatch& sb = *hold[kv.first];
             const size_t m = grp.idx.size();
             if ((rc = pack_inputs(sb, m, grp.idx.data(), proofs, proof_lens, instances32, grp.shape.size(), grp.shape.data())) ||
-                (rc = enqueue_group(sb, 0, m, 1, unit_draws(m).data(), 0, false, d_mult.p, d_idx.p + idx_off[gi])) ||
-                (rc = export_whole_records(sb.b, d_records.p + gi * H2V_ACC_RECORD_BYTES))) return rc;
+                (rc = enqueue_group(sb, on[gi], 0, m, 1, unit_draws(m).data(), 0, false, d_mult.p, d_idx.p + idx_off[gi])) ||
+                (rc = export_whole_records(on[gi], d_records.p + gi * H2V_ACC_RECORD_BYTES))) return rc;
         }
         for (auto& kv : of_key) {
             if (r >= kv.second.size()) continue;
             const size_t gi = kv.second[r];
-            const std::vector<size_t>& idx = groups[gi].idx;
-            std::vector<int> st(idx.size(), 0); int gok = 0;
-            if ((rc = collect_group(*hold[kv.first], 0, st.data(), &gok))) return rc;
-            if (per_proof_status) for (size_t j = 0; j < idx.size(); ++j) per_proof_status[idx[j]] = st[j];
+            st[gi].assign(groups[gi].idx.size(), 0); int gok = 0;
+            if ((rc = collect_group(*hold[kv.first], on[gi], 0, st[gi].data(), &gok))) return rc;
             all_ok = all_ok && gok;
         }
     }
     drain.bs.clear();   // (every group is finished)
-    int ok = 0;
-    if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy))) return rc;
+    int ok = 0, pairing_ok = 0;
+    if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy, &pairing_ok))) return rc;
+    // identification: only a failing pairing has failing proofs to find (a proof with a non-zero status contributes nothing to it)
+    if (n_checks && !pairing_ok && (rc = identify_search(on, st, n_checks))) return rc;
+    if (per_proof_status)
+        for (size_t gi = 0; gi < groups.size(); ++gi)
+            for (size_t j = 0; j < groups[gi].idx.size(); ++j) per_proof_status[groups[gi].idx[j]] = st[gi][j];
     if (batch_ok) *batch_ok = (ok && all_ok) ? 1 : 0;
     return 0;
 }
 
-// what the accumulation and its pairing read from the params (shplonk.rs's -g term, msm.rs:185-203); k may differ
-bool same_srs(const ParamsHost& a, const ParamsHost& b) {
-    auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
-    return !memcmp(&a.g, &b.g, sizeof(G1A)) && same_g2(a.g2, b.g2) && same_g2(a.s_g2, b.s_g2);
-}
-
 // h2v_verify_batch_keys, and h2v_verify_batch_shapes as its call with one context (key_of_proof NULL: every proof is of key 0).  `who`
-// names the entry point in the error messages.
+// names the entry point in the error messages.  n_checks (h2v_verify_batch_keys_identify): identification as well — the draws must be
+// non-zero, and the number of range checks is written there; one group is h2v_verify_batch_identify's case.
 int verify_grouped(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
                    const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
-                   int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy) {
+                   int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t* n_checks = nullptr) {
     const std::string w(who);
     // every argument check comes before the first HIP call
     if (!ctxs || !n_keys || !n_instance_columns || (n && (!proofs || !proof_lens))) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
@@ -314,10 +349,22 @@ int verify_grouped(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const u
     int rc;
     if ((rc = group_proofs(who, n, n_keys, key_of_proof, n_instance_columns, col_lens, proofs, instances32, groups))) return rc;
     if (groups.empty()) groups.push_back({0, std::vector<size_t>(n_instance_columns[0], 0), {}});   // (no proofs: ctxs[0] over empty columns)
+    std::vector<uint8_t> os_rand;
+    if (n_checks) {
+        // a single proof's check equals SingleStrategy's only when its multiplier is non-zero: no draw may be zero (refused before any device work)
+        if ((rc = resolve_draws(rand32, n, os_rand, who, true))) return rc;
+        size_t checks = 0;
+        if (groups.size() == 1) {
+            if ((rc = h2v_verify_batch_identify(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32,
+                                                per_proof_status, batch_ok, out_left_xy, out_right_xy, &checks))) return rc;
+        } else if ((rc = run_groups(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy, &checks)))
+            return rc;
+        *n_checks = checks;
+        return 0;
+    }
     if (groups.size() == 1)   // one key, one shape: the proofs are that group, in call order
         return h2v_verify_batch(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32,
                                 per_proof_status, batch_ok, out_left_xy, out_right_xy);
-    std::vector<uint8_t> os_rand;
     if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
     return run_groups(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
@@ -389,7 +436,7 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
     if ((rc = export_records_enqueue(s, d_jac.p, nullptr, 1, 0, nullptr, 0, 1, d_records.p + H2V_ACC_RECORD_BYTES))) return rc;   // record 1: the scaled seed
     if ((rc = h2v_batch_fold_check_enqueue(b, d_records.p, 2))) return rc;
     // (synchronises: the scoped buffers outlive their use)
-    return collect_group(sb, 0, nullptr, batch_ok, out_left_xy, out_right_xy);
+    return collect_group(sb, sb.b, 0, nullptr, batch_ok, out_left_xy, out_right_xy);
 }
 
 int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
@@ -409,6 +456,18 @@ int h2v_verify_batch_keys(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* k
                           per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
 
+int h2v_verify_batch_keys_identify(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                                   const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                                   const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64],
+                                   size_t* n_range_checks) {
+    if (n && !key_of_proof) { set_last_error("h2v_verify_batch_keys_identify: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    size_t checks = 0;
+    const int rc = verify_grouped("h2v_verify_batch_keys_identify", ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens,
+                                  rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy, &checks);
+    if (!rc && n_range_checks) *n_range_checks = checks;
+    return rc;
+}
+
 int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
                               const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64],
                               size_t* n_range_checks) {
@@ -418,13 +477,13 @@ int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proo
     std::vector<uint8_t> os_rand;
     int rc;
     if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_identify", true))) return rc;
-    std::vector<int> st(n, 0);
+    std::vector<std::vector<int>> st(1, std::vector<int>(n, 0));
     int ok = 0;
     ScratchBatch sb(ctx);
-    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, st.data(), &ok, out_left_xy, out_right_xy))) return rc;
+    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, st[0].data(), &ok, out_left_xy, out_right_xy))) return rc;
     size_t checks = 0;
-    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search(sb.b, st, &checks))) return rc;
-    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
+    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search({sb.b}, st, &checks))) return rc;
+    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[0][i];
     if (batch_ok) *batch_ok = ok;
     if (n_range_checks) *n_range_checks = checks;
     return 0;
@@ -443,7 +502,7 @@ int h2v_verify_each(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const 
     for (size_t off = 0; off < n; off += per) {
         const size_t m = std::min(per, n - off);
         std::vector<int> st(m, 0), gok(m, 0);
-        if ((rc = enqueue_group(sb, off, m, m, unit_draws(m).data(), 1)) || (rc = collect_group(sb, off, st.data(), gok.data()))) return rc;
+        if ((rc = enqueue_group(sb, sb.b, off, m, m, unit_draws(m).data(), 1)) || (rc = collect_group(sb, sb.b, off, st.data(), gok.data()))) return rc;
         for (size_t i = 0; i < m; ++i) {
             if (st[i] == 0 && !gok[i]) st[i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;  // kzg/strategy.rs:171-175
             if (per_proof_status) per_proof_status[off + i] = st[i];

@@ -9,7 +9,7 @@
 //   k_instance_eval   one workgroup per proof       Lagrange sum over a wide instance column   lib.rs:173-218, poly/domain.rs:187-212
 //   k_frvm            one lane per proof            the compiled Fr program            lib.rs:173-346, shplonk.rs:202-264
 //   k_fold_shared     one workgroup per shared base sum over proofs of the scalars of VK-wide bases
-//   k_fold_ranges     one wave per (shared base, range)   the same over arbitrary ranges of proofs (h2v_batch_recheck)
+//   k_fold_ranges     one wave per (shared base, range)   the same over arbitrary ranges of proofs, of one batch or several (h2v_batches_recheck)
 //
 // Layouts are chosen so that lanes (= proofs) are contiguous in the fastest dimension for
 // everything the per-proof kernels re-read: stream words [word][proof], challenges [c][proof],
@@ -632,14 +632,19 @@ __global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ shar
     }
 }
 
-// out[(r * n_shared + j) * 8] = canonical( sum over the proofs p of range r of shared[j][p] ).  The ranges of a re-check are mostly
-// short (a search ends on single proofs): one wave per (base, range), a wave-wide tree in LDS
-__global__ void __launch_bounds__(64) k_fold_ranges(const Fr* __restrict__ shared, uint32_t n, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ out) {
+// out[(ranges[r].out + j) * 8] = canonical( sum over the proofs p of range r of ranges[r].shared[j][p] ).  The ranges of a re-check
+// are mostly short (a search ends on single proofs): one wave per (base, range), a wave-wide tree in LDS.  The ranges of one launch
+// may belong to batches of different keys (h2v_batches_recheck): the grid is as wide as the most VK-wide bases of any of them, and the
+// blocks past a range's own n_shared leave at once (the whole block: the exit is uniform, before the first barrier)
+__global__ void __launch_bounds__(64) k_fold_ranges(const FoldRange* __restrict__ ranges, uint32_t* __restrict__ out) {
     __shared__ Fr red[64];
-    const uint32_t j = blockIdx.x, r = blockIdx.y, t = threadIdx.x;
-    const uint32_t first = ranges[2 * r], end = first + ranges[2 * r + 1];   // (validated on the host: end <= n)
+    const uint32_t j = blockIdx.x, t = threadIdx.x;
+    const FoldRange rg = ranges[blockIdx.y];
+    if (j >= rg.n_shared) return;
+    const Fr* col = rg.shared + (size_t)j * rg.n;
+    const uint32_t end = rg.first + rg.count;   // (validated on the host: end <= n)
     Fr acc = Fr::zero();
-    for (uint32_t p = first + t; p < end; p += 64) acc = acc + shared[(size_t)j * n + p];
+    for (uint32_t p = rg.first + t; p < end; p += 64) acc = acc + col[p];
     red[t] = acc;
     __syncthreads();
     for (uint32_t d = 32; d > 0; d >>= 1) {
@@ -648,7 +653,7 @@ __global__ void __launch_bounds__(64) k_fold_ranges(const Fr* __restrict__ share
     }
     if (t == 0) {
         uint32_t raw[8]; red[0].to_raw(raw);
-        uint32_t* dst = out + ((size_t)r * gridDim.x + j) * 8;
+        uint32_t* dst = out + ((size_t)rg.out + j) * 8;
         for (int i = 0; i < 8; ++i) dst[i] = raw[i];
     }
 }
@@ -766,9 +771,9 @@ int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t 
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int fold_shared_ranges_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t n_shared, const uint32_t* d_ranges, uint32_t n_ranges, uint32_t* d_out) {
-    if (!n_shared || !n_ranges) return 0;
-    hipLaunchKernelGGL(k_fold_ranges, dim3(n_shared, n_ranges), dim3(64), 0, s, d_shared, n, d_ranges, d_out);
+int fold_shared_ranges_enqueue(hipStream_t s, const FoldRange* d_ranges, uint32_t n_ranges, uint32_t max_shared, uint32_t* d_out) {
+    if (!max_shared || !n_ranges) return 0;
+    hipLaunchKernelGGL(k_fold_ranges, dim3(max_shared, n_ranges), dim3(64), 0, s, d_ranges, d_out);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -369,6 +369,35 @@ class AccumulatorStrategy(_Strategy):
         s.seed = (left, right)
         return s
 
+    def finalize_identify(self) -> bool:
+        """finalize() plus the proofs that made it fail (h2v_verify_batch_keys_identify), over one or several VerifyingKeys and any
+        instance shapes.  Returns what finalize() returns; afterwards `statuses` holds, proof by proof in accumulation order, what
+        SingleStrategy reports for it (ConstraintSystemFailure for the proofs whose own pairing fails), `left_xy` / `right_xy` the
+        evaluated channels and `last_range_checks` the number of range checks the search ran.  The draws must be non-zero."""
+        if self.seed is not None:
+            raise ValueError("identification takes an accumulation without a seed")
+        n = len(self._items)
+        rand = self.rand
+        if rand is not None and len(rand) != n:
+            raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
+        if not self._items:
+            self.statuses, self.last_range_checks = [], 0
+            return True
+        keys = {}
+        for vk, _, _ in self._items:
+            keys.setdefault((vk.data, int(vk.format)), vk)
+        index = {key: k for k, key in enumerate(keys)}
+        ctxs = []
+        try:
+            for vk in keys.values():
+                ctxs.append(Context(self.params, vk, self.device, circuit_instances=self.circuit_instances))
+            ok, self.statuses, self.left_xy, self.right_xy, self.last_range_checks = verify_batch_keys_identify(
+                ctxs, [index[(vk.data, int(vk.format))] for vk, _, _ in self._items], [p for _, _, p in self._items], [i for _, i, _ in self._items], rand)
+            return ok
+        finally:
+            for c in ctxs:
+                c.close()
+
     def finalize(self) -> bool:
         """One pairing for everything that was accumulated.  verify_proof takes a VK per call and one strategy may accumulate
         proofs of DIFFERENT VKs over the same params (kzg/strategy.rs:125-140 only ever sees MSMs): proofs are grouped by VK,
@@ -462,6 +491,55 @@ def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None):
     check(lib.h2v_verify_batch_keys(ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok),
                                     left, right))
     return bool(ok.value), list(st)[:n], left.raw, right.raw
+
+
+def verify_batch_keys_identify(contexts, key_of_proof, proofs, instances, rand=None):
+    """verify_batch_keys plus the proofs that made it fail (h2v_verify_batch_keys_identify).  Same arguments as verify_batch_keys
+    (several keys, per-proof instance shapes); rand: n non-zero draws in call order, or None.  Returns (batch_ok, statuses, left_xy,
+    right_xy, range_checks): batch_ok / left_xy / right_xy are what verify_batch_keys returns for the same arguments, statuses[i] is what
+    contexts[key_of_proof[i]].verify_each returns for proof i, range_checks the number of range checks the search ran."""
+    contexts = list(contexts)
+    n = len(proofs)
+    if len(key_of_proof) != n or len(instances) != n:
+        raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {len(key_of_proof)} and {len(instances)}")
+    if not contexts:
+        raise ValueError("at least one context")
+    lib = _lib.load_library()
+    n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
+    rb = _rand_bytes(rand, n)
+    ka = (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])
+    ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
+    st = (ctypes.c_int * max(n, 1))()
+    ok = ctypes.c_int(0)
+    left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+    checks = ctypes.c_size_t(0)
+    check(lib.h2v_verify_batch_keys_identify(ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok),
+                                             left, right, ctypes.byref(checks)))
+    return bool(ok.value), list(st)[:n], left.raw, right.raw, checks.value
+
+
+def recheck_batches(batches, ranges):
+    """Batch.recheck over ranges of several finished batches in one set of launches (h2v_batches_recheck).  batches: Batch objects on
+    one device over the same params (keys and shapes may differ); ranges: list of (batch_index, first, count), each inside one group of
+    that batch's last finished launch.  -> (oks, lefts, rights): one verdict and the two evaluated channels (64-byte x | y) per range."""
+    batches = list(batches)
+    if not batches:
+        raise ValueError("at least one batch")
+    ranges = [(int(b), int(f), int(c)) for b, f, c in ranges]
+    for b, f, c in ranges:   # (uint32 / size_t on the C side: a negative value would wrap around; the library checks the rest)
+        if b < 0 or f < 0 or c < 0:
+            raise ValueError(f"range ({b}, {f}, {c}): the batch index, first and count must be non-negative")
+    lib = batches[0]._lib
+    k = len(ranges)
+    ba = (ctypes.c_void_p * len(batches))(*[b._h.value for b in batches])
+    bor = (ctypes.c_uint32 * max(k, 1))(*[b for b, _, _ in ranges])
+    first = (ctypes.c_size_t * max(k, 1))(*[f for _, f, _ in ranges])
+    count = (ctypes.c_size_t * max(k, 1))(*[c for _, _, c in ranges])
+    ok = (ctypes.c_int * max(k, 1))()
+    left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
+    check(lib.h2v_batches_recheck(ba, len(batches), k, bor, first, count, ok, left, right))
+    lr, rr = left.raw, right.raw
+    return [bool(v) for v in ok][:k], [lr[64 * i:64 * i + 64] for i in range(k)], [rr[64 * i:64 * i + 64] for i in range(k)]
 
 
 class Batch:

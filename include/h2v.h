@@ -251,6 +251,22 @@ int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n,
                               int* per_proof_status, int* batch_ok,
                               uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks);
 
+/* Which proofs made a batch of several VerifyingKeys and instance shapes fail: h2v_verify_batch_keys, plus the proofs that fail the
+ * pairing.  Takes the arguments of h2v_verify_batch_keys (same rules for ctxs, key_of_proof, n_instance_columns and col_lens:
+ * per-proof shapes allowed); h2v_verify_batch_shapes' case is n_keys = 1 with every key index 0.  batch_ok / out_left_xy /
+ * out_right_xy are exactly what h2v_verify_batch_keys returns for the same arguments; per_proof_status[i] is what h2v_verify_each on
+ * ctxs[key_of_proof[i]] returns for proof i (0, the instance / transcript / opening errors, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE).
+ * Every (key, shape) group stays resident until the search ends: a key's first group on its context's one-shot batch, its later groups
+ * on batches made for the call and destroyed at its end.  The search runs only when the folded pairing itself fails: failing ranges of
+ * every group are re-checked together, one set of launches per round over all groups (h2v_batches_recheck), until single proofs remain.
+ * rand32 must hold no zero scalar (H2V_ERR_BAD_ARGUMENT before any device work); NULL = draw from the OS RNG.
+ * n_range_checks (may be NULL): how many range checks the search ran (0 when the pairing passes).  Nothing is written on an error. */
+int h2v_verify_batch_keys_identify(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n,
+                                   const uint8_t* const* proofs, const size_t* proof_lens,
+                                   const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                                   const uint8_t* rand32, int* per_proof_status, int* batch_ok,
+                                   uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks);
+
 /* Debug / parity: the Guard of one proof term by term in the order the reference appends them (shplonk.rs:256-264;
  * gwc.rs:86-132: witness_with_aux, commitment_multi query by query — a commitment opened at several points occurs once per
  * query, each time with that query's own scalar — then (eval_multi, -g)), and the
@@ -317,6 +333,16 @@ int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, 
  * check would say nothing about that proof.  The launch's own results, and later uploads and launches, are unaffected.  Synchronous. */
 int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const size_t* count,
                       int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
+/* h2v_batch_recheck over ranges of several batches in ONE set of launches per MSM_MAX_PROBLEMS / 2 ranges: range i = proofs
+ * [first[i], first[i] + count[i]) of batches[batch_of_range[i]], under h2v_batch_recheck's rules for that batch (inside one group of its
+ * last finished launch, no proof with a zero multiplier, ...); range_ok / out_left_xy / out_right_xy as h2v_batch_recheck.  Every batch
+ * must be Finished, on one device and over the same params (g[0], g2 and s_g2 equal; keys and instance shapes may differ); the same
+ * batch may appear more than once.  A batch not finished, on another device or over other params, an index out of range or a null
+ * pointer: H2V_ERR_BAD_ARGUMENT, and nothing is written.  Synchronous.  The re-checks run on the stream of batches[0] and use its
+ * re-check workspace (the one h2v_batch_recheck on batches[0] uses); the other batches' streams are waited for, and only read.  No
+ * batch's own results are touched. */
+int h2v_batches_recheck(h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range,
+                        const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
 /* Device address of this batch's accumulator points after launch: per group [left, right], 2 x 108 bytes each, Jacobian
  * (X, Y, Z) in the library's Montgomery limb layout (debug / inspection; the record a sharded run exchanges is written by
  * h2v_batch_export_accumulators). */

@@ -178,38 +178,60 @@ public:
         statuses_.resize(items_.size());
         return ok != 0;
     }
-    size_t range_checks() const { return range_checks_; }   // re-checks the last finalize_identify() ran (0: the batch passed)
+    // finalize_identify() over one or several VerifyingKeys and any instance shapes (h2v_verify_batch_keys_identify): returns what
+    // finalize() returns, statuses() then holds every proof's SingleStrategy verdict and range_checks() the re-checks the search ran.
+    // The draws must be non-zero; no seed.
+    bool finalize_identify_keys() {
+        if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes an accumulation without a seed");
+        range_checks_ = 0;
+        if (items_.empty()) { statuses_.clear(); return true; }   // an empty DualMSM: both channels are the identity
+        KeyCall kc(*this);
+        statuses_.assign(items_.size() ? items_.size() : 1, 0);
+        int ok = 0;
+        check(h2v_verify_batch_keys_identify(kc.handles.data(), kc.handles.size(), key_of_.data(), items_.size(), kc.proofs.data(), kc.lens.data(), kc.insts.data(),
+                                             kc.ncols.data(), kc.col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_,
+                                             &range_checks_));
+        statuses_.resize(items_.size());
+        return ok != 0;
+    }
+    size_t range_checks() const { return range_checks_; }   // re-checks the last finalize_identify() or finalize_identify_keys() ran (0: the batch passed)
     const std::vector<int>& statuses() const { return statuses_; }
     const uint8_t* left() const { return left_; }     // evaluated channels of the final DualMSM, canonical x|y
     const uint8_t* right() const { return right_; }
 
 private:
     VerifyingKey vk() const { return vks_.empty() ? VerifyingKey{} : vks_[0]; }
+    // The arguments of a call over several VerifyingKeys: a context per key, every proof in call order, column lengths proof by proof
+    struct KeyCall {
+        std::vector<std::unique_ptr<Context>> ctxs;
+        std::vector<h2v_ctx*> handles;
+        std::vector<size_t> ncols;
+        std::vector<const uint8_t*> proofs, insts;
+        std::vector<size_t> lens, col_lens;
+        std::vector<Bytes> flat;
+        explicit KeyCall(const AccumulatorStrategy& s) : ncols(s.vks_.size(), 0), flat(s.items_.size()) {
+            if (!s.rand_.empty() && s.rand_.size() != 32 * s.items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
+            for (size_t k = 0; k < s.vks_.size(); ++k) {
+                ctxs.emplace_back(new Context(s.params_, s.vks_[k], s.device_, s.mo_, s.tr_, s.ci_));
+                handles.push_back(ctxs.back()->handle());
+                check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
+            }
+            for (size_t i = 0; i < s.items_.size(); ++i) {
+                const Instances& inst = s.items_[i].first;
+                if (inst.size() != ncols[s.key_of_[i]]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
+                for (const Column& c : inst) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
+                proofs.push_back(s.items_[i].second.data()); lens.push_back(s.items_[i].second.size()); insts.push_back(flat[i].data());
+            }
+        }
+    };
     // proofs of several VerifyingKeys: a context per key, every proof in call order (h2v_verify_batch_keys)
     bool finalize_keys() {
         if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes proofs of one VerifyingKey");
-        if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
-        std::vector<std::unique_ptr<Context>> ctxs;
-        std::vector<h2v_ctx*> handles;
-        std::vector<size_t> ncols(vks_.size(), 0);
-        for (size_t k = 0; k < vks_.size(); ++k) {
-            ctxs.emplace_back(new Context(params_, vks_[k], device_, mo_, tr_, ci_));
-            handles.push_back(ctxs.back()->handle());
-            check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
-        }
-        std::vector<const uint8_t*> proofs, insts;
-        std::vector<size_t> lens, col_lens;
-        std::vector<Bytes> flat(items_.size());
-        for (size_t i = 0; i < items_.size(); ++i) {
-            const Instances& inst = items_[i].first;
-            if (inst.size() != ncols[key_of_[i]]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
-            for (const Column& c : inst) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
-            proofs.push_back(items_[i].second.data()); lens.push_back(items_[i].second.size()); insts.push_back(flat[i].data());
-        }
+        KeyCall kc(*this);
         statuses_.assign(items_.size(), 0);
         int ok = 0;
-        check(h2v_verify_batch_keys(handles.data(), handles.size(), key_of_.data(), items_.size(), proofs.data(), lens.data(), insts.data(), ncols.data(),
-                                    col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
+        check(h2v_verify_batch_keys(kc.handles.data(), kc.handles.size(), key_of_.data(), items_.size(), kc.proofs.data(), kc.lens.data(), kc.insts.data(), kc.ncols.data(),
+                                    kc.col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
         return ok != 0;
     }
 
@@ -234,6 +256,24 @@ inline RangeChecks recheck(h2v_batch* b, const std::vector<std::pair<size_t, siz
     RangeChecks out;
     out.lefts.assign(64 * ranges.size(), 0); out.rights.assign(64 * ranges.size(), 0);
     check(h2v_batch_recheck(b, ranges.size(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
+    for (size_t i = 0; i < ranges.size(); ++i) out.ok.push_back(ok[i] != 0);
+    return out;
+}
+
+// The same over ranges of several finished batches in one set of launches (h2v_batches_recheck): a range is (batch index, first, count);
+// the batches must be on one device and over the same params
+struct BatchRange { size_t batch, first, count; };
+inline RangeChecks recheck(const std::vector<h2v_batch*>& batches, const std::vector<BatchRange>& ranges) {
+    std::vector<uint32_t> bor;
+    std::vector<size_t> first, count;
+    for (const auto& r : ranges) {
+        if (r.batch >= batches.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "batch index out of range");
+        bor.push_back((uint32_t)r.batch); first.push_back(r.first); count.push_back(r.count);
+    }
+    std::vector<int> ok(ranges.size() ? ranges.size() : 1, 0);
+    RangeChecks out;
+    out.lefts.assign(64 * ranges.size(), 0); out.rights.assign(64 * ranges.size(), 0);
+    check(h2v_batches_recheck(batches.data(), batches.size(), ranges.size(), bor.data(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
     for (size_t i = 0; i < ranges.size(); ++i) out.ok.push_back(ok[i] != 0);
     return out;
 }

@@ -143,6 +143,24 @@ impl<'p> GpuMultiKeyVerifier<'p> {
         if rc != 0 { return Err(map_err(rc)); }
         Ok(ok == 1)
     }
+
+    /// `finalize`, plus the verdict of every proof in push order: `Ok(())` or the `Error` that `verify_proof` under `SingleStrategy`
+    /// with that proof's key returns for it (`ConstraintSystemFailure` for the proofs whose own pairing fails).  When the pairing passes
+    /// this costs what `finalize` costs; otherwise the failing ranges of every key's proofs are re-checked on the GPU together until
+    /// single proofs remain (h2v_verify_batch_keys_identify).
+    pub fn finalize_identify(self) -> Result<(bool, Vec<Result<(), Error>>), Error> {
+        let n = self.proofs.len();
+        let ptrs: Vec<*const u8> = self.proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = self.proofs.iter().map(|p| p.len()).collect();
+        let iptrs: Vec<*const u8> = self.instances.iter().map(|i| i.as_ptr()).collect();
+        let (mut status, mut ok, mut checks) = (vec![0i32; n.max(1)], 0i32, 0usize);
+        let rc = unsafe { h2v_verify_batch_keys_identify(self.ctxs.as_ptr(), self.ctxs.len(), self.keys.as_ptr(), n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(),
+                                                         self.n_cols.as_ptr(), self.col_lens.as_ptr(), core::ptr::null(), status.as_mut_ptr(), &mut ok,
+                                                         core::ptr::null_mut(), core::ptr::null_mut(), &mut checks) };
+        if rc != 0 { return Err(map_err(rc)); }
+        let verdicts = status[..n].iter().map(|&s| if s == 0 { Ok(()) } else { Err(map_err(s)) }).collect();
+        Ok((ok == 1, verdicts))
+    }
 }
 impl<'p> Drop for GpuMultiKeyVerifier<'p> { fn drop(&mut self) { for &c in &self.ctxs { unsafe { h2v_ctx_destroy(c) } } } }
 
