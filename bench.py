@@ -15,10 +15,14 @@ timed steps start and finish inside the one timed region.  `--dump-outputs DIR` 
 child processes, the parent never touches the GPU); under torch.distributed.run the ranks come from the environment.  Either
 way WORLD_SIZE must equal --gpus, otherwise the run fails instead of silently measuring another job.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the MSM (msm_accumulate): achieved = 96 B x the terms of a
-launch / the kernel's average duration inside the timed region (its dispatch's own timestamps); `roofline.stage` has the whole MSM stage.
-`cpu_baseline` = the CPU oracle (a port of the reference algorithm, single thread like the reference) timed on a bounded
-sample of the same proofs on this host.
+A plain run makes its inputs (from fixed seeds, in memory), warms up, times the K steps, writes --dump-outputs and prints ONE JSON
+line (rank 0): the headline figures, `config`, and `roofline` for the dominant kernel of the MSM (msm_accumulate): achieved = 96 B x
+the terms of a launch / the kernel's average duration inside the timed region (its dispatch's own timestamps).
+
+`--full` adds what takes runs of its own, after the headline: launches re-timed one at a time (`stages_ms`; `roofline.stage` has the
+whole MSM stage), the PCIe-inclusive leg (`value_reupload`), `config3` (N > 1), `config4` and `single_strategy` (N = 1), `parity` of
+a timed launch against the CPU oracle, and `cpu_baseline` = the CPU oracle (a port of the reference algorithm, single thread like the
+reference) timed on a bounded sample of the same proofs on this host.
 """
 import argparse
 import ctypes
@@ -51,9 +55,23 @@ def hw_queue_env():
     os.environ["GPU_MAX_HW_QUEUES"] = str(max(1, min(v, MAX_HW_QUEUES)))
 
 
+def make_proofs(count, k, log):
+    """`count` distinct proofs of the vector_mul circuit from the test prover, with fixed seeds:
+    dict(proofs, inst, vk, params).  A benchmark run makes its inputs afresh, in memory: it reads nothing an earlier run wrote."""
+    import circuits
+    t = time.time()
+    s = circuits.setup_vector_mul(k, N_PUBLIC, s_seed=0x48325630)  # known-s test SRS, s from seed "H2V0"
+    threads = min(32, os.cpu_count() or 1)
+    P, I = circuits.prove_vector_mul_batch(s, count, seed=0x48325630, threads=threads)
+    d = dict(proofs=b"".join(P), inst=b"".join(b"".join(col) for inst in I for col in inst), vk=s.vk, params=s.params)
+    s.free()
+    log(f"generated {count} proofs (k={k}) with {threads} threads in {time.time() - t:.1f}s")
+    return d
+
+
 def _cache_dirs():
-    """Where generated bench inputs are cached, in order: .bench_cache/ in the checkout, then a directory of this user's own
-    under the temp directory (for a checkout the benchmark may not write to).  (path, must be owned by this user)."""
+    """Where load_or_make_proofs() caches the bench's proofs, in order: .bench_cache/ in the checkout, then a directory of this
+    user's own under the temp directory (for a checkout that may not be written to).  (path, must be owned by this user)."""
     return [(os.path.join(ROOT, ".bench_cache"), False),
             (os.path.join(tempfile.gettempdir(), f"h2v_bench_cache_{os.getuid()}"), True)]
 
@@ -87,42 +105,29 @@ def _load_or_make(tag, valid, make):
 
 
 def load_or_make_proofs(count, k, log):
-    """`count` distinct proofs of the vector_mul circuit, cached on disk (_load_or_make)."""
-    import circuits
-
-    def make():
-        t = time.time()
-        s = circuits.setup_vector_mul(k, N_PUBLIC, s_seed=0x48325630)  # known-s test SRS, s from seed "H2V0"
-        threads = min(32, os.cpu_count() or 1)
-        P, I = circuits.prove_vector_mul_batch(s, count, seed=0x48325630, threads=threads)
-        d = dict(proofs=b"".join(P), inst=b"".join(b"".join(col) for inst in I for col in inst), vk=s.vk, params=s.params)
-        s.free()
-        log(f"generated {count} proofs (k={k}) with {threads} threads in {time.time() - t:.1f}s")
-        return d
+    """make_proofs(), cached on disk (_load_or_make): for the tests and probes that use the bench's proofs.  The benchmark itself
+    does not use the cache."""
     return _load_or_make(f"vm_k{k}_pub{N_PUBLIC}_n{count}",
-                         lambda d: len(d["proofs"]) == count * 1024 and len(d["inst"]) == count * 32 * N_PUBLIC, make)
+                         lambda d: len(d["proofs"]) == count * 1024 and len(d["inst"]) == count * 32 * N_PUBLIC,
+                         lambda: make_proofs(count, k, log))
 
 
-def load_or_make_wide(count, k, log):
+def make_wide(count, k, log):
     """BASELINE.json config 4: `count` distinct proofs of the lookup-heavy VK (32 advice, 16 fixed, 8 two-column lookups, gate degree
-    5: 74 points + 170 scalars = 7808-byte proofs, 124 right-channel terms), cached on disk (_load_or_make).  k = 10 here: the test
-    prover needs ~70 s per proof at the k = 16 BASELINE.json names (that size is covered for parity by tests/golden/wide_k16_lookup_heavy.json);
-    the verifier's work per proof does not depend on k beyond the k squarings of x^n."""
+    5: 74 points + 170 scalars = 7808-byte proofs, 124 right-channel terms).  k = 10 here: the test prover needs ~70 s per proof at
+    the k = 16 BASELINE.json names (that size is covered for parity by tests/golden/wide_k16_lookup_heavy.json); the verifier's work
+    per proof does not depend on k beyond the k squarings of x^n."""
     import concurrent.futures
     import circuits
-
-    def make():
-        t = time.time()
-        s = circuits.setup_wide(k, A=32, F=16, L_=8, Sh=0, deg=5)
-        threads = min(32, os.cpu_count() or 1)
-        with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as ex:   # ctypes releases the GIL; the setup is read-only
-            pairs = list(ex.map(lambda i: circuits.prove_wide(s, witness_seed=i, rng_seed=1000 + i), range(count)))
-        d = dict(proofs=b"".join(p for p, _ in pairs), inst=b"".join(b"".join(col) for _, inst in pairs for col in inst), vk=s.vk, params=s.params)
-        s.free()
-        log(f"generated {count} lookup-heavy proofs (k={k}) with {threads} threads in {time.time() - t:.1f}s")
-        return d
-    return _load_or_make(f"wide_k{k}_a32_f16_l8_d5_n{count}",
-                         lambda d: len(d["proofs"]) % count == 0 and len(d["inst"]) == count * 32 * 8, make)
+    t = time.time()
+    s = circuits.setup_wide(k, A=32, F=16, L_=8, Sh=0, deg=5)
+    threads = min(32, os.cpu_count() or 1)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as ex:   # ctypes releases the GIL; the setup is read-only
+        pairs = list(ex.map(lambda i: circuits.prove_wide(s, witness_seed=i, rng_seed=1000 + i), range(count)))
+    d = dict(proofs=b"".join(p for p, _ in pairs), inst=b"".join(b"".join(col) for _, inst in pairs for col in inst), vk=s.vk, params=s.params)
+    s.free()
+    log(f"generated {count} lookup-heavy proofs (k={k}) with {threads} threads in {time.time() - t:.1f}s")
+    return d
 
 
 def oracle_group(d, n, draws):
@@ -266,7 +271,7 @@ def config4_leg(h2v, args, log):
     batch its own accumulators and pairing — the same pipeline as the headline on the VK that stresses expression evaluation."""
     import torch
     k, B, G, depth, launches = 10, 1024, 8, 4, 12
-    d = load_or_make_wide(B, k, log)
+    d = make_wide(B, k, log)
     plen = len(d["proofs"]) // B
     ctx = h2v.Context(h2v.ParamsKZG(d["params"], h2v.SerdeFormat.RawBytes), h2v.VerifyingKey(d["vk"], h2v.SerdeFormat.RawBytes))
     shape = ctx.proof_shape()
@@ -412,12 +417,12 @@ def rank_main(args):
             else:
                 dist.barrier()
 
-    # inputs: rank 0 generates (or loads) the proofs, the others wait and read the cache
-    if rank == 0:
-        d = load_or_make_proofs(args.distinct, K_CIRCUIT, log)
-    barrier()
-    if rank != 0:
-        d = load_or_make_proofs(args.distinct, K_CIRCUIT, log)
+    # inputs: rank 0 makes the proofs (the prover takes the host's CPUs), the other ranks receive a copy
+    d = make_proofs(args.distinct, K_CIRCUIT, log) if rank == 0 else None
+    if world > 1:
+        box = [d]
+        dist.broadcast_object_list(box, src=0, device=torch.device(dev) if backend == "nccl" else None)
+        d = box[0]
 
     ctx = h2v.Context(h2v.ParamsKZG(d["params"], h2v.SerdeFormat.RawBytes), h2v.VerifyingKey(d["vk"], h2v.SerdeFormat.RawBytes), device=local_rank)
     shape = ctx.proof_shape()
@@ -551,16 +556,19 @@ def rank_main(args):
         return dict(dt=dt, G=G, launches=launches, rem=rem, depth=depth, total=total, stages=stages, isolated=isolated, terms_launch=terms_launch, B=B,
                     group0=last_group0[0], group0_draws=tails[0] if world == 1 else None, last_step=last_step)
 
-    m = measure(args.batch, args.steps, args.warmup, args.groups, args.depth, reupload=args.reupload, isolated_launches=4 if world == 1 else 2)
+    # A plain run stops after the timed region (and --dump-outputs): whatever else the benchmark measures or checks takes runs of its
+    # own and comes with --full.
+    m = measure(args.batch, args.steps, args.warmup, args.groups, args.depth, reupload=args.reupload,
+                isolated_launches=(4 if world == 1 else 2) if args.full else 0)
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, m["last_step"])
     m_re = None
-    if world == 1 and not args.reupload and not args.no_reupload_leg:
+    if args.full and world == 1 and not args.reupload and not args.no_reupload_leg:
         # PCIe-inclusive leg (SURVEY.md §8d timing method): the same K steps with the host buffers copied to the device again
         # before every launch; reported as value_reupload beside `value`, never instead of it
         m_re = measure(args.batch, args.steps, args.warmup, args.groups, args.depth, reupload=True)
     m_c3 = None
-    if world > 1 and not args.no_config3:
+    if args.full and world > 1 and not args.no_config3:
         # BASELINE.json configs 3 and 5: 8192 proofs per GPU per step (65 536 over 8 GPUs), ONE pairing for the whole N x 8192
         # step.  Measured after the headline so that `value` keeps the per-GPU shape of the N = 1 run (weak scaling).
         m_c3 = measure(8192, args.config3_steps, 2, 2, 2)
@@ -569,17 +577,8 @@ def rank_main(args):
         G, depth, B = m["G"], m["depth"], m["B"]
         stages, isolated = m["stages"], m["isolated"]
         terms_total = m["terms_launch"]
-        src = isolated if isolated else stages
-        msm_ms = src["msm"]
         traffic, traffic_src, tj = traffic_record(terms_total)
-        achieved = (96.0 * terms_total) / (msm_ms * 1e-3) / 1e9 if msm_ms > 0 else 0.0
-        acc_ms = src.get("msm_accumulate", 0.0)
-        valu = None
-        try:
-            va = (tj or {}).get("valu_active", {})
-            valu = next((v for k2, v in va.items() if k2 == "h2v::msm_accumulate" or k2.startswith("h2v::msm_accumulate<")), None)
-        except Exception:
-            pass
+        acc_ms = (isolated or {}).get("msm_accumulate", 0.0)
         acc_timed = stages.get("msm_accumulate", 0.0) or acc_ms          # the dispatch's own timestamps, every launch of the timed region
         # HBM traffic of the dominant kernel alone, from the same committed PMC record (scaled per term when the shape differs)
         acc_traffic = None
@@ -591,14 +590,17 @@ def rank_main(args):
         except Exception:
             pass
         acc_gbps = (96.0 * terms_total) / (acc_timed * 1e-3) / 1e9 if acc_timed > 0 else 0.0
-        kernels = {"msm_accumulate": {"ms": acc_ms, "ms_timed_region": stages.get("msm_accumulate", 0.0),
-                                      "timing": "the dispatch's own start / stop timestamps (hipExtLaunchKernelGGL events), every launch of the timed region; `ms` = the same for launches re-timed one at a time", "alg_GBps": (96.0 * terms_total) / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else None,
-                                      "valu_active": valu, "valu_active_source": "SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES from the committed --pmc pass named in traffic_source",
-                                      "alu_frac": (2 * 12 * 11 * terms_total) / (acc_ms * 1e-3) / 168e9 if acc_ms > 0 else None,
-                                      "alu_frac_note": "Fq products/s of the kernel (11 per mixed addition, 2 x 12 additions per term) over the measured chip-wide peak of the Montgomery product, 168 G/s (tools/limb29_microbench.hip)"}}
         workload = (f"batch {B} proofs/GPU/step, k={K_CIRCUIT}, vector_mul VK (3 advice, 1 fixed, 1 instance col with {N_PUBLIC} public inputs, 4 permutation cols), "
                     f"SHPLONK/Blake2b, AccumulatorStrategy (one pairing per step" + (f" for all {world} x {B} proofs" if world > 1 else "") + f"), {args.distinct} distinct proofs; "
                     f"{G} steps per launch (grouped batch), {depth} launches in flight" + (f", + one launch of {m['rem']} steps" if m["rem"] else ""))
+        # the DOMINANT KERNEL (msm_accumulate: the bucket accumulation of every MSM of a launch): algorithmic bytes of a launch over the
+        # kernel's average duration inside the timed region; with --full, the whole MSM stage (all its kernels) is in `stage`
+        roofline = {"bound": "hbm", "achieved": acc_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": acc_gbps / HBM_PEAK_GBPS, "traffic": acc_traffic,
+                    "traffic_source": traffic_src,
+                    "kernel": "msm_accumulate (the dominant kernel of the MSM stage: one mixed G1 addition per entry of the sorted (term, half, window) list of every MSM of a launch)",
+                    "kernel_ms": acc_timed,
+                    "timing": "the dispatch's own start / stop timestamps on the stream it is launched on (hipExtLaunchKernelGGL events), averaged over every launch of the timed region",
+                    "terms_per_launch": terms_total, "algorithmic_bytes_per_launch": 96 * terms_total}
         out = {
             "metric": "proofs verified/sec (BN254, k=14)",
             "value": m["total"] * args.steps / m["dt"],
@@ -617,27 +619,35 @@ def rank_main(args):
             "config": {"workload": workload,
                        "inputs": "copied host -> device before every launch (PCIe-inclusive)" if args.reupload else "resident in HBM before the timed region",
                        "proofs_per_gpu_per_step": B, "steps_per_launch": G, "pipeline_depth": depth, "proof_bytes": shape["proof_len"]},
-            # the DOMINANT KERNEL (msm_accumulate: the bucket accumulation of every MSM of a launch): algorithmic bytes of a launch over the
-            # kernel's average duration inside the timed region; the whole MSM stage (all its kernels) is in `stage`
-            "roofline": {"bound": "hbm", "achieved": acc_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": acc_gbps / HBM_PEAK_GBPS, "traffic": acc_traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": "msm_accumulate (the dominant kernel of the MSM stage: one mixed G1 addition per entry of the sorted (term, half, window) list of every MSM of a launch)",
-                         "kernel_ms": acc_timed, "kernel_ms_one_launch_in_flight": acc_ms,
-                         "timing": "the dispatch's own start / stop timestamps on the stream it is launched on (hipExtLaunchKernelGGL events), averaged over every launch of the timed region",
-                         "terms_per_launch": terms_total, "algorithmic_bytes_per_launch": 96 * terms_total,
-                         "kernels": kernels,
-                         "stage": {"what": "the whole MSM stage (msm_glv_prep, msm_sort_lds, msm_seg_scan, msm_accumulate, msm_accumulate_redo, msm_fixup, msm_window, msm_final_parts; both channels of every step of a launch)",
-                                   "achieved": achieved, "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "mean_stage_ms": msm_ms,
-                                   "timing": "HIP events on the launch's stream, one launch in flight (after the timed region)" if isolated else "HIP events on the launch's stream, inside the timed region (other launches in flight)"},
-                         "alu": {"note": "the stage is bound by 32-bit integer multiply issue, not by HBM: achieved Fq products/s of the stage against the "
-                                         "measured chip-wide peak of the Montgomery product (tools/limb29_microbench.hip)",
-                                 "fq_products_per_term": 2 * 12 * 11, "fq_products_per_term_note": "2 GLV halves x 12 windows (c = 11, the 1024-proof step) x 11 per mixed addition",
-                                 "achieved_Gprod_s": (2 * 12 * 11 * terms_total) / (msm_ms * 1e-3) / 1e9 if msm_ms > 0 else 0.0,
-                                 "peak_Gprod_s": 168.0}},
-            "stages_ms": isolated if isolated else stages,
-            "stages_ms_note": "HIP events between the stages, launches re-timed one at a time after the timed region (inside it only msm_accumulate is timed: an event between stages is a barrier packet, ~6 us of idle stream)",
-            "stages_ms_one_launch_in_flight": isolated,
+            "roofline": roofline,
         }
+        if isolated:
+            # --full: the launches re-timed one at a time after the timed region (per-stage and per-kernel figures)
+            msm_ms = isolated["msm"]
+            achieved = (96.0 * terms_total) / (msm_ms * 1e-3) / 1e9 if msm_ms > 0 else 0.0
+            valu = None
+            try:
+                va = (tj or {}).get("valu_active", {})
+                valu = next((v for k2, v in va.items() if k2 == "h2v::msm_accumulate" or k2.startswith("h2v::msm_accumulate<")), None)
+            except Exception:
+                pass
+            roofline["kernel_ms_one_launch_in_flight"] = acc_ms
+            roofline["kernels"] = {"msm_accumulate": {"ms": acc_ms, "ms_timed_region": stages.get("msm_accumulate", 0.0),
+                                                      "timing": "the dispatch's own start / stop timestamps (hipExtLaunchKernelGGL events), every launch of the timed region; `ms` = the same for launches re-timed one at a time", "alg_GBps": (96.0 * terms_total) / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else None,
+                                                      "valu_active": valu, "valu_active_source": "SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES from the committed --pmc pass named in traffic_source",
+                                                      "alu_frac": (2 * 12 * 11 * terms_total) / (acc_ms * 1e-3) / 168e9 if acc_ms > 0 else None,
+                                                      "alu_frac_note": "Fq products/s of the kernel (11 per mixed addition, 2 x 12 additions per term) over the measured chip-wide peak of the Montgomery product, 168 G/s (tools/limb29_microbench.hip)"}}
+            roofline["stage"] = {"what": "the whole MSM stage (msm_glv_prep, msm_sort_lds, msm_seg_scan, msm_accumulate, msm_accumulate_redo, msm_fixup, msm_window, msm_final_parts; both channels of every step of a launch)",
+                                 "achieved": achieved, "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "mean_stage_ms": msm_ms,
+                                 "timing": "HIP events on the launch's stream, one launch in flight (after the timed region)"}
+            roofline["alu"] = {"note": "the stage is bound by 32-bit integer multiply issue, not by HBM: achieved Fq products/s of the stage against the "
+                                       "measured chip-wide peak of the Montgomery product (tools/limb29_microbench.hip)",
+                               "fq_products_per_term": 2 * 12 * 11, "fq_products_per_term_note": "2 GLV halves x 12 windows (c = 11, the 1024-proof step) x 11 per mixed addition",
+                               "achieved_Gprod_s": (2 * 12 * 11 * terms_total) / (msm_ms * 1e-3) / 1e9 if msm_ms > 0 else 0.0,
+                               "peak_Gprod_s": 168.0}
+            out["stages_ms"] = isolated
+            out["stages_ms_note"] = "HIP events between the stages, launches re-timed one at a time after the timed region (inside it only msm_accumulate is timed: an event between stages is a barrier packet, ~6 us of idle stream)"
+            out["stages_ms_one_launch_in_flight"] = isolated
         if tuning:
             out["tuning"] = tuning   # NOT the library's own choice of kernel variants: a measurement aid (--tuning)
         if m_re:
@@ -650,10 +660,10 @@ def rank_main(args):
                                           f"{m_c3['G']} steps per launch, {m_c3['depth']} launches in flight, {args.config3_steps} steps timed",
                               "value": m_c3["total"] * args.config3_steps / m_c3["dt"], "unit": "proofs/s", "ms_per_step": m_c3["dt"] / args.config3_steps * 1e3,
                               "proofs_per_step": m_c3["total"]}
-        if world == 1 and not args.no_extra_legs:
+        if args.full and world == 1 and not args.no_extra_legs:
             out["config4"] = config4_leg(h2v, args, log)
             out["single_strategy"] = single_strategy_leg(h2v, ctx, d, args)
-        if world == 1 and m["group0"] is not None and not args.no_cpu_baseline:
+        if args.full and world == 1 and m["group0"] is not None and not args.no_cpu_baseline:
             # parity of the benched launch itself: timed group 0 (the accumulators of its last timed launch) against the CPU oracle
             # on the same proofs and the same draws — (left, right) bit for bit, both accepting
             reps = (B + args.distinct - 1) // args.distinct
@@ -666,7 +676,7 @@ def rank_main(args):
             if not match:
                 print(json.dumps(out), file=sys.stderr, flush=True)
                 raise SystemExit("bench.py: the benched launch's accumulators differ from the CPU oracle's")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline({**d, "proofs": (d["proofs"] * ((args.cpu_sample + args.distinct - 1) // args.distinct))[: args.cpu_sample * 1024],
                                                 "inst": (d["inst"] * ((args.cpu_sample + args.distinct - 1) // args.distinct))[: args.cpu_sample * 32 * N_PUBLIC]},
                                                args.cpu_sample, log)
@@ -686,15 +696,18 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="steps (independent batches, one pairing each) carried by one launch (h2v_batch_set_groups); 0 = choose from --steps")
     ap.add_argument("--depth", type=int, default=0, help="launches in flight per GPU (one HIP stream each); 0 = 8")
     ap.add_argument("--distinct", type=int, default=1024, help="distinct proofs generated (cycled if --batch is larger)")
-    ap.add_argument("--cpu-sample", type=int, default=2048)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--reupload", action="store_true", help="copy the host buffers to the device again before every launch inside the headline run itself")
-    ap.add_argument("--no-reupload-leg", action="store_true", help="skip the extra PCIe-inclusive leg (value_reupload)")
-    ap.add_argument("--no-config3", action="store_true", help="N > 1: skip the extra 8192-proofs-per-GPU leg (BASELINE.json configs 3/5)")
-    ap.add_argument("--config3-steps", type=int, default=8)
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the results of the last timed step to DIR/<name>.npy (see dump_outputs())")
     ap.add_argument("--tuning", default="", help="measurement aid: forced kernel variants, key=value[,key=value...] of h2v_tuning (default: automatic)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="N = 1: skip the config-4 (lookup-heavy VK) and SingleStrategy legs")
+    ap.add_argument("--full", action="store_true", help="after the headline, also what takes runs of its own: launches re-timed one at a time (stages_ms, "
+                    "roofline.stage / kernels / alu), the PCIe-inclusive leg, config 3 (N > 1), config 4 and SingleStrategy (N = 1), parity with the "
+                    "CPU oracle and the CPU baseline (N = 1)")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="--full: proofs in the CPU baseline's sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the parity check and the CPU baseline")
+    ap.add_argument("--no-reupload-leg", action="store_true", help="--full: skip the extra PCIe-inclusive leg (value_reupload)")
+    ap.add_argument("--no-config3", action="store_true", help="--full, N > 1: skip the extra 8192-proofs-per-GPU leg (BASELINE.json configs 3/5)")
+    ap.add_argument("--config3-steps", type=int, default=8, help="--full, N > 1: timed steps of the config-3 leg")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full, N = 1: skip the config-4 (lookup-heavy VK) and SingleStrategy legs")
     ap.add_argument("--dry-run", action="store_true", help="print the launch plan (and, for N > 1, prove the N-rank rendezvous over gloo) without touching the GPU")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:

@@ -109,20 +109,20 @@ def headline_stats(sub, dst, header):
 
 bdrv, bdef = bench_line("driver.json"), bench_line("default.json")
 avg_all = stats("driver", f"{tag}_kernel_stats_driver_cmd_all_legs.csv",
-                ["rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5   (the command the driver runs; MI355X)",
+                ["rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full   (the headline command with every leg; MI355X)",
                  "%s" % bdrv.get("config", {}).get("workload", ""),
                  "calls: 1 warm-up + 7 timed launches (the timed region repeated, median reported) + 4 launches re-timed alone after the timed region, the same again for the PCIe-inclusive leg, + the config-4 and SingleStrategy legs; every headline launch carries 20 steps",
                  "bench line of this run: value=%.0f proofs/s, ms_per_step=%.4f, stages_ms_one_launch_in_flight=%s" % (bdrv.get("value", 0), bdrv.get("ms_per_step", 0), json.dumps(bdrv.get("stages_ms_one_launch_in_flight", {})))])
 avg_drv = headline_stats("driver", f"{tag}_kernel_stats_driver_cmd.csv",
-                         ["rocprofv3 --kernel-trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5   (the command the driver runs; MI355X)",
+                         ["rocprofv3 --kernel-trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full   (the headline command with every leg; MI355X)",
                           "%s" % bdrv.get("config", {}).get("workload", ""),
                           "bench line of this run: value=%.0f proofs/s, ms_per_step=%.4f, stages_ms_one_launch_in_flight=%s" % (bdrv.get("value", 0), bdrv.get("ms_per_step", 0), json.dumps(bdrv.get("stages_ms_one_launch_in_flight", {})))]) or avg_all
 stats("default", f"{tag}_kernel_stats_default_cmd.csv",
-      ["rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline   (the default bench command: 32 steps per launch, 8 launches in flight; MI355X)",
+      ["rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-extra-legs   (the default bench command: 32 steps per launch, 8 launches in flight; MI355X)",
        "%s" % bdef.get("config", {}).get("workload", ""),
        "bench line of this run: value=%.0f proofs/s, ms_per_step=%.4f (kernels of different launches overlap, durations are inflated by sharing)" % (bdef.get("value", 0), bdef.get("ms_per_step", 0))])
 
-for shape, pre, cmd in (("steps20", "drv", "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-reupload-leg"),
+for shape, pre, cmd in (("steps20", "drv", "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-reupload-leg --no-extra-legs"),
                         ("steps32", "d1", "python3 bench.py --steps 128 --warmup 32 --depth 1 --no-cpu-baseline --no-reupload-leg")):
     fetch, write, valu = counters(pre + "_fetch"), counters(pre + "_write"), counters(pre + "_valu")
     if not fetch and not write:
