@@ -80,7 +80,9 @@ int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uin
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // groups > 1: group g owns proofs [g*n/groups, ..) and the draws tail[g*n_tail/groups, ..)
-int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult);
+// d_scratch: multipliers_scratch(n_tail, groups) elements (the tiles' products of the two-level scan)
+size_t multipliers_scratch(uint32_t n_tail, uint32_t groups);
+int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult, Fr* d_scratch);
 // out[i] = src[idx[i]]: the multipliers of a non-contiguous subset of a larger accumulation
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
@@ -130,6 +132,7 @@ struct LaunchRecord {           // what the last launch (or fold) left (close_en
     bool pairing = false;       // its pairing checks were enqueued: the `ok` words are its verdicts
     bool pieces = false;        // no pairing, accumulators in pieces only: acc / out_bytes are put together on demand (ensure_whole)
     bool tail_on_aux = false;   // whatever the stage: its whole accumulators, their bytes and the result copy are still on the auxiliary stream (join_tail)
+    bool host_block = false;    // the launch itself sends the result block to the host (the pairing launch's tail workgroups, or the auxiliary stream)
 };
 // The staged batch's steps (batch.hip) that the one-shot entry points (oneshot.hip) run on their scratch batches
 int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false);
@@ -147,10 +150,10 @@ int export_whole_records(h2v_batch* b, void* device_dst);
 
 struct h2v_batch {
     h2v_ctx* ctx = nullptr;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;     // the caller's (h2v_batch_set_stream), or the batch's own from its first use on (need_stream)
     bool owns_stream = true;
-    hipStream_t aux = nullptr;        // the accumulators' affine conversion runs here, beside the pairing (both only read them)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork0 = nullptr, ev_join0 = nullptr;
+    hipStream_t aux = nullptr;        // only for a launch whose tail the pairing launch cannot carry (close_enqueue, need_aux): the affine conversion beside the pairing
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // h2v_batch_upload_launch: the host -> device copies run on `copy`, chunk by chunk, each followed (after the blocking copy has
     // returned) by the decompression of that chunk on `stream`
     hipStream_t copy = nullptr;
@@ -167,6 +170,8 @@ struct h2v_batch {
     h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)
     h2v::DevBuf<uint8_t> ycanon;
     h2v::DevBuf<unsigned long long> words; h2v::DevBuf<h2v::Fr> chal, mult, slots;
+    h2v::DevBuf<h2v::Fr> mult_tiles;  // multipliers_enqueue's scratch
+    bool mult_of_draws = false;       // Uploaded and later: `mult` holds the multipliers of the uploaded draws (not gathered ones, h2v_verify_batch_shapes)
     h2v::DevBuf<uint32_t> msm_scal; h2v::DevBuf<h2v::Fr> shared; h2v::DevBuf<uint32_t> left_scal;
     h2v::DevBuf<h2v::Fr> insteval;    // [query][proof] (wide instance vectors)
     h2v::DevBuf<uint32_t> guard_scal; // [proof][guard term][8] (h2v_guard_msm with GWC)

@@ -129,34 +129,72 @@ void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_
     pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
 }
 
+// The streams of a batch exist from their first use on: a batch whose caller binds a stream (h2v_batch_set_stream) never creates one of
+// its own, and the auxiliary stream is made by the first launch whose tail needs it.  (The runtime gives every stream of the process one
+// of a few in-order hardware queues, and the kernels of all streams on a queue run one after another: with a second and a third stream
+// per batch, seven of eight launches in flight shared one queue — profiles/r04_queue_gaps.txt)
+int need_stream(h2v_batch* b) {
+    if (b->stream || !b->owns_stream) return 0;   // (a caller's stream may be the null stream)
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    H2V_HIP_CHECK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    return 0;
+}
+int need_aux(h2v_batch* b) {
+    if (b->aux) return 0;
+    H2V_HIP_CHECK(hipStreamCreateWithFlags(&b->aux, hipStreamNonBlocking));
+    H2V_HIP_CHECK(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+    H2V_HIP_CHECK(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
+    return 0;
+}
+
 // The end of a launch: the pairing checks and the conversion of the accumulators to affine bytes only READ the accumulators, and
-// both are latency chains on a few waves (0.5 ms and 0.35 ms) — they run side by side, the conversion and the copy of the result block
-// on the batch's auxiliary stream.  That stream is NOT joined back into the main one (its last event, ev_join, is what join_tail makes
-// the main stream wait for if anything but h2v_batch_finish comes next).
+// both are latency chains on a few waves (0.5 ms and 0.35 ms) — they run side by side.  A launch that left its accumulators in pieces
+// (every launch of at most 64 groups) does both in ONE kernel launch on its own stream: the checks' workgroups first, then the
+// workgroups that put the whole points together, convert them and send the result block to the host (PairTail, pairing.hip).  The
+// launch then lives on one stream from its first kernel to its last: with more streams in flight than hardware queues, every
+// event that forks to or joins a second stream is a barrier packet in a queue that other launches' kernels sit in as well.
+// Otherwise (whole accumulators, the one-stream pairing table) the conversion and the copy of the result block run on the batch's
+// auxiliary stream, which is NOT joined back into the main one (its last event, ev_join, is what join_tail makes the main stream
+// wait for if anything but h2v_batch_finish comes next).
 int close_enqueue(h2v_batch* b, bool with_pairing) {
     hipStream_t s = b->stream;
     const uint32_t G = b->groups;
     int rc;
-    b->last.pairing = with_pairing; b->last.pieces = false;
+    b->last.pairing = with_pairing; b->last.pieces = false; b->last.host_block = false;
     if (!with_pairing) {
         if (b->split.parts) { b->last.pieces = true; return 0; }   // pieces only for now
         return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
     }
+    const ResultsLayout L{G, b->n};
+    uint8_t* const host = static_cast<uint8_t*>(b->results_host.dev);
+    const bool one_stream = b->ctx->tuning.pairing_one_stream != 0;
+    if (b->split.parts && pairing_tail_fits(b->ctx->pairing, one_stream)) {
+        // (the verdicts are still the last thing the launch writes: the tail's workgroups are done long before the checks')
+        PairTail t;
+        t.pieces = b->split.pts; t.prs = b->ws.final_problems; t.count = b->split.count; t.parts = b->split.parts; t.shift = b->split.shift;
+        t.out_bytes = b->out_bytes; t.out_ident = b->out_ident;
+        t.host_bytes = host + L.out_bytes(); t.host_ident = reinterpret_cast<uint32_t*>(host + L.out_ident());
+        t.src = reinterpret_cast<const uint32_t*>(b->results.p + L.fold_failed()); t.dst = reinterpret_cast<uint32_t*>(host + L.fold_failed());
+        t.n_words = (uint32_t)((L.total() - L.fold_failed()) / 4);
+        t.skip_lo = (uint32_t)((L.out_ident() - L.fold_failed()) / 4); t.skip_hi = (uint32_t)((L.status() - L.fold_failed()) / 4);   // (the converting workgroups write those)
+        if (t.count != 2 * G) { set_last_error("close_enqueue: the pieces are not this launch's"); return H2V_ERR_BAD_ARGUMENT; }
+        b->last.host_block = true;
+        return pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, false, &t);
+    }
+    if ((rc = need_aux(b))) return rc;
     H2V_HIP_CHECK(hipEventRecord(b->ev_fork, s));
     H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork, 0));
     // (beside the pairing: kept off the pairing workgroups' CUs by an LDS request, internal.h)
     if (b->split.parts && (rc = msm_combine_enqueue(b->aux, b->ws, b->split, H2V_AUX_LDS_RESERVE))) return rc;   // acc <- the whole points
     if ((rc = point_to_bytes_enqueue(b->aux, b->acc.p, b->out_bytes, b->out_ident, 2 * G, H2V_AUX_LDS_RESERVE))) return rc;
     // the result block (all but the verdicts, which the pairing kernel writes to the host itself) goes back on the auxiliary stream too, and the
-    // main stream does NOT wait for it: its last operation is the pairing kernel — the join (a barrier packet) and the copy behind it were
-    // 16 us at the end of every launch.  h2v_batch_finish waits for both streams; anything else that touches the batch first calls join_tail.
+    // main stream does NOT wait for it: its last operation is the pairing kernel.  h2v_batch_finish waits for both streams; anything else
+    // that touches the batch first calls join_tail.
     // (by a kernel, not hipMemcpyAsync: a copy enqueued now, behind kernels that end a launch later, can hold up an SDMA queue — util.hip)
-    const ResultsLayout L{G, b->n};
-    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), static_cast<uint8_t*>(b->results_host.dev) + L.fold_failed(), (L.total() - L.fold_failed()) / 4,
-                                 H2V_AUX_LDS_RESERVE))) return rc;
+    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), host + L.fold_failed(), (L.total() - L.fold_failed()) / 4, H2V_AUX_LDS_RESERVE))) return rc;
     H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
-    b->last.tail_on_aux = true;
-    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, b->ctx->tuning.pairing_one_stream != 0))) return rc; }
+    b->last.tail_on_aux = true; b->last.host_block = true;
+    if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, one_stream))) return rc; }
     else if ((rc = pairing_check_enqueue(s, b->ctx->pairing, b->acc.p, G, b->ok))) return rc;
     return 0;
 }
@@ -220,7 +258,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     if (!rand_tail) n_tail = n;
     if ((rc = resolve_draws(rand_tail, n_tail, os_rand, "h2v_batch_upload"))) return rc;
     // every argument is valid: from here on the batch takes the upload
-    if ((rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
+    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
     if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
     b->plan = pin.take(); b->n = (uint32_t)n;
     const PlanDevice* pd = b->plan;
@@ -232,8 +270,8 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
             for (size_t j = nt; j-- > 1;)
                 if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
     }
-    if ((rc = b->tail.reserve(32 * n_tail))) return rc;
-    b->n_tail = (uint32_t)n_tail;
+    if ((rc = b->tail.reserve(32 * n_tail)) || (rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
+    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false;
     hipStream_t s = b->stream;
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
         if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs.p + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
@@ -308,6 +346,8 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         if ((rc = decompress_finish_enqueue(s, g))) return rc;
     }
     b->decompressed = mode != 3;
+    // the batch multipliers depend on the draws alone: computed once per upload (the draws are on the device), kept by every launch of it
+    if (n) { if ((rc = multipliers_enqueue(s, b->tail.p, b->n_tail, (uint32_t)n, b->groups, b->mult.p, b->mult_tiles.p))) return rc; b->mult_of_draws = true; }
     commit.commit(BatchStage::Uploaded);
     return 0;
 }
@@ -330,8 +370,8 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     mark();
     StageArgs g{n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
     // stage 1: point decompression + canonicity checks (already on the stream, behind its chunked upload, after h2v_batch_upload_launch);
-    // stage 2: absorbed stream, Blake2b challenges, batch multipliers.  The status words are cleared first, then the auxiliary stream is
-    // forked: the scalar canonicity check (proof bytes only) runs there beside the decompression, with the multipliers
+    // stage 2: absorbed stream, Blake2b challenges.  Everything is enqueued on the batch's one stream: the scalar canonicity check reads a
+    // word per scalar, the multipliers are the upload's, the MSM's problem descriptors stay on the device from launch to launch
     const bool run_decompress = !(b->stage == BatchStage::Uploaded && b->decompressed);   // (a relaunch of the same upload runs it again)
     // cleared per launch: fold_failed (set by h2v_batch_fold_check_enqueue only) and — unless the upload already did (h2v_batch_upload_launch) —
     // the status words.  The results block is [ok][fold_failed][out_ident][out_bytes][status]: one fill from fold_failed to the last status word
@@ -339,28 +379,21 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     const ResultsLayout L{G, n};
     if (run_decompress && n) H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, L.total() - L.fold_failed(), s));
     else H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, 4 * (size_t)G, s));   // (its G words)
-    H2V_HIP_CHECK(hipEventRecord(b->ev_fork0, s));   // everything enqueued before this point (uploads, the cleared status words) is visible to the auxiliary stream
-    if (run_decompress && (rc = decompress_range_enqueue(s, g, 0, n))) return rc;
+    if (run_decompress && n && ((rc = decompress_finish_enqueue(s, g)) || (rc = decompress_range_enqueue(s, g, 0, n)))) return rc;   // k_check_scalars, k_decompress
     mark();
     if ((rc = transcript_stage_enqueue(s, g))) return rc;
     // both channels of every group in one set of launches: [2g] left, [2g+1] right (channel_problems), the group's folded VK-wide
-    // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: they go to the device on the auxiliary stream, beside the decompression (msm_prepare_problems below).
+    // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: msm_enqueue_multi sends them only when they differ from the workspace's.
     MsmProblems pr;
     for (uint32_t g = 0; g < G; ++g)
         channel_problems(pr, b, pl, (size_t)g * gs, gs, b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
     b->ws.tune = ctx->tuning;
-    // the batch multipliers depend only on the uploaded draws: they run on the auxiliary stream beside decompression and transcript
     if (n) {
-        H2V_HIP_CHECK(hipStreamWaitEvent(b->aux, b->ev_fork0, 0));
-        hipStream_t sm = b->aux;
-        if (run_decompress && (rc = decompress_finish_enqueue(sm, g))) return rc;   // k_check_scalars
-        if (ext_mult) { if ((rc = gather_multipliers_enqueue(sm, ext_mult, ext_idx, n, b->mult.p))) return rc; }
-        else if ((rc = multipliers_enqueue(sm, b->tail.p, b->n_tail, n, G, b->mult.p))) return rc;
+        // gathered multipliers replace the upload's; a launch on the draws after one on gathered multipliers computes the upload's again
+        if (ext_mult) { b->mult_of_draws = false; if ((rc = gather_multipliers_enqueue(s, ext_mult, ext_idx, n, b->mult.p))) return rc; }
+        else if (!b->mult_of_draws) { if ((rc = multipliers_enqueue(s, b->tail.p, b->n_tail, n, G, b->mult.p, b->mult_tiles.p))) return rc; b->mult_of_draws = true; }
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
-        if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, sm));
-        if ((rc = msm_prepare_problems(sm, b->ws, pr))) return rc;   // (5 us of launch + kernel boundary that the main stream's chain no longer carries)
-        H2V_HIP_CHECK(hipEventRecord(b->ev_join0, sm));
-        H2V_HIP_CHECK(hipStreamWaitEvent(s, b->ev_join0, 0));   // joined before the Fr program reads them
+        if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, s));
     }
     mark();
     FrvmArgs a{pd->code.p, (uint32_t)pl.code.size(), pd->consts.p, b->slots.p, n, b->proofs.p, pl.proof_len, pd->scalar_offsets.p, b->inst.p, pl.n_instance_values,
@@ -423,11 +456,12 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     { int rcw = ensure_whole(b); if (rcw) return rcw; }
     const ResultsLayout L{G, n};
     hipError_t e;
-    if (b->last.tail_on_aux) {
-        // a launch that ended in its own pairing checks: the block is on its way on the auxiliary stream, the verdicts come from the kernel
-        b->last.tail_on_aux = false;
+    if (b->last.host_block) {
+        // a launch that ended in its own pairing checks: the block travels by the launch's own kernels (the pairing launch's tail workgroups,
+        // or the auxiliary stream), the verdicts come from the pairing kernel
         e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->aux);   // (not hipEventSynchronize on its last event: that wait goes through the runtime's event thread, and a host that re-uploads per launch lost 40 % to it)
+        if (e == hipSuccess && b->last.tail_on_aux) e = hipStreamSynchronize(b->aux);
+        b->last.tail_on_aux = false;   // (not hipEventSynchronize on its last event: that wait goes through the runtime's event thread, and a host that re-uploads per launch lost 40 % to it)
     } else {
         H2V_HIP_CHECK(hipMemcpyAsync(b->results_host.p + L.fold_failed(), b->results.p + L.fold_failed(), L.total() - L.fold_failed(), hipMemcpyDeviceToHost, s));
         e = hipStreamSynchronize(s);
@@ -521,7 +555,7 @@ int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, s
     // their buffers (a finished batch's normally are: only a fold after the finish leaves work behind)
     if ((rc = join_tail(host))) return rc;
     for (size_t k = 1; k < n_batches; ++k)
-        if (batches[k] != host) { H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->stream)); H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->aux)); }
+        if (batches[k] != host) { H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->stream)); if (batches[k]->aux) H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->aux)); }
     hipStream_t s = host->stream;
     Recheck& rk = host->recheck;
     const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;
@@ -630,13 +664,8 @@ int h2v_batch_create(h2v_ctx* ctx, size_t max_proofs, size_t max_instance_values
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     h2v_batch* b = new h2v_batch();
     b->ctx = ctx; b->max_proofs = max_proofs; b->max_inst = max_instance_values_per_proof;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&b->aux, hipStreamNonBlocking) != hipSuccess) {
-        if (b->stream) hipStreamDestroy(b->stream);
-        delete b; set_last_error("hipStreamCreate failed"); return H2V_ERR_DEVICE;
-    }
+    // (no stream yet: need_stream, need_aux)
     for (int i = 0; i < 8; ++i) hipEventCreate(&b->ev[i]);
-    hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming); hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->ev_fork0, hipEventDisableTiming); hipEventCreateWithFlags(&b->ev_join0, hipEventDisableTiming);
     *out = b;
     return 0;
 }
@@ -644,7 +673,7 @@ int h2v_batch_create(h2v_ctx* ctx, size_t max_proofs, size_t max_instance_values
 void h2v_batch_destroy(h2v_batch* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
-    if (b->stream) hipStreamSynchronize(b->stream);
+    if (b->stream || !b->owns_stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
     for (int i = 0; i < 8; ++i) if (b->ev[i]) hipEventDestroy(b->ev[i]);
@@ -653,8 +682,6 @@ void h2v_batch_destroy(h2v_batch* b) {
 
     if (b->ev_fork) hipEventDestroy(b->ev_fork);
     if (b->ev_join) hipEventDestroy(b->ev_join);
-    if (b->ev_fork0) hipEventDestroy(b->ev_fork0);
-    if (b->ev_join0) hipEventDestroy(b->ev_join0);
     if (b->stream && b->owns_stream) hipStreamDestroy(b->stream);
     delete b;   // (frees the buffers)
 }
@@ -692,11 +719,11 @@ int h2v_batch_accumulators(h2v_batch* b, void** device_ptr, size_t* nbytes) {
     if (nbytes) *nbytes = 2 * sizeof(G1J) * b->groups;   // raw points, no failure word: see h2v_batch_export_accumulators
     return 0;
 }
-void* h2v_batch_stream(h2v_batch* b) { return b ? (void*)b->stream : nullptr; }
+void* h2v_batch_stream(h2v_batch* b) { return b && !need_stream(b) ? (void*)b->stream : nullptr; }
 int h2v_batch_set_stream(h2v_batch* b, void* hip_stream) {
     if (!b) return H2V_ERR_BAD_ARGUMENT;
     hipSetDevice(b->ctx->device);
-    if (b->stream) hipStreamSynchronize(b->stream);
+    if (b->stream || !b->owns_stream) hipStreamSynchronize(b->stream);
     if (b->owns_stream && b->stream) hipStreamDestroy(b->stream);
     b->stream = (hipStream_t)hip_stream; b->owns_stream = false;
     return join_tail(b);   // (the new stream waits for what the last launch left on the auxiliary stream)

@@ -259,4 +259,50 @@ H2V_FN bool g1_decompress(const uint8_t in[32], G1A& out) {
     return true;
 }
 
+// ---- Horner over points by a quad of lanes (msm.hip: msm_final; pairing.hip: the tail workgroups of k_pairing2) — device only
+template <int S> __device__ __forceinline__ Fq quad_bcast(const Fq& v) {
+    Fq r;
+#pragma unroll
+    for (int l = 0; l < H2V_LIMBS; ++l) r.v[l] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.v[l], S * 0x55, 0xf, 0xf, true);   // quad_perm [S,S,S,S]
+    return r;
+}
+__device__ __forceinline__ Fq fq_sel(bool c, const Fq& a, const Fq& b) {
+    Fq r;
+#pragma unroll
+    for (int l = 0; l < H2V_LIMBS; ++l) r.v[l] = c ? a.v[l] : b.v[l];
+    return r;
+}
+__device__ __forceinline__ void g1_dbl_quad(G1J& p, uint32_t r) {
+    // g1_dbl_inl's formulas (curve.hip.h: lazy linear forms, D = 4 X B as a product, X3 through one carry sweep, Y3 one dot2), the
+    // products of a level on different lanes.  The identity (Z = 0) stays the identity: Z3 = (2Y) Z.
+    // level 1   lane 0: A = X^2   lane 1: B = Y^2   lanes 2, 3: Z3 = (2Y) Z
+    const Fq Y2 = Fq::lazy_dbl(p.Y);
+    const Fq p1 = Fq::mul_inl(fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, Y2)), fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, p.Z)));
+    const Fq A = quad_bcast<0>(p1), B = quad_bcast<1>(p1), Z3 = quad_bcast<2>(p1);
+    // level 2   lane 0: C = B^2   lane 1: X B   lane 2: E^2, E = 3A   (lane 3: E B, unused)
+    const Fq E = Fq::lazy_add2(A, A);
+    const Fq p2 = Fq::mul_inl(fq_sel(r == 0, B, fq_sel(r == 1, p.X, E)), fq_sel(r == 2, E, B));
+    const Fq C = quad_bcast<0>(p2), XB = quad_bcast<1>(p2), F = quad_bcast<2>(p2);
+    // level 3   every lane: X3 = E^2 - 8 X B, Y3 = E (4 X B - X3) - 8 C
+    const Fq D = Fq::lazy_dbl(Fq::lazy_dbl(XB));
+    int64_t acc[9];
+#pragma unroll
+    for (int l = 0; l < 9; ++l) acc[l] = (int64_t)F.v[l] + (int64_t)Fq::KP29(9, l) - 2 * (int64_t)D.v[l];
+    p.X = Fq::from_wide(acc);
+    p.Y = Fq::dot2_inl(E, Fq::lazy_sub(D, p.X), C, g1_minus_eight());
+    p.Z = Z3;
+}
+// Horner over the points src[0 .. items) (src[i] weighs 2^(dbl * i)) by the quad that lane r belongs to
+// (Slot: a padded point, `.p` the G1J — internal.h G1JSlot)
+template <class Slot> __device__ __forceinline__ G1J msm_horner_quad(const Slot* __restrict__ src, uint32_t items, uint32_t dbl, uint32_t r) {
+    G1J acc = src[items - 1].p;
+    for (int w = (int)items - 2; w >= 0; --w) {
+        const G1J cur = src[w].p;   // in flight during the doublings
+#pragma unroll 1
+        for (uint32_t i = 0; i < dbl; ++i) g1_dbl_quad(acc, r);
+        acc = g1_add_inl(acc, cur);
+    }
+    return acc;
+}
+
 }  // namespace h2v

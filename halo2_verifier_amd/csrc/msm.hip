@@ -135,7 +135,7 @@ int MsmWorkspace::reserve(uint32_t max_terms, uint32_t max_problems, uint32_t ma
     if (covers(max_terms, max_problems, max_per_problem)) return 0;
     max_terms = std::max(max_terms, cap_terms); max_problems = std::max(max_problems, cap_parents); max_per_problem = std::max(max_per_problem, cap_per_problem);
     cap_terms = cap_parents = cap_per_problem = 0;   // (covers nothing until every buffer below is in place)
-    prepared.clear(); final_problems = nullptr; profile_recorded = false;
+    resident.clear(); final_problems = nullptr; profile_recorded = false;
     const uint32_t subs = msm_subproblems(max_per_problem);
     cap_problems = (uint32_t)std::min<size_t>((size_t)max_problems * subs, MSM_MAX_PROBLEMS);
     if (cap_problems < max_problems) cap_problems = max_problems;
@@ -895,49 +895,7 @@ __global__ void __launch_bounds__(MSM_WIN_THREADS) msm_window(const G1JSlot* __r
 //   level 3   every lane: X3 (a carry sweep), Y3 = E (D - X3) - 8C (one dot2)
 // three products deep instead of seven, values exchanged by DPP quad broadcasts (no LDS).  X, Y, Z are replicated in the four
 // lanes; the one addition per window is done redundantly by all of them (nothing to exchange).
-template <int S> __device__ __forceinline__ Fq quad_bcast(const Fq& v) {
-    Fq r;
-#pragma unroll
-    for (int l = 0; l < H2V_LIMBS; ++l) r.v[l] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.v[l], S * 0x55, 0xf, 0xf, true);   // quad_perm [S,S,S,S]
-    return r;
-}
-__device__ __forceinline__ Fq fq_sel(bool c, const Fq& a, const Fq& b) {
-    Fq r;
-#pragma unroll
-    for (int l = 0; l < H2V_LIMBS; ++l) r.v[l] = c ? a.v[l] : b.v[l];
-    return r;
-}
-__device__ __forceinline__ void g1_dbl_quad(G1J& p, uint32_t r) {
-    // g1_dbl_inl's formulas (curve.hip.h: lazy linear forms, D = 4 X B as a product, X3 through one carry sweep, Y3 one dot2), the
-    // products of a level on different lanes.  The identity (Z = 0) stays the identity: Z3 = (2Y) Z.
-    // level 1   lane 0: A = X^2   lane 1: B = Y^2   lanes 2, 3: Z3 = (2Y) Z
-    const Fq Y2 = Fq::lazy_dbl(p.Y);
-    const Fq p1 = Fq::mul_inl(fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, Y2)), fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, p.Z)));
-    const Fq A = quad_bcast<0>(p1), B = quad_bcast<1>(p1), Z3 = quad_bcast<2>(p1);
-    // level 2   lane 0: C = B^2   lane 1: X B   lane 2: E^2, E = 3A   (lane 3: E B, unused)
-    const Fq E = Fq::lazy_add2(A, A);
-    const Fq p2 = Fq::mul_inl(fq_sel(r == 0, B, fq_sel(r == 1, p.X, E)), fq_sel(r == 2, E, B));
-    const Fq C = quad_bcast<0>(p2), XB = quad_bcast<1>(p2), F = quad_bcast<2>(p2);
-    // level 3   every lane: X3 = E^2 - 8 X B, Y3 = E (4 X B - X3) - 8 C
-    const Fq D = Fq::lazy_dbl(Fq::lazy_dbl(XB));
-    int64_t acc[9];
-#pragma unroll
-    for (int l = 0; l < 9; ++l) acc[l] = (int64_t)F.v[l] + (int64_t)Fq::KP29(9, l) - 2 * (int64_t)D.v[l];
-    p.X = Fq::from_wide(acc);
-    p.Y = Fq::dot2_inl(E, Fq::lazy_sub(D, p.X), C, g1_minus_eight());
-    p.Z = Z3;
-}
-// Horner over the points src[0 .. items) (src[i] weighs 2^(dbl * i)) by the quad that lane r belongs to
-__device__ __forceinline__ G1J msm_horner_quad(const G1JSlot* __restrict__ src, uint32_t items, uint32_t dbl, uint32_t r) {
-    G1J acc = src[items - 1].p;
-    for (int w = (int)items - 2; w >= 0; --w) {
-        const G1J cur = src[w].p;   // in flight during the doublings
-#pragma unroll 1
-        for (uint32_t i = 0; i < dbl; ++i) g1_dbl_quad(acc, r);
-        acc = g1_add_inl(acc, cur);
-    }
-    return acc;
-}
+// (quad_bcast, g1_dbl_quad and msm_horner_quad live in curve.hip.h: the pairing launch's tail workgroups run the same Horner, pairing.hip)
 __global__ void __launch_bounds__(64) msm_final(const G1JSlot* __restrict__ window_sums, const MsmProblem* __restrict__ prs, uint32_t count, MsmPlan p) {
     __builtin_amdgcn_s_setprio(3);   // a latency chain: its waves win the issue arbitration over the throughput kernels of other launches in flight
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, q = t >> 2, r = t & 3u;
@@ -1065,23 +1023,9 @@ static bool msm_same_problems(const std::vector<MsmProblem>& a, const std::vecto
     }
     return true;
 }
-// The problem descriptors depend on addresses and sizes only: a caller that knows them before the scalars exist (the batch verifier,
-// while the Fr program still runs) hands them to the device early — on the stream of the MSM in front of the kernel that produces the
-// scalars, or on a stream that is joined into it before the MSM (the batch verifier's auxiliary stream, beside the decompression) — and
-// msm_enqueue_multi finds them there (two 5 us launches and a kernel boundary off the chain behind the Fr program).
-int msm_prepare_problems(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr) {
-    ws.prepared.clear();
-    if (pr.p.empty()) return 0;
-    MsmLaunchShape L;
-    int rc = msm_shape(ws, pr, L);
-    if (rc) return rc;
-    if (L.cut) msm_upload_problems(s, L.parents_p, false, ws.parents.p);
-    msm_upload_problems(s, L.launch_p, true, ws.problems.p);
-    H2V_HIP_CHECK(hipGetLastError());
-    ws.prepared = pr.p;
-    return 0;
-}
-
+// The problem descriptors depend on addresses and sizes only (and on how large problems are cut): a workspace keeps the ones of its last
+// launch on the device, and a launch over the same problems — a batch launched again on resident inputs — sends none (two 5 us
+// launches and their kernel boundaries off the chain in front of the sort).  Nothing but msm_set_problems writes them.
 int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, MsmSplit* split) {
     if (split) { split->parts = 0; split->shift = 0; split->count = 0; split->pts = nullptr; split->ready = nullptr; }
     const uint32_t n_callers = (uint32_t)pr.p.size();
@@ -1091,11 +1035,11 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     const bool cut = L.cut;
     uint32_t nmax = L.nmax; const size_t total = L.total, total_nz = L.total_nz;
     const std::vector<MsmProblem>& launch_p = L.launch_p;
-    const bool uploaded = msm_same_problems(ws.prepared, pr.p);   // msm_prepare_problems, earlier in stream order
-    ws.prepared.clear();
+    const bool uploaded = !ws.resident.empty() && ws.resident_no_split == ws.tune.msm_no_term_split && msm_same_problems(ws.resident, pr.p);
     if (!uploaded) {
         if (cut) msm_upload_problems(s, L.parents_p, false, ws.parents.p);
         msm_upload_problems(s, launch_p, true, ws.problems.p);
+        ws.resident = pr.p; ws.resident_no_split = ws.tune.msm_no_term_split;
     }
     const uint32_t count = (uint32_t)launch_p.size();
     ws.final_problems = cut ? ws.parents.p : ws.problems.p;

@@ -261,11 +261,11 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         idx32.insert(idx32.end(), groups[gi].idx.begin(), groups[gi].idx.end());
     }
     // whole-sequence multipliers on the folding context's stream
-    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
-    if ((rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
+    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult, d_tiles; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
+    if ((rc = d_tiles.alloc(multipliers_scratch((uint32_t)n, 1))) || (rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
     H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
     H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-    if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p))) return rc;
+    if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p, d_tiles.p))) return rc;
     H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
     // one batch object per key serves every shape group of that key (its buffers grow to the largest group's plan: ensure_buffers)
     for (auto& kv : of_key) {
@@ -292,7 +292,7 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
     // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
     struct Drain {
         std::vector<h2v_batch*> bs;
-        ~Drain() { for (h2v_batch* b : bs) { hipStreamSynchronize(b->stream); hipStreamSynchronize(b->aux); } }
+        ~Drain() { for (h2v_batch* b : bs) { if (b->stream) hipStreamSynchronize(b->stream); if (b->aux) hipStreamSynchronize(b->aux); } }
     } drain;
     drain.bs = on;
     bool all_ok = true;

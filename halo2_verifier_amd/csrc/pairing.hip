@@ -446,12 +446,50 @@ struct alignas(16) PairShared2 {
 };
 static_assert(sizeof(PairShared2) <= 64 * 1024, "k_pairing2's static LDS");
 static_assert(sizeof(PairShared2) + H2V_AUX_LDS_RESERVE > 160 * 1024, "the auxiliary-stream kernels' LDS request must not fit beside a k_pairing2 workgroup (internal.h)");
+// The tail workgroups of a k_pairing2 launch (PairTail; block b of them, 2 * PAIR_THREADS threads).  The first ceil(count / 64) convert:
+// a quad of lanes per point puts the pieces together (msm_horner_quad, ~250 dependent doublings), its first lane writes the whole
+// point, inverts Z and writes the affine bytes to the device block and to the host block — every dependency stays inside one quad.
+// The others copy the rest of the result block (final before the launch starts) to the host, PAIR_TAIL_COPY_WORDS words per thread.
+#define PAIR_TAIL_COPY_WORDS 8u
+static uint32_t pair_tail_blocks(const PairTail& tl) {
+    return (tl.count + 2 * PAIR_THREADS / 4 - 1) / (2 * PAIR_THREADS / 4) + (tl.n_words + 2 * PAIR_THREADS * PAIR_TAIL_COPY_WORDS - 1) / (2 * PAIR_THREADS * PAIR_TAIL_COPY_WORDS);
+}
+__device__ __forceinline__ void pair_tail_role(const PairTail& tl, uint32_t b, uint32_t t) {
+    const uint32_t conv_blocks = (tl.count + 2 * PAIR_THREADS / 4 - 1) / (2 * PAIR_THREADS / 4);
+    if (b < conv_blocks) {
+        const uint32_t q = b * (2 * PAIR_THREADS / 4) + (t >> 2), r = t & 3u;
+        if (q >= tl.count) return;   // whole quads
+        const G1J acc = msm_horner_quad(tl.pieces + (size_t)q * tl.parts, tl.parts, tl.shift, r);
+        if (r != 0) return;
+        *tl.prs[q].out = acc;
+        const G1A a = g1_to_affine(acc);
+        uint32_t w[16];
+        const bool ident = a.is_identity();
+        if (ident) { for (int j = 0; j < 16; ++j) w[j] = 0; }
+        else {
+            uint8_t tmp[64];
+            a.x.to_bytes(tmp); a.y.to_bytes(tmp + 32);
+            for (int j = 0; j < 16; ++j) w[j] = (uint32_t)tmp[4 * j] | ((uint32_t)tmp[4 * j + 1] << 8) | ((uint32_t)tmp[4 * j + 2] << 16) | ((uint32_t)tmp[4 * j + 3] << 24);
+        }
+        uint32_t* d0 = reinterpret_cast<uint32_t*>(tl.out_bytes + 64 * (size_t)q);   // (the blocks are 16-byte aligned, the points 64 bytes apart)
+        uint32_t* d1 = reinterpret_cast<uint32_t*>(tl.host_bytes + 64 * (size_t)q);
+        for (int j = 0; j < 16; ++j) { d0[j] = w[j]; d1[j] = w[j]; }
+        tl.out_ident[q] = ident ? 1u : 0u; tl.host_ident[q] = ident ? 1u : 0u;
+        return;
+    }
+    const uint32_t first = ((b - conv_blocks) * 2 * PAIR_THREADS) * PAIR_TAIL_COPY_WORDS + t;
+#pragma unroll
+    for (uint32_t k = 0; k < PAIR_TAIL_COPY_WORDS; ++k) {
+        const uint32_t i = first + k * 2 * PAIR_THREADS;
+        if (i < tl.n_words && (i < tl.skip_lo || i >= tl.skip_hi)) tl.dst[i] = tl.src[i];
+    }
+}
 __global__ void __launch_bounds__(2 * PAIR_THREADS, 1) k_pairing2(uint32_t n, const PairingConsts* __restrict__ consts, const uint2* __restrict__ prog, uint32_t n_steps,
-                                                               const Fq2* __restrict__ pre, uint32_t* __restrict__ ok) {
+                                                               const Fq2* __restrict__ pre, uint32_t* __restrict__ ok, PairTail tail) {
     __builtin_amdgcn_s_setprio(3);
     __shared__ PairShared2 s;
     const uint32_t chk = blockIdx.x, t = threadIdx.x, g = t / PAIR_THREADS, tl = t % PAIR_THREADS;
-    if (chk >= n) return;
+    if (chk >= n) { pair_tail_role(tail, chk - n, t); return; }   // (the launch has blocks beyond n only when it carries a tail)
     {
         const uint4* src = reinterpret_cast<const uint4*>(pre + (size_t)chk * PAIR_ITERS * 6);
         uint4* dst = reinterpret_cast<uint4*>(&s.line[0][0]);
@@ -665,7 +703,10 @@ int pairing_check_enqueue(hipStream_t s, const PairingDevice& pd, const G1J* d_p
     return 0;
 }
 
-int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot* d_ready, uint32_t n, uint32_t parts, uint32_t shift, void* d_line_ws, uint32_t* d_ok, bool one_stream) {
+bool pairing_tail_fits(const PairingDevice& pd, bool one_stream) { return pd.prog2.p && !one_stream; }
+int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot* d_ready, uint32_t n, uint32_t parts, uint32_t shift, void* d_line_ws, uint32_t* d_ok, bool one_stream,
+                                const PairTail* tail) {
+    if (tail && (!n || !pairing_tail_fits(pd, one_stream))) { set_last_error("pairing: this launch cannot carry a tail"); return H2V_ERR_BAD_ARGUMENT; }
     if (!n) return 0;
     if (!pd.prog_merged.p || pd.n_ops_merged > PAIR_MAX_OPS) { set_last_error("pairing: operation table missing or too long"); return H2V_ERR_BAD_ARGUMENT; }
     if (!parts || parts > PL_MAX_PARTS || !d_line_ws) { set_last_error("pairing: bad split"); return H2V_ERR_BAD_ARGUMENT; }
@@ -675,7 +716,9 @@ int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot*
     Fq2* lines = reinterpret_cast<Fq2*>(d_line_ws);
     hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, s, d_ready, parts, tab, pair_iterations(), lines);
     // (one_stream: h2v_tuning.pairing_one_stream — the single-stream table over the same lines)
-    if (pd.prog2.p && !one_stream) hipLaunchKernelGGL(k_pairing2, dim3(n), dim3(2 * PAIR_THREADS), 0, s, n, pd.consts.p, reinterpret_cast<const uint2*>(pd.prog2.p), pd.n_steps2, (const Fq2*)lines, d_ok);
+    if (pd.prog2.p && !one_stream)
+        hipLaunchKernelGGL(k_pairing2, dim3(n + (tail ? pair_tail_blocks(*tail) : 0u)), dim3(2 * PAIR_THREADS), 0, s, n, pd.consts.p, reinterpret_cast<const uint2*>(pd.prog2.p), pd.n_steps2,
+                           (const Fq2*)lines, d_ok, tail ? *tail : PairTail{});
     else {
         if ((rc = pair1_lds_grant())) return rc;
         hipLaunchKernelGGL(k_pairing, dim3(n), dim3(PAIR_THREADS), sizeof(PairShared1), s, (const G1J*)nullptr, n, pd.l_sg2.p, pd.l_ng2.p, pd.consts.p, pd.prog_merged.p, pd.n_ops_merged, (const Fq2*)lines, d_ok);

@@ -49,6 +49,18 @@ int split_line_rows(const G2A& sg2, const G2A& ng2, uint32_t shift, uint32_t par
 int pairing_check_enqueue(hipStream_t s, const PairingDevice& pd, const G1J* d_pairs, uint32_t n, uint32_t* d_ok);
 // check g over split accumulators: left = sum_j 2^(shift j) piece[(2 g) parts + j], right likewise at 2 g + 1 (MsmSplit), the
 // pieces given line-ready as (X Z, Y, Z^3); d_line_ws: n * H2V_PAIRING_LINE_WS_BYTES of device scratch owned by the caller
-int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot* d_ready, uint32_t n, uint32_t parts, uint32_t shift, void* d_line_ws, uint32_t* d_ok, bool one_stream = false);
+// `tail` (k_pairing2 only, see pairing_tail_fits): the work that only READS what the checks read — the whole accumulators, their affine
+// bytes, the result block's way to the host — done by extra workgroups of the pairing launch itself, behind the checks' workgroups in
+// block order, instead of by kernels on a second stream beside it
+struct PairTail {
+    const G1JSlot* pieces; const MsmProblem* prs; uint32_t count, parts, shift;   // *prs[q].out <- sum_j 2^(shift j) pieces[q parts + j], q < count
+    uint8_t* out_bytes; uint32_t* out_ident;      // [count][64], [count]: the affine bytes of those points, in the device block ...
+    uint8_t* host_bytes; uint32_t* host_ident;    // ... and in the mapped host block
+    const uint32_t* src; uint32_t* dst;           // words [0, n_words) of src -> dst (mapped host memory), except [skip_lo, skip_hi)
+    uint32_t n_words, skip_lo, skip_hi;
+};
+bool pairing_tail_fits(const PairingDevice& pd, bool one_stream);   // the launch pairing_check_split_enqueue makes can carry a tail
+int pairing_check_split_enqueue(hipStream_t s, PairingDevice& pd, const G1JSlot* d_ready, uint32_t n, uint32_t parts, uint32_t shift, void* d_line_ws, uint32_t* d_ok, bool one_stream = false,
+                                const PairTail* tail = nullptr);
 
 }  // namespace h2v

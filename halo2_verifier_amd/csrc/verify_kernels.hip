@@ -5,7 +5,7 @@
 //   k_check_scalars   one lane per (proof, scalar)  Fr::from_repr canonicity           transcript/mod.rs:168-176
 //   k_stream_build    one lane per (proof, 8-byte word of the absorbed stream)         transcript/mod.rs:216-231
 //   k_transcript      four lanes per proof          Blake2b-512 + challenges           transcript/mod.rs:124-133,209-214,500-514
-//   k_multipliers     one workgroup                 suffix products of the batch draws kzg/strategy.rs:129, msm.rs:173-176
+//   k_mult_tiles ...  a two-level scan              suffix products of the batch draws kzg/strategy.rs:129, msm.rs:173-176
 //   k_instance_eval   one workgroup per proof       Lagrange sum over a wide instance column   lib.rs:173-218, poly/domain.rs:187-212
 //   k_frvm            one lane per proof            the compiled Fr program            lib.rs:173-346, shplonk.rs:202-264
 //   k_fold_shared     one workgroup per shared base sum over proofs of the scalars of VK-wide bases
@@ -100,6 +100,12 @@ __global__ void __launch_bounds__(256) k_check_scalars(const uint8_t* __restrict
     if (t >= n * per) return;
     uint32_t p = t / per, i = t % per;
     const uint8_t* b = i < ns ? proofs + (size_t)p * proof_len + scalar_offsets[i] : inst + ((size_t)p * ninst + (i - ns)) * 32;
+    // The top word decides for all but 2^-32 of the values: below r's top word the scalar is canonical whatever the rest holds.  One
+    // aligned word per lane instead of 32 byte loads: the kernel was 283 us of byte loads per 20-step launch, and it now sits on the
+    // launch's own stream in front of the decompression instead of on a second stream beside it.
+    const uint32_t top = ((uintptr_t)b & 3u) == 0 ? *reinterpret_cast<const uint32_t*>(b + 28)
+                                                  : (uint32_t)b[28] | ((uint32_t)b[29] << 8) | ((uint32_t)b[30] << 16) | ((uint32_t)b[31] << 24);
+    if (top < FrParams::P(7)) return;
     uint32_t raw[8];
     for (int j = 0; j < 8; ++j) raw[j] = (uint32_t)b[4 * j] | ((uint32_t)b[4 * j + 1] << 8) | ((uint32_t)b[4 * j + 2] << 16) | ((uint32_t)b[4 * j + 3] << 24);
     // a non-canonical public input cannot be represented as an Fr on the reference side at all: bad argument for that proof
@@ -390,31 +396,53 @@ __global__ void __launch_bounds__(64) k_transcript_keccak(const unsigned long lo
     }
 }
 
-// mult[p] = prod_{j > first+p} r_j over the tail of draws; tail[0] is the draw of this shard's proof 0.
-// One workgroup per group of a grouped batch (blockIdx.x = group; n_tail and n are per group).
-__global__ void __launch_bounds__(1024) k_multipliers(const uint8_t* __restrict__ tail, uint32_t n_tail, uint32_t n, Fr* __restrict__ mult) {
-    __shared__ Fr part[1024];
-    uint32_t t = threadIdx.x;
-    tail += (size_t)blockIdx.x * n_tail * 32; mult += (size_t)blockIdx.x * n;
-    uint32_t chunk = (n_tail + 1023) / 1024;
-    uint32_t lo = min(n_tail, t * chunk), hi = min(n_tail, lo + chunk);
-    Fr prod = Fr::one();
-    for (uint32_t j = lo; j < hi; ++j) { Fr r; Fr::from_bytes(tail + 32 * (size_t)j, r); prod = prod * r; }
-    part[t] = prod;
+// mult[p] = prod_{j > first+p} r_j over the tail of draws; tail[0] is the draw of this shard's proof 0.  Per group of a grouped batch
+// (blockIdx.y = group; n_tail and n are per group), as a two-level suffix scan over tiles of MULT_TILE draws:
+//   k_mult_tiles       a workgroup per tile: mult[j] <- the product of the LATER draws of j's own tile, tile_prod[tile] <- the tile's product
+//   k_mult_scan_tiles  a workgroup per group: tile_prod[tile] <- the product of all LATER tiles (chunks of 1024 tiles, last chunk first)
+//   k_mult_apply       mult[j] <- mult[j] * tile_prod[j's tile]
+// (One 1024-thread workgroup per group walked its draws in 1024 serial chunks: 210 us for a 20-step launch.  The multipliers depend on
+// the uploaded draws alone, so they are computed once per upload, not per launch: upload_impl.)
+#define MULT_TILE 256u
+// part[t] <- prod_{t' >= t} part[t'] over the workgroup's T values (T a power of two); every thread calls it
+template <uint32_t T> __device__ __forceinline__ void fr_suffix_scan(Fr* part, uint32_t t) {
     __syncthreads();
-    // inclusive suffix scan: part[t] = prod_{t' >= t} P_t'
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        Fr v = t + d < 1024 ? part[t + d] : Fr::one();
+    for (uint32_t d = 1; d < T; d <<= 1) {
+        const Fr v = t + d < T ? part[t + d] : Fr::one();
         __syncthreads();
         part[t] = part[t] * v;
         __syncthreads();
     }
-    Fr run = t + 1 < 1024 ? part[t + 1] : Fr::one();  // product of everything after this lane's chunk
-    for (uint32_t j = hi; j > lo; --j) {
-        if (j - 1 < n) mult[j - 1] = run;
-        Fr r; Fr::from_bytes(tail + 32 * (size_t)(j - 1), r);
-        run = run * r;
+}
+__global__ void __launch_bounds__(MULT_TILE) k_mult_tiles(const uint8_t* __restrict__ tail, uint32_t n_tail, uint32_t n, uint32_t tiles, Fr* __restrict__ mult, Fr* __restrict__ tile_prod) {
+    __shared__ Fr part[MULT_TILE];
+    const uint32_t t = threadIdx.x, g = blockIdx.y, j = blockIdx.x * MULT_TILE + t;
+    Fr r = Fr::one();
+    if (j < n_tail) Fr::from_bytes(tail + 32 * ((size_t)g * n_tail + j), r);
+    part[t] = r;
+    fr_suffix_scan<MULT_TILE>(part, t);
+    if (j < n) mult[(size_t)g * n + j] = t + 1 < MULT_TILE ? part[t + 1] : Fr::one();
+    if (t == 0) tile_prod[(size_t)g * tiles + blockIdx.x] = part[0];
+}
+__global__ void __launch_bounds__(1024) k_mult_scan_tiles(Fr* __restrict__ tile_prod, uint32_t tiles) {
+    __shared__ Fr part[1024];
+    const uint32_t t = threadIdx.x;
+    tile_prod += (size_t)blockIdx.x * tiles;
+    Fr carry = Fr::one();   // the product of every tile behind the chunk
+    for (uint32_t hi = tiles; hi > 0; hi = hi > 1024 ? hi - 1024 : 0) {
+        const uint32_t lo = hi > 1024 ? hi - 1024 : 0, i = lo + t;
+        part[t] = i < hi ? tile_prod[i] : Fr::one();
+        fr_suffix_scan<1024>(part, t);
+        const Fr later = (t + 1 < 1024 ? part[t + 1] : Fr::one()) * carry;
+        const Fr all = part[0] * carry;
+        __syncthreads();   // (part is written again in the next round)
+        if (i < hi) tile_prod[i] = later;
+        carry = all;
     }
+}
+__global__ void __launch_bounds__(MULT_TILE) k_mult_apply(Fr* __restrict__ mult, uint32_t n, uint32_t tiles, const Fr* __restrict__ tile_prod) {
+    const uint32_t g = blockIdx.y, j = blockIdx.x * MULT_TILE + threadIdx.x;
+    if (j < n && blockIdx.x + 1 < tiles) mult[(size_t)g * n + j] = mult[(size_t)g * n + j] * tile_prod[(size_t)g * tiles + blockIdx.x];
 }
 
 // Instance evaluation for wide instance vectors (lib.rs:173-218; l_i_range, poly/domain.rs:187-212):
@@ -713,8 +741,16 @@ int transcript_stage_enqueue(hipStream_t s, const StageArgs& g) {
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult) {
-    hipLaunchKernelGGL(k_multipliers, dim3(groups), dim3(1024), 0, s, d_tail, n_tail / groups, n / groups, d_mult);
+size_t multipliers_scratch(uint32_t n_tail, uint32_t groups) { return (size_t)groups * ((n_tail / groups + MULT_TILE - 1) / MULT_TILE); }
+int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult, Fr* d_scratch) {
+    const uint32_t nt = n_tail / groups, ng = n / groups, tiles = (nt + MULT_TILE - 1) / MULT_TILE;
+    if (!tiles || !ng) return 0;
+    if (tiles > 65535u * 1024u || groups > 65535u) { set_last_error("multipliers: too many draws or groups"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_mult_tiles, dim3(tiles, groups), dim3(MULT_TILE), 0, s, d_tail, nt, ng, tiles, d_mult, d_scratch);
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_mult_scan_tiles, dim3(groups), dim3(1024), 0, s, d_scratch, tiles);
+        hipLaunchKernelGGL(k_mult_apply, dim3((ng + MULT_TILE - 1) / MULT_TILE, groups), dim3(MULT_TILE), 0, s, d_mult, ng, tiles, (const Fr*)d_scratch);
+    }
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,93 @@
+"""The batch multipliers (csrc/verify_kernels.hip: a two-level suffix scan over many workgroups, k_mult_tiles / k_mult_scan_tiles /
+k_mult_apply behind multipliers_enqueue) against Python big integers: mult[g][p] = the product of the draws of the LATER proofs of
+p's own group, mod r (kzg/strategy.rs:129, msm.rs:173-176).  build/multipliers_units (tests/cpp/multipliers_units.hip, built by
+csrc/Makefile with the library's flags) runs the library's own kernels on raw draws chosen here: n = 1, 2, 63, 64, 65, 1024 and 8192
+proofs per group in 1, 4 and 32 groups, with a zero draw inside a group (it zeroes the multipliers of the group's earlier proofs and
+of no other group: the proofs h2v_batch_recheck refuses ranges over), and a shard's form (more draws than proofs: the tail of the
+whole batch).  The values are compared exactly, as canonical residues."""
+import os
+import random
+import struct
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "multipliers_units")
+R = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
+SIZES = [1, 2, 63, 64, 65, 1024, 8192]
+GROUPS = [1, 4, 32]
+
+
+def _expected(draws, n):
+    """draws: one group's tail -> the multipliers of its first n proofs"""
+    out, run = [0] * len(draws), 1
+    for j in range(len(draws) - 1, -1, -1):
+        out[j] = run
+        run = run * draws[j] % R
+    return out[:n]
+
+
+def _run(jobs, tmp_path):
+    """jobs: [(groups, n_tail, n, draws[groups][n_tail])] -> per job the multipliers [groups][n]"""
+    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
+    blob = [struct.pack("<I", len(jobs))]
+    for G, nt, n, draws in jobs:
+        blob.append(struct.pack("<III", G, nt, n))
+        blob.append(b"".join(d.to_bytes(32, "little") for grp in draws for d in grp))
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    src.write_bytes(b"".join(blob))
+    r = subprocess.run([EXE, str(src), str(dst)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    raw = dst.read_bytes()
+    out, at = [], 0
+    for G, nt, n, _ in jobs:
+        out.append([[int.from_bytes(raw[at + 32 * (g * n + p):at + 32 * (g * n + p) + 32], "little") for p in range(n)] for g in range(G)])
+        at += 32 * G * n
+    assert at == len(raw)
+    return out
+
+
+def _check(jobs, got):
+    for (G, nt, n, draws), m in zip(jobs, got):
+        for g in range(G):
+            want = _expected(draws[g], n)
+            bad = [p for p in range(n) if m[g][p] != want[p]]
+            assert not bad, f"G={G} n_tail={nt} n={n} group {g}: {len(bad)} multipliers differ, first at proof {bad[0]}: {m[g][bad[0]]:#x} != {want[bad[0]]:#x}"
+
+
+@pytest.mark.parametrize("G", GROUPS)
+def test_multipliers_match_big_integers(G, tmp_path):
+    rnd = random.Random(100 + G)
+    jobs = [(G, n, n, [[rnd.randrange(1, R) for _ in range(n)] for _ in range(G)]) for n in SIZES]
+    _check(jobs, _run(jobs, tmp_path))
+
+
+@pytest.mark.parametrize("G", GROUPS)
+def test_zero_draw_zeroes_the_earlier_multipliers_of_its_group_only(G, tmp_path):
+    rnd = random.Random(200 + G)
+    jobs = []
+    for n in SIZES:
+        draws = [[rnd.randrange(1, R) for _ in range(n)] for _ in range(G)]
+        g0 = G // 2
+        z = n // 2 if n < 1024 else 3 * 256 + 17      # (inside a tile that is neither the first nor the last)
+        draws[g0][z] = 0
+        jobs.append((G, n, n, draws))
+    got = _run(jobs, tmp_path)
+    _check(jobs, got)
+    for (G_, nt, n, draws), m in zip(jobs, got):
+        g0 = G_ // 2
+        z = draws[g0].index(0)
+        assert all(v == 0 for v in m[g0][:z]) and all(v != 0 for v in m[g0][z:])
+        assert all(v != 0 for g in range(G_) if g != g0 for v in m[g])
+
+
+def test_a_shard_uploads_the_tail_of_the_whole_batch(tmp_path):
+    """more draws than proofs (distributed.tail_for_shard): the later shards' draws count, and their proofs get no multiplier here"""
+    rnd = random.Random(300)
+    jobs = []
+    for G, n, nt in [(1, 1, 9), (1, 64, 65), (4, 63, 1024), (4, 256, 257), (2, 1024, 8192), (32, 65, 130)]:
+        jobs.append((G, nt, n, [[rnd.randrange(R) for _ in range(nt)] for _ in range(G)]))
+    _check(jobs, _run(jobs, tmp_path))
