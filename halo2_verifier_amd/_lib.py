@@ -23,7 +23,7 @@ c_vp = ctypes.c_void_p
 c_szp = ctypes.POINTER(ctypes.c_size_t)
 c_intp = ctypes.POINTER(ctypes.c_int)
 
-ABI_VERSION = 3   # include/h2v.h H2V_ABI_VERSION: the struct layouts this binding mirrors
+ABI_VERSION = 4   # include/h2v.h H2V_ABI_VERSION: the struct layouts this binding mirrors
 
 # every symbol include/h2v.h declares: (restype, argtypes)
 SIGNATURES = {

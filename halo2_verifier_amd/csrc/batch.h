@@ -71,12 +71,10 @@ struct StageArgs {
     Fr* chal;
 };
 
-int decompress_stage_enqueue(hipStream_t s, const StageArgs& g);
-// the same stage in pieces (h2v_batch_upload_launch): reset the status words; decompress the points of proofs [p0, p1); check the
+// the decompression stage in pieces (h2v_batch_upload_launch runs them around its copies): reset the status words; decompress the points of proofs [p0, p1); check the
 // scalars of all proofs
 int decompress_begin_enqueue(hipStream_t s, const StageArgs& g);
-// (src / src_stride: read the proof bytes from there instead of g.proofs — the caller's host buffer, h2v_batch_upload_launch)
-int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1, const uint8_t* src = nullptr, uint32_t src_stride = 0);
+int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // groups > 1: group g owns proofs [g*n/groups, ..) and the draws tail[g*n_tail/groups, ..)

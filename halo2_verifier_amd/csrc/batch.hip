@@ -234,8 +234,13 @@ int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storag
     return 0;
 }
 
-// `overlap`: the copies run on the batch's copy stream in chunks and the decompression of every chunk is enqueued on the batch's own
-// stream behind that chunk's event (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
+// what the decompression and transcript stages work on: the batch's upload (its plan and n) and its buffers
+static StageArgs stage_args(const h2v_batch* b) {
+    return StageArgs{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
+}
+
+// `overlap`: where it pays (see `points_first` below), the point bytes are copied first on the batch's copy stream and the decompression
+// runs under the copy of everything else (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
 // `guard`: the guard variant of the plan (h2v_guard_msm)
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
                 const uint8_t* rand_tail, size_t n_tail, bool overlap, bool guard) {
@@ -308,36 +313,21 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     }
     size_t point_bytes = 0;
     for (auto& r : runs) point_bytes += r.second;
-    int mode = overlap ? ctx->tuning.upload_mode : 3;
-    if (mode == 0) mode = 1;   // (one launch + finish, best of 15, tools/h2d_probe.py: resident 2.98 ms, points-first 3.29, two halves 3.33, plain 3.47;
-                               //  in the benchmark's loop, PCIe-inclusive over resident: 0.905 / 0.885 / 0.835, tools/r03_ab.sh)
-    if (mode == 1 && (runs.size() > 4 || 2 * point_bytes > pl.proof_len)) mode = 3;   // points all over the proof, or most of it: nothing to gain
-    if (n < 2048) mode = 3;                                                           // a copy of a megabyte or two is not worth two launches
-    if (mode == 3) {
+    // (one launch + finish, best of 15, tools/h2d_probe.py: resident 2.98 ms, points-first 3.29, plain 3.47.  A third form — the proofs
+    //  in two halves, each decompressed as soon as it had arrived, the second copy behind the first half's round — was measured and
+    //  removed: 3.33 ms there, and in the benchmark's loop, PCIe-inclusive over resident, 0.885 against 0.905 for points-first and
+    //  0.835 for plain: 5.90 against 6.05 and 5.50 M proofs/s with re-upload, profiles/r03_variants_ab.txt.)
+    const bool points_first = overlap && n >= 2048 &&                                  // a copy of a megabyte or two is not worth two launches
+                              runs.size() <= 4 && 2 * point_bytes <= pl.proof_len;    // points all over the proof, or most of it: nothing to gain
+    if (!points_first) {
         if (n && ((rc = copy_proofs(s, 0, n)) || (rc = copy_rest(s)))) return rc;
         H2V_HIP_CHECK(hipStreamSynchronize(s));  // the host buffers are the caller's again
     } else {
         if (!b->copy) H2V_HIP_CHECK(hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking));
         H2V_HIP_CHECK(hipStreamSynchronize(s));   // an earlier launch of this batch may still read the buffers (normally long finished: h2v_batch_finish)
-    }
-    if (mode == 2) {
-        // the proofs in two halves: [first half] -> its decompression is enqueued -> [second half, instances, draws] travel while the GPU
-        // decompresses the first -> the second half's decompression.  Two rounds of the decompression kernel at half occupancy take about
-        // what one round at full occupancy takes, and the second copy hides behind the first round.
-        StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
-        if ((rc = decompress_begin_enqueue(s, g))) return rc;
-        const size_t half = (n / 2 + 15) / 16 * 16;
-        if ((rc = copy_proofs(b->copy, 0, half))) return rc;
-        H2V_HIP_CHECK(hipStreamSynchronize(b->copy));
-        if ((rc = decompress_range_enqueue(s, g, 0, (uint32_t)half))) return rc;
-        if ((rc = copy_proofs(b->copy, half, n)) || (rc = copy_rest(b->copy))) return rc;
-        H2V_HIP_CHECK(hipStreamSynchronize(b->copy));   // everything is on the device; the host buffers are the caller's again
-        if ((rc = decompress_range_enqueue(s, g, (uint32_t)half, (uint32_t)n))) return rc;
-        if ((rc = decompress_finish_enqueue(s, g))) return rc;
-    } else if (mode != 3) {   // (1)
+        const StageArgs g = stage_args(b);
         for (auto& r : runs) H2V_HIP_CHECK(hipMemcpy2DAsync(b->proofs.p + r.first, pl.proof_len, proofs_flat + r.first, proof_len, r.second, n, hipMemcpyHostToDevice, b->copy));
         H2V_HIP_CHECK(hipStreamSynchronize(b->copy));
-        StageArgs g{(uint32_t)n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
         if ((rc = decompress_begin_enqueue(s, g))) return rc;
         if ((rc = decompress_range_enqueue(s, g, 0, (uint32_t)n))) return rc;
         // (the whole proofs again, point bytes included: identical bytes over the ones the kernel is reading)
@@ -345,7 +335,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         H2V_HIP_CHECK(hipStreamSynchronize(b->copy));   // everything is on the device; the host buffers are the caller's again
         if ((rc = decompress_finish_enqueue(s, g))) return rc;
     }
-    b->decompressed = mode != 3;
+    b->decompressed = points_first;
     // the batch multipliers depend on the draws alone: computed once per upload (the draws are on the device), kept by every launch of it
     if (n) { if ((rc = multipliers_enqueue(s, b->tail.p, b->n_tail, (uint32_t)n, b->groups, b->mult.p, b->mult_tiles.p))) return rc; b->mult_of_draws = true; }
     commit.commit(BatchStage::Uploaded);
@@ -368,7 +358,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     int ev = 0;
     auto mark = [&]() { if (b->profiling >= 2) hipEventRecord(b->ev[ev], s); ++ev; };   // (an event record is a barrier packet: ~6 us of idle stream each)
     mark();
-    StageArgs g{n, &pl, pd, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
+    const StageArgs g = stage_args(b);
     // stage 1: point decompression + canonicity checks (already on the stream, behind its chunked upload, after h2v_batch_upload_launch);
     // stage 2: absorbed stream, Blake2b challenges.  Everything is enqueued on the batch's one stream: the scalar canonicity check reads a
     // word per scalar, the multipliers are the upload's, the MSM's problem descriptors stay on the device from launch to launch

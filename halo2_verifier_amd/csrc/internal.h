@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include "../../include/h2v.h"
 #include "curve.hip.h"
 
 namespace h2v {
@@ -61,14 +62,9 @@ struct MappedHostBuf {
     void reset() { if (p) hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
 };
 
-// Forced kernel variants (include/h2v.h: h2v_tuning; every field 0 = automatic).  Lives in the context; a launch copies it into
-// the objects that choose (MsmWorkspace::tune, FrvmArgs, the pairing launcher's argument).  The library reads no environment variable.
-struct Tuning {
-    int frvm_streams = 0, frvm_lds_kb = 0;
-    int msm_parts = 0, msm_global_sort = 0, msm_no_term_split = 0, msm_window_threads = 0, msm_window_wpw = 0, msm_window_slots = 0, msm_acc_waves = 0;
-    int pairing_one_stream = 0;
-    int upload_mode = 0;
-};
+// Forced kernel variants: the validated h2v_tuning itself (include/h2v.h; every field 0 = automatic) lives in the context, and a launch
+// copies it into the objects that choose (MsmWorkspace::tune, FrvmArgs, the pairing launcher's argument).  The library reads no
+// environment variable.
 
 // ------------------------------------------------------------------ MSM (msm.hip)
 // Pippenger over pooled (scalar, base) terms.  Scalars: canonical little-endian 32-bit words, 8 per
@@ -148,7 +144,7 @@ struct MsmWorkspace {
     DevBuf<uint32_t> seg_total;    // [problems * windows] entries per list segment
     DevBuf<uint32_t> seg_start;    // [problems * windows + 1] logical start of every segment
     // optional HIP events around msm_accumulate (the dominant kernel: bench.py's roofline.kernels), recorded when `profile` is set
-    Tuning tune;                     // forced variants for the next launch (copied from the context by the caller)
+    h2v_tuning tune = {};            // forced variants for the next launch (copied from the context by the caller)
     bool profile = false, profile_recorded = false;
     hipEvent_t ev_acc[2] = {nullptr, nullptr};
     // Grow-only: every dimension becomes the larger of what the workspace holds and what is asked for, and the buffers are allocated

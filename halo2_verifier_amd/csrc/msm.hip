@@ -55,7 +55,10 @@ namespace h2v {
 #define MSM_CHUNK_MIN 16u
 #define MSM_CHUNK_MAX 64u
 #define MSM_ACC_LANES_PER_ROUND 196608u   // 3 waves per SIMD x 1024 SIMDs x 64 lanes (msm_accumulate: 156 VGPRs since its slow path left the kernel)
-// (R = lanes per round: MSM_ACC_LANES_PER_ROUND, or 4 waves per SIMD's worth when the launch runs that variant — MsmSeg::lanes_round)
+// (R = lanes per round, always MSM_ACC_LANES_PER_ROUND since the four-wave build of msm_accumulate went: the host passes it to the device
+// in MsmSeg::lanes_round.  Folding the constant into msm_chunk_len was measured and put back: msm_fixup's callees get another register
+// allocation (260 + 12 -> 280 + 32) and another size, which moves g1_add_to relative to msm_window and g1_dbl_to in the code object,
+// and the unchanged msm_window then takes 316 instead of 295 us of the driver's launch, msm_fixup 74 instead of 69.)
 // (A SHORT list — a batch of up to ~256 proofs; the MSM of ONE proof is ~900 entries — is cut into chunks of MSM_CHUNK_SMALL: 16 entries
 // on each of 57 lanes took 0.21 ms where 4 entries on 228 lanes take 0.12.  Not beyond: shorter chunks spread a bucket over more of
 // them, and from ~512 proofs on the longer fix-up chains of the top window's buckets cost more than the accumulation gains — one
@@ -660,9 +663,9 @@ __device__ __forceinline__ void msm_accumulate_chunk(const MsmProblem* __restric
     if (!ok) { redo[atomicAdd(&control[4], 1u)] = lane; return; }
     msm_chunk_tail(b, bin_lo, bin_hi, chunk_lo, chunk_hi, CH, lane, nb, control, lists);
 }
-// WPE = waves per SIMD the kernel is compiled for: 3 (156 registers, nothing spilled) is the default; 4 fits 128 registers with 30 of
-// them spilled to scratch (h2v_tuning.msm_acc_waves; measured in DESIGN.md)
-template <int WPE> __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) msm_accumulate(const MsmProblem* __restrict__ prs, uint32_t nbq, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
+// Compiled for 3 waves per SIMD: 156 registers, nothing spilled.  (A build for 4 waves fits 128 registers with 30 of them spilled to
+// scratch; it was measured, lost and was removed: 0.663 ms against 0.615 - 0.627, profiles/r03_variants_ab.txt, DESIGN.md.)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) msm_accumulate(const MsmProblem* __restrict__ prs, uint32_t nbq, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
                                                      const uint32_t* __restrict__ list, G1JSlot* __restrict__ bucket_pts, G1JSlot* __restrict__ partial, uint32_t nb, MsmSeg g,
                                                      uint32_t* __restrict__ control, uint32_t* __restrict__ lists, const G1A* __restrict__ phi_pts, uint32_t* __restrict__ redo) {
     const uint32_t E = counts[nb + 1];
@@ -1059,13 +1062,12 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     const bool lds_sort = nmax <= MSM_LDS_SORT_MAX_TERMS && sort_lds <= 150 * 1024 && (size_t)count * p.windows * stride <= ws.cap_list &&
                           (size_t)count * p.windows <= (size_t)128 * ws.cap_problems && !ws.tune.msm_global_sort;
     MsmSeg g;
-    const uint32_t lanes_round = ws.tune.msm_acc_waves == 4 ? 262144u : MSM_ACC_LANES_PER_ROUND;
     if (lds_sort) {
         hipLaunchKernelGGL(msm_glv_prep, dim3((nmax + 255) / 256, count), dim3(256), 0, s, ws.problems.p, count, p, ws.glv.p, ws.phi_pts.p);
         if (sort_lds > 64 * 1024) H2V_HIP_CHECK(hipFuncSetAttribute((const void*)msm_sort_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
         hipLaunchKernelGGL(msm_sort_lds, dim3(p.windows, count), dim3(MSM_SORT_THREADS), sort_lds, s, ws.problems.p, ws.glv.p, p, stride, ws.counts.p, ws.offsets.p, ws.list.p, ws.seg_total.p);
         hipLaunchKernelGGL(msm_seg_scan, dim3(1), dim3(1024), 0, s, ws.seg_total.p, p.windows * count, ws.seg_start.p, ws.counts.p + nb);
-        g = MsmSeg{ws.seg_start.p, p.windows * count, p.buckets, stride, lanes_round};
+        g = MsmSeg{ws.seg_start.p, p.windows * count, p.buckets, stride, MSM_ACC_LANES_PER_ROUND};
     } else {
     H2V_HIP_CHECK(hipMemsetAsync(ws.counts.p, 0, ((size_t)nb + MSM_CONTROL_WORDS) * 4, s));
     H2V_HIP_CHECK(hipMemsetAsync(ws.seg_start.p, 0, 4, s));   // one segment that starts at 0
@@ -1079,22 +1081,21 @@ int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, Ms
     hipLaunchKernelGGL(msm_scan_sums, dim3(1), dim3(1024), 0, s, ws.block_sums.p, nblk, ws.counts.p + nb + 1);
     hipLaunchKernelGGL(msm_offsets, dim3(nblk), dim3(1024), 0, s, ws.counts.p, ws.block_sums.p, ws.offsets.p, ws.cursor.p, nb);
     hipLaunchKernelGGL(msm_count_or_scatter<true>, gt, dim3(MSM_TILE_THREADS), lds, s, ws.problems.p, count, tiles, p, wpp, ws.counts.p, ws.offsets.p, ws.cursor.p, ws.list.p);
-    g = MsmSeg{ws.seg_start.p, 1, nb, 0, lanes_round};
+    g = MsmSeg{ws.seg_start.p, 1, nb, 0, MSM_ACC_LANES_PER_ROUND};
     }
     // one lane per chunk of the sorted list; the entry count is only known on the device, the grid covers the host's bound on it.
     // Surplus workgroups are not free: the kernel holds exactly its occupancy in working workgroups (3 waves per SIMD), so the
     // surplus is dispatched after they retire, ~7 ns each — the old bound (every term non-zero, shortest chunk) cost 9 500 empty
     // workgroups, 0.07 ms, at the end of every 20-step launch.
-    const uint32_t acc_blocks = msm_accumulate_blocks(total_nz * 2 * p.windows, lanes_round);
+    const uint32_t acc_blocks = msm_accumulate_blocks(total_nz * 2 * p.windows, MSM_ACC_LANES_PER_ROUND);
     {
         const G1A* phi_tab = lds_sort ? (const G1A*)ws.phi_pts.p : (const G1A*)nullptr;
-        auto kern = ws.tune.msm_acc_waves == 4 ? msm_accumulate<4> : msm_accumulate<3>;
         // (the profiling events are attached to the dispatch itself — its own start and stop timestamps — instead of being recorded around it:
         // a recorded event is a barrier packet, ~6 us of idle stream on either side of the kernel)
         if (ws.profile) {
-            hipExtLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.ev_acc[0], ws.ev_acc[1], 0, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
+            hipExtLaunchKernelGGL(msm_accumulate, dim3(acc_blocks), dim3(64), 0, s, ws.ev_acc[0], ws.ev_acc[1], 0, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
             ws.profile_recorded = true;
-        } else hipLaunchKernelGGL(kern, dim3(acc_blocks), dim3(64), 0, s, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
+        } else hipLaunchKernelGGL(msm_accumulate, dim3(acc_blocks), dim3(64), 0, s, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, phi_tab, ws.redo.p);
     }
     hipLaunchKernelGGL(msm_accumulate_redo, dim3(256), dim3(64), 0, s, ws.problems.p, nbq, ws.counts.p, ws.offsets.p, ws.list.p, ws.bucket_pts.p, ws.partial.p, nb, g, ws.counts.p + nb, ws.cursor.p, ws.redo.p);
     hipLaunchKernelGGL(msm_fixup, dim3((nb + 63) / 64 + MSM_FIXUP_TEAM_BLOCKS + MSM_FIXUP_HEAVY_BLOCKS), dim3(64), 0, s, ws.counts.p, ws.offsets.p, ws.partial.p, ws.cursor.p, ws.bucket_pts.p, nb, g);

@@ -87,7 +87,7 @@ int h2v_ctx_create(const uint8_t* params, size_t params_len, int params_format,
  * h2v_ctx_create == h2v_ctx_create_ex with {sizeof(h2v_options), 0, 0, 1, 0}. */
 typedef struct h2v_options { size_t struct_size; int multiopen; int transcript; int circuit_instances; int instance_kernel_threshold; } h2v_options;
 #define H2V_OPTIONS_INIT { sizeof(h2v_options), 0, 0, 1, 0 }
-#define H2V_ABI_VERSION 3   /* bumped whenever a struct of this header changes layout; h2v_abi_version() returns the library's */
+#define H2V_ABI_VERSION 4   /* bumped whenever a struct of this header changes layout; h2v_abi_version() returns the library's */
 int h2v_abi_version(void);
 #define H2V_MULTIOPEN_SHPLONK 0
 #define H2V_MULTIOPEN_GWC 1
@@ -109,17 +109,12 @@ int h2v_ctx_create_ex(const uint8_t* params, size_t params_len, int params_forma
  *   msm_window_threads  lanes per window reduction (64, 128, 256; automatic by bucket and window count)
  *   msm_window_wpw      windows per workgroup of the window reduction (1, 2, 4)
  *   msm_window_slots    3: the 20 KB form of the window reduction without the two-bit digit table (automatic: beyond 1024 windows)
- *   msm_acc_waves       3 or 4: waves per SIMD msm_accumulate is compiled for (automatic: 3 — 156 registers, no spills)
- *   pairing_one_stream  1: the single-stream pairing table over split accumulators instead of the two-stream one
- *   upload_mode         h2v_batch_upload_launch: 1 = point bytes first, then one decompression launch under the full copy;
- *                       2 = the proofs in two halves, each decompressed as soon as it has arrived; 3 = plain upload, then launch
- *                       (automatic: see the function) */
+ *   pairing_one_stream  1: the single-stream pairing table over split accumulators instead of the two-stream one */
 typedef struct h2v_tuning {
     size_t struct_size;
     int frvm_streams, frvm_lds_kb;
-    int msm_parts, msm_global_sort, msm_no_term_split, msm_window_threads, msm_window_wpw, msm_window_slots, msm_acc_waves;
+    int msm_parts, msm_global_sort, msm_no_term_split, msm_window_threads, msm_window_wpw, msm_window_slots;
     int pairing_one_stream;
-    int upload_mode;
 } h2v_tuning;
 int h2v_ctx_set_tuning(h2v_ctx* ctx, const h2v_tuning* tuning);
 /* Destroys the context and everything compiled for it.  Every h2v_batch created on it must have been destroyed before. */

@@ -118,7 +118,7 @@ def test_options_struct_size_guards_the_layout(lib):
     revision of the header), before it looks at any other argument that needs a device."""
     from halo2_verifier_amd import verifier
     lib.h2v_abi_version.restype = ctypes.c_int
-    assert lib.h2v_abi_version() == 3
+    assert lib.h2v_abi_version() == 4
     lib.h2v_last_error.restype = ctypes.c_char_p
     srs = open(os.path.join(ROOT, "tests", "golden", "kzg_bn254_8.srs"), "rb").read()
     params = srs[:4] + srs[4:68] + srs[-256:]

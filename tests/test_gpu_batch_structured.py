@@ -186,7 +186,7 @@ def test_throughput_launch_shapes_with_patterns(pool, G, gs):
 KNOBS = [dict(pairing_one_stream=1), dict(frvm_streams=1), dict(pairing_one_stream=1, frvm_streams=1), dict(frvm_streams=2), dict(frvm_streams=3),
          dict(frvm_streams=2, frvm_lds_kb=36), dict(frvm_streams=4, frvm_lds_kb=78), dict(msm_global_sort=1), dict(msm_parts=1, frvm_streams=1),
          dict(msm_window_threads=64, msm_window_slots=3), dict(msm_window_threads=64, msm_window_wpw=2), dict(msm_window_threads=128, msm_window_wpw=2),
-         dict(msm_window_threads=256), dict(msm_acc_waves=4), dict(msm_acc_waves=4, msm_global_sort=1),
+         dict(msm_window_threads=256),
          dict(msm_parts=1), dict(msm_parts=2), dict(msm_parts=6), dict(msm_no_term_split=1)]
 
 
