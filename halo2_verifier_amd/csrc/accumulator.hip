@@ -1,0 +1,185 @@
+// The resident accumulator behind h2v_accumulator (include/h2v.h): an AccumulatorStrategy that lives across calls.
+//
+// The reference's AccumulatorStrategy is incremental: verify_proof takes a key and instances on every call and hands the strategy back
+// (kzg/strategy.rs:125-136), finalize() runs the one pairing whenever the caller decides (:138-140), with(DualMSM) resumes an earlier
+// accumulation (:76-78).  Here the strategy's DualMSM is two G1 points that stay in device memory.  A process call of n proofs with draws
+// r_0 .. r_{n-1} is n x (scale by the draw, add the Guard):
+//     (L, R) <- M (L, R) + sum_i (prod_{j > i} r_j) Guard_i,     M = r_0 r_1 .. r_{n-1}
+// so process(A); process(B); finalize() equals one h2v_verify_batch_keys over A || B with the draws concatenated, for any cut.
+//   - M (L, R) is k_accumulator_scale (msm.hip) on the accumulator's stream, enqueued first: it depends on the draws and the previous
+//     accumulator only, and runs beside the groups' chains.  It writes a staging record, not the accumulator.
+//   - the sum is the call's (key, shape) groups on their keys' scratch batches, each without a pairing, with the whole-sequence
+//     multipliers (run_group_batches, oneshot.hip: what h2v_verify_batch_keys runs in front of its fold).
+//   - one fold over [staging record, group records ..] writes the accumulator, as the last step: a call that fails before it leaves
+//     the accumulator and the counters as they were.
+// No pairing runs before finalize, and no accumulator point goes through host memory.
+#include "../../include/h2v.h"
+#include "batch.h"
+#include <string.h>
+
+using namespace h2v;
+
+struct h2v_accumulator {
+    h2v_ctx* ctx = nullptr;          // the params (same_srs for every context of a process call), the pairing tables, add_msm's MSMs
+    hipStream_t stream = nullptr;    // its own, of the highest priority (h2v_accumulator_create); idle whenever a call returns
+    DevBuf<G1J> acc;                 // [0] left, [1] right: whole Jacobian points
+    DevBuf<uint8_t> records;         // [0] the staging record (the scaled accumulator), [1 ..] the records of a call's groups (at most H2V_MAX_SHAPES_PER_CALL)
+    DevBuf<uint32_t> scalar;         // M of the call in flight, 8 canonical words
+    DevBuf<uint32_t> words;          // [0] fold_failed, [1] the pairing's verdict, [2, 3] identity flags of the two points, [4, 5] add_msm's base flags
+    DevBuf<uint8_t> bytes;           // the affine bytes of the two points (read / finalize); add_msm: the evaluated channels on their way in
+    DevBuf<G1A> affine;              // add_msm
+    DevBuf<G1J> jacobian;            // add_msm
+    uint32_t host_scalar[8] = {0};   // what `scalar` is copied from (it outlives the copy)
+    size_t n_proofs = 0, n_failed = 0;
+};
+
+namespace {
+
+// every operation of the object ends here: its stream is idle when a call returns
+int sync(h2v_accumulator* a, const char* who) {
+    const hipError_t e = hipStreamSynchronize(a->stream);
+    if (e != hipSuccess) { set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    return 0;
+}
+
+// the affine bytes of the two points into out_left / out_right (either may be null); with `ok`, the pairing check beside them
+int read_points(h2v_accumulator* a, const char* who, int* ok, uint8_t* out_left, uint8_t* out_right) {
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    int rc;
+    uint32_t okv = 0; uint8_t out[128];
+    if (ok && (rc = pairing_check_enqueue(a->stream, a->ctx->pairing, a->acc.p, 1, a->words.p + 1))) return rc;
+    if ((rc = point_to_bytes_enqueue(a->stream, a->acc.p, a->bytes.p, a->words.p + 2, 2))) return rc;
+    if (ok) H2V_HIP_CHECK(hipMemcpyAsync(&okv, a->words.p + 1, 4, hipMemcpyDeviceToHost, a->stream));
+    H2V_HIP_CHECK(hipMemcpyAsync(out, a->bytes.p, 128, hipMemcpyDeviceToHost, a->stream));
+    if ((rc = sync(a, who))) return rc;
+    if (ok) *ok = (okv && !a->n_failed) ? 1 : 0;
+    if (out_left) memcpy(out_left, out, 64);
+    if (out_right) memcpy(out_right, out + 64, 64);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int h2v_accumulator_create(h2v_ctx* ctx, h2v_accumulator** out) {
+    if (!ctx || !out) { set_last_error("h2v_accumulator_create: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    *out = nullptr;
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<h2v_accumulator, void (*)(h2v_accumulator*)> a(new h2v_accumulator, h2v_accumulator_destroy);
+    a->ctx = ctx;
+    // A stream of the highest priority: the runtime keeps hardware queues per priority, so this stream never shares an in-order queue
+    // with the batches' streams (all of normal priority), whatever other streams the process has made — the scale step then runs
+    // BESIDE a call's groups, not in front of them on their queue ("Streams and hardware queues").
+    int least = 0, greatest = 0;
+    H2V_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    H2V_HIP_CHECK(hipStreamCreateWithPriority(&a->stream, hipStreamNonBlocking, greatest));
+    int rc;
+    if ((rc = a->acc.alloc(2)) || (rc = a->records.alloc((size_t)H2V_ACC_RECORD_BYTES * (1 + H2V_MAX_SHAPES_PER_CALL))) || (rc = a->scalar.alloc(8)) ||
+        (rc = a->words.alloc(6)) || (rc = a->bytes.alloc(128)) || (rc = a->affine.alloc(2)) || (rc = a->jacobian.alloc(2))) return rc;
+    const G1J empty[2] = {G1J::identity(), G1J::identity()};   // AccumulatorStrategy::new: an empty DualMSM
+    H2V_HIP_CHECK(hipMemcpyAsync(a->acc.p, empty, sizeof(empty), hipMemcpyHostToDevice, a->stream));
+    if ((rc = sync(a.get(), "h2v_accumulator_create"))) return rc;
+    *out = a.release();
+    return 0;
+}
+
+void h2v_accumulator_destroy(h2v_accumulator* a) {
+    if (!a) return;
+    hipSetDevice(a->ctx->device);
+    if (a->stream) { hipStreamSynchronize(a->stream); hipStreamDestroy(a->stream); }
+    delete a;
+}
+
+int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                            const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                            const uint8_t* rand32, int* per_proof_status, int* all_ok) {
+    const char* who = "h2v_accumulator_process";
+    // every argument check comes before the first HIP call
+    if (!a || (n && !key_of_proof)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    std::vector<CallGroup> groups;
+    int rc;
+    if ((rc = grouped_call_args(who, ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, groups))) return rc;
+    for (size_t k = 0; k < n_keys; ++k) {
+        if (ctxs[k]->device != a->ctx->device) { set_last_error(std::string(who) + ": a context on another device than the accumulator"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!same_srs(ctxs[k]->params, a->ctx->params)) { set_last_error(std::string(who) + ": a context over other params than the accumulator (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    std::vector<uint8_t> os_rand;
+    if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
+    if (all_ok) *all_ok = 1;
+    if (!n) return 0;   // no verify_proof: no scale, no Guard
+    // M, the product of the call's draws (host: n Fr products)
+    Fr M = Fr::one();
+    for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
+    uint8_t m_bytes[32];
+    M.to_bytes(m_bytes);
+    memcpy(a->host_scalar, m_bytes, 32);
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    // on an error past this point the stream is drained before the call returns; the accumulator is written by the last step only
+    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain{a->stream};
+    // the scale step first, beside the groups: staging record <- M (L, R)
+    H2V_HIP_CHECK(hipMemcpyAsync(a->scalar.p, a->host_scalar, 32, hipMemcpyHostToDevice, a->stream));
+    if ((rc = accumulator_scale_enqueue(a->stream, a->acc.p, a->scalar.p, a->records.p))) return rc;
+    // the groups, each without a pairing, finished by the host when this returns: records 1 ..
+    GroupsHeldPtr held;   // the contexts' locks and scratch batches, until the call returns
+    std::vector<std::vector<int>> st;
+    bool groups_ok = true;
+    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, a->records.p + H2V_ACC_RECORD_BYTES, false, held, st, groups_ok))) return rc;
+    // the commit: (L, R) <- staging record + the groups' records
+    if ((rc = fold_records_enqueue(a->stream, a->records.p, (uint32_t)(1 + groups.size()), 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) return rc;
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    size_t failed = 0;
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        for (size_t j = 0; j < groups[gi].idx.size(); ++j) {
+            if (st[gi][j]) ++failed;
+            if (per_proof_status) per_proof_status[groups[gi].idx[j]] = st[gi][j];
+        }
+    a->n_proofs += n; a->n_failed += failed;
+    if (all_ok) *all_ok = failed ? 0 : 1;
+    return 0;
+}
+
+int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, const uint8_t* left_bases64, size_t n_left,
+                            const uint8_t* right_scalars32, const uint8_t* right_bases64, size_t n_right) {
+    const char* who = "h2v_accumulator_add_msm";
+    if (!a || (n_left && (!left_scalars32 || !left_bases64)) || (n_right && (!right_scalars32 || !right_bases64))) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n_left > (1u << 24) || n_right > (1u << 24)) { set_last_error(std::string(who) + ": too many terms"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint8_t* sc[2] = {left_scalars32, right_scalars32};
+    const size_t ns[2] = {n_left, n_right};
+    for (int side = 0; side < 2; ++side)
+        for (size_t j = 0; j < ns[side]; ++j) {
+            Fr v;
+            if (!Fr::from_bytes(sc[side] + 32 * j, v)) { set_last_error(std::string(who) + ": scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
+        }
+    // both channels are evaluated (h2v_msm_g1 rejects bases that are not on the curve) before anything of the accumulator changes
+    int rc, ident = 0;
+    uint8_t xy[128];
+    if ((rc = h2v_msm_g1(a->ctx, left_scalars32, left_bases64, n_left, xy, &ident))) return rc;
+    if ((rc = h2v_msm_g1(a->ctx, right_scalars32, right_bases64, n_right, xy + 64, &ident))) return rc;
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    hipStream_t s = a->stream;
+    // (L, R) <- (L, R) + the two sums, unscaled: the accumulator and the sums as two whole-point records, folded
+    H2V_HIP_CHECK(hipMemcpyAsync(a->bytes.p, xy, 128, hipMemcpyHostToDevice, s));
+    if ((rc = bases_from_bytes_enqueue(s, a->bytes.p, a->affine.p, a->words.p + 4, 2)) ||
+        (rc = affine_to_jacobian_enqueue(s, a->affine.p, a->jacobian.p, 2)) ||
+        (rc = export_records_enqueue(s, a->acc.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p)) ||
+        (rc = export_records_enqueue(s, a->jacobian.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p + H2V_ACC_RECORD_BYTES)) ||
+        (rc = fold_records_enqueue(s, a->records.p, 2, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) { hipStreamSynchronize(s); return rc; }
+    return sync(a, who);
+}
+
+int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_proofs, size_t* n_failed) {
+    if (!a) { set_last_error("h2v_accumulator_read: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rc = read_points(a, "h2v_accumulator_read", nullptr, out_left_xy, out_right_xy)) return rc;
+    if (n_proofs) *n_proofs = a->n_proofs;
+    if (n_failed) *n_failed = a->n_failed;
+    return 0;
+}
+
+int h2v_accumulator_finalize(h2v_accumulator* a, int* ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
+    if (!a || !ok) { set_last_error("h2v_accumulator_finalize: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    return read_points(a, "h2v_accumulator_finalize", ok, out_left_xy, out_right_xy);
+}
+
+}  // extern "C"

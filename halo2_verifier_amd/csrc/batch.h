@@ -2,6 +2,7 @@
 #pragma once
 #include "ctx.h"
 #include "vkplan.h"
+#include <memory>
 
 namespace h2v {
 
@@ -144,6 +145,21 @@ bool same_srs(const ParamsHost& a, const ParamsHost& b);
 int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range, const size_t* first,
                  const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right);
 int export_whole_records(h2v_batch* b, void* device_dst);
+
+// ---- grouped one-shot calls (oneshot.hip): h2v_verify_batch_keys and its forms, and a resident accumulator's process (accumulator.hip)
+#define H2V_MAX_SHAPES_PER_CALL 64   // distinct (key, instance shape) groups one call takes (H2V_ERR_UNSUPPORTED beyond)
+// the proofs of one key with one instance shape, in call order
+struct CallGroup { size_t key; std::vector<size_t> shape, idx; };
+// what a grouped call holds until it returns: the contexts' locks and scratch batches, and the batches made for the call
+struct GroupsHeld;
+struct GroupsHeldDelete { void operator()(GroupsHeld* h) const; };
+typedef std::unique_ptr<GroupsHeld, GroupsHeldDelete> GroupsHeldPtr;
+int grouped_call_args(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                      const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                      std::vector<CallGroup>& groups);
+int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+                      const uint8_t* const* instances32, const uint8_t* rand32, uint8_t* d_records, bool resident, GroupsHeldPtr& held,
+                      std::vector<std::vector<int>>& st, bool& all_ok);
 }  // namespace h2v
 
 struct h2v_batch {

@@ -118,6 +118,14 @@ struct MsmSplit {
     const G1JSlot* ready = nullptr;                 // out: the same pieces as (X Z, Y, Z^3), the form the Miller lines are evaluated at
 };
 
+// The record a rank contributes to a sharded batch (include/h2v.h H2V_ACC_RECORD_BYTES): the two accumulators of one group —
+// in the pieces the launch left them in (MsmSplit), or whole (parts = 1) — plus the number of the shard's proofs that failed
+// before the MSM.  A failed proof is zeroed out of its shard's accumulators, so without the count every OTHER rank's folded
+// pairing would still pass.
+struct AccRecord { uint32_t failed, parts, shift, reserved; G1J left[H2V_ACC_RECORD_PIECES], right[H2V_ACC_RECORD_PIECES]; };
+static_assert(sizeof(AccRecord) == H2V_ACC_RECORD_BYTES && H2V_ACC_RECORD_BYTES == 16 + 2 * H2V_ACC_RECORD_PIECES * 108, "accumulator record layout");
+static_assert(H2V_ACC_RECORD_PIECES >= MSM_MAX_PARTS, "a record holds every piece a launch can leave");
+
 struct MsmWorkspace {
     // what the workspace was sized for (reserve): terms of a launch, the caller's problems, terms of the largest problem
     uint32_t cap_terms = 0, cap_parents = 0, cap_per_problem = 0;
@@ -171,6 +179,9 @@ int msm_combine_enqueue(hipStream_t s, MsmWorkspace& ws, const MsmSplit& sp, siz
 // k_pairing2 workgroup (160 KB - 58 KB) is never placed on such a CU, and its CU takes no pairing workgroup afterwards.
 #define H2V_AUX_LDS_RESERVE ((size_t)110 * 1024)
 int msm_enqueue(hipStream_t s, MsmWorkspace& ws, const uint32_t* d_scalars, const G1A* d_bases, uint32_t n, G1J* d_out);
+// d_record (an accumulator record, whole points: parts = 1, failed = 0) <- M * (d_points[0], d_points[1]); d_scalar_words: M as 8 canonical
+// little-endian words.  One wave (k_accumulator_scale): the scale step of a resident accumulator (accumulator.hip)
+int accumulator_scale_enqueue(hipStream_t s, const G1J* d_points, const uint32_t* d_scalar_words, void* d_record);
 
 // ------------------------------------------------------------------ small helpers (util.hip)
 // canonical x|y bytes (64 B each, all-zero = identity) -> affine Montgomery; flags[i] = 0 ok, 1 not canonical / not on curve

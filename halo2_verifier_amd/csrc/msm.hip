@@ -249,6 +249,82 @@ __device__ __forceinline__ uint32_t raw_window(const uint32_t m[5], uint32_t w, 
     if (sh + c > 32 && word + 1 < 5) v |= m[word + 1] << (32 - sh);
     return v & ((1u << c) - 1);
 }
+// ---- The scale step of a resident accumulator (accumulator.hip): M (L, R) for the two accumulator points and one scalar M, the product
+// of the draws of a process call — what the reference does draw by draw at the top of every verify_proof, msm_accumulator.scale(draw)
+// (kzg/strategy.rs:129, msm.rs:173-176).  Two scalar multiplications and nothing to parallelise across: a latency chain like the MSM's
+// final Horner, shaped the same way.  M is split with glv_decompose into two signed 128-bit halves, the second acting on
+// phi(P) = (beta X, Y, Z), which gives four chains (2 points x 2 halves) of half the length; every chain runs on a quad of lanes that
+// splits each doubling (g1_dbl_quad) and walks signed 4-bit windows from the top over a table of 1 P .. 8 P in LDS (a register table
+// indexed by the digit would live in scratch memory).  The digits need no carry chain: with 8 added to every nibble of the magnitude,
+// digit w = nibble w of (|k| + 0x88..8) - 8, in [-8, 7], and sum_w digit_w 16^w = |k|; |k| < 2^129 keeps the sum inside 33 nibbles.
+// A negative half negates its point before the table is made.  Every addition is the complete one: the table of an identity point is
+// all identities, M = 0 gives 33 zero digits (the result is the identity), and the running sum may meet a table entry or its negative
+// (M = r - 1 against M = 1: the halves of one point add up to -P) — in the loop, and where the two halves of a point are joined.
+// One workgroup of one wave: lanes 0..15 are the four quads; the other lanes repeat them (one code path for the wave) and write nothing.
+// No raised issue priority, unlike the MSM's own tail kernels: this chain (~0.5 ms) is shorter than the chain of the groups it runs
+// beside (>= 1.2 ms), and where its wave shares a SIMD with one of their single-wave kernels, theirs is the one the call waits for.
+#define ACC_SCALE_TABLE 8u      // multiples 1 P .. 8 P per chain
+#define ACC_SCALE_DIGITS 33u    // nibbles of |k| + 0x8..8, |k| < 2^129
+__global__ void __launch_bounds__(64) k_accumulator_scale(const G1J* __restrict__ in, const uint32_t* __restrict__ m_words, AccRecord* __restrict__ out) {
+    __shared__ G1J table[4][ACC_SCALE_TABLE];
+    __shared__ G1J half_sum[4];
+    const uint32_t lane = threadIdx.x, chain = (lane >> 2) & 3u, r = lane & 3u;
+    const uint32_t side = chain >> 1, half = chain & 1u;
+    const bool writer = lane < 16 && r == 0;
+    uint32_t k[8];
+    for (int i = 0; i < 8; ++i) k[i] = m_words[i];
+    GlvHalf h1, h2;
+    glv_decompose(k, h1, h2);
+    const bool neg = half ? h2.neg : h1.neg;
+    uint32_t mag[5];
+    {
+        uint64_t c = 0;
+        for (int i = 0; i < 5; ++i) { const uint64_t v = (uint64_t)(half ? h2.mag[i] : h1.mag[i]) + (i < 4 ? 0x88888888u : 0x8u) + c; mag[i] = (uint32_t)v; c = v >> 32; }
+    }
+    G1J p = in[side];
+    if (half) p.X = g1_beta_times(p.X);
+    if (neg) p.Y = p.Y.neg();
+    {
+        // 1 P .. 8 P, every lane of the quad the same; the chain's first lane writes
+        G1J t = p;
+        if (writer) table[chain][0] = t;
+        t = g1_dbl(t);
+        if (writer) table[chain][1] = t;
+#pragma unroll 1
+        for (uint32_t j = 2; j < ACC_SCALE_TABLE; ++j) { t = g1_add(t, p); if (writer) table[chain][j] = t; }
+    }
+    __syncthreads();
+    G1J acc = G1J::identity();
+#pragma unroll 1
+    for (int w = (int)ACC_SCALE_DIGITS - 1; w >= 0; --w) {
+        if (w != (int)ACC_SCALE_DIGITS - 1) {
+#pragma unroll 1
+            for (int i = 0; i < 4; ++i) g1_dbl_quad(acc, r);
+        }
+        const int d = (int)raw_window(mag, (uint32_t)w, 4) - 8;
+        if (d != 0) {
+            G1J t = table[chain][(d < 0 ? -d : d) - 1];   // (LDS: 3.4 KB for the four chains)
+            if (d < 0) t.Y = t.Y.neg();
+            acc = g1_add_inl(acc, t);
+        }
+    }
+    if (writer) half_sum[chain] = acc;
+    __syncthreads();
+    // k1 P + k2 phi(P) per point, and the record: a whole point (parts = 1) with no failed proof of its own
+    if (lane < 2) {
+        const G1J a = half_sum[2 * lane], b = half_sum[2 * lane + 1];
+        G1J* dst = lane ? out->right : out->left;
+        dst[0] = g1_add_inl(a, b);
+        for (uint32_t j = 1; j < H2V_ACC_RECORD_PIECES; ++j) dst[j] = G1J::identity();
+    }
+    if (lane == 0) { out->failed = 0; out->parts = 1; out->shift = 0; out->reserved = 0; }
+}
+int accumulator_scale_enqueue(hipStream_t s, const G1J* d_points, const uint32_t* d_scalar_words, void* d_record) {
+    hipLaunchKernelGGL(k_accumulator_scale, dim3(1), dim3(64), 0, s, d_points, d_scalar_words, (AccRecord*)d_record);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // entry of the sorted list: term index | half << 30 | negate << 31
 #define MSM_ENTRY_HALF 0x40000000u
 #define MSM_ENTRY_NEG 0x80000000u

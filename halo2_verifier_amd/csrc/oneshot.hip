@@ -196,54 +196,94 @@ int fold_check_locked(h2v_ctx* ctx, const void* device_accumulators, size_t n_pa
 // (O(program length^2) host work, ~10 device uploads) and may grow the batch's buffers: a call takes at most
 // H2V_MAX_SHAPES_PER_CALL distinct (key, shape) groups (H2V_ERR_UNSUPPORTED beyond), the groups of a key share ONE batch object, and
 // the plans go through the context's bounded cache (H2V_MAX_CACHED_PLANS, least recently used out).
-#define H2V_MAX_SHAPES_PER_CALL 64
-
-// the proofs of one key with one instance shape, in call order
-struct CallGroup { size_t key; std::vector<size_t> shape, idx; };
+// (H2V_MAX_SHAPES_PER_CALL: batch.h)
 
 // the (key, shape) groups of a call in first-appearance order; every key index and every pointer the groups will read is checked here
 int group_proofs(const char* who, size_t n, size_t n_keys, const uint32_t* key_of_proof, const size_t* n_instance_columns, const size_t* col_lens,
                  const uint8_t* const* proofs, const uint8_t* const* instances32, std::vector<CallGroup>& groups) {
     std::map<std::pair<size_t, std::vector<size_t>>, size_t> group_of;
     const size_t* cl = col_lens;
+    size_t last = 0;   // the previous proof's group: runs of one key and shape (the common case) skip the map
     for (size_t i = 0; i < n; ++i) {
         const size_t k = key_of_proof ? key_of_proof[i] : 0;
         if (k >= n_keys) { set_last_error(std::string(who) + ": key index out of range"); return H2V_ERR_BAD_ARGUMENT; }
         const size_t nc = n_instance_columns[k];
         if (nc && !col_lens) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
-        std::vector<size_t> shape(cl, cl + nc);
+        const size_t* shape_at = cl;
         cl += nc;
         if (!proofs[i]) { set_last_error(std::string(who) + ": null proof pointer"); return H2V_ERR_BAD_ARGUMENT; }
         size_t values = 0;
-        for (size_t l : shape) values += l;
+        for (size_t c = 0; c < nc; ++c) values += shape_at[c];
         if (values && (!instances32 || !instances32[i])) { set_last_error(std::string(who) + ": null instances pointer"); return H2V_ERR_BAD_ARGUMENT; }
-        auto it = group_of.find({k, shape});
+        if (i && groups[last].key == k && groups[last].shape.size() == nc && std::equal(shape_at, shape_at + nc, groups[last].shape.begin())) {
+            groups[last].idx.push_back(i);
+            continue;
+        }
+        std::pair<size_t, std::vector<size_t>> key(k, std::vector<size_t>(shape_at, shape_at + nc));
+        auto it = group_of.find(key);
         if (it == group_of.end()) {
             if (groups.size() == H2V_MAX_SHAPES_PER_CALL) { set_last_error(std::string(who) + ": more than 64 distinct (key, instance shape) groups in one call"); return H2V_ERR_UNSUPPORTED; }
-            it = group_of.emplace(std::make_pair(k, shape), groups.size()).first;
-            groups.push_back({k, shape, {}});
+            groups.push_back({k, key.second, {}});
+            it = group_of.emplace(std::move(key), groups.size() - 1).first;
         }
-        groups[it->second].idx.push_back(i);
+        last = it->second;
+        groups[last].idx.push_back(i);
     }
     return 0;
 }
 
+}  // namespace
+
+namespace h2v {
+
+// What a grouped call holds until it returns: every context's lock and scratch batch (ctxs[k]'s: hold[k]), the batches made for the
+// call (identification), and the batch every group ran on
+struct GroupsHeld {
+    std::vector<std::unique_ptr<ScratchBatch>> hold;
+    struct Destroy { void operator()(h2v_batch* b) const { h2v_batch_destroy(b); } };
+    std::vector<std::unique_ptr<h2v_batch, Destroy>> own;
+    std::vector<h2v_batch*> on;
+};
+void GroupsHeldDelete::operator()(GroupsHeld* h) const { delete h; }
+
+// The argument checks of a grouped call, every one before the first HIP call, and its (key, shape) groups.  `who` names the entry point
+// in the error messages.
+int grouped_call_args(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                      const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                      std::vector<CallGroup>& groups) {
+    const std::string w(who);
+    if (!ctxs || !n_keys || !n_instance_columns || (n && (!proofs || !proof_lens))) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t k = 0; k < n_keys; ++k) {
+        if (!ctxs[k]) { set_last_error(w + ": null context"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!ctxs[k]->vk) { set_last_error(w + ": a context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+        for (size_t j = 0; j < k; ++j) if (ctxs[j] == ctxs[k]) { set_last_error(w + ": the same context twice"); return H2V_ERR_BAD_ARGUMENT; }
+        if (ctxs[k]->device != ctxs[0]->device) { set_last_error(w + ": contexts on different devices"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!same_srs(ctxs[k]->params, ctxs[0]->params)) { set_last_error(w + ": contexts over different params (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    for (size_t k = 0; k < n_keys; ++k) if (n_instance_columns[k] != ctx_total_instance_columns(ctxs[k])) { set_last_error(w + ": instances do not match a VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
+    return group_proofs(who, n, n_keys, key_of_proof, n_instance_columns, col_lens, proofs, instances32, groups);
+}
+
 // The groups of a call on their keys' scratch batches (ctxs[k]'s; keys without a group are not touched), their records (whole points:
-// export_whole_records) folded into ONE pairing on the first group's context.  rand32: the n draws in call order (resolved).
+// export_whole_records) written to d_records, H2V_ACC_RECORD_BYTES per group in the groups' order.  rand32: the n draws in call order
+// (resolved).  Every context's lock and scratch batch is taken for the whole call and handed to the caller in `held` (released when it
+// goes); the whole-sequence multipliers are computed on the first group's context's stream.
 // Keys do not wait for each other on the host: each round enqueues one group of every key (upload, launch without a pairing, record
-// export on that key's batch stream), then finishes them; groups of one key run one after another on its batch.
-// n_checks (identification, h2v_verify_batch_keys_identify): every group stays resident — a key's first group on its scratch batch, its
-// later groups on batches made for the call (destroyed at its end) — and when the folded pairing itself fails, the failing proofs are
-// searched for over all groups at once (identify_search); the number of range checks it ran is ADDED to *n_checks.
-int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
-               const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy,
-               size_t* n_checks = nullptr) {
+// export on that key's batch stream), then finishes them; groups of one key run one after another on its batch.  When the call
+// returns 0 every group is finished — the records are written — st[g] holds group g's statuses and all_ok says whether all are 0.
+// resident (identification): every group stays resident — a key's first group on its scratch batch, its later groups on batches made
+// for the call (held->own, destroyed with `held`).
+int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+                      const uint8_t* const* instances32, const uint8_t* rand32, uint8_t* d_records, bool resident, GroupsHeldPtr& held,
+                      std::vector<std::vector<int>>& st, bool& all_ok) {
+    held.reset(new GroupsHeld);
     // every context's lock and scratch batch for the whole call, taken in one global order (by address): calls over overlapping sets of
     // contexts cannot deadlock
     std::vector<size_t> order(n_keys);
     for (size_t k = 0; k < n_keys; ++k) order[k] = k;
     std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::less<const h2v_ctx*>()(ctxs[a], ctxs[b]); });
-    std::vector<std::unique_ptr<ScratchBatch>> hold(n_keys);
+    std::vector<std::unique_ptr<ScratchBatch>>& hold = held->hold;
+    hold.resize(n_keys);
     for (size_t k : order) hold[k].reset(new ScratchBatch(ctxs[k]));
     h2v_ctx* fold_ctx = ctxs[groups[0].key];
     H2V_HIP_CHECK(hipSetDevice(fold_ctx->device));
@@ -260,13 +300,19 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         idx_off[gi] = idx32.size();
         idx32.insert(idx32.end(), groups[gi].idx.begin(), groups[gi].idx.end());
     }
-    // whole-sequence multipliers on the folding context's stream
-    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult, d_tiles; DevBuf<uint8_t> d_records; DevBuf<uint32_t> d_idx;
-    if ((rc = d_tiles.alloc(multipliers_scratch((uint32_t)n, 1))) || (rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size())) || (rc = d_idx.alloc(n))) return rc;
-    H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-    H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-    if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p, d_tiles.p))) return rc;
-    H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
+    // whole-sequence multipliers on the folding context's stream.  A call of ONE group needs none: the whole sequence is the group's own
+    // (its proofs are the call's, in call order), and the group's upload makes exactly these multipliers from the draws themselves —
+    // no buffers, no second multiplier pass, no wait (a resident accumulator's leg of one key and one shape; the one-pairing entry
+    // points hand such a call to h2v_verify_batch and never come here with one group)
+    const bool own_draws = groups.size() == 1;
+    DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult, d_tiles; DevBuf<uint32_t> d_idx;
+    if (!own_draws) {
+        if ((rc = d_tiles.alloc(multipliers_scratch((uint32_t)n, 1))) || (rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_idx.alloc(n))) return rc;
+        H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
+        H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
+        if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p, d_tiles.p))) return rc;
+        H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
+    }
     // one batch object per key serves every shape group of that key (its buffers grow to the largest group's plan: ensure_buffers)
     for (auto& kv : of_key) {
         size_t max_group = 1, max_inst = 0;
@@ -274,19 +320,18 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         if ((rc = hold[kv.first]->take(max_group, max_inst))) return rc;
     }
     // the batch of every group: its key's scratch batch, or (identification, a key's later groups) a batch of its own for the call
-    struct Destroy { void operator()(h2v_batch* b) const { h2v_batch_destroy(b); } };
-    std::vector<std::unique_ptr<h2v_batch, Destroy>> own;
-    std::vector<h2v_batch*> on(groups.size());
+    std::vector<h2v_batch*>& on = held->on;
+    on.resize(groups.size());
     for (auto& kv : of_key)
         for (size_t r = 0; r < kv.second.size(); ++r) {
             const size_t gi = kv.second[r];
             on[gi] = hold[kv.first]->b;
-            if (!n_checks || r == 0) continue;
+            if (!resident || r == 0) continue;
             size_t inst = 0;
             for (size_t l : groups[gi].shape) inst += l;
             h2v_batch* b = nullptr;
             if ((rc = h2v_batch_create(ctxs[kv.first], groups[gi].idx.size(), inst, &b))) return rc;
-            own.emplace_back(b);
+            held->own.emplace_back(b);
             on[gi] = b;
         }
     // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
@@ -295,8 +340,8 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         ~Drain() { for (h2v_batch* b : bs) { if (b->stream) hipStreamSynchronize(b->stream); if (b->aux) hipStreamSynchronize(b->aux); } }
     } drain;
     drain.bs = on;
-    bool all_ok = true;
-    std::vector<std::vector<int>> st(groups.size());
+    all_ok = true;
+    st.assign(groups.size(), std::vector<int>());
     for (size_t r = 0; r < rounds; ++r) {
         for (auto& kv : of_key) {
             if (r >= kv.second.size()) continue;
@@ -305,8 +350,9 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
             ScratchBatch& sb = *hold[kv.first];
             const size_t m = grp.idx.size();
             if ((rc = pack_inputs(sb, m, grp.idx.data(), proofs, proof_lens, instances32, grp.shape.size(), grp.shape.data())) ||
-                (rc = enqueue_group(sb, on[gi], 0, m, 1, unit_draws(m).data(), 0, false, d_mult.p, d_idx.p + idx_off[gi])) ||
-                (rc = export_whole_records(on[gi], d_records.p + gi * H2V_ACC_RECORD_BYTES))) return rc;
+                (rc = own_draws ? enqueue_group(sb, on[gi], 0, m, 1, rand32, 0)
+                                : enqueue_group(sb, on[gi], 0, m, 1, unit_draws(m).data(), 0, false, d_mult.p, d_idx.p + idx_off[gi])) ||
+                (rc = export_whole_records(on[gi], d_records + gi * H2V_ACC_RECORD_BYTES))) return rc;
         }
         for (auto& kv : of_key) {
             if (r >= kv.second.size()) continue;
@@ -317,10 +363,32 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
         }
     }
     drain.bs.clear();   // (every group is finished)
+    return 0;
+}
+
+}  // namespace h2v
+
+namespace {
+
+// A grouped call closed by its own pairing: the groups' records (run_group_batches) folded into ONE pairing on the first group's context.
+// n_checks (identification, h2v_verify_batch_keys_identify): every group stays resident, and when the folded pairing itself fails, the
+// failing proofs are searched for over all groups at once (identify_search); the number of range checks it ran is ADDED to *n_checks.
+int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+               const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy,
+               size_t* n_checks = nullptr) {
+    h2v_ctx* fold_ctx = ctxs[groups[0].key];
+    int rc;
+    DevBuf<uint8_t> d_records;
+    H2V_HIP_CHECK(hipSetDevice(fold_ctx->device));
+    if ((rc = d_records.alloc(H2V_ACC_RECORD_BYTES * groups.size()))) return rc;
+    GroupsHeldPtr held;   // (declared after d_records: the batches go, and the contexts are released, before the records are freed)
+    std::vector<std::vector<int>> st;
+    bool all_ok = true;
+    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, d_records.p, n_checks != nullptr, held, st, all_ok))) return rc;
     int ok = 0, pairing_ok = 0;
     if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy, &pairing_ok))) return rc;
     // identification: only a failing pairing has failing proofs to find (a proof with a non-zero status contributes nothing to it)
-    if (n_checks && !pairing_ok && (rc = identify_search(on, st, n_checks))) return rc;
+    if (n_checks && !pairing_ok && (rc = identify_search(held->on, st, n_checks))) return rc;
     if (per_proof_status)
         for (size_t gi = 0; gi < groups.size(); ++gi)
             for (size_t j = 0; j < groups[gi].idx.size(); ++j) per_proof_status[groups[gi].idx[j]] = st[gi][j];
@@ -334,20 +402,10 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
 int verify_grouped(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
                    const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
                    int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t* n_checks = nullptr) {
-    const std::string w(who);
     // every argument check comes before the first HIP call
-    if (!ctxs || !n_keys || !n_instance_columns || (n && (!proofs || !proof_lens))) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    for (size_t k = 0; k < n_keys; ++k) {
-        if (!ctxs[k]) { set_last_error(w + ": null context"); return H2V_ERR_BAD_ARGUMENT; }
-        if (!ctxs[k]->vk) { set_last_error(w + ": a context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-        for (size_t j = 0; j < k; ++j) if (ctxs[j] == ctxs[k]) { set_last_error(w + ": the same context twice"); return H2V_ERR_BAD_ARGUMENT; }
-        if (ctxs[k]->device != ctxs[0]->device) { set_last_error(w + ": contexts on different devices"); return H2V_ERR_BAD_ARGUMENT; }
-        if (!same_srs(ctxs[k]->params, ctxs[0]->params)) { set_last_error(w + ": contexts over different params (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
-    }
-    for (size_t k = 0; k < n_keys; ++k) if (n_instance_columns[k] != ctx_total_instance_columns(ctxs[k])) { set_last_error(w + ": instances do not match a VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
     std::vector<CallGroup> groups;
     int rc;
-    if ((rc = group_proofs(who, n, n_keys, key_of_proof, n_instance_columns, col_lens, proofs, instances32, groups))) return rc;
+    if ((rc = grouped_call_args(who, ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, groups))) return rc;
     if (groups.empty()) groups.push_back({0, std::vector<size_t>(n_instance_columns[0], 0), {}});   // (no proofs: ctxs[0] over empty columns)
     std::vector<uint8_t> os_rand;
     if (n_checks) {

@@ -40,13 +40,7 @@ __global__ void k_point_to_bytes(const G1J* __restrict__ in, uint8_t* __restrict
     for (int j = 0; j < 64; ++j) out[64 * (size_t)i + j] = tmp[j];
 }
 
-// The record a rank contributes to a sharded batch (include/h2v.h H2V_ACC_RECORD_BYTES): the two accumulators of one group —
-// in the pieces the launch left them in (MsmSplit), or whole (parts = 1) — plus the number of the shard's proofs that failed
-// before the MSM.  A failed proof is zeroed out of its shard's accumulators, so without the count every OTHER rank's folded
-// pairing would still pass.
-struct AccRecord { uint32_t failed, parts, shift, reserved; G1J left[H2V_ACC_RECORD_PIECES], right[H2V_ACC_RECORD_PIECES]; };
-static_assert(sizeof(AccRecord) == H2V_ACC_RECORD_BYTES && H2V_ACC_RECORD_BYTES == 16 + 2 * H2V_ACC_RECORD_PIECES * 108, "accumulator record layout");
-static_assert(H2V_ACC_RECORD_PIECES >= MSM_MAX_PARTS, "a record holds every piece a launch can leave");
+// (AccRecord, the record a rank contributes to a sharded batch: internal.h)
 // acc: whole points [2g], [2g+1] (parts == 1) — or pieces: [(2g + side) * parts + j]
 __global__ void __launch_bounds__(256) k_export_records(const G1J* __restrict__ acc, const G1JSlot* __restrict__ pieces, uint32_t parts, uint32_t shift,
                                                         const int* __restrict__ status, uint32_t gs, AccRecord* __restrict__ out) {

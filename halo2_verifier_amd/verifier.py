@@ -518,6 +518,100 @@ def verify_batch_keys_identify(contexts, key_of_proof, proofs, instances, rand=N
     return bool(ok.value), list(st)[:n], left.raw, right.raw, checks.value
 
 
+def _seed_side(side):
+    """One channel of a DualMSM given as (scalars, bases) -> (scalar bytes, base bytes, n); everything the C side indexes is checked here"""
+    scalars, bases = side
+    scalars, bases = list(scalars), list(bases)
+    if len(scalars) != len(bases):
+        raise ValueError("scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
+    if any(not isinstance(b, (bytes, bytearray)) or len(b) != 64 for b in bases):
+        raise ValueError("every base must be 64 bytes (x | y)")
+    return b"".join(_scalar32(x) for x in scalars), b"".join(bytes(b) for b in bases), len(scalars)
+
+
+class Accumulator:
+    """A resident AccumulatorStrategy (h2v_accumulator): two G1 points that stay on the GPU across calls.  process() feeds proofs as
+    they arrive — any mix of VerifyingKeys and instance shapes over the context's params — and finalize() runs the one pairing whenever
+    the caller decides (kzg/strategy.rs:125-140).  process(A); process(B); finalize() equals verify_batch_keys over A + B with the draws
+    concatenated.  `context` supplies the device, the params and the pairing tables; it needs no VerifyingKey and must outlive the object."""
+
+    def __init__(self, context: Context):
+        if not isinstance(context, Context):
+            raise TypeError("Accumulator takes a Context")
+        self.ctx, self._lib = context, context._lib
+        self._h = ctypes.c_void_p()
+        check(self._lib.h2v_accumulator_create(context._h, ctypes.byref(self._h)))
+        if not hasattr(context, "_batches"):
+            import weakref
+            context._batches = weakref.WeakSet()
+        context._batches.add(self)   # Context.close() closes what lives on it first
+        self.last_all_ok = True
+
+    def close(self):
+        if self._h:
+            self._lib.h2v_accumulator_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, contexts, key_of_proof, proofs, instances, rand=None):
+        """n x verify_proof on this accumulator (h2v_accumulator_process): contexts[k] holds key k, proof i belongs to
+        contexts[key_of_proof[i]]; a single Context with key_of_proof=None is the one-key form.  instances / rand as verify_batch_keys.
+        Returns the statuses of this call's proofs; `last_all_ok` says whether all are 0.  A call that raises H2VError leaves the
+        accumulator as it was."""
+        one_key = isinstance(contexts, Context)
+        if one_key:
+            if key_of_proof is not None:
+                raise ValueError("a single Context takes key_of_proof=None")
+            contexts = [contexts]
+        else:
+            contexts = list(contexts)
+            if key_of_proof is None:
+                raise ValueError("a list of contexts takes one key index per proof")
+        n = len(proofs)
+        if (not one_key and len(key_of_proof) != n) or len(instances) != n:
+            raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {n if one_key else len(key_of_proof)} and {len(instances)}")
+        if not contexts:
+            raise ValueError("at least one context")
+        rb = _rand_bytes(rand, n)
+        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
+        ka = (ctypes.c_uint32 * max(n, 1))() if one_key else (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])   # (one key: every index 0)
+        ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
+        # column lengths proof by proof (a leg of one shape: that shape n times)
+        col_lens = _sizes(shapes[0] * n if n and all(l == shapes[0] for l in shapes) else [v for l in shapes for v in l])
+        st = (ctypes.c_int * max(n, 1))()
+        ok = ctypes.c_int(0)
+        check(self._lib.h2v_accumulator_process(self._h, ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), col_lens, rb, st,
+                                                ctypes.byref(ok)))
+        self.last_all_ok = bool(ok.value)
+        return list(st)[:n]
+
+    def add_msm(self, left, right):
+        """(L, R) += the two term lists evaluated, unscaled (h2v_accumulator_add_msm: AccumulatorStrategy::with on an empty accumulator,
+        DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""
+        l, r = _seed_side(left), _seed_side(right)
+        check(self._lib.h2v_accumulator_add_msm(self._h, *l, *r))
+
+    def read(self):
+        """-> (left_xy, right_xy, n_proofs, n_failed): the two points as affine bytes (zeros = identity) and the counters"""
+        left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+        n, f = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        check(self._lib.h2v_accumulator_read(self._h, left, right, ctypes.byref(n), ctypes.byref(f)))
+        return left.raw, right.raw, n.value, f.value
+
+    def finalize(self):
+        """-> (ok, left_xy, right_xy): ok = the pairing of (L, R) passes and no processed proof failed.  The accumulator is not
+        consumed: processing may go on, and finalize() may be called again."""
+        ok = ctypes.c_int(0)
+        left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+        check(self._lib.h2v_accumulator_finalize(self._h, ctypes.byref(ok), left, right))
+        return bool(ok.value), left.raw, right.raw
+
+
 def recheck_batches(batches, ranges):
     """Batch.recheck over ranges of several finished batches in one set of launches (h2v_batches_recheck).  batches: Batch objects on
     one device over the same params (keys and shapes may differ); ranges: list of (batch_index, first, count), each inside one group of

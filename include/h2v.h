@@ -223,6 +223,48 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n,
                             int* per_proof_status, int* batch_ok,
                             uint8_t out_left_xy[64], uint8_t out_right_xy[64]);
 
+/* ---- resident accumulator: an AccumulatorStrategy that lives across calls.  The strategy's DualMSM is two G1 points (L, R) that stay
+ * in device memory, both the identity at creation, plus two counters (proofs processed, proofs that failed).  Proofs are fed as they
+ * arrive, in any number of h2v_accumulator_process calls over any mix of VerifyingKeys and instance shapes over one SRS, and ONE
+ * pairing runs when the caller asks for it.  A process call of n proofs with draws r_0 .. r_{n-1} is n x (scale the accumulator by
+ * the draw, add the proof's Guard), kzg/strategy.rs:129-134:
+ *     (L, R) <- M (L, R) + sum_i (prod_{j > i} r_j) Guard_i,     M = r_0 r_1 .. r_{n-1}     (a failed proof contributes nothing)
+ * so process(A); process(B); finalize() equals, bit for bit, one h2v_verify_batch_keys over A || B with the draws concatenated: the
+ * verdict, the per-proof statuses and both accumulator points, for any cut and any number of calls.  No pairing runs, and no
+ * accumulator point passes through host memory, before finalize / read.
+ * Threading: one accumulator is used from one thread at a time; several accumulators may share a context. */
+typedef struct h2v_accumulator h2v_accumulator;
+/* An empty accumulator on ctx's device, over ctx's params.  ctx may have been created without a VK; it must outlive the accumulator.
+ *   replaces: AccumulatorStrategy::new (poly/kzg/strategy.rs:69-73). */
+int h2v_accumulator_create(h2v_ctx* ctx, h2v_accumulator** out);
+void h2v_accumulator_destroy(h2v_accumulator* a);
+/* n x verify_proof on this strategy.
+ *   replaces: the loop  s = verify_proof(&params, &vk_i, s, instances_i, transcript_i)?  (lib.rs:33-49, poly/kzg/strategy.rs:125-136).
+ * Takes the arguments of h2v_verify_batch_keys under its rules (contexts distinct, each with a VK, per-proof shapes allowed, at most
+ * 64 (key, instance shape) groups per call, rand32 NULL = OS draws); every context must be on the accumulator's device and over its
+ * params (g[0], g2 and s_g2 equal).  Every argument check runs before any device work.  per_proof_status[i]: as h2v_verify_batch;
+ * all_ok: 1 when every status of THIS call is 0.  n == 0 changes nothing.  A call that returns non-zero leaves the accumulator and the
+ * counters exactly as they were: the scaled accumulator goes to a staging record and the accumulator is written by the call's last step.
+ * The call holds every context (and its one-shot scratch batch) for its whole duration, taken in one global order. */
+int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n,
+                            const uint8_t* const* proofs, const size_t* proof_lens,
+                            const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                            const uint8_t* rand32, int* per_proof_status, int* all_ok);
+/* (L, R) += (sum left_scalars[i] left_bases[i], sum right_scalars[i] right_bases[i]), unscaled; on an empty accumulator this starts
+ * from an existing DualMSM.
+ *   replaces: AccumulatorStrategy::with(msm_accumulator) (poly/kzg/strategy.rs:76-78), DualMSM::add_msm (poly/kzg/msm.rs:179-183).
+ * Scalars 32-byte canonical, bases 64-byte x | y on the curve or all-zero (the identity), as the seed of h2v_verify_batch_seeded: a
+ * violation is H2V_ERR_BAD_ARGUMENT and changes nothing.  Either list may be empty. */
+int h2v_accumulator_add_msm(h2v_accumulator* a,
+                            const uint8_t* left_scalars32, const uint8_t* left_bases64, size_t n_left,
+                            const uint8_t* right_scalars32, const uint8_t* right_bases64, size_t n_right);
+/* The two points as affine bytes (all-zero = identity) and the counters; any pointer but `a` may be NULL. */
+int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_proofs, size_t* n_failed);
+/* ok = the pairing check of (L, R) passes AND no processed proof failed — what batch_ok means for h2v_verify_batch.
+ *   replaces: AccumulatorStrategy::finalize (poly/kzg/strategy.rs:138-140).
+ * The accumulator is not consumed and not changed: the caller may go on processing, or finalize again. */
+int h2v_accumulator_finalize(h2v_accumulator* a, int* ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]);
+
 /* N x verify_proof under SingleStrategy (one pairing per proof; poly/kzg/strategy.rs:164-176).
  * per_proof_status[i] = 0, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE when that proof's pairing fails,
  * or the transcript/opening error. */

@@ -15,6 +15,8 @@
 //   AccumulatorStrategy::{new, process, finalize}                 AccumulatorStrategy(params): verify_proof() queues,
 //                                         kzg/strategy.rs:99-141    finalize() runs the batch on the GPU
 //   SingleStrategy                        kzg/strategy.rs:143-181 SingleStrategy(params): verify_proof() runs at once
+//   AccumulatorStrategy used incrementally (process per proof,    Accumulator(context): process() runs a run of proofs at once into
+//     finalize when the caller decides, with)  kzg/strategy.rs:69-140   two points resident on the GPU; add_msm(), read(), finalize()
 //   VerifierSHPLONK / VerifierGWC, Blake2bRead / Keccak256Read    MultiOpen, TranscriptKind (generic parameters of lib.rs:33-40)
 //
 // There is no CPU fallback: constructing a Context without a HIP device throws Failure{H2V_ERR_DEVICE}.
@@ -243,6 +245,75 @@ private:
     Bytes seed_ls_, seed_lb_, seed_rs_, seed_rb_;
     std::vector<int> statuses_;
     size_t range_checks_ = 0;
+    uint8_t left_[64] = {0}, right_[64] = {0};
+};
+
+// A resident AccumulatorStrategy (h2v_accumulator): the strategy's two accumulator points stay on the GPU across calls.  process()
+// feeds proofs as they arrive — any mix of keys (a Context each) and instance shapes over the context's params — and finalize() runs the
+// one pairing whenever the caller decides (kzg/strategy.rs:125-140): process(A); process(B); finalize() equals one AccumulatorStrategy
+// over A then B with the draws concatenated.  The context supplies the device, the params and the pairing tables, and must outlive the object.
+class Accumulator {
+public:
+    struct Item { uint32_t key; Instances instances; Bytes proof; };   // proof of contexts[key]
+    explicit Accumulator(const Context& ctx) { check(h2v_accumulator_create(ctx.handle(), &h_)); }
+    ~Accumulator() { h2v_accumulator_destroy(h_); }
+    Accumulator(const Accumulator&) = delete;
+    Accumulator& operator=(const Accumulator&) = delete;
+    // n x verify_proof on this accumulator; rand32: one 32-byte draw per item, or empty = OS RNG.  -> the statuses of this call's proofs
+    // (all_ok(): whether all are 0).  A Failure leaves the accumulator as it was.
+    std::vector<int> process(const std::vector<const Context*>& contexts, const std::vector<Item>& items, const Bytes& rand32 = Bytes()) {
+        if (contexts.empty()) throw Failure(H2V_ERR_BAD_ARGUMENT, "at least one context");
+        if (!rand32.empty() && rand32.size() != 32 * items.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
+        std::vector<h2v_ctx*> handles;
+        std::vector<size_t> ncols(contexts.size(), 0);
+        for (size_t k = 0; k < contexts.size(); ++k) {
+            handles.push_back(contexts[k]->handle());
+            check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
+        }
+        std::vector<uint32_t> keys;
+        std::vector<const uint8_t*> proofs, insts;
+        std::vector<size_t> lens, col_lens;
+        std::vector<Bytes> flat(items.size());
+        for (size_t i = 0; i < items.size(); ++i) {
+            const Item& it = items[i];
+            if (it.key >= contexts.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "key index out of range");
+            if (it.instances.size() != ncols[it.key]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
+            for (const Column& c : it.instances) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
+            keys.push_back(it.key); proofs.push_back(it.proof.data()); lens.push_back(it.proof.size()); insts.push_back(flat[i].data());
+        }
+        std::vector<int> st(items.size() ? items.size() : 1, 0);
+        int ok = 0;
+        check(h2v_accumulator_process(h_, handles.data(), handles.size(), keys.data(), items.size(), proofs.data(), lens.data(), insts.data(), ncols.data(),
+                                      col_lens.data(), rand32.empty() ? nullptr : rand32.data(), st.data(), &ok));
+        all_ok_ = ok != 0;
+        st.resize(items.size());
+        return st;
+    }
+    bool all_ok() const { return all_ok_; }
+    // AccumulatorStrategy::with / DualMSM::add_msm: (L, R) += the two term lists evaluated, unscaled — scalars 32 bytes each, bases 64 bytes (x | y) each
+    void add_msm(const Bytes& left_scalars, const Bytes& left_bases, const Bytes& right_scalars, const Bytes& right_bases) {
+        if (left_scalars.size() % 32 || left_bases.size() != 2 * left_scalars.size() || right_scalars.size() % 32 || right_bases.size() != 2 * right_scalars.size())
+            throw Failure(H2V_ERR_BAD_ARGUMENT, "a channel is n 32-byte scalars and n 64-byte bases");
+        check(h2v_accumulator_add_msm(h_, left_scalars.data(), left_bases.data(), left_scalars.size() / 32, right_scalars.data(), right_bases.data(),
+                                      right_scalars.size() / 32));
+    }
+    // the two points as canonical x | y (left(), right(); all-zero = identity) and the counters
+    void read() { check(h2v_accumulator_read(h_, left_, right_, &n_proofs_, &n_failed_)); }
+    // -> true iff the pairing of (L, R) passes and no processed proof failed; left() / right() hold the points.  The accumulator is not consumed.
+    bool finalize() {
+        int ok = 0;
+        check(h2v_accumulator_finalize(h_, &ok, left_, right_));
+        return ok != 0;
+    }
+    const uint8_t* left() const { return left_; }
+    const uint8_t* right() const { return right_; }
+    size_t n_proofs() const { return n_proofs_; }   // as of the last read()
+    size_t n_failed() const { return n_failed_; }
+
+private:
+    h2v_accumulator* h_ = nullptr;
+    bool all_ok_ = true;
+    size_t n_proofs_ = 0, n_failed_ = 0;
     uint8_t left_[64] = {0}, right_[64] = {0};
 };
 

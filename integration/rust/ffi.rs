@@ -7,6 +7,7 @@ use core::ffi::{c_char, c_float, c_int, c_void};
 
 #[repr(C)] pub struct h2v_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct h2v_batch { _p: [u8; 0] }
+#[repr(C)] pub struct h2v_accumulator { _p: [u8; 0] }
 /// struct_size: `core::mem::size_of::<h2v_options>()` (the library rejects a layout it does not know);
 /// multiopen: VerifierSHPLONK / VerifierGWC; transcript: Blake2bRead / Keccak256Read; circuit_instances: `instances.len()` of
 /// verify_proof (0 or 1 = one circuit instance per transcript); instance_kernel_threshold: debug, 0 = default
@@ -76,6 +77,16 @@ extern "C" {
                                    seed_left_scalars32: *const u8, seed_left_bases64: *const u8, n_seed_left: usize,
                                    seed_right_scalars32: *const u8, seed_right_bases64: *const u8, n_seed_right: usize,
                                    per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
+    pub fn h2v_accumulator_create(ctx: *mut h2v_ctx, out: *mut *mut h2v_accumulator) -> c_int;
+    pub fn h2v_accumulator_destroy(a: *mut h2v_accumulator);
+    pub fn h2v_accumulator_process(a: *mut h2v_accumulator, ctxs: *const *mut h2v_ctx, n_keys: usize, key_of_proof: *const u32, n: usize,
+                                   proofs: *const *const u8, proof_lens: *const usize, instances32: *const *const u8,
+                                   n_instance_columns: *const usize, col_lens: *const usize, rand32: *const u8,
+                                   per_proof_status: *mut c_int, all_ok: *mut c_int) -> c_int;
+    pub fn h2v_accumulator_add_msm(a: *mut h2v_accumulator, left_scalars32: *const u8, left_bases64: *const u8, n_left: usize,
+                                   right_scalars32: *const u8, right_bases64: *const u8, n_right: usize) -> c_int;
+    pub fn h2v_accumulator_read(a: *mut h2v_accumulator, out_left_xy: *mut u8, out_right_xy: *mut u8, n_proofs: *mut usize, n_failed: *mut usize) -> c_int;
+    pub fn h2v_accumulator_finalize(a: *mut h2v_accumulator, ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_verify_each(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, per_proof_status: *mut c_int) -> c_int;
     pub fn h2v_verify_batch_identify(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,

@@ -4,6 +4,8 @@
 //!                               (halo2_verifier/src/lib.rs:33-49, poly/kzg/strategy.rs:125-140) in one call.
 //! * `GpuMultiKeyVerifier`     — the same seam over several VerifyingKeys sharing the params: one context per key,
 //!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
+//! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
+//!                               sharing the params; `finalize` whenever the caller decides (h2v_accumulator_*).
 //! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) whose `finalize`
 //!                               evaluates the two `MSMKZG` channels and the pairing on the GPU
 //!                               (poly/kzg/msm.rs:81-86, 185-203) while `verify_proof` itself stays on the CPU.
@@ -163,6 +165,98 @@ impl<'p> GpuMultiKeyVerifier<'p> {
     }
 }
 impl<'p> Drop for GpuMultiKeyVerifier<'p> { fn drop(&mut self) { for &c in &self.ctxs { unsafe { h2v_ctx_destroy(c) } } } }
+
+/// The incremental seam: `AccumulatorStrategy` as the reference uses it — `verify_proof` per proof as proofs arrive, any `vk` over the
+/// same params on every call, `finalize` whenever the caller decides (poly/kzg/strategy.rs:125-140) — with the two accumulator points
+/// resident on the GPU between calls (h2v_accumulator_*).  `process` feeds a run of proofs; `process(a); process(b); finalize()` equals
+/// one `GpuMultiKeyVerifier` over `a` then `b`.
+pub struct GpuResidentAccumulator {
+    ctxs: Vec<*mut h2v_ctx>,
+    n_cols: Vec<usize>,
+    acc: *mut h2v_accumulator,
+}
+
+impl GpuResidentAccumulator {
+    /// `AccumulatorStrategy::new(params)`: one context per key (key index = position in `vks`, at least one), an empty accumulator.
+    pub fn new(params: &ParamsKZG<Bn256>, vks: &[&VerifyingKey<G1Affine>], device: i32) -> Result<Self, Error> {
+        let mut pb = Vec::new();
+        params.write_custom(&mut pb, SerdeFormat::RawBytes).map_err(|_| Error::Opening)?;
+        let mut me = Self { ctxs: Vec::new(), n_cols: Vec::new(), acc: core::ptr::null_mut() };
+        for vk in vks {
+            let mut vb = Vec::new();
+            vk.write(&mut vb, SerdeFormat::RawBytes).map_err(|_| Error::Opening)?;
+            let mut ctx = core::ptr::null_mut();
+            let rc = unsafe { h2v_ctx_create(pb.as_ptr(), pb.len(), H2V_SERDE_RAW_BYTES, vb.as_ptr(), vb.len(), H2V_SERDE_RAW_BYTES, device, &mut ctx) };
+            if rc != 0 { return Err(map_err(rc)); }   // (what was made so far goes with `me`)
+            me.ctxs.push(ctx);
+            let mut ncols = 0usize;
+            let rc = unsafe { h2v_ctx_proof_shape(ctx, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), &mut ncols) };
+            if rc != 0 { return Err(map_err(rc)); }
+            me.n_cols.push(ncols);
+        }
+        if me.ctxs.is_empty() { return Err(Error::InvalidInstances); }
+        let rc = unsafe { h2v_accumulator_create(me.ctxs[0], &mut me.acc) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(me)
+    }
+
+    /// `AccumulatorStrategy::with(msm_accumulator)` / `DualMSM::add_msm`: adds the evaluated channels of `msm`, unscaled.
+    pub fn add_msm(&mut self, left: &[(Fr, G1Affine)], right: &[(Fr, G1Affine)]) -> Result<(), Error> {
+        fn flat(terms: &[(Fr, G1Affine)]) -> (Vec<u8>, Vec<u8>) {
+            let (mut s, mut b) = (Vec::new(), Vec::new());
+            for (k, p) in terms {
+                s.extend_from_slice(k.to_repr().as_ref());
+                let c = p.coordinates();
+                if bool::from(c.is_some()) { let c = c.unwrap(); b.extend_from_slice(c.x().to_repr().as_ref()); b.extend_from_slice(c.y().to_repr().as_ref()); }
+                else { b.extend_from_slice(&[0u8; 64]); }
+            }
+            (s, b)
+        }
+        let ((ls, lb), (rs, rb)) = (flat(left), flat(right));
+        let rc = unsafe { h2v_accumulator_add_msm(self.acc, ls.as_ptr(), lb.as_ptr(), left.len(), rs.as_ptr(), rb.as_ptr(), right.len()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
+    }
+
+    /// One `verify_proof(&params, vks[key], strategy, &[instances], &mut Blake2bRead::init(proof))` call per item, in order:
+    /// `(key, proof, instances)`.  Returns the verdict of every proof of this call (`Ok(())` or the `Error` of its `verify_proof`).
+    /// An `Err` of the call itself leaves the accumulator as it was.
+    pub fn process(&mut self, items: &[(usize, &[u8], &[&[Fr]])]) -> Result<Vec<Result<(), Error>>, Error> {
+        let n = items.len();
+        let (mut keys, mut col_lens, mut flats) = (Vec::with_capacity(n), Vec::new(), Vec::with_capacity(n));
+        for (key, _, instances) in items {
+            if *key >= self.ctxs.len() || instances.len() != self.n_cols[*key] { return Err(Error::InvalidInstances); }
+            let mut flat = Vec::with_capacity(32 * instances.iter().map(|c| c.len()).sum::<usize>());
+            for col in instances.iter() { for v in col.iter() { flat.extend_from_slice(v.to_repr().as_ref()); } }
+            col_lens.extend(instances.iter().map(|c| c.len()));
+            keys.push(*key as u32);
+            flats.push(flat);
+        }
+        let ptrs: Vec<*const u8> = items.iter().map(|(_, p, _)| p.as_ptr()).collect();
+        let lens: Vec<usize> = items.iter().map(|(_, p, _)| p.len()).collect();
+        let iptrs: Vec<*const u8> = flats.iter().map(|i| i.as_ptr()).collect();
+        let (mut status, mut ok) = (vec![0i32; n.max(1)], 0i32);
+        let rc = unsafe { h2v_accumulator_process(self.acc, self.ctxs.as_ptr(), self.ctxs.len(), keys.as_ptr(), n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(),
+                                                  self.n_cols.as_ptr(), col_lens.as_ptr(), core::ptr::null(), status.as_mut_ptr(), &mut ok) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(status[..n].iter().map(|&s| if s == 0 { Ok(()) } else { Err(map_err(s)) }).collect())
+    }
+
+    /// `strategy.finalize()`: true iff every processed proof was well formed and the single pairing check passes.  The accumulator is
+    /// not consumed: processing may go on afterwards.
+    pub fn finalize(&mut self) -> Result<bool, Error> {
+        let mut ok = 0i32;
+        let rc = unsafe { h2v_accumulator_finalize(self.acc, &mut ok, core::ptr::null_mut(), core::ptr::null_mut()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(ok == 1)
+    }
+}
+impl Drop for GpuResidentAccumulator {
+    fn drop(&mut self) {
+        unsafe { h2v_accumulator_destroy(self.acc) }   // (the accumulator goes before the context it lives on; null is allowed)
+        for &c in &self.ctxs { unsafe { h2v_ctx_destroy(c) } }
+    }
+}
 
 /// Trait seam: same `process` as AccumulatorStrategy (kzg/strategy.rs:125-136); `finalize` on the GPU.
 pub struct GpuAccumulatorStrategy<'params> { acc: DualMSM<'params, Bn256>, ctx: *mut h2v_ctx }

@@ -1,0 +1,149 @@
+"""Cost of feeding proofs to a resident accumulator (h2v_accumulator_process x K + h2v_accumulator_finalize) against what the library
+offered before it.  Median wall times of --reps runs, host proofs in, one MI355X:
+   python tools/accumulator_probe.py [--k 14] [--reps 7] [--out FILE] [--library PATH] [--baseline-only] [--trace]
+1. legs:     K = 8 legs of 64 and of 1024 proofs of one key (the k = 14 pool bench.py caches; a leg is the pool's first proofs, every leg
+             under draws of its own).  Baseline: the chain of K h2v_verify_batch_seeded calls, each resuming from the (L, R) bytes of the
+             one before — the only way to continue an accumulation without the accumulator.
+2. one leg:  one process of 1024 proofs of one key against h2v_verify_batch of the same proofs (which runs a pairing; process does not).
+3. (--trace) a few process calls only, for a `rocprofv3 --kernel-trace --stats -- python tools/accumulator_probe.py --trace` run that
+             gives k_accumulator_scale's own duration.
+4. two keys: 2 x 512 interleaved proofs of two k = 8 vector-mul keys in 4 legs against ONE h2v_verify_batch_keys over all 1024.
+--library PATH loads another build of libh2v_amd.so; --baseline-only times the baselines alone (a build without the accumulator)."""
+import argparse, json, os, random, sys, time
+sys.path.insert(0, "."); sys.path.insert(0, "tests")
+import bench
+bench.hw_queue_env()
+from halo2_verifier_amd import _lib
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--k", type=int, default=14)
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--out", default=None)
+ap.add_argument("--library", default=None)
+ap.add_argument("--baseline-only", action="store_true")
+ap.add_argument("--trace", action="store_true")
+args = ap.parse_args()
+if args.library:
+    _lib.lib_path = lambda: os.path.abspath(args.library)
+if args.baseline_only:   # a build from before the accumulator exports none of its symbols
+    for name in [s for s in _lib.SIGNATURES if s.startswith("h2v_accumulator_")]:
+        del _lib.SIGNATURES[name]
+import halo2_verifier_amd as h2v
+
+R_MOD = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
+RAW = h2v.SerdeFormat.RawBytes
+K = 8
+
+
+def timed(fn):
+    fn()   # warm-up: plans, scratch batches, workspaces
+    ts = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter(); r = fn(); ts.append((time.perf_counter() - t0) * 1e3)
+    return sorted(ts)[len(ts) // 2], r
+
+
+n, N = 1024, bench.N_PUBLIC
+d = bench.load_or_make_proofs(n, args.k, print)
+ctx = h2v.Context(h2v.ParamsKZG(d["params"], RAW), h2v.VerifyingKey(d["vk"], RAW))
+P = [d["proofs"][1024 * i:1024 * (i + 1)] for i in range(n)]
+I = [[[d["inst"][32 * (N * i + j):32 * (N * i + j + 1)] for j in range(N)]] for i in range(n)]
+rnd = random.Random(2025)
+draws = [[rnd.randrange(1, R_MOD) for _ in range(n)] for _ in range(K)]
+
+
+def seeded_chain(m):
+    """K legs of the pool's first m proofs through h2v_verify_batch_seeded, each from the bytes of the one before"""
+    L = R = None
+    ok = True
+    for j in range(K):
+        seed = (([], []), ([], [])) if L is None else (([1], [L]), ([1], [R]))
+        okj, _, L, R = ctx.verify_batch(P[:m], I[:m], draws[j][:m], seed=seed)
+        ok = ok and okj
+    return ok, L, R
+
+
+def accumulator_legs(m):
+    acc = h2v.Accumulator(ctx)
+    for j in range(K):
+        acc.process(ctx, None, P[:m], I[:m], draws[j][:m])
+    r = acc.finalize()
+    acc.close()
+    return r
+
+
+res = {"k": args.k, "reps": args.reps, "legs": K, "library": args.library or "in-tree", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+if args.trace:
+    acc = h2v.Accumulator(ctx)
+    for j in range(K):
+        acc.process(ctx, None, P, I, draws[j])
+    assert acc.finalize()[0]
+    acc.close()
+    ctx.close()
+    sys.exit(0)
+
+res["legs_ms"] = {}
+for m in (64, 1024):
+    t0, want = timed(lambda: seeded_chain(m))
+    assert want[0]
+    row = {"seeded_chain_ms": round(t0, 3)}
+    line = f"{K} legs of {m:4d}: seeded chain {t0:9.3f} ms"
+    if not args.baseline_only:
+        t1, got = timed(lambda: accumulator_legs(m))
+        assert got == want, "the accumulator's legs and the seeded chain disagree"
+        row["accumulator_ms"] = round(t1, 3)
+        line += f"   process x {K} + finalize {t1:9.3f} ms   ({t1 / t0:.3f}x)"
+    res["legs_ms"][m] = row
+    print(line, flush=True)
+
+t0, r = timed(lambda: ctx.verify_batch(P, I, draws[0]))
+assert r[0]
+res["one_leg_ms"] = {"verify_batch_ms": round(t0, 3)}
+line = f"one leg of 1024: verify_batch {t0:9.3f} ms"
+if not args.baseline_only:
+    acc = h2v.Accumulator(ctx)
+    acc.process(ctx, None, P[:8], I[:8], draws[1][:8])   # (a non-empty accumulator: the scale step has points to scale)
+    t1, st = timed(lambda: acc.process(ctx, None, P, I, draws[0]))
+    assert st == [0] * n and acc.finalize()[0]
+    acc.close()
+    res["one_leg_ms"]["process_ms"] = round(t1, 3)
+    line += f"   process {t1:9.3f} ms   ({t1 / t0:.3f}x)"
+print(line, flush=True)
+ctx.close()
+
+# two keys at k = 8 (the bench pool has one key)
+import circuits
+POOL = 64
+setups = [circuits.setup_vector_mul(8, m) for m in (8, 7)]
+pools = [circuits.prove_vector_mul_batch(s, POOL, seed=100 + k, threads=16) for k, s in enumerate(setups)]
+ctxs = [h2v.Context(h2v.ParamsKZG(s.params, RAW), h2v.VerifyingKey(s.vk, RAW)) for s in setups]
+keys = [i % 2 for i in range(n)]
+P2 = [pools[k][0][(i // 2) % POOL] for i, k in enumerate(keys)]
+I2 = [pools[k][1][(i // 2) % POOL] for i, k in enumerate(keys)]
+t0, want = timed(lambda: h2v.verify_batch_keys(ctxs, keys, P2, I2, draws[0]))
+assert want[0]
+res["two_keys_ms"] = {"verify_batch_keys_ms": round(t0, 3)}
+line = f"two keys, 1024:  verify_batch_keys {t0:9.3f} ms"
+if not args.baseline_only:
+    def four_legs():
+        acc = h2v.Accumulator(ctxs[0])
+        st = []
+        for a in range(0, n, n // 4):
+            st += acc.process(ctxs, keys[a:a + n // 4], P2[a:a + n // 4], I2[a:a + n // 4], draws[0][a:a + n // 4])
+        ok, left, right = acc.finalize()
+        acc.close()
+        return ok, st, left, right
+    t1, got = timed(four_legs)
+    assert got == want
+    res["two_keys_ms"]["four_legs_ms"] = round(t1, 3)
+    line += f"   4 legs of 256 + finalize {t1:9.3f} ms   ({t1 / t0:.3f}x)"
+print(line, flush=True)
+print(json.dumps(res))
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+for c in ctxs:
+    c.close()
+for s in setups:
+    s.free()
