@@ -13,9 +13,22 @@
 //   - one fold over [staging record, group records ..] writes the accumulator, as the last step: a call that fails before it leaves
 //     the accumulator and the counters as they were.
 // No pairing runs before finalize, and no accumulator point goes through host memory.
+//
+// The leg journal (h2v_accumulator_journal_begin; off by default, and then nothing below differs).  A proof that is wrong but decodes and
+// passes its transcript poisons (L, R) with every status 0.  With the journal on, every successful call that changed the accumulator
+// leaves an entry: its own sum (l, r) in a device slot of two points — one more fold over the call's group records WITHOUT the staging
+// record — and on the host M and the call's counters.  Entry 0, the base, is the accumulator as it stood at journal_begin.  Invariant:
+//     (L, R) = sum_e W_e sum_e,     W_e = prod_{f > e} M_f
+//   - check_legs: one pairing_check_enqueue over the slots, a check per entry side by side.
+//   - drop_legs: the host makes W_e of the kept entries, one k_accumulator_scale launch (an item per kept entry) writes W_e sum_e as
+//     whole-point records, one fold over them writes the accumulator as the last step; the host's bookkeeping follows the synchronise.
+// Entries never move in device memory: the host keeps entry -> slot and hands that map to the kernels, so a call that fails on the way
+// leaves nothing half-moved.  A slot is written before its entry is visible (the commit rule of the accumulator, extended).
 #include "../../include/h2v.h"
 #include "batch.h"
 #include <string.h>
+#include <algorithm>
+#include <functional>
 
 using namespace h2v;
 
@@ -25,12 +38,21 @@ struct h2v_accumulator {
     DevBuf<G1J> acc;                 // [0] left, [1] right: whole Jacobian points
     DevBuf<uint8_t> records;         // [0] the staging record (the scaled accumulator), [1 ..] the records of a call's groups (at most H2V_MAX_SHAPES_PER_CALL)
     DevBuf<uint32_t> scalar;         // M of the call in flight, 8 canonical words
-    DevBuf<uint32_t> words;          // [0] fold_failed, [1] the pairing's verdict, [2, 3] identity flags of the two points, [4, 5] add_msm's base flags
+    DevBuf<uint32_t> words;          // [0] fold_failed, [1] the pairing's verdict, [2, 3] identity flags of the two points, [4, 5] add_msm's base flags, [6] an entry fold's fold_failed
     DevBuf<uint8_t> bytes;           // the affine bytes of the two points (read / finalize); add_msm: the evaluated channels on their way in
     DevBuf<G1A> affine;              // add_msm
     DevBuf<G1J> jacobian;            // add_msm
     uint32_t host_scalar[8] = {0};   // what `scalar` is copied from (it outlives the copy)
     size_t n_proofs = 0, n_failed = 0;
+    // the leg journal
+    struct Entry { uint32_t slot; Fr M; size_t n_proofs, n_failed; };
+    size_t j_cap = 0;                // entries the journal holds, the base included; 0 = off
+    std::vector<Entry> entries;      // [0] the base
+    std::vector<uint32_t> free_slots;   // descending: the lowest free slot is taken first, so the slots in use stay at the front
+    DevBuf<G1J> j_sums;              // [2 j_cap] slot s: the sum (l, r) of the entry that owns it
+    DevBuf<uint8_t> j_records;       // [j_cap] drop_legs: W_e sum_e of the kept entries as whole-point records
+    DevBuf<uint32_t> j_words;        // drop_legs: [8 K] W_e of the K kept entries, [K] their slots; check_legs: [9 j_cap ..] a verdict per slot
+    std::vector<uint32_t> j_host;    // what j_words is copied from and to
 };
 
 namespace {
@@ -58,6 +80,17 @@ int read_points(h2v_accumulator* a, const char* who, int* ok, uint8_t* out_left,
     return 0;
 }
 
+// the slot the next entry will own, or (journal off) null; the caller has checked that the journal is not full
+G1J* next_slot(h2v_accumulator* a) { return a->j_cap ? a->j_sums.p + 2 * (size_t)a->free_slots.back() : nullptr; }
+bool journal_full(const h2v_accumulator* a) { return a->j_cap && a->entries.size() >= a->j_cap; }
+// the entry of a call that has just succeeded becomes visible
+void commit_entry(h2v_accumulator* a, const Fr& M, size_t n_proofs, size_t n_failed) {
+    if (!a->j_cap) return;
+    a->entries.push_back({a->free_slots.back(), M, n_proofs, n_failed});
+    a->free_slots.pop_back();
+}
+void journal_off(h2v_accumulator* a) { a->j_cap = 0; a->entries.clear(); a->free_slots.clear(); }
+
 }  // namespace
 
 extern "C" {
@@ -76,7 +109,7 @@ int h2v_accumulator_create(h2v_ctx* ctx, h2v_accumulator** out) {
     H2V_HIP_CHECK(hipStreamCreateWithPriority(&a->stream, hipStreamNonBlocking, greatest));
     int rc;
     if ((rc = a->acc.alloc(2)) || (rc = a->records.alloc((size_t)H2V_ACC_RECORD_BYTES * (1 + H2V_MAX_SHAPES_PER_CALL))) || (rc = a->scalar.alloc(8)) ||
-        (rc = a->words.alloc(6)) || (rc = a->bytes.alloc(128)) || (rc = a->affine.alloc(2)) || (rc = a->jacobian.alloc(2))) return rc;
+        (rc = a->words.alloc(7)) || (rc = a->bytes.alloc(128)) || (rc = a->affine.alloc(2)) || (rc = a->jacobian.alloc(2))) return rc;
     const G1J empty[2] = {G1J::identity(), G1J::identity()};   // AccumulatorStrategy::new: an empty DualMSM
     H2V_HIP_CHECK(hipMemcpyAsync(a->acc.p, empty, sizeof(empty), hipMemcpyHostToDevice, a->stream));
     if ((rc = sync(a.get(), "h2v_accumulator_create"))) return rc;
@@ -107,7 +140,8 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     std::vector<uint8_t> os_rand;
     if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
     if (all_ok) *all_ok = 1;
-    if (!n) return 0;   // no verify_proof: no scale, no Guard
+    if (!n) return 0;   // no verify_proof: no scale, no Guard, no entry
+    if (journal_full(a)) { set_last_error(std::string(who) + ": the journal is full"); return H2V_ERR_UNSUPPORTED; }
     // M, the product of the call's draws (host: n Fr products)
     Fr M = Fr::one();
     for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
@@ -125,6 +159,9 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     std::vector<std::vector<int>> st;
     bool groups_ok = true;
     if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, a->records.p + H2V_ACC_RECORD_BYTES, false, held, st, groups_ok))) return rc;
+    // the journal's entry: the groups' records alone, into a slot no entry owns yet
+    if (G1J* slot = next_slot(a))
+        if ((rc = fold_records_enqueue(a->stream, a->records.p + H2V_ACC_RECORD_BYTES, (uint32_t)groups.size(), 1, 1, 0, slot, nullptr, nullptr, a->words.p + 6))) return rc;
     // the commit: (L, R) <- staging record + the groups' records
     if ((rc = fold_records_enqueue(a->stream, a->records.p, (uint32_t)(1 + groups.size()), 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) return rc;
     drain.armed = false;
@@ -136,6 +173,7 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
             if (per_proof_status) per_proof_status[groups[gi].idx[j]] = st[gi][j];
         }
     a->n_proofs += n; a->n_failed += failed;
+    commit_entry(a, M, n, failed);
     if (all_ok) *all_ok = failed ? 0 : 1;
     return 0;
 }
@@ -152,6 +190,7 @@ int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, c
             Fr v;
             if (!Fr::from_bytes(sc[side] + 32 * j, v)) { set_last_error(std::string(who) + ": scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
         }
+    if (journal_full(a)) { set_last_error(std::string(who) + ": the journal is full"); return H2V_ERR_UNSUPPORTED; }
     // both channels are evaluated (h2v_msm_g1 rejects bases that are not on the curve) before anything of the accumulator changes
     int rc, ident = 0;
     uint8_t xy[128];
@@ -163,10 +202,13 @@ int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, c
     H2V_HIP_CHECK(hipMemcpyAsync(a->bytes.p, xy, 128, hipMemcpyHostToDevice, s));
     if ((rc = bases_from_bytes_enqueue(s, a->bytes.p, a->affine.p, a->words.p + 4, 2)) ||
         (rc = affine_to_jacobian_enqueue(s, a->affine.p, a->jacobian.p, 2)) ||
+        (rc = affine_to_jacobian_enqueue(s, a->affine.p, next_slot(a), next_slot(a) ? 2 : 0)) ||   // the journal's entry: the two sums
         (rc = export_records_enqueue(s, a->acc.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p)) ||
         (rc = export_records_enqueue(s, a->jacobian.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p + H2V_ACC_RECORD_BYTES)) ||
         (rc = fold_records_enqueue(s, a->records.p, 2, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) { hipStreamSynchronize(s); return rc; }
-    return sync(a, who);
+    if ((rc = sync(a, who))) return rc;
+    commit_entry(a, Fr::one(), 0, 0);
+    return 0;
 }
 
 int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_proofs, size_t* n_failed) {
@@ -180,6 +222,97 @@ int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t ou
 int h2v_accumulator_finalize(h2v_accumulator* a, int* ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
     if (!a || !ok) { set_last_error("h2v_accumulator_finalize: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     return read_points(a, "h2v_accumulator_finalize", ok, out_left_xy, out_right_xy);
+}
+
+int h2v_accumulator_journal_begin(h2v_accumulator* a, size_t capacity) {
+    const char* who = "h2v_accumulator_journal_begin";
+    if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (capacity == 1 || capacity > H2V_ACC_JOURNAL_MAX) { set_last_error(std::string(who) + ": capacity must be 0 or in [2, H2V_ACC_JOURNAL_MAX]"); return H2V_ERR_BAD_ARGUMENT; }
+    journal_off(a);
+    if (!capacity) return 0;
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    int rc;
+    if ((rc = a->j_sums.reserve(2 * capacity)) || (rc = a->j_records.reserve((size_t)H2V_ACC_RECORD_BYTES * capacity)) || (rc = a->j_words.reserve(10 * capacity))) return rc;
+    // every slot starts as a pair of identities (check_legs reads the slots up to the highest one in use); slot 0 <- the base
+    const std::vector<G1J> empty(2 * capacity, G1J::identity());
+    H2V_HIP_CHECK(hipMemcpyAsync(a->j_sums.p, empty.data(), empty.size() * sizeof(G1J), hipMemcpyHostToDevice, a->stream));
+    H2V_HIP_CHECK(hipMemcpyAsync(a->j_sums.p, a->acc.p, 2 * sizeof(G1J), hipMemcpyDeviceToDevice, a->stream));
+    if ((rc = sync(a, who))) return rc;
+    a->j_cap = capacity;
+    a->j_host.assign(10 * capacity, 0);
+    for (size_t sl = capacity; sl-- > 1;) a->free_slots.push_back((uint32_t)sl);
+    a->entries.push_back({0, Fr::one(), a->n_proofs, a->n_failed});
+    return 0;
+}
+
+int h2v_accumulator_check_legs(h2v_accumulator* a, size_t cap, size_t* n_legs, size_t* leg_proofs, size_t* leg_failed, int* leg_pairing_ok) {
+    const char* who = "h2v_accumulator_check_legs";
+    if (!a || !n_legs) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t J = a->entries.size();
+    *n_legs = J;
+    if ((leg_proofs || leg_failed || leg_pairing_ok) && cap < J) { set_last_error(std::string(who) + ": the arrays are shorter than the journal"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t e = 0; e < J; ++e) {
+        if (leg_proofs) leg_proofs[e] = a->entries[e].n_proofs;
+        if (leg_failed) leg_failed[e] = a->entries[e].n_failed;
+    }
+    if (!J || !leg_pairing_ok) return 0;
+    // the slots in use are the lowest ones but for what drop_legs freed: every slot below the highest in use holds a pair of points
+    uint32_t hi = 0;
+    for (const auto& e : a->entries) hi = std::max(hi, e.slot + 1);
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    int rc;
+    uint32_t* d_ok = a->j_words.p + 9 * a->j_cap;
+    uint32_t* h_ok = a->j_host.data() + 9 * a->j_cap;
+    if ((rc = pairing_check_enqueue(a->stream, a->ctx->pairing, a->j_sums.p, hi, d_ok))) { hipStreamSynchronize(a->stream); return rc; }
+    H2V_HIP_CHECK(hipMemcpyAsync(h_ok, d_ok, 4 * (size_t)hi, hipMemcpyDeviceToHost, a->stream));
+    if ((rc = sync(a, who))) return rc;
+    for (size_t e = 0; e < J; ++e) leg_pairing_ok[e] = h_ok[a->entries[e].slot] ? 1 : 0;
+    return 0;
+}
+
+int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_drop) {
+    const char* who = "h2v_accumulator_drop_legs";
+    if (!a || (n_drop && !legs)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!a->j_cap) { set_last_error(std::string(who) + ": the journal is off"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t J = a->entries.size();
+    std::vector<bool> drop(J, false);
+    for (size_t i = 0; i < n_drop; ++i) {
+        if (legs[i] == 0 || legs[i] >= J || drop[legs[i]]) { set_last_error(std::string(who) + ": an entry index that is 0 (the base), out of range or given twice"); return H2V_ERR_BAD_ARGUMENT; }
+        drop[legs[i]] = true;
+    }
+    // W_e of the kept entries, from the last one down, and their slots
+    std::vector<size_t> kept;
+    for (size_t e = 0; e < J; ++e) if (!drop[e]) kept.push_back(e);
+    const size_t K = kept.size();   // >= 1: the base
+    uint32_t* h = a->j_host.data();
+    Fr W = Fr::one();
+    for (size_t i = K; i-- > 0;) {
+        uint8_t w_bytes[32];
+        W.to_bytes(w_bytes);
+        memcpy(h + 8 * i, w_bytes, 32);
+        h[8 * K + i] = a->entries[kept[i]].slot;
+        W = W * a->entries[kept[i]].M;
+    }
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain{a->stream};
+    int rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(a->j_words.p, h, 4 * 9 * K, hipMemcpyHostToDevice, a->stream));
+    if ((rc = accumulator_scale_many_enqueue(a->stream, a->j_sums.p, a->j_words.p + 8 * K, a->j_words.p, (uint32_t)K, a->j_records.p))) return rc;
+    // the commit: (L, R) <- the sum of the K records
+    if ((rc = fold_records_enqueue(a->stream, a->j_records.p, (uint32_t)K, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) return rc;
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    std::vector<h2v_accumulator::Entry> next;
+    size_t n_proofs = 0, n_failed = 0;
+    for (size_t e = 0; e < J; ++e) {
+        if (drop[e]) { a->free_slots.push_back(a->entries[e].slot); continue; }
+        next.push_back(a->entries[e]);
+        n_proofs += a->entries[e].n_proofs; n_failed += a->entries[e].n_failed;
+    }
+    std::sort(a->free_slots.begin(), a->free_slots.end(), std::greater<uint32_t>());
+    a->entries.swap(next);
+    a->n_proofs = n_proofs; a->n_failed = n_failed;
+    return 0;
 }
 
 }  // extern "C"

@@ -182,6 +182,9 @@ int msm_enqueue(hipStream_t s, MsmWorkspace& ws, const uint32_t* d_scalars, cons
 // d_record (an accumulator record, whole points: parts = 1, failed = 0) <- M * (d_points[0], d_points[1]); d_scalar_words: M as 8 canonical
 // little-endian words.  One wave (k_accumulator_scale): the scale step of a resident accumulator (accumulator.hip)
 int accumulator_scale_enqueue(hipStream_t s, const G1J* d_points, const uint32_t* d_scalar_words, void* d_record);
+// The same for n (pair, scalar) items in one launch, one one-wave workgroup each: d_records[i] <- scalar i * (d_pairs[2 slot],
+// d_pairs[2 slot + 1]) with slot = d_slots[i], scalar i = d_scalar_words[8 i ..].  The rebuild of a journaled accumulator.
+int accumulator_scale_many_enqueue(hipStream_t s, const G1J* d_pairs, const uint32_t* d_slots, const uint32_t* d_scalar_words, uint32_t n, void* d_records);
 
 // ------------------------------------------------------------------ small helpers (util.hip)
 // canonical x|y bytes (64 B each, all-zero = identity) -> affine Montgomery; flags[i] = 0 ok, 1 not canonical / not on curve

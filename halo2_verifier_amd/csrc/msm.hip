@@ -265,9 +265,17 @@ __device__ __forceinline__ uint32_t raw_window(const uint32_t m[5], uint32_t w, 
 // beside (>= 1.2 ms), and where its wave shares a SIMD with one of their single-wave kernels, theirs is the one the call waits for.
 #define ACC_SCALE_TABLE 8u      // multiples 1 P .. 8 P per chain
 #define ACC_SCALE_DIGITS 33u    // nibbles of |k| + 0x8..8, |k| < 2^129
-__global__ void __launch_bounds__(64) k_accumulator_scale(const G1J* __restrict__ in, const uint32_t* __restrict__ m_words, AccRecord* __restrict__ out) {
+// One workgroup per item: block i multiplies the pair at in[2 slot], in[2 slot + 1], slot = slots[i] (slots null: slot = i), by the scalar
+// at scalars[8 i ..] and writes record i.  The scale step of a process call is the one-item launch; the rebuild of a journaled
+// accumulator (h2v_accumulator_drop_legs) is one item per kept entry, every workgroup a chain of its own with its own LDS table.
+__global__ void __launch_bounds__(64) k_accumulator_scale(const G1J* __restrict__ in, const uint32_t* __restrict__ slots, const uint32_t* __restrict__ scalars,
+                                                          AccRecord* __restrict__ out) {
     __shared__ G1J table[4][ACC_SCALE_TABLE];
     __shared__ G1J half_sum[4];
+    const uint32_t item = blockIdx.x;
+    in += 2 * (size_t)(slots ? slots[item] : item);
+    const uint32_t* m_words = scalars + 8 * (size_t)item;
+    out += item;
     const uint32_t lane = threadIdx.x, chain = (lane >> 2) & 3u, r = lane & 3u;
     const uint32_t side = chain >> 1, half = chain & 1u;
     const bool writer = lane < 16 && r == 0;
@@ -320,7 +328,11 @@ __global__ void __launch_bounds__(64) k_accumulator_scale(const G1J* __restrict_
     if (lane == 0) { out->failed = 0; out->parts = 1; out->shift = 0; out->reserved = 0; }
 }
 int accumulator_scale_enqueue(hipStream_t s, const G1J* d_points, const uint32_t* d_scalar_words, void* d_record) {
-    hipLaunchKernelGGL(k_accumulator_scale, dim3(1), dim3(64), 0, s, d_points, d_scalar_words, (AccRecord*)d_record);
+    return accumulator_scale_many_enqueue(s, d_points, nullptr, d_scalar_words, 1, d_record);
+}
+int accumulator_scale_many_enqueue(hipStream_t s, const G1J* d_pairs, const uint32_t* d_slots, const uint32_t* d_scalar_words, uint32_t n, void* d_records) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_accumulator_scale, dim3(n), dim3(64), 0, s, d_pairs, d_slots, d_scalar_words, (AccRecord*)d_records);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -533,11 +533,19 @@ class Accumulator:
     """A resident AccumulatorStrategy (h2v_accumulator): two G1 points that stay on the GPU across calls.  process() feeds proofs as
     they arrive — any mix of VerifyingKeys and instance shapes over the context's params — and finalize() runs the one pairing whenever
     the caller decides (kzg/strategy.rs:125-140).  process(A); process(B); finalize() equals verify_batch_keys over A + B with the draws
-    concatenated.  `context` supplies the device, the params and the pairing tables; it needs no VerifyingKey and must outlive the object."""
+    concatenated.  `context` supplies the device, the params and the pairing tables; it needs no VerifyingKey and must outlive the object.
 
-    def __init__(self, context: Context):
+    journal=capacity turns the leg journal on from the start (journal_begin): one entry per process / add_msm call, so that
+    check_legs() names the legs whose own pairing fails and drop_legs() takes them out again.  keep_inputs=True also retains every leg's
+    (contexts, key_of_proof, proofs, instances) in host memory, which lets identify() name the proofs inside a failing leg."""
+
+    JOURNAL_MAX = 4096   # include/h2v.h H2V_ACC_JOURNAL_MAX
+    _keep_inputs, _inputs = False, ()
+
+    def __init__(self, context: Context, journal=0, keep_inputs=False):
         if not isinstance(context, Context):
             raise TypeError("Accumulator takes a Context")
+        journal = self._capacity(journal)
         self.ctx, self._lib = context, context._lib
         self._h = ctypes.c_void_p()
         check(self._lib.h2v_accumulator_create(context._h, ctypes.byref(self._h)))
@@ -546,6 +554,18 @@ class Accumulator:
             context._batches = weakref.WeakSet()
         context._batches.add(self)   # Context.close() closes what lives on it first
         self.last_all_ok = True
+        self._keep_inputs = bool(keep_inputs)
+        self._inputs = []   # with keep_inputs: one item per journal entry, None for the base and for add_msm entries
+        if journal:
+            self.journal_begin(journal)
+
+    @classmethod
+    def _capacity(cls, capacity):
+        if not isinstance(capacity, int) or isinstance(capacity, bool):
+            raise ValueError("the journal's capacity is an integer")
+        if capacity != 0 and not 2 <= capacity <= cls.JOURNAL_MAX:
+            raise ValueError(f"the journal's capacity is 0 (off) or in [2, {cls.JOURNAL_MAX}], got {capacity}")
+        return capacity
 
     def close(self):
         if self._h:
@@ -588,6 +608,8 @@ class Accumulator:
         check(self._lib.h2v_accumulator_process(self._h, ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), col_lens, rb, st,
                                                 ctypes.byref(ok)))
         self.last_all_ok = bool(ok.value)
+        if n and self._inputs:   # (journal on: the call has appended an entry)
+            self._inputs.append((contexts, None if one_key else [int(k) for k in key_of_proof], list(proofs), list(instances)) if self._keep_inputs else None)
         return list(st)[:n]
 
     def add_msm(self, left, right):
@@ -595,6 +617,8 @@ class Accumulator:
         DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""
         l, r = _seed_side(left), _seed_side(right)
         check(self._lib.h2v_accumulator_add_msm(self._h, *l, *r))
+        if self._inputs:
+            self._inputs.append(None)
 
     def read(self):
         """-> (left_xy, right_xy, n_proofs, n_failed): the two points as affine bytes (zeros = identity) and the counters"""
@@ -610,6 +634,60 @@ class Accumulator:
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
         check(self._lib.h2v_accumulator_finalize(self._h, ctypes.byref(ok), left, right))
         return bool(ok.value), left.raw, right.raw
+
+    # -- the leg journal: find and drop failing legs
+    def journal_begin(self, capacity):
+        """Begin the leg journal (h2v_accumulator_journal_begin): `capacity` entries, the base included, in [2, JOURNAL_MAX]; 0 turns
+        it off.  Entry 0, the base, is the accumulator as it stands; on a journaled accumulator this is a checkpoint.  Retained inputs
+        are forgotten.  The points and counters do not change."""
+        capacity = self._capacity(capacity)
+        check(self._lib.h2v_accumulator_journal_begin(self._h, capacity))
+        self._inputs = [None] if capacity else []
+
+    def check_legs(self):
+        """-> [(n_proofs, n_failed, pairing_ok)] per journal entry, the base first (h2v_accumulator_check_legs): pairing_ok is the
+        pairing check of the entry's own sum, every entry's side by side in one launch.  [] with the journal off."""
+        n = ctypes.c_size_t(0)
+        check(self._lib.h2v_accumulator_check_legs(self._h, 0, ctypes.byref(n), None, None, None))
+        cap = n.value
+        proofs, failed, ok = (ctypes.c_size_t * max(cap, 1))(), (ctypes.c_size_t * max(cap, 1))(), (ctypes.c_int * max(cap, 1))()
+        check(self._lib.h2v_accumulator_check_legs(self._h, cap, ctypes.byref(n), proofs, failed, ok))
+        return [(proofs[e], failed[e], bool(ok[e])) for e in range(n.value)]
+
+    def drop_legs(self, indices):
+        """Take journal entries out again (h2v_accumulator_drop_legs): afterwards the points, the counters and the journal are those of
+        an accumulator that was never given the dropped calls; later entries move down.  indices: distinct entry numbers, none 0 (the
+        base stays).  An empty list rebuilds the points from the journal."""
+        indices = list(indices)
+        if any(not isinstance(e, int) or isinstance(e, bool) for e in indices):
+            raise ValueError("entry indices are integers")
+        if any(e <= 0 for e in indices):
+            raise ValueError("entry indices are positive: entry 0, the base, cannot be dropped")
+        if len(set(indices)) != len(indices):
+            raise ValueError("an entry index given twice")
+        if self._inputs and any(e >= len(self._inputs) for e in indices):
+            raise ValueError(f"the journal has {len(self._inputs)} entries")
+        check(self._lib.h2v_accumulator_drop_legs(self._h, _sizes(indices), len(indices)))
+        gone = set(indices)
+        self._inputs = [x for e, x in enumerate(self._inputs) if e not in gone]
+
+    def identify(self):
+        """Name the failing proofs of the failing legs: check_legs(), then verify_batch_keys_identify with fresh OS draws over the
+        retained inputs of every non-base entry whose pairing fails.  -> {entry: statuses}, statuses[i] what verify_each returns for
+        proof i of that leg.  Needs keep_inputs=True; an add_msm entry that fails is reported with statuses None."""
+        if not self._keep_inputs:
+            raise ValueError("identify() needs the legs' inputs: create the Accumulator with keep_inputs=True")
+        out = {}
+        for e, (_, _, ok) in enumerate(self.check_legs()):
+            if e == 0 or ok:
+                continue
+            kept = self._inputs[e]
+            if kept is None:
+                out[e] = None
+                continue
+            contexts, keys, proofs, instances = kept
+            out[e] = verify_batch_keys_identify(contexts, keys if keys is not None else [0] * len(proofs), proofs, instances)[1]
+        return out
 
 
 def recheck_batches(batches, ranges):

@@ -265,6 +265,36 @@ int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t ou
  * The accumulator is not consumed and not changed: the caller may go on processing, or finalize again. */
 int h2v_accumulator_finalize(h2v_accumulator* a, int* ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]);
 
+/* ---- the leg journal of a resident accumulator: find and drop failing legs.  A proof that decodes and passes its transcript but is
+ * wrong (a wrong public input, a flipped h2) leaves every status 0 and poisons (L, R) for good; the journal keeps what it takes to
+ * say which LEG (one process or add_msm call) did it and to take that leg out again, without feeding the good proofs a second time.
+ * Off by default: an accumulator that never begins a journal runs the launches it ran before.  With the journal on the accumulator
+ * keeps one entry per successful call that changed it: the call's own sum (l, r) — two Jacobian points in device memory, for process
+ * sum_i (prod_{j > i} r_j) Guard_i over the call's proofs alone, what h2v_verify_batch_keys over that leg accumulates; for add_msm
+ * the two evaluated sums — M, the product of the call's draws (1 for add_msm; host memory), and the call's proof and failure counts.
+ * Entry 0 is the base: the points and counters as they stood when the journal was begun.  At every return
+ *     (L, R) = sum_e W_e sum_e,     W_e = prod_{f > e} M_f   over the entries present. */
+#define H2V_ACC_JOURNAL_MAX 4096
+/* capacity 0: the journal off, its entries forgotten.  capacity in [2, H2V_ACC_JOURNAL_MAX]: a fresh journal of that many entries, the
+ * base included, whose base is the current points and counters — on a journaled accumulator a checkpoint, "everything so far is one
+ * base".  Any other capacity: H2V_ERR_BAD_ARGUMENT.  The points and counters never change.  A device error leaves the journal off.
+ *   serves: AccumulatorStrategy::with(msm_accumulator) (poly/kzg/strategy.rs:76-78) — the base is the DualMSM an accumulation resumes. */
+int h2v_accumulator_journal_begin(h2v_accumulator* a, size_t capacity);
+/* One pairing check per entry, side by side in one launch: *n_legs = the entries present, the base included (always written; 0 with
+ * the journal off); leg_proofs[e] / leg_failed[e] = the entry's counters; leg_pairing_ok[e] = the raw bit of
+ * e(l_e, s_g2) e(r_e, -g2) == 1 — for a process entry the pairing of h2v_verify_batch_keys over that leg alone: a leg of good proofs
+ * always passes, a leg of n proofs holding a bad one passes with probability <= n / r.  A proof that failed by status contributes
+ * nothing to its leg's sum: it shows in leg_failed, not in the bit.  The arrays may be NULL; a non-NULL array with cap < *n_legs is
+ * H2V_ERR_BAD_ARGUMENT.  Changes nothing.
+ *   serves: AccumulatorStrategy::finalize (poly/kzg/strategy.rs:138-140), DualMSM::check (poly/kzg/msm.rs:185-203), per leg. */
+int h2v_accumulator_check_legs(h2v_accumulator* a, size_t cap, size_t* n_legs, size_t* leg_proofs, size_t* leg_failed, int* leg_pairing_ok);
+/* Take entries out again: afterwards the points, the counters and the journal are those of an accumulator that was never given the
+ * dropped calls, with the same draws for the kept ones; later entries move down.  legs: n_drop distinct entry indices, each below the
+ * entry count and none 0 (the base stays) — else, or with the journal off, H2V_ERR_BAD_ARGUMENT before any device work.  n_drop == 0
+ * rebuilds the points from the journal.  A call that returns non-zero leaves points, counters and journal as they were.
+ *   serves: DualMSM::scale, DualMSM::add_msm (poly/kzg/msm.rs:173-183): (L, R) <- sum over the kept entries of W_e sum_e. */
+int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_drop);
+
 /* N x verify_proof under SingleStrategy (one pairing per proof; poly/kzg/strategy.rs:164-176).
  * per_proof_status[i] = 0, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE when that proof's pairing fails,
  * or the transcript/opening error. */

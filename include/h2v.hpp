@@ -305,6 +305,33 @@ public:
         check(h2v_accumulator_finalize(h_, &ok, left_, right_));
         return ok != 0;
     }
+    // The leg journal (h2v_accumulator_journal_begin): `capacity` entries, the base included, in [2, H2V_ACC_JOURNAL_MAX]; 0 = off.  The base is
+    // the accumulator as it stands (AccumulatorStrategy::with, kzg/strategy.rs:76-78); on a journaled accumulator a checkpoint.
+    void journal_begin(size_t capacity) {
+        if (capacity == 1 || capacity > H2V_ACC_JOURNAL_MAX) throw Failure(H2V_ERR_BAD_ARGUMENT, "journal capacity must be 0 or in [2, H2V_ACC_JOURNAL_MAX]");
+        check(h2v_accumulator_journal_begin(h_, capacity));
+    }
+    // DualMSM::check (kzg/msm.rs:185-203) of every entry's own sum, side by side in one launch; entry 0 is the base.  Empty with the journal off.
+    struct Leg { size_t n_proofs, n_failed; bool pairing_ok; };
+    std::vector<Leg> check_legs() {
+        size_t n = 0;
+        check(h2v_accumulator_check_legs(h_, 0, &n, nullptr, nullptr, nullptr));
+        std::vector<size_t> proofs(n ? n : 1), failed(n ? n : 1);
+        std::vector<int> ok(n ? n : 1, 0);
+        check(h2v_accumulator_check_legs(h_, n, &n, proofs.data(), failed.data(), ok.data()));
+        std::vector<Leg> legs;
+        for (size_t e = 0; e < n; ++e) legs.push_back({proofs[e], failed[e], ok[e] != 0});
+        return legs;
+    }
+    // Take entries out again (distinct, none 0, each below the entry count): the accumulator, the counters and the journal become those of
+    // an accumulator that was never given the dropped calls (DualMSM::scale / add_msm over the kept entries, kzg/msm.rs:173-183)
+    void drop_legs(const std::vector<size_t>& legs) {
+        for (size_t i = 0; i < legs.size(); ++i) {
+            if (legs[i] == 0) throw Failure(H2V_ERR_BAD_ARGUMENT, "the base entry cannot be dropped");
+            for (size_t j = 0; j < i; ++j) if (legs[j] == legs[i]) throw Failure(H2V_ERR_BAD_ARGUMENT, "an entry index given twice");
+        }
+        check(h2v_accumulator_drop_legs(h_, legs.data(), legs.size()));
+    }
     const uint8_t* left() const { return left_; }
     const uint8_t* right() const { return right_; }
     size_t n_proofs() const { return n_proofs_; }   // as of the last read()

@@ -43,6 +43,8 @@ pub const H2V_TRANSCRIPT_KECCAK256: c_int = 1;
 pub const H2V_ACC_RECORD_PIECES: usize = 6;
 /// bytes one shard contributes per group to a sharded batch ([failed, parts, shift, 0] + 2 x 6 Jacobian pieces)
 pub const H2V_ACC_RECORD_BYTES: usize = 1312;
+/// entries a leg journal holds at most, the base included (h2v_accumulator_journal_begin)
+pub const H2V_ACC_JOURNAL_MAX: usize = 4096;
 /// h2v_batch_set_profiling: only the dominant kernel's own timestamps
 pub const H2V_PROFILE_KERNEL: c_int = 3;
 
@@ -87,6 +89,10 @@ extern "C" {
                                    right_scalars32: *const u8, right_bases64: *const u8, n_right: usize) -> c_int;
     pub fn h2v_accumulator_read(a: *mut h2v_accumulator, out_left_xy: *mut u8, out_right_xy: *mut u8, n_proofs: *mut usize, n_failed: *mut usize) -> c_int;
     pub fn h2v_accumulator_finalize(a: *mut h2v_accumulator, ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
+    pub fn h2v_accumulator_journal_begin(a: *mut h2v_accumulator, capacity: usize) -> c_int;
+    pub fn h2v_accumulator_check_legs(a: *mut h2v_accumulator, cap: usize, n_legs: *mut usize, leg_proofs: *mut usize, leg_failed: *mut usize,
+                                      leg_pairing_ok: *mut c_int) -> c_int;
+    pub fn h2v_accumulator_drop_legs(a: *mut h2v_accumulator, legs: *const usize, n_drop: usize) -> c_int;
     pub fn h2v_verify_each(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, per_proof_status: *mut c_int) -> c_int;
     pub fn h2v_verify_batch_identify(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,

@@ -6,6 +6,8 @@
 //!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
 //! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
 //!                               sharing the params; `finalize` whenever the caller decides (h2v_accumulator_*).
+//!                               Its leg journal (`journal_begin`, `check_legs`, `drop_legs`) finds the legs whose own pairing
+//!                               fails and takes them out again.
 //! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) whose `finalize`
 //!                               evaluates the two `MSMKZG` channels and the pairing on the GPU
 //!                               (poly/kzg/msm.rs:81-86, 185-203) while `verify_proof` itself stays on the CPU.
@@ -249,6 +251,35 @@ impl GpuResidentAccumulator {
         let rc = unsafe { h2v_accumulator_finalize(self.acc, &mut ok, core::ptr::null_mut(), core::ptr::null_mut()) };
         if rc != 0 { return Err(map_err(rc)); }
         Ok(ok == 1)
+    }
+
+    /// Begin (or checkpoint) the leg journal: `capacity` entries, the base included, in `[2, H2V_ACC_JOURNAL_MAX]`; 0 turns it off.
+    /// The base is the accumulator as it stands — the `DualMSM` an `AccumulatorStrategy::with` would resume (poly/kzg/strategy.rs:76-78).
+    pub fn journal_begin(&mut self, capacity: usize) -> Result<(), Error> {
+        if capacity == 1 || capacity > H2V_ACC_JOURNAL_MAX { return Err(Error::InvalidInstances); }
+        let rc = unsafe { h2v_accumulator_journal_begin(self.acc, capacity) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
+    }
+
+    /// `DualMSM::check` (poly/kzg/msm.rs:185-203) of every journal entry's own sum, side by side: `(n_proofs, n_failed, pairing_ok)` per
+    /// entry, the base first.  Empty with the journal off.
+    pub fn check_legs(&mut self) -> Result<Vec<(usize, usize, bool)>, Error> {
+        let mut n = 0usize;
+        let rc = unsafe { h2v_accumulator_check_legs(self.acc, 0, &mut n, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        let (mut proofs, mut failed, mut ok) = (vec![0usize; n.max(1)], vec![0usize; n.max(1)], vec![0i32; n.max(1)]);
+        let rc = unsafe { h2v_accumulator_check_legs(self.acc, n, &mut n, proofs.as_mut_ptr(), failed.as_mut_ptr(), ok.as_mut_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok((0..n).map(|e| (proofs[e], failed[e], ok[e] == 1)).collect())
+    }
+
+    /// Take journal entries out again (distinct, none 0, each below the entry count): the accumulator becomes what it would be had the
+    /// dropped calls never been made — `DualMSM::scale` and `add_msm` (poly/kzg/msm.rs:173-183) over the kept entries.
+    pub fn drop_legs(&mut self, legs: &[usize]) -> Result<(), Error> {
+        let rc = unsafe { h2v_accumulator_drop_legs(self.acc, legs.as_ptr(), legs.len()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
     }
 }
 impl Drop for GpuResidentAccumulator {

@@ -8,8 +8,14 @@ offered before it.  Median wall times of --reps runs, host proofs in, one MI355X
 3. (--trace) a few process calls only, for a `rocprofv3 --kernel-trace --stats -- python tools/accumulator_probe.py --trace` run that
              gives k_accumulator_scale's own duration.
 4. two keys: 2 x 512 interleaved proofs of two k = 8 vector-mul keys in 4 legs against ONE h2v_verify_batch_keys over all 1024.
---library PATH loads another build of libh2v_amd.so; --baseline-only times the baselines alone (a build without the accumulator)."""
-import argparse, json, os, random, sys, time
+--library PATH loads another build of libh2v_amd.so; --baseline-only times the baselines alone (a build without the accumulator).
+5. (--journal) the leg journal, instead of 1 - 4:
+   a. K = 8 legs of 1024 proofs + finalize with the journal on, with it off and (--parent PATH: a libh2v_amd.so built from the parent
+      commit, loaded beside the in-tree one) on the parent's library, the variants alternating inside every repetition.
+   b. check_legs() and the rebuild drop_legs([]) at 8, 64 and 512 entries (the base and legs of 16 proofs), beside the repair a library without the
+      journal offers: a fresh accumulator fed the same legs again from host bytes.
+   With --trace: one check_legs and one drop_legs at each of the three sizes, for a `rocprofv3 --kernel-trace --stats` run."""
+import argparse, ctypes, json, os, random, sys, time
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import bench
 bench.hw_queue_env()
@@ -22,6 +28,8 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--library", default=None)
 ap.add_argument("--baseline-only", action="store_true")
 ap.add_argument("--trace", action="store_true")
+ap.add_argument("--journal", action="store_true")
+ap.add_argument("--parent", default=None)
 args = ap.parse_args()
 if args.library:
     _lib.lib_path = lambda: os.path.abspath(args.library)
@@ -73,6 +81,108 @@ def accumulator_legs(m):
 
 
 res = {"k": args.k, "reps": args.reps, "legs": K, "library": args.library or "in-tree", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+
+
+def median(ts):
+    return sorted(ts)[len(ts) // 2]
+
+
+def parent_context(path):
+    """a Context on another build of the library, loaded beside the in-tree one (a parent build lacks the journal's symbols)"""
+    lib = ctypes.CDLL(os.path.abspath(path))
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    mine = _lib.load_library()
+    _lib._LIB = lib
+    try:
+        return h2v.Context(h2v.ParamsKZG(d["params"], RAW), h2v.VerifyingKey(d["vk"], RAW))
+    finally:
+        _lib._LIB = mine
+
+
+def journal_probe():
+    LEG, SIZES = 16, (8, 64, 512)
+
+    def journaled(J):
+        """a journal of J entries: the (empty) base and J - 1 legs"""
+        acc = h2v.Accumulator(ctx, journal=J)
+        for j in range(J - 1):
+            acc.process(ctx, None, P[:LEG], I[:LEG], draws[j % K][:LEG])
+        return acc
+
+    if args.trace:
+        for J in SIZES:
+            acc = journaled(J)
+            before = acc.read()
+            assert all(ok for _, _, ok in acc.check_legs())
+            acc.drop_legs([])
+            assert acc.read() == before
+            acc.close()
+        return
+    # a. 8 legs of 1024 + finalize
+    variants = {"journal_on": (ctx, K + 1), "journal_off": (ctx, 0)}
+    if args.parent:
+        variants["parent"] = (parent_context(args.parent), 0)
+
+    def legs(c, journal):
+        acc = h2v.Accumulator(c, journal=journal) if journal else h2v.Accumulator(c)
+        for j in range(K):
+            acc.process(c, None, P, I, draws[j])
+        r = acc.finalize()
+        acc.close()
+        return r
+    want = legs(ctx, 0)
+    assert want[0]
+    ts = {v: [] for v in variants}
+    for v, (c, journal) in variants.items():
+        assert legs(c, journal) == want   # warm-up
+    for _ in range(args.reps):
+        for v, (c, journal) in variants.items():
+            t0 = time.perf_counter(); legs(c, journal); ts[v].append((time.perf_counter() - t0) * 1e3)
+    row = {v: round(median(t), 3) for v, t in ts.items()}
+    row.update({v + "_min_max": [round(min(t), 3), round(max(t), 3)] for v, t in ts.items()})
+    line = f"{K} legs of 1024 + finalize: " + "   ".join(f"{v} {row[v]:.3f} ms" for v in variants)
+    if args.parent:
+        for v in ("journal_on", "journal_off"):
+            row[v + "_over_parent"] = round(row[v] / row["parent"], 4)
+            line += f"   {v} / parent {row[v + '_over_parent']:.3f}x ({'within' if row[v + '_over_parent'] <= 1.08 else 'OUTSIDE'} 1.08x)"
+    res["legs_1024_ms"] = row
+    print(line, flush=True)
+    # b. check_legs and the rebuild at 8, 64, 512 entries of 16 proofs; the repair without the journal beside them
+    res["journal_ops_ms"] = {}
+    for J in SIZES:
+        acc = journaled(J)
+        before = acc.read()
+        t_check, got = timed(acc.check_legs)
+        assert len(got) == J and all(ok for _, _, ok in got)
+        t_drop, _ = timed(lambda: acc.drop_legs([]))
+        assert acc.read() == before
+        acc.close()
+
+        def refeed():
+            fresh = h2v.Accumulator(ctx)
+            for j in range(J - 1):
+                fresh.process(ctx, None, P[:LEG], I[:LEG], draws[j % K][:LEG])
+            r = fresh.read()
+            fresh.close()
+            return r
+        t_feed, again = timed(refeed)
+        assert again == before
+        res["journal_ops_ms"][J] = {"check_legs_ms": round(t_check, 3), "drop_legs_ms": round(t_drop, 3), "refeed_ms": round(t_feed, 3)}
+        print(f"{J:4d} entries, legs of {LEG}: check_legs {t_check:8.3f} ms   drop_legs (rebuild) {t_drop:8.3f} ms   a fresh accumulator fed again {t_feed:9.3f} ms", flush=True)
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if args.journal:
+    journal_probe()
+    ctx.close()
+    sys.exit(0)
 if args.trace:
     acc = h2v.Accumulator(ctx)
     for j in range(K):
