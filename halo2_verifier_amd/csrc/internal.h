@@ -72,7 +72,9 @@ struct MappedHostBuf {
 struct MsmPlan {
     uint32_t n;        // terms
     uint32_t c;        // window bits
-    uint32_t windows;  // ceil(129 / c): GLV halves are 128-bit magnitudes, +1 bit for the signed-digit carry
+    uint32_t windows;  // ceil(130 / c) (msm_plan).  GLV halves are magnitudes below 2^127 (glv_decompose: exact floors) and the signed-digit carry adds a
+                       // bit: ceil(128 / c) windows hold every digit — the top digit sits in window floor(126 / c) or, by the carry, floor(127 / c)
+                       // (tests/test_gpu_msm_units.py) — and the plan keeps two bits more (one more window at c = 2, 3, 4 and 8, none at the other widths up to 15)
     uint32_t buckets;  // 2^(c-1) per window (signed digits)
 };
 MsmPlan msm_plan(uint32_t n, bool latency = false);

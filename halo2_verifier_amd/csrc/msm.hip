@@ -210,7 +210,23 @@ __device__ __forceinline__ void mul_hi256(uint32_t out[5], const uint32_t k[8], 
     }
     for (int i = 0; i < 5; ++i) out[i] = t[8 + i];
 }
-struct GlvHalf { uint32_t mag[5]; bool neg; };  // |k_i| < 2^128 (limb 4 only ever holds the recoding carry)
+// a * b mod 2^256 for a in two's complement (8 limbs) and a constant b of nb limbs
+__device__ __forceinline__ void mul_lo8(uint32_t out[8], const uint32_t a[8], const uint32_t* b, int nb) {
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    for (int j = 0; j < nb; ++j) {
+        uint64_t carry = 0;
+        for (int i = 0; i + j < 8; ++i) {
+            uint64_t t = (uint64_t)a[i] * b[j] + out[i + j] + carry;
+            out[i + j] = (uint32_t)t; carry = t >> 32;
+        }
+    }
+}
+__device__ __forceinline__ bool glv_geq_r(const uint32_t v[8]) {   // v >= r, v an unsigned 256-bit integer
+    const uint32_t RW[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+    for (int i = 7; i >= 0; --i) { if (v[i] > RW[i]) return true; if (v[i] < RW[i]) return false; }
+    return true;
+}
+struct GlvHalf { uint32_t mag[5]; bool neg; };  // |k_i| < 2^127 (limb 4 only ever holds the recoding carry)
 __device__ __forceinline__ void glv_finish(GlvHalf& h, uint32_t t[5]) {  // t = two's complement mod 2^160
     h.neg = (t[4] >> 31) != 0;
     if (h.neg) { uint64_t c = 1; for (int i = 0; i < 5; ++i) { uint64_t v = (uint64_t)(~t[i]) + c; t[i] = (uint32_t)v; c = v >> 32; } }
@@ -224,23 +240,45 @@ __device__ __forceinline__ void glv_decompose(const uint32_t* __restrict__ k, Gl
     const uint32_t G2[5] = {0xc7e0b3d7u, 0xd91d232eu, 0x2u, 0u, 0u};
     uint32_t kk[8];
     for (int i = 0; i < 8; ++i) kk[i] = k[i];
-    uint32_t c1[5], c2[5], p1[5], p2[5], t[5];
+    uint32_t c1[5], c2[5], p1[5], p2[5], t1[8], t2[8];
     mul_hi256(c1, kk, G1);
     mul_hi256(c2, kk, G2);
     // k1 = k - c1*a1 - c2*a2
     mul_lo5(p1, c1, 5, A1, 5); mul_lo5(p2, c2, 5, B1N, 5);
     {
         int64_t borrow = 0;
-        for (int i = 0; i < 5; ++i) { int64_t v = (int64_t)kk[i] - p1[i] - p2[i] + borrow; t[i] = (uint32_t)v; borrow = v >> 32; }
+        for (int i = 0; i < 5; ++i) { int64_t v = (int64_t)kk[i] - p1[i] - p2[i] + borrow; t1[i] = (uint32_t)v; borrow = v >> 32; }
     }
-    glv_finish(h1, t);
     // k2 = -c1*b1 - c2*b2 = c1*(-b1) - c2*b2
     mul_lo5(p1, c1, 5, B1N, 5); mul_lo5(p2, c2, 5, B2, 5);
     {
         int64_t borrow = 0;
-        for (int i = 0; i < 5; ++i) { int64_t v = (int64_t)p1[i] - p2[i] + borrow; t[i] = (uint32_t)v; borrow = v >> 32; }
+        for (int i = 0; i < 5; ++i) { int64_t v = (int64_t)p1[i] - p2[i] + borrow; t2[i] = (uint32_t)v; borrow = v >> 32; }
     }
-    glv_finish(h2, t);
+    // The quotients above are floors of (k g) >> 256 with g = floor(2^256 b / r): never above the exact floor(k b / r) and at most one
+    // below it (the shortfall is under k / 2^256 < 0.19).  A quotient that is one short leaves its basis vector in the halves:
+    // (k1, k2) = alpha (a1, b1) + beta (a2, b2) with alpha or beta in [1, 2) instead of [0, 1).  alpha r = k1 b2 - a2 k2 and
+    // beta r = a1 k2 + a2 k1 (the determinant a1 b2 - a2 b1 is r) lie in [0, 2r), so they are exact mod 2^256: where one reaches r its vector
+    // is taken out again.  The halves are then those of the exact floors: 0 <= k1 < a1 + a2 and -a2 < k2 < b2, magnitudes below 2^127 —
+    // and k2 is negative exactly in the sliver beta b2 < alpha a2 (tests/test_gpu_msm_units.py builds such scalars, k1 - j lambda).
+    {
+        const uint32_t s1 = (t1[4] >> 31) ? 0xffffffffu : 0u, s2 = (t2[4] >> 31) ? 0xffffffffu : 0u;
+        for (int i = 5; i < 8; ++i) { t1[i] = s1; t2[i] = s2; }
+        uint32_t u[8], v[8], w[8];
+        mul_lo8(u, t1, B2, 4); mul_lo8(w, t2, B1N, 2);
+        { int64_t borrow = 0; for (int i = 0; i < 8; ++i) { int64_t d = (int64_t)u[i] - w[i] + borrow; u[i] = (uint32_t)d; borrow = d >> 32; } }
+        mul_lo8(v, t2, A1, 4); mul_lo8(w, t1, B1N, 2);
+        { uint64_t carry = 0; for (int i = 0; i < 8; ++i) { uint64_t d = (uint64_t)v[i] + w[i] + carry; v[i] = (uint32_t)d; carry = d >> 32; } }
+        const bool e1 = glv_geq_r(u), e2 = glv_geq_r(v);
+        // k1 -= e1 a1 + e2 a2 ;  k2 -= e1 b1 + e2 b2 = -e1 a2 + e2 b2
+        int64_t b1 = 0, b2 = 0;
+        for (int i = 0; i < 5; ++i) {
+            int64_t d = (int64_t)t1[i] - (e1 ? A1[i] : 0u) - (e2 ? B1N[i] : 0u) + b1; t1[i] = (uint32_t)d; b1 = d >> 32;
+            d = (int64_t)t2[i] + (e1 ? B1N[i] : 0u) - (e2 ? B2[i] : 0u) + b2; t2[i] = (uint32_t)d; b2 = d >> 32;
+        }
+    }
+    glv_finish(h1, t1);
+    glv_finish(h2, t2);
 }
 __device__ __forceinline__ uint32_t raw_window(const uint32_t m[5], uint32_t w, uint32_t c) {
     uint32_t off = w * c, word = off >> 5, sh = off & 31;

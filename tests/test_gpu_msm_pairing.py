@@ -101,6 +101,26 @@ def test_msm_skewed_inputs(ctx, srs, oracle, kind):
     assert ctx.msm_g1(scalars, bases) == oracle_lib.g1_msm(oracle, scalars, bases)
 
 
+def test_msm_edge_and_negative_half_scalars(ctx, srs, oracle):
+    """The scalar classes of tests/test_gpu_msm_units.py through the shipped library: 0, 1, r - 1, lambda and its neighbours, 2^i, 2^i - 1
+    and r - 2^i for every i, and scalars whose second GLV half is negative (k1 - j lambda: glv_finish's negation and the entry sign
+    `neg_digit != h.neg`) — with the per-window LDS sort and with the global counting sort."""
+    import msm_reference
+    rnd = random.Random(515)
+    scalars = msm_reference.edge_scalars() + [k for k, _, _ in msm_reference.negative_half_scalars()]
+    scalars += [k for k, _, _ in msm_reference.width_scalars(7)]
+    pts = [g1_xy(p) for p in srs.g]
+    bases = [pts[rnd.randrange(srs.n)] for _ in scalars]
+    bases[11] = bytes(64)
+    exp = oracle_lib.g1_msm(oracle, scalars, bases)
+    assert ctx.msm_g1(scalars, bases) == exp
+    ctx.set_tuning(msm_global_sort=1)
+    try:
+        assert ctx.msm_g1(scalars, bases) == exp
+    finally:
+        ctx.set_tuning()
+
+
 def test_msm_cancellation_gives_identity(ctx, srs):
     p = srs.g[7]
     q = (p[0], srs_util.P - p[1])
