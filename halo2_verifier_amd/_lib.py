@@ -59,6 +59,8 @@ SIGNATURES = {
     "h2v_verify_batch_identify": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p, c_szp]),
     "h2v_verify_batch_keys_identify": (c_int, [ctypes.POINTER(c_vp), c_sz, ctypes.POINTER(ctypes.c_uint32), c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_szp,
                                                c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p, c_szp]),
+    "h2v_verify_batch_seeded_identify": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
+                                                 c_sz, c_intp, c_intp, c_intp, c_u8p, c_u8p, c_szp]),
     "h2v_guard_msm": (c_int, [c_vp, c_u8p, c_sz, c_u8p, c_sz, c_szp, c_u8p, c_u8p, c_szp, c_u8p, c_u8p, c_szp, c_u8p, c_szp]),
     "h2v_random_scalars": (c_int, [c_u8p, c_sz]),
     "h2v_batch_create": (c_int, [c_vp, c_sz, c_sz, ctypes.POINTER(c_vp)]),
@@ -71,6 +73,7 @@ SIGNATURES = {
     "h2v_batch_finish_groups": (c_int, [c_vp, c_intp, c_intp, c_u8p, c_u8p, c_sz]),
     "h2v_batch_recheck": (c_int, [c_vp, c_sz, c_szp, c_szp, c_intp, c_u8p, c_u8p]),
     "h2v_batches_recheck": (c_int, [ctypes.POINTER(c_vp), c_sz, c_sz, ctypes.POINTER(ctypes.c_uint32), c_szp, c_szp, c_intp, c_u8p, c_u8p]),
+    "h2v_batch_identify": (c_int, [c_vp, c_vp, c_intp, c_intp, c_szp]),
     "h2v_batch_accumulators": (c_int, [c_vp, ctypes.POINTER(c_vp), c_szp]),
     "h2v_batch_stream": (c_vp, [c_vp]),
     "h2v_batch_set_stream": (c_int, [c_vp, c_vp]),

@@ -108,6 +108,7 @@ struct Recheck {
     DevBuf<G1J> acc;              // [2 r] left, [2 r + 1] right
     DevBuf<uint32_t> ok;          // [range]
     DevBuf<uint8_t> out_bytes; DevBuf<uint32_t> out_ident;     // [range][128]; [2 range]
+    DevBuf<uint32_t> failed;      // [group]: the failure counts of the records h2v_batch_identify puts together (read by nobody)
 };
 
 // The block of everything h2v_batch_finish reads back, in bytes, for G groups and n proofs: [ok G][fold_failed G][out_ident 2 G]
@@ -132,6 +133,7 @@ struct LaunchRecord {           // what the last launch (or fold) left (close_en
     bool pieces = false;        // no pairing, accumulators in pieces only: acc / out_bytes are put together on demand (ensure_whole)
     bool tail_on_aux = false;   // whatever the stage: its whole accumulators, their bytes and the result copy are still on the auxiliary stream (join_tail)
     bool host_block = false;    // the launch itself sends the result block to the host (the pairing launch's tail workgroups, or the auxiliary stream)
+    bool folded = false;        // a fold ran since the launch: acc / the pieces / the `ok` words are the folded records', not the launch's own
 };
 // The staged batch's steps (batch.hip) that the one-shot entry points (oneshot.hip) run on their scratch batches
 int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false);
@@ -145,6 +147,12 @@ bool same_srs(const ParamsHost& a, const ParamsHost& b);
 int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range, const size_t* first,
                  const size_t* count, int* range_ok, uint8_t* out_left, uint8_t* out_right);
 int export_whole_records(h2v_batch* b, void* device_dst);
+// The search of the identifying entry points (oneshot.hip): st[k][i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof i of bs[k] that
+// lies in a start range and whose own check fails.  start: ranges of finished batches, each inside one group of its launch;
+// known: every start range has failed a check of its own (else the first round checks them as they are).  The number of ranges
+// handed to re-check launches is ADDED to *n_checks.
+struct IdentifyStart { uint32_t b; size_t first, count; };
+int identify_search(const std::vector<h2v_batch*>& bs, const std::vector<IdentifyStart>& start, bool known, std::vector<std::vector<int>>& st, size_t* n_checks);
 
 // ---- grouped one-shot calls (oneshot.hip): h2v_verify_batch_keys and its forms, and a resident accumulator's process (accumulator.hip)
 #define H2V_MAX_SHAPES_PER_CALL 64   // distinct (key, instance shape) groups one call takes (H2V_ERR_UNSUPPORTED beyond)

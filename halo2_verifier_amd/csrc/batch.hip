@@ -422,6 +422,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     }
     mark();
     if ((rc = close_enqueue(b, with_pairing != 0))) return rc;
+    b->last.folded = false;
     mark();
     commit.commit(BatchStage::Launched);
     return 0;
@@ -741,7 +742,70 @@ int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, 
         if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, b->split.parts, b->split.shift, b->acc.p, pieces, ready, b->fold_failed))) return rc;
     } else if ((rc = fold_records_enqueue(b->stream, device_accumulators, (uint32_t)n_parts, G, 1, 0, b->acc.p, nullptr, nullptr, b->fold_failed))) return rc;
     if ((rc = close_enqueue(b, true))) return rc;
+    b->last.folded = true;     // (h2v_batch_identify: the batch's own accumulators are now only in the record it exported)
     commit.commit(b->stage);   // (a launch folded after its finish stays Finished)
+    return 0;
+}
+// Which proofs of a finished staged batch fail the pairing.  Step 1: every group's OWN verdict — the launch's bit if its pairing ran
+// over the group's own accumulators, else one pairing launch over all groups (the records the launch exported put together, or the
+// whole points a launch without a pairing left); no MSM.  Step 2: one pooled search (identify_search) from the groups whose own check
+// fails.  Only the re-check's buffers are written.
+int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_status, int* group_own_ok, size_t* n_range_checks) {
+    static const char who[] = "h2v_batch_identify";
+    int rc;
+    if ((rc = require_stage(b, BatchStage::Finished, who))) return rc;
+    const uint32_t n = b->n, G = b->groups, gs = n / G;
+    if (!own_records && b->last.folded) { set_last_error(std::string(who) + ": a fold has replaced the batch's own accumulators: pass the records it exported"); return H2V_ERR_BAD_ARGUMENT; }
+    // a single proof's check equals SingleStrategy's only when its multiplier is non-zero (h2v_batch_recheck's rule, for every proof)
+    for (uint32_t g = 0; g < G; ++g)
+        if (b->zero_below[g]) { set_last_error(std::string(who) + ": a proof of the batch has a zero multiplier (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
+    h2v_ctx* ctx = b->ctx;
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = b->stream;
+    // (a fold after the finish may still be sending the result block: the same statuses again)
+    H2V_HIP_CHECK(hipStreamSynchronize(s));
+    if (b->aux) H2V_HIP_CHECK(hipStreamSynchronize(b->aux));
+    const ResultsLayout L{G, n};
+    const int* raw = reinterpret_cast<const int*>(b->results_host.p + L.status());
+    std::vector<std::vector<int>> st(1, std::vector<int>(n));
+    std::vector<uint32_t> failed(G, 0);
+    for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[i / gs]; }
+    if (own_records) {
+        std::vector<uint32_t> hdr(4 * (size_t)G);   // [failed, parts, shift, 0] of every record
+        H2V_HIP_CHECK(hipMemcpy2DAsync(hdr.data(), 16, own_records, H2V_ACC_RECORD_BYTES, 16, G, hipMemcpyDeviceToHost, s));
+        H2V_HIP_CHECK(hipStreamSynchronize(s));
+        for (uint32_t g = 0; g < G; ++g)
+            if (hdr[4 * g + 1] < 1 || hdr[4 * g + 1] > H2V_ACC_RECORD_PIECES || hdr[4 * g] != failed[g]) {
+                set_last_error(std::string(who) + ": own_records does not hold the records this launch exported (piece count, or failure count against the statuses)");
+                return H2V_ERR_BAD_ARGUMENT;
+            }
+    }
+    std::vector<uint32_t> own(G, 0);
+    if (b->last.pairing && !b->last.folded) {
+        for (uint32_t g = 0; g < G; ++g) own[g] = pairing_passed(b, g) ? 1u : 0u;
+    } else {
+        Recheck& rk = b->recheck;
+        const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;   // (recheck_impl's sizes: G <= max_ranges, h2v_batch_set_groups)
+        if ((rc = rk.acc.reserve(2 * (size_t)max_ranges)) || (rc = rk.ok.reserve(max_ranges)) || (rc = rk.failed.reserve(max_ranges))) return rc;
+        if ((rc = join_tail(b))) return rc;
+        // without records: a finished launch without a pairing has its whole points in acc (finish_impl: ensure_whole)
+        const G1J* pts = b->acc.p;
+        if (own_records) {
+            if ((rc = fold_records_enqueue(s, own_records, 1, G, 1, 0, rk.acc.p, nullptr, nullptr, rk.failed.p))) return rc;
+            pts = rk.acc.p;
+        }
+        if ((rc = pairing_check_enqueue(s, ctx->pairing, pts, G, rk.ok.p))) return rc;
+        H2V_HIP_CHECK(hipMemcpyAsync(own.data(), rk.ok.p, 4 * (size_t)G, hipMemcpyDeviceToHost, s));
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    }
+    std::vector<IdentifyStart> start;
+    for (uint32_t g = 0; g < G; ++g) if (!own[g] && gs) start.push_back({0, (size_t)g * gs, gs});
+    size_t checks = 0;
+    if (!start.empty() && (rc = identify_search({b}, start, true, st, &checks))) return rc;
+    if (per_proof_status) for (uint32_t i = 0; i < n; ++i) per_proof_status[i] = st[0][i];
+    if (group_own_ok) for (uint32_t g = 0; g < G; ++g) group_own_ok[g] = own[g] ? 1 : 0;
+    if (n_range_checks) *n_range_checks = checks;
     return 0;
 }
 int h2v_batch_set_profiling(h2v_batch* b, int level) { if (!b) return H2V_ERR_BAD_ARGUMENT; b->profiling = level == 0 ? 0 : (level == H2V_PROFILE_KERNEL ? 1 : 2); return 0; }

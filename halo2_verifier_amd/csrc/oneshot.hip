@@ -111,14 +111,19 @@ int pack_and_run(ScratchBatch& sb, size_t n, const uint8_t* const* proofs, const
 #define H2V_IDENTIFY_DIRECT 512
 #define H2V_IDENTIFY_ROUND (MSM_MAX_PROBLEMS / 2)
 
-// the pairing's verdict of failed batches of one group each, proof by proof: st[k][i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof
-// i of batch bs[k] whose own check fails (st[k][i] == 0 on entry).  A range whose check fails holds at least one failing proof (the check
-// of a range is the product of its pieces' checks), so every round ends with at least one failing piece per failing range.  Every round is
-// ONE re-check over the pieces of all batches (recheck_impl).  With one batch the policy is the one measured above, and its whole range is
-// known to fail (its own pairing did).  Over several batches only the fold of all of them is known to fail: the first round checks every
-// batch's range, a one-proof range included, before anything is flagged.
-int identify_search(const std::vector<h2v_batch*>& bs, std::vector<std::vector<int>>& st, size_t* n_checks) {
-    struct Item { uint32_t b; size_t first, count; };
+}  // namespace
+
+namespace h2v {
+
+// the pairing's verdict of failing ranges of finished batches, proof by proof: st[k][i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for every proof
+// i of a start range of batch bs[k] whose own check fails (st[k][i] == 0 on entry).  A range whose check fails holds at least one failing
+// proof (the check of a range is the product of its pieces' checks), so every round ends with at least one failing piece per failing range.
+// Every round is ONE re-check over the pieces of all start ranges (recheck_impl).  From one start range the policy is the one measured
+// above.  `known`: every start range has failed a check of its own (a batch's own pairing, a group's own verdict: h2v_batch_identify);
+// else only the fold of all of them is known to fail (h2v_verify_batch_keys_identify): the first round checks every start range as it
+// is, a one-proof range included, before anything is flagged.
+int identify_search(const std::vector<h2v_batch*>& bs, const std::vector<IdentifyStart>& start, bool known, std::vector<std::vector<int>>& st, size_t* n_checks) {
+    typedef IdentifyStart Item;
     // proofs with a non-zero status contribute nothing: a range is trimmed to its first and last live proof, and one without a live proof passes
     auto trim = [&](uint32_t k, size_t a, size_t c, std::vector<Item>& out) {
         const std::vector<int>& sk = st[k];
@@ -128,9 +133,8 @@ int identify_search(const std::vector<h2v_batch*>& bs, std::vector<std::vector<i
         if (e > a) out.push_back({k, a, e - a});
     };
     std::vector<Item> failing, pieces;
-    for (uint32_t k = 0; k < bs.size(); ++k) trim(k, 0, st[k].size(), failing);
-    const bool pooled = bs.size() > 1;
-    bool known = !pooled;   // every range in `failing` has failed a check of its own
+    for (const Item& r : start) trim(r.b, r.first, r.count, failing);
+    const bool pooled = start.size() > 1;
     int rc = 0;
     while (!failing.empty()) {
         pieces.clear();
@@ -161,6 +165,17 @@ int identify_search(const std::vector<h2v_batch*>& bs, std::vector<std::vector<i
         }
     }
     return 0;
+}
+
+}  // namespace h2v
+
+namespace {
+
+// the whole range of every batch (one group each) as the start of a search
+std::vector<IdentifyStart> whole_batches(const std::vector<std::vector<int>>& st) {
+    std::vector<IdentifyStart> start;
+    for (uint32_t k = 0; k < st.size(); ++k) start.push_back({k, 0, st[k].size()});
+    return start;
 }
 
 // (the caller holds ctx->mu)  pairing_ok (may be null): the pairing's own verdict, before the records' failure counts are folded into `ok`
@@ -388,7 +403,7 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
     int ok = 0, pairing_ok = 0;
     if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy, &pairing_ok))) return rc;
     // identification: only a failing pairing has failing proofs to find (a proof with a non-zero status contributes nothing to it)
-    if (n_checks && !pairing_ok && (rc = identify_search(held->on, st, n_checks))) return rc;
+    if (n_checks && !pairing_ok && (rc = identify_search(held->on, whole_batches(st), false, st, n_checks))) return rc;
     if (per_proof_status)
         for (size_t gi = 0; gi < groups.size(); ++gi)
             for (size_t j = 0; j < groups[gi].idx.size(); ++j) per_proof_status[groups[gi].idx[j]] = st[gi][j];
@@ -449,18 +464,24 @@ int h2v_verify_batch(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const
 // draw before the proof's Guard joins (strategy.rs:129), so the seed ends up scaled by the product of ALL n draws of this call:
 // the seed's two channels are evaluated (two pooled MSMs with the scalars already multiplied by that product), written as a
 // record, and folded with the batch's own record into the one pairing.
-int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
-                            const size_t* col_lens, const uint8_t* rand32,
-                            const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
-                            const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
-                            int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
+// n_checks (h2v_verify_batch_seeded_identify): identification as well.  The seed's terms belong to no proof, so the failing proofs
+// are those of the batch's OWN record — record 0 of the fold, still in device memory: h2v_batch_identify checks it on its own and
+// searches only when it fails.  seed_ok: the pairing of the evaluated seed alone (scaled by the product of the draws, which is
+// non-zero: the verdict of the seed as it was given).  Nothing is written before the call's last step.
+static int verify_seeded(const char* who, h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
+                         size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
+                         const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
+                         const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
+                         int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, int* seed_ok, size_t* n_checks) {
+    const std::string w(who);
     if (!ctx || (n_seed_left && (!seed_left_scalars32 || !seed_left_bases64)) || (n_seed_right && (!seed_right_scalars32 || !seed_right_bases64))) {
-        set_last_error("h2v_verify_batch_seeded: null argument"); return H2V_ERR_BAD_ARGUMENT;
+        set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT;
     }
-    if (n_seed_left > (1u << 24) || n_seed_right > (1u << 24)) { set_last_error("h2v_verify_batch_seeded: seed too large"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n_seed_left > (1u << 24) || n_seed_right > (1u << 24)) { set_last_error(w + ": seed too large"); return H2V_ERR_BAD_ARGUMENT; }
     int rc;
     std::vector<uint8_t> os_rand;
-    if ((rc = resolve_draws(rand32, n, os_rand, "h2v_verify_batch_seeded"))) return rc;
+    // (identification: a single proof's check equals SingleStrategy's only when its multiplier is non-zero)
+    if ((rc = resolve_draws(rand32, n, os_rand, who, n_checks != nullptr))) return rc;
     // the product of this call's draws, and the seed's scalars times it (host: a few hundred Fr products)
     Fr M = Fr::one();
     for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
@@ -471,30 +492,70 @@ int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs
         sc[side].resize(32 * ns[side]);
         for (size_t j = 0; j < ns[side]; ++j) {
             Fr v;
-            if (!Fr::from_bytes(in_s[side] + 32 * j, v)) { set_last_error("h2v_verify_batch_seeded: seed scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
+            if (!Fr::from_bytes(in_s[side] + 32 * j, v)) { set_last_error(w + ": seed scalar not canonical"); return H2V_ERR_BAD_ARGUMENT; }
             (v * M).to_bytes(&sc[side][32 * j]);
         }
     }
     uint8_t seed_xy[128]; int ident = 0;
-    // (before the scratch batch is taken: h2v_msm_g1 holds ctx->mu itself)
+    // (before the scratch batch is taken: h2v_msm_g1 and h2v_pairing_check hold ctx->mu themselves)
     if ((rc = h2v_msm_g1(ctx, sc[0].data(), seed_left_bases64, n_seed_left, seed_xy, &ident))) return rc;         // (rejects bases that are not on the curve)
     if ((rc = h2v_msm_g1(ctx, sc[1].data(), seed_right_bases64, n_seed_right, seed_xy + 64, &ident))) return rc;
+    int seed_passes = 1;   // (an empty seed: two identities)
+    if (n_checks && (n_seed_left || n_seed_right) && (rc = h2v_pairing_check(ctx, seed_xy, seed_xy + 64, &seed_passes))) return rc;
     // the proofs: one batch without its pairing, kept for the fold
     ScratchBatch sb(ctx);
-    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 0, false, per_proof_status, nullptr, nullptr, nullptr))) return rc;
+    std::vector<int> st(n ? n : 1, 0);
+    if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 0, false, st.data(), nullptr, nullptr, nullptr))) return rc;
     h2v_batch* b = sb.b;
     if (hipSetDevice(ctx->device) != hipSuccess) return H2V_ERR_DEVICE;
     DevBuf<uint8_t> d_xy, d_records; DevBuf<G1A> d_aff; DevBuf<G1J> d_jac; DevBuf<uint32_t> d_flags;
     if ((rc = d_xy.alloc(128)) || (rc = d_records.alloc(2 * H2V_ACC_RECORD_BYTES)) || (rc = d_aff.alloc(2)) || (rc = d_jac.alloc(2)) || (rc = d_flags.alloc(2))) return rc;
     hipStream_t s = b->stream;
-    if (hipMemcpyAsync(d_xy.p, seed_xy, 128, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error("h2v_verify_batch_seeded: copy failed"); return H2V_ERR_DEVICE; }
+    if (hipMemcpyAsync(d_xy.p, seed_xy, 128, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error(w + ": copy failed"); return H2V_ERR_DEVICE; }
     if ((rc = bases_from_bytes_enqueue(s, d_xy.p, d_aff.p, d_flags.p, 2))) return rc;
     if ((rc = affine_to_jacobian_enqueue(s, d_aff.p, d_jac.p, 2))) return rc;
     if ((rc = h2v_batch_export_accumulators(b, d_records.p))) return rc;                                                                  // record 0: the proofs of this call
     if ((rc = export_records_enqueue(s, d_jac.p, nullptr, 1, 0, nullptr, 0, 1, d_records.p + H2V_ACC_RECORD_BYTES))) return rc;   // record 1: the scaled seed
     if ((rc = h2v_batch_fold_check_enqueue(b, d_records.p, 2))) return rc;
     // (synchronises: the scoped buffers outlive their use)
-    return collect_group(sb, sb.b, 0, nullptr, batch_ok, out_left_xy, out_right_xy);
+    int ok = 0; uint8_t left[64], right[64];
+    if ((rc = collect_group(sb, sb.b, 0, nullptr, &ok, left, right))) return rc;
+    size_t checks = 0;
+    if (n_checks) {
+        // the statuses the device set; those pack_inputs forced (a short proof: its points undecodable, so never flagged) go over them
+        int own_ok = 0;
+        if ((rc = h2v_batch_identify(b, d_records.p, st.data(), &own_ok, &checks))) return rc;
+    }
+    for (size_t i = 0; i < n; ++i) if (sb.forced[i]) st[i] = sb.forced[i];
+    if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[i];
+    if (batch_ok) *batch_ok = ok;
+    if (out_left_xy) memcpy(out_left_xy, left, 64);
+    if (out_right_xy) memcpy(out_right_xy, right, 64);
+    if (seed_ok) *seed_ok = seed_passes;
+    if (n_checks) *n_checks = checks;
+    return 0;
+}
+
+int h2v_verify_batch_seeded(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
+                            const size_t* col_lens, const uint8_t* rand32,
+                            const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
+                            const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
+                            int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
+    return verify_seeded("h2v_verify_batch_seeded", ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, seed_left_scalars32, seed_left_bases64,
+                         n_seed_left, seed_right_scalars32, seed_right_bases64, n_seed_right, per_proof_status, batch_ok, out_left_xy, out_right_xy, nullptr, nullptr);
+}
+
+int h2v_verify_batch_seeded_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
+                                     size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
+                                     const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
+                                     const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
+                                     int* per_proof_status, int* batch_ok, int* seed_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks) {
+    size_t checks = 0;
+    const int rc = verify_seeded("h2v_verify_batch_seeded_identify", ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, seed_left_scalars32,
+                                 seed_left_bases64, n_seed_left, seed_right_scalars32, seed_right_bases64, n_seed_right, per_proof_status, batch_ok, out_left_xy, out_right_xy,
+                                 seed_ok, &checks);
+    if (!rc && n_range_checks) *n_range_checks = checks;
+    return rc;
 }
 
 int h2v_verify_batch_shapes(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
@@ -540,7 +601,7 @@ int h2v_verify_batch_identify(h2v_ctx* ctx, size_t n, const uint8_t* const* proo
     ScratchBatch sb(ctx);
     if ((rc = pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, st[0].data(), &ok, out_left_xy, out_right_xy))) return rc;
     size_t checks = 0;
-    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search({sb.b}, st, &checks))) return rc;
+    if (n && !pairing_passed(sb.b, 0) && (rc = identify_search({sb.b}, whole_batches(st), true, st, &checks))) return rc;
     if (per_proof_status) for (size_t i = 0; i < n; ++i) per_proof_status[i] = st[0][i];
     if (batch_ok) *batch_ok = ok;
     if (n_range_checks) *n_range_checks = checks;

@@ -17,6 +17,9 @@ Entry points
   verify_batch_sharded_local(ctx, proofs, instances, rand, world)
       the same computation with the `world` shards run one after the other on ONE GPU (no process group): sharding invariance
       at full size on a single device, and hosts with one GPU.
+  verify_batch_sharded_identify / verify_batch_sharded_local_identify
+      the same two with the failing proofs named: statuses[i] is what SingleStrategy reports for proof i.  Every rank searches its
+      own shard only (ShardedBatch.identify), and nothing but the existing status gather crosses ranks.
   ShardedBatch
       the staged form both are built on (and bench.py pipelines): upload the shard once, launch() = shard pipeline -> export ->
       all-gather -> fold -> one pairing, asynchronous on the batch's stream; finish() fetches the verdict.
@@ -155,6 +158,8 @@ class ShardedBatch:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)   # (allocated and zeroed on torch's current stream, written on the batch's)
         self.gathered = None
+        self._exchanged = False     # the last launch exported its records (and a fold may have replaced the batch's own accumulators)
+        self._finished = None       # what the last finish() returned
 
     def close(self):
         if self.batch is not None:
@@ -170,6 +175,7 @@ class ShardedBatch:
         """Shard pipeline without a pairing + export of the accumulator records -> the local record tensor (stream-ordered)."""
         self.batch.launch(with_pairing=False)
         self.batch.export_accumulators(self.records.data_ptr())
+        self._exchanged = True
         return self.records
 
     def fold(self, gathered, n_records: int):
@@ -182,17 +188,20 @@ class ShardedBatch:
         (h2v_batch_upload_launch): for shards that arrive from the host for every batch."""
         if self.world == 1 and not self.always_exchange:
             self.batch.upload_launch(proofs_flat, proof_len, instances_flat, col_lens, rand_tail, with_pairing=True)
+            self._exchanged = False
             return
         import torch
         ctxm = torch.cuda.stream(self._external_stream()) if (self.device.type == "cuda" and self._stream_handle is not None) else _NullCtx()
         with ctxm:
             self.batch.upload_launch(proofs_flat, proof_len, instances_flat, col_lens, rand_tail, with_pairing=False)
             self.batch.export_accumulators(self.records.data_ptr())
+            self._exchanged = True
             self.fold(gather_accumulators(self.records, self.world, self.group), self.world)
 
     def launch(self):
         if self.world == 1 and not self.always_exchange:
             self.batch.launch(with_pairing=True)
+            self._exchanged = False
             return
         import torch
         ctxm = torch.cuda.stream(self._external_stream()) if (self.device.type == "cuda" and self._stream_handle is not None) else _NullCtx()
@@ -209,7 +218,27 @@ class ShardedBatch:
     def finish(self, raw_statuses=False):
         """-> (group_ok[groups], local statuses, left_xy[groups], right_xy[groups]); the verdict and the accumulators are those of
         the WHOLE sharded batch (identical on every rank), the statuses are this rank's proofs'."""
-        return self.batch.finish_groups(raw_statuses=raw_statuses)
+        self._finished = self.batch.finish_groups(raw_statuses=raw_statuses)
+        return self._finished
+
+    def identify(self, verdicts=None):
+        """After finish(): which of THIS rank's proofs fail the pairing (Batch.identify) -> (local statuses, range_checks).  Local to
+        the rank, no collective: a shard's own sum, sum over its proofs of (the product of all later draws of the batch) * Guard_i, is a
+        random linear combination with distinct monomials, so a shard holding a bad proof fails its own pairing except with
+        probability <= count / r, a shard of good proofs always passes, and the whole batch is the product of the shards' checks.  The
+        rank's own accumulators are lost at the fold (it overwrites the pieces in the workspace) and survive in the record the rank
+        exported: `records` is passed on whenever the launch exchanged records.
+        verdicts: the groups' verdicts of the whole batch, default the last finish()'s (verify_batch_sharded_local passes the fold's,
+        which only shard 0 sees).  When every one passed, the finished statuses come back with 0 range checks and nothing runs."""
+        if self._finished is None:
+            raise ValueError("identify() comes after finish()")
+        group_ok, statuses = self._finished[0], self._finished[1]
+        if isinstance(statuses, (bytes, bytearray)):
+            statuses = memoryview(bytes(statuses)).cast('i').tolist()
+        if all(group_ok if verdicts is None else verdicts):
+            return list(statuses), 0
+        st, _, checks = self.batch.identify(self.records.data_ptr() if self._exchanged else None)
+        return st, checks
 
 
 class _NullCtx:
@@ -260,7 +289,15 @@ def _all_statuses(local, n, world, group, backend, device):
     return res
 
 
-def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None):
+def _refuse_zero_draws(draws: bytes):
+    """Identification needs every multiplier non-zero (a single proof's check is SingleStrategy's only then).  Every rank holds the whole
+    draw stream, so every rank refuses the same batches, before any upload: none enters a collective the others skip."""
+    zero = bytes(32)
+    if any(draws[i:i + 32] == zero for i in range(0, len(draws), 32)):
+        raise ValueError("identification takes non-zero draws: a draw of the batch is zero")
+
+
+def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, identify=False):
     """N x verify_proof under ONE AccumulatorStrategy followed by finalize() (lib.rs:33-425, kzg/strategy.rs:125-140) with the
     proofs sharded over the ranks of `group` (default: the world) — BASELINE.json configs 3 and 5.
 
@@ -268,12 +305,15 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     Context (one per GPU).  rand: the n Fr::random draws in call order, the same on every rank — or None: rank 0 draws them from
     the OS and broadcasts.  Rank r verifies shard_bounds(n, world, r) with the draw tail of its global position, the 1312-byte
     accumulator records are all-gathered (RCCL under the nccl backend), folded, and ONE pairing closes the batch.
-    -> (ok, statuses[n], left_xy, right_xy), identical on every rank and — for given draws — for every world size."""
+    -> (ok, statuses[n], left_xy, right_xy), identical on every rank and — for given draws — for every world size.
+    identify: verify_batch_sharded_identify's form -> (ok, statuses[n], left_xy, right_xy, local_range_checks)."""
     rank, world, backend = _group_info(group)
     n = len(proofs)
     if device is None and batch_factory is None:
         device = f"cuda:{ctx.device}"
     draws = common_draws(n, rand, group, device)
+    if identify:
+        _refuse_zero_draws(draws)
     lo, hi = shard_bounds(n, world, rank)
     flat, plen, iflat, lens = _flatten(proofs[lo:hi], instances[lo:hi])
     if lens is None:                       # an empty shard still takes part in the collectives
@@ -285,21 +325,39 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
         sb.upload(flat, plen, iflat, lens, tail_for_shard(draws, lo))
         sb.launch()
         ok, st, left, right = sb.finish()
+        checks = 0
+        if identify:
+            st, checks = sb.identify()
     finally:
         sb.close()
     statuses = _all_statuses(st, n, world, group, backend, sb.device)
+    if identify:
+        return bool(ok[0]), statuses, left[0], right[0], checks
     return bool(ok[0]), statuses, left[0], right[0]
 
 
-def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_factory=None, device=None):
+def verify_batch_sharded_identify(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None):
+    """verify_batch_sharded plus the proofs that made it fail.  -> (ok, statuses[n], left_xy, right_xy, local_range_checks): ok / left_xy /
+    right_xy are verify_batch_sharded's, statuses[i] is what Context.verify_each returns for proof i — identical on every rank and for
+    every world size — and local_range_checks is the number of range checks THIS rank's search ran (0 on a rank whose shard is clean, and
+    everywhere when the batch passes).  Every rank searches its own shard (ShardedBatch.identify) before the status all-gather that
+    verify_batch_sharded ends with; no other collective is added.  A zero among the common draws raises ValueError on every rank before
+    any upload."""
+    return verify_batch_sharded(ctx, proofs, instances, rand, group, batch_factory, device, identify=True)
+
+
+def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_factory=None, device=None, identify=False):
     """The `world`-rank computation of verify_batch_sharded run shard after shard on ONE device, no process group: every shard is
     uploaded with the draw tail of its global position and launched without a pairing, the records are laid out as the all-gather
-    would, shard 0 folds them and runs the one pairing.  -> (ok, statuses[n], left_xy, right_xy)."""
+    would, shard 0 folds them and runs the one pairing.  -> (ok, statuses[n], left_xy, right_xy).
+    identify: verify_batch_sharded_local_identify's form -> (ok, statuses[n], left_xy, right_xy, range_checks[world])."""
     import torch
     n = len(proofs)
     if rand is not None and len(rand) != n:
         raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
     draws = _scalar_bytes(rand) if rand is not None else draw_scalars(n)
+    if identify:
+        _refuse_zero_draws(draws)
     if device is None and batch_factory is None:
         device = f"cuda:{ctx.device}"
     shards, statuses = [], []
@@ -321,7 +379,22 @@ def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_f
             torch.cuda.synchronize(gathered.device)
         shards[0].fold(gathered, world)
         ok, _, left, right = shards[0].finish()
+        checks = []
+        if identify:   # every shard searches its own proofs, told the verdict of the whole batch
+            statuses = []
+            for sb in shards:
+                st, c = sb.identify(verdicts=ok)
+                statuses += st
+                checks.append(c)
     finally:
         for sb in shards:
             sb.close()
+    if identify:
+        return bool(ok[0]), statuses, left[0], right[0], checks
     return bool(ok[0]), statuses, left[0], right[0]
+
+
+def verify_batch_sharded_local_identify(ctx, proofs, instances, rand, world: int, batch_factory=None, device=None):
+    """verify_batch_sharded_identify's computation in verify_batch_sharded_local's sequential one-GPU form.
+    -> (ok, statuses[n], left_xy, right_xy, range_checks[world]): the range checks every shard's search ran, shard by shard."""
+    return verify_batch_sharded_local(ctx, proofs, instances, rand, world, batch_factory, device, identify=True)

@@ -156,6 +156,22 @@ def _rand_bytes(rand, n):
     return b"".join(_scalar32(r) for r in rand)
 
 
+def _seed_sides(seed):
+    """The two channels of a seed DualMSM, ((left_scalars, left_bases), (right_scalars, right_bases)), as the (scalar bytes, base bytes,
+    n) triples the seeded entry points take"""
+    sides = []
+    for scalars, bases in seed:
+        scalars, bases = list(scalars), list(bases)
+        if len(scalars) != len(bases):
+            raise ValueError("seed scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
+        if any(len(b) != 64 for b in bases):
+            raise ValueError("every seed base must be 64 bytes (x | y)")
+        sides.append((b"".join(_scalar32(x) for x in scalars), b"".join(bases), len(scalars)))
+    if len(sides) != 2:
+        raise ValueError("a seed is (left, right)")
+    return sides
+
+
 def _marshal_batch(contexts, proofs, instances, key_of_proof=None):
     """Pointer arrays for the one-shot calls.  Everything the C side will index is checked here: one instance list per proof,
     proofs are bytes, key indices are in range, every scalar is 32 bytes, the proofs of a key have one column count.  Proof i
@@ -280,14 +296,7 @@ class Context:
         if seed is not None:
             if not all(l == shapes[0] for l in shapes):
                 raise ValueError("a seeded batch takes one instance shape")
-            sides = []
-            for scalars, bases in seed:
-                scalars, bases = list(scalars), list(bases)
-                if len(scalars) != len(bases):
-                    raise ValueError("seed scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
-                if any(len(b) != 64 for b in bases):
-                    raise ValueError("every seed base must be 64 bytes (x | y)")
-                sides.append((b"".join(_scalar32(x) for x in scalars), b"".join(bases), len(scalars)))
+            sides = _seed_sides(seed)
             check(self._lib.h2v_verify_batch_seeded(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, *sides[0], *sides[1], st, ctypes.byref(ok),
                                                     left, right))
         elif all(l == shapes[0] for l in shapes):
@@ -296,11 +305,13 @@ class Context:
             check(self._lib.h2v_verify_batch_shapes(self._h, n, pa, pl, ia, ncols, _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok), left, right))
         return bool(ok.value), list(st)[:n], left.raw, right.raw
 
-    def verify_batch_identify(self, proofs, instances, rand=None):
+    def verify_batch_identify(self, proofs, instances, rand=None, seed=None):
         """verify_batch plus the proofs that made it fail (h2v_verify_batch_identify).  Returns (batch_ok, statuses, left_xy, right_xy):
         batch_ok / left_xy / right_xy are what verify_batch returns for the same arguments, statuses[i] is what verify_each returns for
         proof i.  rand: n non-zero scalars or None.  One instance shape per call.  The number of range checks the search ran is kept in
-        self.last_range_checks."""
+        self.last_range_checks.
+        seed: as verify_batch's (h2v_verify_batch_seeded_identify).  The seed enters no proof's check; self.last_seed_ok says whether
+        the seed alone passes the pairing (True without a seed, and for an empty one)."""
         n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
         if not all(l == shapes[0] for l in shapes):
             raise ValueError("verify_batch_identify takes one instance shape per call")
@@ -309,8 +320,14 @@ class Context:
         ok = ctypes.c_int(0)
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
         checks = ctypes.c_size_t(0)
-        check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
-        self.last_range_checks = checks.value
+        seed_ok = ctypes.c_int(1)
+        if seed is not None:
+            sides = _seed_sides(seed)
+            check(self._lib.h2v_verify_batch_seeded_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, *sides[0], *sides[1], st, ctypes.byref(ok),
+                                                             ctypes.byref(seed_ok), left, right, ctypes.byref(checks)))
+        else:
+            check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
+        self.last_range_checks, self.last_seed_ok = checks.value, bool(seed_ok.value)
         return bool(ok.value), list(st)[:n], left.raw, right.raw
 
     def verify_each(self, proofs, instances):
@@ -373,19 +390,31 @@ class AccumulatorStrategy(_Strategy):
         """finalize() plus the proofs that made it fail (h2v_verify_batch_keys_identify), over one or several VerifyingKeys and any
         instance shapes.  Returns what finalize() returns; afterwards `statuses` holds, proof by proof in accumulation order, what
         SingleStrategy reports for it (ConstraintSystemFailure for the proofs whose own pairing fails), `left_xy` / `right_xy` the
-        evaluated channels and `last_range_checks` the number of range checks the search ran.  The draws must be non-zero."""
-        if self.seed is not None:
-            raise ValueError("identification takes an accumulation without a seed")
+        evaluated channels and `last_range_checks` the number of range checks the search ran.  The draws must be non-zero.
+        A seeded accumulation (with_accumulator) takes proofs of one VerifyingKey and one instance shape, as finalize() does; the seed
+        enters no proof's check, and `last_seed_ok` says whether the seed alone passes the pairing."""
         n = len(self._items)
         rand = self.rand
         if rand is not None and len(rand) != n:
             raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
-        if not self._items:
+        self.last_seed_ok = True
+        if not self._items:   # (as finalize())
             self.statuses, self.last_range_checks = [], 0
             return True
         keys = {}
         for vk, _, _ in self._items:
             keys.setdefault((vk.data, int(vk.format)), vk)
+        if self.seed is not None:
+            if len(keys) != 1:
+                raise ValueError("a seeded accumulation takes proofs of one VerifyingKey")
+            ctx = Context(self.params, self._items[0][0], self.device, circuit_instances=self.circuit_instances)
+            try:
+                ok, self.statuses, self.left_xy, self.right_xy = ctx.verify_batch_identify([p for _, _, p in self._items], [i for _, i, _ in self._items], rand,
+                                                                                           seed=self.seed)
+                self.last_range_checks, self.last_seed_ok = ctx.last_range_checks, ctx.last_seed_ok
+                return ok
+            finally:
+                ctx.close()
         index = {key: k for k, key in enumerate(keys)}
         ctxs = []
         try:
@@ -836,6 +865,20 @@ class Batch:
         check(self._lib.h2v_batch_recheck(self._h, k, first, count, ok, left, right))
         lr, rr = left.raw, right.raw
         return [bool(v) for v in ok][:k], [lr[64 * i:64 * i + 64] for i in range(k)], [rr[64 * i:64 * i + 64] for i in range(k)]
+
+    def identify(self, own_records=None):
+        """Which proofs of the last finished launch fail the pairing (h2v_batch_identify), whatever closed the launch: its own pairing,
+        none, or a later fold.  own_records: the device address (or a tensor) of the records export_accumulators wrote for this launch —
+        needed after fold_check_enqueue, which overwrites the batch's own accumulators; None otherwise.
+        -> (statuses, group_own_ok[groups], range_checks): statuses[i] is what verify_each returns for proof i, group_own_ok[g] the
+        pairing check of group g's own accumulators.  The launch's results are untouched."""
+        if own_records is not None and hasattr(own_records, "data_ptr"):
+            own_records = own_records.data_ptr()
+        st = (ctypes.c_int * max(self.n, 1))()
+        own = (ctypes.c_int * self.groups)()
+        checks = ctypes.c_size_t(0)
+        check(self._lib.h2v_batch_identify(self._h, ctypes.c_void_p(own_records) if own_records is not None else None, st, own, ctypes.byref(checks)))
+        return memoryview(st).cast('B').cast('i').tolist()[:self.n], [bool(v) for v in own], checks.value
 
     PROFILE_KERNEL = 3   # H2V_PROFILE_KERNEL: the dominant kernel's own timestamps only
 

@@ -334,6 +334,23 @@ int h2v_verify_batch_keys_identify(h2v_ctx* const* ctxs, size_t n_keys, const ui
                                    const uint8_t* rand32, int* per_proof_status, int* batch_ok,
                                    uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks);
 
+/* h2v_verify_batch_seeded, plus the proofs that fail the pairing.  Takes the arguments of h2v_verify_batch_seeded; batch_ok /
+ * out_left_xy / out_right_xy are exactly what it returns for them (seed included).  The seed's terms belong to no proof, so it enters
+ * no proof's check: per_proof_status[i] is what h2v_verify_each returns for proof i, and seed_ok (may be NULL) is the pairing check
+ * of the evaluated seed alone (1 for an empty seed) — batch_ok = 0 with every status 0 and seed_ok = 0 says "the accumulator this call
+ * resumed was bad already".  The batch's own record (the sum over this call's proofs, without the seed) is checked on its own, and the
+ * search (h2v_batch_identify on that record) runs only when it fails.  rand32 must hold no zero scalar (H2V_ERR_BAD_ARGUMENT before
+ * any device work); NULL = draw from the OS RNG.  n_range_checks (may be NULL): how many range checks the search ran.  Nothing is
+ * written on an error. */
+int h2v_verify_batch_seeded_identify(h2v_ctx* ctx, size_t n,
+                                     const uint8_t* const* proofs, const size_t* proof_lens,
+                                     const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
+                                     const uint8_t* rand32,
+                                     const uint8_t* seed_left_scalars32, const uint8_t* seed_left_bases64, size_t n_seed_left,
+                                     const uint8_t* seed_right_scalars32, const uint8_t* seed_right_bases64, size_t n_seed_right,
+                                     int* per_proof_status, int* batch_ok, int* seed_ok,
+                                     uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_range_checks);
+
 /* Debug / parity: the Guard of one proof term by term in the order the reference appends them (shplonk.rs:256-264;
  * gwc.rs:86-132: witness_with_aux, commitment_multi query by query — a commitment opened at several points occurs once per
  * query, each time with that query's own scalar — then (eval_multi, -g)), and the
@@ -356,7 +373,7 @@ int h2v_random_scalars(uint8_t* out32, size_t n);
  * and closes with h2v_batch_fold_check_enqueue (or h2v_fold_check).
  * After an error from h2v_batch_upload, h2v_batch_launch, h2v_batch_upload_launch, h2v_batch_finish(_groups) or
  * h2v_batch_fold_check_enqueue the batch holds nothing: every call that works on an upload or a launch (launch, finish,
- * finish_groups, recheck, export_accumulators, fold_check_enqueue) returns H2V_ERR_BAD_ARGUMENT until an upload succeeds.
+ * finish_groups, recheck, identify, export_accumulators, fold_check_enqueue) returns H2V_ERR_BAD_ARGUMENT until an upload succeeds.
  * h2v_batch_set_groups leaves the batch empty in the same way. */
 int h2v_batch_create(h2v_ctx* ctx, size_t max_proofs, size_t max_instance_values_per_proof, h2v_batch** out);
 void h2v_batch_destroy(h2v_batch* b);
@@ -411,6 +428,27 @@ int h2v_batch_recheck(h2v_batch* b, size_t n_ranges, const size_t* first, const 
  * batch's own results are touched. */
 int h2v_batches_recheck(h2v_batch* const* batches, size_t n_batches, size_t n_ranges, const uint32_t* batch_of_range,
                         const size_t* first, const size_t* count, int* range_ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
+/* Which proofs of the last FINISHED launch of b fail the pairing — whatever closed it: its own pairing checks, none (a shard), or a
+ * later h2v_batch_fold_check_enqueue (a sharded or seeded batch); any group count.
+ * Step 1, the groups' own verdicts: group_own_ok[g] (groups entries, may be NULL) = the raw bit of e(L_g, s_g2) e(R_g, -g2) == 1 over
+ * group g's OWN accumulators, sum over the group's proofs of multiplier_p * Guard_p — what the launch's pairing says when it ran and
+ * no fold followed, otherwise one pairing launch over all groups; no MSM runs.  A group of good proofs always passes; a group of
+ * count proofs holding a bad one passes with probability <= count / r (its sum is a random linear combination with distinct
+ * monomials in the draws), whatever other shards or a seed add to the batch's final verdict.
+ * own_records: the device address of the groups x H2V_ACC_RECORD_BYTES records h2v_batch_export_accumulators wrote for THIS launch, or
+ * NULL when the batch's resident accumulators are still its own.  A fold overwrites them: NULL after a fold is
+ * H2V_ERR_BAD_ARGUMENT.  A record whose piece count is outside 1 .. H2V_ACC_RECORD_PIECES, or whose failure count differs from the
+ * group's number of non-zero statuses, is H2V_ERR_BAD_ARGUMENT.
+ * Step 2: the groups whose own check fails are searched together, as h2v_verify_batch_keys_identify searches its batches: failing
+ * ranges are re-checked on the resident scalars (h2v_batch_recheck) and cut until single proofs remain.
+ * per_proof_status[i] (n entries, may be NULL): the launch's status for proof i, and H2V_ERR_CONSTRAINT_SYSTEM_FAILURE for the proofs
+ * with status 0 whose own check fails — what h2v_verify_each returns.  n_range_checks (may be NULL): the ranges handed to re-check
+ * launches (the pairing of step 1 not counted; 0 when every group passes).
+ * H2V_ERR_BAD_ARGUMENT, before any device work, when a proof of the batch has a zero multiplier (a zero draw behind it in its
+ * group's uploaded draws: h2v_batch_recheck's rule), or when the batch is not finished.  The launch's results, its accumulators and
+ * its workspace are untouched (h2v_batch_finish_groups afterwards returns what it returned before), and a call that returns
+ * non-zero writes nothing.  Synchronous. */
+int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_status, int* group_own_ok, size_t* n_range_checks);
 /* Device address of this batch's accumulator points after launch: per group [left, right], 2 x 108 bytes each, Jacobian
  * (X, Y, Z) in the library's Montgomery limb layout (debug / inspection; the record a sharded run exchanges is written by
  * h2v_batch_export_accumulators). */

@@ -163,9 +163,9 @@ public:
     }
     // finalize() plus the proofs that made the batch fail (h2v_verify_batch_identify): returns what finalize() returns, and statuses()
     // then holds, for every proof, the plonk::Error SingleStrategy reports for it — ConstraintSystemFailure for the proofs whose own
-    // pairing fails.  The draws must be non-zero.  One instance shape, no seed.
+    // pairing fails.  The draws must be non-zero.  One instance shape.  A seeded accumulation (with) runs
+    // h2v_verify_batch_seeded_identify: the seed enters no proof's check, and seed_ok() says whether the seed alone passes the pairing.
     bool finalize_identify() {
-        if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes an accumulation without a seed");
         if (vks_.size() > 1) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes proofs of one VerifyingKey");
         Context ctx(params_, vk(), device_, mo_, tr_, ci_);
         size_t ncols = 0;
@@ -174,9 +174,15 @@ public:
         if (!pk.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes one instance shape");
         if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
         statuses_.assign(items_.size() ? items_.size() : 1, 0);
-        int ok = 0;
-        check(h2v_verify_batch_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
-                                        rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_, &range_checks_));
+        int ok = 0, seed_ok = 1;
+        if (seeded_)
+            check(h2v_verify_batch_seeded_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
+                                                   rand_.empty() ? nullptr : rand_.data(), seed_ls_.data(), seed_lb_.data(), seed_ls_.size() / 32, seed_rs_.data(),
+                                                   seed_rb_.data(), seed_rs_.size() / 32, statuses_.data(), &ok, &seed_ok, left_, right_, &range_checks_));
+        else
+            check(h2v_verify_batch_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
+                                            rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_, &range_checks_));
+        seed_ok_ = seed_ok != 0;
         statuses_.resize(items_.size());
         return ok != 0;
     }
@@ -196,6 +202,7 @@ public:
         statuses_.resize(items_.size());
         return ok != 0;
     }
+    bool seed_ok() const { return seed_ok_; }               // the last finalize_identify(): the seed alone passes the pairing (true without a seed)
     size_t range_checks() const { return range_checks_; }   // re-checks the last finalize_identify() or finalize_identify_keys() ran (0: the batch passed)
     const std::vector<int>& statuses() const { return statuses_; }
     const uint8_t* left() const { return left_; }     // evaluated channels of the final DualMSM, canonical x|y
@@ -245,6 +252,7 @@ private:
     Bytes seed_ls_, seed_lb_, seed_rs_, seed_rb_;
     std::vector<int> statuses_;
     size_t range_checks_ = 0;
+    bool seed_ok_ = true;
     uint8_t left_[64] = {0}, right_[64] = {0};
 };
 

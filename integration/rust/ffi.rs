@@ -103,6 +103,12 @@ extern "C" {
                                           proof_lens: *const usize, instances32: *const *const u8, n_instance_columns: *const usize, col_lens: *const usize,
                                           rand32: *const u8, per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8,
                                           n_range_checks: *mut usize) -> c_int;
+    pub fn h2v_verify_batch_seeded_identify(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
+                                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, rand32: *const u8,
+                                            seed_left_scalars32: *const u8, seed_left_bases64: *const u8, n_seed_left: usize,
+                                            seed_right_scalars32: *const u8, seed_right_bases64: *const u8, n_seed_right: usize,
+                                            per_proof_status: *mut c_int, batch_ok: *mut c_int, seed_ok: *mut c_int, out_left_xy: *mut u8,
+                                            out_right_xy: *mut u8, n_range_checks: *mut usize) -> c_int;
     pub fn h2v_guard_msm(ctx: *mut h2v_ctx, proof: *const u8, proof_len: usize, instances32: *const u8, n_instance_columns: usize, col_lens: *const usize,
                          right_scalars32: *mut u8, right_bases64: *mut u8, n_right: *mut usize,
                          left_scalars32: *mut u8, left_bases64: *mut u8, n_left: *mut usize,
@@ -123,6 +129,8 @@ extern "C" {
                              out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_batches_recheck(batches: *const *mut h2v_batch, n_batches: usize, n_ranges: usize, batch_of_range: *const u32, first: *const usize,
                                count: *const usize, range_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
+    pub fn h2v_batch_identify(b: *mut h2v_batch, own_records: *const c_void, per_proof_status: *mut c_int, group_own_ok: *mut c_int,
+                              n_range_checks: *mut usize) -> c_int;
     pub fn h2v_batch_accumulators(b: *mut h2v_batch, device_ptr: *mut *mut c_void, nbytes: *mut usize) -> c_int;
     pub fn h2v_batch_stream(b: *mut h2v_batch) -> *mut c_void;
     pub fn h2v_batch_set_stream(b: *mut h2v_batch, hip_stream: *mut c_void) -> c_int;

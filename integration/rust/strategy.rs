@@ -2,6 +2,10 @@
 //!
 //! * `GpuBatchVerifier`        — whole-batch seam: N x `verify_proof` + `AccumulatorStrategy::finalize`
 //!                               (halo2_verifier/src/lib.rs:33-49, poly/kzg/strategy.rs:125-140) in one call.
+//!                               `with_seed` resumes an existing accumulator (`AccumulatorStrategy::with`), and
+//!                               `finalize_identify` names the failing proofs, with or without a seed.
+//! * `GpuStagedBatch`          — the staged interface (h2v_batch_*): proofs resident on the GPU, `upload` / `launch` / `finish`, and
+//!                               `identify` on the finished launch — also after a fold (a shard of a sharded batch).
 //! * `GpuMultiKeyVerifier`     — the same seam over several VerifyingKeys sharing the params: one context per key,
 //!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
 //! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
@@ -37,6 +41,19 @@ pub struct GpuBatchVerifier<'p> {
     proofs: Vec<&'p [u8]>,
     instances: Vec<Vec<u8>>,
     col_lens: Vec<usize>,
+    seed: Option<[(Vec<u8>, Vec<u8>); 2]>,   // (scalars, bases) of the left and the right channel
+}
+
+/// The terms of one `MSMKZG` channel as the C ABI takes them: 32-byte scalars, 64-byte x | y bases (all-zero = identity).
+fn flat_terms(terms: &[(Fr, G1Affine)]) -> (Vec<u8>, Vec<u8>) {
+    let (mut s, mut b) = (Vec::new(), Vec::new());
+    for (k, p) in terms {
+        s.extend_from_slice(k.to_repr().as_ref());
+        let c = p.coordinates();
+        if bool::from(c.is_some()) { let c = c.unwrap(); b.extend_from_slice(c.x().to_repr().as_ref()); b.extend_from_slice(c.y().to_repr().as_ref()); }
+        else { b.extend_from_slice(&[0u8; 64]); }
+    }
+    (s, b)
 }
 
 impl<'p> GpuBatchVerifier<'p> {
@@ -47,7 +64,14 @@ impl<'p> GpuBatchVerifier<'p> {
         let mut ctx = core::ptr::null_mut();
         let rc = unsafe { h2v_ctx_create(pb.as_ptr(), pb.len(), H2V_SERDE_RAW_BYTES, vb.as_ptr(), vb.len(), H2V_SERDE_RAW_BYTES, device, &mut ctx) };
         if rc != 0 { return Err(map_err(rc)); }
-        Ok(Self { ctx, proofs: Vec::new(), instances: Vec::new(), col_lens: Vec::new() })
+        Ok(Self { ctx, proofs: Vec::new(), instances: Vec::new(), col_lens: Vec::new(), seed: None })
+    }
+
+    /// `AccumulatorStrategy::with(msm_accumulator)` (poly/kzg/strategy.rs:75-78): start from an existing `DualMSM`, given as the terms of
+    /// its two channels.  `finalize_identify` then runs h2v_verify_batch_seeded_identify.
+    pub fn with_seed(mut self, left: &[(Fr, G1Affine)], right: &[(Fr, G1Affine)]) -> Self {
+        self.seed = Some([flat_terms(left), flat_terms(right)]);
+        self
     }
 
     /// One `verify_proof(&params, &vk, strategy, &[instances], &mut Blake2bRead::init(proof))` call.
@@ -76,19 +100,82 @@ impl<'p> GpuBatchVerifier<'p> {
     /// (`ConstraintSystemFailure` for the proofs whose own pairing fails).  When the batch passes this costs what `finalize` costs;
     /// otherwise the failing ranges of proofs are re-checked on the GPU until single proofs remain (h2v_verify_batch_identify).
     pub fn finalize_identify(self) -> Result<(bool, Vec<Result<(), Error>>), Error> {
+        self.finalize_identify_seeded().map(|(ok, verdicts, _)| (ok, verdicts))
+    }
+
+    /// `finalize_identify`, plus the verdict of the seed alone (`true` without a seed and for an empty one).  The seed's terms belong to
+    /// no proof and enter no proof's verdict: a failing batch whose proofs are all `Ok(())` and whose seed fails resumed a bad
+    /// accumulator (h2v_verify_batch_seeded_identify).
+    pub fn finalize_identify_seeded(self) -> Result<(bool, Vec<Result<(), Error>>, bool), Error> {
         let n = self.proofs.len();
         let ptrs: Vec<*const u8> = self.proofs.iter().map(|p| p.as_ptr()).collect();
         let lens: Vec<usize> = self.proofs.iter().map(|p| p.len()).collect();
         let iptrs: Vec<*const u8> = self.instances.iter().map(|i| i.as_ptr()).collect();
-        let (mut status, mut ok, mut checks) = (vec![0i32; n.max(1)], 0i32, 0usize);
-        let rc = unsafe { h2v_verify_batch_identify(self.ctx, n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(), self.col_lens.len(), self.col_lens.as_ptr(),
-                                                    core::ptr::null(), status.as_mut_ptr(), &mut ok, core::ptr::null_mut(), core::ptr::null_mut(), &mut checks) };
+        let (mut status, mut ok, mut seed_ok, mut checks) = (vec![0i32; n.max(1)], 0i32, 1i32, 0usize);
+        let rc = match &self.seed {
+            Some([(ls, lb), (rs, rb)]) => unsafe {
+                h2v_verify_batch_seeded_identify(self.ctx, n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(), self.col_lens.len(), self.col_lens.as_ptr(),
+                                                 core::ptr::null(), ls.as_ptr(), lb.as_ptr(), ls.len() / 32, rs.as_ptr(), rb.as_ptr(), rs.len() / 32,
+                                                 status.as_mut_ptr(), &mut ok, &mut seed_ok, core::ptr::null_mut(), core::ptr::null_mut(), &mut checks) },
+            None => unsafe {
+                h2v_verify_batch_identify(self.ctx, n, ptrs.as_ptr(), lens.as_ptr(), iptrs.as_ptr(), self.col_lens.len(), self.col_lens.as_ptr(),
+                                          core::ptr::null(), status.as_mut_ptr(), &mut ok, core::ptr::null_mut(), core::ptr::null_mut(), &mut checks) },
+        };
         if rc != 0 { return Err(map_err(rc)); }
         let verdicts = status[..n].iter().map(|&s| if s == 0 { Ok(()) } else { Err(map_err(s)) }).collect();
-        Ok((ok == 1, verdicts))
+        Ok((ok == 1, verdicts, seed_ok == 1))
     }
 }
 impl<'p> Drop for GpuBatchVerifier<'p> { fn drop(&mut self) { unsafe { h2v_ctx_destroy(self.ctx) } } }
+
+/// The staged interface on one context (h2v_batch_*): the proofs stay resident on the GPU between `upload`, `launch`, `finish` and
+/// `identify`.  `groups` independent accumulator batches travel in one launch (h2v_batch_set_groups).  The context outlives the batch.
+pub struct GpuStagedBatch { b: *mut h2v_batch, n: usize, groups: usize }
+
+impl GpuStagedBatch {
+    pub fn new(ctx: *mut h2v_ctx, max_proofs: usize, max_instance_values: usize, groups: usize) -> Result<Self, Error> {
+        let mut b = core::ptr::null_mut();
+        let rc = unsafe { h2v_batch_create(ctx, max_proofs, max_instance_values, &mut b) };
+        if rc != 0 { return Err(map_err(rc)); }
+        let me = Self { b, n: 0, groups };
+        if groups != 1 { let rc = unsafe { h2v_batch_set_groups(me.b, groups) }; if rc != 0 { return Err(map_err(rc)); } }
+        Ok(me)
+    }
+    /// `n` proofs of `proof_len` bytes each, their instance values (32 bytes each) and the draws from the shard's first proof to the end
+    /// of the whole batch (empty: OS draws, unsharded only).
+    pub fn upload(&mut self, n: usize, proofs_flat: &[u8], proof_len: usize, instances_flat: &[u8], col_lens: &[usize], rand_tail: &[u8]) -> Result<(), Error> {
+        if proofs_flat.len() != n * proof_len || instances_flat.len() != n * col_lens.iter().sum::<usize>() * 32 || rand_tail.len() % 32 != 0 { return Err(Error::InvalidInstances); }
+        let tail = if rand_tail.is_empty() { core::ptr::null() } else { rand_tail.as_ptr() };
+        let rc = unsafe { h2v_batch_upload(self.b, n, proofs_flat.as_ptr(), proof_len, instances_flat.as_ptr(), col_lens.len(), col_lens.as_ptr(), tail, rand_tail.len() / 32) };
+        if rc != 0 { return Err(map_err(rc)); }
+        self.n = n;
+        Ok(())
+    }
+    pub fn launch(&mut self, with_pairing: bool) -> Result<(), Error> {
+        let rc = unsafe { h2v_batch_launch(self.b, with_pairing as i32) };
+        if rc != 0 { Err(map_err(rc)) } else { Ok(()) }
+    }
+    /// -> the verdict of every group and the status of every proof
+    pub fn finish(&mut self) -> Result<(Vec<bool>, Vec<i32>), Error> {
+        let (mut status, mut ok) = (vec![0i32; self.n.max(1)], vec![0i32; self.groups]);
+        let rc = unsafe { h2v_batch_finish_groups(self.b, status.as_mut_ptr(), ok.as_mut_ptr(), core::ptr::null_mut(), core::ptr::null_mut(), self.groups) };
+        if rc != 0 { return Err(map_err(rc)); }
+        status.truncate(self.n);
+        Ok((ok.iter().map(|&v| v == 1).collect(), status))
+    }
+    /// Which proofs of the finished launch fail the pairing (h2v_batch_identify): every proof's verdict as `verify_proof` under
+    /// `SingleStrategy` returns it, the pairing of every group's own accumulators, and the number of range checks the search ran.
+    /// `own_records`: the device address of the records h2v_batch_export_accumulators wrote for this launch — needed after a fold
+    /// (h2v_batch_fold_check_enqueue), which overwrites the batch's own accumulators; null otherwise.
+    pub fn identify(&mut self, own_records: *const core::ffi::c_void) -> Result<(Vec<Result<(), Error>>, Vec<bool>, usize), Error> {
+        let (mut status, mut own, mut checks) = (vec![0i32; self.n.max(1)], vec![0i32; self.groups], 0usize);
+        let rc = unsafe { h2v_batch_identify(self.b, own_records, status.as_mut_ptr(), own.as_mut_ptr(), &mut checks) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok((status[..self.n].iter().map(|&s| if s == 0 { Ok(()) } else { Err(map_err(s)) }).collect(), own.iter().map(|&v| v == 1).collect(), checks))
+    }
+    pub fn handle(&self) -> *mut h2v_batch { self.b }
+}
+impl Drop for GpuStagedBatch { fn drop(&mut self) { unsafe { h2v_batch_destroy(self.b) } } }
 
 /// Whole-batch seam over several circuits: N x `verify_proof` with a different `vk` per call on ONE `AccumulatorStrategy`, then
 /// `finalize` — one pairing for all of them (h2v_verify_batch_keys).  Every key shares the params.
@@ -204,17 +291,7 @@ impl GpuResidentAccumulator {
 
     /// `AccumulatorStrategy::with(msm_accumulator)` / `DualMSM::add_msm`: adds the evaluated channels of `msm`, unscaled.
     pub fn add_msm(&mut self, left: &[(Fr, G1Affine)], right: &[(Fr, G1Affine)]) -> Result<(), Error> {
-        fn flat(terms: &[(Fr, G1Affine)]) -> (Vec<u8>, Vec<u8>) {
-            let (mut s, mut b) = (Vec::new(), Vec::new());
-            for (k, p) in terms {
-                s.extend_from_slice(k.to_repr().as_ref());
-                let c = p.coordinates();
-                if bool::from(c.is_some()) { let c = c.unwrap(); b.extend_from_slice(c.x().to_repr().as_ref()); b.extend_from_slice(c.y().to_repr().as_ref()); }
-                else { b.extend_from_slice(&[0u8; 64]); }
-            }
-            (s, b)
-        }
-        let ((ls, lb), (rs, rb)) = (flat(left), flat(right));
+        let ((ls, lb), (rs, rb)) = (flat_terms(left), flat_terms(right));
         let rc = unsafe { h2v_accumulator_add_msm(self.acc, ls.as_ptr(), lb.as_ptr(), left.len(), rs.as_ptr(), rb.as_ptr(), right.len()) };
         if rc != 0 { return Err(map_err(rc)); }
         Ok(())

@@ -8,8 +8,12 @@ the sign of h2 flipped: it decodes and passes the transcript, only the pairing r
 measures identification over several VerifyingKeys instead (h2v_verify_batch_keys_identify): V distinct k = 8 vector-mul VKs over one
 setup, 1024 proofs interleaved (proof i belongs to key i mod V), 0 / 1 / 4 / 32 / all bad, next to h2v_verify_batch_keys and to
 h2v_verify_each summed over the keys; the pass path with two instance shapes per key; and one pooled round of re-checks over V staged
-batches (h2v_batches_recheck) against the same ranges re-checked batch by batch."""
-import argparse, json, os, random, sys, time
+batches (h2v_batches_recheck) against the same ranges re-checked batch by batch.
+   python tools/identify_probe.py --parent PATH [--k 14] [--reps 7] [--out FILE]
+compares this build with another build of libh2v_amd.so (PATH: one made from the parent commit, loaded beside the in-tree one): one
+round of re-checks of 1 range of 1024, 8 of 128, 32 of 32 and 32 single proofs, and the 0-bad pass path of h2v_verify_batch_identify,
+the two builds alternating inside every repetition; medians, and each build's min - max spread."""
+import argparse, ctypes, json, os, random, sys, time
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import bench
 bench.hw_queue_env()
@@ -21,6 +25,7 @@ ap.add_argument("--k", type=int, default=14)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--out", default=None)
 ap.add_argument("--keys", default=None, help="comma-separated key counts: identification over several VerifyingKeys")
+ap.add_argument("--parent", default=None, help="another build of libh2v_amd.so to compare the re-check rounds with")
 args = ap.parse_args()
 
 
@@ -135,6 +140,78 @@ def spoiled(bad):
         b = bytearray(Q[i]); b[-1] ^= 0x40; Q[i] = bytes(b)
     return Q
 
+
+
+
+def against_parent(path):
+    from halo2_verifier_amd import _lib
+    lib = ctypes.CDLL(os.path.abspath(path))   # (a parent build lacks the newer symbols)
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    mine = _lib.load_library()
+    _lib._LIB = lib
+    try:
+        pctx = h2v.Context(h2v.ParamsKZG(d["params"], h2v.SerdeFormat.RawBytes), h2v.VerifyingKey(d["vk"], h2v.SerdeFormat.RawBytes))
+    finally:
+        _lib._LIB = mine
+    builds = {"this": ctx, "parent": pctx}
+    staged = {}
+    for v, c in builds.items():
+        b = h2v.Batch(c, n, N)
+        b.upload(d["proofs"], 1024, d["inst"], [N], b"".join(x.to_bytes(32, "little") for x in rand))
+        b.launch(); b.finish()
+        staged[v] = b
+    res = {"n": n, "k": args.k, "reps": args.reps, "parent": path, "rows": {}}
+
+    def alternate(name, fns):
+        """fns: build -> a call; warm-up, then args.reps repetitions with the builds alternating inside each"""
+        want = None
+        for v, fn in fns.items():
+            got = fn()
+            assert want is None or got == want, name   # both builds give the same answer
+            want = got
+        ts = {v: [] for v in fns}
+        for _ in range(args.reps):
+            for v, fn in fns.items():
+                t0 = time.perf_counter(); fn(); ts[v].append((time.perf_counter() - t0) * 1e3)
+        row = {}
+        for v, t in ts.items():
+            row[v] = {"median_ms": round(sorted(t)[len(t) // 2], 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3)}
+        spread = row["parent"]["max_ms"] - row["parent"]["min_ms"]
+        row["parent_spread_ms"] = round(spread, 3)
+        row["this_minus_parent_ms"] = round(row["this"]["median_ms"] - row["parent"]["median_ms"], 3)
+        res["rows"][name] = row
+        print(f"{name:28s} this {row['this']['median_ms']:7.3f} ms [{row['this']['min_ms']:.3f} .. {row['this']['max_ms']:.3f}]   "
+              f"parent {row['parent']['median_ms']:7.3f} ms [{row['parent']['min_ms']:.3f} .. {row['parent']['max_ms']:.3f}]   "
+              f"difference {row['this_minus_parent_ms']:+.3f} ms, parent's spread {spread:.3f} ms", flush=True)
+
+    for width, size in ((1, 1024), (8, 128), (32, 32), (32, 1)):
+        ranges = [(i * (n // width), size) for i in range(width)] if size > 1 else [(i, 1) for i in range(width)]
+        alternate(f"recheck {width} x {size}", {v: (lambda b=b: b.recheck(ranges)[0]) for v, b in staged.items()})
+    alternate("verify_batch_identify, 0 bad", {v: (lambda c=c: c.verify_batch_identify(P, I, rand)) for v, c in builds.items()})
+    rounds = [k for k in res["rows"] if k.startswith("recheck")]
+    res["rounds_faster_by_more_than_parent_spread"] = all(-res["rows"][k]["this_minus_parent_ms"] > res["rows"][k]["parent_spread_ms"] for k in rounds)
+    pass_row = res["rows"]["verify_batch_identify, 0 bad"]
+    res["pass_path_within_parent_spread"] = pass_row["this_minus_parent_ms"] <= pass_row["parent_spread_ms"]
+    print("every round faster than the parent by more than the parent's spread:", res["rounds_faster_by_more_than_parent_spread"])
+    print("pass path not above the parent by more than the parent's spread:", res["pass_path_within_parent_spread"], flush=True)
+    for b in staged.values():
+        b.close()
+    pctx.close()
+    return res
+
+
+if args.parent:
+    res = against_parent(args.parent)
+    ctx.close()
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+    sys.exit(0)
 
 res = {"n": n, "k": args.k, "reps": args.reps}
 t, r = timed(lambda: ctx.verify_batch(P, I, rand))
