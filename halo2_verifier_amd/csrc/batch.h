@@ -63,6 +63,13 @@ struct InstEvalArgs {
 };
 int instance_eval_enqueue(hipStream_t s, const InstEvalArgs& a);
 
+// 64-bit words a proof's absorbed stream of `stream_len` bytes takes in the `words` buffer: whole hash blocks (136-byte Keccak /
+// 128-byte Blake2b), plus room for a final partial one.  The rule of batch_sizes, and of whoever fills a StageArgs by hand.
+inline uint32_t stream_words_for(size_t stream_len, int transcript) {
+    const uint32_t words = (uint32_t)((stream_len + 7) / 8);
+    const uint32_t blockw = transcript == H2V_TRANSCRIPT_KECCAK256 ? 17 : 16;
+    return (words + blockw) / blockw * blockw;
+}
 struct StageArgs {
     uint32_t n;
     const Plan* plan; const PlanDevice* pd;

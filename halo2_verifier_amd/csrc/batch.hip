@@ -19,9 +19,7 @@ struct BatchSizes {
 };
 BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G) {
     BatchSizes z;
-    const uint32_t words = (uint32_t)((pl.stream.size() + 7) / 8);
-    const uint32_t blockw = pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256 ? 17 : 16;   // 136-byte Keccak / 128-byte Blake2b blocks
-    z.stream_words = (words + blockw) / blockw * blockw;  // whole blocks, plus room for a final partial one
+    z.stream_words = stream_words_for(pl.stream.size(), pl.opts.transcript);
     z.proofs = N * pl.proof_len;
     z.inst = N * (size_t)pl.n_instance_values * 32;
     z.pts = N * pl.n_points + pl.n_shared;

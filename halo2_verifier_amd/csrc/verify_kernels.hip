@@ -714,17 +714,17 @@ int transcript_stage_enqueue(hipStream_t s, const StageArgs& g) {
     const Plan& pl = *g.plan;
     uint32_t stream_len = (uint32_t)pl.stream.size();
     uint32_t n_words = g.stream_words;
+    const bool keccak = pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256;
+    const uint32_t nsq = (uint32_t)pl.squeeze_at.size();
+    const size_t lds = ((size_t)16 * TR4_MSG_STRIDE + (size_t)16 * nsq * 8) * 8;   // k_transcript's message blocks and digests
+    // (refused before anything is launched: a stage that returns an error has not touched the words either)
+    if (!keccak && lds > 60 * 1024) { set_last_error("transcript: too many challenges for one workgroup's LDS"); return H2V_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(k_stream_build, dim3((n + STREAM_PROOFS_PER_BLOCK - 1) / STREAM_PROOFS_PER_BLOCK), dim3(256), 0, s, g.pd->stream.p, stream_len, g.proofs, pl.proof_len, g.ycanon, pl.n_points, g.inst,
                        pl.n_instance_values, n, n_words, g.words);
-    if (pl.opts.transcript == H2V_TRANSCRIPT_KECCAK256)
-        hipLaunchKernelGGL(k_transcript_keccak, dim3((n + 63) / 64), dim3(64), 0, s, g.words, n_words, g.pd->squeeze_at.p, (uint32_t)pl.squeeze_at.size(), n, g.chal);
+    if (keccak)
+        hipLaunchKernelGGL(k_transcript_keccak, dim3((n + 63) / 64), dim3(64), 0, s, g.words, n_words, g.pd->squeeze_at.p, nsq, n, g.chal);
     else
-    {
-        const uint32_t nsq = (uint32_t)pl.squeeze_at.size();
-        const size_t lds = ((size_t)16 * TR4_MSG_STRIDE + (size_t)16 * nsq * 8) * 8;
-        if (lds > 60 * 1024) { set_last_error("transcript: too many challenges for one workgroup's LDS"); return H2V_ERR_UNSUPPORTED; }
         hipLaunchKernelGGL(k_transcript, dim3((n + 15) / 16), dim3(64), lds, s, g.words, n_words, g.pd->squeeze_at.p, nsq, n, g.chal);
-    }
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,372 @@
+// The per-proof kernels (halo2_verifier_amd/csrc/verify_kernels.hip) stage by stage, on inputs programmed by
+// tests/test_gpu_verify_units.py and compared there with tests/verify_reference.py.  Built with the library's flags by
+// halo2_verifier_amd/csrc/Makefile (build/verify_units).
+//
+//   verify_units decompress IN OUT   decompress_begin / _range (in the pieces the input gives) / _finish: k_decompress, k_check_scalars
+//   verify_units stream     IN OUT   transcript_stage_enqueue: k_stream_build, then k_transcript or k_transcript_keccak
+//   verify_units insteval   IN OUT   instance_eval_enqueue: k_instance_eval
+//   verify_units frvm       IN OUT   frvm_enqueue: k_frvm / k_frvm2 on a programmed VmInstr program
+//   verify_units fold       IN OUT   fold_shared_enqueue (k_fold_shared) and fold_shared_ranges_enqueue (k_fold_ranges)
+// IN is little-endian: a word n_jobs, then per job the words and byte blocks its reader below takes, in that order.  OUT is the jobs'
+// results one after another (the layouts are at the writers).  Field elements cross the file boundary as 32 canonical little-endian
+// bytes.  The Plan and PlanDevice a launcher wants are filled by hand from the input: no compile_plan, no PlanDevice::upload.
+// Every HIP call is checked: the first error ends the program with a non-zero status.  Every count, offset and index that reaches a
+// kernel is checked on the host against the buffer sizes first ("bad input", status 2): no input can make a kernel leave its buffers.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+#include "../../halo2_verifier_amd/csrc/verify_kernels.hip"
+
+namespace h2v {
+static std::string g_err;
+void set_last_error(const std::string& s) { g_err = s; }
+}
+using namespace h2v;
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
+#define REQUIRE(c, msg) do { if (!(c)) { fprintf(stderr, "bad input: %s (%s)\n", msg, #c); exit(2); } } while (0)
+#define RC(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s: %d %s\n", #x, rc_, g_err.c_str()); exit(4); } } while (0)
+
+#define FILL 0x11   // what every output buffer holds before a launch: limbs 0x11111111 are normalised, so an unwritten Fr still converts
+
+// a cursor over the input bytes
+struct In {
+    std::vector<uint8_t> b;
+    size_t at = 0;
+    uint32_t word() { REQUIRE(b.size() - at >= 4, "input too short"); uint32_t w; memcpy(&w, b.data() + at, 4); at += 4; return w; }
+    std::vector<uint32_t> words(size_t n) { REQUIRE(n <= (b.size() - at) / 4, "input too short"); std::vector<uint32_t> v(n); if (n) memcpy(v.data(), b.data() + at, 4 * n); at += 4 * n; return v; }
+    const uint8_t* bytes(size_t n) { REQUIRE(n <= b.size() - at, "input too short"); const uint8_t* p = b.data() + at; at += n; return p; }
+    Fr fr() { Fr v; REQUIRE(Fr::from_bytes(bytes(32), v), "field element not canonical"); return v; }
+    std::vector<Fr> frs(size_t n) { REQUIRE(n <= (b.size() - at) / 32, "input too short"); std::vector<Fr> v(n); for (size_t i = 0; i < n; ++i) v[i] = fr(); return v; }
+};
+struct Out {
+    std::vector<uint8_t> b;
+    void word(uint32_t w) { const size_t o = b.size(); b.resize(o + 4); memcpy(&b[o], &w, 4); }
+    void raw(const void* p, size_t n) { const size_t o = b.size(); b.resize(o + n); if (n) memcpy(&b[o], p, n); }
+    template <class F> void field(const F& v) { const size_t o = b.size(); b.resize(o + 32); v.to_bytes(&b[o]); }
+};
+// a device buffer of n elements, filled with FILL
+template <class T> static void fresh(DevBuf<T>& d, size_t n) {
+    RC(d.alloc(n));
+    CK(hipMemset((void*)d.p, FILL, (n ? n : 1) * sizeof(T)));
+}
+template <class T> static void upload(DevBuf<T>& d, const T* h, size_t n) {
+    RC(d.alloc(n));
+    if (n) CK(hipMemcpy((void*)d.p, (const void*)h, n * sizeof(T), hipMemcpyHostToDevice));
+}
+template <class T> static std::vector<T> download(const T* d, size_t n) {
+    std::vector<T> h(n);
+    if (n) CK(hipMemcpy((void*)h.data(), (const void*)d, n * sizeof(T), hipMemcpyDeviceToHost));
+    return h;
+}
+// a source buffer of the stream builder: 32 bytes of slack on both sides, filled with 0xA5 (the unaligned 8-byte loads of the fast
+// path stay inside the allocation for any table; a byte wrongly taken from the slack shows in the result)
+struct Slack {
+    DevBuf<uint8_t> buf;
+    const uint8_t* p = nullptr;
+    void set(const uint8_t* h, size_t n) {
+        RC(buf.alloc(n + 64));
+        CK(hipMemset(buf.p, 0xA5, n + 64));
+        if (n) CK(hipMemcpy(buf.p + 32, h, n, hipMemcpyHostToDevice));
+        p = buf.p + 32;
+    }
+};
+static void out_fields(Out& out, const Fr* d, size_t n) { for (const Fr& v : download(d, n)) out.field(v); }
+static void out_words(Out& out, const void* d, size_t n_words) { const std::vector<uint32_t> h = download((const uint32_t*)d, n_words); out.raw(h.data(), 4 * n_words); }
+
+#define MAX_PROOFS 4096u
+#define MAX_ITEMS 1024u
+#define MAX_LEN (1u << 20)
+
+// ---- decompress
+// job: n, np, n_main, ns, ninst, proof_len, n_pieces, n_pieces + 1 piece bounds (0 = b[0] < .. < b[n_pieces] = n), point_offsets[np], scalar_offsets[ns],
+//      proofs [n][proof_len], inst [n][ninst][32]
+// out: per (proof, point): x, y of pts, x, y of phi (32 bytes each), a word (1 = pts holds the identity), the 32 ycanon bytes; then n raw status words
+static void run_decompress(In& in, Out& out) {
+    const uint32_t n = in.word(), np = in.word(), n_main = in.word(), ns = in.word(), ninst = in.word(), proof_len = in.word(), n_pieces = in.word();
+    REQUIRE(n >= 1 && n <= MAX_PROOFS && np >= 1 && np <= MAX_ITEMS && ns <= MAX_ITEMS && ninst <= MAX_ITEMS, "counts");
+    REQUIRE(n_main <= np && proof_len >= 32 && proof_len <= MAX_LEN && proof_len % 32 == 0, "proof length");
+    REQUIRE(n_pieces >= 1 && n_pieces <= n, "pieces");
+    const std::vector<uint32_t> cut = in.words(n_pieces + 1);
+    REQUIRE(cut[0] == 0 && cut[n_pieces] == n, "pieces must cover [0, n)");
+    for (uint32_t i = 0; i < n_pieces; ++i) REQUIRE(cut[i] < cut[i + 1], "pieces must ascend");
+    PlanDevice pd;
+    Plan& pl = pd.host;
+    pl.n_points = np; pl.n_main_points = n_main; pl.n_scalars = ns; pl.n_instance_values = ninst; pl.proof_len = proof_len;
+    pl.point_offsets = in.words(np); pl.scalar_offsets = in.words(ns);
+    for (uint32_t o : pl.point_offsets) REQUIRE(o % 32 == 0 && o <= proof_len - 32, "point offset");      // (two 16-byte loads per point)
+    for (uint32_t o : pl.scalar_offsets) REQUIRE(o % 32 == 0 && o <= proof_len - 32, "scalar offset");
+    upload(pd.point_offsets, pl.point_offsets.data(), np);
+    upload(pd.scalar_offsets, pl.scalar_offsets.data(), ns);
+    DevBuf<uint8_t> proofs, inst, ycanon; DevBuf<G1A> pts, phi; DevBuf<int> status;
+    upload(proofs, in.bytes((size_t)n * proof_len), (size_t)n * proof_len);
+    upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
+    const size_t tp = (size_t)n * np;
+    fresh(pts, tp); fresh(phi, tp); fresh(ycanon, tp * 32); fresh(status, n);   // (the status words too: the begin step resets them)
+    StageArgs g{n, &pl, &pd, proofs.p, inst.p, pts.p, phi.p, ycanon.p, status.p, nullptr, 0, nullptr};
+    RC(decompress_begin_enqueue(0, g));
+    for (uint32_t i = 0; i < n_pieces; ++i) RC(decompress_range_enqueue(0, g, cut[i], cut[i + 1]));
+    RC(decompress_finish_enqueue(0, g));
+    CK(hipDeviceSynchronize());
+    const std::vector<G1A> hp = download(pts.p, tp), hf = download(phi.p, tp);
+    const std::vector<uint8_t> hy = download(ycanon.p, tp * 32);
+    for (size_t i = 0; i < tp; ++i) {
+        out.field(hp[i].x); out.field(hp[i].y); out.field(hf[i].x); out.field(hf[i].y);
+        out.word(hp[i].is_identity() ? 1u : 0u);
+        out.raw(&hy[32 * i], 32);
+    }
+    out_words(out, status.p, n);
+}
+
+// ---- stream
+// job: n, transcript (0 Blake2b, 1 Keccak-256), proof_len, np, ninst, stream_len, n_squeeze, stream_len x (kind | value << 8, offset), squeeze_at[n_squeeze],
+//      proofs [n][proof_len], ycanon [n][np][32], inst [n][ninst][32]
+// out: the launcher's return code, stream_words, the words buffer [n][stream_words] (8 bytes each), the challenges [n_squeeze][n]
+//      (both as the launcher left them: FILL where nothing was written)
+static void run_stream(In& in, Out& out) {
+    const uint32_t n = in.word(), kind = in.word(), proof_len = in.word(), np = in.word(), ninst = in.word(), stream_len = in.word(), nsq = in.word();
+    REQUIRE(n >= 1 && n <= MAX_PROOFS && kind <= 1 && proof_len <= MAX_LEN && np <= MAX_ITEMS && ninst <= MAX_ITEMS, "counts");
+    REQUIRE(stream_len >= 1 && stream_len <= (1u << 16) && nsq >= 1 && nsq <= 4096, "stream length");
+    PlanDevice pd;
+    Plan& pl = pd.host;
+    pl.n_points = np; pl.n_instance_values = ninst; pl.proof_len = proof_len;
+    pl.opts.transcript = kind ? H2V_TRANSCRIPT_KECCAK256 : 0;
+    pl.stream.resize(stream_len);
+    for (uint32_t i = 0; i < stream_len; ++i) {
+        const uint32_t kv = in.word(), off = in.word(), k = kv & 0xffu;
+        REQUIRE(kv <= 0xffffu && k <= TranscriptSrc::INSTANCE, "stream entry kind");
+        const size_t per = k == TranscriptSrc::CONST ? 1 : (k == TranscriptSrc::YCOORD ? (size_t)np * 32 : (k == TranscriptSrc::INSTANCE ? (size_t)ninst * 32 : (size_t)proof_len));
+        REQUIRE(off < per, "stream entry offset");   // a byte of the proof's own record
+        pl.stream[i].kind = (uint8_t)k; pl.stream[i].value = (uint8_t)(kv >> 8); pl.stream[i].offset = off;
+    }
+    pl.squeeze_at = in.words(nsq);
+    for (uint32_t q = 0; q < nsq; ++q) REQUIRE(pl.squeeze_at[q] >= 1 && pl.squeeze_at[q] <= stream_len && (q == 0 || pl.squeeze_at[q] >= pl.squeeze_at[q - 1]), "squeeze position");
+    upload(pd.stream, pl.stream.data(), stream_len);
+    upload(pd.squeeze_at, pl.squeeze_at.data(), nsq);
+    Slack proofs, ycanon, inst;
+    proofs.set(in.bytes((size_t)n * proof_len), (size_t)n * proof_len);
+    ycanon.set(in.bytes((size_t)n * np * 32), (size_t)n * np * 32);
+    inst.set(in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
+    const uint32_t sw = stream_words_for(stream_len, pl.opts.transcript);
+    REQUIRE((size_t)sw * 8 > stream_len, "stream words");   // every squeeze's last block, and a prefetched block behind it, lie inside
+    DevBuf<unsigned long long> words; DevBuf<Fr> chal;
+    fresh(words, (size_t)n * sw); fresh(chal, (size_t)nsq * n);
+    StageArgs g{n, &pl, &pd, proofs.p, inst.p, nullptr, nullptr, const_cast<uint8_t*>(ycanon.p), nullptr, words.p, sw, chal.p};
+    const int rc = transcript_stage_enqueue(0, g);
+    CK(hipDeviceSynchronize());
+    out.word((uint32_t)rc); out.word(sw);
+    out_words(out, words.p, (size_t)n * sw * 2);
+    out_fields(out, chal.p, (size_t)nsq * n);
+}
+
+// ---- insteval
+// job: n, k, ninst, base, len, rot (two's complement), x_chal, n_chal, omega (the 2^k-th root of unity), inst [n][ninst][32], chal [n_chal][n]
+// out: out[p] (n field elements), n raw status words
+static void run_insteval(In& in, Out& out) {
+    const uint32_t n = in.word(), k = in.word(), ninst = in.word(), base = in.word(), len = in.word();
+    const int32_t rot = (int32_t)in.word();
+    const uint32_t x_chal = in.word(), n_chal = in.word();
+    REQUIRE(n >= 1 && n <= 64 && k >= 1 && k <= 28 && ninst <= (1u << 16) && n_chal <= 64, "counts");
+    REQUIRE(base <= ninst && len <= ninst - base && x_chal < n_chal && rot >= -1024 && rot <= 1024, "column");
+    const Fr omega = in.fr();
+    DevBuf<uint8_t> inst; DevBuf<Fr> chal, res; DevBuf<int> status;
+    upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
+    const std::vector<Fr> hc = in.frs((size_t)n_chal * n);
+    upload(chal, hc.data(), hc.size());
+    fresh(res, n);
+    RC(status.alloc(n));
+    CK(hipMemset(status.p, 0, sizeof(int) * n));
+    Fr step = omega;
+    for (int i = 0; i < 8; ++i) step = step.sqr();   // omega^256: a thread's stride through the column
+    const Fr w_start = rot >= 0 ? omega.inv().pow_u32((uint32_t)rot) : omega.pow_u32((uint32_t)-rot);   // omega^(-rot)
+    InstEvalArgs a{inst.p, ninst, chal.p, x_chal, n, k, base, len, w_start, omega, step, step.inv(), Fr::from_u32(1u << k).inv(), res.p, status.p};
+    RC(instance_eval_enqueue(0, a));
+    CK(hipDeviceSynchronize());
+    out_fields(out, res.p, n);
+    out_words(out, status.p, n);
+}
+
+// ---- frvm
+struct VmBounds { uint32_t n_slots, n_consts, ns, ninst, n_chal, n_insteval, np, n_guard, n_shared; };
+// every index of a stream lies inside its buffer; returns the stream's number of barriers
+static uint32_t check_code(const std::vector<VmInstr>& code, const VmBounds& z) {
+    uint32_t barriers = 0;
+    auto slot = [&](uint32_t s) { REQUIRE(s < z.n_slots, "slot"); };
+    auto opnd = [&](uint32_t x) { if (x & VM_CONST_OPERAND) REQUIRE((x & ~VM_CONST_OPERAND) < z.n_consts, "constant operand"); else slot(x); };
+    for (const VmInstr& in : code) {
+        switch (in.op) {
+            case OP_BARRIER: ++barriers; break;
+            case OP_CONST: slot(in.d); REQUIRE(in.a < z.n_consts, "constant"); break;
+            case OP_MUL: case OP_ADD: case OP_SUB: slot(in.d); opnd(in.a); opnd(in.b); break;
+            case OP_NEG: case OP_INV: case OP_POW: slot(in.d); slot(in.a); break;
+            case OP_SQRN: slot(in.d); slot(in.a); REQUIRE(in.b <= 64, "squarings"); break;
+            case OP_LOAD_SCALAR: slot(in.d); REQUIRE(in.a < z.ns, "scalar"); break;
+            case OP_LOAD_INST: slot(in.d); REQUIRE(in.a < z.ninst, "instance value"); break;
+            case OP_LOAD_CHAL: slot(in.d); REQUIRE(in.a < z.n_chal, "challenge"); break;
+            case OP_LOAD_INSTEVAL: slot(in.d); REQUIRE(in.a < z.n_insteval, "insteval"); break;
+            case OP_LOAD_MULT: slot(in.d); break;
+            case OP_STORE_MSM: case OP_STORE_LEFT: slot(in.a); REQUIRE(in.b < z.np, "point slot"); break;
+            case OP_STORE_GUARD: slot(in.a); REQUIRE(in.b < z.n_guard, "guard term"); break;
+            case OP_STORE_SHARED: slot(in.a); REQUIRE(in.b < z.n_shared, "shared row"); break;
+            default: REQUIRE(false, "opcode");
+        }
+    }
+    return barriers;
+}
+static std::vector<VmInstr> read_code(In& in, uint32_t n_code) {
+    REQUIRE(n_code <= 4096, "program length");
+    std::vector<VmInstr> c(n_code);
+    for (VmInstr& i : c) { i.op = in.word(); i.d = in.word(); i.a = in.word(); i.b = in.word(); }
+    return c;
+}
+// job: n, n_code, n_slots, n_consts, ns, ninst, n_chal, n_insteval, np, n_guard, n_shared, proof_len, force_streams, force_lds_kb,
+//      then for K = 2, 3, 4: n_slots_k, n_code_k[0..4) (all zero: no K-stream form);
+//      code, the K forms' streams in that order, consts, scalar_offsets[ns], proofs [n][proof_len], inst [n][ninst][32], chal [n_chal][n],
+//      insteval [n_insteval][n], mult [n], n status words to start from
+// out: msm_scal [n][np][8], left_scal [n][np][8], guard_scal [n][n_guard][8] (raw words), shared [n_shared][n] (canonical), n raw status words
+static void run_frvm(In& in, Out& out) {
+    const uint32_t n = in.word(), n_code = in.word(), n_slots = in.word(), n_consts = in.word(), ns = in.word(), ninst = in.word(), n_chal = in.word(), n_insteval = in.word(),
+                   np = in.word(), n_guard = in.word(), n_shared = in.word(), proof_len = in.word();
+    const int force_streams = (int)in.word(), force_lds_kb = (int)in.word();
+    REQUIRE(n >= 1 && n <= MAX_PROOFS && n_code >= 1 && n_slots >= 1 && n_slots <= 1024 && n_consts <= MAX_ITEMS && ns <= MAX_ITEMS && ninst <= MAX_ITEMS, "counts");
+    REQUIRE(n_chal <= MAX_ITEMS && n_insteval <= MAX_ITEMS && np <= MAX_ITEMS && n_guard <= MAX_ITEMS && n_shared <= MAX_ITEMS, "counts");
+    REQUIRE(proof_len <= MAX_LEN && proof_len % 32 == 0 && force_streams >= 0 && force_streams <= FRVM_MAX_STREAMS && force_lds_kb >= 0 && force_lds_kb <= 156, "sizes");
+    uint32_t n_slots_k[3], n_code_k[3][FRVM_MAX_STREAMS], max_slots = n_slots;
+    for (int k = 0; k < 3; ++k) {
+        n_slots_k[k] = in.word();
+        for (int w = 0; w < FRVM_MAX_STREAMS; ++w) n_code_k[k][w] = in.word();
+        REQUIRE(n_slots_k[k] <= 1024, "slots of a K-stream form");
+        if (n_slots_k[k] > max_slots) max_slots = n_slots_k[k];
+    }
+    VmBounds z{n_slots, n_consts, ns, ninst, n_chal, n_insteval, np, n_guard, n_shared};
+    const std::vector<VmInstr> code = read_code(in, n_code);
+    check_code(code, z);
+    std::vector<VmInstr> code_k[3][FRVM_MAX_STREAMS];
+    for (int k = 0; k < 3; ++k) {
+        const bool have = n_code_k[k][0] != 0;
+        uint32_t barriers = 0;
+        for (int w = 0; w < FRVM_MAX_STREAMS; ++w) {
+            // a K-stream form has K non-empty streams that meet at the same number of barriers (a workgroup barrier one wave skips hangs the others)
+            REQUIRE(have && w < k + 2 ? n_code_k[k][w] >= 1 : n_code_k[k][w] == 0, "streams of a K-stream form");
+            code_k[k][w] = read_code(in, n_code_k[k][w]);
+            VmBounds zk = z; zk.n_slots = n_slots_k[k];
+            const uint32_t b = check_code(code_k[k][w], zk);
+            if (w == 0) barriers = b;
+            else if (n_code_k[k][w]) REQUIRE(b == barriers, "barriers of a K-stream form");
+        }
+    }
+    const std::vector<Fr> consts = in.frs(n_consts);
+    const std::vector<uint32_t> soff = in.words(ns);
+    for (uint32_t o : soff) REQUIRE(proof_len >= 32 && o % 32 == 0 && o <= proof_len - 32, "scalar offset");   // (two 16-byte loads per scalar)
+    DevBuf<VmInstr> d_code, d_code_k[3][FRVM_MAX_STREAMS]; DevBuf<Fr> d_consts, slots, chal, insteval, mult, shared; DevBuf<uint32_t> d_soff, msm, left, guard;
+    DevBuf<uint8_t> proofs, inst; DevBuf<int> status;
+    upload(d_code, code.data(), code.size());
+    upload(d_consts, consts.data(), consts.size());
+    upload(d_soff, soff.data(), soff.size());
+    upload(proofs, in.bytes((size_t)n * proof_len), (size_t)n * proof_len);
+    upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
+    { const std::vector<Fr> h = in.frs((size_t)n_chal * n); upload(chal, h.data(), h.size()); }
+    { const std::vector<Fr> h = in.frs((size_t)n_insteval * n); upload(insteval, h.data(), h.size()); }
+    { const std::vector<Fr> h = in.frs(n); upload(mult, h.data(), h.size()); }
+    { const std::vector<uint32_t> h = in.words(n); upload(status, (const int*)h.data(), h.size()); }
+    fresh(slots, (size_t)max_slots * n);
+    fresh(msm, (size_t)n * np * 8); fresh(left, (size_t)n * np * 8); fresh(guard, (size_t)n * n_guard * 8); fresh(shared, (size_t)n_shared * n);
+    FrvmArgs a;
+    a.code = d_code.p; a.n_code = n_code; a.consts = d_consts.p; a.slots = slots.p; a.n = n;
+    a.proofs = proofs.p; a.proof_len = proof_len; a.scalar_offsets = d_soff.p; a.inst = inst.p; a.ninst = ninst;
+    a.chal = chal.p; a.mult = mult.p; a.status = status.p; a.msm_scal = msm.p; a.np = np; a.shared = shared.p; a.left_scal = left.p;
+    a.insteval = insteval.p; a.guard_scal = guard.p; a.n_guard = n_guard;
+    for (int k = 0; k < 3; ++k) {
+        a.n_slots_k[k] = n_slots_k[k];
+        for (int w = 0; w < FRVM_MAX_STREAMS; ++w) {
+            if (!n_code_k[k][w]) continue;
+            upload(d_code_k[k][w], code_k[k][w].data(), code_k[k][w].size());
+            a.code_k[k][w] = d_code_k[k][w].p; a.n_code_k[k][w] = n_code_k[k][w];
+        }
+    }
+    a.force_streams = force_streams; a.force_lds_kb = force_lds_kb;
+    RC(frvm_enqueue(0, a, n_slots));
+    CK(hipDeviceSynchronize());
+    out_words(out, msm.p, (size_t)n * np * 8);
+    out_words(out, left.p, (size_t)n * np * 8);
+    out_words(out, guard.p, (size_t)n * n_guard * 8);
+    out_fields(out, shared.p, (size_t)n_shared * n);
+    out_words(out, status.p, n);
+}
+
+// ---- fold
+// job, form 0 (fold_shared_enqueue): 0, n, np, n_shared, groups, shared [n_shared][n]
+//      out: msm_scal, all (n np + groups n_shared) rows of 8 raw words (FILL where nothing was written)
+// job, form 1 (fold_shared_ranges_enqueue): 1, n_batches, per batch (n, n_shared, shared [n_shared][n]), n_ranges, per range (batch, first, count, out),
+//      max_shared, out_rows
+//      out: all out_rows rows of 8 raw words (FILL where nothing was written)
+static void run_fold(In& in, Out& out) {
+    const uint32_t form = in.word();
+    REQUIRE(form <= 1, "form");
+    if (form == 0) {
+        const uint32_t n = in.word(), np = in.word(), n_shared = in.word(), groups = in.word();
+        REQUIRE(n >= 1 && n <= (1u << 16) && np <= 16 && n_shared >= 1 && n_shared <= MAX_ITEMS && groups >= 1 && groups <= n && n % groups == 0, "counts");
+        DevBuf<Fr> shared; DevBuf<uint32_t> msm;
+        { const std::vector<Fr> h = in.frs((size_t)n_shared * n); upload(shared, h.data(), h.size()); }
+        const size_t rows = (size_t)n * np + (size_t)groups * n_shared;
+        fresh(msm, rows * 8);
+        RC(fold_shared_enqueue(0, shared.p, n, np, n_shared, groups, msm.p));
+        CK(hipDeviceSynchronize());
+        out_words(out, msm.p, rows * 8);
+        return;
+    }
+    const uint32_t n_batches = in.word();
+    REQUIRE(n_batches >= 1 && n_batches <= 16, "batches");
+    std::vector<DevBuf<Fr>> shared(n_batches);
+    std::vector<uint32_t> bn(n_batches), bs(n_batches);
+    for (uint32_t b = 0; b < n_batches; ++b) {
+        bn[b] = in.word(); bs[b] = in.word();
+        REQUIRE(bn[b] >= 1 && bn[b] <= (1u << 16) && bs[b] >= 1 && bs[b] <= MAX_ITEMS, "batch");
+        const std::vector<Fr> h = in.frs((size_t)bs[b] * bn[b]);
+        upload(shared[b], h.data(), h.size());
+    }
+    const uint32_t n_ranges = in.word();
+    REQUIRE(n_ranges >= 1 && n_ranges <= 4096, "ranges");
+    std::vector<FoldRange> rg(n_ranges);
+    std::vector<uint32_t> rb(n_ranges);
+    for (uint32_t r = 0; r < n_ranges; ++r) {
+        rb[r] = in.word();
+        REQUIRE(rb[r] < n_batches, "range's batch");
+        rg[r].shared = shared[rb[r]].p; rg[r].n = bn[rb[r]]; rg[r].n_shared = bs[rb[r]];
+        rg[r].first = in.word(); rg[r].count = in.word(); rg[r].out = in.word(); rg[r].pad = 0;
+        REQUIRE(rg[r].first <= rg[r].n && rg[r].count <= rg[r].n - rg[r].first, "range");
+    }
+    const uint32_t max_shared = in.word(), out_rows = in.word();
+    REQUIRE(max_shared >= 1 && max_shared <= MAX_ITEMS && out_rows <= (1u << 20), "rows");
+    for (uint32_t r = 0; r < n_ranges; ++r) REQUIRE(rg[r].n_shared <= max_shared && rg[r].out <= out_rows && rg[r].n_shared <= out_rows - rg[r].out, "range's rows");
+    DevBuf<FoldRange> d_rg; DevBuf<uint32_t> rows;
+    upload(d_rg, rg.data(), rg.size());
+    fresh(rows, (size_t)out_rows * 8);
+    RC(fold_shared_ranges_enqueue(0, d_rg.p, n_ranges, max_shared, rows.p));
+    CK(hipDeviceSynchronize());
+    out_words(out, rows.p, (size_t)out_rows * 8);
+}
+
+int main(int argc, char** argv) {
+    REQUIRE(argc == 4, "usage: verify_units decompress|stream|insteval|frvm|fold IN OUT");
+    const std::string mode = argv[1];
+    void (*run)(In&, Out&) = mode == "decompress" ? run_decompress : mode == "stream" ? run_stream : mode == "insteval" ? run_insteval : mode == "frvm" ? run_frvm : mode == "fold" ? run_fold : nullptr;
+    REQUIRE(run, "unknown mode");
+    In in;
+    {
+        std::ifstream f(argv[2], std::ios::binary);
+        REQUIRE(f.good(), "cannot open input");
+        in.b.assign((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    }
+    Out out;
+    const uint32_t jobs = in.word();
+    REQUIRE(jobs <= 4096, "jobs");
+    for (uint32_t j = 0; j < jobs; ++j) run(in, out);
+    REQUIRE(in.at == in.b.size(), "input longer than its jobs");
+    FILE* g = fopen(argv[3], "wb");
+    REQUIRE(g && fwrite(out.b.data(), 1, out.b.size(), g) == out.b.size() && fclose(g) == 0, "cannot write output");
+    return 0;
+}
