@@ -26,6 +26,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
+#include "field_chain.hip.h"
 
 // Small helpers are plain inline; the multi-hundred-instruction bodies (Montgomery product,
 // exponentiation, group law, tower products) are real function calls on the device: inlining
@@ -351,11 +353,16 @@ template <class PR> struct Fp {
     // Montgomery product a*b/R mod p by product scanning: column k collects a_i*b_(k-i) and m_i*p_(k-i) in one 64-bit
     // accumulator (<= 18 terms < 2^58 each, plus a carry < 2^35), m_k is chosen to clear the column's low 29 bits.
     // Any limb-normalised inputs are safe against overflow; representatives < 2p give a result < 1.04p.
-    // (The compiler's reassociation starts every column from zero and adds the carry of the previous column last: a 64-bit add per
-    // column, 143 per mixed addition beside its 1593 multiply-adds.  Forcing the chain to start FROM the carry (an empty asm statement
-    // after each step) removes them, but every multiply-add that follows an asm statement gets an s_nop from the hazard recogniser and
-    // the products no longer interleave: 4.69 instead of 4.63 us per list entry at three waves per SIMD, 4.79 instead of 5.13 at two
-    // (tools/affine_microbench.hip, round 3).  Left to the compiler.)
+    // This is the C++ form: what the host runs, and the reference the chained form below is held to.  The compiler's reassociation starts
+    // every column from zero and adds the carry of the previous column last: a 64-bit add (v_lshl_add_u64) per column, as dear as a
+    // multiply-add, 16 of the 222 vector instructions of a product.  Forcing the chain to start FROM the carry with an empty asm statement
+    // after EVERY multiply-add removed them but drew a wait state behind each of ~160 statements and kept the products from interleaving
+    // (4.69 instead of 4.63 us per list entry at three waves per SIMD, 4.79 instead of 5.13 at two: not kept).  One asm statement per COLUMN
+    // (mul_chain below, 14 wait states per product) wins at every occupancy, the lone wave included: 426 ns instead of 485 per product in
+    // a dependent chain, 165 instead of 151 G products/s at three waves per SIMD, 175 instead of 163 at four; the mixed-addition loop
+    // 4.7 instead of 5.1 us per entry at three waves (profiles/field_chain_microbench.txt).  The device code uses the chained form
+    // wherever its kernel got faster with it (profiles/field_chain_kernel_stats.txt: all but the pairing kernels' own inlined products and
+    // msm_fixup's in-register addition); this one stays for those, for the host, and as the other side of tests/test_gpu_field_units.py.
     __host__ __device__ __forceinline__ static Fp mul_inl(const Fp& a, const Fp& b) {
         uint64_t acc = 0;
         uint32_t m[9];
@@ -467,11 +474,137 @@ template <class PR> struct Fp {
         r.v[8] = (uint32_t)acc;
         return r;
     }
+    // ---- The same three products with every column's multiply-adds CHAINED from the previous column's carry: the column is one asm
+    // statement (field_chain.hip.h) whose first multiply-add takes the running accumulator as its addend, so the 64-bit addition that the
+    // compiler's form spends per column is gone (16 of the 222 vector instructions of a product, 16 of the 193 of a squaring).  Same
+    // product scanning, same quotient digits m[k], same masks and shifts: a column's sum is an exact integer below 2^64 whatever the order
+    // of its terms, so every result limb is bit for bit that of mul_inl / sqr_inl / dot2_inl.  Device only; on the host the three names
+    // are the C++ forms.  A call site picks its form by name, or through the template switches mul_as / sqr_as / dot2_as / sqdot_as below.
+#if defined(__HIP_DEVICE_COMPILE__)
+    // column K: the NV operand products x[i] y[i] and the reduction's m_i p_(K-i) in one run, then the column's close
+    template <int K, int NV> __device__ __forceinline__ static void chain_col(uint64_t& acc, uint32_t (&m)[9], Fp& r, const uint32_t* x, const uint32_t* y) {
+        constexpr int lo = K < 9 ? 0 : K - 8, ns = K < 9 ? K : 17 - K;
+        if constexpr (K == 0) {
+            acc = 0;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) acc += (uint64_t)x[i] * y[i];
+        } else {
+            uint32_t mm[ns], q[ns];
+#pragma unroll
+            for (int j = 0; j < ns; ++j) { mm[j] = m[lo + j]; q[j] = PR::P29(K - lo - j); }
+            MadRun<NV, ns>::run(acc, x, y, mm, q);
+        }
+        if constexpr (K < 9) {
+            m[K] = ((uint32_t)acc * PR::INV29) & H2V_LIMB_MASK;
+            acc += (uint64_t)m[K] * PR::P29(0);
+        } else r.v[K - 9] = (uint32_t)acc & H2V_LIMB_MASK;
+        acc >>= 29;
+    }
+    template <int K> __device__ __forceinline__ static void mul_col(uint64_t& acc, uint32_t (&m)[9], Fp& r, const Fp& a, const Fp& b) {
+        constexpr int lo = K < 9 ? 0 : K - 8, n = K < 9 ? K + 1 : 17 - K;
+        uint32_t x[n], y[n];
+#pragma unroll
+        for (int j = 0; j < n; ++j) { x[j] = a.v[lo + j]; y[j] = b.v[K - lo - j]; }
+        chain_col<K, n>(acc, m, r, x, y);
+    }
+    template <int K> __device__ __forceinline__ static void dot2_col(uint64_t& acc, uint32_t (&m)[9], Fp& r, const Fp& a0, const Fp& b0, const Fp& a1, const Fp& b1) {
+        constexpr int lo = K < 9 ? 0 : K - 8, n = K < 9 ? K + 1 : 17 - K;
+        uint32_t x[2 * n], y[2 * n];
+#pragma unroll
+        for (int j = 0; j < n; ++j) { x[2 * j] = a0.v[lo + j]; y[2 * j] = b0.v[K - lo - j]; x[2 * j + 1] = a1.v[lo + j]; y[2 * j + 1] = b1.v[K - lo - j]; }
+        chain_col<K, 2 * n>(acc, m, r, x, y);
+    }
+    // d = the doubled limbs: d_i v_(K-i) for lo <= i < K/2, and the diagonal term of an even column
+    template <int K> __device__ __forceinline__ static void sqr_col(uint64_t& acc, uint32_t (&m)[9], Fp& r, const uint32_t (&d)[9], const Fp& a) {
+        constexpr int lo = K < 9 ? 0 : K - 8, off = (K + 1) / 2 - lo, n = off + (K % 2 == 0 ? 1 : 0);
+        uint32_t x[n], y[n];
+#pragma unroll
+        for (int j = 0; j < off; ++j) { x[j] = d[lo + j]; y[j] = a.v[K - lo - j]; }
+        if constexpr (K % 2 == 0) { x[off] = a.v[K / 2]; y[off] = a.v[K / 2]; }
+        chain_col<K, n>(acc, m, r, x, y);
+    }
+    template <int K> __device__ __forceinline__ static void sqdot_col(uint64_t& acc, uint32_t (&m)[9], Fp& r, const uint32_t (&d)[9], const Fp& a, const Fp& a1, const Fp& b1) {
+        constexpr int lo = K < 9 ? 0 : K - 8, off = (K + 1) / 2 - lo, nsq = off + (K % 2 == 0 ? 1 : 0), n = K < 9 ? K + 1 : 17 - K;
+        uint32_t x[nsq + n], y[nsq + n];
+#pragma unroll
+        for (int j = 0; j < off; ++j) { x[j] = d[lo + j]; y[j] = a.v[K - lo - j]; }
+        if constexpr (K % 2 == 0) { x[off] = a.v[K / 2]; y[off] = a.v[K / 2]; }
+#pragma unroll
+        for (int j = 0; j < n; ++j) { x[nsq + j] = a1.v[lo + j]; y[nsq + j] = b1.v[K - lo - j]; }
+        chain_col<K, nsq + n>(acc, m, r, x, y);
+    }
+    template <int... K> __device__ __forceinline__ static Fp mul_cols(const Fp& a, const Fp& b, std::integer_sequence<int, K...>) {
+        uint64_t acc; uint32_t m[9]; Fp r;
+        (mul_col<K>(acc, m, r, a, b), ...);
+        r.v[8] = (uint32_t)acc;
+        return r;
+    }
+    template <int... K> __device__ __forceinline__ static Fp dot2_cols(const Fp& a0, const Fp& b0, const Fp& a1, const Fp& b1, std::integer_sequence<int, K...>) {
+        uint64_t acc; uint32_t m[9]; Fp r;
+        (dot2_col<K>(acc, m, r, a0, b0, a1, b1), ...);
+        r.v[8] = (uint32_t)acc;
+        return r;
+    }
+    template <int... K> __device__ __forceinline__ static Fp sqr_cols(const Fp& a, std::integer_sequence<int, K...>) {
+        uint64_t acc; uint32_t m[9], d[9]; Fp r;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) d[i] = a.v[i] << 1;
+        (sqr_col<K>(acc, m, r, d, a), ...);
+        r.v[8] = (uint32_t)acc;
+        return r;
+    }
+    template <int... K> __device__ __forceinline__ static Fp sqdot_cols(const Fp& a, const Fp& a1, const Fp& b1, std::integer_sequence<int, K...>) {
+        uint64_t acc; uint32_t m[9], d[9]; Fp r;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) d[i] = a.v[i] << 1;
+        (sqdot_col<K>(acc, m, r, d, a, a1, b1), ...);
+        r.v[8] = (uint32_t)acc;
+        return r;
+    }
+#endif
+    __host__ __device__ __forceinline__ static Fp mul_chain(const Fp& a, const Fp& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return mul_cols(a, b, std::make_integer_sequence<int, 17>());
+#else
+        return mul_inl(a, b);
+#endif
+    }
+    __host__ __device__ __forceinline__ static Fp dot2_chain(const Fp& a0, const Fp& b0, const Fp& a1, const Fp& b1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return dot2_cols(a0, b0, a1, b1, std::make_integer_sequence<int, 17>());
+#else
+        return dot2_inl(a0, b0, a1, b1);
+#endif
+    }
+    __host__ __device__ __forceinline__ Fp sqr_chain() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return sqr_cols(*this, std::make_integer_sequence<int, 17>());
+#else
+        return sqr_inl();
+#endif
+    }
+    // (a^2 + a1*b1)/R mod p, the dot2 whose first product is a squaring (X3 of the group law).  In C++ it is dot2_inl(a, a, a1, b1): the
+    // compiler itself finds the 36 equal pairs of that call and takes each once, doubled.  An asm statement hides its products from
+    // that, so the chained form spells the squaring out (without this, a chained mixed addition carried 36 multiply-adds more than the
+    // compiler's).
+    __host__ __device__ __forceinline__ static Fp sqdot_inl(const Fp& a, const Fp& a1, const Fp& b1) { return dot2_inl(a, a, a1, b1); }
+    __host__ __device__ __forceinline__ static Fp sqdot_chain(const Fp& a, const Fp& a1, const Fp& b1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return sqdot_cols(a, a1, b1, std::make_integer_sequence<int, 17>());
+#else
+        return sqdot_inl(a, a1, b1);
+#endif
+    }
+    // the form as a template parameter, for routines (the group law) that several kernels instantiate with different forms
+    template <bool CHAIN> __host__ __device__ __forceinline__ static Fp mul_as(const Fp& a, const Fp& b) { if constexpr (CHAIN) return mul_chain(a, b); else return mul_inl(a, b); }
+    template <bool CHAIN> __host__ __device__ __forceinline__ static Fp dot2_as(const Fp& a0, const Fp& b0, const Fp& a1, const Fp& b1) { if constexpr (CHAIN) return dot2_chain(a0, b0, a1, b1); else return dot2_inl(a0, b0, a1, b1); }
+    template <bool CHAIN> __host__ __device__ __forceinline__ static Fp sqdot_as(const Fp& a, const Fp& a1, const Fp& b1) { if constexpr (CHAIN) return sqdot_chain(a, a1, b1); else return sqdot_inl(a, a1, b1); }
+    template <bool CHAIN> __host__ __device__ __forceinline__ Fp sqr_as() const { if constexpr (CHAIN) return sqr_chain(); else return sqr_inl(); }
     // The same product as a real function call (operands and result by value, i.e. in VGPRs).  Mid-level routines
     // (Fq2 products, the G1 group law) inline mul_inl so that their independent products can be interleaved by the
     // scheduler, while everything else calls this one copy to keep code size and compile time bounded.
-    H2V_FN static Fp mul(Fp a, Fp b) { return mul_inl(a, b); }
-    H2V_FN static Fp sqr_fn(Fp a) { return a.sqr_inl(); }
+    H2V_FN static Fp mul(Fp a, Fp b) { return mul_chain(a, b); }
+    H2V_FN static Fp sqr_fn(Fp a) { return a.sqr_chain(); }
     H2V_HD Fp operator*(const Fp& b) const { return mul(*this, b); }
     H2V_HD Fp sqr() const { return sqr_fn(*this); }
 

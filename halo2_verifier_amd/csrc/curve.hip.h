@@ -40,8 +40,12 @@ struct G1J {
 // The group law routines come in two forms: *_inl bodies that hot kernels inline so that the accumulator stays in
 // registers, and plain functions (real calls) for everything else.  Field products are inlined in both (see Fp::mul).
 H2V_FN G1J g1_dbl(const G1J& p);
-#define H2V_M(a, b) Fq::mul_inl((a), (b))
-#define H2V_S(a) (a).sqr_inl()
+// (CHAIN, the template parameter of the routines below, picks the form of their field products per call site: false is the compiler's
+// form, true the chained one of bn254.hip.h.  Same numbers either way; which one is faster depends on the kernel around it.)
+#define H2V_M(a, b) Fq::template mul_as<CHAIN>((a), (b))
+#define H2V_S(a) (a).template sqr_as<CHAIN>()
+#define H2V_D(...) Fq::template dot2_as<CHAIN>(__VA_ARGS__)
+#define H2V_SD(...) Fq::template sqdot_as<CHAIN>(__VA_ARGS__)
 // -8 in Montgomery form (29-bit limbs, R = 2^261): the constant of Y3 = E (D - X3) - 8 C as the second term of a dot2
 __host__ __device__ __forceinline__ Fq g1_minus_eight() {
     const Fq k = {{0x1d9096cdu, 0x022be75eu, 0x12c66350u, 0x1e1f47a4u, 0x0b760e9fu, 0x1e7fbbcfu, 0x134a4383u, 0x01be3557u, 0x0022eb3au}};
@@ -52,7 +56,7 @@ __host__ __device__ __forceinline__ Fq g1_minus_eight() {
 // (from_wide), Y3 = E (D + 2p - X3) - 8C as one dot2, Z3 = (2Y) Z.  Bounds for coordinates below 2p, in multiples of p: A, B, C, XB < 1.03;
 // E < 3.1; D < 4.2; E^2 + 9p - 2D in (0.7, 10.1) -> X3 < 1.0001; D + 2p - X3 < 6.2; Y3 < 1.13; Z3 < 1.05.  13 corrected additions
 // (~65 instructions each) became 5 lazy ones and a sweep: 2295 -> ~1700 instructions.  The identity (Z = 0) stays the identity.
-__host__ __device__ __forceinline__ G1J g1_dbl_inl(const G1J& p) {
+template <bool CHAIN = true> __host__ __device__ __forceinline__ G1J g1_dbl_inl(const G1J& p) {
     if (p.is_identity()) return p;
     const Fq A = H2V_S(p.X), B = H2V_S(p.Y), XB = H2V_M(p.X, B), C = H2V_S(B);
     const Fq E = Fq::lazy_add2(A, A), F = H2V_S(E), D = Fq::lazy_dbl(Fq::lazy_dbl(XB));
@@ -61,7 +65,7 @@ __host__ __device__ __forceinline__ G1J g1_dbl_inl(const G1J& p) {
     for (int l = 0; l < 9; ++l) acc[l] = (int64_t)F.v[l] + (int64_t)Fq::KP29(9, l) - 2 * (int64_t)D.v[l];
     G1J r;
     r.X = Fq::from_wide(acc);
-    r.Y = Fq::dot2_inl(E, Fq::lazy_sub(D, r.X), C, g1_minus_eight());
+    r.Y = H2V_D(E, Fq::lazy_sub(D, r.X), C, g1_minus_eight());
     r.Z = H2V_M(Fq::lazy_dbl(p.Y), p.Z);
     return r;
 }
@@ -75,7 +79,7 @@ __host__ __device__ __forceinline__ G1J g1_dbl_inl(const G1J& p) {
 // H < 3.03; 2H, r < 6.1; I < 1.23 (so "I is zero" is the limb string 0 or p, and I = 0 <=> the x coordinates agree);
 // 8p - H - 2 U1 in (0.9, 8); 4p - 2 S1 <= 4; X3 < 1.28; r U1 - 2 S1 H < 1.15; Y3 < 1.09; Z3 < 1.08 — the results are ordinary
 // representatives below 2p again, nothing downstream sees the lazy values.
-__host__ __device__ __forceinline__ bool g1_madd_fast(G1J& acc, const G1A& q) {
+template <bool CHAIN = true> __host__ __device__ __forceinline__ bool g1_madd_fast(G1J& acc, const G1A& q) {
     if (q.is_identity()) return true;
     if (acc.is_identity()) { acc.X = q.x; acc.Y = q.y; acc.Z = Fq::one(); return true; }
     const Fq Z1Z1 = H2V_S(acc.Z);
@@ -83,14 +87,14 @@ __host__ __device__ __forceinline__ bool g1_madd_fast(G1J& acc, const G1A& q) {
     const Fq H = Fq::lazy_sub(U2, acc.X), H2 = Fq::lazy_dbl(H), I = H2V_S(H2);
     if (I.is_zero()) return false;
     const Fq B = Fq::lazy_neg2(acc.Y), rr = Fq::lazy_add2(B, S2);
-    const Fq X3 = Fq::dot2_inl(rr, rr, I, Fq::template lazy_lin<8, 1, 2>(H, acc.X));
-    const Fq W = Fq::dot2_inl(rr, acc.X, H, B);
-    acc.Y = Fq::dot2_inl(I, W, rr, Fq::lazy_neg(X3));
+    const Fq X3 = H2V_SD(rr, I, Fq::template lazy_lin<8, 1, 2>(H, acc.X));
+    const Fq W = H2V_D(rr, acc.X, H, B);
+    acc.Y = H2V_D(I, W, rr, Fq::lazy_neg(X3));
     acc.Z = H2V_M(acc.Z, H2);
     acc.X = X3;
     return true;
 }
-__host__ __device__ __forceinline__ bool g1_add_fast(G1J& acc, const G1J& q) {
+template <bool CHAIN = true> __host__ __device__ __forceinline__ bool g1_add_fast(G1J& acc, const G1J& q) {
     if (q.is_identity()) return true;
     if (acc.is_identity()) { acc.X = q.X; acc.Y = q.Y; acc.Z = q.Z; return true; }
     const Fq Z1Z1 = H2V_S(acc.Z), Z2Z2 = H2V_S(q.Z);
@@ -99,18 +103,18 @@ __host__ __device__ __forceinline__ bool g1_add_fast(G1J& acc, const G1J& q) {
     if (I.is_zero()) return false;
     const Fq S1 = H2V_M(H2V_M(acc.Y, q.Z), Z2Z2), S2 = H2V_M(H2V_M(q.Y, acc.Z), Z1Z1);
     const Fq B = Fq::lazy_neg2(S1), rr = Fq::lazy_add2(B, S2);
-    const Fq X3 = Fq::dot2_inl(rr, rr, I, Fq::template lazy_lin<8, 1, 2>(H, U1));
-    const Fq W = Fq::dot2_inl(rr, U1, H, B);
-    acc.Y = Fq::dot2_inl(I, W, rr, Fq::lazy_neg(X3));
+    const Fq X3 = H2V_SD(rr, I, Fq::template lazy_lin<8, 1, 2>(H, U1));
+    const Fq W = H2V_D(rr, U1, H, B);
+    acc.Y = H2V_D(I, W, rr, Fq::lazy_neg(X3));
     acc.Z = H2V_M(H2V_M(acc.Z, q.Z), H2);
     acc.X = X3;
     return true;
 }
 // The complete additions: the fast forms above, and behind their `false` the two cases they leave out (rare: the sums of an MSM
 // meet equal or opposite points only in adversarial inputs — which the tests construct).
-__host__ __device__ __forceinline__ G1J g1_add_inl(const G1J& p, const G1J& q) {
+template <bool CHAIN = true> __host__ __device__ __forceinline__ G1J g1_add_inl(const G1J& p, const G1J& q) {
     G1J r = p;
-    if (g1_add_fast(r, q)) return r;
+    if (g1_add_fast<CHAIN>(r, q)) return r;
     // the x coordinates agree: the same point (double it) or opposite points
     const Fq Z1Z1 = H2V_S(p.Z), Z2Z2 = H2V_S(q.Z);
     const Fq S1 = H2V_M(H2V_M(p.Y, q.Z), Z2Z2), S2 = H2V_M(H2V_M(q.Y, p.Z), Z1Z1);
@@ -118,9 +122,9 @@ __host__ __device__ __forceinline__ G1J g1_add_inl(const G1J& p, const G1J& q) {
     return G1J::identity();
 }
 
-__host__ __device__ __forceinline__ G1J g1_add_affine_inl(const G1J& p, const G1A& q) {
+template <bool CHAIN = true> __host__ __device__ __forceinline__ G1J g1_add_affine_inl(const G1J& p, const G1A& q) {
     G1J r = p;
-    if (g1_madd_fast(r, q)) return r;
+    if (g1_madd_fast<CHAIN>(r, q)) return r;
     const Fq Z1Z1 = H2V_S(p.Z);
     const Fq S2 = H2V_M(H2V_M(q.y, p.Z), Z1Z1);
     if (p.Y == S2) return g1_dbl(r);
@@ -133,7 +137,7 @@ H2V_FN G1J g1_dbl(const G1J& p) { return g1_dbl_inl(p); }
 // through the out-of-line Fp::mul the constant travelled as a stack argument (36 bytes of scratch written and read back per call).
 __host__ __device__ __forceinline__ Fq g1_beta_times(const Fq& x) {
     const Fq beta = {{0x18ccb791u, 0x175b1c3au, 0x0b83d6e2u, 0x0e8ed071u, 0x1282bee2u, 0x04220e84u, 0x1fe4017fu, 0x15084d4au, 0x00169119u}};
-    return Fq::mul_inl(x, beta);
+    return Fq::mul_chain(x, beta);
 }
 __host__ __device__ __forceinline__ G1A g1_phi(const G1A& p) { G1A r; r.x = g1_beta_times(p.x); r.y = p.y; return r; }   // (the identity (0, 0) stays the identity)
 H2V_FN G1J g1_add(const G1J& p, const G1J& q) { return g1_add_inl(p, q); }
@@ -211,10 +215,10 @@ template <int W> constexpr FqSqrtRuns fq_sqrt_runs() {
 }
 #if defined(__HIPCC__)
 __device__ __constant__ const FqSqrtRuns fq_sqrt_runs_w3 = fq_sqrt_runs<3>();
-__device__ __forceinline__ Fq fq_sqrt_candidate_loop_w3(const Fq& a) {
+template <bool CHAIN = true> __device__ __forceinline__ Fq fq_sqrt_candidate_loop_w3(const Fq& a) {
     Fq t0 = a;
-    const Fq a2 = a.sqr_inl();
-    const Fq t1 = Fq::mul_inl(t0, a2), t2 = Fq::mul_inl(t1, a2), t3 = Fq::mul_inl(t2, a2);   // a, a^3, a^5, a^7
+    const Fq a2 = H2V_S(a);
+    const Fq t1 = H2V_M(t0, a2), t2 = H2V_M(t1, a2), t3 = H2V_M(t2, a2);   // a, a^3, a^5, a^7
     auto pick = [&](uint32_t i) -> Fq {
         Fq s;
 #pragma unroll
@@ -227,12 +231,12 @@ __device__ __forceinline__ Fq fq_sqrt_candidate_loop_w3(const Fq& a) {
     for (int k = 0; k < n; ++k) {
         const uint32_t nsq = fq_sqrt_runs_w3.nsq[k], idx = fq_sqrt_runs_w3.idx[k];
 #pragma unroll 1
-        for (uint32_t i = 0; i < nsq; ++i) r = r.sqr_inl();
+        for (uint32_t i = 0; i < nsq; ++i) r = H2V_S(r);
         // (idx is wave-uniform: four copies of the product behind scalar branches instead of 27 selects in front of one)
-        if (idx == 0u) r = Fq::mul_inl(r, t0);
-        else if (idx == 1u) r = Fq::mul_inl(r, t1);
-        else if (idx == 2u) r = Fq::mul_inl(r, t2);
-        else if (idx == 3u) r = Fq::mul_inl(r, t3);
+        if (idx == 0u) r = H2V_M(r, t0);
+        else if (idx == 1u) r = H2V_M(r, t1);
+        else if (idx == 2u) r = H2V_M(r, t2);
+        else if (idx == 3u) r = H2V_M(r, t3);
     }
     return r;
 }
@@ -277,11 +281,11 @@ __device__ __forceinline__ void g1_dbl_quad(G1J& p, uint32_t r) {
     // products of a level on different lanes.  The identity (Z = 0) stays the identity: Z3 = (2Y) Z.
     // level 1   lane 0: A = X^2   lane 1: B = Y^2   lanes 2, 3: Z3 = (2Y) Z
     const Fq Y2 = Fq::lazy_dbl(p.Y);
-    const Fq p1 = Fq::mul_inl(fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, Y2)), fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, p.Z)));
+    const Fq p1 = Fq::mul_chain(fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, Y2)), fq_sel(r == 0, p.X, fq_sel(r == 1, p.Y, p.Z)));
     const Fq A = quad_bcast<0>(p1), B = quad_bcast<1>(p1), Z3 = quad_bcast<2>(p1);
     // level 2   lane 0: C = B^2   lane 1: X B   lane 2: E^2, E = 3A   (lane 3: E B, unused)
     const Fq E = Fq::lazy_add2(A, A);
-    const Fq p2 = Fq::mul_inl(fq_sel(r == 0, B, fq_sel(r == 1, p.X, E)), fq_sel(r == 2, E, B));
+    const Fq p2 = Fq::mul_chain(fq_sel(r == 0, B, fq_sel(r == 1, p.X, E)), fq_sel(r == 2, E, B));
     const Fq C = quad_bcast<0>(p2), XB = quad_bcast<1>(p2), F = quad_bcast<2>(p2);
     // level 3   every lane: X3 = E^2 - 8 X B, Y3 = E (4 X B - X3) - 8 C
     const Fq D = Fq::lazy_dbl(Fq::lazy_dbl(XB));
@@ -289,7 +293,7 @@ __device__ __forceinline__ void g1_dbl_quad(G1J& p, uint32_t r) {
 #pragma unroll
     for (int l = 0; l < 9; ++l) acc[l] = (int64_t)F.v[l] + (int64_t)Fq::KP29(9, l) - 2 * (int64_t)D.v[l];
     p.X = Fq::from_wide(acc);
-    p.Y = Fq::dot2_inl(E, Fq::lazy_sub(D, p.X), C, g1_minus_eight());
+    p.Y = Fq::dot2_chain(E, Fq::lazy_sub(D, p.X), C, g1_minus_eight());
     p.Z = Z3;
 }
 // Horner over the points src[0 .. items) (src[i] weighs 2^(dbl * i)) by the quad that lane r belongs to

@@ -904,7 +904,7 @@ __global__ void __launch_bounds__(64) msm_fixup(const uint32_t* __restrict__ cou
     // in-register additions; pieces of one bucket can coincide or cancel (the same point in two chunks): complete formulas then
     G1J acc = msm_piece_src(partial, i0, i0, off, CH)->p;
     bool ok = true;
-    for (uint32_t i = i0 + 1; i <= i1 && ok; ++i) ok = g1_add_fast(acc, msm_piece_src(partial, i, i0, off, CH)->p);
+    for (uint32_t i = i0 + 1; i <= i1 && ok; ++i) ok = g1_add_fast<false>(acc, msm_piece_src(partial, i, i0, off, CH)->p);
     if (!ok) { msm_fixup_slow(partial, i0, i1, off, CH, bucket_pts + b); return; }
     bucket_pts[b] = acc;
 }
@@ -1048,8 +1048,8 @@ __global__ void __launch_bounds__(64) msm_final_parts(const G1JSlot* __restrict_
     if (prs[q].n && lo < hi) acc = msm_horner_quad(window_sums + (size_t)q * p.windows + lo, hi - lo, p.c, r);
     if (r == 0) out[quad] = acc;
     // the form the pairing's lines are evaluated at, (X Z, Y, Z^3): two lanes of the quad, two products deep
-    if (r == 0) { ready[quad].p.X = Fq::mul_inl(acc.X, acc.Z); ready[quad].p.Y = acc.Y; }
-    if (r == 1) ready[quad].p.Z = Fq::mul_inl(acc.Z.sqr_inl(), acc.Z);
+    if (r == 0) { ready[quad].p.X = Fq::mul_chain(acc.X, acc.Z); ready[quad].p.Y = acc.Y; }
+    if (r == 1) ready[quad].p.Z = Fq::mul_chain(acc.Z.sqr_chain(), acc.Z);
 }
 __global__ void __launch_bounds__(64) msm_combine_parts(const G1JSlot* __restrict__ pieces, const MsmProblem* __restrict__ prs, uint32_t count, uint32_t parts, uint32_t shift) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, q = t >> 2, r = t & 3u;

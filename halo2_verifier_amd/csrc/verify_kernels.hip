@@ -22,6 +22,11 @@ namespace h2v {
 
 // 32 B in (two 16-byte loads: a point sits at a multiple of 32 bytes inside a proof whose length is a multiple of 32), 72 + 32 B
 // out as 8-byte / 16-byte stores.  Round 1 moved every byte on its own: 13x the algorithmic traffic (profiles/r01_pmc_fetch_write.csv).
+// The kernel asks for 10 KiB of LDS (it uses 4.5): sixteen workgroups, four waves per SIMD, fill a CU's 160 KiB.  With the chained field
+// products the kernel needs 76 registers instead of 120 and would fit six waves per SIMD; the dispatcher fills a CU before it moves on
+// to the next, so a launch that does not fill the chip (the 20-step launch: 1920 waves for 1024 SIMDs) sat on fewer SIMDs and took
+// 542 us instead of 487.  Held to four waves it takes 452 (profiles/field_chain_kernel_stats.txt); caps of three and two measured the same.
+#define K_DECOMPRESS_LDS_WORDS 2560
 __global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
                                                    uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, uint8_t* __restrict__ ycanon,
                                                    int* __restrict__ status) {
@@ -66,7 +71,7 @@ __global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict_
     // lines partially, and the L2 fetched each of them to merge the bytes: 0.2 GB of reads and 0.14 GB of writes for 26 MB of
     // output (profiles/r02_pmc_fetch_write_steps20.csv, first collection).  Transposed in LDS, every store instruction writes
     // 256 contiguous bytes.
-    __shared__ uint32_t out_lds[64 * 18];
+    __shared__ uint32_t out_lds[K_DECOMPRESS_LDS_WORDS];
     const uint32_t lane = threadIdx.x, t0 = blockIdx.x * blockDim.x, live = min(64u, n * np - t0);
     const uint32_t* av = reinterpret_cast<const uint32_t*>(&a);
 #pragma unroll
@@ -562,7 +567,7 @@ template <bool TWO> __device__ __forceinline__ void frvm_run(const FrvmArgs& a, 
         switch (in.op) {
             case OP_BARRIER: if (TWO) __syncthreads(); last_d = 0xffffffffu; break;   // (behind a barrier another stream may own the slot `last` mirrored)
             case OP_CONST: put(in.d, a.consts[in.a]); break;
-            case OP_MUL: put(in.d, Fr::mul_inl(opnd(in.a), opnd(in.b))); break;
+            case OP_MUL: put(in.d, Fr::mul_chain(opnd(in.a), opnd(in.b))); break;
             case OP_ADD: put(in.d, opnd(in.a) + opnd(in.b)); break;
             case OP_SUB: put(in.d, opnd(in.a) - opnd(in.b)); break;
             case OP_NEG: put(in.d, slot(in.a).neg()); break;

@@ -9,6 +9,8 @@
 // pairs, then N/4, ...).  This program measures the three ingredients at the occupancies the kernel runs at and the two candidate
 // loop bodies, with the real field / group code of the library and random 72-byte gathers like the kernel's:
 //   jac     N entries per lane, one mixed Jacobian addition each                         (the kernel today)
+//           `affine_microbench forms` runs only this loop, with the field products in the compiler's form and in the chained form
+//           (bn254.hip.h: mul_chain and friends), at 1 to 4 waves per SIMD, the two alternating
 //   inv     one safegcd inversion per lane
 //   pair1   "v1": the entries taken in PAIRS — pass A computes the suffix products of the N/2 denominators (x only, stored to a
 //           [k][limb][lane] scratch array), ONE inversion, pass B recovers each inverse, forms P + Q in affine coordinates and adds
@@ -29,7 +31,7 @@ namespace h2v { void set_last_error(const std::string&) {} }
 
 __device__ __forceinline__ uint32_t rnd_next(uint32_t& s) { s = s * 1664525u + 1013904223u; return (s >> 8) & (TABLE - 1); }
 
-__global__ void __launch_bounds__(64) k_jac(const G1A* __restrict__ tab, G1J* __restrict__ out, int n) {
+template <bool CHAIN> __global__ void __launch_bounds__(64) k_jac(const G1A* __restrict__ tab, G1J* __restrict__ out, int n) {
     const uint32_t lane = blockIdx.x * 64 + threadIdx.x;
     uint32_t s = lane * 2654435761u + 12345u;
     G1J acc = G1J::identity();
@@ -37,7 +39,7 @@ __global__ void __launch_bounds__(64) k_jac(const G1A* __restrict__ tab, G1J* __
     for (int i = 0; i < n; ++i) {
         const G1A cur = nx;
         nx = tab[rnd_next(s)];
-        g1_madd_fast(acc, cur);
+        g1_madd_fast<CHAIN>(acc, cur);
     }
     out[lane] = acc;
 }
@@ -131,7 +133,7 @@ __global__ void __launch_bounds__(64) k_tree(const G1A* __restrict__ tab, G1A* _
     out[lane] = stage[lane];
 }
 
-int main() {
+int main(int argc, char** argv) {
     std::vector<G1A> h(TABLE);
     uint32_t s = 7;
     for (auto& p : h) { for (int l = 0; l < 9; ++l) { s = s * 1103515245u + 12345u; p.x.v[l] = (s >> 3) & (l == 8 ? 0x1fffffu : H2V_LIMB_MASK); s = s * 1103515245u + 12345u; p.y.v[l] = (s >> 3) & (l == 8 ? 0x1fffffu : H2V_LIMB_MASK); } }
@@ -142,6 +144,19 @@ int main() {
     G1A* stage; hipMalloc(&stage, (size_t)128 * sizeof(G1A) * max_lanes / 2);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     auto timed = [&](auto launch) { launch(); hipDeviceSynchronize(); hipEventRecord(e0); launch(); hipEventRecord(e1); hipEventSynchronize(e1); float ms; hipEventElapsedTime(&ms, e0, e1); return ms; };
+    if (argc > 1 && std::string(argv[1]) == "forms") {
+        printf("jac loop, 64 entries per lane, ns of SIMD time per list entry: compiler's form (two passes) | chained form (two passes)\n");
+        for (int wps : {1, 2, 3, 4}) {
+            const uint32_t blocks = 1024 * wps;
+            float t[4];
+            for (int pass = 0; pass < 2; ++pass) {
+                t[2 * pass] = timed([&] { hipLaunchKernelGGL(k_jac<false>, dim3(blocks), dim3(64), 0, 0, tab, out, 64); });
+                t[2 * pass + 1] = timed([&] { hipLaunchKernelGGL(k_jac<true>, dim3(blocks), dim3(64), 0, 0, tab, out, 64); });
+            }
+            printf("  waves per SIMD = %d:  %7.1f %7.1f | %7.1f %7.1f\n", wps, t[0] * 1e6 / (64 * wps), t[2] * 1e6 / (64 * wps), t[1] * 1e6 / (64 * wps), t[3] * 1e6 / (64 * wps));
+        }
+        return 0;
+    }
     printf("MI355X: 1024 SIMDs.  times in ms; 'per entry' in ns of SIMD time per list entry (= ms / (entries per lane x waves per SIMD))\n");
     for (int wps : {1, 2, 3}) {
         const uint32_t blocks = 1024 * wps;
@@ -149,7 +164,7 @@ int main() {
         printf("waves per SIMD = %d (%u lanes): one inversion per lane %.4f ms\n", wps, blocks * 64, t_inv);
         for (int n : {16, 32, 48, 64, 96, 128}) {
             if ((size_t)n * blocks * 64 > (size_t)128 * max_lanes / 2) continue;
-            const float tj = timed([&] { hipLaunchKernelGGL(k_jac, dim3(blocks), dim3(64), 0, 0, tab, out, n); });
+            const float tj = timed([&] { hipLaunchKernelGGL(k_jac<false>, dim3(blocks), dim3(64), 0, 0, tab, out, n); });
             const float tp = timed([&] { hipLaunchKernelGGL(k_pair1, dim3(blocks), dim3(64), 0, 0, tab, out, scratch, n); });
             const float tt = (n & (n - 1)) == 0 ? timed([&] { hipLaunchKernelGGL(k_tree, dim3(blocks), dim3(64), 0, 0, tab, (G1A*)out, scratch, stage, n); }) : 0.f;
             printf("  entries per lane %3d:  jac %.4f  pair1 %.4f (x%.2f)  tree %.4f (x%.2f)   per entry: jac %.1f ns, pair1 %.1f ns\n", n, tj, tp, tj / tp, tt, tt > 0 ? tj / tt : 0.f,

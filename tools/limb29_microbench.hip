@@ -3,6 +3,8 @@
 // (csrc/bn254.hip.h adopted the prototype; the 8 x 32-bit CIOS product it replaced measured 1052 ns on a lone wave and
 // 83 G products/s chip-wide with this same harness), a two-accumulator variant (no gain: recorded negative result), and the
 // product rate as a function of occupancy (1, 2, 3 waves per SIMD) — the MSM kernels run at 2 waves per SIMD.
+// Last section: the library's product, squaring, dot2 and square-root loop in the compiler's form against the chained form
+// (bn254.hip.h: mul_chain and friends), lone wave and 1 to 4 waves per SIMD, the two forms alternating, two passes.
 // Build: hipcc -O3 --offload-arch=gfx950 -I halo2_verifier_amd/csrc tools/limb29_microbench.hip -o tools/limb29_microbench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -184,6 +186,33 @@ __global__ void k32_chain_add(Fq* io, int iters) {
     io[i] = a;
 }
 
+// the library's routines in either form (CHAIN: bn254.hip.h mul_as / sqr_as / dot2_as)
+template <bool CHAIN> __global__ void __launch_bounds__(64) k_lib_mul(Fq* io, int iters) {
+    size_t i = threadIdx.x + (size_t)blockIdx.x * blockDim.x;
+    Fq a = io[i], b = a;
+    for (int k = 0; k < iters; ++k) a = Fq::mul_as<CHAIN>(a, b);
+    io[i] = a;
+}
+template <bool CHAIN> __global__ void __launch_bounds__(64) k_lib_sqr(Fq* io, int iters) {
+    size_t i = threadIdx.x + (size_t)blockIdx.x * blockDim.x;
+    Fq a = io[i];
+    for (int k = 0; k < iters; ++k) a = a.sqr_as<CHAIN>();
+    io[i] = a;
+}
+template <bool CHAIN> __global__ void __launch_bounds__(64) k_lib_dot2(Fq* io, int iters) {
+    size_t i = threadIdx.x + (size_t)blockIdx.x * blockDim.x;
+    Fq a = io[i], b = a, c = a + a;
+    for (int k = 0; k < iters; ++k) a = Fq::dot2_as<CHAIN>(a, b, c, a);
+    io[i] = a;
+}
+// k_decompress's square root (curve.hip.h), iters / 256 of them (a square root is ~251 squarings and ~58 products)
+template <bool CHAIN> __global__ void __launch_bounds__(64, 4) k_lib_sqrt(Fq* io, int iters) {
+    size_t i = threadIdx.x + (size_t)blockIdx.x * blockDim.x;
+    Fq a = io[i];
+    for (int k = 0; k < iters / 256; ++k) a = fq_sqrt_candidate_loop_w3<CHAIN>(a);
+    io[i] = a;
+}
+
 template <class K, class T> float run(K kern, T* d, int blocks, int threads, int iters) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0); hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, 0, d, iters); hipEventRecord(e1);
@@ -254,6 +283,23 @@ int main() {
         printf("  library add blocks=%5d  %8.2f G/s\n", blocks, (double)blocks * 256 * it * 2 / ms / 1e6);
         ms = run(k29_chain_add, d29, blocks, 256, it);
         printf("  add 9x29 blocks=%5d  %8.2f G/s\n", blocks, (double)blocks * 256 * it * 2 / ms / 1e6);
+    }
+    printf("library routines, compiler's form | chained form (two alternating passes each):\n");
+    struct Form { const char* name; void (*plain)(Fq*, int); void (*chained)(Fq*, int); double ops; };
+    const Form forms[] = {{"mul", k_lib_mul<false>, k_lib_mul<true>, 1}, {"sqr", k_lib_sqr<false>, k_lib_sqr<true>, 1}, {"dot2", k_lib_dot2<false>, k_lib_dot2<true>, 1},
+                          {"sqrt", k_lib_sqrt<false>, k_lib_sqrt<true>, 1.0 / 256}};
+    reset();   // (once: whatever a chain leaves behind is a representative below 2p again, as good an operand as any)
+    for (const Form& f : forms) {
+        const int its = f.ops == 1 ? it : 256 * 8;
+        float ms[4];
+        for (int pass = 0; pass < 2; ++pass) { ms[2 * pass] = run(f.plain, d32, 1, 64, its); ms[2 * pass + 1] = run(f.chained, d32, 1, 64, its); }
+        printf("  %-4s lone wave, ns per op:        %9.1f %9.1f | %9.1f %9.1f\n", f.name, ms[0] * 1e6 / (its * f.ops), ms[2] * 1e6 / (its * f.ops), ms[1] * 1e6 / (its * f.ops), ms[3] * 1e6 / (its * f.ops));
+        for (int wps = 1; wps <= 4; ++wps) {
+            const int blocks = 1024 * wps;
+            for (int pass = 0; pass < 2; ++pass) { ms[2 * pass] = run(f.plain, d32, blocks, 64, its); ms[2 * pass + 1] = run(f.chained, d32, blocks, 64, its); }
+            const double g = (double)blocks * 64 * its * f.ops / 1e6;
+            printf("  %-4s %d waves per SIMD, G op/s:     %9.3f %9.3f | %9.3f %9.3f\n", f.name, wps, g / ms[0], g / ms[2], g / ms[1], g / ms[3]);
+        }
     }
     return 0;
 }
