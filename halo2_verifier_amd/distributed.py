@@ -24,6 +24,7 @@ Entry points
       the staged form both are built on (and bench.py pipelines): upload the shard once, launch() = shard pipeline -> export ->
       all-gather -> fold -> one pairing, asynchronous on the batch's stream; finish() fetches the verdict.
 """
+import contextlib
 import ctypes
 import os
 
@@ -190,9 +191,7 @@ class ShardedBatch:
             self.batch.upload_launch(proofs_flat, proof_len, instances_flat, col_lens, rand_tail, with_pairing=True)
             self._exchanged = False
             return
-        import torch
-        ctxm = torch.cuda.stream(self._external_stream()) if (self.device.type == "cuda" and self._stream_handle is not None) else _NullCtx()
-        with ctxm:
+        with self._on_stream():
             self.batch.upload_launch(proofs_flat, proof_len, instances_flat, col_lens, rand_tail, with_pairing=False)
             self.batch.export_accumulators(self.records.data_ptr())
             self._exchanged = True
@@ -203,11 +202,17 @@ class ShardedBatch:
             self.batch.launch(with_pairing=True)
             self._exchanged = False
             return
-        import torch
-        ctxm = torch.cuda.stream(self._external_stream()) if (self.device.type == "cuda" and self._stream_handle is not None) else _NullCtx()
-        with ctxm:
+        with self._on_stream():
             local = self.launch_shard()
             self.fold(gather_accumulators(local, self.world, self.group), self.world)
+
+    def _on_stream(self):
+        """The context an exchanging launch runs under: the batch's stream as torch's current one, so that the collective is ordered with
+        the batch's kernels (nothing to enter without a GPU stream)"""
+        import torch
+        if self.device.type == "cuda" and self._stream_handle is not None:
+            return torch.cuda.stream(self._external_stream())
+        return contextlib.nullcontext()
 
     def _external_stream(self):
         import torch
@@ -241,14 +246,6 @@ class ShardedBatch:
         return st, checks
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 def _flatten(proofs, instances):
     """-> (proofs_flat, proof_len, instances_flat, col_lens); one instance shape per sharded batch (the staged interface)."""
     from .verifier import _flatten_instances
@@ -266,6 +263,17 @@ def _flatten(proofs, instances):
             raise ValueError("a sharded batch takes one instance shape (use Context.verify_batch for mixed shapes)")
         flats.append(f)
     return b"".join(bytes(p) for p in proofs), plen, b"".join(flats), lens0
+
+
+def _shard(ctx, proofs, instances, lo, hi):
+    """Proofs [lo, hi) of a batch in the staged form -> (proofs_flat, proof_len, instances_flat, col_lens).  An empty shard still takes
+    part in the launch and the collectives: it brings the batch's proof length and instance shape, the context's for a batch of no proofs."""
+    flat, plen, iflat, lens = _flatten(proofs[lo:hi], instances[lo:hi])
+    if lens is None:
+        lens = _flatten(proofs[:1], instances[:1])[3] if len(proofs) else [0] * ctx.proof_shape()["n_instance_columns"]
+    if not plen:
+        plen = len(proofs[0]) if len(proofs) else ctx.proof_shape()["proof_len"]
+    return flat, plen, iflat, lens
 
 
 def _all_statuses(local, n, world, group, backend, device):
@@ -315,11 +323,7 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     if identify:
         _refuse_zero_draws(draws)
     lo, hi = shard_bounds(n, world, rank)
-    flat, plen, iflat, lens = _flatten(proofs[lo:hi], instances[lo:hi])
-    if lens is None:                       # an empty shard still takes part in the collectives
-        _, _, _, lens = _flatten(proofs[:1], instances[:1]) if n else (b"", 0, b"", [0] * ctx.proof_shape()["n_instance_columns"])
-    if not plen:
-        plen = len(proofs[0]) if n else ctx.proof_shape()["proof_len"]
+    flat, plen, iflat, lens = _shard(ctx, proofs, instances, lo, hi)
     sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), group=group, device=device, batch_factory=batch_factory)
     try:
         sb.upload(flat, plen, iflat, lens, tail_for_shard(draws, lo))
@@ -364,10 +368,7 @@ def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_f
     try:
         for r in range(world):
             lo, hi = shard_bounds(n, world, r)
-            flat, plen, iflat, lens = _flatten(proofs[lo:hi], instances[lo:hi])
-            if lens is None:
-                _, _, _, lens = _flatten(proofs[:1], instances[:1])
-                plen = len(proofs[0])
+            flat, plen, iflat, lens = _shard(ctx, proofs, instances, lo, hi)
             sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), device=device, batch_factory=batch_factory, world_size=world)
             shards.append(sb)
             sb.upload(flat, plen, iflat, lens, tail_for_shard(draws, lo))

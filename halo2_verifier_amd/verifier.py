@@ -6,6 +6,8 @@ poly/kzg/commitment.rs:22-29, plonk/vk.rs:16-26, helpers.rs:7-19, plonk/mod.rs:1
 ``SingleStrategy``, and the ``Error`` variants as ``PlonkError``.  All arithmetic happens in the HIP
 library; this file only marshals bytes.
 """
+import collections
+import contextlib
 import ctypes
 import enum
 
@@ -142,11 +144,6 @@ def _sizes(values):
     return (ctypes.c_size_t * max(len(values), 1))(*values)
 
 
-def _col_lens(shapes, ncols):
-    """The column lengths of a call whose proofs share one instance shape: shapes[0], or ncols empty columns for no proofs."""
-    return _sizes(shapes[0] if shapes else [0] * ncols)
-
-
 def _rand_bytes(rand, n):
     """The draws of a one-shot call as n 32-byte scalars, or None (the library draws them)."""
     if rand is None:
@@ -156,27 +153,59 @@ def _rand_bytes(rand, n):
     return b"".join(_scalar32(r) for r in rand)
 
 
+def _channel(side, what=""):
+    """One channel of a DualMSM given as (scalars, bases) -> (scalar bytes, base bytes, n), the triple the seeded entry points and
+    h2v_accumulator_add_msm take; everything the C side indexes is checked here.  what: "seed " in the messages of a seed's channels."""
+    scalars, bases = side
+    scalars, bases = list(scalars), list(bases)
+    if len(scalars) != len(bases):
+        raise ValueError(f"{what}scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
+    if any(not isinstance(b, (bytes, bytearray, memoryview)) or len(b) != 64 for b in bases):
+        raise ValueError(f"every {what}base must be 64 bytes (x | y)")
+    return b"".join(_scalar32(x) for x in scalars), b"".join(bytes(b) for b in bases), len(scalars)
+
+
 def _seed_sides(seed):
-    """The two channels of a seed DualMSM, ((left_scalars, left_bases), (right_scalars, right_bases)), as the (scalar bytes, base bytes,
-    n) triples the seeded entry points take"""
-    sides = []
-    for scalars, bases in seed:
-        scalars, bases = list(scalars), list(bases)
-        if len(scalars) != len(bases):
-            raise ValueError("seed scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
-        if any(len(b) != 64 for b in bases):
-            raise ValueError("every seed base must be 64 bytes (x | y)")
-        sides.append((b"".join(_scalar32(x) for x in scalars), b"".join(bases), len(scalars)))
+    """The two channels of a seed DualMSM, ((left_scalars, left_bases), (right_scalars, right_bases)), as the six arguments the seeded
+    entry points take"""
+    sides = [_channel(side, "seed ") for side in seed]
     if len(sides) != 2:
         raise ValueError("a seed is (left, right)")
-    return sides
+    return sides[0] + sides[1]
+
+
+def _points(buf, k):
+    """k 64-byte points (x | y) out of a result buffer"""
+    raw = buf.raw
+    return [raw[64 * i:64 * i + 64] for i in range(k)]
+
+
+class _Marshalled(collections.namedtuple("_Marshalled", "n proofs proof_lens instances shapes ncols keys keep")):
+    """What _marshal_batch returns: proof pointers and lengths, instance pointers, the per-proof column lengths [n][ncols], the column
+    count of every key, the key index of every proof and the keep-alive list."""
+
+    @property
+    def head(self):
+        """(n, proofs, proof_lens, instances32): the arguments every one-shot entry point takes in a row"""
+        return self[:4]
+
+    @property
+    def uniform(self):
+        return all(l == self.shapes[0] for l in self.shapes)
+
+    def shape0(self):
+        """The column lengths of a call whose proofs share one instance shape: proof 0's, or empty columns for no proofs."""
+        return _sizes(self.shapes[0] if self.shapes else [0] * self.ncols[0])
+
+    def per_proof(self):
+        """The column lengths proof by proof."""
+        return _sizes(v for l in self.shapes for v in l)
 
 
 def _marshal_batch(contexts, proofs, instances, key_of_proof=None):
     """Pointer arrays for the one-shot calls.  Everything the C side will index is checked here: one instance list per proof,
     proofs are bytes, key indices are in range, every scalar is 32 bytes, the proofs of a key have one column count.  Proof i
-    belongs to contexts[key_of_proof[i]] (None: to contexts[0]).  Returns (n, proof ptrs, proof lens, instance ptrs, per-proof
-    column lengths [n][ncols], the column count of every key, keep-alive list)."""
+    belongs to contexts[key_of_proof[i]] (None: to contexts[0]).  -> _Marshalled."""
     n = len(proofs)
     if len(instances) != n:
         raise ValueError(f"{n} proofs but {len(instances)} instance lists: verify_proof takes one per proof (lib.rs:33-49)")
@@ -203,7 +232,54 @@ def _marshal_batch(contexts, proofs, instances, key_of_proof=None):
     PA = ctypes.c_char_p * max(n, 1)
     pa = PA(*[bytes(p) for p in proofs]) if n else PA()
     ia = PA(*flats) if n else PA()
-    return n, pa, _sizes(len(p) for p in proofs), ia, shapes, ncols, flats
+    return _Marshalled(n, pa, _sizes(len(p) for p in proofs), ia, shapes, ncols, keys, flats)
+
+
+class _Results:
+    """The outputs of a one-shot call over n proofs: statuses, verdict, the two evaluated channels, and for the identifying entry points
+    the number of range checks and the seed's own verdict."""
+
+    def __init__(self, n):
+        self.n = n
+        self.st = (ctypes.c_int * max(n, 1))()
+        self.ok = ctypes.c_int(0)
+        self.left, self.right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+        self.checks, self.seed_ok = ctypes.c_size_t(0), ctypes.c_int(1)
+
+    @property
+    def statuses(self):
+        return list(self.st)[:self.n]
+
+    def result(self):
+        """(batch_ok, statuses, left_xy, right_xy)"""
+        return bool(self.ok.value), self.statuses, self.left.raw, self.right.raw
+
+
+def _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context=False):
+    """The arguments h2v_verify_batch_keys, h2v_verify_batch_keys_identify and h2v_accumulator_process share, from the contexts to the
+    draws, checked -> (tuple of arguments, contexts, key_of_proof or None).  bare_context: a single Context with key_of_proof=None is
+    accepted as the one-key form (Accumulator.process), and the draws are refused before the proofs are looked at, as that call always did."""
+    one_key = bare_context and isinstance(contexts, Context)
+    if one_key:
+        if key_of_proof is not None:
+            raise ValueError("a single Context takes key_of_proof=None")
+        contexts = [contexts]
+    else:
+        contexts = list(contexts)
+        if bare_context and key_of_proof is None:
+            raise ValueError("a list of contexts takes one key index per proof")
+    n = len(proofs)
+    if (not one_key and len(key_of_proof) != n) or len(instances) != n:
+        raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {n if one_key else len(key_of_proof)} and {len(instances)}")
+    if not contexts:
+        raise ValueError("at least one context")
+    rb = _rand_bytes(rand, n) if bare_context else None
+    m = _marshal_batch(contexts, proofs, instances, key_of_proof)
+    if not bare_context:
+        rb = _rand_bytes(rand, n)
+    ka = (ctypes.c_uint32 * max(n, 1))(*m.keys)
+    ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
+    return (ca, len(contexts), ka, *m.head, _sizes(m.ncols), m.per_proof(), rb), contexts, None if one_key else m.keys
 
 
 class Context:
@@ -222,6 +298,13 @@ class Context:
         check(self._lib.h2v_ctx_create_ex(params.data, len(params.data), int(params.format), vkb, len(vkb) if vkb else 0,
                                           int(vk.format) if vk is not None else 0, device, ctypes.byref(opts), ctypes.byref(self._h)))
         self.params, self.vk, self.device = params, vk, device
+
+    def _adopt(self, obj):
+        """A batch or an accumulator that lives on this context: close() closes it first"""
+        if not hasattr(self, "_batches"):
+            import weakref
+            self._batches = weakref.WeakSet()
+        self._batches.add(obj)
 
     def close(self):
         if self._h:
@@ -287,23 +370,20 @@ class Context:
         seed: an existing accumulator to start from — AccumulatorStrategy::with (kzg/strategy.rs:75-78) — as
         ((left_scalars, left_bases), (right_scalars, right_bases)): scalars ints / 32-byte strings, bases 64-byte x | y.
         Returns (batch_ok, statuses, left_xy, right_xy)."""
-        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
-        rb = _rand_bytes(rand, n)
-        st = (ctypes.c_int * max(n, 1))()
-        ok = ctypes.c_int(0)
-        left = ctypes.create_string_buffer(64)
-        right = ctypes.create_string_buffer(64)
+        m = _marshal_batch([self], proofs, instances)
+        rb = _rand_bytes(rand, m.n)
+        r = _Results(m.n)
+        outs = (r.st, ctypes.byref(r.ok), r.left, r.right)
         if seed is not None:
-            if not all(l == shapes[0] for l in shapes):
+            if not m.uniform:
                 raise ValueError("a seeded batch takes one instance shape")
             sides = _seed_sides(seed)
-            check(self._lib.h2v_verify_batch_seeded(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, *sides[0], *sides[1], st, ctypes.byref(ok),
-                                                    left, right))
-        elif all(l == shapes[0] for l in shapes):
-            check(self._lib.h2v_verify_batch(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right))
+            check(self._lib.h2v_verify_batch_seeded(self._h, *m.head, m.ncols[0], m.shape0(), rb, *sides, *outs))
+        elif m.uniform:
+            check(self._lib.h2v_verify_batch(self._h, *m.head, m.ncols[0], m.shape0(), rb, *outs))
         else:
-            check(self._lib.h2v_verify_batch_shapes(self._h, n, pa, pl, ia, ncols, _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok), left, right))
-        return bool(ok.value), list(st)[:n], left.raw, right.raw
+            check(self._lib.h2v_verify_batch_shapes(self._h, *m.head, m.ncols[0], m.per_proof(), rb, *outs))
+        return r.result()
 
     def verify_batch_identify(self, proofs, instances, rand=None, seed=None):
         """verify_batch plus the proofs that made it fail (h2v_verify_batch_identify).  Returns (batch_ok, statuses, left_xy, right_xy):
@@ -312,34 +392,31 @@ class Context:
         self.last_range_checks.
         seed: as verify_batch's (h2v_verify_batch_seeded_identify).  The seed enters no proof's check; self.last_seed_ok says whether
         the seed alone passes the pairing (True without a seed, and for an empty one)."""
-        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
-        if not all(l == shapes[0] for l in shapes):
+        m = _marshal_batch([self], proofs, instances)
+        if not m.uniform:
             raise ValueError("verify_batch_identify takes one instance shape per call")
-        rb = _rand_bytes(rand, n)
-        st = (ctypes.c_int * max(n, 1))()
-        ok = ctypes.c_int(0)
-        left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
-        checks = ctypes.c_size_t(0)
-        seed_ok = ctypes.c_int(1)
+        rb = _rand_bytes(rand, m.n)
+        r = _Results(m.n)
         if seed is not None:
             sides = _seed_sides(seed)
-            check(self._lib.h2v_verify_batch_seeded_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, *sides[0], *sides[1], st, ctypes.byref(ok),
-                                                             ctypes.byref(seed_ok), left, right, ctypes.byref(checks)))
+            check(self._lib.h2v_verify_batch_seeded_identify(self._h, *m.head, m.ncols[0], m.shape0(), rb, *sides, r.st, ctypes.byref(r.ok),
+                                                             ctypes.byref(r.seed_ok), r.left, r.right, ctypes.byref(r.checks)))
         else:
-            check(self._lib.h2v_verify_batch_identify(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), rb, st, ctypes.byref(ok), left, right, ctypes.byref(checks)))
-        self.last_range_checks, self.last_seed_ok = checks.value, bool(seed_ok.value)
-        return bool(ok.value), list(st)[:n], left.raw, right.raw
+            check(self._lib.h2v_verify_batch_identify(self._h, *m.head, m.ncols[0], m.shape0(), rb, r.st, ctypes.byref(r.ok), r.left, r.right,
+                                                      ctypes.byref(r.checks)))
+        self.last_range_checks, self.last_seed_ok = r.checks.value, bool(r.seed_ok.value)
+        return r.result()
 
     def verify_each(self, proofs, instances):
-        n, pa, pl, ia, shapes, (ncols,), _keep = _marshal_batch([self], proofs, instances)
-        st = (ctypes.c_int * max(n, 1))()
-        if all(l == shapes[0] for l in shapes):
-            check(self._lib.h2v_verify_each(self._h, n, pa, pl, ia, ncols, _col_lens(shapes, ncols), st))
-            return list(st)[:n]
+        m = _marshal_batch([self], proofs, instances)
+        if m.uniform:
+            r = _Results(m.n)
+            check(self._lib.h2v_verify_each(self._h, *m.head, m.ncols[0], m.shape0(), r.st))
+            return r.statuses
         # SingleStrategy proofs are independent: run every instance shape as its own call and put the statuses back in order
-        out = [0] * n
+        out = [0] * m.n
         by_shape = {}
-        for i, l in enumerate(shapes):
+        for i, l in enumerate(m.shapes):
             by_shape.setdefault(tuple(l), []).append(i)
         for l, idx in by_shape.items():
             sub = self.verify_each([proofs[i] for i in idx], [instances[i] for i in idx])
@@ -393,39 +470,7 @@ class AccumulatorStrategy(_Strategy):
         evaluated channels and `last_range_checks` the number of range checks the search ran.  The draws must be non-zero.
         A seeded accumulation (with_accumulator) takes proofs of one VerifyingKey and one instance shape, as finalize() does; the seed
         enters no proof's check, and `last_seed_ok` says whether the seed alone passes the pairing."""
-        n = len(self._items)
-        rand = self.rand
-        if rand is not None and len(rand) != n:
-            raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
-        self.last_seed_ok = True
-        if not self._items:   # (as finalize())
-            self.statuses, self.last_range_checks = [], 0
-            return True
-        keys = {}
-        for vk, _, _ in self._items:
-            keys.setdefault((vk.data, int(vk.format)), vk)
-        if self.seed is not None:
-            if len(keys) != 1:
-                raise ValueError("a seeded accumulation takes proofs of one VerifyingKey")
-            ctx = Context(self.params, self._items[0][0], self.device, circuit_instances=self.circuit_instances)
-            try:
-                ok, self.statuses, self.left_xy, self.right_xy = ctx.verify_batch_identify([p for _, _, p in self._items], [i for _, i, _ in self._items], rand,
-                                                                                           seed=self.seed)
-                self.last_range_checks, self.last_seed_ok = ctx.last_range_checks, ctx.last_seed_ok
-                return ok
-            finally:
-                ctx.close()
-        index = {key: k for k, key in enumerate(keys)}
-        ctxs = []
-        try:
-            for vk in keys.values():
-                ctxs.append(Context(self.params, vk, self.device, circuit_instances=self.circuit_instances))
-            ok, self.statuses, self.left_xy, self.right_xy, self.last_range_checks = verify_batch_keys_identify(
-                ctxs, [index[(vk.data, int(vk.format))] for vk, _, _ in self._items], [p for _, _, p in self._items], [i for _, i, _ in self._items], rand)
-            return ok
-        finally:
-            for c in ctxs:
-                c.close()
+        return self._finalize(identify=True)
 
     def finalize(self) -> bool:
         """One pairing for everything that was accumulated.  verify_proof takes a VK per call and one strategy may accumulate
@@ -433,35 +478,49 @@ class AccumulatorStrategy(_Strategy):
         every VK gets its own context, and h2v_verify_batch_keys runs them all with the draws indexed by call order over ALL
         queued proofs (proof i is scaled by the product of the draws of all later proofs, whatever their VK) into one pairing.
         left_xy / right_xy hold the evaluated channels afterwards."""
-        if not self._items:
-            return True  # empty DualMSM: both channels are the identity, e(0,..)e(0,..) == 1
-        n = len(self._items)
-        rand = self.rand
-        if rand is not None and len(rand) != n:
-            raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
-        keys = {}
+        return self._finalize(identify=False)
+
+    @contextlib.contextmanager
+    def _contexts(self):
+        """The queued proofs grouped by VerifyingKey: a context per key, open for the block -> (contexts, the key index of every proof)"""
+        index = {}
         for vk, _, _ in self._items:
-            keys.setdefault((vk.data, int(vk.format)), vk)
-        if len(keys) == 1:
-            ctx = Context(self.params, self._items[0][0], self.device, circuit_instances=self.circuit_instances)
-            try:
-                ok, _, self.left_xy, self.right_xy = ctx.verify_batch([p for _, _, p in self._items], [i for _, i, _ in self._items], rand, seed=self.seed)
-                return ok
-            finally:
-                ctx.close()
-        if self.seed is not None:
+            index.setdefault((vk.data, int(vk.format)), (len(index), vk))
+        if self.seed is not None and len(index) != 1:
             raise ValueError("a seeded accumulation takes proofs of one VerifyingKey")
-        index = {key: k for k, key in enumerate(keys)}
         ctxs = []
         try:
-            for vk in keys.values():
+            for _, vk in index.values():
                 ctxs.append(Context(self.params, vk, self.device, circuit_instances=self.circuit_instances))
-            ok, _, self.left_xy, self.right_xy = verify_batch_keys(ctxs, [index[(vk.data, int(vk.format))] for vk, _, _ in self._items],
-                                                                   [p for _, _, p in self._items], [i for _, i, _ in self._items], rand)
-            return ok
+            yield ctxs, [index[(vk.data, int(vk.format))][0] for vk, _, _ in self._items]
         finally:
             for c in ctxs:
                 c.close()
+
+    def _finalize(self, identify):
+        n = len(self._items)
+        if not n and not identify:
+            return True  # empty DualMSM: both channels are the identity, e(0,..)e(0,..) == 1
+        rand = self.rand
+        if rand is not None and len(rand) != n:
+            raise ValueError(f"rand must hold one scalar per accumulated proof ({n}), got {len(rand)}")
+        if identify:
+            self.last_seed_ok = True
+            if not n:   # (as finalize())
+                self.statuses, self.last_range_checks = [], 0
+                return True
+        proofs, instances = [p for _, _, p in self._items], [i for _, i, _ in self._items]
+        with self._contexts() as (ctxs, key_of_proof):
+            if not identify and len(ctxs) == 1:
+                ok, _, self.left_xy, self.right_xy = ctxs[0].verify_batch(proofs, instances, rand, seed=self.seed)
+            elif not identify:
+                ok, _, self.left_xy, self.right_xy = verify_batch_keys(ctxs, key_of_proof, proofs, instances, rand)
+            elif self.seed is not None:
+                ok, self.statuses, self.left_xy, self.right_xy = ctxs[0].verify_batch_identify(proofs, instances, rand, seed=self.seed)
+                self.last_range_checks, self.last_seed_ok = ctxs[0].last_range_checks, ctxs[0].last_seed_ok
+            else:   # (one key too: h2v_verify_batch_keys_identify takes any instance shapes)
+                ok, self.statuses, self.left_xy, self.right_xy, self.last_range_checks = verify_batch_keys_identify(ctxs, key_of_proof, proofs, instances, rand)
+            return ok
 
 
 class SingleStrategy(_Strategy):
@@ -503,23 +562,10 @@ def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None):
     finalize() (h2v_verify_batch_keys): contexts[k] holds key k, proof i belongs to contexts[key_of_proof[i]].  instances: per
     proof, list of columns (shapes may differ from proof to proof; every proof of a key has that key's column count).  rand: n
     draws in call order, or None.  Returns (batch_ok, statuses, left_xy, right_xy)."""
-    contexts = list(contexts)
-    n = len(proofs)
-    if len(key_of_proof) != n or len(instances) != n:
-        raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {len(key_of_proof)} and {len(instances)}")
-    if not contexts:
-        raise ValueError("at least one context")
-    lib = _lib.load_library()
-    n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
-    rb = _rand_bytes(rand, n)
-    ka = (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])
-    ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
-    st = (ctypes.c_int * max(n, 1))()
-    ok = ctypes.c_int(0)
-    left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
-    check(lib.h2v_verify_batch_keys(ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok),
-                                    left, right))
-    return bool(ok.value), list(st)[:n], left.raw, right.raw
+    args, _, _ = _keyed_args(contexts, key_of_proof, proofs, instances, rand)
+    r = _Results(len(proofs))
+    check(_lib.load_library().h2v_verify_batch_keys(*args, r.st, ctypes.byref(r.ok), r.left, r.right))
+    return r.result()
 
 
 def verify_batch_keys_identify(contexts, key_of_proof, proofs, instances, rand=None):
@@ -527,35 +573,10 @@ def verify_batch_keys_identify(contexts, key_of_proof, proofs, instances, rand=N
     (several keys, per-proof instance shapes); rand: n non-zero draws in call order, or None.  Returns (batch_ok, statuses, left_xy,
     right_xy, range_checks): batch_ok / left_xy / right_xy are what verify_batch_keys returns for the same arguments, statuses[i] is what
     contexts[key_of_proof[i]].verify_each returns for proof i, range_checks the number of range checks the search ran."""
-    contexts = list(contexts)
-    n = len(proofs)
-    if len(key_of_proof) != n or len(instances) != n:
-        raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {len(key_of_proof)} and {len(instances)}")
-    if not contexts:
-        raise ValueError("at least one context")
-    lib = _lib.load_library()
-    n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
-    rb = _rand_bytes(rand, n)
-    ka = (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])
-    ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
-    st = (ctypes.c_int * max(n, 1))()
-    ok = ctypes.c_int(0)
-    left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
-    checks = ctypes.c_size_t(0)
-    check(lib.h2v_verify_batch_keys_identify(ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), _sizes(v for l in shapes for v in l), rb, st, ctypes.byref(ok),
-                                             left, right, ctypes.byref(checks)))
-    return bool(ok.value), list(st)[:n], left.raw, right.raw, checks.value
-
-
-def _seed_side(side):
-    """One channel of a DualMSM given as (scalars, bases) -> (scalar bytes, base bytes, n); everything the C side indexes is checked here"""
-    scalars, bases = side
-    scalars, bases = list(scalars), list(bases)
-    if len(scalars) != len(bases):
-        raise ValueError("scalars and bases differ in length")   # MSMKZG keeps them parallel (msm.rs:17-24)
-    if any(not isinstance(b, (bytes, bytearray)) or len(b) != 64 for b in bases):
-        raise ValueError("every base must be 64 bytes (x | y)")
-    return b"".join(_scalar32(x) for x in scalars), b"".join(bytes(b) for b in bases), len(scalars)
+    args, _, _ = _keyed_args(contexts, key_of_proof, proofs, instances, rand)
+    r = _Results(len(proofs))
+    check(_lib.load_library().h2v_verify_batch_keys_identify(*args, r.st, ctypes.byref(r.ok), r.left, r.right, ctypes.byref(r.checks)))
+    return r.result() + (r.checks.value,)
 
 
 class Accumulator:
@@ -578,10 +599,7 @@ class Accumulator:
         self.ctx, self._lib = context, context._lib
         self._h = ctypes.c_void_p()
         check(self._lib.h2v_accumulator_create(context._h, ctypes.byref(self._h)))
-        if not hasattr(context, "_batches"):
-            import weakref
-            context._batches = weakref.WeakSet()
-        context._batches.add(self)   # Context.close() closes what lives on it first
+        context._adopt(self)
         self.last_all_ok = True
         self._keep_inputs = bool(keep_inputs)
         self._inputs = []   # with keep_inputs: one item per journal entry, None for the base and for add_msm entries
@@ -612,39 +630,18 @@ class Accumulator:
         contexts[key_of_proof[i]]; a single Context with key_of_proof=None is the one-key form.  instances / rand as verify_batch_keys.
         Returns the statuses of this call's proofs; `last_all_ok` says whether all are 0.  A call that raises H2VError leaves the
         accumulator as it was."""
-        one_key = isinstance(contexts, Context)
-        if one_key:
-            if key_of_proof is not None:
-                raise ValueError("a single Context takes key_of_proof=None")
-            contexts = [contexts]
-        else:
-            contexts = list(contexts)
-            if key_of_proof is None:
-                raise ValueError("a list of contexts takes one key index per proof")
-        n = len(proofs)
-        if (not one_key and len(key_of_proof) != n) or len(instances) != n:
-            raise ValueError(f"{n} proofs need {n} key indices and {n} instance lists, got {n if one_key else len(key_of_proof)} and {len(instances)}")
-        if not contexts:
-            raise ValueError("at least one context")
-        rb = _rand_bytes(rand, n)
-        n, pa, pl, ia, shapes, ncols, _keep = _marshal_batch(contexts, proofs, instances, key_of_proof)
-        ka = (ctypes.c_uint32 * max(n, 1))() if one_key else (ctypes.c_uint32 * max(n, 1))(*[int(k) for k in key_of_proof])   # (one key: every index 0)
-        ca = (ctypes.c_void_p * len(contexts))(*[c._h.value for c in contexts])
-        # column lengths proof by proof (a leg of one shape: that shape n times)
-        col_lens = _sizes(shapes[0] * n if n and all(l == shapes[0] for l in shapes) else [v for l in shapes for v in l])
-        st = (ctypes.c_int * max(n, 1))()
-        ok = ctypes.c_int(0)
-        check(self._lib.h2v_accumulator_process(self._h, ca, len(contexts), ka, n, pa, pl, ia, _sizes(ncols), col_lens, rb, st,
-                                                ctypes.byref(ok)))
-        self.last_all_ok = bool(ok.value)
-        if n and self._inputs:   # (journal on: the call has appended an entry)
-            self._inputs.append((contexts, None if one_key else [int(k) for k in key_of_proof], list(proofs), list(instances)) if self._keep_inputs else None)
-        return list(st)[:n]
+        args, contexts, keys = _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context=True)
+        r = _Results(len(proofs))
+        check(self._lib.h2v_accumulator_process(self._h, *args, r.st, ctypes.byref(r.ok)))
+        self.last_all_ok = bool(r.ok.value)
+        if r.n and self._inputs:   # (journal on: the call has appended an entry)
+            self._inputs.append((contexts, keys, list(proofs), list(instances)) if self._keep_inputs else None)
+        return r.statuses
 
     def add_msm(self, left, right):
         """(L, R) += the two term lists evaluated, unscaled (h2v_accumulator_add_msm: AccumulatorStrategy::with on an empty accumulator,
         DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""
-        l, r = _seed_side(left), _seed_side(right)
+        l, r = _channel(left), _channel(right)
         check(self._lib.h2v_accumulator_add_msm(self._h, *l, *r))
         if self._inputs:
             self._inputs.append(None)
@@ -719,6 +716,21 @@ class Accumulator:
         return out
 
 
+def _range_args(ranges, names, types):
+    """Ranges as tuples of ints, all of one layout -> (k, their columns as arrays of `types`, the result buffers of k range checks)"""
+    for r in ranges:   # (uint32 / size_t on the C side: a negative value would wrap around; the library checks the rest)
+        if min(r) < 0:
+            raise ValueError(f"range {r}: {names} must be non-negative")
+    k = len(ranges)
+    columns = [(t * max(k, 1))(*[r[j] for r in ranges]) for j, t in enumerate(types)]
+    return k, columns, ((ctypes.c_int * max(k, 1))(), ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1)))
+
+
+def _range_results(k, ok, left, right):
+    """-> (oks, lefts, rights) of k range checks"""
+    return [bool(v) for v in ok][:k], _points(left, k), _points(right, k)
+
+
 def recheck_batches(batches, ranges):
     """Batch.recheck over ranges of several finished batches in one set of launches (h2v_batches_recheck).  batches: Batch objects on
     one device over the same params (keys and shapes may differ); ranges: list of (batch_index, first, count), each inside one group of
@@ -726,21 +738,11 @@ def recheck_batches(batches, ranges):
     batches = list(batches)
     if not batches:
         raise ValueError("at least one batch")
-    ranges = [(int(b), int(f), int(c)) for b, f, c in ranges]
-    for b, f, c in ranges:   # (uint32 / size_t on the C side: a negative value would wrap around; the library checks the rest)
-        if b < 0 or f < 0 or c < 0:
-            raise ValueError(f"range ({b}, {f}, {c}): the batch index, first and count must be non-negative")
-    lib = batches[0]._lib
-    k = len(ranges)
+    k, columns, out = _range_args([(int(b), int(f), int(c)) for b, f, c in ranges], "the batch index, first and count",
+                                  (ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t))
     ba = (ctypes.c_void_p * len(batches))(*[b._h.value for b in batches])
-    bor = (ctypes.c_uint32 * max(k, 1))(*[b for b, _, _ in ranges])
-    first = (ctypes.c_size_t * max(k, 1))(*[f for _, f, _ in ranges])
-    count = (ctypes.c_size_t * max(k, 1))(*[c for _, _, c in ranges])
-    ok = (ctypes.c_int * max(k, 1))()
-    left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
-    check(lib.h2v_batches_recheck(ba, len(batches), k, bor, first, count, ok, left, right))
-    lr, rr = left.raw, right.raw
-    return [bool(v) for v in ok][:k], [lr[64 * i:64 * i + 64] for i in range(k)], [rr[64 * i:64 * i + 64] for i in range(k)]
+    check(batches[0]._lib.h2v_batches_recheck(ba, len(batches), k, *columns, *out))
+    return _range_results(k, *out)
 
 
 class Batch:
@@ -753,10 +755,7 @@ class Batch:
         self.ctx, self._lib = ctx, ctx._lib
         self._h = ctypes.c_void_p()
         check(self._lib.h2v_batch_create(ctx._h, max_proofs, max_instance_values, ctypes.byref(self._h)))
-        if not hasattr(ctx, "_batches"):
-            import weakref
-            ctx._batches = weakref.WeakSet()
-        ctx._batches.add(self)
+        ctx._adopt(self)
         self.max_proofs = max_proofs
         self.n = 0
         self.groups = 1
@@ -789,11 +788,10 @@ class Batch:
     def stream(self) -> int:
         return self._lib.h2v_batch_stream(self._h) or 0
 
-    def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None):
-        """proofs_flat: n * proof_len bytes; instances_flat: n * sum(col_lens) * 32 bytes;
-        rand_tail: bytes of the Fr::random draws of proofs [first, total) of the whole batch (>= n scalars) or None."""
+    def _upload_args(self, proofs_flat, proof_len, instances_flat, col_lens, rand_tail):
+        """The arguments h2v_batch_upload and h2v_batch_upload_launch share, n first.  The C side reads n * proof_len,
+        n * sum(col_lens) * 32 and n_tail * 32 bytes: the buffers must hold exactly that."""
         n = len(proofs_flat) // proof_len if proof_len else 0
-        # the C side reads n * proof_len, n * sum(col_lens) * 32 and n_tail * 32 bytes: the buffers must hold exactly that
         if proof_len and len(proofs_flat) != n * proof_len:
             raise ValueError("proofs_flat is not a whole number of proofs")
         if len(instances_flat) != n * sum(col_lens) * 32:
@@ -802,25 +800,23 @@ class Batch:
             raise ValueError("rand_tail is not a whole number of 32-byte scalars")
         cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
         nt = len(rand_tail) // 32 if rand_tail is not None else 0
-        check(self._lib.h2v_batch_upload(self._h, n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt))
-        self.n = n
+        return n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt
+
+    def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None):
+        """proofs_flat: n * proof_len bytes; instances_flat: n * sum(col_lens) * 32 bytes;
+        rand_tail: bytes of the Fr::random draws of proofs [first, total) of the whole batch (>= n scalars) or None."""
+        args = self._upload_args(proofs_flat, proof_len, instances_flat, col_lens, rand_tail)
+        check(self._lib.h2v_batch_upload(self._h, *args))
+        self.n = args[0]
 
     def launch(self, with_pairing=True):
         check(self._lib.h2v_batch_launch(self._h, 1 if with_pairing else 0))
 
     def upload_launch(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None, with_pairing=True):
         """upload() + launch() with the host -> device copy hidden behind the point decompression (h2v_batch_upload_launch)."""
-        n = len(proofs_flat) // proof_len if proof_len else 0
-        if proof_len and len(proofs_flat) != n * proof_len:
-            raise ValueError("proofs_flat is not a whole number of proofs")
-        if len(instances_flat) != n * sum(col_lens) * 32:
-            raise ValueError(f"instances_flat must be n * sum(col_lens) * 32 = {n * sum(col_lens) * 32} bytes, got {len(instances_flat)}")
-        if rand_tail is not None and len(rand_tail) % 32:
-            raise ValueError("rand_tail is not a whole number of 32-byte scalars")
-        cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
-        nt = len(rand_tail) // 32 if rand_tail is not None else 0
-        check(self._lib.h2v_batch_upload_launch(self._h, n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt, 1 if with_pairing else 0))
-        self.n = n
+        args = self._upload_args(proofs_flat, proof_len, instances_flat, col_lens, rand_tail)
+        check(self._lib.h2v_batch_upload_launch(self._h, *args, 1 if with_pairing else 0))
+        self.n = args[0]
 
     def export_accumulators(self, device_dst: int):
         check(self._lib.h2v_batch_export_accumulators(self._h, ctypes.c_void_p(device_dst)))
@@ -845,26 +841,16 @@ class Batch:
         ok = (ctypes.c_int * g)()
         left, right = ctypes.create_string_buffer(64 * g), ctypes.create_string_buffer(64 * g)
         check(self._lib.h2v_batch_finish_groups(self._h, st, ok, left, right, g))
-        lr, rr = left.raw, right.raw
         statuses = bytes(memoryview(st).cast('B')[:4 * self.n]) if raw_statuses else memoryview(st).cast('B').cast('i').tolist()[:self.n]
-        return ([bool(v) for v in ok], statuses, [lr[64 * i:64 * i + 64] for i in range(g)], [rr[64 * i:64 * i + 64] for i in range(g)])
+        return [bool(v) for v in ok], statuses, _points(left, g), _points(right, g)
 
     def recheck(self, ranges):
         """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
         ranges: list of (first, count), each inside one group of the launch.  -> (oks, lefts, rights): one verdict and the two
         evaluated channels (64-byte x | y) per range."""
-        ranges = [(int(f), int(c)) for f, c in ranges]
-        for f, c in ranges:   # (size_t on the C side: a negative value would wrap around; the library checks the rest)
-            if f < 0 or c < 0:
-                raise ValueError(f"range ({f}, {c}): first and count must be non-negative")
-        k = len(ranges)
-        first = (ctypes.c_size_t * max(k, 1))(*[f for f, _ in ranges])
-        count = (ctypes.c_size_t * max(k, 1))(*[c for _, c in ranges])
-        ok = (ctypes.c_int * max(k, 1))()
-        left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
-        check(self._lib.h2v_batch_recheck(self._h, k, first, count, ok, left, right))
-        lr, rr = left.raw, right.raw
-        return [bool(v) for v in ok][:k], [lr[64 * i:64 * i + 64] for i in range(k)], [rr[64 * i:64 * i + 64] for i in range(k)]
+        k, columns, out = _range_args([(int(f), int(c)) for f, c in ranges], "first and count", (ctypes.c_size_t, ctypes.c_size_t))
+        check(self._lib.h2v_batch_recheck(self._h, k, *columns, *out))
+        return _range_results(k, *out)
 
     def identify(self, own_records=None):
         """Which proofs of the last finished launch fail the pairing (h2v_batch_identify), whatever closed the launch: its own pairing,

@@ -80,32 +80,46 @@ private:
 };
 
 namespace detail {
-// pointer-array view of (proof, instances) pairs in the layout h2v_verify_batch / h2v_verify_each take
-struct Packed {
+// The arguments of a call in the layout the C ABI takes: a context per key, then every proof in call order with its key and its column
+// lengths.  The entry points over one context and one instance shape take key 0's column count and proof 0's shape (shape0()).
+struct Marshalled {
+    std::vector<h2v_ctx*> ctxs;
+    std::vector<size_t> ncols;                 // the instance column count of every key
+    std::vector<uint32_t> keys;                // the key of every proof
     std::vector<const uint8_t*> proofs, insts;
-    std::vector<size_t> lens, col_lens, col_lens_per_proof;   // col_lens: proof 0's shape; per proof: [n][cols]
-    bool uniform = true;                                        // every proof has proof 0's instance shape
+    std::vector<size_t> lens, col_lens;        // col_lens: proof by proof, ncols[key] entries each
+    bool uniform = true;                       // every proof has proof 0's key and instance shape
     std::vector<Bytes> flat;
-    Packed(const std::vector<std::pair<Instances, Bytes>>& items, size_t ncols_if_empty) {
-        for (const auto& it : items) {
-            Bytes f;
-            for (const Column& c : it.first) for (const Bytes& v : c) f.insert(f.end(), v.begin(), v.end());
-            flat.push_back(std::move(f));
-        }
-        for (size_t i = 0; i < items.size(); ++i) {
-            proofs.push_back(items[i].second.data()); lens.push_back(items[i].second.size()); insts.push_back(flat[i].data());
-        }
-        if (!items.empty()) for (const Column& c : items[0].first) col_lens.push_back(c.size());
-        else col_lens.assign(ncols_if_empty, 0);
-        for (const auto& it : items) {
-            if (it.first.size() != col_lens.size()) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
-            for (size_t c = 0; c < col_lens.size(); ++c) {
-                if (it.first[c].size() != col_lens[c]) uniform = false;      // verify_proof takes `instances` per call: shapes may differ
-                col_lens_per_proof.push_back(it.first[c].size());
-            }
-        }
+    // one_key: the calls over a single context hand proof 0's column count over and leave its judgement to the library
+    // (H2V_ERR_INVALID_INSTANCES, lib.rs:51-55); the later proofs must agree with it, as the proofs of every key must with the key's count
+    explicit Marshalled(bool one_key = false) : one_key_(one_key) {}
+    void add_key(h2v_ctx* ctx) {
+        ctxs.push_back(ctx);
+        ncols.push_back(0);
+        check(h2v_ctx_proof_shape(ctx, nullptr, nullptr, nullptr, nullptr, &ncols.back()));
     }
+    void add(uint32_t key, const Instances& inst, const Bytes& proof) {
+        if (key >= ctxs.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "key index out of range");
+        if (one_key_ && keys.empty()) ncols[0] = inst.size();
+        if (inst.size() != ncols[key]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
+        Bytes f;
+        for (size_t c = 0; c < inst.size(); ++c) {
+            if (!keys.empty() && (key != keys[0] || inst[c].size() != col_lens[c])) uniform = false;   // verify_proof takes `instances` per call: shapes may differ
+            col_lens.push_back(inst[c].size());
+            for (const Bytes& v : inst[c]) f.insert(f.end(), v.begin(), v.end());
+        }
+        flat.push_back(std::move(f));
+        keys.push_back(key); proofs.push_back(proof.data()); lens.push_back(proof.size()); insts.push_back(flat.back().data());
+    }
+    size_t n() const { return keys.size(); }
+    const size_t* shape0() { if (keys.empty()) col_lens.assign(ncols[0], 0); return col_lens.data(); }   // (no proofs: empty columns)
+
+private:
+    bool one_key_;
 };
+inline void check_channels(const Bytes& ls, const Bytes& lb, const Bytes& rs, const Bytes& rb, const char* what) {
+    if (ls.size() % 32 || lb.size() != 2 * ls.size() || rs.size() % 32 || rb.size() != 2 * rs.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, what);
+}
 }  // namespace detail
 
 // kzg/strategy.rs:99-141: verify_proof() adds a proof to the accumulator, finalize() runs ONE pairing for all of them.
@@ -120,8 +134,7 @@ public:
     // its evaluated channels (left(), right()) as the single base of either side.
     static AccumulatorStrategy with(const ParamsKZG& p, Bytes left_scalars, Bytes left_bases, Bytes right_scalars, Bytes right_bases, int device = 0,
                                     MultiOpen mo = MultiOpen::SHPLONK, TranscriptKind tr = TranscriptKind::Blake2b, int circuit_instances = 1) {
-        if (left_scalars.size() % 32 || left_bases.size() != 2 * left_scalars.size() || right_scalars.size() % 32 || right_bases.size() != 2 * right_scalars.size())
-            throw Failure(H2V_ERR_BAD_ARGUMENT, "a seed channel is n 32-byte scalars and n 64-byte bases");
+        detail::check_channels(left_scalars, left_bases, right_scalars, right_bases, "a seed channel is n 32-byte scalars and n 64-byte bases");
         AccumulatorStrategy s(p, device, mo, tr, circuit_instances);
         s.seeded_ = true;
         s.seed_ls_ = std::move(left_scalars); s.seed_lb_ = std::move(left_bases); s.seed_rs_ = std::move(right_scalars); s.seed_rb_ = std::move(right_bases);
@@ -137,54 +150,16 @@ public:
         key_of_.push_back((uint32_t)k);
         items_.emplace_back(std::move(inst), std::move(proof));
     }
-    // -> true iff every verify_proof succeeded and the pairing check passed; statuses() then holds the per-proof plonk::Error
-    bool finalize() {
-        if (vks_.size() > 1) return finalize_keys();
-        Context ctx(params_, vk(), device_, mo_, tr_, ci_);
-        size_t ncols = 0;
-        check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
-        detail::Packed pk(items_, ncols);
-        statuses_.assign(items_.size() ? items_.size() : 1, 0);
-        int ok = 0;
-        if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
-        if (seeded_) {
-            if (!pk.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes one instance shape");
-            check(h2v_verify_batch_seeded(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
-                                          rand_.empty() ? nullptr : rand_.data(), seed_ls_.data(), seed_lb_.data(), seed_ls_.size() / 32, seed_rs_.data(), seed_rb_.data(),
-                                          seed_rs_.size() / 32, statuses_.data(), &ok, left_, right_));
-        } else if (pk.uniform)
-            check(h2v_verify_batch(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
-                                   rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
-        else
-            check(h2v_verify_batch_shapes(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens_per_proof.data(),
-                                          rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
-        statuses_.resize(items_.size());
-        return ok != 0;
-    }
+    // -> true iff every verify_proof succeeded and the pairing check passed; statuses() then holds the per-proof plonk::Error.
+    // Proofs of several VerifyingKeys: a context per key, every proof in call order (h2v_verify_batch_keys)
+    bool finalize() { return run(false, vks_.size() > 1); }
     // finalize() plus the proofs that made the batch fail (h2v_verify_batch_identify): returns what finalize() returns, and statuses()
     // then holds, for every proof, the plonk::Error SingleStrategy reports for it — ConstraintSystemFailure for the proofs whose own
     // pairing fails.  The draws must be non-zero.  One instance shape.  A seeded accumulation (with) runs
     // h2v_verify_batch_seeded_identify: the seed enters no proof's check, and seed_ok() says whether the seed alone passes the pairing.
     bool finalize_identify() {
         if (vks_.size() > 1) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes proofs of one VerifyingKey");
-        Context ctx(params_, vk(), device_, mo_, tr_, ci_);
-        size_t ncols = 0;
-        check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
-        detail::Packed pk(items_, ncols);
-        if (!pk.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes one instance shape");
-        if (!rand_.empty() && rand_.size() != 32 * items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
-        statuses_.assign(items_.size() ? items_.size() : 1, 0);
-        int ok = 0, seed_ok = 1;
-        if (seeded_)
-            check(h2v_verify_batch_seeded_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
-                                                   rand_.empty() ? nullptr : rand_.data(), seed_ls_.data(), seed_lb_.data(), seed_ls_.size() / 32, seed_rs_.data(),
-                                                   seed_rb_.data(), seed_rs_.size() / 32, statuses_.data(), &ok, &seed_ok, left_, right_, &range_checks_));
-        else
-            check(h2v_verify_batch_identify(ctx.handle(), items_.size(), pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(),
-                                            rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_, &range_checks_));
-        seed_ok_ = seed_ok != 0;
-        statuses_.resize(items_.size());
-        return ok != 0;
+        return run(true, false);
     }
     // finalize_identify() over one or several VerifyingKeys and any instance shapes (h2v_verify_batch_keys_identify): returns what
     // finalize() returns, statuses() then holds every proof's SingleStrategy verdict and range_checks() the re-checks the search ran.
@@ -193,14 +168,7 @@ public:
         if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes an accumulation without a seed");
         range_checks_ = 0;
         if (items_.empty()) { statuses_.clear(); return true; }   // an empty DualMSM: both channels are the identity
-        KeyCall kc(*this);
-        statuses_.assign(items_.size() ? items_.size() : 1, 0);
-        int ok = 0;
-        check(h2v_verify_batch_keys_identify(kc.handles.data(), kc.handles.size(), key_of_.data(), items_.size(), kc.proofs.data(), kc.lens.data(), kc.insts.data(),
-                                             kc.ncols.data(), kc.col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_,
-                                             &range_checks_));
-        statuses_.resize(items_.size());
-        return ok != 0;
+        return run(true, true);
     }
     bool seed_ok() const { return seed_ok_; }               // the last finalize_identify(): the seed alone passes the pairing (true without a seed)
     size_t range_checks() const { return range_checks_; }   // re-checks the last finalize_identify() or finalize_identify_keys() ran (0: the batch passed)
@@ -209,38 +177,53 @@ public:
     const uint8_t* right() const { return right_; }
 
 private:
-    VerifyingKey vk() const { return vks_.empty() ? VerifyingKey{} : vks_[0]; }
-    // The arguments of a call over several VerifyingKeys: a context per key, every proof in call order, column lengths proof by proof
-    struct KeyCall {
+    // Every finalizer.  keyed: the call over a context per VerifyingKey and per-proof shapes (h2v_verify_batch_keys*), else the call over
+    // one context (h2v_verify_batch*, which a strategy without proofs reaches with an empty key).  The keyed calls have always refused
+    // the draws before a context is made, the others after the proofs were looked at: kept.
+    bool run(bool identify, bool keyed) {
+        if (keyed && seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes proofs of one VerifyingKey");
+        const size_t n = items_.size();
+        const auto check_draws = [&] { if (!rand_.empty() && rand_.size() != 32 * n) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof"); };
+        if (keyed) check_draws();
         std::vector<std::unique_ptr<Context>> ctxs;
-        std::vector<h2v_ctx*> handles;
-        std::vector<size_t> ncols;
-        std::vector<const uint8_t*> proofs, insts;
-        std::vector<size_t> lens, col_lens;
-        std::vector<Bytes> flat;
-        explicit KeyCall(const AccumulatorStrategy& s) : ncols(s.vks_.size(), 0), flat(s.items_.size()) {
-            if (!s.rand_.empty() && s.rand_.size() != 32 * s.items_.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
-            for (size_t k = 0; k < s.vks_.size(); ++k) {
-                ctxs.emplace_back(new Context(s.params_, s.vks_[k], s.device_, s.mo_, s.tr_, s.ci_));
-                handles.push_back(ctxs.back()->handle());
-                check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
-            }
-            for (size_t i = 0; i < s.items_.size(); ++i) {
-                const Instances& inst = s.items_[i].first;
-                if (inst.size() != ncols[s.key_of_[i]]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
-                for (const Column& c : inst) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
-                proofs.push_back(s.items_[i].second.data()); lens.push_back(s.items_[i].second.size()); insts.push_back(flat[i].data());
-            }
+        detail::Marshalled m(!keyed);
+        for (const VerifyingKey& vk : vks_.empty() ? std::vector<VerifyingKey>(1) : vks_) {
+            ctxs.emplace_back(new Context(params_, vk, device_, mo_, tr_, ci_));
+            m.add_key(ctxs.back()->handle());
         }
-    };
-    // proofs of several VerifyingKeys: a context per key, every proof in call order (h2v_verify_batch_keys)
-    bool finalize_keys() {
-        if (seeded_) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes proofs of one VerifyingKey");
-        KeyCall kc(*this);
-        statuses_.assign(items_.size(), 0);
-        int ok = 0;
-        check(h2v_verify_batch_keys(kc.handles.data(), kc.handles.size(), key_of_.data(), items_.size(), kc.proofs.data(), kc.lens.data(), kc.insts.data(), kc.ncols.data(),
-                                    kc.col_lens.data(), rand_.empty() ? nullptr : rand_.data(), statuses_.data(), &ok, left_, right_));
+        for (size_t i = 0; i < n; ++i) m.add(key_of_[i], items_[i].first, items_[i].second);
+        if (!keyed) {
+            if (identify && !m.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "identification takes one instance shape");
+            check_draws();
+            if (seeded_ && !m.uniform) throw Failure(H2V_ERR_UNSUPPORTED, "a seeded accumulation takes one instance shape");
+        }
+        statuses_.assign(n ? n : 1, 0);
+        const uint8_t* rand = rand_.empty() ? nullptr : rand_.data();
+        const size_t n_ls = seed_ls_.size() / 32, n_rs = seed_rs_.size() / 32;
+        int ok = 0, seed_ok = 1;
+        if (keyed && identify)
+            check(h2v_verify_batch_keys_identify(m.ctxs.data(), m.ctxs.size(), m.keys.data(), n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols.data(),
+                                                 m.col_lens.data(), rand, statuses_.data(), &ok, left_, right_, &range_checks_));
+        else if (keyed)
+            check(h2v_verify_batch_keys(m.ctxs.data(), m.ctxs.size(), m.keys.data(), n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols.data(),
+                                        m.col_lens.data(), rand, statuses_.data(), &ok, left_, right_));
+        else if (identify && seeded_)
+            check(h2v_verify_batch_seeded_identify(m.ctxs[0], n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), rand, seed_ls_.data(),
+                                                   seed_lb_.data(), n_ls, seed_rs_.data(), seed_rb_.data(), n_rs, statuses_.data(), &ok, &seed_ok, left_, right_,
+                                                   &range_checks_));
+        else if (identify)
+            check(h2v_verify_batch_identify(m.ctxs[0], n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), rand, statuses_.data(), &ok,
+                                            left_, right_, &range_checks_));
+        else if (seeded_)
+            check(h2v_verify_batch_seeded(m.ctxs[0], n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), rand, seed_ls_.data(),
+                                          seed_lb_.data(), n_ls, seed_rs_.data(), seed_rb_.data(), n_rs, statuses_.data(), &ok, left_, right_));
+        else if (m.uniform)
+            check(h2v_verify_batch(m.ctxs[0], n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), rand, statuses_.data(), &ok, left_, right_));
+        else
+            check(h2v_verify_batch_shapes(m.ctxs[0], n, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.col_lens.data(), rand, statuses_.data(), &ok,
+                                          left_, right_));
+        if (identify && !keyed) seed_ok_ = seed_ok != 0;
+        statuses_.resize(n);
         return ok != 0;
     }
 
@@ -272,27 +255,13 @@ public:
     std::vector<int> process(const std::vector<const Context*>& contexts, const std::vector<Item>& items, const Bytes& rand32 = Bytes()) {
         if (contexts.empty()) throw Failure(H2V_ERR_BAD_ARGUMENT, "at least one context");
         if (!rand32.empty() && rand32.size() != 32 * items.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
-        std::vector<h2v_ctx*> handles;
-        std::vector<size_t> ncols(contexts.size(), 0);
-        for (size_t k = 0; k < contexts.size(); ++k) {
-            handles.push_back(contexts[k]->handle());
-            check(h2v_ctx_proof_shape(handles.back(), nullptr, nullptr, nullptr, nullptr, &ncols[k]));
-        }
-        std::vector<uint32_t> keys;
-        std::vector<const uint8_t*> proofs, insts;
-        std::vector<size_t> lens, col_lens;
-        std::vector<Bytes> flat(items.size());
-        for (size_t i = 0; i < items.size(); ++i) {
-            const Item& it = items[i];
-            if (it.key >= contexts.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "key index out of range");
-            if (it.instances.size() != ncols[it.key]) throw Failure(H2V_ERR_INVALID_INSTANCES, "instances do not match the VK's instance column count");
-            for (const Column& c : it.instances) { col_lens.push_back(c.size()); for (const Bytes& v : c) flat[i].insert(flat[i].end(), v.begin(), v.end()); }
-            keys.push_back(it.key); proofs.push_back(it.proof.data()); lens.push_back(it.proof.size()); insts.push_back(flat[i].data());
-        }
+        detail::Marshalled m;
+        for (const Context* c : contexts) m.add_key(c->handle());
+        for (const Item& it : items) m.add(it.key, it.instances, it.proof);
         std::vector<int> st(items.size() ? items.size() : 1, 0);
         int ok = 0;
-        check(h2v_accumulator_process(h_, handles.data(), handles.size(), keys.data(), items.size(), proofs.data(), lens.data(), insts.data(), ncols.data(),
-                                      col_lens.data(), rand32.empty() ? nullptr : rand32.data(), st.data(), &ok));
+        check(h2v_accumulator_process(h_, m.ctxs.data(), m.ctxs.size(), m.keys.data(), items.size(), m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols.data(),
+                                      m.col_lens.data(), rand32.empty() ? nullptr : rand32.data(), st.data(), &ok));
         all_ok_ = ok != 0;
         st.resize(items.size());
         return st;
@@ -300,8 +269,7 @@ public:
     bool all_ok() const { return all_ok_; }
     // AccumulatorStrategy::with / DualMSM::add_msm: (L, R) += the two term lists evaluated, unscaled — scalars 32 bytes each, bases 64 bytes (x | y) each
     void add_msm(const Bytes& left_scalars, const Bytes& left_bases, const Bytes& right_scalars, const Bytes& right_bases) {
-        if (left_scalars.size() % 32 || left_bases.size() != 2 * left_scalars.size() || right_scalars.size() % 32 || right_bases.size() != 2 * right_scalars.size())
-            throw Failure(H2V_ERR_BAD_ARGUMENT, "a channel is n 32-byte scalars and n 64-byte bases");
+        detail::check_channels(left_scalars, left_bases, right_scalars, right_bases, "a channel is n 32-byte scalars and n 64-byte bases");
         check(h2v_accumulator_add_msm(h_, left_scalars.data(), left_bases.data(), left_scalars.size() / 32, right_scalars.data(), right_bases.data(),
                                       right_scalars.size() / 32));
     }
@@ -355,33 +323,35 @@ private:
 // The pairing checks of ranges (first, count) of a batch's last finished launch on its resident scalars (h2v_batch_recheck): one verdict
 // per range; lefts / rights (optional) receive the evaluated channels, 64 bytes per range.
 struct RangeChecks { std::vector<bool> ok; Bytes lefts, rights; };
-inline RangeChecks recheck(h2v_batch* b, const std::vector<std::pair<size_t, size_t>>& ranges) {
-    std::vector<size_t> first, count;
-    for (const auto& r : ranges) { first.push_back(r.first); count.push_back(r.second); }
-    std::vector<int> ok(ranges.size() ? ranges.size() : 1, 0);
-    RangeChecks out;
-    out.lefts.assign(64 * ranges.size(), 0); out.rights.assign(64 * ranges.size(), 0);
-    check(h2v_batch_recheck(b, ranges.size(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
-    for (size_t i = 0; i < ranges.size(); ++i) out.ok.push_back(ok[i] != 0);
-    return out;
-}
-
-// The same over ranges of several finished batches in one set of launches (h2v_batches_recheck): a range is (batch index, first, count);
-// the batches must be on one device and over the same params
 struct BatchRange { size_t batch, first, count; };
-inline RangeChecks recheck(const std::vector<h2v_batch*>& batches, const std::vector<BatchRange>& ranges) {
+namespace detail {
+// one batch (h2v_batch_recheck, every range's batch index 0) or several (h2v_batches_recheck)
+inline RangeChecks recheck(h2v_batch* const* batches, size_t n_batches, bool several, const std::vector<BatchRange>& ranges) {
     std::vector<uint32_t> bor;
     std::vector<size_t> first, count;
     for (const auto& r : ranges) {
-        if (r.batch >= batches.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "batch index out of range");
+        if (r.batch >= n_batches) throw Failure(H2V_ERR_BAD_ARGUMENT, "batch index out of range");
         bor.push_back((uint32_t)r.batch); first.push_back(r.first); count.push_back(r.count);
     }
-    std::vector<int> ok(ranges.size() ? ranges.size() : 1, 0);
+    const size_t k = ranges.size();
+    std::vector<int> ok(k ? k : 1, 0);
     RangeChecks out;
-    out.lefts.assign(64 * ranges.size(), 0); out.rights.assign(64 * ranges.size(), 0);
-    check(h2v_batches_recheck(batches.data(), batches.size(), ranges.size(), bor.data(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
-    for (size_t i = 0; i < ranges.size(); ++i) out.ok.push_back(ok[i] != 0);
+    out.lefts.assign(64 * k, 0); out.rights.assign(64 * k, 0);
+    if (several) check(h2v_batches_recheck(batches, n_batches, k, bor.data(), first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
+    else check(h2v_batch_recheck(batches[0], k, first.data(), count.data(), ok.data(), out.lefts.data(), out.rights.data()));
+    for (size_t i = 0; i < k; ++i) out.ok.push_back(ok[i] != 0);
     return out;
+}
+}  // namespace detail
+inline RangeChecks recheck(h2v_batch* b, const std::vector<std::pair<size_t, size_t>>& ranges) {
+    std::vector<BatchRange> of_one;
+    for (const auto& r : ranges) of_one.push_back({0, r.first, r.second});
+    return detail::recheck(&b, 1, false, of_one);
+}
+// The same over ranges of several finished batches in one set of launches (h2v_batches_recheck): a range is (batch index, first, count);
+// the batches must be on one device and over the same params
+inline RangeChecks recheck(const std::vector<h2v_batch*>& batches, const std::vector<BatchRange>& ranges) {
+    return detail::recheck(batches.data(), batches.size(), true, ranges);
 }
 
 // kzg/strategy.rs:143-181: one pairing per proof, checked inside verify_proof
@@ -392,13 +362,12 @@ public:
         : params_(p), device_(device), mo_(mo), tr_(tr), ci_(circuit_instances) {}
     Error verify(const VerifyingKey& vk, const Instances& inst, const Bytes& proof) const {
         Context ctx(params_, vk, device_, mo_, tr_, ci_);
-        std::vector<std::pair<Instances, Bytes>> one{{inst, proof}};
-        size_t ncols = 0;
-        check(h2v_ctx_proof_shape(ctx.handle(), nullptr, nullptr, nullptr, nullptr, &ncols));
-        if (inst.size() != ncols) return Error::InvalidInstances;   // lib.rs:51-55
-        detail::Packed pk(one, ncols);
+        detail::Marshalled m;
+        m.add_key(ctx.handle());
+        if (inst.size() != m.ncols[0]) return Error::InvalidInstances;   // lib.rs:51-55
+        m.add(0, inst, proof);
         int st = 0;
-        check(h2v_verify_each(ctx.handle(), 1, pk.proofs.data(), pk.lens.data(), pk.insts.data(), pk.col_lens.size(), pk.col_lens.data(), &st));
+        check(h2v_verify_each(ctx.handle(), 1, m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), &st));
         return (Error)st;
     }
 
