@@ -60,9 +60,9 @@ __global__ void __launch_bounds__(256) k_export_records(const G1J* __restrict__ 
     }
     if (t == 0) { out[g].failed = failed; out[g].parts = parts; out[g].shift = shift; out[g].reserved = 0; }
 }
-// a record's accumulator put together: sum_j 2^(shift j) piece_j (only for records that do not match the fold's own split: rare)
+// a record's accumulator put together: sum_j 2^(shift j) piece_j, 1 <= parts <= H2V_ACC_RECORD_PIECES (only for records that do not match the
+// fold's own split: rare).  shift (parts - 1) dependent doublings: the caller bounds them (ACC_RECORD_MAX_SPAN)
 __device__ __noinline__ G1J acc_record_whole(const G1J* pc, uint32_t parts, uint32_t shift) {
-    if (parts == 0) return G1J::identity();
     G1J a = pc[parts - 1];
     for (uint32_t j = parts - 1; j-- > 0;) {
         for (uint32_t i = 0; i < shift; ++i) a = g1_add(a, a);
@@ -70,10 +70,17 @@ __device__ __noinline__ G1J acc_record_whole(const G1J* pc, uint32_t parts, uint
     }
     return a;
 }
+// The doublings a record may ask for, shift (parts - 1).  What a launch exports: msm_plan picks c in 2 .. 15 with ceil(130 / c) windows, and
+// msm_enqueue_multi cuts them into parts of wpp windows, shift = c wpp with (parts - 1) wpp < windows: shift (parts - 1) <= c (windows - 1) <= 129, and
+// over every (c, parts wanted) at most 128 (c = 2, 4 and 8; tests/record_reference.py max_exported_span).  The record's words come from the caller's memory, and the loop above must not run for as long as a garbage word says.
+#define ACC_RECORD_MAX_SPAN 256u
+__device__ __forceinline__ uint32_t sat_add_u32(uint32_t a, uint32_t b) { const uint32_t s = a + b; return s < a ? 0xffffffffu : s; }
 // Fold: piece j of (group g, side) = sum over the ranks' records of their piece j — records that were cut the same way
 // (parts, shift) add up piece by piece; a record cut differently is put together first and joins piece 0, whose weight is 1.
 // parts == 1: the result is the whole point, written to acc[2g + side]; else to pieces[(2g + side) * parts + j] and, in the form
-// the Miller lines are evaluated at (X Z, Y, Z^3), to ready[...].  fold_failed[g] = total failed proofs over all records.
+// the Miller lines are evaluated at (X Z, Y, Z^3), to ready[...].  fold_failed[g] = total failed proofs over all records, saturating.
+// A malformed record — parts outside 1 .. H2V_ACC_RECORD_PIECES (a record never written is one), or a foreign cut with
+// shift (parts - 1) > ACC_RECORD_MAX_SPAN — contributes the identity and counts as max(its failed word, 1) failed proofs: the fold cannot pass.
 __global__ void __launch_bounds__(64) k_fold_records(const AccRecord* __restrict__ recs, uint32_t n_recs, uint32_t groups, uint32_t parts, uint32_t shift,
                                                      G1J* __restrict__ acc, G1JSlot* __restrict__ pieces, G1JSlot* __restrict__ ready, uint32_t* __restrict__ fold_failed) {
     // a team of eight lanes per output point: lane r adds the records r, r + 8, ..., then a three-level butterfly — the sum over the
@@ -86,10 +93,12 @@ __global__ void __launch_bounds__(64) k_fold_records(const AccRecord* __restrict
     if (live) for (uint32_t i = r; i < n_recs; i += 8) {
         const AccRecord& rec = recs[(size_t)i * groups + g];
         const G1J* pc = side ? rec.right : rec.left;
-        const bool same = rec.parts == parts && (rec.shift == shift || parts == 1) && rec.parts <= H2V_ACC_RECORD_PIECES;
+        const bool sized = rec.parts >= 1 && rec.parts <= H2V_ACC_RECORD_PIECES;
+        const bool same = sized && rec.parts == parts && (rec.shift == shift || parts == 1);
+        const bool foreign = sized && !same && (uint64_t)rec.shift * (rec.parts - 1) <= ACC_RECORD_MAX_SPAN;
         if (same) sum = g1_add(sum, pc[j]);
-        else if (j == 0) sum = g1_add(sum, acc_record_whole(pc, rec.parts <= H2V_ACC_RECORD_PIECES ? rec.parts : 0u, rec.shift));
-        failed += rec.failed;
+        else if (foreign && j == 0) sum = g1_add(sum, acc_record_whole(pc, rec.parts, rec.shift));
+        failed = sat_add_u32(failed, same || foreign ? rec.failed : (rec.failed ? rec.failed : 1u));
     }
     for (uint32_t d = 4; d > 0; d >>= 1) {
         G1J other;
@@ -98,7 +107,7 @@ __global__ void __launch_bounds__(64) k_fold_records(const AccRecord* __restrict
 #pragma unroll
         for (uint32_t w = 0; w < sizeof(G1J) / 4; ++w) dst[w] = (uint32_t)__shfl_down((int)src[w], d, 8);
         sum = g1_add(sum, other);   // lanes r >= 8 - d add a value they do not own: only r = 0 is kept
-        failed += (uint32_t)__shfl_down((int)failed, d, 8);
+        failed = sat_add_u32(failed, (uint32_t)__shfl_down((int)failed, d, 8));
     }
     if (!live || r) return;
     if (parts == 1) acc[gs2] = sum;

@@ -463,7 +463,11 @@ int h2v_batch_accumulators(h2v_batch* b, void** device_ptr, size_t* nbytes);
  * folded pairing takes them in pieces too (the doublings move to precomputed multiples of the two G2 points; the whole point would
  * cost ~120 dependent doublings on every rank before AND the slower pairing after the exchange).  parts = 1, shift = 0 is a whole
  * point.  Records of ranks whose launches chose another (parts, shift) — shards of very different size — are folded correctly all
- * the same (their pieces are put together first). */
+ * the same (their pieces are put together first, and join the fold's piece 0).
+ * A malformed record never vanishes from a fold: one whose `parts` is outside 1 .. H2V_ACC_RECORD_PIECES — a record that was never
+ * written, all zero, is one — or that is cut differently from the fold and asks for more than 256 doublings, shift * (parts - 1) > 256
+ * (a launch exports at most 128), contributes the identity and counts as max(failed, 1) failed proofs, so the fold's group cannot be
+ * ok.  The folded failure count saturates at 2^32 - 1 instead of wrapping. */
 #define H2V_ACC_RECORD_PIECES 6
 #define H2V_ACC_RECORD_BYTES 1312   /* 16 + 2 * H2V_ACC_RECORD_PIECES * 108 */
 /* The HIP stream (hipStream_t) the batch runs on, for event timing and stream-ordered interop. */

@@ -8,6 +8,7 @@
 //   pairing_units check   IN OUT          pair_in_fq_star6 of crafted registers
 //   pairing_units lines   PARAMS IN OUT   k_pair_lines over crafted pieces with the split tables of a PairingDevice
 //   pairing_units verdict PARAMS IN OUT   pairing_check_split_enqueue (k_pairing2 or one stream) and pairing_check_enqueue
+//   pairing_units tail    PARAMS IN OUT   pairing_check_split_enqueue with a PairTail: the tail workgroups of k_pairing2 (pair_tail_role)
 // Files are little-endian uint32 words; the layouts are in the readers below.  Every HIP call is checked: the first error ends the
 // program with a non-zero status.  Every index that reaches a kernel is checked on the host first.
 #include <cstdio>
@@ -252,12 +253,85 @@ static int mode_verdict(const char* params, const char* in, const char* outp) {
     return 0;
 }
 
+// ---- tail: IN: n_jobs, then per job: shift, parts, n, count, n_words, skip_lo, skip_hi; the checks' line-ready pieces (n * 2 * parts, as in
+// `verdict`); the tail's Jacobian pieces (count * parts: point q = sum_j 2^(shift j) piece[q parts + j]); n_words source words.
+// Every output the tail writes per point has count + 1 elements, preset to 0xff: the spare one belongs to no point, must keep its preset and
+// is written out with the rest (its pieces are identities and its problem's `out` is the spare whole point: a lane that took it for a point
+// would write there, inside the buffers).  dst has TAIL_DST_SPARE spare words behind n_words.  host_bytes, host_ident and dst are mapped
+// host memory.
+// OUT per job: n verdicts; count + 1 whole points (27 words); the device block: (count + 1) * 16 words of bytes, count + 1 identity words;
+// the host block likewise; n_words + TAIL_DST_SPARE words of dst
+#define TAIL_DST_SPARE 16u
+static int mode_tail(const char* params, const char* in, const char* outp) {
+    PairingDevice pd;
+    upload_params(params, pd);
+    if (!pairing_tail_fits(pd, false)) { fprintf(stderr, "tail: this device's pairing launch cannot carry a tail (pairing_tail_fits)\n"); return 6; }
+    const std::vector<uint32_t> w = slurp_words(in);
+    Words r{w};
+    const uint32_t jobs = r.next();
+    REQUIRE(jobs <= 256, "too many jobs");
+    std::vector<uint32_t> all;
+    auto append = [&](const void* p, size_t words, bool device) {
+        const size_t at = all.size();
+        all.resize(at + words);
+        if (!words) return;
+        if (device) CK(hipMemcpy(all.data() + at, p, words * 4, hipMemcpyDeviceToHost));
+        else memcpy(all.data() + at, p, words * 4);
+    };
+    for (uint32_t jb = 0; jb < jobs; ++jb) {
+        const uint32_t shift = r.next(), parts = r.next(), n = r.next(), count = r.next(), n_words = r.next(), skip_lo = r.next(), skip_hi = r.next();
+        REQUIRE(n >= 1 && n <= 64 && parts >= 1 && parts <= PL_MAX_PARTS && shift < 256, "tail job");
+        REQUIRE(count >= 1 && count <= 128 && n_words >= 1 && n_words <= (1u << 16) && skip_lo <= skip_hi && skip_hi <= n_words, "tail shape");
+        G1JSlot* d_ready = read_slots(r, (size_t)2 * parts * n);
+        const size_t slots = (size_t)count + 1;
+        std::vector<G1J> pts(slots * parts, G1J::identity());
+        r.take(pts.data(), (size_t)count * parts);
+        std::vector<G1JSlot> pieces(pts.size());
+        for (size_t i = 0; i < pts.size(); ++i) pieces[i] = pts[i];
+        G1JSlot* d_pieces = to_device(pieces.data(), pieces.size());
+        std::vector<uint32_t> src(n_words);
+        r.take(src.data(), n_words);
+        uint32_t* d_src = to_device(src.data(), n_words);
+        G1J* d_whole = nullptr; uint8_t* d_bytes = nullptr; uint32_t* d_ident = nullptr; uint32_t* d_ok = nullptr; void* d_ws = nullptr;
+        CK(hipMalloc(&d_whole, slots * sizeof(G1J))); CK(hipMalloc(&d_bytes, slots * 64)); CK(hipMalloc(&d_ident, slots * 4)); CK(hipMalloc(&d_ok, n * 4));
+        CK(hipMalloc(&d_ws, (size_t)n * H2V_PAIRING_LINE_WS_BYTES));
+        CK(hipMemset(d_whole, 0xff, slots * sizeof(G1J))); CK(hipMemset(d_bytes, 0xff, slots * 64)); CK(hipMemset(d_ident, 0xff, slots * 4)); CK(hipMemset(d_ok, 0xff, n * 4));
+        std::vector<MsmProblem> prs(slots);
+        for (size_t q = 0; q < slots; ++q) prs[q].out = d_whole + q;
+        MsmProblem* d_prs = to_device(prs.data(), slots);
+        MappedHostBuf h_bytes, h_ident, h_dst;
+        const size_t dst_words = (size_t)n_words + TAIL_DST_SPARE;
+        RC(h_bytes.reserve(slots * 64)); RC(h_ident.reserve(slots * 4)); RC(h_dst.reserve(dst_words * 4));
+        memset(h_bytes.p, 0xff, slots * 64); memset(h_ident.p, 0xff, slots * 4); memset(h_dst.p, 0xff, dst_words * 4);
+        PairTail t;
+        t.pieces = d_pieces; t.prs = d_prs; t.count = count; t.parts = parts; t.shift = shift;
+        t.out_bytes = d_bytes; t.out_ident = d_ident;
+        t.host_bytes = reinterpret_cast<uint8_t*>(h_bytes.dev); t.host_ident = reinterpret_cast<uint32_t*>(h_ident.dev);
+        t.src = d_src; t.dst = reinterpret_cast<uint32_t*>(h_dst.dev);
+        t.n_words = n_words; t.skip_lo = skip_lo; t.skip_hi = skip_hi;
+        RC(pairing_check_split_enqueue(0, pd, d_ready, n, parts, shift, d_ws, d_ok, false, &t));
+        CK(hipDeviceSynchronize());
+        append(d_ok, n, true);
+        append(d_whole, slots * sizeof(G1J) / 4, true);
+        append(d_bytes, slots * 16, true); append(d_ident, slots, true);
+        append(h_bytes.p, slots * 16, false); append(h_ident.p, slots, false);
+        append(h_dst.p, dst_words, false);
+        CK(hipFree(d_ready)); CK(hipFree(d_pieces)); CK(hipFree(d_src)); CK(hipFree(d_whole)); CK(hipFree(d_bytes)); CK(hipFree(d_ident));
+        CK(hipFree(d_ok)); CK(hipFree(d_ws)); CK(hipFree(d_prs));
+    }
+    REQUIRE(r.at == w.size(), "trailing input");
+    spill(outp, all.data(), all.size() * 4);
+    printf("tail: %u jobs\n", jobs);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "step" && argc == 4) return mode_step(argv[2], argv[3]);
     if (mode == "check" && argc == 4) return mode_check(argv[2], argv[3]);
     if (mode == "lines" && argc == 5) return mode_lines(argv[2], argv[3], argv[4]);
     if (mode == "verdict" && argc == 5) return mode_verdict(argv[2], argv[3], argv[4]);
-    fprintf(stderr, "usage: pairing_units step|check IN OUT | lines|verdict PARAMS IN OUT\n");
+    if (mode == "tail" && argc == 5) return mode_tail(argv[2], argv[3], argv[4]);
+    fprintf(stderr, "usage: pairing_units step|check IN OUT | lines|verdict|tail PARAMS IN OUT\n");
     return 2;
 }

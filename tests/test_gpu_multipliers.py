@@ -91,3 +91,32 @@ def test_a_shard_uploads_the_tail_of_the_whole_batch(tmp_path):
     for G, n, nt in [(1, 1, 9), (1, 64, 65), (4, 63, 1024), (4, 256, 257), (2, 1024, 8192), (32, 65, 130)]:
         jobs.append((G, nt, n, [[rnd.randrange(R) for _ in range(nt)] for _ in range(G)]))
     _check(jobs, _run(jobs, tmp_path))
+
+
+def test_gather_multipliers(tmp_path):
+    """k_gather_multipliers behind gather_multipliers_enqueue: out[i] = src[idx[i]], the nine limbs as they lie in memory, with repeated,
+    reversed and out-of-order indices at n = 1, 255, 256, 257 and 512 (one and two workgroups, a partial last one); n = 0 launches
+    nothing.  The harness checks every index against the source length before the launch and the guard bands around the output after."""
+    import numpy as np
+    rnd = random.Random(400)
+    jobs = []
+    for n_src, n, kind in [(1, 1, "repeat"), (300, 255, "reverse"), (300, 256, "shuffle"), (300, 257, "repeat"), (257, 257, "reverse"), (7, 512, "shuffle"),
+                           (256, 256, "identity"), (5, 0, "identity")]:
+        src = np.array([[rnd.randrange(1 << 29) for _ in range(9)] for _ in range(n_src)], dtype="<u4").reshape(n_src, 9)
+        if kind == "repeat": idx = [(i // 3) % n_src for i in range(n)]
+        elif kind == "reverse": idx = [n_src - 1 - i % n_src for i in range(n)]
+        elif kind == "shuffle": idx = [rnd.randrange(n_src) for _ in range(n)]
+        else: idx = list(range(n))
+        assert all(0 <= i < n_src for i in idx)
+        jobs.append((src, idx))
+    blob = struct.pack("<I", len(jobs)) + b"".join(struct.pack("<II", len(src), len(idx)) + src.tobytes() + np.asarray(idx, dtype="<u4").tobytes() for src, idx in jobs)
+    a, b = tmp_path / "gather_in.bin", tmp_path / "gather_out.bin"
+    a.write_bytes(blob)
+    r = subprocess.run([EXE, "gather", str(a), str(b)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    out = np.frombuffer(b.read_bytes(), dtype="<u4")
+    at = 0
+    for src, idx in jobs:
+        got = out[at:at + 9 * len(idx)].reshape(len(idx), 9); at += got.size
+        assert (got == src[idx]).all() if idx else got.size == 0, (len(src), len(idx))
+    assert at == len(out)

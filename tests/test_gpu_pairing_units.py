@@ -339,3 +339,149 @@ def test_check_verdicts_match_pyref(tmp_path, srs):
     got = [bool(x) for x in np.fromfile(tmp_path / "verdict.out", dtype=np.uint32)]
     assert len(got) == len(want)
     assert got == want
+
+
+# ====================================================================== the launch tail (PairTail)
+TAIL_COUNTS = [1, 2, 63, 64, 65, 128]
+TAIL_PARTS = [1, 2, 6]
+TAIL_WORDS = [1, 4095, 4096, 4097, 2047, 2048, 2049]       # (a copying workgroup takes 2048 words)
+TAIL_SKIPS = ["inside", "both_ends", "empty", "from_start", "to_end"]
+TAIL_DST_SPARE = 16
+FF = 0xffffffff
+
+
+def _tail_skip(kind, n_words):
+    if kind == "both_ends": return 0, n_words
+    if kind == "empty": return n_words // 2, n_words // 2
+    if kind == "from_start": return 0, max(1, n_words // 3)
+    if kind == "to_end": return min(n_words - 1, 2 * n_words // 3), n_words
+    return (n_words // 3, max(n_words // 3 + 1, 2 * n_words // 3)) if n_words > 1 else (0, 1)
+
+
+@pytest.fixture(scope="module")
+def tail_run(tmp_path_factory, srs):
+    """one child process for the 36 launches with a tail, one for the same checks without"""
+    import msm_reference as ref
+    tmp = tmp_path_factory.mktemp("tail")
+    rnd = random.Random(53)
+    pool = [ref.mul(rnd.randrange(1, pr.R), ref.G) for _ in range(12)]
+    weighted = {}
+
+    def times(pt, e):
+        if (pt, e) not in weighted:
+            weighted[(pt, e)] = ref.mul(pow(2, e, pr.R), pt)
+        return weighted[(pt, e)]
+
+    # the checks of a launch: four per split, of which a job takes the first n
+    checks = {}
+    for parts in TAIL_PARTS:
+        shift = _split_shape(parts)
+        ws = []
+        for kind in ("plain", "off_by_one", "identity_mixed", "plain"):
+            L, Rr = _pieces_for(rnd, srs, parts, kind)
+            w, _ = _encode_pieces(rnd, L, Rr, parts)
+            ws.append(w)
+        checks[parts] = (shift, ws)
+    jobs, blob, vblob = [], [], []
+    for i in range(36):
+        count, parts = TAIL_COUNTS[i % 6], TAIL_PARTS[(i // 6) % 3]
+        n_words = TAIL_WORDS[i % 7]
+        lo, hi = _tail_skip(TAIL_SKIPS[i % 5], n_words)
+        assert 0 <= lo <= hi <= n_words
+        n = 1 + i % 4
+        shift, ws = checks[parts]
+        ready = [v for w in ws[:n] for v in w]
+        # the tail's points: ordinary ones, identity pieces, the identity as a sum of pieces that are not (piece 0 = -2^shift piece 1)
+        words, want = [], []
+        for q in range(count):
+            pcs = [rnd.choice(pool) for _ in range(parts)]
+            if q % 5 == 1:
+                pcs = [None if rnd.random() < 0.5 else p for p in pcs]
+            elif q % 5 == 2:
+                pcs = [None] * parts
+            elif q % 5 == 3 and parts > 1:
+                pcs = [ref.neg(times(pcs[1], shift)), pcs[1]] + [None] * (parts - 2)
+            whole = None
+            for j, p in enumerate(pcs):
+                whole = ref.add(whole, times(p, shift * j) if p is not None else None)
+            if q % 5 == 3 and parts > 1:
+                assert whole is None
+            want.append(whole)
+            for p in pcs:
+                X, Y, Z = pr.jacobian(p, rnd.randrange(1, P))
+                if p is None: X, Y = rnd.randrange(1, P), rnd.randrange(1, P)
+                w = [rep(v, rnd.random() < 0.5) for v in (X, Y, Z)]
+                if p is None and rnd.random() < 0.5: w[2] = P
+                words += w
+        src = np.random.RandomState(i).randint(0, 1 << 32, size=n_words, dtype=np.uint64).astype("<u4")
+        src[src == FF] = 0            # (the preset stands for "not written")
+        blob.append(np.array([shift, parts, n, count, n_words, lo, hi], np.uint32).tobytes() + limbs_np(ready).tobytes() + limbs_np(words).tobytes() + src.tobytes())
+        vblob.append(np.array([0, shift, parts, n], np.uint32).tobytes() + limbs_np(ready).tobytes())
+        jobs.append(dict(count=count, parts=parts, shift=shift, n=n, n_words=n_words, lo=lo, hi=hi, want=want, src=src))
+    (tmp / "params").write_bytes(srs.params_raw)
+    (tmp / "tail.in").write_bytes(np.array([len(jobs)], np.uint32).tobytes() + b"".join(blob))
+    (tmp / "verdict.in").write_bytes(np.array([len(jobs)], np.uint32).tobytes() + b"".join(vblob))
+    _run(["tail", tmp / "params", tmp / "tail.in", tmp / "tail.out"], timeout=300)
+    _run(["verdict", tmp / "params", tmp / "verdict.in", tmp / "verdict.out"], timeout=300)
+    out = np.fromfile(tmp / "tail.out", dtype=np.uint32)
+    plain = np.fromfile(tmp / "verdict.out", dtype=np.uint32)
+    at = vat = 0
+    for j in jobs:
+        s = j["count"] + 1
+        def take(words):
+            nonlocal at
+            v = out[at:at + words]; at += words
+            return v
+        j["ok"] = take(j["n"]).tolist()
+        j["whole"] = take(27 * s).reshape(s, 27)
+        j["dev_bytes"], j["dev_ident"] = take(16 * s).reshape(s, 16), take(s)
+        j["host_bytes"], j["host_ident"] = take(16 * s).reshape(s, 16), take(s)
+        j["dst"] = take(j["n_words"] + TAIL_DST_SPARE)
+        j["plain_ok"] = plain[vat:vat + j["n"]].tolist(); vat += j["n"]
+    assert at == len(out) and vat == len(plain)
+    return jobs
+
+
+def test_tail_covers_its_shapes(tail_run):
+    assert {(j["count"], j["parts"]) for j in tail_run} == {(c, k) for c in TAIL_COUNTS for k in TAIL_PARTS}
+    assert {(j["n_words"], j["lo"] == j["hi"], j["lo"] == 0, j["hi"] == j["n_words"]) for j in tail_run} >= \
+        {(w, e, a, b) for w in (4095, 4096, 4097) for e, a, b in ((True, False, False), (False, True, True), (False, False, False))}
+    assert {j["n"] for j in tail_run} == {1, 2, 3, 4}
+
+
+def test_tail_points_and_bytes(tail_run):
+    """point q < count: the whole point is sum_j 2^(shift j) piece_j, the device and the host block hold its exact bytes and identity flag;
+    the spare element behind each output keeps its preset: no lane takes q = count for a point"""
+    import msm_reference as ref
+    import record_reference as rr
+    kinds = set()
+    for j in tail_run:
+        tag = (j["count"], j["parts"])
+        for q, want in enumerate(j["want"]):
+            w = j["whole"][q].tolist()
+            assert rr.in_range(w) and ref.jac_point(w) == want, (tag, q)
+            by, ident = rr.point_to_bytes(want)
+            assert j["dev_bytes"][q].tobytes() == by and int(j["dev_ident"][q]) == ident, (tag, q)
+            assert j["host_bytes"][q].tobytes() == by and int(j["host_ident"][q]) == ident, (tag, q)
+            kinds.add(want is None)
+        c = j["count"]
+        assert (j["whole"][c] == FF).all() and (j["dev_bytes"][c] == FF).all() and (j["host_bytes"][c] == FF).all(), (tag, "the spare element was written")
+        assert j["dev_ident"][c] == FF and j["host_ident"][c] == FF, (tag, "the spare element was written")
+    assert kinds == {True, False}
+
+
+def test_tail_copies_all_but_the_skipped_range(tail_run):
+    for j in tail_run:
+        n, lo, hi = j["n_words"], j["lo"], j["hi"]
+        tag = (n, lo, hi)
+        assert (j["dst"][:lo] == j["src"][:lo]).all() and (j["dst"][hi:n] == j["src"][hi:n]).all(), tag
+        assert (j["dst"][lo:hi] == FF).all(), (tag, "a word inside the skipped range was written")
+        assert (j["dst"][n:] == FF).all(), (tag, "written past n_words")
+
+
+def test_tail_leaves_the_verdicts_alone(tail_run):
+    """the verdicts of a launch with a tail are those of the same checks without one (the `verdict` mode, compared with pyref above); by
+    construction the plain checks (0 and 3) pass and the one whose right side is off by one (1) fails"""
+    for j in tail_run:
+        assert j["ok"] == j["plain_ok"], (j["count"], j["parts"], j["ok"], j["plain_ok"])
+        assert all(j["ok"][i] == want for i, want in ((0, 1), (1, 0), (3, 1)) if i < j["n"]), (j["count"], j["parts"], j["ok"])
