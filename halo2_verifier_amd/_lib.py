@@ -55,6 +55,7 @@ SIGNATURES = {
     "h2v_accumulator_journal_begin": (c_int, [c_vp, c_sz]),
     "h2v_accumulator_check_legs": (c_int, [c_vp, c_sz, c_szp, c_szp, c_szp, c_intp]),
     "h2v_accumulator_drop_legs": (c_int, [c_vp, c_szp, c_sz]),
+    "h2v_verify_batches": (c_int, [c_vp, c_sz, c_szp, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_verify_each": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_intp]),
     "h2v_verify_batch_identify": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p, c_szp]),
     "h2v_verify_batch_keys_identify": (c_int, [ctypes.POINTER(c_vp), c_sz, ctypes.POINTER(ctypes.c_uint32), c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_szp,
@@ -70,6 +71,7 @@ SIGNATURES = {
     "h2v_batch_upload_launch": (c_int, [c_vp, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_szp, c_u8p, c_sz, c_int]),
     "h2v_batch_finish": (c_int, [c_vp, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_batch_set_groups": (c_int, [c_vp, c_sz]),
+    "h2v_batch_set_group_sizes": (c_int, [c_vp, c_szp, c_sz]),
     "h2v_batch_finish_groups": (c_int, [c_vp, c_intp, c_intp, c_u8p, c_u8p, c_sz]),
     "h2v_batch_recheck": (c_int, [c_vp, c_sz, c_szp, c_szp, c_intp, c_u8p, c_u8p]),
     "h2v_batches_recheck": (c_int, [ctypes.POINTER(c_vp), c_sz, c_sz, ctypes.POINTER(ctypes.c_uint32), c_szp, c_szp, c_intp, c_u8p, c_u8p]),

@@ -2,6 +2,7 @@
 #pragma once
 #include "ctx.h"
 #include "vkplan.h"
+#include <algorithm>
 #include <memory>
 
 namespace h2v {
@@ -89,10 +90,17 @@ int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // d_scratch: multipliers_scratch(n_tail, groups) elements (the tiles' products of the two-level scan)
 size_t multipliers_scratch(uint32_t n_tail, uint32_t groups);
 int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult, Fr* d_scratch);
+// Groups of unequal size (h2v_batch_set_group_sizes): d_mult[j] = the product of the draws behind j inside j's own group, for n draws
+// (one per proof) whose groups end where d_last[j] != 0 (d_last[n - 1] != 0).  A segmented suffix scan over the whole array: work
+// proportional to n whatever the sizes.  d_tile_prod: ragged_multipliers_tiles(n) elements, d_tile_words: twice as many words.
+size_t ragged_multipliers_tiles(uint32_t n);
+int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8_t* d_last, uint32_t n, Fr* d_mult, Fr* d_tile_prod, uint32_t* d_tile_words);
 // out[i] = src[idx[i]]: the multipliers of a non-contiguous subset of a larger accumulation
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
 int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal);
+// the same for groups of unequal size: group g owns the proofs [d_off[g], d_off[g + 1])
+int fold_shared_offsets_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, const uint32_t* d_off, uint32_t* d_msm_scal);
 // One range of a re-check (k_fold_ranges): proofs [first, first + count) of a batch whose VK-wide scalars are shared[j][p] (j <
 // n_shared, p < n); its n_shared folded scalars go to rows [out, out + n_shared) of the output.  Ranges of one launch may belong to
 // different batches (h2v_batches_recheck), so each carries its own batch's pointer and sizes.
@@ -148,6 +156,13 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
                 const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false);
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
 bool pairing_passed(const h2v_batch* b, uint32_t g);
+// The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
+// problem is one slot of every proof.  channel_problems builds its problems from these counts.
+struct ChannelTerms { bool strided; uint32_t left, right; };
+ChannelTerms channel_terms(const Plan& pl, uint32_t count, uint32_t n_shared);
+// whether a launch of groups of these sizes passes msm_enqueue_multi's rule (msm_cuts_within_limit over the groups' channel_terms): what an
+// upload of unequal groups is held to, and what h2v_verify_batches cuts its launches by
+bool groups_cut_within_limit(const Plan& pl, const size_t* sizes, size_t n_groups);
 // what the accumulation and its pairing read from the params (shplonk.rs's -g term, msm.rs:185-203); k may differ
 bool same_srs(const ParamsHost& a, const ParamsHost& b);
 // h2v_batches_recheck (h2v_batch_recheck: one batch, batch_of_range NULL); `who` names the entry point in the error messages
@@ -193,6 +208,12 @@ struct h2v_batch {
     h2v::PlanDevice* plan = nullptr;  // set at upload (depends on the instance shape)
     uint32_t n = 0, n_tail = 0;
     uint32_t groups = 1;              // independent accumulator batches inside this launch (h2v_batch_set_groups)
+    // groups of unequal size (h2v_batch_set_group_sizes): group g owns the proofs [group_off[g], group_off[g + 1]) of an upload of
+    // group_off[groups] proofs.  Empty: equal groups of n / groups proofs (h2v_batch_set_groups)
+    std::vector<uint32_t> group_off;
+    std::vector<uint8_t> group_last;  // per proof: it is the last of its group (the segmented scan's input, copied with the draws)
+    h2v::DevBuf<uint32_t> d_group_off; h2v::DevBuf<uint8_t> d_group_last;
+    h2v::DevBuf<uint32_t> mult_seg;   // ragged_multipliers_enqueue's words per tile
     std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
     // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
     h2v::DevBuf<uint8_t> proofs, inst, tail;
@@ -221,3 +242,14 @@ struct h2v_batch {
     hipEvent_t ev[8] = {nullptr};
     float last_ms[7] = {0, 0, 0, 0, 0, 0, 0};
 };
+
+namespace h2v {
+// where the groups of the batch's upload lie: equal slices, or the offsets of h2v_batch_set_group_sizes
+inline bool ragged(const h2v_batch* b) { return !b->group_off.empty(); }
+inline size_t group_first(const h2v_batch* b, size_t g) { return ragged(b) ? b->group_off[g] : g * (b->n / b->groups); }
+inline size_t group_count(const h2v_batch* b, size_t g) { return ragged(b) ? b->group_off[g + 1] - b->group_off[g] : b->n / b->groups; }
+inline size_t group_of(const h2v_batch* b, size_t proof) {   // proof < n
+    if (!ragged(b)) return proof / (b->n / b->groups);
+    return (size_t)(std::upper_bound(b->group_off.begin(), b->group_off.end(), (uint32_t)proof) - b->group_off.begin()) - 1;
+}
+}  // namespace h2v

@@ -17,7 +17,8 @@ struct BatchSizes {
     size_t proofs, inst, pts, ycanon, words, chal, mult, slots, msm_scal, shared, left_scal, insteval, guard_scal, acc, results;
     uint32_t ws_terms, ws_problems, ws_per_problem;   // MsmWorkspace::reserve
 };
-BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G) {
+// `largest`: the proofs of the largest group (the bucket arrays follow the largest problem of a launch)
+BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G, size_t largest) {
     BatchSizes z;
     z.stream_words = stream_words_for(pl.stream.size(), pl.opts.transcript);
     z.proofs = N * pl.proof_len;
@@ -37,7 +38,7 @@ BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G) {
     z.results = ResultsLayout{G, N}.total();
     z.ws_terms = (uint32_t)(2 * (N * pl.n_points + G * pl.n_shared));
     z.ws_problems = (uint32_t)(2 * G);
-    z.ws_per_problem = (uint32_t)((N + G - 1) / G * pl.n_points + pl.n_shared);
+    z.ws_per_problem = (uint32_t)(largest * pl.n_points + pl.n_shared);
     return z;
 }
 
@@ -45,7 +46,10 @@ BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G) {
 // out_bytes / status into the results block laid out for that group count
 int ensure_buffers(h2v_batch* b, const Plan& pl) {
     const size_t N = b->max_proofs, G = b->groups;
-    const BatchSizes z = batch_sizes(pl, N, G);
+    // equal groups: ceil(N / G) proofs each at capacity; unequal groups: the largest of the sizes set
+    size_t largest = (N + G - 1) / G;
+    if (ragged(b)) { largest = 0; for (size_t g = 0; g < G; ++g) largest = std::max<size_t>(largest, b->group_off[g + 1] - b->group_off[g]); }
+    const BatchSizes z = batch_sizes(pl, N, G, largest);
     int rc;
     if ((rc = b->proofs.reserve(z.proofs)) || (rc = b->inst.reserve(z.inst)) || (rc = b->pts.reserve(z.pts)) || (rc = b->phi.reserve(z.pts)) ||
         (rc = b->ycanon.reserve(z.ycanon)) || (rc = b->words.reserve(z.words)) || (rc = b->chal.reserve(z.chal)) || (rc = b->mult.reserve(z.mult)) ||
@@ -109,21 +113,32 @@ struct StageCommit {
 // The two MSM problems of the proofs [p0, p0 + count) of an uploaded batch: acc2[0] <- the left channel (SHPLONK: sum_p m_p * h2_p;
 // GWC: the witness points), acc2[1] <- the right channel = the proofs' pooled Guard terms + the VK-wide bases with the n_shared
 // folded scalars `shared_scal`.  Both index the batch's point array; unused slots have zero scalars and cost nothing.
+// the term counts of those two problems: the one rule, for channel_problems and for whoever must know a launch's layout before it is built
+ChannelTerms channel_terms(const Plan& pl, uint32_t count, uint32_t n_shared) {
+    const bool strided = pl.left_term_order.size() == 1 && !pl.left_term_order[0].first;
+    return ChannelTerms{strided, strided ? count : count * pl.n_points, count * pl.n_points + n_shared};
+}
+bool groups_cut_within_limit(const Plan& pl, const size_t* sizes, size_t n_groups) {
+    std::vector<uint32_t> terms;
+    for (size_t g = 0; g < n_groups; ++g) { const ChannelTerms t = channel_terms(pl, (uint32_t)sizes[g], pl.n_shared); terms.push_back(t.left); terms.push_back(t.right); }
+    return msm_cuts_within_limit(terms.data(), terms.size());
+}
 void channel_problems(MsmProblems& pr, const h2v_batch* b, const Plan& pl, size_t p0, uint32_t count, G1J* acc2, const uint32_t* shared_scal, uint32_t n_shared) {
     const uint32_t np = pl.n_points;
     const size_t first = p0 * np;
-    if (pl.left_term_order.size() == 1 && !pl.left_term_order[0].first) {
+    const ChannelTerms terms = channel_terms(pl, count, n_shared);
+    if (terms.strided) {
         // SHPLONK: one left term per proof (its h2): the problem is that slot of every proof — a strided view of `count` terms, not the
         // count * np slots with `count` of them non-zero (msm_glv_prep wrote twelve zero words for each of the other slots)
         const size_t at = first + pl.left_term_order[0].second;
-        pr.p.push_back(MsmProblem(b->left_scal.p + at * 8, b->pts.p + at, acc2, 8 * np, np, count));
+        pr.p.push_back(MsmProblem(b->left_scal.p + at * 8, b->pts.p + at, acc2, 8 * np, np, terms.left));
         pr.p.back().phi = b->phi.p + at;
     } else {
-        pr.p.push_back(MsmProblem(b->left_scal.p + first * 8, b->pts.p + first, acc2, 8, 1, count * np));
+        pr.p.push_back(MsmProblem(b->left_scal.p + first * 8, b->pts.p + first, acc2, 8, 1, terms.left));
         pr.p.back().phi = b->phi.p + first;
         pr.p.back().nnz = count * (uint32_t)pl.left_term_order.size();   // the program writes only these slots, the rest stay zero
     }
-    pr.p.push_back(MsmProblem(b->msm_scal.p + first * 8, b->pts.p + first, acc2 + 1, 8, 1, count * np, shared_scal, b->pts.p + (size_t)b->n * np, n_shared));
+    pr.p.push_back(MsmProblem(b->msm_scal.p + first * 8, b->pts.p + first, acc2 + 1, 8, 1, terms.right - n_shared, shared_scal, b->pts.p + (size_t)b->n * np, n_shared));
     pr.p.back().phi = b->phi.p + first; pr.p.back().phi2 = b->phi.p + (size_t)b->n * np;
 }
 
@@ -237,6 +252,12 @@ static StageArgs stage_args(const h2v_batch* b) {
     return StageArgs{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
 }
 
+// the multipliers of the uploaded draws (-> mult), on the batch's stream
+static int draw_multipliers_enqueue(h2v_batch* b) {
+    if (ragged(b)) return ragged_multipliers_enqueue(b->stream, b->tail.p, b->d_group_last.p, b->n, b->mult.p, b->mult_tiles.p, b->mult_seg.p);
+    return multipliers_enqueue(b->stream, b->tail.p, b->n_tail, b->n, b->groups, b->mult.p, b->mult_tiles.p);
+}
+
 // `overlap`: where it pays (see `points_first` below), the point bytes are copied first on the batch's copy stream and the decompression
 // runs under the copy of everything else (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
 // `guard`: the guard variant of the plan (h2v_guard_msm)
@@ -256,7 +277,18 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     if (proof_len < pl.proof_len) { set_last_error("h2v_batch_upload: proof_len is shorter than this VK's proof"); return H2V_ERR_BAD_ARGUMENT; }
     if (pl.n_instance_values && n && !instances_flat) { set_last_error("h2v_batch_upload: instances missing"); return H2V_ERR_BAD_ARGUMENT; }
     if (rand_tail && n_tail < n) { set_last_error("h2v_batch_upload: n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
-    if (b->groups > 1 && (n % b->groups || (rand_tail && n_tail % b->groups))) { set_last_error("h2v_batch_upload: n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
+    if (ragged(b)) {
+        if (n != b->group_off.back()) { set_last_error("h2v_batch_upload: n is not the sum of the group sizes (h2v_batch_set_group_sizes)"); return H2V_ERR_BAD_ARGUMENT; }
+        if (rand_tail && n_tail != n) { set_last_error("h2v_batch_upload: groups of unequal size take one draw per proof (n_tail == n)"); return H2V_ERR_BAD_ARGUMENT; }
+        // the MSM cuts problems too large for its per-window sort into sub-problems, at most MSM_MAX_PROBLEMS per launch; equal groups that miss
+        // the limit all run uncut, a form that unequal groups have never taken: refused before any device work
+        std::vector<size_t> sizes(b->groups);
+        for (size_t g = 0; g < b->groups; ++g) sizes[g] = b->group_off[g + 1] - b->group_off[g];
+        if (!ctx->tuning.msm_no_term_split && !groups_cut_within_limit(pl, sizes.data(), sizes.size())) {
+            set_last_error("h2v_batch_upload: the groups' MSM problems, cut into sub-problems of at most 16384 terms, exceed the launch's problem limit");
+            return H2V_ERR_UNSUPPORTED;
+        }
+    } else if (b->groups > 1 && (n % b->groups || (rand_tail && n_tail % b->groups))) { set_last_error("h2v_batch_upload: n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
     std::vector<uint8_t> os_rand;
     if (!rand_tail) n_tail = n;
     if ((rc = resolve_draws(rand_tail, n_tail, os_rand, "h2v_batch_upload"))) return rc;
@@ -267,13 +299,21 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     const PlanDevice* pd = b->plan;
     // a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs
     b->zero_below.assign(b->groups, 0);
-    if (n) {
+    if (ragged(b)) {
+        for (size_t g = 0; g < b->groups; ++g)   // (each group from its own draws)
+            for (size_t f = b->group_off[g], j = b->group_off[g + 1] - f; j-- > 1;)
+                if (scalar_is_zero(rand_tail + 32 * (f + j))) { b->zero_below[g] = (uint32_t)j; break; }
+    } else if (n) {
         const size_t G = b->groups, gs = n / G, nt = n_tail / G;
         for (size_t g = 0; g < G; ++g)
             for (size_t j = nt; j-- > 1;)
                 if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
     }
-    if ((rc = b->tail.reserve(32 * n_tail)) || (rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
+    if ((rc = b->tail.reserve(32 * n_tail))) return rc;
+    if (ragged(b)) {
+        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
+        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles)) || (rc = b->d_group_off.reserve(b->group_off.size())) || (rc = b->d_group_last.reserve(n))) return rc;
+    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
     b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false;
     hipStream_t s = b->stream;
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
@@ -284,6 +324,10 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     auto copy_rest = [&](hipStream_t cs) -> int {
         if (pl.n_instance_values) H2V_HIP_CHECK(hipMemcpyAsync(b->inst.p, instances_flat, n * (size_t)pl.n_instance_values * 32, hipMemcpyHostToDevice, cs));
         H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, rand_tail, 32 * n_tail, hipMemcpyHostToDevice, cs));
+        if (ragged(b)) {   // (the batch's own vectors: unchanged until the next h2v_batch_set_group_sizes, which waits for the streams)
+            H2V_HIP_CHECK(hipMemcpyAsync(b->d_group_last.p, b->group_last.data(), n, hipMemcpyHostToDevice, cs));
+            H2V_HIP_CHECK(hipMemcpyAsync(b->d_group_off.p, b->group_off.data(), 4 * b->group_off.size(), hipMemcpyHostToDevice, cs));
+        }
         // VK-wide bases sit behind the batch's own points so that one MSM covers both
         H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
         H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
@@ -335,7 +379,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     }
     b->decompressed = points_first;
     // the batch multipliers depend on the draws alone: computed once per upload (the draws are on the device), kept by every launch of it
-    if (n) { if ((rc = multipliers_enqueue(s, b->tail.p, b->n_tail, (uint32_t)n, b->groups, b->mult.p, b->mult_tiles.p))) return rc; b->mult_of_draws = true; }
+    if (n) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
     commit.commit(BatchStage::Uploaded);
     return 0;
 }
@@ -351,7 +395,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     const Plan& pl = pd->host;
     hipStream_t s = b->stream;
     uint32_t n = b->n;
-    const uint32_t G = b->groups, gs = n / G;
+    const uint32_t G = b->groups;
     if ((rc = join_tail(b))) return rc;
     int ev = 0;
     auto mark = [&]() { if (b->profiling >= 2) hipEventRecord(b->ev[ev], s); ++ev; };   // (an event record is a barrier packet: ~6 us of idle stream each)
@@ -374,12 +418,12 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: msm_enqueue_multi sends them only when they differ from the workspace's.
     MsmProblems pr;
     for (uint32_t g = 0; g < G; ++g)
-        channel_problems(pr, b, pl, (size_t)g * gs, gs, b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
+        channel_problems(pr, b, pl, group_first(b, g), (uint32_t)group_count(b, g), b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
     b->ws.tune = ctx->tuning;
     if (n) {
         // gathered multipliers replace the upload's; a launch on the draws after one on gathered multipliers computes the upload's again
         if (ext_mult) { b->mult_of_draws = false; if ((rc = gather_multipliers_enqueue(s, ext_mult, ext_idx, n, b->mult.p))) return rc; }
-        else if (!b->mult_of_draws) { if ((rc = multipliers_enqueue(s, b->tail.p, b->n_tail, n, G, b->mult.p, b->mult_tiles.p))) return rc; b->mult_of_draws = true; }
+        else if (!b->mult_of_draws) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
         if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, s));
     }
@@ -400,7 +444,11 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     for (int k = 0; k < 3; ++k) { for (int q = 0; q < k + 2; ++q) { a.code_k[k][q] = pd->code_k[k][q].p; a.n_code_k[k][q] = (uint32_t)pl.code_k[k][q].size(); } a.n_slots_k[k] = pl.n_slots_k[k]; }
     if ((rc = frvm_enqueue(s, a, pl.n_slots))) return rc;
     mark();
-    if (n) { if ((rc = fold_shared_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->msm_scal.p))) return rc; }
+    if (n) {
+        if (ragged(b)) rc = fold_shared_offsets_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->d_group_off.p, b->msm_scal.p);
+        else rc = fold_shared_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->msm_scal.p);
+        if (rc) return rc;
+    }
     mark();
     {
         b->ws.profile = b->profiling >= 1; b->ws.profile_recorded = false;
@@ -441,7 +489,7 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     StageCommit commit{b};
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     hipStream_t s = b->stream;
-    const uint32_t n = b->n, G = b->groups, gs = n / G;
+    const uint32_t n = b->n, G = b->groups;
     { int rcw = ensure_whole(b); if (rcw) return rcw; }
     const ResultsLayout L{G, n};
     hipError_t e;
@@ -480,7 +528,7 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     uint32_t any = 0;
     for (uint32_t i = 0; i < n; ++i) any |= (uint32_t)st[i];
     if (!any) { if (per_proof_status && n) memset(per_proof_status, 0, sizeof(int) * (size_t)n); }
-    else for (uint32_t g = 0, i = 0; g < G; ++g) for (uint32_t k = 0; k < gs; ++k, ++i) {
+    else for (uint32_t g = 0, i = 0; g < G; ++g) for (uint32_t k = 0, gs = (uint32_t)group_count(b, g); k < gs; ++k, ++i) {
         const int v = status_decode(st[i]);
         if (per_proof_status) per_proof_status[i] = v;
         if (v != 0) all_ok[g] = 0;
@@ -527,14 +575,14 @@ int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, s
     for (size_t i = 0; i < n_ranges; ++i) {
         if (batch_of_range && batch_of_range[i] >= n_batches) { set_last_error(w + ": batch index out of range"); return H2V_ERR_BAD_ARGUMENT; }
         const h2v_batch* b = batch_of(i);
-        const size_t n = b->n, gs = n / b->groups;
+        const size_t n = b->n;
         const size_t f = first[i], c = count[i];
         if (!c || f >= n || c > n - f) { set_last_error(w + ": empty range, or a range past the launch's proofs"); return H2V_ERR_BAD_ARGUMENT; }
-        const size_t g = f / gs;
+        const size_t g = group_of(b, f);
         // multipliers are products of the later draws of the proof's OWN group: the last proof of every group has multiplier 1, and a range
         // over two groups could hold two proofs with equal multipliers whose errors cancel
-        if ((f + c - 1) / gs != g) { set_last_error(w + ": a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
-        if (f - g * gs < b->zero_below[g]) { set_last_error(w + ": a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
+        if (group_of(b, f + c - 1) != g) { set_last_error(w + ": a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
+        if (f - group_first(b, g) < b->zero_below[g]) { set_last_error(w + ": a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
     }
     if (!n_ranges) return 0;
     h2v_batch* host = batches[0];
@@ -693,8 +741,29 @@ int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (!b || !groups || groups > MSM_MAX_PROBLEMS / 2 || groups > b->max_proofs) { set_last_error("h2v_batch_set_groups: bad group count"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
+    if (b->copy) hipStreamSynchronize(b->copy); // (the last upload's copies read the vectors cleared below: h2v_batch_set_group_sizes' rule)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
     b->groups = (uint32_t)groups; b->stage = BatchStage::Empty;  // the next upload grows the buffers if the group count needs more
+    b->group_off.clear(); b->group_last.clear();   // (equal groups again after h2v_batch_set_group_sizes)
+    return 0;
+}
+int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups) {
+    static const char who[] = "h2v_batch_set_group_sizes";
+    if (!b || !sizes || !n_groups || n_groups > MSM_MAX_PROBLEMS / 2) { set_last_error(std::string(who) + ": null argument or bad group count"); return H2V_ERR_BAD_ARGUMENT; }
+    size_t total = 0;
+    for (size_t g = 0; g < n_groups; ++g) {
+        if (!sizes[g]) { set_last_error(std::string(who) + ": a group of no proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        if (sizes[g] > b->max_proofs - total) { set_last_error(std::string(who) + ": the sizes exceed the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
+        total += sizes[g];
+    }
+    // (the last upload's copies read the vectors replaced below)
+    if (b->stream) hipStreamSynchronize(b->stream);
+    if (b->aux) hipStreamSynchronize(b->aux);
+    if (b->copy) hipStreamSynchronize(b->copy);
+    if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
+    b->groups = (uint32_t)n_groups; b->stage = BatchStage::Empty;
+    b->group_off.assign(n_groups + 1, 0); b->group_last.assign(total, 0);
+    for (size_t g = 0; g < n_groups; ++g) { b->group_off[g + 1] = b->group_off[g] + (uint32_t)sizes[g]; b->group_last[b->group_off[g + 1] - 1] = 1; }
     return 0;
 }
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups) {
@@ -720,6 +789,7 @@ int h2v_batch_set_stream(h2v_batch* b, void* hip_stream) {
 int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
     if (int rc = require_stage(b, BatchStage::Launched, "h2v_batch_export_accumulators")) return rc;
     if (!device_dst) { set_last_error("h2v_batch_export_accumulators: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (ragged(b)) { set_last_error("h2v_batch_export_accumulators: the batch has groups of unequal size (a record counts the failures of n / groups proofs)"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     if (int rc = join_tail(b)) return rc;   // (the records: pieces if the launch left pieces)
     if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
@@ -728,6 +798,7 @@ int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
 int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, size_t n_parts) {
     int rc;
     if ((rc = require_stage(b, BatchStage::Launched, "h2v_batch_fold_check_enqueue"))) return rc;
+    if (ragged(b)) { set_last_error("h2v_batch_fold_check_enqueue: the batch has groups of unequal size"); return H2V_ERR_BAD_ARGUMENT; }
     StageCommit commit{b};
     if (!device_accumulators || !n_parts) { set_last_error("h2v_batch_fold_check_enqueue: bad argument"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
@@ -752,7 +823,7 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
     static const char who[] = "h2v_batch_identify";
     int rc;
     if ((rc = require_stage(b, BatchStage::Finished, who))) return rc;
-    const uint32_t n = b->n, G = b->groups, gs = n / G;
+    const uint32_t n = b->n, G = b->groups;
     if (!own_records && b->last.folded) { set_last_error(std::string(who) + ": a fold has replaced the batch's own accumulators: pass the records it exported"); return H2V_ERR_BAD_ARGUMENT; }
     // a single proof's check equals SingleStrategy's only when its multiplier is non-zero (h2v_batch_recheck's rule, for every proof)
     for (uint32_t g = 0; g < G; ++g)
@@ -767,7 +838,8 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
     const int* raw = reinterpret_cast<const int*>(b->results_host.p + L.status());
     std::vector<std::vector<int>> st(1, std::vector<int>(n));
     std::vector<uint32_t> failed(G, 0);
-    for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[i / gs]; }
+    for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[group_of(b, i)]; }
+    if (own_records && ragged(b)) { set_last_error(std::string(who) + ": a batch with groups of unequal size exports no records"); return H2V_ERR_BAD_ARGUMENT; }
     if (own_records) {
         std::vector<uint32_t> hdr(4 * (size_t)G);   // [failed, parts, shift, 0] of every record
         H2V_HIP_CHECK(hipMemcpy2DAsync(hdr.data(), 16, own_records, H2V_ACC_RECORD_BYTES, 16, G, hipMemcpyDeviceToHost, s));
@@ -798,7 +870,7 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
         if (e != hipSuccess) { set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
     }
     std::vector<IdentifyStart> start;
-    for (uint32_t g = 0; g < G; ++g) if (!own[g] && gs) start.push_back({0, (size_t)g * gs, gs});
+    for (uint32_t g = 0; g < G; ++g) if (!own[g] && group_count(b, g)) start.push_back({0, group_first(b, g), group_count(b, g)});
     size_t checks = 0;
     if (!start.empty() && (rc = identify_search({b}, start, true, st, &checks))) return rc;
     if (per_proof_status) for (uint32_t i = 0; i < n; ++i) per_proof_status[i] = st[0][i];

@@ -174,6 +174,9 @@ struct MsmWorkspace {
 // not cut (no terms, or a single window) and *out is written as without `split`.
 int msm_enqueue_multi(hipStream_t s, MsmWorkspace& ws, const MsmProblems& pr, MsmSplit* split = nullptr);
 int msm_combine_enqueue(hipStream_t s, MsmWorkspace& ws, const MsmSplit& sp, size_t lds_reserve = 0);
+// msm_enqueue_multi's rule for a launch of problems of these term counts, for callers that must know before any device work: true if
+// every problem fits the per-window LDS sort as it is, or all of them cut into sub-problems that do are at most MSM_MAX_PROBLEMS
+bool msm_cuts_within_limit(const uint32_t* terms, size_t n_problems);
 // `lds_reserve` (msm_combine_enqueue, point_to_bytes_enqueue): bytes of LDS the launch asks for without using them.  The two kernels run
 // on a batch's auxiliary stream BESIDE the pairing, as a handful of waves with a 0.3 ms chain of their own; where one of those waves
 // landed on a SIMD of a pairing workgroup (which issues at raised priority) it crawled — msm_combine_parts took 0.29 ms alone and up to

@@ -129,6 +129,11 @@ static inline bool msm_latency_bound(size_t total_terms) { return total_terms <=
 // Large problems are cut into sub-problems of at most MSM_LDS_SORT_MAX_TERMS terms (msm_enqueue_multi): the workspace is sized for the
 // sub-problems, and for the uncut form too (h2v_tuning.msm_no_term_split).
 static inline uint32_t msm_subproblems(uint32_t n) { return n > MSM_LDS_SORT_MAX_TERMS ? (n + MSM_LDS_SORT_MAX_TERMS - 1) / MSM_LDS_SORT_MAX_TERMS : 1u; }
+bool msm_cuts_within_limit(const uint32_t* terms, size_t n_problems) {
+    size_t subs = 0;
+    for (size_t q = 0; q < n_problems; ++q) subs += msm_subproblems(terms[q]);
+    return subs <= MSM_MAX_PROBLEMS;
+}
 bool MsmWorkspace::covers(uint32_t max_terms, uint32_t max_problems, uint32_t max_per_problem) const {
     if (!max_per_problem || max_per_problem > max_terms) max_per_problem = max_terms;
     return counts.p && max_terms <= cap_terms && max_problems <= cap_parents && max_per_problem <= cap_per_problem;

@@ -86,7 +86,7 @@ int enqueue_group(const ScratchBatch& sb, h2v_batch* b, size_t off, size_t m, si
 int collect_group(const ScratchBatch& sb, h2v_batch* b, size_t off, int* st, int* group_ok, uint8_t* out_left = nullptr, uint8_t* out_right = nullptr) {
     if (int rc = h2v_batch_finish_groups(b, st, group_ok, out_left, out_right, b->groups)) return rc;
     for (uint32_t i = 0; i < b->n; ++i)
-        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[i / (b->n / b->groups)] = 0; }
+        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[group_of(b, i)] = 0; }
     return 0;
 }
 
@@ -626,6 +626,55 @@ int h2v_verify_each(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const 
             if (st[i] == 0 && !gok[i]) st[i] = H2V_ERR_CONSTRAINT_SYSTEM_FAILURE;  // kzg/strategy.rs:171-175
             if (per_proof_status) per_proof_status[off + i] = st[i];
         }
+    }
+    return 0;
+}
+
+// Many AccumulatorStrategy batches of their own sizes: cut, in call order, into launches of unequal groups on the scratch batch
+// (h2v_batch_set_group_sizes), each of at most MSM_MAX_PROBLEMS / 2 batches, H2V_BATCHES_LAUNCH_PROOFS proofs and MSM_MAX_PROBLEMS MSM sub-problems.  The budget is the size
+// at which a grouped launch has long reached its rate (20 x 1024 proofs: DESIGN.md section 6) and whose buffers a context holds anyway for a
+// batch of that size; a batch above it runs alone, as one equal group — exactly h2v_verify_batch's launch.
+#define H2V_BATCHES_LAUNCH_PROOFS 16384u
+int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
+                       size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy,
+                       uint8_t* out_right_xy) {
+    static const char who[] = "h2v_verify_batches";
+    if (!ctx || (n_batches && (!batch_sizes || !batch_ok))) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    size_t n = 0;
+    for (size_t i = 0; i < n_batches; ++i) {
+        if (!batch_sizes[i]) { set_last_error(std::string(who) + ": a batch of no proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        if (batch_sizes[i] > ((size_t)1 << 22) || n + batch_sizes[i] > ((size_t)1 << 30)) { set_last_error(std::string(who) + ": too many proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        n += batch_sizes[i];
+    }
+    int rc;
+    std::vector<uint8_t> os_rand;
+    if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
+    ScratchBatch sb(ctx);
+    if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, n_instance_columns, col_lens))) return rc;
+    const Plan& pl = sb.pin.pd->host;
+    // the launches: [first batch, batches, first proof, proofs].  A launch is closed by the batch count, by the proof budget, and where the
+    // next batch would take the launch's MSM problems, cut into sub-problems, past what a launch holds — the rule an upload of unequal
+    // groups is refused by (upload_impl): every launch cut here passes it, and a batch left alone runs as one equal group
+    struct Cut { size_t i0, k, off, m; };
+    std::vector<Cut> cuts;
+    size_t capacity = 1;
+    const bool no_split = ctx->tuning.msm_no_term_split != 0;   // (then nothing is cut and nothing refused)
+    for (size_t i = 0, off = 0; i < n_batches;) {
+        Cut c{i, 0, off, 0};
+        while (i < n_batches && c.k < MSM_MAX_PROBLEMS / 2 && (!c.k || c.m + batch_sizes[i] <= H2V_BATCHES_LAUNCH_PROOFS) &&
+               (!c.k || no_split || groups_cut_within_limit(pl, batch_sizes + c.i0, c.k + 1))) { c.m += batch_sizes[i]; ++c.k; ++i; }
+        off += c.m; capacity = std::max(capacity, c.m);
+        cuts.push_back(c);
+    }
+    if ((rc = sb.take(capacity, pl.n_instance_values))) return rc;
+    for (const Cut& c : cuts) {
+        // (one batch alone: the equal-groups launch, whatever its size)
+        if ((rc = c.k == 1 ? h2v_batch_set_groups(sb.b, 1) : h2v_batch_set_group_sizes(sb.b, batch_sizes + c.i0, c.k)) ||
+            (rc = upload_impl(sb.b, c.m, sb.flat.data() + c.off * pl.proof_len, pl.proof_len, sb.iflat.data() + c.off * (size_t)pl.n_instance_values * 32, sb.cols.size(),
+                              sb.cols.data(), rand32 + 32 * c.off, c.m)) ||
+            (rc = launch_impl(sb.b, 1)) ||
+            (rc = collect_group(sb, sb.b, c.off, per_proof_status ? per_proof_status + c.off : nullptr, batch_ok + c.i0, out_left_xy ? out_left_xy + 64 * c.i0 : nullptr,
+                                out_right_xy ? out_right_xy + 64 * c.i0 : nullptr))) return rc;
     }
     return 0;
 }

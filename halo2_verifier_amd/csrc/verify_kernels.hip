@@ -9,6 +9,8 @@
 //   k_instance_eval   one workgroup per proof       Lagrange sum over a wide instance column   lib.rs:173-218, poly/domain.rs:187-212
 //   k_frvm            one lane per proof            the compiled Fr program            lib.rs:173-346, shplonk.rs:202-264
 //   k_fold_shared     one workgroup per shared base sum over proofs of the scalars of VK-wide bases
+//   k_seg_mult_tiles ...  a segmented two-level scan  the same for groups of unequal size (h2v_batch_set_group_sizes)
+//   k_fold_shared_offsets one workgroup per (shared base, group)  k_fold_shared over groups given by offsets
 //   k_fold_ranges     one wave per (shared base, range)   the same over arbitrary ranges of proofs, of one batch or several (h2v_batches_recheck)
 //
 // Layouts are chosen so that lanes (= proofs) are contiguous in the fastest dimension for
@@ -450,6 +452,66 @@ __global__ void __launch_bounds__(MULT_TILE) k_mult_apply(Fr* __restrict__ mult,
     if (j < n && blockIdx.x + 1 < tiles) mult[(size_t)g * n + j] = mult[(size_t)g * n + j] * tile_prod[(size_t)g * tiles + blockIdx.x];
 }
 
+// The same multipliers for groups of UNEQUAL size (h2v_batch_set_group_sizes): mult[j] = the product of the later draws of j's own
+// group, as a SEGMENTED suffix scan over the whole draw array — work proportional to n whatever the sizes, where a grid of (tiles of
+// the largest group, groups) would launch mostly workgroups that leave at once.  last[j] != 0 marks the last proof of a group.  The
+// scan carries a pair (v, closed) per span [i, k] of draws: v = the product of the draws from i to the end of i's group or k, whichever
+// comes first; closed = i's group ends inside the span.  (a, b) of two adjacent spans combine to a if a is closed, else (a.v b.v, b.closed).
+//   k_seg_mult_tiles       a workgroup per tile of MULT_TILE draws: mult[j] <- the later draws of j's group inside the tile; the tile's pair;
+//                          open_from[tile] <- the first thread whose group goes on behind the tile (the closed spans are a prefix of the tile)
+//   k_seg_mult_scan_tiles  one workgroup: tile_prod[tile] <- what the later tiles give a group that is still open at the tile's end
+//   k_seg_mult_apply       mult[j] <- mult[j] * tile_prod[j's tile] for the threads from open_from[tile] on
+// part[t] <- the pair of the span [t, T); every thread calls it (fr_suffix_scan's barriers)
+template <uint32_t T> __device__ __forceinline__ void fr_seg_suffix_scan(Fr* part, uint32_t* closed, uint32_t t) {
+    __syncthreads();
+    for (uint32_t d = 1; d < T; d <<= 1) {
+        const bool has = t + d < T;
+        const Fr v = has ? part[t + d] : Fr::one();
+        const uint32_t c = has ? closed[t + d] : 0u;
+        __syncthreads();
+        if (!closed[t]) { part[t] = part[t] * v; closed[t] = c; }   // (closed[t] is read and written by thread t alone in this phase)
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_tiles(const uint8_t* __restrict__ tail, const uint8_t* __restrict__ last, uint32_t n, Fr* __restrict__ mult,
+                                                              Fr* __restrict__ tile_prod, uint32_t* __restrict__ tile_closed, uint32_t* __restrict__ open_from) {
+    __shared__ Fr part[MULT_TILE];
+    __shared__ uint32_t closed[MULT_TILE];
+    const uint32_t t = threadIdx.x, j = blockIdx.x * MULT_TILE + t;
+    Fr r = Fr::one();
+    uint32_t end = 1;   // (past the draws: one-element groups of their own, behind the last group's end)
+    if (j < n) { Fr::from_bytes(tail + 32 * (size_t)j, r); end = last[j] ? 1u : 0u; }
+    part[t] = r; closed[t] = end;
+    fr_seg_suffix_scan<MULT_TILE>(part, closed, t);
+    if (j < n) mult[j] = (end || t + 1 == MULT_TILE) ? Fr::one() : part[t + 1];
+    if (!closed[t] && (t == 0 || closed[t - 1])) open_from[blockIdx.x] = t;
+    if (t + 1 == MULT_TILE && closed[t]) open_from[blockIdx.x] = MULT_TILE;
+    if (t == 0) { tile_prod[blockIdx.x] = part[0]; tile_closed[blockIdx.x] = closed[0]; }
+}
+__global__ void __launch_bounds__(1024) k_seg_mult_scan_tiles(Fr* __restrict__ tile_prod, const uint32_t* __restrict__ tile_closed, uint32_t tiles) {
+    __shared__ Fr part[1024];
+    __shared__ uint32_t closed[1024];
+    const uint32_t t = threadIdx.x;
+    Fr carry = Fr::one();   // the value of all tiles behind the chunk (behind the last tile: nothing, no group goes on there; its closed bit is never needed: the last draw closes the last group)
+    for (uint32_t hi = tiles; hi > 0; hi = hi > 1024 ? hi - 1024 : 0) {
+        const uint32_t lo = hi > 1024 ? hi - 1024 : 0, i = lo + t;
+        part[t] = i < hi ? tile_prod[i] : Fr::one();
+        closed[t] = i < hi ? tile_closed[i] : 0u;   // (the combination's identity)
+        fr_seg_suffix_scan<1024>(part, closed, t);
+        // the later tiles of the chunk, then the carry
+        Fr later = carry;
+        if (t + 1 < 1024) later = closed[t + 1] ? part[t + 1] : part[t + 1] * carry;
+        const Fr all = closed[0] ? part[0] : part[0] * carry;
+        __syncthreads();   // (part is written again in the next round)
+        if (i < hi) tile_prod[i] = later;
+        carry = all;
+    }
+}
+__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_apply(Fr* __restrict__ mult, uint32_t n, const Fr* __restrict__ tile_prod, const uint32_t* __restrict__ open_from) {
+    const uint32_t j = blockIdx.x * MULT_TILE + threadIdx.x;
+    if (j < n && threadIdx.x >= open_from[blockIdx.x]) mult[j] = mult[j] * tile_prod[blockIdx.x];
+}
+
 // Instance evaluation for wide instance vectors (lib.rs:173-218; l_i_range, poly/domain.rs:187-212):
 //   E = sum_j a_j * l_{j-rot}(x),   l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
 // One workgroup per proof.  Thread t owns j = t, t + 256, ...: omega^(j-rot) advances by omega^256 per step.  The
@@ -665,6 +727,26 @@ __global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ shar
     }
 }
 
+// the same for groups of unequal size: group g owns the proofs [off[g], off[g + 1])
+__global__ void __launch_bounds__(256) k_fold_shared_offsets(const Fr* __restrict__ shared, uint32_t n, uint32_t np, const uint32_t* __restrict__ off, uint32_t* __restrict__ msm_scal) {
+    __shared__ Fr red[256];
+    const uint32_t j = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
+    const uint32_t p0 = off[g], p1 = off[g + 1];   // (validated on the host: p0 < p1 <= n)
+    Fr acc = Fr::zero();
+    for (uint32_t p = p0 + t; p < p1; p += 256) acc = acc + shared[(size_t)j * n + p];
+    red[t] = acc;
+    __syncthreads();
+    for (uint32_t d = 128; d > 0; d >>= 1) {
+        if (t < d) red[t] = red[t] + red[t + d];
+        __syncthreads();
+    }
+    if (t == 0) {
+        uint32_t raw[8]; red[0].to_raw(raw);
+        uint32_t* dst = msm_scal + ((size_t)n * np + (size_t)g * gridDim.x + j) * 8;
+        for (int i = 0; i < 8; ++i) dst[i] = raw[i];
+    }
+}
+
 // out[(ranges[r].out + j) * 8] = canonical( sum over the proofs p of range r of ranges[r].shared[j][p] ).  The ranges of a re-check
 // are mostly short (a search ends on single proofs): one wave per (base, range), a wave-wide tree in LDS.  The ranges of one launch
 // may belong to batches of different keys (h2v_batches_recheck): the grid is as wide as the most VK-wide bases of any of them, and the
@@ -746,6 +828,19 @@ int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, u
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
+size_t ragged_multipliers_tiles(uint32_t n) { return ((size_t)n + MULT_TILE - 1) / MULT_TILE; }
+int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8_t* d_last, uint32_t n, Fr* d_mult, Fr* d_tile_prod, uint32_t* d_tile_words) {
+    const uint32_t tiles = (uint32_t)ragged_multipliers_tiles(n);
+    if (!tiles) return 0;
+    uint32_t* tile_closed = d_tile_words; uint32_t* open_from = d_tile_words + tiles;
+    hipLaunchKernelGGL(k_seg_mult_tiles, dim3(tiles), dim3(MULT_TILE), 0, s, d_tail, d_last, n, d_mult, d_tile_prod, tile_closed, open_from);
+    if (tiles > 1) {
+        hipLaunchKernelGGL(k_seg_mult_scan_tiles, dim3(1), dim3(1024), 0, s, d_tile_prod, (const uint32_t*)tile_closed, tiles);
+        hipLaunchKernelGGL(k_seg_mult_apply, dim3(tiles), dim3(MULT_TILE), 0, s, d_mult, n, (const Fr*)d_tile_prod, (const uint32_t*)open_from);
+    }
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 __global__ void __launch_bounds__(256) k_gather_multipliers(const Fr* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, Fr* __restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = src[idx[i]];
@@ -796,6 +891,12 @@ int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots) {
 int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal) {
     if (!n_shared) return 0;
     hipLaunchKernelGGL(k_fold_shared, dim3(n_shared, groups), dim3(256), 0, s, d_shared, n, np, n / groups, d_msm_scal);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int fold_shared_offsets_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, const uint32_t* d_off, uint32_t* d_msm_scal) {
+    if (!n_shared || !groups) return 0;
+    hipLaunchKernelGGL(k_fold_shared_offsets, dim3(n_shared, groups), dim3(256), 0, s, d_shared, n, np, d_off, d_msm_scal);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

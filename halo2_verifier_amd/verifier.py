@@ -10,6 +10,7 @@ import collections
 import contextlib
 import ctypes
 import enum
+import numbers
 
 from . import _lib
 from ._lib import H2VError, check
@@ -142,6 +143,21 @@ def _sizes(values):
     """values as a size_t array (of at least one element)"""
     values = list(values)
     return (ctypes.c_size_t * max(len(values), 1))(*values)
+
+
+MAX_GROUPS = 512   # groups of one launch: half of the MSM's problems per launch (MSM_MAX_PROBLEMS / 2)
+
+
+def _group_sizes(sizes, what="group"):
+    """The sizes of the groups of a launch (or of the batches of a call), checked: integers >= 1.  -> list of ints"""
+    out = []
+    for v in sizes:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"a {what} size must be an integer, got {type(v).__name__}")
+        if v < 1:
+            raise ValueError(f"every {what} holds at least one proof, got a size of {int(v)}")
+        out.append(int(v))
+    return out
 
 
 def _rand_bytes(rand, n):
@@ -406,6 +422,30 @@ class Context:
                                                       ctypes.byref(r.checks)))
         self.last_range_checks, self.last_seed_ok = r.checks.value, bool(r.seed_ok.value)
         return r.result()
+
+    def verify_batches(self, batches, rand=None):
+        """Many AccumulatorStrategy batches of their own sizes in few launches (h2v_verify_batches).  batches: list of (proofs, instances),
+        each as verify_batch takes them and none empty; one instance shape for the whole call; rand: one scalar per proof of the call, batch
+        after batch, or None.  Returns one (batch_ok, statuses, left_xy, right_xy) per batch: what verify_batch returns for it with its draws."""
+        batches = [(list(p), list(i)) for p, i in batches]
+        for p, i in batches:
+            if len(i) != len(p):
+                raise ValueError(f"{len(p)} proofs but {len(i)} instance lists in one batch")
+        sizes = _group_sizes((len(p) for p, _ in batches), "batch")
+        m = _marshal_batch([self], [x for p, _ in batches for x in p], [x for _, i in batches for x in i])
+        if not m.uniform:
+            raise ValueError("verify_batches takes one instance shape per call")
+        rb = _rand_bytes(rand, m.n)
+        k = len(sizes)
+        st = (ctypes.c_int * max(m.n, 1))()
+        ok = (ctypes.c_int * max(k, 1))()
+        left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
+        check(self._lib.h2v_verify_batches(self._h, k, _sizes(sizes), *m.head[1:], m.ncols[0], m.shape0(), rb, st, ok, left, right))
+        out, at = [], 0
+        for g, sz in enumerate(sizes):
+            out.append((bool(ok[g]), list(st[at:at + sz]), left.raw[64 * g:64 * g + 64], right.raw[64 * g:64 * g + 64]))
+            at += sz
+        return out
 
     def verify_each(self, proofs, instances):
         m = _marshal_batch([self], proofs, instances)
@@ -758,7 +798,7 @@ class Batch:
         ctx._adopt(self)
         self.max_proofs = max_proofs
         self.n = 0
-        self.groups = 1
+        self.groups, self.group_sizes = 1, None
         if stream is not None:
             self.set_stream(stream)
         if groups != 1:
@@ -768,7 +808,19 @@ class Batch:
         """`groups` independent AccumulatorStrategy batches per upload/launch (h2v_batch_set_groups): group g owns proofs
         [g*n/groups, (g+1)*n/groups) and the same slice of the draws; each has its own accumulators and pairing."""
         check(self._lib.h2v_batch_set_groups(self._h, groups))
-        self.groups = groups
+        self.groups, self.group_sizes = groups, None
+
+    def set_group_sizes(self, sizes):
+        """Groups of unequal size (h2v_batch_set_group_sizes): group g owns the next sizes[g] proofs of later uploads and the same slice
+        of the draws, and is exactly verify_batch over them.  1 to 512 sizes, each an integer >= 1, summing to at most max_proofs.  An
+        upload then needs sum(sizes) proofs and one draw per proof (or None).  set_groups returns the batch to equal groups."""
+        sizes = _group_sizes(sizes)
+        if not 1 <= len(sizes) <= MAX_GROUPS:
+            raise ValueError(f"a launch holds 1 to {MAX_GROUPS} groups, got {len(sizes)}")
+        if sum(sizes) > self.max_proofs:
+            raise ValueError(f"the group sizes sum to {sum(sizes)}, above the batch capacity of {self.max_proofs}")
+        check(self._lib.h2v_batch_set_group_sizes(self._h, _sizes(sizes), len(sizes)))
+        self.groups, self.group_sizes = len(sizes), sizes
 
     def close(self):
         if self._h:
@@ -800,6 +852,11 @@ class Batch:
             raise ValueError("rand_tail is not a whole number of 32-byte scalars")
         cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
         nt = len(rand_tail) // 32 if rand_tail is not None else 0
+        if getattr(self, "group_sizes", None) is not None:
+            if n != sum(self.group_sizes):
+                raise ValueError(f"the group sizes sum to {sum(self.group_sizes)} proofs, got {n}")
+            if rand_tail is not None and nt != n:
+                raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
         return n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt
 
     def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None):

@@ -303,6 +303,20 @@ int h2v_verify_each(h2v_ctx* ctx, size_t n,
                     const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
                     int* per_proof_status);
 
+/* n_batches x h2v_verify_batch in few launches: batch i holds batch_sizes[i] proofs (>= 1, else H2V_ERR_BAD_ARGUMENT), and the proofs,
+ * instances and draws of all batches sit back to back in call order (n = the sum of the sizes entries each; one instance shape; rand32
+ * NULL = draw from the OS RNG).  per_proof_status[n], batch_ok[n_batches] and out_left_xy / out_right_xy (n_batches x 64 bytes, may
+ * be NULL) hold, for batch i, what h2v_verify_batch returns over its slice.  The batches are cut, in call order, into launches of
+ * groups of unequal size (h2v_batch_set_group_sizes) of at most 512 batches and 16384 proofs each, and of at most the 1024 MSM
+ * sub-problems a launch holds (a batch whose MSM problem exceeds 16384 terms counts for more than two: fewer batches then share its
+ * launch — the call never returns h2v_batch_upload's H2V_ERR_UNSUPPORTED for its own cut); a batch above 16384 proofs, or one left
+ * alone by these rules, runs as h2v_verify_batch does.  Every argument is checked before any device work. */
+int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes,
+                       const uint8_t* const* proofs, const size_t* proof_lens,
+                       const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
+                       const uint8_t* rand32,
+                       int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
+
 /* Which proofs made a batch fail: h2v_verify_batch, plus the proofs that fail the pairing.  batch_ok / out_left_xy / out_right_xy
  * are exactly what h2v_verify_batch returns for the same arguments; per_proof_status[i] is what h2v_verify_each returns for proof i
  * (0, the instance / transcript / opening errors, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE).  When the batch's pairing passes this costs
@@ -407,6 +421,16 @@ int h2v_batch_finish(h2v_batch* b, int* per_proof_status, int* batch_ok, uint8_t
  * every kernel launched once for all of them (the pairing and the tail of the MSM are latency-bound single-wave kernels, so G
  * of them side by side cost the time of one).  n and n_tail of later uploads must be multiples of `groups`.  Call before upload. */
 int h2v_batch_set_groups(h2v_batch* b, size_t groups);
+/* Groups of UNEQUAL size: group g owns the next sizes[g] proofs of later uploads, in order, and the same slice of the draws — exactly
+ * h2v_verify_batch over its proofs with its draws, as h2v_batch_set_groups defines a group.  1 <= n_groups <= 512 (half the MSM's
+ * problems per launch), every size >= 1 (a zero size is H2V_ERR_BAD_ARGUMENT), the sizes sum to at most max_proofs.  Leaves the batch
+ * empty, as h2v_batch_set_groups does; a later h2v_batch_set_groups returns it to equal groups.  An upload then needs n = the sum of
+ * the sizes and takes ONE draw per proof (rand32_tail NULL, or n_tail == n).  launch, upload_launch, finish_groups, accumulators,
+ * recheck, identify and h2v_batches_recheck work as on equal groups (a range must lie inside one group, found from the sizes);
+ * h2v_batch_export_accumulators and h2v_batch_fold_check_enqueue refuse the batch (H2V_ERR_BAD_ARGUMENT): a sharded launch of unequal
+ * groups would need a tail of draws per group.  An upload whose MSM problems, cut into sub-problems of at most 16384 terms, would be
+ * more than a launch holds (1024) is refused with H2V_ERR_UNSUPPORTED before any device work. */
+int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups);
 /* As h2v_batch_finish for a grouped batch: group_ok[n_groups], out_left_xy / out_right_xy = n_groups x 64 bytes. */
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups);
 /* Pairing checks of ranges of the last FINISHED launch of b (h2v_batch_finish / _finish_groups), on its resident per-proof Guard

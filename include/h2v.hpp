@@ -354,6 +354,46 @@ inline RangeChecks recheck(const std::vector<h2v_batch*>& batches, const std::ve
     return detail::recheck(batches.data(), batches.size(), true, ranges);
 }
 
+// Groups of unequal size on a staged batch (h2v_batch_set_group_sizes): group g owns the next sizes[g] proofs of later uploads and the
+// same slice of the draws.  1 to 512 sizes, each at least 1.
+inline void set_group_sizes(h2v_batch* b, const std::vector<size_t>& sizes) {
+    for (size_t v : sizes) if (!v) throw Failure(H2V_ERR_BAD_ARGUMENT, "a group of no proofs");
+    if (sizes.empty() || sizes.size() > 512) throw Failure(H2V_ERR_BAD_ARGUMENT, "a launch holds 1 to 512 groups");
+    check(h2v_batch_set_group_sizes(b, sizes.data(), sizes.size()));
+}
+
+// Many AccumulatorStrategy batches of their own sizes in few launches (h2v_verify_batches): every batch is a list of (instances, proof)
+// in verify_proof order and none is empty; one instance shape for the whole call; rand32: one 32-byte draw per proof of the call, batch
+// after batch, or empty = OS RNG.  -> per batch what its own AccumulatorStrategy::finalize() gives: verdict, statuses, the two channels.
+struct BatchItem { Instances instances; Bytes proof; };
+struct BatchResult { bool ok = false; std::vector<int> statuses; Bytes left, right; };
+inline std::vector<BatchResult> verify_batches(const Context& ctx, const std::vector<std::vector<BatchItem>>& batches, const Bytes& rand32 = Bytes()) {
+    detail::Marshalled m(true);
+    m.add_key(ctx.handle());
+    std::vector<size_t> sizes;
+    for (const auto& batch : batches) {
+        if (batch.empty()) throw Failure(H2V_ERR_BAD_ARGUMENT, "a batch of no proofs");
+        sizes.push_back(batch.size());
+        for (const BatchItem& it : batch) m.add(0, it.instances, it.proof);
+    }
+    const size_t n = m.n(), k = sizes.size();
+    if (!m.uniform) throw Failure(H2V_ERR_BAD_ARGUMENT, "verify_batches takes one instance shape per call");
+    if (!rand32.empty() && rand32.size() != 32 * n) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per proof");
+    std::vector<int> st(n ? n : 1, 0), ok(k ? k : 1, 0);
+    Bytes left(64 * (k ? k : 1), 0), right(64 * (k ? k : 1), 0);
+    sizes.resize(k ? k : 1, 0);
+    check(h2v_verify_batches(ctx.handle(), k, sizes.data(), m.proofs.data(), m.lens.data(), m.insts.data(), m.ncols[0], m.shape0(), rand32.empty() ? nullptr : rand32.data(),
+                             st.data(), ok.data(), left.data(), right.data()));
+    std::vector<BatchResult> out(k);
+    for (size_t g = 0, at = 0; g < k; at += sizes[g], ++g) {
+        out[g].ok = ok[g] != 0;
+        out[g].statuses.assign(st.begin() + at, st.begin() + at + sizes[g]);
+        out[g].left.assign(left.begin() + 64 * g, left.begin() + 64 * g + 64);
+        out[g].right.assign(right.begin() + 64 * g, right.begin() + 64 * g + 64);
+    }
+    return out;
+}
+
 // kzg/strategy.rs:143-181: one pairing per proof, checked inside verify_proof
 class SingleStrategy {
 public:

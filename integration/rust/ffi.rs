@@ -95,6 +95,9 @@ extern "C" {
     pub fn h2v_accumulator_drop_legs(a: *mut h2v_accumulator, legs: *const usize, n_drop: usize) -> c_int;
     pub fn h2v_verify_each(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, per_proof_status: *mut c_int) -> c_int;
+    pub fn h2v_verify_batches(ctx: *mut h2v_ctx, n_batches: usize, batch_sizes: *const usize, proofs: *const *const u8, proof_lens: *const usize,
+                              instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, rand32: *const u8,
+                              per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_verify_batch_identify(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                                      instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, rand32: *const u8,
                                      per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8,
@@ -123,6 +126,7 @@ extern "C" {
                                    n_instance_columns: usize, col_lens: *const usize, rand32_tail: *const u8, n_tail: usize, with_pairing: c_int) -> c_int;
     pub fn h2v_batch_finish(b: *mut h2v_batch, per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_batch_set_groups(b: *mut h2v_batch, groups: usize) -> c_int;
+    pub fn h2v_batch_set_group_sizes(b: *mut h2v_batch, sizes: *const usize, n_groups: usize) -> c_int;
     pub fn h2v_batch_finish_groups(b: *mut h2v_batch, per_proof_status: *mut c_int, group_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8,
                                    n_groups: usize) -> c_int;
     pub fn h2v_batch_recheck(b: *mut h2v_batch, n_ranges: usize, first: *const usize, count: *const usize, range_ok: *mut c_int,
