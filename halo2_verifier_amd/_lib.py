@@ -55,6 +55,9 @@ SIGNATURES = {
     "h2v_accumulator_journal_begin": (c_int, [c_vp, c_sz]),
     "h2v_accumulator_check_legs": (c_int, [c_vp, c_sz, c_szp, c_szp, c_szp, c_intp]),
     "h2v_accumulator_drop_legs": (c_int, [c_vp, c_szp, c_sz]),
+    "h2v_accumulator_merge": (c_int, [c_vp, ctypes.POINTER(c_vp), c_sz, c_u8p, c_u8p]),
+    "h2v_accumulator_export_state": (c_int, [c_vp, c_u8p]),
+    "h2v_accumulator_merge_states": (c_int, [c_vp, c_u8p, c_sz, c_u8p, c_u8p]),
     "h2v_verify_batches": (c_int, [c_vp, c_sz, c_szp, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_verify_each": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_intp]),
     "h2v_verify_batch_identify": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p, c_szp]),

@@ -24,6 +24,14 @@
 //     whole-point records, one fold over them writes the accumulator as the last step; the host's bookkeeping follows the synchronise.
 // Entries never move in device memory: the host keeps entry -> slot and hands that map to the kernels, so a call that fails on the way
 // leaves nothing half-moved.  A slot is written before its entry is visible (the commit rule of the accumulator, extended).
+//
+// Merging (h2v_accumulator_merge / _export_state / _merge_states): one pairing for K accumulators.  With draws c_1 .. c_K, none zero,
+//     (L, R) <- (L, R) + sum_k c_k (L_k, R_k),     the counters += the sources'
+// — per source DualMSM::scale then add_msm (poly/kzg/msm.rs:173-183) on a copy; dst is not scaled and the sources are not changed.  The
+// sources' pairs reach a staging array of dst (device-to-device copies, or the lift of exported states from their bytes), one
+// k_accumulator_scale launch of K workgroups writes c_k (L_k, R_k) as whole-point records, and one k_accumulator_merge_fold launch
+// (util.hip) scatters them into the journal slots of K new entries (M = 1 each: the invariant holds as it stands) and writes the
+// accumulator, as the last step.  Soundness: include/h2v.h.
 #include "../../include/h2v.h"
 #include "batch.h"
 #include <string.h>
@@ -53,6 +61,13 @@ struct h2v_accumulator {
     DevBuf<uint8_t> j_records;       // [j_cap] drop_legs: W_e sum_e of the kept entries as whole-point records
     DevBuf<uint32_t> j_words;        // drop_legs: [8 K] W_e of the K kept entries, [K] their slots; check_legs: [9 j_cap ..] a verdict per slot
     std::vector<uint32_t> j_host;    // what j_words is copied from and to
+    // merge / merge_states: the K sources of the call in flight
+    DevBuf<G1J> m_pairs;             // [2 K] the sources' points, gathered (merge) or lifted from their bytes (merge_states)
+    DevBuf<uint8_t> m_records;       // [K] c_k (L_k, R_k) as whole-point records
+    DevBuf<uint32_t> m_words;        // [8 K] the draws, [K] the journal slots of the K new entries, [2 K] merge_states: the points' flags
+    DevBuf<uint8_t> m_bytes;         // [128 K] merge_states: the states' affine bytes
+    DevBuf<G1A> m_affine;            // [2 K] merge_states
+    std::vector<uint32_t> m_host;    // what m_words is copied from and to
 };
 
 namespace {
@@ -90,6 +105,48 @@ void commit_entry(h2v_accumulator* a, const Fr& M, size_t n_proofs, size_t n_fai
     a->free_slots.pop_back();
 }
 void journal_off(h2v_accumulator* a) { a->j_cap = 0; a->entries.clear(); a->free_slots.clear(); }
+
+struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } };
+
+// What h2v_accumulator_merge and h2v_accumulator_merge_states share in front of any device work: the draws (canonical, none zero; null = OS
+// draws) and room in the journal for K entries.
+int merge_args(h2v_accumulator* a, const char* who, size_t K, const uint8_t*& draws32, std::vector<uint8_t>& os_draws) {
+    if (int rc = resolve_draws(draws32, K, os_draws, who, true)) return rc;
+    if (a->j_cap && a->entries.size() + K > a->j_cap) { set_last_error(std::string(who) + ": the journal has fewer free entries than sources"); return H2V_ERR_UNSUPPORTED; }
+    return 0;
+}
+int merge_reserve(h2v_accumulator* a, size_t K, bool states) {
+    int rc;
+    if ((rc = a->m_pairs.reserve(2 * K)) || (rc = a->m_records.reserve((size_t)H2V_ACC_RECORD_BYTES * K)) || (rc = a->m_words.reserve(11 * K))) return rc;
+    if (states && ((rc = a->m_bytes.reserve(128 * K)) || (rc = a->m_affine.reserve(2 * K)))) return rc;
+    a->m_host.resize(11 * K);
+    return 0;
+}
+// The merge over K pairs already on the device (m_pairs, written by work enqueued on the accumulator's stream):
+//     (L, R) <- (L, R) + sum_k c_k (L_k, R_k),   the counters += the sources', and with the journal on an entry per source, in call order,
+//     whose sum is c_k (L_k, R_k) and whose M is 1 (so (L, R) = sum_e W_e sum_e holds as it stands).
+// One k_accumulator_scale launch of K one-wave workgroups writes the K records; one k_accumulator_merge_fold launch scatters them into the
+// journal slots and writes the accumulator, as the last step.  The counters and the entries follow the synchronise.
+int merge_impl(h2v_accumulator* a, const char* who, size_t K, const uint8_t* draws32, const size_t* src_proofs, const size_t* src_failed, Drain& drain) {
+    uint32_t* h = a->m_host.data();
+    memcpy(h, draws32, 32 * K);
+    for (size_t k = 0; k < K && a->j_cap; ++k) h[8 * K + k] = a->free_slots[a->free_slots.size() - 1 - k];   // the lowest free slots, in call order
+    int rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(a->m_words.p, h, 4 * 9 * K, hipMemcpyHostToDevice, a->stream));
+    if ((rc = accumulator_scale_many_enqueue(a->stream, a->m_pairs.p, nullptr, a->m_words.p, (uint32_t)K, a->m_records.p))) return rc;
+    if ((rc = accumulator_merge_fold_enqueue(a->stream, a->m_records.p, (uint32_t)K, 0, a->m_words.p + 8 * K, a->j_cap ? a->j_sums.p : nullptr, a->acc.p))) return rc;
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    for (size_t k = 0; k < K; ++k) {
+        a->n_proofs += src_proofs[k]; a->n_failed += src_failed[k];
+        commit_entry(a, Fr::one(), src_proofs[k], src_failed[k]);
+    }
+    return 0;
+}
+uint32_t load_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+uint64_t load_u64(const uint8_t* p) { return (uint64_t)load_u32(p) | ((uint64_t)load_u32(p + 4) << 32); }
+void store_u32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); }
+void store_u64(uint8_t* p, uint64_t v) { store_u32(p, (uint32_t)v); store_u32(p + 4, (uint32_t)(v >> 32)); }
 
 }  // namespace
 
@@ -150,7 +207,7 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     memcpy(a->host_scalar, m_bytes, 32);
     H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
     // on an error past this point the stream is drained before the call returns; the accumulator is written by the last step only
-    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain{a->stream};
+    Drain drain{a->stream};
     // the scale step first, beside the groups: staging record <- M (L, R)
     H2V_HIP_CHECK(hipMemcpyAsync(a->scalar.p, a->host_scalar, 32, hipMemcpyHostToDevice, a->stream));
     if ((rc = accumulator_scale_enqueue(a->stream, a->acc.p, a->scalar.p, a->records.p))) return rc;
@@ -294,7 +351,7 @@ int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_d
         W = W * a->entries[kept[i]].M;
     }
     H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
-    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain{a->stream};
+    Drain drain{a->stream};
     int rc;
     H2V_HIP_CHECK(hipMemcpyAsync(a->j_words.p, h, 4 * 9 * K, hipMemcpyHostToDevice, a->stream));
     if ((rc = accumulator_scale_many_enqueue(a->stream, a->j_sums.p, a->j_words.p + 8 * K, a->j_words.p, (uint32_t)K, a->j_records.p))) return rc;
@@ -312,6 +369,82 @@ int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_d
     std::sort(a->free_slots.begin(), a->free_slots.end(), std::greater<uint32_t>());
     a->entries.swap(next);
     a->n_proofs = n_proofs; a->n_failed = n_failed;
+    return 0;
+}
+
+int h2v_accumulator_merge(h2v_accumulator* dst, h2v_accumulator* const* srcs, size_t n_src, const uint8_t* draws32, uint8_t* out_draws32) {
+    const char* who = "h2v_accumulator_merge";
+    // every argument check comes before the first HIP call
+    if (!dst || (n_src && !srcs)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n_src > H2V_ACC_MERGE_MAX) { set_last_error(std::string(who) + ": more than H2V_ACC_MERGE_MAX sources"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t k = 0; k < n_src; ++k) {
+        if (!srcs[k]) { set_last_error(std::string(who) + ": null source"); return H2V_ERR_BAD_ARGUMENT; }
+        if (srcs[k] == dst) { set_last_error(std::string(who) + ": a source is the destination"); return H2V_ERR_BAD_ARGUMENT; }
+        for (size_t j = 0; j < k; ++j) if (srcs[j] == srcs[k]) { set_last_error(std::string(who) + ": a source given twice"); return H2V_ERR_BAD_ARGUMENT; }
+        if (srcs[k]->ctx->device != dst->ctx->device) { set_last_error(std::string(who) + ": a source on another device than the destination"); return H2V_ERR_BAD_ARGUMENT; }
+        if (!same_srs(srcs[k]->ctx->params, dst->ctx->params)) { set_last_error(std::string(who) + ": a source over other params than the destination (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    std::vector<uint8_t> os_draws;
+    int rc;
+    if ((rc = merge_args(dst, who, n_src, draws32, os_draws))) return rc;
+    if (!n_src) return 0;
+    H2V_HIP_CHECK(hipSetDevice(dst->ctx->device));
+    if ((rc = merge_reserve(dst, n_src, false))) return rc;
+    Drain drain{dst->stream};
+    // the sources are idle (every call of the object ends in a synchronise): their pairs are gathered in the destination's stream order
+    std::vector<size_t> np(n_src), nf(n_src);
+    for (size_t k = 0; k < n_src; ++k) {
+        H2V_HIP_CHECK(hipMemcpyAsync(dst->m_pairs.p + 2 * k, srcs[k]->acc.p, 2 * sizeof(G1J), hipMemcpyDeviceToDevice, dst->stream));
+        np[k] = srcs[k]->n_proofs; nf[k] = srcs[k]->n_failed;
+    }
+    if ((rc = merge_impl(dst, who, n_src, draws32, np.data(), nf.data(), drain))) return rc;
+    if (out_draws32) memcpy(out_draws32, draws32, 32 * n_src);
+    return 0;
+}
+
+int h2v_accumulator_export_state(h2v_accumulator* a, uint8_t out[H2V_ACC_STATE_BYTES]) {
+    if (!a || !out) { set_last_error("h2v_accumulator_export_state: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    uint8_t xy[128];
+    if (int rc = read_points(a, "h2v_accumulator_export_state", nullptr, xy, xy + 64)) return rc;
+    store_u32(out, H2V_ACC_STATE_MAGIC); store_u32(out + 4, H2V_ACC_STATE_VERSION);
+    store_u64(out + 8, a->n_proofs); store_u64(out + 16, a->n_failed);
+    memcpy(out + 24, xy, 128);
+    return 0;
+}
+
+int h2v_accumulator_merge_states(h2v_accumulator* dst, const uint8_t* states, size_t n, const uint8_t* draws32, uint8_t* out_draws32) {
+    const char* who = "h2v_accumulator_merge_states";
+    if (!dst || (n && !states)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n > H2V_ACC_MERGE_MAX) { set_last_error(std::string(who) + ": more than H2V_ACC_MERGE_MAX states"); return H2V_ERR_BAD_ARGUMENT; }
+    std::vector<size_t> np(n), nf(n);
+    for (size_t k = 0; k < n; ++k) {
+        const uint8_t* st = states + (size_t)H2V_ACC_STATE_BYTES * k;
+        if (load_u32(st) != H2V_ACC_STATE_MAGIC || load_u32(st + 4) != H2V_ACC_STATE_VERSION) { set_last_error(std::string(who) + ": a state with a wrong magic or version"); return H2V_ERR_BAD_ARGUMENT; }
+        const uint64_t p = load_u64(st + 8), f = load_u64(st + 16);
+        if (f > p) { set_last_error(std::string(who) + ": a state with more failed proofs than proofs"); return H2V_ERR_BAD_ARGUMENT; }
+        np[k] = (size_t)p; nf[k] = (size_t)f;
+    }
+    std::vector<uint8_t> os_draws;
+    int rc;
+    if ((rc = merge_args(dst, who, n, draws32, os_draws))) return rc;
+    if (!n) return 0;
+    H2V_HIP_CHECK(hipSetDevice(dst->ctx->device));
+    if ((rc = merge_reserve(dst, n, true))) return rc;
+    Drain drain{dst->stream};
+    // the lift: bytes -> affine Montgomery (with the curve check) -> Jacobian pairs, as add_msm lifts its sums
+    std::vector<uint8_t> xy(128 * n);
+    for (size_t k = 0; k < n; ++k) memcpy(&xy[128 * k], states + (size_t)H2V_ACC_STATE_BYTES * k + 24, 128);
+    uint32_t* d_flags = dst->m_words.p + 9 * n;
+    uint32_t* h_flags = dst->m_host.data() + 9 * n;
+    H2V_HIP_CHECK(hipMemcpyAsync(dst->m_bytes.p, xy.data(), xy.size(), hipMemcpyHostToDevice, dst->stream));
+    if ((rc = bases_from_bytes_enqueue(dst->stream, dst->m_bytes.p, dst->m_affine.p, d_flags, (uint32_t)(2 * n))) ||
+        (rc = affine_to_jacobian_enqueue(dst->stream, dst->m_affine.p, dst->m_pairs.p, (uint32_t)(2 * n)))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(h_flags, d_flags, 4 * 2 * n, hipMemcpyDeviceToHost, dst->stream));
+    if ((rc = sync(dst, who))) { drain.armed = false; return rc; }
+    for (size_t i = 0; i < 2 * n; ++i)
+        if (h_flags[i]) { set_last_error(std::string(who) + ": a state with a point that is not canonical or not on the curve"); return H2V_ERR_BAD_ARGUMENT; }
+    if ((rc = merge_impl(dst, who, n, draws32, np.data(), nf.data(), drain))) return rc;
+    if (out_draws32) memcpy(out_draws32, draws32, 32 * n);
     return 0;
 }
 

@@ -207,5 +207,10 @@ int export_records_enqueue(hipStream_t s, const G1J* d_acc, const G1JSlot* d_pie
 // as (X Z, Y, Z^3), d_ready) or whole (parts <= 1 -> d_acc[2g + side]); d_fold_failed[g] = sum of the records' failure counts
 int fold_records_enqueue(hipStream_t s, const void* d_recs, uint32_t n_recs, uint32_t groups, uint32_t parts, uint32_t shift, G1J* d_acc, G1JSlot* d_pieces, G1JSlot* d_ready,
                          uint32_t* d_fold_failed);
+// The fold of a merge (k_accumulator_merge_fold), one launch: d_acc[side] <- d_acc[side] + the sum of the n whole-point records' side,
+// and with d_sums record k's two points -> d_sums[2 slot], [2 slot + 1], slot = d_slots[k] (d_slots null: k).  team: the lanes that
+// share a side's sum, a power of two in 1 .. 64; 0 = accumulator_merge_team(n) = min(64, the next power of two >= n + 1).
+uint32_t accumulator_merge_team(uint32_t n);
+int accumulator_merge_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc);
 
 }  // namespace h2v

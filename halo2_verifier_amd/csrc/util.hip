@@ -132,6 +132,45 @@ int fold_records_enqueue(hipStream_t s, const void* d_recs, uint32_t n_recs, uin
     return 0;
 }
 
+// The fold of a merge (h2v_accumulator_merge, accumulator.hip): acc[side] <- acc[side] + sum_k recs[k][side] over n whole-point records
+// (parts = 1, what k_accumulator_scale writes; a record's failed word is not read: the counters of a merge are the host's), and, with
+// `sums`, record k's two points into the journal slot the host assigned: sums[2 slot + side], slot = slots[k] (slots null: slot = k).
+// One one-wave workgroup per side.  The team is the first `team` lanes, a power of two in 1 .. 64 that the host fits to n (k_fold_records'
+// team is eight lanes whatever the count: 67 dependent additions at 512 records, 9 + 6 here): lane r adds the items r, r + team, ..,
+// item 0 the previous accumulator and item i the record i - 1, then a butterfly of log2(team) levels over the words of a G1J.  Every
+// addition is the complete one (items may be identities, equal, or each other's negatives).  Lane 0 writes acc[side], the kernel's last
+// store, after it has read it; the slots are written before it.
+__global__ void __launch_bounds__(64) k_accumulator_merge_fold(const AccRecord* __restrict__ recs, uint32_t n, uint32_t team, const uint32_t* __restrict__ slots,
+                                                               G1J* __restrict__ sums, G1J* __restrict__ acc) {
+    const uint32_t side = blockIdx.x, lane = threadIdx.x;
+    if (sums)
+        for (uint32_t k = lane; k < n; k += 64) sums[2 * (size_t)(slots ? slots[k] : k) + side] = (side ? recs[k].right : recs[k].left)[0];
+    G1J sum = G1J::identity();
+    if (lane < team)
+        for (uint32_t i = lane; i <= n; i += team) sum = g1_add(sum, i ? (side ? recs[i - 1].right : recs[i - 1].left)[0] : acc[side]);
+    for (uint32_t d = team >> 1; d > 0; d >>= 1) {
+        G1J other;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&other);
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&sum);
+#pragma unroll
+        for (uint32_t w = 0; w < sizeof(G1J) / 4; ++w) dst[w] = (uint32_t)__shfl_down((int)src[w], d, 64);
+        sum = g1_add(sum, other);   // lanes r >= d add a value that is not part of the sum: only lane 0 is kept
+    }
+    if (lane == 0) acc[side] = sum;
+}
+uint32_t accumulator_merge_team(uint32_t n) {
+    uint32_t t = 1;
+    while (t < 64 && t < n + 1) t <<= 1;
+    return t;
+}
+int accumulator_merge_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc) {
+    if (!team) team = accumulator_merge_team(n);
+    if (team > 64 || (team & (team - 1))) { set_last_error("accumulator_merge_fold_enqueue: the team is not a power of two in 1 .. 64"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_accumulator_merge_fold, dim3(2), dim3(64), 0, s, (const AccRecord*)d_recs, n, team, d_slots, d_sums, d_acc);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ void k_affine_to_jacobian(const G1A* __restrict__ in, G1J* __restrict__ out, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = G1J::from_affine(in[i]);

@@ -23,9 +23,17 @@ Entry points
   ShardedBatch
       the staged form both are built on (and bench.py pipelines): upload the shard once, launch() = shard pipeline -> export ->
       all-gather -> fold -> one pairing, asynchronous on the batch's stream; finish() fetches the verdict.
+  ShardedAccumulator(ctx, group=None, device=None)
+      the streaming form: every rank owns a resident Accumulator and feeds it its own proofs as they arrive, with no collective per
+      leg; finalize() all-gathers the 152-byte states, takes one fresh draw per rank and merges them under ONE pairing
+      (Accumulator.merge_states), check_ranks() names the ranks whose own accumulator fails.
+  merge_accumulators_local(ctx, accumulators, draws)
+      the same merge over accumulators of one GPU (several feeder threads; tests).
+Neither the sharded batch nor the sharded accumulator has run over RCCL with more than one rank: the multi-rank tests run over gloo.
 """
 import contextlib
 import ctypes
+import hashlib
 import os
 
 from . import _lib
@@ -399,3 +407,120 @@ def verify_batch_sharded_local_identify(ctx, proofs, instances, rand, world: int
     """verify_batch_sharded_identify's computation in verify_batch_sharded_local's sequential one-GPU form.
     -> (ok, statuses[n], left_xy, right_xy, range_checks[world]): the range checks every shard's search ran, shard by shard."""
     return verify_batch_sharded_local(ctx, proofs, instances, rand, world, batch_factory, device, identify=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------- streaming form
+def _refuse_zero_merge_draws(draws: bytes):
+    """A zero draw would drop its rank's accumulator from the merged check.  Every rank holds the whole draw stream, so every rank
+    refuses the same draws at the same point: none enters a collective the others skip."""
+    zero = bytes(32)
+    if any(draws[i:i + 32] == zero for i in range(0, len(draws), 32)):
+        raise ValueError("a merge takes non-zero draws: a draw is zero")
+
+
+def _gather_bytes(mine: bytes, world, group, backend, device):
+    """all_gather of one fixed-length byte string per rank -> the list of them in rank order"""
+    if world == 1:
+        return [mine]
+    import torch
+    import torch.distributed as dist
+    dev = device if (backend == "nccl" and device is not None) else "cpu"
+    local = torch.frombuffer(bytearray(mine), dtype=torch.uint8).to(dev)
+    out = torch.empty(world * len(mine), dtype=torch.uint8, device=dev)
+    dist.all_gather_into_tensor(out, local, group=group)
+    flat = bytes(out.cpu().numpy().tobytes())
+    return [flat[r * len(mine):(r + 1) * len(mine)] for r in range(world)]
+
+
+def _merge_states(ctx, states, draws: bytes, accumulator_factory):
+    """A fresh accumulator with a journal of len(states) + 1 entries, the states merged into it in order: entry 1 + k is state k."""
+    merged = accumulator_factory(ctx, len(states) + 1)
+    try:
+        merged.merge_states(states, [draws[32 * k:32 * k + 32] for k in range(len(states))])
+    except Exception:
+        merged.close()
+        raise
+    return merged
+
+
+def _default_accumulator(ctx, journal):
+    from .verifier import Accumulator
+    return Accumulator(ctx, journal=journal)
+
+
+class ShardedAccumulator:
+    """A resident accumulator per rank of a torch.distributed group (one process per GPU), closed by ONE pairing.
+
+    Every rank feeds `acc` (an Accumulator over the rank's own Context) with its own proofs: acc.process(...) — no collective runs
+    per leg.  finalize() all-gathers the ranks' exported states (152 bytes each), takes one draw per rank — rank 0 draws them from
+    the OS and broadcasts (common_draws) — and merges all states in rank order into a fresh accumulator with a journal of
+    world + 1 entries: (L, R) = sum_k c_k (L_k, R_k), the counters added.  Every rank computes the same merge and gets the same
+    (ok, left_xy, right_xy) bit for bit.  check_ranks() then returns the merged journal's pairing bit per rank: a rank whose own
+    accumulator is poisoned shows 0 (c_k != 0: the entry's bit is the rank's own bit).  The ranks' accumulators are not changed and go
+    on accumulating afterwards.
+
+    At construction the ranks compare a hash of their params bytes once (a state carries no SRS, so the merge cannot check it): a
+    mismatch raises ValueError on every rank.
+    accumulator_factory(ctx, journal) builds the accumulators; the default is verifier.Accumulator (the non-GPU test suite injects a
+    stand-in to exercise the orchestration over gloo)."""
+
+    def __init__(self, ctx, group=None, device=None, accumulator_factory=None):
+        self.rank, self.world, self.backend = _group_info(group)
+        self.group, self.ctx = group, ctx
+        if accumulator_factory is None:
+            accumulator_factory = _default_accumulator
+            if device is None:
+                device = f"cuda:{ctx.device}"
+        self.device = device
+        self._factory = accumulator_factory
+        digest = hashlib.sha256(bytes(ctx.params.data)).digest()
+        if len(set(_gather_bytes(digest, self.world, group, self.backend, device))) != 1:
+            raise ValueError("the ranks of a sharded accumulator hold different params")
+        self.acc = accumulator_factory(ctx, 0)
+        self.merged = None
+        self.last_draws = None
+
+    def close(self):
+        for a in (self.acc, self.merged):
+            if a is not None:
+                a.close()
+        self.acc = self.merged = None
+
+    def process(self, *args, **kwargs):
+        """Accumulator.process on this rank's accumulator"""
+        return self.acc.process(*args, **kwargs)
+
+    def finalize(self, draws=None):
+        """-> (ok, left_xy, right_xy) of the merge of every rank's accumulator, identical on every rank.  draws: one non-zero scalar
+        per rank, the same on every rank (tests), or None: rank 0 draws them and broadcasts.  A zero draw raises ValueError on every rank."""
+        states = _gather_bytes(self.acc.export_state(), self.world, self.group, self.backend, self.device)
+        c = common_draws(self.world, draws, self.group, self.device)
+        _refuse_zero_merge_draws(c)
+        if self.merged is not None:
+            self.merged.close()
+            self.merged = None
+        self.merged = _merge_states(self.ctx, states, c, self._factory)
+        self.last_draws = c
+        return self.merged.finalize()
+
+    def check_ranks(self):
+        """After finalize(): the pairing bit of every rank's own accumulator, [1, 0, ..] in rank order (the merged journal's entries
+        1 .. world; one launch, no collective: every rank holds the merged journal)."""
+        if self.merged is None:
+            raise ValueError("check_ranks() comes after finalize()")
+        return [int(ok) for _, _, ok in self.merged.check_legs()[1:]]
+
+
+def merge_accumulators_local(ctx, accumulators, draws=None, accumulator_factory=None):
+    """ShardedAccumulator.finalize()'s computation over accumulators of ONE GPU (no process group): their exported states merged in
+    order into a fresh accumulator with a journal, one draw each (None: OS draws).  For callers with several feeder threads, each with
+    an accumulator of its own, and for tests.  -> (ok, left_xy, right_xy, bits): bits[k] = the pairing bit of accumulators[k] alone."""
+    accumulators = list(accumulators)
+    c = common_draws(len(accumulators), draws) if draws is not None else draw_scalars(len(accumulators))
+    _refuse_zero_merge_draws(c)
+    merged = _merge_states(ctx, [a.export_state() for a in accumulators], c, accumulator_factory or _default_accumulator)
+    try:
+        ok, left, right = merged.finalize()
+        return ok, left, right, [int(b) for _, _, b in merged.check_legs()[1:]]
+    finally:
+        merged.close()

@@ -11,6 +11,7 @@ import contextlib
 import ctypes
 import enum
 import numbers
+import struct
 
 from . import _lib
 from ._lib import H2VError, check
@@ -736,6 +737,77 @@ class Accumulator:
         check(self._lib.h2v_accumulator_drop_legs(self._h, _sizes(indices), len(indices)))
         gone = set(indices)
         self._inputs = [x for e, x in enumerate(self._inputs) if e not in gone]
+
+    # -- merging: one pairing for several accumulators
+    MERGE_MAX = 512       # include/h2v.h H2V_ACC_MERGE_MAX
+    STATE_BYTES = 152     # include/h2v.h H2V_ACC_STATE_BYTES
+    STATE_MAGIC = 0x53563248   # "H2VS", include/h2v.h H2V_ACC_STATE_MAGIC
+    STATE_VERSION = 1
+
+    @staticmethod
+    def pack_state(left_xy, right_xy, n_proofs, n_failed):
+        """The bytes export_state() writes for these points and counters (include/h2v.h): little-endian
+        [u32 magic][u32 version][u64 n_proofs][u64 n_failed][left x | y][right x | y]"""
+        if len(left_xy) != 64 or len(right_xy) != 64:
+            raise ValueError("a point is 64 bytes (x | y)")
+        return struct.pack("<IIQQ", Accumulator.STATE_MAGIC, Accumulator.STATE_VERSION, n_proofs, n_failed) + bytes(left_xy) + bytes(right_xy)
+
+    @staticmethod
+    def unpack_state(state):
+        """-> (left_xy, right_xy, n_proofs, n_failed) of a state; ValueError for a wrong length, magic or version"""
+        state = bytes(state)
+        if len(state) != Accumulator.STATE_BYTES:
+            raise ValueError(f"a state is {Accumulator.STATE_BYTES} bytes, got {len(state)}")
+        magic, version, n, f = struct.unpack_from("<IIQQ", state)
+        if magic != Accumulator.STATE_MAGIC or version != Accumulator.STATE_VERSION:
+            raise ValueError("a state with a wrong magic or version")
+        return state[24:88], state[88:152], n, f
+
+    def _merge_draws(self, draws, n, what):
+        """(draw bytes or None, the buffer the draws used are written to), every length the C side indexes checked"""
+        if n > self.MERGE_MAX:
+            raise ValueError(f"a merge takes at most {self.MERGE_MAX} {what}, got {n}")
+        if draws is not None and len(draws) != n:
+            raise ValueError(f"draws must hold one scalar per merged accumulator ({n}), got {len(draws)}")   # the C side reads n * 32 bytes
+        return (None if draws is None else b"".join(_scalar32(c) for c in draws)), ctypes.create_string_buffer(max(32 * n, 1))
+
+    def _merged(self, n, out):
+        if self._inputs:   # (journal on: the call has appended an entry per source)
+            self._inputs.extend([None] * n)
+        return [out.raw[32 * k: 32 * k + 32] for k in range(n)]
+
+    def merge(self, sources, draws=None):
+        """(L, R) += sum_k c_k (L_k, R_k) over the accumulators `sources`, the counters += theirs (h2v_accumulator_merge): one pairing
+        for all of them afterwards.  draws: one non-zero scalar per source, or None for fresh OS draws (the sound form: the draws must
+        not be known when the sources are made).  The sources are not changed; with the journal on every source leaves an entry, which
+        check_legs() tests and drop_legs() takes out.  -> the draws used, 32 bytes each.  A call that raises leaves everything as it was."""
+        sources = list(sources)
+        if any(not isinstance(a, Accumulator) for a in sources):
+            raise TypeError("merge takes Accumulators")
+        if any(a is self for a in sources) or len({id(a) for a in sources}) != len(sources):
+            raise ValueError("a source is the destination, or is given twice")
+        if any(not a._h for a in sources):
+            raise ValueError("a source is closed")
+        c, out = self._merge_draws(draws, len(sources), "sources")
+        handles = (ctypes.c_void_p * max(len(sources), 1))(*[a._h.value for a in sources])
+        check(self._lib.h2v_accumulator_merge(self._h, handles, len(sources), c, out))
+        return self._merged(len(sources), out)
+
+    def export_state(self):
+        """-> the accumulator as STATE_BYTES bytes (h2v_accumulator_export_state): the counters and the two affine points, for a
+        merge_states() on another device or in another process.  A state carries no SRS: the importer cannot check it."""
+        out = ctypes.create_string_buffer(self.STATE_BYTES)
+        check(self._lib.h2v_accumulator_export_state(self._h, out))
+        return out.raw
+
+    def merge_states(self, states, draws=None):
+        """merge() over exported states (h2v_accumulator_merge_states): states is a list of STATE_BYTES-byte strings.  -> the draws used."""
+        states = list(states)
+        if any(not isinstance(st, (bytes, bytearray, memoryview)) or len(st) != self.STATE_BYTES for st in states):
+            raise ValueError(f"every state is {self.STATE_BYTES} bytes")   # the C side reads n * STATE_BYTES bytes
+        c, out = self._merge_draws(draws, len(states), "states")
+        check(self._lib.h2v_accumulator_merge_states(self._h, b"".join(bytes(st) for st in states), len(states), c, out))
+        return self._merged(len(states), out)
 
     def identify(self):
         """Name the failing proofs of the failing legs: check_legs(), then verify_batch_keys_identify with fresh OS draws over the

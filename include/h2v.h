@@ -295,6 +295,47 @@ int h2v_accumulator_check_legs(h2v_accumulator* a, size_t cap, size_t* n_legs, s
  *   serves: DualMSM::scale, DualMSM::add_msm (poly/kzg/msm.rs:173-183): (L, R) <- sum over the kept entries of W_e sum_e. */
 int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_drop);
 
+/* ---- merging resident accumulators: ONE pairing for K accumulators (one per feeder thread, per GPU of a node, per process).
+ * With draws c_1 .. c_K
+ *     (L, R) <- (L, R) + sum_k c_k (L_k, R_k),     n_proofs += sum_k n_proofs_k,     n_failed += sum_k n_failed_k
+ * dst itself is not scaled; the sources are neither consumed nor changed, and a source's own journal is not read.  finalize afterwards
+ * means what it means now: the pairing passes and no counted proof failed.
+ * Soundness.  The check phi(L, R) = e(L, s_g2) e(R, -g2) is a homomorphism from pairs of G1 points into G_T, so the merged accumulator
+ * is checked as phi(dst) prod_k phi(src_k)^(c_k).  If one of the factors phi(dst), phi(src_1) .. phi(src_K) is not 1 and the c_k are
+ * independent and uniform in F_r (G_T has prime order r), the product is 1 for at most one value of a c_k given the others:
+ * probability <= 1 / r (when only phi(dst) != 1 and every source is good the product is phi(dst) != 1, always).  Good accumulators
+ * always merge to a good one.  A zero draw would drop its source from the check without a trace, so it is refused.  The draws must be
+ * made AFTER the sources are fixed (draws32 NULL = fresh OS draws, the safe form; programmed draws are for tests and for ranks that
+ * must agree on them).
+ * Journal.  With dst's journal on, every source leaves one entry, in call order: its sum is c_k (L_k, R_k), its M is 1 (as for add_msm)
+ * and it carries the source's counters, so (L, R) = sum_e W_e sum_e holds unchanged.  check_legs names a bad source (c_k != 0: the
+ * entry's bit is the source's own bit), drop_legs takes the source out again.  A merge that needs more entries than are free is refused
+ * as a whole with H2V_ERR_UNSUPPORTED, after the argument checks and before any device work.
+ * Refusals, H2V_ERR_BAD_ARGUMENT before any device work: a null argument with n > 0; n above H2V_ACC_MERGE_MAX; a source equal to dst
+ * or given twice; a source on another device or over other params (g[0], g2, s_g2); a draw that is not canonical or is zero.  n == 0
+ * changes nothing.  A call that returns non-zero leaves points, counters and journal exactly as they were: the accumulator is written
+ * by the call's last enqueued step, the counters and entries follow the synchronise.  out_draws32 (n x 32, may be NULL): the draws
+ * used, written on success.
+ *   serves: DualMSM::scale and DualMSM::add_msm (poly/kzg/msm.rs:173-183) per source, AccumulatorStrategy::with (poly/kzg/strategy.rs:76-78). */
+#define H2V_ACC_MERGE_MAX 512   /* sources per call */
+int h2v_accumulator_merge(h2v_accumulator* dst, h2v_accumulator* const* srcs, size_t n_src, const uint8_t* draws32, uint8_t* out_draws32);
+/* An accumulator as bytes, for a merge on another device or in another process; little-endian:
+ *   [u32 magic = H2V_ACC_STATE_MAGIC ("H2VS")][u32 version = 1][u64 n_proofs][u64 n_failed][left x | y (64)][right x | y (64)]
+ * the points as h2v_accumulator_read gives them (affine, canonical, all-zero = the identity).  Changes nothing.  A state carries no
+ * SRS: the importer CANNOT check that it was accumulated over its own params — that is the caller's to guarantee (compare the params
+ * bytes once, as ShardedAccumulator does); a state over another SRS makes the merged pairing fail, it cannot make a bad proof pass.
+ *   serves: AccumulatorStrategy::with (poly/kzg/strategy.rs:76-78): a state is a DualMSM handed on. */
+#define H2V_ACC_STATE_BYTES 152
+#define H2V_ACC_STATE_MAGIC 1398157896   /* 0x53563248 */
+#define H2V_ACC_STATE_VERSION 1
+int h2v_accumulator_export_state(h2v_accumulator* a, uint8_t out[H2V_ACC_STATE_BYTES]);
+/* h2v_accumulator_merge over n exported states (n x H2V_ACC_STATE_BYTES, contiguous): the states' points are lifted into device memory
+ * and merged by the very code of h2v_accumulator_merge, under its rules, draws and journal entries included.  Further refusals,
+ * H2V_ERR_BAD_ARGUMENT: a state with a wrong magic or version, or with n_failed > n_proofs (host checks, before any device work); a state
+ * with a point that is not canonical or not on the curve and is not all-zero (checked on the device, before anything of dst changes).
+ *   serves: DualMSM::scale, DualMSM::add_msm (poly/kzg/msm.rs:173-183), AccumulatorStrategy::with (poly/kzg/strategy.rs:76-78). */
+int h2v_accumulator_merge_states(h2v_accumulator* dst, const uint8_t* states, size_t n, const uint8_t* draws32, uint8_t* out_draws32);
+
 /* N x verify_proof under SingleStrategy (one pairing per proof; poly/kzg/strategy.rs:164-176).
  * per_proof_status[i] = 0, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE when that proof's pairing fails,
  * or the transcript/opening error. */

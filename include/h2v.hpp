@@ -308,12 +308,48 @@ public:
         }
         check(h2v_accumulator_drop_legs(h_, legs.data(), legs.size()));
     }
+    // One pairing for several accumulators (h2v_accumulator_merge): (L, R) += sum_k c_k (L_k, R_k), the counters += theirs — DualMSM::scale
+    // and add_msm (kzg/msm.rs:173-183) per source, which is not changed.  draws32: one non-zero 32-byte draw per source, or empty = fresh
+    // OS draws.  -> the draws used.  With the journal on every source leaves an entry.  A Failure leaves the accumulator as it was.
+    Bytes merge(const std::vector<Accumulator*>& sources, const Bytes& draws32 = Bytes()) {
+        check_merge(sources.size(), draws32);
+        std::vector<h2v_accumulator*> hs;
+        for (Accumulator* a : sources) {
+            if (!a || a == this) throw Failure(H2V_ERR_BAD_ARGUMENT, "a source is null or the destination");
+            hs.push_back(a->h_);
+        }
+        Bytes used(32 * sources.size() + 1);
+        check(h2v_accumulator_merge(h_, hs.data(), hs.size(), draws32.empty() ? nullptr : draws32.data(), used.data()));
+        used.resize(32 * sources.size());
+        return used;
+    }
+    // The accumulator as H2V_ACC_STATE_BYTES bytes (h2v_accumulator_export_state: the counters and the two affine points), for a
+    // merge_states on another device or in another process.  A state carries no SRS: the importer cannot check it.
+    Bytes export_state() {
+        Bytes out(H2V_ACC_STATE_BYTES);
+        check(h2v_accumulator_export_state(h_, out.data()));
+        return out;
+    }
+    // merge over exported states, concatenated (h2v_accumulator_merge_states).  -> the draws used.
+    Bytes merge_states(const Bytes& states, const Bytes& draws32 = Bytes()) {
+        if (states.size() % H2V_ACC_STATE_BYTES) throw Failure(H2V_ERR_BAD_ARGUMENT, "states are H2V_ACC_STATE_BYTES bytes each");
+        const size_t n = states.size() / H2V_ACC_STATE_BYTES;
+        check_merge(n, draws32);
+        Bytes used(32 * n + 1);
+        check(h2v_accumulator_merge_states(h_, states.data(), n, draws32.empty() ? nullptr : draws32.data(), used.data()));
+        used.resize(32 * n);
+        return used;
+    }
     const uint8_t* left() const { return left_; }
     const uint8_t* right() const { return right_; }
     size_t n_proofs() const { return n_proofs_; }   // as of the last read()
     size_t n_failed() const { return n_failed_; }
 
 private:
+    static void check_merge(size_t n, const Bytes& draws32) {
+        if (n > H2V_ACC_MERGE_MAX) throw Failure(H2V_ERR_BAD_ARGUMENT, "at most H2V_ACC_MERGE_MAX sources");
+        if (!draws32.empty() && draws32.size() != 32 * n) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per source");
+    }
     h2v_accumulator* h_ = nullptr;
     bool all_ok_ = true;
     size_t n_proofs_ = 0, n_failed_ = 0;

@@ -45,6 +45,12 @@ pub const H2V_ACC_RECORD_PIECES: usize = 6;
 pub const H2V_ACC_RECORD_BYTES: usize = 1312;
 /// entries a leg journal holds at most, the base included (h2v_accumulator_journal_begin)
 pub const H2V_ACC_JOURNAL_MAX: usize = 4096;
+/// sources one h2v_accumulator_merge / h2v_accumulator_merge_states call takes
+pub const H2V_ACC_MERGE_MAX: usize = 512;
+/// an exported accumulator: u32 magic, u32 version, u64 n_proofs, u64 n_failed, left x | y, right x | y (little-endian)
+pub const H2V_ACC_STATE_BYTES: usize = 152;
+pub const H2V_ACC_STATE_MAGIC: u32 = 1398157896;
+pub const H2V_ACC_STATE_VERSION: u32 = 1;
 /// h2v_batch_set_profiling: only the dominant kernel's own timestamps
 pub const H2V_PROFILE_KERNEL: c_int = 3;
 
@@ -93,6 +99,9 @@ extern "C" {
     pub fn h2v_accumulator_check_legs(a: *mut h2v_accumulator, cap: usize, n_legs: *mut usize, leg_proofs: *mut usize, leg_failed: *mut usize,
                                       leg_pairing_ok: *mut c_int) -> c_int;
     pub fn h2v_accumulator_drop_legs(a: *mut h2v_accumulator, legs: *const usize, n_drop: usize) -> c_int;
+    pub fn h2v_accumulator_merge(dst: *mut h2v_accumulator, srcs: *const *mut h2v_accumulator, n_src: usize, draws32: *const u8, out_draws32: *mut u8) -> c_int;
+    pub fn h2v_accumulator_export_state(a: *mut h2v_accumulator, out: *mut u8) -> c_int;
+    pub fn h2v_accumulator_merge_states(dst: *mut h2v_accumulator, states: *const u8, n: usize, draws32: *const u8, out_draws32: *mut u8) -> c_int;
     pub fn h2v_verify_each(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, per_proof_status: *mut c_int) -> c_int;
     pub fn h2v_verify_batches(ctx: *mut h2v_ctx, n_batches: usize, batch_sizes: *const usize, proofs: *const *const u8, proof_lens: *const usize,

@@ -10,6 +10,7 @@
 //!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
 //! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
 //!                               sharing the params; `finalize` whenever the caller decides (h2v_accumulator_*).
+//!                               `merge` / `export_state` / `merge_states` fold several of them into one pairing.
 //!                               Its leg journal (`journal_begin`, `check_legs`, `drop_legs`) finds the legs whose own pairing
 //!                               fails and takes them out again.
 //! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) whose `finalize`
@@ -357,6 +358,40 @@ impl GpuResidentAccumulator {
         let rc = unsafe { h2v_accumulator_drop_legs(self.acc, legs.as_ptr(), legs.len()) };
         if rc != 0 { return Err(map_err(rc)); }
         Ok(())
+    }
+
+    /// One pairing for several strategies: `(L, R) += sum_k c_k (L_k, R_k)` with a fresh OS draw `c_k` per source, the counters added
+    /// (h2v_accumulator_merge) — per source `DualMSM::scale` then `add_msm` (poly/kzg/msm.rs:173-183) on a copy; the sources are not
+    /// changed.  With the journal on every source leaves an entry that `check_legs` tests and `drop_legs` takes out.  Returns the
+    /// draws used, 32 bytes per source.  At most `H2V_ACC_MERGE_MAX` sources, all on this device and over these params.
+    pub fn merge(&mut self, sources: &[&GpuResidentAccumulator]) -> Result<Vec<u8>, Error> {
+        if sources.len() > H2V_ACC_MERGE_MAX { return Err(Error::InvalidInstances); }
+        let handles: Vec<*mut h2v_accumulator> = sources.iter().map(|s| s.acc).collect();
+        let mut draws = vec![0u8; 32 * sources.len().max(1)];
+        let rc = unsafe { h2v_accumulator_merge(self.acc, handles.as_ptr(), handles.len(), core::ptr::null(), draws.as_mut_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        draws.truncate(32 * sources.len());
+        Ok(draws)
+    }
+
+    /// The strategy as `H2V_ACC_STATE_BYTES` bytes (h2v_accumulator_export_state), for a `merge_states` on another device or in
+    /// another process.  A state carries no SRS: the importer cannot check it.
+    pub fn export_state(&mut self) -> Result<[u8; H2V_ACC_STATE_BYTES], Error> {
+        let mut out = [0u8; H2V_ACC_STATE_BYTES];
+        let rc = unsafe { h2v_accumulator_export_state(self.acc, out.as_mut_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(out)
+    }
+
+    /// `merge` over exported states (h2v_accumulator_merge_states), with fresh OS draws; returns the draws used.
+    pub fn merge_states(&mut self, states: &[[u8; H2V_ACC_STATE_BYTES]]) -> Result<Vec<u8>, Error> {
+        if states.len() > H2V_ACC_MERGE_MAX { return Err(Error::InvalidInstances); }
+        let flat: Vec<u8> = states.iter().flat_map(|s| s.iter().copied()).collect();
+        let mut draws = vec![0u8; 32 * states.len().max(1)];
+        let rc = unsafe { h2v_accumulator_merge_states(self.acc, flat.as_ptr(), states.len(), core::ptr::null(), draws.as_mut_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        draws.truncate(32 * states.len());
+        Ok(draws)
     }
 }
 impl Drop for GpuResidentAccumulator {

@@ -14,7 +14,15 @@ offered before it.  Median wall times of --reps runs, host proofs in, one MI355X
       commit, loaded beside the in-tree one) on the parent's library, the variants alternating inside every repetition.
    b. check_legs() and the rebuild drop_legs([]) at 8, 64 and 512 entries (the base and legs of 16 proofs), beside the repair a library without the
       journal offers: a fresh accumulator fed the same legs again from host bytes.
-   With --trace: one check_legs and one drop_legs at each of the three sizes, for a `rocprofv3 --kernel-trace --stats` run."""
+   With --trace: one check_legs and one drop_legs at each of the three sizes, for a `rocprofv3 --kernel-trace --stats` run.
+6. (--merge) merging accumulators, instead of 1 - 5; the variants alternate inside every repetition, after >= 50 ms of warm-up:
+   a. merge of K = 2, 8, 64 and 512 sources (accumulators fed one leg of 16 proofs) into one destination, against the host round trip a
+      caller of the parent commit's library has (--parent PATH): per source read(), then add_msm of the two one-term lists.  merge() runs
+      over K distinct accumulators up to 64 (every accumulator owns a stream); merge_states() over K states at every K, the 512 states
+      those of 64 accumulators, cycled; the round trip cycles over the same accumulators.
+   b. (--parent) process x 8 + finalize on legs of 1024 proofs, this build against the parent's.
+   With --trace: at K = 8, 64 and 512, one drop_legs([]) over a journal of K entries (k_fold_records over K whole-point records) and one
+   merge_states of K states (k_accumulator_merge_fold over K records), for a `rocprofv3 --kernel-trace --stats` run."""
 import argparse, ctypes, json, os, random, sys, time
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import bench
@@ -30,6 +38,7 @@ ap.add_argument("--baseline-only", action="store_true")
 ap.add_argument("--trace", action="store_true")
 ap.add_argument("--journal", action="store_true")
 ap.add_argument("--parent", default=None)
+ap.add_argument("--merge", action="store_true")
 args = ap.parse_args()
 if args.library:
     _lib.lib_path = lambda: os.path.abspath(args.library)
@@ -179,6 +188,100 @@ def journal_probe():
             json.dump(res, f, indent=1)
 
 
+def merge_probe():
+    LEG, SIZES, OBJECTS = 16, (2, 8, 64, 512), 64
+
+    def fed(c, j):
+        acc = h2v.Accumulator(c)
+        acc.process(c, None, P[:LEG], I[:LEG], draws[j % K][j % 7:j % 7 + LEG])
+        return acc
+
+    cs = [rnd.randrange(1, R_MOD) for _ in range(max(SIZES))]
+    if args.trace:
+        srcs = [fed(ctx, j) for j in range(8)]
+        states = [a.export_state() for a in srcs]
+        for J in (8, 64, 512):
+            acc = h2v.Accumulator(ctx, journal=J)
+            acc.merge_states([states[k % 8] for k in range(J - 1)], cs[:J - 1])      # a journal of J entries, the base included
+            before = acc.read()
+            acc.drop_legs([])                                                       # k_fold_records over J records
+            assert acc.read() == before
+            acc.close()
+            acc = h2v.Accumulator(ctx)
+            acc.merge_states([states[k % 8] for k in range(J)], cs[:J])             # k_accumulator_merge_fold over J records
+            acc.close()
+        for a in srcs:
+            a.close()
+        return
+    srcs = [fed(ctx, j) for j in range(OBJECTS)]
+    states = [a.export_state() for a in srcs]
+    pctx = parent_context(args.parent) if args.parent else None
+    psrcs = [fed(pctx, j) for j in range(OBJECTS)] if pctx else []
+    assert not psrcs or [a.read() for a in psrcs] == [a.read() for a in srcs]
+    res["merge_ms"] = {}
+    for Kn in SIZES:
+        variants = {}
+        dst = h2v.Accumulator(ctx)
+        if Kn <= OBJECTS:
+            variants["merge"] = lambda: dst.merge(srcs[:Kn], cs[:Kn])
+        variants["merge_states"] = lambda: dst.merge_states([states[k % OBJECTS] for k in range(Kn)], cs[:Kn])
+        if pctx:
+            pdst = h2v.Accumulator(pctx)
+
+            def round_trip():
+                for k in range(Kn):
+                    left, right, _, _ = psrcs[k % OBJECTS].read()
+                    pdst.add_msm(([cs[k]], [left]), ([cs[k]], [right]))
+            variants["parent_round_trip"] = round_trip
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.05:   # warm-up
+            for fn in variants.values():
+                fn()
+        ts = {v: [] for v in variants}
+        for _ in range(args.reps):
+            for v, fn in variants.items():
+                t0 = time.perf_counter(); fn(); ts[v].append((time.perf_counter() - t0) * 1e3)
+        row = {v: round(median(t), 3) for v, t in ts.items()}
+        row.update({v + "_min_max": [round(min(t), 3), round(max(t), 3)] for v, t in ts.items()})
+        res["merge_ms"][Kn] = row
+        print(f"{Kn:4d} sources of {LEG} proofs: " + "   ".join(f"{v} {row[v]:9.3f} ms" for v in variants), flush=True)
+        dst.close()
+        if pctx:
+            pdst.close()
+    for a in srcs + psrcs:
+        a.close()
+    if pctx:
+        def legs(c):
+            acc = h2v.Accumulator(c)
+            for j in range(K):
+                acc.process(c, None, P, I, draws[j])
+            r = acc.finalize()
+            acc.close()
+            return r
+        variants = {"this_build": ctx, "parent": pctx}
+        want = legs(ctx)
+        assert want[0] and legs(pctx) == want   # warm-up
+        ts = {v: [] for v in variants}
+        for _ in range(args.reps):
+            for v, c in variants.items():
+                t0 = time.perf_counter(); legs(c); ts[v].append((time.perf_counter() - t0) * 1e3)
+        row = {v: round(median(t), 3) for v, t in ts.items()}
+        row.update({v + "_min_max": [round(min(t), 3), round(max(t), 3)] for v, t in ts.items()})
+        row["this_over_parent"] = round(row["this_build"] / row["parent"], 4)
+        res["legs_1024_ms"] = row
+        print(f"{K} legs of 1024 + finalize: this build {row['this_build']:.3f} ms   parent {row['parent']:.3f} ms   ratio {row['this_over_parent']:.3f}x "
+              f"({'within' if row['this_over_parent'] <= 1.08 else 'OUTSIDE'} 1.08x)", flush=True)
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if args.merge:
+    merge_probe()
+    ctx.close()
+    sys.exit(0)
 if args.journal:
     journal_probe()
     ctx.close()
