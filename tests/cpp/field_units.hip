@@ -9,15 +9,9 @@
 // products take any limb-normalised operands, canonical or not).  gpu mode wants a multiple of 64 tuples.  Every limb must be below
 // 2^29 ("bad input", status 2).  stdout: per tuple one line per routine, "<routine> l0 .. l8" in hex: mul = a0 b0 / R, sqr = a0^2 / R,
 // dot2 = (a0 b0 + a1 b1) / R, sqdot = (a0^2 + a1 b1) / R, the result limbs exactly as the routine leaves them.  Every HIP call is checked (status 3).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 #include "../../halo2_verifier_amd/csrc/bn254.hip.h"
-using namespace h2v;
+#include "units.h"   // (CK alone: this program speaks text over stdin and stdout)
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
 #define TUPLE_WORDS 36u
 #define LANES 64u
 #define DEVICE_ROUTINES 8u
@@ -89,8 +83,7 @@ template <class F> static int run(bool gpu) {
     return 0;
 }
 int main(int argc, char** argv) {
-    if (argc != 3) return 1;
-    const std::string field = argv[1], mode = argv[2];
-    if ((field != "fq" && field != "fr") || (mode != "gpu" && mode != "host")) return 1;
+    const std::string field = argc == 3 ? argv[1] : "", mode = argc == 3 ? argv[2] : "";
+    if ((field != "fq" && field != "fr") || (mode != "gpu" && mode != "host")) { fprintf(stderr, "usage: field_units fq|fr gpu|host\n"); return 2; }
     return field == "fq" ? run<Fq>(mode == "gpu") : run<Fr>(mode == "gpu");
 }

@@ -11,63 +11,16 @@
 //   msm_units scale  IN OUT   k_accumulator_scale through accumulator_scale_many_enqueue: the records as they are in memory
 // Files are little-endian uint32 words; the layouts are in the readers below.  Scalars are 8 raw words, affine bases 64 canonical
 // bytes (x | y, all zero = the identity) that the host converts with Fq::from_bytes; Jacobian points and every result are raw limbs.
-// Every HIP call is checked: the first error ends the program with a non-zero status.  Every count and index that reaches a kernel
-// is checked on the host first.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
+// Every count and index that reaches a kernel is checked on the host first.  The results a mode allocates itself (not those of an
+// MsmWorkspace) are preset to 0xff and lie between guard bands that are checked after the kernels.  The prelude is tests/cpp/units.h.
 #include "../../halo2_verifier_amd/csrc/msm.hip"
+#include "units.h"
 
-namespace h2v {
-static std::string g_err;
-void set_last_error(const std::string& s) { g_err = s; }
-}
-using namespace h2v;
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
-#define REQUIRE(c, msg) do { if (!(c)) { fprintf(stderr, "bad input: %s\n", msg); exit(2); } } while (0)
-#define RC(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s: %d %s\n", #x, rc_, g_err.c_str()); exit(4); } } while (0)
-
-static std::vector<uint32_t> slurp_words(const char* path) {
-    std::ifstream f(path, std::ios::binary);
-    REQUIRE(f.good(), "cannot open input");
-    std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    REQUIRE(b.size() % 4 == 0, "input is not whole words");
-    std::vector<uint32_t> w(b.size() / 4);
-    memcpy(w.data(), b.data(), b.size());
-    return w;
-}
-static void spill(const char* path, const std::vector<uint32_t>& out) {
-    FILE* f = fopen(path, "wb");
-    REQUIRE(f && fwrite(out.data(), 4, out.size(), f) == out.size() && fclose(f) == 0, "cannot write output");
-}
-template <class T> static T* to_device(const T* h, size_t n) {
-    T* d = nullptr;
-    CK(hipMalloc(&d, (n ? n : 1) * sizeof(T)));
-    if (n) CK(hipMemcpy((void*)d, (const void*)h, n * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-template <class T> static void append(std::vector<uint32_t>& out, const T* d, size_t n) {   // device records -> output words
-    static_assert(sizeof(T) % 4 == 0, "word records");
-    const size_t o = out.size(), words = n * sizeof(T) / 4;
-    out.resize(o + words);
-    if (n) CK(hipMemcpy(out.data() + o, (const void*)d, words * 4, hipMemcpyDeviceToHost));
-}
-// a cursor over the input words
-struct Words {
-    const std::vector<uint32_t>& w;
-    size_t at = 0;
-    uint32_t next() { REQUIRE(at < w.size(), "input too short"); return w[at++]; }
-    const uint32_t* span(size_t words) { REQUIRE(words <= w.size() - at, "input too short"); const uint32_t* p = w.data() + at; at += words; return p; }
-    template <class T> void take(T* out, size_t n) { memcpy((void*)out, span(n * sizeof(T) / 4), n * sizeof(T)); }
-};
 // n affine bases of 64 canonical bytes each
-static std::vector<G1A> bases_from_bytes(Words& in, size_t n) {
+static std::vector<G1A> bases_from_bytes(In& in, size_t n) {
     std::vector<G1A> v(n);
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(in.span(16 * n));
+    REQUIRE(n <= in.left() / 64, "input too short");
+    const uint8_t* b = in.bytes(64 * n);
     for (size_t i = 0; i < n; ++i) REQUIRE(Fq::from_bytes(b + 64 * i, v[i].x) && Fq::from_bytes(b + 64 * i + 32, v[i].y), "base coordinate not canonical");
     return v;
 }
@@ -123,14 +76,14 @@ __global__ void __launch_bounds__(64) k_units_chain(const ChainOp* __restrict__ 
 }
 // IN: n_pool, pool points (27 words each); n_cases, cases (LawCase); n_ops, the chain's start (27 words), ops (ChainOp)
 // OUT: n_cases LawOut, then (n_ops > 0) one LawOut of the chain
-static void run_law(Words& in, std::vector<uint32_t>& out) {
-    const uint32_t n_pool = in.next();
+static void run_law(In& in, Out& out) {
+    const uint32_t n_pool = in.word();
     REQUIRE(n_pool >= 1 && n_pool <= (1u << 16), "bad pool");
     std::vector<G1J> pool_pts(n_pool);
     in.take(pool_pts.data(), n_pool);
     std::vector<G1JSlot> pool(n_pool);
     for (uint32_t i = 0; i < n_pool; ++i) pool[i] = pool_pts[i];
-    const uint32_t n = in.next();
+    const uint32_t n = in.word();
     REQUIRE(n <= (1u << 16), "too many cases");
     std::vector<LawCase> cases(n);
     in.take(cases.data(), n);
@@ -138,7 +91,7 @@ static void run_law(Words& in, std::vector<uint32_t>& out) {
         REQUIRE(c.op < LAW_COUNT, "bad operation");
         if (c.op == LAW_HORNER) REQUIRE(c.a1 >= 1 && c.a0 <= n_pool && c.a1 <= n_pool - c.a0 && c.a2 <= 64, "bad Horner case");
     }
-    const uint32_t n_ops = in.next();
+    const uint32_t n_ops = in.word();
     REQUIRE(n_ops <= (1u << 16), "chain too long");
     G1J start = G1J::identity();
     std::vector<ChainOp> ops(n_ops);
@@ -147,27 +100,23 @@ static void run_law(Words& in, std::vector<uint32_t>& out) {
     G1JSlot* d_pool = to_device(pool.data(), n_pool);
     LawCase* d_cases = to_device(cases.data(), n);
     ChainOp* d_ops = to_device(ops.data(), n_ops);
-    LawOut* d_out = nullptr;
-    CK(hipMalloc(&d_out, ((size_t)n + 1) * sizeof(LawOut)));
-    CK(hipMemset(d_out, 0xff, ((size_t)n + 1) * sizeof(LawOut)));
-    if (n) hipLaunchKernelGGL(k_units_law, dim3((4 * n + 63) / 64), dim3(64), 0, 0, d_cases, n, d_pool, d_out);
+    Guarded<LawOut> res((size_t)n + (n_ops ? 1 : 0));
+    if (n) hipLaunchKernelGGL(k_units_law, dim3((4 * n + 63) / 64), dim3(64), 0, 0, d_cases, n, d_pool, res.p);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
-    if (n_ops) hipLaunchKernelGGL(k_units_chain, dim3(1), dim3(64), 0, 0, d_ops, n_ops, d_pool, start, d_out + n);
+    if (n_ops) hipLaunchKernelGGL(k_units_chain, dim3(1), dim3(64), 0, 0, d_ops, n_ops, d_pool, start, res.p + n);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
-    append(out, d_out, (size_t)n + (n_ops ? 1 : 0));
-    CK(hipFree(d_pool)); CK(hipFree(d_cases)); CK(hipFree(d_ops)); CK(hipFree(d_out));
+    res.collect(out, "law results");
+    CK(hipFree(d_pool)); CK(hipFree(d_cases)); CK(hipFree(d_ops));
 }
 
 // ---- digits
 // IN: n_jobs; per job: c, windows, n, n scalars (8 words), n bases (64 bytes)
 // OUT per job: windows, buckets, nb, E; the digit table (windows * n words, window-major); counts (nb + MSM_CONTROL_WORDS); offsets (nb); list (E)
-static void run_digits(Words& in, std::vector<uint32_t>& out) {
-    const uint32_t jobs = in.next();
-    REQUIRE(jobs <= 64, "too many jobs");
-    for (uint32_t job = 0; job < jobs; ++job) {
-        const uint32_t c = in.next(), windows = in.next(), n = in.next();
+static void run_digits(In& in, Out& out) {
+    for (uint32_t job = 0, jobs = job_count(in, 64); job < jobs; ++job) {
+        const uint32_t c = in.word(), windows = in.word(), n = in.word();
         REQUIRE(c >= 2 && c <= 15 && windows >= 1 && windows <= 128 && n >= 1 && n <= (1u << 16), "bad job");
         const MsmPlan p{n, c, windows, 1u << (c - 1)};
         const uint32_t nb = p.windows * p.buckets;
@@ -177,13 +126,13 @@ static void run_digits(Words& in, std::vector<uint32_t>& out) {
         G1A* d_bases = to_device(bases.data(), n);
         MsmProblem q(d_scalars, d_bases, nullptr, 8, 1, n);
         MsmProblem* d_q = to_device(&q, 1);
-        uint32_t *d_dig, *d_counts, *d_offsets, *d_cursor, *d_list, *d_block;
+        uint32_t *d_cursor, *d_block;
         G1A* d_phi;
         const uint32_t nblk = (nb + 1023) / 1024;
-        CK(hipMalloc(&d_dig, (size_t)windows * n * 4)); CK(hipMalloc(&d_counts, ((size_t)nb + MSM_CONTROL_WORDS) * 4)); CK(hipMalloc(&d_offsets, (size_t)nb * 4));
-        CK(hipMalloc(&d_cursor, (size_t)nb * 4)); CK(hipMalloc(&d_list, list_cap * 4)); CK(hipMalloc(&d_block, ((size_t)nblk + 2) * 4)); CK(hipMalloc(&d_phi, (size_t)n * sizeof(G1A)));
-        CK(hipMemset(d_dig, 0xff, (size_t)windows * n * 4)); CK(hipMemset(d_list, 0xff, list_cap * 4));
-        CK(hipMemset(d_offsets, 0xff, (size_t)nb * 4)); CK(hipMemset(d_cursor, 0xff, (size_t)nb * 4));
+        Guarded<uint32_t> dig((size_t)windows * n), counts((size_t)nb + MSM_CONTROL_WORDS), offsets(nb), list(list_cap);
+        uint32_t *d_dig = dig.p, *d_counts = counts.p, *d_offsets = offsets.p, *d_list = list.p;
+        CK(hipMalloc(&d_cursor, (size_t)nb * 4)); CK(hipMalloc(&d_block, ((size_t)nblk + 2) * 4)); CK(hipMalloc(&d_phi, (size_t)n * sizeof(G1A)));
+        CK(hipMemset(d_cursor, 0xff, (size_t)nb * 4));
         hipLaunchKernelGGL(msm_glv_prep, dim3((n + 255) / 256, 1), dim3(256), 0, 0, d_q, 1u, p, d_dig, d_phi);
         CK(hipGetLastError());
         // the global counting sort as msm_enqueue_multi runs it
@@ -204,13 +153,9 @@ static void run_digits(Words& in, std::vector<uint32_t>& out) {
         hipLaunchKernelGGL(msm_count_or_scatter<true>, gt, dim3(MSM_TILE_THREADS), lds, 0, d_q, 1u, tiles, p, wpp, d_counts, d_offsets, d_cursor, d_list);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
-        out.push_back(windows); out.push_back(p.buckets); out.push_back(nb); out.push_back(E);
-        append(out, d_dig, (size_t)windows * n);
-        append(out, d_counts, (size_t)nb + MSM_CONTROL_WORDS);
-        append(out, d_offsets, nb);
-        append(out, d_list, E);
-        CK(hipFree(d_scalars)); CK(hipFree(d_bases)); CK(hipFree(d_q)); CK(hipFree(d_dig)); CK(hipFree(d_counts)); CK(hipFree(d_offsets));
-        CK(hipFree(d_cursor)); CK(hipFree(d_list)); CK(hipFree(d_block)); CK(hipFree(d_phi));
+        out.word(windows); out.word(p.buckets); out.word(nb); out.word(E);
+        dig.collect(out, "digits"); counts.collect(out, "counts"); offsets.collect(out, "offsets"); list.collect(out, "list", E);
+        CK(hipFree(d_scalars)); CK(hipFree(d_bases)); CK(hipFree(d_q)); CK(hipFree(d_cursor)); CK(hipFree(d_block)); CK(hipFree(d_phi));
     }
 }
 
@@ -219,24 +164,21 @@ static void run_digits(Words& in, std::vector<uint32_t>& out) {
 //     n, n1 (terms of the first segment, <= n), phi (1: the caller brings phi(P) with its bases), n scalars (8 words), n bases (64 bytes)
 // OUT per job: c, windows, buckets, problems of the launch (sub-problems when cut), cut, chunk length, the control words
 //     (MSM_CONTROL_WORDS of them: heavy, E, straddling, team, redo, ...), then every problem's result (27 words)
-static void run_msm(Words& in, std::vector<uint32_t>& out) {
-    const uint32_t jobs = in.next();
-    REQUIRE(jobs <= 64, "too many jobs");
-    for (uint32_t job = 0; job < jobs; ++job) {
+static void run_msm(In& in, Out& out) {
+    for (uint32_t job = 0, jobs = job_count(in, 64); job < jobs; ++job) {
         MsmWorkspace ws;
         ws.tune.struct_size = sizeof(h2v_tuning);
-        ws.tune.msm_global_sort = (int)in.next(); ws.tune.msm_no_term_split = (int)in.next(); ws.tune.msm_window_threads = (int)in.next();
-        ws.tune.msm_window_wpw = (int)in.next(); ws.tune.msm_window_slots = (int)in.next();
-        const uint32_t count = in.next();
+        ws.tune.msm_global_sort = (int)in.word(); ws.tune.msm_no_term_split = (int)in.word(); ws.tune.msm_window_threads = (int)in.word();
+        ws.tune.msm_window_wpw = (int)in.word(); ws.tune.msm_window_slots = (int)in.word();
+        const uint32_t count = in.word();
         REQUIRE(count >= 1 && count <= MSM_MAX_PROBLEMS, "bad problem count");
         std::vector<void*> owned;
         MsmProblems pr;
-        G1J* d_out = nullptr;
-        CK(hipMalloc(&d_out, (size_t)count * sizeof(G1J)));
-        CK(hipMemset(d_out, 0xff, (size_t)count * sizeof(G1J)));
+        Guarded<G1J> res(count);
+        G1J* d_out = res.p;
         size_t total = 0; uint32_t nmax = 0;
         for (uint32_t qi = 0; qi < count; ++qi) {
-            const uint32_t n = in.next(), n1 = in.next(), phi = in.next();
+            const uint32_t n = in.word(), n1 = in.word(), phi = in.word();
             REQUIRE(n <= (1u << 20) && n1 <= n && phi <= 1, "bad problem");
             const uint32_t* sc = in.span((size_t)8 * n);
             const std::vector<G1A> bases = bases_from_bytes(in, n);
@@ -267,23 +209,20 @@ static void run_msm(Words& in, std::vector<uint32_t>& out) {
         REQUIRE((size_t)nb + MSM_CONTROL_WORDS <= ws.counts.cap, "plan outside the workspace");
         uint32_t control[MSM_CONTROL_WORDS];
         CK(hipMemcpy(control, ws.counts.p + nb, sizeof(control), hipMemcpyDeviceToHost));
-        out.push_back(p.c); out.push_back(p.windows); out.push_back(p.buckets); out.push_back(launched); out.push_back(L.cut ? 1u : 0u);
-        out.push_back(msm_chunk_len(control[1], MSM_ACC_LANES_PER_ROUND));
-        for (uint32_t i = 0; i < MSM_CONTROL_WORDS; ++i) out.push_back(control[i]);
-        append(out, d_out, count);
+        out.word(p.c); out.word(p.windows); out.word(p.buckets); out.word(launched); out.word(L.cut ? 1u : 0u);
+        out.word(msm_chunk_len(control[1], MSM_ACC_LANES_PER_ROUND));
+        out.raw(control, sizeof(control));
+        res.collect(out, "results");
         for (void* d : owned) CK(hipFree(d));
-        CK(hipFree(d_out));
     }
 }
 
 // ---- scale
 // IN: n_jobs; per job: J items, n_pairs, 2 * n_pairs Jacobian points (27 words each), J slots, J scalars (8 words)
 // OUT per job: words per record, then J records as k_accumulator_scale left them (memory preset to 0xff)
-static void run_scale(Words& in, std::vector<uint32_t>& out) {
-    const uint32_t jobs = in.next();
-    REQUIRE(jobs <= 64, "too many jobs");
-    for (uint32_t job = 0; job < jobs; ++job) {
-        const uint32_t J = in.next(), n_pairs = in.next();
+static void run_scale(In& in, Out& out) {
+    for (uint32_t job = 0, jobs = job_count(in, 64); job < jobs; ++job) {
+        const uint32_t J = in.word(), n_pairs = in.word();
         REQUIRE(J >= 1 && J <= 1024 && n_pairs >= 1 && n_pairs <= 1024, "bad job");
         std::vector<G1J> pairs((size_t)2 * n_pairs);
         in.take(pairs.data(), pairs.size());
@@ -292,29 +231,14 @@ static void run_scale(Words& in, std::vector<uint32_t>& out) {
         uint32_t* d_slots = to_device(slots, J);
         uint32_t* d_scalars = to_device(in.span((size_t)8 * J), (size_t)8 * J);
         G1J* d_pairs = to_device(pairs.data(), pairs.size());
-        AccRecord* d_rec = nullptr;
-        CK(hipMalloc(&d_rec, (size_t)J * sizeof(AccRecord)));
-        CK(hipMemset(d_rec, 0xff, (size_t)J * sizeof(AccRecord)));
-        RC(accumulator_scale_many_enqueue(0, d_pairs, d_slots, d_scalars, J, d_rec));
+        Guarded<AccRecord> rec(J);
+        RC(accumulator_scale_many_enqueue(0, d_pairs, d_slots, d_scalars, J, rec.p));
         CK(hipDeviceSynchronize());
-        out.push_back((uint32_t)(sizeof(AccRecord) / 4));
-        append(out, d_rec, J);
-        CK(hipFree(d_slots)); CK(hipFree(d_scalars)); CK(hipFree(d_pairs)); CK(hipFree(d_rec));
+        out.word((uint32_t)(sizeof(AccRecord) / 4));
+        rec.collect(out, "records");
+        CK(hipFree(d_slots)); CK(hipFree(d_scalars)); CK(hipFree(d_pairs));
     }
 }
 
-int main(int argc, char** argv) {
-    REQUIRE(argc == 4, "usage: msm_units law|digits|msm|scale IN OUT");
-    const std::string mode = argv[1];
-    const std::vector<uint32_t> words = slurp_words(argv[2]);
-    Words in{words};
-    std::vector<uint32_t> out;
-    if (mode == "law") run_law(in, out);
-    else if (mode == "digits") run_digits(in, out);
-    else if (mode == "msm") run_msm(in, out);
-    else if (mode == "scale") run_scale(in, out);
-    else REQUIRE(false, "unknown mode");
-    REQUIRE(in.at == words.size(), "input longer than its jobs");
-    spill(argv[3], out);
-    return 0;
-}
+static const Mode MODES[] = {{"law", run_law, true, false}, {"digits", run_digits, true, false}, {"msm", run_msm, true, false}, {"scale", run_scale, true, false}};
+int main(int argc, char** argv) { return units_main("msm_units", MODES, argc, argv); }

@@ -9,59 +9,12 @@
 //   pairing_units lines   PARAMS IN OUT   k_pair_lines over crafted pieces with the split tables of a PairingDevice
 //   pairing_units verdict PARAMS IN OUT   pairing_check_split_enqueue (k_pairing2 or one stream) and pairing_check_enqueue
 //   pairing_units tail    PARAMS IN OUT   pairing_check_split_enqueue with a PairTail: the tail workgroups of k_pairing2 (pair_tail_role)
-// Files are little-endian uint32 words; the layouts are in the readers below.  Every HIP call is checked: the first error ends the
-// program with a non-zero status.  Every index that reaches a kernel is checked on the host first.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
+// Files are little-endian uint32 words; the layouts are in the readers below.  Every index that reaches a kernel is checked on the
+// host first.  The outputs a mode allocates itself are preset to 0xff and lie between guard bands that are checked after the kernels
+// (the line workspace and the mapped host blocks are the library's own types and stay as they are).  The prelude is tests/cpp/units.h.
 #include "../../halo2_verifier_amd/csrc/pairing.hip"
 #include "../../halo2_verifier_amd/csrc/params.hip"
-
-namespace h2v {
-static std::string g_err;
-void set_last_error(const std::string& s) { g_err = s; }
-}
-using namespace h2v;
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
-#define REQUIRE(c, msg) do { if (!(c)) { fprintf(stderr, "bad input: %s\n", msg); exit(2); } } while (0)
-#define RC(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s: %d %s\n", #x, rc_, g_err.c_str()); exit(4); } } while (0)
-
-static std::vector<uint32_t> slurp_words(const char* path) {
-    std::ifstream f(path, std::ios::binary);
-    REQUIRE(f.good(), "cannot open input");
-    std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    REQUIRE(b.size() % 4 == 0, "input is not whole words");
-    std::vector<uint32_t> w(b.size() / 4);
-    memcpy(w.data(), b.data(), b.size());
-    return w;
-}
-static void spill(const char* path, const void* p, size_t bytes) {
-    FILE* f = fopen(path, "wb");
-    REQUIRE(f && fwrite(p, 1, bytes, f) == bytes && fclose(f) == 0, "cannot write output");
-}
-template <class T> static T* to_device(const T* h, size_t n) {
-    T* d = nullptr;
-    CK(hipMalloc(&d, (n ? n : 1) * sizeof(T)));
-    if (n) CK(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-// a cursor over the input words
-struct Words {
-    const std::vector<uint32_t>& w;
-    size_t at = 0;
-    uint32_t next() { REQUIRE(at < w.size(), "input too short"); return w[at++]; }
-    template <class T> void take(T* out, size_t n) {
-        static_assert(sizeof(T) % 4 == 0, "word records");
-        const size_t words = n * sizeof(T) / 4;
-        REQUIRE(at + words <= w.size(), "input too short");
-        memcpy((void*)out, w.data() + at, words * 4);
-        at += words;
-    }
-};
+#include "units.h"
 
 // ---- step: registers 0, 1 come from the pool, register 2 starts as limbs no kernel stores (0xffffffff), the line from the line pool
 #define UNIT_REGS 3
@@ -93,16 +46,14 @@ __global__ void __launch_bounds__(2 * PAIR_THREADS) k_units_step(const StepCase*
 
 // IN: n_pool, n_lines, n_a (k_pairing layout), n_b (column B), pool[n_pool] (Coef6[6]), lines[n_lines] (Fq2[6]), cases[n_a + n_b]
 // OUT: the destination register (Coef6[6]) of every case, in input order
-static int mode_step(const char* in, const char* outp) {
-    const std::vector<uint32_t> w = slurp_words(in);
-    Words r{w};
-    const uint32_t n_pool = r.next(), n_lines = r.next(), n_a = r.next(), n_b = r.next();
+static void mode_step(In& r, Out& out) {
+    const uint32_t n_pool = r.word(), n_lines = r.word(), n_a = r.word(), n_b = r.word();
     REQUIRE(n_pool && n_lines && n_pool < (1u << 24) && n_lines < (1u << 24) && (size_t)n_a + n_b < (1u << 24), "sizes");
     std::vector<Coef6> pool((size_t)n_pool * 6);
     std::vector<Fq2> lines((size_t)n_lines * 6);
     std::vector<StepCase> cases((size_t)n_a + n_b);
     r.take(pool.data(), pool.size()); r.take(lines.data(), lines.size()); r.take(cases.data(), cases.size());
-    REQUIRE(r.at == w.size(), "trailing input");
+    REQUIRE(r.at_end(), "trailing input");
     for (const StepCase& c : cases) {
         const uint32_t op = c.word & 255u, rd = (c.word >> 8) & 255u, ra = (c.word >> 16) & 255u, rb = c.word >> 24;
         const bool known = op == P_SQR || op == P_MUL || op == P_MULL || op == P_CONJ || op == P_CONJ0 || op == P_COPY || op == P_FROB ||
@@ -116,19 +67,15 @@ static int mode_step(const char* in, const char* outp) {
     auto* d_pool = reinterpret_cast<const Coef6(*)[6]>(to_device(pool.data(), pool.size()));
     auto* d_lines = reinterpret_cast<const Fq2(*)[6]>(to_device(lines.data(), lines.size()));
     StepCase* d_cases = to_device(cases.data(), cases.size());
-    Coef6* d_out = nullptr;
-    CK(hipMalloc(&d_out, (cases.size() ? cases.size() : 1) * 6 * sizeof(Coef6)));
-    auto* out6 = reinterpret_cast<Coef6(*)[6]>(d_out);
+    Guarded<Coef6> regs(cases.size() * 6);
+    auto* out6 = reinterpret_cast<Coef6(*)[6]>(regs.p);
     if (n_a) hipLaunchKernelGGL(k_units_step, dim3(n_a), dim3(PAIR_THREADS), 0, 0, d_cases, d_pool, d_lines, d_k, 0u, out6);
     CK(hipGetLastError());
     if (n_b) hipLaunchKernelGGL(k_units_step, dim3(n_b), dim3(2 * PAIR_THREADS), 0, 0, d_cases + n_a, d_pool, d_lines, d_k, 1u, out6 + n_a);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
-    std::vector<Coef6> out(cases.size() * 6);
-    if (!out.empty()) CK(hipMemcpy(out.data(), d_out, out.size() * sizeof(Coef6), hipMemcpyDeviceToHost));
-    spill(outp, out.data(), out.size() * sizeof(Coef6));
+    regs.collect(out, "registers");
     printf("step: %u + %u cases\n", n_a, n_b);
-    return 0;
 }
 
 // ---- check: IN: n, registers[n] (Coef6[6]); OUT: n words, pair_in_fq_star6
@@ -136,36 +83,31 @@ __global__ void k_units_check(const Coef6 (*__restrict__ x)[6], uint32_t n, uint
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) ok[i] = pair_in_fq_star6(x[i]) ? 1u : 0u;
 }
-static int mode_check(const char* in, const char* outp) {
-    const std::vector<uint32_t> w = slurp_words(in);
-    Words r{w};
-    const uint32_t n = r.next();
+static void mode_check(In& r, Out& out) {
+    const uint32_t n = r.word();
     REQUIRE(n && n < (1u << 20), "sizes");
     std::vector<Coef6> regs((size_t)n * 6);
     r.take(regs.data(), regs.size());
-    REQUIRE(r.at == w.size(), "trailing input");
+    REQUIRE(r.at_end(), "trailing input");
     auto* d_regs = reinterpret_cast<const Coef6(*)[6]>(to_device(regs.data(), regs.size()));
-    uint32_t* d_ok = nullptr;
-    CK(hipMalloc(&d_ok, n * 4));
-    hipLaunchKernelGGL(k_units_check, dim3((n + 63) / 64), dim3(64), 0, 0, d_regs, n, d_ok);
+    Guarded<uint32_t> ok(n);
+    hipLaunchKernelGGL(k_units_check, dim3((n + 63) / 64), dim3(64), 0, 0, d_regs, n, ok.p);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
-    std::vector<uint32_t> ok(n);
-    CK(hipMemcpy(ok.data(), d_ok, n * 4, hipMemcpyDeviceToHost));
-    spill(outp, ok.data(), n * 4);
+    ok.collect(out, "verdicts");
     printf("check: %u registers\n", n);
-    return 0;
 }
 
 static void upload_params(const char* path, PairingDevice& pd) {
-    const std::vector<uint32_t> w = slurp_words(path);
+    const std::vector<uint8_t> b = read_file(path);
+    REQUIRE(b.size() % 4 == 0, "params are not whole words");
     ParamsHost params;
     std::string err;
-    if (!params_from_bytes(reinterpret_cast<const uint8_t*>(w.data()), w.size() * 4, H2V_SERDE_RAW_BYTES, params, err)) { fprintf(stderr, "params: %s\n", err.c_str()); exit(2); }
+    if (!params_from_bytes(b.data(), b.size(), H2V_SERDE_RAW_BYTES, params, err)) { fprintf(stderr, "params: %s\n", err.c_str()); exit(2); }
     RC(pd.upload(params));
 }
 // pieces of n checks over `parts` split accumulators, G1J each (X Z, Y, Z^3 for the split entry points), into G1JSlot
-static G1JSlot* read_slots(Words& r, size_t count) {
+static G1JSlot* read_slots(In& r, size_t count) {
     std::vector<G1J> pts(count);
     r.take(pts.data(), count);
     std::vector<G1JSlot> slots(count);
@@ -175,16 +117,13 @@ static G1JSlot* read_slots(Words& r, size_t count) {
 
 // ---- lines: IN: n_jobs, then per job: shift, parts, n, pieces[n * 2 * parts] (check c: L_j at (2c) parts + j, R_j at (2c + 1) parts + j)
 // OUT: per job, k_pair_lines' output: n x PAIR_ITERS x 6 Fq2;  OUT.tables: per job, the host rows of its table (split_line_rows)
-static int mode_lines(const char* params, const char* in, const char* outp) {
+static void mode_lines(In& r, Out& out) {
+    const uint32_t jobs = r.word();
     PairingDevice pd;
-    upload_params(params, pd);
-    const std::vector<uint32_t> w = slurp_words(in);
-    Words r{w};
-    const uint32_t jobs = r.next();
-    std::vector<Fq2> all;
+    upload_params(r.params, pd);
     std::vector<LineCoeff> all_rows;
     for (uint32_t jb = 0; jb < jobs; ++jb) {
-        const uint32_t shift = r.next(), parts = r.next(), n = r.next();
+        const uint32_t shift = r.word(), parts = r.word(), n = r.word();
         REQUIRE(parts >= 1 && parts <= PL_MAX_PARTS && n >= 1 && n <= 64 && shift < 256, "lines job");
         G1JSlot* d_ready = read_slots(r, (size_t)2 * parts * n);
         const LineCoeff* tab = nullptr;
@@ -192,39 +131,28 @@ static int mode_lines(const char* params, const char* in, const char* outp) {
         std::vector<LineCoeff> rows;
         RC(split_line_rows(pd.h_sg2, pd.h_ng2, shift, parts, rows));
         all_rows.insert(all_rows.end(), rows.begin(), rows.end());
-        Fq2* d_out = nullptr;
-        CK(hipMalloc(&d_out, (size_t)n * PAIR_ITERS * 6 * sizeof(Fq2)));
-        hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, 0, d_ready, parts, tab, pair_iterations(), d_out);
+        Guarded<Fq2> lines((size_t)n * PAIR_ITERS * 6);
+        hipLaunchKernelGGL(k_pair_lines, dim3(PAIR_ITERS, n), dim3(PL_THREADS), 0, 0, d_ready, parts, tab, pair_iterations(), lines.p);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
-        const size_t at = all.size();
-        all.resize(at + (size_t)n * PAIR_ITERS * 6);
-        CK(hipMemcpy(all.data() + at, d_out, (size_t)n * PAIR_ITERS * 6 * sizeof(Fq2), hipMemcpyDeviceToHost));
-        CK(hipFree(d_out));
+        lines.collect(out, "lines");
         CK(hipFree(d_ready));
     }
-    REQUIRE(r.at == w.size(), "trailing input");
-    spill(outp, all.data(), all.size() * sizeof(Fq2));
-    spill((std::string(outp) + ".tables").c_str(), all_rows.data(), all_rows.size() * sizeof(LineCoeff));
+    write_file((out.path + ".tables").c_str(), all_rows.data(), all_rows.size() * sizeof(LineCoeff));
     printf("lines: %u jobs\n", jobs);
-    return 0;
 }
 
 // ---- verdict: IN: n_jobs, then per job: kind (0: split, k_pairing2; 1: split, one stream; 2: whole points), shift, parts, n,
 // pieces (split: n * 2 * parts line-ready pieces as in `lines`; whole: n pairs of Jacobian points); OUT: the n verdicts of every job
-static int mode_verdict(const char* params, const char* in, const char* outp) {
+static void mode_verdict(In& r, Out& out) {
+    const uint32_t jobs = r.word();
     PairingDevice pd;
-    upload_params(params, pd);
-    const std::vector<uint32_t> w = slurp_words(in);
-    Words r{w};
-    const uint32_t jobs = r.next();
-    std::vector<uint32_t> all;
+    upload_params(r.params, pd);
     for (uint32_t jb = 0; jb < jobs; ++jb) {
-        const uint32_t kind = r.next(), shift = r.next(), parts = r.next(), n = r.next();
+        const uint32_t kind = r.word(), shift = r.word(), parts = r.word(), n = r.word();
         REQUIRE(kind <= 2 && n >= 1 && n <= 64 && shift < 256, "verdict job");
-        uint32_t* d_ok = nullptr;
-        CK(hipMalloc(&d_ok, n * 4));
-        CK(hipMemset(d_ok, 0xff, n * 4));
+        Guarded<uint32_t> ok(n);
+        uint32_t* d_ok = ok.p;
         if (kind == 2) {
             std::vector<G1J> pairs((size_t)2 * n);
             r.take(pairs.data(), pairs.size());
@@ -242,15 +170,9 @@ static int mode_verdict(const char* params, const char* in, const char* outp) {
             CK(hipFree(d_ws));
             CK(hipFree(d_ready));
         }
-        const size_t at = all.size();
-        all.resize(at + n);
-        CK(hipMemcpy(all.data() + at, d_ok, n * 4, hipMemcpyDeviceToHost));
-        CK(hipFree(d_ok));
+        ok.collect(out, "verdicts");
     }
-    REQUIRE(r.at == w.size(), "trailing input");
-    spill(outp, all.data(), all.size() * 4);
     printf("verdict: %u jobs\n", jobs);
-    return 0;
 }
 
 // ---- tail: IN: n_jobs, then per job: shift, parts, n, count, n_words, skip_lo, skip_hi; the checks' line-ready pieces (n * 2 * parts, as in
@@ -262,24 +184,13 @@ static int mode_verdict(const char* params, const char* in, const char* outp) {
 // OUT per job: n verdicts; count + 1 whole points (27 words); the device block: (count + 1) * 16 words of bytes, count + 1 identity words;
 // the host block likewise; n_words + TAIL_DST_SPARE words of dst
 #define TAIL_DST_SPARE 16u
-static int mode_tail(const char* params, const char* in, const char* outp) {
+static void mode_tail(In& r, Out& out) {
+    const uint32_t jobs = job_count(r, 256);
     PairingDevice pd;
-    upload_params(params, pd);
-    if (!pairing_tail_fits(pd, false)) { fprintf(stderr, "tail: this device's pairing launch cannot carry a tail (pairing_tail_fits)\n"); return 6; }
-    const std::vector<uint32_t> w = slurp_words(in);
-    Words r{w};
-    const uint32_t jobs = r.next();
-    REQUIRE(jobs <= 256, "too many jobs");
-    std::vector<uint32_t> all;
-    auto append = [&](const void* p, size_t words, bool device) {
-        const size_t at = all.size();
-        all.resize(at + words);
-        if (!words) return;
-        if (device) CK(hipMemcpy(all.data() + at, p, words * 4, hipMemcpyDeviceToHost));
-        else memcpy(all.data() + at, p, words * 4);
-    };
+    upload_params(r.params, pd);
+    if (!pairing_tail_fits(pd, false)) { fprintf(stderr, "tail: this device's pairing launch cannot carry a tail (pairing_tail_fits)\n"); exit(6); }
     for (uint32_t jb = 0; jb < jobs; ++jb) {
-        const uint32_t shift = r.next(), parts = r.next(), n = r.next(), count = r.next(), n_words = r.next(), skip_lo = r.next(), skip_hi = r.next();
+        const uint32_t shift = r.word(), parts = r.word(), n = r.word(), count = r.word(), n_words = r.word(), skip_lo = r.word(), skip_hi = r.word();
         REQUIRE(n >= 1 && n <= 64 && parts >= 1 && parts <= PL_MAX_PARTS && shift < 256, "tail job");
         REQUIRE(count >= 1 && count <= 128 && n_words >= 1 && n_words <= (1u << 16) && skip_lo <= skip_hi && skip_hi <= n_words, "tail shape");
         G1JSlot* d_ready = read_slots(r, (size_t)2 * parts * n);
@@ -292,12 +203,11 @@ static int mode_tail(const char* params, const char* in, const char* outp) {
         std::vector<uint32_t> src(n_words);
         r.take(src.data(), n_words);
         uint32_t* d_src = to_device(src.data(), n_words);
-        G1J* d_whole = nullptr; uint8_t* d_bytes = nullptr; uint32_t* d_ident = nullptr; uint32_t* d_ok = nullptr; void* d_ws = nullptr;
-        CK(hipMalloc(&d_whole, slots * sizeof(G1J))); CK(hipMalloc(&d_bytes, slots * 64)); CK(hipMalloc(&d_ident, slots * 4)); CK(hipMalloc(&d_ok, n * 4));
+        Guarded<G1J> whole(slots); Guarded<uint8_t> bytes(slots * 64); Guarded<uint32_t> ident(slots), ok(n);
+        void* d_ws = nullptr;
         CK(hipMalloc(&d_ws, (size_t)n * H2V_PAIRING_LINE_WS_BYTES));
-        CK(hipMemset(d_whole, 0xff, slots * sizeof(G1J))); CK(hipMemset(d_bytes, 0xff, slots * 64)); CK(hipMemset(d_ident, 0xff, slots * 4)); CK(hipMemset(d_ok, 0xff, n * 4));
         std::vector<MsmProblem> prs(slots);
-        for (size_t q = 0; q < slots; ++q) prs[q].out = d_whole + q;
+        for (size_t q = 0; q < slots; ++q) prs[q].out = whole.p + q;
         MsmProblem* d_prs = to_device(prs.data(), slots);
         MappedHostBuf h_bytes, h_ident, h_dst;
         const size_t dst_words = (size_t)n_words + TAIL_DST_SPARE;
@@ -305,33 +215,21 @@ static int mode_tail(const char* params, const char* in, const char* outp) {
         memset(h_bytes.p, 0xff, slots * 64); memset(h_ident.p, 0xff, slots * 4); memset(h_dst.p, 0xff, dst_words * 4);
         PairTail t;
         t.pieces = d_pieces; t.prs = d_prs; t.count = count; t.parts = parts; t.shift = shift;
-        t.out_bytes = d_bytes; t.out_ident = d_ident;
+        t.out_bytes = bytes.p; t.out_ident = ident.p;
         t.host_bytes = reinterpret_cast<uint8_t*>(h_bytes.dev); t.host_ident = reinterpret_cast<uint32_t*>(h_ident.dev);
         t.src = d_src; t.dst = reinterpret_cast<uint32_t*>(h_dst.dev);
         t.n_words = n_words; t.skip_lo = skip_lo; t.skip_hi = skip_hi;
-        RC(pairing_check_split_enqueue(0, pd, d_ready, n, parts, shift, d_ws, d_ok, false, &t));
+        RC(pairing_check_split_enqueue(0, pd, d_ready, n, parts, shift, d_ws, ok.p, false, &t));
         CK(hipDeviceSynchronize());
-        append(d_ok, n, true);
-        append(d_whole, slots * sizeof(G1J) / 4, true);
-        append(d_bytes, slots * 16, true); append(d_ident, slots, true);
-        append(h_bytes.p, slots * 16, false); append(h_ident.p, slots, false);
-        append(h_dst.p, dst_words, false);
-        CK(hipFree(d_ready)); CK(hipFree(d_pieces)); CK(hipFree(d_src)); CK(hipFree(d_whole)); CK(hipFree(d_bytes)); CK(hipFree(d_ident));
-        CK(hipFree(d_ok)); CK(hipFree(d_ws)); CK(hipFree(d_prs));
+        ok.collect(out, "verdicts"); whole.collect(out, "whole points");
+        bytes.collect(out, "device bytes"); ident.collect(out, "device identity words");
+        out.raw(h_bytes.p, slots * 64); out.raw(h_ident.p, slots * 4);
+        out.raw(h_dst.p, dst_words * 4);
+        CK(hipFree(d_ready)); CK(hipFree(d_pieces)); CK(hipFree(d_src)); CK(hipFree(d_ws)); CK(hipFree(d_prs));
     }
-    REQUIRE(r.at == w.size(), "trailing input");
-    spill(outp, all.data(), all.size() * 4);
     printf("tail: %u jobs\n", jobs);
-    return 0;
 }
 
-int main(int argc, char** argv) {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    if (mode == "step" && argc == 4) return mode_step(argv[2], argv[3]);
-    if (mode == "check" && argc == 4) return mode_check(argv[2], argv[3]);
-    if (mode == "lines" && argc == 5) return mode_lines(argv[2], argv[3], argv[4]);
-    if (mode == "verdict" && argc == 5) return mode_verdict(argv[2], argv[3], argv[4]);
-    if (mode == "tail" && argc == 5) return mode_tail(argv[2], argv[3], argv[4]);
-    fprintf(stderr, "usage: pairing_units step|check IN OUT | lines|verdict|tail PARAMS IN OUT\n");
-    return 2;
-}
+static const Mode MODES[] = {{"step", mode_step, true, false}, {"check", mode_check, true, false},
+                             {"lines", mode_lines, true, true}, {"verdict", mode_verdict, true, true}, {"tail", mode_tail, true, true}};
+int main(int argc, char** argv) { return units_main("pairing_units", MODES, argc, argv); }

@@ -1,66 +1,30 @@
 // The per-proof kernels (halo2_verifier_amd/csrc/verify_kernels.hip) stage by stage, on inputs programmed by
-// tests/test_gpu_verify_units.py and compared there with tests/verify_reference.py.  Built with the library's flags by
-// halo2_verifier_amd/csrc/Makefile (build/verify_units).
+// tests/test_gpu_verify_units.py and compared there with tests/verify_reference.py, and the batch multipliers' kernels on raw draws
+// chosen by tests/test_gpu_multipliers.py and tests/test_gpu_ragged_multipliers.py.  Built with the library's flags by
+// halo2_verifier_amd/csrc/Makefile (build/verify_units); the prelude is tests/cpp/units.h.
 //
-//   verify_units decompress IN OUT   decompress_begin / _range (in the pieces the input gives) / _finish: k_decompress, k_check_scalars
-//   verify_units stream     IN OUT   transcript_stage_enqueue: k_stream_build, then k_transcript or k_transcript_keccak
-//   verify_units insteval   IN OUT   instance_eval_enqueue: k_instance_eval
-//   verify_units frvm       IN OUT   frvm_enqueue: k_frvm / k_frvm2 on a programmed VmInstr program
-//   verify_units fold       IN OUT   fold_shared_enqueue (k_fold_shared) and fold_shared_ranges_enqueue (k_fold_ranges)
+//   verify_units decompress  IN OUT   decompress_begin / _range (in the pieces the input gives) / _finish: k_decompress, k_check_scalars
+//   verify_units stream      IN OUT   transcript_stage_enqueue: k_stream_build, then k_transcript or k_transcript_keccak
+//   verify_units insteval    IN OUT   instance_eval_enqueue: k_instance_eval
+//   verify_units frvm        IN OUT   frvm_enqueue: k_frvm / k_frvm2 on a programmed VmInstr program
+//   verify_units fold        IN OUT   fold_shared_enqueue (k_fold_shared) and fold_shared_ranges_enqueue (k_fold_ranges)
+//   verify_units multipliers IN OUT   multipliers_enqueue: k_mult_tiles, k_mult_scan_tiles, k_mult_apply over groups of equal size
+//   verify_units gather      IN OUT   gather_multipliers_enqueue: k_gather_multipliers (a file of whole words)
+//   verify_units ragged      IN OUT   ragged_multipliers_enqueue: the segmented suffix scan k_seg_mult_tiles, k_seg_mult_scan_tiles,
+//                                     k_seg_mult_apply over groups of unequal size
 // IN is little-endian: a word n_jobs, then per job the words and byte blocks its reader below takes, in that order.  OUT is the jobs'
 // results one after another (the layouts are at the writers).  Field elements cross the file boundary as 32 canonical little-endian
 // bytes.  The Plan and PlanDevice a launcher wants are filled by hand from the input: no compile_plan, no PlanDevice::upload.
-// Every HIP call is checked: the first error ends the program with a non-zero status.  Every count, offset and index that reaches a
-// kernel is checked on the host against the buffer sizes first ("bad input", status 2): no input can make a kernel leave its buffers.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
+// Every count, offset and index that reaches a kernel is checked on the host against the buffer sizes first ("bad input", status 2):
+// no input can make a kernel leave its buffers.  Every output buffer lies between guard bands that are checked after the launch.
 #include "../../halo2_verifier_amd/csrc/verify_kernels.hip"
+#include "units.h"
 
-namespace h2v {
-static std::string g_err;
-void set_last_error(const std::string& s) { g_err = s; }
-}
-using namespace h2v;
+#define FILL 0x11   // what the per-proof stages' output buffers hold before a launch: limbs 0x11111111 are normalised, so an unwritten Fr still converts
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); exit(3); } } while (0)
-#define REQUIRE(c, msg) do { if (!(c)) { fprintf(stderr, "bad input: %s (%s)\n", msg, #c); exit(2); } } while (0)
-#define RC(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s: %d %s\n", #x, rc_, g_err.c_str()); exit(4); } } while (0)
-
-#define FILL 0x11   // what every output buffer holds before a launch: limbs 0x11111111 are normalised, so an unwritten Fr still converts
-
-// a cursor over the input bytes
-struct In {
-    std::vector<uint8_t> b;
-    size_t at = 0;
-    uint32_t word() { REQUIRE(b.size() - at >= 4, "input too short"); uint32_t w; memcpy(&w, b.data() + at, 4); at += 4; return w; }
-    std::vector<uint32_t> words(size_t n) { REQUIRE(n <= (b.size() - at) / 4, "input too short"); std::vector<uint32_t> v(n); if (n) memcpy(v.data(), b.data() + at, 4 * n); at += 4 * n; return v; }
-    const uint8_t* bytes(size_t n) { REQUIRE(n <= b.size() - at, "input too short"); const uint8_t* p = b.data() + at; at += n; return p; }
-    Fr fr() { Fr v; REQUIRE(Fr::from_bytes(bytes(32), v), "field element not canonical"); return v; }
-    std::vector<Fr> frs(size_t n) { REQUIRE(n <= (b.size() - at) / 32, "input too short"); std::vector<Fr> v(n); for (size_t i = 0; i < n; ++i) v[i] = fr(); return v; }
-};
-struct Out {
-    std::vector<uint8_t> b;
-    void word(uint32_t w) { const size_t o = b.size(); b.resize(o + 4); memcpy(&b[o], &w, 4); }
-    void raw(const void* p, size_t n) { const size_t o = b.size(); b.resize(o + n); if (n) memcpy(&b[o], p, n); }
-    template <class F> void field(const F& v) { const size_t o = b.size(); b.resize(o + 32); v.to_bytes(&b[o]); }
-};
-// a device buffer of n elements, filled with FILL
-template <class T> static void fresh(DevBuf<T>& d, size_t n) {
-    RC(d.alloc(n));
-    CK(hipMemset((void*)d.p, FILL, (n ? n : 1) * sizeof(T)));
-}
 template <class T> static void upload(DevBuf<T>& d, const T* h, size_t n) {
     RC(d.alloc(n));
     if (n) CK(hipMemcpy((void*)d.p, (const void*)h, n * sizeof(T), hipMemcpyHostToDevice));
-}
-template <class T> static std::vector<T> download(const T* d, size_t n) {
-    std::vector<T> h(n);
-    if (n) CK(hipMemcpy((void*)h.data(), (const void*)d, n * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
 }
 // a source buffer of the stream builder: 32 bytes of slack on both sides, filled with 0xA5 (the unaligned 8-byte loads of the fast
 // path stay inside the allocation for any table; a byte wrongly taken from the slack shows in the result)
@@ -74,8 +38,7 @@ struct Slack {
         p = buf.p + 32;
     }
 };
-static void out_fields(Out& out, const Fr* d, size_t n) { for (const Fr& v : download(d, n)) out.field(v); }
-static void out_words(Out& out, const void* d, size_t n_words) { const std::vector<uint32_t> h = download((const uint32_t*)d, n_words); out.raw(h.data(), 4 * n_words); }
+static void out_fields(Out& out, const Guarded<Fr>& d, const char* what) { for (const Fr& v : d.host(what)) out.field(v); }
 
 #define MAX_PROOFS 4096u
 #define MAX_ITEMS 1024u
@@ -101,24 +64,24 @@ static void run_decompress(In& in, Out& out) {
     for (uint32_t o : pl.scalar_offsets) REQUIRE(o % 32 == 0 && o <= proof_len - 32, "scalar offset");
     upload(pd.point_offsets, pl.point_offsets.data(), np);
     upload(pd.scalar_offsets, pl.scalar_offsets.data(), ns);
-    DevBuf<uint8_t> proofs, inst, ycanon; DevBuf<G1A> pts, phi; DevBuf<int> status;
+    DevBuf<uint8_t> proofs, inst;
     upload(proofs, in.bytes((size_t)n * proof_len), (size_t)n * proof_len);
     upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
     const size_t tp = (size_t)n * np;
-    fresh(pts, tp); fresh(phi, tp); fresh(ycanon, tp * 32); fresh(status, n);   // (the status words too: the begin step resets them)
+    Guarded<G1A> pts(tp, FILL), phi(tp, FILL); Guarded<uint8_t> ycanon(tp * 32, FILL); Guarded<int> status(n, FILL);   // (the status words too: the begin step resets them)
     StageArgs g{n, &pl, &pd, proofs.p, inst.p, pts.p, phi.p, ycanon.p, status.p, nullptr, 0, nullptr};
     RC(decompress_begin_enqueue(0, g));
     for (uint32_t i = 0; i < n_pieces; ++i) RC(decompress_range_enqueue(0, g, cut[i], cut[i + 1]));
     RC(decompress_finish_enqueue(0, g));
     CK(hipDeviceSynchronize());
-    const std::vector<G1A> hp = download(pts.p, tp), hf = download(phi.p, tp);
-    const std::vector<uint8_t> hy = download(ycanon.p, tp * 32);
+    const std::vector<G1A> hp = pts.host("pts"), hf = phi.host("phi");
+    const std::vector<uint8_t> hy = ycanon.host("ycanon");
     for (size_t i = 0; i < tp; ++i) {
         out.field(hp[i].x); out.field(hp[i].y); out.field(hf[i].x); out.field(hf[i].y);
         out.word(hp[i].is_identity() ? 1u : 0u);
         out.raw(&hy[32 * i], 32);
     }
-    out_words(out, status.p, n);
+    status.collect(out, "status");
 }
 
 // ---- stream
@@ -152,14 +115,13 @@ static void run_stream(In& in, Out& out) {
     inst.set(in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
     const uint32_t sw = stream_words_for(stream_len, pl.opts.transcript);
     REQUIRE((size_t)sw * 8 > stream_len, "stream words");   // every squeeze's last block, and a prefetched block behind it, lie inside
-    DevBuf<unsigned long long> words; DevBuf<Fr> chal;
-    fresh(words, (size_t)n * sw); fresh(chal, (size_t)nsq * n);
+    Guarded<unsigned long long> words((size_t)n * sw, FILL); Guarded<Fr> chal((size_t)nsq * n, FILL);
     StageArgs g{n, &pl, &pd, proofs.p, inst.p, nullptr, nullptr, const_cast<uint8_t*>(ycanon.p), nullptr, words.p, sw, chal.p};
     const int rc = transcript_stage_enqueue(0, g);
     CK(hipDeviceSynchronize());
     out.word((uint32_t)rc); out.word(sw);
-    out_words(out, words.p, (size_t)n * sw * 2);
-    out_fields(out, chal.p, (size_t)nsq * n);
+    words.collect(out, "stream words");
+    out_fields(out, chal, "challenges");
 }
 
 // ---- insteval
@@ -171,12 +133,12 @@ static void run_insteval(In& in, Out& out) {
     const uint32_t x_chal = in.word(), n_chal = in.word();
     REQUIRE(n >= 1 && n <= 64 && k >= 1 && k <= 28 && ninst <= (1u << 16) && n_chal <= 64, "counts");
     REQUIRE(base <= ninst && len <= ninst - base && x_chal < n_chal && rot >= -1024 && rot <= 1024, "column");
-    const Fr omega = in.fr();
-    DevBuf<uint8_t> inst; DevBuf<Fr> chal, res; DevBuf<int> status;
+    const Fr omega = in.field<Fr>();
+    DevBuf<uint8_t> inst; DevBuf<Fr> chal; DevBuf<int> status;
     upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
-    const std::vector<Fr> hc = in.frs((size_t)n_chal * n);
+    const std::vector<Fr> hc = in.fields<Fr>((size_t)n_chal * n);
     upload(chal, hc.data(), hc.size());
-    fresh(res, n);
+    Guarded<Fr> res(n, FILL);
     RC(status.alloc(n));
     CK(hipMemset(status.p, 0, sizeof(int) * n));
     Fr step = omega;
@@ -185,8 +147,8 @@ static void run_insteval(In& in, Out& out) {
     InstEvalArgs a{inst.p, ninst, chal.p, x_chal, n, k, base, len, w_start, omega, step, step.inv(), Fr::from_u32(1u << k).inv(), res.p, status.p};
     RC(instance_eval_enqueue(0, a));
     CK(hipDeviceSynchronize());
-    out_fields(out, res.p, n);
-    out_words(out, status.p, n);
+    out_fields(out, res, "out");
+    append(out, status.p, n);
 }
 
 // ---- frvm
@@ -258,22 +220,22 @@ static void run_frvm(In& in, Out& out) {
             else if (n_code_k[k][w]) REQUIRE(b == barriers, "barriers of a K-stream form");
         }
     }
-    const std::vector<Fr> consts = in.frs(n_consts);
+    const std::vector<Fr> consts = in.fields<Fr>(n_consts);
     const std::vector<uint32_t> soff = in.words(ns);
     for (uint32_t o : soff) REQUIRE(proof_len >= 32 && o % 32 == 0 && o <= proof_len - 32, "scalar offset");   // (two 16-byte loads per scalar)
-    DevBuf<VmInstr> d_code, d_code_k[3][FRVM_MAX_STREAMS]; DevBuf<Fr> d_consts, slots, chal, insteval, mult, shared; DevBuf<uint32_t> d_soff, msm, left, guard;
+    DevBuf<VmInstr> d_code, d_code_k[3][FRVM_MAX_STREAMS]; DevBuf<Fr> d_consts, chal, insteval, mult; DevBuf<uint32_t> d_soff;
     DevBuf<uint8_t> proofs, inst; DevBuf<int> status;
     upload(d_code, code.data(), code.size());
     upload(d_consts, consts.data(), consts.size());
     upload(d_soff, soff.data(), soff.size());
     upload(proofs, in.bytes((size_t)n * proof_len), (size_t)n * proof_len);
     upload(inst, in.bytes((size_t)n * ninst * 32), (size_t)n * ninst * 32);
-    { const std::vector<Fr> h = in.frs((size_t)n_chal * n); upload(chal, h.data(), h.size()); }
-    { const std::vector<Fr> h = in.frs((size_t)n_insteval * n); upload(insteval, h.data(), h.size()); }
-    { const std::vector<Fr> h = in.frs(n); upload(mult, h.data(), h.size()); }
+    { const std::vector<Fr> h = in.fields<Fr>((size_t)n_chal * n); upload(chal, h.data(), h.size()); }
+    { const std::vector<Fr> h = in.fields<Fr>((size_t)n_insteval * n); upload(insteval, h.data(), h.size()); }
+    { const std::vector<Fr> h = in.fields<Fr>(n); upload(mult, h.data(), h.size()); }
     { const std::vector<uint32_t> h = in.words(n); upload(status, (const int*)h.data(), h.size()); }
-    fresh(slots, (size_t)max_slots * n);
-    fresh(msm, (size_t)n * np * 8); fresh(left, (size_t)n * np * 8); fresh(guard, (size_t)n * n_guard * 8); fresh(shared, (size_t)n_shared * n);
+    Guarded<Fr> slots((size_t)max_slots * n, FILL), shared((size_t)n_shared * n, FILL);
+    Guarded<uint32_t> msm((size_t)n * np * 8, FILL), left((size_t)n * np * 8, FILL), guard((size_t)n * n_guard * 8, FILL);
     FrvmArgs a;
     a.code = d_code.p; a.n_code = n_code; a.consts = d_consts.p; a.slots = slots.p; a.n = n;
     a.proofs = proofs.p; a.proof_len = proof_len; a.scalar_offsets = d_soff.p; a.inst = inst.p; a.ninst = ninst;
@@ -290,11 +252,10 @@ static void run_frvm(In& in, Out& out) {
     a.force_streams = force_streams; a.force_lds_kb = force_lds_kb;
     RC(frvm_enqueue(0, a, n_slots));
     CK(hipDeviceSynchronize());
-    out_words(out, msm.p, (size_t)n * np * 8);
-    out_words(out, left.p, (size_t)n * np * 8);
-    out_words(out, guard.p, (size_t)n * n_guard * 8);
-    out_fields(out, shared.p, (size_t)n_shared * n);
-    out_words(out, status.p, n);
+    slots.host("slots");
+    msm.collect(out, "msm_scal"); left.collect(out, "left_scal"); guard.collect(out, "guard_scal");
+    out_fields(out, shared, "shared");
+    append(out, status.p, n);
 }
 
 // ---- fold
@@ -309,13 +270,13 @@ static void run_fold(In& in, Out& out) {
     if (form == 0) {
         const uint32_t n = in.word(), np = in.word(), n_shared = in.word(), groups = in.word();
         REQUIRE(n >= 1 && n <= (1u << 16) && np <= 16 && n_shared >= 1 && n_shared <= MAX_ITEMS && groups >= 1 && groups <= n && n % groups == 0, "counts");
-        DevBuf<Fr> shared; DevBuf<uint32_t> msm;
-        { const std::vector<Fr> h = in.frs((size_t)n_shared * n); upload(shared, h.data(), h.size()); }
+        DevBuf<Fr> shared;
+        { const std::vector<Fr> h = in.fields<Fr>((size_t)n_shared * n); upload(shared, h.data(), h.size()); }
         const size_t rows = (size_t)n * np + (size_t)groups * n_shared;
-        fresh(msm, rows * 8);
+        Guarded<uint32_t> msm(rows * 8, FILL);
         RC(fold_shared_enqueue(0, shared.p, n, np, n_shared, groups, msm.p));
         CK(hipDeviceSynchronize());
-        out_words(out, msm.p, rows * 8);
+        msm.collect(out, "msm_scal");
         return;
     }
     const uint32_t n_batches = in.word();
@@ -325,7 +286,7 @@ static void run_fold(In& in, Out& out) {
     for (uint32_t b = 0; b < n_batches; ++b) {
         bn[b] = in.word(); bs[b] = in.word();
         REQUIRE(bn[b] >= 1 && bn[b] <= (1u << 16) && bs[b] >= 1 && bs[b] <= MAX_ITEMS, "batch");
-        const std::vector<Fr> h = in.frs((size_t)bs[b] * bn[b]);
+        const std::vector<Fr> h = in.fields<Fr>((size_t)bs[b] * bn[b]);
         upload(shared[b], h.data(), h.size());
     }
     const uint32_t n_ranges = in.word();
@@ -342,31 +303,79 @@ static void run_fold(In& in, Out& out) {
     const uint32_t max_shared = in.word(), out_rows = in.word();
     REQUIRE(max_shared >= 1 && max_shared <= MAX_ITEMS && out_rows <= (1u << 20), "rows");
     for (uint32_t r = 0; r < n_ranges; ++r) REQUIRE(rg[r].n_shared <= max_shared && rg[r].out <= out_rows && rg[r].n_shared <= out_rows - rg[r].out, "range's rows");
-    DevBuf<FoldRange> d_rg; DevBuf<uint32_t> rows;
+    DevBuf<FoldRange> d_rg;
     upload(d_rg, rg.data(), rg.size());
-    fresh(rows, (size_t)out_rows * 8);
+    Guarded<uint32_t> rows((size_t)out_rows * 8, FILL);
     RC(fold_shared_ranges_enqueue(0, d_rg.p, n_ranges, max_shared, rows.p));
     CK(hipDeviceSynchronize());
-    out_words(out, rows.p, (size_t)out_rows * 8);
+    rows.collect(out, "rows");
 }
 
-int main(int argc, char** argv) {
-    REQUIRE(argc == 4, "usage: verify_units decompress|stream|insteval|frvm|fold IN OUT");
-    const std::string mode = argv[1];
-    void (*run)(In&, Out&) = mode == "decompress" ? run_decompress : mode == "stream" ? run_stream : mode == "insteval" ? run_insteval : mode == "frvm" ? run_frvm : mode == "fold" ? run_fold : nullptr;
-    REQUIRE(run, "unknown mode");
-    In in;
-    {
-        std::ifstream f(argv[2], std::ios::binary);
-        REQUIRE(f.good(), "cannot open input");
-        in.b.assign((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    }
-    Out out;
-    const uint32_t jobs = in.word();
-    REQUIRE(jobs <= 4096, "jobs");
-    for (uint32_t j = 0; j < jobs; ++j) run(in, out);
-    REQUIRE(in.at == in.b.size(), "input longer than its jobs");
-    FILE* g = fopen(argv[3], "wb");
-    REQUIRE(g && fwrite(out.b.data(), 1, out.b.size(), g) == out.b.size() && fclose(g) == 0, "cannot write output");
-    return 0;
+// ---- multipliers
+// job: groups, n_tail per group, n per group, then groups * n_tail draws of 32 little-endian bytes
+// out: groups * n multipliers of 32 canonical bytes: mult[g][p] = prod_{j > p} draw[g][j] mod r
+static void run_multipliers(In& in, Out& out) {
+    const uint32_t G = in.word(), nt = in.word(), n = in.word();
+    REQUIRE(G && nt && n && n <= nt && G <= 1024 && nt <= (1u << 22) && (size_t)G * nt <= (1u << 22), "bad job");
+    const size_t draws = (size_t)G * nt, mults = (size_t)G * n;
+    REQUIRE(draws <= in.left() / 32, "input too short");
+    uint8_t* d_tail = to_device(in.bytes(32 * draws), 32 * draws);
+    Guarded<Fr> mult(mults), scratch(multipliers_scratch(G * nt, G));
+    RC(multipliers_enqueue(0, d_tail, G * nt, G * n, G, mult.p, scratch.p));
+    CK(hipDeviceSynchronize());
+    scratch.host("scratch");
+    out_fields(out, mult, "multipliers");
+    CK(hipFree(d_tail));
 }
+
+// ---- gather
+// job: n_src, n, n_src source elements (9 raw limbs each, as they lie in memory), n indices
+// out: n elements (9 limbs each): out[i] = src[idx[i]]
+static void run_gather(In& in, Out& out) {
+    static_assert(sizeof(Fr) == 36, "nine limbs");
+    const uint32_t n_src = in.word(), n = in.word();
+    REQUIRE(n_src >= 1 && n_src <= (1u << 16) && n <= (1u << 16), "bad gather job");
+    std::vector<Fr> src(n_src);
+    in.take(src.data(), n_src);
+    const std::vector<uint32_t> idx = in.words(n);
+    for (uint32_t i : idx) REQUIRE(i < n_src, "index outside the source");
+    Fr* d_src = to_device(src.data(), n_src);
+    uint32_t* d_idx = to_device(idx.data(), n);
+    Guarded<Fr> res(n);
+    RC(gather_multipliers_enqueue(0, d_src, d_idx, n, res.p));
+    CK(hipDeviceSynchronize());
+    res.collect(out, "gathered elements");
+    CK(hipFree(d_src)); CK(hipFree(d_idx));
+}
+
+// ---- ragged
+// job: n_groups, the n_groups sizes, then sum(sizes) draws of 32 little-endian bytes
+// out: sum(sizes) multipliers of 32 canonical bytes: mult[p] = the product of the draws behind p in p's group
+// The "last proof of its group" bytes are built here as the library's host side builds them; the per-tile scratch arrays lie between bands too.
+static void run_ragged(In& in, Out& out) {
+    const uint32_t G = in.word();
+    REQUIRE(G >= 1 && G <= (1u << 20), "bad group count");
+    std::vector<uint8_t> last;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t sz = in.word();
+        REQUIRE(sz >= 1 && sz <= (1u << 22) && last.size() + sz <= (1u << 22), "bad group size");
+        last.resize(last.size() + sz, 0); last.back() = 1;
+    }
+    const size_t n = last.size(), tiles = ragged_multipliers_tiles((uint32_t)n);
+    REQUIRE(n <= in.left() / 32, "input too short");
+    uint8_t* d_tail = to_device(in.bytes(32 * n), 32 * n);
+    uint8_t* d_last = to_device(last.data(), n);
+    Guarded<Fr> mult(n), tile_prod(tiles);
+    Guarded<uint32_t> tile_words(2 * tiles);
+    RC(ragged_multipliers_enqueue(0, d_tail, d_last, (uint32_t)n, mult.p, tile_prod.p, tile_words.p));
+    CK(hipDeviceSynchronize());
+    tile_prod.host("tile products"); tile_words.host("tile words");
+    out_fields(out, mult, "multipliers");
+    CK(hipFree(d_tail)); CK(hipFree(d_last));
+}
+
+static const Mode MODES[] = {{"decompress", each_job<run_decompress, 4096>, false, false}, {"stream", each_job<run_stream, 4096>, false, false},
+                             {"insteval", each_job<run_insteval, 4096>, false, false}, {"frvm", each_job<run_frvm, 4096>, false, false},
+                             {"fold", each_job<run_fold, 4096>, false, false}, {"multipliers", each_job<run_multipliers, 64>, false, false},
+                             {"gather", each_job<run_gather, 64>, true, false}, {"ragged", each_job<run_ragged, 64>, false, false}};
+int main(int argc, char** argv) { return units_main("verify_units", MODES, argc, argv); }

@@ -1,5 +1,5 @@
 """The fold of a merge, k_accumulator_merge_fold (csrc/util.hip), alone against Python big integers (tests/merge_reference.py).
-build/merge_units (tests/cpp/merge_units.hip, built by csrc/Makefile with the library's flags) runs the kernel through the library's
+build/util_units merge_fold (tests/cpp/util_units.hip, built by csrc/Makefile with the library's flags) runs the kernel through the library's
 own launcher on raw limbs chosen here, with the outputs between guard bands that the harness checks.
 
 K = 0, 1, 2, 7, 8, 63, 64, 65, 129 and 512 records, each with the team the host rule picks and with the team forced to 1, 8 and 64
@@ -9,10 +9,8 @@ complete addition, inside a lane's own loop and at every butterfly level), P bes
 the records into journal slots — without a journal, without a map, and through a map whose slots are out of order.
 The accumulator is compared as a pair of group elements; a journal slot is the record's point word for word, and a slot no record owns
 keeps its preset.  One child process for all jobs, under a time limit."""
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,11 +19,10 @@ import merge_reference as mr
 import msm_reference as ref
 import record_reference as rr
 from msm_reference import R
+import units_harness as uh
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "merge_units")
 KS = [0, 1, 2, 7, 8, 63, 64, 65, 129, 512]
 TEAMS = [0, 1, 8, 64]           # 0: the host rule
 REPS3 = [(a, b, c) for a in (False, True) for b in (False, True) for c in (False, True)]
@@ -178,12 +175,7 @@ def _jobs():
 
 
 def _run(blob, tmp_path, timeout=120):
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
-    src, dst = tmp_path / "merge_in.bin", tmp_path / "merge_out.bin"
-    src.write_bytes(blob)
-    r = subprocess.run([EXE, "fold", str(src), str(dst)], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    return np.frombuffer(dst.read_bytes(), dtype="<u4")
+    return uh.as_words(uh.run("util_units", ["merge_fold"], blob, tmp_path, timeout))
 
 
 def test_host_rule():

@@ -13,10 +13,8 @@ library's own code on scalars, points and bucket layouts chosen here; every comp
 One child process per mode, each under a time limit."""
 import functools
 import itertools
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,11 +22,11 @@ import pytest
 import msm_reference as ref
 import oracle_lib
 from msm_reference import LAMBDA, P, R
+from units_harness import words as _words
+import units_harness as uh
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "msm_units")
 WIDTHS = [2, 3, 4, 5, 6, 7, 10, 11, 12]
 ENTRY_HALF, ENTRY_NEG, ENTRY_TERM = 0x40000000, 0x80000000, 0x3fffffff
 FIXUP_TEAM, FIXUP_SERIAL, SHORT_LIST = 3, 64, 98304       # msm.hip: MSM_FIXUP_TEAM, MSM_FIXUP_SERIAL, MSM_SHORT_LIST
@@ -37,16 +35,7 @@ IDENTITY_WORDS = ref.fq_words(0) + ref.fq_words(1) + ref.fq_words(0)
 
 def _run(mode, blob, tmp_path, timeout=300):
     """the harness on one input file -> its output words"""
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
-    src, dst = tmp_path / (mode + "_in.bin"), tmp_path / (mode + "_out.bin")
-    src.write_bytes(blob)
-    r = subprocess.run([EXE, mode, str(src), str(dst)], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    return np.frombuffer(dst.read_bytes(), dtype="<u4")
-
-
-def _words(ws):
-    return np.asarray(ws, dtype="<u4").tobytes()
+    return uh.as_words(uh.run("msm_units", [mode], blob, tmp_path, timeout))
 
 
 def _scalars(ks):

@@ -1,21 +1,19 @@
 """The batch multipliers (csrc/verify_kernels.hip: a two-level suffix scan over many workgroups, k_mult_tiles / k_mult_scan_tiles /
 k_mult_apply behind multipliers_enqueue) against Python big integers: mult[g][p] = the product of the draws of the LATER proofs of
-p's own group, mod r (kzg/strategy.rs:129, msm.rs:173-176).  build/multipliers_units (tests/cpp/multipliers_units.hip, built by
+p's own group, mod r (kzg/strategy.rs:129, msm.rs:173-176).  build/verify_units multipliers (tests/cpp/verify_units.hip, built by
 csrc/Makefile with the library's flags) runs the library's own kernels on raw draws chosen here: n = 1, 2, 63, 64, 65, 1024 and 8192
 proofs per group in 1, 4 and 32 groups, with a zero draw inside a group (it zeroes the multipliers of the group's earlier proofs and
 of no other group: the proofs h2v_batch_recheck refuses ranges over), and a shard's form (more draws than proofs: the tail of the
 whole batch).  The values are compared exactly, as canonical residues."""
-import os
 import random
 import struct
-import subprocess
 
 import pytest
 
+import units_harness as uh
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "multipliers_units")
 R = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 SIZES = [1, 2, 63, 64, 65, 1024, 8192]
 GROUPS = [1, 4, 32]
@@ -32,16 +30,11 @@ def _expected(draws, n):
 
 def _run(jobs, tmp_path):
     """jobs: [(groups, n_tail, n, draws[groups][n_tail])] -> per job the multipliers [groups][n]"""
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
     blob = [struct.pack("<I", len(jobs))]
     for G, nt, n, draws in jobs:
         blob.append(struct.pack("<III", G, nt, n))
         blob.append(b"".join(d.to_bytes(32, "little") for grp in draws for d in grp))
-    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
-    src.write_bytes(b"".join(blob))
-    r = subprocess.run([EXE, str(src), str(dst)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    raw = dst.read_bytes()
+    raw = uh.run("verify_units", ["multipliers"], b"".join(blob), tmp_path, timeout=600)
     out, at = [], 0
     for G, nt, n, _ in jobs:
         out.append([[int.from_bytes(raw[at + 32 * (g * n + p):at + 32 * (g * n + p) + 32], "little") for p in range(n)] for g in range(G)])
@@ -110,11 +103,7 @@ def test_gather_multipliers(tmp_path):
         assert all(0 <= i < n_src for i in idx)
         jobs.append((src, idx))
     blob = struct.pack("<I", len(jobs)) + b"".join(struct.pack("<II", len(src), len(idx)) + src.tobytes() + np.asarray(idx, dtype="<u4").tobytes() for src, idx in jobs)
-    a, b = tmp_path / "gather_in.bin", tmp_path / "gather_out.bin"
-    a.write_bytes(blob)
-    r = subprocess.run([EXE, "gather", str(a), str(b)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    out = np.frombuffer(b.read_bytes(), dtype="<u4")
+    out = uh.as_words(uh.run("verify_units", ["gather"], blob, tmp_path, timeout=120))
     at = 0
     for src, idx in jobs:
         got = out[at:at + 9 * len(idx)].reshape(len(idx), 9); at += got.size

@@ -11,19 +11,16 @@ Montgomery representatives v 2^261 mod p or that plus p (below 2p, the contract 
   * lines: k_pair_lines' merged iteration products against the products of the sparse line values.
   * verdict: the split checks (k_pairing2 and one stream) and the whole-point check against pyref.pairing_check of the folded points.
 Each mode runs once, in a child process under a time limit."""
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import pairing_reference as pr
+import units_harness as uh
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "pairing_units")
 P = pr.P
 MASK = (1 << 29) - 1
 EDGE = [0, 1, P - 1, (P - 1) // 2, (P + 1) // 2]
@@ -35,9 +32,7 @@ FORM_NAME = ["c0", "c1", "-c1", "9c0-c1", "9c1+c0", "-(9c1+c0)"]
 
 
 def _run(args, timeout):
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
-    r = subprocess.run([EXE] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    uh.run("pairing_units", args, timeout=timeout)
 
 
 def limbs_np(vals):

@@ -1,21 +1,18 @@
 """The multipliers of groups of unequal size (csrc/verify_kernels.hip: the segmented suffix scan k_seg_mult_tiles / k_seg_mult_scan_tiles /
 k_seg_mult_apply behind ragged_multipliers_enqueue) against Python big integers (tests/ragged_reference.py), exactly, as canonical
-residues.  build/ragged_units (tests/cpp/ragged_units.hip, built by csrc/Makefile with the library's flags) runs the library's own enqueue
+residues.  build/verify_units ragged (tests/cpp/verify_units.hip, built by csrc/Makefile with the library's flags) runs the library's own enqueue
 function on raw draws chosen here; it presets the outputs and checks the guard bands around them and around the per-tile scratch."""
-import os
 import random
 import struct
-import subprocess
 
 import pytest
 
 import ragged_reference as rr
+import units_harness as uh
 from ragged_reference import R
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "ragged_units")
 
 # the scan over tile products walks chunks of 1024 tiles (262 144 draws), last chunk first: the second group lies in all three chunks of this list
 CHUNKED = [3, 270000, 1, 262144 + 517, 2]
@@ -24,17 +21,12 @@ SIZE_LISTS = [[1], [1, 1, 1], [255, 1], [256, 256], [257, 1, 254], [1] * 300, [3
 
 def _run(jobs, tmp_path):
     """jobs: [(sizes, draws)] -> per job the multipliers"""
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
     blob = [struct.pack("<I", len(jobs))]
     for sizes, draws in jobs:
         assert len(draws) == sum(sizes)
         blob.append(struct.pack(f"<I{len(sizes)}I", len(sizes), *sizes))
         blob.append(b"".join(d.to_bytes(32, "little") for d in draws))
-    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
-    src.write_bytes(b"".join(blob))
-    r = subprocess.run([EXE, str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    raw = dst.read_bytes()
+    raw = uh.run("verify_units", ["ragged"], b"".join(blob), tmp_path, timeout=120)
     out, at = [], 0
     for sizes, _ in jobs:
         n = sum(sizes)

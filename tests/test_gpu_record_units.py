@@ -13,10 +13,8 @@ guard bands that the harness checks.
   to_jacobian, copy
 Points are compared as group elements (the identity: Z = 0) unless the kernel promises a form; bytes, flags, words and counts exactly.
 One child process per mode (two where a mode's input is another's output), each under a time limit."""
-import os
 import random
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,27 +23,18 @@ import msm_reference as ref
 import pairing_reference as pr
 import record_reference as rr
 from msm_reference import P, R
+from units_harness import words as _words
+import units_harness as uh
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "util_units")
 REPS3 = [(a, b, c) for a in (False, True) for b in (False, True) for c in (False, True)]
 FF = 0xffffffff
 
 
 def _run(mode, blob, tmp_path, timeout=120):
     """the harness on one input file -> its output words"""
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
-    src, dst = tmp_path / (mode + "_in.bin"), tmp_path / (mode + "_out.bin")
-    src.write_bytes(blob)
-    r = subprocess.run([EXE, mode, str(src), str(dst)], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    return np.frombuffer(dst.read_bytes(), dtype="<u4")
-
-
-def _words(ws):
-    return np.asarray(ws, dtype="<u4").tobytes()
+    return uh.as_words(uh.run("util_units", [mode], blob, tmp_path, timeout))
 
 
 _POOL = None

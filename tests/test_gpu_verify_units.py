@@ -6,19 +6,17 @@ of what compile_plan and the oracle's prover happen to produce: squeezes on the 
 stream builder's fast path, the register forwarding and the LDS / global slot boundary of the Fr program, the shadow lanes of
 k_frvm2, the zero-denominator path of the instance evaluation, fold ranges of several batches in one grid, and the ranking of several
 faults in one proof.  Every comparison is exact, on canonical residues and bytes."""
-import os
 import random
 import struct
-import subprocess
 
 import pytest
 
+import units_harness as uh
 import verify_reference as vr
+from units_harness import Cursor
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "halo2_verifier_amd", "csrc", "build", "verify_units")
 P, R = vr.P, vr.R
 FILL32 = b"\x11" * 32
 H2V_ERR_UNSUPPORTED = -19
@@ -30,23 +28,7 @@ def W(*v):
 
 def _run(mode, jobs, tmp_path):
     """jobs: the encoded jobs -> the program's output bytes"""
-    assert os.path.exists(EXE), EXE + " is missing: build() makes it (halo2_verifier_amd/csrc/Makefile)"
-    src, dst = tmp_path / f"{mode}.in", tmp_path / f"{mode}.out"
-    src.write_bytes(W(len(jobs)) + b"".join(jobs))
-    r = subprocess.run([EXE, mode, str(src), str(dst)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-2000:])
-    return dst.read_bytes()
-
-
-class Cursor:
-    def __init__(self, raw): self.raw, self.at = raw, 0
-    def take(self, n):
-        assert self.at + n <= len(self.raw), "output too short"
-        b = self.raw[self.at:self.at + n]; self.at += n; return b
-    def word(self): return struct.unpack("<I", self.take(4))[0]
-    def sword(self): return struct.unpack("<i", self.take(4))[0]
-    def num(self): return int.from_bytes(self.take(32), "little")
-    def done(self): assert self.at == len(self.raw), "output longer than its jobs"
+    return uh.run("verify_units", [mode], W(len(jobs)) + b"".join(jobs), tmp_path, timeout=300)
 
 
 # ------------------------------------------------------------------ decompression and scalar check
