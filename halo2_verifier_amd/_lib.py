@@ -39,6 +39,7 @@ SIGNATURES = {
     "h2v_ctx_proof_shape": (c_int, [c_vp, c_szp, c_szp, c_szp, c_szp, c_szp]),
     "h2v_msm_g1": (c_int, [c_vp, c_u8p, c_u8p, c_sz, c_u8p, c_intp]),
     "h2v_pairing_check": (c_int, [c_vp, c_u8p, c_u8p, c_intp]),
+    "h2v_guards_check_each": (c_int, [c_vp, c_sz, c_szp, c_szp, c_u8p, c_u8p, c_u8p, c_u8p, c_intp]),
     "h2v_verify_batch": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_verify_batch_shapes": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_verify_batch_keys": (c_int, [ctypes.POINTER(c_vp), c_sz, ctypes.POINTER(ctypes.c_uint32), c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_szp, c_szp,
@@ -50,6 +51,7 @@ SIGNATURES = {
     "h2v_accumulator_process": (c_int, [c_vp, ctypes.POINTER(c_vp), c_sz, ctypes.POINTER(ctypes.c_uint32), c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_szp,
                                         c_szp, c_u8p, c_intp, c_intp]),
     "h2v_accumulator_add_msm": (c_int, [c_vp, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_sz]),
+    "h2v_accumulator_process_guards": (c_int, [c_vp, c_sz, c_szp, c_szp, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "h2v_accumulator_read": (c_int, [c_vp, c_u8p, c_u8p, c_szp, c_szp]),
     "h2v_accumulator_finalize": (c_int, [c_vp, c_intp, c_u8p, c_u8p]),
     "h2v_accumulator_journal_begin": (c_int, [c_vp, c_sz]),

@@ -68,6 +68,12 @@ struct h2v_accumulator {
     DevBuf<uint8_t> m_bytes;         // [128 K] merge_states: the states' affine bytes
     DevBuf<G1A> m_affine;            // [2 K] merge_states
     std::vector<uint32_t> m_host;    // what m_words is copied from and to
+    // process_guards: staging buffers and an MSM workspace of its own (grow-only), so that accumulators that share a context do not meet
+    GuardStage g_stage;              // the call's terms
+    MsmWorkspace g_ws;               // the two pooled channels
+    DevBuf<uint8_t> g_rand;          // [32 n] the draws
+    DevBuf<Fr> g_mult, g_tiles;      // [n] the multipliers, and multipliers_enqueue's scratch
+    DevBuf<G1J> g_sums;              // [2] the call's own sum: sum_i mult_i Guard_i, left and right
 };
 
 namespace {
@@ -232,6 +238,62 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     a->n_proofs += n; a->n_failed += failed;
     commit_entry(a, M, n, failed);
     if (all_ok) *all_ok = failed ? 0 : 1;
+    return 0;
+}
+
+// n x (scale by the draw, add the Guard), the Guards supplied by the caller: process with the groups' chains replaced by one conversion of
+// the terms (k_guard_terms: bytes -> MSM inputs, each scalar times its guard's multiplier) and one pooled MSM of two problems.
+//   scale step first (staging record <- M (L, R)), beside the rest; multipliers; terms; MSM -> g_sums; the validity word read behind a
+//   synchronise; then g_sums as record 1, the journal's entry, and the fold that writes the accumulator, as the last step.
+int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n, const size_t* left_counts, const size_t* right_counts, const uint8_t* left_scalars32,
+                                   const uint8_t* left_bases64, const uint8_t* right_scalars32, const uint8_t* right_bases64, const uint8_t* rand32) {
+    const char* who = "h2v_accumulator_process_guards";
+    // every argument check the host can make comes before the first HIP call
+    if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    GuardArgs g{n, {left_counts, right_counts}, {left_scalars32, right_scalars32}, {left_bases64, right_bases64}, {}};
+    int rc;
+    if ((rc = guard_args_check(who, g))) return rc;
+    std::vector<uint8_t> os_rand;
+    if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
+    if (!n) return 0;   // no verify_proof: no scale, no Guard, no entry
+    if (journal_full(a)) { set_last_error(std::string(who) + ": the journal is full"); return H2V_ERR_UNSUPPORTED; }
+    Fr M = Fr::one();
+    for (size_t i = 0; i < n; ++i) { Fr r; Fr::from_bytes(rand32 + 32 * i, r); M = M * r; }
+    uint8_t m_bytes[32];
+    M.to_bytes(m_bytes);
+    memcpy(a->host_scalar, m_bytes, 32);
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    const uint32_t nl = (uint32_t)std::max<size_t>(g.off[0][n], 1), nr = (uint32_t)std::max<size_t>(g.off[1][n], 1);   // (an empty side is staged as one zero term)
+    if ((rc = a->g_rand.reserve(32 * n)) || (rc = a->g_mult.reserve(n)) || (rc = a->g_tiles.reserve(multipliers_scratch((uint32_t)n, 1))) || (rc = a->g_sums.reserve(2)) ||
+        (rc = a->g_ws.reserve(std::max(nl + nr, 1024u), 2, std::max(nl, nr)))) return rc;
+    hipStream_t s = a->stream;
+    Drain drain{s};
+    // the scale step first: it depends on the draws and the previous accumulator only
+    H2V_HIP_CHECK(hipMemcpyAsync(a->scalar.p, a->host_scalar, 32, hipMemcpyHostToDevice, s));
+    if ((rc = accumulator_scale_enqueue(s, a->acc.p, a->scalar.p, a->records.p))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(a->g_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, s));
+    if ((rc = multipliers_enqueue(s, a->g_rand.p, (uint32_t)n, (uint32_t)n, 1, a->g_mult.p, a->g_tiles.p))) return rc;
+    GuardStage& st = a->g_stage;
+    if ((rc = guard_stage_enqueue(s, st, g, 0, n, false, a->g_mult.p))) return rc;
+    MsmProblems pr;
+    for (uint32_t q = 0; q < 2; ++q) pr.p.push_back(MsmProblem(st.scal.p + 8 * (size_t)st.seg[q], st.pts.p + st.seg[q], a->g_sums.p + q, 8, 1, st.seg[q + 1] - st.seg[q]));
+    a->g_ws.tune = a->ctx->tuning;
+    if ((rc = msm_enqueue_multi(s, a->g_ws, pr))) return rc;
+    // the one synchronise in front of the commit: no term of the call is bad, or nothing of the accumulator changes
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    if ((rc = guard_stage_verdict(who, st, 0))) return rc;
+    drain.armed = true;
+    if ((rc = export_records_enqueue(s, a->g_sums.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p + H2V_ACC_RECORD_BYTES))) return rc;
+    // the journal's entry: the call's own sum, into a slot no entry owns yet
+    if (G1J* slot = next_slot(a))
+        if ((rc = fold_records_enqueue(s, a->records.p + H2V_ACC_RECORD_BYTES, 1, 1, 1, 0, slot, nullptr, nullptr, a->words.p + 6))) return rc;
+    // the commit: (L, R) <- staging record + the call's sum
+    if ((rc = fold_records_enqueue(s, a->records.p, 2, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) return rc;
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    a->n_proofs += n;
+    commit_entry(a, M, n, 0);
     return 0;
 }
 

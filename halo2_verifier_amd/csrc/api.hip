@@ -2,6 +2,7 @@
 // The batch-verification entry points live in batch.hip (staged) and oneshot.hip (one-shot).
 #include "../../include/h2v.h"
 #include "ctx.h"
+#include <algorithm>
 #include <mutex>
 #include <string.h>
 #include <stddef.h>
@@ -9,6 +10,59 @@
 namespace h2v {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
+
+int guard_args_check(const char* who, GuardArgs& g) {
+    if (g.n > ((size_t)1 << 20)) { set_last_error(std::string(who) + ": more than 2^20 guards"); return H2V_ERR_BAD_ARGUMENT; }
+    if (g.n && (!g.counts[0] || !g.counts[1])) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    for (int side = 0; side < 2; ++side) {
+        g.off[side].assign(g.n + 1, 0);
+        for (size_t i = 0; i < g.n; ++i) {
+            if (g.counts[side][i] > ((size_t)1 << 24) || g.off[side][i] + g.counts[side][i] > ((size_t)1 << 24)) { set_last_error(std::string(who) + ": more than 2^24 terms on a side"); return H2V_ERR_BAD_ARGUMENT; }
+            g.off[side][i + 1] = g.off[side][i] + g.counts[side][i];
+        }
+        if (g.off[side][g.n] && (!g.scalars[side] || !g.bases[side])) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    return 0;
+}
+
+int guard_stage_enqueue(hipStream_t s, GuardStage& st, const GuardArgs& g, size_t g0, size_t g1, bool per_guard, const Fr* d_mult) {
+    st.h_sb.clear(); st.h_bb.clear(); st.h_side.clear(); st.h_gidx.clear(); st.seg.clear();
+    // the terms of one side of the guards [ga, gb) as one segment
+    auto segment = [&](int side, size_t ga, size_t gb) {
+        st.seg.push_back((uint32_t)st.h_gidx.size());
+        const size_t t0 = g.off[side][ga], t1 = g.off[side][gb];
+        if (t1 > t0) {
+            st.h_sb.insert(st.h_sb.end(), g.scalars[side] + 32 * t0, g.scalars[side] + 32 * t1);
+            st.h_bb.insert(st.h_bb.end(), g.bases[side] + 64 * t0, g.bases[side] + 64 * t1);
+            for (size_t i = ga; i < gb; ++i) st.h_gidx.insert(st.h_gidx.end(), g.counts[side][i], (uint32_t)(i - g0));
+        } else {
+            st.h_sb.insert(st.h_sb.end(), 32, 0); st.h_bb.insert(st.h_bb.end(), 64, 0);
+            st.h_gidx.push_back((uint32_t)(ga - g0));
+        }
+        st.h_side.resize(st.h_gidx.size(), (uint8_t)side);
+    };
+    if (per_guard) for (size_t i = g0; i < g1; ++i) { segment(0, i, i + 1); segment(1, i, i + 1); }
+    else { segment(0, g0, g1); segment(1, g0, g1); }
+    const size_t T = st.h_gidx.size();
+    st.seg.push_back((uint32_t)T);
+    const size_t cap = T < 1024 ? 1024 : T;
+    int rc;
+    if ((rc = st.sb.reserve(32 * cap)) || (rc = st.bb.reserve(64 * cap)) || (rc = st.gidx.reserve(cap)) || (rc = st.scal.reserve(8 * cap)) || (rc = st.pts.reserve(cap)) || (rc = st.word.reserve(1))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(st.sb.p, st.h_sb.data(), 32 * T, hipMemcpyHostToDevice, s));
+    H2V_HIP_CHECK(hipMemcpyAsync(st.bb.p, st.h_bb.data(), 64 * T, hipMemcpyHostToDevice, s));
+    if (d_mult) H2V_HIP_CHECK(hipMemcpyAsync(st.gidx.p, st.h_gidx.data(), 4 * T, hipMemcpyHostToDevice, s));
+    if ((rc = guard_terms_enqueue(s, st.sb.p, st.bb.p, st.gidx.p, d_mult, st.scal.p, st.pts.p, st.word.p, (uint32_t)T))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(&st.h_word, st.word.p, 4, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+int guard_stage_verdict(const char* who, const GuardStage& st, size_t g0) {
+    if (st.h_word == 0xffffffffu) return 0;
+    if (st.h_word >= st.h_gidx.size()) { set_last_error(std::string(who) + ": the validity word names a term the call does not have"); return H2V_ERR_DEVICE; }
+    set_last_error(std::string(who) + ": guard " + std::to_string(g0 + st.h_gidx[st.h_word]) + ", " + (st.h_side[st.h_word] ? "right" : "left") +
+                   " side: a scalar that is not canonical, or a base that is neither all-zero nor a canonical point on the curve");
+    return H2V_ERR_BAD_ARGUMENT;
+}
 }  // namespace h2v
 
 using namespace h2v;
@@ -154,6 +208,52 @@ int h2v_pairing_check(h2v_ctx* ctx, const uint8_t left_xy[64], const uint8_t rig
     H2V_HIP_CHECK(hipStreamSynchronize(s));
     if (flags[0] || flags[1]) { set_last_error("h2v_pairing_check: point not on the curve"); return H2V_ERR_BAD_ARGUMENT; }
     *ok = (int)flags[2];
+    return 0;
+}
+
+int h2v_guards_check_each(h2v_ctx* ctx, size_t n, const size_t* left_counts, const size_t* right_counts, const uint8_t* left_scalars32, const uint8_t* left_bases64,
+                          const uint8_t* right_scalars32, const uint8_t* right_bases64, int* guard_ok) {
+    const char* who = "h2v_guards_check_each";
+    if (!ctx || (n && !guard_ok)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    GuardArgs g{n, {left_counts, right_counts}, {left_scalars32, right_scalars32}, {left_bases64, right_bases64}, {}};
+    int rc;
+    if ((rc = guard_args_check(who, g))) return rc;
+    if (!n) return 0;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    struct Drain { hipStream_t s; ~Drain() { hipStreamSynchronize(s); } } drain{s};   // no return path leaves work behind on the context's stream
+    std::vector<int> verdicts(n);
+    std::vector<uint32_t> h_ok, terms;
+    for (size_t g0 = 0; g0 < n;) {
+        // the launch: guards [g0, g1), at most 512 (two problems each), fewer where the MSM would cut their problems into more than it takes
+        size_t g1 = g0;
+        uint32_t total = 0, per = 1;
+        terms.clear();
+        while (g1 < n && g1 - g0 < MSM_MAX_PROBLEMS / 2) {
+            const uint32_t l = (uint32_t)std::max<size_t>(g.counts[0][g1], 1), r = (uint32_t)std::max<size_t>(g.counts[1][g1], 1);
+            terms.push_back(l); terms.push_back(r);
+            if (g1 > g0 && (!msm_cuts_within_limit(terms.data(), terms.size()) || (uint64_t)total + l + r > (1u << 26))) { terms.resize(terms.size() - 2); break; }
+            total += l + r; per = std::max(per, std::max(l, r));
+            ++g1;
+        }
+        const uint32_t K = (uint32_t)(g1 - g0);
+        if ((rc = ctx->guard_ws.reserve(std::max(total, 1024u), 2 * K, per)) || (rc = ctx->guard_pairs.reserve(MSM_MAX_PROBLEMS)) || (rc = ctx->guard_ok.reserve(MSM_MAX_PROBLEMS / 2))) return rc;
+        GuardStage& st = ctx->guards;
+        if ((rc = guard_stage_enqueue(s, st, g, g0, g1, true, nullptr))) return rc;
+        MsmProblems pr;
+        for (uint32_t q = 0; q < 2 * K; ++q) pr.p.push_back(MsmProblem(st.scal.p + 8 * (size_t)st.seg[q], st.pts.p + st.seg[q], ctx->guard_pairs.p + q, 8, 1, st.seg[q + 1] - st.seg[q]));
+        ctx->guard_ws.tune = ctx->tuning;
+        if ((rc = msm_enqueue_multi(s, ctx->guard_ws, pr))) return rc;
+        if ((rc = pairing_check_enqueue(s, ctx->pairing, ctx->guard_pairs.p, K, ctx->guard_ok.p))) return rc;
+        h_ok.assign(K, 0);
+        H2V_HIP_CHECK(hipMemcpyAsync(h_ok.data(), ctx->guard_ok.p, 4 * (size_t)K, hipMemcpyDeviceToHost, s));
+        H2V_HIP_CHECK(hipStreamSynchronize(s));
+        if ((rc = guard_stage_verdict(who, st, g0))) return rc;
+        for (uint32_t i = 0; i < K; ++i) verdicts[g0 + i] = h_ok[i] ? 1 : 0;
+        g0 = g1;
+    }
+    for (size_t i = 0; i < n; ++i) guard_ok[i] = verdicts[i];   // nothing is written on an error
     return 0;
 }
 

@@ -12,14 +12,42 @@ namespace h2v {
 struct OneShotMsm {
     DevBuf<uint8_t> sb, bb, out; DevBuf<uint32_t> s, flags; DevBuf<G1A> b; DevBuf<G1J> res;
 };
+// Guards at the trait seam (h2v_accumulator_process_guards, h2v_guards_check_each; api.hip): guard i is counts[side][i] terms of each
+// side, the terms of all guards of a call back to back in four flat arrays.
+struct GuardArgs {
+    size_t n;
+    const size_t* counts[2];                      // [side][guard]
+    const uint8_t* scalars[2]; const uint8_t* bases[2];   // [side]: 32 / 64 bytes per term
+    std::vector<size_t> off[2];                   // guard_args_check: [side][guard] first term, n + 1 entries
+};
+// The terms of one launch on their way to the MSM: staged on the host as segments (one per MSM problem; a segment without a term holds
+// one zero scalar under the identity, so that no problem of a launch is empty), copied, and converted by one k_guard_terms launch.
+// Grow-only buffers, owned by whoever runs the launches (an accumulator, or the context under its lock).
+struct GuardStage {
+    DevBuf<uint8_t> sb, bb; DevBuf<uint32_t> gidx, scal, word; DevBuf<G1A> pts;
+    std::vector<uint8_t> h_sb, h_bb, h_side;      // what sb / bb are copied from; per staged term its side
+    std::vector<uint32_t> h_gidx, seg;            // per staged term its guard, counted from the launch's first; seg[q] = first staged term of segment q (+ the total)
+    uint32_t h_word = 0xffffffffu;                // what `word` (k_guard_terms' validity word) is copied to
+};
+// null arrays that the counts say are read, n > 2^20, a side's total above 2^24 (H2V_ERR_BAD_ARGUMENT); fills g.off
+int guard_args_check(const char* who, GuardArgs& g);
+// Guards [g0, g1): the segments (per_guard: guard by guard its left and its right side; else every left term, then every right term), the
+// copies, the conversion (d_mult: per guard of the launch, or null) and the copy of the validity word, all on s.  MSM problem q reads
+// st.scal.p + 8 st.seg[q] and st.pts.p + st.seg[q], st.seg[q + 1] - st.seg[q] terms.
+int guard_stage_enqueue(hipStream_t s, GuardStage& st, const GuardArgs& g, size_t g0, size_t g1, bool per_guard, const Fr* d_mult);
+// after the synchronise: 0, or H2V_ERR_BAD_ARGUMENT with the guard and the side of the first bad term in the message
+int guard_stage_verdict(const char* who, const GuardStage& st, size_t g0);
 }  // namespace h2v
 
 struct h2v_ctx {
     int device = 0;
     h2v::ParamsHost params;
     h2v::PairingDevice pairing;
-    h2v::MsmWorkspace msm_ws;      // used by h2v_msm_g1 only; batches own their workspaces
+    h2v::MsmWorkspace msm_ws;      // used by h2v_msm_g1 only; batches and accumulators own their workspaces
     h2v::OneShotMsm one_shot;
+    h2v::GuardStage guards;        // h2v_guards_check_each: the launch in flight, its workspace (sized for many small problems, where msm_ws
+    h2v::MsmWorkspace guard_ws;    // is sized for one large one), its evaluated pairs and its verdicts
+    h2v::DevBuf<h2v::G1J> guard_pairs; h2v::DevBuf<uint32_t> guard_ok;
     hipStream_t stream = nullptr;  // used by the synchronous single-shot entry points
     std::mutex mu;                 // serialises the single-shot entry points
     h2v::VkDevice* vk = nullptr;   // per-VK compiled program and constants (vkplan.hip)

@@ -196,6 +196,13 @@ int accumulator_scale_many_enqueue(hipStream_t s, const G1J* d_pairs, const uint
 int bases_from_bytes_enqueue(hipStream_t s, const uint8_t* d_bytes, G1A* d_out, uint32_t* d_flags, uint32_t n);
 // canonical 32-B scalars -> 8 x 32-bit words (validated < r); flags[i] = 1 when >= r
 int scalars_from_bytes_enqueue(hipStream_t s, const uint8_t* d_bytes, uint32_t* d_out, uint32_t* d_flags, uint32_t n);
+// Both conversions for the n terms of a call's Guards in one launch (k_guard_terms), one validity word instead of a flag per term:
+// *d_first_bad = the lowest index of a term whose scalar is >= r or whose base is neither all-zero nor a canonical point on the curve
+// (0xffffffff: none; the launcher presets it; such a term is written as a zero scalar and the identity).  With d_mult, scalar i is
+// multiplied by d_mult[d_guard_of_term[i]] (multipliers as multipliers_enqueue leaves them); d_mult null: unscaled, d_guard_of_term
+// is not read.  The byte arrays and d_out_scalars lie on 16-byte boundaries.
+int guard_terms_enqueue(hipStream_t s, const uint8_t* d_scalars32, const uint8_t* d_bases64, const uint32_t* d_guard_of_term, const Fr* d_mult, uint32_t* d_out_scalars,
+                        G1A* d_out_bases, uint32_t* d_first_bad, uint32_t n);
 // Jacobian -> canonical x|y bytes (+ identity flag word after the 64 bytes: out is 68 B aligned to 4)
 int copy_words_enqueue(hipStream_t s, const void* d_src, void* d_dst, size_t n_words, size_t lds_reserve = 0);   // by a kernel (the destination may be mapped host memory)
 int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, uint32_t* d_is_identity, uint32_t n, size_t lds_reserve = 0);

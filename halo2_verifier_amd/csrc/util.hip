@@ -30,6 +30,57 @@ __global__ void __launch_bounds__(256) k_scalars_from_bytes(const uint8_t* __res
     flags[i] = bad;
 }
 
+// The terms of a call's Guards (h2v_accumulator_process_guards, h2v_guards_check_each: the term lists a CPU verify_proof hands over), one
+// thread per term, both conversions above in one launch and the draw's multiplier on the way:
+//   scalar: 32 canonical bytes, refused when >= r; with `mult`, s * mult[guard_of_term[i]] — ONE Montgomery product: the bytes' integer
+//           times the multiplier as multipliers_enqueue leaves it (m R) is s m — as the 8 canonical words the MSM reads (sstride 8);
+//   base:   64 bytes x | y, all-zero = the identity, else canonical and on the curve, as a G1A.
+// A bad term writes a zero scalar and the identity, and its index joins *first_bad by atomicMin (the launcher presets the word to
+// 0xffffffff): one word per launch, the lowest offending term.  The byte arrays are read as 16-byte words (every term lies at a
+// multiple of 32 / 64 bytes of a hipMalloc allocation; the launcher checks the pointers): 2 + 4 loads per lane, not 96 byte loads.
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 74 VGPRs, 52 SGPRs, no spills, 80 bytes of scratch per lane (the call frames of the
+// field product and the square, real function calls throughout the library: bn254.hip.h), no LDS; 6 waves per SIMD.
+__global__ void __launch_bounds__(256) k_guard_terms(const uint4* __restrict__ scalars, const uint4* __restrict__ bases, const uint32_t* __restrict__ guard_of_term,
+                                                     const Fr* __restrict__ mult, uint4* __restrict__ out_scalars, G1A* __restrict__ out_bases,
+                                                     uint32_t* __restrict__ first_bad, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 s0 = scalars[2 * (size_t)i], s1 = scalars[2 * (size_t)i + 1];
+    uint32_t raw[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    bool bad = Fr::geq_p(raw);
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const uint4 v = bases[4 * (size_t)i + j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
+    uint32_t any = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) any |= w[j];
+    G1A p = G1A::identity();
+    if (any) {
+        if (Fq::geq_p(w) || Fq::geq_p(w + 8)) bad = true;
+        else {
+            p.x = Fq::from_raw(w); p.y = Fq::from_raw(w + 8);
+            if (!p.on_curve()) bad = true;
+        }
+    }
+    if (!bad && mult) {
+        Fr t;
+        Fr::pack29(t.v, raw);
+        const Fr prod = Fr::mul(t, mult[guard_of_term[i]]);
+        uint32_t c[9];
+        prod.canonical(c);
+        Fr::unpack29(raw, c);
+    }
+    if (bad) {
+        p = G1A::identity();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) raw[j] = 0;
+        atomicMin(first_bad, i);
+    }
+    out_scalars[2 * (size_t)i] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+    out_scalars[2 * (size_t)i + 1] = make_uint4(raw[4], raw[5], raw[6], raw[7]);
+    out_bases[i] = p;
+}
+
 __global__ void k_point_to_bytes(const G1J* __restrict__ in, uint8_t* __restrict__ out, uint32_t* __restrict__ is_identity, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -191,6 +242,19 @@ int bases_from_bytes_enqueue(hipStream_t s, const uint8_t* d_bytes, G1A* d_out, 
 int scalars_from_bytes_enqueue(hipStream_t s, const uint8_t* d_bytes, uint32_t* d_out, uint32_t* d_flags, uint32_t n) {
     if (!n) return 0;
     hipLaunchKernelGGL(k_scalars_from_bytes, dim3((n + 255) / 256), dim3(256), 0, s, d_bytes, d_out, d_flags, n);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int guard_terms_enqueue(hipStream_t s, const uint8_t* d_scalars32, const uint8_t* d_bases64, const uint32_t* d_guard_of_term, const Fr* d_mult, uint32_t* d_out_scalars,
+                        G1A* d_out_bases, uint32_t* d_first_bad, uint32_t n) {
+    if (!d_first_bad || (n && (!d_scalars32 || !d_bases64 || !d_out_scalars || !d_out_bases)) || (n && d_mult && !d_guard_of_term)) {
+        set_last_error("guard_terms_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT;
+    }
+    if (((uintptr_t)d_scalars32 | (uintptr_t)d_bases64 | (uintptr_t)d_out_scalars) & 15u) { set_last_error("guard_terms_enqueue: an array off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
+    H2V_HIP_CHECK(hipMemsetAsync(d_first_bad, 0xff, 4, s));
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_guard_terms, dim3((n + 255) / 256), dim3(256), 0, s, (const uint4*)d_scalars32, (const uint4*)d_bases64, d_guard_of_term, d_mult, (uint4*)d_out_scalars, d_out_bases,
+                       d_first_bad, n);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

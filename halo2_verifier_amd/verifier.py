@@ -191,6 +191,30 @@ def _seed_sides(seed):
     return sides[0] + sides[1]
 
 
+def _guard_sides(guard):
+    """A Guard — ((left_scalars, left_bases), (right_scalars, right_bases)), or the dict Context.guard_msm returns — as (left, right)"""
+    if isinstance(guard, dict):
+        return (guard["left_scalars"], guard["left_bases"]), (guard["right_scalars"], guard["right_bases"])
+    sides = tuple(guard)
+    if len(sides) != 2:
+        raise ValueError("a guard is (left, right)")
+    return sides
+
+
+def _guards_args(guards):
+    """Guards as the arguments h2v_accumulator_process_guards / h2v_guards_check_each take in a row: (n, left_counts, right_counts,
+    left_scalars32, left_bases64, right_scalars32, right_bases64), the terms of all guards back to back in guard order; everything the
+    C side indexes is checked here (_channel)."""
+    counts, sc, bs = ([], []), ([], []), ([], [])
+    n = 0
+    for i, guard in enumerate(guards):
+        n += 1
+        for side, ch in enumerate(_guard_sides(guard)):
+            s, b, k = _channel(ch, f"guard {i}: ")
+            counts[side].append(k); sc[side].append(s); bs[side].append(b)
+    return (n, _sizes(counts[0]), _sizes(counts[1]), b"".join(sc[0]), b"".join(bs[0]), b"".join(sc[1]), b"".join(bs[1]))
+
+
 def _points(buf, k):
     """k 64-byte points (x | y) out of a result buffer"""
     raw = buf.raw
@@ -373,6 +397,16 @@ class Context:
             raise ValueError("points are 64 bytes (x | y)")
         check(self._lib.h2v_pairing_check(self._h, left_xy, right_xy, ctypes.byref(ok)))
         return bool(ok.value)
+
+    # -- n x DualMSM::check: SingleStrategy at the trait seam (poly/kzg/strategy.rs:164-176)
+    def guards_check_each(self, guards):
+        """One pairing verdict per Guard (h2v_guards_check_each), the Guards as a CPU verify_proof hands them over: each
+        ((left_scalars, left_bases), (right_scalars, right_bases)) or the dict guard_msm returns.  -> [bool]: e(L_i, s_g2) e(R_i, -g2) == 1
+        over guard i's own evaluated channels.  A malformed term raises H2VError naming the guard and the side."""
+        args = _guards_args(guards)
+        ok = (ctypes.c_int * max(args[0], 1))()
+        check(self._lib.h2v_guards_check_each(self._h, *args, ok))
+        return [bool(v) for v in ok][:args[0]]
 
     def proof_shape(self):
         vals = [ctypes.c_size_t(0) for _ in range(5)]
@@ -679,6 +713,18 @@ class Accumulator:
             self._inputs.append((contexts, keys, list(proofs), list(instances)) if self._keep_inputs else None)
         return r.statuses
 
+    def process_guards(self, guards, rand=None):
+        """n x (scale by the draw, add the Guard) on this accumulator (h2v_accumulator_process_guards): the trait seam, where a CPU
+        verify_proof made the Guards.  guards: each ((left_scalars, left_bases), (right_scalars, right_bases)) — scalars ints / 32-byte
+        strings, bases 64-byte x | y — or the dict Context.guard_msm returns; rand: one scalar per guard, or None.  Equals process() over
+        the proofs the Guards came from, with the same draws.  A call that raises H2VError leaves the accumulator as it was."""
+        guards = list(guards)
+        args = _guards_args(guards)
+        rb = _rand_bytes(rand, args[0])
+        check(self._lib.h2v_accumulator_process_guards(self._h, *args, rb))
+        if args[0] and self._inputs:   # (journal on: the call has appended an entry)
+            self._inputs.append(("guards", guards) if self._keep_inputs else None)
+
     def add_msm(self, left, right):
         """(L, R) += the two term lists evaluated, unscaled (h2v_accumulator_add_msm: AccumulatorStrategy::with on an empty accumulator,
         DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""
@@ -812,7 +858,8 @@ class Accumulator:
     def identify(self):
         """Name the failing proofs of the failing legs: check_legs(), then verify_batch_keys_identify with fresh OS draws over the
         retained inputs of every non-base entry whose pairing fails.  -> {entry: statuses}, statuses[i] what verify_each returns for
-        proof i of that leg.  Needs keep_inputs=True; an add_msm entry that fails is reported with statuses None."""
+        proof i of that leg; for a process_guards leg, guards_check_each over its Guards: 0 or ConstraintSystemFailure per Guard.  Needs
+        keep_inputs=True; an add_msm entry that fails is reported with statuses None."""
         if not self._keep_inputs:
             raise ValueError("identify() needs the legs' inputs: create the Accumulator with keep_inputs=True")
         out = {}
@@ -822,6 +869,9 @@ class Accumulator:
             kept = self._inputs[e]
             if kept is None:
                 out[e] = None
+                continue
+            if kept[0] == "guards":   # a process_guards leg: the verdict of every Guard of its own
+                out[e] = [0 if ok_i else PlonkError.ConstraintSystemFailure.value for ok_i in self.ctx.guards_check_each(kept[1])]
                 continue
             contexts, keys, proofs, instances = kept
             out[e] = verify_batch_keys_identify(contexts, keys if keys is not None else [0] * len(proofs), proofs, instances)[1]

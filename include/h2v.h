@@ -18,7 +18,7 @@
  *   - serde format codes follow helpers.rs:7-19: 0 Processed, 1 RawBytes, 2 RawBytesUnchecked.
  *   - Threading: a context may be shared between host threads: its VK / params / compiled plans are
  *     immutable after creation, and the one-shot entry points (h2v_verify_batch, h2v_verify_each,
- *     h2v_guard_msm, h2v_msm_g1, h2v_pairing_check, h2v_fold_check) serialise themselves on an internal
+ *     h2v_guard_msm, h2v_msm_g1, h2v_pairing_check, h2v_guards_check_each, h2v_fold_check) serialise themselves on an internal
  *     lock (they share the context's stream and a cached workspace).  A batch object owns one HIP stream
  *     and its device workspace and must be used from one thread at a time; several batches may be in
  *     flight on one context.
@@ -146,6 +146,15 @@ int h2v_msm_g1(h2v_ctx* ctx, const uint8_t* scalars32, const uint8_t* bases64, s
 /* e(left, s_g2) * e(right, -g2) == 1 ?
  *   replaces: DualMSM::check after both channels are evaluated (poly/kzg/msm.rs:185-203). */
 int h2v_pairing_check(h2v_ctx* ctx, const uint8_t left_xy[64], const uint8_t right_xy[64], int* ok);
+/* n x DualMSM::check, one verdict per Guard: SingleStrategy::process at the trait seam (kzg/strategy.rs:164-176, msm.rs:185-203).
+ * The Guards in the formats of h2v_accumulator_process_guards, under its refusals (nothing is written on an error).  guard_ok[i] is the
+ * raw bit of e(L_i, s_g2) e(R_i, -g2) == 1 over Guard i's own evaluated channels.  Runs in launches of at most 512 Guards — one pooled
+ * MSM over their 2 K problems, one pairing launch over the K pairs, one copy of K verdict words — and serialises on the context's lock. */
+int h2v_guards_check_each(h2v_ctx* ctx, size_t n,
+                          const size_t* left_counts, const size_t* right_counts,
+                          const uint8_t* left_scalars32, const uint8_t* left_bases64,
+                          const uint8_t* right_scalars32, const uint8_t* right_bases64,
+                          int* guard_ok);
 
 /* N x verify_proof under AccumulatorStrategy, then finalize():
  *   replaces: the loop  s = verify_proof(&params, &vk, s, instances_i, &mut Blake2bRead::init(proof_i))?
@@ -258,6 +267,26 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
 int h2v_accumulator_add_msm(h2v_accumulator* a,
                             const uint8_t* left_scalars32, const uint8_t* left_bases64, size_t n_left,
                             const uint8_t* right_scalars32, const uint8_t* right_bases64, size_t n_right);
+/* n x (scale the accumulator by the draw, add the Guard): AccumulatorStrategy::process at the trait seam, where the reference's own
+ * verify_proof runs on the CPU and hands over the Guard it made.
+ *   replaces: msm_accumulator.scale(Fr::random) then f(acc) adding the Guard's terms (kzg/strategy.rs:125-136, msm.rs:173-183)
+ * Guard i is two term lists: side s has counts_s[i] terms (either may be 0), scalars 32-byte canonical, bases 64-byte x | y with
+ * all-zero = the identity (the seed formats of h2v_verify_batch_seeded); the terms of all guards lie back to back, in guard order, in
+ * the four flat arrays.  With draws r_0 .. r_{n-1} (rand32; NULL = OS draws; zero draws allowed):
+ *     (L, R) <- M (L, R) + sum_i (prod_{j > i} r_j) (sum_t ls_it lb_it, sum_t rs_it rb_it),     M = r_0 r_1 .. r_{n-1}
+ * — h2v_accumulator_process with the Guard supplied instead of computed: feeding each proof's Guard equals, bit for bit, process over
+ * the same proofs and draws when every status is 0, and equals n x (scale by r_i; add_msm(guard_i)).  n == 0 changes nothing.
+ * Counters: n_proofs += n, n_failed unchanged (a Guard exists only where verify_proof succeeded).  Journal: one entry, as process leaves.
+ * H2V_ERR_BAD_ARGUMENT, with points, counters and journal exactly as they were: a null array that the counts say is read, n > 2^20,
+ * a side's total above 2^24, a draw or scalar that is not canonical, a base that is neither all-zero nor a canonical point on the curve
+ * (h2v_last_error names the guard and the side of the first bad term).  A full journal: H2V_ERR_UNSUPPORTED before any device work.
+ * No accumulator point and no MSM result passes through host memory; the accumulator is written by the call's last step, after the
+ * terms are known to be valid.  The context may have been created without a VK.  The call uses buffers of the accumulator only. */
+int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n,
+                                   const size_t* left_counts, const size_t* right_counts,
+                                   const uint8_t* left_scalars32, const uint8_t* left_bases64,
+                                   const uint8_t* right_scalars32, const uint8_t* right_bases64,
+                                   const uint8_t* rand32);
 /* The two points as affine bytes (all-zero = identity) and the counters; any pointer but `a` may be NULL. */
 int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_proofs, size_t* n_failed);
 /* ok = the pairing check of (L, R) passes AND no processed proof failed — what batch_ok means for h2v_verify_batch.

@@ -17,6 +17,8 @@
 //   SingleStrategy                        kzg/strategy.rs:143-181 SingleStrategy(params): verify_proof() runs at once
 //   AccumulatorStrategy used incrementally (process per proof,    Accumulator(context): process() runs a run of proofs at once into
 //     finalize when the caller decides, with)  kzg/strategy.rs:69-140   two points resident on the GPU; add_msm(), read(), finalize()
+//   the same two strategies handed the Guards of a verify_proof   Accumulator::process_guards(guards, rand32), check_guards(context, guards):
+//     that ran on the CPU       kzg/strategy.rs:125-136, 164-176     a Guard is the two term lists of its DualMSM
 //   VerifierSHPLONK / VerifierGWC, Blake2bRead / Keccak256Read    MultiOpen, TranscriptKind (generic parameters of lib.rs:33-40)
 //
 // There is no CPU fallback: constructing a Context without a HIP device throws Failure{H2V_ERR_DEVICE}.
@@ -79,6 +81,10 @@ private:
     h2v_ctx* h_ = nullptr;
 };
 
+// The Guard a CPU verify_proof returns (kzg/strategy.rs:164-176: its DualMSM), as two term lists: scalars 32 bytes each, bases 64 bytes
+// (x | y, all-zero = the identity) each; either side may be empty
+struct Guard { Bytes left_scalars, left_bases, right_scalars, right_bases; };
+
 namespace detail {
 // The arguments of a call in the layout the C ABI takes: a context per key, then every proof in call order with its key and its column
 // lengths.  The entry points over one context and one instance shape take key 0's column count and proof 0's shape (shape0()).
@@ -116,6 +122,21 @@ struct Marshalled {
 
 private:
     bool one_key_;
+};
+// Guards in the layout h2v_accumulator_process_guards / h2v_guards_check_each take: a count per guard and side, the terms of all guards
+// back to back in guard order; every length the C side indexes is checked here
+struct FlatGuards {
+    std::vector<size_t> left_counts, right_counts;
+    Bytes ls, lb, rs, rb;
+    explicit FlatGuards(const std::vector<Guard>& guards) {
+        for (const Guard& g : guards) {
+            if (g.left_scalars.size() % 32 || g.left_bases.size() != 2 * g.left_scalars.size() || g.right_scalars.size() % 32 || g.right_bases.size() != 2 * g.right_scalars.size())
+                throw Failure(H2V_ERR_BAD_ARGUMENT, "a guard's channel is n 32-byte scalars and n 64-byte bases");
+            left_counts.push_back(g.left_scalars.size() / 32); right_counts.push_back(g.right_scalars.size() / 32);
+            ls.insert(ls.end(), g.left_scalars.begin(), g.left_scalars.end()); lb.insert(lb.end(), g.left_bases.begin(), g.left_bases.end());
+            rs.insert(rs.end(), g.right_scalars.begin(), g.right_scalars.end()); rb.insert(rb.end(), g.right_bases.begin(), g.right_bases.end());
+        }
+    }
 };
 inline void check_channels(const Bytes& ls, const Bytes& lb, const Bytes& rs, const Bytes& rb, const char* what) {
     if (ls.size() % 32 || lb.size() != 2 * ls.size() || rs.size() % 32 || rb.size() != 2 * rs.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, what);
@@ -273,6 +294,14 @@ public:
         check(h2v_accumulator_add_msm(h_, left_scalars.data(), left_bases.data(), left_scalars.size() / 32, right_scalars.data(), right_bases.data(),
                                       right_scalars.size() / 32));
     }
+    // n x (scale by the draw, add the Guard): AccumulatorStrategy::process at the trait seam (kzg/strategy.rs:125-136), the Guards made by a CPU
+    // verify_proof.  rand32: one 32-byte canonical draw per guard; empty = OS RNG.  Equals process() over the proofs the Guards came from.
+    void process_guards(const std::vector<Guard>& guards, const Bytes& rand32 = Bytes()) {
+        if (!rand32.empty() && rand32.size() != 32 * guards.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "one 32-byte draw per guard");
+        const detail::FlatGuards f(guards);
+        check(h2v_accumulator_process_guards(h_, guards.size(), f.left_counts.data(), f.right_counts.data(), f.ls.data(), f.lb.data(), f.rs.data(), f.rb.data(),
+                                             rand32.empty() ? nullptr : rand32.data()));
+    }
     // the two points as canonical x | y (left(), right(); all-zero = identity) and the counters
     void read() { check(h2v_accumulator_read(h_, left_, right_, &n_proofs_, &n_failed_)); }
     // -> true iff the pairing of (L, R) passes and no processed proof failed; left() / right() hold the points.  The accumulator is not consumed.
@@ -355,6 +384,16 @@ private:
     size_t n_proofs_ = 0, n_failed_ = 0;
     uint8_t left_[64] = {0}, right_[64] = {0};
 };
+
+// n x DualMSM::check, one verdict per Guard: SingleStrategy::process at the trait seam (kzg/strategy.rs:164-176), h2v_guards_check_each
+inline std::vector<bool> check_guards(const Context& ctx, const std::vector<Guard>& guards) {
+    const detail::FlatGuards f(guards);
+    std::vector<int> ok(guards.size() ? guards.size() : 1, 0);
+    check(h2v_guards_check_each(ctx.handle(), guards.size(), f.left_counts.data(), f.right_counts.data(), f.ls.data(), f.lb.data(), f.rs.data(), f.rb.data(), ok.data()));
+    std::vector<bool> out;
+    for (size_t i = 0; i < guards.size(); ++i) out.push_back(ok[i] != 0);
+    return out;
+}
 
 // The pairing checks of ranges (first, count) of a batch's last finished launch on its resident scalars (h2v_batch_recheck): one verdict
 // per range; lefts / rights (optional) receive the evaluated channels, 64 bytes per range.

@@ -71,6 +71,9 @@ extern "C" {
                                n_right_terms: *mut usize, n_instance_columns: *mut usize) -> c_int;
     pub fn h2v_msm_g1(ctx: *mut h2v_ctx, scalars32: *const u8, bases64: *const u8, n: usize, out_xy: *mut u8, out_is_identity: *mut c_int) -> c_int;
     pub fn h2v_pairing_check(ctx: *mut h2v_ctx, left_xy: *const u8, right_xy: *const u8, ok: *mut c_int) -> c_int;
+    pub fn h2v_guards_check_each(ctx: *mut h2v_ctx, n: usize, left_counts: *const usize, right_counts: *const usize,
+                                 left_scalars32: *const u8, left_bases64: *const u8, right_scalars32: *const u8, right_bases64: *const u8,
+                                 guard_ok: *mut c_int) -> c_int;
     pub fn h2v_verify_batch(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                             instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, rand32: *const u8,
                             per_proof_status: *mut c_int, batch_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
@@ -93,6 +96,9 @@ extern "C" {
                                    per_proof_status: *mut c_int, all_ok: *mut c_int) -> c_int;
     pub fn h2v_accumulator_add_msm(a: *mut h2v_accumulator, left_scalars32: *const u8, left_bases64: *const u8, n_left: usize,
                                    right_scalars32: *const u8, right_bases64: *const u8, n_right: usize) -> c_int;
+    pub fn h2v_accumulator_process_guards(a: *mut h2v_accumulator, n: usize, left_counts: *const usize, right_counts: *const usize,
+                                          left_scalars32: *const u8, left_bases64: *const u8, right_scalars32: *const u8, right_bases64: *const u8,
+                                          rand32: *const u8) -> c_int;
     pub fn h2v_accumulator_read(a: *mut h2v_accumulator, out_left_xy: *mut u8, out_right_xy: *mut u8, n_proofs: *mut usize, n_failed: *mut usize) -> c_int;
     pub fn h2v_accumulator_finalize(a: *mut h2v_accumulator, ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_accumulator_journal_begin(a: *mut h2v_accumulator, capacity: usize) -> c_int;

@@ -10,12 +10,13 @@
 //!                               `push(key, proof, instances)`, one pairing at `finalize` (h2v_verify_batch_keys).
 //! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
 //!                               sharing the params; `finalize` whenever the caller decides (h2v_accumulator_*).
+//!                               `process_guards` takes the Guards of proofs that a CPU `verify_proof` went through.
 //!                               `merge` / `export_state` / `merge_states` fold several of them into one pairing.
 //!                               Its leg journal (`journal_begin`, `check_legs`, `drop_legs`) finds the legs whose own pairing
 //!                               fails and takes them out again.
-//! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) whose `finalize`
-//!                               evaluates the two `MSMKZG` channels and the pairing on the GPU
-//!                               (poly/kzg/msm.rs:81-86, 185-203) while `verify_proof` itself stays on the CPU.
+//! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) over a resident accumulator:
+//!                               `verify_proof` itself stays on the CPU, every Guard it returns is scaled in and added on the GPU
+//!                               (h2v_accumulator_process_guards), `finalize` is the one pairing there.
 use super::ffi::*;
 use crate::{
     helpers::SerdeFormat,
@@ -298,6 +299,22 @@ impl GpuResidentAccumulator {
         Ok(())
     }
 
+    /// The trait seam in runs: one Guard per `verify_proof` that ran on the CPU, as the terms `(left, right)` of its `DualMSM`, in
+    /// order; every Guard is joined under a fresh OS draw — n x (`DualMSM::scale`, then the Guard's terms; kzg/strategy.rs:125-136,
+    /// msm.rs:173-183) in one call (h2v_accumulator_process_guards).  An `Err` leaves the accumulator as it was.
+    pub fn process_guards(&mut self, guards: &[(&[(Fr, G1Affine)], &[(Fr, G1Affine)])]) -> Result<(), Error> {
+        let (mut lc, mut rc_, mut ls, mut lb, mut rs, mut rb) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        for (left, right) in guards {
+            let ((s0, b0), (s1, b1)) = (flat_terms(left), flat_terms(right));
+            lc.push(left.len()); rc_.push(right.len());
+            ls.extend(s0); lb.extend(b0); rs.extend(s1); rb.extend(b1);
+        }
+        let rc = unsafe { h2v_accumulator_process_guards(self.acc, guards.len(), lc.as_ptr(), rc_.as_ptr(), ls.as_ptr(), lb.as_ptr(), rs.as_ptr(), rb.as_ptr(),
+                                                         core::ptr::null()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
+    }
+
     /// One `verify_proof(&params, vks[key], strategy, &[instances], &mut Blake2bRead::init(proof))` call per item, in order:
     /// `(key, proof, instances)`.  Returns the verdict of every proof of this call (`Ok(())` or the `Error` of its `verify_proof`).
     /// An `Err` of the call itself leaves the accumulator as it was.
@@ -401,39 +418,51 @@ impl Drop for GpuResidentAccumulator {
     }
 }
 
-/// Trait seam: same `process` as AccumulatorStrategy (kzg/strategy.rs:125-136); `finalize` on the GPU.
-pub struct GpuAccumulatorStrategy<'params> { acc: DualMSM<'params, Bn256>, ctx: *mut h2v_ctx }
+/// The terms of one `MSMKZG` channel as it holds them (scalars, projective bases; poly/kzg/msm.rs:17-24) in the C ABI's layout.
+fn flat_channel(scalars: &[Fr], bases: &[<G1Affine as CurveAffine>::CurveExt]) -> (Vec<u8>, Vec<u8>) {
+    let terms: Vec<(Fr, G1Affine)> = scalars.iter().zip(bases.iter()).map(|(s, b)| (*s, b.to_affine())).collect();
+    flat_terms(&terms)
+}
+
+/// Trait seam: the reference's own `verify_proof` stays the driver on the CPU, and the strategy it is handed is a resident accumulator
+/// on the GPU.  `process` is `AccumulatorStrategy::process` (kzg/strategy.rs:125-136) with the scale and the addition on the device:
+/// `f` gets an empty `DualMSM::new(params)` and returns its Guard, whose terms go, with a fresh draw, to
+/// h2v_accumulator_process_guards — scale (L, R) by the draw, add the Guard's two evaluated channels.  Nothing of the accumulation is
+/// kept on the host, and no earlier scalar is touched again.  `finalize` is the one pairing (h2v_accumulator_finalize).
+pub struct GpuAccumulatorStrategy<'params> { params: &'params ParamsKZG<Bn256>, ctx: *mut h2v_ctx, acc: *mut h2v_accumulator }
 
 impl<'params> VerificationStrategy<'params, KZGCommitmentScheme<Bn256>, VerifierSHPLONK<'params, Bn256>> for GpuAccumulatorStrategy<'params> {
     type Output = Self;
     fn new(params: &'params ParamsKZG<Bn256>) -> Self {
         let mut pb = Vec::new();
         params.write_custom(&mut pb, SerdeFormat::RawBytes).expect("vec write");
-        let mut ctx = core::ptr::null_mut();
-        let rc = unsafe { h2v_ctx_create(pb.as_ptr(), pb.len(), H2V_SERDE_RAW_BYTES, core::ptr::null(), 0, 0, 0, &mut ctx) };
+        let mut me = Self { params, ctx: core::ptr::null_mut(), acc: core::ptr::null_mut() };   // (what was made goes with `me` if an assert fails)
+        let rc = unsafe { h2v_ctx_create(pb.as_ptr(), pb.len(), H2V_SERDE_RAW_BYTES, core::ptr::null(), 0, 0, 0, &mut me.ctx) };
         assert_eq!(rc, 0, "h2v_ctx_create");
-        Self { acc: DualMSM::new(params), ctx }
+        let rc = unsafe { h2v_accumulator_create(me.ctx, &mut me.acc) };
+        assert_eq!(rc, 0, "h2v_accumulator_create");
+        me
     }
-    fn process(mut self, f: impl FnOnce(DualMSM<'params, Bn256>) -> Result<GuardKZG<'params, Bn256>, Error>) -> Result<Self, Error> {
-        self.acc.scale(Fr::random(getrandom_or_panic::getrandom_or_panic()));
-        let guard = f(self.acc)?;
-        Ok(Self { acc: guard.msm_accumulator, ctx: self.ctx })
+    fn process(self, f: impl FnOnce(DualMSM<'params, Bn256>) -> Result<GuardKZG<'params, Bn256>, Error>) -> Result<Self, Error> {
+        let guard = f(DualMSM::new(self.params))?;   // (an Err drops `self`: the accumulator and the context go with it)
+        let msm = &guard.msm_accumulator;
+        let (ls, lb) = flat_channel(&msm.left.scalars(), &msm.left.bases());
+        let (rs, rb) = flat_channel(&msm.right.scalars(), &msm.right.bases());
+        let (nl, nr) = (ls.len() / 32, rs.len() / 32);
+        let draw = Fr::random(getrandom_or_panic::getrandom_or_panic()).to_repr();
+        let rc = unsafe { h2v_accumulator_process_guards(self.acc, 1, &nl, &nr, ls.as_ptr(), lb.as_ptr(), rs.as_ptr(), rb.as_ptr(), draw.as_ref().as_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(self)
     }
     fn finalize(self) -> bool {
-        let eval = |m: &dyn Fn() -> (Vec<Fr>, Vec<<G1Affine as CurveAffine>::CurveExt>)| -> [u8; 64] {
-            let (scalars, bases) = m();
-            let sb: Vec<u8> = scalars.iter().flat_map(|s| s.to_repr().as_ref().to_vec()).collect();
-            let bb: Vec<u8> = bases.iter().flat_map(|b| { let a = b.to_affine(); let c = a.coordinates();
-                if bool::from(c.is_some()) { let c = c.unwrap(); [c.x().to_repr().as_ref(), c.y().to_repr().as_ref()].concat() } else { vec![0u8; 64] } }).collect();
-            let (mut out, mut ident) = ([0u8; 64], 0i32);
-            let rc = unsafe { h2v_msm_g1(self.ctx, sb.as_ptr(), bb.as_ptr(), scalars.len(), out.as_mut_ptr(), &mut ident) };
-            assert_eq!(rc, 0, "h2v_msm_g1");
-            out
-        };
-        let left = eval(&|| (self.acc.left.scalars(), self.acc.left.bases()));
-        let right = eval(&|| (self.acc.right.scalars(), self.acc.right.bases()));
         let mut ok = 0i32;
-        let rc = unsafe { h2v_pairing_check(self.ctx, left.as_ptr(), right.as_ptr(), &mut ok) };
+        let rc = unsafe { h2v_accumulator_finalize(self.acc, &mut ok, core::ptr::null_mut(), core::ptr::null_mut()) };
         rc == 0 && ok == 1
+    }
+}
+impl<'params> Drop for GpuAccumulatorStrategy<'params> {
+    fn drop(&mut self) {
+        unsafe { h2v_accumulator_destroy(self.acc) }   // (the accumulator goes before the context it lives on; null is allowed)
+        if !self.ctx.is_null() { unsafe { h2v_ctx_destroy(self.ctx) } }
     }
 }
