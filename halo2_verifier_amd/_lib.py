@@ -52,6 +52,7 @@ SIGNATURES = {
                                         c_szp, c_u8p, c_intp, c_intp]),
     "h2v_accumulator_add_msm": (c_int, [c_vp, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_sz]),
     "h2v_accumulator_process_guards": (c_int, [c_vp, c_sz, c_szp, c_szp, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "h2v_accumulator_process_batch": (c_int, [c_vp, c_vp, c_szp, c_szp]),
     "h2v_accumulator_read": (c_int, [c_vp, c_u8p, c_u8p, c_szp, c_szp]),
     "h2v_accumulator_finalize": (c_int, [c_vp, c_intp, c_u8p, c_u8p]),
     "h2v_accumulator_journal_begin": (c_int, [c_vp, c_sz]),

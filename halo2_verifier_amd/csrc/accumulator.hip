@@ -32,6 +32,12 @@
 // k_accumulator_scale launch of K workgroups writes c_k (L_k, R_k) as whole-point records, and one k_accumulator_merge_fold launch
 // (util.hip) scatters them into the journal slots of K new entries (M = 1 each: the invariant holds as it stands) and writes the
 // accumulator, as the last step.  Soundness: include/h2v.h.
+//
+// A finished staged batch as legs (h2v_accumulator_process_batch): process once per group of the batch, with the groups' sums S_g and
+// the products M_g of their draws taken from what the launch left on the device:
+//     (L, R) <- (prod_g M_g) (L, R) + sum_g W_g S_g,     W_g = prod_{f > g} M_f
+// k_leg_weights (verify_kernels.hip) makes the scalars, one k_accumulator_scale launch of G + 1 items the records, k_accumulator_legs_fold
+// (util.hip) the journal's G entries and the accumulator, as the last step.
 #include "../../include/h2v.h"
 #include "batch.h"
 #include <string.h>
@@ -68,6 +74,12 @@ struct h2v_accumulator {
     DevBuf<uint8_t> m_bytes;         // [128 K] merge_states: the states' affine bytes
     DevBuf<G1A> m_affine;            // [2 K] merge_states
     std::vector<uint32_t> m_host;    // what m_words is copied from and to
+    // process_batch: the G legs of the call in flight (grow-only)
+    DevBuf<G1J> l_pairs;             // [2 (G + 1)] the accumulator's pair, then the batch's G unscaled sums, gathered
+    DevBuf<uint8_t> l_records;       // [G + 1] M (L, R), then W_g S_g, as whole-point records
+    DevBuf<uint32_t> l_words;        // [8 (G + 1)] prod M_g and the W_g, [8 G] the M_g, [G] the journal slots of the G new entries
+    MappedHostBuf l_legs;            // [32 G] the M_g as they come back (pinned: the copy is enqueued between the launches and must not hold the host)
+    std::vector<uint32_t> l_host;    // [G] what the slots are copied from
     // process_guards: staging buffers and an MSM workspace of its own (grow-only), so that accumulators that share a context do not meet
     GuardStage g_stage;              // the call's terms
     MsmWorkspace g_ws;               // the two pooled channels
@@ -294,6 +306,76 @@ int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n, const size_t* l
     if ((rc = sync(a, who))) return rc;
     a->n_proofs += n;
     commit_entry(a, M, n, 0);
+    return 0;
+}
+
+// The G groups of a finished staged batch as G legs, in group order: process once per group, with the groups' chains replaced by what the
+// launch left on the device.  Group g's own sum S_g is b->acc[2g], [2g + 1]; its M_g is its first draw (b->tail) times its first proof's
+// multiplier (b->mult).  Three launches on the accumulator's stream, no host synchronise between them:
+//   k_leg_weights             [prod M, W_0 .. W_{G-1}] and [M_0 .. M_{G-1}], W_g = prod_{f > g} M_f
+//   k_accumulator_scale       G + 1 items over the gathered pairs [(L, R), S_0 .. S_{G-1}]: the records M (L, R), W_g S_g
+//   k_accumulator_legs_fold   the unscaled S_g into the journal slots of G new entries, then (L, R) <- the sum of the records: the last step
+// The M_g reach the host behind the one synchronise (the batch keeps no host draws); the counters and the entries follow it.  The batch
+// is only read: its stream is idle (the stage is Finished), and nothing of its state changes.
+int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_proofs_added, size_t* n_failed_added) {
+    const char* who = "h2v_accumulator_process_batch";
+    // every argument check comes before the first HIP call
+    if (!a || !b) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->stage != BatchStage::Finished) { set_last_error(std::string(who) + ": the batch has no finished launch (h2v_batch_finish / _finish_groups)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->last.folded) { set_last_error(std::string(who) + ": a fold ran since the launch: the batch holds the folded records' sums, not its own"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->n_tail != b->n) { set_last_error(std::string(who) + ": the batch is a shard (a tail of draws longer than the upload)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->n && !b->mult_of_draws) { set_last_error(std::string(who) + ": the batch's multipliers are not those of its uploaded draws"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->plan && b->plan->host.opts.guard_terms) { set_last_error(std::string(who) + ": a guard-variant upload (h2v_guard_msm)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->ctx->device != a->ctx->device) { set_last_error(std::string(who) + ": a batch on another device than the accumulator"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!same_srs(b->ctx->params, a->ctx->params)) { set_last_error(std::string(who) + ": a batch over other params than the accumulator (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t G = b->groups, n = b->n;
+    if (n_proofs_added) *n_proofs_added = 0;
+    if (n_failed_added) *n_failed_added = 0;
+    if (!n) return 0;   // no verify_proof: no scale, no Guard, no entry
+    if (a->j_cap && a->entries.size() + G > a->j_cap) { set_last_error(std::string(who) + ": the journal has fewer free entries than the batch has groups"); return H2V_ERR_UNSUPPORTED; }
+    // the groups' counters, from the statuses the finished launch left in the batch's host block
+    const int* st = reinterpret_cast<const int*>(b->results_host.p + ResultsLayout{G, n}.status());
+    std::vector<size_t> count(G), failed(G, 0);
+    size_t all_failed = 0;
+    for (size_t g = 0, i = 0; g < G; ++g) {
+        count[g] = group_count(b, g);
+        for (size_t k = 0; k < count[g]; ++k, ++i) if (st[i]) ++failed[g];
+        all_failed += failed[g];
+    }
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    int rc;
+    if ((rc = a->l_pairs.reserve(2 * (G + 1))) || (rc = a->l_records.reserve((size_t)H2V_ACC_RECORD_BYTES * (G + 1))) || (rc = a->l_words.reserve(8 * (G + 1) + 9 * G)) ||
+        (rc = a->l_legs.reserve(32 * G))) return rc;
+    a->l_host.resize(G);
+    uint32_t* d_weights = a->l_words.p;
+    uint32_t* d_legs = d_weights + 8 * (G + 1);
+    uint32_t* d_slots = d_legs + 8 * G;
+    const uint8_t* h_legs = a->l_legs.p;
+    uint32_t* h_slots = a->l_host.data();
+    hipStream_t s = a->stream;
+    Drain drain{s};
+    // the pairs, gathered in the accumulator's stream order: (L, R), then the groups' sums as the launch left them
+    H2V_HIP_CHECK(hipMemcpyAsync(a->l_pairs.p, a->acc.p, 2 * sizeof(G1J), hipMemcpyDeviceToDevice, s));
+    H2V_HIP_CHECK(hipMemcpyAsync(a->l_pairs.p + 2, b->acc.p, 2 * G * sizeof(G1J), hipMemcpyDeviceToDevice, s));
+    if (a->j_cap) {
+        for (size_t g = 0; g < G; ++g) h_slots[g] = a->free_slots[a->free_slots.size() - 1 - g];   // the lowest free slots, in group order
+        H2V_HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, 4 * G, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = leg_weights_enqueue(s, b->tail.p, b->mult.p, ragged(b) ? b->d_group_off.p : nullptr, (uint32_t)(n / G), (uint32_t)G, d_weights, d_legs))) return rc;
+    H2V_HIP_CHECK(hipMemcpyAsync(a->l_legs.p, d_legs, 32 * G, hipMemcpyDeviceToHost, s));   // (in front of the commit: nothing that can fail is enqueued behind it)
+    if ((rc = accumulator_scale_many_enqueue(s, a->l_pairs.p, nullptr, d_weights, (uint32_t)(G + 1), a->l_records.p))) return rc;
+    // the commit: the journal's slots, then (L, R) <- M (L, R) + sum_g W_g S_g
+    if ((rc = accumulator_legs_fold_enqueue(s, a->l_records.p, (uint32_t)(G + 1), 0, a->l_pairs.p + 2, d_slots, a->j_cap ? a->j_sums.p : nullptr, a->acc.p))) return rc;
+    drain.armed = false;
+    if ((rc = sync(a, who))) return rc;
+    for (size_t g = 0; g < G; ++g) {
+        Fr M;
+        Fr::from_bytes(h_legs + 32 * g, M);
+        commit_entry(a, M, count[g], failed[g]);
+    }
+    a->n_proofs += n; a->n_failed += all_failed;
+    if (n_proofs_added) *n_proofs_added = n;
+    if (n_failed_added) *n_failed_added = all_failed;
     return 0;
 }
 

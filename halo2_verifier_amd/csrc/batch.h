@@ -95,6 +95,11 @@ int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, u
 // proportional to n whatever the sizes.  d_tile_prod: ragged_multipliers_tiles(n) elements, d_tile_words: twice as many words.
 size_t ragged_multipliers_tiles(uint32_t n);
 int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8_t* d_last, uint32_t n, Fr* d_mult, Fr* d_tile_prod, uint32_t* d_tile_words);
+// The legs of a finished batch (k_leg_weights; h2v_accumulator_process_batch): with M_g = the product of group g's draws — the draw of
+// its first proof, d_tail[32 first_g ..], times that proof's multiplier d_mult[first_g]; first_g = d_off[g], or g * gs (d_off null) —
+// d_weights <- [prod_g M_g, W_0 .. W_{G-1}], W_g = prod_{f > g} M_f, and d_legs <- [M_0 .. M_{G-1}], canonical 8-word scalars.
+// 1 <= groups <= 512: one workgroup.
+int leg_weights_enqueue(hipStream_t s, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_off, uint32_t gs, uint32_t groups, uint32_t* d_weights, uint32_t* d_legs);
 // out[i] = src[idx[i]]: the multipliers of a non-contiguous subset of a larger accumulation
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);

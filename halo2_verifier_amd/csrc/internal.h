@@ -219,5 +219,9 @@ int fold_records_enqueue(hipStream_t s, const void* d_recs, uint32_t n_recs, uin
 // share a side's sum, a power of two in 1 .. 64; 0 = accumulator_merge_team(n) = min(64, the next power of two >= n + 1).
 uint32_t accumulator_merge_team(uint32_t n);
 int accumulator_merge_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc);
+// The fold of a batch's legs (k_accumulator_legs_fold), one launch: d_acc[side] <- the sum of the n >= 1 whole-point records' side (the
+// accumulator is replaced: record 0 is its scaled self), and with d_sums the unscaled pair of leg g < n - 1, d_pairs[2 g], [2 g + 1]
+// -> d_sums[2 slot], [2 slot + 1], slot = d_slots[g] (d_slots null: g).  team: as above; 0 = accumulator_merge_team(n - 1).
+int accumulator_legs_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const G1J* d_pairs, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc);
 
 }  // namespace h2v

@@ -222,6 +222,41 @@ int accumulator_merge_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n
     return 0;
 }
 
+// The fold of a batch's legs (h2v_accumulator_process_batch, accumulator.hip): acc[side] <- sum_i recs[i][side] over n whole-point records
+// — it REPLACES the accumulator: record 0 is the scaled accumulator M (L, R), record 1 + g is W_g S_g, all written by one
+// k_accumulator_scale launch.  With `sums`, the UNSCALED pair of leg g, pairs[2 g + side], goes into the journal slot the host assigned:
+// sums[2 slot + side], slot = slots[g] (slots null: slot = g), for the n - 1 legs.  k_accumulator_merge_fold's shape: one one-wave
+// workgroup per side, a team of the first `team` lanes (a power of two in 1 .. 64), lane r adds the records r, r + team, .., then a
+// butterfly of log2(team) levels; every addition is the complete one (records may be identities, equal, or each other's negatives).
+// The slots are written before acc[side], lane 0's store and the kernel's last.
+__global__ void __launch_bounds__(64) k_accumulator_legs_fold(const AccRecord* __restrict__ recs, uint32_t n, uint32_t team, const G1J* __restrict__ pairs,
+                                                              const uint32_t* __restrict__ slots, G1J* __restrict__ sums, G1J* __restrict__ acc) {
+    const uint32_t side = blockIdx.x, lane = threadIdx.x;
+    if (sums)
+        for (uint32_t g = lane; g + 1 < n; g += 64) sums[2 * (size_t)(slots ? slots[g] : g) + side] = pairs[2 * (size_t)g + side];
+    G1J sum = G1J::identity();
+    if (lane < team)
+        for (uint32_t i = lane; i < n; i += team) sum = g1_add(sum, (side ? recs[i].right : recs[i].left)[0]);
+    for (uint32_t d = team >> 1; d > 0; d >>= 1) {
+        G1J other;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&other);
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&sum);
+#pragma unroll
+        for (uint32_t w = 0; w < sizeof(G1J) / 4; ++w) dst[w] = (uint32_t)__shfl_down((int)src[w], d, 64);
+        sum = g1_add(sum, other);   // lanes r >= d add a value that is not part of the sum: only lane 0 is kept
+    }
+    if (lane == 0) acc[side] = sum;
+}
+int accumulator_legs_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const G1J* d_pairs, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc) {
+    if (!n) { set_last_error("accumulator_legs_fold_enqueue: no record"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!team) team = accumulator_merge_team(n - 1);   // (n items, as a merge of n - 1 records has)
+    if (team > 64 || (team & (team - 1))) { set_last_error("accumulator_legs_fold_enqueue: the team is not a power of two in 1 .. 64"); return H2V_ERR_BAD_ARGUMENT; }
+    if (d_sums && n > 1 && !d_pairs) { set_last_error("accumulator_legs_fold_enqueue: journal slots without the legs' pairs"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_accumulator_legs_fold, dim3(2), dim3(64), 0, s, (const AccRecord*)d_recs, n, team, d_pairs, d_slots, d_sums, d_acc);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ void k_affine_to_jacobian(const G1A* __restrict__ in, G1J* __restrict__ out, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = G1J::from_affine(in[i]);

@@ -512,6 +512,39 @@ __global__ void __launch_bounds__(MULT_TILE) k_seg_mult_apply(Fr* __restrict__ m
     if (j < n && threadIdx.x >= open_from[blockIdx.x]) mult[j] = mult[j] * tile_prod[blockIdx.x];
 }
 
+// The weights of a finished batch's groups fed to a resident accumulator as G legs (h2v_accumulator_process_batch, accumulator.hip).
+// Group g's M_g, the product of its draws, is its first draw times the multiplier of its first proof (the product of the later draws
+// of the group, what the upload left in mult); first_g = off[g], or g * gs for equal groups (off null).  One workgroup of LEG_WEIGHTS_MAX
+// threads, thread g its group (the threads past G hold 1), one suffix scan in LDS (18 KB), then as canonical 8-word scalars
+//   weights[0] = prod_g M_g,  weights[1 + g] = W_g = prod_{f > g} M_f   (the items of the k_accumulator_scale launch that follows)
+//   legs[g] = M_g                                                       (for the host's journal)
+#define LEG_WEIGHTS_MAX 512u
+__device__ __forceinline__ void fr_store_canonical(uint32_t* out, const Fr& v) {
+    uint32_t raw[8];
+    v.to_raw(raw);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = raw[j];
+}
+__global__ void __launch_bounds__(LEG_WEIGHTS_MAX) k_leg_weights(const uint8_t* __restrict__ tail, const Fr* __restrict__ mult, const uint32_t* __restrict__ off, uint32_t gs,
+                                                                 uint32_t G, uint32_t* __restrict__ weights, uint32_t* __restrict__ legs) {
+    __shared__ Fr part[LEG_WEIGHTS_MAX];
+    const uint32_t t = threadIdx.x;
+    Fr m = Fr::one();
+    if (t < G) {
+        const size_t first = off ? off[t] : (size_t)t * gs;
+        Fr r;
+        Fr::from_bytes(tail + 32 * first, r);
+        m = r * mult[first];
+    }
+    part[t] = m;
+    fr_suffix_scan<LEG_WEIGHTS_MAX>(part, t);
+    if (t < G) {
+        fr_store_canonical(weights + 8 * (size_t)(t + 1), t + 1 < LEG_WEIGHTS_MAX ? part[t + 1] : Fr::one());
+        fr_store_canonical(legs + 8 * (size_t)t, m);
+    }
+    if (t == 0) fr_store_canonical(weights, part[0]);
+}
+
 // Instance evaluation for wide instance vectors (lib.rs:173-218; l_i_range, poly/domain.rs:187-212):
 //   E = sum_j a_j * l_{j-rot}(x),   l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
 // One workgroup per proof.  Thread t owns j = t, t + 256, ...: omega^(j-rot) advances by omega^256 per step.  The
@@ -838,6 +871,13 @@ int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8
         hipLaunchKernelGGL(k_seg_mult_scan_tiles, dim3(1), dim3(1024), 0, s, d_tile_prod, (const uint32_t*)tile_closed, tiles);
         hipLaunchKernelGGL(k_seg_mult_apply, dim3(tiles), dim3(MULT_TILE), 0, s, d_mult, n, (const Fr*)d_tile_prod, (const uint32_t*)open_from);
     }
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int leg_weights_enqueue(hipStream_t s, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_off, uint32_t gs, uint32_t groups, uint32_t* d_weights, uint32_t* d_legs) {
+    if (!groups || groups > LEG_WEIGHTS_MAX) { set_last_error("leg_weights_enqueue: the group count is not in 1 .. 512"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!d_tail || !d_mult || !d_weights || !d_legs) { set_last_error("leg_weights_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_leg_weights, dim3(1), dim3(LEG_WEIGHTS_MAX), 0, s, d_tail, d_mult, d_off, gs, groups, d_weights, d_legs);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -725,6 +725,27 @@ class Accumulator:
         if args[0] and self._inputs:   # (journal on: the call has appended an entry)
             self._inputs.append(("guards", guards) if self._keep_inputs else None)
 
+    def process_batch(self, batch):
+        """The groups of a finished staged Batch as legs of this accumulator, in group order (h2v_accumulator_process_batch): equals
+        process() once per group over that group's proofs and draws, with the groups' sums taken from what the launch left on the GPU.
+        batch: a Batch whose finish() / finish_groups() has returned, over this accumulator's device and params; it is only read and may
+        be uploaded again at once.  With the journal on every group leaves an entry: check_legs() names a failing group, and
+        Batch.identify() on the still-resident batch names the proofs inside it.  -> (n_proofs_added, n_failed_added).  A call that
+        raises leaves the accumulator as it was."""
+        if not isinstance(batch, Batch):
+            raise TypeError("process_batch takes a Batch")
+        if self._keep_inputs:
+            raise ValueError("process_batch on an Accumulator with keep_inputs=True: retained inputs are host bytes and a Batch has none; "
+                             "use Batch.identify() on the resident batch to name the proofs of a failing group")
+        if not self._h or not batch._h:
+            raise ValueError("the accumulator or the batch is closed")
+        n, f = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        check(self._lib.h2v_accumulator_process_batch(self._h, batch._h, ctypes.byref(n), ctypes.byref(f)))
+        self.last_all_ok = f.value == 0
+        if n.value and self._inputs:   # (journal on: the call has appended an entry per group)
+            self._inputs.extend([None] * batch.groups)
+        return n.value, f.value
+
     def add_msm(self, left, right):
         """(L, R) += the two term lists evaluated, unscaled (h2v_accumulator_add_msm: AccumulatorStrategy::with on an empty accumulator,
         DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""

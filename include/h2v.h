@@ -287,6 +287,28 @@ int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n,
                                    const uint8_t* left_scalars32, const uint8_t* left_bases64,
                                    const uint8_t* right_scalars32, const uint8_t* right_bases64,
                                    const uint8_t* rand32);
+/* The G groups of a finished staged batch as G legs, in group order: the staged launch's throughput under this strategy's one pairing.
+ *   replaces: per group, msm_accumulator.scale(draw) then the Guard's terms for each of its proofs (kzg/strategy.rs:125-136,
+ *   msm.rs:173-183) — with the Guards' sum taken from what the launch left on the device instead of computed again.
+ * Group g holds the proofs [first_g, first_g + n_g) with the draws the batch was uploaded with; S_g is its own sum (the two points the
+ * launch left for it) and M_g the product of its draws:
+ *     (L, R) <- (prod_g M_g) (L, R) + sum_g W_g S_g,     W_g = prod_{f > g} M_f,     n_proofs += n,   n_failed += the non-zero statuses
+ * — bit for bit, in everything read / finalize / check_legs return, what h2v_accumulator_process called once per group over that group's
+ * proofs and draws leaves, and so ONE h2v_verify_batch (or _keys) over all proofs so far with all draws concatenated.  Zero draws are
+ * allowed (M_g = 0 drops everything before it); a proof that failed by status contributes nothing and is counted.
+ * b: a batch whose last launch is finished (h2v_batch_finish / _finish_groups has returned), groups equal or unequal, launched with or
+ * without its own pairing.  H2V_ERR_BAD_ARGUMENT before any device work, h2v_last_error naming the reason: a null argument; a batch that
+ * is not finished; a fold since the launch (h2v_batch_fold_check_enqueue); a shard (a tail of draws longer than the upload); multipliers
+ * that are not those of the uploaded draws; a guard-variant upload; a batch on another device, or over other params (g[0], g2, s_g2).
+ * A journal with fewer than G free entries: H2V_ERR_UNSUPPORTED before any device work.  Any non-zero return leaves points, counters
+ * and journal exactly as they were: the accumulator is written by the call's last enqueued step, the counters and entries follow the
+ * one synchronise.  An upload of no proofs changes nothing.  n_proofs_added / n_failed_added (may be NULL): what the call added.
+ * The batch is only read: finish_groups, recheck and identify afterwards return what they returned before, and it may be uploaded
+ * again at once.  Synchronous like every accumulator call (its stream is idle at return); other batches' launches stay in flight.
+ * Journal: G entries in group order, entry g with sum S_g (unscaled), M_g (read back from the device: 32 G bytes with the call's
+ * synchronise) and the group's size and non-zero statuses; (L, R) = sum_e W_e sum_e holds as it stands.  check_legs names a failing
+ * GROUP and drop_legs takes it out; h2v_batch_identify / h2v_batch_recheck on the still-resident batch name the proofs inside it. */
+int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_proofs_added, size_t* n_failed_added);
 /* The two points as affine bytes (all-zero = identity) and the counters; any pointer but `a` may be NULL. */
 int h2v_accumulator_read(h2v_accumulator* a, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t* n_proofs, size_t* n_failed);
 /* ok = the pairing check of (L, R) passes AND no processed proof failed — what batch_ok means for h2v_verify_batch.

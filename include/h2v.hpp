@@ -302,6 +302,17 @@ public:
         check(h2v_accumulator_process_guards(h_, guards.size(), f.left_counts.data(), f.right_counts.data(), f.ls.data(), f.lb.data(), f.rs.data(), f.rb.data(),
                                              rand32.empty() ? nullptr : rand32.data()));
     }
+    // The groups of a finished staged batch as legs, in group order (h2v_accumulator_process_batch): per group scale by its draws, add its
+    // Guards' sum (kzg/strategy.rs:125-136, msm.rs:173-183) as the launch left it on the device.  Equals process() once per group.  The batch
+    // is only read.  -> what the call added; all_ok(): whether no proof of the batch failed.  A Failure leaves the accumulator as it was.
+    struct Added { size_t n_proofs, n_failed; };
+    Added process_batch(h2v_batch* batch) {
+        if (!batch) throw Failure(H2V_ERR_BAD_ARGUMENT, "process_batch takes a finished batch");
+        Added added{0, 0};
+        check(h2v_accumulator_process_batch(h_, batch, &added.n_proofs, &added.n_failed));
+        all_ok_ = added.n_failed == 0;
+        return added;
+    }
     // the two points as canonical x | y (left(), right(); all-zero = identity) and the counters
     void read() { check(h2v_accumulator_read(h_, left_, right_, &n_proofs_, &n_failed_)); }
     // -> true iff the pairing of (L, R) passes and no processed proof failed; left() / right() hold the points.  The accumulator is not consumed.

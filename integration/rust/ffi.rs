@@ -99,6 +99,7 @@ extern "C" {
     pub fn h2v_accumulator_process_guards(a: *mut h2v_accumulator, n: usize, left_counts: *const usize, right_counts: *const usize,
                                           left_scalars32: *const u8, left_bases64: *const u8, right_scalars32: *const u8, right_bases64: *const u8,
                                           rand32: *const u8) -> c_int;
+    pub fn h2v_accumulator_process_batch(a: *mut h2v_accumulator, b: *mut h2v_batch, n_proofs_added: *mut usize, n_failed_added: *mut usize) -> c_int;
     pub fn h2v_accumulator_read(a: *mut h2v_accumulator, out_left_xy: *mut u8, out_right_xy: *mut u8, n_proofs: *mut usize, n_failed: *mut usize) -> c_int;
     pub fn h2v_accumulator_finalize(a: *mut h2v_accumulator, ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_accumulator_journal_begin(a: *mut h2v_accumulator, capacity: usize) -> c_int;

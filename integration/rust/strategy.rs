@@ -11,6 +11,7 @@
 //! * `GpuResidentAccumulator`  — the incremental seam: an accumulator that stays on the GPU across `process` calls over any keys
 //!                               sharing the params; `finalize` whenever the caller decides (h2v_accumulator_*).
 //!                               `process_guards` takes the Guards of proofs that a CPU `verify_proof` went through.
+//!                               `process_batch` takes the groups of a finished `GpuStagedBatch` as legs, from what its launch left on the GPU.
 //!                               `merge` / `export_state` / `merge_states` fold several of them into one pairing.
 //!                               Its leg journal (`journal_begin`, `check_legs`, `drop_legs`) finds the legs whose own pairing
 //!                               fails and takes them out again.
@@ -313,6 +314,18 @@ impl GpuResidentAccumulator {
                                                          core::ptr::null()) };
         if rc != 0 { return Err(map_err(rc)); }
         Ok(())
+    }
+
+    /// The groups of a finished staged batch as legs of this strategy, in group order (h2v_accumulator_process_batch): per group
+    /// `DualMSM::scale` by its draws, then the sum of its Guards' terms (kzg/strategy.rs:125-136, msm.rs:173-183) as the launch left it on
+    /// the device — what `process` once per group over that group's proofs and draws leaves.  `batch` has finished (`finish` /
+    /// `finish_groups` has returned), lives on this device over these params, and is only read.  With the journal on every group leaves
+    /// an entry.  Returns `(n_proofs_added, n_failed_added)`.  An `Err` leaves the accumulator as it was.
+    pub fn process_batch(&mut self, batch: &GpuStagedBatch) -> Result<(usize, usize), Error> {
+        let (mut n, mut f) = (0usize, 0usize);
+        let rc = unsafe { h2v_accumulator_process_batch(self.acc, batch.b, &mut n, &mut f) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok((n, f))
     }
 
     /// One `verify_proof(&params, vks[key], strategy, &[instances], &mut Blake2bRead::init(proof))` call per item, in order:

@@ -22,7 +22,15 @@ offered before it.  Median wall times of --reps runs, host proofs in, one MI355X
       those of 64 accumulators, cycled; the round trip cycles over the same accumulators.
    b. (--parent) process x 8 + finalize on legs of 1024 proofs, this build against the parent's.
    With --trace: at K = 8, 64 and 512, one drop_legs([]) over a journal of K entries (k_fold_records over K whole-point records) and one
-   merge_states of K states (k_accumulator_merge_fold over K records), for a `rocprofv3 --kernel-trace --stats` run."""
+   merge_states of K states (k_accumulator_merge_fold over K records), for a `rocprofv3 --kernel-trace --stats` run.
+7. (--batch) feeding a finished staged batch, instead of 1 - 6; --parent PATH as above; the variants alternate inside every repetition,
+   after >= 50 ms of warm-up:
+   a. one RESIDENT launch of 20 x 1024 proofs without a pairing + finish_groups + process_batch, against 20 process calls of 1024 host
+      proofs on the parent's library.  Reported, not gated: the two sides differ in where their inputs live.
+   b. process_batch alone over a finished batch of G = 20 (x 1024) and G = 512 (x 2) groups, against a merge of G sources on the parent's
+      library — the same scale-many + fold shape: h2v_accumulator_merge over 20 accumulators; at 512, where the probe makes no 512
+      objects (each owns a stream), h2v_accumulator_merge_states over 512 states.  Gate: process_batch <= 1.25 x the merge.
+   With --trace: one process_batch at G = 20 and at G = 512, for a `rocprofv3 --kernel-trace --stats` run."""
 import argparse, ctypes, json, os, random, sys, time
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import bench
@@ -39,6 +47,7 @@ ap.add_argument("--trace", action="store_true")
 ap.add_argument("--journal", action="store_true")
 ap.add_argument("--parent", default=None)
 ap.add_argument("--merge", action="store_true")
+ap.add_argument("--batch", action="store_true")
 args = ap.parse_args()
 if args.library:
     _lib.lib_path = lambda: os.path.abspath(args.library)
@@ -278,6 +287,115 @@ def merge_probe():
             json.dump(res, f, indent=1)
 
 
+def batch_probe():
+    LEGS = 20
+    flat_p, flat_i = d["proofs"][:1024 * n], d["inst"][:32 * N * n]
+
+    def staged(groups, per_group):
+        """a resident batch of groups x per_group proofs (the pool, cycled), uploaded once"""
+        total = groups * per_group
+        reps_, rest = divmod(total, n)
+        b = h2v.Batch(ctx, total, N, groups=groups)
+        tail = b"".join(rnd.randrange(1, R_MOD).to_bytes(32, "little") for _ in range(total))
+        b.upload(flat_p * reps_ + flat_p[:1024 * rest], 1024, flat_i * reps_ + flat_i[:32 * N * rest], [N], tail)
+        return b
+
+    big, wide = staged(LEGS, n), staged(512, 2)
+    for b in (big, wide):
+        b.launch(with_pairing=False)
+        ok, st, _, _ = b.finish_groups(raw_statuses=True)
+        assert all(ok) and not any(st)
+    if args.trace:
+        for b in (big, wide):
+            acc = h2v.Accumulator(ctx)
+            acc.process(ctx, None, P[:8], I[:8], draws[1][:8])
+            assert acc.process_batch(b) == (b.n, 0) and acc.finalize()[0]
+            acc.close()
+        return
+    pctx = parent_context(args.parent) if args.parent else None
+    res["batch_ms"] = {}
+
+    def alternate(variants):
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.05:   # warm-up
+            for fn in variants.values():
+                fn()
+        ts = {v: [] for v in variants}
+        for _ in range(args.reps):
+            for v, fn in variants.items():
+                t0 = time.perf_counter(); fn(); ts[v].append((time.perf_counter() - t0) * 1e3)
+        row = {v: round(median(t), 3) for v, t in ts.items()}
+        row.update({v + "_min_max": [round(min(t), 3), round(max(t), 3)] for v, t in ts.items()})
+        return row
+
+    # a. launch + finish_groups + process_batch of 20 x 1024 resident proofs, against 20 process calls of 1024 host proofs
+    acc = h2v.Accumulator(ctx)
+
+    def resident():
+        big.launch(with_pairing=False)
+        big.finish_groups(raw_statuses=True)
+        return acc.process_batch(big)
+    variants = {"launch_finish_process_batch": resident}
+    if pctx:
+        pacc = h2v.Accumulator(pctx)
+
+        def host_legs():
+            for j in range(LEGS):
+                pacc.process(pctx, None, P, I, draws[j % K])
+        variants["parent_process_x20"] = host_legs
+    row = alternate(variants)
+    assert acc.finalize()[0]
+    line = f"{LEGS} x 1024 proofs: " + "   ".join(f"{v} {row[v]:9.3f} ms" for v in variants)
+    if pctx:
+        row["parent_over_this"] = round(row["parent_process_x20"] / row["launch_finish_process_batch"], 2)
+        line += f"   ({row['parent_over_this']:.1f}x; resident inputs against host bytes: reported, not gated)"
+        pacc.close()
+    res["batch_ms"]["resident_20x1024"] = row
+    print(line, flush=True)
+    acc.close()
+    # b. process_batch alone, against a merge of as many sources on the parent's library
+    cs = [rnd.randrange(1, R_MOD) for _ in range(512)]
+    for b, G in ((big, LEGS), (wide, 512)):
+        acc = h2v.Accumulator(ctx)
+        acc.process(ctx, None, P[:8], I[:8], draws[1][:8])   # (a non-empty accumulator: the scale step has points to scale)
+        variants = {"process_batch": lambda: acc.process_batch(b)}
+        psrcs = []
+        if pctx:
+            pdst = h2v.Accumulator(pctx)
+            for j in range(min(G, LEGS)):
+                a = h2v.Accumulator(pctx)
+                a.process(pctx, None, P[:16], I[:16], draws[j % K][:16])
+                psrcs.append(a)
+            if G <= LEGS:
+                variants["parent_merge"] = lambda: pdst.merge(psrcs, cs[:G])
+            else:
+                states = [a.export_state() for a in psrcs]
+                variants["parent_merge_states"] = lambda: pdst.merge_states([states[k % len(states)] for k in range(G)], cs[:G])
+        row = alternate(variants)
+        line = f"G = {G:3d}: " + "   ".join(f"{v} {row[v]:8.3f} ms" for v in variants)
+        if pctx:
+            other = [v for v in variants if v != "process_batch"][0]
+            row["over_merge"] = round(row["process_batch"] / row[other], 4)
+            line += f"   ratio {row['over_merge']:.3f}x ({'within' if row['over_merge'] <= 1.25 else 'OUTSIDE'} 1.25x)"
+            pdst.close()
+        res["batch_ms"][f"process_batch_G{G}"] = row
+        print(line, flush=True)
+        assert acc.finalize()[0]
+        acc.close()
+        for a in psrcs:
+            a.close()
+    big.close(); wide.close()
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if args.batch:
+    batch_probe()
+    ctx.close()
+    sys.exit(0)
 if args.merge:
     merge_probe()
     ctx.close()
