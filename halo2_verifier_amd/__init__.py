@@ -10,5 +10,6 @@ from ._lib import H2VError, lib_path, load_library, device_count  # noqa: F401
 from .verifier import (  # noqa: F401
     SerdeFormat, ParamsKZG, VerifyingKey, Context, AccumulatorStrategy, SingleStrategy, verify_proof, verify_batch,
     PlonkError, Batch, MultiOpen, TranscriptKind, verify_batch_keys, verify_batch_keys_identify, recheck_batches, Accumulator,
+    MSMKZG, DualMSM, eval_many, dual_check_many,
 )
 from . import distributed  # noqa: F401

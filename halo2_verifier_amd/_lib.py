@@ -61,6 +61,16 @@ SIGNATURES = {
     "h2v_accumulator_merge": (c_int, [c_vp, ctypes.POINTER(c_vp), c_sz, c_u8p, c_u8p]),
     "h2v_accumulator_export_state": (c_int, [c_vp, c_u8p]),
     "h2v_accumulator_merge_states": (c_int, [c_vp, c_u8p, c_sz, c_u8p, c_u8p]),
+    "h2v_msm_create": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "h2v_msm_destroy": (None, [c_vp]),
+    "h2v_msm_append_terms": (c_int, [c_vp, c_u8p, c_u8p, c_sz]),
+    "h2v_msm_add_msm": (c_int, [c_vp, c_vp]),
+    "h2v_msm_scale": (c_int, [c_vp, c_u8p]),
+    "h2v_msm_len": (c_int, [c_vp, c_szp]),
+    "h2v_msm_terms": (c_int, [c_vp, c_sz, c_sz, c_u8p, c_u8p]),
+    "h2v_msm_eval_many": (c_int, [ctypes.POINTER(c_vp), c_sz, c_u8p, c_intp]),
+    "h2v_dual_msm_check_many": (c_int, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sz, c_intp, c_u8p, c_u8p]),
+    "h2v_accumulator_add_msms": (c_int, [c_vp, c_vp, c_vp]),
     "h2v_verify_batches": (c_int, [c_vp, c_sz, c_szp, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p]),
     "h2v_verify_each": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_intp]),
     "h2v_verify_batch_identify": (c_int, [c_vp, c_sz, ctypes.POINTER(c_u8p), c_szp, ctypes.POINTER(c_u8p), c_sz, c_szp, c_u8p, c_intp, c_intp, c_u8p, c_u8p, c_szp]),

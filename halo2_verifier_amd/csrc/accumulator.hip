@@ -40,6 +40,7 @@
 // (util.hip) the journal's G entries and the accumulator, as the last step.
 #include "../../include/h2v.h"
 #include "batch.h"
+#include "msm_object.h"
 #include <string.h>
 #include <algorithm>
 #include <functional>
@@ -405,6 +406,31 @@ int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, c
         (rc = affine_to_jacobian_enqueue(s, a->affine.p, a->jacobian.p, 2)) ||
         (rc = affine_to_jacobian_enqueue(s, a->affine.p, next_slot(a), next_slot(a) ? 2 : 0)) ||   // the journal's entry: the two sums
         (rc = export_records_enqueue(s, a->acc.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p)) ||
+        (rc = export_records_enqueue(s, a->jacobian.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p + H2V_ACC_RECORD_BYTES)) ||
+        (rc = fold_records_enqueue(s, a->records.p, 2, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) { hipStreamSynchronize(s); return rc; }
+    if ((rc = sync(a, who))) return rc;
+    commit_entry(a, Fr::one(), 0, 0);
+    return 0;
+}
+
+// h2v_accumulator_add_msm with both channels resident (h2v_msm, msm_object.hip): one pooled launch of two problems on the context's
+// stream evaluates them straight into `jacobian`, and the steps of add_msm behind its two h2v_msm_g1 calls follow — unscaled, the same
+// counters, the same journal entry; no point crosses host memory.
+int h2v_accumulator_add_msms(h2v_accumulator* a, h2v_msm* left, h2v_msm* right) {
+    const char* who = "h2v_accumulator_add_msms";
+    if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (journal_full(a)) { set_last_error(std::string(who) + ": the journal is full"); return H2V_ERR_UNSUPPORTED; }
+    // both channels are evaluated before anything of the accumulator changes (its stream is idle: the context's stream writes `jacobian`)
+    int rc;
+    if ((rc = msm_object_eval_pair(a->ctx, who, left, right, a->jacobian.p))) return rc;
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    hipStream_t s = a->stream;
+    // (L, R) <- (L, R) + the two sums, unscaled: the accumulator and the sums as two whole-point records, folded
+    if (G1J* slot = next_slot(a)) {   // the journal's entry: the two sums
+        const hipError_t e = hipMemcpyAsync(slot, a->jacobian.p, 2 * sizeof(G1J), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) { hipStreamSynchronize(s); set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    }
+    if ((rc = export_records_enqueue(s, a->acc.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p)) ||
         (rc = export_records_enqueue(s, a->jacobian.p, nullptr, 1, 0, nullptr, 0, 1, a->records.p + H2V_ACC_RECORD_BYTES)) ||
         (rc = fold_records_enqueue(s, a->records.p, 2, 1, 1, 0, a->acc.p, nullptr, nullptr, a->words.p))) { hipStreamSynchronize(s); return rc; }
     if ((rc = sync(a, who))) return rc;

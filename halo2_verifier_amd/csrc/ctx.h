@@ -37,6 +37,13 @@ int guard_args_check(const char* who, GuardArgs& g);
 int guard_stage_enqueue(hipStream_t s, GuardStage& st, const GuardArgs& g, size_t g0, size_t g1, bool per_guard, const Fr* d_mult);
 // after the synchronise: 0, or H2V_ERR_BAD_ARGUMENT with the guard and the side of the first bad term in the message
 int guard_stage_verdict(const char* who, const GuardStage& st, size_t g0);
+// What the resident MSM objects of a context (h2v_msm, msm_object.hip) share, under the context's lock (grow-only): the bytes of an
+// append on their way in, the bytes of a read-back or an evaluation on their way out, and the one zero term on the identity that an
+// empty object is evaluated as (8 zero words, then an all-zero G1A).  An object owns its two term arrays and nothing else.
+struct MsmObjectStage {
+    DevBuf<uint8_t> sb, bb, out; DevBuf<uint32_t> word, flags, zero;
+    bool zero_ready = false;
+};
 }  // namespace h2v
 
 struct h2v_ctx {
@@ -55,6 +62,7 @@ struct h2v_ctx {
     int instance_kernel_threshold = 0;                         // h2v_options (debug): 0 = default
     h2v_tuning tuning = {};                                    // h2v_ctx_set_tuning (debug / test): forced kernel variants
     struct h2v_batch* scratch_batch = nullptr;  // kept between one-shot calls (h2v_verify_batch / _each): ~20 device allocations saved per call
+    h2v::MsmObjectStage msm_objects;   // h2v_msm_*: staging shared by the context's resident MSM objects (they evaluate through guard_ws / guard_pairs / guard_ok)
 };
 
 namespace h2v {

@@ -203,6 +203,12 @@ int scalars_from_bytes_enqueue(hipStream_t s, const uint8_t* d_bytes, uint32_t* 
 // is not read.  The byte arrays and d_out_scalars lie on 16-byte boundaries.
 int guard_terms_enqueue(hipStream_t s, const uint8_t* d_scalars32, const uint8_t* d_bases64, const uint32_t* d_guard_of_term, const Fr* d_mult, uint32_t* d_out_scalars,
                         G1A* d_out_bases, uint32_t* d_first_bad, uint32_t n);
+// A resident MSM object's scalars in place (k_msm_scale): words i <- words i * f mod r for n terms of 8 canonical words, `factor` = f in
+// Montgomery form.  d_words lies on a 16-byte boundary.
+int msm_scale_enqueue(hipStream_t s, uint32_t* d_words, const Fr& factor, uint32_t n);
+// affine Montgomery -> canonical x|y bytes (64 B each, the identity all-zero): the inverse of bases_from_bytes_enqueue (k_affine_to_bytes).
+// d_out lies on a 16-byte boundary.
+int affine_to_bytes_enqueue(hipStream_t s, const G1A* d_in, uint8_t* d_out, uint32_t n);
 // Jacobian -> canonical x|y bytes (+ identity flag word after the 64 bytes: out is 68 B aligned to 4)
 int copy_words_enqueue(hipStream_t s, const void* d_src, void* d_dst, size_t n_words, size_t lds_reserve = 0);   // by a kernel (the destination may be mapped host memory)
 int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, uint32_t* d_is_identity, uint32_t n, size_t lds_reserve = 0);

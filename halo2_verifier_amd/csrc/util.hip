@@ -81,6 +81,47 @@ __global__ void __launch_bounds__(256) k_guard_terms(const uint4* __restrict__ s
     out_bases[i] = p;
 }
 
+// scalar_i <- scalar_i * f mod r over the n terms of a resident MSM object (h2v_msm_scale, msm_object.hip: MSMKZG::scale, msm.rs:67-75), one
+// thread per term, in place.  The words are 8 canonical little-endian u32 per term (what the MSM reads, sstride 8); `factor` is f in
+// Montgomery form (f R, made once per call on the host), and the words' integer times f R under the Montgomery product is s f — the
+// identity k_guard_terms relies on for its multipliers.  Two 16-byte loads, ONE field product, canonical, two 16-byte stores; a thread
+// past n touches nothing.
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 30 VGPRs, 39 SGPRs, no spills, 48 bytes of scratch per lane (the call frame of the
+// field product), no LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_msm_scale(uint4* __restrict__ scalars, const Fr factor, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 s0 = scalars[2 * (size_t)i], s1 = scalars[2 * (size_t)i + 1];
+    uint32_t raw[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    Fr t;
+    Fr::pack29(t.v, raw);
+    const Fr prod = Fr::mul(t, factor);
+    uint32_t c[9];
+    prod.canonical(c);
+    Fr::unpack29(raw, c);
+    scalars[2 * (size_t)i] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+    scalars[2 * (size_t)i + 1] = make_uint4(raw[4], raw[5], raw[6], raw[7]);
+}
+
+// Affine Montgomery points -> canonical little-endian x | y, 64 bytes each, the identity as 64 zero bytes: the inverse of
+// k_bases_from_bytes, for the read-back of a resident MSM object's bases (h2v_msm_terms: MSMKZG::bases, msm.rs:88-90).  One thread per
+// point: x and y leave Montgomery form by one product with 1 each (to_raw), four 16-byte stores.  `out` lies on a 16-byte boundary
+// (the launcher checks); the points are read as they lie (a G1A is 72 bytes: word loads).
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 56 VGPRs, 39 SGPRs, no spills, 48 bytes of scratch per lane (the call frame of the
+// field product), no LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_affine_to_bytes(const G1A* __restrict__ in, uint4* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G1A a = in[i];
+    uint32_t w[16];
+    if (a.is_identity()) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) w[j] = 0;
+    } else { a.x.to_raw(w); a.y.to_raw(w + 8); }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[4 * (size_t)i + j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+}
+
 __global__ void k_point_to_bytes(const G1J* __restrict__ in, uint8_t* __restrict__ out, uint32_t* __restrict__ is_identity, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -290,6 +331,22 @@ int guard_terms_enqueue(hipStream_t s, const uint8_t* d_scalars32, const uint8_t
     if (!n) return 0;
     hipLaunchKernelGGL(k_guard_terms, dim3((n + 255) / 256), dim3(256), 0, s, (const uint4*)d_scalars32, (const uint4*)d_bases64, d_guard_of_term, d_mult, (uint4*)d_out_scalars, d_out_bases,
                        d_first_bad, n);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int msm_scale_enqueue(hipStream_t s, uint32_t* d_words, const Fr& factor, uint32_t n) {
+    if (!n) return 0;
+    if (!d_words) { set_last_error("msm_scale_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if ((uintptr_t)d_words & 15u) { set_last_error("msm_scale_enqueue: the words off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_msm_scale, dim3((n + 255) / 256), dim3(256), 0, s, (uint4*)d_words, factor, n);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int affine_to_bytes_enqueue(hipStream_t s, const G1A* d_in, uint8_t* d_out, uint32_t n) {
+    if (!n) return 0;
+    if (!d_in || !d_out) { set_last_error("affine_to_bytes_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if ((uintptr_t)d_out & 15u) { set_last_error("affine_to_bytes_enqueue: the bytes off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_affine_to_bytes, dim3((n + 255) / 256), dim3(256), 0, s, d_in, (uint4*)d_out, n);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -754,6 +754,20 @@ class Accumulator:
         if self._inputs:
             self._inputs.append(None)
 
+    def add_msms(self, dual):
+        """add_msm with both channels resident (h2v_accumulator_add_msms): dual is a DualMSM, or a pair (left, right) of MSMKZG objects,
+        either of which may be None (empty).  The two channels are evaluated in one pooled launch and added unscaled; counters, journal
+        entry and refusals are add_msm's."""
+        left, right = (dual.left, dual.right) if isinstance(dual, DualMSM) else tuple(dual)
+        for m in (left, right):
+            if m is not None and not isinstance(m, MSMKZG):
+                raise TypeError("add_msms takes a DualMSM or a pair of MSMKZG objects (or None)")
+        if not self._h:
+            raise ValueError("the accumulator is closed")
+        check(self._lib.h2v_accumulator_add_msms(self._h, left._handle() if left is not None else None, right._handle() if right is not None else None))
+        if self._inputs:
+            self._inputs.append(None)
+
     def read(self):
         """-> (left_xy, right_xy, n_proofs, n_failed): the two points as affine bytes (zeros = identity) and the counters"""
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
@@ -897,6 +911,198 @@ class Accumulator:
             contexts, keys, proofs, instances = kept
             out[e] = verify_batch_keys_identify(contexts, keys if keys is not None else [0] * len(proofs), proofs, instances)[1]
         return out
+
+
+class MSMKZG:
+    """A device-resident MSMKZG (h2v_msm): the (scalar, base) terms of the reference's MSM trait (poly/commitment.rs:56-79,
+    poly/kzg/msm.rs:17-95), kept on the context's GPU in the form the pooled MSM reads in place.  For term lists that live across calls;
+    the per-proof feeders (Accumulator.process, process_guards, process_batch) stay the fast paths.  Scalars are ints or 32-byte strings,
+    bases 64-byte x | y (all-zero = the identity).  At most 2^24 terms.  A call that raises H2VError leaves the object as it was.
+    `context` supplies the device, the params, the stream and the workspaces, and must outlive the object."""
+
+    MAX_TERMS = 1 << 24
+
+    def __init__(self, context: Context):
+        if not isinstance(context, Context):
+            raise TypeError("MSMKZG takes a Context")
+        self.ctx, self._lib = context, context._lib
+        self._h = ctypes.c_void_p()
+        check(self._lib.h2v_msm_create(context._h, ctypes.byref(self._h)))
+        context._adopt(self)
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the MSM object is closed")
+        return self._h
+
+    def close(self):
+        if self._h:
+            self._lib.h2v_msm_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        n = ctypes.c_size_t(0)
+        check(self._lib.h2v_msm_len(self._handle(), ctypes.byref(n)))
+        return n.value
+
+    def append_term(self, scalar, base):                       # msm.rs:57-60
+        self.append_terms([scalar], [base])
+
+    def append_terms(self, scalars, bases):
+        """append_term x n, in order (h2v_msm_append_terms).  A scalar >= r or a base that is not on the curve raises H2VError naming the
+        lowest bad term; the object is unchanged."""
+        h = self._handle()
+        sb, bb, n = _channel((scalars, bases))
+        check(self._lib.h2v_msm_append_terms(h, sb, bb, n))
+
+    def add_msm(self, other):                                  # msm.rs:62-65
+        """This object's terms, then other's, in order; other is not changed.  other is self raises H2VError."""
+        if not isinstance(other, MSMKZG):
+            raise TypeError("add_msm takes an MSMKZG")
+        check(self._lib.h2v_msm_add_msm(self._handle(), other._handle()))
+
+    def scale(self, factor):                                   # msm.rs:67-75
+        """Every scalar times factor mod r, applied at once: scalars() afterwards returns the scaled values."""
+        check(self._lib.h2v_msm_scale(self._handle(), _scalar32(factor)))
+
+    def _terms(self, first, count, want_scalars, want_bases):
+        h = self._handle()
+        n = len(self)
+        if count is None:
+            count = n - first
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError(f"terms [{first}, {first + count}) outside an object of {n}")
+        sc = ctypes.create_string_buffer(32 * max(count, 1)) if want_scalars else None
+        bs = ctypes.create_string_buffer(64 * max(count, 1)) if want_bases else None
+        check(self._lib.h2v_msm_terms(h, first, count, sc, bs))
+        return sc, bs, count
+
+    def scalars(self, first=0, count=None):                    # msm.rs:92-94
+        """-> the scalars of the terms [first, first + count) as ints"""
+        sc, _, k = self._terms(first, count, True, False)
+        return [int.from_bytes(sc.raw[32 * i:32 * i + 32], "little") for i in range(k)]
+
+    def bases(self, first=0, count=None):                      # msm.rs:88-90
+        """-> the bases of the terms [first, first + count) as 64-byte x | y (zeros = the identity)"""
+        _, bs, k = self._terms(first, count, False, True)
+        return _points(bs, k)
+
+    def eval(self):                                            # msm.rs:81-86
+        """-> 64-byte x | y (zeros = the identity).  One launch for one object: eval_many() takes many."""
+        return eval_many([self])[0][0]
+
+    def check(self):                                           # msm.rs:77-79
+        return eval_many([self])[1][0]
+
+    def clone(self):
+        """A new object with the same terms, independent of this one (create + add_msm)"""
+        self._handle()
+        m = MSMKZG(self.ctx)
+        try:
+            m.add_msm(self)
+        except Exception:
+            m.close()
+            raise
+        return m
+
+
+def _handles(msms, what):
+    msms = list(msms)
+    for m in msms:
+        if not isinstance(m, MSMKZG):
+            raise TypeError(f"{what} takes MSMKZG objects")
+    return msms, (ctypes.c_void_p * max(len(msms), 1))(*[m._handle() for m in msms])
+
+
+def eval_many(msms):
+    """MSMKZG::eval for k objects, one pooled launch per 1024 of them (h2v_msm_eval_many); the same object may occur more than once.
+    -> ([64-byte x | y], [is_identity: bool]): the points (zeros = the identity) and MSMKZG::check per object"""
+    msms, arr = _handles(msms, "eval_many")
+    k = len(msms)
+    if not k:
+        return [], []
+    out = ctypes.create_string_buffer(64 * k)
+    ident = (ctypes.c_int * k)()
+    check(msms[0]._lib.h2v_msm_eval_many(arr, k, out, ident))
+    return _points(out, k), [bool(v) for v in ident]
+
+
+class DualMSM:
+    """Two resident MSMKZG objects and the pairing (poly/kzg/msm.rs:146-204): e(left, s_g2) e(right, -g2) == 1.  Built empty over a
+    context, or from two existing objects (which it then owns)."""
+
+    def __init__(self, context: Context, left: MSMKZG = None, right: MSMKZG = None):
+        if (left is None) != (right is None):
+            raise ValueError("a DualMSM takes both channels or none")
+        self.ctx = context
+        self.left = left if left is not None else MSMKZG(context)
+        try:
+            self.right = right if right is not None else MSMKZG(context)
+        except Exception:
+            self.left.close()
+            raise
+
+    def close(self):
+        self.left.close()
+        self.right.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def scale(self, factor):                                   # msm.rs:173-177
+        """Both channels times factor.  The factor is checked before either channel changes."""
+        f = _scalar32(factor)
+        self.left._handle(), self.right._handle()
+        self.left.scale(f)
+        self.right.scale(f)
+
+    def add_msm(self, other):                                  # msm.rs:179-183
+        """other: a DualMSM, or a Guard as Accumulator.process_guards takes it — ((left_scalars, left_bases), (right_scalars,
+        right_bases)) or the dict Context.guard_msm returns — whose terms are appended."""
+        if isinstance(other, DualMSM):
+            self.left.add_msm(other.left)
+            self.right.add_msm(other.right)
+            return
+        l, r = _guard_sides(other)
+        l, r = _channel(l, "left "), _channel(r, "right ")    # (both checked before either channel changes)
+        check(self.left._lib.h2v_msm_append_terms(self.left._handle(), *l))
+        check(self.right._lib.h2v_msm_append_terms(self.right._handle(), *r))
+
+    def check(self):                                           # msm.rs:185-203
+        return dual_check_many([self])[0][0]
+
+
+def dual_check_many(duals):
+    """DualMSM::check for k objects: per 512 of them one pooled MSM over the 2 k channels and one pairing launch
+    (h2v_dual_msm_check_many).  -> ([ok: bool], [left_xy], [right_xy]): the raw pairing bit and the evaluated channels per object"""
+    duals = list(duals)
+    for d in duals:
+        if not isinstance(d, DualMSM):
+            raise TypeError("dual_check_many takes DualMSM objects")
+    k = len(duals)
+    if not k:
+        return [], [], []
+    _, lefts = _handles([d.left for d in duals], "dual_check_many")
+    _, rights = _handles([d.right for d in duals], "dual_check_many")
+    ok = (ctypes.c_int * k)()
+    left, right = ctypes.create_string_buffer(64 * k), ctypes.create_string_buffer(64 * k)
+    check(duals[0].left._lib.h2v_dual_msm_check_many(lefts, rights, k, ok, left, right))
+    return [bool(v) for v in ok], _points(left, k), _points(right, k)
 
 
 def _range_args(ranges, names, types):

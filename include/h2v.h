@@ -387,6 +387,56 @@ int h2v_accumulator_export_state(h2v_accumulator* a, uint8_t out[H2V_ACC_STATE_B
  *   serves: DualMSM::scale, DualMSM::add_msm (poly/kzg/msm.rs:173-183), AccumulatorStrategy::with (poly/kzg/strategy.rs:76-78). */
 int h2v_accumulator_merge_states(h2v_accumulator* dst, const uint8_t* states, size_t n, const uint8_t* draws32, uint8_t* out_draws32);
 
+/* A device-resident MSMKZG: the (scalar, base) terms of the reference's MSM trait (poly/commitment.rs:56-79) as MSMKZG holds them
+ * (poly/kzg/msm.rs:17-21), kept on the context's GPU in the form the pooled MSM reads in place.  For term lists that live across calls —
+ * a GuardKZG::msm_accumulator to manipulate, an AccumulatorStrategy::with(msm) to resume, the Guards of many proofs combined under the
+ * caller's own scheme; the per-proof feeders (h2v_accumulator_process, _process_guards, _process_batch) stay the fast paths.
+ *   - An object holds at most 2^24 terms (H2V_ERR_BAD_ARGUMENT beyond).  Scalars 32-byte canonical, bases 64-byte x | y on the curve,
+ *     all-zero = the identity.
+ *   - Commit rule: a call that returns non-zero leaves every object it was given exactly as it was (length, contents, read-back).
+ *   - Every call takes the lock of the objects' contexts, runs on the context's stream with the context's workspaces (an object owns its
+ *     two term arrays and nothing else: there may be one per Guard) and returns with that stream idle.  The objects of one call share the
+ *     device and the params (g[0], g2, s_g2), else H2V_ERR_BAD_ARGUMENT before any device work.  An object is used from one thread at a
+ *     time and is destroyed before its context.
+ *   - Evaluation is offered for MANY objects per call (K objects = K problems of one pooled MSM launch, at most 1024 problems or 512
+ *     pairs per launch): the reference builds many tiny MSMs, and a launch per tiny object would be a bad trade. */
+typedef struct h2v_msm h2v_msm;
+/*   replaces: MSMKZG::new (poly/kzg/msm.rs:25-30): no term. */
+int h2v_msm_create(h2v_ctx* ctx, h2v_msm** out);
+void h2v_msm_destroy(h2v_msm* m);
+/* n x MSM::append_term, in order (msm.rs:57-60).  A scalar >= r, or a base that is neither all-zero nor a canonical point on the curve, is
+ * H2V_ERR_BAD_ARGUMENT (checked on the device): h2v_last_error names the lowest bad term ("term i"), and the object is unchanged.  n = 0 is
+ * a no-op. */
+int h2v_msm_append_terms(h2v_msm* m, const uint8_t* scalars32, const uint8_t* bases64, size_t n);
+/*   replaces: MSM::add_msm (msm.rs:62-65): dst's terms, then src's, in order; src is not changed.  dst == src is H2V_ERR_BAD_ARGUMENT (the
+ * reference's borrow rules forbid it); an empty src is a no-op. */
+int h2v_msm_add_msm(h2v_msm* dst, const h2v_msm* src);
+/*   replaces: MSM::scale (msm.rs:67-75): scalar_i <- scalar_i * factor mod r for every term, applied at once (h2v_msm_terms afterwards
+ * returns the scaled values, as the reference's scalars() does).  A factor >= r is H2V_ERR_BAD_ARGUMENT; 0 is allowed (every scalar
+ * becomes 0, the terms stay); an empty object is a no-op. */
+int h2v_msm_scale(h2v_msm* m, const uint8_t factor32[32]);
+/* The number of terms. */
+int h2v_msm_len(const h2v_msm* m, size_t* n);
+/*   replaces: MSM::scalars, MSM::bases (msm.rs:88-94) over the terms [first, first + count): count x 32 and count x 64 canonical bytes.
+ * Either output may be NULL.  A range outside the object is H2V_ERR_BAD_ARGUMENT; nothing is written on an error. */
+int h2v_msm_terms(h2v_msm* m, size_t first, size_t count, uint8_t* scalars32, uint8_t* bases64);
+/*   replaces: MSM::eval + to_affine (msm.rs:81-86) for k objects, and MSM::check (msm.rs:77-79): out_is_identity[i].
+ * out_xy: k x 64 bytes; an empty object evaluates to the identity (all-zero bytes, flag 1).  Either output may be NULL.  The same object
+ * may occur more than once.  Runs in launches of at most 1024 problems, one synchronise each, the MSM reading the objects' own arrays
+ * (no copy, no conversion).  Nothing is written on an error. */
+int h2v_msm_eval_many(h2v_msm* const* msms, size_t k, uint8_t* out_xy, int* out_is_identity);
+/*   replaces: DualMSM::check (msm.rs:185-203) for k pairs (lefts[i], rights[i]): per launch of at most 512 pairs one pooled MSM over the
+ * 2 K problems, one pairing launch over the K pairs, one copy of K verdict words.  ok[i] is the raw bit of e(L_i, s_g2) e(R_i, -g2) == 1
+ * (two empty channels: 1); out_left_xy / out_right_xy (k x 64 bytes each, either may be NULL) are the evaluated channels.
+ * lefts[i] == rights[i] is allowed.  Nothing is written on an error. */
+int h2v_dual_msm_check_many(h2v_msm* const* lefts, h2v_msm* const* rights, size_t k,
+                            int* ok, uint8_t* out_left_xy, uint8_t* out_right_xy);
+/* h2v_accumulator_add_msm with both channels resident: left and right are evaluated in one pooled launch and added unscaled, with the
+ * counters, the journal entry and the refusals of h2v_accumulator_add_msm (a full journal: H2V_ERR_UNSUPPORTED before any device work).
+ * Either channel may be NULL (empty).  The objects lie on the accumulator's device, over its params.
+ *   replaces: AccumulatorStrategy::with(msm_accumulator) (poly/kzg/strategy.rs:76-78), DualMSM::add_msm (poly/kzg/msm.rs:179-183). */
+int h2v_accumulator_add_msms(h2v_accumulator* a, h2v_msm* left, h2v_msm* right);
+
 /* N x verify_proof under SingleStrategy (one pairing per proof; poly/kzg/strategy.rs:164-176).
  * per_proof_status[i] = 0, or H2V_ERR_CONSTRAINT_SYSTEM_FAILURE when that proof's pairing fails,
  * or the transcript/opening error. */

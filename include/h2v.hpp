@@ -19,6 +19,8 @@
 //     finalize when the caller decides, with)  kzg/strategy.rs:69-140   two points resident on the GPU; add_msm(), read(), finalize()
 //   the same two strategies handed the Guards of a verify_proof   Accumulator::process_guards(guards, rand32), check_guards(context, guards):
 //     that ran on the CPU       kzg/strategy.rs:125-136, 164-176     a Guard is the two term lists of its DualMSM
+//   MSM trait: MSMKZG, DualMSM    poly/commitment.rs:56-79,       Msm(context), DualMsm(context): the terms resident on the GPU; append_terms, add_msm,
+//                                 kzg/msm.rs:17-95, 146-204         scale, scalars, bases; Msm::eval_many, DualMsm::check_many, Accumulator::add_msms
 //   VerifierSHPLONK / VerifierGWC, Blake2bRead / Keccak256Read    MultiOpen, TranscriptKind (generic parameters of lib.rs:33-40)
 //
 // There is no CPU fallback: constructing a Context without a HIP device throws Failure{H2V_ERR_DEVICE}.
@@ -84,6 +86,88 @@ private:
 // The Guard a CPU verify_proof returns (kzg/strategy.rs:164-176: its DualMSM), as two term lists: scalars 32 bytes each, bases 64 bytes
 // (x | y, all-zero = the identity) each; either side may be empty
 struct Guard { Bytes left_scalars, left_bases, right_scalars, right_bases; };
+
+// A device-resident MSMKZG (h2v_msm): the reference's MSM trait (poly/commitment.rs:56-79, poly/kzg/msm.rs:17-95) over terms kept on the
+// context's GPU.  Move-only; the context must outlive the object.  Scalars 32 bytes each, bases 64 bytes (x | y, all-zero = the identity)
+// each.  A Failure leaves the object as it was.  Evaluation is offered for many objects per launch: eval_many.
+class Msm {
+public:
+    struct Evaluated { Bytes xy; std::vector<bool> is_identity; };   // k x 64 bytes, and MSMKZG::check per object
+    explicit Msm(const Context& ctx) : ctx_(ctx.handle()) { halo2_verifier::check(h2v_msm_create(ctx_, &h_)); }
+    ~Msm() { h2v_msm_destroy(h_); }
+    Msm(const Msm&) = delete;
+    Msm& operator=(const Msm&) = delete;
+    Msm(Msm&& o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Msm& operator=(Msm&& o) noexcept { if (this != &o) { h2v_msm_destroy(h_); ctx_ = o.ctx_; h_ = o.h_; o.h_ = nullptr; } return *this; }
+    h2v_msm* handle() const { return h_; }
+    size_t size() const { size_t n = 0; halo2_verifier::check(h2v_msm_len(live(), &n)); return n; }
+    void append_term(const Bytes& scalar32, const Bytes& base64) { append_terms(scalar32, base64); }                      // msm.rs:57-60
+    void append_terms(const Bytes& scalars, const Bytes& bases) {
+        if (scalars.size() % 32 || bases.size() != 2 * scalars.size()) throw Failure(H2V_ERR_BAD_ARGUMENT, "terms are n 32-byte scalars and n 64-byte bases");
+        halo2_verifier::check(h2v_msm_append_terms(live(), scalars.data(), bases.data(), scalars.size() / 32));
+    }
+    void add_msm(const Msm& other) { halo2_verifier::check(h2v_msm_add_msm(live(), other.live())); }                                      // msm.rs:62-65
+    void scale(const Bytes& factor32) {                                                                                   // msm.rs:67-75
+        if (factor32.size() != 32) throw Failure(H2V_ERR_BAD_ARGUMENT, "a factor is 32 bytes");
+        halo2_verifier::check(h2v_msm_scale(live(), factor32.data()));
+    }
+    Bytes scalars() const { const size_t n = size(); Bytes s(32 * n); halo2_verifier::check(h2v_msm_terms(h_, 0, n, s.data(), nullptr)); return s; }   // msm.rs:92-94
+    Bytes bases() const { const size_t n = size(); Bytes b(64 * n); halo2_verifier::check(h2v_msm_terms(h_, 0, n, nullptr, b.data())); return b; }     // msm.rs:88-90
+    Bytes eval() const { return eval_many({this}).xy; }                                                                   // msm.rs:81-86
+    bool check() const      { return eval_many({this}).is_identity[0]; }                                                  // MSM::check, msm.rs:77-79
+    Msm clone() const { Msm c(ctx_, nullptr); c.add_msm(*this); return c; }   // create + add_msm: independent of its source
+    // MSM::eval for k objects, one pooled launch per 1024 of them; the same object may occur more than once
+    static Evaluated eval_many(const std::vector<const Msm*>& msms) {
+        Evaluated e;
+        if (msms.empty()) return e;
+        std::vector<h2v_msm*> hs;
+        for (const Msm* m : msms) { if (!m) throw Failure(H2V_ERR_BAD_ARGUMENT, "null object"); hs.push_back(m->live()); }
+        e.xy.resize(64 * hs.size());
+        std::vector<int> ident(hs.size(), 0);
+        halo2_verifier::check(h2v_msm_eval_many(hs.data(), hs.size(), e.xy.data(), ident.data()));
+        for (int v : ident) e.is_identity.push_back(v != 0);
+        return e;
+    }
+
+private:
+    Msm(h2v_ctx* ctx, std::nullptr_t) : ctx_(ctx) { halo2_verifier::check(h2v_msm_create(ctx_, &h_)); }
+    h2v_msm* live() const { if (!h_) throw Failure(H2V_ERR_BAD_ARGUMENT, "a moved-from Msm"); return h_; }
+    h2v_ctx* ctx_ = nullptr;
+    h2v_msm* h_ = nullptr;
+};
+
+// DualMSM (poly/kzg/msm.rs:146-204): two resident channels and the pairing e(left, s_g2) e(right, -g2) == 1.  Move-only.
+class DualMsm {
+public:
+    struct Checked { std::vector<bool> ok; Bytes lefts, rights; };   // per object the raw pairing bit and the evaluated channels (k x 64 bytes each)
+    explicit DualMsm(const Context& ctx) : left(ctx), right(ctx) {}
+    DualMsm(Msm&& l, Msm&& r) : left(std::move(l)), right(std::move(r)) {}
+    DualMsm(DualMsm&&) = default;
+    DualMsm& operator=(DualMsm&&) = default;
+    Msm left, right;
+    void scale(const Bytes& factor32) {                                                                                   // msm.rs:173-177
+        if (factor32.size() != 32) throw Failure(H2V_ERR_BAD_ARGUMENT, "a factor is 32 bytes");
+        left.scale(factor32); right.scale(factor32);
+    }
+    void add_msm(const DualMsm& other) { left.add_msm(other.left); right.add_msm(other.right); }                          // msm.rs:179-183
+    void add_guard(const Guard& g) { left.append_terms(g.left_scalars, g.left_bases); right.append_terms(g.right_scalars, g.right_bases); }
+    bool check() const { return check_many({this}).ok[0]; }                                                               // msm.rs:185-203
+    // DualMSM::check for k objects: per 512 of them one pooled MSM over the 2 k channels and one pairing launch
+    static Checked check_many(const std::vector<const DualMsm*>& duals) {
+        Checked c;
+        if (duals.empty()) return c;
+        std::vector<h2v_msm*> ls, rs;
+        for (const DualMsm* d : duals) {
+            if (!d || !d->left.handle() || !d->right.handle()) throw Failure(H2V_ERR_BAD_ARGUMENT, "a null or moved-from DualMsm");
+            ls.push_back(d->left.handle()); rs.push_back(d->right.handle());
+        }
+        std::vector<int> ok(duals.size(), 0);
+        c.lefts.resize(64 * duals.size()); c.rights.resize(64 * duals.size());
+        halo2_verifier::check(h2v_dual_msm_check_many(ls.data(), rs.data(), duals.size(), ok.data(), c.lefts.data(), c.rights.data()));
+        for (int v : ok) c.ok.push_back(v != 0);
+        return c;
+    }
+};
 
 namespace detail {
 // The arguments of a call in the layout the C ABI takes: a context per key, then every proof in call order with its key and its column
@@ -293,6 +377,12 @@ public:
         detail::check_channels(left_scalars, left_bases, right_scalars, right_bases, "a channel is n 32-byte scalars and n 64-byte bases");
         check(h2v_accumulator_add_msm(h_, left_scalars.data(), left_bases.data(), left_scalars.size() / 32, right_scalars.data(), right_bases.data(),
                                       right_scalars.size() / 32));
+    }
+    // add_msm with both channels resident (h2v_accumulator_add_msms): evaluated in one pooled launch, added unscaled
+    void add_msms(const DualMsm& msm) { add_msms(&msm.left, &msm.right); }
+    void add_msms(const Msm* left, const Msm* right) {   // either may be null: empty
+        if ((left && !left->handle()) || (right && !right->handle())) throw Failure(H2V_ERR_BAD_ARGUMENT, "a moved-from Msm");
+        check(h2v_accumulator_add_msms(h_, left ? left->handle() : nullptr, right ? right->handle() : nullptr));
     }
     // n x (scale by the draw, add the Guard): AccumulatorStrategy::process at the trait seam (kzg/strategy.rs:125-136), the Guards made by a CPU
     // verify_proof.  rand32: one 32-byte canonical draw per guard; empty = OS RNG.  Equals process() over the proofs the Guards came from.
@@ -510,3 +600,4 @@ inline AccumulatorStrategy& verify_proof(const ParamsKZG&, const VerifyingKey& v
 }
 
 }  // namespace halo2_verifier
+namespace h2v = halo2_verifier;   // the short name: h2v::Msm, h2v::DualMsm, ...

@@ -8,6 +8,7 @@ use core::ffi::{c_char, c_float, c_int, c_void};
 #[repr(C)] pub struct h2v_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct h2v_batch { _p: [u8; 0] }
 #[repr(C)] pub struct h2v_accumulator { _p: [u8; 0] }
+#[repr(C)] pub struct h2v_msm { _p: [u8; 0] }
 /// struct_size: `core::mem::size_of::<h2v_options>()` (the library rejects a layout it does not know);
 /// multiopen: VerifierSHPLONK / VerifierGWC; transcript: Blake2bRead / Keccak256Read; circuit_instances: `instances.len()` of
 /// verify_proof (0 or 1 = one circuit instance per transcript); instance_kernel_threshold: debug, 0 = default
@@ -109,6 +110,17 @@ extern "C" {
     pub fn h2v_accumulator_merge(dst: *mut h2v_accumulator, srcs: *const *mut h2v_accumulator, n_src: usize, draws32: *const u8, out_draws32: *mut u8) -> c_int;
     pub fn h2v_accumulator_export_state(a: *mut h2v_accumulator, out: *mut u8) -> c_int;
     pub fn h2v_accumulator_merge_states(dst: *mut h2v_accumulator, states: *const u8, n: usize, draws32: *const u8, out_draws32: *mut u8) -> c_int;
+    pub fn h2v_msm_create(ctx: *mut h2v_ctx, out: *mut *mut h2v_msm) -> c_int;
+    pub fn h2v_msm_destroy(m: *mut h2v_msm);
+    pub fn h2v_msm_append_terms(m: *mut h2v_msm, scalars32: *const u8, bases64: *const u8, n: usize) -> c_int;
+    pub fn h2v_msm_add_msm(dst: *mut h2v_msm, src: *const h2v_msm) -> c_int;
+    pub fn h2v_msm_scale(m: *mut h2v_msm, factor32: *const u8) -> c_int;
+    pub fn h2v_msm_len(m: *const h2v_msm, n: *mut usize) -> c_int;
+    pub fn h2v_msm_terms(m: *mut h2v_msm, first: usize, count: usize, scalars32: *mut u8, bases64: *mut u8) -> c_int;
+    pub fn h2v_msm_eval_many(msms: *const *mut h2v_msm, k: usize, out_xy: *mut u8, out_is_identity: *mut c_int) -> c_int;
+    pub fn h2v_dual_msm_check_many(lefts: *const *mut h2v_msm, rights: *const *mut h2v_msm, k: usize, ok: *mut c_int, out_left_xy: *mut u8,
+                                   out_right_xy: *mut u8) -> c_int;
+    pub fn h2v_accumulator_add_msms(a: *mut h2v_accumulator, left: *mut h2v_msm, right: *mut h2v_msm) -> c_int;
     pub fn h2v_verify_each(ctx: *mut h2v_ctx, n: usize, proofs: *const *const u8, proof_lens: *const usize,
                            instances32: *const *const u8, n_instance_columns: usize, col_lens: *const usize, per_proof_status: *mut c_int) -> c_int;
     pub fn h2v_verify_batches(ctx: *mut h2v_ctx, n_batches: usize, batch_sizes: *const usize, proofs: *const *const u8, proof_lens: *const usize,

@@ -18,6 +18,8 @@
 //! * `GpuAccumulatorStrategy`  — trait seam: `impl VerificationStrategy` (poly/strategy.rs:12-31) over a resident accumulator:
 //!                               `verify_proof` itself stays on the CPU, every Guard it returns is scaled in and added on the GPU
 //!                               (h2v_accumulator_process_guards), `finalize` is the one pairing there.
+//! * `GpuMsm`, `GpuDualMsm`    — the `MSM` trait row: `impl MSM<G1Affine>` over a term list resident on the GPU (h2v_msm_*), and the
+//!                               two-channel object with the pairing; evaluation and check for many objects per launch.
 use super::ffi::*;
 use crate::{
     helpers::SerdeFormat,
@@ -30,7 +32,7 @@ use crate::{
     VerifyingKey,
 };
 use ff::{Field, PrimeField};
-use group::Curve;
+use group::{prime::PrimeCurveAffine, Curve, Group};
 use halo2curves::bn256::{Bn256, Fr, G1Affine};
 use halo2curves::CurveAffine;
 
@@ -477,5 +479,129 @@ impl<'params> Drop for GpuAccumulatorStrategy<'params> {
     fn drop(&mut self) {
         unsafe { h2v_accumulator_destroy(self.acc) }   // (the accumulator goes before the context it lives on; null is allowed)
         if !self.ctx.is_null() { unsafe { h2v_ctx_destroy(self.ctx) } }
+    }
+}
+
+/// The reference's `MSM<G1Affine>` (poly/commitment.rs:56-79) as `MSMKZG` implements it (poly/kzg/msm.rs:17-95), with the terms resident
+/// on the GPU (h2v_msm_*): hold one where a term list lives across calls — a `GuardKZG::msm_accumulator` to manipulate, an
+/// `AccumulatorStrategy::with(msm)` to resume, Guards combined under the caller's own scheme.  Where Guards are only fed once, feed them
+/// (`GpuResidentAccumulator::process_guards`): that is the faster path.  The trait's methods cannot fail, so a refused call panics with
+/// the library's code; `ctx` outlives the object.  Evaluating MANY objects per launch is `GpuMsm::eval_many`.
+#[derive(Debug)]
+pub struct GpuMsm { ctx: *mut h2v_ctx, m: *mut h2v_msm }
+unsafe impl Send for GpuMsm {}
+unsafe impl Sync for GpuMsm {}
+
+fn point_from_xy(xy: &[u8]) -> <G1Affine as CurveAffine>::CurveExt {
+    if xy.iter().all(|&b| b == 0) { return <G1Affine as CurveAffine>::CurveExt::identity(); }
+    let (mut x, mut y) = (<<G1Affine as CurveAffine>::Base as PrimeField>::Repr::default(), <<G1Affine as CurveAffine>::Base as PrimeField>::Repr::default());
+    x.as_mut().copy_from_slice(&xy[..32]); y.as_mut().copy_from_slice(&xy[32..64]);
+    let (x, y) = (<G1Affine as CurveAffine>::Base::from_repr(x).unwrap(), <G1Affine as CurveAffine>::Base::from_repr(y).unwrap());
+    G1Affine::from_xy(x, y).unwrap().to_curve()
+}
+
+impl GpuMsm {
+    /// `MSMKZG::new()`: no term.
+    pub fn new(ctx: *mut h2v_ctx) -> Result<Self, Error> {
+        let mut m = core::ptr::null_mut();
+        let rc = unsafe { h2v_msm_create(ctx, &mut m) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(Self { ctx, m })
+    }
+    pub fn len(&self) -> usize {
+        let mut n = 0usize;
+        let rc = unsafe { h2v_msm_len(self.m, &mut n) };
+        assert_eq!(rc, 0, "h2v_msm_len");
+        n
+    }
+    /// `append_term` x n in one call; an `Err` (a base off the curve) leaves the object as it was.
+    pub fn append_terms(&mut self, terms: &[(Fr, G1Affine)]) -> Result<(), Error> {
+        let (s, b) = flat_terms(terms);
+        let rc = unsafe { h2v_msm_append_terms(self.m, s.as_ptr(), b.as_ptr(), terms.len()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
+    }
+    /// `eval` for many objects, one pooled launch per 1024 of them: the points and `check` (is the identity) per object.
+    pub fn eval_many(msms: &[&GpuMsm]) -> Result<Vec<(<G1Affine as CurveAffine>::CurveExt, bool)>, Error> {
+        let hs: Vec<*mut h2v_msm> = msms.iter().map(|m| m.m).collect();
+        let (mut xy, mut ident) = (vec![0u8; 64 * hs.len()], vec![0i32; hs.len()]);
+        let rc = unsafe { h2v_msm_eval_many(hs.as_ptr(), hs.len(), xy.as_mut_ptr(), ident.as_mut_ptr()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok((0..hs.len()).map(|i| (point_from_xy(&xy[64 * i..64 * i + 64]), ident[i] == 1)).collect())
+    }
+    pub fn handle(&self) -> *mut h2v_msm { self.m }
+}
+
+impl Clone for GpuMsm {
+    /// create + add_msm: the copy is independent of its source
+    fn clone(&self) -> Self {
+        let mut c = GpuMsm::new(self.ctx).expect("h2v_msm_create");
+        MSM::<G1Affine>::add_msm(&mut c, self);
+        c
+    }
+}
+
+impl MSM<G1Affine> for GpuMsm {
+    fn append_term(&mut self, scalar: Fr, point: <G1Affine as CurveAffine>::CurveExt) {
+        self.append_terms(&[(scalar, point.to_affine())]).expect("h2v_msm_append_terms");
+    }
+    fn add_msm(&mut self, other: &Self) {
+        let rc = unsafe { h2v_msm_add_msm(self.m, other.m) };
+        assert_eq!(rc, 0, "h2v_msm_add_msm");
+    }
+    fn scale(&mut self, factor: Fr) {
+        let rc = unsafe { h2v_msm_scale(self.m, factor.to_repr().as_ref().as_ptr()) };
+        assert_eq!(rc, 0, "h2v_msm_scale");
+    }
+    fn check(&self) -> bool { GpuMsm::eval_many(&[self]).expect("h2v_msm_eval_many")[0].1 }
+    fn eval(&self) -> <G1Affine as CurveAffine>::CurveExt { GpuMsm::eval_many(&[self]).expect("h2v_msm_eval_many")[0].0 }
+    fn bases(&self) -> Vec<<G1Affine as CurveAffine>::CurveExt> {
+        let n = self.len();
+        let mut b = vec![0u8; 64 * n];
+        let rc = unsafe { h2v_msm_terms(self.m, 0, n, core::ptr::null_mut(), b.as_mut_ptr()) };
+        assert_eq!(rc, 0, "h2v_msm_terms");
+        (0..n).map(|i| point_from_xy(&b[64 * i..64 * i + 64])).collect()
+    }
+    fn scalars(&self) -> Vec<Fr> {
+        let n = self.len();
+        let mut s = vec![0u8; 32 * n];
+        let rc = unsafe { h2v_msm_terms(self.m, 0, n, s.as_mut_ptr(), core::ptr::null_mut()) };
+        assert_eq!(rc, 0, "h2v_msm_terms");
+        (0..n).map(|i| { let mut r = <Fr as PrimeField>::Repr::default(); r.as_mut().copy_from_slice(&s[32 * i..32 * i + 32]); Fr::from_repr(r).unwrap() }).collect()
+    }
+}
+impl Drop for GpuMsm { fn drop(&mut self) { unsafe { h2v_msm_destroy(self.m) } } }   // (before its context; null is allowed)
+
+/// `DualMSM` (poly/kzg/msm.rs:146-204) over two resident channels.  `check` borrows where the reference consumes: the object may be
+/// scaled, extended and checked again.  Many at once: `GpuDualMsm::check_many`.
+#[derive(Debug, Clone)]
+pub struct GpuDualMsm { pub left: GpuMsm, pub right: GpuMsm }
+
+impl GpuDualMsm {
+    pub fn new(ctx: *mut h2v_ctx) -> Result<Self, Error> { Ok(Self { left: GpuMsm::new(ctx)?, right: GpuMsm::new(ctx)? }) }
+    pub fn scale(&mut self, e: Fr) { self.left.scale(e); self.right.scale(e); }
+    pub fn add_msm(&mut self, other: &Self) {
+        MSM::<G1Affine>::add_msm(&mut self.left, &other.left);
+        MSM::<G1Affine>::add_msm(&mut self.right, &other.right);
+    }
+    pub fn check(&self) -> Result<bool, Error> { Ok(Self::check_many(&[self])?[0]) }
+    /// `DualMSM::check` for many objects: per 512 of them one pooled MSM over the 2 k channels and one pairing launch.
+    pub fn check_many(duals: &[&GpuDualMsm]) -> Result<Vec<bool>, Error> {
+        let ls: Vec<*mut h2v_msm> = duals.iter().map(|d| d.left.m).collect();
+        let rs: Vec<*mut h2v_msm> = duals.iter().map(|d| d.right.m).collect();
+        let mut ok = vec![0i32; duals.len()];
+        let rc = unsafe { h2v_dual_msm_check_many(ls.as_ptr(), rs.as_ptr(), duals.len(), ok.as_mut_ptr(), core::ptr::null_mut(), core::ptr::null_mut()) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(ok.iter().map(|&v| v == 1).collect())
+    }
+}
+// (Drop: the two channels' own)
+
+impl GpuResidentAccumulator {
+    /// `add_msm` with both channels resident (h2v_accumulator_add_msms): evaluated in one pooled launch, added unscaled.
+    pub fn add_msms(&mut self, msm: &GpuDualMsm) -> Result<(), Error> {
+        let rc = unsafe { h2v_accumulator_add_msms(self.acc, msm.left.m, msm.right.m) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
     }
 }
