@@ -726,6 +726,7 @@ int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const ui
         // reorder squeeze order -> [user challenges.., theta, beta, gamma, y, x, y', v, u]
         size_t nc = pl.n_challenges;
         if (nc > *n_challenges) { set_last_error("h2v_guard_msm: challenge capacity too small"); return H2V_ERR_BAD_ARGUMENT; }
+        memset(challenges32, 0, 32 * nc);   // a user challenge that is never squeezed stays zero, as in the reference (lib.rs:89-108)
         for (size_t q = 0; q < chal.size(); ++q) chal[q].to_bytes(challenges32 + 32 * pl.squeeze_order[q]);
         *n_challenges = nc;
     }

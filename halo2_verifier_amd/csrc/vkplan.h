@@ -91,7 +91,8 @@ struct Plan {
     // transcript
     std::vector<TranscriptSrc> stream;     // absorbed byte stream incl. the 0x00 challenge markers
     std::vector<uint32_t> squeeze_at;      // stream length at which the i-th squeeze happens
-    std::vector<uint32_t> squeeze_order;   // challenge id of the i-th squeeze (a user challenge of a phase no advice column has is never squeezed)
+    std::vector<uint32_t> squeeze_order;   // challenge id of the i-th squeeze; a user challenge of a phase above every advice column's is never
+                                           // squeezed and has no entry: the program reads it as the constant zero, h2v_guard_msm reports zero
     uint32_t n_challenges = 0;             // user challenges + theta, beta, gamma, y, x, y', v, u
     uint32_t n_user_challenges = 0;
     // program

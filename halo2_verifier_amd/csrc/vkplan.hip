@@ -771,9 +771,12 @@ void lay_out_multiopen(const Shape& s, const Opening& op, Transcript& tr, VkLayo
 // ---------------- the Fr program
 struct Challenges { std::vector<Val> user; Val theta, beta, gamma, y, x, sy, sv, su, xn, xn_m1; };
 Challenges load_challenges(Builder& b, const Shape& s, const Plan& plan, uint32_t k) {
-    std::vector<uint32_t> sq_of(plan.n_challenges, 0);   // challenge id -> position in squeeze order
+    const uint32_t NEVER = (uint32_t)-1;
+    std::vector<uint32_t> sq_of(plan.n_challenges, NEVER);   // challenge id -> position in squeeze order
     for (size_t q = 0; q < plan.squeeze_order.size(); ++q) sq_of[plan.squeeze_order[q]] = (uint32_t)q;
-    auto chal = [&](uint32_t id) { return b.load_chal(sq_of[id]); };
+    // a user challenge of a phase above every advice column's is never squeezed: it keeps the value the reference's challenge
+    // vector starts with, zero (lib.rs:89-108)
+    auto chal = [&](uint32_t id) { return sq_of[id] == NEVER ? b.zero() : b.load_chal(sq_of[id]); };
     Challenges c;
     for (size_t i = 0; i < s.Ch; ++i) c.user.push_back(chal((uint32_t)i));
     c.theta = chal(s.C_THETA); c.beta = chal(s.C_BETA); c.gamma = chal(s.C_GAMMA); c.y = chal(s.C_Y); c.x = chal(s.C_X); c.sv = chal(s.C_SV); c.su = chal(s.C_SU);

@@ -33,7 +33,7 @@ struct Setup {
     int multiopen = 0, transcript = 0;   // options of the prover side (h2o_setup_set_options)
     CommitKey ck;
     ProvingKey pk;
-    int kind;  // 0 vector_mul, 1 two-phase shuffle, 2 wide
+    int kind;  // 0 vector_mul, 1 two-phase shuffle, 2 wide, 3 generated
     size_t n_mul, W, H;
     u64 wide_seed;
 };
@@ -210,6 +210,18 @@ void* h2o_setup_shuffle(uint32_t k, size_t W, size_t H, const uint8_t* srs, size
 void* h2o_setup_wide(uint32_t k, size_t A, size_t F, size_t L, size_t Sh, uint32_t deg, uint64_t seed, const uint8_t* srs, size_t srs_len, uint64_t s_seed) {
     try { Setup* s = make_setup(circuit_wide(k, A, F, L, Sh, deg, seed), srs, srs_len, s_seed); if (s) { s->kind = 2; s->wide_seed = seed; } return s; } catch (...) { return nullptr; }
 }
+// a circuit whose whole shape is drawn from `seed` (prover.hpp: circuit_generated)
+void* h2o_setup_generated(uint32_t k, uint64_t seed, const uint8_t* srs, size_t srs_len, uint64_t s_seed) {
+    try { Setup* s = make_setup(circuit_generated(k, seed), srs, srs_len, s_seed); if (s) s->kind = 3; return s; } catch (...) { return nullptr; }
+}
+// GenFeature bits of a generated setup's circuit (0 for the other families)
+uint64_t h2o_setup_features(void* h) { return ((Setup*)h)->pk.circuit.gen.features; }
+// a generated setup's instance column lengths: returns their count, writes at most cap of them
+size_t h2o_setup_col_lens(void* h, size_t* out, size_t cap) {
+    const std::vector<size_t>& l = ((Setup*)h)->pk.circuit.gen.inst_lens;
+    for (size_t j = 0; j < l.size() && j < cap; ++j) out[j] = l[j];
+    return l.size();
+}
 void h2o_setup_free(void* h) { delete (Setup*)h; }
 void h2o_setup_set_options(void* h, int multiopen, int transcript) { ((Setup*)h)->multiopen = multiopen; ((Setup*)h)->transcript = transcript; }
 // verifier-side options for every h2o_verify_* / h2o_guard_msm call of this thread (0/0 = SHPLONK + Blake2b)
@@ -329,6 +341,28 @@ size_t h2o_prove_wide_multi(void* h, size_t M, uint64_t witness_seed, int tamper
     }
     Rng rng(rng_seed);
     return copy_out(create_proof_multi(s->pk, s->ck, insts, ws, rng, s->multiopen, s->transcript), proof, cap);
+}
+// M instances of a generated circuit in one transcript (witness_seed + 7919 q each); tamper_at in [0, M) changes one result cell of
+// that instance, -1 none.  col_lens_out receives the circuit's instance column lengths (one per column), instances_out the M x
+// columns public inputs, instance-major; either may be NULL.
+size_t h2o_prove_generated(void* h, size_t M, uint64_t witness_seed, int tamper_at, uint64_t rng_seed, uint8_t* proof, size_t cap, uint8_t* instances_out, size_t* col_lens_out) {
+    Setup* s = (Setup*)h;
+    if (s->kind != 3) return 0;
+    try {
+        const Circuit& c = s->pk.circuit;
+        std::vector<std::vector<std::vector<Fr>>> insts(M);
+        std::vector<WitnessFn> ws;
+        size_t off = 0;
+        for (size_t j = 0; col_lens_out && j < c.gen.inst_lens.size(); ++j) col_lens_out[j] = c.gen.inst_lens[j];
+        for (size_t q = 0; q < M; ++q) {
+            const uint64_t ws_seed = witness_seed + 7919ULL * q;
+            insts[q] = instances_generated(c, ws_seed);
+            for (const auto& col : insts[q]) for (const Fr& v : col) { if (instances_out) v.to_bytes(instances_out + 32 * off); ++off; }
+            ws.push_back(witness_generated(c, ws_seed, (int)q == tamper_at));
+        }
+        Rng rng(rng_seed);
+        return copy_out(create_proof_multi(s->pk, s->ck, insts, ws, rng, s->multiopen, s->transcript), proof, cap);
+    } catch (...) { return 0; }
 }
 // wide circuit: instances_out receives the 8 public inputs; tamper != 0 corrupts one lookup input cell
 size_t h2o_prove_wide(void* h, uint64_t witness_seed, int tamper, uint64_t rng_seed, uint8_t* proof, size_t cap, uint8_t* instances_out) {

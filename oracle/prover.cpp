@@ -3,7 +3,9 @@
 #include <algorithm>
 #include <array>
 #include <map>
+#include <climits>
 #include <numeric>
+#include <set>
 
 namespace h2o {
 
@@ -813,6 +815,449 @@ WitnessFn witness_wide(const Circuit& c, u64 seed) {
                 adv[b + 2][i] = adv[b][i] * adv[b + 1][i].pow_u64(deg - 2) + c.fixed[3 + j][i] * adv[b][i + 1] - adv[b][i - 1];
         }
         for (size_t col = 4 * blocks; col < A; ++col) for (size_t i = 0; i < u; ++i) adv[col][i] = rng.fr();
+    };
+}
+
+// ------------------------------------------------------------------------------ generated circuits
+namespace {
+struct Pick {   // the generator's draws
+    Rng r;
+    explicit Pick(u64 seed) : r(seed) {}
+    size_t below(size_t m) { return m ? (size_t)(r.next() % m) : 0; }
+    size_t in(size_t lo, size_t hi) { return lo + below(hi - lo + 1); }   // inclusive
+    bool chance(size_t num, size_t den) { return below(den) < num; }
+    template <class T> const T& of(const std::vector<T>& v) { return v[below(v.size())]; }
+    template <class T> void shuffle(std::vector<T>& v) { for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[below(i)]); }
+};
+enum AdvRole { ROLE_RANDOM, ROLE_LOOKUP, ROLE_SHUFFLE, ROLE_RESULT, ROLE_UNQUERIED };
+struct AdvPlan { uint8_t phase; AdvRole role; std::vector<int32_t> rots; bool in_perm = false; };
+const int32_t ROT_LAST = INT32_MIN;   // stands for -(blinding_factors + 1) until the query counts are known
+void add_factor(ExprTerm& t, uint32_t var, uint32_t pw) {
+    for (auto& f : t.factors) if (f.first == var) { f.second += pw; return; }
+    t.factors.push_back({var, pw});
+}
+std::vector<VarSrc> row_vars_of(const ConstraintSystem& cs, const std::vector<std::vector<Fr>>& adv, const std::vector<std::vector<Fr>>& fix,
+                                const std::vector<std::vector<Fr>>& ins, const std::vector<Fr>& challenges) {
+    std::vector<VarSrc> vars;
+    for (const Query& q : cs.advice_queries) vars.push_back({&adv[q.column.index], q.rotation, Fr::zero()});
+    for (const Query& q : cs.fixed_queries) vars.push_back({&fix[q.column.index], q.rotation, Fr::zero()});
+    for (const Query& q : cs.instance_queries) vars.push_back({&ins[q.column.index], q.rotation, Fr::zero()});
+    for (size_t j = 0; j < cs.num_challenges; ++j) vars.push_back({nullptr, 0, j < challenges.size() ? challenges[j] : Fr::zero()});
+    return vars;
+}
+}  // namespace
+
+Circuit circuit_generated(uint32_t k, u64 seed) {
+    if (k < 5 || k > 12) throw std::runtime_error("circuit_generated: 5 <= k <= 12");
+    Circuit c; c.k = k;
+    ConstraintSystem& cs = c.cs; GenInfo& gi = c.gen;
+    Pick p(seed * 0x9e3779b97f4a7c15ULL + 0x67656e65);
+    const size_t n = c.n();
+    uint64_t feat = (k != 8 && k != 14 && k != 18) ? GF_SMALL_K : 0;
+    if (p.chance(1, 2)) feat |= GF_TWO_INSTANCES;
+
+    // ---- advice columns by role, then a random assignment of column indices (phase order and index order differ)
+    const uint8_t mp = (uint8_t)p.below(3);
+    std::vector<AdvPlan> adv;   // logical columns
+    auto new_col = [&](uint8_t phase, AdvRole role) { adv.push_back({phase, role, {}}); return (uint32_t)adv.size() - 1; };
+    std::vector<uint32_t> free0, late_free, result_lc;
+    for (size_t i = p.in(1, 3); i > 0; --i) free0.push_back(new_col(0, ROLE_RANDOM));
+    std::vector<std::vector<uint32_t>> lookup_lc, shuffle_in_lc, shuffle_out_lc;
+    {
+        static const size_t NL[] = {0, 0, 1, 2, 2, 3}, NS[] = {0, 0, 1, 1, 2};
+        size_t room = 5;
+        for (size_t l = NL[p.below(6)]; l > 0 && room > 0; --l) {
+            size_t arity = std::min(room, p.in(1, 3)); room -= arity;
+            lookup_lc.push_back({});
+            for (size_t j = 0; j < arity; ++j) lookup_lc.back().push_back(new_col(0, ROLE_LOOKUP));
+        }
+        room = 3;
+        for (size_t s = NS[p.below(5)]; s > 0 && room > 0; --s) {
+            size_t arity = std::min(room, p.in(1, 2)); room -= arity;
+            shuffle_in_lc.push_back({}); shuffle_out_lc.push_back({});
+            for (size_t j = 0; j < arity; ++j) { shuffle_in_lc.back().push_back(new_col(0, ROLE_SHUFFLE)); shuffle_out_lc.back().push_back(new_col(0, ROLE_SHUFFLE)); }
+        }
+    }
+    for (uint8_t ph = 1; ph <= mp; ++ph) if (p.chance(1, 2)) late_free.push_back(new_col(ph, ROLE_RANDOM));
+    const size_t G = p.in(1, 4);
+    for (size_t g = 0; g < G; ++g) result_lc.push_back(new_col(g + 1 == G ? mp : (uint8_t)p.below(mp + 1u), ROLE_RESULT));
+    if (p.chance(1, 3)) { new_col(0, ROLE_UNQUERIED); feat |= GF_ADVICE_UNQUERIED; }
+    const size_t A = adv.size();
+    std::vector<uint32_t> col_of(A);   // logical -> column index
+    std::iota(col_of.begin(), col_of.end(), 0u); p.shuffle(col_of);
+
+    // ---- advice queries: rotation 0 for every queried column, up to three more from {last, -3, -1, 1, 2, 5}
+    static const std::vector<int32_t> ADV_ROTS = {ROT_LAST, -3, -1, 1, 2, 5}, SIDE_ROTS = {-1, 1, 2};
+    std::vector<int32_t> lookup_rot(A, 0);
+    for (uint32_t lc = 0; lc < A; ++lc) {
+        AdvPlan& a = adv[lc];
+        if (a.role == ROLE_UNQUERIED) continue;
+        a.rots.push_back(0);
+        if (a.role == ROLE_LOOKUP) {
+            if (p.chance(1, 2)) { lookup_rot[lc] = p.of(SIDE_ROTS); if (p.chance(1, 2)) a.rots.clear(); a.rots.push_back(lookup_rot[lc]); }
+            continue;
+        }
+        static const size_t EXTRA[] = {0, 0, 1, 1, 2, 3};
+        for (size_t e = EXTRA[p.below(6)]; e > 0; --e) { int32_t r = p.of(ADV_ROTS); if (std::find(a.rots.begin(), a.rots.end(), r) == a.rots.end()) a.rots.push_back(r); }
+    }
+    cs.num_advice_columns = (uint32_t)A; cs.advice_column_phase.assign(A, 0); cs.num_advice_queries.assign(A, 0);
+    for (uint32_t lc = 0; lc < A; ++lc) { cs.advice_column_phase[col_of[lc]] = adv[lc].phase; cs.num_advice_queries[col_of[lc]] = (uint32_t)adv[lc].rots.size(); }
+    const int32_t rot_last = -(int32_t)(cs.blinding_factors() + 1);
+    const size_t u = c.usable_rows();
+    int32_t R = 0;
+    auto widen = [&](int32_t r) { R = std::max(R, r < 0 ? -r : r); };
+    {
+        std::vector<std::pair<uint32_t, int32_t>> qs;
+        for (uint32_t lc = 0; lc < A; ++lc) for (int32_t& r : adv[lc].rots) {
+            if (r == ROT_LAST) { r = rot_last; feat |= GF_ADVICE_ROT_LAST; }
+            if (r < -1 || r > 1) feat |= GF_ADVICE_ROT_FAR;
+            widen(r); qs.push_back({lc, r});
+        }
+        p.shuffle(qs);
+        for (const auto& q : qs) cs.advice_queries.push_back({adv_col(col_of[q.first], adv[q.first].phase), q.second});
+    }
+    const uint32_t Qa = (uint32_t)cs.advice_queries.size();
+    auto adv_var = [&](uint32_t lc, int32_t rot) -> uint32_t {
+        for (uint32_t i = 0; i < Qa; ++i) if (cs.advice_queries[i].column.index == col_of[lc] && cs.advice_queries[i].rotation == rot) return i;
+        throw std::runtime_error("circuit_generated: missing advice query");
+    };
+    auto has_rot0 = [&](uint32_t lc) { return std::find(adv[lc].rots.begin(), adv[lc].rots.end(), 0) != adv[lc].rots.end(); };
+
+    // ---- fixed columns: f0 is the selector; exactly one query per column COUNT, possibly two on one column and none on another
+    const uint32_t F = (uint32_t)p.in(2, 5);
+    cs.num_fixed_columns = F; cs.num_selectors = 1;
+    uint32_t fixed_twice = 0;   // the column with two queries (0: none)
+    {
+        std::vector<std::pair<uint32_t, int32_t>> qs = {{0, 0}};
+        uint32_t& twice = fixed_twice; uint32_t never = 0;
+        if (F >= 3 && p.chance(1, 3)) { twice = (uint32_t)p.in(1, F - 1); do never = (uint32_t)p.in(1, F - 1); while (never == twice); feat |= GF_FIXED_TWICE; }
+        for (uint32_t f = 1; f < F; ++f) {
+            if (twice && f == never) continue;
+            if (twice && f == twice) { qs.push_back({f, 0}); qs.push_back({f, p.of(SIDE_ROTS)}); continue; }
+            qs.push_back({f, p.chance(1, 2) ? 0 : p.of(SIDE_ROTS)});
+        }
+        p.shuffle(qs);
+        for (const auto& q : qs) { cs.fixed_queries.push_back({{q.first, COL_FIXED}, q.second}); widen(q.second); if (q.second) feat |= GF_FIXED_ROTATED; }
+    }
+    const uint32_t Qf = (uint32_t)cs.fixed_queries.size();
+    auto fixed_var = [&](uint32_t qi) { return Qa + qi; };
+    uint32_t sel_var = 0;
+    std::vector<uint32_t> data_fixed_vars;   // queries of the non-selector columns
+    for (uint32_t i = 0; i < Qf; ++i) { if (cs.fixed_queries[i].column.index == 0) sel_var = fixed_var(i); else data_fixed_vars.push_back(fixed_var(i)); }
+
+    // ---- permutation membership (decided here: an instance column in it keeps rotation 0)
+    const bool has_perm = p.chance(3, 4);
+    // ---- instance columns
+    static const size_t NI_OF[] = {0, 1, 1, 2, 2, 3, 3};
+    const uint32_t NI = (uint32_t)NI_OF[p.below(7)];
+    cs.num_instance_columns = NI;
+    gi.inst_lens.resize(NI);
+    for (size_t& l : gi.inst_lens) l = p.in(1, 12);
+    if (NI >= 2 && p.chance(1, 2)) gi.inst_lens[p.below(NI)] = 0;
+    std::vector<char> inst_in_perm(NI, 0);
+    {
+        std::vector<uint32_t> outside;
+        for (uint32_t i = 0; i < NI; ++i) { inst_in_perm[i] = has_perm && p.chance(1, 2); if (!inst_in_perm[i]) outside.push_back(i); }
+        uint32_t twice = NI, never = NI;
+        if (outside.size() >= 2 && p.chance(1, 2)) { p.shuffle(outside); twice = outside[0]; never = outside[1]; }
+        std::vector<std::pair<uint32_t, int32_t>> qs;
+        for (uint32_t i = 0; i < NI; ++i) {
+            if (i == never) continue;
+            if (inst_in_perm[i]) { qs.push_back({i, 0}); continue; }
+            if (i == twice) { qs.push_back({i, 0}); qs.push_back({i, p.of(SIDE_ROTS)}); continue; }
+            qs.push_back({i, p.chance(1, 2) ? 0 : p.of(SIDE_ROTS)});
+        }
+        p.shuffle(qs);
+        for (const auto& q : qs) { cs.instance_queries.push_back({{q.first, COL_INSTANCE}, q.second}); widen(q.second); }
+    }
+    const uint32_t Qi = (uint32_t)cs.instance_queries.size();
+    if (NI == 0) feat |= GF_INSTANCE_COLUMNS_0;
+    if (NI == 2) feat |= GF_INSTANCE_COLUMNS_2;
+    if (NI == 3) feat |= GF_INSTANCE_COLUMNS_3;
+    {
+        bool empty = false, filled = false;
+        for (size_t l : gi.inst_lens) { if (l) filled = true; else empty = true; }
+        if (empty && filled) feat |= GF_INSTANCE_EMPTY_COLUMN;
+    }
+
+    // ---- user challenges: any phase 0..2; one of a phase above the last advice phase is never squeezed
+    static const size_t CH_OF[] = {0, 1, 1, 2, 2, 3};
+    const uint32_t Ch = (uint32_t)CH_OF[p.below(6)];
+    cs.num_challenges = Ch;
+    for (uint32_t i = 0; i < Ch; ++i) {
+        cs.challenge_phase.push_back((uint8_t)p.below(3));
+        if (cs.challenge_phase[i] > mp) feat |= GF_CHALLENGE_UNSQUEEZED; else if (cs.challenge_phase[i] > 0) feat |= GF_CHALLENGE_LATE;
+    }
+    if (mp == 2) feat |= GF_PHASE_2;
+    const uint32_t nvars = Qa + Qf + Qi + Ch;
+    auto chal_var = [&](uint32_t i) { return Qa + Qf + Qi + i; };
+    auto squeezed = [&](uint32_t i) { return cs.challenge_phase[i] <= mp; };
+
+    // ---- the selector's rows and the fixed values
+    if ((size_t)(2 * R + 4) > u) throw std::runtime_error("circuit_generated: no active rows");
+    gi.act_lo = (size_t)R; gi.act_hi = u - (size_t)R;
+    {
+        Rng fr_(seed ^ 0x6669786564ULL);
+        c.fixed.assign(F, std::vector<Fr>(n, Fr::zero()));
+        for (size_t i = gi.act_lo; i < gi.act_hi; ++i) c.fixed[0][i] = Fr::one();
+        // the other columns vanish on the rows that row 0 reaches through a fixed rotation: every table expression is zero there
+        for (uint32_t f = 1; f < F; ++f) for (size_t i = 3; i + 1 < n; ++i) c.fixed[f][i] = fr_.fr();
+    }
+
+    // ---- coefficients: 0, 1, -1, then random values, the first of them with its negative
+    {
+        Rng cr(seed ^ 0x636f656666ULL);
+        cs.coeff_vals = {Fr::zero(), Fr::one(), Fr::one().neg()};
+        Fr c0 = cr.fr();
+        cs.coeff_vals.push_back(c0); cs.coeff_vals.push_back(c0.neg());
+        for (size_t i = p.in(1, 4); i > 0; --i) cs.coeff_vals.push_back(cr.fr());
+    }
+    const size_t NCO = cs.coeff_vals.size();
+
+    // ---- cs_degree first (the permutation's chunk is cs_degree - 2).  The quotient's top piece must not vanish — its commitment
+    // could not be written — so some expression has to reach the degree exactly: gate 0 carries the term sel * a^(cs_degree - 1)
+    c.cs_degree = p.chance(1, 5) ? 9 : (uint32_t)p.in(lookup_lc.empty() ? 3 : 5, 8);
+    if (c.cs_degree == 9) feat |= GF_DEGREE_9;
+    const std::pair<uint32_t, uint32_t> anchor = {adv_var(free0[0], 0), c.cs_degree - 1};
+
+    // ---- gates S_g * (E_g - r_g)
+    uint32_t need_degree = 3;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> powers_of_gate;   // (var, pow >= 2) per gate, for the shared-power bit
+    bool exp_chal = false, exp_fixed = false;
+    std::vector<ExprPoly> gate_polys;
+    bool tamper_set = false;
+    for (size_t g = 0; g < G; ++g) {
+        const uint32_t rlc = result_lc[g];
+        const uint8_t ph = adv[rlc].phase;
+        std::vector<uint32_t> av, cv;   // advice / challenge variables this gate may read
+        for (uint32_t lc = 0; lc < A; ++lc) {
+            const AdvPlan& a = adv[lc];
+            if (a.role == ROLE_UNQUERIED || a.phase > ph || lc == rlc) continue;
+            if (a.role == ROLE_RESULT && std::find(result_lc.begin(), result_lc.begin() + (ptrdiff_t)g, lc) == result_lc.begin() + (ptrdiff_t)g) continue;
+            for (int32_t r : a.rots) av.push_back(adv_var(lc, r));
+        }
+        for (uint32_t i = 0; i < Ch; ++i) if (!squeezed(i) || cs.challenge_phase[i] < ph) cv.push_back(chal_var(i));
+        static const uint32_t BUDGET[] = {2, 3, 4, 8};
+        const uint32_t budget = std::min(BUDGET[p.below(4)], c.cs_degree - 1);   // column degree of a term of E_g
+        GenGate gg; gg.result_col = col_of[rlc]; gg.phase = ph; gg.expr.num_vars = nvars;
+        uint32_t deg = 1;
+        if (g == 0) { gg.expr.terms.push_back(term(1, {anchor})); deg = anchor.second; }
+        for (size_t t = p.in(1, g == 0 ? 4 : 5); t > 0; --t) {
+            ExprTerm term_; term_.coeff_idx = (uint16_t)p.below(NCO);
+            uint32_t used = 0;
+            for (size_t f = p.below(5); f > 0; --f) {
+                if (g > 0 && p.chance(1, 3)) {   // a (variable, power) pair of an earlier gate, where this gate may read the variable
+                    const auto& pool = powers_of_gate[p.below(g)];
+                    if (!pool.empty()) {
+                        const auto pr = p.of(pool);
+                        const bool is_chal = pr.first >= Qa + Qf + Qi;
+                        const bool allowed = is_chal ? std::find(cv.begin(), cv.end(), pr.first) != cv.end()
+                                                     : (pr.first >= Qa || std::find(av.begin(), av.end(), pr.first) != av.end());
+                        bool fresh = true;
+                        for (const auto& ff : term_.factors) if (ff.first == pr.first) fresh = false;
+                        if (allowed && fresh && (is_chal || used + pr.second <= budget)) { term_.factors.push_back(pr); if (!is_chal) used += pr.second; continue; }
+                    }
+                }
+                const size_t kind = p.below(9);   // 0-2 advice, 3-4 fixed, 5-6 instance, 7-8 challenge
+                uint32_t pw = (uint32_t)p.in(1, 5);
+                if (kind >= 7) { if (!cv.empty()) add_factor(term_, p.of(cv), pw); continue; }
+                if (used >= budget) continue;
+                pw = std::min(pw, budget - used);
+                uint32_t var;
+                if (kind <= 2) { if (av.empty()) continue; var = p.of(av); }
+                else if (kind <= 4) { if (data_fixed_vars.empty()) continue; var = p.of(data_fixed_vars); }
+                else { if (!Qi) continue; var = Qa + Qf + (uint32_t)p.below(Qi); }
+                add_factor(term_, var, pw); used += pw;
+            }
+            if (g == 0 && term_.factors.size() == 1 && term_.factors[0] == anchor) continue;   // would join (or cancel) the anchor term
+            if (term_.coeff_idx >= 3) feat |= GF_COEFFICIENTS;
+            deg = std::max(deg, used);
+            gg.expr.terms.push_back(term_);
+        }
+        // S_g: the selector, sometimes times a power of a user challenge (gate 0 only a squeezed one: its result cell is the tampered one)
+        std::vector<std::pair<uint32_t, uint32_t>> sfac = {{sel_var, 1}};
+        bool zero_s = false;
+        if (Ch && p.chance(1, 2)) {
+            const uint32_t ci = (uint32_t)p.below(Ch);
+            if (g > 0 || squeezed(ci)) { sfac.push_back({chal_var(ci), (uint32_t)p.in(1, 4)}); zero_s = !squeezed(ci); }
+        }
+        if (!zero_s && !tamper_set) { gi.tamper = {gg.result_col, (uint32_t)p.in(gi.act_lo, gi.act_hi - 1)}; tamper_set = true; }
+        ExprPoly poly; poly.num_vars = nvars;
+        for (ExprTerm t : gg.expr.terms) { for (const auto& sf : sfac) add_factor(t, sf.first, sf.second); poly.terms.push_back(t); }
+        { ExprTerm t; t.coeff_idx = 2; t.factors.push_back({adv_var(rlc, 0), 1}); for (const auto& sf : sfac) add_factor(t, sf.first, sf.second); poly.terms.push_back(t); }
+        need_degree = std::max(need_degree, deg + 1);
+        powers_of_gate.push_back({});
+        for (const ExprTerm& t : poly.terms) for (const auto& f : t.factors) {
+            if (f.second >= 2) powers_of_gate.back().push_back(f);
+            if (f.second > 2 && f.first >= Qa + Qf + Qi) exp_chal = true;
+            if (f.second > 2 && f.first >= Qa && f.first < Qa + Qf) exp_fixed = true;
+        }
+        gate_polys.push_back(poly);
+        gi.gates.push_back(gg);
+    }
+    if (exp_chal && exp_fixed) feat |= GF_HIGH_EXPONENT;
+    for (const ExprPoly& poly : gate_polys) for (const ExprTerm& t : poly.terms) for (const auto& f : t.factors)   // a rotated instance query that a gate really reads
+        if (t.coeff_idx != 0 && f.first >= Qa + Qf && f.first < Qa + Qf + Qi) {
+            const Query& q = cs.instance_queries[f.first - Qa - Qf];
+            if (q.rotation != 0 && gi.inst_lens[q.column.index] > 0) feat |= GF_INSTANCE_ROTATED;
+        }
+    for (size_t g = 1; g < G; ++g) for (const auto& f : powers_of_gate[g]) for (size_t h = 0; h < g; ++h)
+        if (std::find(powers_of_gate[h].begin(), powers_of_gate[h].end(), f) != powers_of_gate[h].end()) feat |= GF_SHARED_POWER;
+    if (p.chance(1, 3)) {   // a gate that holds identically: c * v^e - c * v^e as two terms
+        const uint32_t var = (uint32_t)p.below(Qa + Qf), pw = (uint32_t)p.below(3);   // power 0: two terms without any factor
+        ExprPoly poly; poly.num_vars = nvars;
+        poly.terms.push_back(term(3, {})); poly.terms.push_back(term(4, {}));
+        if (pw) for (ExprTerm& t : poly.terms) t.factors.push_back({var, pw}); else feat |= GF_CONSTANT_TERM;
+        gate_polys.insert(gate_polys.begin() + (ptrdiff_t)p.below(gate_polys.size() + 1), poly);
+        feat |= GF_IDENTITY_GATE | GF_COEFFICIENTS;
+    }
+    cs.gates = gate_polys;
+
+    // ---- lookups: inputs sel * a_j(rot), tables polynomials over the non-selector fixed queries without a constant term
+    for (size_t l = 0; l < lookup_lc.size(); ++l) {
+        LookupArg la; gi.lookup_inputs.push_back({});
+        uint32_t tdeg = 1;
+        for (uint32_t lc : lookup_lc[l]) {
+            ExprPoly in; in.num_vars = nvars; in.terms.push_back(term(1, {{adv_var(lc, lookup_rot[lc]), 1}, {sel_var, 1}}));
+            ExprPoly tb; tb.num_vars = nvars;
+            for (size_t t = p.in(1, 2); t > 0; --t) {
+                ExprTerm tt; tt.coeff_idx = (uint16_t)p.in(1, NCO - 1);
+                uint32_t d = 0;
+                const uint32_t tmax = std::min(2u, c.cs_degree - 4);
+                for (size_t f = p.in(1, 2); f > 0 && d < tmax; --f) { uint32_t pw = (uint32_t)p.in(1, tmax - d); add_factor(tt, p.of(data_fixed_vars), pw); d += pw; }
+                tdeg = std::max(tdeg, d);
+                if (tt.coeff_idx >= 3) feat |= GF_COEFFICIENTS;
+                tb.terms.push_back(tt);
+            }
+            if (tb.terms.size() > 1 || tb.terms[0].factors.size() > 1 || tb.terms[0].factors[0].second > 1) feat |= GF_LOOKUP_COMPOSITE;
+            la.input.push_back(in); la.table.push_back(tb);
+            gi.lookup_inputs.back().push_back({col_of[lc], lookup_rot[lc]});
+        }
+        need_degree = std::max(need_degree, 2 + 2 + tdeg);
+        if (la.input.size() == 1) feat |= GF_LOOKUP_ARITY_1;
+        if (la.input.size() >= 3) feat |= GF_LOOKUP_ARITY_3;
+        cs.lookups.push_back(la);
+    }
+    if (cs.lookups.empty()) feat |= GF_NO_LOOKUPS;
+    // ---- shuffles: one column against a row permutation of it per position, a coefficient on both sides alike
+    for (size_t s = 0; s < shuffle_in_lc.size(); ++s) {
+        ShuffleArg sa; gi.shuffle_cols.push_back({});
+        for (size_t j = 0; j < shuffle_in_lc[s].size(); ++j) {
+            const uint16_t co = p.chance(1, 2) ? 1 : (uint16_t)p.in(3, NCO - 1);
+            if (co >= 3) feat |= GF_COEFFICIENTS;
+            ExprPoly a, b; a.num_vars = b.num_vars = nvars;
+            a.terms.push_back(term(co, {{adv_var(shuffle_in_lc[s][j], 0), 1}})); b.terms.push_back(term(co, {{adv_var(shuffle_out_lc[s][j], 0), 1}}));
+            if (p.chance(1, 3)) { const uint16_t k0 = (uint16_t)p.below(NCO); a.terms.push_back(term(k0, {})); b.terms.push_back(term(k0, {})); feat |= GF_CONSTANT_TERM; }   // the same constant on both sides
+            sa.input.push_back(a); sa.shuffle.push_back(b);
+            gi.shuffle_cols.back().push_back({col_of[shuffle_in_lc[s][j]], col_of[shuffle_out_lc[s][j]]});
+        }
+        cs.shuffles.push_back(sa);
+    }
+    if (cs.lookups.size() >= 2 && !cs.shuffles.empty() && (feat & GF_TWO_INSTANCES)) feat |= GF_MANY_ARGUMENTS_M2;
+
+    if (need_degree > c.cs_degree) throw std::runtime_error("circuit_generated: an expression exceeds cs_degree");
+
+    // ---- permutation: an ordered subset of the columns that have a query at rotation 0, and copies the witness honours
+    if (has_perm) {
+        std::vector<Column> pc;
+        adv[free0[0]].in_perm = true;
+        for (uint32_t lc = 0; lc < A; ++lc) { if (lc != free0[0] && has_rot0(lc) && p.chance(1, 2)) adv[lc].in_perm = true; if (adv[lc].in_perm) pc.push_back(adv_col(col_of[lc], adv[lc].phase)); }
+        std::vector<uint32_t> perm_fixed;
+        for (size_t qi = 0; qi < cs.fixed_queries.size(); ++qi) {
+            const Query& q = cs.fixed_queries[qi];
+            if (q.rotation != 0 || !(p.chance(1, 3) || (q.column.index == fixed_twice && fixed_twice && p.chance(1, 2)))) continue;
+            pc.push_back({q.column.index, COL_FIXED}); if (q.column.index) perm_fixed.push_back(q.column.index);
+            feat |= GF_PERM_FIXED;
+            for (size_t e = 0; e < qi; ++e) if (cs.fixed_queries[e].column.index == q.column.index) feat |= GF_PERM_FIXED_QUERY_NOT_FIRST;
+        }
+        for (uint32_t i = 0; i < NI; ++i) if (inst_in_perm[i]) pc.push_back({i, COL_INSTANCE});
+        p.shuffle(pc);
+        cs.permutation_columns = pc;
+        auto pos_of = [&](const Column& col) { return (uint32_t)(std::find(pc.begin(), pc.end(), col) - pc.begin()); };
+        for (uint32_t i = 0; i < pc.size(); ++i) if (pc[i].type == COL_INSTANCE && i > 0) feat |= GF_PERM_INSTANCE_NOT_FIRST;
+        std::vector<uint32_t> hosts;   // phase-0 random columns of the permutation: their cells take the copies
+        for (uint32_t lc : free0) if (adv[lc].in_perm) hosts.push_back(lc);
+        uint32_t pair_ = 0;   // copy t owns rows 2t and 2t + 1, so no cell is written twice
+        for (size_t t = p.below(3); t > 0; --t, ++pair_) {
+            const uint32_t a = p.of(hosts), b = p.of(hosts);
+            gi.advice_copies.push_back({{col_of[a], 2 * pair_}, {col_of[b], 2 * pair_ + 1}});
+            c.copies.push_back({pos_of(adv_col(col_of[a], 0)), 2 * pair_, pos_of(adv_col(col_of[b], 0)), 2 * pair_ + 1});
+        }
+        for (uint32_t i = 0; i < NI; ++i) if (inst_in_perm[i])
+            for (size_t t = std::min(gi.inst_lens[i], p.in(1, 2)); t > 0; --t, ++pair_) {
+                const uint32_t host = p.of(hosts), row = (uint32_t)p.below(gi.inst_lens[i]);
+                gi.instance_copies.push_back({{i, row}, {col_of[host], 2 * pair_}});
+                c.copies.push_back({pos_of({i, COL_INSTANCE}), row, pos_of(adv_col(col_of[host], 0)), 2 * pair_});
+            }
+        for (uint32_t f : perm_fixed) { c.fixed[f][5] = c.fixed[f][4]; c.copies.push_back({pos_of({f, COL_FIXED}), 4, pos_of({f, COL_FIXED}), 5}); }
+        const size_t P = pc.size(), chunk = c.cs_degree - 2;
+        if (chunk > P) feat |= GF_CHUNK_ABOVE;
+        if (chunk == P) feat |= GF_CHUNK_EQUAL;
+        if (chunk < P && P % chunk) feat |= GF_CHUNK_NOT_DIVIDING;
+    } else feat |= GF_NO_PERMUTATION;
+
+    // ---- what the multi-open argument will see: distinct opening points, and the widest set of points of one commitment
+    {
+        const size_t P = cs.permutation_columns.size(), chunk = c.cs_degree - 2, nsets = P ? (P + chunk - 1) / chunk : 0;
+        std::set<int32_t> points = {0};
+        size_t widest = 1;
+        for (uint32_t lc = 0; lc < A; ++lc) { for (int32_t r : adv[lc].rots) points.insert(r); widest = std::max(widest, adv[lc].rots.size()); }
+        for (uint32_t f = 0; f < F; ++f) { size_t cnt = 0; for (const Query& q : cs.fixed_queries) if (q.column.index == f) { points.insert(q.rotation); ++cnt; } widest = std::max(widest, cnt); }
+        if (nsets) { points.insert(1); widest = std::max<size_t>(widest, 2); }
+        if (nsets > 1) { points.insert(rot_last); widest = std::max<size_t>(widest, 3); }
+        if (!cs.lookups.empty()) { points.insert(1); points.insert(-1); widest = std::max<size_t>(widest, 2); }
+        if (!cs.shuffles.empty()) { points.insert(1); widest = std::max<size_t>(widest, 2); }
+        if (points.size() > 3) feat |= GF_GWC_MANY_POINTS;
+        if (widest >= 3) feat |= GF_ROTATION_SET_3;
+    }
+    for (uint32_t lc = 0; lc < A; ++lc) if (adv[lc].role != ROLE_RESULT) gi.random_cols.push_back(col_of[lc]);
+    gi.features = feat;
+    return c;
+}
+
+std::vector<std::vector<Fr>> instances_generated(const Circuit& c, u64 seed) {
+    Rng r(seed ^ 0x696e7374ULL);
+    std::vector<std::vector<Fr>> out;
+    for (size_t l : c.gen.inst_lens) { out.push_back({}); for (size_t i = 0; i < l; ++i) out.back().push_back(r.fr()); }
+    return out;
+}
+
+WitnessFn witness_generated(const Circuit& c, u64 seed, bool tamper) {
+    const std::vector<std::vector<Fr>> inst = instances_generated(c, seed);
+    return [c, seed, tamper, inst](unsigned phase, const std::vector<Fr>& ch, std::vector<std::vector<Fr>>& adv) {
+        const ConstraintSystem& cs = c.cs; const GenInfo& gi = c.gen;
+        const size_t n = c.n(), u = c.usable_rows();
+        for (uint32_t col : gi.random_cols) {
+            if (cs.advice_column_phase[col] != phase) continue;
+            Rng r(seed * 0x100000001b3ULL + col);
+            for (size_t i = 0; i < u; ++i) adv[col][i] = r.fr();
+        }
+        std::vector<std::vector<Fr>> ins(inst.size(), std::vector<Fr>(n, Fr::zero()));
+        for (size_t j = 0; j < inst.size(); ++j) std::copy(inst[j].begin(), inst[j].end(), ins[j].begin());
+        const std::vector<VarSrc> vars = row_vars_of(cs, adv, c.fixed, ins, ch);
+        if (phase == 0) {
+            Rng r(seed ^ 0x61726773ULL);
+            for (const auto& cp : gi.instance_copies) adv[cp.second.col][cp.second.row] = inst[cp.first.col][cp.first.row];
+            for (const auto& cp : gi.advice_copies) adv[cp.second.col][cp.second.row] = adv[cp.first.col][cp.first.row];
+            for (size_t l = 0; l < gi.lookup_inputs.size(); ++l)   // where the selector is set the inputs are the table's tuple of a random row
+                for (size_t i = gi.act_lo; i < gi.act_hi; ++i) {
+                    const size_t row = r.next() % u;
+                    for (size_t j = 0; j < gi.lookup_inputs[l].size(); ++j)
+                        adv[gi.lookup_inputs[l][j].first][(size_t)((int64_t)i + gi.lookup_inputs[l][j].second)] = eval_expr_at(cs.lookups[l].table[j], cs.coeff_vals, vars, row, n, 1);
+                }
+            for (const auto& sh : gi.shuffle_cols) {
+                std::vector<size_t> perm(u); std::iota(perm.begin(), perm.end(), (size_t)0);
+                for (size_t i = u - 1; i > 0; --i) std::swap(perm[i], perm[r.next() % (i + 1)]);
+                for (const auto& io : sh) for (size_t i = 0; i < u; ++i) adv[io.second][i] = adv[io.first][perm[i]];
+            }
+        }
+        for (const GenGate& g : gi.gates) {   // in gate order: E_g reads columns that are complete by now
+            if (g.phase != phase) continue;
+            Rng r(seed * 0x100000001b3ULL + 0x5000 + g.result_col);
+            for (size_t i = 0; i < u; ++i) adv[g.result_col][i] = r.fr();
+            for (size_t i = gi.act_lo; i < gi.act_hi; ++i) adv[g.result_col][i] = eval_expr_at(g.expr, cs.coeff_vals, vars, i, n, 1);
+        }
+        if (tamper && cs.advice_column_phase[gi.tamper.col] == phase) adv[gi.tamper.col][gi.tamper.row] += Fr::one();
     };
 }
 

@@ -40,12 +40,67 @@ struct CommitKey {
 
 struct CopyConstraint { uint32_t col_a, row_a, col_b, row_b; };  // indices into cs.permutation_columns
 
+// What circuit_generated decided for one seed and witness_generated needs to satisfy it (empty for the hand-written families)
+struct GenGate { uint32_t result_col; uint8_t phase; ExprPoly expr; };          // S_g * (expr - result_col@0)
+struct GenCell { uint32_t col, row; };
+struct GenInfo {
+    uint64_t features = 0;                        // GenFeature bits
+    size_t act_lo = 0, act_hi = 0;                // the selector is 1 on rows [act_lo, act_hi)
+    std::vector<size_t> inst_lens;
+    std::vector<uint32_t> random_cols;            // advice columns the witness fills with random values, in their own phase
+    std::vector<GenGate> gates;                   // in gate order
+    std::vector<std::vector<std::pair<uint32_t, int32_t>>> lookup_inputs;   // per lookup: (advice column, rotation) of each input
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> shuffle_cols;   // per shuffle: (input column, shuffled column) of each position
+    std::vector<std::pair<GenCell, GenCell>> advice_copies;                 // (from, to): two cells of phase-0 random columns
+    std::vector<std::pair<GenCell, GenCell>> instance_copies;               // (instance cell, advice cell)
+    GenCell tamper = {0, 0};                      // a result cell of an active row whose gate a wrong value breaks
+};
+enum GenFeature : uint64_t {   // one bit per branch of the plan compiler that only the generated family reaches (h2o_setup_features)
+    GF_PERM_FIXED = 1ull << 0,           // a fixed column in the permutation
+    GF_PERM_INSTANCE_NOT_FIRST = 1ull << 1,   // an instance column in the permutation behind position 0
+    GF_INSTANCE_ROTATED = 1ull << 2,     // an instance query at a non-zero rotation, of a column with values, that a gate reads
+    GF_FIXED_ROTATED = 1ull << 3,        // a fixed query at a non-zero rotation
+    GF_ADVICE_ROT_FAR = 1ull << 4,       // an advice rotation beyond +-1
+    GF_ADVICE_ROT_LAST = 1ull << 5,      // an advice rotation equal to -(blinding_factors + 1)
+    GF_PHASE_2 = 1ull << 6,              // an advice column of phase 2
+    GF_CHALLENGE_LATE = 1ull << 7,       // a user challenge of phase 1 or 2 that is squeezed
+    GF_CHALLENGE_UNSQUEEZED = 1ull << 8, // a user challenge of a phase above every advice column's
+    GF_CONSTANT_TERM = 1ull << 9,        // a term without factors
+    GF_COEFFICIENTS = 1ull << 10,        // a coefficient other than 0, 1, -1
+    GF_HIGH_EXPONENT = 1ull << 11,       // an exponent above 2 on a challenge and on a fixed query
+    GF_SHARED_POWER = 1ull << 12,        // one (variable, exponent >= 2) pair in two gates
+    GF_LOOKUP_ARITY_1 = 1ull << 13,
+    GF_LOOKUP_ARITY_3 = 1ull << 14,
+    GF_LOOKUP_COMPOSITE = 1ull << 15,    // a table expression of several terms or factors
+    GF_MANY_ARGUMENTS_M2 = 1ull << 16,   // two or more lookups and a shuffle under two circuit instances
+    GF_CHUNK_ABOVE = 1ull << 17,         // cs_degree - 2 > number of permutation columns (> 0)
+    GF_CHUNK_EQUAL = 1ull << 18,
+    GF_CHUNK_NOT_DIVIDING = 1ull << 19,  // several permutation sets, the last one short
+    GF_DEGREE_9 = 1ull << 20,
+    GF_ADVICE_UNQUERIED = 1ull << 21,
+    GF_FIXED_TWICE = 1ull << 22,         // a fixed column queried twice, another never
+    GF_INSTANCE_COLUMNS_0 = 1ull << 23,
+    GF_INSTANCE_COLUMNS_2 = 1ull << 24,
+    GF_INSTANCE_COLUMNS_3 = 1ull << 25,
+    GF_INSTANCE_EMPTY_COLUMN = 1ull << 26,   // an instance column of length 0 beside a longer one
+    GF_SMALL_K = 1ull << 27,             // k other than 8, 14, 18
+    GF_NO_PERMUTATION = 1ull << 28,
+    GF_NO_LOOKUPS = 1ull << 29,
+    GF_GWC_MANY_POINTS = 1ull << 30,     // more than three distinct opening points
+    GF_ROTATION_SET_3 = 1ull << 31,      // a commitment opened at three or more points
+    GF_IDENTITY_GATE = 1ull << 32,       // a gate that holds identically: c * v - c * v
+    GF_PERM_FIXED_QUERY_NOT_FIRST = 1ull << 33,   // a fixed column of the permutation whose rotated query precedes its query at rotation 0
+    GF_TWO_INSTANCES = 1ull << 34,       // the seed asks for two circuit instances per transcript
+    GF_ALL = (1ull << 34) - 1,           // every bit that names a branch (all but GF_TWO_INSTANCES)
+};
+
 struct Circuit {
     uint32_t k = 0;
     uint32_t cs_degree = 3;
     ConstraintSystem cs;
     std::vector<std::vector<Fr>> fixed;   // [num_fixed_columns][n]
     std::vector<CopyConstraint> copies;
+    GenInfo gen;
     uint64_t n() const { return 1ULL << k; }
     size_t usable_rows() const { return n() - (cs.blinding_factors() + 1); }
 };
@@ -86,5 +141,12 @@ WitnessFn witness_two_phase_shuffle(const std::vector<std::vector<Fr>>& original
 // input/table expressions, Sh shuffle arguments, a degree-`deg` gate, permutation over all advice columns.
 Circuit circuit_wide(uint32_t k, size_t A, size_t F, size_t L, size_t Sh, uint32_t gate_degree, u64 seed);
 WitnessFn witness_wide(const Circuit& c, u64 seed);
+// A circuit whose whole shape is drawn from `seed` (columns, phases, queries and their rotations, gates S_g * (E_g - r_g) with a
+// result column r_g per gate, lookups, shuffles, permutation, cs_degree), satisfiable by construction: c.gen holds what the witness
+// needs and the GenFeature bits of what the seed contains.  instances_generated draws the public inputs of one circuit instance,
+// witness_generated fills the advice from the same seed; `tamper` changes one result cell of an active row afterwards.
+Circuit circuit_generated(uint32_t k, u64 seed);
+std::vector<std::vector<Fr>> instances_generated(const Circuit& c, u64 seed);
+WitnessFn witness_generated(const Circuit& c, u64 seed, bool tamper);
 
 }  // namespace h2o

@@ -156,6 +156,50 @@ def prove_wide(s, witness_seed=3, tamper=False, rng_seed=13):
     return buf.raw[:n], [[inst.raw[32 * i:32 * i + 32] for i in range(8)]]
 
 
+def setup_generated(k=6, seed=1, s_seed=45):
+    """A circuit whose whole shape is drawn from `seed` (oracle/prover.hpp: circuit_generated).  s.features: GenFeature bits,
+    s.col_lens: its instance column lengths, s.want_instances: the circuit_instances count the seed asks for (1 or 2)."""
+    L = oracle_lib.load()
+    h = L.h2o_setup_generated(k, seed, None, 0, s_seed)
+    assert h, f"circuit_generated({k}, {seed}) failed"
+    s = Setup(L, h, 0)
+    s.features = setup_features(s)
+    s.want_instances = 2 if s.features & GF["TWO_INSTANCES"] else 1
+    lens = (ctypes.c_size_t * 8)()
+    s.ninst_cols = L.h2o_setup_col_lens(h, lens, 8)
+    s.col_lens = list(lens)[:s.ninst_cols]
+    return s
+
+
+def setup_features(s):
+    return int(s.L.h2o_setup_features(s.h))
+
+
+# oracle/prover.hpp: GenFeature
+GF_NAMES = ["PERM_FIXED", "PERM_INSTANCE_NOT_FIRST", "INSTANCE_ROTATED", "FIXED_ROTATED", "ADVICE_ROT_FAR", "ADVICE_ROT_LAST", "PHASE_2", "CHALLENGE_LATE",
+            "CHALLENGE_UNSQUEEZED", "CONSTANT_TERM", "COEFFICIENTS", "HIGH_EXPONENT", "SHARED_POWER", "LOOKUP_ARITY_1", "LOOKUP_ARITY_3", "LOOKUP_COMPOSITE",
+            "MANY_ARGUMENTS_M2", "CHUNK_ABOVE", "CHUNK_EQUAL", "CHUNK_NOT_DIVIDING", "DEGREE_9", "ADVICE_UNQUERIED", "FIXED_TWICE", "INSTANCE_COLUMNS_0",
+            "INSTANCE_COLUMNS_2", "INSTANCE_COLUMNS_3", "INSTANCE_EMPTY_COLUMN", "SMALL_K", "NO_PERMUTATION", "NO_LOOKUPS", "GWC_MANY_POINTS", "ROTATION_SET_3",
+            "IDENTITY_GATE", "PERM_FIXED_QUERY_NOT_FIRST", "TWO_INSTANCES"]
+GF = {name: 1 << i for i, name in enumerate(GF_NAMES)}
+GF_ALL = (1 << 34) - 1   # every bit that names a branch of the plan compiler (all but TWO_INSTANCES)
+
+
+def prove_generated(s, m=1, witness_seed=3, tamper_at=-1, rng_seed=17):
+    """ONE proof over m circuit instances of a generated setup -> (proof, instances): m x columns, instance-major"""
+    buf = ctypes.create_string_buffer(1 << 20)
+    total = sum(s.col_lens)
+    inst = ctypes.create_string_buffer(32 * max(m * total, 1))
+    n = s.L.h2o_prove_generated(s.h, m, witness_seed, tamper_at, rng_seed, buf, len(buf), inst, None)
+    assert n > 0
+    cols, at = [], 0
+    for _ in range(m):
+        for l in s.col_lens:
+            cols.append([inst.raw[32 * (at + i):32 * (at + i + 1)] for i in range(l)])
+            at += l
+    return buf.raw[:n], cols
+
+
 # ---- oracle-side verification helpers (the checker)
 def _flat(instances):
     flat = b"".join(b"".join(col) for col in instances)

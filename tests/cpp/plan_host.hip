@@ -7,6 +7,12 @@
 //   (3) status order — every store that reads the proof's status word (STORE_MSM / STORE_SHARED / STORE_LEFT zero a failed proof's
 //       scalars) runs after every OP_INV (which sets it when the reference would panic): later in the same stream, or behind a barrier.
 // Usage: plan_host <vk file> <params file> <multiopen> <transcript> <circuit_instances> <guard 0|1> <col_len>...
+//    or: plan_host --dump <out file> <instance_kernel_threshold> <vk file> <params file> <multiopen> <transcript> <circuit_instances> <guard 0|1> <col_len>...
+// The second form checks nothing: it writes the compiled plan's single-stream program and term maps as flat little-endian 32-bit
+// words, for tests/test_generated_circuits.py to interpret against the oracle's Guard.  Every list is its length followed by its
+// entries, in this order: the word 0x50563248; code (op, d, a, b); consts (8 words, canonical); point_offsets; scalar_offsets;
+// squeeze_order; the words n_points, n_shared; right_term_order, left_term_order, guard_term_order (is_shared, index);
+// inst_queries (base, len, 8 words w_start); the words wide_instances, proof_len, n_challenges, x_chal, domain_k.
 // Build (tests/test_plan_streams.py): hipcc -O1 -std=c++17 --offload-arch=gfx950 plan_host.hip ../../halo2_verifier_amd/csrc/vkplan.hip ../../halo2_verifier_amd/csrc/params.hip
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +37,29 @@ using namespace h2v;
 static std::vector<uint8_t> slurp(const char* path) {
     std::ifstream f(path, std::ios::binary);
     return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+static void put_fr(std::vector<uint32_t>& w, const Fr& f) {
+    uint8_t b[32]; f.to_bytes(b);
+    for (int i = 0; i < 8; ++i) w.push_back((uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24));
+}
+static bool dump_plan(const Plan& plan, const char* path) {
+    std::vector<uint32_t> w = {0x50563248u};
+    auto words = [&](const std::vector<uint32_t>& v) { w.push_back((uint32_t)v.size()); w.insert(w.end(), v.begin(), v.end()); };
+    auto terms = [&](const std::vector<std::pair<uint8_t, uint32_t>>& v) { w.push_back((uint32_t)v.size()); for (const auto& t : v) { w.push_back(t.first); w.push_back(t.second); } };
+    w.push_back((uint32_t)plan.code.size());
+    for (const VmInstr& in : plan.code) { w.push_back(in.op); w.push_back(in.d); w.push_back(in.a); w.push_back(in.b); }
+    w.push_back((uint32_t)plan.consts.size());
+    for (const Fr& f : plan.consts) put_fr(w, f);
+    words(plan.point_offsets); words(plan.scalar_offsets); words(plan.squeeze_order);
+    w.push_back(plan.n_points); w.push_back(plan.n_shared);
+    terms(plan.right_term_order); terms(plan.left_term_order); terms(plan.guard_term_order);
+    w.push_back((uint32_t)plan.inst_queries.size());
+    for (const Plan::InstQuery& q : plan.inst_queries) { w.push_back(q.base); w.push_back(q.len); put_fr(w, q.w_start); }
+    w.push_back(plan.wide_instances ? 1u : 0u); w.push_back(plan.proof_len); w.push_back(plan.n_challenges); w.push_back(plan.x_chal); w.push_back(plan.domain_k);
+    std::ofstream f(path, std::ios::binary);
+    for (uint32_t x : w) { const char b[4] = {(char)(x & 0xff), (char)((x >> 8) & 0xff), (char)((x >> 16) & 0xff), (char)(x >> 24)}; f.write(b, 4); }
+    return (bool)f;
 }
 
 struct Access { std::vector<uint32_t> reads; int write; };   // slots an instruction reads / the slot it writes (-1: none)
@@ -84,9 +113,12 @@ static bool step(Sym& sym, const VmInstr& in, std::map<uint32_t, uint64_t>& slot
 }
 
 int main(int argc, char** argv) {
-    if (argc < 7) { fprintf(stderr, "usage: plan_host vk params multiopen transcript circuit_instances guard col_len...\n"); return 2; }
+    const char* dump_to = nullptr;
+    PlanOptions opts;
+    if (argc >= 4 && std::string(argv[1]) == "--dump") { dump_to = argv[2]; opts.instance_kernel_threshold = atoi(argv[3]); argv += 3; argc -= 3; }
+    if (argc < 7) { fprintf(stderr, "usage: plan_host [--dump out instance_kernel_threshold] vk params multiopen transcript circuit_instances guard col_len...\n"); return 2; }
     const std::vector<uint8_t> vkb = slurp(argv[1]), pb = slurp(argv[2]);
-    PlanOptions opts; opts.multiopen = atoi(argv[3]); opts.transcript = atoi(argv[4]); opts.circuit_instances = atoi(argv[5]); opts.guard_terms = atoi(argv[6]) != 0;
+    opts.multiopen = atoi(argv[3]); opts.transcript = atoi(argv[4]); opts.circuit_instances = atoi(argv[5]); opts.guard_terms = atoi(argv[6]) != 0;
     std::vector<size_t> col_lens;
     for (int i = 7; i < argc; ++i) col_lens.push_back((size_t)atoll(argv[i]));
     std::string err;
@@ -96,6 +128,7 @@ int main(int argc, char** argv) {
     Plan plan;
     const int rc = compile_plan(vk, params, col_lens, opts, plan, err);
     if (rc) { fprintf(stderr, "compile_plan: %d %s\n", rc, err.c_str()); return 1; }
+    if (dump_to) { if (!dump_plan(plan, dump_to)) { fprintf(stderr, "cannot write %s\n", dump_to); return 1; } return 0; }
     // the single-stream program is the reference
     Sym sym;
     Outputs want;

@@ -13,8 +13,9 @@ def load():
     if _LIB is not None:
         return _LIB
     path = os.path.join(ROOT, "oracle", "build", "liboracle.so")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
+    # every time: the Makefile tracks the sources, so this costs nothing when the library is current, and a stale one cannot
+    # silently lack an entry point
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")], stdout=subprocess.DEVNULL)
     L = c.CDLL(path)
     szp = c.POINTER(c.c_size_t)
     intp = c.POINTER(c.c_int)
@@ -35,8 +36,15 @@ def load():
     L.h2o_verify_batch.argtypes = [c.c_char_p, c.c_size_t, c.c_int, c.c_char_p, c.c_size_t, c.c_int, c.c_size_t, c.c_char_p, c.c_size_t, c.c_char_p, szp, c.c_size_t,
                                    c.c_char_p, intp, intp, c.c_char_p, c.c_char_p]
     L.h2o_verify_each.argtypes = [c.c_char_p, c.c_size_t, c.c_int, c.c_char_p, c.c_size_t, c.c_int, c.c_size_t, c.c_char_p, c.c_size_t, c.c_char_p, szp, c.c_size_t, intp]
-    for f in ("h2o_setup_vector_mul", "h2o_setup_shuffle", "h2o_setup_wide"):
+    for f in ("h2o_setup_vector_mul", "h2o_setup_shuffle", "h2o_setup_wide", "h2o_setup_generated"):
         getattr(L, f).restype = c.c_void_p
+    L.h2o_setup_generated.argtypes = [c.c_uint32, c.c_uint64, c.c_char_p, c.c_size_t, c.c_uint64]
+    L.h2o_setup_features.restype = c.c_uint64
+    L.h2o_setup_features.argtypes = [c.c_void_p]
+    L.h2o_setup_col_lens.restype = c.c_size_t
+    L.h2o_setup_col_lens.argtypes = [c.c_void_p, szp, c.c_size_t]
+    L.h2o_prove_generated.restype = c.c_size_t
+    L.h2o_prove_generated.argtypes = [c.c_void_p, c.c_size_t, c.c_uint64, c.c_int, c.c_uint64, c.c_char_p, c.c_size_t, c.c_char_p, szp]
     L.h2o_setup_vector_mul.argtypes = [c.c_uint32, c.c_size_t, c.c_char_p, c.c_size_t, c.c_uint64]
     L.h2o_setup_shuffle.argtypes = [c.c_uint32, c.c_size_t, c.c_size_t, c.c_char_p, c.c_size_t, c.c_uint64]
     L.h2o_setup_wide.argtypes = [c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, c.c_size_t, c.c_uint32, c.c_uint64, c.c_char_p, c.c_size_t, c.c_uint64]
