@@ -14,7 +14,7 @@ PROGRAMS = {
     "pairing_units": {"step": [], "check": [], "lines": ["PARAMS"], "verdict": ["PARAMS"], "tail": ["PARAMS"]},
     "verify_units": {m: [] for m in ["decompress", "stream", "insteval", "frvm", "fold", "multipliers", "gather", "ragged"]},
     "util_units": {m: [] for m in ["fold", "export", "to_bytes", "bases", "scalars", "to_jacobian", "copy", "merge_fold"]},
-    "field_units": {m: None for m in ["fq", "fr", "gpu", "host"]},      # (text over stdin: no file-reading mode)
+    "field_units": {m: None for m in ["fq", "fr", "gpu", "host", "products", "linear", "wide", "convert", "inverse", "root"]},      # (text over stdin: no file-reading mode)
 }
 
 
