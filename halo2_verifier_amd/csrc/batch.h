@@ -220,6 +220,10 @@ struct h2v_batch {
     h2v::DevBuf<uint32_t> d_group_off; h2v::DevBuf<uint8_t> d_group_last;
     h2v::DevBuf<uint32_t> mult_seg;   // ragged_multipliers_enqueue's words per tile
     std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
+    // h2v_batch_upload_device with the caller's draws: k_ingest_draws checks them, and its verdict [fault][zero_below x groups] waits in
+    // pinned memory of the batch's own for h2v_batch_finish, which fills zero_below from it (device block: + the count of workgroups done)
+    bool device_draws = false;
+    h2v::DevBuf<uint32_t> ingest_verdict; h2v::MappedHostBuf ingest_host;
     // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
     h2v::DevBuf<uint8_t> proofs, inst, tail;
     h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)

@@ -258,6 +258,41 @@ static int draw_multipliers_enqueue(h2v_batch* b) {
     return multipliers_enqueue(b->stream, b->tail.p, b->n_tail, b->n, b->groups, b->mult.p, b->mult_tiles.p);
 }
 
+// The checks of an upload on its sizes alone, for the plan `pl` of its instance shape: the draws' count against n, the groups'
+// divisibility or the sum of their sizes, and the launch's MSM cut.  have_tail: the caller passes draws (n_tail of them).
+static int upload_size_checks(const h2v_batch* b, const Plan& pl, size_t n, bool have_tail, size_t n_tail, const char* who) {
+    const std::string w(who);
+    if (have_tail && n_tail < n) { set_last_error(w + ": n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
+    if (ragged(b)) {
+        if (n != b->group_off.back()) { set_last_error(w + ": n is not the sum of the group sizes (h2v_batch_set_group_sizes)"); return H2V_ERR_BAD_ARGUMENT; }
+        if (have_tail && n_tail != n) { set_last_error(w + ": groups of unequal size take one draw per proof (n_tail == n)"); return H2V_ERR_BAD_ARGUMENT; }
+        // the MSM cuts problems too large for its per-window sort into sub-problems, at most MSM_MAX_PROBLEMS per launch; equal groups that miss
+        // the limit all run uncut, a form that unequal groups have never taken: refused before any device work
+        std::vector<size_t> sizes(b->groups);
+        for (size_t g = 0; g < b->groups; ++g) sizes[g] = b->group_off[g + 1] - b->group_off[g];
+        if (!b->ctx->tuning.msm_no_term_split && !groups_cut_within_limit(pl, sizes.data(), sizes.size())) {
+            set_last_error(w + ": the groups' MSM problems, cut into sub-problems of at most 16384 terms, exceed the launch's problem limit");
+            return H2V_ERR_UNSUPPORTED;
+        }
+    } else if (b->groups > 1 && (n % b->groups || (have_tail && n_tail % b->groups))) { set_last_error(w + ": n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
+    return 0;
+}
+// a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs.
+// (The rule k_ingest_draws restates for draws in device memory.)
+static void zero_below_of_draws(h2v_batch* b, size_t n, const uint8_t* rand_tail, size_t n_tail) {
+    b->zero_below.assign(b->groups, 0);
+    if (ragged(b)) {
+        for (size_t g = 0; g < b->groups; ++g)   // (each group from its own draws)
+            for (size_t f = b->group_off[g], j = b->group_off[g + 1] - f; j-- > 1;)
+                if (scalar_is_zero(rand_tail + 32 * (f + j))) { b->zero_below[g] = (uint32_t)j; break; }
+    } else if (n) {
+        const size_t G = b->groups, gs = n / G, nt = n_tail / G;
+        for (size_t g = 0; g < G; ++g)
+            for (size_t j = nt; j-- > 1;)
+                if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
+    }
+}
+
 // `overlap`: where it pays (see `points_first` below), the point bytes are copied first on the batch's copy stream and the decompression
 // runs under the copy of everything else (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
 // `guard`: the guard variant of the plan (h2v_guard_msm)
@@ -276,19 +311,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     const Plan& pl = pin.pd->host;
     if (proof_len < pl.proof_len) { set_last_error("h2v_batch_upload: proof_len is shorter than this VK's proof"); return H2V_ERR_BAD_ARGUMENT; }
     if (pl.n_instance_values && n && !instances_flat) { set_last_error("h2v_batch_upload: instances missing"); return H2V_ERR_BAD_ARGUMENT; }
-    if (rand_tail && n_tail < n) { set_last_error("h2v_batch_upload: n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ragged(b)) {
-        if (n != b->group_off.back()) { set_last_error("h2v_batch_upload: n is not the sum of the group sizes (h2v_batch_set_group_sizes)"); return H2V_ERR_BAD_ARGUMENT; }
-        if (rand_tail && n_tail != n) { set_last_error("h2v_batch_upload: groups of unequal size take one draw per proof (n_tail == n)"); return H2V_ERR_BAD_ARGUMENT; }
-        // the MSM cuts problems too large for its per-window sort into sub-problems, at most MSM_MAX_PROBLEMS per launch; equal groups that miss
-        // the limit all run uncut, a form that unequal groups have never taken: refused before any device work
-        std::vector<size_t> sizes(b->groups);
-        for (size_t g = 0; g < b->groups; ++g) sizes[g] = b->group_off[g + 1] - b->group_off[g];
-        if (!ctx->tuning.msm_no_term_split && !groups_cut_within_limit(pl, sizes.data(), sizes.size())) {
-            set_last_error("h2v_batch_upload: the groups' MSM problems, cut into sub-problems of at most 16384 terms, exceed the launch's problem limit");
-            return H2V_ERR_UNSUPPORTED;
-        }
-    } else if (b->groups > 1 && (n % b->groups || (rand_tail && n_tail % b->groups))) { set_last_error("h2v_batch_upload: n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
+    if ((rc = upload_size_checks(b, pl, n, rand_tail != nullptr, n_tail, "h2v_batch_upload"))) return rc;
     std::vector<uint8_t> os_rand;
     if (!rand_tail) n_tail = n;
     if ((rc = resolve_draws(rand_tail, n_tail, os_rand, "h2v_batch_upload"))) return rc;
@@ -297,24 +320,13 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
     b->plan = pin.take(); b->n = (uint32_t)n;
     const PlanDevice* pd = b->plan;
-    // a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs
-    b->zero_below.assign(b->groups, 0);
-    if (ragged(b)) {
-        for (size_t g = 0; g < b->groups; ++g)   // (each group from its own draws)
-            for (size_t f = b->group_off[g], j = b->group_off[g + 1] - f; j-- > 1;)
-                if (scalar_is_zero(rand_tail + 32 * (f + j))) { b->zero_below[g] = (uint32_t)j; break; }
-    } else if (n) {
-        const size_t G = b->groups, gs = n / G, nt = n_tail / G;
-        for (size_t g = 0; g < G; ++g)
-            for (size_t j = nt; j-- > 1;)
-                if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
-    }
+    zero_below_of_draws(b, n, rand_tail, n_tail);
     if ((rc = b->tail.reserve(32 * n_tail))) return rc;
     if (ragged(b)) {
         const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
         if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles)) || (rc = b->d_group_off.reserve(b->group_off.size())) || (rc = b->d_group_last.reserve(n))) return rc;
     } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
-    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false;
+    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false; b->device_draws = false;
     hipStream_t s = b->stream;
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
         if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs.p + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
@@ -379,6 +391,83 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     }
     b->decompressed = points_first;
     // the batch multipliers depend on the draws alone: computed once per upload (the draws are on the device), kept by every launch of it
+    if (n) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
+    commit.commit(BatchStage::Uploaded);
+    return 0;
+}
+
+// `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary
+static int device_range_check(const void* p, size_t bytes, int device, const char* what) {
+    const std::string w = std::string("h2v_batch_upload_device: ") + what;
+    if ((uintptr_t)p & 15u) { set_last_error(w + " is not 16-byte aligned"); return H2V_ERR_BAD_ARGUMENT; }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); set_last_error(w + " is not device memory"); return H2V_ERR_BAD_ARGUMENT; }   // (a plain host address)
+    if (at.type != hipMemoryTypeDevice || at.device != device) { set_last_error(w + " is not device memory of the context's device"); return H2V_ERR_BAD_ARGUMENT; }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); set_last_error(w + ": no allocation holds the address"); return H2V_ERR_BAD_ARGUMENT; }
+    const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
+    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo)) { set_last_error(w + ": the bytes the call reads end past the pointer's allocation"); return H2V_ERR_BAD_ARGUMENT; }
+    return 0;
+}
+
+// h2v_batch_upload_device: upload_impl for inputs in device memory.  Every check comes before the first device work; with the caller's
+// draws nothing here waits for the stream, and what the host cannot see — the draws — is checked by k_ingest_draws, whose verdict
+// finish_impl reads (b->device_draws).
+int upload_device_impl(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, size_t ncols, const size_t* col_lens,
+                       const void* d_rand_tail, size_t n_tail) {
+    static const char who[] = "h2v_batch_upload_device";
+    StageCommit commit{b};
+    if (!b || (n && !d_proofs) || (ncols && !col_lens)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n > b->max_proofs) { set_last_error(std::string(who) + ": n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
+    h2v_ctx* ctx = b->ctx;
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+    if (ncols != ctx_total_instance_columns(ctx)) { set_last_error(std::string(who) + ": instances do not match the VK's instance column count"); return H2V_ERR_BAD_ARGUMENT; }
+    PlanPin pin(ctx);
+    int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols), false);
+    if (rc) return rc;
+    const Plan& pl = pin.pd->host;
+    if (proof_stride < pl.proof_len || (proof_stride & 15u)) { set_last_error(std::string(who) + ": proof_stride is below this VK's proof length, or no multiple of 16"); return H2V_ERR_BAD_ARGUMENT; }
+    if (pl.proof_len & 15u) { set_last_error(std::string(who) + ": this VK's proof length is no multiple of 16"); return H2V_ERR_UNSUPPORTED; }
+    const size_t inst_bytes = n * (size_t)pl.n_instance_values * 32;
+    if (inst_bytes && !d_instances) { set_last_error(std::string(who) + ": instances missing"); return H2V_ERR_BAD_ARGUMENT; }
+    if ((rc = upload_size_checks(b, pl, n, d_rand_tail != nullptr, n_tail, who))) return rc;
+    if (!d_rand_tail) n_tail = n;
+    if (n && (rc = device_range_check(d_proofs, (n - 1) * proof_stride + pl.proof_len, ctx->device, "d_proofs"))) return rc;
+    if (inst_bytes && (rc = device_range_check(d_instances, inst_bytes, ctx->device, "d_instances"))) return rc;
+    if (d_rand_tail && n_tail && (rc = device_range_check(d_rand_tail, 32 * n_tail, ctx->device, "d_rand_tail"))) return rc;
+    std::vector<uint8_t> os_rand;
+    const uint8_t* host_tail = nullptr;
+    if (!d_rand_tail && (rc = resolve_draws(host_tail, n_tail, os_rand, who))) return rc;
+    // every argument is valid: from here on the batch takes the upload
+    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
+    if (b->plan) ctx_put_plan(ctx, b->plan);
+    b->plan = pin.take(); b->n = (uint32_t)n;
+    const PlanDevice* pd = b->plan;
+    const uint32_t G = b->groups;
+    b->zero_below.assign(G, 0);   // (device draws: filled by h2v_batch_finish from the verdict block)
+    if (host_tail) zero_below_of_draws(b, n, host_tail, n_tail);
+    if ((rc = b->tail.reserve(32 * n_tail)) || (rc = b->ingest_verdict.reserve((size_t)G + 2)) || (rc = b->ingest_host.reserve(4 * ((size_t)G + 1)))) return rc;
+    if (ragged(b)) {   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
+        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
+        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles))) return rc;
+    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, G)))) return rc;
+    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false; b->decompressed = false;
+    hipStream_t s = b->stream;
+    if ((rc = ingest_rows_enqueue(s, d_proofs, proof_stride, pl.proof_len, n, d_instances, inst_bytes, b->proofs.p, b->inst.p, d_rand_tail ? b->ingest_verdict.p : nullptr, G))) return rc;
+    if (d_rand_tail) {
+        if ((rc = ingest_draws_enqueue(s, d_rand_tail, b->tail.p, (uint32_t)n_tail, (uint32_t)n, G, ragged(b) ? b->d_group_off.p : nullptr, b->ingest_verdict.p,
+                                       static_cast<uint32_t*>(b->ingest_host.dev)))) return rc;
+    } else if (n_tail) H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, host_tail, 32 * n_tail, hipMemcpyHostToDevice, s));
+    if (n) {
+        // VK-wide bases sit behind the batch's own points so that one MSM covers both
+        H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, s));
+        H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, s));
+    }
+    if (!d_rand_tail) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (the OS draws leave with this call)
+    b->device_draws = d_rand_tail != nullptr;
     if (n) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
     commit.commit(BatchStage::Uploaded);
     return 0;
@@ -504,6 +593,16 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
         e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) { set_last_error(std::string("h2v_batch_finish: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    if (b->device_draws) {
+        // the upload took its draws from device memory (h2v_batch_upload_device): k_ingest_draws' verdict, [fault][zero_below x G], has been
+        // in the batch's pinned block since the upload's kernels ran.  A draw >= r: nothing is written and the batch is left Empty.
+        const uint32_t* verdict = reinterpret_cast<const uint32_t*>(b->ingest_host.p);
+        if (verdict[0] != 0xffffffffu) {
+            set_last_error(std::string(who) + ": rand_tail scalar not canonical (draw " + std::to_string(verdict[0]) + " of the tail uploaded from device memory)");
+            return H2V_ERR_BAD_ARGUMENT;
+        }
+        b->zero_below.assign(verdict + 1, verdict + 1 + G);
+    }
     const uint8_t* host = b->results_host.p;
     const uint32_t* okv = reinterpret_cast<const uint32_t*>(host + L.ok());
     const uint32_t* foldf = reinterpret_cast<const uint32_t*>(host + L.fold_failed());
@@ -727,6 +826,10 @@ int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t 
                      const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail) {
     return upload_impl(b, n, proofs_flat, proof_len, instances_flat, n_instance_columns, col_lens, rand32_tail, n_tail);
 }
+int h2v_batch_upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, size_t n_instance_columns,
+                            const size_t* col_lens, const void* d_rand_tail, size_t n_tail) {
+    return upload_device_impl(b, n, d_proofs, proof_stride, d_instances, n_instance_columns, col_lens, d_rand_tail, n_tail);
+}
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
                             const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail, int with_pairing) {
@@ -764,6 +867,14 @@ int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups
     b->groups = (uint32_t)n_groups; b->stage = BatchStage::Empty;
     b->group_off.assign(n_groups + 1, 0); b->group_last.assign(total, 0);
     for (size_t g = 0; g < n_groups; ++g) { b->group_off[g + 1] = b->group_off[g] + (uint32_t)sizes[g]; b->group_last[b->group_off[g + 1] - 1] = 1; }
+    // The offsets and the last-of-group marks go to the device here, where they change and every stream of the batch is idle: an upload
+    // from device memory (h2v_batch_upload_device) enqueues behind a busy stream and must not copy from host vectors there.
+    // (h2v_batch_upload sends them again with its own copies.)
+    int rc;
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    if ((rc = b->d_group_off.reserve(b->group_off.size())) || (rc = b->d_group_last.reserve(total))) return rc;
+    H2V_HIP_CHECK(hipMemcpy(b->d_group_off.p, b->group_off.data(), 4 * b->group_off.size(), hipMemcpyHostToDevice));
+    H2V_HIP_CHECK(hipMemcpy(b->d_group_last.p, b->group_last.data(), total, hipMemcpyHostToDevice));
     return 0;
 }
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups) {

@@ -212,6 +212,19 @@ int affine_to_bytes_enqueue(hipStream_t s, const G1A* d_in, uint8_t* d_out, uint
 // Jacobian -> canonical x|y bytes (+ identity flag word after the 64 bytes: out is 68 B aligned to 4)
 int copy_words_enqueue(hipStream_t s, const void* d_src, void* d_dst, size_t n_words, size_t lds_reserve = 0);   // by a kernel (the destination may be mapped host memory)
 int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, uint32_t* d_is_identity, uint32_t n, size_t lds_reserve = 0);
+// An upload from device memory (h2v_batch_upload_device), two launches.  The verdict block d_verdict holds groups + 2 words:
+// [fault][zero_below x groups][workgroups done].
+// rows: n rows of row_len bytes, `stride` bytes apart -> packed at d_out_rows, and inst_bytes bytes d_inst -> d_out_inst, in one launch
+// (k_ingest_rows); every pointer, the stride and both lengths are multiples of 16.  With d_verdict the launch presets the verdict block
+// (fault 0xffffffff, the rest 0), also when there is nothing to copy.
+int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
+                        uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups);
+// draws: n_tail 32-byte scalars d_draws -> d_tail, the scalar 1 in place of a draw >= r (k_ingest_draws); the verdict block preset by
+// ingest_rows_enqueue on the same stream takes the lowest index of such a draw and every group's zero_below (upload_impl's rule; groups
+// of n / groups proofs and n_tail / groups draws, or d_group_off[0 .. groups] with n_tail == n), and its first 1 + groups words go to
+// d_host_verdict (mapped host memory) when the last workgroup is done.
+int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, const uint32_t* d_group_off, uint32_t* d_verdict,
+                         uint32_t* d_host_verdict);
 // Sharded batches exchange H2V_ACC_RECORD_BYTES records per group: [failed, parts, shift, 0][left pieces][right pieces] (h2v.h).
 // export: d_out[g] <- the group's accumulators — pieces [(2g + side) * parts + j] if d_pieces, else the whole points d_acc[2g], [2g+1] —
 // and the number of non-zero statuses among the group's n / groups proofs

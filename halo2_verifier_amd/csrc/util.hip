@@ -364,6 +364,90 @@ int copy_words_enqueue(hipStream_t s, const void* d_src, void* d_dst, size_t n_w
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
+// ---- an upload from device memory (h2v_batch_upload_device, batch.hip): two launches, both on the batch's stream.
+// The verdict block is [fault][zero_below x G][blocks done] on the device and its first 1 + G words in the batch's pinned host memory.
+//
+// k_ingest_rows: the caller's strided proof rows -> the batch's packed proofs, and the instance bytes behind them in the same launch
+// (by a kernel, not hipMemcpy2DAsync: k_copy_words' reason above).  One 16-byte load and one 16-byte store per thread: thread i owns
+// 16-byte word i of the packed rows (row i / row16, word i % row16 of it: consecutive lanes read consecutive words of a row and write
+// consecutive words of the output), the threads behind the rows own the instance words; a thread past both touches nothing.  The first
+// workgroup also presets the verdict block for k_ingest_draws, which runs behind it on the stream: fault 0xffffffff, the rest 0.
+// gfx950 (tools/kernel_resources.py): 14 VGPRs, 24 SGPRs, no spills, no scratch, no LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_ingest_rows(const uint4* __restrict__ rows, uint32_t stride16, uint32_t row16, uint64_t rows16, const uint4* __restrict__ inst,
+                                                     uint64_t inst16, uint4* __restrict__ out_rows, uint4* __restrict__ out_inst, uint32_t* __restrict__ verdict,
+                                                     uint32_t n_verdict) {
+    if (blockIdx.x == 0)
+        for (uint32_t t = threadIdx.x; t < n_verdict; t += 256) verdict[t] = t ? 0u : 0xffffffffu;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < rows16) {
+        const uint64_t r = i / row16;
+        out_rows[i] = rows[r * stride16 + (i - r * row16)];
+    } else if (i - rows16 < inst16) out_inst[i - rows16] = inst[i - rows16];
+}
+// k_ingest_draws: one thread per draw of the caller's tail, the checks the host makes for a tail in host memory (upload_impl): two
+// 16-byte loads, Fr::geq_p and a zero test as k_guard_terms reads its scalars.  The draw goes into the batch's tail, or the scalar 1
+// in place of a draw >= r, whose index joins verdict[0] by atomicMin (a stored zero would zero the multipliers of the earlier proofs
+// and drop them out of the accumulators).  A zero draw at index j >= 1 of its group's draws raises zero_below[g] = verdict[1 + g] by
+// atomicMax: to j for unequal groups (g found in off[0 .. G], one draw per proof), to min(j, gs) for equal groups of gs proofs and nt
+// draws each (nt > gs: a shard's tail) — the two branches of upload_impl's rule.  The workgroup that finishes last (a count of the
+// workgroups done, behind a device-wide fence) sends the 1 + G verdict words to host_verdict, so the verdict needs no third launch.
+// gfx950 (tools/kernel_resources.py): 22 VGPRs, 46 SGPRs, no spills, no scratch, 4 bytes of LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_ingest_draws(const uint4* __restrict__ draws, uint4* __restrict__ tail, uint32_t n_tail, uint32_t nt, uint32_t gs,
+                                                      const uint32_t* __restrict__ off, uint32_t G, uint32_t* __restrict__ verdict, uint32_t* __restrict__ host_verdict) {
+    __shared__ uint32_t last;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_tail) {
+        const uint4 s0 = draws[2 * (size_t)i], s1 = draws[2 * (size_t)i + 1];
+        const uint32_t raw[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        const bool zero = !(s0.x | s0.y | s0.z | s0.w | s1.x | s1.y | s1.z | s1.w);
+        if (Fr::geq_p(raw)) {
+            atomicMin(&verdict[0], i);
+            tail[2 * (size_t)i] = make_uint4(1, 0, 0, 0); tail[2 * (size_t)i + 1] = make_uint4(0, 0, 0, 0);
+        } else { tail[2 * (size_t)i] = s0; tail[2 * (size_t)i + 1] = s1; }
+        if (zero) {
+            uint32_t g, below;
+            if (off) {
+                uint32_t lo = 0, hi = G;   // the last g with off[g] <= i (off[0] = 0, off[G] = n_tail > i)
+                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+                g = lo; below = i - off[g];
+            } else { g = i / nt; const uint32_t j = i - g * nt; below = j ? (j < gs ? j : gs) : 0; }
+            if (below) atomicMax(&verdict[1 + g], below);
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(&verdict[1 + G], 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last) return;
+    for (uint32_t t = threadIdx.x; t < 1 + G; t += 256) host_verdict[t] = __hip_atomic_load(&verdict[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
+                        uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups) {
+    if ((n && row_len && (!d_rows || !d_out_rows)) || (inst_bytes && (!d_inst || !d_out_inst))) { set_last_error("ingest_rows_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (((uintptr_t)d_rows | (uintptr_t)d_inst | (uintptr_t)d_out_rows | (uintptr_t)d_out_inst | stride | row_len | inst_bytes) & 15u) {
+        set_last_error("ingest_rows_enqueue: a pointer, the stride or a length is not a multiple of 16 bytes"); return H2V_ERR_BAD_ARGUMENT;
+    }
+    if (stride < row_len || (stride >> 4) > 0xffffffffu) { set_last_error("ingest_rows_enqueue: the stride is below the row length, or too large"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint64_t rows16 = (uint64_t)n * (row_len >> 4), inst16 = inst_bytes >> 4;
+    if (rows16 + inst16 > 0xffffff00ull) { set_last_error("ingest_rows_enqueue: too many bytes for one launch"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint64_t blocks = (rows16 + inst16 + 255) / 256;
+    if (!blocks && !d_verdict) return 0;
+    hipLaunchKernelGGL(k_ingest_rows, dim3((uint32_t)(blocks ? blocks : 1)), dim3(256), 0, s, (const uint4*)d_rows, (uint32_t)(stride >> 4), (uint32_t)(row_len >> 4), rows16,
+                       (const uint4*)d_inst, inst16, (uint4*)d_out_rows, (uint4*)d_out_inst, d_verdict, d_verdict ? groups + 2 : 0u);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, const uint32_t* d_group_off, uint32_t* d_verdict,
+                         uint32_t* d_host_verdict) {
+    if (!groups || !d_verdict || !d_host_verdict || (n_tail && (!d_draws || !d_tail))) { set_last_error("ingest_draws_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (((uintptr_t)d_draws | (uintptr_t)d_tail) & 15u) { set_last_error("ingest_draws_enqueue: an array off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
+    if (d_group_off ? n_tail != n : (n % groups || n_tail % groups || n_tail < n)) { set_last_error("ingest_draws_enqueue: the draws do not match the groups"); return H2V_ERR_BAD_ARGUMENT; }
+    // (no draw: one workgroup still sends the preset verdict)
+    hipLaunchKernelGGL(k_ingest_draws, dim3(n_tail ? (n_tail + 255) / 256 : 1), dim3(256), 0, s, (const uint4*)d_draws, (uint4*)d_tail, n_tail, n_tail / groups, n / groups,
+                       d_group_off, groups, d_verdict, d_host_verdict);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, uint32_t* d_is_identity, uint32_t n, size_t lds_reserve) {
     if (!n) return 0;
     if (lds_reserve > 64 * 1024) H2V_HIP_CHECK(hipFuncSetAttribute((const void*)k_point_to_bytes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reserve));

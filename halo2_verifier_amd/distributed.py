@@ -127,6 +127,23 @@ def common_draws(n: int, rand, group=None, device=None) -> bytes:
     return bytes(buf[: 32 * n].cpu().numpy().tobytes())
 
 
+def common_draws_tensor(n: int, rand, group=None, device=None):
+    """common_draws as a uint8 tensor [n, 32] on `device`, for ShardedBatch.upload_tensors (a shard's tail is the rows from its first
+    proof on).  Under nccl with `rand` None the draws rank 0 made are broadcast on the device and stay there: no copy back to the host.
+    In every other case (given draws, a world of one, gloo) the bytes of common_draws are copied to the device."""
+    import torch
+    rank, world, backend = _group_info(group)
+    if rand is not None or world == 1 or backend != "nccl" or device is None:
+        flat = common_draws(n, rand, group, device)
+        return torch.frombuffer(bytearray(flat) if n else bytearray(32), dtype=torch.uint8)[: 32 * n].reshape(n, 32).to(device if device is not None else "cpu")
+    import torch.distributed as dist
+    buf = torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=device)
+    if rank == 0 and n:
+        buf[:n] = torch.frombuffer(bytearray(draw_scalars(n)), dtype=torch.uint8).reshape(n, 32).to(device)
+    dist.broadcast(buf, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    return buf[:n]
+
+
 class ShardedBatch:
     """One rank's share of a sharded batch (or of `groups` independent sharded batches that travel in one launch), resident on
     its GPU.  launch() enqueues, on the batch's stream and without host synchronisation: the shard's pipeline up to its two
@@ -179,6 +196,12 @@ class ShardedBatch:
         """This rank's shard (of every group: group-major) and, per group, the draws from its first proof to the end of the
         group's whole batch."""
         self.batch.upload(proofs_flat, proof_len, instances_flat, col_lens, rand_tail)
+
+    def upload_tensors(self, proofs, instances, col_lens, rand_tail):
+        """upload() for a shard that is already in device memory (Batch.upload_tensors): uint8 tensors on the batch's device, proofs
+        [n, >= proof length], instances [n, sum(col_lens) * 32] or None, rand_tail [n_tail, 32] — common_draws_tensor's rows from the
+        shard's first proof on.  Device work only, ordered behind the tensors' current stream; no host wait."""
+        self.batch.upload_tensors(proofs, instances, col_lens, rand_tail)
 
     def launch_shard(self):
         """Shard pipeline without a pairing + export of the accumulator records -> the local record tensor (stream-ordered)."""

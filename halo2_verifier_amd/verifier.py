@@ -1147,6 +1147,7 @@ class Batch:
         ctx._adopt(self)
         self.max_proofs = max_proofs
         self.n = 0
+        self._keep = None   # upload_tensors: the tensors the enqueued upload reads, until finish()
         self.groups, self.group_sizes = 1, None
         if stream is not None:
             self.set_stream(stream)
@@ -1215,6 +1216,112 @@ class Batch:
         check(self._lib.h2v_batch_upload(self._h, *args))
         self.n = args[0]
 
+    def upload_device(self, proofs_addr: int, n: int, proof_stride: int, instances_addr, col_lens, rand_addr=None, n_tail=None):
+        """upload() for inputs already in device memory (h2v_batch_upload_device), given as addresses: row i of the proofs starts at
+        proofs_addr + i * proof_stride (only the VK's proof length of it is read), instances_addr holds n * sum(col_lens) * 32 bytes
+        (None when there are none), rand_addr holds n_tail 32-byte draws under upload()'s tail rules — or None: OS draws made on the
+        host, the one form that waits for the stream.  Everything is device work on the batch's stream, behind whatever is queued
+        there: the caller orders the producers of the inputs before the call and leaves the inputs alone until finish().  A draw >= r
+        is found by a kernel and raised by finish() / finish_groups(), which leave the batch empty."""
+        def whole(v, what):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise TypeError(f"{what} must be an integer, got {type(v).__name__}")
+            if v < 0 or v >> 64:
+                raise ValueError(f"{what} must be in [0, 2^64), got {int(v)}")
+            return int(v)
+
+        def address(v, what, needed):
+            v = whole(0 if v is None else v, what)
+            if needed and not v:
+                raise ValueError(f"{what} is missing")
+            if v % 16:
+                raise ValueError(f"{what} must be 16-byte aligned, got {v:#x}")
+            return v
+
+        n, proof_stride = whole(n, "n"), whole(proof_stride, "proof_stride")
+        col_lens = [whole(c, "a column length") for c in col_lens]
+        if n > getattr(self, "max_proofs", n):
+            raise ValueError(f"n = {n} exceeds the batch capacity of {self.max_proofs}")
+        if not proof_stride or proof_stride % 16:
+            raise ValueError(f"proof_stride must be a positive multiple of 16, got {proof_stride}")
+        proofs_addr = address(proofs_addr, "proofs_addr", n > 0)
+        instances_addr = address(instances_addr, "instances_addr", n > 0 and sum(col_lens) > 0)
+        rand_addr = address(rand_addr, "rand_addr", False)
+        if not rand_addr:
+            if n_tail is not None:
+                raise ValueError("n_tail without rand_addr: OS draws are one per proof")
+            nt = 0
+        else:
+            nt = whole(n if n_tail is None else n_tail, "n_tail")
+            if nt < n:
+                raise ValueError(f"n_tail = {nt} is below n = {n}")
+        groups = getattr(self, "groups", 1)
+        if getattr(self, "group_sizes", None) is not None:
+            if n != sum(self.group_sizes):
+                raise ValueError(f"the group sizes sum to {sum(self.group_sizes)} proofs, got {n}")
+            if rand_addr and nt != n:
+                raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
+        elif n % groups or nt % groups:
+            raise ValueError(f"n and n_tail must be multiples of the group count ({groups}), got {n} and {nt}")
+        cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
+        self._keep = None
+        check(self._lib.h2v_batch_upload_device(self._h, n, ctypes.c_void_p(proofs_addr), proof_stride, ctypes.c_void_p(instances_addr), len(col_lens), cl,
+                                                ctypes.c_void_p(rand_addr), nt))
+        self.n = n
+
+    @staticmethod
+    def _tensor_bytes(t, what, device, rows=None, row_len=None):
+        """A duck-typed tensor as device bytes: uint8, on `device`, 2-D with unit inner stride (`rows` rows; `row_len` given: exactly
+        that many bytes per row and no padding between rows) -> (address, rows, row stride)"""
+        for attr in ("dtype", "device", "shape", "stride", "data_ptr"):
+            if not hasattr(t, attr):
+                raise TypeError(f"{what} must be a tensor (no .{attr})")
+        if not str(t.dtype).endswith("uint8"):
+            raise TypeError(f"{what} must be a uint8 tensor, got {t.dtype}")
+        if getattr(t.device, "type", None) != "cuda" or t.device.index != device:
+            raise ValueError(f"{what} must be on the context's device (cuda:{device}), got {t.device}")
+        shape, stride = tuple(t.shape), tuple(t.stride())
+        if len(shape) != 2 or (shape[1] > 1 and stride[1] != 1):
+            raise ValueError(f"{what} must be 2-D with unit inner stride, got shape {shape} and strides {stride}")
+        if rows is not None and shape[0] != rows:
+            raise ValueError(f"{what} must hold {rows} rows, got {shape[0]}")
+        row_stride = stride[0] if shape[0] > 1 else max(stride[0], shape[1])
+        if row_stride < shape[1]:
+            raise ValueError(f"{what}: rows overlap (row stride {row_stride} below the row length {shape[1]})")
+        if row_len is not None and (shape[1] != row_len or (shape[0] > 1 and row_stride != row_len)):
+            raise ValueError(f"{what} must be contiguous rows of {row_len} bytes, got shape {shape} and strides {stride}")
+        return int(t.data_ptr()), shape[0], row_stride
+
+    def upload_tensors(self, proofs, instances, col_lens, rand_tail=None):
+        """upload_device() from tensors (torch's, or anything with dtype / device / shape / stride() / data_ptr()): proofs [n, >= proof
+        length] with any row stride that is a multiple of 16, instances [n, sum(col_lens) * 32] contiguous (None when there are none),
+        rand_tail [n_tail, 32] contiguous or None (OS draws).  The batch's stream is made to wait, on the device, for the work queued on
+        the tensors' current stream; the tensors are kept referenced until finish()."""
+        device = self.ctx.device
+        col_lens = list(col_lens)
+        addr, n, stride = self._tensor_bytes(proofs, "proofs", device)
+        ninst = sum(col_lens) * 32
+        iaddr = None
+        if ninst:   # (no instance values: `instances` is not looked at)
+            if instances is None:
+                raise ValueError("instances missing")
+            iaddr = self._tensor_bytes(instances, "instances", device, n, ninst)[0]
+        raddr = nt = None
+        if rand_tail is not None:
+            raddr, nt, _ = self._tensor_bytes(rand_tail, "rand_tail", device, None, 32)
+        # the inputs are written on the tensors' current stream: the batch's stream waits for it by an event, the host for nothing
+        import sys
+        cuda = getattr(sys.modules.get(type(proofs).__module__.partition(".")[0]), "cuda", None)
+        if cuda is None:
+            raise TypeError("the tensors' module has no cuda streams to order the upload behind")
+        current, mine = cuda.current_stream(proofs.device), self.stream
+        if current.cuda_stream != mine:
+            ev = cuda.Event()
+            ev.record(current)
+            cuda.ExternalStream(mine, device=proofs.device).wait_event(ev)
+        self.upload_device(addr, n, stride, iaddr, col_lens, raddr, nt)
+        self._keep = (proofs, instances, rand_tail)
+
     def launch(self, with_pairing=True):
         check(self._lib.h2v_batch_launch(self._h, 1 if with_pairing else 0))
 
@@ -1236,6 +1343,7 @@ class Batch:
         ok = ctypes.c_int(0)
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
         check(self._lib.h2v_batch_finish(self._h, st, ctypes.byref(ok), left, right))
+        self._keep = None   # (upload_tensors' inputs: the enqueued work has run)
         return bool(ok.value), memoryview(st).cast('B').cast('i').tolist()[:self.n], left.raw, right.raw
 
     def finish_groups(self, raw_statuses=False):
@@ -1247,6 +1355,7 @@ class Batch:
         ok = (ctypes.c_int * g)()
         left, right = ctypes.create_string_buffer(64 * g), ctypes.create_string_buffer(64 * g)
         check(self._lib.h2v_batch_finish_groups(self._h, st, ok, left, right, g))
+        self._keep = None   # (upload_tensors' inputs: the enqueued work has run)
         statuses = bytes(memoryview(st).cast('B')[:4 * self.n]) if raw_statuses else memoryview(st).cast('B').cast('i').tolist()[:self.n]
         return [bool(v) for v in ok], statuses, _points(left, g), _points(right, g)
 

@@ -540,6 +540,25 @@ void h2v_batch_destroy(h2v_batch* b);
 int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len,
                      const uint8_t* instances_flat, size_t n_instance_columns, const size_t* col_lens,
                      const uint8_t* rand32_tail, size_t n_tail);
+/* h2v_batch_upload for inputs that are ALREADY in device memory (a shard received over RCCL, a GPU prover's output, a NIC's buffer, a
+ * tensor): device -> device, on the batch's stream (its own, or h2v_batch_set_stream's), with no host wait when the draws are given.
+ * Row i of the proofs starts at d_proofs + i * proof_stride and only the VK's proof length of it is read (proof_stride >= that
+ * length); d_instances has h2v_batch_upload's flat layout; d_rand_tail holds n_tail canonical 32-byte scalars under h2v_batch_upload's
+ * tail rules (equal groups, unequal groups with n_tail == n, a shard's tail with n_tail > n).  d_rand_tail NULL = OS draws made on
+ * the host and copied: only that form waits for the stream.  col_lens is a host array.
+ * Checked on the host before any device work (H2V_ERR_BAD_ARGUMENT, the batch untouched): everything h2v_batch_upload checks without
+ * reading an input byte; every pointer is device memory of the context's device, 16-byte aligned, and the bytes read from it lie
+ * inside its allocation; proof_stride is a multiple of 16.
+ * The caller orders whatever produces the inputs before this call (the same stream, or an event the stream waits for) and leaves the
+ * inputs alone until the enqueued work has run: return from h2v_batch_finish(_groups) is sufficient.
+ * The DRAWS cannot be seen by the host: a kernel checks them, and its verdict arrives with h2v_batch_finish(_groups).  A draw >= r makes
+ * that call return H2V_ERR_BAD_ARGUMENT naming the lowest offending index; it writes nothing and leaves the batch empty.  (The batch's
+ * own copy of the tail holds the scalar 1 in place of such a draw: no proof drops out of an accumulator, and ranks of a sharded batch
+ * that upload the same tail substitute alike, so a record exported before the finish is never a silent partial sum.)  Zero draws are
+ * handled as in h2v_batch_upload; what h2v_batch_recheck and h2v_batch_identify need to know about them is there after the finish. */
+int h2v_batch_upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride,
+                            const void* d_instances, size_t n_instance_columns, const size_t* col_lens,
+                            const void* d_rand_tail, size_t n_tail);
 /* Enqueue decompress -> transcript -> Fr program -> fold -> MSM (-> pairing if with_pairing). */
 int h2v_batch_launch(h2v_batch* b, int with_pairing);
 /* h2v_batch_upload followed by h2v_batch_launch, with most of the host -> device copy HIDDEN behind the first stage: only the point

@@ -538,6 +538,20 @@ inline void set_group_sizes(h2v_batch* b, const std::vector<size_t>& sizes) {
     check(h2v_batch_set_group_sizes(b, sizes.data(), sizes.size()));
 }
 
+// A staged batch's upload from device memory (h2v_batch_upload_device): n proof rows `proof_stride` bytes apart at d_proofs, the flat
+// instance values at d_instances, n_tail draws at d_rand_tail (null: OS draws, the one form that waits for the stream).  Device work
+// only, on the batch's stream; the verdict on the draws comes with h2v_batch_finish(_groups).  What the host can check is checked here
+// first: 16-byte alignment, a stride that is a multiple of 16.
+inline void upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, const std::vector<size_t>& col_lens,
+                          const void* d_rand_tail = nullptr, size_t n_tail = 0) {
+    if (n && !d_proofs) throw Failure(H2V_ERR_BAD_ARGUMENT, "upload_device: no proofs");
+    if (proof_stride % 16) throw Failure(H2V_ERR_BAD_ARGUMENT, "upload_device: proof_stride must be a multiple of 16");
+    for (const void* p : {d_proofs, d_instances, d_rand_tail})
+        if (reinterpret_cast<uintptr_t>(p) % 16) throw Failure(H2V_ERR_BAD_ARGUMENT, "upload_device: a device pointer off a 16-byte boundary");
+    if (d_rand_tail && n_tail < n) throw Failure(H2V_ERR_BAD_ARGUMENT, "upload_device: n_tail < n");
+    check(h2v_batch_upload_device(b, n, d_proofs, proof_stride, d_instances, col_lens.size(), col_lens.data(), d_rand_tail, d_rand_tail ? n_tail : 0));
+}
+
 // Many AccumulatorStrategy batches of their own sizes in few launches (h2v_verify_batches): every batch is a list of (instances, proof)
 // in verify_proof order and none is empty; one instance shape for the whole call; rand32: one 32-byte draw per proof of the call, batch
 // after batch, or empty = OS RNG.  -> per batch what its own AccumulatorStrategy::finalize() gives: verdict, statuses, the two channels.

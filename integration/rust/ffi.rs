@@ -149,6 +149,8 @@ extern "C" {
     pub fn h2v_batch_destroy(b: *mut h2v_batch);
     pub fn h2v_batch_upload(b: *mut h2v_batch, n: usize, proofs_flat: *const u8, proof_len: usize, instances_flat: *const u8,
                             n_instance_columns: usize, col_lens: *const usize, rand32_tail: *const u8, n_tail: usize) -> c_int;
+    pub fn h2v_batch_upload_device(b: *mut h2v_batch, n: usize, d_proofs: *const c_void, proof_stride: usize, d_instances: *const c_void,
+                                   n_instance_columns: usize, col_lens: *const usize, d_rand_tail: *const c_void, n_tail: usize) -> c_int;
     pub fn h2v_batch_launch(b: *mut h2v_batch, with_pairing: c_int) -> c_int;
     pub fn h2v_batch_upload_launch(b: *mut h2v_batch, n: usize, proofs_flat: *const u8, proof_len: usize, instances_flat: *const u8,
                                    n_instance_columns: usize, col_lens: *const usize, rand32_tail: *const u8, n_tail: usize, with_pairing: c_int) -> c_int;

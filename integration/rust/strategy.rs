@@ -156,6 +156,18 @@ impl GpuStagedBatch {
         self.n = n;
         Ok(())
     }
+    /// `upload` for inputs already in device memory (h2v_batch_upload_device): `n` proof rows `proof_stride` bytes apart at `d_proofs`,
+    /// the flat instance values at `d_instances`, `n_tail` draws at `d_rand_tail` (null: OS draws, the one form that waits for the
+    /// stream).  Device work only, on the batch's stream; a draw that is not canonical is reported by `finish`.
+    /// Safety: the pointers are device memory that holds what the call reads, and stays untouched until `finish` has returned.
+    pub unsafe fn upload_device(&mut self, n: usize, d_proofs: *const core::ffi::c_void, proof_stride: usize, d_instances: *const core::ffi::c_void, col_lens: &[usize],
+                                d_rand_tail: *const core::ffi::c_void, n_tail: usize) -> Result<(), Error> {
+        if proof_stride % 16 != 0 || (d_proofs as usize | d_instances as usize | d_rand_tail as usize) % 16 != 0 || (!d_rand_tail.is_null() && n_tail < n) { return Err(Error::InvalidInstances); }
+        let rc = h2v_batch_upload_device(self.b, n, d_proofs, proof_stride, d_instances, col_lens.len(), col_lens.as_ptr(), d_rand_tail, if d_rand_tail.is_null() { 0 } else { n_tail });
+        if rc != 0 { return Err(map_err(rc)); }
+        self.n = n;
+        Ok(())
+    }
     pub fn launch(&mut self, with_pairing: bool) -> Result<(), Error> {
         let rc = unsafe { h2v_batch_launch(self.b, with_pairing as i32) };
         if rc != 0 { Err(map_err(rc)) } else { Ok(()) }
