@@ -21,7 +21,7 @@ __device__ __forceinline__ void status_set(int* status, uint32_t p, int dev_code
 // a status word that another wave of the same kernel may have set (the Fr program's inversion, ordered before this read by a
 // workgroup barrier): read at device scope, past the CU's vector cache, like the atomic that wrote it
 __device__ __forceinline__ int status_get(const int* status, uint32_t p) { return __hip_atomic_load(&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-inline int status_decode(int dev) {
+__host__ __device__ inline int status_decode(int dev) {
     switch (dev) {
         case 0: return 0;
         case H2V_DEV_ST_INVALID_INSTANCES: return H2V_ERR_INVALID_INSTANCES;
@@ -159,6 +159,8 @@ struct LaunchRecord {           // what the last launch (or fold) left (close_en
 int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false);
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
                 const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false);
+int finish_device_impl(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
+                       void* d_summary);
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
 bool pairing_passed(const h2v_batch* b, uint32_t g);
 // The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
@@ -224,6 +226,8 @@ struct h2v_batch {
     // pinned memory of the batch's own for h2v_batch_finish, which fills zero_below from it (device block: + the count of workgroups done)
     bool device_draws = false;
     h2v::DevBuf<uint32_t> ingest_verdict; h2v::MappedHostBuf ingest_host;
+    // h2v_batch_finish_device's scratch (results_enqueue): a word per tile of 256 proofs; a word per group, zero between calls
+    h2v::DevBuf<uint32_t> finish_tiles, finish_groups;
     // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
     h2v::DevBuf<uint8_t> proofs, inst, tail;
     h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)

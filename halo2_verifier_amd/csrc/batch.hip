@@ -397,8 +397,9 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
 }
 
 // `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary
-static int device_range_check(const void* p, size_t bytes, int device, const char* what) {
-    const std::string w = std::string("h2v_batch_upload_device: ") + what;
+// (who / does: the entry point and the verb of the error message)
+static int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who = "h2v_batch_upload_device", const char* does = "reads") {
+    const std::string w = std::string(who) + ": " + what;
     if ((uintptr_t)p & 15u) { set_last_error(w + " is not 16-byte aligned"); return H2V_ERR_BAD_ARGUMENT; }
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);
@@ -408,7 +409,7 @@ static int device_range_check(const void* p, size_t bytes, int device, const cha
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); set_last_error(w + ": no allocation holds the address"); return H2V_ERR_BAD_ARGUMENT; }
     const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
-    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo)) { set_last_error(w + ": the bytes the call reads end past the pointer's allocation"); return H2V_ERR_BAD_ARGUMENT; }
+    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo)) { set_last_error(w + ": the bytes the call " + does + " end past the pointer's allocation"); return H2V_ERR_BAD_ARGUMENT; }
     return 0;
 }
 
@@ -646,6 +647,47 @@ bool pairing_passed(const h2v_batch* b, uint32_t g) {
     return b->last.pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
 }
 
+// h2v_batch_finish_device: what finish_impl hands the host, handed to the caller's device arrays by kernels on the batch's stream
+// (results_enqueue, util.hip).  Nothing here waits: no synchronise, no copy.  Every check comes before the first device work and a refusal
+// leaves the batch as it was; the stage does not change, so the call may be repeated and a host finish may precede or follow it.
+int finish_device_impl(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
+                       void* d_summary) {
+    static const char who[] = "h2v_batch_finish_device";
+    int rc;
+    if ((rc = require_stage(b, BatchStage::Launched, who))) return rc;
+    const uint32_t n = b->n, G = b->groups;
+    const int device = b->ctx->device;
+    H2V_HIP_CHECK(hipSetDevice(device));
+    if (d_failed_index && !failed_cap) { set_last_error(std::string(who) + ": failed_cap is 0 with d_failed_index given"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint32_t cap = d_failed_index ? (uint32_t)std::min<size_t>(failed_cap, n) : 0;   // (no more than n indices exist)
+    const struct { const void* p; size_t bytes; const char* what; } outs[] = {
+        {d_status, 4 * (size_t)n, "d_status"}, {d_group_ok, 4 * (size_t)G, "d_group_ok"}, {d_left_xy, 64 * (size_t)G, "d_left_xy"}, {d_right_xy, 64 * (size_t)G, "d_right_xy"},
+        {d_group_failed, 4 * (size_t)G, "d_group_failed"}, {d_failed_index, 4 * (size_t)cap, "d_failed_index"}, {d_summary, 4 * (size_t)H2V_SUMMARY_WORDS, "d_summary"}};
+    for (const auto& o : outs)
+        if (o.p && (rc = device_range_check(o.p, o.bytes, device, o.what, who, "writes"))) return rc;
+    // every argument is valid: device work from here on, and a failure of it leaves the batch Empty like any other
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
+    // the scratch: grow-only, for the batch's capacity and group count (ensure_buffers' rule).  The group words are zero between calls
+    // (results_enqueue), so new memory is zeroed once, on the stream.
+    if ((rc = b->finish_tiles.reserve(results_tiles(b->max_proofs)))) return rc;
+    if (!b->finish_groups.p || G > b->finish_groups.cap) {
+        if ((rc = b->finish_groups.reserve(G))) return rc;
+        H2V_HIP_CHECK(hipMemsetAsync(b->finish_groups.p, 0, 4 * b->finish_groups.cap, b->stream));
+    }
+    ResultsOut out;
+    out.status = static_cast<int*>(d_status); out.group_ok = static_cast<int*>(d_group_ok);
+    out.left_xy = static_cast<uint8_t*>(d_left_xy); out.right_xy = static_cast<uint8_t*>(d_right_xy);
+    out.group_failed = static_cast<uint32_t*>(d_group_failed); out.failed_index = cap ? static_cast<uint32_t*>(d_failed_index) : nullptr; out.failed_cap = cap;
+    out.summary = static_cast<uint32_t*>(d_summary);
+    const uint32_t flags = (b->last.pairing ? 1u : 0u) | (b->last.folded ? 2u : 0u);
+    if ((rc = results_enqueue(b->stream, b->status, n, G, ragged(b) ? b->d_group_off.p : nullptr, b->fold_failed, b->ok, flags, b->out_bytes,
+                              b->device_draws ? b->ingest_verdict.p : nullptr, b->finish_tiles.p, b->finish_groups.p, out))) return rc;
+    commit.commit(stage);
+    return 0;
+}
+
 bool same_srs(const ParamsHost& a, const ParamsHost& b) {
     auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
     return !memcmp(&a.g, &b.g, sizeof(G1A)) && same_g2(a.g2, b.g2) && same_g2(a.s_g2, b.s_g2);
@@ -829,6 +871,10 @@ int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t 
 int h2v_batch_upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, size_t n_instance_columns,
                             const size_t* col_lens, const void* d_rand_tail, size_t n_tail) {
     return upload_device_impl(b, n, d_proofs, proof_stride, d_instances, n_instance_columns, col_lens, d_rand_tail, n_tail);
+}
+int h2v_batch_finish_device(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
+                            void* d_summary) {
+    return finish_device_impl(b, d_status, d_group_ok, d_left_xy, d_right_xy, d_group_failed, d_failed_index, failed_cap, d_summary);
 }
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,

@@ -1,6 +1,7 @@
 // Format-conversion and small group kernels at the C-ABI boundary.
 #include "../../include/h2v.h"
 #include "ctx.h"
+#include "batch.h"   // the status words' rank codes (k_results_tiles)
 
 namespace h2v {
 
@@ -446,6 +447,142 @@ int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, ui
     hipLaunchKernelGGL(k_ingest_draws, dim3(n_tail ? (n_tail + 255) / 256 : 1), dim3(256), 0, s, (const uint4*)d_draws, (uint4*)d_tail, n_tail, n_tail / groups, n / groups,
                        d_group_off, groups, d_verdict, d_host_verdict);
     H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// ---- a finish into device memory (h2v_batch_finish_device, batch.hip): what finish_impl hands the host, written by kernels on the
+// batch's stream into the caller's device arrays — two launches, and a third when the failing proofs' indices are wanted.  No copy
+// engine (k_copy_words' reason above).  The scratch is a word per tile of 256 proofs and a word per group; the group words are ZERO
+// on entry and are left zero: k_results_close clears each after reading it, so no launch is spent on zeroing.
+//
+// k_results_tiles: one thread per proof, a workgroup per tile of RESULTS_TILE.  The status word is decoded (status_decode, batch.h) and
+// stored, 4 bytes per lane, consecutive lanes to consecutive words.  A wave's failing lanes (status != 0) are one 64-bit ballot: its
+// popcount goes into the tile's count through LDS, and into the groups' words by one atomicAdd per group present among them — the lanes of
+// the lowest failing lane's group are peeled off the ballot until it is empty, so a wave without a failing proof (every wave of a clean
+// launch) does no lookup and no atomic.  Only failing lanes find their group: a division for equal groups, k_ingest_draws' search of
+// off[0 .. G] otherwise.  The sums do not depend on the order of the additions.
+// gfx950 (tools/kernel_resources.py): 10 VGPRs, 28 SGPRs, no spills, no scratch, 16 bytes of LDS; 8 waves per SIMD.
+#define RESULTS_TILE 256u
+__global__ void __launch_bounds__(RESULTS_TILE) k_results_tiles(const int* __restrict__ status, uint32_t n, uint32_t gs, const uint32_t* __restrict__ off, uint32_t G,
+                                                                int* __restrict__ out_status, uint32_t* __restrict__ tile_count, uint32_t* __restrict__ group_failed) {
+    __shared__ uint32_t wave_count[RESULTS_TILE / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, i = blockIdx.x * RESULTS_TILE + t;
+    const int w = i < n ? status[i] : 0;
+    if (i < n && out_status) out_status[i] = status_decode(w);
+    unsigned long long failing = __ballot(w != 0);
+    if (lane == 0) wave_count[t >> 6] = (uint32_t)__popcll(failing);
+    uint32_t g = 0;
+    if (w != 0) {
+        if (off) {
+            uint32_t lo = 0, hi = G;   // the last g with off[g] <= i (off[0] = 0, off[G] = n > i)
+            while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+            g = lo;
+        } else g = i / gs;
+    }
+    while (failing) {   // (the same value in every lane of the wave)
+        const uint32_t leader = (uint32_t)__ffsll((long long)failing) - 1;
+        const uint32_t gl = (uint32_t)__shfl((int)g, (int)leader);
+        const unsigned long long same = __ballot(w != 0 && g == gl);
+        if (lane == leader) atomicAdd(&group_failed[gl], (uint32_t)__popcll(same));
+        failing &= ~same;
+    }
+    __syncthreads();
+    if (t == 0) tile_count[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+// k_results_close: ONE workgroup, behind k_results_tiles on the stream (its own launch: see DESIGN.md, "A finish into device memory").
+//  - the tile counts become their exclusive prefix sums in place, 256 tiles per pass with the running total carried from pass to pass
+//    (as k_seg_mult_scan_tiles carries its value); the total is the number of failing proofs;
+//  - a thread per group: group_ok = no failing proof && !fold_failed && (no pairing of the launch's own || ok) && no draw fault, the
+//    group's word of the scratch read and cleared, the 128 bytes of its accumulators split into the caller's two arrays (16 bytes a thread);
+//  - the summary words (h2v.h).
+// `ok` is host memory behind a mapped pointer, written by the pairing kernel earlier on the same stream: it is read by an atomic load
+// of SYSTEM scope, which goes past the vector cache and the device's L2 to the memory itself; a plain (cached) vector load could be
+// served a line that was fetched before the pairing kernel's store arrived.
+// gfx950 (tools/kernel_resources.py): 18 VGPRs, 49 SGPRs, no spills, no scratch, 1028 bytes of LDS.
+__global__ void __launch_bounds__(256) k_results_close(uint32_t* __restrict__ tile_count, uint32_t tiles, uint32_t* __restrict__ group_failed, uint32_t G, uint32_t n,
+                                                       const uint32_t* __restrict__ fold_failed, const uint32_t* ok, uint32_t flags, const uint4* __restrict__ out_bytes,
+                                                       const uint32_t* __restrict__ fault, int* __restrict__ out_group_ok, uint4* __restrict__ out_left,
+                                                       uint4* __restrict__ out_right, uint32_t* __restrict__ out_group_failed, uint32_t* __restrict__ summary) {
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t n_ok;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) n_ok = 0;
+    uint32_t total = 0;
+    for (uint32_t base = 0; base < tiles; base += 256) {
+        const uint32_t v = base + t < tiles ? tile_count[base + t] : 0;
+        part[t] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < 256; d <<= 1) {
+            const uint32_t below = t >= d ? part[t - d] : 0;
+            __syncthreads();
+            part[t] += below;
+            __syncthreads();
+        }
+        if (base + t < tiles) tile_count[base + t] = total + part[t] - v;
+        total += part[255];
+        __syncthreads();
+    }
+    __syncthreads();   // (n_ok = 0 before the first addition, also without a tile)
+    const uint32_t fault_word = fault ? fault[0] : 0xffffffffu;
+    for (uint32_t g = t; g < G; g += 256) {
+        const uint32_t failed = group_failed[g];
+        group_failed[g] = 0;
+        const uint32_t paired = (flags & 1u) ? __hip_atomic_load(&ok[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 1u;
+        const bool good = !failed && !fold_failed[g] && paired && fault_word == 0xffffffffu;
+        if (out_group_ok) out_group_ok[g] = good ? 1 : 0;
+        if (out_group_failed) out_group_failed[g] = failed;
+        if (good) atomicAdd(&n_ok, 1u);
+    }
+    if (out_left || out_right)
+        for (uint32_t q = t; q < 8 * G; q += 256) {   // 16-byte word q & 7 of group q >> 3: 0 .. 3 left, 4 .. 7 right
+            const uint32_t g = q >> 3, k = q & 7u;
+            uint4* const dst = k < 4 ? out_left : out_right;
+            if (dst) dst[4 * (size_t)g + (k & 3u)] = out_bytes[q];
+        }
+    __syncthreads();
+    if (t < 8 && summary) summary[t] = t == 0 ? fault_word : t == 1 ? total : t == 2 ? n_ok : t == 3 ? n : t == 4 ? G : t == 5 ? flags : 0u;
+}
+// k_results_scatter: the failing proofs' indices, ascending.  A tile's failing lanes go to [the tile's offset (k_results_close's prefix
+// sum) + the lane's rank inside the tile), the rank being the failing lanes below it in its wave's ballot plus the earlier waves' counts
+// from LDS; tiles follow each other in the offsets and lanes in the ranks, so the output is sorted without a sort.  A position from
+// `cap` on is not written.
+// gfx950 (tools/kernel_resources.py): 14 VGPRs, 20 SGPRs, no spills, no scratch, 16 bytes of LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(RESULTS_TILE) k_results_scatter(const int* __restrict__ status, uint32_t n, const uint32_t* __restrict__ tile_offset,
+                                                                  uint32_t* __restrict__ failed_index, uint32_t cap) {
+    __shared__ uint32_t wave_count[RESULTS_TILE / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6, i = blockIdx.x * RESULTS_TILE + t;
+    const int w = i < n ? status[i] : 0;
+    const unsigned long long failing = __ballot(w != 0);
+    if (lane == 0) wave_count[wave] = (uint32_t)__popcll(failing);
+    __syncthreads();
+    if (w == 0) return;
+    uint32_t pos = tile_offset[blockIdx.x] + (uint32_t)__popcll(failing & ((1ull << lane) - 1ull));
+    for (uint32_t k = 0; k < wave; ++k) pos += wave_count[k];
+    if (pos < cap) failed_index[pos] = i;
+}
+int results_enqueue(hipStream_t s, const int* d_status, uint32_t n, uint32_t groups, const uint32_t* d_group_off, const uint32_t* d_fold_failed, const uint32_t* d_ok,
+                    uint32_t flags, const uint8_t* d_out_bytes, const uint32_t* d_fault, uint32_t* d_tile_words, uint32_t* d_group_words, const ResultsOut& out) {
+    if (!groups || !d_fold_failed || !d_out_bytes || !d_group_words || (n && (!d_status || !d_tile_words)) || ((flags & 1u) && !d_ok)) { set_last_error("results_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (((uintptr_t)d_out_bytes | (uintptr_t)out.left_xy | (uintptr_t)out.right_xy) & 15u) { set_last_error("results_enqueue: accumulator bytes off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
+    if (((uintptr_t)d_status | (uintptr_t)out.status | (uintptr_t)out.group_ok | (uintptr_t)out.group_failed | (uintptr_t)out.failed_index | (uintptr_t)out.summary) & 3u) {
+        set_last_error("results_enqueue: a word array off a 4-byte boundary"); return H2V_ERR_BAD_ARGUMENT;
+    }
+    if (!d_group_off && n % groups) { set_last_error("results_enqueue: equal groups do not divide n"); return H2V_ERR_BAD_ARGUMENT; }
+    if (groups > (1u << 24) || (flags & ~3u)) { set_last_error("results_enqueue: too many groups, or an unknown flag"); return H2V_ERR_BAD_ARGUMENT; }
+    if (out.failed_index && !out.failed_cap) { set_last_error("results_enqueue: failed_cap is 0"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + RESULTS_TILE - 1) / RESULTS_TILE);
+    uint32_t* const tile_words = d_tile_words;
+    uint32_t* const group_words = d_group_words;
+    if (tiles) {
+        hipLaunchKernelGGL(k_results_tiles, dim3(tiles), dim3(RESULTS_TILE), 0, s, d_status, n, n / groups, d_group_off, groups, out.status, tile_words, group_words);
+        H2V_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_results_close, dim3(1), dim3(256), 0, s, tile_words, tiles, group_words, groups, n, d_fold_failed, d_ok, flags, (const uint4*)d_out_bytes, d_fault,
+                       out.group_ok, (uint4*)out.left_xy, (uint4*)out.right_xy, out.group_failed, out.summary);
+    H2V_HIP_CHECK(hipGetLastError());
+    if (tiles && out.failed_index) {
+        hipLaunchKernelGGL(k_results_scatter, dim3(tiles), dim3(RESULTS_TILE), 0, s, d_status, n, tile_words, out.failed_index, out.failed_cap);
+        H2V_HIP_CHECK(hipGetLastError());
+    }
     return 0;
 }
 int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, uint32_t* d_is_identity, uint32_t n, size_t lds_reserve) {

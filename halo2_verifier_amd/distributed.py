@@ -257,6 +257,22 @@ class ShardedBatch:
         self._finished = self.batch.finish_groups(raw_statuses=raw_statuses)
         return self._finished
 
+    def finish_tensors(self):
+        """finish() into device memory (Batch.finish_into), without a host wait -> dict of seven tensors on the rank's device: status
+        int32 [n] (this rank's proofs), group_ok int32 [groups], left_xy / right_xy uint8 [groups, 64] (the whole sharded batch's, as
+        finish() gives them), group_failed int32 [groups] (this rank's failing proofs per group), failed_index int32 [n] (their
+        indices in ascending order, then -1), summary int32 [Batch.SUMMARY_WORDS].  They are written on the batch's stream and torch's
+        current stream is made to wait for it on the device: work queued there afterwards sees them.  finish() may still follow."""
+        import torch
+        n, g, dev = self.batch.n, self.batch.groups, self.device
+        out = {"status": torch.empty(n, dtype=torch.int32, device=dev), "group_ok": torch.empty(g, dtype=torch.int32, device=dev),
+               "left_xy": torch.empty((g, 64), dtype=torch.uint8, device=dev), "right_xy": torch.empty((g, 64), dtype=torch.uint8, device=dev),
+               "group_failed": torch.empty(g, dtype=torch.int32, device=dev), "failed_index": torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev),
+               "summary": torch.empty(self.batch.SUMMARY_WORDS, dtype=torch.int32, device=dev)}
+        self.batch.finish_into(**out)
+        out["failed_index"] = out["failed_index"][:n]
+        return out
+
     def identify(self, verdicts=None):
         """After finish(): which of THIS rank's proofs fail the pairing (Batch.identify) -> (local statuses, range_checks).  Local to
         the rank, no collective: a shard's own sum, sum over its proofs of (the product of all later draws of the batch) * Guard_i, is a

@@ -1359,6 +1359,97 @@ class Batch:
         statuses = bytes(memoryview(st).cast('B')[:4 * self.n]) if raw_statuses else memoryview(st).cast('B').cast('i').tolist()[:self.n]
         return [bool(v) for v in ok], statuses, _points(left, g), _points(right, g)
 
+    SUMMARY_WORDS = 8   # H2V_SUMMARY_WORDS: [draw fault or 0xffffffff, failing proofs, accepted groups, n, groups, flags, 0, 0]
+
+    def finish_device(self, status_addr=None, group_ok_addr=None, left_xy_addr=None, right_xy_addr=None, group_failed_addr=None,
+                      failed_index_addr=None, failed_cap=0, summary_addr=None):
+        """finish_groups() into device memory (h2v_batch_finish_device), given as addresses, None = not wanted: n int32 statuses, `groups`
+        int32 verdicts, 64 bytes per group of either channel, `groups` uint32 counts of failing proofs, the failing proofs' indices in
+        ascending order (the first failed_cap of them), SUMMARY_WORDS uint32.  Device work on the batch's stream only: the call waits
+        for nothing, leaves the batch's stage alone and may be repeated; the caller orders its readers behind the batch's stream.  The
+        batch must be launched (or finished)."""
+        def address(v, what):
+            if v is None:
+                return 0
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise TypeError(f"{what} must be an integer address or None, got {type(v).__name__}")
+            if v <= 0 or v >> 64:
+                raise ValueError(f"{what} must be in (0, 2^64), got {int(v)}")
+            if v % 16:
+                raise ValueError(f"{what} must be 16-byte aligned, got {int(v):#x}")
+            return int(v)
+
+        addrs = [address(v, what) for v, what in ((status_addr, "status_addr"), (group_ok_addr, "group_ok_addr"), (left_xy_addr, "left_xy_addr"),
+                                                  (right_xy_addr, "right_xy_addr"), (group_failed_addr, "group_failed_addr"),
+                                                  (failed_index_addr, "failed_index_addr"), (summary_addr, "summary_addr"))]
+        if isinstance(failed_cap, bool) or not isinstance(failed_cap, numbers.Integral):
+            raise TypeError(f"failed_cap must be an integer, got {type(failed_cap).__name__}")
+        if failed_cap < 0 or failed_cap >> 64:
+            raise ValueError(f"failed_cap must be in [0, 2^64), got {int(failed_cap)}")
+        if addrs[5] and not failed_cap:
+            raise ValueError("failed_cap must be at least 1 when failed_index_addr is given")
+        vp = [ctypes.c_void_p(a) for a in addrs]
+        check(self._lib.h2v_batch_finish_device(self._h, *vp[:6], int(failed_cap) if addrs[5] else 0, vp[6]))
+
+    @staticmethod
+    def _tensor_words(t, what, device, dtypes, count):
+        """A duck-typed tensor as an output array: one of `dtypes`, on `device`, contiguous, `count` elements (None: any number, at
+        least one) -> (address, elements)"""
+        for attr in ("dtype", "device", "shape", "stride", "data_ptr"):
+            if not hasattr(t, attr):
+                raise TypeError(f"{what} must be a tensor (no .{attr})")
+        name = str(t.dtype).rpartition(".")[2]
+        if name not in dtypes:
+            raise TypeError(f"{what} must be a tensor of {' or '.join(dtypes)}, got {t.dtype}")
+        if getattr(t.device, "type", None) != "cuda" or t.device.index != device:
+            raise ValueError(f"{what} must be on the context's device (cuda:{device}), got {t.device}")
+        shape, stride = tuple(t.shape), tuple(t.stride())
+        numel, expect = 1, 1
+        for size in shape:
+            numel *= size
+        for size, step in zip(reversed(shape), reversed(stride)):   # (row-major without gaps; a dimension of one element may have any stride)
+            if size != 1 and step != expect:
+                raise ValueError(f"{what} must be contiguous, got shape {shape} and strides {stride}")
+            expect *= size
+        if count is None and not numel:
+            raise ValueError(f"{what} must hold at least one element")
+        if count is not None and numel != count:
+            raise ValueError(f"{what} must hold {count} elements, got {numel} (shape {shape})")
+        return (int(t.data_ptr()) if numel else None), numel   # (no element: nothing to write, and no address)
+
+    def finish_into(self, status=None, group_ok=None, left_xy=None, right_xy=None, group_failed=None, failed_index=None, summary=None):
+        """finish_device() into tensors (torch's, or anything with dtype / device / shape / stride() / data_ptr()), each contiguous and
+        on the batch's device, None = not wanted: status int32 [n], group_ok int32 [groups], left_xy / right_xy uint8 [groups, 64],
+        group_failed int32 or uint32 [groups], failed_index int32 or uint32 (as many failing proofs as it has elements are reported),
+        summary int32 or uint32 [SUMMARY_WORDS].  The batch's stream first waits for the tensors' current stream (whatever made or
+        filled them), and that stream then waits, on the device, for the batch's kernels: work queued on it afterwards sees the
+        results.  The host waits for nothing; the tensors are the caller's to keep alive until that work has run."""
+        device, g = self.ctx.device, self.groups
+        words = ("int32", "uint32")
+        spec = ((status, "status", ("int32",), self.n), (group_ok, "group_ok", ("int32",), g), (left_xy, "left_xy", ("uint8",), 64 * g),
+                (right_xy, "right_xy", ("uint8",), 64 * g), (group_failed, "group_failed", words, g), (failed_index, "failed_index", words, None),
+                (summary, "summary", words, self.SUMMARY_WORDS))
+        given = [t for t, *_ in spec if t is not None]
+        if not given:
+            raise ValueError("finish_into: no output tensor given")
+        got = [(None, 0) if t is None else self._tensor_words(t, what, device, dtypes, count) for t, what, dtypes, count in spec]
+        import sys
+        cuda = getattr(sys.modules.get(type(given[0]).__module__.partition(".")[0]), "cuda", None)
+        if cuda is None:
+            raise TypeError("the tensors' module has no cuda streams to order the results by")
+        current, mine = cuda.current_stream(given[0].device), self.stream
+        ordered = current.cuda_stream != mine
+        if ordered:
+            batch_stream = cuda.ExternalStream(mine, device=given[0].device)
+            before = cuda.Event()
+            before.record(current)
+            batch_stream.wait_event(before)
+        self.finish_device(*[a for a, _ in got[:6]], got[5][1], got[6][0])
+        if ordered:
+            after = cuda.Event()
+            after.record(batch_stream)
+            current.wait_event(after)
+
     def recheck(self, ranges):
         """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
         ranges: list of (first, count), each inside one group of the launch.  -> (oks, lefts, rights): one verdict and the two

@@ -594,6 +594,32 @@ int h2v_batch_set_groups(h2v_batch* b, size_t groups);
 int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups);
 /* As h2v_batch_finish for a grouped batch: group_ok[n_groups], out_left_xy / out_right_xy = n_groups x 64 bytes. */
 int h2v_batch_finish_groups(h2v_batch* b, int* per_proof_status, int* group_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t n_groups);
+/* h2v_batch_finish_groups INTO DEVICE MEMORY, for a consumer that lives on the GPU (a tensor pipeline that masks the rejected proofs, a
+ * rank that gathers statuses, a service that queues launches back to back): the results of the last launch are written by kernels on
+ * the batch's stream into the caller's device arrays, bit for bit what h2v_batch_finish_groups would write to host arrays for the same
+ * launch.  The call waits for nothing — no stream or event synchronise, no blocking copy — and returns once the kernels are enqueued;
+ * the caller orders its readers behind the batch's stream (h2v_batch_stream).  Every output pointer may be NULL (not wanted):
+ *   d_status        n int32: the per-proof codes (0 or H2V_ERR_*)
+ *   d_group_ok      G int32: 0 / 1
+ *   d_left_xy, d_right_xy   G x 64 bytes each
+ *   d_group_failed  G uint32: the proofs of the group whose status is not 0
+ *   d_failed_index  the proofs whose status is not 0, ASCENDING, the first failed_cap of them; nothing is written from position
+ *                   failed_cap on (failed_cap is read only with d_failed_index, and 0 is refused)
+ *   d_summary       H2V_SUMMARY_WORDS uint32:
+ *     [0] 0xffffffff, or the lowest index of a non-canonical draw of an upload that took its draws from device memory
+ *         (h2v_batch_upload_device).  With such a fault every group_ok is 0 and [2] is 0; statuses and bytes are what the launch left.
+ *     [1] the number of proofs whose status is not 0 (the true count, also above failed_cap)
+ *     [2] the number of groups with group_ok = 1        [3] n        [4] G
+ *     [5] flags: bit 0 the launch ran its own pairing checks, bit 1 a fold ran since the launch (h2v_batch_fold_check_enqueue)
+ *     [6], [7] 0
+ * The batch must be launched or finished; its stage does not change, so the call may be repeated, and h2v_batch_finish(_groups) before
+ * or after it returns exactly what it returns without it (after a draw fault: the refusal, and the batch left empty).
+ * Checked on the host before any device work (H2V_ERR_BAD_ARGUMENT, h2v_last_error names the argument, the batch untouched): the stage;
+ * every pointer given is device memory of the context's device, 16-byte aligned, and the bytes written to it lie inside its
+ * allocation (d_failed_index: min(failed_cap, n) words). */
+#define H2V_SUMMARY_WORDS 8
+int h2v_batch_finish_device(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed,
+                            void* d_failed_index, size_t failed_cap, void* d_summary);
 /* Pairing checks of ranges of the last FINISHED launch of b (h2v_batch_finish / _finish_groups), on its resident per-proof Guard
  * scalars: no stage before the MSM runs again.  Range i = proofs [first[i], first[i] + count[i]); count > 0; every range inside one
  * group of the launch (else H2V_ERR_BAD_ARGUMENT: the last proof of every group has multiplier 1, so a range over two groups could

@@ -552,6 +552,25 @@ inline void upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t p
     check(h2v_batch_upload_device(b, n, d_proofs, proof_stride, d_instances, col_lens.size(), col_lens.data(), d_rand_tail, d_rand_tail ? n_tail : 0));
 }
 
+// A staged batch's finish into device memory (h2v_batch_finish_device): the results of the last launch written by kernels on the batch's
+// stream into the caller's device arrays, nothing waited for.  Null = not wanted.  What the host can check is checked here first.
+struct DeviceResults {
+    void* status = nullptr;         // n int32
+    void* group_ok = nullptr;       // groups int32
+    void* left_xy = nullptr;        // groups x 64 bytes
+    void* right_xy = nullptr;       // groups x 64 bytes
+    void* group_failed = nullptr;   // groups uint32
+    void* failed_index = nullptr;   // failed_cap uint32, ascending
+    size_t failed_cap = 0;
+    void* summary = nullptr;        // H2V_SUMMARY_WORDS uint32
+};
+inline void finish_device(h2v_batch* b, const DeviceResults& out) {
+    for (const void* p : {out.status, out.group_ok, out.left_xy, out.right_xy, out.group_failed, out.failed_index, out.summary})
+        if (reinterpret_cast<uintptr_t>(p) % 16) throw Failure(H2V_ERR_BAD_ARGUMENT, "finish_device: a device pointer off a 16-byte boundary");
+    if (out.failed_index && !out.failed_cap) throw Failure(H2V_ERR_BAD_ARGUMENT, "finish_device: failed_cap is 0");
+    check(h2v_batch_finish_device(b, out.status, out.group_ok, out.left_xy, out.right_xy, out.group_failed, out.failed_index, out.failed_index ? out.failed_cap : 0, out.summary));
+}
+
 // Many AccumulatorStrategy batches of their own sizes in few launches (h2v_verify_batches): every batch is a list of (instances, proof)
 // in verify_proof order and none is empty; one instance shape for the whole call; rand32: one 32-byte draw per proof of the call, batch
 // after batch, or empty = OS RNG.  -> per batch what its own AccumulatorStrategy::finalize() gives: verdict, statuses, the two channels.

@@ -44,6 +44,7 @@ pub const H2V_TRANSCRIPT_KECCAK256: c_int = 1;
 pub const H2V_ACC_RECORD_PIECES: usize = 6;
 /// bytes one shard contributes per group to a sharded batch ([failed, parts, shift, 0] + 2 x 6 Jacobian pieces)
 pub const H2V_ACC_RECORD_BYTES: usize = 1312;
+pub const H2V_SUMMARY_WORDS: usize = 8;
 /// entries a leg journal holds at most, the base included (h2v_accumulator_journal_begin)
 pub const H2V_ACC_JOURNAL_MAX: usize = 4096;
 /// sources one h2v_accumulator_merge / h2v_accumulator_merge_states call takes
@@ -159,6 +160,8 @@ extern "C" {
     pub fn h2v_batch_set_group_sizes(b: *mut h2v_batch, sizes: *const usize, n_groups: usize) -> c_int;
     pub fn h2v_batch_finish_groups(b: *mut h2v_batch, per_proof_status: *mut c_int, group_ok: *mut c_int, out_left_xy: *mut u8, out_right_xy: *mut u8,
                                    n_groups: usize) -> c_int;
+    pub fn h2v_batch_finish_device(b: *mut h2v_batch, d_status: *mut c_void, d_group_ok: *mut c_void, d_left_xy: *mut c_void, d_right_xy: *mut c_void,
+                                   d_group_failed: *mut c_void, d_failed_index: *mut c_void, failed_cap: usize, d_summary: *mut c_void) -> c_int;
     pub fn h2v_batch_recheck(b: *mut h2v_batch, n_ranges: usize, first: *const usize, count: *const usize, range_ok: *mut c_int,
                              out_left_xy: *mut u8, out_right_xy: *mut u8) -> c_int;
     pub fn h2v_batches_recheck(batches: *const *mut h2v_batch, n_batches: usize, n_ranges: usize, batch_of_range: *const u32, first: *const usize,

@@ -180,6 +180,20 @@ impl GpuStagedBatch {
         status.truncate(self.n);
         Ok((ok.iter().map(|&v| v == 1).collect(), status))
     }
+    /// `finish` into device memory (h2v_batch_finish_device): the launch's results written by kernels on the batch's stream, nothing
+    /// waited for; the stage does not change and the call may be repeated.  Every pointer may be null (not wanted): `n` i32 statuses,
+    /// `groups` i32 verdicts, 64 bytes per group of either channel, `groups` u32 counts of failing proofs, the first `failed_cap`
+    /// failing proofs' indices in ascending order, H2V_SUMMARY_WORDS u32.
+    /// Safety: every pointer given is device memory with room for what the call writes, 16-byte aligned, and is read only behind the
+    /// batch's stream.
+    pub unsafe fn finish_device(&mut self, d_status: *mut core::ffi::c_void, d_group_ok: *mut core::ffi::c_void, d_left_xy: *mut core::ffi::c_void,
+                                d_right_xy: *mut core::ffi::c_void, d_group_failed: *mut core::ffi::c_void, d_failed_index: *mut core::ffi::c_void, failed_cap: usize,
+                                d_summary: *mut core::ffi::c_void) -> Result<(), Error> {
+        if (d_status as usize | d_group_ok as usize | d_left_xy as usize | d_right_xy as usize | d_group_failed as usize | d_failed_index as usize | d_summary as usize) % 16 != 0
+            || (!d_failed_index.is_null() && failed_cap == 0) { return Err(Error::InvalidInstances); }
+        let rc = h2v_batch_finish_device(self.b, d_status, d_group_ok, d_left_xy, d_right_xy, d_group_failed, d_failed_index, if d_failed_index.is_null() { 0 } else { failed_cap }, d_summary);
+        if rc != 0 { Err(map_err(rc)) } else { Ok(()) }
+    }
     /// Which proofs of the finished launch fail the pairing (h2v_batch_identify): every proof's verdict as `verify_proof` under
     /// `SingleStrategy` returns it, the pairing of every group's own accumulators, and the number of range checks the search ran.
     /// `own_records`: the device address of the records h2v_batch_export_accumulators wrote for this launch — needed after a fold
