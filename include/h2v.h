@@ -16,12 +16,21 @@
  *     (VerifyingKey::write  halo2_verifier/src/plonk/vk.rs:41-64;
  *      ParamsKZG::write_custom  halo2_verifier/src/poly/kzg/commitment.rs:142-152).
  *   - serde format codes follow helpers.rs:7-19: 0 Processed, 1 RawBytes, 2 RawBytesUnchecked.
- *   - Threading: a context may be shared between host threads: its VK / params / compiled plans are
- *     immutable after creation, and the one-shot entry points (h2v_verify_batch, h2v_verify_each,
- *     h2v_guard_msm, h2v_msm_g1, h2v_pairing_check, h2v_guards_check_each, h2v_fold_check) serialise themselves on an internal
- *     lock (they share the context's stream and a cached workspace).  A batch object owns one HIP stream
- *     and its device workspace and must be used from one thread at a time; several batches may be in
- *     flight on one context.
+ *   - Threading: a context may be shared between host threads.  Its VK and params are immutable after creation; its compiled plans
+ *     are a bounded cache behind a lock of its own, and a plan stays pinned while a batch holds it.  The entry points that run on the
+ *     context's stream with its cached workspaces serialise themselves on the context's lock — on the lock of every context they
+ *     are given, taken in address order, so that calls over overlapping sets of contexts cannot deadlock.  They are:
+ *       h2v_verify_batch, h2v_verify_batch_shapes, h2v_verify_batch_keys, h2v_verify_batch_seeded, h2v_verify_batches,
+ *       h2v_verify_each, h2v_verify_batch_identify, h2v_verify_batch_keys_identify, h2v_verify_batch_seeded_identify,
+ *       h2v_guard_msm, h2v_msm_g1, h2v_pairing_check, h2v_guards_check_each, h2v_fold_check,
+ *       h2v_msm_append_terms, h2v_msm_add_msm, h2v_msm_scale, h2v_msm_terms, h2v_msm_eval_many, h2v_dual_msm_check_many,
+ *       h2v_msm_destroy, h2v_accumulator_process, h2v_accumulator_add_msm, h2v_accumulator_add_msms, h2v_ctx_set_tuning.
+ *     Some of them take the lock several times in a row — the seeded forms (two MSMs over the seed, its pairing, then the batch) and
+ *     the accumulator's add_msm (two MSMs) — so another thread's call may run between their steps; every step is complete in itself.
+ *     The tuning call writes under the lock, but launches of staged batches read the setting without it: set it while the context is
+ *     idle.  A batch, an accumulator or an MSM object is used by one thread at a time (a batch and an accumulator own a HIP stream and
+ *     their device memory); many of them may be in flight on one context, and one accumulator per feeder thread, merged at the end,
+ *     is the intended use.  An object may pass from one thread to another between calls.  The text of the last error is per thread.
  */
 #ifndef H2V_H
 #define H2V_H
