@@ -12,4 +12,6 @@ from .verifier import (  # noqa: F401
     PlonkError, Batch, MultiOpen, TranscriptKind, verify_batch_keys, verify_batch_keys_identify, recheck_batches, Accumulator,
     MSMKZG, DualMSM, eval_many, dual_check_many,
 )
+from . import draws  # noqa: F401
+from .draws import expand, expand_tensor, new_seed  # noqa: F401
 from . import distributed  # noqa: F401

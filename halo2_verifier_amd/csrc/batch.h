@@ -162,6 +162,9 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
 int finish_device_impl(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
                        void* d_summary);
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
+// `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary (who / does: the entry
+// point and the verb of the error message): what every entry point that takes a caller's device pointer holds it to
+int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who = "h2v_batch_upload_device", const char* does = "reads");
 bool pairing_passed(const h2v_batch* b, uint32_t g);
 // The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
 // problem is one slot of every proof.  channel_problems builds its problems from these counts.

@@ -398,7 +398,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
 
 // `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary
 // (who / does: the entry point and the verb of the error message)
-static int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who = "h2v_batch_upload_device", const char* does = "reads") {
+int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who, const char* does) {
     const std::string w = std::string(who) + ": " + what;
     if ((uintptr_t)p & 15u) { set_last_error(w + " is not 16-byte aligned"); return H2V_ERR_BAD_ARGUMENT; }
     hipPointerAttribute_t at;

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/h2v.h"
+#include "../../include/h2v_draws.h"
 #include "curve.hip.h"
 
 namespace h2v {
@@ -263,5 +264,13 @@ int accumulator_merge_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n
 // accumulator is replaced: record 0 is its scaled self), and with d_sums the unscaled pair of leg g < n - 1, d_pairs[2 g], [2 g + 1]
 // -> d_sums[2 slot], [2 slot + 1], slot = d_slots[g] (d_slots null: g).  team: as above; 0 = accumulator_merge_team(n - 1).
 int accumulator_legs_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n, uint32_t team, const G1J* d_pairs, const uint32_t* d_slots, G1J* d_sums, G1J* d_acc);
+
+// ------------------------------------------------------------------ draws from a seed (verify_kernels.hip, draws.hip; include/h2v_draws.h)
+// d_out[32 j ..] <- draw(seed32, first + j) for j < n, canonical bytes (k_expand_draws: one launch, 16 draws per wave; the seed
+// travels as kernel arguments).  d_out lies on a 16-byte boundary; first + n does not wrap; n <= H2V_DRAWS_DEVICE_MAX (the launch stays
+// below 2^32 threads).  n = 0 launches nothing.
+int expand_draws_enqueue(hipStream_t s, const uint8_t seed32[32], uint64_t first, size_t n, void* d_out);
+// the same values on the host (a BLAKE2b-512 single-block compression of its own, RFC 7693)
+void expand_draws_host(const uint8_t seed32[32], uint64_t first, size_t n, uint8_t* out32);
 
 }  // namespace h2v

@@ -322,6 +322,42 @@ __global__ void __launch_bounds__(64) k_transcript(const unsigned long long* __r
     }
 }
 
+// The draws of a seed (include/h2v_draws.h):  draw(seed, i) = LE512(BLAKE2b-512(seed[32] | LE64(i), personal "h2v-draws-v1")) mod r,
+// as 32 canonical little-endian bytes at out[2 i], out[2 i + 1].  One draw per quad of lanes, 16 per wave, one compression each: the
+// 40-byte message is a single final block.  The seed arrives as four kernel arguments (no buffer, no copy); i = first + the draw's
+// number, a 64-bit sum (first + n does not wrap: the entry points refuse it).
+__global__ void __launch_bounds__(64) k_expand_draws(unsigned long long seed0, unsigned long long seed1, unsigned long long seed2, unsigned long long seed3,
+                                                     unsigned long long first, unsigned long long n, uint4* __restrict__ out) {
+    __shared__ unsigned long long ex_lds[16 * TR4_MSG_STRIDE];   // [16][TR4_MSG_STRIDE] message block; its first 8 words take the digest afterwards
+    const uint32_t tid = threadIdx.x, r = tid & 3u, pq = tid >> 2;
+    const unsigned long long d_raw = (unsigned long long)blockIdx.x * 16 + pq, d = d_raw < n ? d_raw : n - 1;   // lanes beyond n shadow the last draw (uniform control flow)
+    unsigned long long* msg = ex_lds + pq * TR4_MSG_STRIDE;
+    uint32_t sig[12];
+#pragma unroll
+    for (int rd = 0; rd < 12; ++rd)
+        sig[rd] = (uint32_t)BLAKE_SIGMA[rd][2 * r] | ((uint32_t)BLAKE_SIGMA[rd][2 * r + 1] << 4) | ((uint32_t)BLAKE_SIGMA[rd][8 + 2 * r] << 8) | ((uint32_t)BLAKE_SIGMA[rd][9 + 2 * r] << 12);
+    // parameter block: digest 64, no key, fanout = depth = 1, personal "h2v-draws-v1" and four zero bytes
+    const unsigned long long pers0 = 0x776172642d763268ULL, pers1 = 0x0000000031762d73ULL;  // "h2v-draw" "s-v1\0\0\0\0" little endian
+    unsigned long long h0 = BLAKE_IV[r] ^ (r == 0 ? 0x01010040ULL : 0ULL), h1 = BLAKE_IV[4 + r] ^ (r == 2 ? pers0 : (r == 3 ? pers1 : 0ULL));
+    // lane r writes message words 4 r .. 4 r + 3: the seed, the index, zeros
+    msg[4 * r + 0] = r == 0 ? seed0 : (r == 1 ? first + d : 0ULL);
+    msg[4 * r + 1] = r == 0 ? seed1 : 0ULL;
+    msg[4 * r + 2] = r == 0 ? seed2 : 0ULL;
+    msg[4 * r + 3] = r == 0 ? seed3 : 0ULL;
+    __syncthreads();
+    blake2b_compress_quad(h0, h1, msg, sig, 40, true, r);
+    __syncthreads();   // (every lane of the quad has read its message words)
+    msg[r] = h0; msg[4 + r] = h1;
+    __syncthreads();
+    // 64 digest bytes -> Fr -> canonical words: the quad's lanes all hold the draw, lanes 0 and 1 store its two halves
+    uint32_t w32[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const unsigned long long v = msg[i]; w32[2 * i] = (uint32_t)v; w32[2 * i + 1] = (uint32_t)(v >> 32); }
+    uint32_t raw[8];
+    Fr::from_uniform_words(w32).to_raw(raw);
+    if (d_raw < n && r < 2) out[2 * d + r] = r == 0 ? make_uint4(raw[0], raw[1], raw[2], raw[3]) : make_uint4(raw[4], raw[5], raw[6], raw[7]);
+}
+
 // ------------------------------------------------------------------ legacy Keccak-256 transcript (transcript/mod.rs:234-272)
 __device__ __forceinline__ unsigned long long rotl64(unsigned long long x, int c) { return c ? (x << c) | (x >> (64 - c)) : x; }
 __constant__ unsigned long long KECCAK_RC[24] = {
@@ -845,6 +881,16 @@ int transcript_stage_enqueue(hipStream_t s, const StageArgs& g) {
         hipLaunchKernelGGL(k_transcript_keccak, dim3((n + 63) / 64), dim3(64), 0, s, g.words, n_words, g.pd->squeeze_at.p, nsq, n, g.chal);
     else
         hipLaunchKernelGGL(k_transcript, dim3((n + 15) / 16), dim3(64), lds, s, g.words, n_words, g.pd->squeeze_at.p, nsq, n, g.chal);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int expand_draws_enqueue(hipStream_t s, const uint8_t seed32[32], uint64_t first, size_t n, void* d_out) {
+    if (!n) return 0;
+    if (n > (size_t)H2V_DRAWS_DEVICE_MAX) { set_last_error("expand_draws: more than H2V_DRAWS_DEVICE_MAX draws for one launch"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t blocks = (n - 1) / 16 + 1;   // (< 2^26: the launch's 64 x blocks threads stay below 2^32, which HIP refuses)
+    unsigned long long w[4];
+    for (int j = 0; j < 4; ++j) { w[j] = 0; for (int k = 7; k >= 0; --k) w[j] = (w[j] << 8) | seed32[8 * j + k]; }
+    hipLaunchKernelGGL(k_expand_draws, dim3((uint32_t)blocks), dim3(64), 0, s, w[0], w[1], w[2], w[3], (unsigned long long)first, (unsigned long long)n, (uint4*)d_out);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

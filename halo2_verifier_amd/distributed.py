@@ -11,9 +11,11 @@ Multipliers: proof i of the whole batch is scaled by the product of the Fr::rand
 draws from its first proof to the END of the batch (its "tail").
 
 Entry points
-  verify_batch_sharded(ctx, proofs, instances, rand=None, group=None)
+  verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, seed=None)
       N x verify_proof on ONE AccumulatorStrategy + finalize(), the proofs sharded over the ranks of a torch.distributed group.
-      Every rank passes the whole batch and gets the same (ok, statuses, left_xy, right_xy).
+      Every rank passes the whole batch and gets the same (ok, statuses, left_xy, right_xy).  With seed (True: common_seed, one
+      32-byte broadcast; bytes: given) the draws are draws.expand(seed, 0, n) and every rank expands only its own tail
+      (seeded_tail, seeded_tail_tensor): no n x 32-byte broadcast.
   verify_batch_sharded_local(ctx, proofs, instances, rand, world)
       the same computation with the `world` shards run one after the other on ONE GPU (no process group): sharding invariance
       at full size on a single device, and hosts with one GPU.
@@ -144,6 +146,51 @@ def common_draws_tensor(n: int, rand, group=None, device=None):
     return buf[:n]
 
 
+def common_seed(group=None, device=None) -> bytes:
+    """The ONE 32-byte seed every rank of a sharded batch expands its draws from (draws.expand): rank 0 takes it from the OS and
+    broadcasts it — one 32-byte broadcast, whatever the size of the batch."""
+    from . import draws
+    rank, world, backend = _group_info(group)
+    if world == 1:
+        return draws.new_seed()
+    import torch
+    import torch.distributed as dist
+    dev = device if (backend == "nccl" and device is not None) else "cpu"
+    buf = torch.zeros(32, dtype=torch.uint8, device=dev)
+    if rank == 0:
+        buf[:] = torch.frombuffer(bytearray(draws.new_seed()), dtype=torch.uint8).to(dev)
+    dist.broadcast(buf, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    return bytes(buf.cpu().numpy().tobytes())
+
+
+def _resolve_seed(seed, group=None, device=None) -> bytes:
+    """seed=True: common_seed; bytes: a given seed, the same on every rank"""
+    return common_seed(group, device) if seed is True else bytes(seed)
+
+
+def seeded_tail(seed: bytes, lo: int, total: int, groups: int = 1) -> bytes:
+    """The draws a shard needs, from a seed, on the host: the whole stream is draws.expand(seed, 0, groups * total), group g owns
+    indices [g * total, (g + 1) * total), and the shard that starts at proof `lo` of every group takes [g * total + lo, (g + 1) *
+    total) of each, group-major."""
+    from . import draws
+    return b"".join(draws.expand(seed, g * total + lo, total - lo) for g in range(groups))
+
+
+def seeded_tail_tensor(seed: bytes, lo: int, total: int, groups: int = 1, device=None, stream=None):
+    """seeded_tail in device memory -> uint8 tensor [groups * (total - lo), 32] on `device`, a kernel per group on `stream`
+    (draws.expand_into's rules; None = torch's current stream).  No draw bytes cross to the device and nothing waits."""
+    import torch
+    from . import draws
+    if not 0 <= lo <= total or groups < 1:
+        raise ValueError(f"a shard starts inside its batch: lo = {lo}, total = {total}, groups = {groups}")
+    per = total - lo
+    out = torch.empty((groups * per, 32), dtype=torch.uint8, device=device)
+    for g in range(groups):
+        if per:
+            draws.expand_into(seed, g * total + lo, out[g * per:(g + 1) * per], stream)
+    return out
+
+
 class ShardedBatch:
     """One rank's share of a sharded batch (or of `groups` independent sharded batches that travel in one launch), resident on
     its GPU.  launch() enqueues, on the batch's stream and without host synchronisation: the shard's pipeline up to its two
@@ -197,11 +244,26 @@ class ShardedBatch:
         group's whole batch."""
         self.batch.upload(proofs_flat, proof_len, instances_flat, col_lens, rand_tail)
 
-    def upload_tensors(self, proofs, instances, col_lens, rand_tail):
+    def upload_tensors(self, proofs, instances, col_lens, rand_tail=None, seed=None, lo=None, total=None):
         """upload() for a shard that is already in device memory (Batch.upload_tensors): uint8 tensors on the batch's device, proofs
         [n, >= proof length], instances [n, sum(col_lens) * 32] or None, rand_tail [n_tail, 32] — common_draws_tensor's rows from the
-        shard's first proof on.  Device work only, ordered behind the tensors' current stream; no host wait."""
-        self.batch.upload_tensors(proofs, instances, col_lens, rand_tail)
+        shard's first proof on.  Device work only, ordered behind the tensors' current stream; no host wait.
+        seed (instead of rand_tail) with lo and total: the shard starts at proof `lo` of a batch of `total` proofs per group, and its
+        tail is seeded_tail_tensor(seed, lo, total, groups), expanded on the batch's stream: the rank receives 32 bytes, not the draws."""
+        if seed is None:
+            if lo is not None or total is not None:
+                raise ValueError("lo and total go with seed")
+            self.batch.upload_tensors(proofs, instances, col_lens, rand_tail)
+            return
+        if rand_tail is not None:
+            raise ValueError("give the draws (rand_tail) or the seed they come from, not both")
+        if lo is None or total is None:
+            raise ValueError("a seeded shard needs its place in the batch: lo and total")
+        tail = seeded_tail_tensor(seed, lo, total, self.groups, proofs.device, self.batch.stream)
+        try:
+            self.batch.upload_tensors(proofs, instances, col_lens, tail)
+        finally:
+            self.batch.hold_tail(tail)   # (no caller holds this tensor: the batch does, until its stream has read it)
 
     def launch_shard(self):
         """Shard pipeline without a pairing + export of the accumulator records -> the local record tensor (stream-ordered)."""
@@ -352,7 +414,19 @@ def _refuse_zero_draws(draws: bytes):
         raise ValueError("identification takes non-zero draws: a draw of the batch is zero")
 
 
-def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, identify=False):
+def _seeded_draws(seed, rand, n, lo, identify, group=None, device=None):
+    """The tail of a shard that starts at proof `lo` of n, from `seed` (True: common_seed; bytes: given) -> n - lo draws as bytes.
+    Only the identifying forms expand the whole stream, to refuse a zero draw on every rank alike."""
+    if rand is not None:
+        raise ValueError("give the draws (rand) or the seed they come from, not both")
+    from . import draws
+    seed = _resolve_seed(seed, group, device)
+    if identify:
+        _refuse_zero_draws(draws.expand(seed, 0, n))
+    return seed, seeded_tail(seed, lo, n)
+
+
+def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, identify=False, seed=None):
     """N x verify_proof under ONE AccumulatorStrategy followed by finalize() (lib.rs:33-425, kzg/strategy.rs:125-140) with the
     proofs sharded over the ranks of `group` (default: the world) — BASELINE.json configs 3 and 5.
 
@@ -361,19 +435,26 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     the OS and broadcasts.  Rank r verifies shard_bounds(n, world, r) with the draw tail of its global position, the 1312-byte
     accumulator records are all-gathered (RCCL under the nccl backend), folded, and ONE pairing closes the batch.
     -> (ok, statuses[n], left_xy, right_xy), identical on every rank and — for given draws — for every world size.
-    identify: verify_batch_sharded_identify's form -> (ok, statuses[n], left_xy, right_xy, local_range_checks)."""
+    identify: verify_batch_sharded_identify's form -> (ok, statuses[n], left_xy, right_xy, local_range_checks).
+    seed (instead of rand): the draws are draws.expand(seed, 0, n) — True: rank 0 takes a seed from the OS and broadcasts its 32
+    bytes (common_seed); bytes: a given seed, the same on every rank.  No n x 32-byte broadcast happens: every rank expands its own
+    tail, and the result is the one of rand = those draws."""
     rank, world, backend = _group_info(group)
     n = len(proofs)
     if device is None and batch_factory is None:
         device = f"cuda:{ctx.device}"
-    draws = common_draws(n, rand, group, device)
-    if identify:
-        _refuse_zero_draws(draws)
     lo, hi = shard_bounds(n, world, rank)
+    if seed is not None:
+        tail = _seeded_draws(seed, rand, n, lo, identify, group, device)[1]
+    else:
+        draws = common_draws(n, rand, group, device)
+        if identify:
+            _refuse_zero_draws(draws)
+        tail = tail_for_shard(draws, lo)
     flat, plen, iflat, lens = _shard(ctx, proofs, instances, lo, hi)
     sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), group=group, device=device, batch_factory=batch_factory)
     try:
-        sb.upload(flat, plen, iflat, lens, tail_for_shard(draws, lo))
+        sb.upload(flat, plen, iflat, lens, tail)
         sb.launch()
         ok, st, left, right = sb.finish()
         checks = 0
@@ -387,28 +468,34 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     return bool(ok[0]), statuses, left[0], right[0]
 
 
-def verify_batch_sharded_identify(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None):
+def verify_batch_sharded_identify(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, seed=None):
     """verify_batch_sharded plus the proofs that made it fail.  -> (ok, statuses[n], left_xy, right_xy, local_range_checks): ok / left_xy /
     right_xy are verify_batch_sharded's, statuses[i] is what Context.verify_each returns for proof i — identical on every rank and for
     every world size — and local_range_checks is the number of range checks THIS rank's search ran (0 on a rank whose shard is clean, and
     everywhere when the batch passes).  Every rank searches its own shard (ShardedBatch.identify) before the status all-gather that
     verify_batch_sharded ends with; no other collective is added.  A zero among the common draws raises ValueError on every rank before
     any upload."""
-    return verify_batch_sharded(ctx, proofs, instances, rand, group, batch_factory, device, identify=True)
+    return verify_batch_sharded(ctx, proofs, instances, rand, group, batch_factory, device, identify=True, seed=seed)
 
 
-def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_factory=None, device=None, identify=False):
+def verify_batch_sharded_local(ctx, proofs, instances, rand=None, world: int = 1, batch_factory=None, device=None, identify=False, seed=None):
     """The `world`-rank computation of verify_batch_sharded run shard after shard on ONE device, no process group: every shard is
     uploaded with the draw tail of its global position and launched without a pairing, the records are laid out as the all-gather
     would, shard 0 folds them and runs the one pairing.  -> (ok, statuses[n], left_xy, right_xy).
-    identify: verify_batch_sharded_local_identify's form -> (ok, statuses[n], left_xy, right_xy, range_checks[world])."""
+    identify: verify_batch_sharded_local_identify's form -> (ok, statuses[n], left_xy, right_xy, range_checks[world]).
+    seed (instead of rand): verify_batch_sharded's — every shard's tail is expanded from the seed on its own."""
     import torch
     n = len(proofs)
     if rand is not None and len(rand) != n:
         raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
-    draws = _scalar_bytes(rand) if rand is not None else draw_scalars(n)
-    if identify:
-        _refuse_zero_draws(draws)
+    if seed is not None:
+        seed = _seeded_draws(seed, rand, n, n, identify)[0]
+        tail_of = lambda lo: seeded_tail(seed, lo, n)
+    else:
+        draws = _scalar_bytes(rand) if rand is not None else draw_scalars(n)
+        if identify:
+            _refuse_zero_draws(draws)
+        tail_of = lambda lo: tail_for_shard(draws, lo)
     if device is None and batch_factory is None:
         device = f"cuda:{ctx.device}"
     shards, statuses = [], []
@@ -418,7 +505,7 @@ def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_f
             flat, plen, iflat, lens = _shard(ctx, proofs, instances, lo, hi)
             sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), device=device, batch_factory=batch_factory, world_size=world)
             shards.append(sb)
-            sb.upload(flat, plen, iflat, lens, tail_for_shard(draws, lo))
+            sb.upload(flat, plen, iflat, lens, tail_of(lo))
             sb.launch_shard()
             _, st, _, _ = sb.finish()
             statuses += st
@@ -442,10 +529,10 @@ def verify_batch_sharded_local(ctx, proofs, instances, rand, world: int, batch_f
     return bool(ok[0]), statuses, left[0], right[0]
 
 
-def verify_batch_sharded_local_identify(ctx, proofs, instances, rand, world: int, batch_factory=None, device=None):
+def verify_batch_sharded_local_identify(ctx, proofs, instances, rand=None, world: int = 1, batch_factory=None, device=None, seed=None):
     """verify_batch_sharded_identify's computation in verify_batch_sharded_local's sequential one-GPU form.
     -> (ok, statuses[n], left_xy, right_xy, range_checks[world]): the range checks every shard's search ran, shard by shard."""
-    return verify_batch_sharded_local(ctx, proofs, instances, rand, world, batch_factory, device, identify=True)
+    return verify_batch_sharded_local(ctx, proofs, instances, rand, world, batch_factory, device, identify=True, seed=seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------- streaming form

@@ -1148,6 +1148,7 @@ class Batch:
         self.max_proofs = max_proofs
         self.n = 0
         self._keep = None   # upload_tensors: the tensors the enqueued upload reads, until finish()
+        self._tails = []    # hold_tail: (event, tensor) of the tensors the library itself made for an upload (a seed's expanded tail)
         self.groups, self.group_sizes = 1, None
         if stream is not None:
             self.set_stream(stream)
@@ -1176,6 +1177,7 @@ class Batch:
         if self._h:
             self._lib.h2v_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self._tails = []   # (the destroy waited for the batch's streams)
 
     def __del__(self):
         try:
@@ -1183,8 +1185,29 @@ class Batch:
         except Exception:
             pass
 
+    def hold_tail(self, tensor):
+        """Keep `tensor` — device memory the library itself made for the upload just enqueued, such as a seed's expanded tail, which no
+        caller holds — referenced until the batch's stream has passed this point: an event is recorded on the stream now, and the
+        tensor is dropped once the event has completed, which the next upload, finish_into() and finish() look at (without waiting).
+        So a batch that never waits on the host (upload, launch, finish_into, again) holds the tails of the launches still in
+        flight and no more."""
+        import sys
+        cuda = getattr(sys.modules.get(type(tensor).__module__.partition(".")[0]), "cuda", None)
+        if cuda is None:
+            raise TypeError("the tensor's module has no cuda events to hold it by")
+        self._drop_done_tails()
+        ev = cuda.Event()
+        ev.record(cuda.ExternalStream(self.stream, device=tensor.device))
+        self._tails = getattr(self, "_tails", []) + [(ev, tensor)]
+
+    def _drop_done_tails(self, waited=False):
+        """Let go of the held tensors whose event has completed (waited: the host has waited for the stream: all of them)"""
+        self._tails = [] if waited else [(ev, t) for ev, t in getattr(self, "_tails", []) if not ev.query()]
+
     def set_stream(self, hip_stream: int):
+        self._drop_done_tails()
         check(self._lib.h2v_batch_set_stream(self._h, ctypes.c_void_p(hip_stream)))
+        self._drop_done_tails(waited=True)   # (the call waited for the stream it leaves)
 
     @property
     def stream(self) -> int:
@@ -1209,9 +1232,15 @@ class Batch:
                 raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
         return n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt
 
-    def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None):
+    def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None, seed=None, first_index=0, n_tail=None):
         """proofs_flat: n * proof_len bytes; instances_flat: n * sum(col_lens) * 32 bytes;
-        rand_tail: bytes of the Fr::random draws of proofs [first, total) of the whole batch (>= n scalars) or None."""
+        rand_tail: bytes of the Fr::random draws of proofs [first, total) of the whole batch (>= n scalars) or None.
+        seed (instead of rand_tail): the tail is draws.expand(seed, first_index, n_tail), n_tail = n when None — the draws of a
+        32-byte seed (include/h2v_draws.h), expanded on the host."""
+        if seed is not None:
+            rand_tail = self._seeded_tail(seed, rand_tail, first_index, n_tail, len(proofs_flat) // proof_len if proof_len else 0)[0]
+        elif first_index or n_tail is not None:
+            raise ValueError("first_index and n_tail go with seed")
         args = self._upload_args(proofs_flat, proof_len, instances_flat, col_lens, rand_tail)
         check(self._lib.h2v_batch_upload(self._h, *args))
         self.n = args[0]
@@ -1265,6 +1294,7 @@ class Batch:
             raise ValueError(f"n and n_tail must be multiples of the group count ({groups}), got {n} and {nt}")
         cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
         self._keep = None
+        self._drop_done_tails()
         check(self._lib.h2v_batch_upload_device(self._h, n, ctypes.c_void_p(proofs_addr), proof_stride, ctypes.c_void_p(instances_addr), len(col_lens), cl,
                                                 ctypes.c_void_p(rand_addr), nt))
         self.n = n
@@ -1292,11 +1322,32 @@ class Batch:
             raise ValueError(f"{what} must be contiguous rows of {row_len} bytes, got shape {shape} and strides {stride}")
         return int(t.data_ptr()), shape[0], row_stride
 
-    def upload_tensors(self, proofs, instances, col_lens, rand_tail=None):
+    @staticmethod
+    def _seeded_tail(seed, rand_tail, first_index, n_tail, n, device=None, stream=None):
+        """The tail a seed stands for -> (draws, n_tail): draws.expand(seed, first_index, n_tail) as bytes, or with `device` the same
+        as a tensor written by a kernel on `stream` (draws.expand_tensor).  n_tail None: one draw per proof."""
+        from . import draws
+        if rand_tail is not None:
+            raise ValueError("give the draws (rand_tail) or the seed they come from, not both")
+        nt = n if n_tail is None else n_tail
+        if isinstance(nt, bool) or not isinstance(nt, numbers.Integral) or nt < n:
+            raise ValueError(f"n_tail must be an integer >= n = {n}, got {nt!r}")
+        if device is None:
+            return draws.expand(seed, first_index, nt), nt
+        return draws.expand_tensor(seed, first_index, nt, device, stream), nt
+
+    def upload_tensors(self, proofs, instances, col_lens, rand_tail=None, seed=None, first_index=0, n_tail=None):
         """upload_device() from tensors (torch's, or anything with dtype / device / shape / stride() / data_ptr()): proofs [n, >= proof
         length] with any row stride that is a multiple of 16, instances [n, sum(col_lens) * 32] contiguous (None when there are none),
         rand_tail [n_tail, 32] contiguous or None (OS draws).  The batch's stream is made to wait, on the device, for the work queued on
-        the tensors' current stream; the tensors are kept referenced until finish()."""
+        the tensors' current stream; the tensors are kept referenced until finish().
+        seed (instead of rand_tail): the tail is the draws of a 32-byte seed (include/h2v_draws.h), indices [first_index, first_index +
+        n_tail) with n_tail = n when None, expanded by a kernel on the batch's stream into a tensor the batch holds until the stream
+        has read it (hold_tail) and then taken as rand_tail is: no draw bytes cross to the device, and nothing waits for the stream."""
+        if seed is None and (first_index or n_tail is not None):
+            raise ValueError("first_index and n_tail go with seed")
+        if seed is not None and rand_tail is not None:
+            raise ValueError("give the draws (rand_tail) or the seed they come from, not both")
         device = self.ctx.device
         col_lens = list(col_lens)
         addr, n, stride = self._tensor_bytes(proofs, "proofs", device)
@@ -1319,7 +1370,16 @@ class Batch:
             ev = cuda.Event()
             ev.record(current)
             cuda.ExternalStream(mine, device=proofs.device).wait_event(ev)
-        self.upload_device(addr, n, stride, iaddr, col_lens, raddr, nt)
+        if seed is not None:   # (behind the wait: the tensor may be memory that work on the current stream still uses)
+            rand_tail, nt = self._seeded_tail(seed, None, first_index, n_tail, n, proofs.device, mine)
+            raddr = self._tensor_bytes(rand_tail, "rand_tail", device, None, 32)[0]
+            if not nt:   # (an upload of no proofs: nothing to draw)
+                raddr = nt = None
+        try:
+            self.upload_device(addr, n, stride, iaddr, col_lens, raddr, nt)
+        finally:
+            if seed is not None:   # (also when the upload was refused: the expansion is enqueued)
+                self.hold_tail(rand_tail)
         self._keep = (proofs, instances, rand_tail)
 
     def launch(self, with_pairing=True):
@@ -1344,6 +1404,7 @@ class Batch:
         left, right = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
         check(self._lib.h2v_batch_finish(self._h, st, ctypes.byref(ok), left, right))
         self._keep = None   # (upload_tensors' inputs: the enqueued work has run)
+        self._drop_done_tails(waited=True)
         return bool(ok.value), memoryview(st).cast('B').cast('i').tolist()[:self.n], left.raw, right.raw
 
     def finish_groups(self, raw_statuses=False):
@@ -1356,6 +1417,7 @@ class Batch:
         left, right = ctypes.create_string_buffer(64 * g), ctypes.create_string_buffer(64 * g)
         check(self._lib.h2v_batch_finish_groups(self._h, st, ok, left, right, g))
         self._keep = None   # (upload_tensors' inputs: the enqueued work has run)
+        self._drop_done_tails(waited=True)
         statuses = bytes(memoryview(st).cast('B')[:4 * self.n]) if raw_statuses else memoryview(st).cast('B').cast('i').tolist()[:self.n]
         return [bool(v) for v in ok], statuses, _points(left, g), _points(right, g)
 
@@ -1449,6 +1511,7 @@ class Batch:
             after = cuda.Event()
             after.record(batch_stream)
             current.wait_event(after)
+        self._drop_done_tails()
 
     def recheck(self, ranges):
         """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
