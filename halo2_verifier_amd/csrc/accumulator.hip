@@ -335,7 +335,7 @@ int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_pr
     if (!n) return 0;   // no verify_proof: no scale, no Guard, no entry
     if (a->j_cap && a->entries.size() + G > a->j_cap) { set_last_error(std::string(who) + ": the journal has fewer free entries than the batch has groups"); return H2V_ERR_UNSUPPORTED; }
     // the groups' counters, from the statuses the finished launch left in the batch's host block
-    const int* st = reinterpret_cast<const int*>(b->results_host.p + ResultsLayout{G, n}.status());
+    const int* st = results_at(b->results_host.p, ResultsLayout{G, n}).status;
     std::vector<size_t> count(G), failed(G, 0);
     size_t all_failed = 0;
     for (size_t g = 0, i = 0; g < G; ++g) {

@@ -144,6 +144,14 @@ struct ResultsLayout {
     size_t status() const { return 144 * G; }
     size_t total() const { return 144 * G + 4 * n; }
 };
+// The block at `base` as typed pointers: the device block, the pinned host block, or the host block's mapped device address.  The one
+// place that says what lies at each offset.
+struct ResultsPtrs { uint32_t* ok; uint32_t* fold_failed; uint32_t* out_ident; uint8_t* out_bytes; int* status; };
+inline ResultsPtrs results_at(void* base, const ResultsLayout& L) {
+    uint8_t* const p = static_cast<uint8_t*>(base);
+    return ResultsPtrs{reinterpret_cast<uint32_t*>(p + L.ok()), reinterpret_cast<uint32_t*>(p + L.fold_failed()), reinterpret_cast<uint32_t*>(p + L.out_ident()),
+                       p + L.out_bytes(), reinterpret_cast<int*>(p + L.status())};
+}
 
 // Where a batch is in its life.  An operation sets the stage as its last step, once it has succeeded; a failed upload, launch, finish or
 // fold leaves the batch Empty, and the calls that need an upload or a launch refuse it until an upload succeeds.
@@ -159,13 +167,13 @@ struct LaunchRecord {           // what the last launch (or fold) left (close_en
 int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storage, const char* who, bool nonzero = false);
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
                 const uint8_t* rand_tail, size_t n_tail, bool overlap = false, bool guard = false);
-int finish_device_impl(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
-                       void* d_summary);
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, const uint32_t* ext_idx = nullptr);
 // `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary (who / does: the entry
 // point and the verb of the error message): what every entry point that takes a caller's device pointer holds it to
 int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who = "h2v_batch_upload_device", const char* does = "reads");
 bool pairing_passed(const h2v_batch* b, uint32_t g);
+// the host waits for every stream the batch has (its own or the caller's, the auxiliary and the copy stream) -> the first error
+hipError_t wait_for_streams(h2v_batch* b);
 // The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
 // problem is one slot of every proof.  channel_problems builds its problems from these counts.
 struct ChannelTerms { bool strided; uint32_t left, right; };

@@ -60,11 +60,9 @@ int ensure_buffers(h2v_batch* b, const Plan& pl) {
     // the verdicts are the LAST thing a launch produces: the pairing kernel writes them into the host block itself (one word per group over
     // PCIe) and no copy follows it; everything else in the block is final before the pairing starts and is copied beside it (close_enqueue)
     const ResultsLayout L{G, N};
-    b->ok = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b->results_host.dev) + L.ok());
-    b->fold_failed = reinterpret_cast<uint32_t*>(b->results.p + L.fold_failed());
-    b->out_ident = reinterpret_cast<uint32_t*>(b->results.p + L.out_ident());
-    b->out_bytes = b->results.p + L.out_bytes();
-    b->status = reinterpret_cast<int*>(b->results.p + L.status());
+    const ResultsPtrs dev = results_at(b->results.p, L);
+    b->ok = results_at(b->results_host.dev, L).ok;
+    b->fold_failed = dev.fold_failed; b->out_ident = dev.out_ident; b->out_bytes = dev.out_bytes; b->status = dev.status;
     if ((rc = b->ws.reserve(z.ws_terms, z.ws_problems, z.ws_per_problem))) return rc;
     b->stream_words = z.stream_words;
     return 0;
@@ -110,12 +108,14 @@ struct StageCommit {
 
 #define H2V_SPLIT_MAX_GROUPS 64u
 
+// the left channel is one term per proof, in the same slot of every proof (SHPLONK's h2): a strided problem, its other slots never read
+static bool left_strided(const Plan& pl) { return pl.left_term_order.size() == 1 && !pl.left_term_order[0].first; }
 // The two MSM problems of the proofs [p0, p0 + count) of an uploaded batch: acc2[0] <- the left channel (SHPLONK: sum_p m_p * h2_p;
 // GWC: the witness points), acc2[1] <- the right channel = the proofs' pooled Guard terms + the VK-wide bases with the n_shared
 // folded scalars `shared_scal`.  Both index the batch's point array; unused slots have zero scalars and cost nothing.
 // the term counts of those two problems: the one rule, for channel_problems and for whoever must know a launch's layout before it is built
 ChannelTerms channel_terms(const Plan& pl, uint32_t count, uint32_t n_shared) {
-    const bool strided = pl.left_term_order.size() == 1 && !pl.left_term_order[0].first;
+    const bool strided = left_strided(pl);
     return ChannelTerms{strided, strided ? count : count * pl.n_points, count * pl.n_points + n_shared};
 }
 bool groups_cut_within_limit(const Plan& pl, const size_t* sizes, size_t n_groups) {
@@ -179,15 +179,15 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
         return point_to_bytes_enqueue(s, b->acc.p, b->out_bytes, b->out_ident, 2 * G);
     }
     const ResultsLayout L{G, b->n};
-    uint8_t* const host = static_cast<uint8_t*>(b->results_host.dev);
+    const ResultsPtrs host = results_at(b->results_host.dev, L);   // (the mapped host block, as the device sees it)
     const bool one_stream = b->ctx->tuning.pairing_one_stream != 0;
     if (b->split.parts && pairing_tail_fits(b->ctx->pairing, one_stream)) {
         // (the verdicts are still the last thing the launch writes: the tail's workgroups are done long before the checks')
         PairTail t;
         t.pieces = b->split.pts; t.prs = b->ws.final_problems; t.count = b->split.count; t.parts = b->split.parts; t.shift = b->split.shift;
         t.out_bytes = b->out_bytes; t.out_ident = b->out_ident;
-        t.host_bytes = host + L.out_bytes(); t.host_ident = reinterpret_cast<uint32_t*>(host + L.out_ident());
-        t.src = reinterpret_cast<const uint32_t*>(b->results.p + L.fold_failed()); t.dst = reinterpret_cast<uint32_t*>(host + L.fold_failed());
+        t.host_bytes = host.out_bytes; t.host_ident = host.out_ident;
+        t.src = b->fold_failed; t.dst = host.fold_failed;
         t.n_words = (uint32_t)((L.total() - L.fold_failed()) / 4);
         t.skip_lo = (uint32_t)((L.out_ident() - L.fold_failed()) / 4); t.skip_hi = (uint32_t)((L.status() - L.fold_failed()) / 4);   // (the converting workgroups write those)
         if (t.count != 2 * G) { set_last_error("close_enqueue: the pieces are not this launch's"); return H2V_ERR_BAD_ARGUMENT; }
@@ -204,7 +204,7 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
     // main stream does NOT wait for it: its last operation is the pairing kernel.  h2v_batch_finish waits for both streams; anything else
     // that touches the batch first calls join_tail.
     // (by a kernel, not hipMemcpyAsync: a copy enqueued now, behind kernels that end a launch later, can hold up an SDMA queue — util.hip)
-    if ((rc = copy_words_enqueue(b->aux, b->results.p + L.fold_failed(), host + L.fold_failed(), (L.total() - L.fold_failed()) / 4, H2V_AUX_LDS_RESERVE))) return rc;
+    if ((rc = copy_words_enqueue(b->aux, b->fold_failed, host.fold_failed, (L.total() - L.fold_failed()) / 4, H2V_AUX_LDS_RESERVE))) return rc;
     H2V_HIP_CHECK(hipEventRecord(b->ev_join, b->aux));
     b->last.tail_on_aux = true; b->last.host_block = true;
     if (b->split.parts) { if ((rc = pairing_check_split_enqueue(s, b->ctx->pairing, b->split.ready, G, b->split.parts, b->split.shift, b->line_ws.p, b->ok, one_stream))) return rc; }
@@ -258,10 +258,42 @@ static int draw_multipliers_enqueue(h2v_batch* b) {
     return multipliers_enqueue(b->stream, b->tail.p, b->n_tail, b->n, b->groups, b->mult.p, b->mult_tiles.p);
 }
 
-// The checks of an upload on its sizes alone, for the plan `pl` of its instance shape: the draws' count against n, the groups'
-// divisibility or the sum of their sizes, and the launch's MSM cut.  have_tail: the caller passes draws (n_tail of them).
-static int upload_size_checks(const h2v_batch* b, const Plan& pl, size_t n, bool have_tail, size_t n_tail, const char* who) {
-    const std::string w(who);
+// ---- An upload, whatever its source: host bytes (upload_impl) or device memory (h2v_batch_upload_device).  Every step the sources share
+// exists once — upload_pin, upload_size_checks, upload_take, shared_bases_enqueue, upload_commit — and an entry point adds its own
+// checks between the first two and after the second, and its own transfer between upload_take and upload_commit.
+
+// What the sources share of their arguments.  proofs / instances: host or device memory; tail: the caller's draws, or null for OS draws
+struct UploadArgs {
+    const char* who; size_t n;  // the entry point, in the error messages; the proofs
+    const void* proofs; const void* instances;
+    size_t ncols; const size_t* col_lens;
+    const void* tail; size_t n_tail;
+};
+
+// The checks that need no plan, then the plan of the instance shape -> pin.  columns_code: what a wrong column count returns, the
+// reference's own refusal H2V_ERR_INVALID_INSTANCES (lib.rs:51-55, in pack_inputs' words) or the entry point's H2V_ERR_BAD_ARGUMENT.
+static int upload_pin(const h2v_batch* b, const UploadArgs& a, int columns_code, bool guard, PlanPin& pin) {
+    const std::string w(a.who);
+    if (!b || (a.n && !a.proofs) || (a.ncols && !a.col_lens)) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (a.n > b->max_proofs) { set_last_error(w + ": n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
+    h2v_ctx* ctx = b->ctx;
+    H2V_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+    if (a.ncols != ctx_total_instance_columns(ctx)) {
+        set_last_error((columns_code == H2V_ERR_INVALID_INSTANCES ? std::string() : w + ": ") + "instances do not match the VK's instance column count");
+        return columns_code;
+    }
+    pin.ctx = ctx;   // (b may be null: the pin learns its context here)
+    return pin.get(std::vector<size_t>(a.col_lens, a.col_lens + a.ncols), guard);
+}
+
+// The checks of an upload on its sizes alone, for the plan `pl` of its instance shape: instances where the plan has instance values, the
+// draws' count against n, the groups' divisibility or the sum of their sizes, and the launch's MSM cut.
+static int upload_size_checks(const h2v_batch* b, const Plan& pl, const UploadArgs& a) {
+    const std::string w(a.who);
+    const size_t n = a.n, n_tail = a.n_tail;
+    const bool have_tail = a.tail != nullptr;
+    if (pl.n_instance_values && n && !a.instances) { set_last_error(w + ": instances missing"); return H2V_ERR_BAD_ARGUMENT; }
     if (have_tail && n_tail < n) { set_last_error(w + ": n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
     if (ragged(b)) {
         if (n != b->group_off.back()) { set_last_error(w + ": n is not the sum of the group sizes (h2v_batch_set_group_sizes)"); return H2V_ERR_BAD_ARGUMENT; }
@@ -293,40 +325,59 @@ static void zero_below_of_draws(h2v_batch* b, size_t n, const uint8_t* rand_tail
     }
 }
 
+// Every argument is valid: from here on the batch takes the upload of n proofs under the pinned plan, with n_tail draws: host_draws,
+// or (device_draws) the caller's draws in device memory, which the host cannot see and k_ingest_draws checks into the verdict block.
+static int upload_take(h2v_batch* b, PlanPin& pin, size_t n, size_t n_tail, const uint8_t* host_draws, bool device_draws) {
+    int rc;
+    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pin.pd->host))) return rc;
+    if (b->plan) ctx_put_plan(b->ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
+    b->plan = pin.take(); b->n = (uint32_t)n; b->n_tail = (uint32_t)n_tail;
+    const size_t G = b->groups;
+    if (device_draws) b->zero_below.assign(G, 0);   // (filled by h2v_batch_finish from the verdict block)
+    else zero_below_of_draws(b, n, host_draws, n_tail);
+    if ((rc = b->tail.reserve(32 * n_tail))) return rc;
+    if (device_draws && ((rc = b->ingest_verdict.reserve(G + 2)) || (rc = b->ingest_host.reserve(4 * (G + 1))))) return rc;
+    if (ragged(b)) {   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
+        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
+        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles))) return rc;
+    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
+    b->mult_of_draws = false; b->decompressed = false; b->device_draws = device_draws;
+    return 0;
+}
+// VK-wide bases sit behind the batch's own points so that one MSM covers both (and their phi images behind the points' images)
+static int shared_bases_enqueue(h2v_batch* b, hipStream_t cs) {
+    const PlanDevice* pd = b->plan;
+    const Plan& pl = pd->host;
+    if (!b->n) return 0;
+    H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + b->n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
+    H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + b->n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
+    return 0;
+}
+// The end of an upload, its draws on the device: the batch multipliers depend on the draws alone, so they are computed once per upload
+// and kept by every launch of it
+static int upload_commit(h2v_batch* b, StageCommit& commit) {
+    if (b->n) { if (int rc = draw_multipliers_enqueue(b)) return rc; b->mult_of_draws = true; }
+    commit.commit(BatchStage::Uploaded);
+    return 0;
+}
+
 // `overlap`: where it pays (see `points_first` below), the point bytes are copied first on the batch's copy stream and the decompression
 // runs under the copy of everything else (h2v_batch_upload_launch); otherwise everything is copied on the batch's stream (h2v_batch_upload).
 // `guard`: the guard variant of the plan (h2v_guard_msm)
 int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t ncols, const size_t* col_lens,
                 const uint8_t* rand_tail, size_t n_tail, bool overlap, bool guard) {
+    const UploadArgs a{"h2v_batch_upload", n, proofs_flat, instances_flat, ncols, col_lens, rand_tail, n_tail};
     StageCommit commit{b};
-    if (!b || (n && !proofs_flat)) { set_last_error("h2v_batch_upload: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (n > b->max_proofs) { set_last_error("h2v_batch_upload: n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
-    h2v_ctx* ctx = b->ctx;
-    H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ncols != ctx_total_instance_columns(ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }  // lib.rs:51-55
-    PlanPin pin(ctx);
-    int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols), guard);
-    if (rc) return rc;
+    PlanPin pin(nullptr);
+    int rc;
+    if ((rc = upload_pin(b, a, H2V_ERR_INVALID_INSTANCES, guard, pin))) return rc;
     const Plan& pl = pin.pd->host;
     if (proof_len < pl.proof_len) { set_last_error("h2v_batch_upload: proof_len is shorter than this VK's proof"); return H2V_ERR_BAD_ARGUMENT; }
-    if (pl.n_instance_values && n && !instances_flat) { set_last_error("h2v_batch_upload: instances missing"); return H2V_ERR_BAD_ARGUMENT; }
-    if ((rc = upload_size_checks(b, pl, n, rand_tail != nullptr, n_tail, "h2v_batch_upload"))) return rc;
+    if ((rc = upload_size_checks(b, pl, a))) return rc;
     std::vector<uint8_t> os_rand;
     if (!rand_tail) n_tail = n;
-    if ((rc = resolve_draws(rand_tail, n_tail, os_rand, "h2v_batch_upload"))) return rc;
-    // every argument is valid: from here on the batch takes the upload
-    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
-    if (b->plan) ctx_put_plan(ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
-    b->plan = pin.take(); b->n = (uint32_t)n;
-    const PlanDevice* pd = b->plan;
-    zero_below_of_draws(b, n, rand_tail, n_tail);
-    if ((rc = b->tail.reserve(32 * n_tail))) return rc;
-    if (ragged(b)) {
-        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
-        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles)) || (rc = b->d_group_off.reserve(b->group_off.size())) || (rc = b->d_group_last.reserve(n))) return rc;
-    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
-    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false; b->device_draws = false;
+    if ((rc = resolve_draws(rand_tail, n_tail, os_rand, a.who))) return rc;
+    if ((rc = upload_take(b, pin, n, n_tail, rand_tail, false))) return rc;
     hipStream_t s = b->stream;
     auto copy_proofs = [&](hipStream_t cs, size_t p0, size_t p1) -> int {
         if (proof_len == pl.proof_len) H2V_HIP_CHECK(hipMemcpyAsync(b->proofs.p + p0 * pl.proof_len, proofs_flat + p0 * proof_len, (p1 - p0) * proof_len, hipMemcpyHostToDevice, cs));
@@ -336,14 +387,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
     auto copy_rest = [&](hipStream_t cs) -> int {
         if (pl.n_instance_values) H2V_HIP_CHECK(hipMemcpyAsync(b->inst.p, instances_flat, n * (size_t)pl.n_instance_values * 32, hipMemcpyHostToDevice, cs));
         H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, rand_tail, 32 * n_tail, hipMemcpyHostToDevice, cs));
-        if (ragged(b)) {   // (the batch's own vectors: unchanged until the next h2v_batch_set_group_sizes, which waits for the streams)
-            H2V_HIP_CHECK(hipMemcpyAsync(b->d_group_last.p, b->group_last.data(), n, hipMemcpyHostToDevice, cs));
-            H2V_HIP_CHECK(hipMemcpyAsync(b->d_group_off.p, b->group_off.data(), 4 * b->group_off.size(), hipMemcpyHostToDevice, cs));
-        }
-        // VK-wide bases sit behind the batch's own points so that one MSM covers both
-        H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
-        H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, cs));
-        return 0;
+        return shared_bases_enqueue(b, cs);   // (the offsets and marks of unequal groups are on the device since h2v_batch_set_group_sizes)
     };
     // Overlapped form (h2v_batch_upload_launch).  What was measured on the way (profiles/r03_h2d_microbench.txt, r03_upload_timeline.txt):
     //  * a 26 MB copy takes 0.47 ms from pageable and from pinned memory alike, and an "asynchronous" copy out of pageable memory
@@ -390,10 +434,7 @@ int upload_impl(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof
         if ((rc = decompress_finish_enqueue(s, g))) return rc;
     }
     b->decompressed = points_first;
-    // the batch multipliers depend on the draws alone: computed once per upload (the draws are on the device), kept by every launch of it
-    if (n) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
-    commit.commit(BatchStage::Uploaded);
-    return 0;
+    return upload_commit(b, commit);
 }
 
 // `bytes` bytes from `p` on are device memory of `device`, inside one allocation, and p lies on a 16-byte boundary
@@ -413,66 +454,6 @@ int device_range_check(const void* p, size_t bytes, int device, const char* what
     return 0;
 }
 
-// h2v_batch_upload_device: upload_impl for inputs in device memory.  Every check comes before the first device work; with the caller's
-// draws nothing here waits for the stream, and what the host cannot see — the draws — is checked by k_ingest_draws, whose verdict
-// finish_impl reads (b->device_draws).
-int upload_device_impl(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, size_t ncols, const size_t* col_lens,
-                       const void* d_rand_tail, size_t n_tail) {
-    static const char who[] = "h2v_batch_upload_device";
-    StageCommit commit{b};
-    if (!b || (n && !d_proofs) || (ncols && !col_lens)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (n > b->max_proofs) { set_last_error(std::string(who) + ": n exceeds the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
-    h2v_ctx* ctx = b->ctx;
-    H2V_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->vk) { set_last_error("the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ncols != ctx_total_instance_columns(ctx)) { set_last_error(std::string(who) + ": instances do not match the VK's instance column count"); return H2V_ERR_BAD_ARGUMENT; }
-    PlanPin pin(ctx);
-    int rc = pin.get(std::vector<size_t>(col_lens, col_lens + ncols), false);
-    if (rc) return rc;
-    const Plan& pl = pin.pd->host;
-    if (proof_stride < pl.proof_len || (proof_stride & 15u)) { set_last_error(std::string(who) + ": proof_stride is below this VK's proof length, or no multiple of 16"); return H2V_ERR_BAD_ARGUMENT; }
-    if (pl.proof_len & 15u) { set_last_error(std::string(who) + ": this VK's proof length is no multiple of 16"); return H2V_ERR_UNSUPPORTED; }
-    const size_t inst_bytes = n * (size_t)pl.n_instance_values * 32;
-    if (inst_bytes && !d_instances) { set_last_error(std::string(who) + ": instances missing"); return H2V_ERR_BAD_ARGUMENT; }
-    if ((rc = upload_size_checks(b, pl, n, d_rand_tail != nullptr, n_tail, who))) return rc;
-    if (!d_rand_tail) n_tail = n;
-    if (n && (rc = device_range_check(d_proofs, (n - 1) * proof_stride + pl.proof_len, ctx->device, "d_proofs"))) return rc;
-    if (inst_bytes && (rc = device_range_check(d_instances, inst_bytes, ctx->device, "d_instances"))) return rc;
-    if (d_rand_tail && n_tail && (rc = device_range_check(d_rand_tail, 32 * n_tail, ctx->device, "d_rand_tail"))) return rc;
-    std::vector<uint8_t> os_rand;
-    const uint8_t* host_tail = nullptr;
-    if (!d_rand_tail && (rc = resolve_draws(host_tail, n_tail, os_rand, who))) return rc;
-    // every argument is valid: from here on the batch takes the upload
-    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pl))) return rc;
-    if (b->plan) ctx_put_plan(ctx, b->plan);
-    b->plan = pin.take(); b->n = (uint32_t)n;
-    const PlanDevice* pd = b->plan;
-    const uint32_t G = b->groups;
-    b->zero_below.assign(G, 0);   // (device draws: filled by h2v_batch_finish from the verdict block)
-    if (host_tail) zero_below_of_draws(b, n, host_tail, n_tail);
-    if ((rc = b->tail.reserve(32 * n_tail)) || (rc = b->ingest_verdict.reserve((size_t)G + 2)) || (rc = b->ingest_host.reserve(4 * ((size_t)G + 1)))) return rc;
-    if (ragged(b)) {   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
-        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
-        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles))) return rc;
-    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, G)))) return rc;
-    b->n_tail = (uint32_t)n_tail; b->mult_of_draws = false; b->decompressed = false;
-    hipStream_t s = b->stream;
-    if ((rc = ingest_rows_enqueue(s, d_proofs, proof_stride, pl.proof_len, n, d_instances, inst_bytes, b->proofs.p, b->inst.p, d_rand_tail ? b->ingest_verdict.p : nullptr, G))) return rc;
-    if (d_rand_tail) {
-        if ((rc = ingest_draws_enqueue(s, d_rand_tail, b->tail.p, (uint32_t)n_tail, (uint32_t)n, G, ragged(b) ? b->d_group_off.p : nullptr, b->ingest_verdict.p,
-                                       static_cast<uint32_t*>(b->ingest_host.dev)))) return rc;
-    } else if (n_tail) H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, host_tail, 32 * n_tail, hipMemcpyHostToDevice, s));
-    if (n) {
-        // VK-wide bases sit behind the batch's own points so that one MSM covers both
-        H2V_HIP_CHECK(hipMemcpyAsync(b->pts.p + n * (size_t)pl.n_points, pd->shared_bases.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, s));
-        H2V_HIP_CHECK(hipMemcpyAsync(b->phi.p + n * (size_t)pl.n_points, pd->shared_phi.p, sizeof(G1A) * pl.n_shared, hipMemcpyDeviceToDevice, s));
-    }
-    if (!d_rand_tail) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (the OS draws leave with this call)
-    b->device_draws = d_rand_tail != nullptr;
-    if (n) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
-    commit.commit(BatchStage::Uploaded);
-    return 0;
-}
 
 // ext_mult / ext_idx: the multipliers of a non-contiguous subset of a larger accumulation (h2v_verify_batch_shapes), instead of the draws'
 int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32_t* ext_idx) {
@@ -515,7 +496,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
         if (ext_mult) { b->mult_of_draws = false; if ((rc = gather_multipliers_enqueue(s, ext_mult, ext_idx, n, b->mult.p))) return rc; }
         else if (!b->mult_of_draws) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
-        if (!(pl.left_term_order.size() == 1 && !pl.left_term_order[0].first)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, s));
+        if (!left_strided(pl)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, s));
     }
     mark();
     FrvmArgs a{pd->code.p, (uint32_t)pl.code.size(), pd->consts.p, b->slots.p, n, b->proofs.p, pl.proof_len, pd->scalar_offsets.p, b->inst.p, pl.n_instance_values,
@@ -582,6 +563,7 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     const uint32_t n = b->n, G = b->groups;
     { int rcw = ensure_whole(b); if (rcw) return rcw; }
     const ResultsLayout L{G, n};
+    const ResultsPtrs host = results_at(b->results_host.p, L);
     hipError_t e;
     if (b->last.host_block) {
         // a launch that ended in its own pairing checks: the block travels by the launch's own kernels (the pairing launch's tail workgroups,
@@ -590,7 +572,7 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
         if (e == hipSuccess && b->last.tail_on_aux) e = hipStreamSynchronize(b->aux);
         b->last.tail_on_aux = false;   // (not hipEventSynchronize on its last event: that wait goes through the runtime's event thread, and a host that re-uploads per launch lost 40 % to it)
     } else {
-        H2V_HIP_CHECK(hipMemcpyAsync(b->results_host.p + L.fold_failed(), b->results.p + L.fold_failed(), L.total() - L.fold_failed(), hipMemcpyDeviceToHost, s));
+        H2V_HIP_CHECK(hipMemcpyAsync(host.fold_failed, b->fold_failed, L.total() - L.fold_failed(), hipMemcpyDeviceToHost, s));
         e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) { set_last_error(std::string("h2v_batch_finish: ") + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
@@ -604,19 +586,11 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
         }
         b->zero_below.assign(verdict + 1, verdict + 1 + G);
     }
-    const uint8_t* host = b->results_host.p;
-    const uint32_t* okv = reinterpret_cast<const uint32_t*>(host + L.ok());
-    const uint32_t* foldf = reinterpret_cast<const uint32_t*>(host + L.fold_failed());
-    const uint8_t* outb = host + L.out_bytes();
-    const int* st = reinterpret_cast<const int*>(host + L.status());
+    const int* st = host.status;
     for (int i = 0; i < 7; ++i) b->last_ms[i] = 0;
-    if (b->profiling >= 2) {
-        // events: 0 start, 1 after decompression, 2 after transcript + multipliers, 3 after Fr program, 4 after fold, 5 after MSMs, 6 after pairing
-        float t01 = 0, t12 = 0, t23 = 0, t34 = 0, t45 = 0, t56 = 0;
-        hipEventElapsedTime(&t01, b->ev[0], b->ev[1]); hipEventElapsedTime(&t12, b->ev[1], b->ev[2]); hipEventElapsedTime(&t23, b->ev[2], b->ev[3]);
-        hipEventElapsedTime(&t34, b->ev[3], b->ev[4]); hipEventElapsedTime(&t45, b->ev[4], b->ev[5]); hipEventElapsedTime(&t56, b->ev[5], b->ev[6]);
-        b->last_ms[0] = t01; b->last_ms[1] = t12; b->last_ms[2] = t23; b->last_ms[3] = t34; b->last_ms[4] = t45; b->last_ms[5] = t56;
-    }
+    // events: 0 start, 1 after decompression, 2 after transcript + multipliers, 3 after Fr program, 4 after fold, 5 after MSMs, 6 after pairing
+    for (int i = 0; i < 6 && b->profiling >= 2; ++i)
+        if (hipEventElapsedTime(&b->last_ms[i], b->ev[i], b->ev[i + 1]) != hipSuccess) b->last_ms[i] = 0;   // (a pair that was not recorded)
     if (b->profiling >= 1) {
         float tacc = 0;
         if (b->ws.profile_recorded) hipEventElapsedTime(&tacc, b->ws.ev_acc[0], b->ws.ev_acc[1]);
@@ -635,58 +609,26 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     }
     for (uint32_t g = 0; g < G; ++g) {
         // a sharded group is accepted only if no shard reported a failed proof (their terms are zeroed out of the accumulators)
-        if (group_ok) group_ok[g] = (all_ok[g] && !foldf[g] && (!b->last.pairing || okv[g])) ? 1 : 0;
-        if (out_left) memcpy(out_left + 64 * (size_t)g, &outb[128 * (size_t)g], 64);
-        if (out_right) memcpy(out_right + 64 * (size_t)g, &outb[128 * (size_t)g + 64], 64);
+        if (group_ok) group_ok[g] = (all_ok[g] && !host.fold_failed[g] && (!b->last.pairing || host.ok[g])) ? 1 : 0;
+        if (out_left) memcpy(out_left + 64 * (size_t)g, &host.out_bytes[128 * (size_t)g], 64);
+        if (out_right) memcpy(out_right + 64 * (size_t)g, &host.out_bytes[128 * (size_t)g + 64], 64);
     }
     commit.commit(BatchStage::Finished);
     return 0;
 }
 // the verdict of group g's own pairing check in the last finished launch (finish_impl folds the statuses into group_ok; this is the pairing alone)
 bool pairing_passed(const h2v_batch* b, uint32_t g) {
-    return b->last.pairing && reinterpret_cast<const uint32_t*>(b->results_host.p + ResultsLayout{b->groups, b->n}.ok())[g] != 0;
+    return b->last.pairing && results_at(b->results_host.p, ResultsLayout{b->groups, b->n}).ok[g] != 0;
+}
+hipError_t wait_for_streams(h2v_batch* b) {
+    hipError_t first = hipSuccess;
+    auto wait = [&](hipStream_t s) { const hipError_t e = hipStreamSynchronize(s); if (first == hipSuccess) first = e; };
+    if (b->stream || !b->owns_stream) wait(b->stream);   // (a caller's stream may be the null stream)
+    if (b->aux) wait(b->aux);                             // (the tail of the last launch may still be running there)
+    if (b->copy) wait(b->copy);                           // (the last upload's copies)
+    return first;
 }
 
-// h2v_batch_finish_device: what finish_impl hands the host, handed to the caller's device arrays by kernels on the batch's stream
-// (results_enqueue, util.hip).  Nothing here waits: no synchronise, no copy.  Every check comes before the first device work and a refusal
-// leaves the batch as it was; the stage does not change, so the call may be repeated and a host finish may precede or follow it.
-int finish_device_impl(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
-                       void* d_summary) {
-    static const char who[] = "h2v_batch_finish_device";
-    int rc;
-    if ((rc = require_stage(b, BatchStage::Launched, who))) return rc;
-    const uint32_t n = b->n, G = b->groups;
-    const int device = b->ctx->device;
-    H2V_HIP_CHECK(hipSetDevice(device));
-    if (d_failed_index && !failed_cap) { set_last_error(std::string(who) + ": failed_cap is 0 with d_failed_index given"); return H2V_ERR_BAD_ARGUMENT; }
-    const uint32_t cap = d_failed_index ? (uint32_t)std::min<size_t>(failed_cap, n) : 0;   // (no more than n indices exist)
-    const struct { const void* p; size_t bytes; const char* what; } outs[] = {
-        {d_status, 4 * (size_t)n, "d_status"}, {d_group_ok, 4 * (size_t)G, "d_group_ok"}, {d_left_xy, 64 * (size_t)G, "d_left_xy"}, {d_right_xy, 64 * (size_t)G, "d_right_xy"},
-        {d_group_failed, 4 * (size_t)G, "d_group_failed"}, {d_failed_index, 4 * (size_t)cap, "d_failed_index"}, {d_summary, 4 * (size_t)H2V_SUMMARY_WORDS, "d_summary"}};
-    for (const auto& o : outs)
-        if (o.p && (rc = device_range_check(o.p, o.bytes, device, o.what, who, "writes"))) return rc;
-    // every argument is valid: device work from here on, and a failure of it leaves the batch Empty like any other
-    StageCommit commit{b};
-    const BatchStage stage = b->stage;
-    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
-    // the scratch: grow-only, for the batch's capacity and group count (ensure_buffers' rule).  The group words are zero between calls
-    // (results_enqueue), so new memory is zeroed once, on the stream.
-    if ((rc = b->finish_tiles.reserve(results_tiles(b->max_proofs)))) return rc;
-    if (!b->finish_groups.p || G > b->finish_groups.cap) {
-        if ((rc = b->finish_groups.reserve(G))) return rc;
-        H2V_HIP_CHECK(hipMemsetAsync(b->finish_groups.p, 0, 4 * b->finish_groups.cap, b->stream));
-    }
-    ResultsOut out;
-    out.status = static_cast<int*>(d_status); out.group_ok = static_cast<int*>(d_group_ok);
-    out.left_xy = static_cast<uint8_t*>(d_left_xy); out.right_xy = static_cast<uint8_t*>(d_right_xy);
-    out.group_failed = static_cast<uint32_t*>(d_group_failed); out.failed_index = cap ? static_cast<uint32_t*>(d_failed_index) : nullptr; out.failed_cap = cap;
-    out.summary = static_cast<uint32_t*>(d_summary);
-    const uint32_t flags = (b->last.pairing ? 1u : 0u) | (b->last.folded ? 2u : 0u);
-    if ((rc = results_enqueue(b->stream, b->status, n, G, ragged(b) ? b->d_group_off.p : nullptr, b->fold_failed, b->ok, flags, b->out_bytes,
-                              b->device_draws ? b->ingest_verdict.p : nullptr, b->finish_tiles.p, b->finish_groups.p, out))) return rc;
-    commit.commit(stage);
-    return 0;
-}
 
 bool same_srs(const ParamsHost& a, const ParamsHost& b) {
     auto same_g2 = [](const G2A& p, const G2A& q) { return p.inf == q.inf && !memcmp(&p.x, &q.x, sizeof(Fq2)) && !memcmp(&p.y, &q.y, sizeof(Fq2)); };
@@ -733,14 +675,13 @@ int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, s
     // their buffers (a finished batch's normally are: only a fold after the finish leaves work behind)
     if ((rc = join_tail(host))) return rc;
     for (size_t k = 1; k < n_batches; ++k)
-        if (batches[k] != host) { H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->stream)); if (batches[k]->aux) H2V_HIP_CHECK(hipStreamSynchronize(batches[k]->aux)); }
+        if (batches[k] != host) H2V_HIP_CHECK(wait_for_streams(batches[k]));
     hipStream_t s = host->stream;
     Recheck& rk = host->recheck;
     const uint32_t max_ranges = MSM_MAX_PROBLEMS / 2;
     // the plan facts of every range's batch, and the term budget of a set: about the largest launch's own
     auto plan_of = [&](size_t i) -> const Plan& { return batch_of(i)->plan->host; };
-    auto strided = [](const Plan& pl) { return pl.left_term_order.size() == 1 && !pl.left_term_order[0].first; };
-    auto terms_of = [&](size_t i) { const Plan& pl = plan_of(i); const size_t c = count[i], np = pl.n_points; return (strided(pl) ? c : c * np) + c * np + pl.n_shared; };
+    auto terms_of = [&](size_t i) -> size_t { const Plan& pl = plan_of(i); const ChannelTerms t = channel_terms(pl, (uint32_t)count[i], pl.n_shared); return (size_t)t.left + t.right; };
     size_t budget = 0;   // > terms_of(every range): every range fits in a set of its own
     for (size_t k = 0; k < n_batches; ++k) { const Plan& pl = batches[k]->plan->host; budget = std::max(budget, 2 * ((size_t)batches[k]->n * pl.n_points + (size_t)max_ranges * pl.n_shared)); }
     if ((rc = rk.ranges.reserve(max_ranges)) || (rc = rk.acc.reserve(2 * (size_t)max_ranges)) || (rc = rk.ok.reserve(max_ranges)) ||
@@ -851,13 +792,11 @@ int h2v_batch_create(h2v_ctx* ctx, size_t max_proofs, size_t max_instance_values
 void h2v_batch_destroy(h2v_batch* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
-    if (b->stream || !b->owns_stream) hipStreamSynchronize(b->stream);
-    if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
+    wait_for_streams(b);
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
     for (int i = 0; i < 8; ++i) if (b->ev[i]) hipEventDestroy(b->ev[i]);
-    if (b->aux) { hipStreamSynchronize(b->aux); hipStreamDestroy(b->aux); }
-    if (b->copy) { hipStreamSynchronize(b->copy); hipStreamDestroy(b->copy); }
-
+    if (b->aux) hipStreamDestroy(b->aux);
+    if (b->copy) hipStreamDestroy(b->copy);
     if (b->ev_fork) hipEventDestroy(b->ev_fork);
     if (b->ev_join) hipEventDestroy(b->ev_join);
     if (b->stream && b->owns_stream) hipStreamDestroy(b->stream);
@@ -868,13 +807,81 @@ int h2v_batch_upload(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t 
                      const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail) {
     return upload_impl(b, n, proofs_flat, proof_len, instances_flat, n_instance_columns, col_lens, rand32_tail, n_tail);
 }
+// h2v_batch_upload_device: upload_impl for inputs in device memory.  Every check comes before the first device work; with the caller's
+// draws nothing here waits for the stream, and what the host cannot see — the draws — is checked by k_ingest_draws, whose verdict
+// finish_impl reads (b->device_draws).
 int h2v_batch_upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t proof_stride, const void* d_instances, size_t n_instance_columns,
                             const size_t* col_lens, const void* d_rand_tail, size_t n_tail) {
-    return upload_device_impl(b, n, d_proofs, proof_stride, d_instances, n_instance_columns, col_lens, d_rand_tail, n_tail);
+    static const char who[] = "h2v_batch_upload_device";
+    const UploadArgs a{who, n, d_proofs, d_instances, n_instance_columns, col_lens, d_rand_tail, n_tail};
+    StageCommit commit{b};
+    PlanPin pin(nullptr);
+    int rc;
+    if ((rc = upload_pin(b, a, H2V_ERR_BAD_ARGUMENT, false, pin))) return rc;
+    const Plan& pl = pin.pd->host;
+    const int device = b->ctx->device;
+    if (proof_stride < pl.proof_len || (proof_stride & 15u)) { set_last_error(std::string(who) + ": proof_stride is below this VK's proof length, or no multiple of 16"); return H2V_ERR_BAD_ARGUMENT; }
+    if (pl.proof_len & 15u) { set_last_error(std::string(who) + ": this VK's proof length is no multiple of 16"); return H2V_ERR_UNSUPPORTED; }
+    if ((rc = upload_size_checks(b, pl, a))) return rc;
+    const size_t inst_bytes = n * (size_t)pl.n_instance_values * 32;
+    if (!d_rand_tail) n_tail = n;
+    if (n && (rc = device_range_check(d_proofs, (n - 1) * proof_stride + pl.proof_len, device, "d_proofs"))) return rc;
+    if (inst_bytes && (rc = device_range_check(d_instances, inst_bytes, device, "d_instances"))) return rc;
+    if (d_rand_tail && n_tail && (rc = device_range_check(d_rand_tail, 32 * n_tail, device, "d_rand_tail"))) return rc;
+    std::vector<uint8_t> os_rand;
+    const uint8_t* host_tail = nullptr;
+    if (!d_rand_tail && (rc = resolve_draws(host_tail, n_tail, os_rand, who))) return rc;
+    if ((rc = upload_take(b, pin, n, n_tail, host_tail, d_rand_tail != nullptr))) return rc;
+    hipStream_t s = b->stream;
+    const uint32_t G = b->groups;
+    if ((rc = ingest_rows_enqueue(s, d_proofs, proof_stride, pl.proof_len, n, d_instances, inst_bytes, b->proofs.p, b->inst.p, d_rand_tail ? b->ingest_verdict.p : nullptr, G))) return rc;
+    if (d_rand_tail) {
+        if ((rc = ingest_draws_enqueue(s, d_rand_tail, b->tail.p, (uint32_t)n_tail, (uint32_t)n, G, ragged(b) ? b->d_group_off.p : nullptr, b->ingest_verdict.p,
+                                       static_cast<uint32_t*>(b->ingest_host.dev)))) return rc;
+    } else if (n_tail) H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, host_tail, 32 * n_tail, hipMemcpyHostToDevice, s));
+    if ((rc = shared_bases_enqueue(b, s))) return rc;
+    if (!d_rand_tail) H2V_HIP_CHECK(hipStreamSynchronize(s));   // (the OS draws leave with this call)
+    return upload_commit(b, commit);
 }
+// h2v_batch_finish_device: what finish_impl hands the host, handed to the caller's device arrays by kernels on the batch's stream
+// (results_enqueue, util.hip).  Nothing here waits: no synchronise, no copy.  Every check comes before the first device work and a refusal
+// leaves the batch as it was; the stage does not change, so the call may be repeated and a host finish may precede or follow it.
 int h2v_batch_finish_device(h2v_batch* b, void* d_status, void* d_group_ok, void* d_left_xy, void* d_right_xy, void* d_group_failed, void* d_failed_index, size_t failed_cap,
                             void* d_summary) {
-    return finish_device_impl(b, d_status, d_group_ok, d_left_xy, d_right_xy, d_group_failed, d_failed_index, failed_cap, d_summary);
+    static const char who[] = "h2v_batch_finish_device";
+    int rc;
+    if ((rc = require_stage(b, BatchStage::Launched, who))) return rc;
+    const uint32_t n = b->n, G = b->groups;
+    const int device = b->ctx->device;
+    H2V_HIP_CHECK(hipSetDevice(device));
+    if (d_failed_index && !failed_cap) { set_last_error(std::string(who) + ": failed_cap is 0 with d_failed_index given"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint32_t cap = d_failed_index ? (uint32_t)std::min<size_t>(failed_cap, n) : 0;   // (no more than n indices exist)
+    const struct { const void* p; size_t bytes; const char* what; } outs[] = {
+        {d_status, 4 * (size_t)n, "d_status"}, {d_group_ok, 4 * (size_t)G, "d_group_ok"}, {d_left_xy, 64 * (size_t)G, "d_left_xy"}, {d_right_xy, 64 * (size_t)G, "d_right_xy"},
+        {d_group_failed, 4 * (size_t)G, "d_group_failed"}, {d_failed_index, 4 * (size_t)cap, "d_failed_index"}, {d_summary, 4 * (size_t)H2V_SUMMARY_WORDS, "d_summary"}};
+    for (const auto& o : outs)
+        if (o.p && (rc = device_range_check(o.p, o.bytes, device, o.what, who, "writes"))) return rc;
+    // every argument is valid: device work from here on, and a failure of it leaves the batch Empty like any other
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
+    // the scratch: grow-only, for the batch's capacity and group count (ensure_buffers' rule).  The group words are zero between calls
+    // (results_enqueue), so new memory is zeroed once, on the stream.
+    if ((rc = b->finish_tiles.reserve(results_tiles(b->max_proofs)))) return rc;
+    if (!b->finish_groups.p || G > b->finish_groups.cap) {
+        if ((rc = b->finish_groups.reserve(G))) return rc;
+        H2V_HIP_CHECK(hipMemsetAsync(b->finish_groups.p, 0, 4 * b->finish_groups.cap, b->stream));
+    }
+    ResultsOut out;
+    out.status = static_cast<int*>(d_status); out.group_ok = static_cast<int*>(d_group_ok);
+    out.left_xy = static_cast<uint8_t*>(d_left_xy); out.right_xy = static_cast<uint8_t*>(d_right_xy);
+    out.group_failed = static_cast<uint32_t*>(d_group_failed); out.failed_index = cap ? static_cast<uint32_t*>(d_failed_index) : nullptr; out.failed_cap = cap;
+    out.summary = static_cast<uint32_t*>(d_summary);
+    const uint32_t flags = (b->last.pairing ? 1u : 0u) | (b->last.folded ? 2u : 0u);
+    if ((rc = results_enqueue(b->stream, b->status, n, G, ragged(b) ? b->d_group_off.p : nullptr, b->fold_failed, b->ok, flags, b->out_bytes,
+                              b->device_draws ? b->ingest_verdict.p : nullptr, b->finish_tiles.p, b->finish_groups.p, out))) return rc;
+    commit.commit(stage);
+    return 0;
 }
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
@@ -888,9 +895,7 @@ int h2v_batch_finish(h2v_batch* b, int* per_proof_status, int* batch_ok, uint8_t
 }
 int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (!b || !groups || groups > MSM_MAX_PROBLEMS / 2 || groups > b->max_proofs) { set_last_error("h2v_batch_set_groups: bad group count"); return H2V_ERR_BAD_ARGUMENT; }
-    if (b->stream) hipStreamSynchronize(b->stream);
-    if (b->aux) hipStreamSynchronize(b->aux);   // (the tail of the last launch may still be running there)
-    if (b->copy) hipStreamSynchronize(b->copy); // (the last upload's copies read the vectors cleared below: h2v_batch_set_group_sizes' rule)
+    wait_for_streams(b);   // (the last launch and the last upload read what changes below)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
     b->groups = (uint32_t)groups; b->stage = BatchStage::Empty;  // the next upload grows the buffers if the group count needs more
     b->group_off.clear(); b->group_last.clear();   // (equal groups again after h2v_batch_set_group_sizes)
@@ -905,17 +910,13 @@ int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups
         if (sizes[g] > b->max_proofs - total) { set_last_error(std::string(who) + ": the sizes exceed the batch capacity"); return H2V_ERR_BAD_ARGUMENT; }
         total += sizes[g];
     }
-    // (the last upload's copies read the vectors replaced below)
-    if (b->stream) hipStreamSynchronize(b->stream);
-    if (b->aux) hipStreamSynchronize(b->aux);
-    if (b->copy) hipStreamSynchronize(b->copy);
+    wait_for_streams(b);   // (the last launch reads the device copies replaced below)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
     b->groups = (uint32_t)n_groups; b->stage = BatchStage::Empty;
     b->group_off.assign(n_groups + 1, 0); b->group_last.assign(total, 0);
     for (size_t g = 0; g < n_groups; ++g) { b->group_off[g + 1] = b->group_off[g] + (uint32_t)sizes[g]; b->group_last[b->group_off[g + 1] - 1] = 1; }
-    // The offsets and the last-of-group marks go to the device here, where they change and every stream of the batch is idle: an upload
-    // from device memory (h2v_batch_upload_device) enqueues behind a busy stream and must not copy from host vectors there.
-    // (h2v_batch_upload sends them again with its own copies.)
+    // The offsets and the last-of-group marks go to the device here, where they change and every stream of the batch is idle, and
+    // nowhere else: no upload copies them (one from device memory enqueues behind a busy stream and must not copy from host vectors there).
     int rc;
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     if ((rc = b->d_group_off.reserve(b->group_off.size())) || (rc = b->d_group_last.reserve(total))) return rc;
@@ -989,10 +990,8 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
     H2V_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = b->stream;
     // (a fold after the finish may still be sending the result block: the same statuses again)
-    H2V_HIP_CHECK(hipStreamSynchronize(s));
-    if (b->aux) H2V_HIP_CHECK(hipStreamSynchronize(b->aux));
-    const ResultsLayout L{G, n};
-    const int* raw = reinterpret_cast<const int*>(b->results_host.p + L.status());
+    H2V_HIP_CHECK(wait_for_streams(b));
+    const int* raw = results_at(b->results_host.p, ResultsLayout{G, n}).status;
     std::vector<std::vector<int>> st(1, std::vector<int>(n));
     std::vector<uint32_t> failed(G, 0);
     for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[group_of(b, i)]; }

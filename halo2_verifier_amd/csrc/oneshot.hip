@@ -352,7 +352,7 @@ int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<Cal
     // on an error with work in flight: nothing returns (and frees the buffers above) before every batch's streams are idle
     struct Drain {
         std::vector<h2v_batch*> bs;
-        ~Drain() { for (h2v_batch* b : bs) { if (b->stream) hipStreamSynchronize(b->stream); if (b->aux) hipStreamSynchronize(b->aux); } }
+        ~Drain() { for (h2v_batch* b : bs) wait_for_streams(b); }
     } drain;
     drain.bs = on;
     all_ok = true;

@@ -12,6 +12,7 @@ import ctypes
 import enum
 import numbers
 import struct
+import sys
 
 from . import _lib
 from ._lib import H2VError, check
@@ -1134,6 +1135,58 @@ def recheck_batches(batches, ranges):
     return _range_results(k, *out)
 
 
+def _integer(v, what, kind="an integer", positive=False):
+    """v as an int in [0, 2^64), or (0, 2^64) if `positive`; no bool, no float.  kind: what the TypeError says it must be"""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise TypeError(f"{what} must be {kind}, got {type(v).__name__}")
+    if v < (1 if positive else 0) or v >> 64:
+        raise ValueError(f"{what} must be in {'(' if positive else '['}0, 2^64), got {int(v)}")
+    return int(v)
+
+
+def _address(v, what, kind="an integer", positive=False, needed=False):
+    """A 16-byte aligned device address as an int, None as 0.  positive: a number given must not be 0; needed: neither None nor 0 will do"""
+    v = 0 if v is None else _integer(v, what, kind, positive)
+    if needed and not v:
+        raise ValueError(f"{what} is missing")
+    if v % 16:
+        raise ValueError(f"{what} must be 16-byte aligned, got {v:#x}")
+    return v
+
+
+def _check_group_shape(group_sizes, groups, n, nt, draws):
+    """What the groups of a batch ask of an upload of n proofs and nt draws (draws: the caller passes some).  Unequal groups (group_sizes):
+    their sum, and one draw per proof; equal groups: multiples of their count — groups None leaves that rule to the library."""
+    if group_sizes is not None:
+        if n != sum(group_sizes):
+            raise ValueError(f"the group sizes sum to {sum(group_sizes)} proofs, got {n}")
+        if draws and nt != n:
+            raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
+    elif groups is not None and (n % groups or nt % groups):
+        raise ValueError(f"n and n_tail must be multiples of the group count ({groups}), got {n} and {nt}")
+
+
+def _cuda_of(tensor, missing):
+    """The cuda namespace (streams, events) of the module a tensor comes from; TypeError(missing) if it has none"""
+    cuda = getattr(sys.modules.get(type(tensor).__module__.partition(".")[0]), "cuda", None)
+    if cuda is None:
+        raise TypeError(missing)
+    return cuda
+
+
+def _device_tensor(t, what, device, dtypes, wanted):
+    """What every tensor argument is held to first: a duck-typed tensor, of one of `dtypes` (wanted: the TypeError's words for them), on
+    `device` -> (shape, strides)"""
+    for attr in ("dtype", "device", "shape", "stride", "data_ptr"):
+        if not hasattr(t, attr):
+            raise TypeError(f"{what} must be a tensor (no .{attr})")
+    if str(t.dtype).rpartition(".")[2] not in dtypes:
+        raise TypeError(f"{what} must be {wanted}, got {t.dtype}")
+    if getattr(t.device, "type", None) != "cuda" or t.device.index != device:
+        raise ValueError(f"{what} must be on the context's device (cuda:{device}), got {t.device}")
+    return tuple(t.shape), tuple(t.stride())
+
+
 class Batch:
     """Staged, device-resident batch (h2v_batch): upload once, launch asynchronously on its stream, finish later.
     Several batches may be in flight on one Context (one HIP stream each)."""
@@ -1191,10 +1244,7 @@ class Batch:
         tensor is dropped once the event has completed, which the next upload, finish_into() and finish() look at (without waiting).
         So a batch that never waits on the host (upload, launch, finish_into, again) holds the tails of the launches still in
         flight and no more."""
-        import sys
-        cuda = getattr(sys.modules.get(type(tensor).__module__.partition(".")[0]), "cuda", None)
-        if cuda is None:
-            raise TypeError("the tensor's module has no cuda events to hold it by")
+        cuda = _cuda_of(tensor, "the tensor's module has no cuda events to hold it by")
         self._drop_done_tails()
         ev = cuda.Event()
         ev.record(cuda.ExternalStream(self.stream, device=tensor.device))
@@ -1225,11 +1275,7 @@ class Batch:
             raise ValueError("rand_tail is not a whole number of 32-byte scalars")
         cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
         nt = len(rand_tail) // 32 if rand_tail is not None else 0
-        if getattr(self, "group_sizes", None) is not None:
-            if n != sum(self.group_sizes):
-                raise ValueError(f"the group sizes sum to {sum(self.group_sizes)} proofs, got {n}")
-            if rand_tail is not None and nt != n:
-                raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
+        _check_group_shape(getattr(self, "group_sizes", None), None, n, nt, rand_tail is not None)   # (equal groups: the library's H2VError)
         return n, proofs_flat, proof_len, instances_flat, len(col_lens), cl, rand_tail, nt
 
     def upload(self, proofs_flat: bytes, proof_len: int, instances_flat: bytes, col_lens, rand_tail=None, seed=None, first_index=0, n_tail=None):
@@ -1252,46 +1298,24 @@ class Batch:
         host, the one form that waits for the stream.  Everything is device work on the batch's stream, behind whatever is queued
         there: the caller orders the producers of the inputs before the call and leaves the inputs alone until finish().  A draw >= r
         is found by a kernel and raised by finish() / finish_groups(), which leave the batch empty."""
-        def whole(v, what):
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-                raise TypeError(f"{what} must be an integer, got {type(v).__name__}")
-            if v < 0 or v >> 64:
-                raise ValueError(f"{what} must be in [0, 2^64), got {int(v)}")
-            return int(v)
-
-        def address(v, what, needed):
-            v = whole(0 if v is None else v, what)
-            if needed and not v:
-                raise ValueError(f"{what} is missing")
-            if v % 16:
-                raise ValueError(f"{what} must be 16-byte aligned, got {v:#x}")
-            return v
-
-        n, proof_stride = whole(n, "n"), whole(proof_stride, "proof_stride")
-        col_lens = [whole(c, "a column length") for c in col_lens]
+        n, proof_stride = _integer(n, "n"), _integer(proof_stride, "proof_stride")
+        col_lens = [_integer(c, "a column length") for c in col_lens]
         if n > getattr(self, "max_proofs", n):
             raise ValueError(f"n = {n} exceeds the batch capacity of {self.max_proofs}")
         if not proof_stride or proof_stride % 16:
             raise ValueError(f"proof_stride must be a positive multiple of 16, got {proof_stride}")
-        proofs_addr = address(proofs_addr, "proofs_addr", n > 0)
-        instances_addr = address(instances_addr, "instances_addr", n > 0 and sum(col_lens) > 0)
-        rand_addr = address(rand_addr, "rand_addr", False)
+        proofs_addr = _address(proofs_addr, "proofs_addr", needed=n > 0)
+        instances_addr = _address(instances_addr, "instances_addr", needed=n > 0 and sum(col_lens) > 0)
+        rand_addr = _address(rand_addr, "rand_addr")
         if not rand_addr:
             if n_tail is not None:
                 raise ValueError("n_tail without rand_addr: OS draws are one per proof")
             nt = 0
         else:
-            nt = whole(n if n_tail is None else n_tail, "n_tail")
+            nt = _integer(n if n_tail is None else n_tail, "n_tail")
             if nt < n:
                 raise ValueError(f"n_tail = {nt} is below n = {n}")
-        groups = getattr(self, "groups", 1)
-        if getattr(self, "group_sizes", None) is not None:
-            if n != sum(self.group_sizes):
-                raise ValueError(f"the group sizes sum to {sum(self.group_sizes)} proofs, got {n}")
-            if rand_addr and nt != n:
-                raise ValueError(f"groups of unequal size take one draw per proof ({n}), got {nt}")
-        elif n % groups or nt % groups:
-            raise ValueError(f"n and n_tail must be multiples of the group count ({groups}), got {n} and {nt}")
+        _check_group_shape(getattr(self, "group_sizes", None), getattr(self, "groups", 1), n, nt, bool(rand_addr))
         cl = (ctypes.c_size_t * max(len(col_lens), 1))(*col_lens)
         self._keep = None
         self._drop_done_tails()
@@ -1303,14 +1327,7 @@ class Batch:
     def _tensor_bytes(t, what, device, rows=None, row_len=None):
         """A duck-typed tensor as device bytes: uint8, on `device`, 2-D with unit inner stride (`rows` rows; `row_len` given: exactly
         that many bytes per row and no padding between rows) -> (address, rows, row stride)"""
-        for attr in ("dtype", "device", "shape", "stride", "data_ptr"):
-            if not hasattr(t, attr):
-                raise TypeError(f"{what} must be a tensor (no .{attr})")
-        if not str(t.dtype).endswith("uint8"):
-            raise TypeError(f"{what} must be a uint8 tensor, got {t.dtype}")
-        if getattr(t.device, "type", None) != "cuda" or t.device.index != device:
-            raise ValueError(f"{what} must be on the context's device (cuda:{device}), got {t.device}")
-        shape, stride = tuple(t.shape), tuple(t.stride())
+        shape, stride = _device_tensor(t, what, device, ("uint8",), "a uint8 tensor")
         if len(shape) != 2 or (shape[1] > 1 and stride[1] != 1):
             raise ValueError(f"{what} must be 2-D with unit inner stride, got shape {shape} and strides {stride}")
         if rows is not None and shape[0] != rows:
@@ -1361,10 +1378,7 @@ class Batch:
         if rand_tail is not None:
             raddr, nt, _ = self._tensor_bytes(rand_tail, "rand_tail", device, None, 32)
         # the inputs are written on the tensors' current stream: the batch's stream waits for it by an event, the host for nothing
-        import sys
-        cuda = getattr(sys.modules.get(type(proofs).__module__.partition(".")[0]), "cuda", None)
-        if cuda is None:
-            raise TypeError("the tensors' module has no cuda streams to order the upload behind")
+        cuda = _cuda_of(proofs, "the tensors' module has no cuda streams to order the upload behind")
         current, mine = cuda.current_stream(proofs.device), self.stream
         if current.cuda_stream != mine:
             ev = cuda.Event()
@@ -1430,24 +1444,11 @@ class Batch:
         ascending order (the first failed_cap of them), SUMMARY_WORDS uint32.  Device work on the batch's stream only: the call waits
         for nothing, leaves the batch's stage alone and may be repeated; the caller orders its readers behind the batch's stream.  The
         batch must be launched (or finished)."""
-        def address(v, what):
-            if v is None:
-                return 0
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-                raise TypeError(f"{what} must be an integer address or None, got {type(v).__name__}")
-            if v <= 0 or v >> 64:
-                raise ValueError(f"{what} must be in (0, 2^64), got {int(v)}")
-            if v % 16:
-                raise ValueError(f"{what} must be 16-byte aligned, got {int(v):#x}")
-            return int(v)
-
-        addrs = [address(v, what) for v, what in ((status_addr, "status_addr"), (group_ok_addr, "group_ok_addr"), (left_xy_addr, "left_xy_addr"),
-                                                  (right_xy_addr, "right_xy_addr"), (group_failed_addr, "group_failed_addr"),
-                                                  (failed_index_addr, "failed_index_addr"), (summary_addr, "summary_addr"))]
-        if isinstance(failed_cap, bool) or not isinstance(failed_cap, numbers.Integral):
-            raise TypeError(f"failed_cap must be an integer, got {type(failed_cap).__name__}")
-        if failed_cap < 0 or failed_cap >> 64:
-            raise ValueError(f"failed_cap must be in [0, 2^64), got {int(failed_cap)}")
+        addrs = [_address(v, what, "an integer address or None", positive=True)
+                 for v, what in ((status_addr, "status_addr"), (group_ok_addr, "group_ok_addr"), (left_xy_addr, "left_xy_addr"),
+                                 (right_xy_addr, "right_xy_addr"), (group_failed_addr, "group_failed_addr"),
+                                 (failed_index_addr, "failed_index_addr"), (summary_addr, "summary_addr"))]
+        failed_cap = _integer(failed_cap, "failed_cap")
         if addrs[5] and not failed_cap:
             raise ValueError("failed_cap must be at least 1 when failed_index_addr is given")
         vp = [ctypes.c_void_p(a) for a in addrs]
@@ -1457,15 +1458,7 @@ class Batch:
     def _tensor_words(t, what, device, dtypes, count):
         """A duck-typed tensor as an output array: one of `dtypes`, on `device`, contiguous, `count` elements (None: any number, at
         least one) -> (address, elements)"""
-        for attr in ("dtype", "device", "shape", "stride", "data_ptr"):
-            if not hasattr(t, attr):
-                raise TypeError(f"{what} must be a tensor (no .{attr})")
-        name = str(t.dtype).rpartition(".")[2]
-        if name not in dtypes:
-            raise TypeError(f"{what} must be a tensor of {' or '.join(dtypes)}, got {t.dtype}")
-        if getattr(t.device, "type", None) != "cuda" or t.device.index != device:
-            raise ValueError(f"{what} must be on the context's device (cuda:{device}), got {t.device}")
-        shape, stride = tuple(t.shape), tuple(t.stride())
+        shape, stride = _device_tensor(t, what, device, dtypes, f"a tensor of {' or '.join(dtypes)}")
         numel, expect = 1, 1
         for size in shape:
             numel *= size
@@ -1495,10 +1488,7 @@ class Batch:
         if not given:
             raise ValueError("finish_into: no output tensor given")
         got = [(None, 0) if t is None else self._tensor_words(t, what, device, dtypes, count) for t, what, dtypes, count in spec]
-        import sys
-        cuda = getattr(sys.modules.get(type(given[0]).__module__.partition(".")[0]), "cuda", None)
-        if cuda is None:
-            raise TypeError("the tensors' module has no cuda streams to order the results by")
+        cuda = _cuda_of(given[0], "the tensors' module has no cuda streams to order the results by")
         current, mine = cuda.current_stream(given[0].device), self.stream
         ordered = current.cuda_stream != mine
         if ordered:

@@ -267,7 +267,7 @@ def test_the_transcribed_table_is_the_sources():
     found = {}
     for least, who in re.findall(r'require_stage\(\w+(?:\[k\])?, BatchStage::(\w+), (\w+|"[^"]+")\)', src):
         if who == "who":
-            continue                 # (finish_impl / finish_device_impl / recheck_impl / identify: named where they are called)
+            continue                 # (finish_impl / h2v_batch_finish_device / recheck_impl / identify: named where they are called)
         found[who.strip('"')] = least
     # the entry points that pass their name on
     assert re.search(r'static const char who\[\] = "h2v_batch_finish_device";\s+int rc;\s+if \(\(rc = require_stage\(b, BatchStage::Launched, who\)\)\)', src)

@@ -288,6 +288,96 @@ def test_refusals_come_before_any_device_work(pool, ctx):
     b.close()
 
 
+# The refusals every upload shares, whatever its source: (name, set_groups / set_group_sizes first, the call's changes, code, message,
+# entry points).  Codes and texts are those of include/h2v.h and of the three entry points before they shared their checks:
+# H2V_ERR_BAD_ARGUMENT -16 everywhere but the host forms' column count, the reference's own H2V_ERR_INVALID_INSTANCES -1.
+HOST_FORMS, ALL_FORMS = ("upload", "upload_launch"), ("upload", "upload_launch", "upload_device")
+SHARED_REFUSALS = [
+    ("capacity", None, dict(n=9, nt=9), -16, "capacity", ALL_FORMS),
+    ("columns_host", None, dict(cols=[4, 4]), -1, "column count", HOST_FORMS),
+    ("columns_device", None, dict(cols=[4, 4]), -16, "column count", ("upload_device",)),
+    ("short_tail", None, dict(nt=7), -16, "n_tail < n", ALL_FORMS),
+    ("group_multiple", 4, dict(n=6, nt=6), -16, "multiples of the group count", ALL_FORMS),
+    ("group_sum", [1, 7], dict(n=7, nt=7), -16, "sum of the group sizes", ALL_FORMS),
+    ("group_draws", [1, 7], dict(nt=9), -16, "one draw per proof", ALL_FORMS),
+    ("no_instances", None, dict(instances=False), -16, "instances missing", ALL_FORMS),
+    ("no_col_lens", None, dict(col_lens=False), -16, "null argument", ALL_FORMS),
+    ("short_proof_len", None, dict(proof_len=PLEN - 1), -16, "proof_len is shorter", HOST_FORMS),
+    ("draw_of_r", None, dict(first_draw=R_MOD), -16, "rand32 scalar not canonical", HOST_FORMS),
+]
+
+
+@pytest.mark.parametrize("form", ALL_FORMS)
+def test_shared_refusals_through_every_entry_point(pool, ctx, form):
+    """raw calls of h2v_batch_upload, h2v_batch_upload_launch and h2v_batch_upload_device with one argument wrong at a time: the code,
+    the text, a batch left Empty; then a valid upload through the same entry point equals the host run"""
+    import torch
+    import halo2_verifier_amd as h2v
+    s, P, I = pool
+    rand = _draws(9, 31)                       # (a ninth draw for the tail that is one too long)
+    want = _host(ctx, P[:8], I[:8], rand[:8])
+    assert want[0] == [True] and want[1] == [0] * 8
+    flat, inst = _flat(P[:8], I[:8])
+    proofs, insts, draws = _tensors(P[:8], I[:8], rand)
+    torch.cuda.synchronize()
+    b = _batch(ctx, 8)
+    lib, sz = b._lib, h2v.verifier._sizes
+
+    def call(n=8, nt=8, cols=(8,), instances=True, col_lens=True, proof_len=PLEN, first_draw=None):
+        cl = sz(list(cols)) if col_lens else None
+        ncols = len(cols)
+        if form == "upload_device":
+            vp = ctypes.c_void_p
+            return lib.h2v_batch_upload_device(b._h, n, vp(proofs.data_ptr()), PLEN, vp(insts.data_ptr() if instances else 0), ncols, cl, vp(draws.data_ptr()), nt)
+        tail = _rand_bytes(([first_draw] if first_draw is not None else rand[:1]) + rand[1:])
+        args = (b._h, n, flat, proof_len, inst if instances else None, ncols, cl, tail, nt)
+        return lib.h2v_batch_upload(*args) if form == "upload" else lib.h2v_batch_upload_launch(*args, 1)
+
+    ran = []
+    for name, groups, changes, code, text, forms in SHARED_REFUSALS:
+        if form not in forms:
+            continue
+        if isinstance(groups, list):
+            b.set_group_sizes(groups)
+        else:
+            b.set_groups(groups or 1)
+        assert call(**changes) == code, (name, h2v._lib.last_error())
+        assert text in h2v._lib.last_error(), (name, h2v._lib.last_error())
+        with pytest.raises(h2v.H2VError, match="nothing uploaded"):
+            b.launch()
+        ran.append(name)
+    assert len(ran) == (10 if form != "upload_device" else 8)
+    b.set_groups(1)
+    assert call() == 0, h2v._lib.last_error()
+    b.n = 8
+    if form != "upload_launch":
+        b.launch()
+    assert b.finish_groups() == want
+    b.close()
+
+
+def test_unequal_groups_reach_the_device_by_set_group_sizes_alone(pool, ctx):
+    """one object: unequal sizes, other unequal sizes, equal groups, a host upload of the same proofs and draws each time.  No upload
+    sends the offsets or the last-of-group marks: a stale device copy of either would give another group's channels"""
+    s, P, I = pool
+    rand = _draws(8, 37)
+    flat, inst = _flat(P[:8], I[:8])
+    b = _batch(ctx, 8)
+    seen = []
+    for groups, sizes in ((1, [1, 7]), (1, [5, 3]), (2, None)):
+        if sizes:
+            b.set_group_sizes(sizes)
+        else:
+            b.set_groups(groups)
+        b.upload(flat, PLEN, inst, [8], _rand_bytes(rand)); b.launch()
+        got = b.finish_groups()
+        assert got[0] == [True, True] and got[1] == [0] * 8
+        assert got == _host(ctx, P[:8], I[:8], rand, groups, sizes), (groups, sizes)
+        seen.append(got)
+    assert seen[0][2:] != seen[1][2:] and seen[1][2:] != seen[2][2:]     # (the shapes do differ in what they accumulate)
+    b.close()
+
+
 def test_a_draw_of_r_is_reported_by_finish(pool, ctx):
     import torch
     import halo2_verifier_amd as h2v
