@@ -172,6 +172,24 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult = nullptr, co
 // point and the verb of the error message): what every entry point that takes a caller's device pointer holds it to
 int device_range_check(const void* p, size_t bytes, int device, const char* what, const char* who = "h2v_batch_upload_device", const char* does = "reads");
 bool pairing_passed(const h2v_batch* b, uint32_t g);
+// The gather of a batch's Guards (k_guards_gather, guards_out.hip; include/h2v_guards.h): the terms of one channel of the proofs
+// [first, first + count) of an upload of n proofs with np point slots each, T terms per proof in the order d_order, one thread per
+// (proof, term); output term i = (p - first) * T + t.  A slot term reads its 8 canonical words at d_slot_scal[(p np + slot) 8] and its
+// base at d_pts[p np + slot]; a VK-wide term reads d_shared[j n + p] (Montgomery) and d_pts[n np + j].  A proof whose status word is
+// non-zero gives zero scalars under the identity.  Either output may be null.  count * T < 2^31
+// (H2V_ERR_UNSUPPORTED beyond); every index of d_order lies below np (kind 0) or the number of VK-wide bases (kind 1): the caller's.
+struct GuardsGather {
+    const GuardTerm* d_order; uint32_t T;
+    const uint32_t* d_slot_scal; const Fr* d_shared; const G1A* d_pts; const int* d_status;
+    uint32_t n, np, first, count;
+};
+// bytes: 32 canonical little-endian bytes per scalar, 64 bytes x | y per base (the identity all-zero); both on 16-byte boundaries
+int guards_gather_bytes_enqueue(hipStream_t s, const GuardsGather& g, uint8_t* d_scalars32, uint8_t* d_bases64);
+// object form: the 8 words and the G1A as they lie, for the arrays of a resident h2v_msm (d_words on a 16-byte boundary)
+int guards_gather_terms_enqueue(hipStream_t s, const GuardsGather& g, uint32_t* d_words, G1A* d_bases);
+// per proof of [first, first + count): d_mult32[32 j ..] = d_mult[first + j] as canonical bytes, d_status_out[j] = status_decode(d_status[first + j]);
+// either output may be null; d_mult32 on a 16-byte boundary
+int guards_proofs_enqueue(hipStream_t s, const Fr* d_mult, const int* d_status, uint32_t first, uint32_t count, uint8_t* d_mult32, int* d_status_out);
 // the host waits for every stream the batch has (its own or the caller's, the auxiliary and the copy stream) -> the first error
 hipError_t wait_for_streams(h2v_batch* b);
 // The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
@@ -239,6 +257,8 @@ struct h2v_batch {
     h2v::DevBuf<uint32_t> ingest_verdict; h2v::MappedHostBuf ingest_host;
     // h2v_batch_finish_device's scratch (results_enqueue): a word per tile of 256 proofs; a word per group, zero between calls
     h2v::DevBuf<uint32_t> finish_tiles, finish_groups;
+    // h2v_batch_guards' scratch (guards_out.hip): the byte form of the range's terms on their way to the host, grow-only
+    h2v::DevBuf<uint8_t> guards_scratch;
     // device buffers: every one grow-only, sized for max_proofs, the group count and the largest plan uploaded so far (ensure_buffers)
     h2v::DevBuf<uint8_t> proofs, inst, tail;
     h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)

@@ -2,6 +2,7 @@
 // points (oneshot.hip) run on it through the steps batch.h declares.
 #include "../../include/h2v.h"
 #include "batch.h"
+#include "msm_object.h"
 #include <string.h>
 #include <algorithm>
 #include <utility>
@@ -883,6 +884,167 @@ int h2v_batch_finish_device(h2v_batch* b, void* d_status, void* d_group_ok, void
     commit.commit(stage);
     return 0;
 }
+
+// ---- every proof's Guard out of a launch (include/h2v_guards.h; the kernels: guards_out.hip).  The three forms share their checks
+// (guards_call_check) and the kernels' arguments (gather_args); like h2v_batch_finish_device they begin with join_tail / ensure_whole,
+// leave the stage as it is, and only READ what the launch left: msm_scal, left_scal, shared, pts, mult and the status words stay put
+// until the next upload (h2v_batch_recheck relies on the same).
+namespace {
+struct GuardsCall { uint32_t first, count, TL, TR; };
+// Launched or Finished, no guard variant, the range inside the upload, fewer than 2^31 terms per channel: before any device work
+int guards_call_check(const h2v_batch* b, const char* who, size_t first, size_t count, GuardsCall& c) {
+    if (int rc = require_stage(b, BatchStage::Launched, who)) return rc;
+    const std::string w(who);
+    if (!b->plan) { set_last_error(w + ": the batch holds no plan"); return H2V_ERR_BAD_ARGUMENT; }
+    const Plan& pl = b->plan->host;
+    if (pl.opts.guard_terms) { set_last_error(w + ": a guard-variant upload (h2v_guard_msm)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (first > b->n || count > b->n - first) { set_last_error(w + ": a range outside the upload"); return H2V_ERR_BAD_ARGUMENT; }
+    for (const auto& t : pl.left_term_order)   // (no plan has one: the left channel's terms are the proof's own points)
+        if (t.first) { set_last_error(w + ": a VK-wide base in the left channel"); return H2V_ERR_UNSUPPORTED; }
+    const size_t TL = pl.left_term_order.size(), TR = pl.right_term_order.size();
+    if ((uint64_t)count * std::max(TL, TR) >= (1ull << 31)) { set_last_error(w + ": 2^31 terms or more in one call: take the range in pieces"); return H2V_ERR_UNSUPPORTED; }
+    c = GuardsCall{(uint32_t)first, (uint32_t)count, (uint32_t)TL, (uint32_t)TR};
+    return 0;
+}
+GuardsGather gather_args(const h2v_batch* b, bool left, const GuardsCall& c) {
+    const PlanDevice* pd = b->plan;
+    return GuardsGather{left ? pd->left_terms.p : pd->right_terms.p, left ? c.TL : c.TR, left ? b->left_scal.p : b->msm_scal.p, b->shared.p, b->pts.p, b->status,
+                        b->n, pd->host.n_points, c.first, c.count};
+}
+// the byte form of the range into six arrays of device memory (each may be null), on the batch's stream
+int guards_bytes_enqueue(h2v_batch* b, const GuardsCall& c, uint8_t* const d[6]) {
+    int rc;
+    if ((rc = guards_gather_bytes_enqueue(b->stream, gather_args(b, true, c), d[0], d[1])) ||
+        (rc = guards_gather_bytes_enqueue(b->stream, gather_args(b, false, c), d[2], d[3]))) return rc;
+    return guards_proofs_enqueue(b->stream, b->mult.p, b->status, c.first, c.count, d[4], reinterpret_cast<int*>(d[5]));
+}
+// After a synchronise of the batch's stream: an upload that took its draws from device memory (h2v_batch_upload_device) has
+// k_ingest_draws' verdict in the batch's pinned block, and a draw >= r there is what finish_impl refuses the launch for.  The forms that
+// wait for the stream refuse it in the same words and hand out nothing; the stage stays, so the finish still reports it.
+int guards_draw_fault(const h2v_batch* b, const char* who) {
+    if (!b->device_draws) return 0;
+    const uint32_t* verdict = reinterpret_cast<const uint32_t*>(b->ingest_host.p);
+    if (verdict[0] == 0xffffffffu) return 0;
+    set_last_error(std::string(who) + ": rand_tail scalar not canonical (draw " + std::to_string(verdict[0]) + " of the tail uploaded from device memory)");
+    return H2V_ERR_BAD_ARGUMENT;
+}
+// the bytes the byte form writes per output: scalars and bases of either channel, multipliers, statuses
+void guards_bytes_sizes(const GuardsCall& c, size_t bytes[6]) {
+    const size_t n = c.count;
+    bytes[0] = 32 * n * c.TL; bytes[1] = 64 * n * c.TL; bytes[2] = 32 * n * c.TR; bytes[3] = 64 * n * c.TR; bytes[4] = 32 * n; bytes[5] = 4 * n;
+}
+}  // namespace
+
+int h2v_batch_guard_shape(const h2v_batch* b, size_t* n_left_terms, size_t* n_right_terms) {
+    static const char who[] = "h2v_batch_guard_shape";
+    if (int rc = require_stage(b, BatchStage::Uploaded, who)) return rc;
+    if (!b->plan) { set_last_error(std::string(who) + ": the batch holds no plan"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n_left_terms) *n_left_terms = b->plan->host.left_term_order.size();
+    if (n_right_terms) *n_right_terms = b->plan->host.right_term_order.size();
+    return 0;
+}
+
+int h2v_batch_guards_device(h2v_batch* b, size_t first, size_t count, void* d_left_scalars32, void* d_left_bases64, void* d_right_scalars32, void* d_right_bases64,
+                            void* d_mult32, void* d_status) {
+    static const char who[] = "h2v_batch_guards_device";
+    static const char* const what[6] = {"d_left_scalars32", "d_left_bases64", "d_right_scalars32", "d_right_bases64", "d_mult32", "d_status"};
+    GuardsCall c;
+    int rc;
+    if ((rc = guards_call_check(b, who, first, count, c))) return rc;
+    if (!count) return 0;
+    uint8_t* const d[6] = {static_cast<uint8_t*>(d_left_scalars32), static_cast<uint8_t*>(d_left_bases64), static_cast<uint8_t*>(d_right_scalars32),
+                           static_cast<uint8_t*>(d_right_bases64), static_cast<uint8_t*>(d_mult32), static_cast<uint8_t*>(d_status)};
+    size_t bytes[6];
+    guards_bytes_sizes(c, bytes);
+    const int device = b->ctx->device;
+    H2V_HIP_CHECK(hipSetDevice(device));
+    for (int k = 0; k < 6; ++k)
+        if (d[k] && (rc = device_range_check(d[k], bytes[k], device, what[k], who, "writes"))) return rc;
+    // every argument is valid: device work from here on, and a failure of it leaves the batch Empty like any other
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b)) || (rc = guards_bytes_enqueue(b, c, d))) return rc;
+    commit.commit(stage);
+    return 0;
+}
+
+int h2v_batch_guards(h2v_batch* b, size_t first, size_t count, uint8_t* left_scalars32, uint8_t* left_bases64, uint8_t* right_scalars32, uint8_t* right_bases64,
+                     uint8_t* mult32, int* per_proof_status) {
+    static const char who[] = "h2v_batch_guards";
+    GuardsCall c;
+    int rc;
+    if ((rc = guards_call_check(b, who, first, count, c))) return rc;
+    uint8_t* const h[6] = {left_scalars32, left_bases64, right_scalars32, right_bases64, mult32, reinterpret_cast<uint8_t*>(per_proof_status)};
+    size_t bytes[6], at[6], total = 0;
+    guards_bytes_sizes(c, bytes);
+    for (int k = 0; k < 6; ++k) { at[k] = total; if (h[k]) total += bytes[k]; }   // (every size but the last is a multiple of 16)
+    if (!total) return 0;
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
+    // (the scratch is idle: the call that used it last has waited for the stream)
+    if ((rc = b->guards_scratch.reserve(total))) return rc;
+    uint8_t* d[6];
+    for (int k = 0; k < 6; ++k) d[k] = h[k] ? b->guards_scratch.p + at[k] : nullptr;
+    if ((rc = guards_bytes_enqueue(b, c, d))) return rc;
+    std::vector<uint8_t> host(total);   // (nothing is written on an error)
+    H2V_HIP_CHECK(hipMemcpyAsync(host.data(), b->guards_scratch.p, total, hipMemcpyDeviceToHost, b->stream));
+    H2V_HIP_CHECK(hipStreamSynchronize(b->stream));
+    commit.commit(stage);   // (the device work is done; a draw fault below refuses the call and leaves the launch to its finish)
+    if ((rc = guards_draw_fault(b, who))) return rc;
+    for (int k = 0; k < 6; ++k) if (h[k]) memcpy(h[k], host.data() + at[k], bytes[k]);
+    return 0;
+}
+
+// The object form: k_guards_gather writes the words and the points straight behind the objects' ends, on the BATCH's stream.  The
+// objects' arrays belong to their contexts' streams, which every h2v_msm_* call leaves idle and which the locks held here keep idle;
+// the batch's stream is waited for before the lengths change, so the call returns as every call on an object does: nothing in flight
+// over its arrays.  (h2v_accumulator_process_batch orders the two sides the same way: one side idle, one synchronise at the end.)
+int h2v_batch_guards_append(h2v_batch* b, size_t first, size_t count, h2v_msm* left, h2v_msm* right, size_t* n_failed) {
+    static const char who[] = "h2v_batch_guards_append";
+    const std::string w(who);
+    GuardsCall c;
+    int rc;
+    if ((rc = guards_call_check(b, who, first, count, c))) return rc;
+    if (left && left == right) { set_last_error(w + ": left and right are the same object"); return H2V_ERR_BAD_ARGUMENT; }
+    h2v_msm* const objs[2] = {left, right};
+    const size_t add[2] = {count * (size_t)c.TL, count * (size_t)c.TR};
+    for (int k = 0; k < 2; ++k) {
+        const h2v_msm* m = objs[k];
+        if (!m) continue;
+        if (m->ctx->device != b->ctx->device) { set_last_error(w + ": an object on another device than the batch"); return H2V_ERR_BAD_ARGUMENT; }
+        if (m->ctx != b->ctx && !same_srs(m->ctx->params, b->ctx->params)) { set_last_error(w + ": an object over other params than the batch (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    }
+    const CtxLocksPtr locks = lock_contexts(left ? left->ctx : nullptr, right ? right->ctx : nullptr);   // the objects' contexts, in the one order, until the call returns
+    for (int k = 0; k < 2; ++k)   // (the lengths are read under the lock)
+        if (objs[k] && (add[k] > H2V_MSM_MAX_TERMS || objs[k]->n + add[k] > H2V_MSM_MAX_TERMS)) { set_last_error(w + ": more than 2^24 terms in one object"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!count) { if (n_failed) *n_failed = 0; return 0; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    for (int k = 0; k < 2; ++k)   // grow first: nothing a caller can see changes
+        if (objs[k] && (rc = msm_object_reserve(objs[k], objs[k]->n + add[k], objs[k]->ctx->stream))) return rc;
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b)) || (rc = b->guards_scratch.reserve(4 * (size_t)count))) return rc;
+    int* const d_status = reinterpret_cast<int*>(b->guards_scratch.p);
+    if ((left && (rc = guards_gather_terms_enqueue(b->stream, gather_args(b, true, c), left->scal.p + 8 * left->n, left->pts.p + left->n))) ||
+        (right && (rc = guards_gather_terms_enqueue(b->stream, gather_args(b, false, c), right->scal.p + 8 * right->n, right->pts.p + right->n))) ||
+        (rc = guards_proofs_enqueue(b->stream, nullptr, b->status, c.first, c.count, nullptr, d_status))) { hipStreamSynchronize(b->stream); return rc; }
+    std::vector<int> st(count);
+    hipError_t e = hipMemcpyAsync(st.data(), d_status, 4 * count, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t e2 = hipStreamSynchronize(b->stream);   // (whatever the copy said: nothing stays in flight over the objects' arrays)
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { set_last_error(w + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    commit.commit(stage);   // (the device work is done; a draw fault below refuses the call and leaves the launch to its finish)
+    if ((rc = guards_draw_fault(b, who))) return rc;
+    // the commit: both lengths, then what the caller reads
+    for (int k = 0; k < 2; ++k) if (objs[k]) objs[k]->n += add[k];
+    size_t failed = 0;
+    for (int v : st) if (v) ++failed;
+    if (n_failed) *n_failed = failed;
+    return 0;
+}
+
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
                             const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail, int with_pairing) {

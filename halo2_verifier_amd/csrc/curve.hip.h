@@ -24,6 +24,12 @@ struct G1A {
         Fq three = Fq::from_u32(3);
         return y.sqr() == x.sqr() * x + three;
     }
+    // canonical little-endian x | y as 16 words, the identity all-zero: the point's bytes at the library's boundary (k_affine_to_bytes,
+    // k_guards_gather); x and y leave Montgomery form by one product with 1 each
+    H2V_HD void to_xy_raw(uint32_t w[16]) const {
+        if (is_identity()) { for (int j = 0; j < 16; ++j) w[j] = 0; }
+        else { x.to_raw(w); y.to_raw(w + 8); }
+    }
 };
 
 struct G1J {

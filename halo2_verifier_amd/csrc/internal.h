@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/h2v.h"
 #include "../../include/h2v_draws.h"
+#include "../../include/h2v_guards.h"
 #include "curve.hip.h"
 
 namespace h2v {

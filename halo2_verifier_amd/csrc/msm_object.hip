@@ -28,10 +28,7 @@
 
 using namespace h2v;
 
-namespace {
-
-struct Drain { hipStream_t s; ~Drain() { hipStreamSynchronize(s); } };
-
+namespace h2v {
 // the locks of the distinct contexts of a call, taken in one global order (by address) and held until the call returns
 struct CtxLocks {
     std::vector<h2v_ctx*> c;
@@ -45,6 +42,18 @@ struct CtxLocks {
     }
     ~CtxLocks() { if (held) for (size_t i = c.size(); i-- > 0;) c[i]->mu.unlock(); }
 };
+void CtxLocksDelete::operator()(CtxLocks* l) const { delete l; }
+CtxLocksPtr lock_contexts(h2v_ctx* a, h2v_ctx* b) {
+    CtxLocksPtr l(new CtxLocks);
+    l->add(a); l->add(b);
+    l->lock();
+    return l;
+}
+}  // namespace h2v
+
+namespace {
+
+struct Drain { hipStream_t s; ~Drain() { hipStreamSynchronize(s); } };
 
 int bad(const char* who, const char* what) { set_last_error(std::string(who) + ": " + what); return H2V_ERR_BAD_ARGUMENT; }
 
@@ -135,6 +144,7 @@ int eval_launches(h2v_ctx* ctx, const char* who, h2v_msm* const* objs, size_t P,
 }  // namespace
 
 namespace h2v {
+int msm_object_reserve(h2v_msm* m, size_t need, hipStream_t s) { return grow(m, need, s); }
 int msm_object_eval_pair(h2v_ctx* ctx, const char* who, h2v_msm* left, h2v_msm* right, G1J* d_pair) {
     h2v_msm* objs[2] = {left, right};
     int rc;

@@ -115,10 +115,7 @@ __global__ void __launch_bounds__(256) k_affine_to_bytes(const G1A* __restrict__
     if (i >= n) return;
     const G1A a = in[i];
     uint32_t w[16];
-    if (a.is_identity()) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = 0;
-    } else { a.x.to_raw(w); a.y.to_raw(w + 8); }
+    a.to_xy_raw(w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) out[4 * (size_t)i + j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
 }

@@ -125,6 +125,10 @@ struct Plan {
 // Returns 0 or an H2V error code (InstanceTooLarge, ReferencePanic for an empty gate polynomial, ...)
 int compile_plan(const VkHost& vk, const ParamsHost& params, const std::vector<size_t>& col_lens, PlanOptions opts, Plan& out, std::string& err);
 
+// One term of a channel in the plan's order, as the gather of a batch's Guards reads it (guards_out.hip): kind 0 = point slot `index`
+// of the proof (its scalar in msm_scal / left_scal), kind 1 = VK-wide base `index` (its scalar in shared)
+struct GuardTerm { uint32_t kind, index; };
+
 struct PlanDevice {
     Plan host;
     DevBuf<VmInstr> code;
@@ -135,6 +139,7 @@ struct PlanDevice {
     DevBuf<uint32_t> point_offsets;
     DevBuf<uint32_t> scalar_offsets;
     DevBuf<G1A> shared_bases, shared_phi;   // the VK-wide bases and their images under phi (MsmProblem::phi2)
+    DevBuf<GuardTerm> left_terms, right_terms;   // host.left_term_order / right_term_order as (kind, index) pairs (k_guards_gather)
     int pins = 0;             // users that hold the plan (batches between upload and their next upload / destruction, entry points while
                               // they read it); guarded by VkDevice::mu.  Only unpinned plans are evicted.
     uint64_t last_use = 0;    // VkDevice::clock at the last ctx_get_plan

@@ -1128,6 +1128,12 @@ int PlanDevice::upload() {
     std::vector<G1A> phi;
     for (const G1A& b : host.shared_bases) phi.push_back(g1_phi(b));
     if ((rc = upload_vec(phi, shared_phi))) return rc;
+    std::vector<GuardTerm> order;
+    for (const auto& t : host.left_term_order) order.push_back(GuardTerm{t.first, t.second});
+    if ((rc = upload_vec(order, left_terms))) return rc;
+    order.clear();
+    for (const auto& t : host.right_term_order) order.push_back(GuardTerm{t.first, t.second});
+    if ((rc = upload_vec(order, right_terms))) return rc;
     return 0;
 }
 

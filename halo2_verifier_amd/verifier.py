@@ -1503,6 +1503,32 @@ class Batch:
             current.wait_event(after)
         self._drop_done_tails()
 
+    # ---- every proof's Guard out of the last launch (include/h2v_guards.h; guards.py holds the binding and says what a Guard of a batch is)
+    def guard_shape(self):
+        """-> (T_L, T_R): the terms of a proof's left and right channel under the plan of the upload"""
+        from . import guards
+        return guards.guard_shape(self)
+
+    def guards(self, first=0, count=None):
+        """The Guards of proofs [first, first + count) (count None: to the end) of the last launch, by one kernel, one copy and one
+        synchronise -> one dict per proof as Context.guard_msm returns it (right_scalars, right_bases, left_scalars, left_bases), plus
+        mult (32 bytes: the product of the draws behind the proof in its group, which every scalar carries) and status.  The batch
+        must be launched or finished; its stage and its results do not change."""
+        from . import guards
+        return guards.guards(self, first, count)
+
+    def guards_into(self, first=0, count=None, left_scalars=None, left_bases=None, right_scalars=None, right_bases=None, mult=None, status=None):
+        """guards() into device memory, tensors or 16-byte aligned device addresses (None = not wanted), by kernels on the batch's
+        stream and without a host wait (guards.guards_into)."""
+        from . import guards
+        return guards.guards_into(self, first, count, left_scalars, left_bases, right_scalars, right_bases, mult, status)
+
+    def guards_append(self, left=None, right=None, first=0, count=None):
+        """The range's left terms behind the end of the MSMKZG `left`, its right terms behind the end of `right` (either may be None),
+        in the objects' own form -> the number of proofs of the range with a non-zero status (guards.guards_append)."""
+        from . import guards
+        return guards.guards_append(self, left, right, first, count)
+
     def recheck(self, ranges):
         """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
         ranges: list of (first, count), each inside one group of the launch.  -> (oks, lefts, rights): one verdict and the two
