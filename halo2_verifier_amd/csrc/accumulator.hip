@@ -276,8 +276,9 @@ int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n, const size_t* l
     M.to_bytes(m_bytes);
     memcpy(a->host_scalar, m_bytes, 32);
     H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    const GroupShape whole{1, (uint32_t)n, (uint32_t)n, nullptr};   // the Guards of one call: one group, a draw each
     const uint32_t nl = (uint32_t)std::max<size_t>(g.off[0][n], 1), nr = (uint32_t)std::max<size_t>(g.off[1][n], 1);   // (an empty side is staged as one zero term)
-    if ((rc = a->g_rand.reserve(32 * n)) || (rc = a->g_mult.reserve(n)) || (rc = a->g_tiles.reserve(multipliers_scratch((uint32_t)n, 1))) || (rc = a->g_sums.reserve(2)) ||
+    if ((rc = a->g_rand.reserve(32 * n)) || (rc = a->g_mult.reserve(n)) || (rc = a->g_tiles.reserve(multipliers_scratch(whole))) || (rc = a->g_sums.reserve(2)) ||
         (rc = a->g_ws.reserve(std::max(nl + nr, 1024u), 2, std::max(nl, nr)))) return rc;
     hipStream_t s = a->stream;
     Drain drain{s};
@@ -285,7 +286,7 @@ int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n, const size_t* l
     H2V_HIP_CHECK(hipMemcpyAsync(a->scalar.p, a->host_scalar, 32, hipMemcpyHostToDevice, s));
     if ((rc = accumulator_scale_enqueue(s, a->acc.p, a->scalar.p, a->records.p))) return rc;
     H2V_HIP_CHECK(hipMemcpyAsync(a->g_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, s));
-    if ((rc = multipliers_enqueue(s, a->g_rand.p, (uint32_t)n, (uint32_t)n, 1, a->g_mult.p, a->g_tiles.p))) return rc;
+    if ((rc = multipliers_enqueue(s, whole, a->g_rand.p, nullptr, a->g_mult.p, a->g_tiles.p))) return rc;
     GuardStage& st = a->g_stage;
     if ((rc = guard_stage_enqueue(s, st, g, 0, n, false, a->g_mult.p))) return rc;
     MsmProblems pr;
@@ -339,7 +340,7 @@ int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_pr
     std::vector<size_t> count(G), failed(G, 0);
     size_t all_failed = 0;
     for (size_t g = 0, i = 0; g < G; ++g) {
-        count[g] = group_count(b, g);
+        count[g] = group_shape(b).count(g);
         for (size_t k = 0; k < count[g]; ++k, ++i) if (st[i]) ++failed[g];
         all_failed += failed[g];
     }
@@ -362,7 +363,7 @@ int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_pr
         for (size_t g = 0; g < G; ++g) h_slots[g] = a->free_slots[a->free_slots.size() - 1 - g];   // the lowest free slots, in group order
         H2V_HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, 4 * G, hipMemcpyHostToDevice, s));
     }
-    if ((rc = leg_weights_enqueue(s, b->tail.p, b->mult.p, ragged(b) ? b->d_group_off.p : nullptr, (uint32_t)(n / G), (uint32_t)G, d_weights, d_legs))) return rc;
+    if ((rc = leg_weights_enqueue(s, group_shape_device(b), b->tail.p, b->mult.p, d_weights, d_legs))) return rc;
     H2V_HIP_CHECK(hipMemcpyAsync(a->l_legs.p, d_legs, 32 * G, hipMemcpyDeviceToHost, s));   // (in front of the commit: nothing that can fail is enqueued behind it)
     if ((rc = accumulator_scale_many_enqueue(s, a->l_pairs.p, nullptr, d_weights, (uint32_t)(G + 1), a->l_records.p))) return rc;
     // the commit: the journal's slots, then (L, R) <- M (L, R) + sum_g W_g S_g

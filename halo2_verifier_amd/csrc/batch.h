@@ -86,26 +86,65 @@ int decompress_begin_enqueue(hipStream_t s, const StageArgs& g);
 int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
-// groups > 1: group g owns proofs [g*n/groups, ..) and the draws tail[g*n_tail/groups, ..)
-// d_scratch: multipliers_scratch(n_tail, groups) elements (the tiles' products of the two-level scan)
-size_t multipliers_scratch(uint32_t n_tail, uint32_t groups);
-int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult, Fr* d_scratch);
-// Groups of unequal size (h2v_batch_set_group_sizes): d_mult[j] = the product of the draws behind j inside j's own group, for n draws
-// (one per proof) whose groups end where d_last[j] != 0 (d_last[n - 1] != 0).  A segmented suffix scan over the whole array: work
-// proportional to n whatever the sizes.  d_tile_prod: ragged_multipliers_tiles(n) elements, d_tile_words: twice as many words.
-size_t ragged_multipliers_tiles(uint32_t n);
-int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8_t* d_last, uint32_t n, Fr* d_mult, Fr* d_tile_prod, uint32_t* d_tile_words);
+// The groups of one upload: which proofs and which draws belong to group g.  One plain struct for host code and kernels (a kernel
+// takes it by value); everything that must know where a group starts, how long it is or whose a proof is asks it.
+//   off null      G equal groups (h2v_batch_set_groups) of gs proofs and nt >= gs draws each (nt > gs: a shard's tail): group g owns
+//                 the proofs [g gs, (g + 1) gs) and the draws [g nt, (g + 1) nt)
+//   off[0 .. G]   groups of unequal size (h2v_batch_set_group_sizes), host or device memory as the reader needs: group g owns the
+//                 proofs [off[g], off[g + 1]) and the same draws, one per proof; gs = nt = off[G], all the proofs, so that fits()
+//                 looks into no array
+struct GroupShape {
+    uint32_t G, gs, nt; const uint32_t* off;
+    static GroupShape equal(uint32_t G, uint32_t n, uint32_t n_tail) { return GroupShape{G, n / G, n_tail / G, nullptr}; }
+    static GroupShape unequal(uint32_t G, uint32_t n, const uint32_t* off) { return GroupShape{G, n, n, off}; }
+    __host__ __device__ uint32_t first(uint32_t g) const { return off ? off[g] : g * gs; }
+    __host__ __device__ uint32_t count(uint32_t g) const { return off ? off[g + 1] - off[g] : gs; }
+    __host__ __device__ uint32_t draw_first(uint32_t g) const { return off ? off[g] : g * nt; }
+    __host__ __device__ uint32_t of(uint32_t proof) const { return owner(proof, gs); }   // proof < n
+    struct Draw { uint32_t g, j; };
+    __host__ __device__ Draw draw_at(uint32_t i) const { const uint32_t g = owner(i, nt); return Draw{g, i - draw_first(g)}; }   // draw i < n_tail is the j-th of group g
+    // A zero draw zeroes the multipliers of every earlier proof of its group: the j-th draw of group g, when zero, leaves the group's
+    // proofs [0, zero_below(j, g)) with a zero multiplier (an equal group's draws past its proofs, a shard's tail, zero them all)
+    __host__ __device__ uint32_t zero_below(uint32_t j, uint32_t g) const { const uint32_t c = count(g); return j < c ? j : c; }
+    uint32_t largest() const { uint32_t m = off ? 0 : gs; for (uint32_t g = 0; off && g < G; ++g) m = std::max(m, count(g)); return m; }
+    // What keeps an upload of n proofs and n_tail draws (have_tail false: no draws of the caller's, n_tail is not looked at) from having
+    // this shape, in the words of the upload's error messages; null: it fits
+    const char* misfit(size_t n, size_t n_tail, bool have_tail) const {
+        if (have_tail && n_tail < n) return "n_tail < n";
+        if (off) {
+            if (n != gs) return "n is not the sum of the group sizes (h2v_batch_set_group_sizes)";
+            if (have_tail && n_tail != n) return "groups of unequal size take one draw per proof (n_tail == n)";
+        } else if (n != (size_t)G * gs || (have_tail && n_tail != (size_t)G * nt)) return "n and n_tail must be multiples of the group count";
+        return nullptr;
+    }
+    bool fits(size_t n, size_t n_tail, bool have_tail) const { return !misfit(n, n_tail, have_tail); }
+private:
+    // the group that owns index i: i / per for equal groups, else the last g with off[g] <= i (off[0] = 0, off[G] > i)
+    __host__ __device__ uint32_t owner(uint32_t i, uint32_t per) const {
+        if (!off) return i / per;
+        uint32_t lo = 0, hi = G;
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+        return lo;
+    }
+};
+// d_mult[p] = the product of the draws behind proof p's own inside p's group, for the draws d_tail of `shape` (off in device memory or
+// not: only its presence is read): one segmented suffix scan over the whole draw array, work proportional to the draws whatever the
+// sizes.  Unequal groups end where d_last[j] != 0 (one byte per draw, d_last[n - 1] != 0); equal groups end by arithmetic, d_last is
+// not read and may be null.  d_scratch: multipliers_scratch(shape) elements.
+size_t multipliers_scratch(const GroupShape& shape);
+int multipliers_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const uint8_t* d_last, Fr* d_mult, Fr* d_scratch);
 // The legs of a finished batch (k_leg_weights; h2v_accumulator_process_batch): with M_g = the product of group g's draws — the draw of
-// its first proof, d_tail[32 first_g ..], times that proof's multiplier d_mult[first_g]; first_g = d_off[g], or g * gs (d_off null) —
+// its first proof, d_tail[32 shape.first(g) ..], times that proof's multiplier d_mult[shape.first(g)] (one draw per proof; off in
+// device memory, read up to off[G - 1]) —
 // d_weights <- [prod_g M_g, W_0 .. W_{G-1}], W_g = prod_{f > g} M_f, and d_legs <- [M_0 .. M_{G-1}], canonical 8-word scalars.
-// 1 <= groups <= 512: one workgroup.
-int leg_weights_enqueue(hipStream_t s, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_off, uint32_t gs, uint32_t groups, uint32_t* d_weights, uint32_t* d_legs);
+// 1 <= shape.G <= 512: one workgroup.
+int leg_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const Fr* d_mult, uint32_t* d_weights, uint32_t* d_legs);
 // out[i] = src[idx[i]]: the multipliers of a non-contiguous subset of a larger accumulation
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
-int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal);
-// the same for groups of unequal size: group g owns the proofs [d_off[g], d_off[g + 1])
-int fold_shared_offsets_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, const uint32_t* d_off, uint32_t* d_msm_scal);
+// d_msm_scal[(n np + g n_shared + j) 8 ..] = canonical( sum over the proofs p of group g of d_shared[j n + p] ), n the proofs of the
+// upload (shape.off in device memory)
+int fold_shared_enqueue(hipStream_t s, const GroupShape& shape, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t* d_msm_scal);
 // One range of a re-check (k_fold_ranges): proofs [first, first + count) of a batch whose VK-wide scalars are shared[j][p] (j <
 // n_shared, p < n); its n_shared folded scalars go to rows [out, out + n_shared) of the output.  Ranges of one launch may belong to
 // different batches (h2v_batches_recheck), so each carries its own batch's pointer and sizes.
@@ -249,7 +288,6 @@ struct h2v_batch {
     std::vector<uint32_t> group_off;
     std::vector<uint8_t> group_last;  // per proof: it is the last of its group (the segmented scan's input, copied with the draws)
     h2v::DevBuf<uint32_t> d_group_off; h2v::DevBuf<uint8_t> d_group_last;
-    h2v::DevBuf<uint32_t> mult_seg;   // ragged_multipliers_enqueue's words per tile
     std::vector<uint32_t> zero_below; // per group: proofs [0, zero_below[g]) of the group have a zero multiplier (a zero draw behind them in the uploaded tail)
     // h2v_batch_upload_device with the caller's draws: k_ingest_draws checks them, and its verdict [fault][zero_below x groups] waits in
     // pinned memory of the batch's own for h2v_batch_finish, which fills zero_below from it (device block: + the count of workgroups done)
@@ -264,7 +302,7 @@ struct h2v_batch {
     h2v::DevBuf<h2v::G1A> pts, phi;   // the batch's points + the VK-wide bases, and their images under the GLV endomorphism (same shape)
     h2v::DevBuf<uint8_t> ycanon;
     h2v::DevBuf<unsigned long long> words; h2v::DevBuf<h2v::Fr> chal, mult, slots;
-    h2v::DevBuf<h2v::Fr> mult_tiles;  // multipliers_enqueue's scratch
+    h2v::DevBuf<h2v::Fr> mult_scratch;  // multipliers_enqueue's scratch
     bool mult_of_draws = false;       // Uploaded and later: `mult` holds the multipliers of the uploaded draws (not gathered ones, h2v_verify_batch_shapes)
     h2v::DevBuf<uint32_t> msm_scal; h2v::DevBuf<h2v::Fr> shared; h2v::DevBuf<uint32_t> left_scal;
     h2v::DevBuf<h2v::Fr> insteval;    // [query][proof] (wide instance vectors)
@@ -288,12 +326,11 @@ struct h2v_batch {
 };
 
 namespace h2v {
-// where the groups of the batch's upload lie: equal slices, or the offsets of h2v_batch_set_group_sizes
-inline bool ragged(const h2v_batch* b) { return !b->group_off.empty(); }
-inline size_t group_first(const h2v_batch* b, size_t g) { return ragged(b) ? b->group_off[g] : g * (b->n / b->groups); }
-inline size_t group_count(const h2v_batch* b, size_t g) { return ragged(b) ? b->group_off[g + 1] - b->group_off[g] : b->n / b->groups; }
-inline size_t group_of(const h2v_batch* b, size_t proof) {   // proof < n
-    if (!ragged(b)) return proof / (b->n / b->groups);
-    return (size_t)(std::upper_bound(b->group_off.begin(), b->group_off.end(), (uint32_t)proof) - b->group_off.begin()) - 1;
+// The groups of the batch's upload — what (groups, n, n_tail, group_off) fixed — for host code, and with the offsets' device copy for
+// a kernel; group_shape_of: of an upload of n proofs and n_tail draws that the batch has not taken yet
+inline GroupShape group_shape_of(const h2v_batch* b, size_t n, size_t n_tail, const uint32_t* off) {
+    return b->group_off.empty() ? GroupShape::equal(b->groups, (uint32_t)n, (uint32_t)n_tail) : GroupShape::unequal(b->groups, b->group_off.back(), off);
 }
+inline GroupShape group_shape(const h2v_batch* b) { return group_shape_of(b, b->n, b->n_tail, b->group_off.data()); }
+inline GroupShape group_shape_device(const h2v_batch* b) { return group_shape_of(b, b->n, b->n_tail, b->d_group_off.p); }
 }  // namespace h2v

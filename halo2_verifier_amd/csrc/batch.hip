@@ -47,10 +47,8 @@ BatchSizes batch_sizes(const Plan& pl, size_t N, size_t G, size_t largest) {
 // out_bytes / status into the results block laid out for that group count
 int ensure_buffers(h2v_batch* b, const Plan& pl) {
     const size_t N = b->max_proofs, G = b->groups;
-    // equal groups: ceil(N / G) proofs each at capacity; unequal groups: the largest of the sizes set
-    size_t largest = (N + G - 1) / G;
-    if (ragged(b)) { largest = 0; for (size_t g = 0; g < G; ++g) largest = std::max<size_t>(largest, b->group_off[g + 1] - b->group_off[g]); }
-    const BatchSizes z = batch_sizes(pl, N, G, largest);
+    // the shape at capacity: equal groups of ceil(N / G) proofs each; unequal groups: the sizes set
+    const BatchSizes z = batch_sizes(pl, N, G, group_shape_of(b, N + G - 1, N + G - 1, b->group_off.data()).largest());
     int rc;
     if ((rc = b->proofs.reserve(z.proofs)) || (rc = b->inst.reserve(z.inst)) || (rc = b->pts.reserve(z.pts)) || (rc = b->phi.reserve(z.pts)) ||
         (rc = b->ycanon.reserve(z.ycanon)) || (rc = b->words.reserve(z.words)) || (rc = b->chal.reserve(z.chal)) || (rc = b->mult.reserve(z.mult)) ||
@@ -253,12 +251,6 @@ static StageArgs stage_args(const h2v_batch* b) {
     return StageArgs{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
 }
 
-// the multipliers of the uploaded draws (-> mult), on the batch's stream
-static int draw_multipliers_enqueue(h2v_batch* b) {
-    if (ragged(b)) return ragged_multipliers_enqueue(b->stream, b->tail.p, b->d_group_last.p, b->n, b->mult.p, b->mult_tiles.p, b->mult_seg.p);
-    return multipliers_enqueue(b->stream, b->tail.p, b->n_tail, b->n, b->groups, b->mult.p, b->mult_tiles.p);
-}
-
 // ---- An upload, whatever its source: host bytes (upload_impl) or device memory (h2v_batch_upload_device).  Every step the sources share
 // exists once — upload_pin, upload_size_checks, upload_take, shared_bases_enqueue, upload_commit — and an entry point adds its own
 // checks between the first two and after the second, and its own transfer between upload_take and upload_commit.
@@ -289,41 +281,35 @@ static int upload_pin(const h2v_batch* b, const UploadArgs& a, int columns_code,
 }
 
 // The checks of an upload on its sizes alone, for the plan `pl` of its instance shape: instances where the plan has instance values, the
-// draws' count against n, the groups' divisibility or the sum of their sizes, and the launch's MSM cut.
+// proofs and draws against the batch's groups (GroupShape::misfit), and the launch's MSM cut.
 static int upload_size_checks(const h2v_batch* b, const Plan& pl, const UploadArgs& a) {
     const std::string w(a.who);
-    const size_t n = a.n, n_tail = a.n_tail;
     const bool have_tail = a.tail != nullptr;
-    if (pl.n_instance_values && n && !a.instances) { set_last_error(w + ": instances missing"); return H2V_ERR_BAD_ARGUMENT; }
-    if (have_tail && n_tail < n) { set_last_error(w + ": n_tail < n"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ragged(b)) {
-        if (n != b->group_off.back()) { set_last_error(w + ": n is not the sum of the group sizes (h2v_batch_set_group_sizes)"); return H2V_ERR_BAD_ARGUMENT; }
-        if (have_tail && n_tail != n) { set_last_error(w + ": groups of unequal size take one draw per proof (n_tail == n)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (pl.n_instance_values && a.n && !a.instances) { set_last_error(w + ": instances missing"); return H2V_ERR_BAD_ARGUMENT; }
+    const GroupShape shape = group_shape_of(b, a.n, have_tail ? a.n_tail : a.n, b->group_off.data());
+    if (const char* why = shape.misfit(a.n, a.n_tail, have_tail)) { set_last_error(w + ": " + why); return H2V_ERR_BAD_ARGUMENT; }
+    if (shape.off) {
         // the MSM cuts problems too large for its per-window sort into sub-problems, at most MSM_MAX_PROBLEMS per launch; equal groups that miss
         // the limit all run uncut, a form that unequal groups have never taken: refused before any device work
-        std::vector<size_t> sizes(b->groups);
-        for (size_t g = 0; g < b->groups; ++g) sizes[g] = b->group_off[g + 1] - b->group_off[g];
+        std::vector<size_t> sizes(shape.G);
+        for (uint32_t g = 0; g < shape.G; ++g) sizes[g] = shape.count(g);
         if (!b->ctx->tuning.msm_no_term_split && !groups_cut_within_limit(pl, sizes.data(), sizes.size())) {
             set_last_error(w + ": the groups' MSM problems, cut into sub-problems of at most 16384 terms, exceed the launch's problem limit");
             return H2V_ERR_UNSUPPORTED;
         }
-    } else if (b->groups > 1 && (n % b->groups || (have_tail && n_tail % b->groups))) { set_last_error(w + ": n and n_tail must be multiples of the group count"); return H2V_ERR_BAD_ARGUMENT; }
+    }
     return 0;
 }
 // a zero draw zeroes the multipliers of every earlier proof of its group: h2v_batch_recheck refuses ranges over those proofs.
-// (The rule k_ingest_draws restates for draws in device memory.)
-static void zero_below_of_draws(h2v_batch* b, size_t n, const uint8_t* rand_tail, size_t n_tail) {
+// (k_ingest_draws runs the body of this loop, a thread per draw, for draws in device memory.)
+static void zero_below_of_draws(h2v_batch* b, const uint8_t* rand_tail) {
     b->zero_below.assign(b->groups, 0);
-    if (ragged(b)) {
-        for (size_t g = 0; g < b->groups; ++g)   // (each group from its own draws)
-            for (size_t f = b->group_off[g], j = b->group_off[g + 1] - f; j-- > 1;)
-                if (scalar_is_zero(rand_tail + 32 * (f + j))) { b->zero_below[g] = (uint32_t)j; break; }
-    } else if (n) {
-        const size_t G = b->groups, gs = n / G, nt = n_tail / G;
-        for (size_t g = 0; g < G; ++g)
-            for (size_t j = nt; j-- > 1;)
-                if (scalar_is_zero(rand_tail + 32 * (g * nt + j))) { b->zero_below[g] = (uint32_t)std::min(j, gs); break; }
-    }
+    const GroupShape shape = group_shape(b);
+    for (uint32_t i = 0; i < b->n_tail; ++i)
+        if (scalar_is_zero(rand_tail + 32 * (size_t)i)) {
+            const GroupShape::Draw d = shape.draw_at(i);
+            b->zero_below[d.g] = std::max(b->zero_below[d.g], shape.zero_below(d.j, d.g));
+        }
 }
 
 // Every argument is valid: from here on the batch takes the upload of n proofs under the pinned plan, with n_tail draws: host_draws,
@@ -335,13 +321,10 @@ static int upload_take(h2v_batch* b, PlanPin& pin, size_t n, size_t n_tail, cons
     b->plan = pin.take(); b->n = (uint32_t)n; b->n_tail = (uint32_t)n_tail;
     const size_t G = b->groups;
     if (device_draws) b->zero_below.assign(G, 0);   // (filled by h2v_batch_finish from the verdict block)
-    else zero_below_of_draws(b, n, host_draws, n_tail);
+    else zero_below_of_draws(b, host_draws);
     if ((rc = b->tail.reserve(32 * n_tail))) return rc;
     if (device_draws && ((rc = b->ingest_verdict.reserve(G + 2)) || (rc = b->ingest_host.reserve(4 * (G + 1))))) return rc;
-    if (ragged(b)) {   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
-        const size_t tiles = ragged_multipliers_tiles((uint32_t)n);
-        if ((rc = b->mult_tiles.reserve(tiles)) || (rc = b->mult_seg.reserve(2 * tiles))) return rc;
-    } else if ((rc = b->mult_tiles.reserve(multipliers_scratch((uint32_t)n_tail, b->groups)))) return rc;
+    if ((rc = b->mult_scratch.reserve(multipliers_scratch(group_shape(b))))) return rc;   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
     b->mult_of_draws = false; b->decompressed = false; b->device_draws = device_draws;
     return 0;
 }
@@ -357,7 +340,7 @@ static int shared_bases_enqueue(h2v_batch* b, hipStream_t cs) {
 // The end of an upload, its draws on the device: the batch multipliers depend on the draws alone, so they are computed once per upload
 // and kept by every launch of it
 static int upload_commit(h2v_batch* b, StageCommit& commit) {
-    if (b->n) { if (int rc = draw_multipliers_enqueue(b)) return rc; b->mult_of_draws = true; }
+    if (b->n) { if (int rc = multipliers_enqueue(b->stream, group_shape_device(b), b->tail.p, b->d_group_last.p, b->mult.p, b->mult_scratch.p)) return rc; b->mult_of_draws = true; }
     commit.commit(BatchStage::Uploaded);
     return 0;
 }
@@ -468,6 +451,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     hipStream_t s = b->stream;
     uint32_t n = b->n;
     const uint32_t G = b->groups;
+    const GroupShape host_shape = group_shape(b), shape = group_shape_device(b);   // for this function's own loops; for the kernels
     if ((rc = join_tail(b))) return rc;
     int ev = 0;
     auto mark = [&]() { if (b->profiling >= 2) hipEventRecord(b->ev[ev], s); ++ev; };   // (an event record is a barrier packet: ~6 us of idle stream each)
@@ -490,12 +474,12 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     // scalars at the tail of msm_scal.  The descriptors are addresses and sizes: msm_enqueue_multi sends them only when they differ from the workspace's.
     MsmProblems pr;
     for (uint32_t g = 0; g < G; ++g)
-        channel_problems(pr, b, pl, group_first(b, g), (uint32_t)group_count(b, g), b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
+        channel_problems(pr, b, pl, host_shape.first(g), host_shape.count(g), b->acc.p + 2 * g, b->msm_scal.p + ((size_t)n * pl.n_points + (size_t)g * pl.n_shared) * 8, n ? pl.n_shared : 0);
     b->ws.tune = ctx->tuning;
     if (n) {
         // gathered multipliers replace the upload's; a launch on the draws after one on gathered multipliers computes the upload's again
         if (ext_mult) { b->mult_of_draws = false; if ((rc = gather_multipliers_enqueue(s, ext_mult, ext_idx, n, b->mult.p))) return rc; }
-        else if (!b->mult_of_draws) { if ((rc = draw_multipliers_enqueue(b))) return rc; b->mult_of_draws = true; }
+        else if (!b->mult_of_draws) { if ((rc = multipliers_enqueue(s, shape, b->tail.p, b->d_group_last.p, b->mult.p, b->mult_scratch.p))) return rc; b->mult_of_draws = true; }
         // the program writes only the slots the left channel uses; with ONE left term per proof the MSM reads exactly those (the strided problem above)
         if (!left_strided(pl)) H2V_HIP_CHECK(hipMemsetAsync(b->left_scal.p, 0, (size_t)n * pl.n_points * 32, s));
     }
@@ -516,11 +500,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     for (int k = 0; k < 3; ++k) { for (int q = 0; q < k + 2; ++q) { a.code_k[k][q] = pd->code_k[k][q].p; a.n_code_k[k][q] = (uint32_t)pl.code_k[k][q].size(); } a.n_slots_k[k] = pl.n_slots_k[k]; }
     if ((rc = frvm_enqueue(s, a, pl.n_slots))) return rc;
     mark();
-    if (n) {
-        if (ragged(b)) rc = fold_shared_offsets_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->d_group_off.p, b->msm_scal.p);
-        else rc = fold_shared_enqueue(s, b->shared.p, n, pl.n_points, pl.n_shared, G, b->msm_scal.p);
-        if (rc) return rc;
-    }
+    if (n && (rc = fold_shared_enqueue(s, shape, b->shared.p, n, pl.n_points, pl.n_shared, b->msm_scal.p))) return rc;
     mark();
     {
         b->ws.profile = b->profiling >= 1; b->ws.profile_recorded = false;
@@ -603,7 +583,7 @@ int finish_impl(h2v_batch* b, const char* who, int* per_proof_status, int* group
     uint32_t any = 0;
     for (uint32_t i = 0; i < n; ++i) any |= (uint32_t)st[i];
     if (!any) { if (per_proof_status && n) memset(per_proof_status, 0, sizeof(int) * (size_t)n); }
-    else for (uint32_t g = 0, i = 0; g < G; ++g) for (uint32_t k = 0, gs = (uint32_t)group_count(b, g); k < gs; ++k, ++i) {
+    else for (uint32_t g = 0, i = 0; g < G; ++g) for (uint32_t k = 0, gs = group_shape(b).count(g); k < gs; ++k, ++i) {
         const int v = status_decode(st[i]);
         if (per_proof_status) per_proof_status[i] = v;
         if (v != 0) all_ok[g] = 0;
@@ -662,11 +642,12 @@ int recheck_impl(const char* who, h2v_batch* const* batches, size_t n_batches, s
         const size_t n = b->n;
         const size_t f = first[i], c = count[i];
         if (!c || f >= n || c > n - f) { set_last_error(w + ": empty range, or a range past the launch's proofs"); return H2V_ERR_BAD_ARGUMENT; }
-        const size_t g = group_of(b, f);
+        const GroupShape shape = group_shape(b);
+        const uint32_t g = shape.of((uint32_t)f);
         // multipliers are products of the later draws of the proof's OWN group: the last proof of every group has multiplier 1, and a range
         // over two groups could hold two proofs with equal multipliers whose errors cancel
-        if (group_of(b, f + c - 1) != g) { set_last_error(w + ": a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
-        if (f - group_first(b, g) < b->zero_below[g]) { set_last_error(w + ": a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
+        if (shape.of((uint32_t)(f + c - 1)) != g) { set_last_error(w + ": a range crosses a group boundary of the launch"); return H2V_ERR_BAD_ARGUMENT; }
+        if (f - shape.first(g) < b->zero_below[g]) { set_last_error(w + ": a range covers a proof whose multiplier is zero (a zero draw)"); return H2V_ERR_BAD_ARGUMENT; }
     }
     if (!n_ranges) return 0;
     h2v_batch* host = batches[0];
@@ -837,7 +818,7 @@ int h2v_batch_upload_device(h2v_batch* b, size_t n, const void* d_proofs, size_t
     const uint32_t G = b->groups;
     if ((rc = ingest_rows_enqueue(s, d_proofs, proof_stride, pl.proof_len, n, d_instances, inst_bytes, b->proofs.p, b->inst.p, d_rand_tail ? b->ingest_verdict.p : nullptr, G))) return rc;
     if (d_rand_tail) {
-        if ((rc = ingest_draws_enqueue(s, d_rand_tail, b->tail.p, (uint32_t)n_tail, (uint32_t)n, G, ragged(b) ? b->d_group_off.p : nullptr, b->ingest_verdict.p,
+        if ((rc = ingest_draws_enqueue(s, d_rand_tail, b->tail.p, (uint32_t)n_tail, (uint32_t)n, group_shape_device(b), b->ingest_verdict.p,
                                        static_cast<uint32_t*>(b->ingest_host.dev)))) return rc;
     } else if (n_tail) H2V_HIP_CHECK(hipMemcpyAsync(b->tail.p, host_tail, 32 * n_tail, hipMemcpyHostToDevice, s));
     if ((rc = shared_bases_enqueue(b, s))) return rc;
@@ -879,7 +860,7 @@ int h2v_batch_finish_device(h2v_batch* b, void* d_status, void* d_group_ok, void
     out.group_failed = static_cast<uint32_t*>(d_group_failed); out.failed_index = cap ? static_cast<uint32_t*>(d_failed_index) : nullptr; out.failed_cap = cap;
     out.summary = static_cast<uint32_t*>(d_summary);
     const uint32_t flags = (b->last.pairing ? 1u : 0u) | (b->last.folded ? 2u : 0u);
-    if ((rc = results_enqueue(b->stream, b->status, n, G, ragged(b) ? b->d_group_off.p : nullptr, b->fold_failed, b->ok, flags, b->out_bytes,
+    if ((rc = results_enqueue(b->stream, b->status, n, group_shape_device(b), b->fold_failed, b->ok, flags, b->out_bytes,
                               b->device_draws ? b->ingest_verdict.p : nullptr, b->finish_tiles.p, b->finish_groups.p, out))) return rc;
     commit.commit(stage);
     return 0;
@@ -1109,7 +1090,7 @@ int h2v_batch_set_stream(h2v_batch* b, void* hip_stream) {
 int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
     if (int rc = require_stage(b, BatchStage::Launched, "h2v_batch_export_accumulators")) return rc;
     if (!device_dst) { set_last_error("h2v_batch_export_accumulators: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    if (ragged(b)) { set_last_error("h2v_batch_export_accumulators: the batch has groups of unequal size (a record counts the failures of n / groups proofs)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (group_shape(b).off) { set_last_error("h2v_batch_export_accumulators: the batch has groups of unequal size (a record counts the failures of n / groups proofs)"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     if (int rc = join_tail(b)) return rc;   // (the records: pieces if the launch left pieces)
     if (b->split.parts) return export_records_enqueue(b->stream, nullptr, b->split.pts, b->split.parts, b->split.shift, b->status, b->n, b->groups, device_dst);
@@ -1118,7 +1099,7 @@ int h2v_batch_export_accumulators(h2v_batch* b, void* device_dst) {
 int h2v_batch_fold_check_enqueue(h2v_batch* b, const void* device_accumulators, size_t n_parts) {
     int rc;
     if ((rc = require_stage(b, BatchStage::Launched, "h2v_batch_fold_check_enqueue"))) return rc;
-    if (ragged(b)) { set_last_error("h2v_batch_fold_check_enqueue: the batch has groups of unequal size"); return H2V_ERR_BAD_ARGUMENT; }
+    if (group_shape(b).off) { set_last_error("h2v_batch_fold_check_enqueue: the batch has groups of unequal size"); return H2V_ERR_BAD_ARGUMENT; }
     StageCommit commit{b};
     if (!device_accumulators || !n_parts) { set_last_error("h2v_batch_fold_check_enqueue: bad argument"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
@@ -1156,8 +1137,9 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
     const int* raw = results_at(b->results_host.p, ResultsLayout{G, n}).status;
     std::vector<std::vector<int>> st(1, std::vector<int>(n));
     std::vector<uint32_t> failed(G, 0);
-    for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[group_of(b, i)]; }
-    if (own_records && ragged(b)) { set_last_error(std::string(who) + ": a batch with groups of unequal size exports no records"); return H2V_ERR_BAD_ARGUMENT; }
+    const GroupShape shape = group_shape(b);
+    for (uint32_t i = 0; i < n; ++i) { st[0][i] = status_decode(raw[i]); if (raw[i]) ++failed[shape.of(i)]; }
+    if (own_records && shape.off) { set_last_error(std::string(who) + ": a batch with groups of unequal size exports no records"); return H2V_ERR_BAD_ARGUMENT; }
     if (own_records) {
         std::vector<uint32_t> hdr(4 * (size_t)G);   // [failed, parts, shift, 0] of every record
         H2V_HIP_CHECK(hipMemcpy2DAsync(hdr.data(), 16, own_records, H2V_ACC_RECORD_BYTES, 16, G, hipMemcpyDeviceToHost, s));
@@ -1188,7 +1170,7 @@ int h2v_batch_identify(h2v_batch* b, const void* own_records, int* per_proof_sta
         if (e != hipSuccess) { set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
     }
     std::vector<IdentifyStart> start;
-    for (uint32_t g = 0; g < G; ++g) if (!own[g] && group_count(b, g)) start.push_back({0, group_first(b, g), group_count(b, g)});
+    for (uint32_t g = 0; g < G; ++g) if (!own[g] && shape.count(g)) start.push_back({0, shape.first(g), shape.count(g)});
     size_t checks = 0;
     if (!start.empty() && (rc = identify_search({b}, start, true, st, &checks))) return rc;
     if (per_proof_status) for (uint32_t i = 0; i < n; ++i) per_proof_status[i] = st[0][i];

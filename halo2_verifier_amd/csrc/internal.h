@@ -222,11 +222,11 @@ int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, 
 int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
                         uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups);
 // draws: n_tail 32-byte scalars d_draws -> d_tail, the scalar 1 in place of a draw >= r (k_ingest_draws); the verdict block preset by
-// ingest_rows_enqueue on the same stream takes the lowest index of such a draw and every group's zero_below (upload_impl's rule; groups
-// of n / groups proofs and n_tail / groups draws, or d_group_off[0 .. groups] with n_tail == n), and its first 1 + groups words go to
-// d_host_verdict (mapped host memory) when the last workgroup is done.
-int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, const uint32_t* d_group_off, uint32_t* d_verdict,
-                         uint32_t* d_host_verdict);
+// ingest_rows_enqueue on the same stream takes the lowest index of such a draw and every group's zero_below (GroupShape::zero_below; the
+// n proofs and n_tail draws fit `shape`, batch.h, its offsets in device memory), and its first 1 + shape.G words go to d_host_verdict
+// (mapped host memory) when the last workgroup is done.
+struct GroupShape;
+int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, const GroupShape& shape, uint32_t* d_verdict, uint32_t* d_host_verdict);
 // A finish into device memory (h2v_batch_finish_device): two launches, three with the failing proofs' indices (k_results_tiles,
 // k_results_close, k_results_scatter).  Every output of ResultsOut may be null = not wanted.
 struct ResultsOut {
@@ -241,13 +241,13 @@ struct ResultsOut {
 };
 // the words of d_tile_words: a word per tile of 256 proofs
 inline size_t results_tiles(size_t n) { return (n + 255) / 256; }
-// d_status: the n rank-coded status words; groups of n / groups proofs, or d_group_off[0 .. groups]; d_fold_failed, d_ok (read only
-// with flag bit 0; may be mapped host memory), d_out_bytes: [groups] words, words and 128 bytes of the results block; d_fault: the word
-// the summary reports as the draw fault (null: none; a value other than 0xffffffff rejects every group); flags: summary word 5.
-// Scratch: d_tile_words (results_tiles(n) words, any contents) and d_group_words (`groups` words: ZERO on entry, and zero again when the
+// d_status: the n rank-coded status words of the proofs of `shape` (batch.h; its offsets in device memory); d_fold_failed, d_ok (read
+// only with flag bit 0; may be mapped host memory), d_out_bytes: [shape.G] words, words and 128 bytes of the results block; d_fault: the
+// word the summary reports as the draw fault (null: none; a value other than 0xffffffff rejects every group); flags: summary word 5.
+// Scratch: d_tile_words (results_tiles(n) words, any contents) and d_group_words (shape.G words: ZERO on entry, and zero again when the
 // launches have run).
-int results_enqueue(hipStream_t s, const int* d_status, uint32_t n, uint32_t groups, const uint32_t* d_group_off, const uint32_t* d_fold_failed, const uint32_t* d_ok,
-                    uint32_t flags, const uint8_t* d_out_bytes, const uint32_t* d_fault, uint32_t* d_tile_words, uint32_t* d_group_words, const ResultsOut& out);
+int results_enqueue(hipStream_t s, const int* d_status, uint32_t n, const GroupShape& shape, const uint32_t* d_fold_failed, const uint32_t* d_ok, uint32_t flags,
+                    const uint8_t* d_out_bytes, const uint32_t* d_fault, uint32_t* d_tile_words, uint32_t* d_group_words, const ResultsOut& out);
 // Sharded batches exchange H2V_ACC_RECORD_BYTES records per group: [failed, parts, shift, 0][left pieces][right pieces] (h2v.h).
 // export: d_out[g] <- the group's accumulators — pieces [(2g + side) * parts + j] if d_pieces, else the whole points d_acc[2g], [2g+1] —
 // and the number of non-zero statuses among the group's n / groups proofs

@@ -86,7 +86,7 @@ int enqueue_group(const ScratchBatch& sb, h2v_batch* b, size_t off, size_t m, si
 int collect_group(const ScratchBatch& sb, h2v_batch* b, size_t off, int* st, int* group_ok, uint8_t* out_left = nullptr, uint8_t* out_right = nullptr) {
     if (int rc = h2v_batch_finish_groups(b, st, group_ok, out_left, out_right, b->groups)) return rc;
     for (uint32_t i = 0; i < b->n; ++i)
-        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[group_of(b, i)] = 0; }
+        if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[group_shape(b).of(i)] = 0; }
     return 0;
 }
 
@@ -322,10 +322,11 @@ int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<Cal
     const bool own_draws = groups.size() == 1;
     DevBuf<uint8_t> d_rand; DevBuf<Fr> d_mult, d_tiles; DevBuf<uint32_t> d_idx;
     if (!own_draws) {
-        if ((rc = d_tiles.alloc(multipliers_scratch((uint32_t)n, 1))) || (rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_idx.alloc(n))) return rc;
+        const GroupShape whole{1, (uint32_t)n, (uint32_t)n, nullptr};
+        if ((rc = d_tiles.alloc(multipliers_scratch(whole))) || (rc = d_rand.alloc(32 * n)) || (rc = d_mult.alloc(n)) || (rc = d_idx.alloc(n))) return rc;
         H2V_HIP_CHECK(hipMemcpyAsync(d_rand.p, rand32, 32 * n, hipMemcpyHostToDevice, fold_ctx->stream));
         H2V_HIP_CHECK(hipMemcpyAsync(d_idx.p, idx32.data(), 4 * n, hipMemcpyHostToDevice, fold_ctx->stream));
-        if ((rc = multipliers_enqueue(fold_ctx->stream, d_rand.p, (uint32_t)n, (uint32_t)n, 1, d_mult.p, d_tiles.p))) return rc;
+        if ((rc = multipliers_enqueue(fold_ctx->stream, whole, d_rand.p, nullptr, d_mult.p, d_tiles.p))) return rc;
         H2V_HIP_CHECK(hipStreamSynchronize(fold_ctx->stream));
     }
     // one batch object per key serves every shape group of that key (its buffers grow to the largest group's plan: ensure_buffers)

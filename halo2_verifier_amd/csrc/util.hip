@@ -385,13 +385,13 @@ __global__ void __launch_bounds__(256) k_ingest_rows(const uint4* __restrict__ r
 // k_ingest_draws: one thread per draw of the caller's tail, the checks the host makes for a tail in host memory (upload_impl): two
 // 16-byte loads, Fr::geq_p and a zero test as k_guard_terms reads its scalars.  The draw goes into the batch's tail, or the scalar 1
 // in place of a draw >= r, whose index joins verdict[0] by atomicMin (a stored zero would zero the multipliers of the earlier proofs
-// and drop them out of the accumulators).  A zero draw at index j >= 1 of its group's draws raises zero_below[g] = verdict[1 + g] by
-// atomicMax: to j for unequal groups (g found in off[0 .. G], one draw per proof), to min(j, gs) for equal groups of gs proofs and nt
-// draws each (nt > gs: a shard's tail) — the two branches of upload_impl's rule.  The workgroup that finishes last (a count of the
-// workgroups done, behind a device-wide fence) sends the 1 + G verdict words to host_verdict, so the verdict needs no third launch.
-// gfx950 (tools/kernel_resources.py): 22 VGPRs, 46 SGPRs, no spills, no scratch, 4 bytes of LDS; 8 waves per SIMD.
-__global__ void __launch_bounds__(256) k_ingest_draws(const uint4* __restrict__ draws, uint4* __restrict__ tail, uint32_t n_tail, uint32_t nt, uint32_t gs,
-                                                      const uint32_t* __restrict__ off, uint32_t G, uint32_t* __restrict__ verdict, uint32_t* __restrict__ host_verdict) {
+// and drop them out of the accumulators).  A zero draw, the j-th of group g's draws (GroupShape::draw_at), raises zero_below[g] =
+// verdict[1 + g] by atomicMax to GroupShape::zero_below(j, g): the loop of zero_below_of_draws (batch.hip), a thread per draw.  The
+// workgroup that finishes last (a count of the workgroups done, behind a device-wide fence) sends the 1 + G verdict words to
+// host_verdict, so the verdict needs no third launch.
+// gfx950 (tools/kernel_resources.py): 22 VGPRs, 48 SGPRs, no spills, no scratch, 4 bytes of LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_ingest_draws(const uint4* __restrict__ draws, uint4* __restrict__ tail, uint32_t n_tail, GroupShape shape,
+                                                      uint32_t* __restrict__ verdict, uint32_t* __restrict__ host_verdict) {
     __shared__ uint32_t last;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_tail) {
@@ -403,21 +403,16 @@ __global__ void __launch_bounds__(256) k_ingest_draws(const uint4* __restrict__ 
             tail[2 * (size_t)i] = make_uint4(1, 0, 0, 0); tail[2 * (size_t)i + 1] = make_uint4(0, 0, 0, 0);
         } else { tail[2 * (size_t)i] = s0; tail[2 * (size_t)i + 1] = s1; }
         if (zero) {
-            uint32_t g, below;
-            if (off) {
-                uint32_t lo = 0, hi = G;   // the last g with off[g] <= i (off[0] = 0, off[G] = n_tail > i)
-                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-                g = lo; below = i - off[g];
-            } else { g = i / nt; const uint32_t j = i - g * nt; below = j ? (j < gs ? j : gs) : 0; }
-            if (below) atomicMax(&verdict[1 + g], below);
+            const GroupShape::Draw d = shape.draw_at(i);
+            if (const uint32_t below = shape.zero_below(d.j, d.g)) atomicMax(&verdict[1 + d.g], below);
         }
     }
     __threadfence();
     __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(&verdict[1 + G], 1u) == gridDim.x - 1 ? 1u : 0u;
+    if (threadIdx.x == 0) last = atomicAdd(&verdict[1 + shape.G], 1u) == gridDim.x - 1 ? 1u : 0u;
     __syncthreads();
     if (!last) return;
-    for (uint32_t t = threadIdx.x; t < 1 + G; t += 256) host_verdict[t] = __hip_atomic_load(&verdict[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t t = threadIdx.x; t < 1 + shape.G; t += 256) host_verdict[t] = __hip_atomic_load(&verdict[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
                         uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups) {
@@ -435,14 +430,12 @@ int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, const uint32_t* d_group_off, uint32_t* d_verdict,
-                         uint32_t* d_host_verdict) {
-    if (!groups || !d_verdict || !d_host_verdict || (n_tail && (!d_draws || !d_tail))) { set_last_error("ingest_draws_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, uint32_t n_tail, uint32_t n, const GroupShape& shape, uint32_t* d_verdict, uint32_t* d_host_verdict) {
+    if (!shape.G || !d_verdict || !d_host_verdict || (n_tail && (!d_draws || !d_tail))) { set_last_error("ingest_draws_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (((uintptr_t)d_draws | (uintptr_t)d_tail) & 15u) { set_last_error("ingest_draws_enqueue: an array off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
-    if (d_group_off ? n_tail != n : (n % groups || n_tail % groups || n_tail < n)) { set_last_error("ingest_draws_enqueue: the draws do not match the groups"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!shape.fits(n, n_tail, true)) { set_last_error("ingest_draws_enqueue: the draws do not match the groups"); return H2V_ERR_BAD_ARGUMENT; }
     // (no draw: one workgroup still sends the preset verdict)
-    hipLaunchKernelGGL(k_ingest_draws, dim3(n_tail ? (n_tail + 255) / 256 : 1), dim3(256), 0, s, (const uint4*)d_draws, (uint4*)d_tail, n_tail, n_tail / groups, n / groups,
-                       d_group_off, groups, d_verdict, d_host_verdict);
+    hipLaunchKernelGGL(k_ingest_draws, dim3(n_tail ? (n_tail + 255) / 256 : 1), dim3(256), 0, s, (const uint4*)d_draws, (uint4*)d_tail, n_tail, shape, d_verdict, d_host_verdict);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -455,26 +448,19 @@ int ingest_draws_enqueue(hipStream_t s, const void* d_draws, uint8_t* d_tail, ui
 // stored, 4 bytes per lane, consecutive lanes to consecutive words.  A wave's failing lanes (status != 0) are one 64-bit ballot: its
 // popcount goes into the tile's count through LDS, and into the groups' words by one atomicAdd per group present among them — the lanes of
 // the lowest failing lane's group are peeled off the ballot until it is empty, so a wave without a failing proof (every wave of a clean
-// launch) does no lookup and no atomic.  Only failing lanes find their group: a division for equal groups, k_ingest_draws' search of
-// off[0 .. G] otherwise.  The sums do not depend on the order of the additions.
-// gfx950 (tools/kernel_resources.py): 10 VGPRs, 28 SGPRs, no spills, no scratch, 16 bytes of LDS; 8 waves per SIMD.
+// launch) does no lookup and no atomic.  Only failing lanes find their group (GroupShape::of).  The sums do not depend on the order of
+// the additions.
+// gfx950 (tools/kernel_resources.py): 10 VGPRs, 26 SGPRs, no spills, no scratch, 16 bytes of LDS; 8 waves per SIMD.
 #define RESULTS_TILE 256u
-__global__ void __launch_bounds__(RESULTS_TILE) k_results_tiles(const int* __restrict__ status, uint32_t n, uint32_t gs, const uint32_t* __restrict__ off, uint32_t G,
-                                                                int* __restrict__ out_status, uint32_t* __restrict__ tile_count, uint32_t* __restrict__ group_failed) {
+__global__ void __launch_bounds__(RESULTS_TILE) k_results_tiles(const int* __restrict__ status, uint32_t n, GroupShape shape, int* __restrict__ out_status,
+                                                                uint32_t* __restrict__ tile_count, uint32_t* __restrict__ group_failed) {
     __shared__ uint32_t wave_count[RESULTS_TILE / 64];
     const uint32_t t = threadIdx.x, lane = t & 63u, i = blockIdx.x * RESULTS_TILE + t;
     const int w = i < n ? status[i] : 0;
     if (i < n && out_status) out_status[i] = status_decode(w);
     unsigned long long failing = __ballot(w != 0);
     if (lane == 0) wave_count[t >> 6] = (uint32_t)__popcll(failing);
-    uint32_t g = 0;
-    if (w != 0) {
-        if (off) {
-            uint32_t lo = 0, hi = G;   // the last g with off[g] <= i (off[0] = 0, off[G] = n > i)
-            while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-            g = lo;
-        } else g = i / gs;
-    }
+    const uint32_t g = w != 0 ? shape.of(i) : 0;
     while (failing) {   // (the same value in every lane of the wave)
         const uint32_t leader = (uint32_t)__ffsll((long long)failing) - 1;
         const uint32_t gl = (uint32_t)__shfl((int)g, (int)leader);
@@ -556,21 +542,22 @@ __global__ void __launch_bounds__(RESULTS_TILE) k_results_scatter(const int* __r
     for (uint32_t k = 0; k < wave; ++k) pos += wave_count[k];
     if (pos < cap) failed_index[pos] = i;
 }
-int results_enqueue(hipStream_t s, const int* d_status, uint32_t n, uint32_t groups, const uint32_t* d_group_off, const uint32_t* d_fold_failed, const uint32_t* d_ok,
-                    uint32_t flags, const uint8_t* d_out_bytes, const uint32_t* d_fault, uint32_t* d_tile_words, uint32_t* d_group_words, const ResultsOut& out) {
+int results_enqueue(hipStream_t s, const int* d_status, uint32_t n, const GroupShape& shape, const uint32_t* d_fold_failed, const uint32_t* d_ok, uint32_t flags,
+                    const uint8_t* d_out_bytes, const uint32_t* d_fault, uint32_t* d_tile_words, uint32_t* d_group_words, const ResultsOut& out) {
+    const uint32_t groups = shape.G;
     if (!groups || !d_fold_failed || !d_out_bytes || !d_group_words || (n && (!d_status || !d_tile_words)) || ((flags & 1u) && !d_ok)) { set_last_error("results_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (((uintptr_t)d_out_bytes | (uintptr_t)out.left_xy | (uintptr_t)out.right_xy) & 15u) { set_last_error("results_enqueue: accumulator bytes off a 16-byte boundary"); return H2V_ERR_BAD_ARGUMENT; }
     if (((uintptr_t)d_status | (uintptr_t)out.status | (uintptr_t)out.group_ok | (uintptr_t)out.group_failed | (uintptr_t)out.failed_index | (uintptr_t)out.summary) & 3u) {
         set_last_error("results_enqueue: a word array off a 4-byte boundary"); return H2V_ERR_BAD_ARGUMENT;
     }
-    if (!d_group_off && n % groups) { set_last_error("results_enqueue: equal groups do not divide n"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!shape.fits(n, n, false)) { set_last_error("results_enqueue: equal groups do not divide n"); return H2V_ERR_BAD_ARGUMENT; }
     if (groups > (1u << 24) || (flags & ~3u)) { set_last_error("results_enqueue: too many groups, or an unknown flag"); return H2V_ERR_BAD_ARGUMENT; }
     if (out.failed_index && !out.failed_cap) { set_last_error("results_enqueue: failed_cap is 0"); return H2V_ERR_BAD_ARGUMENT; }
     const uint32_t tiles = (uint32_t)(((uint64_t)n + RESULTS_TILE - 1) / RESULTS_TILE);
     uint32_t* const tile_words = d_tile_words;
     uint32_t* const group_words = d_group_words;
     if (tiles) {
-        hipLaunchKernelGGL(k_results_tiles, dim3(tiles), dim3(RESULTS_TILE), 0, s, d_status, n, n / groups, d_group_off, groups, out.status, tile_words, group_words);
+        hipLaunchKernelGGL(k_results_tiles, dim3(tiles), dim3(RESULTS_TILE), 0, s, d_status, n, shape, out.status, tile_words, group_words);
         H2V_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_results_close, dim3(1), dim3(256), 0, s, tile_words, tiles, group_words, groups, n, d_fold_failed, d_ok, flags, (const uint4*)d_out_bytes, d_fault,

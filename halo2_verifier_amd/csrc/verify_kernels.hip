@@ -5,12 +5,10 @@
 //   k_check_scalars   one lane per (proof, scalar)  Fr::from_repr canonicity           transcript/mod.rs:168-176
 //   k_stream_build    one lane per (proof, 8-byte word of the absorbed stream)         transcript/mod.rs:216-231
 //   k_transcript      four lanes per proof          Blake2b-512 + challenges           transcript/mod.rs:124-133,209-214,500-514
-//   k_mult_tiles ...  a two-level scan              suffix products of the batch draws kzg/strategy.rs:129, msm.rs:173-176
 //   k_instance_eval   one workgroup per proof       Lagrange sum over a wide instance column   lib.rs:173-218, poly/domain.rs:187-212
 //   k_frvm            one lane per proof            the compiled Fr program            lib.rs:173-346, shplonk.rs:202-264
-//   k_fold_shared     one workgroup per shared base sum over proofs of the scalars of VK-wide bases
-//   k_seg_mult_tiles ...  a segmented two-level scan  the same for groups of unequal size (h2v_batch_set_group_sizes)
-//   k_fold_shared_offsets one workgroup per (shared base, group)  k_fold_shared over groups given by offsets
+//   k_seg_mult_tiles ...  a segmented two-level scan  suffix products of the batch draws, group by group   kzg/strategy.rs:129, msm.rs:173-176
+//   k_fold_shared     one workgroup per (shared base, group)   sum over the group's proofs of the scalars of VK-wide bases
 //   k_fold_ranges     one wave per (shared base, range)   the same over arbitrary ranges of proofs, of one batch or several (h2v_batches_recheck)
 //
 // Layouts are chosen so that lanes (= proofs) are contiguous in the fastest dimension for
@@ -439,15 +437,21 @@ __global__ void __launch_bounds__(64) k_transcript_keccak(const unsigned long lo
     }
 }
 
-// mult[p] = prod_{j > first+p} r_j over the tail of draws; tail[0] is the draw of this shard's proof 0.  Per group of a grouped batch
-// (blockIdx.y = group; n_tail and n are per group), as a two-level suffix scan over tiles of MULT_TILE draws:
-//   k_mult_tiles       a workgroup per tile: mult[j] <- the product of the LATER draws of j's own tile, tile_prod[tile] <- the tile's product
-//   k_mult_scan_tiles  a workgroup per group: tile_prod[tile] <- the product of all LATER tiles (chunks of 1024 tiles, last chunk first)
-//   k_mult_apply       mult[j] <- mult[j] * tile_prod[j's tile]
+// The batch multipliers: mult[p] = the product of the draws BEHIND proof p's own inside p's group (kzg/strategy.rs:129, msm.rs:173-176),
+// for the groups of a GroupShape, equal or not, as ONE segmented suffix scan over the whole draw array in tiles of MULT_TILE draws —
+// work proportional to the draws whatever the groups' sizes.  A group is the segment of its draws: it ends at the draw whose byte in
+// last[] is not zero (unequal groups: one draw per proof) or, by arithmetic, at the nt-th draw of an equal group, whose draws past its
+// gs proofs (a shard's tail) count in the products and have no multiplier of their own.  The scan carries a pair (v, closed) per span
+// [i, k] of draws: v = the product of the draws from i to the end of i's group or k, whichever comes first; closed = i's group ends
+// inside the span.  (a, b) of two adjacent spans combine to a if a is closed, else (a.v b.v, b.closed).
+//   k_seg_mult_tiles       a workgroup per tile: mult[j] <- the later draws of j's group inside the tile; the tile's pair;
+//                          open_from[tile] <- the first thread whose group goes on behind the tile (the closed spans are a prefix of the tile)
+//   k_seg_mult_scan_tiles  one workgroup: tile_prod[tile] <- what the later tiles give a group that is still open at the tile's end
+//   k_seg_mult_apply       mult[j] <- mult[j] * tile_prod[j's tile] for the threads from open_from[tile] on
 // (One 1024-thread workgroup per group walked its draws in 1024 serial chunks: 210 us for a 20-step launch.  The multipliers depend on
 // the uploaded draws alone, so they are computed once per upload, not per launch: upload_impl.)
 #define MULT_TILE 256u
-// part[t] <- prod_{t' >= t} part[t'] over the workgroup's T values (T a power of two); every thread calls it
+// part[t] <- prod_{t' >= t} part[t'] over the workgroup's T values (T a power of two); every thread calls it (k_leg_weights)
 template <uint32_t T> __device__ __forceinline__ void fr_suffix_scan(Fr* part, uint32_t t) {
     __syncthreads();
     for (uint32_t d = 1; d < T; d <<= 1) {
@@ -457,46 +461,6 @@ template <uint32_t T> __device__ __forceinline__ void fr_suffix_scan(Fr* part, u
         __syncthreads();
     }
 }
-__global__ void __launch_bounds__(MULT_TILE) k_mult_tiles(const uint8_t* __restrict__ tail, uint32_t n_tail, uint32_t n, uint32_t tiles, Fr* __restrict__ mult, Fr* __restrict__ tile_prod) {
-    __shared__ Fr part[MULT_TILE];
-    const uint32_t t = threadIdx.x, g = blockIdx.y, j = blockIdx.x * MULT_TILE + t;
-    Fr r = Fr::one();
-    if (j < n_tail) Fr::from_bytes(tail + 32 * ((size_t)g * n_tail + j), r);
-    part[t] = r;
-    fr_suffix_scan<MULT_TILE>(part, t);
-    if (j < n) mult[(size_t)g * n + j] = t + 1 < MULT_TILE ? part[t + 1] : Fr::one();
-    if (t == 0) tile_prod[(size_t)g * tiles + blockIdx.x] = part[0];
-}
-__global__ void __launch_bounds__(1024) k_mult_scan_tiles(Fr* __restrict__ tile_prod, uint32_t tiles) {
-    __shared__ Fr part[1024];
-    const uint32_t t = threadIdx.x;
-    tile_prod += (size_t)blockIdx.x * tiles;
-    Fr carry = Fr::one();   // the product of every tile behind the chunk
-    for (uint32_t hi = tiles; hi > 0; hi = hi > 1024 ? hi - 1024 : 0) {
-        const uint32_t lo = hi > 1024 ? hi - 1024 : 0, i = lo + t;
-        part[t] = i < hi ? tile_prod[i] : Fr::one();
-        fr_suffix_scan<1024>(part, t);
-        const Fr later = (t + 1 < 1024 ? part[t + 1] : Fr::one()) * carry;
-        const Fr all = part[0] * carry;
-        __syncthreads();   // (part is written again in the next round)
-        if (i < hi) tile_prod[i] = later;
-        carry = all;
-    }
-}
-__global__ void __launch_bounds__(MULT_TILE) k_mult_apply(Fr* __restrict__ mult, uint32_t n, uint32_t tiles, const Fr* __restrict__ tile_prod) {
-    const uint32_t g = blockIdx.y, j = blockIdx.x * MULT_TILE + threadIdx.x;
-    if (j < n && blockIdx.x + 1 < tiles) mult[(size_t)g * n + j] = mult[(size_t)g * n + j] * tile_prod[(size_t)g * tiles + blockIdx.x];
-}
-
-// The same multipliers for groups of UNEQUAL size (h2v_batch_set_group_sizes): mult[j] = the product of the later draws of j's own
-// group, as a SEGMENTED suffix scan over the whole draw array — work proportional to n whatever the sizes, where a grid of (tiles of
-// the largest group, groups) would launch mostly workgroups that leave at once.  last[j] != 0 marks the last proof of a group.  The
-// scan carries a pair (v, closed) per span [i, k] of draws: v = the product of the draws from i to the end of i's group or k, whichever
-// comes first; closed = i's group ends inside the span.  (a, b) of two adjacent spans combine to a if a is closed, else (a.v b.v, b.closed).
-//   k_seg_mult_tiles       a workgroup per tile of MULT_TILE draws: mult[j] <- the later draws of j's group inside the tile; the tile's pair;
-//                          open_from[tile] <- the first thread whose group goes on behind the tile (the closed spans are a prefix of the tile)
-//   k_seg_mult_scan_tiles  one workgroup: tile_prod[tile] <- what the later tiles give a group that is still open at the tile's end
-//   k_seg_mult_apply       mult[j] <- mult[j] * tile_prod[j's tile] for the threads from open_from[tile] on
 // part[t] <- the pair of the span [t, T); every thread calls it (fr_suffix_scan's barriers)
 template <uint32_t T> __device__ __forceinline__ void fr_seg_suffix_scan(Fr* part, uint32_t* closed, uint32_t t) {
     __syncthreads();
@@ -509,17 +473,25 @@ template <uint32_t T> __device__ __forceinline__ void fr_seg_suffix_scan(Fr* par
         __syncthreads();
     }
 }
-__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_tiles(const uint8_t* __restrict__ tail, const uint8_t* __restrict__ last, uint32_t n, Fr* __restrict__ mult,
-                                                              Fr* __restrict__ tile_prod, uint32_t* __restrict__ tile_closed, uint32_t* __restrict__ open_from) {
+// draw j of the array: where its proof keeps its multiplier (NO_MULT: a draw without a proof), and whether it is the last of its group
+#define NO_MULT 0xffffffffu
+struct SegDraw { uint32_t slot; bool end; };
+__device__ __forceinline__ SegDraw seg_draw(const GroupShape& shape, const uint8_t* __restrict__ last, uint32_t j) {
+    if (shape.off) return SegDraw{j, last[j] != 0};
+    const GroupShape::Draw d = shape.draw_at(j);
+    return SegDraw{d.j < shape.gs ? shape.first(d.g) + d.j : NO_MULT, d.j + 1 == shape.nt};
+}
+__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_tiles(const uint8_t* __restrict__ tail, const uint8_t* __restrict__ last, GroupShape shape, uint32_t n_draws,
+                                                              Fr* __restrict__ mult, Fr* __restrict__ tile_prod, uint32_t* __restrict__ tile_closed, uint32_t* __restrict__ open_from) {
     __shared__ Fr part[MULT_TILE];
     __shared__ uint32_t closed[MULT_TILE];
     const uint32_t t = threadIdx.x, j = blockIdx.x * MULT_TILE + t;
     Fr r = Fr::one();
-    uint32_t end = 1;   // (past the draws: one-element groups of their own, behind the last group's end)
-    if (j < n) { Fr::from_bytes(tail + 32 * (size_t)j, r); end = last[j] ? 1u : 0u; }
-    part[t] = r; closed[t] = end;
+    SegDraw d{NO_MULT, true};   // (past the draws: one-element groups of their own, behind the last group's end)
+    if (j < n_draws) { Fr::from_bytes(tail + 32 * (size_t)j, r); d = seg_draw(shape, last, j); }
+    part[t] = r; closed[t] = d.end ? 1u : 0u;
     fr_seg_suffix_scan<MULT_TILE>(part, closed, t);
-    if (j < n) mult[j] = (end || t + 1 == MULT_TILE) ? Fr::one() : part[t + 1];
+    if (d.slot != NO_MULT) mult[d.slot] = (d.end || t + 1 == MULT_TILE) ? Fr::one() : part[t + 1];
     if (!closed[t] && (t == 0 || closed[t - 1])) open_from[blockIdx.x] = t;
     if (t + 1 == MULT_TILE && closed[t]) open_from[blockIdx.x] = MULT_TILE;
     if (t == 0) { tile_prod[blockIdx.x] = part[0]; tile_closed[blockIdx.x] = closed[0]; }
@@ -543,14 +515,17 @@ __global__ void __launch_bounds__(1024) k_seg_mult_scan_tiles(Fr* __restrict__ t
         carry = all;
     }
 }
-__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_apply(Fr* __restrict__ mult, uint32_t n, const Fr* __restrict__ tile_prod, const uint32_t* __restrict__ open_from) {
+__global__ void __launch_bounds__(MULT_TILE) k_seg_mult_apply(Fr* __restrict__ mult, const uint8_t* __restrict__ last, GroupShape shape, uint32_t n_draws,
+                                                              const Fr* __restrict__ tile_prod, const uint32_t* __restrict__ open_from) {
     const uint32_t j = blockIdx.x * MULT_TILE + threadIdx.x;
-    if (j < n && threadIdx.x >= open_from[blockIdx.x]) mult[j] = mult[j] * tile_prod[blockIdx.x];
+    if (j >= n_draws || threadIdx.x < open_from[blockIdx.x]) return;
+    const uint32_t slot = seg_draw(shape, last, j).slot;
+    if (slot != NO_MULT) mult[slot] = mult[slot] * tile_prod[blockIdx.x];
 }
 
 // The weights of a finished batch's groups fed to a resident accumulator as G legs (h2v_accumulator_process_batch, accumulator.hip).
 // Group g's M_g, the product of its draws, is its first draw times the multiplier of its first proof (the product of the later draws
-// of the group, what the upload left in mult); first_g = off[g], or g * gs for equal groups (off null).  One workgroup of LEG_WEIGHTS_MAX
+// of the group, what the upload left in mult); first_g = GroupShape::first(g).  One workgroup of LEG_WEIGHTS_MAX
 // threads, thread g its group (the threads past G hold 1), one suffix scan in LDS (18 KB), then as canonical 8-word scalars
 //   weights[0] = prod_g M_g,  weights[1 + g] = W_g = prod_{f > g} M_f   (the items of the k_accumulator_scale launch that follows)
 //   legs[g] = M_g                                                       (for the host's journal)
@@ -561,13 +536,13 @@ __device__ __forceinline__ void fr_store_canonical(uint32_t* out, const Fr& v) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) out[j] = raw[j];
 }
-__global__ void __launch_bounds__(LEG_WEIGHTS_MAX) k_leg_weights(const uint8_t* __restrict__ tail, const Fr* __restrict__ mult, const uint32_t* __restrict__ off, uint32_t gs,
-                                                                 uint32_t G, uint32_t* __restrict__ weights, uint32_t* __restrict__ legs) {
+__global__ void __launch_bounds__(LEG_WEIGHTS_MAX) k_leg_weights(const uint8_t* __restrict__ tail, const Fr* __restrict__ mult, GroupShape shape,
+                                                                 uint32_t* __restrict__ weights, uint32_t* __restrict__ legs) {
     __shared__ Fr part[LEG_WEIGHTS_MAX];
-    const uint32_t t = threadIdx.x;
+    const uint32_t t = threadIdx.x, G = shape.G;
     Fr m = Fr::one();
     if (t < G) {
-        const size_t first = off ? off[t] : (size_t)t * gs;
+        const size_t first = shape.first(t);
         Fr r;
         Fr::from_bytes(tail + 32 * first, r);
         m = r * mult[first];
@@ -777,69 +752,43 @@ __global__ void __launch_bounds__(64 * FRVM_MAX_STREAMS) k_frvm2(FrvmArgs a, uin
     frvm_run<true>(a, a.code_k[k][w], a.n_code_k[k][w], sf, p, live);
 }
 
-// msm_scal[n*np + g*n_shared + j] = canonical( sum over the proofs p of group g of shared[j][p] )
-__global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ shared, uint32_t n, uint32_t np, uint32_t gs, uint32_t* __restrict__ msm_scal) {
-    __shared__ Fr red[256];
-    uint32_t j = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
+// dst[0 .. 8) = canonical( sum over the proofs p of [p0, p1) of col[p] ) by the workgroup's T threads (T a power of two; every thread
+// calls it): a strided sum per thread, a tree in LDS
+template <uint32_t T> __device__ __forceinline__ void fold_column(const Fr* __restrict__ col, uint32_t p0, uint32_t p1, uint32_t* __restrict__ dst) {
+    __shared__ Fr red[T];
+    const uint32_t t = threadIdx.x;
     Fr acc = Fr::zero();
-    for (uint32_t p = g * gs + t; p < (g + 1) * gs; p += 256) acc = acc + shared[(size_t)j * n + p];
+    for (uint32_t p = p0 + t; p < p1; p += T) acc = acc + col[p];
     red[t] = acc;
     __syncthreads();
-    for (uint32_t d = 128; d > 0; d >>= 1) {
+    for (uint32_t d = T / 2; d > 0; d >>= 1) {
         if (t < d) red[t] = red[t] + red[t + d];
         __syncthreads();
     }
     if (t == 0) {
         uint32_t raw[8]; red[0].to_raw(raw);
-        uint32_t* dst = msm_scal + ((size_t)n * np + (size_t)g * gridDim.x + j) * 8;
         for (int i = 0; i < 8; ++i) dst[i] = raw[i];
     }
 }
-
-// the same for groups of unequal size: group g owns the proofs [off[g], off[g + 1])
-__global__ void __launch_bounds__(256) k_fold_shared_offsets(const Fr* __restrict__ shared, uint32_t n, uint32_t np, const uint32_t* __restrict__ off, uint32_t* __restrict__ msm_scal) {
-    __shared__ Fr red[256];
-    const uint32_t j = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
-    const uint32_t p0 = off[g], p1 = off[g + 1];   // (validated on the host: p0 < p1 <= n)
-    Fr acc = Fr::zero();
-    for (uint32_t p = p0 + t; p < p1; p += 256) acc = acc + shared[(size_t)j * n + p];
-    red[t] = acc;
-    __syncthreads();
-    for (uint32_t d = 128; d > 0; d >>= 1) {
-        if (t < d) red[t] = red[t] + red[t + d];
-        __syncthreads();
-    }
-    if (t == 0) {
-        uint32_t raw[8]; red[0].to_raw(raw);
-        uint32_t* dst = msm_scal + ((size_t)n * np + (size_t)g * gridDim.x + j) * 8;
-        for (int i = 0; i < 8; ++i) dst[i] = raw[i];
-    }
+// msm_scal[n*np + g*n_shared + j] = canonical( sum over the proofs p of group g of shared[j][p] ): a workgroup per (shared base, group)
+// (the offsets of unequal groups are validated on the host: first(g) + count(g) <= n)
+// gfx950 (tools/kernel_resources.py), with equal and with unequal groups as the two kernels it replaces: 32 VGPRs, 39 SGPRs, no spills,
+// 48 bytes of scratch, 9216 bytes of LDS; 8 waves per SIMD.
+__global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ shared, uint32_t n, uint32_t np, GroupShape shape, uint32_t* __restrict__ msm_scal) {
+    const uint32_t j = blockIdx.x, g = blockIdx.y, p0 = shape.first(g);
+    fold_column<256>(shared + (size_t)j * n, p0, p0 + shape.count(g), msm_scal + ((size_t)n * np + (size_t)g * gridDim.x + j) * 8);
 }
 
 // out[(ranges[r].out + j) * 8] = canonical( sum over the proofs p of range r of ranges[r].shared[j][p] ).  The ranges of a re-check
 // are mostly short (a search ends on single proofs): one wave per (base, range), a wave-wide tree in LDS.  The ranges of one launch
 // may belong to batches of different keys (h2v_batches_recheck): the grid is as wide as the most VK-wide bases of any of them, and the
 // blocks past a range's own n_shared leave at once (the whole block: the exit is uniform, before the first barrier)
+// gfx950 (tools/kernel_resources.py): 32 VGPRs, 39 SGPRs, no spills, 48 bytes of scratch, 2304 bytes of LDS; 8 waves per SIMD.
 __global__ void __launch_bounds__(64) k_fold_ranges(const FoldRange* __restrict__ ranges, uint32_t* __restrict__ out) {
-    __shared__ Fr red[64];
-    const uint32_t j = blockIdx.x, t = threadIdx.x;
+    const uint32_t j = blockIdx.x;
     const FoldRange rg = ranges[blockIdx.y];
     if (j >= rg.n_shared) return;
-    const Fr* col = rg.shared + (size_t)j * rg.n;
-    const uint32_t end = rg.first + rg.count;   // (validated on the host: end <= n)
-    Fr acc = Fr::zero();
-    for (uint32_t p = rg.first + t; p < end; p += 64) acc = acc + col[p];
-    red[t] = acc;
-    __syncthreads();
-    for (uint32_t d = 32; d > 0; d >>= 1) {
-        if (t < d) red[t] = red[t] + red[t + d];
-        __syncthreads();
-    }
-    if (t == 0) {
-        uint32_t raw[8]; red[0].to_raw(raw);
-        uint32_t* dst = out + ((size_t)rg.out + j) * 8;
-        for (int i = 0; i < 8; ++i) dst[i] = raw[i];
-    }
+    fold_column<64>(rg.shared + (size_t)j * rg.n, rg.first, rg.first + rg.count, out + ((size_t)rg.out + j) * 8);   // (validated on the host: first + count <= n)
 }
 
 // ------------------------------------------------------------------ launchers
@@ -894,36 +843,30 @@ int expand_draws_enqueue(hipStream_t s, const uint8_t seed32[32], uint64_t first
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-size_t multipliers_scratch(uint32_t n_tail, uint32_t groups) { return (size_t)groups * ((n_tail / groups + MULT_TILE - 1) / MULT_TILE); }
-int multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, uint32_t n_tail, uint32_t n, uint32_t groups, Fr* d_mult, Fr* d_scratch) {
-    const uint32_t nt = n_tail / groups, ng = n / groups, tiles = (nt + MULT_TILE - 1) / MULT_TILE;
-    if (!tiles || !ng) return 0;
-    if (tiles > 65535u * 1024u || groups > 65535u) { set_last_error("multipliers: too many draws or groups"); return H2V_ERR_BAD_ARGUMENT; }
-    hipLaunchKernelGGL(k_mult_tiles, dim3(tiles, groups), dim3(MULT_TILE), 0, s, d_tail, nt, ng, tiles, d_mult, d_scratch);
+// The scratch of the multipliers, in elements: a product per tile of the draw array and, behind the products, two words per tile
+// (closed, open_from)
+static uint32_t mult_tiles_of(const GroupShape& shape) { return (uint32_t)(((uint64_t)(shape.off ? 1u : shape.G) * shape.nt + MULT_TILE - 1) / MULT_TILE); }
+size_t multipliers_scratch(const GroupShape& shape) {
+    const size_t tiles = mult_tiles_of(shape);
+    return tiles + (2 * tiles * sizeof(uint32_t) + sizeof(Fr) - 1) / sizeof(Fr);
+}
+int multipliers_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const uint8_t* d_last, Fr* d_mult, Fr* d_scratch) {
+    const uint32_t tiles = mult_tiles_of(shape), n_draws = (shape.off ? 1u : shape.G) * shape.nt;
+    if (!tiles || !shape.gs) return 0;
+    if (shape.off && !d_last) { set_last_error("multipliers: groups of unequal size without their last-of-group marks"); return H2V_ERR_BAD_ARGUMENT; }
+    uint32_t* tile_closed = reinterpret_cast<uint32_t*>(d_scratch + tiles); uint32_t* open_from = tile_closed + tiles;
+    hipLaunchKernelGGL(k_seg_mult_tiles, dim3(tiles), dim3(MULT_TILE), 0, s, d_tail, d_last, shape, n_draws, d_mult, d_scratch, tile_closed, open_from);
     if (tiles > 1) {
-        hipLaunchKernelGGL(k_mult_scan_tiles, dim3(groups), dim3(1024), 0, s, d_scratch, tiles);
-        hipLaunchKernelGGL(k_mult_apply, dim3((ng + MULT_TILE - 1) / MULT_TILE, groups), dim3(MULT_TILE), 0, s, d_mult, ng, tiles, (const Fr*)d_scratch);
+        hipLaunchKernelGGL(k_seg_mult_scan_tiles, dim3(1), dim3(1024), 0, s, d_scratch, (const uint32_t*)tile_closed, tiles);
+        hipLaunchKernelGGL(k_seg_mult_apply, dim3(tiles), dim3(MULT_TILE), 0, s, d_mult, d_last, shape, n_draws, (const Fr*)d_scratch, (const uint32_t*)open_from);
     }
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-size_t ragged_multipliers_tiles(uint32_t n) { return ((size_t)n + MULT_TILE - 1) / MULT_TILE; }
-int ragged_multipliers_enqueue(hipStream_t s, const uint8_t* d_tail, const uint8_t* d_last, uint32_t n, Fr* d_mult, Fr* d_tile_prod, uint32_t* d_tile_words) {
-    const uint32_t tiles = (uint32_t)ragged_multipliers_tiles(n);
-    if (!tiles) return 0;
-    uint32_t* tile_closed = d_tile_words; uint32_t* open_from = d_tile_words + tiles;
-    hipLaunchKernelGGL(k_seg_mult_tiles, dim3(tiles), dim3(MULT_TILE), 0, s, d_tail, d_last, n, d_mult, d_tile_prod, tile_closed, open_from);
-    if (tiles > 1) {
-        hipLaunchKernelGGL(k_seg_mult_scan_tiles, dim3(1), dim3(1024), 0, s, d_tile_prod, (const uint32_t*)tile_closed, tiles);
-        hipLaunchKernelGGL(k_seg_mult_apply, dim3(tiles), dim3(MULT_TILE), 0, s, d_mult, n, (const Fr*)d_tile_prod, (const uint32_t*)open_from);
-    }
-    H2V_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-int leg_weights_enqueue(hipStream_t s, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_off, uint32_t gs, uint32_t groups, uint32_t* d_weights, uint32_t* d_legs) {
-    if (!groups || groups > LEG_WEIGHTS_MAX) { set_last_error("leg_weights_enqueue: the group count is not in 1 .. 512"); return H2V_ERR_BAD_ARGUMENT; }
+int leg_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const Fr* d_mult, uint32_t* d_weights, uint32_t* d_legs) {
+    if (!shape.G || shape.G > LEG_WEIGHTS_MAX) { set_last_error("leg_weights_enqueue: the group count is not in 1 .. 512"); return H2V_ERR_BAD_ARGUMENT; }
     if (!d_tail || !d_mult || !d_weights || !d_legs) { set_last_error("leg_weights_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    hipLaunchKernelGGL(k_leg_weights, dim3(1), dim3(LEG_WEIGHTS_MAX), 0, s, d_tail, d_mult, d_off, gs, groups, d_weights, d_legs);
+    hipLaunchKernelGGL(k_leg_weights, dim3(1), dim3(LEG_WEIGHTS_MAX), 0, s, d_tail, d_mult, shape, d_weights, d_legs);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -974,15 +917,9 @@ int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots) {
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int fold_shared_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, uint32_t* d_msm_scal) {
-    if (!n_shared) return 0;
-    hipLaunchKernelGGL(k_fold_shared, dim3(n_shared, groups), dim3(256), 0, s, d_shared, n, np, n / groups, d_msm_scal);
-    H2V_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-int fold_shared_offsets_enqueue(hipStream_t s, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t groups, const uint32_t* d_off, uint32_t* d_msm_scal) {
-    if (!n_shared || !groups) return 0;
-    hipLaunchKernelGGL(k_fold_shared_offsets, dim3(n_shared, groups), dim3(256), 0, s, d_shared, n, np, d_off, d_msm_scal);
+int fold_shared_enqueue(hipStream_t s, const GroupShape& shape, const Fr* d_shared, uint32_t n, uint32_t np, uint32_t n_shared, uint32_t* d_msm_scal) {
+    if (!n_shared || !shape.G) return 0;
+    hipLaunchKernelGGL(k_fold_shared, dim3(n_shared, shape.G), dim3(256), 0, s, d_shared, n, np, shape, d_msm_scal);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -43,7 +43,8 @@ static void draws_job(In& in, Out& out) {
     uint32_t* d_draws = to_device(in.span((size_t)8 * n_tail), (size_t)8 * n_tail);
     Guarded<uint32_t> tail((size_t)8 * n_tail), host(1 + groups), verdict(groups + 2);
     RC(ingest_rows_enqueue(0, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, verdict.p, groups));   // (the preset, as the upload makes it)
-    RC(ingest_draws_enqueue(0, d_draws, reinterpret_cast<uint8_t*>(tail.p), n_tail, n, groups, d_off, verdict.p, host.p));
+    const GroupShape shape = d_off ? GroupShape::unequal(groups, n, d_off) : GroupShape::equal(groups, n, n_tail);
+    RC(ingest_draws_enqueue(0, d_draws, reinterpret_cast<uint8_t*>(tail.p), n_tail, n, shape, verdict.p, host.p));
     CK(hipDeviceSynchronize());
     tail.collect(out, "tail"); host.collect(out, "host verdict"); verdict.collect(out, "verdict block");
     CK(hipFree(d_draws));

@@ -26,7 +26,7 @@ static void job_weights(In& in, Out& out) {
     Fr* d_mult = to_device(mult.data(), n);
     uint32_t* d_off = with_off ? to_device(off.data(), G) : nullptr;
     Guarded<uint32_t> weights((size_t)8 * (G + 1)), legs((size_t)8 * G);
-    RC(leg_weights_enqueue(0, d_tail, d_mult, d_off, gs, G, weights.p, legs.p));
+    RC(leg_weights_enqueue(0, GroupShape{G, gs, gs, d_off}, d_tail, d_mult, weights.p, legs.p));   // (the kernel reads first(g) alone: off[0 .. G - 1], or g * gs)
     CK(hipDeviceSynchronize());
     weights.collect(out, "weights"); legs.collect(out, "legs");
     CK(hipFree(d_tail)); CK(hipFree(d_mult));

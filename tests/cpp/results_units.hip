@@ -42,9 +42,9 @@ static void finish_job(In& in, Out& out) {
     if (want & 16u) o.group_failed = group_failed.p;
     if (want & 32u) { o.failed_index = index.p; o.failed_cap = cap; }
     if (want & 64u) o.summary = summary.p;
+    const GroupShape shape = d_off ? GroupShape::unequal(groups, n, d_off) : GroupShape::equal(groups, n, n);
     for (uint32_t r = 0; r < repeat; ++r)
-        RC(results_enqueue(0, reinterpret_cast<const int*>(d_status), n, groups, d_off, d_fold, d_ok, flags, reinterpret_cast<const uint8_t*>(d_bytes), d_fault, tile_words.p,
-                           group_words.p, o));
+        RC(results_enqueue(0, reinterpret_cast<const int*>(d_status), n, shape, d_fold, d_ok, flags, reinterpret_cast<const uint8_t*>(d_bytes), d_fault, tile_words.p, group_words.p, o));
     CK(hipDeviceSynchronize());
     status.collect(out, "status"); group_ok.collect(out, "group_ok"); left.collect(out, "left_xy"); right.collect(out, "right_xy");
     group_failed.collect(out, "group_failed"); index.collect(out, "failed_index"); summary.collect(out, "summary");

@@ -7,10 +7,10 @@
 //   verify_units stream      IN OUT   transcript_stage_enqueue: k_stream_build, then k_transcript or k_transcript_keccak
 //   verify_units insteval    IN OUT   instance_eval_enqueue: k_instance_eval
 //   verify_units frvm        IN OUT   frvm_enqueue: k_frvm / k_frvm2 on a programmed VmInstr program
-//   verify_units fold        IN OUT   fold_shared_enqueue (k_fold_shared) and fold_shared_ranges_enqueue (k_fold_ranges)
-//   verify_units multipliers IN OUT   multipliers_enqueue: k_mult_tiles, k_mult_scan_tiles, k_mult_apply over groups of equal size
+//   verify_units fold        IN OUT   fold_shared_enqueue (k_fold_shared, equal or unequal groups) and fold_shared_ranges_enqueue (k_fold_ranges)
+//   verify_units multipliers IN OUT   multipliers_enqueue over groups of equal size (a shard's longer tail included)
 //   verify_units gather      IN OUT   gather_multipliers_enqueue: k_gather_multipliers (a file of whole words)
-//   verify_units ragged      IN OUT   ragged_multipliers_enqueue: the segmented suffix scan k_seg_mult_tiles, k_seg_mult_scan_tiles,
+//   verify_units ragged      IN OUT   multipliers_enqueue: the segmented suffix scan k_seg_mult_tiles, k_seg_mult_scan_tiles,
 //                                     k_seg_mult_apply over groups of unequal size
 // IN is little-endian: a word n_jobs, then per job the words and byte blocks its reader below takes, in that order.  OUT is the jobs'
 // results one after another (the layouts are at the writers).  Field elements cross the file boundary as 32 canonical little-endian
@@ -259,7 +259,8 @@ static void run_frvm(In& in, Out& out) {
 }
 
 // ---- fold
-// job, form 0 (fold_shared_enqueue): 0, n, np, n_shared, groups, shared [n_shared][n]
+// job, form 0 (fold_shared_enqueue): 0, n, np, n_shared, groups, with_off, (with_off) groups + 1 offsets from 0 to n, shared [n_shared][n];
+//      without offsets the groups are equal
 //      out: msm_scal, all (n np + groups n_shared) rows of 8 raw words (FILL where nothing was written)
 // job, form 1 (fold_shared_ranges_enqueue): 1, n_batches, per batch (n, n_shared, shared [n_shared][n]), n_ranges, per range (batch, first, count, out),
 //      max_shared, out_rows
@@ -268,13 +269,21 @@ static void run_fold(In& in, Out& out) {
     const uint32_t form = in.word();
     REQUIRE(form <= 1, "form");
     if (form == 0) {
-        const uint32_t n = in.word(), np = in.word(), n_shared = in.word(), groups = in.word();
-        REQUIRE(n >= 1 && n <= (1u << 16) && np <= 16 && n_shared >= 1 && n_shared <= MAX_ITEMS && groups >= 1 && groups <= n && n % groups == 0, "counts");
+        const uint32_t n = in.word(), np = in.word(), n_shared = in.word(), groups = in.word(), with_off = in.word();
+        REQUIRE(n >= 1 && n <= (1u << 16) && np <= 16 && n_shared >= 1 && n_shared <= MAX_ITEMS && groups >= 1 && groups <= n && with_off <= 1, "counts");
+        DevBuf<uint32_t> d_off;
+        if (with_off) {
+            const std::vector<uint32_t> off = in.words(groups + 1);
+            REQUIRE(off[0] == 0 && off[groups] == n, "offsets from 0 to n");
+            for (uint32_t g = 0; g < groups; ++g) REQUIRE(off[g] < off[g + 1], "a group of no proofs");
+            upload(d_off, off.data(), off.size());
+        } else REQUIRE(n % groups == 0, "equal groups divide n");
+        const GroupShape shape = with_off ? GroupShape::unequal(groups, n, d_off.p) : GroupShape::equal(groups, n, n);
         DevBuf<Fr> shared;
         { const std::vector<Fr> h = in.fields<Fr>((size_t)n_shared * n); upload(shared, h.data(), h.size()); }
         const size_t rows = (size_t)n * np + (size_t)groups * n_shared;
         Guarded<uint32_t> msm(rows * 8, FILL);
-        RC(fold_shared_enqueue(0, shared.p, n, np, n_shared, groups, msm.p));
+        RC(fold_shared_enqueue(0, shape, shared.p, n, np, n_shared, msm.p));
         CK(hipDeviceSynchronize());
         msm.collect(out, "msm_scal");
         return;
@@ -320,8 +329,9 @@ static void run_multipliers(In& in, Out& out) {
     const size_t draws = (size_t)G * nt, mults = (size_t)G * n;
     REQUIRE(draws <= in.left() / 32, "input too short");
     uint8_t* d_tail = to_device(in.bytes(32 * draws), 32 * draws);
-    Guarded<Fr> mult(mults), scratch(multipliers_scratch(G * nt, G));
-    RC(multipliers_enqueue(0, d_tail, G * nt, G * n, G, mult.p, scratch.p));
+    const GroupShape shape{G, n, nt, nullptr};
+    Guarded<Fr> mult(mults), scratch(multipliers_scratch(shape));
+    RC(multipliers_enqueue(0, shape, d_tail, nullptr, mult.p, scratch.p));
     CK(hipDeviceSynchronize());
     scratch.host("scratch");
     out_fields(out, mult, "multipliers");
@@ -351,27 +361,30 @@ static void run_gather(In& in, Out& out) {
 // ---- ragged
 // job: n_groups, the n_groups sizes, then sum(sizes) draws of 32 little-endian bytes
 // out: sum(sizes) multipliers of 32 canonical bytes: mult[p] = the product of the draws behind p in p's group
-// The "last proof of its group" bytes are built here as the library's host side builds them; the per-tile scratch arrays lie between bands too.
+// The offsets and the "last proof of its group" bytes are built here as the library's host side builds them; the scratch lies between bands too.
 static void run_ragged(In& in, Out& out) {
     const uint32_t G = in.word();
     REQUIRE(G >= 1 && G <= (1u << 20), "bad group count");
     std::vector<uint8_t> last;
+    std::vector<uint32_t> off(1, 0);
     for (uint32_t g = 0; g < G; ++g) {
         const uint32_t sz = in.word();
         REQUIRE(sz >= 1 && sz <= (1u << 22) && last.size() + sz <= (1u << 22), "bad group size");
         last.resize(last.size() + sz, 0); last.back() = 1;
+        off.push_back((uint32_t)last.size());
     }
-    const size_t n = last.size(), tiles = ragged_multipliers_tiles((uint32_t)n);
+    const size_t n = last.size();
     REQUIRE(n <= in.left() / 32, "input too short");
     uint8_t* d_tail = to_device(in.bytes(32 * n), 32 * n);
     uint8_t* d_last = to_device(last.data(), n);
-    Guarded<Fr> mult(n), tile_prod(tiles);
-    Guarded<uint32_t> tile_words(2 * tiles);
-    RC(ragged_multipliers_enqueue(0, d_tail, d_last, (uint32_t)n, mult.p, tile_prod.p, tile_words.p));
+    uint32_t* d_off = to_device(off.data(), off.size());
+    const GroupShape shape = GroupShape::unequal(G, (uint32_t)n, d_off);
+    Guarded<Fr> mult(n), scratch(multipliers_scratch(shape));
+    RC(multipliers_enqueue(0, shape, d_tail, d_last, mult.p, scratch.p));
     CK(hipDeviceSynchronize());
-    tile_prod.host("tile products"); tile_words.host("tile words");
+    scratch.host("scratch");
     out_fields(out, mult, "multipliers");
-    CK(hipFree(d_tail)); CK(hipFree(d_last));
+    CK(hipFree(d_tail)); CK(hipFree(d_last)); CK(hipFree(d_off));
 }
 
 static const Mode MODES[] = {{"decompress", each_job<run_decompress, 4096>, false, false}, {"stream", each_job<run_stream, 4096>, false, false},

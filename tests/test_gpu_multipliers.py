@@ -1,5 +1,5 @@
-"""The batch multipliers (csrc/verify_kernels.hip: a two-level suffix scan over many workgroups, k_mult_tiles / k_mult_scan_tiles /
-k_mult_apply behind multipliers_enqueue) against Python big integers: mult[g][p] = the product of the draws of the LATER proofs of
+"""The batch multipliers of equal groups (csrc/verify_kernels.hip: the segmented suffix scan k_seg_mult_tiles / k_seg_mult_scan_tiles /
+k_seg_mult_apply behind multipliers_enqueue) against Python big integers: mult[g][p] = the product of the draws of the LATER proofs of
 p's own group, mod r (kzg/strategy.rs:129, msm.rs:173-176).  build/verify_units multipliers (tests/cpp/verify_units.hip, built by
 csrc/Makefile with the library's flags) runs the library's own kernels on raw draws chosen here: n = 1, 2, 63, 64, 65, 1024 and 8192
 proofs per group in 1, 4 and 32 groups, with a zero draw inside a group (it zeroes the multipliers of the group's earlier proofs and
@@ -83,6 +83,14 @@ def test_a_shard_uploads_the_tail_of_the_whole_batch(tmp_path):
     jobs = []
     for G, n, nt in [(1, 1, 9), (1, 64, 65), (4, 63, 1024), (4, 256, 257), (2, 1024, 8192), (32, 65, 130)]:
         jobs.append((G, nt, n, [[rnd.randrange(R) for _ in range(nt)] for _ in range(G)]))
+    _check(jobs, _run(jobs, tmp_path))
+
+
+def test_groups_against_the_tile_boundaries(tmp_path):
+    """equal groups are segments of one scan over the whole draw array, in tiles of 256 draws: a group whose draws past its proofs
+    straddle a tile's end (gs = 255, nt = 257, G = 3), and groups that end exactly on a tile's end (gs = nt = 256, G = 2)"""
+    rnd = random.Random(350)
+    jobs = [(G, nt, n, [[rnd.randrange(1, R) for _ in range(nt)] for _ in range(G)]) for G, n, nt in [(3, 255, 257), (2, 256, 256)]]
     _check(jobs, _run(jobs, tmp_path))
 
 

@@ -1,5 +1,5 @@
 """The multipliers of groups of unequal size (csrc/verify_kernels.hip: the segmented suffix scan k_seg_mult_tiles / k_seg_mult_scan_tiles /
-k_seg_mult_apply behind ragged_multipliers_enqueue) against Python big integers (tests/ragged_reference.py), exactly, as canonical
+k_seg_mult_apply behind multipliers_enqueue) against Python big integers (tests/ragged_reference.py), exactly, as canonical
 residues.  build/verify_units ragged (tests/cpp/verify_units.hip, built by csrc/Makefile with the library's flags) runs the library's own enqueue
 function on raw draws chosen here; it presets the outputs and checks the guard bands around them and around the per-tile scratch."""
 import random

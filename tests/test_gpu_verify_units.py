@@ -360,17 +360,26 @@ def test_fold_shared(tmp_path):
             for n_shared in (1, 5):
                 n, np = gs * groups, 2
                 sh = [[rnd.randrange(R) for _ in range(n)] for _ in range(n_shared)]
-                jobs.append(W(0, n, np, n_shared, groups) + b"".join(vr.le32(v) for row in sh for v in row))
-                meta.append((gs, groups, n_shared, n, np, sh))
+                jobs.append(W(0, n, np, n_shared, groups, 0) + b"".join(vr.le32(v) for row in sh for v in row))
+                meta.append(([gs] * groups, n_shared, n, np, sh))
+    # unequal groups, by their offsets: a group below, at and above the 256-lane stride, and a one-proof group between large ones
+    for sizes in ([1], [1, 255, 256, 257], [257, 1, 1000]):
+        for n_shared in (1, 5):
+            n, np = sum(sizes), 2
+            off = [sum(sizes[:g]) for g in range(len(sizes) + 1)]
+            sh = [[rnd.randrange(R) for _ in range(n)] for _ in range(n_shared)]
+            jobs.append(W(0, n, np, n_shared, len(sizes), 1, *off) + b"".join(vr.le32(v) for row in sh for v in row))
+            meta.append((sizes, n_shared, n, np, sh))
     out = Cursor(_run("fold", jobs, tmp_path))
     fill = int.from_bytes(FILL32, "little")
-    for gs, groups, n_shared, n, np, sh in meta:
+    for sizes, n_shared, n, np, sh in meta:
+        groups = len(sizes)
         rows = _rows(out, n * np + groups * n_shared)
-        what = f"fold_shared gs={gs} groups={groups} n_shared={n_shared}"
+        what = f"fold_shared sizes={sizes} n_shared={n_shared}"
         assert all(v == fill for v in rows[:n * np]), f"{what}: a row of the proofs' own scalars was written"
         for g in range(groups):
             for j in range(n_shared):
-                v, w = rows[n * np + g * n_shared + j], vr.fold(sh, n, j, g * gs, gs)
+                v, w = rows[n * np + g * n_shared + j], vr.fold(sh, n, j, sum(sizes[:g]), sizes[g])
                 assert v == w, f"{what}: group {g} row {j} is {v:#x}, not {w:#x}"
     out.done()
 

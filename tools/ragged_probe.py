@@ -1,8 +1,8 @@
 """What groups of unequal size cost (h2v_batch_set_group_sizes, h2v_verify_batches), on the benchmark's k = 14 proofs (1024 distinct,
 cycled).  Three measurements, each a median of --reps runs after a warm-up of at least 50 ms of the same work:
   equal     one launch of 20 x 1024 proofs, inputs resident: launch + finish on a batch set up with set_groups(20), and the same on a
-            batch set up with set_group_sizes([1024] * 20) — the segmented scan and the fold by offsets in place of the equal-groups kernels
-            — and upload + launch + finish of the same (the multipliers are computed at upload: k_mult_* against the segmented k_seg_mult_*;
+            batch set up with set_group_sizes([1024] * 20) — the same kernels over a GroupShape with offsets (csrc/batch.h), the groups' ends from
+            the last-of-group marks — and upload + launch + finish of the same (the multipliers are computed at upload;
             --only-upload runs this leg alone, the form to put under a kernel trace for the kernels' own durations)
   skewed    [200, 1, 1, 1] x 8 (the window plan follows the largest problem of a launch) beside 32 equal groups of the same total
   batches   32 batches summing to 32 768 proofs, sizes from random.Random(2026) (SIZES below), from host bytes: one h2v_verify_batches
