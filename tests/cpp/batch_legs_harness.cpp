@@ -1,8 +1,8 @@
 // C++ caller of the feed of a finished staged batch to a resident accumulator (include/h2v.hpp Accumulator::process_batch).
 //
 //   batch_legs_harness <dir> <sizes>
-// reads <dir>/params.bin, vk0.bin, rand.bin (n x 32) and items.txt in the format of tests/cpp/journal_harness.cpp (one key: "1 n",
-// then a line per proof, all of one instance shape); <sizes> are the group sizes, comma-separated, summing to n.  The proofs go through
+// reads <dir>/params.bin, vk0.bin, rand.bin (n x 32) and the keyed items.txt of one key (tests/cpp/caller.h: "1 n", then a line per
+// proof), all of one instance shape; <sizes> are the group sizes, comma-separated, summing to n.  The proofs go through
 // one staged launch of those groups without a pairing (the C ABI's h2v_batch_*), and the finished batch is fed to a journaled
 // accumulator; a second accumulator is given the same proofs by one process call per group.  It prints
 //   added <n_proofs> <n_failed> <all_ok 0/1>
@@ -13,38 +13,10 @@
 //   refused <what>                                                    (what the mirror refuses before any C call: a null batch)
 // tests/test_gpu_cpp_batch_legs.py builds it with g++ over the library and compares the lines with the Python class and the CPU oracle;
 // tests/test_accumulator_batch_host.py builds it with the address and undefined-behaviour sanitizers over the stand-in library.
-#include <cstdio>
-#include <fstream>
-#include <iostream>
-#include <iterator>
 #include <sstream>
-#include <string>
-#include "../../include/h2v.hpp"
+#include "caller.h"
 
-using namespace halo2_verifier;
-
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static Bytes unhex(const std::string& h) {
-    Bytes out;
-    if (h == "-") return out;
-    for (size_t i = 0; i + 1 < h.size(); i += 2) out.push_back((uint8_t)std::stoul(h.substr(i, 2), nullptr, 16));
-    return out;
-}
-static void hex(const uint8_t* b, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", b[i]); }
-static void report(const char* what, Accumulator& acc) {
-    const bool ok = acc.finalize();
-    acc.read();
-    printf("%s %d ", what, ok ? 1 : 0); hex(acc.left(), 64); printf(" "); hex(acc.right(), 64);
-    printf(" %zu %zu\n", acc.n_proofs(), acc.n_failed());
-}
-struct BatchHandle {
-    h2v_batch* b = nullptr;
-    ~BatchHandle() { if (b) h2v_batch_destroy(b); }
-};
+using namespace caller;
 
 int main(int argc, char** argv) {
     if (argc != 3) { fprintf(stderr, "usage: batch_legs_harness <dir> <sizes>\n"); return 2; }
@@ -54,35 +26,24 @@ int main(int argc, char** argv) {
         std::stringstream ss(argv[2]);
         for (std::string tok; std::getline(ss, tok, ',');) sizes.push_back(std::stoul(tok));
     }
-    std::ifstream in(d + "/items.txt");
-    size_t n_keys = 0, n = 0, total = 0;
+    const Items in = read_items(d, true);
+    const size_t n = in.items.size();
+    size_t total = 0;
     for (size_t v : sizes) total += v;
-    if (!(in >> n_keys >> n) || n_keys != 1 || sizes.empty() || total != n) return 2;
-    std::vector<Accumulator::Item> items(n);
+    if (in.n_keys != 1 || sizes.empty() || total != n || !n) return 2;
+    const std::vector<Accumulator::Item> items = accumulator_items(in.items);
+    // a staged launch holds one shape: proofs of one length, instance columns of the same lengths
     std::vector<size_t> col_lens;
+    for (const Column& c : items[0].instances) col_lens.push_back(c.size());
+    const size_t proof_len = items[0].proof.size();
     Bytes proofs_flat, inst_flat;
-    size_t proof_len = 0;
-    for (size_t i = 0; i < n; ++i) {
-        Accumulator::Item& it = items[i];
-        size_t ncols = 0;
-        in >> it.key >> ncols;
-        std::vector<size_t> lens(ncols);
-        for (size_t& l : lens) in >> l;
-        std::string ph, ih;
-        in >> ph >> ih;
-        it.proof = unhex(ph);
-        const Bytes flat = unhex(ih);
-        if (i == 0) { col_lens = lens; proof_len = it.proof.size(); }
-        if (lens != col_lens || it.proof.size() != proof_len) return 2;   // a staged launch holds one shape
-        size_t at = 0;
-        for (size_t l : lens) {
-            Column c;
-            for (size_t j = 0; j < l; ++j, at += 32) c.emplace_back(flat.begin() + at, flat.begin() + at + 32);
-            it.instances.push_back(c);
+    for (const Accumulator::Item& it : items) {
+        if (it.instances.size() != col_lens.size() || it.proof.size() != proof_len) return 2;
+        for (size_t c = 0; c < col_lens.size(); ++c) {
+            if (it.instances[c].size() != col_lens[c]) return 2;
+            for (const Bytes& v : it.instances[c]) inst_flat.insert(inst_flat.end(), v.begin(), v.end());
         }
-        if (at != flat.size()) return 2;
         proofs_flat.insert(proofs_flat.end(), it.proof.begin(), it.proof.end());
-        inst_flat.insert(inst_flat.end(), flat.begin(), flat.end());
     }
     try {
         ParamsKZG params{slurp(d + "/params.bin"), SerdeFormat::RawBytes};
@@ -92,7 +53,7 @@ int main(int argc, char** argv) {
         size_t n_inst = 0;
         for (size_t l : col_lens) n_inst += l;
         // the staged launch: groups of the given sizes, no pairing of its own
-        BatchHandle bh;
+        BatchHolder bh;
         check(h2v_batch_create(ctx.handle(), n, n_inst, &bh.b));
         set_group_sizes(bh.b, sizes);
         check(h2v_batch_upload(bh.b, n, proofs_flat.data(), proof_len, inst_flat.data(), col_lens.size(), col_lens.data(), rand.data(), n));
@@ -119,8 +80,7 @@ int main(int argc, char** argv) {
         fed.process_batch(bh.b);
         fed.read();
         printf("again %zu %zu\n", fed.n_proofs(), fed.n_failed());
-        try { fed.process_batch(nullptr); printf("accepted a null batch\n"); }
-        catch (const Failure& f) { if (f.code == H2V_ERR_BAD_ARGUMENT) printf("refused a null batch\n"); else throw; }
+        refused("a null batch", [&] { fed.process_batch(nullptr); });
     } catch (const Failure& f) {
         fprintf(stderr, "failure %d: %s\n", f.code, f.what());
         return 1;

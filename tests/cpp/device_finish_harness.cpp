@@ -1,8 +1,8 @@
 // C++ caller of a staged batch's finish into device memory (include/h2v.hpp finish_device -> h2v_batch_finish_device).
 //
 //   device_finish_harness <dir> <n> <groups> <proof_len> <values per proof>
-// reads <dir>/params.bin, vk.bin, proofs.bin (n x proof_len), instances.bin (n x values x 32) and rand.bin (n x 32), uploads and
-// launches one grouped batch, and prints
+// reads <dir>/params.bin, vk.bin and the flat inputs of a staged batch (tests/cpp/caller.h), uploads and launches one grouped batch,
+// and prints
 //   refused <code>          three times: what the mirror refuses itself (a pointer off a 16-byte boundary, failed_cap 0), and what the
 //                           library refuses (a status array in an allocation ONE byte short)
 //   device <group verdicts> <status...> <left hex per group> <right hex per group> | <failed per group...> | <indices...> | <summary...>
@@ -10,29 +10,9 @@
 //   host <group verdicts> <status...> <left hex> <right hex>          h2v_batch_finish_groups of the same launch
 //   device ...              h2v::finish_device again, after the host finish
 // tests/test_gpu_cpp_device_finish.py builds it and compares the lines with each other and with Batch.finish_groups in Python.
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <hip/hip_runtime_api.h>
-#include "../../include/h2v.hpp"
+#include "caller_hip.h"
 
-using namespace halo2_verifier;
-
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void hex(const uint8_t* b, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", b[i]); }
-#define HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 3; } } while (0)
-
-static void print_results(const char* tag, const std::vector<int>& ok, const std::vector<int>& st, const Bytes& left, const Bytes& right) {
-    printf("%s ", tag);
-    for (int v : ok) printf("%d", v);
-    for (int v : st) printf(" %d", v);
-    printf(" "); hex(left.data(), left.size()); printf(" "); hex(right.data(), right.size());
-}
+using namespace caller;
 
 // the seven outputs in device memory, every byte preset to 0xEE
 struct DeviceArrays {
@@ -58,7 +38,7 @@ struct DeviceArrays {
         HIP(hipMemcpy(left.data(), r.left_xy, 64 * groups, hipMemcpyDeviceToHost)); HIP(hipMemcpy(right.data(), r.right_xy, 64 * groups, hipMemcpyDeviceToHost));
         HIP(hipMemcpy(failed.data(), r.group_failed, 4 * groups, hipMemcpyDeviceToHost)); HIP(hipMemcpy(index.data(), r.failed_index, 4 * n, hipMemcpyDeviceToHost));
         HIP(hipMemcpy(summary.data(), r.summary, 4 * H2V_SUMMARY_WORDS, hipMemcpyDeviceToHost));
-        print_results("device", ok, st, left, right);
+        group_results("device", ok, st, left, right);
         printf(" |"); for (uint32_t v : failed) printf(" %u", v);
         printf(" |"); for (uint32_t v : index) printf(" %u", v);
         printf(" |"); for (uint32_t v : summary) printf(" %u", v);
@@ -74,22 +54,17 @@ int main(int argc, char** argv) {
     if (argc != 6) { fprintf(stderr, "usage: device_finish_harness <dir> <n> <groups> <proof_len> <values per proof>\n"); return 2; }
     const std::string d = argv[1];
     const size_t n = std::stoul(argv[2]), groups = std::stoul(argv[3]), plen = std::stoul(argv[4]), values = std::stoul(argv[5]);
-    struct Batch { h2v_batch* b = nullptr; ~Batch() { if (b) h2v_batch_destroy(b); } };   // (waits for the batch's stream before the outputs go)
     DeviceArrays out{n, groups, {}};
     void* short_status = nullptr;
     int rc = 0;
     try {
         ParamsKZG params{slurp(d + "/params.bin"), SerdeFormat::RawBytes};
         VerifyingKey vk{slurp(d + "/vk.bin"), SerdeFormat::RawBytes};
-        const Bytes proofs = slurp(d + "/proofs.bin"), inst = slurp(d + "/instances.bin"), rand = slurp(d + "/rand.bin");
-        if (!n || proofs.size() != n * plen || inst.size() != n * values * 32 || rand.size() != n * 32) { fprintf(stderr, "the files do not hold n proofs\n"); return 2; }
+        const Staged in = read_staged(d, n, plen, values);
         Context ctx(params, vk);
-        const std::vector<size_t> col_lens{values};
-        Batch batch;   // (gone before its context)
-        check(h2v_batch_create(ctx.handle(), n, values, &batch.b));
+        BatchHolder batch;   // (gone before its context; waits for the batch's stream before the outputs go)
+        stage(batch, ctx, n, groups, plen, values, in);
         h2v_batch* const b = batch.b;
-        check(h2v_batch_set_groups(b, groups));
-        check(h2v_batch_upload(b, n, proofs.data(), plen, inst.data(), col_lens.size(), col_lens.data(), rand.data(), n));
         check(h2v_batch_launch(b, 1));
         if ((rc = out.alloc()) || (rc = out.preset())) return rc;
         HIP(hipMalloc(&short_status, 4 * n - 1));
@@ -108,7 +83,7 @@ int main(int argc, char** argv) {
         std::vector<int> st(n), ok(groups);
         Bytes left(64 * groups), right(64 * groups);
         check(h2v_batch_finish_groups(b, st.data(), ok.data(), left.data(), right.data(), groups));
-        print_results("host", ok, st, left, right);
+        group_results("host", ok, st, left, right);
         printf("\n");
         if ((rc = out.preset())) return rc;
         finish_device(b, out.r);

@@ -1,8 +1,8 @@
 // C++ caller of every proof's Guard out of a launch (include/h2v_guards.hpp -> include/h2v_guards.h).
 //
 //   guards_out_harness <dir> <n> <groups> <proof_len> <values per proof> <first> <count>
-// reads <dir>/params.bin, vk.bin, proofs.bin (n x proof_len), instances.bin (n x values x 32) and rand.bin (n x 32), uploads and
-// launches one grouped batch, and prints for the range [first, first + count)
+// reads <dir>/params.bin, vk.bin and the flat inputs of a staged batch (tests/cpp/caller.h), uploads and launches one grouped batch,
+// and prints for the range [first, first + count)
 //   shape <T_L> <T_R>
 //   refused <code>          twice: what the mirror refuses itself (a pointer off a 16-byte boundary) and what the library refuses (a
 //                           range past the upload)
@@ -13,27 +13,16 @@
 //   guard <j> <right scalars hex>                                   h2v::guards::guard_of for the range's last proof
 //   finish <group verdicts> <status...>                             h2v_batch_finish_groups afterwards
 // tests/test_gpu_cpp_guards_out.py builds it and compares the lines with each other and with Batch.guards in Python.
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <hip/hip_runtime_api.h>
+#include "caller_hip.h"
 #include "../../include/h2v_guards.hpp"
 
-using namespace halo2_verifier;
-
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void hex(const Bytes& b) { if (b.empty()) printf("-"); for (uint8_t v : b) printf("%02x", v); }
-#define HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 3; } } while (0)
+using namespace caller;
 
 static void print_guards(const char* tag, const std::vector<int>& st, const Guard& g, const Bytes& mult) {
     printf("%s", tag);
     for (int v : st) printf(" %d", v);
-    printf(" | "); hex(g.left_scalars); printf(" "); hex(g.left_bases); printf(" "); hex(g.right_scalars); printf(" "); hex(g.right_bases); printf(" "); hex(mult);
+    printf(" | "); hex_or_dash(g.left_scalars); printf(" "); hex_or_dash(g.left_bases); printf(" "); hex_or_dash(g.right_scalars); printf(" "); hex_or_dash(g.right_bases);
+    printf(" "); hex_or_dash(mult);
     printf("\n");
 }
 
@@ -42,22 +31,18 @@ int main(int argc, char** argv) {
     const std::string d = argv[1];
     const size_t n = std::stoul(argv[2]), groups = std::stoul(argv[3]), plen = std::stoul(argv[4]), values = std::stoul(argv[5]), first = std::stoul(argv[6]),
                  count = std::stoul(argv[7]);
-    struct Batch { h2v_batch* b = nullptr; ~Batch() { if (b) h2v_batch_destroy(b); } };   // (waits for the batch's stream before the outputs go)
     void* dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int rc = 0;
     try {
         ParamsKZG params{slurp(d + "/params.bin"), SerdeFormat::RawBytes};
         VerifyingKey vk{slurp(d + "/vk.bin"), SerdeFormat::RawBytes};
-        const Bytes proofs = slurp(d + "/proofs.bin"), inst = slurp(d + "/instances.bin"), rand = slurp(d + "/rand.bin");
-        if (!n || !count || first + count > n || proofs.size() != n * plen || inst.size() != n * values * 32 || rand.size() != n * 32) { fprintf(stderr, "the files do not hold n proofs, or the range lies outside them\n"); return 2; }
+        const Staged in = read_staged(d, n, plen, values);
+        if (!count || first + count > n) bad_input("the range lies outside the n proofs");
         Context ctx(params, vk);
-        const std::vector<size_t> col_lens{values};
         Msm left(ctx), right(ctx);   // (gone before the context, after the batch)
-        Batch batch;
-        check(h2v_batch_create(ctx.handle(), n, values, &batch.b));
+        BatchHolder batch;           // (waits for the batch's stream before the outputs go)
+        stage(batch, ctx, n, groups, plen, values, in);
         h2v_batch* const b = batch.b;
-        check(h2v_batch_set_groups(b, groups));
-        check(h2v_batch_upload(b, n, proofs.data(), plen, inst.data(), col_lens.size(), col_lens.data(), rand.data(), n));
         check(h2v_batch_launch(b, 1));
         const guards::Shape sh = guards::shape(b);
         printf("shape %zu %zu\n", sh.left_terms, sh.right_terms);
@@ -82,9 +67,10 @@ int main(int argc, char** argv) {
         HIP(hipMemcpy(mult.data(), dev[4], bytes[4], hipMemcpyDeviceToHost)); HIP(hipMemcpy(st.data(), dev[5], bytes[5], hipMemcpyDeviceToHost));
         print_guards("device", st, g, mult);
         const size_t failed = guards::append(b, first, count, &left, &right);
-        printf("append %zu | ", failed); hex(left.scalars()); printf(" "); hex(left.bases()); printf(" "); hex(right.scalars()); printf(" "); hex(right.bases()); printf("\n");
+        printf("append %zu | ", failed); hex_or_dash(left.scalars()); printf(" "); hex_or_dash(left.bases()); printf(" "); hex_or_dash(right.scalars()); printf(" "); hex_or_dash(right.bases());
+        printf("\n");
         const Guard last = guards::guard_of(host, count - 1);
-        printf("guard %zu ", count - 1); hex(last.right_scalars); printf("\n");
+        printf("guard %zu ", count - 1); hex_or_dash(last.right_scalars); printf("\n");
         std::vector<int> fst(n), ok(groups);
         check(h2v_batch_finish_groups(b, fst.data(), ok.data(), nullptr, nullptr, groups));
         printf("finish ");

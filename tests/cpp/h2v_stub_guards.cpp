@@ -2,19 +2,11 @@
 // tests/test_guards_host.py): each prints its name, its scalar arguments and an FNV-1a hash of every input array, read with the
 // lengths the call's own counts give — so a sanitizer build catches a mirror that hands over too short a buffer — and writes canned
 // verdicts.  No GPU, no arithmetic.
-#include <cinttypes>
-#include <cstdio>
 #include "../../include/h2v.h"
+#include "h2v_stub.h"
 
 namespace {
-uint64_t fnv(const void* p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) { h ^= ((const uint8_t*)p)[i]; h *= 1099511628211ull; }
-    return h;
-}
-void bytes(const char* name, const void* p, size_t n) {
-    if (!p) printf(" %s=null", name); else printf(" %s=%zu:%016" PRIx64, name, n, fnv(p, n));
-}
+using h2v_stub::bytes;
 void guards(size_t n, const size_t* lc, const size_t* rc, const uint8_t* ls, const uint8_t* lb, const uint8_t* rs, const uint8_t* rb) {
     size_t nl = 0, nr = 0;
     for (size_t i = 0; i < n; ++i) { nl += lc[i]; nr += rc[i]; }

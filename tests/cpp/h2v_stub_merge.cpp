@@ -2,20 +2,12 @@
 // tests/test_accumulator_merge_host.py): each prints its name, its scalar arguments and an FNV-1a hash of every input array, read
 // with the lengths the call itself passes — so a sanitizer build catches a mirror that hands over too short a buffer — and writes
 // canned outputs.  No GPU, no arithmetic.
-#include <cinttypes>
-#include <cstdio>
 #include <cstring>
 #include "../../include/h2v.h"
+#include "h2v_stub.h"
 
 namespace {
-uint64_t fnv(const void* p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) { h ^= ((const uint8_t*)p)[i]; h *= 1099511628211ull; }
-    return h;
-}
-void bytes(const char* name, const void* p, size_t n) {
-    if (!p) printf(" %s=null", name); else printf(" %s=%zu:%016" PRIx64, name, n, fnv(p, n));
-}
+using h2v_stub::bytes;
 void draws_out(uint8_t* out, size_t n) { if (out) for (size_t i = 0; i < 32 * n; ++i) out[i] = (uint8_t)(0xd0 + i % 16); }
 }
 

@@ -7,21 +7,16 @@
 //   h2v_stub_set_fail(name, rc): from now on the entry point `name` returns rc and does nothing else (null / rc 0: none); the environment
 //   variable H2V_STUB_FAIL=name does the same with rc -16 for a program that cannot call it.
 //   h2v_stub_take_log(): the log since the last call, as one string.
-#include <cinttypes>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include "../../include/h2v.h"
+#include "h2v_stub.h"
 
 struct h2v_msm { size_t n; h2v_ctx* ctx; };
 
 namespace {
-uint64_t fnv(const void* p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) { h ^= ((const uint8_t*)p)[i]; h *= 1099511628211ull; }
-    return h;
-}
+using h2v_stub::fnv;
 std::string g_log, g_taken, g_fail;
 int g_fail_rc = 0;
 bool g_env_read = false;

@@ -6,21 +6,11 @@
 // ("n proof_len n_pub"), runs the same calls a Rust user of the crate would make, and prints one line per result:
 //   single <i> <plonk::Error as int>
 //   batch <ok 0/1> <left hex> <right hex> <status...>
-// tests/test_gpu_cpp_harness.py builds it with g++, feeds it seeded inputs and compares every line with the CPU oracle.
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include "../../include/h2v.hpp"
+// tests/test_gpu_cpp_harness.py builds it with g++, feeds it seeded inputs and compares every line with the CPU oracle.  slurp, hex and
+// verdict ("<tag> <ok> <left hex> <right hex>") are those of tests/cpp/caller.h, the prelude of all the caller programs.
+#include "caller.h"
 
-using namespace halo2_verifier;
-
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void hex(const uint8_t* b, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", b[i]); }
+using namespace caller;
 
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: harness <dir>\n"); return 2; }
@@ -47,7 +37,7 @@ int main(int argc, char** argv) {
         acc.set_randomness(rand);
         for (size_t i = 0; i < n; ++i) verify_proof(params, vk, acc, inst_of(i), proof_of(i));
         const bool ok = acc.finalize();
-        printf("batch %d ", ok ? 1 : 0); hex(acc.left(), 64); printf(" "); hex(acc.right(), 64);
+        verdict("batch", ok, acc.left(), acc.right());
         for (int s : acc.statuses()) printf(" %d", s);
         printf("\n");
         // AccumulatorStrategy::with(msm_accumulator) (kzg/strategy.rs:75-78): the first half accumulated, its evaluated channels
@@ -62,7 +52,7 @@ int main(int argc, char** argv) {
         second.set_randomness(Bytes(rand.begin() + 32 * half, rand.end()));
         for (size_t i = half; i < n; ++i) verify_proof(params, vk, second, inst_of(i), proof_of(i));
         const bool ok2 = second.finalize();
-        printf("resumed %d ", (ok1 && ok2) ? 1 : 0); hex(second.left(), 64); printf(" "); hex(second.right(), 64);
+        verdict("resumed", ok1 && ok2, second.left(), second.right());
         printf("\n");
     } catch (const Failure& e) {
         printf("failure %d %s\n", e.code, e.what());

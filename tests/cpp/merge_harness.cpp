@@ -1,9 +1,9 @@
 // C++ caller of the merge of resident accumulators (include/h2v.hpp Accumulator::merge / export_state / merge_states).
 //
 //   merge_harness <dir> <n_sources>
-// reads <dir>/params.bin, vk0.bin, rand.bin (n x 32), draws.bin (n_sources x 32) and items.txt in the format of
-// tests/cpp/journal_harness.cpp (one key: "1 n", then a line per proof).  Proof i is fed to source i % n_sources, each source in one
-// process call with the draws of its proofs; a journaled destination merges the sources with the draws of draws.bin, a second one
+// reads <dir>/params.bin, vk0.bin, rand.bin (n x 32), draws.bin (n_sources x 32) and the keyed items.txt of one key (tests/cpp/caller.h:
+// "1 n", then a line per proof).  Proof i is fed to source i % n_sources, each source in one process call with the draws of its
+// proofs; a journaled destination merges the sources with the draws of draws.bin, a second one
 // merges their exported states with the same draws, a third with draws of the library's own.  It prints
 //   state <k> <hex of the 152 bytes>                         (export_state() of every source)
 //   merge <ok 0/1> <left hex> <right hex> <n_proofs> <n_failed> <entries> <draws used hex>
@@ -13,63 +13,26 @@
 //                                                             wrong length, states of a wrong length, the destination as a source)
 // tests/test_gpu_cpp_merge.py builds it with g++ over the library and compares the lines with the Python class and the CPU oracle;
 // tests/test_accumulator_merge_host.py builds it with the address and undefined-behaviour sanitizers over the stand-in library.
-#include <cstdio>
-#include <fstream>
-#include <iostream>
-#include <iterator>
-#include <memory>
-#include <string>
-#include "../../include/h2v.hpp"
+#include "caller.h"
 
-using namespace halo2_verifier;
+using namespace caller;
 
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static Bytes unhex(const std::string& h) {
-    Bytes out;
-    if (h == "-") return out;
-    for (size_t i = 0; i + 1 < h.size(); i += 2) out.push_back((uint8_t)std::stoul(h.substr(i, 2), nullptr, 16));
-    return out;
-}
-static void hex(const uint8_t* b, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", b[i]); }
 static void report(const char* what, Accumulator& acc, const Bytes& used) {
     const bool ok = acc.finalize();
     acc.read();
     const size_t entries = acc.check_legs().size();
-    printf("%s %d ", what, ok ? 1 : 0); hex(acc.left(), 64); printf(" "); hex(acc.right(), 64);
-    printf(" %zu %zu %zu ", acc.n_proofs(), acc.n_failed(), entries); hex(used.data(), used.size()); printf("\n");
-}
-template <class F> static void refused(const char* what, F call) {
-    try { call(); printf("accepted %s\n", what); } catch (const Failure& f) { if (f.code == H2V_ERR_BAD_ARGUMENT) printf("refused %s\n", what); else throw; }
+    verdict(what, ok, acc.left(), acc.right());
+    printf(" %zu %zu %zu ", acc.n_proofs(), acc.n_failed(), entries); hex(used); printf("\n");
 }
 
 int main(int argc, char** argv) {
     if (argc != 3) { fprintf(stderr, "usage: merge_harness <dir> <n_sources>\n"); return 2; }
     const std::string d = argv[1];
     const size_t K = std::stoul(argv[2]);
-    std::ifstream in(d + "/items.txt");
-    size_t n_keys = 0, n = 0;
-    if (!(in >> n_keys >> n) || n_keys != 1 || K < 1 || K > 16) return 2;
-    std::vector<Accumulator::Item> items(n);
-    for (Accumulator::Item& it : items) {
-        size_t ncols = 0;
-        in >> it.key >> ncols;
-        std::vector<size_t> lens(ncols);
-        for (size_t& l : lens) in >> l;
-        std::string ph, ih;
-        in >> ph >> ih;
-        it.proof = unhex(ph);
-        const Bytes flat = unhex(ih);
-        size_t at = 0;
-        for (size_t l : lens) {
-            Column c;
-            for (size_t j = 0; j < l; ++j, at += 32) c.emplace_back(flat.begin() + at, flat.begin() + at + 32);
-            it.instances.push_back(c);
-        }
-    }
+    const Items in = read_items(d, true);
+    const size_t n = in.items.size();
+    if (in.n_keys != 1 || K < 1 || K > 16) return 2;
+    const std::vector<Accumulator::Item> items = accumulator_items(in.items);
     try {
         ParamsKZG params{slurp(d + "/params.bin"), SerdeFormat::RawBytes};
         Context ctx(params, VerifyingKey{slurp(d + "/vk0.bin"), SerdeFormat::RawBytes});
@@ -86,7 +49,7 @@ int main(int argc, char** argv) {
             srcs.back()->process({&ctx}, mine, r);
             handles.push_back(srcs.back().get());
             const Bytes st = srcs.back()->export_state();
-            printf("state %zu ", k); hex(st.data(), st.size()); printf("\n");
+            printf("state %zu ", k); hex(st); printf("\n");
             states.insert(states.end(), st.begin(), st.end());
         }
         Accumulator a(ctx), b(ctx), c(ctx);
@@ -97,7 +60,7 @@ int main(int argc, char** argv) {
         const Bytes used = c.merge(handles);
         const bool ok = c.finalize();
         c.read();
-        printf("drawn %d %zu ", ok ? 1 : 0, c.n_proofs()); hex(used.data(), used.size()); printf("\n");
+        printf("drawn %d %zu ", ok ? 1 : 0, c.n_proofs()); hex(used); printf("\n");
         refused("too many sources", [&] { c.merge(std::vector<Accumulator*>(H2V_ACC_MERGE_MAX + 1, handles[0]), Bytes()); });
         refused("draws of a wrong length", [&] { c.merge(handles, Bytes(32 * K + 1)); });
         refused("states of a wrong length", [&] { c.merge_states(Bytes(states.begin(), states.end() - 1)); });

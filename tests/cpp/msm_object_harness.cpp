@@ -2,8 +2,7 @@
 // h2v_accumulator_add_msms): AccumulatorStrategy::process by hand over the Guards of a CPU verify_proof.
 //
 //   msm_object_harness <dir>
-// reads <dir>/params.bin, rand.bin (n x 32), factor.bin (32) and guards.txt: one line per Guard, "<left scalars hex> <left bases hex>
-// <right scalars hex> <right bases hex>", "-" for an empty list.  It prints
+// reads <dir>/params.bin, rand.bin (n x 32), factor.bin (32) and guards.txt with one line per Guard (tests/cpp/caller.h).  It prints
 //   hand <ok 0/1> <left hex> <right hex> <n left terms> <n right terms>   D = DualMsm(); per Guard i: D.scale(rand_i); D.add_guard(g_i); check_many({D})
 //   each <0/1>...                                                         check_many over one DualMsm per Guard
 //   scaled <ok> <left hex> <right hex>                                    E = DualMsm(); E.add_msm(D); E.scale(factor)
@@ -16,37 +15,16 @@
 //   refused <count>                                                       what the mirror refuses before any C call
 // A Failure ends the program with status 1 after "failure <code>", every object destroyed on the way out.
 // tests/test_gpu_cpp_msm_object.py builds it over the library; tests/test_msm_object_host.py over the stand-in library, with sanitizers.
-#include <cstdio>
-#include <fstream>
-#include <iostream>
-#include <iterator>
-#include <string>
-#include "../../include/h2v.hpp"
+#include "caller.h"
 
-using namespace h2v;
+using namespace caller;
 
-static Bytes slurp(const std::string& p) {
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    return Bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static Bytes unhex(const std::string& h) {
-    Bytes out;
-    if (h == "-") return out;
-    for (size_t i = 0; i + 1 < h.size(); i += 2) out.push_back((uint8_t)std::stoul(h.substr(i, 2), nullptr, 16));
-    return out;
-}
-static void hex(const uint8_t* b, size_t n) { for (size_t i = 0; i < n; ++i) printf("%02x", b[i]); }
-static void checked(const char* name, const DualMsm::Checked& c) {
-    printf("%s %d ", name, c.ok[0] ? 1 : 0); hex(c.lefts.data(), 64); printf(" "); hex(c.rights.data(), 64);
-}
+static void checked(const char* name, const DualMsm::Checked& c) { verdict(name, c.ok[0], c.lefts.data(), c.rights.data()); }
 
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: msm_object_harness <dir>\n"); return 2; }
     const std::string d = argv[1];
-    std::ifstream gin(d + "/guards.txt");
-    std::vector<Guard> guards;
-    for (std::string a, b, c, e; gin >> a >> b >> c >> e;) guards.push_back(Guard{unhex(a), unhex(b), unhex(c), unhex(e)});
+    const std::vector<Guard> guards = read_guards(d);
     const Bytes rand = slurp(d + "/rand.bin"), factor = slurp(d + "/factor.bin");
     if (guards.empty() || rand.size() != 32 * guards.size() || factor.size() != 32) return 2;
     try {
@@ -97,7 +75,8 @@ int main(int argc, char** argv) {
             acc.add_msms(&D.left, nullptr);
             const bool ok = acc.finalize();
             acc.read();
-            printf("acc %d ", ok ? 1 : 0); hex(acc.left(), 64); printf(" "); hex(acc.right(), 64); printf("\n");
+            verdict("acc", ok, acc.left(), acc.right());
+            printf("\n");
         }
         const size_t e0 = DualMsm::check_many({}).ok.size(), e1 = Msm::eval_many({}).xy.size();
         printf("empty %zu %zu\n", e0, e1);

@@ -7,15 +7,12 @@
     which read every array with the lengths the calls pass), hands over buffers of the right lengths and refuses a null batch before
     any C call."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 from test_accumulator_host import _unbacked
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class _Recorder:
@@ -81,19 +78,10 @@ def test_process_batch_call_and_bookkeeping(monkeypatch):
 
 
 def test_cpp_mirror_over_the_stand_in_library(tmp_path):
-    exe = tmp_path / "batch_legs_harness"
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                    "-I", os.path.join(ROOT, "include"), "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "batch_legs_harness.cpp"),
-                    os.path.join(ROOT, "tests", "cpp", "h2v_stub.cpp"), os.path.join(ROOT, "tests", "cpp", "h2v_stub_batch_legs.cpp")], check=True)
+    exe = ch.build("batch_legs_harness", tmp_path, sanitize=True, stubs=("h2v_stub", "h2v_stub_batch_legs"))
     n, sizes = 6, [1, 3, 2]
-    (tmp_path / "params.bin").write_bytes(b"p" * 100)
-    (tmp_path / "vk0.bin").write_bytes(b"v" * 50)
-    (tmp_path / "rand.bin").write_bytes(bytes(range(32)) * n)
-    (tmp_path / "items.txt").write_text("\n".join(["1 %d" % n] + ["0 2 1 1 " + ("%02x" % i) * 40 + " " + "ab" * 64 for i in range(n)]) + "\n")
-    r = subprocess.run([str(exe), str(tmp_path), ",".join(map(str, sizes))], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = r.stdout.splitlines()
+    ch.write_dir(tmp_path, b"p" * 100, vks=[b"v" * 50], rand=bytes(range(32)) * n, items_txt=ch.stand_in_items_text(n))
+    out = ch.run(exe, [tmp_path, ",".join(map(str, sizes))], timeout=120).stdout.splitlines()
     up = [l for l in out if l.startswith("h2v_batch_upload ")]
     assert len(up) == 1 and re.fullmatch(r"h2v_batch_upload batch=\S+ n=6 proof_len=40 ncols=2 n_tail=6 proofs=240:[0-9a-f]{16} inst=384:[0-9a-f]{16} tail=192:[0-9a-f]{16}", up[0])
     assert [l for l in out if l.startswith("h2v_batch_set_group_sizes ")] == ["h2v_batch_set_group_sizes batch=0xb000 sizes=[1,3,2]"]

@@ -12,11 +12,11 @@ import os
 import re
 import socket
 import struct
-import subprocess
 import sys
 
 import pytest
 
+import caller_harness as ch
 import merge_reference as mr
 from test_accumulator_host import _unbacked
 
@@ -92,20 +92,10 @@ def test_state_layout():
 
 
 def test_cpp_mirror_over_the_stand_in_library(tmp_path):
-    exe = tmp_path / "merge_harness"
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                    "-I", os.path.join(ROOT, "include"), "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "merge_harness.cpp"),
-                    os.path.join(ROOT, "tests", "cpp", "h2v_stub.cpp"), os.path.join(ROOT, "tests", "cpp", "h2v_stub_merge.cpp")], check=True)
+    exe = ch.build("merge_harness", tmp_path, sanitize=True, stubs=("h2v_stub", "h2v_stub_merge"))
     n, K = 5, 3
-    (tmp_path / "params.bin").write_bytes(b"p" * 100)
-    (tmp_path / "vk0.bin").write_bytes(b"v" * 50)
-    (tmp_path / "rand.bin").write_bytes(bytes(range(32)) * n)
-    (tmp_path / "draws.bin").write_bytes(bytes(range(1, 33)) * K)
-    (tmp_path / "items.txt").write_text("\n".join(["1 %d" % n] + ["0 2 1 1 " + ("%02x" % i) * 40 + " " + "ab" * 64 for i in range(n)]) + "\n")
-    r = subprocess.run([str(exe), str(tmp_path), str(K)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = r.stdout.splitlines()
+    ch.write_dir(tmp_path, b"p" * 100, vks=[b"v" * 50], rand=bytes(range(32)) * n, draws_bin=bytes(range(1, 33)) * K, items_txt=ch.stand_in_items_text(n))
+    out = ch.run(exe, [tmp_path, K], timeout=120).stdout.splitlines()
     merges = [l for l in out if l.startswith("h2v_accumulator_merge ")]
     assert len(merges) == 2                                         # the refused calls never reach the library
     assert re.fullmatch(r"h2v_accumulator_merge acc=\S+ srcs=\[\S+,\S+,\S+\] draws=96:[0-9a-f]{16} out=asked", merges[0])

@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+import caller_harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R_MOD = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 SEED_A = bytes(range(32))
@@ -174,4 +176,4 @@ def test_cpp_mirror_header_compiles(tmp_path):
                    "    h2v::draws::expand_device(0, nullptr, seed, 0, 0, nullptr);\n"
                    "    return d.size() == 96 ? 0 : 1;\n"
                    "}\n")
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src)], check=True)
+    caller_harness.check_syntax(src)

@@ -1,26 +1,20 @@
 """The C++ mirror (include/h2v.hpp Accumulator) over proofs of two VerifyingKeys in two legs: tests/cpp/accumulator_harness.cpp feeds
 them to one resident accumulator as they would arrive and prints the bytes; every line is compared with the Python class on the same
 legs and with the CPU oracle's one accumulation over all of them."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_accumulator_two_legs_over_two_vks(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "accumulator_harness"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "accumulator_harness.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("accumulator_harness", tmp_path)
     s8, s4 = circuits.setup_vector_mul(8, 8), circuits.setup_vector_mul(8, 4)
     assert s8.params == s4.params
     P8, I8 = circuits.prove_vector_mul_batch(s8, 5, seed=51, threads=4)
@@ -34,17 +28,8 @@ def test_cpp_accumulator_two_legs_over_two_vks(tmp_path):
     ctxs = [h2v.Context(h2v.ParamsKZG(s.params, h2v.SerdeFormat.RawBytes), h2v.VerifyingKey(s.vk, h2v.SerdeFormat.RawBytes)) for s in (s8, s4)]
 
     def run(items):
-        d = tmp_path
-        (d / "params.bin").write_bytes(s8.params)
-        (d / "vk0.bin").write_bytes(s8.vk)
-        (d / "vk1.bin").write_bytes(s4.vk)
-        (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-        lines = [f"2 {len(items)}"]
-        for s, p, inst in items:
-            flat = b"".join(v for col in inst for v in col)
-            lines.append(" ".join([str(0 if s is s8 else 1), str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-        (d / "items.txt").write_text("\n".join(lines) + "\n")
-        return subprocess.run([str(exe), str(d), str(cut)], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+        d = ch.write_dir(tmp_path, s8.params, vks=[s8.vk, s4.vk], rand=rand, items_txt=ch.keyed_items_text(items, (s8, s4)))
+        return ch.run(exe, [d, cut]).stdout.splitlines()
 
     def python_legs(items):
         acc = h2v.Accumulator(ctxs[0])

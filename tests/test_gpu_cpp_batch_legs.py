@@ -2,42 +2,28 @@
 ABI: tests/cpp/batch_legs_harness.cpp stages ten proofs in groups of 3 / 1 / 4 / 2 without a pairing, one of them failing by status,
 feeds the finished batch to a journaled accumulator and the same proofs to a second one by process, group by group; every line is
 compared with the Python class on the same proofs and with the CPU oracle's one accumulation."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_feed_of_a_batch_in_four_groups(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "batch_legs_harness"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "batch_legs_harness.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("batch_legs_harness", tmp_path)
     n, sizes = 10, [3, 1, 4, 2]
     s = circuits.setup_vector_mul(8, 8)
     P, I = circuits.prove_vector_mul_batch(s, n, seed=71, threads=4)
     P[5] = P[5][:-96] + b"\xff" * 32 + P[5][-64:]                    # a non-canonical scalar: status -5, in group 2
     rnd = random.Random(72)
     rand = [rnd.randrange(1, R_MOD) for _ in range(n)]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params)
-    (d / "vk0.bin").write_bytes(s.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-    lines = [f"1 {n}"]
-    for p, inst in zip(P, I):
-        flat = b"".join(v for col in inst for v in col)
-        lines.append(" ".join(["0", str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-    (d / "items.txt").write_text("\n".join(lines) + "\n")
-    out = subprocess.run([str(exe), str(d), ",".join(map(str, sizes))], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s.params, vks=[s.vk], rand=rand, items_txt=ch.items_text(P, I, keys=[0] * n))
+    out = ch.run(exe, [d, ",".join(map(str, sizes))]).stdout.splitlines()
 
     exp = circuits.oracle_verify_batch(s, P, I, rand)
     assert exp[0] is False and [i for i, v in enumerate(exp[1]) if v] == [5]

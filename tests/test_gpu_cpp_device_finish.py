@@ -2,28 +2,21 @@
 grouped batch, reads h2v::finish_device's arrays before and after h2v_batch_finish_groups and prints all three; the device lines must
 be one line twice, agree with the host line and with Batch.finish_groups in Python, and carry the counts, indices and summary that
 follow from the statuses.  It also holds the refusal of a status array in an allocation one byte short (hipMalloc's own size)."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 import results_reference as rr
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_finish_device_equals_finish_groups(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe, obj = tmp_path / "device_finish_harness", tmp_path / "device_finish_harness.o"
-    # (host code over the HIP runtime's API: hipcc for its include and library paths; two steps, so that only the source is read as HIP)
-    subprocess.run(["hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", "-c", "-o", str(obj), os.path.join(ROOT, "tests", "cpp", "device_finish_harness.cpp")], check=True)
-    subprocess.run(["hipcc", "-o", str(exe), str(obj), lib, "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("device_finish_harness", tmp_path, hip=True)
     s = circuits.setup_vector_mul(8, 8)
     n, groups = 12, 3
     P, I = circuits.prove_vector_mul_batch(s, n, seed=77, threads=4)
@@ -33,10 +26,8 @@ def test_cpp_finish_device_equals_finish_groups(tmp_path):
     I2[5] = [[circuits.le32(5)] + I[5][0][1:]]          # a wrong public input: the pairing of group 1 fails
     P2[9] = P2[9][:-96] + b"\xff" * 32 + P2[9][-64:]    # a non-canonical scalar: status -5, in group 2
     flat, inst = b"".join(P2), b"".join(b"".join(col) for i in I2 for col in i)
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params); (d / "vk.bin").write_bytes(s.vk)
-    (d / "proofs.bin").write_bytes(flat); (d / "instances.bin").write_bytes(inst); (d / "rand.bin").write_bytes(rand)
-    out = subprocess.run([str(exe), str(d), str(n), str(groups), "1024", "8"], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s.params, vk=s.vk, rand=rand, proofs_bin=flat, instances_bin=inst)
+    out = ch.run(exe, [d, n, groups, 1024, 8]).stdout.splitlines()
     assert out[:3] == ["refused -16"] * 3, out[:3]
     before, host, after = out[3], out[4].split(), out[5]
     assert before == after and before.startswith("device ") and host[0] == "host"

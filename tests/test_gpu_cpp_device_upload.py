@@ -1,27 +1,20 @@
 """The C++ mirror (include/h2v.hpp) of a staged batch's upload from device memory: tests/cpp/device_upload_harness.cpp runs one grouped
 batch through h2v_batch_upload and through h2v::upload_device (the same bytes in device memory, rows 48 bytes apart) and prints both
 results; they must be one line twice, and equal Batch.upload in Python."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_upload_device_equals_upload(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe, obj = tmp_path / "device_upload_harness", tmp_path / "device_upload_harness.o"
-    # (host code over the HIP runtime's API: hipcc for its include and library paths; two steps, so that only the source is read as HIP)
-    subprocess.run(["hipcc", "-std=c++17", "-O1", "--offload-arch=gfx950", "-c", "-o", str(obj), os.path.join(ROOT, "tests", "cpp", "device_upload_harness.cpp")], check=True)
-    subprocess.run(["hipcc", "-o", str(exe), str(obj), lib, "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("device_upload_harness", tmp_path, hip=True)
     s = circuits.setup_vector_mul(8, 8)
     n, groups = 12, 3
     P, I = circuits.prove_vector_mul_batch(s, n, seed=77, threads=4)
@@ -30,10 +23,8 @@ def test_cpp_upload_device_equals_upload(tmp_path):
     I2 = list(I)
     I2[5] = [[circuits.le32(5)] + I[5][0][1:]]          # a wrong public input: the pairing of group 1 fails
     flat, inst = b"".join(P), b"".join(b"".join(col) for i in I2 for col in i)
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params); (d / "vk.bin").write_bytes(s.vk)
-    (d / "proofs.bin").write_bytes(flat); (d / "instances.bin").write_bytes(inst); (d / "rand.bin").write_bytes(rand)
-    out = subprocess.run([str(exe), str(d), str(n), str(groups), "1024", "8"], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s.params, vk=s.vk, rand=rand, proofs_bin=flat, instances_bin=inst)
+    out = ch.run(exe, [d, n, groups, 1024, 8]).stdout.splitlines()
     assert out[1:3] == ["refused -16", "refused -16"], out[1:3]
     host, device = out[0].split(), out[3].split()
     assert host[0] == "host" and device[0] == "device" and host[1:] == device[1:]

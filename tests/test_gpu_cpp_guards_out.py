@@ -1,27 +1,20 @@
 """The C++ mirror (include/h2v_guards.hpp) of every proof's Guard out of a launch: tests/cpp/guards_out_harness.cpp launches one small
 grouped batch and prints a range's Guards through h2v::guards::to_host, to_device and append; the three must agree with each other
 and with Batch.guards in Python, and the finish afterwards with Batch.finish_groups."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_guards_round_trip(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe, obj = tmp_path / "guards_out_harness", tmp_path / "guards_out_harness.o"
-    # (host code over the HIP runtime's API: hipcc for its include and library paths; two steps, so that only the source is read as HIP)
-    subprocess.run(["hipcc", "-std=c++17", "-O1", "-Wall", "-Werror", "--offload-arch=gfx950", "-c", "-o", str(obj), os.path.join(ROOT, "tests", "cpp", "guards_out_harness.cpp")], check=True)
-    subprocess.run(["hipcc", "-o", str(exe), str(obj), lib, "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("guards_out_harness", tmp_path, hip=True)
     s = circuits.setup_vector_mul(8, 8)
     n, groups, first, count = 12, 3, 2, 8                       # the range crosses both group boundaries
     P, I = circuits.prove_vector_mul_batch(s, n, seed=177, threads=4)
@@ -30,11 +23,8 @@ def test_cpp_guards_round_trip(tmp_path):
     P2 = list(P)
     P2[6] = P2[6][:-96] + b"\xff" * 32 + P2[6][-64:]            # a non-canonical scalar: status -5, a zero row inside the range
     flat, inst = b"".join(P2), b"".join(b"".join(col) for i in I for col in i)
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params); (d / "vk.bin").write_bytes(s.vk)
-    (d / "proofs.bin").write_bytes(flat); (d / "instances.bin").write_bytes(inst); (d / "rand.bin").write_bytes(rand)
-    out = subprocess.run([str(exe), str(d), str(n), str(groups), "1024", "8", str(first), str(count)], check=True, capture_output=True, text=True,
-                         timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s.params, vk=s.vk, rand=rand, proofs_bin=flat, instances_bin=inst)
+    out = ch.run(exe, [d, n, groups, 1024, 8, first, count]).stdout.splitlines()
     assert out[0] == "shape 1 18" and out[1:3] == ["refused -16"] * 2, out[:3]
     host, device, append, guard, finish = out[3:8]
     assert host.startswith("host ") and device == "device" + host[4:]

@@ -1,25 +1,19 @@
 """The C++ mirror (include/h2v.hpp) of identification over proofs of two VerifyingKeys: tests/cpp/identify_keys.cpp queues them on
 one AccumulatorStrategy in call order and finalize_identify_keys() runs h2v_verify_batch_keys_identify.  The printed verdict,
 channels and statuses are compared with the CPU oracle."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_finalize_identify_keys_over_two_vks(tmp_path):
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "identify_keys"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "identify_keys.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("identify_keys", tmp_path)
     s8, s4 = circuits.setup_vector_mul(8, 8), circuits.setup_vector_mul(8, 4)
     assert s8.params == s4.params
     P8, I8 = circuits.prove_vector_mul_batch(s8, 6, seed=81, threads=4)
@@ -29,19 +23,11 @@ def test_cpp_finalize_identify_keys_over_two_vks(tmp_path):
         items += [(s8, P8[j], I8[j]), (s4, P4[j], I4[j])]
     rnd = random.Random(83)
     rand = [rnd.randrange(1, R_MOD) for _ in items]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s8.params)
-    (d / "vk0.bin").write_bytes(s8.vk)
-    (d / "vk1.bin").write_bytes(s4.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
+    d = ch.write_dir(tmp_path, s8.params, vks=[s8.vk, s4.vk], rand=rand)
 
     def run(items):
-        lines = [f"2 {len(items)}"]
-        for s, p, inst in items:
-            flat = b"".join(v for col in inst for v in col)
-            lines.append(" ".join([str(0 if s is s8 else 1), str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-        (d / "items.txt").write_text("\n".join(lines) + "\n")
-        return subprocess.run([str(exe), str(d)], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+        ch.write_dir(d, items_txt=ch.keyed_items_text(items, (s8, s4)))
+        return ch.run(exe, [d]).stdout.splitlines()
 
     for case in ("good", "bad"):
         if case == "bad":   # a wrong public input on the second key: only the pairing rejects it

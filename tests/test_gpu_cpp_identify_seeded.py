@@ -1,43 +1,29 @@
 """The C++ mirror (include/h2v.hpp) of identification on a SEEDED accumulation: tests/cpp/identify_seeded.cpp resumes the first half's
 accumulator with AccumulatorStrategy::with, queues the second half and finalize_identify() runs h2v_verify_batch_seeded_identify.  The
 printed verdict, channels, statuses and the seed's own verdict are compared with the CPU oracle."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_finalize_identify_on_a_seeded_accumulation(tmp_path):
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "identify_seeded"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "identify_seeded.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("identify_seeded", tmp_path)
     s = circuits.setup_vector_mul(8, 8)
     P, I = circuits.prove_vector_mul_batch(s, 12, seed=85, threads=4)
     rnd = random.Random(87)
     rand = [rnd.randrange(1, R_MOD) for _ in P]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params)
-    (d / "vk.bin").write_bytes(s.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand[6:]))
+    d = ch.write_dir(tmp_path, s.params, vk=s.vk, rand=rand[6:])
 
     def run(P, I):
         _, _, left, right = circuits.oracle_verify_batch(s, P[:6], I[:6], rand[:6])
-        (d / "seed.bin").write_bytes(left + right)
-        lines = [f"{len(P) - 6}"]
-        for p, inst in zip(P[6:], I[6:]):
-            flat = b"".join(v for col in inst for v in col)
-            lines.append(" ".join([str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-        (d / "items.txt").write_text("\n".join(lines) + "\n")
-        out = subprocess.run([str(exe), str(d)], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+        ch.write_dir(d, seed_bin=left + right, items_txt=ch.items_text(P[6:], I[6:]))
+        out = ch.run(exe, [d]).stdout.splitlines()
         return out, circuits.oracle_pairing_check(s, left, right)
 
     for case in ("good", "bad_second_half", "bad_seed"):

@@ -2,26 +2,20 @@
 VerifyingKeys in three legs, one of them holding a proof that only the pairing rejects: tests/cpp/journal_harness.cpp feeds them to
 one journaled accumulator, drops the legs whose own pairing fails and prints the bytes; every line is compared with the Python class on
 the same legs and with the CPU oracle's accumulation over the kept legs."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_journal_three_legs_over_two_vks(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "journal_harness"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "journal_harness.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("journal_harness", tmp_path)
     s8, s4 = circuits.setup_vector_mul(8, 8), circuits.setup_vector_mul(8, 4)
     assert s8.params == s4.params
     P8, I8 = circuits.prove_vector_mul_batch(s8, 5, seed=51, threads=4)
@@ -34,17 +28,8 @@ def test_cpp_journal_three_legs_over_two_vks(tmp_path):
     rnd = random.Random(55)
     rand = [rnd.randrange(1, R_MOD) for _ in items]
     bounds = [0, 3, 7, 10]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s8.params)
-    (d / "vk0.bin").write_bytes(s8.vk)
-    (d / "vk1.bin").write_bytes(s4.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-    lines = [f"2 {len(items)}"]
-    for s, p, inst in items:
-        flat = b"".join(v for col in inst for v in col)
-        lines.append(" ".join([str(0 if s is s8 else 1), str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-    (d / "items.txt").write_text("\n".join(lines) + "\n")
-    out = subprocess.run([str(exe), str(d), "3", "7"], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s8.params, vks=[s8.vk, s4.vk], rand=rand, items_txt=ch.keyed_items_text(items, (s8, s4)))
+    out = ch.run(exe, [d, 3, 7]).stdout.splitlines()
 
     # the Python class on the same legs
     ctxs = [h2v.Context(h2v.ParamsKZG(s.params, h2v.SerdeFormat.RawBytes), h2v.VerifyingKey(s.vk, h2v.SerdeFormat.RawBytes)) for s in (s8, s4)]

@@ -2,28 +2,22 @@
 C ABI: tests/cpp/merge_harness.cpp feeds ten proofs to three accumulators, merges them into a journaled one — directly, through
 their exported states, and with draws of the library's own — and prints the bytes; every line is compared with the Python class on
 the same proofs and with the CPU oracle's merge."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 import merge_reference as mr
 import oracle_lib
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_merge_of_three_accumulators(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "merge_harness"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "merge_harness.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("merge_harness", tmp_path)
     n, K = 10, 3
     s = circuits.setup_vector_mul(8, 8)
     P, I = circuits.prove_vector_mul_batch(s, n, seed=61, threads=4)
@@ -31,17 +25,8 @@ def test_cpp_merge_of_three_accumulators(tmp_path):
     rnd = random.Random(62)
     rand = [rnd.randrange(1, R_MOD) for _ in range(n)]
     draws = [rnd.randrange(1, R_MOD) for _ in range(K)]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params)
-    (d / "vk0.bin").write_bytes(s.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-    (d / "draws.bin").write_bytes(b"".join(c.to_bytes(32, "little") for c in draws))
-    lines = [f"1 {n}"]
-    for p, inst in zip(P, I):
-        flat = b"".join(v for col in inst for v in col)
-        lines.append(" ".join(["0", str(len(inst))] + [str(len(c)) for c in inst] + [p.hex(), flat.hex() or "-"]))
-    (d / "items.txt").write_text("\n".join(lines) + "\n")
-    out = subprocess.run([str(exe), str(d), str(K)], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    d = ch.write_dir(tmp_path, s.params, vks=[s.vk], rand=rand, draws_bin=ch.draws(draws), items_txt=ch.items_text(P, I, keys=[0] * n))
+    out = ch.run(exe, [d, K]).stdout.splitlines()
 
     # the oracle: every source alone, then the merge
     L = oracle_lib.load()

@@ -1,26 +1,20 @@
 """The C++ mirror of the resident MSM object on the GPU (include/h2v.hpp Msm, DualMsm, Accumulator::add_msms): tests/cpp/msm_object_harness.cpp
 builds a DualMsm from the Guards the library made for five proofs, scales, adds and checks, and prints verdicts and channels; they must
 equal what the Python mirror computes over the same Guards, draws and factor."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_msm_object_equals_python(tmp_path):
     import halo2_verifier_amd as h2v
-    from halo2_verifier_amd import _lib
-    lib = _lib.lib_path()
-    exe = tmp_path / "msm_object_harness"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "msm_object_harness.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("msm_object_harness", tmp_path)
     s = circuits.setup_vector_mul(8, 8)
     P, I = circuits.prove_vector_mul_batch(s, 5, seed=81, threads=4)
     rnd = random.Random(82)
@@ -36,12 +30,8 @@ def test_cpp_msm_object_equals_python(tmp_path):
             rs[1] = ((int.from_bytes(rs[1], "little") + 1) % R_MOD).to_bytes(32, "little")
             g["right_scalars"] = rs
         guards.append(g)
-    (tmp_path / "params.bin").write_bytes(s.params)
-    (tmp_path / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-    (tmp_path / "factor.bin").write_bytes(factor.to_bytes(32, "little"))
-    (tmp_path / "guards.txt").write_text("\n".join(" ".join(b"".join(g[k]).hex() or "-" for k in ("left_scalars", "left_bases", "right_scalars", "right_bases"))
-                                                   for g in guards) + "\n")
-    out = subprocess.run([str(exe), str(tmp_path)], check=True, capture_output=True, text=True, timeout=300).stdout.splitlines()
+    ch.write_dir(tmp_path, s.params, rand=rand, factor_bin=factor.to_bytes(32, "little"), guards_txt=ch.guards_text(guards))
+    out = ch.run(exe, [tmp_path]).stdout.splitlines()
     got = {l.split()[0]: l.split()[1:] for l in out}
     # the same in Python
     D = h2v.DualMSM(ctx)

@@ -2,17 +2,15 @@
 bit for bit what h2v_verify_batch gives over its slice with its draws: for a call of mixed sizes in one launch, for 520 batches (two
 launches: a launch holds 512 groups), for a batch above the proof budget of a launch beside small ones, with OS draws, and through the
 C++ mirror."""
-import os
 import random
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import circuits
 from circuits import R_MOD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAUNCH_PROOFS = 16384      # H2V_BATCHES_LAUNCH_PROOFS (csrc/oneshot.hip)
 
 
@@ -122,29 +120,17 @@ def test_os_draws_accept_valid_proofs_and_arguments_are_checked_first(pool, ctx)
 
 
 def test_cpp_mirror_verify_batches(pool, ctx, tmp_path):
-    from halo2_verifier_amd import _lib
     s, P, I = pool
-    lib = _lib.lib_path()
-    exe = tmp_path / "verify_batches"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "verify_batches.cpp"), lib,
-                    "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    exe = ch.build("verify_batches", tmp_path)
     sizes = [4, 1, 9]
     batches = _cut(P, I, sizes)
     p1, i1 = batches[1]
     i1[0] = [[circuits.le32(5)] + i1[0][0][1:]]
     rnd = random.Random(71)
     rand = [rnd.randrange(1, R_MOD) for _ in range(sum(sizes))]
-    d = tmp_path
-    (d / "params.bin").write_bytes(s.params)
-    (d / "vk.bin").write_bytes(s.vk)
-    (d / "rand.bin").write_bytes(b"".join(r.to_bytes(32, "little") for r in rand))
-    lines = [str(len(sizes)), " ".join(map(str, sizes))]
-    for p, i in batches:
-        for proof, inst in zip(p, i):
-            flat = b"".join(v for col in inst for v in col)
-            lines.append(" ".join([str(len(inst))] + [str(len(c)) for c in inst] + [proof.hex(), flat.hex() or "-"]))
-    (d / "items.txt").write_text("\n".join(lines) + "\n")
-    out = subprocess.run([str(exe), str(d)], check=True, capture_output=True, text=True, timeout=120).stdout.splitlines()
+    text = ch.items_text([x for p, _ in batches for x in p], [x for _, i in batches for x in i], header="%d\n%s" % (len(sizes), " ".join(map(str, sizes))))
+    d = ch.write_dir(tmp_path, s.params, vk=s.vk, rand=rand, items_txt=text)
+    out = ch.run(exe, [d], timeout=120).stdout.splitlines()
     rows = [l.split() for l in out if l.startswith("batch ")]
     assert len(rows) == 3 and "empty_refused -16" in out
     want = ctx.verify_batches(batches, rand)

@@ -6,16 +6,13 @@
     program built with the address and undefined-behaviour sanitizers over the stand-in library (tests/cpp/h2v_stub.cpp +
     h2v_stub_guards.cpp, which read every array with the lengths the call's own counts give), prints a hash of every array it was
     handed; the same hashes are made here from what the Python mirror would hand over."""
-import os
 import re
 import struct
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 from test_accumulator_host import _unbacked
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _guard(seed, nl, nr):
@@ -68,40 +65,23 @@ def test_dicts_and_tuples_flatten_alike():
     assert empty[0] == 0 and empty[3:] == (b"", b"", b"", b"")
 
 
-def _fnv(b):
-    h = 1469598103934665603
-    for x in b:
-        h = ((h ^ x) * 1099511628211) & 0xffffffffffffffff
-    return "%d:%016x" % (len(b), h)
-
-
 def _fields(guards, rand=None):
     from halo2_verifier_amd.verifier import _guards_args
     n, lc, rc, ls, lb, rs, rb = _guards_args(guards)
-    out = {"n": str(n), "left_counts": _fnv(struct.pack("<%dQ" % n, *list(lc)[:n])), "right_counts": _fnv(struct.pack("<%dQ" % n, *list(rc)[:n])),
-           "ls": _fnv(ls), "lb": _fnv(lb), "rs": _fnv(rs), "rb": _fnv(rb)}
+    out = {"n": str(n), "left_counts": ch.fnv(struct.pack("<%dQ" % n, *list(lc)[:n])), "right_counts": ch.fnv(struct.pack("<%dQ" % n, *list(rc)[:n])),
+           "ls": ch.fnv(ls), "lb": ch.fnv(lb), "rs": ch.fnv(rs), "rb": ch.fnv(rb)}
     if rand is not None:
-        out["rand"] = _fnv(rand)
+        out["rand"] = ch.fnv(rand)
     return out
 
 
 def test_cpp_and_python_mirrors_hand_over_the_same_arrays(tmp_path):
-    exe = tmp_path / "guards_harness"
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                    "-I", os.path.join(ROOT, "include"), "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "guards_harness.cpp"),
-                    os.path.join(ROOT, "tests", "cpp", "h2v_stub.cpp"), os.path.join(ROOT, "tests", "cpp", "h2v_stub_guards.cpp")], check=True)
+    exe = ch.build("guards_harness", tmp_path, sanitize=True, stubs=("h2v_stub", "h2v_stub_guards"))
     n, cut = len(GUARDS), 2
     rand = bytes(range(32)) * n
-    (tmp_path / "params.bin").write_bytes(b"p" * 100)
-    (tmp_path / "vk0.bin").write_bytes(b"v" * 50)
-    (tmp_path / "rand.bin").write_bytes(rand)
-    (tmp_path / "items.txt").write_text("\n".join(["1 %d" % n] + ["0 2 1 1 " + ("%02x" % i) * 40 + " " + "ab" * 64 for i in range(n)]) + "\n")
-    hx = lambda parts: b"".join(parts).hex() or "-"
-    (tmp_path / "guards.txt").write_text("\n".join(" ".join([hx(l[0]), hx(l[1]), hx(r[0]), hx(r[1])]) for l, r in GUARDS) + "\n")
-    r = subprocess.run([str(exe), str(tmp_path), str(cut)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = r.stdout.splitlines()
+    guards = [dict(left_scalars=l[0], left_bases=l[1], right_scalars=r[0], right_bases=r[1]) for l, r in GUARDS]
+    ch.write_dir(tmp_path, b"p" * 100, vks=[b"v" * 50], rand=rand, items_txt=ch.stand_in_items_text(n), guards_txt=ch.guards_text(guards))
+    out = ch.run(exe, [tmp_path, cut], timeout=120).stdout.splitlines()
     calls = [dict(kv.split("=", 1) for kv in l.split()[1:]) for l in out if l.startswith("h2v_accumulator_process_guards ")]
     want = [_fields(GUARDS[cut:], rand[32 * cut:]), _fields(GUARDS[:cut], rand[:32 * cut]), _fields(GUARDS[cut:], rand[32 * cut:])]
     assert len(calls) == 3                                             # the refused calls never reach the library

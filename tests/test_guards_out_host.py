@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+import caller_harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["h2v_batch_guard_shape", "h2v_batch_guards", "h2v_batch_guards_append", "h2v_batch_guards_device"]
 
@@ -142,4 +144,4 @@ def test_cpp_mirror_header_compiles(tmp_path):
                    "        return (int)(s.left_terms + one.left_scalars.size() + failed);\n"
                    "    } catch (const h2v::Failure&) { return 0; }\n"
                    "}\n")
-    subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src)], check=True)
+    caller_harness.check_syntax(src)

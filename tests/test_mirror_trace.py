@@ -3,10 +3,10 @@ value and every refusal.  Python: tests/mirror_trace.py records halo2_verifier_a
 walks include/h2v.hpp over tests/cpp/h2v_stub.cpp, built with the address and undefined-behaviour sanitizers.  No GPU, no real library."""
 import json
 import os
-import subprocess
 
 import pytest
 
+import caller_harness as ch
 import mirror_trace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,12 +52,8 @@ def test_recording_leaves_the_loaded_library_alone():
 
 
 def test_cpp_mirror_sends_what_it_sent(tmp_path):
-    exe = tmp_path / "mirror_trace"
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                    "-I", os.path.join(ROOT, "include"),
-                    "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "mirror_trace.cpp"), os.path.join(ROOT, "tests", "cpp", "h2v_stub.cpp")], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=120).stdout
+    exe = ch.build("mirror_trace", tmp_path, sanitize=True, stubs=("h2v_stub",))
+    out = ch.run(exe, timeout=120).stdout
     with open(os.path.join(GOLDEN, "mirror_calls_cpp.txt")) as f:
         want = f.read()
     assert out.splitlines() == want.splitlines()

@@ -10,12 +10,11 @@ call, reads every array with the lengths the call passes, and can be told to fai
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
+import caller_harness as ch
+
 MSM_SYMBOLS = ["h2v_msm_create", "h2v_msm_destroy", "h2v_msm_append_terms", "h2v_msm_add_msm", "h2v_msm_scale", "h2v_msm_len", "h2v_msm_terms",
                "h2v_msm_eval_many", "h2v_dual_msm_check_many", "h2v_accumulator_add_msms"]
 
@@ -24,9 +23,7 @@ MSM_SYMBOLS = ["h2v_msm_create", "h2v_msm_destroy", "h2v_msm_append_terms", "h2v
 def stub(tmp_path_factory):
     """the stand-in as a shared library, with the signatures of halo2_verifier_amd/_lib.py"""
     from halo2_verifier_amd import _lib
-    so = tmp_path_factory.mktemp("stub") / "libh2v_stub_msm.so"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-DH2V_STUB_QUIET", "-I", os.path.join(ROOT, "include"), "-o", str(so),
-                    os.path.join(CPP, "h2v_stub_msm.cpp")], check=True, stdout=subprocess.DEVNULL)
+    so = ch.build("h2v_stub_msm", tmp_path_factory.mktemp("stub"), shared=True, defines=("H2V_STUB_QUIET",))
     lib = ctypes.CDLL(str(so))
     for name in MSM_SYMBOLS:
         fn = getattr(lib, name)
@@ -207,24 +204,16 @@ def test_python_failing_call_raises_and_leaves_the_object_usable(ctx, stub):
 def harness(tmp_path_factory):
     """the sanitizer build of the harness over the stand-in, and a directory with its inputs"""
     tmp_path = tmp_path_factory.mktemp("harness")
-    exe = tmp_path / "msm_object_harness"
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                    "-I", os.path.join(ROOT, "include"), "-o", str(exe), os.path.join(CPP, "msm_object_harness.cpp"), os.path.join(CPP, "h2v_stub.cpp"),
-                    os.path.join(CPP, "h2v_stub_msm.cpp")], check=True)
-    (tmp_path / "params.bin").write_bytes(b"p" * 100)
-    (tmp_path / "rand.bin").write_bytes(bytes(range(32)) * 3)
-    (tmp_path / "factor.bin").write_bytes(bytes([7]) * 32)
-    (tmp_path / "guards.txt").write_text("\n".join(["aa" * 32 + " " + "bb" * 64 + " " + "cc" * 64 + " " + "dd" * 128, "- - " + "ee" * 32 + " " + "ff" * 64,
-                                                    "11" * 64 + " " + "22" * 128 + " - -"]) + "\n")
+    exe = ch.build("msm_object_harness", tmp_path, sanitize=True, stubs=("h2v_stub", "h2v_stub_msm"))
+    guards = "\n".join(["aa" * 32 + " " + "bb" * 64 + " " + "cc" * 64 + " " + "dd" * 128, "- - " + "ee" * 32 + " " + "ff" * 64, "11" * 64 + " " + "22" * 128 + " - -"]) + "\n"
+    ch.write_dir(tmp_path, b"p" * 100, rand=bytes(range(32)) * 3, factor_bin=bytes([7]) * 32, guards_txt=guards)
     return exe, tmp_path
 
 
 def test_cpp_mirror_over_the_stand_in_library(harness):
     exe, tmp_path = harness
     env = {k: v for k, v in os.environ.items() if k != "H2V_STUB_FAIL"}
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
+    r = ch.run(exe, [tmp_path], timeout=120, env=env)
     out = r.stdout.splitlines()
     # D: left 1 + 0 + 2 terms, right 2 + 1 + 0; every scale before the Guard it precedes
     assert [l for l in out if l.startswith("hand ")] == ["hand 1 " + "10" * 64 + " " + "20" * 64 + " 3 3"]
@@ -250,7 +239,7 @@ def test_cpp_mirror_over_the_stand_in_library(harness):
 def test_cpp_mirror_exception_paths(harness, fail):
     """A failing call throws Failure with the library's code; every object made so far is destroyed on the way out, before the context."""
     exe, tmp_path = harness
-    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=120, env=dict(os.environ, H2V_STUB_FAIL=fail))
+    r = ch.run(exe, [tmp_path], timeout=120, allow_fail=True, env=dict(os.environ, H2V_STUB_FAIL=fail))
     assert r.returncode == 1 and "failure -16" in r.stdout.splitlines(), (r.returncode, r.stderr[-2000:])
     out = r.stdout.splitlines()
     made = len([l for l in out if l == "h2v_msm_create"])
