@@ -78,6 +78,11 @@ struct StageArgs {
     G1A* pts; G1A* phi; uint8_t* ycanon; int* status;
     unsigned long long* words; uint32_t stream_words;
     Fr* chal;
+    // point hints (include/h2v_hints.h): the claimed canonical y of every point, [proof][point][32] like ycanon (and possibly ycanon
+    // itself: a workgroup reads its own 64 rows before it writes them), and the word that counts the hints not used.  Null: no hints,
+    // decompress_range_enqueue launches k_decompress as ever.
+    uint32_t* hint_misses = nullptr;
+    const uint8_t* hints = nullptr;
 };
 
 // the decompression stage in pieces (h2v_batch_upload_launch runs them around its copies): reset the status words; decompress the points of proofs [p0, p1); check the
@@ -85,6 +90,9 @@ struct StageArgs {
 int decompress_begin_enqueue(hipStream_t s, const StageArgs& g);
 int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
+// k_decompress_hinted over the proofs [p0, p1) of a stage with hints: decompress_range_enqueue's other branch (the miss word is cleared by
+// decompress_begin_enqueue or by the launch)
+int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // The groups of one upload: which proofs and which draws belong to group g.  One plain struct for host code and kernels (a kernel
 // takes it by value); everything that must know where a group starts, how long it is or whose a proof is asks it.
@@ -278,6 +286,11 @@ struct h2v_batch {
     hipStream_t copy = nullptr;
     h2v::BatchStage stage = h2v::BatchStage::Empty;
     bool decompressed = false;        // Uploaded: the upload has decompressed the points already (h2v_batch_upload_launch)
+    // point hints (include/h2v_hints.h).  hinted: h2v_batch_set_hints has put the claimed y of the upload's points into `ycanon`, where
+    // k_decompress_hinted reads them and writes the canonical y back; set there, cleared by upload_take and by every way to Empty, never
+    // inferred from the buffer.  launch_hinted: the last launch ran with hints, and hint_misses[0] counts the ones it did not use.
+    bool hinted = false, launch_hinted = false;
+    h2v::DevBuf<uint32_t> hint_misses;
     h2v::LaunchRecord last;
     size_t max_proofs = 0, max_inst = 0;
     h2v::PlanDevice* plan = nullptr;  // set at upload (depends on the instance shape)

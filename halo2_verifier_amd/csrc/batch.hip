@@ -101,7 +101,7 @@ int require_stage(const h2v_batch* b, BatchStage least, const char* who) {
 // The stage an operation leaves: Empty on every way out but its last step, commit(its stage of success).  (b may be null.)
 struct StageCommit {
     h2v_batch* b;
-    ~StageCommit() { if (b) b->stage = BatchStage::Empty; }
+    ~StageCommit() { if (b) { b->stage = BatchStage::Empty; b->hinted = false; } }   // (an empty batch has no upload, so no hints)
     void commit(BatchStage st) { b->stage = st; b = nullptr; }
 };
 
@@ -248,7 +248,9 @@ int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storag
 
 // what the decompression and transcript stages work on: the batch's upload (its plan and n) and its buffers
 static StageArgs stage_args(const h2v_batch* b) {
-    return StageArgs{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
+    StageArgs g{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
+    if (b->hinted) { g.hint_misses = b->hint_misses.p; g.hints = b->ycanon.p; }   // (h2v_batch_set_hints: the hints wait where the canonical y will lie)
+    return g;
 }
 
 // ---- An upload, whatever its source: host bytes (upload_impl) or device memory (h2v_batch_upload_device).  Every step the sources share
@@ -326,6 +328,7 @@ static int upload_take(h2v_batch* b, PlanPin& pin, size_t n, size_t n_tail, cons
     if (device_draws && ((rc = b->ingest_verdict.reserve(G + 2)) || (rc = b->ingest_host.reserve(4 * (G + 1))))) return rc;
     if ((rc = b->mult_scratch.reserve(multipliers_scratch(group_shape(b))))) return rc;   // (d_group_off and d_group_last are on the device since h2v_batch_set_group_sizes)
     b->mult_of_draws = false; b->decompressed = false; b->device_draws = device_draws;
+    b->hinted = false;   // (hints belong to one upload)
     return 0;
 }
 // VK-wide bases sit behind the batch's own points so that one MSM covers both (and their phi images behind the points' images)
@@ -467,7 +470,9 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     const ResultsLayout L{G, n};
     if (run_decompress && n) H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, L.total() - L.fold_failed(), s));
     else H2V_HIP_CHECK(hipMemsetAsync(b->fold_failed, 0, 4 * (size_t)G, s));   // (its G words)
-    if (run_decompress && n && ((rc = decompress_finish_enqueue(s, g)) || (rc = decompress_range_enqueue(s, g, 0, n)))) return rc;   // k_check_scalars, k_decompress
+    const bool hinted = run_decompress && n && g.hints;   // (a launch without hints enqueues nothing new)
+    if (hinted) H2V_HIP_CHECK(hipMemsetAsync(b->hint_misses.p, 0, sizeof(uint32_t), s));
+    if (run_decompress && n && ((rc = decompress_finish_enqueue(s, g)) || (rc = decompress_range_enqueue(s, g, 0, n)))) return rc;   // k_check_scalars, k_decompress (with hints: k_decompress_hinted)
     mark();
     if ((rc = transcript_stage_enqueue(s, g))) return rc;
     // both channels of every group in one set of launches: [2g] left, [2g+1] right (channel_problems), the group's folded VK-wide
@@ -521,6 +526,7 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     mark();
     if ((rc = close_enqueue(b, with_pairing != 0))) return rc;
     b->last.folded = false;
+    b->launch_hinted = hinted;
     mark();
     commit.commit(BatchStage::Launched);
     return 0;
@@ -1026,6 +1032,144 @@ int h2v_batch_guards_append(h2v_batch* b, size_t first, size_t count, h2v_msm* l
     return 0;
 }
 
+// ---- point hints (include/h2v_hints.h; the kernels: k_decompress_hinted in verify_kernels.hip, k_hint_rows_out in util.hip).  The hints of an upload wait in `ycanon`, which has their shape and
+// which no call between an upload and its launch reads or writes: k_decompress_hinted reads each point's hint there and writes the
+// canonical y back, so what a launch leaves is a right set of hints for the next one (zeros for the points that do not decode), and
+// h2v_batch_hints hands out the same bytes.  Like every h2v_batch_* call these take no context lock.
+namespace {
+// the checks the two forms of set_hints share, before any device work: Uploaded and not launched since, not decompressed by its upload, the upload's n
+int set_hints_check(const h2v_batch* b, const char* who, size_t n) {
+    const std::string w(who);
+    if (!b) { set_last_error(w + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->stage != BatchStage::Uploaded || !b->plan) { set_last_error(w + ": the batch holds no upload that has not been launched yet"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->decompressed) { set_last_error(w + ": the upload has decompressed its points already (h2v_batch_upload_launch)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n != b->n) { set_last_error(w + ": n is not the upload's"); return H2V_ERR_BAD_ARGUMENT; }
+    return 0;
+}
+// a range of a launch's rows: Launched or Finished, inside the upload
+int hints_range_check(const h2v_batch* b, const char* who, size_t first, size_t count) {
+    if (int rc = require_stage(b, BatchStage::Launched, who)) return rc;
+    if (!b->plan) { set_last_error(std::string(who) + ": the batch holds no plan"); return H2V_ERR_BAD_ARGUMENT; }
+    if (first > b->n || count > b->n - first) { set_last_error(std::string(who) + ": a range outside the upload"); return H2V_ERR_BAD_ARGUMENT; }
+    return 0;
+}
+int strided_rows_check(const char* who, const void* d, size_t rows, size_t row_len, size_t row_stride, int device, const char* does) {
+    if (row_stride < row_len || (row_stride & 15u) || (row_stride >> 4) > 0xffffffffu) { set_last_error(std::string(who) + ": row_stride is below 32 x n_points, or no multiple of 16"); return H2V_ERR_BAD_ARGUMENT; }
+    return device_range_check(d, (rows - 1) * row_stride + row_len, device, "d_y32", who, does);
+}
+}  // namespace
+
+int h2v_hints_point_offsets(const h2v_ctx* ctx, size_t* offsets, size_t cap, size_t* n_points) {
+    static const char who[] = "h2v_hints_point_offsets";
+    if (!ctx || !ctx->vk) { set_last_error(std::string(who) + ": the context was created without a VerifyingKey"); return H2V_ERR_BAD_ARGUMENT; }
+    // (the layout does not depend on instance lengths: the plan for empty columns, as h2v_ctx_proof_shape takes it)
+    std::vector<size_t> lens(ctx_total_instance_columns(ctx), 0);
+    PlanPin pin(const_cast<h2v_ctx*>(ctx));
+    if (int rc = pin.get(lens)) return rc;
+    const std::vector<uint32_t>& po = pin.pd->host.point_offsets;
+    if (n_points) *n_points = po.size();
+    if (!offsets) return 0;
+    if (cap < po.size()) { set_last_error(std::string(who) + ": cap is below the number of points"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t j = 0; j < po.size(); ++j) offsets[j] = po[j];
+    return 0;
+}
+
+int h2v_hints_from_points(const uint8_t* points32, size_t n, uint8_t* y32, uint8_t* decoded) {
+    if (n && (!points32 || !y32)) { set_last_error("h2v_hints_from_points: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t* in = points32 + 32 * i;
+        G1A pt;
+        // (the identity's own encoding decodes but is no point of a proof: k_decompress refuses the flag, and so does this)
+        const bool ok = !(in[31] & G1_FLAG_IDENTITY) && g1_decompress(in, pt);
+        if (ok) pt.y.to_bytes(y32 + 32 * i); else memset(y32 + 32 * i, 0, 32);
+        if (decoded) decoded[i] = ok ? 1 : 0;
+    }
+    return 0;
+}
+
+int h2v_batch_set_hints(h2v_batch* b, size_t n, const uint8_t* y32) {
+    static const char who[] = "h2v_batch_set_hints";
+    if (int rc = set_hints_check(b, who, n)) return rc;
+    if (!y32) { b->hinted = false; return 0; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};   // device work from here on: a failure of it leaves the batch Empty like any other
+    if (int rc = b->hint_misses.reserve(1)) return rc;
+    const size_t bytes = (size_t)n * b->plan->host.n_points * 32;
+    if (bytes) {
+        H2V_HIP_CHECK(hipMemcpyAsync(b->ycanon.p, y32, bytes, hipMemcpyHostToDevice, b->stream));
+        H2V_HIP_CHECK(hipStreamSynchronize(b->stream));   // the host buffer is the caller's again
+    }
+    commit.commit(BatchStage::Uploaded);
+    b->hinted = true;
+    return 0;
+}
+
+int h2v_batch_set_hints_device(h2v_batch* b, size_t n, const void* d_y32, size_t row_stride) {
+    static const char who[] = "h2v_batch_set_hints_device";
+    int rc;
+    if ((rc = set_hints_check(b, who, n))) return rc;
+    if (!d_y32) { b->hinted = false; return 0; }
+    const size_t row_len = (size_t)b->plan->host.n_points * 32;
+    const int device = b->ctx->device;
+    H2V_HIP_CHECK(hipSetDevice(device));
+    if (n && row_len && (rc = strided_rows_check(who, d_y32, n, row_len, row_stride, device, "reads"))) return rc;
+    StageCommit commit{b};
+    if ((rc = b->hint_misses.reserve(1)) || (rc = ingest_rows_enqueue(b->stream, d_y32, row_stride, row_len, n, nullptr, 0, b->ycanon.p, nullptr, nullptr, 0))) return rc;
+    commit.commit(BatchStage::Uploaded);
+    b->hinted = true;
+    return 0;
+}
+
+int h2v_batch_hints(h2v_batch* b, size_t first, size_t count, uint8_t* y32) {
+    static const char who[] = "h2v_batch_hints";
+    if (int rc = hints_range_check(b, who, first, count)) return rc;
+    const size_t row_len = (size_t)b->plan->host.n_points * 32;
+    if (!count || !row_len) return 0;
+    if (!y32) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    H2V_HIP_CHECK(hipMemcpyAsync(y32, b->ycanon.p + first * row_len, count * row_len, hipMemcpyDeviceToHost, b->stream));
+    H2V_HIP_CHECK(hipStreamSynchronize(b->stream));
+    commit.commit(stage);
+    return 0;
+}
+
+int h2v_batch_hints_device(h2v_batch* b, size_t first, size_t count, void* d_y32, size_t row_stride) {
+    static const char who[] = "h2v_batch_hints_device";
+    int rc;
+    if ((rc = hints_range_check(b, who, first, count))) return rc;
+    const size_t row_len = (size_t)b->plan->host.n_points * 32;
+    if (!count || !row_len) return 0;
+    if (!d_y32) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    const int device = b->ctx->device;
+    H2V_HIP_CHECK(hipSetDevice(device));
+    if ((rc = strided_rows_check(who, d_y32, count, row_len, row_stride, device, "writes"))) return rc;
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    if ((rc = hint_rows_out_enqueue(b->stream, b->ycanon.p + first * row_len, row_len, count, d_y32, row_stride))) return rc;
+    commit.commit(stage);
+    return 0;
+}
+
+int h2v_batch_hint_stats(h2v_batch* b, size_t* n_points, size_t* n_hinted, size_t* n_missed) {
+    static const char who[] = "h2v_batch_hint_stats";
+    if (int rc = require_stage(b, BatchStage::Launched, who)) return rc;
+    if (!b->plan) { set_last_error(std::string(who) + ": the batch holds no plan"); return H2V_ERR_BAD_ARGUMENT; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};
+    const BatchStage stage = b->stage;
+    uint32_t missed = 0;
+    if (b->launch_hinted) H2V_HIP_CHECK(hipMemcpyAsync(&missed, b->hint_misses.p, sizeof missed, hipMemcpyDeviceToHost, b->stream));
+    H2V_HIP_CHECK(hipStreamSynchronize(b->stream));
+    commit.commit(stage);
+    const size_t points = (size_t)b->n * b->plan->host.n_points;
+    if (n_points) *n_points = points;
+    if (n_hinted) *n_hinted = b->launch_hinted ? points : 0;
+    if (n_missed) *n_missed = missed;
+    return 0;
+}
+
 int h2v_batch_launch(h2v_batch* b, int with_pairing) { return launch_impl(b, with_pairing); }
 int h2v_batch_upload_launch(h2v_batch* b, size_t n, const uint8_t* proofs_flat, size_t proof_len, const uint8_t* instances_flat, size_t n_instance_columns,
                             const size_t* col_lens, const uint8_t* rand32_tail, size_t n_tail, int with_pairing) {
@@ -1040,7 +1184,7 @@ int h2v_batch_set_groups(h2v_batch* b, size_t groups) {
     if (!b || !groups || groups > MSM_MAX_PROBLEMS / 2 || groups > b->max_proofs) { set_last_error("h2v_batch_set_groups: bad group count"); return H2V_ERR_BAD_ARGUMENT; }
     wait_for_streams(b);   // (the last launch and the last upload read what changes below)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    b->groups = (uint32_t)groups; b->stage = BatchStage::Empty;  // the next upload grows the buffers if the group count needs more
+    b->groups = (uint32_t)groups; b->stage = BatchStage::Empty; b->hinted = false;  // the next upload grows the buffers if the group count needs more
     b->group_off.clear(); b->group_last.clear();   // (equal groups again after h2v_batch_set_group_sizes)
     return 0;
 }
@@ -1055,7 +1199,7 @@ int h2v_batch_set_group_sizes(h2v_batch* b, const size_t* sizes, size_t n_groups
     }
     wait_for_streams(b);   // (the last launch reads the device copies replaced below)
     if (b->plan) { ctx_put_plan(b->ctx, b->plan); b->plan = nullptr; }
-    b->groups = (uint32_t)n_groups; b->stage = BatchStage::Empty;
+    b->groups = (uint32_t)n_groups; b->stage = BatchStage::Empty; b->hinted = false;
     b->group_off.assign(n_groups + 1, 0); b->group_last.assign(total, 0);
     for (size_t g = 0; g < n_groups; ++g) { b->group_off[g + 1] = b->group_off[g] + (uint32_t)sizes[g]; b->group_last[b->group_off[g + 1] - 1] = 1; }
     // The offsets and the last-of-group marks go to the device here, where they change and every stream of the batch is idle, and

@@ -221,6 +221,9 @@ int point_to_bytes_enqueue(hipStream_t s, const G1J* d_in, uint8_t* d_out_xy64, 
 // (fault 0xffffffff, the rest 0), also when there is nothing to copy.
 int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
                         uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups);
+// k_ingest_rows the other way round (k_hint_rows_out; h2v_batch_hints_device): n packed rows of row_len bytes at d_rows into the caller's
+// rows at d_out + i * stride; every pointer, the stride and the length are multiples of 16
+int hint_rows_out_enqueue(hipStream_t s, const uint8_t* d_rows, size_t row_len, size_t n, void* d_out, size_t stride);
 // draws: n_tail 32-byte scalars d_draws -> d_tail, the scalar 1 in place of a draw >= r (k_ingest_draws); the verdict block preset by
 // ingest_rows_enqueue on the same stream takes the lowest index of such a draw and every group's zero_below (GroupShape::zero_below; the
 // n proofs and n_tail draws fit `shape`, batch.h, its offsets in device memory), and its first 1 + shape.G words go to d_host_verdict

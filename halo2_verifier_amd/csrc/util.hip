@@ -414,6 +414,26 @@ __global__ void __launch_bounds__(256) k_ingest_draws(const uint4* __restrict__ 
     if (!last) return;
     for (uint32_t t = threadIdx.x; t < 1 + shape.G; t += 256) host_verdict[t] = __hip_atomic_load(&verdict[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// k_ingest_rows (util.hip) the other way round: thread i owns 16-byte word i of the packed rows (row i / row16, word i % row16 of it)
+// and stores it into the caller's row; the bytes between the caller's rows are not touched.  One 16-byte load and store per thread.
+__global__ void __launch_bounds__(256) k_hint_rows_out(const uint4* __restrict__ rows, uint32_t row16, uint64_t rows16, uint4* __restrict__ out, uint32_t stride16) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows16) return;
+    const uint64_t r = i / row16;
+    out[r * stride16 + (i - r * row16)] = rows[i];
+}
+
+int hint_rows_out_enqueue(hipStream_t s, const uint8_t* d_rows, size_t row_len, size_t n, void* d_out, size_t stride) {
+    if (!n || !row_len) return 0;
+    if (!d_rows || !d_out) { set_last_error("hint_rows_out_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (((uintptr_t)d_rows | (uintptr_t)d_out | stride | row_len) & 15u) { set_last_error("hint_rows_out_enqueue: a pointer, the stride or the length is not a multiple of 16 bytes"); return H2V_ERR_BAD_ARGUMENT; }
+    if (stride < row_len || (stride >> 4) > 0xffffffffu) { set_last_error("hint_rows_out_enqueue: the stride is below the row length, or too large"); return H2V_ERR_BAD_ARGUMENT; }
+    const uint64_t rows16 = (uint64_t)n * (row_len >> 4);
+    if (rows16 > 0xffffff00ull) { set_last_error("hint_rows_out_enqueue: too many bytes for one launch"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_hint_rows_out, dim3((uint32_t)((rows16 + 255) / 256)), dim3(256), 0, s, (const uint4*)d_rows, (uint32_t)(row_len >> 4), rows16, (uint4*)d_out, (uint32_t)(stride >> 4));
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 int ingest_rows_enqueue(hipStream_t s, const void* d_rows, size_t stride, size_t row_len, size_t n, const void* d_inst, size_t inst_bytes, uint8_t* d_out_rows,
                         uint8_t* d_out_inst, uint32_t* d_verdict, uint32_t groups) {
     if ((n && row_len && (!d_rows || !d_out_rows)) || (inst_bytes && (!d_inst || !d_out_inst))) { set_last_error("ingest_rows_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }

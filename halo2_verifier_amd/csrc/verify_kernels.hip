@@ -2,6 +2,7 @@
 // VerifierSHPLONK::verify_proof (shplonk.rs:175-267) do before the MSMs are evaluated.
 //
 //   k_decompress      one lane per (proof, point)   G1Affine::from_bytes               transcript/mod.rs:158-166
+//   k_decompress_hinted  the same with the claimed y beside every point (include/h2v_hints.h): a curve check, the root only on a miss
 //   k_check_scalars   one lane per (proof, scalar)  Fr::from_repr canonicity           transcript/mod.rs:168-176
 //   k_stream_build    one lane per (proof, 8-byte word of the absorbed stream)         transcript/mod.rs:216-231
 //   k_transcript      four lanes per proof          Blake2b-512 + challenges           transcript/mod.rs:124-133,209-214,500-514
@@ -82,6 +83,114 @@ __global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict_
     for (int i = 0; i < 18; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 18) dp[k] = out_lds[k]; }
     __syncthreads();
     // phi(P) = (beta x, y) beside every point: the MSM's second GLV half gathers it instead of multiplying per list entry (msm.hip: msm_entry_load)
+    a.x = g1_beta_times(a.x);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out_lds[lane * 18 + i] = av[i];     // (y is still there)
+    __syncthreads();
+    dp = reinterpret_cast<uint32_t*>(phi + t0);
+#pragma unroll
+    for (int i = 0; i < 18; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 18) dp[k] = out_lds[k]; }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out_lds[lane * 8 + i] = yraw[i];
+    __syncthreads();
+    uint32_t* dy = reinterpret_cast<uint32_t*>(ycanon + (size_t)t0 * 32);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 8) dy[k] = out_lds[k]; }
+}
+
+// k_decompress with a hint per point (include/h2v_hints.h).  The encoding fixes y completely — y^2 = x^3 + 3 and the parity of the
+// canonical y is the sign flag — so the hint h is CHECKED, never trusted: it is used exactly when x < p, the identity flag is clear,
+// h < p, (h & 1) == sign and h^2 == x^3 + 3, and then h IS the canonical y that k_decompress would have found (the two roots y and
+// p - y differ in parity, p being odd).  That is two squarings, one product and a comparison instead of the ~320 products of the root.
+// BN254's G1 has prime order, so no point of the curve has y = 0 (it would have order 2): the `nz` branch of k_decompress is dead for
+// every decodable point and the hinted path needs no special case for it — a zero hint fails h^2 == x^3 + 3 like any other wrong value.
+//
+// A lane whose hint fails computes what k_decompress computes for its point, statuses included (its own copy of that body below:
+// k_decompress itself stays as it is, with its registers and its four waves per SIMD).  The branch is per lane, so the other lanes of
+// the wave wait for the root: one miss in a wave costs the wave a root, and a wave of hits costs none.  The outputs leave through the
+// same LDS transposition, every store instruction contiguous; lanes past the end shadow the last point, and every lane reaches every
+// barrier (the divergent part has none).
+//
+// hints and ycanon may be the same memory (the batch keeps its hints where the canonical y will lie): a workgroup reads the 64 rows of
+// its own lanes before it writes the same 64 rows, and no other workgroup touches them.  Hence no __restrict__ on the two.
+//
+// Misses are counted per wave: a ballot over the live lanes, and one atomic add by lane 0 only when the count is not zero.
+//
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 102 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD
+// (k_decompress beside it, as before this kernel came: 76 VGPRs, 62 SGPRs, 48 bytes of scratch, 10240 bytes of LDS, 4 waves).
+// Launch bounds and LDS: k_decompress's, 64 threads held to four waves per SIMD by a request of 10 KiB of LDS (4.5 used) — four waves
+// is also all that 102 registers allow.  The miss
+// path IS k_decompress's loop, which was measured fastest under that cap when the launch does not fill the chip (see its comment), and
+// a sender of bad hints is promised that speed.  The hit path is too short for the cap to bind at the sizes measured: the 1920 waves of
+// the headline launch are all resident at once under four waves per SIMD (4096 places).  Whether the dispatcher's packing matters to
+// an all-hit launch was not measured apart from that.
+#define K_DECOMPRESS_HINTED_LDS_WORDS 2560
+__global__ void __launch_bounds__(64, 4) k_decompress_hinted(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
+                                                          uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, const uint8_t* hints,
+                                                          uint8_t* ycanon, int* __restrict__ status, uint32_t* __restrict__ misses) {
+    const uint32_t total = n * np;
+    const uint32_t t_raw = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t t = min(t_raw, total - 1);   // lanes past the end shadow the last point (all lanes reach the barriers below); their output is not stored
+    const uint32_t p = t / np, slot = t % np;
+    const uint4* src = reinterpret_cast<const uint4*>(proofs + (size_t)p * proof_len + point_offsets[slot]);
+    const uint4 lo = src[0], hi = src[1];
+    const uint4* hsrc = reinterpret_cast<const uint4*>(hints + (size_t)t * 32);
+    const uint4 hlo = hsrc[0], hhi = hsrc[1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t yraw[8] = {hlo.x, hlo.y, hlo.z, hlo.w, hhi.x, hhi.y, hhi.z, hhi.w};   // the hint; on a hit, the canonical y as it is
+    // G1Affine::from_bytes (compressed): flags in the top byte, x below
+    const bool is_inf = (w[7] >> 24) & G1_FLAG_IDENTITY, sign = (w[7] >> 24) & G1_FLAG_SIGN;
+    w[7] &= 0x3fffffffu;
+    G1A a = G1A::identity();
+    // the identity decodes (x = 0, no sign) but cannot be absorbed: an error either way (k_decompress)
+    bool ok = !Fq::geq_p(w) && !is_inf;
+    bool hit = false;
+    Fq x = Fq::zero(), rhs = Fq::zero();
+    if (ok) {
+        x = Fq::from_raw(w);
+        const Fq three = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
+        rhs = x.sqr() * x + (three + three + three);
+        if (!Fq::geq_p(yraw) && (bool)(yraw[0] & 1u) == sign) {
+            const Fq h = Fq::from_raw(yraw);
+            if (h.sqr() == rhs) { hit = true; a.x = x; a.y = h; }
+        }
+    }
+    const unsigned long long missed = __ballot(!hit && t_raw < total);
+    if (missed && threadIdx.x == 0) atomicAdd(misses, (uint32_t)__popcll(missed));
+    if (!hit) {
+        // k_decompress's body for this point, from the root on
+        if (ok) {
+            Fq y = fq_sqrt_candidate_loop_w3(rhs);
+            if (y.sqr() != rhs) ok = false;
+            else {
+                y.to_raw(yraw);                       // canonical y: its parity decides the sign, its bytes are absorbed
+                uint32_t nz = 0;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) nz |= yraw[i];
+                if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
+                    y = y.neg();
+                    uint64_t borrow = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)FqParams::P(i) - yraw[i] - borrow; yraw[i] = (uint32_t)d; borrow = (d >> 32) & 1u; }
+                }
+                a.x = x; a.y = y;
+            }
+        }
+        if (!ok) { status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING); a = G1A::identity(); for (int i = 0; i < 8; ++i) yraw[i] = 0; }
+    }
+    // outputs through LDS, as k_decompress writes them: every store instruction writes 256 contiguous bytes
+    __shared__ uint32_t out_lds[K_DECOMPRESS_HINTED_LDS_WORDS];
+    const uint32_t lane = threadIdx.x, t0 = blockIdx.x * blockDim.x, live = min(64u, total - t0);
+    const uint32_t* av = reinterpret_cast<const uint32_t*>(&a);
+#pragma unroll
+    for (int i = 0; i < 18; ++i) out_lds[lane * 18 + i] = av[i];
+    __syncthreads();
+    uint32_t* dp = reinterpret_cast<uint32_t*>(pts + t0);
+#pragma unroll
+    for (int i = 0; i < 18; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 18) dp[k] = out_lds[k]; }
+    __syncthreads();
+    // phi(P) = (beta x, y) beside every point (msm.hip: msm_entry_load)
     a.x = g1_beta_times(a.x);
 #pragma unroll
     for (int i = 0; i < 9; ++i) out_lds[lane * 18 + i] = av[i];     // (y is still there)
@@ -794,6 +903,7 @@ __global__ void __launch_bounds__(64) k_fold_ranges(const FoldRange* __restrict_
 // ------------------------------------------------------------------ launchers
 int decompress_begin_enqueue(hipStream_t s, const StageArgs& g) {
     if (g.n) H2V_HIP_CHECK(hipMemsetAsync(g.status, 0, sizeof(int) * g.n, s));
+    if (g.n && g.hints && g.hint_misses) H2V_HIP_CHECK(hipMemsetAsync(g.hint_misses, 0, sizeof(uint32_t), s));   // (a stage with hints: the misses of its pieces add up)
     return 0;
 }
 int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1) {
@@ -801,8 +911,21 @@ int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uin
     const Plan& pl = *g.plan;
     const uint32_t m = p1 - p0, tp = m * pl.n_points;
     if (!tp) return 0;
+    if (g.hints) return decompress_hinted_range_enqueue(s, g, p0, p1);   // k_decompress_hinted: the same outputs, a square root only where a hint fails
     hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, m,
                        g.pts + (size_t)p0 * pl.n_points, g.phi + (size_t)p0 * pl.n_points, g.ycanon + (size_t)p0 * pl.n_points * 32, g.status + p0);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1) {
+    if (p1 <= p0) return 0;
+    const Plan& pl = *g.plan;
+    const uint32_t m = p1 - p0, tp = m * pl.n_points;
+    if (!tp) return 0;
+    if (!g.hints || !g.hint_misses) { set_last_error("decompress_hinted_range_enqueue: hints without a miss word"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t off = (size_t)p0 * pl.n_points;   // the hints' rows are the points': offset by p0 exactly as ycanon is
+    hipLaunchKernelGGL(k_decompress_hinted, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p, pl.n_points,
+                       pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1529,6 +1529,37 @@ class Batch:
         from . import guards
         return guards.guards_append(self, left, right, first, count)
 
+    # ---- point hints (include/h2v_hints.h; hints.py holds the binding and says what a hint is): they change a launch's time, never its results
+    def set_hints(self, y32):
+        """The claimed y of every point of the current upload, n * n_points * 32 bytes in the proofs' byte order (hints.for_proofs), or
+        None to drop them.  The batch must be uploaded and not launched since; every launch of the upload then checks the hints
+        instead of taking square roots, and takes the root where a hint does not hold."""
+        from . import hints
+        return hints.set_hints(self, y32)
+
+    def set_hints_tensor(self, t):
+        """set_hints from a uint8 tensor [n, 32 * n_points] on the batch's device (row stride a multiple of 16), device -> device on
+        the batch's stream, which is made to wait for the tensor's current stream; no host wait."""
+        from . import hints
+        return hints.set_hints_tensor(self, t)
+
+    def hints(self, first=0, count=None):
+        """The canonical y of the points of proofs [first, first + count) of the last launch, count * n_points * 32 bytes (zeros for a
+        point that did not decode): hints for the next verifier of the same proofs."""
+        from . import hints
+        return hints.hints(self, first, count)
+
+    def hints_into(self, t, first=0, count=None):
+        """hints() into a uint8 tensor [count, 32 * n_points] on the batch's device (row stride a multiple of 16), by one kernel on the
+        batch's stream; the tensor's current stream is made to wait for it, the host for nothing."""
+        from . import hints
+        return hints.hints_into(self, t, first, count)
+
+    def hint_stats(self):
+        """-> (n_points, n_hinted, n_missed) of the last launch: n * n_points; the same if the launch had hints, else 0; the hints not used"""
+        from . import hints
+        return hints.hint_stats(self)
+
     def recheck(self, ranges):
         """The pairing checks of ranges of proofs of the last finished launch, on its resident scalars (h2v_batch_recheck).
         ranges: list of (first, count), each inside one group of the launch.  -> (oks, lefts, rights): one verdict and the two
