@@ -39,6 +39,7 @@
 // k_leg_weights (verify_kernels.hip) makes the scalars, one k_accumulator_scale launch of G + 1 items the records, k_accumulator_legs_fold
 // (util.hip) the journal's G entries and the accumulator, as the last step.
 #include "../../include/h2v.h"
+#include "../../include/h2v_hint_rows.h"
 #include "batch.h"
 #include "msm_object.h"
 #include <string.h>
@@ -200,10 +201,10 @@ void h2v_accumulator_destroy(h2v_accumulator* a) {
     delete a;
 }
 
-int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
-                            const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
-                            const uint8_t* rand32, int* per_proof_status, int* all_ok) {
-    const char* who = "h2v_accumulator_process";
+// h2v_accumulator_process, with or without hint rows (h2v_accumulator_process_hinted, include/h2v_hints.h)
+static int process_proofs(const char* who, h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                          const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                          const uint8_t* rand32, int* per_proof_status, int* all_ok, const CallHints& hints) {
     // every argument check comes before the first HIP call
     if (!a || (n && !key_of_proof)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     std::vector<CallGroup> groups;
@@ -234,7 +235,7 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     GroupsHeldPtr held;   // the contexts' locks and scratch batches, until the call returns
     std::vector<std::vector<int>> st;
     bool groups_ok = true;
-    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, a->records.p + H2V_ACC_RECORD_BYTES, false, held, st, groups_ok))) return rc;
+    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, a->records.p + H2V_ACC_RECORD_BYTES, false, held, st, groups_ok, hints))) return rc;
     // the journal's entry: the groups' records alone, into a slot no entry owns yet
     if (G1J* slot = next_slot(a))
         if ((rc = fold_records_enqueue(a->stream, a->records.p + H2V_ACC_RECORD_BYTES, (uint32_t)groups.size(), 1, 1, 0, slot, nullptr, nullptr, a->words.p + 6))) return rc;
@@ -252,6 +253,21 @@ int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_k
     commit_entry(a, M, n, failed);
     if (all_ok) *all_ok = failed ? 0 : 1;
     return 0;
+}
+int h2v_accumulator_process(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                            const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                            const uint8_t* rand32, int* per_proof_status, int* all_ok) {
+    return process_proofs("h2v_accumulator_process", a, ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, per_proof_status,
+                          all_ok, CallHints());
+}
+int h2v_accumulator_process_hinted(h2v_accumulator* a, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
+                                   const size_t* proof_lens, const uint8_t* const* hint_rows, const uint8_t* const* instances32, const size_t* n_instance_columns,
+                                   const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* all_ok, size_t hint_stats[3]) {
+    size_t stats[3] = {0, 0, 0};
+    const int rc = process_proofs("h2v_accumulator_process_hinted", a, ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32,
+                                  per_proof_status, all_ok, CallHints{hint_rows, hint_stats ? stats : nullptr});
+    if (!rc && hint_stats) memcpy(hint_stats, stats, sizeof stats);
+    return rc;
 }
 
 // n x (scale by the draw, add the Guard), the Guards supplied by the caller: process with the groups' chains replaced by one conversion of

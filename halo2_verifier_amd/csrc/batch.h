@@ -83,6 +83,11 @@ struct StageArgs {
     // decompress_range_enqueue launches k_decompress as ever.
     uint32_t* hint_misses = nullptr;
     const uint8_t* hints = nullptr;
+    // the miss list of a stage with hints: one word per point of the stage, and the word that counts a piece's entries (cleared on the
+    // stream by every decompress_hinted_range_enqueue).  Given: a wave with a hit and a miss lists its misses, and k_decompress_misses
+    // takes their roots densely right behind.  Null: every miss takes its root in place.
+    uint32_t* miss_list = nullptr;
+    uint32_t* miss_list_count = nullptr;
 };
 
 // the decompression stage in pieces (h2v_batch_upload_launch runs them around its copies): reset the status words; decompress the points of proofs [p0, p1); check the
@@ -91,7 +96,7 @@ int decompress_begin_enqueue(hipStream_t s, const StageArgs& g);
 int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
 // k_decompress_hinted over the proofs [p0, p1) of a stage with hints: decompress_range_enqueue's other branch (the miss word is cleared by
-// decompress_begin_enqueue or by the launch)
+// decompress_begin_enqueue or by the launch); with a miss list, k_decompress_misses behind it.  Either way the call leaves its range complete.
 int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // The groups of one upload: which proofs and which draws belong to group g.  One plain struct for host code and kernels (a kernel
@@ -270,9 +275,12 @@ typedef std::unique_ptr<GroupsHeld, GroupsHeldDelete> GroupsHeldPtr;
 int grouped_call_args(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
                       const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
                       std::vector<CallGroup>& groups);
+// the point hints of a _hinted call (include/h2v_hints.h): rows[i] is proof i's row or null, in call order (null: a call without hints);
+// stats: three counters to which every launch of the call adds its h2v_batch_hint_stats (null: not asked for)
+struct CallHints { const uint8_t* const* rows = nullptr; size_t* stats = nullptr; };
 int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
                       const uint8_t* const* instances32, const uint8_t* rand32, uint8_t* d_records, bool resident, GroupsHeldPtr& held,
-                      std::vector<std::vector<int>>& st, bool& all_ok);
+                      std::vector<std::vector<int>>& st, bool& all_ok, const CallHints& hints = CallHints());
 }  // namespace h2v
 
 struct h2v_batch {
@@ -289,8 +297,13 @@ struct h2v_batch {
     // point hints (include/h2v_hints.h).  hinted: h2v_batch_set_hints has put the claimed y of the upload's points into `ycanon`, where
     // k_decompress_hinted reads them and writes the canonical y back; set there, cleared by upload_take and by every way to Empty, never
     // inferred from the buffer.  launch_hinted: the last launch ran with hints, and hint_misses[0] counts the ones it did not use.
+    // hint_misses[1] counts the entries of a piece's segment of miss_list (StageArgs::miss_list: one word per point `ycanon` holds),
+    // which every hinted launch is given.  null_rows: the proofs whose hint row h2v_batch_set_hint_rows staged as zeros because the
+    // caller gave none (0 after h2v_batch_set_hints / _device); launch_null_rows: the same of the last launch.  h2v_batch_hint_stats
+    // counts neither as hinted nor as missed the Np points of each of them.
     bool hinted = false, launch_hinted = false;
-    h2v::DevBuf<uint32_t> hint_misses;
+    uint32_t null_rows = 0, launch_null_rows = 0;
+    h2v::DevBuf<uint32_t> hint_misses, miss_list;
     h2v::LaunchRecord last;
     size_t max_proofs = 0, max_inst = 0;
     h2v::PlanDevice* plan = nullptr;  // set at upload (depends on the instance shape)

@@ -1,6 +1,7 @@
 // C-ABI staged batch (include/h2v.h, h2v_batch_*): upload / launch / finish, range re-checks, export and fold.  The one-shot entry
 // points (oneshot.hip) run on it through the steps batch.h declares.
 #include "../../include/h2v.h"
+#include "../../include/h2v_hint_rows.h"
 #include "batch.h"
 #include "msm_object.h"
 #include <string.h>
@@ -249,7 +250,8 @@ int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storag
 // what the decompression and transcript stages work on: the batch's upload (its plan and n) and its buffers
 static StageArgs stage_args(const h2v_batch* b) {
     StageArgs g{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
-    if (b->hinted) { g.hint_misses = b->hint_misses.p; g.hints = b->ycanon.p; }   // (h2v_batch_set_hints: the hints wait where the canonical y will lie)
+    // (h2v_batch_set_hints: the hints wait where the canonical y will lie; the miss list and its counter: hints_reserve)
+    if (b->hinted) { g.hint_misses = b->hint_misses.p; g.hints = b->ycanon.p; g.miss_list = b->miss_list.p; g.miss_list_count = b->hint_misses.p + 1; }
     return g;
 }
 
@@ -526,7 +528,8 @@ int launch_impl(h2v_batch* b, int with_pairing, const Fr* ext_mult, const uint32
     mark();
     if ((rc = close_enqueue(b, with_pairing != 0))) return rc;
     b->last.folded = false;
-    b->launch_hinted = hinted;
+    b->launch_hinted = hinted; b->launch_null_rows = hinted ? b->null_rows : 0;
+    if (hinted) b->null_rows = 0;   // (a relaunch of this upload finds the canonical y of ALL its points where the rows lay: every point hinted)
     mark();
     commit.commit(BatchStage::Launched);
     return 0;
@@ -1053,6 +1056,13 @@ int hints_range_check(const h2v_batch* b, const char* who, size_t first, size_t 
     if (first > b->n || count > b->n - first) { set_last_error(std::string(who) + ": a range outside the upload"); return H2V_ERR_BAD_ARGUMENT; }
     return 0;
 }
+// what every hinted launch needs beside the hints: the miss word and the list counter, and a list word per point `ycanon` holds
+// (grow-only, like every buffer of the batch: it grows only when ycanon has grown)
+int hints_reserve(h2v_batch* b) {
+    int rc;
+    if ((rc = b->hint_misses.reserve(2)) || (rc = b->miss_list.reserve(b->ycanon.cap / 32))) return rc;
+    return 0;
+}
 int strided_rows_check(const char* who, const void* d, size_t rows, size_t row_len, size_t row_stride, int device, const char* does) {
     if (row_stride < row_len || (row_stride & 15u) || (row_stride >> 4) > 0xffffffffu) { set_last_error(std::string(who) + ": row_stride is below 32 x n_points, or no multiple of 16"); return H2V_ERR_BAD_ARGUMENT; }
     return device_range_check(d, (rows - 1) * row_stride + row_len, device, "d_y32", who, does);
@@ -1093,14 +1103,38 @@ int h2v_batch_set_hints(h2v_batch* b, size_t n, const uint8_t* y32) {
     if (!y32) { b->hinted = false; return 0; }
     H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
     StageCommit commit{b};   // device work from here on: a failure of it leaves the batch Empty like any other
-    if (int rc = b->hint_misses.reserve(1)) return rc;
+    if (int rc = hints_reserve(b)) return rc;
     const size_t bytes = (size_t)n * b->plan->host.n_points * 32;
     if (bytes) {
         H2V_HIP_CHECK(hipMemcpyAsync(b->ycanon.p, y32, bytes, hipMemcpyHostToDevice, b->stream));
         H2V_HIP_CHECK(hipStreamSynchronize(b->stream));   // the host buffer is the caller's again
     }
     commit.commit(BatchStage::Uploaded);
-    b->hinted = true;
+    b->hinted = true; b->null_rows = 0;
+    return 0;
+}
+
+// A row per proof, or none: the rows given are packed beside zero rows for the others (a zero hint always misses: no point of the
+// curve has y = 0), and the whole goes where h2v_batch_set_hints puts its rows.  An upload none of whose proofs has a row has no hints.
+int h2v_batch_set_hint_rows(h2v_batch* b, size_t n, const uint8_t* const* rows) {
+    static const char who[] = "h2v_batch_set_hint_rows";
+    if (int rc = set_hints_check(b, who, n)) return rc;
+    if (!rows) { b->hinted = false; return 0; }
+    const size_t row_len = (size_t)b->plan->host.n_points * 32;
+    std::vector<uint8_t> flat(n * row_len, 0);
+    size_t null_rows = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (rows[i]) { if (row_len) memcpy(&flat[i * row_len], rows[i], row_len); } else ++null_rows;
+    if (null_rows == n) { b->hinted = false; return 0; }
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};   // device work from here on: a failure of it leaves the batch Empty like any other
+    if (int rc = hints_reserve(b)) return rc;
+    if (!flat.empty()) {
+        H2V_HIP_CHECK(hipMemcpyAsync(b->ycanon.p, flat.data(), flat.size(), hipMemcpyHostToDevice, b->stream));
+        H2V_HIP_CHECK(hipStreamSynchronize(b->stream));   // (flat goes with this call)
+    }
+    commit.commit(BatchStage::Uploaded);
+    b->hinted = true; b->null_rows = (uint32_t)null_rows;
     return 0;
 }
 
@@ -1114,9 +1148,9 @@ int h2v_batch_set_hints_device(h2v_batch* b, size_t n, const void* d_y32, size_t
     H2V_HIP_CHECK(hipSetDevice(device));
     if (n && row_len && (rc = strided_rows_check(who, d_y32, n, row_len, row_stride, device, "reads"))) return rc;
     StageCommit commit{b};
-    if ((rc = b->hint_misses.reserve(1)) || (rc = ingest_rows_enqueue(b->stream, d_y32, row_stride, row_len, n, nullptr, 0, b->ycanon.p, nullptr, nullptr, 0))) return rc;
+    if ((rc = hints_reserve(b)) || (rc = ingest_rows_enqueue(b->stream, d_y32, row_stride, row_len, n, nullptr, 0, b->ycanon.p, nullptr, nullptr, 0))) return rc;
     commit.commit(BatchStage::Uploaded);
-    b->hinted = true;
+    b->hinted = true; b->null_rows = 0;
     return 0;
 }
 
@@ -1165,8 +1199,10 @@ int h2v_batch_hint_stats(h2v_batch* b, size_t* n_points, size_t* n_hinted, size_
     commit.commit(stage);
     const size_t points = (size_t)b->n * b->plan->host.n_points;
     if (n_points) *n_points = points;
-    if (n_hinted) *n_hinted = b->launch_hinted ? points : 0;
-    if (n_missed) *n_missed = missed;
+    // (the points of proofs without a row were staged as zero hints and all missed: neither hinted nor missed)
+    const size_t unhinted = (size_t)b->launch_null_rows * b->plan->host.n_points;
+    if (n_hinted) *n_hinted = b->launch_hinted ? points - unhinted : 0;
+    if (n_missed) *n_missed = b->launch_hinted ? missed - unhinted : 0;
     return 0;
 }
 

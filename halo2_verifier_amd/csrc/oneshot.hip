@@ -1,6 +1,7 @@
 // C-ABI one-shot verification entry points (include/h2v.h): h2v_verify_batch and its _seeded / _shapes / _keys / _identify / _keys_identify forms,
 // h2v_verify_each, h2v_guard_msm and h2v_fold_check.  Each call runs on its context's scratch batch through the staged batch of batch.hip.
 #include "../../include/h2v.h"
+#include "../../include/h2v_hint_rows.h"
 #include "batch.h"
 #include <string.h>
 #include <algorithm>
@@ -25,6 +26,10 @@ struct ScratchBatch {
     std::vector<size_t> cols;           // and its column lengths
     std::vector<uint8_t> flat, iflat;   // the proofs and their instances, proof after proof
     std::vector<int> forced;            // per proof: the status fixed on the host (a short proof), or 0
+    // point hints (include/h2v_hints.h; a _hinted call): per packed proof its hint row where the caller holds it, or null (none given, or
+    // a short proof); empty in a call without hints.  hstats: where the call sums its launches' h2v_batch_hint_stats, or null
+    std::vector<const uint8_t*> hrows;
+    size_t* hstats = nullptr;
     explicit ScratchBatch(h2v_ctx* c) : ctx(c), lock(c->mu), pin(c) {}
     ~ScratchBatch() { if (b && b->max_proofs <= H2V_SCRATCH_BATCH_MAX && !ctx->scratch_batch) ctx->scratch_batch = b; else h2v_batch_destroy(b); }
     int take(size_t capacity, size_t max_inst) {   // the context's batch, or a new one if it has none or a smaller one (once per holder)
@@ -37,9 +42,9 @@ struct ScratchBatch {
 // The argument checks of a one-shot call over one instance shape, its plan (in `sb.pin`), and its pointer-array proofs / instances packed
 // into the flat layout (in `sb`): proof i is proofs[idx[i]] (idx null: proofs[i]).  Proofs shorter than the VK's proof are the reader
 // running dry: "failed to fill whole buffer" -> Error::Transcript, or Opening inside the multi-open part (pl.opening_offset: h1, the first
-// point after all scalars)
+// point after all scalars).  hints: the call's hint rows, indexed like the proofs, and its counters (a call without hints: neither)
 int pack_inputs(ScratchBatch& sb, size_t n, const size_t* idx, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
-                size_t ncols, const size_t* col_lens) {
+                size_t ncols, const size_t* col_lens, const CallHints& hints = CallHints()) {
     if ((n && (!proofs || !proof_lens)) || (ncols && !col_lens)) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (sb.ctx->vk && ncols != ctx_total_instance_columns(sb.ctx)) { set_last_error("instances do not match the VK's instance column count"); return H2V_ERR_INVALID_INSTANCES; }
     sb.cols.assign(col_lens, col_lens + ncols);
@@ -47,6 +52,7 @@ int pack_inputs(ScratchBatch& sb, size_t n, const size_t* idx, const uint8_t* co
     const Plan& pl = sb.pin.pd->host;
     const size_t per_inst = (size_t)pl.n_instance_values * 32;
     sb.flat.assign(n * pl.proof_len, 0); sb.iflat.assign(n * per_inst, 0); sb.forced.assign(n, 0);
+    sb.hrows.assign(hints.rows ? n : 0, nullptr); sb.hstats = hints.stats;
     for (size_t i = 0; i < n; ++i) {
         const size_t j = idx ? idx[i] : i;
         if (!proofs[j]) { set_last_error("null proof pointer"); return H2V_ERR_BAD_ARGUMENT; }
@@ -55,7 +61,10 @@ int pack_inputs(ScratchBatch& sb, size_t n, const size_t* idx, const uint8_t* co
             // contributes nothing, and the status is set to what the reference reports for the place where it ran dry
             sb.forced[i] = proof_lens[j] < pl.opening_offset ? H2V_ERR_TRANSCRIPT : H2V_ERR_OPENING;
             memset(&sb.flat[i * pl.proof_len], 0xff, pl.proof_len);
-        } else memcpy(&sb.flat[i * pl.proof_len], proofs[j], pl.proof_len);
+        } else {
+            memcpy(&sb.flat[i * pl.proof_len], proofs[j], pl.proof_len);
+            if (hints.rows) sb.hrows[i] = hints.rows[j];   // (a short proof keeps none: the batch stages a zero row for it)
+        }
         if (per_inst) { if (!instances32 || !instances32[j]) { set_last_error("null instances pointer"); return H2V_ERR_BAD_ARGUMENT; } memcpy(&sb.iflat[i * per_inst], instances32[j], per_inst); }
     }
     return 0;
@@ -70,14 +79,18 @@ std::vector<uint8_t> unit_draws(size_t n) {
 
 // Packed proofs on a batch (the scratch batch, or one the call made for itself), first half: proofs [off, off + m) of `sb` as `groups`
 // groups on b, uploaded with the draws rand32 (null: OS draws) and launched with or without the pairing checks, the multipliers gathered
-// from mult[idx[..]] if mult is given.  Nothing waits.
+// from mult[idx[..]] if mult is given.  Nothing waits (but the copy of the hint rows of a call that has them).
+// The hint rows of the packed proofs [off, off + m) onto b's upload of them, through the staged batch's own setter; a call without hints: nothing
+int place_hints(const ScratchBatch& sb, h2v_batch* b, size_t off, size_t m) {
+    return sb.hrows.empty() ? 0 : h2v_batch_set_hint_rows(b, m, sb.hrows.data() + off);
+}
 int enqueue_group(const ScratchBatch& sb, h2v_batch* b, size_t off, size_t m, size_t groups, const uint8_t* rand32, int with_pairing, bool guard = false,
                   const Fr* mult = nullptr, const uint32_t* idx = nullptr) {
     const Plan& pl = sb.pin.pd->host;
     int rc;
     if ((rc = h2v_batch_set_groups(b, groups)) ||
         (rc = upload_impl(b, m, sb.flat.data() + off * pl.proof_len, pl.proof_len, sb.iflat.data() + off * (size_t)pl.n_instance_values * 32, sb.cols.size(), sb.cols.data(),
-                          rand32, m, false, guard))) return rc;
+                          rand32, m, false, guard)) || (rc = place_hints(sb, b, off, m))) return rc;
     return launch_impl(b, with_pairing, mult, idx);
 }
 
@@ -87,15 +100,20 @@ int collect_group(const ScratchBatch& sb, h2v_batch* b, size_t off, int* st, int
     if (int rc = h2v_batch_finish_groups(b, st, group_ok, out_left, out_right, b->groups)) return rc;
     for (uint32_t i = 0; i < b->n; ++i)
         if (const int v = sb.forced[off + i]) { if (st) st[i] = v; if (group_ok) group_ok[group_shape(b).of(i)] = 0; }
+    if (sb.hstats) {   // a _hinted call that asked for its counters: this launch's
+        size_t c[3];
+        if (int rc = h2v_batch_hint_stats(b, &c[0], &c[1], &c[2])) return rc;
+        for (int k = 0; k < 3; ++k) sb.hstats[k] += c[k];
+    }
     return 0;
 }
 
 // One AccumulatorStrategy batch of a one-shot call, packed and run on the context's scratch batch; the batch stays in `sb` for the caller
 int pack_and_run(ScratchBatch& sb, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t ncols,
                  const size_t* col_lens, const uint8_t* rand32, int with_pairing, bool guard, int* per_proof_status, int* batch_ok, uint8_t* out_left,
-                 uint8_t* out_right) {
+                 uint8_t* out_right, const CallHints& hints = CallHints()) {
     int rc;
-    if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, ncols, col_lens)) || (rc = sb.take(n ? n : 1, sb.pin.pd->host.n_instance_values)) ||
+    if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, ncols, col_lens, hints)) || (rc = sb.take(n ? n : 1, sb.pin.pd->host.n_instance_values)) ||
         (rc = enqueue_group(sb, sb.b, 0, n, 1, rand32, with_pairing, guard))) return rc;
     return collect_group(sb, sb.b, 0, per_proof_status, batch_ok, out_left, out_right);
 }
@@ -290,7 +308,7 @@ int grouped_call_args(const char* who, h2v_ctx* const* ctxs, size_t n_keys, cons
 // for the call (held->own, destroyed with `held`).
 int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
                       const uint8_t* const* instances32, const uint8_t* rand32, uint8_t* d_records, bool resident, GroupsHeldPtr& held,
-                      std::vector<std::vector<int>>& st, bool& all_ok) {
+                      std::vector<std::vector<int>>& st, bool& all_ok, const CallHints& hints) {
     held.reset(new GroupsHeld);
     // every context's lock and scratch batch for the whole call, taken in one global order (by address): calls over overlapping sets of
     // contexts cannot deadlock
@@ -365,7 +383,7 @@ int run_group_batches(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<Cal
             const CallGroup& grp = groups[gi];
             ScratchBatch& sb = *hold[kv.first];
             const size_t m = grp.idx.size();
-            if ((rc = pack_inputs(sb, m, grp.idx.data(), proofs, proof_lens, instances32, grp.shape.size(), grp.shape.data())) ||
+            if ((rc = pack_inputs(sb, m, grp.idx.data(), proofs, proof_lens, instances32, grp.shape.size(), grp.shape.data(), hints)) ||
                 (rc = own_draws ? enqueue_group(sb, on[gi], 0, m, 1, rand32, 0)
                                 : enqueue_group(sb, on[gi], 0, m, 1, unit_draws(m).data(), 0, false, d_mult.p, d_idx.p + idx_off[gi])) ||
                 (rc = export_whole_records(on[gi], d_records + gi * H2V_ACC_RECORD_BYTES))) return rc;
@@ -391,7 +409,7 @@ namespace {
 // failing proofs are searched for over all groups at once (identify_search); the number of range checks it ran is ADDED to *n_checks.
 int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>& groups, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
                const uint8_t* const* instances32, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy,
-               size_t* n_checks = nullptr) {
+               size_t* n_checks = nullptr, const CallHints& hints = CallHints()) {
     h2v_ctx* fold_ctx = ctxs[groups[0].key];
     int rc;
     DevBuf<uint8_t> d_records;
@@ -400,7 +418,7 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
     GroupsHeldPtr held;   // (declared after d_records: the batches go, and the contexts are released, before the records are freed)
     std::vector<std::vector<int>> st;
     bool all_ok = true;
-    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, d_records.p, n_checks != nullptr, held, st, all_ok))) return rc;
+    if ((rc = run_group_batches(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, d_records.p, n_checks != nullptr, held, st, all_ok, hints))) return rc;
     int ok = 0, pairing_ok = 0;
     if ((rc = fold_check_locked(fold_ctx, d_records.p, groups.size(), &ok, out_left_xy, out_right_xy, &pairing_ok))) return rc;
     // identification: only a failing pairing has failing proofs to find (a proof with a non-zero status contributes nothing to it)
@@ -412,12 +430,20 @@ int run_groups(h2v_ctx* const* ctxs, size_t n_keys, const std::vector<CallGroup>
     return 0;
 }
 
+// h2v_verify_batch on a context the caller has checked, with or without hint rows
+int verify_one(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
+               const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, const CallHints& hints) {
+    ScratchBatch sb(ctx);
+    return pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, per_proof_status, batch_ok, out_left_xy, out_right_xy, hints);
+}
+
 // h2v_verify_batch_keys, and h2v_verify_batch_shapes as its call with one context (key_of_proof NULL: every proof is of key 0).  `who`
 // names the entry point in the error messages.  n_checks (h2v_verify_batch_keys_identify): identification as well — the draws must be
 // non-zero, and the number of range checks is written there; one group is h2v_verify_batch_identify's case.
 int verify_grouped(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
                    const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens, const uint8_t* rand32,
-                   int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t* n_checks = nullptr) {
+                   int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t* n_checks = nullptr,
+                   const CallHints& hints = CallHints()) {
     // every argument check comes before the first HIP call
     std::vector<CallGroup> groups;
     int rc;
@@ -436,11 +462,11 @@ int verify_grouped(const char* who, h2v_ctx* const* ctxs, size_t n_keys, const u
         *n_checks = checks;
         return 0;
     }
-    if (groups.size() == 1)   // one key, one shape: the proofs are that group, in call order
-        return h2v_verify_batch(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32,
-                                per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    if (groups.size() == 1)   // one key, one shape: the proofs are that group, in call order: h2v_verify_batch
+        return verify_one(ctxs[groups[0].key], n, proofs, proof_lens, instances32, groups[0].shape.size(), groups[0].shape.data(), rand32,
+                          per_proof_status, batch_ok, out_left_xy, out_right_xy, hints);
     if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
-    return run_groups(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    return run_groups(ctxs, n_keys, groups, n, proofs, proof_lens, instances32, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy, nullptr, hints);
 }
 
 }  // namespace
@@ -456,8 +482,7 @@ int h2v_fold_check(h2v_ctx* ctx, const void* device_accumulators, size_t n_parts
 int h2v_verify_batch(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32, size_t n_instance_columns,
                      const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64]) {
     if (!ctx) { set_last_error("null argument"); return H2V_ERR_BAD_ARGUMENT; }
-    ScratchBatch sb(ctx);
-    return pack_and_run(sb, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, 1, false, per_proof_status, batch_ok, out_left_xy, out_right_xy);
+    return verify_one(ctx, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, per_proof_status, batch_ok, out_left_xy, out_right_xy, CallHints());
 }
 
 // AccumulatorStrategy::with(msm_accumulator) (kzg/strategy.rs:75-78): the strategy starts from an existing DualMSM — the
@@ -576,6 +601,18 @@ int h2v_verify_batch_keys(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* k
                           per_proof_status, batch_ok, out_left_xy, out_right_xy);
 }
 
+// (include/h2v_hints.h)  The counters are the call's own until it has succeeded
+int h2v_verify_batch_keys_hinted(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs, const size_t* proof_lens,
+                                 const uint8_t* const* hint_rows, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
+                                 const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64], size_t hint_stats[3]) {
+    if (n && !key_of_proof) { set_last_error("h2v_verify_batch_keys_hinted: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    size_t stats[3] = {0, 0, 0};
+    const int rc = verify_grouped("h2v_verify_batch_keys_hinted", ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32,
+                                  per_proof_status, batch_ok, out_left_xy, out_right_xy, nullptr, CallHints{hint_rows, hint_stats ? stats : nullptr});
+    if (!rc && hint_stats) memcpy(hint_stats, stats, sizeof stats);
+    return rc;
+}
+
 int h2v_verify_batch_keys_identify(h2v_ctx* const* ctxs, size_t n_keys, const uint32_t* key_of_proof, size_t n, const uint8_t* const* proofs,
                                    const size_t* proof_lens, const uint8_t* const* instances32, const size_t* n_instance_columns, const size_t* col_lens,
                                    const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t out_left_xy[64], uint8_t out_right_xy[64],
@@ -636,10 +673,9 @@ int h2v_verify_each(h2v_ctx* ctx, size_t n, const uint8_t* const* proofs, const 
 // at which a grouped launch has long reached its rate (20 x 1024 proofs: DESIGN.md section 6) and whose buffers a context holds anyway for a
 // batch of that size; a batch above it runs alone, as one equal group — exactly h2v_verify_batch's launch.
 #define H2V_BATCHES_LAUNCH_PROOFS 16384u
-int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
-                       size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy,
-                       uint8_t* out_right_xy) {
-    static const char who[] = "h2v_verify_batches";
+static int verify_batches(const char* who, h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes, const uint8_t* const* proofs, const size_t* proof_lens,
+                          const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok,
+                          uint8_t* out_left_xy, uint8_t* out_right_xy, const CallHints& hints) {
     if (!ctx || (n_batches && (!batch_sizes || !batch_ok))) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     size_t n = 0;
     for (size_t i = 0; i < n_batches; ++i) {
@@ -651,7 +687,7 @@ int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes
     std::vector<uint8_t> os_rand;
     if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
     ScratchBatch sb(ctx);
-    if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, n_instance_columns, col_lens))) return rc;
+    if ((rc = pack_inputs(sb, n, nullptr, proofs, proof_lens, instances32, n_instance_columns, col_lens, hints))) return rc;
     const Plan& pl = sb.pin.pd->host;
     // the launches: [first batch, batches, first proof, proofs].  A launch is closed by the batch count, by the proof budget, and where the
     // next batch would take the launch's MSM problems, cut into sub-problems, past what a launch holds — the rule an upload of unequal
@@ -673,11 +709,27 @@ int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes
         if ((rc = c.k == 1 ? h2v_batch_set_groups(sb.b, 1) : h2v_batch_set_group_sizes(sb.b, batch_sizes + c.i0, c.k)) ||
             (rc = upload_impl(sb.b, c.m, sb.flat.data() + c.off * pl.proof_len, pl.proof_len, sb.iflat.data() + c.off * (size_t)pl.n_instance_values * 32, sb.cols.size(),
                               sb.cols.data(), rand32 + 32 * c.off, c.m)) ||
-            (rc = launch_impl(sb.b, 1)) ||
+            (rc = place_hints(sb, sb.b, c.off, c.m)) || (rc = launch_impl(sb.b, 1)) ||
             (rc = collect_group(sb, sb.b, c.off, per_proof_status ? per_proof_status + c.off : nullptr, batch_ok + c.i0, out_left_xy ? out_left_xy + 64 * c.i0 : nullptr,
                                 out_right_xy ? out_right_xy + 64 * c.i0 : nullptr))) return rc;
     }
     return 0;
+}
+
+int h2v_verify_batches(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes, const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances32,
+                       size_t n_instance_columns, const size_t* col_lens, const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy,
+                       uint8_t* out_right_xy) {
+    return verify_batches("h2v_verify_batches", ctx, n_batches, batch_sizes, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32, per_proof_status, batch_ok,
+                          out_left_xy, out_right_xy, CallHints());
+}
+int h2v_verify_batches_hinted(h2v_ctx* ctx, size_t n_batches, const size_t* batch_sizes, const uint8_t* const* proofs, const size_t* proof_lens,
+                              const uint8_t* const* hint_rows, const uint8_t* const* instances32, size_t n_instance_columns, const size_t* col_lens,
+                              const uint8_t* rand32, int* per_proof_status, int* batch_ok, uint8_t* out_left_xy, uint8_t* out_right_xy, size_t hint_stats[3]) {
+    size_t stats[3] = {0, 0, 0};
+    const int rc = verify_batches("h2v_verify_batches_hinted", ctx, n_batches, batch_sizes, proofs, proof_lens, instances32, n_instance_columns, col_lens, rand32,
+                                  per_proof_status, batch_ok, out_left_xy, out_right_xy, CallHints{hint_rows, hint_stats ? stats : nullptr});
+    if (!rc && hint_stats) memcpy(hint_stats, stats, sizeof stats);
+    return rc;
 }
 
 int h2v_guard_msm(h2v_ctx* ctx, const uint8_t* proof, size_t proof_len, const uint8_t* instances32, size_t n_instance_columns, const size_t* col_lens,

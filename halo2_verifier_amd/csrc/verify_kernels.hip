@@ -125,10 +125,24 @@ __global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict_
 // a sender of bad hints is promised that speed.  The hit path is too short for the cap to bind at the sizes measured: the 1920 waves of
 // the headline launch are all resident at once under four waves per SIMD (4096 places).  Whether the dispatcher's packing matters to
 // an all-hit launch was not measured apart from that.
+//
+// LISTED (a stage with a miss list, StageArgs::miss_list): one miss no longer costs its wave a root.  Every live lane is checked as above,
+// and then the WAVE decides, from one ballot: if all its live lanes miss it takes its roots in place, as without a list (no lane waits
+// for another, and a sender of nothing but bad hints keeps that path); if it has a hit and a miss, the missing lanes store the
+// placeholder a failed decode stores (the identity, a zero y) through the same LDS transposition, WITHOUT a status, and append their
+// point indices to the list: one returning atomic add per wave by lane 0, the lanes' places from their ranks in the ballot.
+// k_decompress_misses, enqueued right behind on the same stream, takes those roots densely, 64 listed points per wave whatever waves
+// they came from.  The entries are indices into the whole stage (t_base = p0 x Np of the piece added), written to the piece's own
+// segment of the list, which starts at t_base: a piece lists at most its own points, so the segments of pieces never overlap.
+// The instantiation without a list is the kernel as it was before there was one.
+// gfx950 (-Rpass-analysis=kernel-resource-usage), LISTED: 102 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD
+// (the same figures as without a list).
 #define K_DECOMPRESS_HINTED_LDS_WORDS 2560
+template <bool LISTED>
 __global__ void __launch_bounds__(64, 4) k_decompress_hinted(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
                                                           uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, const uint8_t* hints,
-                                                          uint8_t* ycanon, int* __restrict__ status, uint32_t* __restrict__ misses) {
+                                                          uint8_t* ycanon, int* __restrict__ status, uint32_t* __restrict__ misses,
+                                                          uint32_t* __restrict__ list, uint32_t* __restrict__ list_count, uint32_t t_base) {
     const uint32_t total = n * np;
     const uint32_t t_raw = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t t = min(t_raw, total - 1);   // lanes past the end shadow the last point (all lanes reach the barriers below); their output is not stored
@@ -158,7 +172,18 @@ __global__ void __launch_bounds__(64, 4) k_decompress_hinted(const uint8_t* __re
     }
     const unsigned long long missed = __ballot(!hit && t_raw < total);
     if (missed && threadIdx.x == 0) atomicAdd(misses, (uint32_t)__popcll(missed));
-    if (!hit) {
+    bool in_place = true;   // (uniform over the wave)
+    if constexpr (LISTED) {
+        in_place = missed == __ballot(t_raw < total);
+        if (missed && !in_place) {
+            uint32_t at = 0;
+            if (threadIdx.x == 0) at = atomicAdd(list_count, (uint32_t)__popcll(missed));   // (lane 0 is live in every workgroup)
+            at = __shfl(at, 0);
+            if (!hit && t_raw < total) list[at + (uint32_t)__popcll(missed & ((1ull << threadIdx.x) - 1))] = t_base + t;
+        }
+    }
+    if (!hit && !in_place) { a = G1A::identity(); for (int i = 0; i < 8; ++i) yraw[i] = 0; }   // the placeholder; k_decompress_misses writes the point and its status
+    if (!hit && in_place) {
         // k_decompress's body for this point, from the root on
         if (ok) {
             Fq y = fq_sqrt_candidate_loop_w3(rhs);
@@ -205,6 +230,68 @@ __global__ void __launch_bounds__(64, 4) k_decompress_hinted(const uint8_t* __re
     uint32_t* dy = reinterpret_cast<uint32_t*>(ycanon + (size_t)t0 * 32);
 #pragma unroll
     for (int i = 0; i < 8; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 8) dy[k] = out_lds[k]; }
+}
+
+// The roots that the mixed waves of k_decompress_hinted<true> left out, densely: lane i below *list_count takes point t = list[i] of the
+// stage (an index over all its proofs: the pointers are the stage's own, not a piece's) with k_decompress's body from the proof bytes
+// on, and writes that point's pts, phi and ycanon rows and, where it does not decode, its proof's status (status_set: the rank-coded
+// atomic minimum, so the order of the list does not matter).  The grid is fixed from the piece's size on the host, which never reads
+// the count: a workgroup past the count leaves at once.  The listed points are scattered, so the rows are stored lane by lane (72 and
+// 32 bytes each, as 8- and 16-byte stores) and not through LDS; rows that are not listed are not touched, so hints and ycanon may
+// still be the same memory.  Launched with k_decompress's 10 KiB of LDS (dynamic: none is used), which holds it to the four waves per
+// SIMD that k_decompress's root loop was measured fastest at.
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 76 VGPRs, 39 SGPRs, no spills, 48 bytes of scratch, no static LDS; 6 waves per SIMD by its
+// registers, 4 under the launch's LDS request.
+__global__ void __launch_bounds__(64, 4) k_decompress_misses(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
+                                                          uint32_t np, uint32_t n_main_points, G1A* __restrict__ pts, G1A* __restrict__ phi, uint8_t* __restrict__ ycanon,
+                                                          int* __restrict__ status, const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= *list_count) return;
+    const uint32_t t = list[i];
+    const uint32_t p = t / np, slot = t % np;
+    const uint4* src = reinterpret_cast<const uint4*>(proofs + (size_t)p * proof_len + point_offsets[slot]);
+    const uint4 lo = src[0], hi = src[1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const bool is_inf = (w[7] >> 24) & G1_FLAG_IDENTITY, sign = (w[7] >> 24) & G1_FLAG_SIGN;
+    w[7] &= 0x3fffffffu;
+    G1A a = G1A::identity();
+    bool ok = !Fq::geq_p(w);
+    uint32_t yraw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ok) {
+        const Fq x = Fq::from_raw(w);
+        if (is_inf) ok = false;   // (k_decompress)
+        else {
+            const Fq three = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
+            const Fq rhs = x.sqr() * x + (three + three + three);
+            Fq y = fq_sqrt_candidate_loop_w3(rhs);
+            if (y.sqr() != rhs) ok = false;
+            else {
+                y.to_raw(yraw);                       // canonical y: its parity decides the sign, its bytes are absorbed
+                uint32_t nz = 0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) nz |= yraw[k];
+                if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
+                    y = y.neg();
+                    uint64_t borrow = 0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) { const uint64_t d = (uint64_t)FqParams::P(k) - yraw[k] - borrow; yraw[k] = (uint32_t)d; borrow = (d >> 32) & 1u; }
+                }
+                a.x = x; a.y = y;
+            }
+        }
+    }
+    if (!ok) { status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING); a = G1A::identity(); for (int k = 0; k < 8; ++k) yraw[k] = 0; }
+    const uint2* av = reinterpret_cast<const uint2*>(&a);   // (a G1A: 18 words, 8-byte aligned)
+    uint2* dp = reinterpret_cast<uint2*>(pts + t);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dp[k] = av[k];
+    a.x = g1_beta_times(a.x);   // phi(P) = (beta x, y)
+    dp = reinterpret_cast<uint2*>(phi + t);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dp[k] = av[k];
+    uint4* dy = reinterpret_cast<uint4*>(ycanon + (size_t)t * 32);
+    dy[0] = make_uint4(yraw[0], yraw[1], yraw[2], yraw[3]);
+    dy[1] = make_uint4(yraw[4], yraw[5], yraw[6], yraw[7]);
 }
 
 __global__ void __launch_bounds__(256) k_check_scalars(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ scalar_offsets,
@@ -924,8 +1011,21 @@ int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t 
     if (!tp) return 0;
     if (!g.hints || !g.hint_misses) { set_last_error("decompress_hinted_range_enqueue: hints without a miss word"); return H2V_ERR_BAD_ARGUMENT; }
     const size_t off = (size_t)p0 * pl.n_points;   // the hints' rows are the points': offset by p0 exactly as ycanon is
-    hipLaunchKernelGGL(k_decompress_hinted, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p, pl.n_points,
-                       pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses);
+    if (!g.miss_list) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decompress_hinted<false>), dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p,
+                           pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses, nullptr, nullptr, 0u);
+        H2V_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // With a list: the piece's segment of it starts at its first point, and its counter is cleared here, on the stream, in front of its
+    // two kernels — so a piece neither sees nor redoes an earlier piece's entries, and every call leaves its own range complete.
+    if (!g.miss_list_count) { set_last_error("decompress_hinted_range_enqueue: a miss list without its counter"); return H2V_ERR_BAD_ARGUMENT; }
+    H2V_HIP_CHECK(hipMemsetAsync(g.miss_list_count, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decompress_hinted<true>), dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p,
+                       pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses, g.miss_list + off,
+                       g.miss_list_count, (uint32_t)off);
+    hipLaunchKernelGGL(k_decompress_misses, dim3((tp + 63) / 64), dim3(64), K_DECOMPRESS_LDS_WORDS * sizeof(uint32_t), s, g.proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points,
+                       pl.n_main_points, g.pts, g.phi, g.ycanon, g.status, g.miss_list + off, g.miss_list_count);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

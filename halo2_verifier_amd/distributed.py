@@ -265,6 +265,15 @@ class ShardedBatch:
         finally:
             self.batch.hold_tail(tail)   # (no caller holds this tensor: the batch does, until its stream has read it)
 
+    def set_hints(self, y32):
+        """Point hints for this rank's upload (Batch.set_hints): the rows of the rank's own proofs, n * n_points * 32 bytes, or None.
+        Hints are a rank's own business: they change its launch's time and nothing that is exchanged."""
+        self.batch.set_hints(y32)
+
+    def set_hint_rows(self, rows):
+        """The same from one row or None per proof of this rank's upload (Batch.set_hint_rows)."""
+        self.batch.set_hint_rows(rows)
+
     def launch_shard(self):
         """Shard pipeline without a pairing + export of the accumulator records -> the local record tensor (stream-ordered)."""
         self.batch.launch(with_pairing=False)
@@ -385,6 +394,18 @@ def _shard(ctx, proofs, instances, lo, hi):
     return flat, plen, iflat, lens
 
 
+def _hint_rows(hints, n):
+    """The hints= keyword of the sharded calls: one row (bytes) or None per proof of the WHOLE batch, checked before anything runs;
+    every rank then takes its own slice.  Hints are not exchanged."""
+    if hints is None:
+        return None
+    if isinstance(hints, (bytes, bytearray, str)) or not hasattr(hints, "__len__"):
+        raise TypeError("hints must be a sequence of bytes or None, one per proof")
+    if len(hints) != n:
+        raise ValueError(f"{n} proofs need {n} hint rows (None for a proof without hints), got {len(hints)}")
+    return list(hints)
+
+
 def _all_statuses(local, n, world, group, backend, device):
     """Per-proof statuses of the whole batch, in call order, on every rank (a second, 4 n-byte all-gather)."""
     if world == 1:
@@ -426,7 +447,7 @@ def _seeded_draws(seed, rand, n, lo, identify, group=None, device=None):
     return seed, seeded_tail(seed, lo, n)
 
 
-def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, identify=False, seed=None):
+def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_factory=None, device=None, identify=False, seed=None, hints=None):
     """N x verify_proof under ONE AccumulatorStrategy followed by finalize() (lib.rs:33-425, kzg/strategy.rs:125-140) with the
     proofs sharded over the ranks of `group` (default: the world) — BASELINE.json configs 3 and 5.
 
@@ -438,9 +459,12 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     identify: verify_batch_sharded_identify's form -> (ok, statuses[n], left_xy, right_xy, local_range_checks).
     seed (instead of rand): the draws are draws.expand(seed, 0, n) — True: rank 0 takes a seed from the OS and broadcasts its 32
     bytes (common_seed); bytes: a given seed, the same on every rank.  No n x 32-byte broadcast happens: every rank expands its own
-    tail, and the result is the one of rand = those draws."""
+    tail, and the result is the one of rand = those draws.
+    hints: one hint row (hints.for_proofs) or None per proof of the whole batch; rank r stages the rows of its own shard
+    (Batch.set_hint_rows).  The result is the one without hints."""
     rank, world, backend = _group_info(group)
     n = len(proofs)
+    hints = _hint_rows(hints, n)
     if device is None and batch_factory is None:
         device = f"cuda:{ctx.device}"
     lo, hi = shard_bounds(n, world, rank)
@@ -455,6 +479,8 @@ def verify_batch_sharded(ctx, proofs, instances, rand=None, group=None, batch_fa
     sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), group=group, device=device, batch_factory=batch_factory)
     try:
         sb.upload(flat, plen, iflat, lens, tail)
+        if hints is not None:
+            sb.set_hint_rows(hints[lo:hi])
         sb.launch()
         ok, st, left, right = sb.finish()
         checks = 0
@@ -478,14 +504,16 @@ def verify_batch_sharded_identify(ctx, proofs, instances, rand=None, group=None,
     return verify_batch_sharded(ctx, proofs, instances, rand, group, batch_factory, device, identify=True, seed=seed)
 
 
-def verify_batch_sharded_local(ctx, proofs, instances, rand=None, world: int = 1, batch_factory=None, device=None, identify=False, seed=None):
+def verify_batch_sharded_local(ctx, proofs, instances, rand=None, world: int = 1, batch_factory=None, device=None, identify=False, seed=None, hints=None):
     """The `world`-rank computation of verify_batch_sharded run shard after shard on ONE device, no process group: every shard is
     uploaded with the draw tail of its global position and launched without a pairing, the records are laid out as the all-gather
     would, shard 0 folds them and runs the one pairing.  -> (ok, statuses[n], left_xy, right_xy).
     identify: verify_batch_sharded_local_identify's form -> (ok, statuses[n], left_xy, right_xy, range_checks[world]).
-    seed (instead of rand): verify_batch_sharded's — every shard's tail is expanded from the seed on its own."""
+    seed (instead of rand): verify_batch_sharded's — every shard's tail is expanded from the seed on its own.
+    hints: verify_batch_sharded's — shard r stages the rows [lo, hi) of its own proofs."""
     import torch
     n = len(proofs)
+    hints = _hint_rows(hints, n)
     if rand is not None and len(rand) != n:
         raise ValueError(f"rand must hold one scalar per proof ({n}), got {len(rand)}")
     if seed is not None:
@@ -506,6 +534,8 @@ def verify_batch_sharded_local(ctx, proofs, instances, rand=None, world: int = 1
             sb = ShardedBatch(ctx, hi - lo, max(sum(lens), 1), device=device, batch_factory=batch_factory, world_size=world)
             shards.append(sb)
             sb.upload(flat, plen, iflat, lens, tail_of(lo))
+            if hints is not None:
+                sb.set_hint_rows(hints[lo:hi])
             sb.launch_shard()
             _, st, _, _ = sb.finish()
             statuses += st

@@ -1,5 +1,6 @@
-"""Point hints for a staged batch: ctypes binding of include/h2v_hints.h, behind Batch.set_hints, .set_hints_tensor, .hints,
-.hints_into and .hint_stats.
+"""Point hints: ctypes binding of include/h2v_hints.h (a staged batch: Batch.set_hints, .set_hints_tensor, .hints, .hints_into,
+.hint_stats) and of include/h2v_hint_rows.h (a row per proof or None: Batch.set_hint_rows, and the hints= keyword of
+Context.verify_batch, Context.verify_batches, verify_batch_keys, Accumulator.process and verify_proof with an AccumulatorStrategy).
 
 Every launch of a Batch decodes every compressed G1 point of every proof, a square root in Fq per point.  Whoever sends a proof knows
 both coordinates of its points.  A hint is the claimed y of a point, 32 canonical little-endian bytes; a hint row holds the y of the
@@ -15,8 +16,11 @@ hold, change its time and nothing else.
   set_hints / set_hints_device / set_hints_tensor   the hints of the batch's current upload, from host or device memory
   hints / hints_device / hints_into          the canonical y a launch leaves behind: hints for the next verifier of the same proofs
   hint_stats                                 (n_points, n_hinted, n_missed) of the last launch
+  set_hint_rows                              the same from one row per proof, None where a sender gave none
+  call_rows(contexts, keys, hints)           the checked row array of a one-shot call's hints= keyword (verifier.py)
 
-Cost: 32 bytes per point beside the proof.  A sender of bad hints gets the speed of a launch without hints plus the check.
+Cost: 32 bytes per point beside the proof.  A sender of bad hints gets the speed of a launch without hints plus the check; the
+points without a usable hint, whichever proofs they belong to, have their roots taken together behind the check.
 """
 import ctypes
 
@@ -35,6 +39,16 @@ SIGNATURES = {
     "h2v_batch_hints_device": (c_int, [c_vp, c_sz, c_sz, c_vp, c_sz]),
     "h2v_batch_hint_stats": (c_int, [c_vp, c_szp, c_szp, c_szp]),
 }
+# and include/h2v_hint_rows.h: a row per proof or none.  hint_rows after proof_lens, hint_stats (size_t[3]) last
+_u8pp, _u32p, _vpp, _intp = ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(c_vp), ctypes.POINTER(c_int)
+ROW_SIGNATURES = {
+    "h2v_batch_set_hint_rows": (c_int, [c_vp, c_sz, _u8pp]),
+    "h2v_verify_batch_keys_hinted": (c_int, [_vpp, c_sz, _u32p, c_sz, _u8pp, c_szp, _u8pp, _u8pp, c_szp, c_szp, ctypes.c_char_p, _intp, _intp, ctypes.c_char_p,
+                                             ctypes.c_char_p, c_szp]),
+    "h2v_verify_batches_hinted": (c_int, [c_vp, c_sz, c_szp, _u8pp, c_szp, _u8pp, _u8pp, c_sz, c_szp, ctypes.c_char_p, _intp, _intp, ctypes.c_char_p, ctypes.c_char_p,
+                                          c_szp]),
+    "h2v_accumulator_process_hinted": (c_int, [c_vp, _vpp, c_sz, _u32p, c_sz, _u8pp, c_szp, _u8pp, _u8pp, c_szp, c_szp, ctypes.c_char_p, _intp, _intp, c_szp]),
+}
 _BOUND = None
 
 
@@ -43,7 +57,7 @@ def _library():
     global _BOUND
     if _BOUND is None:
         lib = _lib.load_library()
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(ROW_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _BOUND = lib
@@ -119,6 +133,64 @@ def set_hints(batch, y32):
     if len(y32) != want:
         raise ValueError(f"the hints of {n} proofs are n * n_points * 32 = {want} bytes, got {len(y32)}")
     _lib.check(_library().h2v_batch_set_hints(batch._h, n, y32))
+
+
+def _rows_array(rows, row_lens):
+    """rows: a sequence of bytes | None, one per proof; row_lens: the length each must have -> the char* array h2v_hint_rows.h takes.
+    Every refusal comes before any library call."""
+    if rows is None or isinstance(rows, (bytes, bytearray, str)) or not hasattr(rows, "__len__"):
+        raise TypeError("hints must be a sequence of bytes or None, one per proof")
+    rows, n = list(rows), len(row_lens)
+    if len(rows) != n:
+        raise ValueError(f"{n} proofs need {n} hint rows (None for a proof without hints), got {len(rows)}")
+    for i, (row, want) in enumerate(zip(rows, row_lens)):
+        if row is None:
+            continue
+        if not isinstance(row, (bytes, bytearray)):
+            raise TypeError(f"hint row {i} must be bytes or None, got {type(row).__name__}")
+        if len(row) != want:
+            raise ValueError(f"hint row {i} must hold n_points * 32 = {want} bytes, got {len(row)}")
+    return (ctypes.c_char_p * max(n, 1))(*[None if r is None else bytes(r) for r in rows])
+
+
+def _points_of(ctx):
+    """Np of a context's key (kept on the context: it is a fact of the key)"""
+    np_ = getattr(ctx, "_hint_points", None)
+    if np_ is None:
+        np_ = ctx._hint_points = int(ctx.proof_shape()["n_points"])
+    return np_
+
+
+def call_rows(contexts, keys, rows):
+    """The hints= keyword of a one-shot call: rows[i] is proof i's row of 32 Np bytes, Np of contexts[keys[i]], or None -> the array
+    the _hinted entry points take (the sequence is sized before a context is asked for its Np)"""
+    if rows is not None and hasattr(rows, "__len__") and not isinstance(rows, (bytes, bytearray, str)) and len(rows) != len(keys):
+        raise ValueError(f"{len(keys)} proofs need {len(keys)} hint rows (None for a proof without hints), got {len(rows)}")
+    return _rows_array(rows, [32 * _points_of(contexts[k]) for k in keys])
+
+
+def stats_out():
+    return (c_sz * 3)()
+
+
+def expected_stats(n_points_per_proof, rows, missed):
+    """What the entry points report for rows given per proof: (points, hinted points, hinted points missed).  n_points_per_proof: Np of
+    every proof; rows: per proof a row or None; missed: per proof the hints of its row that the device does not use (0 where rows[i] is
+    None) -> the three counters.  The arithmetic of h2v_batch_hint_stats after h2v_batch_set_hint_rows, for tests and probes."""
+    points = sum(n_points_per_proof)
+    hinted = sum(np_ for np_, r in zip(n_points_per_proof, rows) if r is not None)
+    return points, hinted, sum(m for m, r in zip(missed, rows) if r is not None)
+
+
+def set_hint_rows(batch, rows):
+    """The hints of the batch's current upload from one row per proof, None where the proof's sender gave none
+    (h2v_batch_set_hint_rows); rows=None drops them.  The batch must be uploaded and not launched since."""
+    n = int(batch.n)
+    if rows is None:
+        _lib.check(_library().h2v_batch_set_hint_rows(batch._h, n, None))
+        return
+    arr = _rows_array(rows, [32 * _n_points(batch)] * n)
+    _lib.check(_library().h2v_batch_set_hint_rows(batch._h, n, arr))
 
 
 def set_hints_device(batch, addr, row_stride):

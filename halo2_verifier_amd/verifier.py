@@ -324,6 +324,23 @@ def _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context=Fa
     return (ca, len(contexts), ka, *m.head, _sizes(m.ncols), m.per_proof(), rb), contexts, None if one_key else m.keys
 
 
+def _hinted_keyed(entry, handle, contexts, key_of_proof, proofs, instances, rand, hint_rows, outs, bare_context=False):
+    """A keyed call with hint rows (include/h2v_hint_rows.h: hint_rows after proof_lens, the counters last): the rows are checked before
+    anything else -> (the contexts, the key indices or None, (points, hinted, missed))"""
+    from . import hints
+    one_key = bare_context and isinstance(contexts, Context)
+    ctx_list = [contexts] if one_key else list(contexts)
+    keys = [0] * len(proofs) if one_key or key_of_proof is None else [int(k) for k in key_of_proof]
+    if any(not 0 <= k < len(ctx_list) for k in keys):
+        raise ValueError(f"key index out of range for {len(ctx_list)} contexts")
+    rows = hints.call_rows(ctx_list, keys, hint_rows)
+    args, contexts, keys = _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context)
+    stats = hints.stats_out()
+    head = args[:6] + (rows,) + args[6:]           # (ctxs, n_keys, key_of_proof, n, proofs, proof_lens | hint_rows | instances32, ...)
+    check(getattr(hints._library(), entry)(*((handle,) if handle is not None else ()), *head, *outs, stats))
+    return contexts, keys, tuple(stats)
+
+
 class Context:
     """ParamsKZG + VerifyingKey resident on one GPU (h2v_ctx)."""
 
@@ -416,12 +433,21 @@ class Context:
         return dict(zip(keys, (v.value for v in vals)))
 
     # -- N x verify_proof + AccumulatorStrategy::finalize
-    def verify_batch(self, proofs, instances, rand=None, seed=None):
+    def verify_batch(self, proofs, instances, rand=None, seed=None, hints=None):
         """proofs: list of bytes; instances: per proof, list of columns of scalars (column lengths may differ from proof to
         proof, as N independent verify_proof calls allow); rand: list of n ints/bytes or None.
         seed: an existing accumulator to start from — AccumulatorStrategy::with (kzg/strategy.rs:75-78) — as
         ((left_scalars, left_bases), (right_scalars, right_bases)): scalars ints / 32-byte strings, bases 64-byte x | y.
+        hints: per proof its hint row (hints.for_proofs: n_points * 32 bytes) or None (h2v_verify_batch_keys_hinted; not with a seed): the
+        same results sooner; (points, hinted points, hinted points missed) are kept in self.last_hint_stats.
         Returns (batch_ok, statuses, left_xy, right_xy)."""
+        if hints is not None:
+            if seed is not None:
+                raise ValueError("a seeded batch takes no hints")
+            r = _Results(len(proofs))
+            _, _, self.last_hint_stats = _hinted_keyed("h2v_verify_batch_keys_hinted", None, [self], [0] * len(proofs), proofs, instances, rand, hints,
+                                                       (r.st, ctypes.byref(r.ok), r.left, r.right))
+            return r.result()
         m = _marshal_batch([self], proofs, instances)
         rb = _rand_bytes(rand, m.n)
         r = _Results(m.n)
@@ -459,11 +485,16 @@ class Context:
         self.last_range_checks, self.last_seed_ok = r.checks.value, bool(r.seed_ok.value)
         return r.result()
 
-    def verify_batches(self, batches, rand=None):
+    def verify_batches(self, batches, rand=None, hints=None):
         """Many AccumulatorStrategy batches of their own sizes in few launches (h2v_verify_batches).  batches: list of (proofs, instances),
         each as verify_batch takes them and none empty; one instance shape for the whole call; rand: one scalar per proof of the call, batch
-        after batch, or None.  Returns one (batch_ok, statuses, left_xy, right_xy) per batch: what verify_batch returns for it with its draws."""
+        after batch, or None.  hints: one row or None per proof of the call, batch after batch (h2v_verify_batches_hinted; the counters in
+        self.last_hint_stats).  Returns one (batch_ok, statuses, left_xy, right_xy) per batch: what verify_batch returns for it with its draws."""
         batches = [(list(p), list(i)) for p, i in batches]
+        rows = None
+        if hints is not None:
+            from . import hints as hints_mod
+            rows = hints_mod.call_rows([self], [0] * sum(len(p) for p, _ in batches), hints)
         for p, i in batches:
             if len(i) != len(p):
                 raise ValueError(f"{len(p)} proofs but {len(i)} instance lists in one batch")
@@ -476,7 +507,13 @@ class Context:
         st = (ctypes.c_int * max(m.n, 1))()
         ok = (ctypes.c_int * max(k, 1))()
         left, right = ctypes.create_string_buffer(64 * max(k, 1)), ctypes.create_string_buffer(64 * max(k, 1))
-        check(self._lib.h2v_verify_batches(self._h, k, _sizes(sizes), *m.head[1:], m.ncols[0], m.shape0(), rb, st, ok, left, right))
+        if rows is None:
+            check(self._lib.h2v_verify_batches(self._h, k, _sizes(sizes), *m.head[1:], m.ncols[0], m.shape0(), rb, st, ok, left, right))
+        else:
+            stats = hints_mod.stats_out()
+            check(hints_mod._library().h2v_verify_batches_hinted(self._h, k, _sizes(sizes), m.proofs, m.proof_lens, rows, m.instances, m.ncols[0], m.shape0(), rb, st,
+                                                                 ok, left, right, stats))
+            self.last_hint_stats = tuple(stats)
         out, at = [], 0
         for g, sz in enumerate(sizes):
             out.append((bool(ok[g]), list(st[at:at + sz]), left.raw[64 * g:64 * g + 64], right.raw[64 * g:64 * g + 64]))
@@ -519,6 +556,7 @@ class _Strategy:
     def __init__(self, params: ParamsKZG):
         self.params = params
         self._items = []  # (vk, instances, proof)
+        self._hints = []  # per item its hint row or None (AccumulatorStrategy)
 
 
 class AccumulatorStrategy(_Strategy):
@@ -587,10 +625,11 @@ class AccumulatorStrategy(_Strategy):
                 return True
         proofs, instances = [p for _, _, p in self._items], [i for _, i, _ in self._items]
         with self._contexts() as (ctxs, key_of_proof):
+            rows = self._hints if self.seed is None and any(h is not None for h in self._hints) else None   # (no row queued: the calls without hints)
             if not identify and len(ctxs) == 1:
-                ok, _, self.left_xy, self.right_xy = ctxs[0].verify_batch(proofs, instances, rand, seed=self.seed)
+                ok, _, self.left_xy, self.right_xy = ctxs[0].verify_batch(proofs, instances, rand, seed=self.seed, hints=rows)
             elif not identify:
-                ok, _, self.left_xy, self.right_xy = verify_batch_keys(ctxs, key_of_proof, proofs, instances, rand)
+                ok, _, self.left_xy, self.right_xy = verify_batch_keys(ctxs, key_of_proof, proofs, instances, rand, hints=rows)[:4]
             elif self.seed is not None:
                 ok, self.statuses, self.left_xy, self.right_xy = ctxs[0].verify_batch_identify(proofs, instances, rand, seed=self.seed)
                 self.last_range_checks, self.last_seed_ok = ctxs[0].last_range_checks, ctxs[0].last_seed_ok
@@ -607,11 +646,14 @@ class SingleStrategy(_Strategy):
         self.device, self.circuit_instances = device, circuit_instances
 
 
-def verify_proof(params: ParamsKZG, vk: VerifyingKey, strategy, instances, proof: bytes):
+def verify_proof(params: ParamsKZG, vk: VerifyingKey, strategy, instances, proof: bytes, hints=None):
     """lib.rs:33-49.  `instances` = one circuit instance: list of columns — or, for a strategy created with circuit_instances = M,
     the M x columns of the M instances that share the transcript, instance by instance (the reference's `&[&[&[Fr]]]` flattened).
     With SingleStrategy returns None or raises H2VError(code = PlonkError); with AccumulatorStrategy returns the strategy
-    (Output = Self)."""
+    (Output = Self).  hints: the proof's hint row (hints.for_proofs) for an AccumulatorStrategy, handed on at finalize(); a
+    SingleStrategy, finalize_identify() and a seeded accumulation run without hints."""
+    if hints is not None and not isinstance(hints, (bytes, bytearray)):
+        raise TypeError("a proof's hints are one row of bytes")
     if isinstance(strategy, SingleStrategy):
         ctx = Context(params, vk, strategy.device, circuit_instances=strategy.circuit_instances)
         try:
@@ -622,6 +664,7 @@ def verify_proof(params: ParamsKZG, vk: VerifyingKey, strategy, instances, proof
             raise H2VError(st, PlonkError(st).name)
         return None
     strategy._items.append((vk, instances, proof))
+    strategy._hints.append(hints)
     return strategy
 
 
@@ -633,13 +676,19 @@ def verify_batch(params, vk, proofs, instances, rand=None, device=0):
         ctx.close()
 
 
-def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None):
+def verify_batch_keys(contexts, key_of_proof, proofs, instances, rand=None, hints=None):
     """N x verify_proof on ONE AccumulatorStrategy whose proofs belong to several VerifyingKeys over the same params, then
     finalize() (h2v_verify_batch_keys): contexts[k] holds key k, proof i belongs to contexts[key_of_proof[i]].  instances: per
     proof, list of columns (shapes may differ from proof to proof; every proof of a key has that key's column count).  rand: n
-    draws in call order, or None.  Returns (batch_ok, statuses, left_xy, right_xy)."""
-    args, _, _ = _keyed_args(contexts, key_of_proof, proofs, instances, rand)
+    draws in call order, or None.  hints: per proof its hint row — 32 bytes per point of ITS key — or None
+    (h2v_verify_batch_keys_hinted); then the result has a fifth item, (points, hinted points, hinted points missed).
+    Returns (batch_ok, statuses, left_xy, right_xy)."""
     r = _Results(len(proofs))
+    if hints is not None:
+        _, _, stats = _hinted_keyed("h2v_verify_batch_keys_hinted", None, contexts, key_of_proof, proofs, instances, rand, hints,
+                                    (r.st, ctypes.byref(r.ok), r.left, r.right))
+        return r.result() + (stats,)
+    args, _, _ = _keyed_args(contexts, key_of_proof, proofs, instances, rand)
     check(_lib.load_library().h2v_verify_batch_keys(*args, r.st, ctypes.byref(r.ok), r.left, r.right))
     return r.result()
 
@@ -701,14 +750,20 @@ class Accumulator:
         except Exception:
             pass
 
-    def process(self, contexts, key_of_proof, proofs, instances, rand=None):
+    def process(self, contexts, key_of_proof, proofs, instances, rand=None, hints=None):
         """n x verify_proof on this accumulator (h2v_accumulator_process): contexts[k] holds key k, proof i belongs to
         contexts[key_of_proof[i]]; a single Context with key_of_proof=None is the one-key form.  instances / rand as verify_batch_keys.
+        hints: per proof its hint row (32 bytes per point of its key) or None (h2v_accumulator_process_hinted): the same accumulator
+        sooner; the counters are kept in `last_hint_stats`.
         Returns the statuses of this call's proofs; `last_all_ok` says whether all are 0.  A call that raises H2VError leaves the
         accumulator as it was."""
-        args, contexts, keys = _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context=True)
         r = _Results(len(proofs))
-        check(self._lib.h2v_accumulator_process(self._h, *args, r.st, ctypes.byref(r.ok)))
+        if hints is not None:
+            contexts, keys, self.last_hint_stats = _hinted_keyed("h2v_accumulator_process_hinted", self._h, contexts, key_of_proof, proofs, instances, rand, hints,
+                                                                 (r.st, ctypes.byref(r.ok)), bare_context=True)
+        else:
+            args, contexts, keys = _keyed_args(contexts, key_of_proof, proofs, instances, rand, bare_context=True)
+            check(self._lib.h2v_accumulator_process(self._h, *args, r.st, ctypes.byref(r.ok)))
         self.last_all_ok = bool(r.ok.value)
         if r.n and self._inputs:   # (journal on: the call has appended an entry)
             self._inputs.append((contexts, keys, list(proofs), list(instances)) if self._keep_inputs else None)
@@ -1536,6 +1591,13 @@ class Batch:
         instead of taking square roots, and takes the root where a hint does not hold."""
         from . import hints
         return hints.set_hints(self, y32)
+
+    def set_hint_rows(self, rows):
+        """set_hints from one row per proof of the current upload — n_points * 32 bytes, or None where the proof's sender gave none
+        (include/h2v_hint_rows.h); rows=None drops the hints.  hint_stats() then counts the rows given: n_hinted = n_points * (rows that
+        are not None), n_missed = the hints of those rows that were not used."""
+        from . import hints
+        return hints.set_hint_rows(self, rows)
 
     def set_hints_tensor(self, t):
         """set_hints from a uint8 tensor [n, 32 * n_points] on the batch's device (row stride a multiple of 16), device -> device on

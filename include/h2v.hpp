@@ -372,6 +372,7 @@ public:
         return st;
     }
     bool all_ok() const { return all_ok_; }
+    h2v_accumulator* handle() const { return h_; }   // for the extensions of the C ABI (h2v_hints.hpp: hints::process)
     // AccumulatorStrategy::with / DualMSM::add_msm: (L, R) += the two term lists evaluated, unscaled — scalars 32 bytes each, bases 64 bytes (x | y) each
     void add_msm(const Bytes& left_scalars, const Bytes& left_bases, const Bytes& right_scalars, const Bytes& right_bases) {
         detail::check_channels(left_scalars, left_bases, right_scalars, right_bases, "a channel is n 32-byte scalars and n 64-byte bases");

@@ -1,4 +1,5 @@
-/* h2v_hints.h — point hints for a staged batch: an extension of the C ABI of include/h2v.h, exported by the same library.
+/* h2v_hints.h — point hints for a staged batch, the one-shot calls and the resident accumulator: an extension of the C ABI of
+ * include/h2v.h, exported by the same library.
  *
  * Every launch of a staged batch begins with G1Affine::from_bytes for every compressed point of every proof, and each of them pays a
  * square root in Fq: about 320 field products.  The sender of a proof — a prover, a relay, a rank that has verified the shard
@@ -19,13 +20,19 @@
  * not decode.
  *
  * Cost.  Hints add 32 bytes per point to what is sent and uploaded (12 x 32 B beside a 1024 B proof for the headline key).  A sender
- * of bad hints gets the speed of a launch without hints plus the check; within a wave of 64 points one miss costs the wave a root.
+ * of bad hints gets the speed of a launch without hints plus the check.  Hints may come from SOME senders only: a proof has a row or
+ * none (include/h2v_hint_rows.h).  The points whose hint is not used are collected on the device and their
+ * roots are taken together, 64 to a wave, behind the check: a launch pays for the roots it needs, whichever proofs they belong to.
+ * (Only a wave of 64 consecutive points ALL of whose hints fail takes its roots where it stands.)
  *
- * Out of its reach: the one-shot calls (h2v_verify_batch*, h2v_verify_each, h2v_accumulator_process) and h2v_batch_upload_launch,
- * whose decompression runs under its own copy, take no hints.
+ * Who takes hints.  A staged batch, here; and through include/h2v_hint_rows.h a staged batch row by row (h2v_batch_set_hint_rows), the
+ * one-shot calls h2v_verify_batch, _shapes and _keys (h2v_verify_batch_keys_hinted), h2v_verify_batches (h2v_verify_batches_hinted) and
+ * the resident accumulator (h2v_accumulator_process_hinted).  Without hints still: the identifying and the seeded one-shot calls (h2v_verify_batch_identify,
+ * _keys_identify, _seeded, _seeded_identify), h2v_verify_each, and h2v_batch_upload_launch, whose decompression runs under its own
+ * copy.  The calls of include/h2v.h enqueue exactly what they enqueue without this header.
  *
  * Threading.  A batch is used from one thread at a time, as for every h2v_batch_* call; none of the calls here takes a context's
- * lock.  h2v_hints_from_points touches neither a context nor a device and may be called from any thread at any time;
+ * lock (the one-shot calls of include/h2v_hint_rows.h do, as their forms without hints).  h2v_hints_from_points touches neither a context nor a device and may be called from any thread at any time;
  * h2v_hints_point_offsets reads the context as h2v_ctx_proof_shape does.  The entry points are not named in the scene table that
  * covers include/h2v.h (tests/thread_scenes.py), and join h2v.h when that table is next revised.  Errors are reported as in h2v.h
  * (h2v_last_error, per thread).
@@ -69,7 +76,8 @@ int h2v_batch_hints(h2v_batch* b, size_t first, size_t count, uint8_t* y32);
 int h2v_batch_hints_device(h2v_batch* b, size_t first, size_t count, void* d_y32, size_t row_stride);
 
 /* Of the last launch (Launched or Finished; waits for the batch's stream): n_points = n x Np; n_hinted = n_points when the
- * launch had hints, else 0; n_missed = the hinted points whose hint was not used.  A hint is USED exactly when the point
+ * launch had hints — after h2v_batch_set_hint_rows (include/h2v_hint_rows.h), Np x (the rows that were not NULL) — else 0; n_missed = the hinted points whose
+ * hint was not used (the points of a proof without a row are neither hinted nor missed).  A hint is USED exactly when the point
  * decodes and the hint's 32 bytes equal its canonical y; every other case is a miss (a wrong, non-canonical or
  * other-root hint, and every point that does not decode).  Any pointer may be NULL. */
 int h2v_batch_hint_stats(h2v_batch* b, size_t* n_points, size_t* n_hinted, size_t* n_missed);
