@@ -84,20 +84,18 @@ struct StageArgs {
     uint32_t* hint_misses = nullptr;
     const uint8_t* hints = nullptr;
     // the miss list of a stage with hints: one word per point of the stage, and the word that counts a piece's entries (cleared on the
-    // stream by every decompress_hinted_range_enqueue).  Given: a wave with a hit and a miss lists its misses, and k_decompress_misses
-    // takes their roots densely right behind.  Null: every miss takes its root in place.
+    // stream by every decompress_range_enqueue).  A wave with a hit and a miss lists its misses, and k_decompress_misses takes their
+    // roots densely right behind.  A stage with hints has both (decompress_range_enqueue refuses it otherwise); without hints, null.
     uint32_t* miss_list = nullptr;
     uint32_t* miss_list_count = nullptr;
 };
 
 // the decompression stage in pieces (h2v_batch_upload_launch runs them around its copies): reset the status words; decompress the points of proofs [p0, p1); check the
-// scalars of all proofs
+// scalars of all proofs.  A stage with hints: _range launches k_decompress_hinted with k_decompress_misses behind it (the miss word is
+// cleared by _begin or by the launch) and leaves its range complete all the same.
 int decompress_begin_enqueue(hipStream_t s, const StageArgs& g);
 int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int decompress_finish_enqueue(hipStream_t s, const StageArgs& g);
-// k_decompress_hinted over the proofs [p0, p1) of a stage with hints: decompress_range_enqueue's other branch (the miss word is cleared by
-// decompress_begin_enqueue or by the launch); with a miss list, k_decompress_misses behind it.  Either way the call leaves its range complete.
-int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1);
 int transcript_stage_enqueue(hipStream_t s, const StageArgs& g);
 // The groups of one upload: which proofs and which draws belong to group g.  One plain struct for host code and kernels (a kernel
 // takes it by value); everything that must know where a group starts, how long it is or whose a proof is asks it.

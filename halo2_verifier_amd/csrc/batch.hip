@@ -6,6 +6,7 @@
 #include "msm_object.h"
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <utility>
 #include <stdio.h>
 
@@ -250,7 +251,7 @@ int resolve_draws(const uint8_t*& rand32, size_t n, std::vector<uint8_t>& storag
 // what the decompression and transcript stages work on: the batch's upload (its plan and n) and its buffers
 static StageArgs stage_args(const h2v_batch* b) {
     StageArgs g{b->n, &b->plan->host, b->plan, b->proofs.p, b->inst.p, b->pts.p, b->phi.p, b->ycanon.p, b->status, b->words.p, b->stream_words, b->chal.p};
-    // (h2v_batch_set_hints: the hints wait where the canonical y will lie; the miss list and its counter: hints_reserve)
+    // (h2v_batch_set_hints: the hints wait where the canonical y will lie; the miss list and its counter: hints_stage)
     if (b->hinted) { g.hint_misses = b->hint_misses.p; g.hints = b->ycanon.p; g.miss_list = b->miss_list.p; g.miss_list_count = b->hint_misses.p + 1; }
     return g;
 }
@@ -1056,11 +1057,17 @@ int hints_range_check(const h2v_batch* b, const char* who, size_t first, size_t 
     if (first > b->n || count > b->n - first) { set_last_error(std::string(who) + ": a range outside the upload"); return H2V_ERR_BAD_ARGUMENT; }
     return 0;
 }
-// what every hinted launch needs beside the hints: the miss word and the list counter, and a list word per point `ycanon` holds
-// (grow-only, like every buffer of the batch: it grows only when ycanon has grown)
-int hints_reserve(h2v_batch* b) {
+// What the three set_hints forms do once their arguments are checked and there are hints to stage.  Device work from the StageCommit
+// on: a failure of it leaves the batch Empty like any other.  Reserved: what every hinted launch needs beside the hints, the miss word
+// and the list counter, and a list word per point `ycanon` holds (grow-only: it grows only when ycanon has grown).  `transfer` brings
+// the rows into `ycanon` and waits for whatever host memory it read; null_rows of the upload's proofs came without a row.
+int hints_stage(h2v_batch* b, size_t null_rows, const std::function<int()>& transfer) {
+    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
+    StageCommit commit{b};
     int rc;
-    if ((rc = b->hint_misses.reserve(2)) || (rc = b->miss_list.reserve(b->ycanon.cap / 32))) return rc;
+    if ((rc = b->hint_misses.reserve(2)) || (rc = b->miss_list.reserve(b->ycanon.cap / 32)) || (rc = transfer())) return rc;
+    commit.commit(BatchStage::Uploaded);
+    b->hinted = true; b->null_rows = (uint32_t)null_rows;
     return 0;
 }
 int strided_rows_check(const char* who, const void* d, size_t rows, size_t row_len, size_t row_stride, int device, const char* does) {
@@ -1101,17 +1108,13 @@ int h2v_batch_set_hints(h2v_batch* b, size_t n, const uint8_t* y32) {
     static const char who[] = "h2v_batch_set_hints";
     if (int rc = set_hints_check(b, who, n)) return rc;
     if (!y32) { b->hinted = false; return 0; }
-    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
-    StageCommit commit{b};   // device work from here on: a failure of it leaves the batch Empty like any other
-    if (int rc = hints_reserve(b)) return rc;
     const size_t bytes = (size_t)n * b->plan->host.n_points * 32;
-    if (bytes) {
+    return hints_stage(b, 0, [&]() -> int {
+        if (!bytes) return 0;
         H2V_HIP_CHECK(hipMemcpyAsync(b->ycanon.p, y32, bytes, hipMemcpyHostToDevice, b->stream));
         H2V_HIP_CHECK(hipStreamSynchronize(b->stream));   // the host buffer is the caller's again
-    }
-    commit.commit(BatchStage::Uploaded);
-    b->hinted = true; b->null_rows = 0;
-    return 0;
+        return 0;
+    });
 }
 
 // A row per proof, or none: the rows given are packed beside zero rows for the others (a zero hint always misses: no point of the
@@ -1126,16 +1129,12 @@ int h2v_batch_set_hint_rows(h2v_batch* b, size_t n, const uint8_t* const* rows) 
     for (size_t i = 0; i < n; ++i)
         if (rows[i]) { if (row_len) memcpy(&flat[i * row_len], rows[i], row_len); } else ++null_rows;
     if (null_rows == n) { b->hinted = false; return 0; }
-    H2V_HIP_CHECK(hipSetDevice(b->ctx->device));
-    StageCommit commit{b};   // device work from here on: a failure of it leaves the batch Empty like any other
-    if (int rc = hints_reserve(b)) return rc;
-    if (!flat.empty()) {
+    return hints_stage(b, null_rows, [&]() -> int {
+        if (flat.empty()) return 0;
         H2V_HIP_CHECK(hipMemcpyAsync(b->ycanon.p, flat.data(), flat.size(), hipMemcpyHostToDevice, b->stream));
         H2V_HIP_CHECK(hipStreamSynchronize(b->stream));   // (flat goes with this call)
-    }
-    commit.commit(BatchStage::Uploaded);
-    b->hinted = true; b->null_rows = (uint32_t)null_rows;
-    return 0;
+        return 0;
+    });
 }
 
 int h2v_batch_set_hints_device(h2v_batch* b, size_t n, const void* d_y32, size_t row_stride) {
@@ -1145,13 +1144,9 @@ int h2v_batch_set_hints_device(h2v_batch* b, size_t n, const void* d_y32, size_t
     if (!d_y32) { b->hinted = false; return 0; }
     const size_t row_len = (size_t)b->plan->host.n_points * 32;
     const int device = b->ctx->device;
-    H2V_HIP_CHECK(hipSetDevice(device));
+    H2V_HIP_CHECK(hipSetDevice(device));   // (the pointer's check asks the runtime: an argument check still, it leaves the stage alone)
     if (n && row_len && (rc = strided_rows_check(who, d_y32, n, row_len, row_stride, device, "reads"))) return rc;
-    StageCommit commit{b};
-    if ((rc = hints_reserve(b)) || (rc = ingest_rows_enqueue(b->stream, d_y32, row_stride, row_len, n, nullptr, 0, b->ycanon.p, nullptr, nullptr, 0))) return rc;
-    commit.commit(BatchStage::Uploaded);
-    b->hinted = true; b->null_rows = 0;
-    return 0;
+    return hints_stage(b, 0, [&] { return ingest_rows_enqueue(b->stream, d_y32, row_stride, row_len, n, nullptr, 0, b->ycanon.p, nullptr, nullptr, 0); });   // (no wait: stream-ordered)
 }
 
 int h2v_batch_hints(h2v_batch* b, size_t first, size_t count, uint8_t* y32) {

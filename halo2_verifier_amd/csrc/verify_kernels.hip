@@ -3,6 +3,7 @@
 //
 //   k_decompress      one lane per (proof, point)   G1Affine::from_bytes               transcript/mod.rs:158-166
 //   k_decompress_hinted  the same with the claimed y beside every point (include/h2v_hints.h): a curve check, the root only on a miss
+//   k_decompress_misses  one lane per point that a wave of k_decompress_hinted with hits and misses listed: its root
 //   k_check_scalars   one lane per (proof, scalar)  Fr::from_repr canonicity           transcript/mod.rs:168-176
 //   k_stream_build    one lane per (proof, 8-byte word of the absorbed stream)         transcript/mod.rs:216-231
 //   k_transcript      four lanes per proof          Blake2b-512 + challenges           transcript/mod.rs:124-133,209-214,500-514
@@ -21,59 +22,72 @@
 
 namespace h2v {
 
-// 32 B in (two 16-byte loads: a point sits at a multiple of 32 bytes inside a proof whose length is a multiple of 32), 72 + 32 B
-// out as 8-byte / 16-byte stores.  Round 1 moved every byte on its own: 13x the algorithmic traffic (profiles/r01_pmc_fetch_write.csv).
-// The kernel asks for 10 KiB of LDS (it uses 4.5): sixteen workgroups, four waves per SIMD, fill a CU's 160 KiB.  With the chained field
-// products the kernel needs 76 registers instead of 120 and would fit six waves per SIMD; the dispatcher fills a CU before it moves on
-// to the next, so a launch that does not fill the chip (the 20-step launch: 1920 waves for 1024 SIMDs) sat on fewer SIMDs and took
-// 542 us instead of 487.  Held to four waves it takes 452 (profiles/field_chain_kernel_stats.txt); caps of three and two measured the same.
-#define K_DECOMPRESS_LDS_WORDS 2560
-__global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
-                                                   uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, uint8_t* __restrict__ ycanon,
-                                                   int* __restrict__ status) {
-    const uint32_t t_raw = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t t = min(t_raw, n * np - 1);   // lanes past the end shadow the last point (all lanes reach the barriers below); their output is not stored
-    uint32_t p = t / np, slot = t % np;
+// ------------------------------------------------------------------ point decompression
+// k_decompress, k_decompress_hinted and k_decompress_misses, and in front of them the steps they share, each force-inlined into its
+// kernels: what is said at a step holds for every kernel that takes it.
+
+// A point's 32 bytes as they lie in its proof, two 16-byte loads (a point sits at a multiple of 32 bytes inside a proof whose length is
+// a multiple of 32; round 1 moved every byte on its own: 13x the algorithmic traffic, profiles/r01_pmc_fetch_write.csv), taken apart
+// as G1Affine::from_bytes (compressed) takes them: flags in the top byte, x below.
+struct PointIn { uint32_t w[8]; bool is_inf, sign; };
+__device__ __forceinline__ PointIn point_load(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets, uint32_t p, uint32_t slot) {
     const uint4* src = reinterpret_cast<const uint4*>(proofs + (size_t)p * proof_len + point_offsets[slot]);
     const uint4 lo = src[0], hi = src[1];
-    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    // G1Affine::from_bytes (compressed): flags in the top byte, x below
-    const bool is_inf = (w[7] >> 24) & G1_FLAG_IDENTITY, sign = (w[7] >> 24) & G1_FLAG_SIGN;
-    w[7] &= 0x3fffffffu;
-    G1A a = G1A::identity();
-    bool ok = !Fq::geq_p(w);
-    uint32_t yraw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok) {
-        const Fq x = Fq::from_raw(w);
-        if (is_inf) ok = false;   // the identity decodes (x = 0, no sign) but cannot be absorbed ("cannot write points at infinity to the transcript"): an error either way
-        else {
-            const Fq three = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
-            const Fq rhs = x.sqr() * x + (three + three + three);
-            Fq y = fq_sqrt_candidate_loop_w3(rhs);
-            if (y.sqr() != rhs) ok = false;
-            else {
-                y.to_raw(yraw);                       // canonical y: its parity decides the sign, its bytes are absorbed
-                uint32_t nz = 0;
+    PointIn in = {{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}, (bool)((hi.w >> 24) & G1_FLAG_IDENTITY), (bool)((hi.w >> 24) & G1_FLAG_SIGN)};
+    in.w[7] &= 0x3fffffffu;
+    return in;
+}
+// the curve's right-hand side, x^3 + 3
+__device__ __forceinline__ Fq curve_rhs(const Fq& x) {
+    const Fq one = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
+    return x.sqr() * x + (one + one + one);
+}
+// a = (x, y) and yraw = the canonical y, from the root of rhs = x^3 + 3 on; false, with a and yraw untouched (the caller
+// refuses the point), where rhs has no root.  The canonical y is needed raw: its parity decides the sign, its bytes are absorbed.
+__device__ __forceinline__ bool point_from_root(const Fq& x, const Fq& rhs, bool sign, G1A& a, uint32_t yraw[8]) {
+    Fq y = fq_sqrt_candidate_loop_w3(rhs);
+    if (y.sqr() != rhs) return false;
+    y.to_raw(yraw);
+    uint32_t nz = 0;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) nz |= yraw[i];
-                if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
-                    y = y.neg();
-                    uint64_t borrow = 0;
+    for (int i = 0; i < 8; ++i) nz |= yraw[i];
+    if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
+        y = y.neg();
+        uint64_t borrow = 0;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)FqParams::P(i) - yraw[i] - borrow; yraw[i] = (uint32_t)d; borrow = (d >> 32) & 1u; }
-                }
-                a.x = x; a.y = y;
-            }
-        }
+        for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)FqParams::P(i) - yraw[i] - borrow; yraw[i] = (uint32_t)d; borrow = (d >> 32) & 1u; }
     }
-    if (!ok) { status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING); a = G1A::identity(); for (int i = 0; i < 8; ++i) yraw[i] = 0; }
-    // Outputs through LDS: consecutive lanes own consecutive points (t = proof * np + slot), so a wave's 64 points are 4608
-    // contiguous bytes and its 64 canonical y are 2048.  Written lane by lane (72-byte stride) every store instruction touched 36
-    // lines partially, and the L2 fetched each of them to merge the bytes: 0.2 GB of reads and 0.14 GB of writes for 26 MB of
-    // output (profiles/r02_pmc_fetch_write_steps20.csv, first collection).  Transposed in LDS, every store instruction writes
-    // 256 contiguous bytes.
+    a.x = x; a.y = y;
+    return true;
+}
+// G1Affine::from_bytes from the bytes on: x < p, not the identity, a root of the right sign
+__device__ __forceinline__ bool point_decode(const PointIn& in, G1A& a, uint32_t yraw[8]) {
+    if (Fq::geq_p(in.w)) return false;
+    const Fq x = Fq::from_raw(in.w);
+    if (in.is_inf) return false;   // the identity decodes (x = 0, no sign) but cannot be absorbed ("cannot write points at infinity to the transcript"): an error either way
+    return point_from_root(x, curve_rhs(x), in.sign, a, yraw);
+}
+// what a point that does not decode leaves in its rows: the identity and a zero y
+__device__ __forceinline__ void point_none(G1A& a, uint32_t yraw[8]) {
+    a = G1A::identity();
+    for (int i = 0; i < 8; ++i) yraw[i] = 0;
+}
+// ... and in its proof's status word, by the slot's kind (status_set: the rank-coded atomic minimum, so the order of refusals does not matter)
+__device__ __forceinline__ void point_refuse(int* __restrict__ status, uint32_t p, uint32_t slot, uint32_t n_main_points, G1A& a, uint32_t yraw[8]) {
+    status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING);
+    point_none(a, yraw);
+}
+// A workgroup's 64 rows of pts, phi and ycanon (the pointers: the launch's first row; `total` rows in the launch), through LDS.
+// Consecutive lanes own consecutive points (t = proof * np + slot), so a wave's 64 points are 4608 contiguous bytes and its 64 canonical
+// y are 2048.  Written lane by lane (72-byte stride) every store instruction touched 36 lines partially, and the L2 fetched each of
+// them to merge the bytes: 0.2 GB of reads and 0.14 GB of writes for 26 MB of output (profiles/r02_pmc_fetch_write_steps20.csv, first
+// collection).  Transposed in LDS, every store instruction writes 256 contiguous bytes.  EVERY lane of the workgroup must come here (five
+// barriers); a lane past the end brings the shadow of the last point, which is not stored.  a.x leaves as beta x.
+// The array asks for 10 KiB (4.5 are used): k_decompress's occupancy cap, see there.
+#define K_DECOMPRESS_LDS_WORDS 2560
+__device__ __forceinline__ void wave_rows_store(G1A& a, const uint32_t yraw[8], uint32_t total, G1A* __restrict__ pts, G1A* __restrict__ phi, uint8_t* ycanon) {
     __shared__ uint32_t out_lds[K_DECOMPRESS_LDS_WORDS];
-    const uint32_t lane = threadIdx.x, t0 = blockIdx.x * blockDim.x, live = min(64u, n * np - t0);
+    const uint32_t lane = threadIdx.x, t0 = blockIdx.x * blockDim.x, live = min(64u, total - t0);
     const uint32_t* av = reinterpret_cast<const uint32_t*>(&a);
 #pragma unroll
     for (int i = 0; i < 18; ++i) out_lds[lane * 18 + i] = av[i];
@@ -99,147 +113,96 @@ __global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict_
     for (int i = 0; i < 8; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 8) dy[k] = out_lds[k]; }
 }
 
+// One lane per (proof, point): 32 B in, 72 + 72 + 32 B out.
+// The kernel asks for 10 KiB of LDS (it uses 4.5): sixteen workgroups, four waves per SIMD, fill a CU's 160 KiB.  With the chained field
+// products the kernel needs 76 registers instead of 120 and would fit six waves per SIMD; the dispatcher fills a CU before it moves on
+// to the next, so a launch that does not fill the chip (the 20-step launch: 1920 waves for 1024 SIMDs) sat on fewer SIMDs and took
+// 542 us instead of 487.  Held to four waves it takes 452 (profiles/field_chain_kernel_stats.txt); caps of three and two measured the same.
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 76 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD.
+__global__ void __launch_bounds__(64, 4) k_decompress(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
+                                                   uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, uint8_t* __restrict__ ycanon,
+                                                   int* __restrict__ status) {
+    const uint32_t total = n * np;
+    const uint32_t t = min(blockIdx.x * blockDim.x + threadIdx.x, total - 1);   // lanes past the end shadow the last point (wave_rows_store)
+    const uint32_t p = t / np, slot = t % np;
+    G1A a;
+    uint32_t yraw[8];
+    if (!point_decode(point_load(proofs, proof_len, point_offsets, p, slot), a, yraw)) point_refuse(status, p, slot, n_main_points, a, yraw);
+    wave_rows_store(a, yraw, total, pts, phi, ycanon);
+}
+
 // k_decompress with a hint per point (include/h2v_hints.h).  The encoding fixes y completely — y^2 = x^3 + 3 and the parity of the
 // canonical y is the sign flag — so the hint h is CHECKED, never trusted: it is used exactly when x < p, the identity flag is clear,
-// h < p, (h & 1) == sign and h^2 == x^3 + 3, and then h IS the canonical y that k_decompress would have found (the two roots y and
+// h < p, (h & 1) == sign and h^2 == x^3 + 3, and then h IS the canonical y that point_from_root would have found (the two roots y and
 // p - y differ in parity, p being odd).  That is two squarings, one product and a comparison instead of the ~320 products of the root.
-// BN254's G1 has prime order, so no point of the curve has y = 0 (it would have order 2): the `nz` branch of k_decompress is dead for
+// BN254's G1 has prime order, so no point of the curve has y = 0 (it would have order 2): the `nz` test of point_from_root is dead for
 // every decodable point and the hinted path needs no special case for it — a zero hint fails h^2 == x^3 + 3 like any other wrong value.
-//
-// A lane whose hint fails computes what k_decompress computes for its point, statuses included (its own copy of that body below:
-// k_decompress itself stays as it is, with its registers and its four waves per SIMD).  The branch is per lane, so the other lanes of
-// the wave wait for the root: one miss in a wave costs the wave a root, and a wave of hits costs none.  The outputs leave through the
-// same LDS transposition, every store instruction contiguous; lanes past the end shadow the last point, and every lane reaches every
-// barrier (the divergent part has none).
 //
 // hints and ycanon may be the same memory (the batch keeps its hints where the canonical y will lie): a workgroup reads the 64 rows of
 // its own lanes before it writes the same 64 rows, and no other workgroup touches them.  Hence no __restrict__ on the two.
 //
 // Misses are counted per wave: a ballot over the live lanes, and one atomic add by lane 0 only when the count is not zero.
 //
-// gfx950 (-Rpass-analysis=kernel-resource-usage): 102 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD
-// (k_decompress beside it, as before this kernel came: 76 VGPRs, 62 SGPRs, 48 bytes of scratch, 10240 bytes of LDS, 4 waves).
-// Launch bounds and LDS: k_decompress's, 64 threads held to four waves per SIMD by a request of 10 KiB of LDS (4.5 used) — four waves
-// is also all that 102 registers allow.  The miss
-// path IS k_decompress's loop, which was measured fastest under that cap when the launch does not fill the chip (see its comment), and
-// a sender of bad hints is promised that speed.  The hit path is too short for the cap to bind at the sizes measured: the 1920 waves of
-// the headline launch are all resident at once under four waves per SIMD (4096 places).  Whether the dispatcher's packing matters to
-// an all-hit launch was not measured apart from that.
+// Then the WAVE decides, from the same ballot, so that one miss does not cost its wave a root.  If all its live lanes miss, each takes
+// its root in place: what k_decompress computes for its point, statuses included; no lane waits for another, and a sender of nothing
+// but bad hints keeps k_decompress's speed.  If it has a hit and a miss, the missing lanes store the placeholder a failed decode
+// stores (point_none) WITHOUT a status, and append their point indices to the list: one returning atomic add per wave by lane 0, the
+// lanes' places from their ranks in the ballot.  k_decompress_misses, enqueued right behind on the same stream, takes those roots
+// densely, 64 listed points per wave whatever waves they came from.  The entries are indices into the whole stage (t_base = p0 x Np of
+// the piece added), written to the piece's own segment of the list, which starts at t_base: a piece lists at most its own points, so
+// the segments of pieces never overlap.  Every lane reaches wave_rows_store (the divergent part has no barrier).
 //
-// LISTED (a stage with a miss list, StageArgs::miss_list): one miss no longer costs its wave a root.  Every live lane is checked as above,
-// and then the WAVE decides, from one ballot: if all its live lanes miss it takes its roots in place, as without a list (no lane waits
-// for another, and a sender of nothing but bad hints keeps that path); if it has a hit and a miss, the missing lanes store the
-// placeholder a failed decode stores (the identity, a zero y) through the same LDS transposition, WITHOUT a status, and append their
-// point indices to the list: one returning atomic add per wave by lane 0, the lanes' places from their ranks in the ballot.
-// k_decompress_misses, enqueued right behind on the same stream, takes those roots densely, 64 listed points per wave whatever waves
-// they came from.  The entries are indices into the whole stage (t_base = p0 x Np of the piece added), written to the piece's own
-// segment of the list, which starts at t_base: a piece lists at most its own points, so the segments of pieces never overlap.
-// The instantiation without a list is the kernel as it was before there was one.
-// gfx950 (-Rpass-analysis=kernel-resource-usage), LISTED: 102 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD
-// (the same figures as without a list).
-#define K_DECOMPRESS_HINTED_LDS_WORDS 2560
-template <bool LISTED>
+// gfx950 (-Rpass-analysis=kernel-resource-usage): 102 VGPRs, 62 SGPRs, no spills, 48 bytes of scratch, 10240 bytes of LDS; 4 waves per SIMD.
+// Launch bounds and LDS: k_decompress's, 64 threads held to four waves per SIMD by the 10 KiB of wave_rows_store — four waves is also
+// all that 102 registers allow.  The root in place IS k_decompress's loop, which was measured fastest under that cap when the launch
+// does not fill the chip (see its comment), and a sender of bad hints is promised that speed.  The hit path is too short for the cap to
+// bind at the sizes measured: the 1920 waves of the headline launch are all resident at once under four waves per SIMD (4096 places).
+// Whether the dispatcher's packing matters to an all-hit launch was not measured apart from that.
 __global__ void __launch_bounds__(64, 4) k_decompress_hinted(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
                                                           uint32_t np, uint32_t n_main_points, uint32_t n, G1A* __restrict__ pts, G1A* __restrict__ phi, const uint8_t* hints,
                                                           uint8_t* ycanon, int* __restrict__ status, uint32_t* __restrict__ misses,
                                                           uint32_t* __restrict__ list, uint32_t* __restrict__ list_count, uint32_t t_base) {
     const uint32_t total = n * np;
     const uint32_t t_raw = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t t = min(t_raw, total - 1);   // lanes past the end shadow the last point (all lanes reach the barriers below); their output is not stored
+    const uint32_t t = min(t_raw, total - 1);   // lanes past the end shadow the last point (wave_rows_store)
     const uint32_t p = t / np, slot = t % np;
-    const uint4* src = reinterpret_cast<const uint4*>(proofs + (size_t)p * proof_len + point_offsets[slot]);
-    const uint4 lo = src[0], hi = src[1];
+    const PointIn in = point_load(proofs, proof_len, point_offsets, p, slot);
     const uint4* hsrc = reinterpret_cast<const uint4*>(hints + (size_t)t * 32);
     const uint4 hlo = hsrc[0], hhi = hsrc[1];
-    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     uint32_t yraw[8] = {hlo.x, hlo.y, hlo.z, hlo.w, hhi.x, hhi.y, hhi.z, hhi.w};   // the hint; on a hit, the canonical y as it is
-    // G1Affine::from_bytes (compressed): flags in the top byte, x below
-    const bool is_inf = (w[7] >> 24) & G1_FLAG_IDENTITY, sign = (w[7] >> 24) & G1_FLAG_SIGN;
-    w[7] &= 0x3fffffffu;
-    G1A a = G1A::identity();
-    // the identity decodes (x = 0, no sign) but cannot be absorbed: an error either way (k_decompress)
-    bool ok = !Fq::geq_p(w) && !is_inf;
+    G1A a;
+    const bool ok = !Fq::geq_p(in.w) && !in.is_inf;   // (point_decode's first two refusals)
     bool hit = false;
     Fq x = Fq::zero(), rhs = Fq::zero();
     if (ok) {
-        x = Fq::from_raw(w);
-        const Fq three = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
-        rhs = x.sqr() * x + (three + three + three);
-        if (!Fq::geq_p(yraw) && (bool)(yraw[0] & 1u) == sign) {
+        x = Fq::from_raw(in.w);
+        rhs = curve_rhs(x);
+        if (!Fq::geq_p(yraw) && (bool)(yraw[0] & 1u) == in.sign) {
             const Fq h = Fq::from_raw(yraw);
             if (h.sqr() == rhs) { hit = true; a.x = x; a.y = h; }
         }
     }
     const unsigned long long missed = __ballot(!hit && t_raw < total);
     if (missed && threadIdx.x == 0) atomicAdd(misses, (uint32_t)__popcll(missed));
-    bool in_place = true;   // (uniform over the wave)
-    if constexpr (LISTED) {
-        in_place = missed == __ballot(t_raw < total);
-        if (missed && !in_place) {
-            uint32_t at = 0;
-            if (threadIdx.x == 0) at = atomicAdd(list_count, (uint32_t)__popcll(missed));   // (lane 0 is live in every workgroup)
-            at = __shfl(at, 0);
-            if (!hit && t_raw < total) list[at + (uint32_t)__popcll(missed & ((1ull << threadIdx.x) - 1))] = t_base + t;
-        }
+    const bool in_place = missed == __ballot(t_raw < total);   // (uniform over the wave)
+    if (missed && !in_place) {
+        uint32_t at = 0;
+        if (threadIdx.x == 0) at = atomicAdd(list_count, (uint32_t)__popcll(missed));   // (lane 0 is live in every workgroup)
+        at = __shfl(at, 0);
+        if (!hit && t_raw < total) list[at + (uint32_t)__popcll(missed & ((1ull << threadIdx.x) - 1))] = t_base + t;
     }
-    if (!hit && !in_place) { a = G1A::identity(); for (int i = 0; i < 8; ++i) yraw[i] = 0; }   // the placeholder; k_decompress_misses writes the point and its status
-    if (!hit && in_place) {
-        // k_decompress's body for this point, from the root on
-        if (ok) {
-            Fq y = fq_sqrt_candidate_loop_w3(rhs);
-            if (y.sqr() != rhs) ok = false;
-            else {
-                y.to_raw(yraw);                       // canonical y: its parity decides the sign, its bytes are absorbed
-                uint32_t nz = 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) nz |= yraw[i];
-                if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
-                    y = y.neg();
-                    uint64_t borrow = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)FqParams::P(i) - yraw[i] - borrow; yraw[i] = (uint32_t)d; borrow = (d >> 32) & 1u; }
-                }
-                a.x = x; a.y = y;
-            }
-        }
-        if (!ok) { status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING); a = G1A::identity(); for (int i = 0; i < 8; ++i) yraw[i] = 0; }
-    }
-    // outputs through LDS, as k_decompress writes them: every store instruction writes 256 contiguous bytes
-    __shared__ uint32_t out_lds[K_DECOMPRESS_HINTED_LDS_WORDS];
-    const uint32_t lane = threadIdx.x, t0 = blockIdx.x * blockDim.x, live = min(64u, total - t0);
-    const uint32_t* av = reinterpret_cast<const uint32_t*>(&a);
-#pragma unroll
-    for (int i = 0; i < 18; ++i) out_lds[lane * 18 + i] = av[i];
-    __syncthreads();
-    uint32_t* dp = reinterpret_cast<uint32_t*>(pts + t0);
-#pragma unroll
-    for (int i = 0; i < 18; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 18) dp[k] = out_lds[k]; }
-    __syncthreads();
-    // phi(P) = (beta x, y) beside every point (msm.hip: msm_entry_load)
-    a.x = g1_beta_times(a.x);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out_lds[lane * 18 + i] = av[i];     // (y is still there)
-    __syncthreads();
-    dp = reinterpret_cast<uint32_t*>(phi + t0);
-#pragma unroll
-    for (int i = 0; i < 18; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 18) dp[k] = out_lds[k]; }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out_lds[lane * 8 + i] = yraw[i];
-    __syncthreads();
-    uint32_t* dy = reinterpret_cast<uint32_t*>(ycanon + (size_t)t0 * 32);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint32_t k = i * 64 + lane; if (k < live * 8) dy[k] = out_lds[k]; }
+    if (!hit && !in_place) point_none(a, yraw);   // the placeholder; k_decompress_misses writes the point and its status
+    if (!hit && in_place && !(ok && point_from_root(x, rhs, in.sign, a, yraw))) point_refuse(status, p, slot, n_main_points, a, yraw);
+    wave_rows_store(a, yraw, total, pts, phi, ycanon);
 }
 
-// The roots that the mixed waves of k_decompress_hinted<true> left out, densely: lane i below *list_count takes point t = list[i] of the
-// stage (an index over all its proofs: the pointers are the stage's own, not a piece's) with k_decompress's body from the proof bytes
-// on, and writes that point's pts, phi and ycanon rows and, where it does not decode, its proof's status (status_set: the rank-coded
-// atomic minimum, so the order of the list does not matter).  The grid is fixed from the piece's size on the host, which never reads
-// the count: a workgroup past the count leaves at once.  The listed points are scattered, so the rows are stored lane by lane (72 and
-// 32 bytes each, as 8- and 16-byte stores) and not through LDS; rows that are not listed are not touched, so hints and ycanon may
-// still be the same memory.  Launched with k_decompress's 10 KiB of LDS (dynamic: none is used), which holds it to the four waves per
-// SIMD that k_decompress's root loop was measured fastest at.
+// The roots that the mixed waves of k_decompress_hinted left out, densely: lane i below *list_count takes point t = list[i] of the
+// stage (an index over all its proofs: the pointers are the stage's own, not a piece's) from the proof bytes on, and writes that
+// point's pts, phi and ycanon rows and, where it does not decode, its proof's status.  The grid is fixed from the piece's size on the
+// host, which never reads the count: a workgroup past the count leaves at once.  The listed points are scattered, so the rows are
+// stored lane by lane (72 and 32 bytes each, as 8- and 16-byte stores) and not through LDS; rows that are not listed are not touched,
+// so hints and ycanon may still be the same memory.  Launched with k_decompress's 10 KiB of LDS (dynamic: none is used), which holds it
+// to the four waves per SIMD that k_decompress's root loop was measured fastest at.
 // gfx950 (-Rpass-analysis=kernel-resource-usage): 76 VGPRs, 39 SGPRs, no spills, 48 bytes of scratch, no static LDS; 6 waves per SIMD by its
 // registers, 4 under the launch's LDS request.
 __global__ void __launch_bounds__(64, 4) k_decompress_misses(const uint8_t* __restrict__ proofs, uint32_t proof_len, const uint32_t* __restrict__ point_offsets,
@@ -249,38 +212,9 @@ __global__ void __launch_bounds__(64, 4) k_decompress_misses(const uint8_t* __re
     if (i >= *list_count) return;
     const uint32_t t = list[i];
     const uint32_t p = t / np, slot = t % np;
-    const uint4* src = reinterpret_cast<const uint4*>(proofs + (size_t)p * proof_len + point_offsets[slot]);
-    const uint4 lo = src[0], hi = src[1];
-    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const bool is_inf = (w[7] >> 24) & G1_FLAG_IDENTITY, sign = (w[7] >> 24) & G1_FLAG_SIGN;
-    w[7] &= 0x3fffffffu;
-    G1A a = G1A::identity();
-    bool ok = !Fq::geq_p(w);
-    uint32_t yraw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok) {
-        const Fq x = Fq::from_raw(w);
-        if (is_inf) ok = false;   // (k_decompress)
-        else {
-            const Fq three = {{FqParams::ONE(0), FqParams::ONE(1), FqParams::ONE(2), FqParams::ONE(3), FqParams::ONE(4), FqParams::ONE(5), FqParams::ONE(6), FqParams::ONE(7), FqParams::ONE(8)}};
-            const Fq rhs = x.sqr() * x + (three + three + three);
-            Fq y = fq_sqrt_candidate_loop_w3(rhs);
-            if (y.sqr() != rhs) ok = false;
-            else {
-                y.to_raw(yraw);                       // canonical y: its parity decides the sign, its bytes are absorbed
-                uint32_t nz = 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) nz |= yraw[k];
-                if ((bool)(yraw[0] & 1u) != sign && nz) {   // the other root: p - y (y = 0 is its own negative)
-                    y = y.neg();
-                    uint64_t borrow = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) { const uint64_t d = (uint64_t)FqParams::P(k) - yraw[k] - borrow; yraw[k] = (uint32_t)d; borrow = (d >> 32) & 1u; }
-                }
-                a.x = x; a.y = y;
-            }
-        }
-    }
-    if (!ok) { status_set(status, p, slot < n_main_points ? H2V_DEV_ST_TRANSCRIPT : H2V_DEV_ST_OPENING); a = G1A::identity(); for (int k = 0; k < 8; ++k) yraw[k] = 0; }
+    G1A a;
+    uint32_t yraw[8];
+    if (!point_decode(point_load(proofs, proof_len, point_offsets, p, slot), a, yraw)) point_refuse(status, p, slot, n_main_points, a, yraw);
     const uint2* av = reinterpret_cast<const uint2*>(&a);   // (a G1A: 18 words, 8-byte aligned)
     uint2* dp = reinterpret_cast<uint2*>(pts + t);
 #pragma unroll
@@ -998,34 +932,25 @@ int decompress_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uin
     const Plan& pl = *g.plan;
     const uint32_t m = p1 - p0, tp = m * pl.n_points;
     if (!tp) return 0;
-    if (g.hints) return decompress_hinted_range_enqueue(s, g, p0, p1);   // k_decompress_hinted: the same outputs, a square root only where a hint fails
-    hipLaunchKernelGGL(k_decompress, dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, m,
-                       g.pts + (size_t)p0 * pl.n_points, g.phi + (size_t)p0 * pl.n_points, g.ycanon + (size_t)p0 * pl.n_points * 32, g.status + p0);
-    H2V_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-int decompress_hinted_range_enqueue(hipStream_t s, const StageArgs& g, uint32_t p0, uint32_t p1) {
-    if (p1 <= p0) return 0;
-    const Plan& pl = *g.plan;
-    const uint32_t m = p1 - p0, tp = m * pl.n_points;
-    if (!tp) return 0;
-    if (!g.hints || !g.hint_misses) { set_last_error("decompress_hinted_range_enqueue: hints without a miss word"); return H2V_ERR_BAD_ARGUMENT; }
-    const size_t off = (size_t)p0 * pl.n_points;   // the hints' rows are the points': offset by p0 exactly as ycanon is
-    if (!g.miss_list) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decompress_hinted<false>), dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p,
-                           pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses, nullptr, nullptr, 0u);
+    const size_t off = (size_t)p0 * pl.n_points;   // the piece's first row of pts, phi, ycanon and (their rows are the points') the hints
+    const uint8_t* proofs = g.proofs + (size_t)p0 * pl.proof_len;
+    uint8_t* ycanon = g.ycanon + off * 32;
+    const dim3 grid((tp + 63) / 64), block(64);
+    if (!g.hints) {
+        hipLaunchKernelGGL(k_decompress, grid, block, 0, s, proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, ycanon, g.status + p0);
         H2V_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // With a list: the piece's segment of it starts at its first point, and its counter is cleared here, on the stream, in front of its
-    // two kernels — so a piece neither sees nor redoes an earlier piece's entries, and every call leaves its own range complete.
-    if (!g.miss_list_count) { set_last_error("decompress_hinted_range_enqueue: a miss list without its counter"); return H2V_ERR_BAD_ARGUMENT; }
+    // With hints: k_decompress_hinted, the same outputs with a square root only where a hint fails, and k_decompress_misses behind it.
+    // The piece's segment of the list starts at its first point, and its counter is cleared here, on the stream, in front of its two
+    // kernels — so a piece neither sees nor redoes an earlier piece's entries, and every call leaves its own range complete.
+    if (!g.hint_misses) { set_last_error("decompress_range_enqueue: hints without a miss word"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!g.miss_list || !g.miss_list_count) { set_last_error("decompress_range_enqueue: hints without a miss list and its counter"); return H2V_ERR_BAD_ARGUMENT; }
     H2V_HIP_CHECK(hipMemsetAsync(g.miss_list_count, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decompress_hinted<true>), dim3((tp + 63) / 64), dim3(64), 0, s, g.proofs + (size_t)p0 * pl.proof_len, pl.proof_len, g.pd->point_offsets.p,
-                       pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32, g.ycanon + off * 32, g.status + p0, g.hint_misses, g.miss_list + off,
-                       g.miss_list_count, (uint32_t)off);
-    hipLaunchKernelGGL(k_decompress_misses, dim3((tp + 63) / 64), dim3(64), K_DECOMPRESS_LDS_WORDS * sizeof(uint32_t), s, g.proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points,
-                       pl.n_main_points, g.pts, g.phi, g.ycanon, g.status, g.miss_list + off, g.miss_list_count);
+    hipLaunchKernelGGL(k_decompress_hinted, grid, block, 0, s, proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points, m, g.pts + off, g.phi + off, g.hints + off * 32,
+                       ycanon, g.status + p0, g.hint_misses, g.miss_list + off, g.miss_list_count, (uint32_t)off);
+    hipLaunchKernelGGL(k_decompress_misses, grid, block, K_DECOMPRESS_LDS_WORDS * sizeof(uint32_t), s, g.proofs, pl.proof_len, g.pd->point_offsets.p, pl.n_points, pl.n_main_points,
+                       g.pts, g.phi, g.ycanon, g.status, g.miss_list + off, g.miss_list_count);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

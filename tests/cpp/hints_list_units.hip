@@ -1,8 +1,7 @@
-// The decompression stage with point hints AND a miss list (k_decompress_hinted<true> and k_decompress_misses,
+// The decompression stage with point hints and their miss list (k_decompress_hinted and k_decompress_misses,
 // halo2_verifier_amd/csrc/verify_kernels.hip; include/h2v_hints.h), on points and hints programmed by
 // tests/test_gpu_hints_list_units.py and compared there with tests/hints_reference.py and with the same stage without hints.  Built
-// with the library's flags by halo2_verifier_amd/csrc/Makefile (build/hints_list_units); the prelude is tests/cpp/units.h.  The stage
-// without a list is tests/cpp/hints_units.hip's.
+// with the library's flags by halo2_verifier_amd/csrc/Makefile (build/hints_list_units); the prelude is tests/cpp/units.h.
 //
 //   hints_list_units decompress IN OUT   decompress_begin / _range (in the pieces the input gives) / _finish; a job with hints runs with the list
 //

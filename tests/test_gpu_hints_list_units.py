@@ -1,9 +1,9 @@
-"""The hinted decompression stage with a miss list (k_decompress_hinted<true> + k_decompress_misses,
+"""The hinted decompression stage with its miss list (k_decompress_hinted + k_decompress_misses,
 halo2_verifier_amd/csrc/verify_kernels.hip; include/h2v_hints.h), through tests/cpp/hints_list_units.hip and the launchers
 decompress_begin_enqueue / decompress_range_enqueue / decompress_finish_enqueue, on programmed points and hints.  Every job with hints
-runs with the list given (the stage without one is tests/test_gpu_hints_units.py's).
+runs with the list given: there is no hinted stage without one.
 
-With a list a wave of the first kernel whose live lanes all miss takes its roots in place; a wave with a hit and a miss stores a
+A wave of the first kernel whose live lanes all miss takes its roots in place; a wave with a hit and a miss stores a
 placeholder for its misses and lists their point indices, and the second kernel takes those roots densely.  Whatever the hints: pts,
 phi (as field elements), ycanon bytes and status words equal the unhinted stage's on the same points, which itself agrees with
 hints_reference.decode; the miss word is hints_reference.count_misses; the list holds exactly the points of mixed waves that missed,
@@ -247,7 +247,12 @@ def test_the_sets_are_what_they_are_named_for(results):
             if pset == "valid":
                 assert listed == 0
         elif kind in ("zero", "other_root", "plus_p", "random"):
-            assert miss == total and listed == 0                    # whole-miss waves only: roots in place, as without a list
+            assert miss == total and listed == 0                    # whole-miss waves only: roots in place
+        elif kind == "lane0_wrong":
+            waves = (total + 63) // 64      # of the whole run: lane t of it owns point t, whatever the pieces
+            assert bad <= miss <= bad + waves and miss >= (1 if pset == "valid" else 0)
+        elif kind == "even_lanes":
+            assert miss == sum(1 for t, pt in enumerate(flat) if t % 2 or decode(pt) is None)
         elif kind in ("lane0", "lane63", "last_live") and pset == "valid":
             assert miss == sum(1 for t in range(total) if {"lane0": t % 64 == 0, "lane63": t % 64 == 63, "last_live": t == min(t // 64 * 64 + 63, total - 1)}[kind])
         elif kind == "alt_proofs" and pset == "valid":

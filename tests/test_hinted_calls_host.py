@@ -64,7 +64,8 @@ def test_the_stage_takes_a_miss_list_last_and_null_by_default():
     fields = re.findall(r"^\s+(?:const )?\w[\w ]*\*+ ?(\w+) = nullptr;", body, re.M)
     assert fields == ["hint_misses", "hints", "miss_list", "miss_list_count"]
     kernels = open(os.path.join(ROOT, "halo2_verifier_amd", "csrc", "verify_kernels.hip")).read()
-    assert "k_decompress_misses" in kernels and "k_decompress_hinted<true>" in kernels and "k_decompress_hinted<false>" in kernels
+    # one hinted kernel, always with the list: no instantiation without one
+    assert "k_decompress_misses" in kernels and "k_decompress_hinted(" in kernels and "k_decompress_hinted<" not in kernels and "LISTED" not in kernels
 
 
 def test_null_arguments_are_refused_before_any_device_work(lib):

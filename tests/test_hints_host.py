@@ -1,6 +1,6 @@
 """Point hints on the host (include/h2v_hints.h): where its seven entry points are declared, exported and bound, the C++ mirror's
 header, h2v_hints_from_points — host code, no device — against tests/hints_reference.decode, and the Python refusals that need no
-library.  The kernel is tests/test_gpu_hints_units.py's, the entry points on a GPU tests/test_gpu_hints.py's."""
+library.  The kernel is tests/test_gpu_hints_list_units.py's, the entry points on a GPU tests/test_gpu_hints.py's."""
 import ctypes
 import os
 import random
