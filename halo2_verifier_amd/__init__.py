@@ -16,4 +16,5 @@ from . import draws  # noqa: F401
 from .draws import expand, expand_tensor, new_seed  # noqa: F401
 from . import guards  # noqa: F401
 from . import hints  # noqa: F401
+from . import feed  # noqa: F401
 from . import distributed  # noqa: F401

@@ -38,19 +38,28 @@
 //     (L, R) <- (prod_g M_g) (L, R) + sum_g W_g S_g,     W_g = prod_{f > g} M_f
 // k_leg_weights (verify_kernels.hip) makes the scalars, one k_accumulator_scale launch of G + 1 items the records, k_accumulator_legs_fold
 // (util.hip) the journal's G entries and the accumulator, as the last step.
+//
+// An enqueued feed (h2v_accumulator_feed_batch, include/h2v_feed.h): process_batch for a LAUNCHED batch, with no host wait.  The
+// accumulator's stream waits for an event on the batch's stream; k_feed_gather and k_feed_weights read the batch into l_pairs / l_words
+// and the batch's read event is recorded; k_accumulator_scale, k_accumulator_legs_fold and k_feed_report follow.  The host keeps a Feed
+// per call: the journal slots it reserved at enqueue (out of free_slots, so that later calls cannot take them) and a pinned block
+// with those slots for the fold and the report for h2v_accumulator_settle, which commits or releases them.  Every other entry point
+// settles first (settle_feeds), so below this comment "idle" reads "idle, or holding only enqueued feeds".
 #include "../../include/h2v.h"
 #include "../../include/h2v_hint_rows.h"
+#include "../../include/h2v_feed.h"
 #include "batch.h"
 #include "msm_object.h"
 #include <string.h>
 #include <algorithm>
+#include <deque>
 #include <functional>
 
 using namespace h2v;
 
 struct h2v_accumulator {
     h2v_ctx* ctx = nullptr;          // the params (same_srs for every context of a process call), the pairing tables, add_msm's MSMs
-    hipStream_t stream = nullptr;    // its own, of the highest priority (h2v_accumulator_create); idle whenever a call returns
+    hipStream_t stream = nullptr;    // its own, of the highest priority (h2v_accumulator_create); idle whenever a call returns, or holding only enqueued feeds
     DevBuf<G1J> acc;                 // [0] left, [1] right: whole Jacobian points
     DevBuf<uint8_t> records;         // [0] the staging record (the scaled accumulator), [1 ..] the records of a call's groups (at most H2V_MAX_SHAPES_PER_CALL)
     DevBuf<uint32_t> scalar;         // M of the call in flight, 8 canonical words
@@ -82,6 +91,20 @@ struct h2v_accumulator {
     DevBuf<uint32_t> l_words;        // [8 (G + 1)] prod M_g and the W_g, [8 G] the M_g, [G] the journal slots of the G new entries
     MappedHostBuf l_legs;            // [32 G] the M_g as they come back (pinned: the copy is enqueued between the launches and must not hold the host)
     std::vector<uint32_t> l_host;    // [G] what the slots are copied from
+    // enqueued feeds (h2v_accumulator_feed_batch): they share l_pairs, l_records and l_words, which stream order serialises — for a feed
+    // l_words is [8 (G + 1)] the weights, [8 G] the M_g, [G] the groups' sizes, [G] their failed counts, [1] rc
+    struct Feed {
+        std::unique_ptr<MappedHostBuf> block;   // pinned, the feed's own until it is reported: [4 + 10 G] the report (k_feed_report), [G] the journal slots (the host's, read by the fold)
+        uint32_t n = 0, G = 0;
+        std::vector<uint32_t> slots;            // the journal slots reserved at enqueue (journal off: none)
+        bool settled = false;
+        int rc = 0; size_t failed = 0;          // of a settled feed
+    };
+    std::deque<Feed> feeds;          // the feeds not reported yet, in feed order: settled ones first
+    size_t f_unsettled = 0;
+    std::vector<std::unique_ptr<MappedHostBuf>> f_blocks;   // blocks of reported feeds, for the next ones
+    std::vector<void*> f_retired;    // device arrays that grew under a pending feed: freed at settle (hipFree would wait for the device)
+    hipEvent_t ev_batch = nullptr;   // recorded on a fed batch's stream; this stream waits for it
     // process_guards: staging buffers and an MSM workspace of its own (grow-only), so that accumulators that share a context do not meet
     GuardStage g_stage;              // the call's terms
     MsmWorkspace g_ws;               // the two pooled channels
@@ -92,6 +115,8 @@ struct h2v_accumulator {
 
 namespace {
 
+void store_u32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); }
+int settle_feeds(h2v_accumulator* a, const char* who);
 // every operation of the object ends here: its stream is idle when a call returns
 int sync(h2v_accumulator* a, const char* who) {
     const hipError_t e = hipStreamSynchronize(a->stream);
@@ -103,6 +128,7 @@ int sync(h2v_accumulator* a, const char* who) {
 int read_points(h2v_accumulator* a, const char* who, int* ok, uint8_t* out_left, uint8_t* out_right) {
     H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
     int rc;
+    if ((rc = settle_feeds(a, who))) return rc;
     uint32_t okv = 0; uint8_t out[128];
     if (ok && (rc = pairing_check_enqueue(a->stream, a->ctx->pairing, a->acc.p, 1, a->words.p + 1))) return rc;
     if ((rc = point_to_bytes_enqueue(a->stream, a->acc.p, a->bytes.p, a->words.p + 2, 2))) return rc;
@@ -119,10 +145,56 @@ int read_points(h2v_accumulator* a, const char* who, int* ok, uint8_t* out_left,
 G1J* next_slot(h2v_accumulator* a) { return a->j_cap ? a->j_sums.p + 2 * (size_t)a->free_slots.back() : nullptr; }
 bool journal_full(const h2v_accumulator* a) { return a->j_cap && a->entries.size() >= a->j_cap; }
 // the entry of a call that has just succeeded becomes visible
-void commit_entry(h2v_accumulator* a, const Fr& M, size_t n_proofs, size_t n_failed) {
+constexpr uint32_t NEXT_FREE_SLOT = 0xffffffffu;
+// (slot: one that an enqueued feed took out of free_slots when it was enqueued)
+void commit_entry(h2v_accumulator* a, const Fr& M, size_t n_proofs, size_t n_failed, uint32_t slot = NEXT_FREE_SLOT) {
     if (!a->j_cap) return;
+    if (slot != NEXT_FREE_SLOT) { a->entries.push_back({slot, M, n_proofs, n_failed}); return; }
     a->entries.push_back({a->free_slots.back(), M, n_proofs, n_failed});
     a->free_slots.pop_back();
+}
+// The host's half of every enqueued feed that has none yet, in feed order, behind one synchronise of the stream: a feed whose report
+// says 0 commits its counters and one entry per group in the slots it reserved; a dropped feed (a draw >= r, found by k_feed_weights:
+// the points kept their value) gives its slots back, leaves no entry and counts its n proofs as processed AND failed.  The reports stay
+// queued for h2v_accumulator_settle.  What every entry point but feed_batch and pending begins with; nothing pending: no HIP call.
+int settle_feeds(h2v_accumulator* a, const char* who) {
+    if (!a->f_unsettled) return 0;
+    hipSetDevice(a->ctx->device);
+    const hipError_t e = hipStreamSynchronize(a->stream);
+    if (e != hipSuccess) { set_last_error(std::string(who) + ": " + hipGetErrorString(e)); return H2V_ERR_DEVICE; }
+    bool released = false;
+    for (auto& f : a->feeds) {
+        if (f.settled) continue;
+        const volatile uint32_t* rep = reinterpret_cast<const volatile uint32_t*>(f.block->p);
+        f.rc = (int)rep[0];
+        if (f.rc == 0) {
+            f.failed = rep[3];
+            for (uint32_t g = 0; g < f.G && a->j_cap; ++g) {
+                uint8_t m_bytes[32];
+                for (int j = 0; j < 8; ++j) store_u32(m_bytes + 4 * j, rep[4 + 10 * (size_t)g + j]);
+                Fr M;
+                Fr::from_bytes(m_bytes, M);
+                commit_entry(a, M, rep[4 + 10 * (size_t)g + 8], rep[4 + 10 * (size_t)g + 9], f.slots[g]);
+            }
+        } else {
+            f.failed = f.n;
+            for (uint32_t sl : f.slots) { a->free_slots.push_back(sl); released = true; }
+        }
+        a->n_proofs += f.n; a->n_failed += f.failed;
+        f.slots.clear();
+        f.settled = true;
+    }
+    if (released) std::sort(a->free_slots.begin(), a->free_slots.end(), std::greater<uint32_t>());
+    a->f_unsettled = 0;
+    for (void* p : a->f_retired) hipFree(p);
+    a->f_retired.clear();
+    return 0;
+}
+// a grow-only array of an accumulator with feeds in flight: the old allocation is kept until settle (a feed's kernels may still use it)
+template <class T> int grow_under_feeds(h2v_accumulator* a, DevBuf<T>& buf, size_t count) {
+    if (buf.p && count <= buf.cap) return 0;
+    if (buf.p && a->f_unsettled) { a->f_retired.push_back(buf.p); buf.p = nullptr; buf.cap = 0; }
+    return buf.alloc(count);
 }
 void journal_off(h2v_accumulator* a) { a->j_cap = 0; a->entries.clear(); a->free_slots.clear(); }
 
@@ -165,7 +237,6 @@ int merge_impl(h2v_accumulator* a, const char* who, size_t K, const uint8_t* dra
 }
 uint32_t load_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t load_u64(const uint8_t* p) { return (uint64_t)load_u32(p) | ((uint64_t)load_u32(p + 4) << 32); }
-void store_u32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); }
 void store_u64(uint8_t* p, uint64_t v) { store_u32(p, (uint32_t)v); store_u32(p + 4, (uint32_t)(v >> 32)); }
 
 }  // namespace
@@ -197,7 +268,9 @@ int h2v_accumulator_create(h2v_ctx* ctx, h2v_accumulator** out) {
 void h2v_accumulator_destroy(h2v_accumulator* a) {
     if (!a) return;
     hipSetDevice(a->ctx->device);
-    if (a->stream) { hipStreamSynchronize(a->stream); hipStreamDestroy(a->stream); }
+    if (a->stream) { hipStreamSynchronize(a->stream); hipStreamDestroy(a->stream); }   // (enqueued feeds included: their batches are free of this object afterwards)
+    for (void* p : a->f_retired) hipFree(p);
+    if (a->ev_batch) hipEventDestroy(a->ev_batch);
     delete a;
 }
 
@@ -209,6 +282,7 @@ static int process_proofs(const char* who, h2v_accumulator* a, h2v_ctx* const* c
     if (!a || (n && !key_of_proof)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     std::vector<CallGroup> groups;
     int rc;
+    if ((rc = settle_feeds(a, who))) return rc;
     if ((rc = grouped_call_args(who, ctxs, n_keys, key_of_proof, n, proofs, proof_lens, instances32, n_instance_columns, col_lens, groups))) return rc;
     for (size_t k = 0; k < n_keys; ++k) {
         if (ctxs[k]->device != a->ctx->device) { set_last_error(std::string(who) + ": a context on another device than the accumulator"); return H2V_ERR_BAD_ARGUMENT; }
@@ -281,6 +355,7 @@ int h2v_accumulator_process_guards(h2v_accumulator* a, size_t n, const size_t* l
     if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     GuardArgs g{n, {left_counts, right_counts}, {left_scalars32, right_scalars32}, {left_bases64, right_bases64}, {}};
     int rc;
+    if ((rc = settle_feeds(a, who))) return rc;
     if ((rc = guard_args_check(who, g))) return rc;
     std::vector<uint8_t> os_rand;
     if ((rc = resolve_draws(rand32, n, os_rand, who))) return rc;
@@ -339,6 +414,7 @@ int h2v_accumulator_process_batch(h2v_accumulator* a, h2v_batch* b, size_t* n_pr
     const char* who = "h2v_accumulator_process_batch";
     // every argument check comes before the first HIP call
     if (!a || !b) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     if (b->stage != BatchStage::Finished) { set_last_error(std::string(who) + ": the batch has no finished launch (h2v_batch_finish / _finish_groups)"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->last.folded) { set_last_error(std::string(who) + ": a fold ran since the launch: the batch holds the folded records' sums, not its own"); return H2V_ERR_BAD_ARGUMENT; }
     if (b->n_tail != b->n) { set_last_error(std::string(who) + ": the batch is a shard (a tail of draws longer than the upload)"); return H2V_ERR_BAD_ARGUMENT; }
@@ -402,6 +478,7 @@ int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, c
     const char* who = "h2v_accumulator_add_msm";
     if (!a || (n_left && (!left_scalars32 || !left_bases64)) || (n_right && (!right_scalars32 || !right_bases64))) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (n_left > (1u << 24) || n_right > (1u << 24)) { set_last_error(std::string(who) + ": too many terms"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     const uint8_t* sc[2] = {left_scalars32, right_scalars32};
     const size_t ns[2] = {n_left, n_right};
     for (int side = 0; side < 2; ++side)
@@ -436,6 +513,7 @@ int h2v_accumulator_add_msm(h2v_accumulator* a, const uint8_t* left_scalars32, c
 int h2v_accumulator_add_msms(h2v_accumulator* a, h2v_msm* left, h2v_msm* right) {
     const char* who = "h2v_accumulator_add_msms";
     if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     if (journal_full(a)) { set_last_error(std::string(who) + ": the journal is full"); return H2V_ERR_UNSUPPORTED; }
     // both channels are evaluated before anything of the accumulator changes (its stream is idle: the context's stream writes `jacobian`)
     int rc;
@@ -472,6 +550,7 @@ int h2v_accumulator_journal_begin(h2v_accumulator* a, size_t capacity) {
     const char* who = "h2v_accumulator_journal_begin";
     if (!a) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
     if (capacity == 1 || capacity > H2V_ACC_JOURNAL_MAX) { set_last_error(std::string(who) + ": capacity must be 0 or in [2, H2V_ACC_JOURNAL_MAX]"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     journal_off(a);
     if (!capacity) return 0;
     H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
@@ -492,6 +571,7 @@ int h2v_accumulator_journal_begin(h2v_accumulator* a, size_t capacity) {
 int h2v_accumulator_check_legs(h2v_accumulator* a, size_t cap, size_t* n_legs, size_t* leg_proofs, size_t* leg_failed, int* leg_pairing_ok) {
     const char* who = "h2v_accumulator_check_legs";
     if (!a || !n_legs) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     const size_t J = a->entries.size();
     *n_legs = J;
     if ((leg_proofs || leg_failed || leg_pairing_ok) && cap < J) { set_last_error(std::string(who) + ": the arrays are shorter than the journal"); return H2V_ERR_BAD_ARGUMENT; }
@@ -517,6 +597,7 @@ int h2v_accumulator_check_legs(h2v_accumulator* a, size_t cap, size_t* n_legs, s
 int h2v_accumulator_drop_legs(h2v_accumulator* a, const size_t* legs, size_t n_drop) {
     const char* who = "h2v_accumulator_drop_legs";
     if (!a || (n_drop && !legs)) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rcs = settle_feeds(a, who)) return rcs;
     if (!a->j_cap) { set_last_error(std::string(who) + ": the journal is off"); return H2V_ERR_BAD_ARGUMENT; }
     const size_t J = a->entries.size();
     std::vector<bool> drop(J, false);
@@ -573,6 +654,8 @@ int h2v_accumulator_merge(h2v_accumulator* dst, h2v_accumulator* const* srcs, si
     }
     std::vector<uint8_t> os_draws;
     int rc;
+    if ((rc = settle_feeds(dst, who))) return rc;
+    for (size_t k = 0; k < n_src; ++k) if ((rc = settle_feeds(srcs[k], who))) return rc;
     if ((rc = merge_args(dst, who, n_src, draws32, os_draws))) return rc;
     if (!n_src) return 0;
     H2V_HIP_CHECK(hipSetDevice(dst->ctx->device));
@@ -613,6 +696,7 @@ int h2v_accumulator_merge_states(h2v_accumulator* dst, const uint8_t* states, si
     }
     std::vector<uint8_t> os_draws;
     int rc;
+    if ((rc = settle_feeds(dst, who))) return rc;
     if ((rc = merge_args(dst, who, n, draws32, os_draws))) return rc;
     if (!n) return 0;
     H2V_HIP_CHECK(hipSetDevice(dst->ctx->device));
@@ -632,6 +716,106 @@ int h2v_accumulator_merge_states(h2v_accumulator* dst, const uint8_t* states, si
         if (h_flags[i]) { set_last_error(std::string(who) + ": a state with a point that is not canonical or not on the curve"); return H2V_ERR_BAD_ARGUMENT; }
     if ((rc = merge_impl(dst, who, n, draws32, np.data(), nf.data(), drain))) return rc;
     if (out_draws32) memcpy(out_draws32, draws32, 32 * n);
+    return 0;
+}
+
+// h2v_accumulator_process_batch, enqueued (include/h2v_feed.h).  On the batch's stream join_tail / ensure_whole and an event; on the
+// accumulator's stream, behind that event:
+//   k_feed_gather             l_pairs <- [(L, R), S_0 .. S_{G-1}]; the groups' sizes and failed counts from the device's status words
+//   k_feed_weights            k_leg_weights, failing closed on the upload's fault word: [1, 0 .. 0] and rc = H2V_ERR_BAD_ARGUMENT
+//   -- the batch's read event: nothing behind it reads the batch
+//   k_accumulator_scale       G + 1 items
+//   k_accumulator_legs_fold   the journal slots (read from the feed's pinned block), then (L, R): the only write to the accumulator
+//   k_feed_report             the report into the feed's pinned block
+// No synchronise, no copy.  The host's half waits in a->feeds for settle_feeds.
+int h2v_accumulator_feed_batch(h2v_accumulator* a, h2v_batch* b) {
+    const char* who = "h2v_accumulator_feed_batch";
+    // every check comes before the first HIP call: a refusal leaves both objects untouched
+    if (!a || !b) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->stage < BatchStage::Launched) { set_last_error(std::string(who) + ": the batch has no launch (h2v_batch_launch)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->last.folded) { set_last_error(std::string(who) + ": a fold ran since the launch: the batch holds the folded records' sums, not its own"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->n_tail != b->n) { set_last_error(std::string(who) + ": the batch is a shard (a tail of draws longer than the upload)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->n && !b->mult_of_draws) { set_last_error(std::string(who) + ": the batch's multipliers are not those of its uploaded draws"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->plan && b->plan->host.opts.guard_terms) { set_last_error(std::string(who) + ": a guard-variant upload (h2v_guard_msm)"); return H2V_ERR_BAD_ARGUMENT; }
+    if (b->ctx->device != a->ctx->device) { set_last_error(std::string(who) + ": a batch on another device than the accumulator"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!same_srs(b->ctx->params, a->ctx->params)) { set_last_error(std::string(who) + ": a batch over other params than the accumulator (g[0], g2 or s_g2 differ)"); return H2V_ERR_BAD_ARGUMENT; }
+    const size_t G = b->groups, n = b->n;
+    if (!n) return 0;   // no verify_proof: no scale, no Guard, no entry, no report
+    if (G > 512) { set_last_error(std::string(who) + ": more than 512 groups"); return H2V_ERR_BAD_ARGUMENT; }
+    size_t legs_pending = 0;
+    for (const auto& f : a->feeds) legs_pending += f.slots.size();   // (a settled feed holds none)
+    if (a->j_cap && a->entries.size() + legs_pending + G > a->j_cap) {
+        set_last_error(std::string(who) + ": the journal has fewer free entries than the batch has groups (the legs of the feeds not settled yet counted)");
+        return H2V_ERR_UNSUPPORTED;
+    }
+    if (a->feeds.size() >= H2V_FEED_MAX_PENDING) { set_last_error(std::string(who) + ": H2V_FEED_MAX_PENDING feeds wait for h2v_accumulator_settle"); return H2V_ERR_UNSUPPORTED; }
+    H2V_HIP_CHECK(hipSetDevice(a->ctx->device));
+    int rc;
+    if (!a->ev_batch) H2V_HIP_CHECK(hipEventCreateWithFlags(&a->ev_batch, hipEventDisableTiming));
+    if (!b->ev_read) H2V_HIP_CHECK(hipEventCreateWithFlags(&b->ev_read, hipEventDisableTiming));
+    if ((rc = grow_under_feeds(a, a->l_pairs, 2 * (G + 1))) || (rc = grow_under_feeds(a, a->l_records, (size_t)H2V_ACC_RECORD_BYTES * (G + 1))) ||
+        (rc = grow_under_feeds(a, a->l_words, 8 * (G + 1) + 10 * G + 1))) return rc;
+    h2v_accumulator::Feed f;
+    const size_t block_bytes = 4 * (H2V_FEED_REPORT_WORDS(G) + G);
+    for (size_t i = 0; i < a->f_blocks.size() && !f.block; ++i)
+        if (a->f_blocks[i]->cap >= block_bytes) { f.block = std::move(a->f_blocks[i]); a->f_blocks.erase(a->f_blocks.begin() + i); }
+    if (!f.block) { f.block.reset(new MappedHostBuf); if ((rc = f.block->reserve(block_bytes))) return rc; }
+    f.n = (uint32_t)n; f.G = (uint32_t)G;
+    uint32_t* const h_report = reinterpret_cast<uint32_t*>(f.block->p);
+    uint32_t* const d_report = static_cast<uint32_t*>(f.block->dev);
+    h_report[0] = (uint32_t)H2V_ERR_DEVICE;   // (what settle finds if the report kernel never ran)
+    for (size_t g = 0; g < G && a->j_cap; ++g) h_report[H2V_FEED_REPORT_WORDS(G) + g] = a->free_slots[a->free_slots.size() - 1 - g];   // the lowest free slots, in group order
+    uint32_t* d_weights = a->l_words.p;
+    uint32_t* d_legs = d_weights + 8 * (G + 1);
+    uint32_t* d_sizes = d_legs + 8 * G;
+    uint32_t* d_failed = d_sizes + G;
+    uint32_t* d_rc = d_failed + G;
+    hipStream_t s = a->stream;
+    // the batch's stream: what h2v_batch_finish_device begins with, then the event this stream waits for
+    if ((rc = join_tail(b)) || (rc = ensure_whole(b))) return rc;
+    H2V_HIP_CHECK(hipEventRecord(a->ev_batch, b->stream));
+    H2V_HIP_CHECK(hipStreamWaitEvent(s, a->ev_batch, 0));
+    // everything that reads the batch, then the batch's read event
+    const GroupShape shape = group_shape_device(b);
+    if ((rc = feed_gather_enqueue(s, a->acc.p, b->acc.p, b->status, shape, a->l_pairs.p, d_sizes, d_failed)) ||
+        (rc = feed_weights_enqueue(s, shape, b->tail.p, b->mult.p, b->device_draws ? b->ingest_verdict.p : nullptr, d_weights, d_legs, d_rc))) return rc;
+    H2V_HIP_CHECK(hipEventRecord(b->ev_read, s));
+    b->read_pending = b->read_unseen = true;
+    if ((rc = accumulator_scale_many_enqueue(s, a->l_pairs.p, nullptr, d_weights, (uint32_t)(G + 1), a->l_records.p))) return rc;
+    // the commit: the journal's slots, then (L, R) <- M (L, R) + sum_g W_g S_g; the report behind it
+    if ((rc = accumulator_legs_fold_enqueue(s, a->l_records.p, (uint32_t)(G + 1), 0, a->l_pairs.p + 2, d_report + H2V_FEED_REPORT_WORDS(G), a->j_cap ? a->j_sums.p : nullptr, a->acc.p))) return rc;
+    // (from here on the accumulator changes: the feed is recorded whatever the last launch returns)
+    rc = feed_report_enqueue(s, d_rc, (uint32_t)n, (uint32_t)G, d_legs, d_sizes, d_failed, d_report);
+    for (size_t g = 0; g < G && a->j_cap; ++g) { f.slots.push_back(a->free_slots.back()); a->free_slots.pop_back(); }
+    a->feeds.push_back(std::move(f));
+    ++a->f_unsettled;
+    return rc;
+}
+
+int h2v_accumulator_pending(const h2v_accumulator* a, size_t* n_unsettled, size_t* n_unreported) {
+    if (!a) { set_last_error("h2v_accumulator_pending: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (n_unsettled) *n_unsettled = a->f_unsettled;
+    if (n_unreported) *n_unreported = a->feeds.size();
+    return 0;
+}
+
+int h2v_accumulator_settle(h2v_accumulator* a, size_t cap, size_t* n_feeds, int* feed_rc, size_t* feed_proofs, size_t* feed_failed) {
+    const char* who = "h2v_accumulator_settle";
+    if (!a || !n_feeds) { set_last_error(std::string(who) + ": null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    if (int rc = settle_feeds(a, who)) return rc;
+    const size_t F = a->feeds.size();
+    *n_feeds = F;
+    const bool wanted = feed_rc || feed_proofs || feed_failed;
+    if (!wanted && !cap) return 0;   // the count alone: the reports are kept
+    if (cap < F) { set_last_error(std::string(who) + ": the arrays are shorter than the feeds to report"); return H2V_ERR_BAD_ARGUMENT; }
+    for (size_t i = 0; i < F; ++i) {
+        h2v_accumulator::Feed& f = a->feeds[i];
+        if (feed_rc) feed_rc[i] = f.rc;
+        if (feed_proofs) feed_proofs[i] = f.n;
+        if (feed_failed) feed_failed[i] = f.failed;
+        a->f_blocks.push_back(std::move(f.block));
+    }
+    a->feeds.clear();
     return 0;
 }
 

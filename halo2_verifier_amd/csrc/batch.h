@@ -150,6 +150,19 @@ int multipliers_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d
 // d_weights <- [prod_g M_g, W_0 .. W_{G-1}], W_g = prod_{f > g} M_f, and d_legs <- [M_0 .. M_{G-1}], canonical 8-word scalars.
 // 1 <= shape.G <= 512: one workgroup.
 int leg_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const Fr* d_mult, uint32_t* d_weights, uint32_t* d_legs);
+// The kernels of an enqueued feed (h2v_accumulator_feed_batch, include/h2v_feed.h), all on the accumulator's stream.
+// feed_gather (k_feed_gather, a workgroup per group): d_pairs <- [d_acc[0], d_acc[1], d_sums[0 .. 2 G)], the accumulator's pair and the
+// batch's unscaled sums; d_sizes[g] <- shape.count(g), d_failed[g] <- the non-zero words among group g's d_status (off in device memory).
+int feed_gather_enqueue(hipStream_t s, const G1J* d_acc, const G1J* d_sums, const int* d_status, const GroupShape& shape, G1J* d_pairs, uint32_t* d_sizes, uint32_t* d_failed);
+// feed_weights (k_feed_weights): leg_weights_enqueue that fails closed on a draw the upload's kernel found >= r.  d_fault: the fault word
+// of k_ingest_draws' verdict block (null: the host has checked the draws).  No fault: k_leg_weights' outputs and d_rc[0] <- 0.  A fault:
+// d_weights <- [1, 0 .. 0] (the accumulator keeps its value, every leg is scaled away) and d_rc[0] <- H2V_ERR_BAD_ARGUMENT.
+int feed_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_fault, uint32_t* d_weights, uint32_t* d_legs,
+                         uint32_t* d_rc);
+// feed_report (k_feed_report), a feed's last kernel: the report [rc, n, G, failed][M_g x 8, size_g, failed_g] x G -> d_report, mapped
+// pinned memory, by plain stores behind a system-scope fence.  H2V_FEED_REPORT_WORDS(G) words.
+#define H2V_FEED_REPORT_WORDS(G) (4 + 10 * (size_t)(G))
+int feed_report_enqueue(hipStream_t s, const uint32_t* d_rc, uint32_t n, uint32_t G, const uint32_t* d_legs, const uint32_t* d_sizes, const uint32_t* d_failed, uint32_t* d_report);
 // out[i] = src[idx[i]]: the multipliers of a non-contiguous subset of a larger accumulation
 int gather_multipliers_enqueue(hipStream_t s, const Fr* d_src, const uint32_t* d_idx, uint32_t n, Fr* d_out);
 int frvm_enqueue(hipStream_t s, const FrvmArgs& a, uint32_t n_slots);
@@ -242,6 +255,12 @@ int guards_gather_terms_enqueue(hipStream_t s, const GuardsGather& g, uint32_t* 
 int guards_proofs_enqueue(hipStream_t s, const Fr* d_mult, const int* d_status, uint32_t first, uint32_t count, uint8_t* d_mult32, int* d_status_out);
 // the host waits for every stream the batch has (its own or the caller's, the auxiliary and the copy stream) -> the first error
 hipError_t wait_for_streams(h2v_batch* b);
+// What every enqueueing h2v_batch_* call begins with, and an enqueued feed of a resident accumulator as well (batch.hip): the batch's
+// stream exists; it waits for what the last launch left on the auxiliary stream and for a pending read event (h2v_batch::ev_read);
+// the whole accumulators are in `acc` if the last launch left pieces only
+int need_stream(h2v_batch* b);
+int join_tail(h2v_batch* b);
+int ensure_whole(h2v_batch* b);
 // The terms of a group's two MSM problems (left channel, right channel with the VK-wide bases) for `count` proofs; strided: the left
 // problem is one slot of every proof.  channel_problems builds its problems from these counts.
 struct ChannelTerms { bool strided; uint32_t left, right; };
@@ -303,6 +322,12 @@ struct h2v_batch {
     uint32_t null_rows = 0, launch_null_rows = 0;
     h2v::DevBuf<uint32_t> hint_misses, miss_list;
     h2v::LaunchRecord last;
+    // A resident accumulator's enqueued feed (h2v_accumulator_feed_batch, include/h2v_feed.h) reads acc, tail, mult, the status words,
+    // the group offsets and ingest_verdict on the ACCUMULATOR's stream, and records ev_read there behind the last of those reads.
+    // read_pending: the batch's stream has not waited for it yet (join_tail does, before anything new is enqueued); read_unseen: nor has
+    // the host (wait_for_streams does, and an upload that would free one of those arrays).  A batch that was never fed has no event.
+    hipEvent_t ev_read = nullptr;
+    bool read_pending = false, read_unseen = false;
     size_t max_proofs = 0, max_inst = 0;
     h2v::PlanDevice* plan = nullptr;  // set at upload (depends on the instance shape)
     uint32_t n = 0, n_tail = 0;

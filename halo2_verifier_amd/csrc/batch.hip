@@ -214,6 +214,8 @@ int close_enqueue(h2v_batch* b, bool with_pairing) {
 }
 // the main stream waits for what the last launch left on the auxiliary stream (before anything new reads or overwrites it)
 int join_tail(h2v_batch* b) {
+    // (a feed enqueued on an accumulator's stream may still read what the next call overwrites: h2v_accumulator_feed_batch)
+    if (b->read_pending) { b->read_pending = false; H2V_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_read, 0)); }
     if (!b->last.tail_on_aux) return 0;
     b->last.tail_on_aux = false;
     H2V_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_join, 0));
@@ -321,7 +323,19 @@ static void zero_below_of_draws(h2v_batch* b, const uint8_t* rand_tail) {
 // or (device_draws) the caller's draws in device memory, which the host cannot see and k_ingest_draws checks into the verdict block.
 static int upload_take(h2v_batch* b, PlanPin& pin, size_t n, size_t n_tail, const uint8_t* host_draws, bool device_draws) {
     int rc;
-    if ((rc = need_stream(b)) || (rc = join_tail(b)) || (rc = ensure_buffers(b, pin.pd->host))) return rc;
+    if ((rc = need_stream(b)) || (rc = join_tail(b))) return rc;
+    if (b->read_unseen) {
+        // an enqueued feed may still read acc, mult, the status words, tail and ingest_verdict on an accumulator's stream: the batch's
+        // stream waits for it on the device (join_tail), but an array that this upload would free is waited for by the host
+        const BatchSizes z = batch_sizes(pin.pd->host, b->max_proofs, b->groups, 1);
+        auto grows = [](const auto& buf, size_t count) { return !buf.p || count > buf.cap; };
+        if (grows(b->acc, z.acc) || grows(b->mult, z.mult) || grows(b->results, z.results) || grows(b->tail, 32 * n_tail) ||
+            (device_draws && grows(b->ingest_verdict, (size_t)b->groups + 2))) {
+            b->read_unseen = false;
+            H2V_HIP_CHECK(hipEventSynchronize(b->ev_read));
+        }
+    }
+    if ((rc = ensure_buffers(b, pin.pd->host))) return rc;
     if (b->plan) ctx_put_plan(b->ctx, b->plan);   // the batch holds its plan from upload to the next upload (or its destruction)
     b->plan = pin.take(); b->n = (uint32_t)n; b->n_tail = (uint32_t)n_tail;
     const size_t G = b->groups;
@@ -617,6 +631,8 @@ hipError_t wait_for_streams(h2v_batch* b) {
     if (b->stream || !b->owns_stream) wait(b->stream);   // (a caller's stream may be the null stream)
     if (b->aux) wait(b->aux);                             // (the tail of the last launch may still be running there)
     if (b->copy) wait(b->copy);                           // (the last upload's copies)
+    // (an accumulator's stream may still read the batch: an enqueued feed)
+    if (b->read_unseen) { b->read_unseen = false; const hipError_t e = hipEventSynchronize(b->ev_read); if (first == hipSuccess) first = e; }
     return first;
 }
 
@@ -791,6 +807,7 @@ void h2v_batch_destroy(h2v_batch* b) {
     if (b->copy) hipStreamDestroy(b->copy);
     if (b->ev_fork) hipEventDestroy(b->ev_fork);
     if (b->ev_join) hipEventDestroy(b->ev_join);
+    if (b->ev_read) hipEventDestroy(b->ev_read);
     if (b->stream && b->owns_stream) hipStreamDestroy(b->stream);
     delete b;   // (frees the buffers)
 }

@@ -296,6 +296,78 @@ int accumulator_legs_fold_enqueue(hipStream_t s, const void* d_recs, uint32_t n,
     return 0;
 }
 
+// ---- an enqueued feed of a batch's legs (h2v_accumulator_feed_batch, accumulator.hip; include/h2v_feed.h): the two kernels around
+// k_feed_weights (verify_kernels.hip), k_accumulator_scale and k_accumulator_legs_fold, on the accumulator's stream.
+//
+// k_feed_gather: everything the feed reads of the batch but its draws, into arrays of the accumulator's own, so that the batch is free
+// once this and k_feed_weights have run (no copy engine: k_copy_words' reason below).  Workgroup g: the words of the batch's sums
+// sums[2 g], [2 g + 1] -> pairs[2 + 2 g], [3 + 2 g] (workgroup 0 also acc[0], [1] -> pairs[0], [1]); sizes[g] <- the group's proofs,
+// failed[g] <- its non-zero status words (a strided count per thread, a butterfly per wave, the four waves' counts through LDS).
+// gfx950 (-Rpass-analysis=kernel-resource-usage): DESIGN.md section 3, "An enqueued feed".
+#define FEED_GATHER_THREADS 256u
+__global__ void __launch_bounds__(FEED_GATHER_THREADS) k_feed_gather(const G1J* __restrict__ acc, const G1J* __restrict__ sums, const int* __restrict__ status, GroupShape shape,
+                                                                     G1J* __restrict__ pairs, uint32_t* __restrict__ sizes, uint32_t* __restrict__ failed) {
+    __shared__ uint32_t wave_count[FEED_GATHER_THREADS / 64];
+    constexpr uint32_t PAIR_WORDS = 2 * sizeof(G1J) / 4;
+    const uint32_t g = blockIdx.x, t = threadIdx.x;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(sums + 2 * (size_t)g);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(pairs + 2 + 2 * (size_t)g);
+        for (uint32_t w = t; w < PAIR_WORDS; w += FEED_GATHER_THREADS) dst[w] = src[w];
+        if (g == 0) {
+            const uint32_t* a = reinterpret_cast<const uint32_t*>(acc);
+            uint32_t* d0 = reinterpret_cast<uint32_t*>(pairs);
+            for (uint32_t w = t; w < PAIR_WORDS; w += FEED_GATHER_THREADS) d0[w] = a[w];
+        }
+    }
+    const uint32_t first = shape.first(g), count = shape.count(g);
+    uint32_t c = 0;
+    for (uint32_t i = t; i < count; i += FEED_GATHER_THREADS) c += status[first + i] != 0 ? 1u : 0u;
+    for (uint32_t d = 32; d > 0; d >>= 1) c += (uint32_t)__shfl_down((int)c, d, 64);
+    if ((t & 63u) == 0) wave_count[t >> 6] = c;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < FEED_GATHER_THREADS / 64; ++w) all += wave_count[w];
+        sizes[g] = count; failed[g] = all;
+    }
+}
+int feed_gather_enqueue(hipStream_t s, const G1J* d_acc, const G1J* d_sums, const int* d_status, const GroupShape& shape, G1J* d_pairs, uint32_t* d_sizes, uint32_t* d_failed) {
+    if (!shape.G || !d_acc || !d_sums || !d_status || !d_pairs || !d_sizes || !d_failed) { set_last_error("feed_gather_enqueue: null argument or no group"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_feed_gather, dim3(shape.G), dim3(FEED_GATHER_THREADS), 0, s, d_acc, d_sums, d_status, shape, d_pairs, d_sizes, d_failed);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// k_feed_report, a feed's last kernel: the report into mapped pinned memory, [rc, n, G, failed] and per group [M_g x 8, size, failed],
+// from the accumulator's own scratch (legs: k_feed_weights; sizes, failed: k_feed_gather).  One workgroup, thread t the groups t,
+// t + 256, ..; the total of the failed counts meets in LDS.  Plain vector stores, a system-scope fence behind them (k_ingest_draws'
+// verdict block); the host reads the report behind a synchronise of the accumulator's stream (h2v_accumulator_settle).
+// gfx950 (-Rpass-analysis=kernel-resource-usage): DESIGN.md section 3, "An enqueued feed".
+__global__ void __launch_bounds__(256) k_feed_report(const uint32_t* __restrict__ rc, uint32_t n, uint32_t G, const uint32_t* __restrict__ legs,
+                                                     const uint32_t* __restrict__ sizes, const uint32_t* __restrict__ failed, uint32_t* __restrict__ report) {
+    __shared__ uint32_t total;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) total = 0;
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint32_t g = t; g < G; g += 256) {
+        uint32_t* row = report + 4 + 10 * (size_t)g;
+        for (uint32_t j = 0; j < 8; ++j) row[j] = legs[8 * (size_t)g + j];
+        row[8] = sizes[g]; row[9] = failed[g];
+        mine += failed[g];
+    }
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (t == 0) { report[0] = rc[0]; report[1] = n; report[2] = G; report[3] = total; }
+    __threadfence_system();
+}
+int feed_report_enqueue(hipStream_t s, const uint32_t* d_rc, uint32_t n, uint32_t G, const uint32_t* d_legs, const uint32_t* d_sizes, const uint32_t* d_failed, uint32_t* d_report) {
+    if (!G || !d_rc || !d_legs || !d_sizes || !d_failed || !d_report) { set_last_error("feed_report_enqueue: null argument or no group"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_feed_report, dim3(1), dim3(256), 0, s, d_rc, n, G, d_legs, d_sizes, d_failed, d_report);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ void k_affine_to_jacobian(const G1A* __restrict__ in, G1J* __restrict__ out, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = G1J::from_affine(in[i]);

@@ -685,6 +685,37 @@ __global__ void __launch_bounds__(LEG_WEIGHTS_MAX) k_leg_weights(const uint8_t* 
     }
     if (t == 0) fr_store_canonical(weights, part[0]);
 }
+// k_leg_weights for an enqueued feed (h2v_accumulator_feed_batch, include/h2v_feed.h), where no host has seen the upload's verdict: the
+// kernel reads the fault word of k_ingest_draws' verdict block itself (fault null: draws the host checked) and fails closed.  A draw
+// >= r (fault[0] != 0xffffffff): weights <- [1, 0 .. 0], so that the k_accumulator_scale launch behind it leaves (L, R) its value and
+// scales every leg away, and rc[0] <- H2V_ERR_BAD_ARGUMENT for the report; legs is written as ever (nobody commits it).  Otherwise
+// k_leg_weights' outputs, word for word, and rc[0] <- 0.  Same shape: one workgroup, one suffix scan in LDS (18 KB).
+// gfx950 (-Rpass-analysis=kernel-resource-usage): DESIGN.md section 3, "An enqueued feed".
+__global__ void __launch_bounds__(LEG_WEIGHTS_MAX) k_feed_weights(const uint8_t* __restrict__ tail, const Fr* __restrict__ mult, GroupShape shape,
+                                                                  const uint32_t* __restrict__ fault, uint32_t* __restrict__ weights, uint32_t* __restrict__ legs,
+                                                                  uint32_t* __restrict__ rc) {
+    __shared__ Fr part[LEG_WEIGHTS_MAX];
+    const uint32_t t = threadIdx.x, G = shape.G;
+    const bool bad = fault && fault[0] != 0xffffffffu;
+    Fr m = Fr::one();
+    if (t < G) {
+        const size_t first = shape.first(t);
+        Fr r;
+        Fr::from_bytes(tail + 32 * first, r);
+        m = r * mult[first];
+    }
+    part[t] = m;
+    fr_suffix_scan<LEG_WEIGHTS_MAX>(part, t);
+    if (t < G) {
+        const Fr w = t + 1 < LEG_WEIGHTS_MAX ? part[t + 1] : Fr::one();
+        fr_store_canonical(weights + 8 * (size_t)(t + 1), bad ? Fr::zero() : w);
+        fr_store_canonical(legs + 8 * (size_t)t, m);
+    }
+    if (t == 0) {
+        fr_store_canonical(weights, bad ? Fr::one() : part[0]);
+        rc[0] = bad ? (uint32_t)H2V_ERR_BAD_ARGUMENT : 0u;
+    }
+}
 
 // Instance evaluation for wide instance vectors (lib.rs:173-218; l_i_range, poly/domain.rs:187-212):
 //   E = sum_j a_j * l_{j-rot}(x),   l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
@@ -1015,6 +1046,14 @@ int leg_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d
     if (!shape.G || shape.G > LEG_WEIGHTS_MAX) { set_last_error("leg_weights_enqueue: the group count is not in 1 .. 512"); return H2V_ERR_BAD_ARGUMENT; }
     if (!d_tail || !d_mult || !d_weights || !d_legs) { set_last_error("leg_weights_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
     hipLaunchKernelGGL(k_leg_weights, dim3(1), dim3(LEG_WEIGHTS_MAX), 0, s, d_tail, d_mult, shape, d_weights, d_legs);
+    H2V_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int feed_weights_enqueue(hipStream_t s, const GroupShape& shape, const uint8_t* d_tail, const Fr* d_mult, const uint32_t* d_fault, uint32_t* d_weights, uint32_t* d_legs,
+                         uint32_t* d_rc) {
+    if (!shape.G || shape.G > LEG_WEIGHTS_MAX) { set_last_error("feed_weights_enqueue: the group count is not in 1 .. 512"); return H2V_ERR_BAD_ARGUMENT; }
+    if (!d_tail || !d_mult || !d_weights || !d_legs || !d_rc) { set_last_error("feed_weights_enqueue: null argument"); return H2V_ERR_BAD_ARGUMENT; }
+    hipLaunchKernelGGL(k_feed_weights, dim3(1), dim3(LEG_WEIGHTS_MAX), 0, s, d_tail, d_mult, shape, d_fault, d_weights, d_legs, d_rc);
     H2V_HIP_CHECK(hipGetLastError());
     return 0;
 }

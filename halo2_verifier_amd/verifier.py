@@ -15,6 +15,7 @@ import struct
 import sys
 
 from . import _lib
+from . import feed as _feed
 from ._lib import H2VError, check
 
 
@@ -716,6 +717,7 @@ class Accumulator:
 
     JOURNAL_MAX = 4096   # include/h2v.h H2V_ACC_JOURNAL_MAX
     _keep_inputs, _inputs = False, ()
+    _fed_groups, _feed_reports = (), ()
 
     def __init__(self, context: Context, journal=0, keep_inputs=False):
         if not isinstance(context, Context):
@@ -728,6 +730,8 @@ class Accumulator:
         self.last_all_ok = True
         self._keep_inputs = bool(keep_inputs)
         self._inputs = []   # with keep_inputs: one item per journal entry, None for the base and for add_msm entries
+        self._fed_groups = []     # the group counts of the feeds enqueued and not settled by this object yet (feed.py)
+        self._feed_reports = []   # (rc, n_proofs, n_failed) of the feeds settled on the way, for the next settle()
         if journal:
             self.journal_begin(journal)
 
@@ -758,6 +762,7 @@ class Accumulator:
         Returns the statuses of this call's proofs; `last_all_ok` says whether all are 0.  A call that raises H2VError leaves the
         accumulator as it was."""
         r = _Results(len(proofs))
+        _feed.collect(self)
         if hints is not None:
             contexts, keys, self.last_hint_stats = _hinted_keyed("h2v_accumulator_process_hinted", self._h, contexts, key_of_proof, proofs, instances, rand, hints,
                                                                  (r.st, ctypes.byref(r.ok)), bare_context=True)
@@ -777,6 +782,7 @@ class Accumulator:
         guards = list(guards)
         args = _guards_args(guards)
         rb = _rand_bytes(rand, args[0])
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_process_guards(self._h, *args, rb))
         if args[0] and self._inputs:   # (journal on: the call has appended an entry)
             self._inputs.append(("guards", guards) if self._keep_inputs else None)
@@ -796,16 +802,36 @@ class Accumulator:
         if not self._h or not batch._h:
             raise ValueError("the accumulator or the batch is closed")
         n, f = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_process_batch(self._h, batch._h, ctypes.byref(n), ctypes.byref(f)))
         self.last_all_ok = f.value == 0
         if n.value and self._inputs:   # (journal on: the call has appended an entry per group)
             self._inputs.extend([None] * batch.groups)
         return n.value, f.value
 
+    def feed(self, batch):
+        """process_batch ENQUEUED (h2v_accumulator_feed_batch, include/h2v_feed.h): the groups of the last launch of `batch` — launched
+        or finished — as legs of this accumulator, on the device, behind the launch.  Waits for nothing and returns nothing; the batch
+        may be uploaded again at once.  Counters, journal and reports follow at settle() (or at any other method, which settles
+        first).  At most feed.FEED_MAX_PENDING feeds between two settle() calls."""
+        _feed.feed(self, batch)
+
+    def settle(self):
+        """Wait for the enqueued feeds and commit them (h2v_accumulator_settle) -> [(rc, n_proofs, n_failed)] of every feed since the
+        last settle(), in feed order.  rc is 0, or H2V_ERR_BAD_ARGUMENT (-16) for a feed the device dropped: a draw >= r
+        in a tail uploaded from device memory; the points keep their value, no journal entry appears, and both counters grow by n."""
+        return _feed.settle(self)
+
+    @property
+    def pending(self):
+        """(feeds not settled yet, feeds whose report settle() has not handed out yet): host state only"""
+        return _feed.pending(self)
+
     def add_msm(self, left, right):
         """(L, R) += the two term lists evaluated, unscaled (h2v_accumulator_add_msm: AccumulatorStrategy::with on an empty accumulator,
         DualMSM::add_msm otherwise).  left / right: (scalars, bases) — scalars ints / 32-byte strings, bases 64-byte x | y."""
         l, r = _channel(left), _channel(right)
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_add_msm(self._h, *l, *r))
         if self._inputs:
             self._inputs.append(None)
@@ -820,6 +846,7 @@ class Accumulator:
                 raise TypeError("add_msms takes a DualMSM or a pair of MSMKZG objects (or None)")
         if not self._h:
             raise ValueError("the accumulator is closed")
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_add_msms(self._h, left._handle() if left is not None else None, right._handle() if right is not None else None))
         if self._inputs:
             self._inputs.append(None)
@@ -845,6 +872,7 @@ class Accumulator:
         it off.  Entry 0, the base, is the accumulator as it stands; on a journaled accumulator this is a checkpoint.  Retained inputs
         are forgotten.  The points and counters do not change."""
         capacity = self._capacity(capacity)
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_journal_begin(self._h, capacity))
         self._inputs = [None] if capacity else []
 
@@ -852,6 +880,7 @@ class Accumulator:
         """-> [(n_proofs, n_failed, pairing_ok)] per journal entry, the base first (h2v_accumulator_check_legs): pairing_ok is the
         pairing check of the entry's own sum, every entry's side by side in one launch.  [] with the journal off."""
         n = ctypes.c_size_t(0)
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_check_legs(self._h, 0, ctypes.byref(n), None, None, None))
         cap = n.value
         proofs, failed, ok = (ctypes.c_size_t * max(cap, 1))(), (ctypes.c_size_t * max(cap, 1))(), (ctypes.c_int * max(cap, 1))()
@@ -869,6 +898,7 @@ class Accumulator:
             raise ValueError("entry indices are positive: entry 0, the base, cannot be dropped")
         if len(set(indices)) != len(indices):
             raise ValueError("an entry index given twice")
+        _feed.collect(self)
         if self._inputs and any(e >= len(self._inputs) for e in indices):
             raise ValueError(f"the journal has {len(self._inputs)} entries")
         check(self._lib.h2v_accumulator_drop_legs(self._h, _sizes(indices), len(indices)))
@@ -926,6 +956,8 @@ class Accumulator:
         if any(not a._h for a in sources):
             raise ValueError("a source is closed")
         c, out = self._merge_draws(draws, len(sources), "sources")
+        for a in [self] + sources:
+            _feed.collect(a)
         handles = (ctypes.c_void_p * max(len(sources), 1))(*[a._h.value for a in sources])
         check(self._lib.h2v_accumulator_merge(self._h, handles, len(sources), c, out))
         return self._merged(len(sources), out)
@@ -943,6 +975,7 @@ class Accumulator:
         if any(not isinstance(st, (bytes, bytearray, memoryview)) or len(st) != self.STATE_BYTES for st in states):
             raise ValueError(f"every state is {self.STATE_BYTES} bytes")   # the C side reads n * STATE_BYTES bytes
         c, out = self._merge_draws(draws, len(states), "states")
+        _feed.collect(self)
         check(self._lib.h2v_accumulator_merge_states(self._h, b"".join(bytes(st) for st in states), len(states), c, out))
         return self._merged(len(states), out)
 

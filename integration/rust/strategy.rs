@@ -356,6 +356,26 @@ impl GpuResidentAccumulator {
         Ok((n, f))
     }
 
+    /// `process_batch` ENQUEUED (h2v_accumulator_feed_batch, feed.rs): `batch` is launched or finished; its groups become legs on the
+    /// device, behind its launch.  Waits for nothing; the batch may be uploaded again at once.  Counters, journal entries and the
+    /// feed's report follow at `settle` — or at any other call on this accumulator, which settles first.
+    pub fn feed_batch(&mut self, batch: &GpuStagedBatch) -> Result<(), Error> {
+        let rc = unsafe { super::feed::h2v_accumulator_feed_batch(self.acc, batch.b) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok(())
+    }
+    /// Waits for the enqueued feeds and commits them -> one report per feed since the last `settle`, in feed order.
+    pub fn settle(&mut self) -> Result<Vec<super::feed::FeedReport>, Error> {
+        unsafe { super::feed::settle_raw(self.acc) }.map_err(map_err)
+    }
+    /// (feeds not settled yet, feeds not reported yet): host state only
+    pub fn pending(&self) -> Result<(usize, usize), Error> {
+        let (mut u, mut r) = (0usize, 0usize);
+        let rc = unsafe { super::feed::h2v_accumulator_pending(self.acc, &mut u, &mut r) };
+        if rc != 0 { return Err(map_err(rc)); }
+        Ok((u, r))
+    }
+
     /// One `verify_proof(&params, vks[key], strategy, &[instances], &mut Blake2bRead::init(proof))` call per item, in order:
     /// `(key, proof, instances)`.  Returns the verdict of every proof of this call (`Ok(())` or the `Error` of its `verify_proof`).
     /// An `Err` of the call itself leaves the accumulator as it was.
